@@ -6,7 +6,11 @@ score_mode aggregation per window, detection state machine) over S synthetic 16 
 streams that are already resident in HBM.  One "scoring" = one (stream, 10 ms frame)
 step in steady state = one scored window.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config); --dump-outputs DIR also writes what the last timed step computed (dump_outputs).  --full adds everything
+else the benchmark measures, listed below.
 
 N > 1: one rank per GPU over torch.distributed (backend nccl == RCCL on ROCm); streams are sharded by
 rank (weak scaling: every GPU gets --streams streams), the only exchange is an RCCL all_gather of the
@@ -15,7 +19,7 @@ per-stream detection summary at the end of each step.  The ranks are either star
 WORLD_SIZE is not set, by bench.py itself: the parent starts that same command as a child process BEFORE
 anything touches the GPU, relays the child's output (rank 0 prints the one JSON line) and exits with its code.
 
-What the one JSON line carries besides the contract's fields (round 4):
+What the one JSON line of a --full run carries besides the contract's fields:
   roofline.frac      the largest of the dominant kernel's pipe fractions (executed work / pipe peak / measured time): VALU issue
                      cycles from the committed instruction mix of its hot loop (profiles/r04_*_isa_mix.json x
                      profiles/valu_rate_table.json), matrix flops, HBM bytes, LDS cycles -- each <= 1 by construction; the
@@ -96,6 +100,33 @@ def host_cpu():
     except Exception:
         pass
     return cores, model
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much
+
+
+def dump_outputs(env, arrays):
+    """--dump-outputs DIR: the arrays a caller of the timed path receives after its last step, as DIR/<name>.npy -- float32 arrays as they
+    are, integer arrays as float64 (exact for int32).  The arrays share their first axis (streams or rows); when together they hold more
+    than DUMP_BYTES, the same fixed, seeded sample of that axis is taken from each and its indices are written to DIR/sample_rows.npy."""
+    import numpy as np
+    torch, path = env.torch, env.args.dump_outputs
+    if not path or env.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    assert all(a.shape[0] == n for a in arrays.values()), "the dumped arrays must share their first axis"
+    per_row = sum(a[0].numel() * (4 if a.dtype == torch.float32 else 8) for a in arrays.values())
+    m = min(n, (DUMP_BYTES - (1 << 20)) // (per_row + 8))   # 1 MB left for the .npy headers; 8 B per row for sample_rows.npy
+    rows = None
+    if m < n:
+        rows = np.sort(np.random.default_rng(SEED).choice(n, m, replace=False))
+        np.save(os.path.join(path, "sample_rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        if rows is not None:
+            a = a.index_select(0, torch.as_tensor(rows, device=a.device))
+        h = a.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), h if h.dtype == np.float32 else h.astype(np.float64))
 
 
 def load_json(rel):
@@ -185,7 +216,14 @@ def main():
                     help="rp_ctx arithmetic of the DTW cost's cosine products (include/rustpotter_hip.h RP_ARITH_*): f32_matrix = the library default "
                          "(matrix cores, three bf16 parts per operand: f32-grade), strict_f32 = f32 vector FMAs only, fast_split = two f16 parts (22-bit)")
     ap.add_argument("--ragged-matrix", action="store_true", help="with --arith fast_split: references of unequal template lengths on dtw_ragged_kernel (RP_CTX_RAGGED_MATRIX)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline step: rooflines and per-kernel times, the strict-f32 / fast-split / "
+                    "i16 steps, the CPU baselines, the other BASELINE configs and shapes, the H2D-included sample (a plain run only sets up, warms up, "
+                    "times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB: a fixed, seeded sample of the streams when the arrays are larger; rank 0's streams)")
     args = ap.parse_args()
+    if args.dump_outputs and args.ingest:
+        ap.error("--dump-outputs: the --ingest measurement keeps no outputs of its own")
     args.total_streams = None
     if args.config == "C2":
         args.streams, args.templates = 1024, 8
@@ -610,9 +648,55 @@ def bench_dtw(env):
     dt = case.time_steps(args.warmup, args.steps, after_call=gather)
     scorings_per_step = (S * world if args.total_streams is None else args.total_streams) * n_win
     value = scorings_per_step * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(env, {**({"scores": case.scores, "aggregate": case.agg} if case.want_arrays else {}),
+                           "detection_fields": case.det[..., :4], "detection_scores": case.det.view(torch.float32)[..., 4:], "n_detections": case.n_det})
+    case.ctx.dtw_kernels()
+    products = list(case.ctx.last_dtw_products)   # the product arithmetic of the timed steps' matrix-core launches
+    work_skipped = args.detect_only or (args.avg_gate and not args.full_scores)
+
+    by_len = {}
+    for Lt in lens:
+        by_len[Lt] = by_len.get(Lt, 0) + 1
+    n_chunks = sum(-(-c // 8) for c in by_len.values())
+    tag = {(65536, 8): "C3", (8192, 64): "C4 (per-GPU share)", (1024, 8): "C2"}.get((S, T), "custom") if len(set(lens)) == 1 and lens[0] == 100 else "custom"
+    if args.total_streams is not None:
+        tag = "C4"
+    config = {"workload": "%s: %s synthetic 16 kHz f32 streams x %d templates%s (%g s streams, L=%s, K=%d, band 5, "
+                          "ScoreMode::%s, %s)" % (tag, ("%d" % S) if args.total_streams is None else ("%d" % args.total_streams), T,
+                                                  " per GPU" if args.total_streams is None else " split over %d rank(s) by stream" % world,
+                                                  N / 16000.0, lens[0] if len(set(lens)) == 1 else "/".join(map(str, lens)), K,
+                                                  args.score_mode.capitalize(),
+                                                  ("averaged template + avg_threshold %g%s, " % (args.avg_threshold, " (reference default)" if args.avg_threshold == 0.2 else "") +
+                                                   ("every window scored anyway" if args.full_scores else "gated windows skipped"))
+                                                  if args.avg_gate else ("avg gate off" + (", detect-only call: DTWs that cannot reach threshold 0.5 "
+                                                                                          "any more are abandoned" if args.detect_only else ""))),
+              "streams_per_gpu": S, "templates": T, "samples_per_stream": N, "frames_per_stream": nf,
+              "windows_per_stream": n_win, "template_chunks": n_chunks,
+              "parallelism": "streams sharded x%d, RCCL all_gather of the per-stream result block (T + 2 floats)" % world}
+    config.update(env.common_config())
+    if env.pg:
+        torch.cuda.synchronize()
+        g = [a.elapsed_time(b) for a, b in gather_ms[args.warmup:]]
+        rows, cols = gathered[0].shape[0], (gathered[0].shape[1] if gathered[0].dim() > 1 else 1)
+        config["gather_ms_per_step"] = {"mean": sum(g) / len(g), "max": max(g), "what": "per-stream result block (best score per template over the stream's "
+                                        "windows, best aggregate, detections: T + 2 floats) reduced from the score arrays and all_gathered, HIP events on the "
+                                        "launch stream around both (every step; the first %d are warm-up)" % args.warmup,
+                                        "gathered_shape": [rows, cols], "bytes_sent_per_gpu": int(rows // world * cols * 4), "bytes_total": int(rows * cols * 4)}
+        assert rows == (S * world if args.total_streams is None else args.total_streams), "the gather must return every stream of the job"
+    out = {
+        "metric": "10ms-frame MFCC+DTW scorings/sec", "value": value, "unit": "scorings/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak" if args.total_streams is None else "strong", "vs_baseline": None,
+        "dtype": DTYPE_DTW_FAST if "f16x2" in products else DTYPE_DTW, "data": "synthetic", "config": config,
+    }
+    if env.backend != "nccl" and world > 1:
+        out["oversubscribed"] = {"devices": torch.cuda.device_count(), "backend": env.backend,
+                                 "note": "ranks share GPUs: a launch-path dry run, not a scaling measurement"}
+    if not args.full:
+        return out
 
     # ---- rooflines, measured live with HIP events on the launch stream (rp_ctx_timing_*: one event pair per launch)
-    case.ctx.dtw_kernels()
     k_ms = case.kernel_times(max(2, min(args.steps, 5)))
     ran = case.ctx.dtw_kernels()   # the DTW kernel families those calls launched (rp_ctx_dtw_kernels)
     pmc, pmc_src = pmc_for(S, N, T, L, K, lens, args)
@@ -645,57 +729,17 @@ def bench_dtw(env):
     roofline["kernels_ms"] = {k: round(v[0], 4) for k, v in k_ms.items()}
     if k_ms["aggregate"][1] == 0:  # no launch of the aggregate pass: ScoreMode::Max ran inside the DTW kernel
         roofline["aggregate_inside_dtw_kernel"] = True
-    work_skipped = args.detect_only or (args.avg_gate and not args.full_scores)
     f_dtw_ref = sum(cells(Lt) * (2 * K + 7) + 2 * Lt * 2 * K + 2 * Lt * K for Lt in lens)
     roofline["path_hbm_frac"] = (value / world) * (640 + 4 * (T + 2)) / HBM_PEAK
     roofline["path_ref_flop_rate_vs_vector_peak"] = (value / world) * (13.2e3 * nf / n_win + f_dtw_ref) / VALU_PEAK
-
-    by_len = {}
-    for Lt in lens:
-        by_len[Lt] = by_len.get(Lt, 0) + 1
-    n_chunks = sum(-(-c // 8) for c in by_len.values())
-    tag = {(65536, 8): "C3", (8192, 64): "C4 (per-GPU share)", (1024, 8): "C2"}.get((S, T), "custom") if len(set(lens)) == 1 and lens[0] == 100 else "custom"
-    if args.total_streams is not None:
-        tag = "C4"
     mfma_kernel = "mfma" in r_dtw["kernel"] or "ragged" in r_dtw["kernel"]
-    config = {"workload": "%s: %s synthetic 16 kHz f32 streams x %d templates%s (%g s streams, L=%s, K=%d, band 5, "
-                          "ScoreMode::%s, %s)" % (tag, ("%d" % S) if args.total_streams is None else ("%d" % args.total_streams), T,
-                                                  " per GPU" if args.total_streams is None else " split over %d rank(s) by stream" % world,
-                                                  N / 16000.0, lens[0] if len(set(lens)) == 1 else "/".join(map(str, lens)), K,
-                                                  args.score_mode.capitalize(),
-                                                  ("averaged template + avg_threshold %g%s, " % (args.avg_threshold, " (reference default)" if args.avg_threshold == 0.2 else "") +
-                                                   ("every window scored anyway" if args.full_scores else "gated windows skipped"))
-                                                  if args.avg_gate else ("avg gate off" + (", detect-only call: DTWs that cannot reach threshold 0.5 "
-                                                                                          "any more are abandoned" if args.detect_only else ""))),
-              "streams_per_gpu": S, "templates": T, "samples_per_stream": N, "frames_per_stream": nf,
-              "windows_per_stream": n_win, "template_chunks": n_chunks,
-              "parallelism": "streams sharded x%d, RCCL all_gather of the per-stream result block (T + 2 floats)" % world}
-    config.update(env.common_config())
-    if env.pg:
-        torch.cuda.synchronize()
-        g = [a.elapsed_time(b) for a, b in gather_ms[args.warmup:]]
-        rows, cols = gathered[0].shape[0], (gathered[0].shape[1] if gathered[0].dim() > 1 else 1)
-        config["gather_ms_per_step"] = {"mean": sum(g) / len(g), "max": max(g), "what": "per-stream result block (best score per template over the stream's "
-                                        "windows, best aggregate, detections: T + 2 floats) reduced from the score arrays and all_gathered, HIP events on the "
-                                        "launch stream around both (every step; the first %d are warm-up)" % args.warmup,
-                                        "gathered_shape": [rows, cols], "bytes_sent_per_gpu": int(rows // world * cols * 4), "bytes_total": int(rows * cols * 4)}
-        assert rows == (S * world if args.total_streams is None else args.total_streams), "the gather must return every stream of the job"
-    out = {
-        "metric": "10ms-frame MFCC+DTW scorings/sec", "value": value, "unit": "scorings/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak" if args.total_streams is None else "strong", "vs_baseline": None,
-        "dtype": DTYPE_DTW_FAST if "f16x2" in products else DTYPE_DTW, "data": "synthetic", "config": config,
-        # work is skipped by design in detect-only / gated runs: pricing the full flop count against the shorter time would
-        # print a fraction above 1, so those lines carry the kernel times only
-        "roofline": roofline if not work_skipped else None,
-        "roofline_other": (r_mfcc if dom == "dtw" else r_dtw) if not work_skipped else None,
-    }
+    # work is skipped by design in detect-only / gated runs: pricing the full flop count against the shorter time would
+    # print a fraction above 1, so those lines carry the kernel times only
+    out["roofline"] = roofline if not work_skipped else None
+    out["roofline_other"] = (r_mfcc if dom == "dtw" else r_dtw) if not work_skipped else None
     if work_skipped:
         out["kernels_ms"] = roofline["kernels_ms"]
         out["note"] = "work is skipped by design in this mode (gated windows / abandoned DTWs): no roofline fraction is quoted"
-    if env.backend != "nccl" and world > 1:
-        out["oversubscribed"] = {"devices": torch.cuda.device_count(), "backend": env.backend,
-                                 "note": "ranks share GPUs: a launch-path dry run, not a scaling measurement"}
     pairs = case.ctx.dtw_ref_pairs()
     out["dtw_reference_cell_pairs"] = pairs   # windows whose frame norms left the scale-invariant range (rp_ctx_dtw_ref_pairs): 0 on this input
     if args.avg_gate:
@@ -1034,7 +1078,7 @@ def _timed(env, call, warmup, steps):
     return (time.perf_counter() - t0) / steps
 
 
-def model_detector_measure(env, S, m_type, warmup, steps):
+def model_detector_measure(env, S, m_type, warmup, steps, dump=False):
     """The wakeword-MODEL detector over whole streams (rp_batch_detect_model: MFCC of mfcc_size 16 -> every window of 195 frames through
     the model -> scores -> detection state machine), SURVEY 8a row a17 in the form the detector runs it."""
     import ctypes as C
@@ -1071,6 +1115,8 @@ def model_detector_measure(env, S, m_type, warmup, steps):
         call()
     env.fence()
     dt = env.max_over_ranks(time.perf_counter() - t0) / steps
+    if dump:
+        dump_outputs(env, {"detection_fields": det[..., :4], "detection_scores": det.view(torch.float32)[..., 4:], "detection_labels": lab, "n_detections": n_det})
     ctx.timing_enable(True)
     ctx.timing_reset()
     for _ in range(3):
@@ -1104,7 +1150,7 @@ def extra_model_detector(env, S=8192):
 def bench_model(env):
     args, world = env.args, env.world
     S = args.streams if args.streams else 8192
-    m = model_detector_measure(env, S, args.model_type, args.warmup, args.steps)
+    m = model_detector_measure(env, S, args.model_type, args.warmup, args.steps, dump=True)
     config = {"workload": "wakeword-model detector: %d synthetic 4 s streams per GPU, %s model %s on every window of 195 frames x 16 coefficients (%d windows per stream)"
                           % (S, args.model_type, "->".join(map(str, m["dims"])), m["n_win"])}
     config.update(env.common_config())
@@ -1156,6 +1202,7 @@ def bench_mlp(env):
     args, world = env.args, env.world
     case = MlpCase(env, args.streams, args.mlp_precision)
     dt, ms, n = case.measure(args.warmup, args.steps)
+    dump_outputs(env, {"logits": case.out})   # every call computes the same rows: the timing calls after the steps leave them as they were
     config = {"workload": "C5: %d rows x %d features, MLP %s" % (case.B, case.dims[0], "->".join(map(str, case.dims)))}
     config.update(env.common_config())
     res = {"metric": "wakeword-model rows/sec (BASELINE config C5)", "value": case.B * world * args.steps / dt, "unit": "rows/s",
@@ -1163,7 +1210,7 @@ def bench_mlp(env):
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": MLP_DTYPE[args.mlp_precision], "data": "synthetic",
            "config": config, "roofline": case.roofline(ms, n)}
     # ---- CPU baseline: the oracle's restatement of the reference forward (candle's Linear -> ReLU chain, f32) on this host's cores
-    if env.rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if env.rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = case.cpu_baseline(args.cpu_seconds)
     return res
 
@@ -1283,6 +1330,7 @@ def bench_stream(env):
         step()
     env.fence()
     dt = env.max_over_ranks(time.perf_counter() - t0)
+    dump_outputs(env, {"detection_fields": det[..., :4], "detection_scores": det.view(torch.float32)[..., 4:], "n_detections": n_det})
     ctx.timing_enable(True)
     ctx.timing_reset()
     for _ in range(5):
@@ -1331,6 +1379,7 @@ def bench_resample(env):
         step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    dump_outputs(env, {"pcm_16k": out})
     ctx.timing_enable(True)
     ctx.timing_reset()
     for _ in range(3):

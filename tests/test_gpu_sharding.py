@@ -206,7 +206,7 @@ def test_bench_starts_its_own_ranks():
     else:
         env.pop("RP_BENCH_OVERSUBSCRIBE", None)  # two or more: one rank per GPU over RCCL, exactly the driver's run
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--streams", "2048", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

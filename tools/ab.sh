@@ -33,7 +33,7 @@ for rep in $(seq 1 $REPS); do
   for flags in "$@"; do
     wi=0
     for w in "${WORK[@]}"; do
-      RP_LIB_PATH=$PWD/rustpotter_amd/variants/lib_$i.so timeout 900 python3 bench.py --no-cpu-baseline --no-extras $w 2> $O/v${i}_w${wi}_$rep.err | grep '^{' | tail -1 > $O/v${i}_w${wi}_$rep.json
+      RP_LIB_PATH=$PWD/rustpotter_amd/variants/lib_$i.so timeout 900 python3 bench.py --no-cpu-baseline --no-extras --full $w 2> $O/v${i}_w${wi}_$rep.err | grep '^{' | tail -1 > $O/v${i}_w${wi}_$rep.json
       python3 - <<PY
 import json
 try:

@@ -96,7 +96,7 @@ c5)
     done
     cut -c1-300 $O/c5_$P.json ;;
 round)
-    HEAD="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+    HEAD="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --full"
     bash tools/prof.sh stats final $HEAD > gpurun_out/final_prof.txt 2>&1
     bash tools/prof.sh pmcset final bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > gpurun_out/final_pmc.txt 2>&1
     bash tools/prof.sh c5 bf16 > gpurun_out/final_c5_bf16.txt 2>&1
@@ -105,7 +105,7 @@ round)
     tail -45 gpurun_out/final_benches.txt ;;
 rounds)
     for s in ${@:-166 331 662 993 1024 1324 2048 4096}; do
-        python3 bench.py --streams $s --steps 50 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+        python3 bench.py --streams $s --steps 50 --warmup 5 --no-cpu-baseline --no-extras --full 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=j['roofline']['kernels_ms']
 tiles=$s*297/32.0

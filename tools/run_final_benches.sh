@@ -7,13 +7,13 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out/final
 O=gpurun_out/final
-B="python3 bench.py --steps 10 --warmup 3 --no-extras"
+B="python3 bench.py --steps 10 --warmup 3 --no-extras --full"
 line() { grep '^{' | tail -1; }
-python3 bench.py --steps 10 --warmup 3 2>/dev/null | line > $O/bench_default.json
+python3 bench.py --steps 10 --warmup 3 --full 2>/dev/null | line > $O/bench_default.json
 $B --no-cpu-baseline --config C2 --steps 50 2>/dev/null | line > $O/c2.json
 $B --no-cpu-baseline --streams 8192 --templates 64 2>/dev/null | line > $O/c4.json
-python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --config C4 2>/dev/null | line > $O/c4_one_gpu.json
-RP_BENCH_OVERSUBSCRIBE=1 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --config C4 --gpus 2 2>/dev/null | line > $O/c4_two_ranks_one_gpu.json
+python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --full --config C4 2>/dev/null | line > $O/c4_one_gpu.json
+RP_BENCH_OVERSUBSCRIBE=1 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --full --config C4 --gpus 2 2>/dev/null | line > $O/c4_two_ranks_one_gpu.json
 # the same shapes in the opt-in two-part f16 arithmetic (RP_ARITH_FAST_SPLIT: 22-bit products, narrower than the reference) and in strict f32
 $B --no-cpu-baseline --arith fast_split 2>/dev/null | line > $O/c3_fast_split.json
 $B --no-cpu-baseline --arith strict_f32 2>/dev/null | line > $O/c3_strict_f32.json
