@@ -447,16 +447,11 @@ int rp_dtw_score_batch(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames
         float *da = do_avg ? static_cast<float *>(sg.out(avg, rows * sizeof(float), c->stage_out2)) : nullptr;
         float *dg = agg ? static_cast<float *>(sg.out(agg, rows * sizeof(float), c->stage_out3)) : nullptr;
         if (rows && (!dm || !ds)) return -1;
-        c->time_begin(kKernelDtw);
-        bool ok = hip_ok(launch_dtw(c->stream, c->dtw_work_for(S, rows * (size_t)(td.rag_count > 1 ? td.rag_count : 1)), td, dm, S, n_frames, 0, n_win, n_win, band_size, score_ref, do_avg ? 1 : 0, ds, da), "dtw kernel");
-        c->time_end();
-        if (!ok) return -1;
-        if (dg) {
-            c->time_begin(kKernelAggregate);
-            ok = hip_ok(launch_aggregate(c->stream, ds, rows, td.T, (int)score_mode, dg), "aggregate_kernel");
-            c->time_end();
-            if (!ok) return -1;
-        }
+        DtwScore q;
+        q.t = &td; q.mfcc = dm; q.S = S; q.frame_pitch = n_frames; q.n_win = n_win; q.band = band_size; q.score_ref = score_ref;
+        q.with_avg = do_avg; q.score_mode = (int)score_mode; q.scores = ds; q.avg = da; q.agg = dg;
+        q.ragged = true; q.padded_rows = false;
+        if (!dtw_score(*c, q)) return -1;
         if (!sg.back(scores, ds, rows * td.T * sizeof(float)) || (do_avg && !sg.back(avg, da, rows * sizeof(float))) ||
             (dg && !sg.back(agg, dg, rows * sizeof(float))) || !sg.finish())
             return -1;
@@ -552,16 +547,6 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
         // caller-provided score arrays are used directly when they are device pointers
         float *ds = (scores && !sg.host) ? scores : nullptr, *dg = (agg && !sg.host) ? agg : nullptr;
         if (!c->ws_mfcc.reserve(S * nf * td.K * sizeof(float) + 64 * td.K * sizeof(float))) return -1;  // slack: the list kernel's band reads past a row
-        // The averaged-template gate as the reference runs it (wakeword_comp.rs:85-93): a window whose avg_score is below
-        // avg_threshold is never compared with the sample templates.  Taken when the caller did not ask for the
-        // per-window score arrays (those are defined for every window) and RP_CTX_FULL_SCORES is not set.
-        const bool detect_only = !scores && !agg && !(c->flags & RP_CTX_FULL_SCORES);
-        const bool gated = do_avg && detect_only && dtw_gate_supported(td, config->band_size, rows);
-        // template sets only the generic kernel serves: the same gate at wave granularity (launch_dtw_generic_gated)
-        const bool gated_generic = do_avg && detect_only && !gated && rows > 0 && dtw_uses_generic(td, config->band_size, S, n_win);
-        // detect-only calls in ScoreMode::Max may also stop DTWs that can no longer reach `threshold` (rp_kernels.h, launch_dtw)
-        const float abandon = (detect_only && config->score_mode == RP_SCORE_MAX) ? dtw_abandon_nc(config->threshold, config->score_ref) : __builtin_inff();
-        if (gated && !c->ws_list.reserve((rows + 1) * sizeof(uint32_t) + 16)) return -1;
         if (!ds) { if (!c->ws_scores.reserve(rows * td.T * sizeof(float) + 16)) return -1; ds = c->ws_scores.as<float>(); }
         if (!dg) { if (!c->ws_agg.reserve(rows * sizeof(float) + 16)) return -1; dg = c->ws_agg.as<float>(); }
         float *da = nullptr;
@@ -572,40 +557,20 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
         bool ok = hip_ok(launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, nf, nf, dm), "mfcc_kernel");
         c->time_end();
         if (!ok) return -1;
-        // the aggregate pass also tells the scan which streams can fire at all (a flag per stream, zeroed here) and writes 0 for the
-        // windows the averaged-template gate rejected (their `scores` rows were never written)
-        AggExtra ax;
-        if (n_win) {
-            ax.hot = c->hot_flags(S);   // zero: the scan below puts every flag it reads back (no memset per call)
-            if (!ax.hot) return -1;
-            ax.threshold = config->threshold; ax.n_win = n_win;
-            if (gated || gated_generic) { ax.gate_avg = da; ax.gate_threshold = config->avg_threshold; }  // only rows the gate really skipped
+        // ws_mfcc ends with slack (padded rows): short streams (fewer than 64 windows each) are scored by cross-stream waves like
+        // live-stream batches.  The averaged-template gate is taken when the caller did not ask for the per-window score arrays (those
+        // are defined for every window) and RP_CTX_FULL_SCORES is not set.
+        DtwScore q;
+        q.t = &td; q.mfcc = dm; q.S = S; q.frame_pitch = nf; q.n_win = n_win; q.band = config->band_size; q.score_ref = config->score_ref;
+        q.with_avg = do_avg; q.detect_only = !scores && !agg && !(c->flags & RP_CTX_FULL_SCORES);
+        q.avg_threshold = config->avg_threshold; q.threshold = config->threshold; q.score_mode = (int)config->score_mode;
+        q.scores = ds; q.avg = da; q.agg = dg;
+        q.gate_generic = true; q.fuse_max = true; q.ragged = true;
+        if (n_win) {   // the aggregate pass also tells the scan which streams can fire at all (a flag per stream)
+            q.hot = c->hot_flags(S);   // zero: the scan below puts every flag it reads back (no memset per call)
+            if (!q.hot) return -1;
         }
-        // ScoreMode::Max of a reference whose templates are one chunk of the matrix-core kernel, no averaged template scored: the DTW
-        // kernel writes the aggregate and the flags itself (DtwFusedAgg, rp_kernels.h) and the aggregate pass is skipped
-        DtwFusedAgg fz;
-        if (config->score_mode == RP_SCORE_MAX && !do_avg && n_win) { fz.agg = dg; fz.hot = ax.hot; fz.threshold = config->threshold; }
-        c->time_begin(kKernelDtw);
-        if (gated) {
-            uint32_t *lst = c->ws_list.as<uint32_t>();
-            ok = hip_ok(launch_dtw_gated(c->stream, c->dtw_work(), td, dm, S, nf, 0, n_win, config->band_size, config->score_ref, config->avg_threshold,
-                                         ds, da, lst + 1, lst, true, abandon), "dtw kernels (gated)");
-        } else if (gated_generic) {
-            ok = hip_ok(launch_dtw_generic_gated(c->stream, c->dtw_work(), td, dm, S, nf, 0, n_win, n_win, config->band_size, config->score_ref,
-                                                 config->avg_threshold, ds, da), "dtw_generic_kernel (gated)");
-        } else {
-            // ws_mfcc ends with slack: short streams (fewer than 64 windows each) are scored by cross-stream waves like live-stream batches
-            ok = hip_ok(launch_dtw(c->stream, c->dtw_work_for(S, rows * (size_t)(td.rag_count > 1 ? td.rag_count : 1)), td, dm, S, nf, 0, n_win, n_win, config->band_size, config->score_ref, do_avg ? 1 : 0, ds, da, true, abandon,
-                                   fz.agg ? &fz : nullptr), "dtw kernel");
-        }
-        c->time_end();
-        if (!ok) return -1;
-        if (!fz.done) {
-            c->time_begin(kKernelAggregate);
-            ok = hip_ok(launch_aggregate(c->stream, ds, rows, td.T, (int)config->score_mode, dg, ax), "aggregate_kernel");
-            c->time_end();
-        }
-        if (!ok) return -1;
+        if (!dtw_score(*c, q)) return -1;
         ScanConfig sc;
         sc.threshold = config->threshold; sc.avg_threshold = config->avg_threshold; sc.min_scores = (int)config->min_scores;
         sc.eager = config->eager ? 1 : 0; sc.max_len = td.max_len; sc.avg_enabled = do_avg ? 1 : 0;
@@ -617,7 +582,7 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
             if (!hip_ok(launch_vad_value(c->stream, dm, S * nf, td.K, dv), "vad_value_kernel")) return -1;
         }
         c->time_begin(kKernelScan);
-        ok = hip_ok(launch_scan(c->stream, dg, da, dv, vad_mode_value(config->vad_mode), S, nf, sc, dd, dn, max_det, ax.hot), "scan_kernel");
+        ok = hip_ok(launch_scan(c->stream, dg, da, dv, vad_mode_value(config->vad_mode), S, nf, sc, dd, dn, max_det, q.hot), "scan_kernel");
         c->time_end();
         if (!ok) return -1;
         if (gather.on) {
@@ -820,27 +785,12 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
             const bool do_avg = td.has_avg && athr != 0.f;  // wakeword_comp.rs:85
             float *dg = c->ws_agg.as<float>() + j * rows, *da = do_avg ? c->ws_avg.as<float>() + j * rows : nullptr;
             if (n_win) {
-                // windows below the wakeword's avg_threshold are not compared with its sample templates (wakeword_comp.rs:85-93)
-                const bool detect_only = !(c->flags & RP_CTX_FULL_SCORES);  // this entry point has no per-window outputs
-                const bool gated = do_avg && detect_only && dtw_gate_supported(td, config->band_size, rows);
-                const float abandon = (detect_only && config->score_mode == RP_SCORE_MAX) ? dtw_abandon_nc(thr, config->score_ref) : __builtin_inff();
-                if (gated && !c->ws_list.reserve((rows + 1) * sizeof(uint32_t) + 16)) return -1;
-                c->time_begin(kKernelDtw);
-                if (gated) {
-                    uint32_t *lst = c->ws_list.as<uint32_t>();
-                    ok = hip_ok(launch_dtw_gated(c->stream, c->dtw_work(), td, dm, S, nf, 0, n_win, config->band_size, config->score_ref, athr, ds, da, lst + 1, lst,
-                                                 true, abandon), "dtw kernels (gated)");
-                } else {
-                    ok = hip_ok(launch_dtw(c->stream, c->dtw_work(), td, dm, S, nf, 0, n_win, n_win, config->band_size, config->score_ref, do_avg ? 1 : 0, ds, da, true, abandon), "dtw kernel");
-                }
-                c->time_end();
-                if (!ok) return -1;
-                AggExtra ax;   // windows the gate rejected were never scored: their aggregate is 0, not what `scores` held
-                if (gated) { ax.gate_avg = da; ax.gate_threshold = athr; }
-                c->time_begin(kKernelAggregate);
-                ok = hip_ok(launch_aggregate(c->stream, ds, rows, td.T, (int)config->score_mode, dg, ax), "aggregate_kernel");
-                c->time_end();
-                if (!ok) return -1;
+                DtwScore q;
+                q.t = &td; q.mfcc = dm; q.S = S; q.frame_pitch = nf; q.n_win = n_win; q.band = config->band_size; q.score_ref = config->score_ref;
+                q.with_avg = do_avg; q.detect_only = !(c->flags & RP_CTX_FULL_SCORES);   // this entry point has no per-window outputs
+                q.avg_threshold = athr; q.threshold = thr; q.score_mode = (int)config->score_mode;
+                q.scores = ds; q.avg = da; q.agg = dg;
+                if (!dtw_score(*c, q)) return -1;
             }
             ww.agg[j] = dg; ww.avg[j] = da; ww.threshold[j] = thr; ww.avg_threshold[j] = athr;
         }
@@ -1128,34 +1078,16 @@ static int stream_batch_process_impl(rp_stream_batch *b, const void *pcm, rp_sam
             return sg.finish() ? 0 : -1;
         }
         float *ds = b->scores.as<float>(), *dg = b->agg.as<float>(), *da = do_avg ? b->avg.as<float>() : nullptr;
-        // the averaged-template gate as a skip (wakeword_comp.rs:85-93), unless the caller wants every window's aggregate
-        const bool detect_only = !agg && !(c->flags & RP_CTX_FULL_SCORES);
-        // (a single live stream with a handful of windows skips the gate's three passes: launch_dtw scores it -- with the batch kernels when
-        // the matrix-core kernel serves its templates (a stream's bits must not depend on the batch it is in), else one wave per DTW)
-        const bool gated = do_avg && detect_only && dtw_gate_supported(td_one, b->cfg.band_size, rows) && !(S == 1 && n_new <= 8);
-        const float abandon = (detect_only && b->cfg.score_mode == RP_SCORE_MAX) ? dtw_abandon_nc(b->cfg.threshold, b->cfg.score_ref) : __builtin_inff();
-        // ScoreMode::Max inside the matrix-core DTW kernel when one chunk holds the reference's templates (DtwFusedAgg, rp_kernels.h)
-        DtwFusedAgg fz;
-        if (b->cfg.score_mode == RP_SCORE_MAX && !do_avg && rows) { fz.agg = dg; fz.threshold = b->cfg.threshold; }
-        c->time_begin(kKernelDtw);
-        if (gated) {
-            uint32_t *lst = b->list.as<uint32_t>();
-            ok = hip_ok(launch_dtw_gated(c->stream, c->dtw_work(), td_one, now, S, pitch, fill - hist, n_new, b->cfg.band_size, b->cfg.score_ref, b->cfg.avg_threshold,
-                                         ds, da, lst + 1, lst, true, abandon), "dtw kernels (gated)");
-        } else {
-            ok = hip_ok(launch_dtw(c->stream, c->dtw_work(), td_one, now, S, pitch, fill - hist, n_new, n_new, b->cfg.band_size, b->cfg.score_ref, do_avg ? 1 : 0, ds, da, true, abandon,
-                                   fz.agg ? &fz : nullptr), "dtw kernel");
-        }
-        c->time_end();
-        if (!ok) return -1;
-        AggExtra ax;   // windows the gate rejected were never scored: their aggregate is 0, not what `scores` held
-        if (gated) { ax.gate_avg = da; ax.gate_threshold = b->cfg.avg_threshold; }
-        if (!fz.done) {
-            c->time_begin(kKernelAggregate);
-            ok = hip_ok(launch_aggregate(c->stream, ds, rows, td.T, (int)b->cfg.score_mode, dg, ax), "aggregate_kernel");
-            c->time_end();
-        }
-        if (!ok) return -1;
+        DtwScore q;
+        q.t = &td_one; q.mfcc = now; q.S = S; q.frame_pitch = pitch; q.first_win = fill - hist; q.n_win = n_new; q.band = b->cfg.band_size;
+        q.score_ref = b->cfg.score_ref; q.with_avg = do_avg;
+        q.detect_only = !agg && !(c->flags & RP_CTX_FULL_SCORES);   // unless the caller wants every window's aggregate
+        q.avg_threshold = b->cfg.avg_threshold; q.threshold = b->cfg.threshold; q.score_mode = (int)b->cfg.score_mode;
+        q.scores = ds; q.avg = da; q.agg = dg; q.gate_list = b->list.as<uint32_t>();
+        // (a single live stream with a handful of windows skips the gate's three passes: the batch kernels score it when the matrix-core
+        // kernel serves its templates (a stream's bits must not depend on the batch it is in), else one wave per DTW)
+        q.gate_one_stream = false; q.fuse_max = true;
+        if (!dtw_score(*c, q)) return -1;
         float *dv = nullptr;
         if (b->cfg.vad_mode != RP_VAD_NONE) {
             dv = b->vad.as<float>();
@@ -1254,24 +1186,12 @@ static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float 
             const bool do_avg = td.has_avg && w.avg_threshold != 0.f;  // wakeword_comp.rs:85
             float *da = do_avg ? w.avg.as<float>() : nullptr, *ds = b->scores.as<float>();
             // the window starts where the longest wakeword's does and this one scores its oldest frames (wakeword_comp.rs:22-27)
-            const bool gated = do_avg && detect_only && dtw_gate_supported(td, b->cfg.band_size, rows);
-            const float abandon = (detect_only && b->cfg.score_mode == RP_SCORE_MAX) ? dtw_abandon_nc(w.threshold, b->cfg.score_ref) : __builtin_inff();
-            c->time_begin(kKernelDtw);
-            if (gated) {
-                uint32_t *lst = b->list.as<uint32_t>();
-                ok = hip_ok(launch_dtw_gated(c->stream, c->dtw_work(), td, now, S, pitch, fill - hist, n_new, b->cfg.band_size, b->cfg.score_ref, w.avg_threshold,
-                                             ds, da, lst + 1, lst, true, abandon), "dtw kernels (gated)");
-            } else {
-                ok = hip_ok(launch_dtw(c->stream, c->dtw_work(), td, now, S, pitch, fill - hist, n_new, n_new, b->cfg.band_size, b->cfg.score_ref, do_avg ? 1 : 0, ds, da, true, abandon), "dtw kernel");
-            }
-            c->time_end();
-            if (!ok) return -1;
-            AggExtra ax;
-            if (gated) { ax.gate_avg = da; ax.gate_threshold = w.avg_threshold; }
-            c->time_begin(kKernelAggregate);
-            ok = hip_ok(launch_aggregate(c->stream, ds, rows, td.T, (int)b->cfg.score_mode, dg, ax), "aggregate_kernel");
-            c->time_end();
-            if (!ok) return -1;
+            DtwScore q;
+            q.t = &td; q.mfcc = now; q.S = S; q.frame_pitch = pitch; q.first_win = fill - hist; q.n_win = n_new; q.band = b->cfg.band_size;
+            q.score_ref = b->cfg.score_ref; q.with_avg = do_avg; q.detect_only = detect_only;
+            q.avg_threshold = w.avg_threshold; q.threshold = w.threshold; q.score_mode = (int)b->cfg.score_mode;
+            q.scores = ds; q.avg = da; q.agg = dg; q.gate_list = b->list.as<uint32_t>();
+            if (!dtw_score(*c, q)) return -1;
             sw.agg[j] = dg; sw.avg[j] = da; sw.threshold[j] = w.threshold; sw.avg_threshold[j] = w.avg_threshold; sw.label[j] = nullptr;
         } else {
             const Model &m = *w.m;

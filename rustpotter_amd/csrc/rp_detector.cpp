@@ -451,9 +451,12 @@ int Rustpotter::process_audio(float *buf, size_t n, Detection *out) {
                     if (e != hipErrorNotSupported) { hip_ok(e, "dtw kernel"); return -1; }
                     (void)hipGetLastError();
                 }
-                if (!hip_ok(launch_dtw(st, ctx_->dtw_work(), w.tmpl->dev, hist, 1, frames_valid, first_win, cnt, cnt, det_.band_size, det_.score_ref,
-                                       w.with_avg ? 1 : 0, res + w.off_scores, res + w.off_avg), "dtw kernel")) return -1;
-                if (!hip_ok(launch_aggregate(st, res + w.off_scores, cnt, T, (int)det_.score_mode, res + w.off_agg), "aggregate_kernel")) return -1;
+                DtwScore q;
+                q.t = &w.tmpl->dev; q.mfcc = hist; q.S = 1; q.frame_pitch = frames_valid; q.first_win = first_win; q.n_win = cnt;
+                q.band = det_.band_size; q.score_ref = det_.score_ref; q.with_avg = w.with_avg; q.score_mode = (int)det_.score_mode;
+                q.scores = res + w.off_scores; q.avg = res + w.off_avg; q.agg = res + w.off_agg;
+                q.padded_rows = false; q.timed = false;
+                if (!dtw_score(*ctx_, q)) return -1;
             } else {
                 const int L = (int)w.model.train_size;
                 w.shape_ok = (size_t)L * K == (size_t)w.dims[0] && first_win + cnt - 1 + L <= frames_valid;

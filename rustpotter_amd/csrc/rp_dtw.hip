@@ -2,6 +2,7 @@
 // (src/mfcc/dtw.rs:56-105 + comparator.rs + normalizer.rs + wakeword_comp.rs:22-27; one lane per window, band and ring
 // in registers) and aggregate_kernel (src/wakewords/comp/wakeword_comp.rs:38-49,108-139).  DESIGN.md §4.2.
 #include "rp_device.h"
+#include "rp_host.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -1008,16 +1009,6 @@ static hipError_t launch_dtw_wide_all(hipStream_t st, const TemplatesDev &t, int
     return launch_dtw_wide<K, W, 2>(st, t, 0, t.class_count[0], mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
 }
 
-// dispatch on the (mfcc_size, band) pairs the wide kernels are built for
-#define RP_WIDE_DISPATCH(CALL)                                                                 \
-    do {                                                                                       \
-        if (t.K == 16) {                                                                       \
-            switch (band) { case 3: return CALL(16, 3); case 4: return CALL(16, 4); case 5: return CALL(16, 5); default: return CALL(16, 6); } \
-        } else {                                                                               \
-            switch (band) { case 3: return CALL(13, 3); case 4: return CALL(13, 4); case 5: return CALL(13, 5); default: return CALL(13, 6); } \
-        }                                                                                      \
-    } while (0)
-
 // Largest template tile the register kernels are built for at this (mfcc_size, band) (0 = only the generic
 // kernel applies).  Built: mfcc_size 5 with band 3..6 (tile 8), mfcc_size 13 and 16 with band 3..6 (tile 2).
 // ---- one DTW per wave, for a handful of windows (the single-stream API: three new windows per 30 ms chunk) -----
@@ -1245,23 +1236,95 @@ __global__ __launch_bounds__(256) void gate_compact_kernel(const float *__restri
     }
 }
 
-bool dtw_gate_supported(const TemplatesDev &t, int band, size_t rows) {
-    return t.has_avg && !t.ref_only && dtw_register_tile(t.K, band) > 0 && t.max_diff == 0 && t.chunks && rows > 0 && rows < 0xffffffffULL &&
-           (size_t)(2 * kDtwWin + 2 * (t.max_len + 8)) * (size_t)(t.K | 1) * sizeof(float) <= 160 * 1024;
+// ---- the route: which kernels score a call ---------------------------------------------------------------------------
+// Decided here once per call, from the template set, the band, the call's shape and whether the averaged template is scored; every
+// launcher below reads it.  The callers describe the call (DtwScore, rp_kernels.h) and never pick kernels themselves.
+enum DtwGate { kGateNone, kGateRegister, kGateGeneric };
+struct DtwRoute {
+    // one stream alone is scored like a batch when the matrix-core kernel serves its templates (a stream's bits must not depend on the
+    // batch it is scored in, live or offline -- only callers without padded rows, the single-stream mirror, keep dtw_single_kernel)
+    bool mfma_batch = false;
+    // many streams with few windows each (streaming batches): cross-stream waves reading frames from global memory (needs padded rows:
+    // slack after the last stream's frames for the never-used out-of-band columns)
+    bool few = false;
+    // dtw_single_kernel, one wave per DTW for a handful of windows of one stream: its LDS, whether it takes the set, whether it scores the call
+    size_t single_lds = 0;
+    bool single_fits = false, single = false;
+    // the register kernels (mfcc_size 5: launch_dtw_k5, 13 / 16: launch_dtw_wide_all) score the sample templates; else, unless the set is
+    // ref-only (dtw_ref_kernel scores every window), dtw_generic_kernel with generic_lds bytes of LDS
+    bool reg = false;
+    size_t generic_lds = 0;
+    DtwGate gate = kGateNone;   // the averaged-template gate the set supports (padded rows only: its list mode reads past a row)
+    bool fuse_max = false;      // ScoreMode::Max can be folded into the matrix-core kernel (DtwFusedAgg)
+};
+
+static DtwRoute dtw_route(const TemplatesDev &t, int band, size_t S, size_t n_win, bool padded, bool with_avg, float score_ref) {
+    DtwRoute r;
+    r.mfma_batch = padded && ((t.K == 5 && ((t.class_count[2] > 0 && dtw_mfma_supported(t, band, n_win, true, 8, score_ref)) ||
+                                            (t.class_count[1] > 0 && dtw_mfma_supported(t, band, n_win, true, 4, score_ref)))) ||
+                              dtw_mfma_wide_supported(t, band, score_ref) || dtw_mfma_wide3_supported(t, band));
+    r.few = padded && (S > 1 || r.mfma_batch) && n_win < (size_t)kDtwWin;
+    if (S == 1 && n_win <= 8 && t.max_diff == 0 && band >= 1 && 2 * band <= 16) {
+        r.single_lds = (2 * (size_t)t.max_len * (t.K | 1) + ((t.K + 3) & ~3) + (size_t)(2 * t.max_len + 2 * band + 16) * 2 * band) * sizeof(float);
+        r.single_fits = r.single_lds <= 64 * 1024;
+    }
+    r.single = r.single_fits && !r.mfma_batch;
+    // the register kernels assume m == n (no template longer than the window)
+    // (a register kernel stages 64..128 windows + two template lengths of frames in LDS: templates beyond ~4 000 frames at
+    // mfcc_size 5 -- 40 s -- do not fit the CU's 160 KB; the generic kernel stages one length and takes them up to ~8 000)
+    const bool reg_built = dtw_register_tile(t.K, band) > 0 && t.max_diff == 0 && t.chunks;
+    const bool reg_staged = reg_built && (size_t)(2 * kDtwWin + 2 * (t.max_len + 8)) * (size_t)(t.K | 1) * sizeof(float) <= 160 * 1024;
+    r.reg = !r.single && !t.ref_only && reg_built && (r.few || reg_staged);
+    // the band is widened to |m-n| inside the generic kernel; size for the worst case over templates
+    const int KP = t.K | 1, Wmax = band > t.max_diff ? band : t.max_diff;
+    r.generic_lds = ((size_t)(64 + t.max_len - 1) * KP + (size_t)t.K * 64 + (size_t)(2 * Wmax + 1) * 64) * sizeof(float);
+    const size_t rows = S * n_win;
+    if (padded && t.has_avg && rows > 0) {
+        if (!t.ref_only && reg_staged && rows < 0xffffffffULL) r.gate = kGateRegister;
+        else if (!r.single_fits && (t.ref_only || !reg_staged)) r.gate = kGateGeneric;
+    }
+    // ScoreMode::Max inside the matrix-core kernel: one chunk of 3..8 templates is all there is to score
+    const int n2 = t.class_count[3] - ((t.has_avg && !with_avg) ? 1 : 0);   // single-template chunks to score
+    r.fuse_max = r.reg && t.K == 5 && n2 == 0 && t.class_count[0] == 0 && t.class_count[1] + t.class_count[2] == 1 && band >= 3 && band <= 5 &&
+                 std::getenv("RP_DTW_NO_FUSED_MAX") == nullptr && dtw_mfma_supported(t, band, n_win, r.few, t.class_count[2] == 1 ? 8 : 4, score_ref);
+    return r;
 }
 
-template <int W>
-static hipError_t gated_k5(hipStream_t st, const DtwWork &wk, int band, const TemplatesDev &t, int avg_chunk, const float *mfcc, size_t S, size_t frame_pitch,
-                           size_t first_win, size_t n_win, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
-                           uint32_t *count, bool few, float abandon_nc) {
-    const size_t rows = S * n_win, tiles = (n_win + kDtwWin - 1) / kDtwWin;
+// e = CALL(K, W) on the (mfcc_size, band) pairs the register kernels are built for (dtw_register_tile > 0).  (A switch, not a generic
+// lambda: it keeps the order in which the kernel templates are instantiated, and with it the layout of the code object.)
+#define RP_BAND_DISPATCH(e, CALL, KK) \
+    switch (band) { case 3: e = CALL(KK, 3); break; case 4: e = CALL(KK, 4); break; case 5: e = CALL(KK, 5); break; default: e = CALL(KK, 6); }
+#define RP_REGISTER_DISPATCH(e, CALL)                                                                                                            \
+    do {                                                                                                                                         \
+        if (t.K == 5) { RP_BAND_DISPATCH(e, CALL, 5) } else if (t.K == 16) { RP_BAND_DISPATCH(e, CALL, 16) } else { RP_BAND_DISPATCH(e, CALL, 13) } \
+    } while (0)
+
+// the register family of (K, W): n1 single-template chunks, then the chunks of several templates
+template <int K, int W>
+static hipError_t launch_dtw_register(hipStream_t st, const TemplatesDev &t, int n1, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
+                                      size_t n_win, float score_ref, float *scores, float *avg, bool few, const GateList &gl, bool padded) {
+    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin;
+    if constexpr (K == 5) return launch_dtw_k5<W>(st, t, n1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, few, gl);
+    else return launch_dtw_wide_all<K, W>(st, t, n1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, few, gl, padded);
+}
+
+// The gate behind the register kernels (few: DtwRoute::few -- live-stream batches score the few newest windows of every stream: then
+// pass 1 also reads its frames from global memory); scores / avg rows have pitch n_win.
+template <int K, int W>
+static hipError_t gated_register(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, bool few, const float *mfcc, size_t S, size_t frame_pitch,
+                                 size_t first_win, size_t n_win, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
+                                 uint32_t *count, float abandon_nc) {
+    const size_t rows = S * n_win;
+    const int avg_chunk = t.class_first[3] + t.class_count[3] - 1;  // the averaged template: last of the single-template chunks
     // pass 1: the averaged template over every window (and, before the gate looks at them, the reference-shaped rescoring of the
     // windows whose frames left the norm range: dtw_ref_kernel)
     GateList g1;
     g1.fix = wk.fix; g1.sched = wk.sched; g1.ran = wk.ran;
-    hipError_t e = launch_dtw_single_chunks<5, W>(st, t, avg_chunk, 1, mfcc, S, frame_pitch, first_win, n_win, n_win, score_ref, scores, avg, few, g1);
+    hipError_t e;
+    if constexpr (K == 5) e = launch_dtw_single_chunks<5, W>(st, t, avg_chunk, 1, mfcc, S, frame_pitch, first_win, n_win, n_win, score_ref, scores, avg, few, g1);
+    else e = launch_dtw_wide<K, W, 1>(st, t, 3, 1, mfcc, S, frame_pitch, (n_win + kDtwWin - 1) / kDtwWin, first_win, n_win, n_win, score_ref, scores, avg, few, g1, avg_chunk);
     if (e != hipSuccess) return e;
-    if ((e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, false, t.T, 1)) != hipSuccess) return e;
+    if ((e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, W, score_ref, scores, avg, false, t.T, 1)) != hipSuccess) return e;
     // pass 2: list the rows whose avg_score is not below the threshold
     const size_t waves = (rows + 1023) / 1024, blocks = (waves + 3) / 4;
     hipLaunchKernelGGL(gate_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, st, avg, rows, avg_threshold, list, count);
@@ -1271,234 +1334,120 @@ static hipError_t gated_k5(hipStream_t st, const DtwWork &wk, int band, const Te
     GateList gl;
     gl.list = list; gl.count = count; gl.abandon_nc = abandon_nc; gl.fix = wk.fix; gl.sched = wk.sched; gl.ran = wk.ran;
     gl.dense_min = few ? 0u : (uint32_t)(rows - rows / 10);
-    e = launch_dtw_k5<W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, false, gl);
+    e = launch_dtw_register<K, W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, first_win, n_win, score_ref, scores, avg, false, gl, true);
     if (e != hipSuccess) return e;
     if (!few) {
         gl.list = nullptr;
-        if ((e = launch_dtw_k5<W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, false, gl)) != hipSuccess) return e;
-    }
-    return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, false, 0, t.T);
-}
-
-template <int K, int W>
-static hipError_t gated_wide(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int avg_chunk, const float *mfcc, size_t S, size_t frame_pitch,
-                             size_t first_win, size_t n_win, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
-                             uint32_t *count, bool few, float abandon_nc) {
-    const size_t rows = S * n_win, tiles = (n_win + kDtwWin - 1) / kDtwWin;
-    GateList g1;
-    g1.fix = wk.fix; g1.sched = wk.sched; g1.ran = wk.ran;
-    hipError_t e = launch_dtw_wide<K, W, 1>(st, t, 3, 1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, few, g1, avg_chunk);
-    if (e != hipSuccess) return e;
-    if ((e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, W, score_ref, scores, avg, false, t.T, 1)) != hipSuccess) return e;
-    const size_t waves = (rows + 1023) / 1024, blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL(gate_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, st, avg, rows, avg_threshold, list, count);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    GateList gl;
-    gl.list = list; gl.count = count; gl.abandon_nc = abandon_nc; gl.fix = wk.fix; gl.sched = wk.sched; gl.ran = wk.ran;
-    gl.dense_min = few ? 0u : (uint32_t)(rows - rows / 10);
-    e = launch_dtw_wide_all<K, W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, false, gl, true);
-    if (e != hipSuccess) return e;
-    if (!few) {
-        gl.list = nullptr;
-        if ((e = launch_dtw_wide_all<K, W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, false, gl, true)) != hipSuccess) return e;
+        if ((e = launch_dtw_register<K, W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, first_win, n_win, score_ref, scores, avg, false, gl, true)) != hipSuccess) return e;
     }
     return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, W, score_ref, scores, avg, false, 0, t.T);
 }
 
-// first_win / few_windows as in launch_dtw (live-stream batches score the few newest windows of every stream: then pass 1
-// also reads its frames from global memory); scores / avg rows have pitch n_win.
-static hipError_t launch_dtw_gated_impl(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                        size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
-                                        uint32_t *count, bool few_windows, float abandon_nc);
-hipError_t launch_dtw_gated(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                            size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
-                            uint32_t *count, bool few_windows, float abandon_nc) {
-    if (!dtw_gate_supported(t, band, S * n_win)) return hipErrorNotSupported;
-    const hipError_t e = launch_dtw_gated_impl(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, band, score_ref, avg_threshold, scores, avg, list, count,
-                                               few_windows, abandon_nc);
-    return e == hipSuccess ? e : dtw_abort(st, wk, e);
-}
-static hipError_t launch_dtw_gated_impl(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                        size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
-                                        uint32_t *count, bool few_windows, float abandon_nc) {
-    const size_t rows = S * n_win;
-    if (!dtw_gate_supported(t, band, rows)) return hipErrorNotSupported;
-    // (as in launch_dtw: one stream alone is scored like a batch when the matrix-core kernel serves its templates)
-    const bool mfma_batch = few_windows && ((t.K == 5 && ((t.class_count[2] > 0 && dtw_mfma_supported(t, band, n_win, true, 8, score_ref)) ||
-                                                          (t.class_count[1] > 0 && dtw_mfma_supported(t, band, n_win, true, 4, score_ref)))) ||
-                                            dtw_mfma_wide_supported(t, band, score_ref) || dtw_mfma_wide3_supported(t, band));
-    const bool few = few_windows && (S > 1 || mfma_batch) && n_win < (size_t)kDtwWin;
-    const int avg_chunk = t.class_first[3] + t.class_count[3] - 1;  // the averaged template: last of the single-template chunks
-    hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
-    if (e != hipSuccess) return e;
-    if (t.K == 5) {
-        switch (band) {
-        case 3: return gated_k5<3>(st, wk, band, t, avg_chunk, mfcc, S, frame_pitch, first_win, n_win, score_ref, avg_threshold, scores, avg, list, count, few, abandon_nc);
-        case 4: return gated_k5<4>(st, wk, band, t, avg_chunk, mfcc, S, frame_pitch, first_win, n_win, score_ref, avg_threshold, scores, avg, list, count, few, abandon_nc);
-        case 5: return gated_k5<5>(st, wk, band, t, avg_chunk, mfcc, S, frame_pitch, first_win, n_win, score_ref, avg_threshold, scores, avg, list, count, few, abandon_nc);
-        default: return gated_k5<6>(st, wk, band, t, avg_chunk, mfcc, S, frame_pitch, first_win, n_win, score_ref, avg_threshold, scores, avg, list, count, few, abandon_nc);
-        }
+// The gate behind the generic kernel: pass 1 scores every window against the averaged template (-> avg), pass 2 the sample
+// templates, each wave leaving at once when none of its 64 windows passed (scores of such rows are not written; the aggregate
+// pass gives them 0).
+static hipError_t gated_generic(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
+                                size_t first_win, size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg) {
+    if (t.ref_only) {  // a template row outside the norm range: every window reference-shaped, no skipping (the aggregate pass writes 0 for rejected rows)
+        if (hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, true, t.T, 1); e != hipSuccess) return e;
+        return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, true, 0, t.T);
     }
-#define RP_WIDE_CALL(KK, WW) gated_wide<KK, WW>(st, wk, t, avg_chunk, mfcc, S, frame_pitch, first_win, n_win, score_ref, avg_threshold, scores, avg, list, count, few, abandon_nc)
-    RP_WIDE_DISPATCH(RP_WIDE_CALL);
-#undef RP_WIDE_CALL
+    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin;
+    if (tiles * (size_t)t.T * S > 0x7fffffffULL) return hipErrorInvalidValue;
+    if (r.generic_lds > 160 * 1024) return hipErrorMemoryAllocation;
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_generic_kernel), 160 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)(tiles * S)), dim3(64), r.generic_lds, st, mfcc, frame_pitch, frame_pitch, (unsigned)tiles,
+                       first_win, n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, t.T, 1, t.max_len, band, score_ref, scores, avg,
+                       static_cast<const float *>(nullptr), 0.f, wk.fix);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    // the gate must see reference-shaped avg scores: rescoring of the listed windows first
+    if (hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, false, t.T, 1); e != hipSuccess) return e;
+    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)(tiles * (size_t)t.T * S)), dim3(64), r.generic_lds, st, mfcc, frame_pitch, frame_pitch,
+                       (unsigned)tiles, first_win, n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, 0, t.T, t.max_len, band, score_ref,
+                       scores, avg, static_cast<const float *>(avg), avg_threshold, wk.fix);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, false, 0, t.T);
+}
+
+// The averaged-template gate in the form the route names (r.gate != kGateNone): list [1 + S * n_win] words, the first the count.
+static hipError_t launch_dtw_gated(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
+                                   size_t first_win, size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg,
+                                   uint32_t *list, float abandon_nc) {
+    hipError_t e;
+    if (r.gate == kGateGeneric) e = gated_generic(st, wk, t, r, mfcc, S, frame_pitch, first_win, n_win, band, score_ref, avg_threshold, scores, avg);
+    else if ((e = hipMemsetAsync(list, 0, sizeof(uint32_t), st)) == hipSuccess) {
+#define RP_GATED(KK, WW) gated_register<KK, WW>(st, wk, t, r.few, mfcc, S, frame_pitch, first_win, n_win, score_ref, avg_threshold, scores, avg, list + 1, list, abandon_nc)
+        RP_REGISTER_DISPATCH(e, RP_GATED);
+#undef RP_GATED
+    }
+    return e == hipSuccess ? e : dtw_abort(st, wk, e);
 }
 
 // Normalised-cost bound above which a DTW cannot reach `threshold` any more: score = 1 / (1 + exp((nc - ref) / ref)) > thr
 // <=> nc < ref * (1 + ln(1/thr - 1)) (comparator.rs:18-26), with a margin for the rounding of the running costs.
-float dtw_abandon_nc(float threshold, float score_ref) {
+static float dtw_abandon_nc(float threshold, float score_ref) {
     if (!(score_ref > 0.f) || !(threshold > 0.f)) return __builtin_inff();  // everything can fire (or the formula is degenerate): never abandon
     if (threshold >= 1.f) return 0.f;                                         // a score is < 1: nothing can fire
     const float nc = score_ref * (1.f + logf(1.f / threshold - 1.f));
     return nc > 0.f ? nc * 1.001f + 1e-4f : nc + 1e-4f;
 }
 
-static hipError_t launch_dtw_fast(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch,
-                                  size_t first_win, size_t n_win, size_t out_win_pitch, int band, float score_ref, int with_avg,
-                                  float *scores, float *avg, bool padded_rows, float abandon_nc, DtwFusedAgg *fuse, bool *self_healing);
+// The ungated fast launches: dtw_single_kernel, the register kernels or dtw_generic_kernel.  fuse: the caller's ScoreMode::Max outputs;
+// `done` is set when the matrix-core kernel writes them.
+static hipError_t launch_dtw_fast(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
+                                  size_t first_win, size_t n_win, int band, float score_ref, int Ttot, float *scores, float *avg, bool padded_rows,
+                                  float abandon_nc, DtwFusedAgg *fuse) {
+    if (r.single) {
+        hipLaunchKernelGGL(dtw_single_kernel, dim3((unsigned)(n_win * Ttot)), dim3(64), r.single_lds, st, mfcc, frame_pitch, first_win,
+                           (unsigned)n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, 0, Ttot, t.max_len, band, score_ref,
+                           scores, avg, t.raw, t.ref_only, wk.fix);
+        dtw_mark(wk, kDtwRanSingle);
+        return hipGetLastError();
+    }
+    if (r.reg) {
+        GateList gl;
+        gl.abandon_nc = abandon_nc; gl.fix = wk.fix; gl.sched = wk.sched; gl.ran = wk.ran; gl.wk_all = wk; gl.padded = padded_rows;
+        if (fuse && fuse->agg && r.fuse_max) {
+            gl.fuse = fuse;
+            fuse->done = true;
+        }
+        // single-template chunks to score: the averaged template is the last of them, scored when Ttot counts it
+        const int n1 = t.class_count[3] - ((t.has_avg && Ttot == t.T) ? 1 : 0);
+        hipError_t e;
+#define RP_REGISTER(KK, WW) launch_dtw_register<KK, WW>(st, t, n1, mfcc, S, frame_pitch, first_win, n_win, score_ref, scores, avg, r.few, gl, padded_rows)
+        RP_REGISTER_DISPATCH(e, RP_REGISTER);
+#undef RP_REGISTER
+        return e;
+    }
+    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin, blocks = tiles * (size_t)Ttot * S;
+    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    if (r.generic_lds > 160 * 1024) return hipErrorMemoryAllocation;  // reported as "template too long" by the callers' hip_ok text
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_generic_kernel), 160 * 1024); e != hipSuccess) return e;
+    dtw_mark(wk, kDtwRanGeneric);
+    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)blocks), dim3(64), r.generic_lds, st, mfcc, frame_pitch, frame_pitch,
+                       (unsigned)tiles, first_win, n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, 0, Ttot,
+                       t.max_len, band, score_ref, scores, avg, static_cast<const float *>(nullptr), 0.f, wk.fix);
+    return hipGetLastError();
+}
 
-
-hipError_t launch_dtw(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch,
-                      size_t first_win, size_t n_win, size_t out_win_pitch, int band, float score_ref, int with_avg,
-                      float *scores, float *avg, bool padded_rows, float abandon_nc, DtwFusedAgg *fuse) {
+// The ungated call: the fast launches, then dtw_ref_kernel's pass over the windows they listed (a frame outside the norm range) -- or
+// over every window for a template set with such a row.
+static hipError_t launch_dtw(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
+                             size_t first_win, size_t n_win, int band, float score_ref, bool with_avg, float *scores, float *avg, bool padded_rows,
+                             float abandon_nc, DtwFusedAgg *fuse) {
     if (fuse) fuse->done = false;
     if (S == 0 || n_win == 0) return hipSuccess;
     if (!wk.fix || !wk.sched) return hipErrorInvalidValue;
     if (t.n_chunks_total > kDtwSchedChunks) return hipErrorInvalidValue;
     const int Ttot = t.T + ((with_avg && t.has_avg) ? 1 : 0);
-    bool self_healing = false;
-    if (!t.ref_only || (S == 1 && n_win <= 8)) {   // (a handful of windows of one stream: dtw_single_kernel takes force_ref itself)
-        if (hipError_t e = launch_dtw_fast(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, band, score_ref, with_avg, scores, avg,
-                                           padded_rows, abandon_nc, fuse, &self_healing); e != hipSuccess) return dtw_abort(st, wk, e);
-        if (self_healing) return hipSuccess;
+    if (r.single || !t.ref_only) {   // (dtw_single_kernel takes a ref-only set itself)
+        if (hipError_t e = launch_dtw_fast(st, wk, t, r, mfcc, S, frame_pitch, first_win, n_win, band, score_ref, Ttot, scores, avg, padded_rows,
+                                           abandon_nc, fuse); e != hipSuccess) return dtw_abort(st, wk, e);
+        if (r.single) return hipSuccess;
     }
-    // the windows the fast kernels listed (a frame outside the norm range), or -- a template set with such a row -- every window
-    const hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, band, score_ref, scores, avg, t.ref_only != 0, 0, Ttot,
+    const hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, t.ref_only != 0, 0, Ttot,
                                         (fuse && fuse->done) ? fuse : nullptr);
     return e == hipSuccess ? e : dtw_abort(st, wk, e);
-}
-
-static hipError_t launch_dtw_fast(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch,
-                                  size_t first_win, size_t n_win, size_t out_win_pitch, int band, float score_ref, int with_avg,
-                                  float *scores, float *avg, bool padded_rows, float abandon_nc, DtwFusedAgg *fuse, bool *self_healing) {
-    GateList gl;
-    gl.abandon_nc = abandon_nc; gl.fix = wk.fix; gl.sched = wk.sched; gl.ran = wk.ran; gl.wk_all = wk; gl.padded = padded_rows;
-    // many streams with few windows each (streaming batches): cross-stream waves reading frames from global memory;
-    // needs `padded_rows` (slack after the last stream's frames for the never-used out-of-band columns)
-    // (one stream alone is a batch too when the matrix-core kernel serves its templates: a stream's bits must not depend on the
-    // batch it is scored in, live or offline -- only the single-stream mirror, which never passes padded_rows, keeps dtw_single_kernel)
-    const bool mfma_batch = padded_rows && ((t.K == 5 && ((t.class_count[2] > 0 && dtw_mfma_supported(t, band, n_win, true, 8, score_ref)) ||
-                                                           (t.class_count[1] > 0 && dtw_mfma_supported(t, band, n_win, true, 4, score_ref)))) ||
-                                            dtw_mfma_wide_supported(t, band, score_ref) || dtw_mfma_wide3_supported(t, band));
-    const bool few = padded_rows && (S > 1 || mfma_batch) && n_win < (size_t)kDtwWin;
-    const bool do_avg = with_avg && t.has_avg;
-    const int Ttot = t.T + (do_avg ? 1 : 0);
-    // a handful of windows of one stream (the single-stream API): one wave per DTW, band lanes on anti-diagonals
-    if (S == 1 && n_win <= 8 && !mfma_batch && t.max_diff == 0 && band >= 1 && 2 * band <= 16) {
-        const int KP = t.K | 1;
-        const size_t lds = (2 * (size_t)t.max_len * KP + ((t.K + 3) & ~3) + (size_t)(2 * t.max_len + 2 * band + 16) * 2 * band) * sizeof(float);
-        if (lds <= 64 * 1024) {
-            hipLaunchKernelGGL(dtw_single_kernel, dim3((unsigned)(n_win * Ttot)), dim3(64), lds, st, mfcc, frame_pitch, first_win,
-                               (unsigned)n_win, out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, 0, Ttot, t.max_len, band, score_ref,
-                               scores, avg, t.raw, t.ref_only, wk.fix);
-            *self_healing = true;
-            dtw_mark(wk, kDtwRanSingle);
-            return hipGetLastError();
-        }
-    }
-    if (t.ref_only) return hipSuccess;  // launch_dtw scores every window with dtw_ref_kernel
-    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin;
-    // the register kernels assume m == n (no template longer than the window)
-    // (a register kernel stages 64..128 windows + two template lengths of frames in LDS: templates beyond ~4 000 frames at
-    // mfcc_size 5 -- 40 s -- do not fit the CU's 160 KB; the generic kernel stages one length and takes them up to ~8 000)
-    const size_t reg_lds = (size_t)(2 * kDtwWin + 2 * (t.max_len + 8)) * (size_t)(t.K | 1) * sizeof(float);
-    if (dtw_register_tile(t.K, band) > 0 && t.max_diff == 0 && t.chunks && (few || reg_lds <= 160 * 1024)) {
-        const int n2 = t.class_count[3] - ((t.has_avg && !do_avg) ? 1 : 0);  // single-template chunks to score
-        if (t.K == 5) {
-            // ScoreMode::Max inside the matrix-core kernel: one chunk of 3..8 templates is all there is to score
-            if (fuse && fuse->agg && n2 == 0 && t.class_count[0] == 0 && t.class_count[1] + t.class_count[2] == 1 && band >= 3 && band <= 5 &&
-                std::getenv("RP_DTW_NO_FUSED_MAX") == nullptr &&
-                dtw_mfma_supported(t, band, n_win, few, t.class_count[2] == 1 ? 8 : 4, score_ref)) {
-                gl.fuse = fuse;
-                fuse->done = true;
-            }
-            switch (band) {
-            case 3: return launch_dtw_k5<3>(st, t, n2, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
-            case 4: return launch_dtw_k5<4>(st, t, n2, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
-            case 5: return launch_dtw_k5<5>(st, t, n2, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
-            default: return launch_dtw_k5<6>(st, t, n2, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
-            }
-        }
-#define RP_WIDE_CALL(KK, WW) launch_dtw_wide_all<KK, WW>(st, t, n2, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl, padded_rows)
-        RP_WIDE_DISPATCH(RP_WIDE_CALL);
-#undef RP_WIDE_CALL
-    }
-    const size_t blocks = tiles * (size_t)Ttot * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const int KP = t.K | 1;
-    // the band is widened to |m-n| inside the kernel; size for the worst case over templates
-    const int Wmax = band > t.max_diff ? band : t.max_diff;
-    const size_t lds = ((size_t)(64 + t.max_len - 1) * KP + (size_t)t.K * 64 + (size_t)(2 * Wmax + 1) * 64) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorMemoryAllocation;  // reported as "template too long" by the callers' hip_ok text
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_generic_kernel), 160 * 1024); e != hipSuccess) return e;
-    dtw_mark(wk, kDtwRanGeneric);
-    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)blocks), dim3(64), lds, st, mfcc, frame_pitch, frame_pitch,
-                       (unsigned)tiles, first_win, n_win, out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, 0, Ttot,
-                       t.max_len, band, score_ref, scores, avg, static_cast<const float *>(nullptr), 0.f, wk.fix);
-    return hipGetLastError();
-}
-
-// true when launch_dtw serves this template set with dtw_generic_kernel (any mfcc_size / band / an averaged template longer
-// than the window)
-bool dtw_uses_generic(const TemplatesDev &t, int band, size_t S, size_t n_win) {
-    if (S == 1 && n_win <= 8 && t.max_diff == 0 && band >= 1 && 2 * band <= 16) {   // dtw_single_kernel, if its LDS fits
-        const size_t lds1 = (2 * (size_t)t.max_len * (t.K | 1) + ((t.K + 3) & ~3) + (size_t)(2 * t.max_len + 2 * band + 16) * 2 * band) * sizeof(float);
-        if (lds1 <= 64 * 1024) return false;
-    }
-    if (t.ref_only) return true;   // dtw_ref_kernel: launch_dtw_generic_gated is the gated form
-    const size_t reg_lds = (size_t)(2 * kDtwWin + 2 * (t.max_len + 8)) * (size_t)(t.K | 1) * sizeof(float);
-    return !(dtw_register_tile(t.K, band) > 0 && t.max_diff == 0 && t.chunks && reg_lds <= 160 * 1024);
-}
-
-// The averaged-template gate behind the generic kernel: pass 1 scores every window against the averaged template (-> avg),
-// pass 2 the sample templates, each wave leaving at once when none of its 64 windows passed (scores of such rows are not
-// written; the aggregate pass gives them 0).
-static hipError_t launch_dtw_generic_gated_impl(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch,
-                                                size_t first_win, size_t n_win, size_t out_win_pitch, int band, float score_ref, float avg_threshold,
-                                                float *scores, float *avg);
-hipError_t launch_dtw_generic_gated(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                    size_t n_win, size_t out_win_pitch, int band, float score_ref, float avg_threshold, float *scores,
-                                    float *avg) {
-    if (S == 0 || n_win == 0) return hipSuccess;
-    if (!t.has_avg || !avg) return hipErrorInvalidValue;
-    const hipError_t e = launch_dtw_generic_gated_impl(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, band, score_ref, avg_threshold, scores, avg);
-    return e == hipSuccess ? e : dtw_abort(st, wk, e);
-}
-static hipError_t launch_dtw_generic_gated_impl(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch,
-                                                size_t first_win, size_t n_win, size_t out_win_pitch, int band, float score_ref, float avg_threshold,
-                                                float *scores, float *avg) {
-    if (t.ref_only) {  // a template row outside the norm range: every window reference-shaped, no skipping (the aggregate pass writes 0 for rejected rows)
-        if (hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, band, score_ref, scores, avg, true, t.T, 1); e != hipSuccess) return e;
-        return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, band, score_ref, scores, avg, true, 0, t.T);
-    }
-    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin;
-    if (tiles * (size_t)t.T * S > 0x7fffffffULL) return hipErrorInvalidValue;
-    const int KP = t.K | 1;
-    const int Wmax = band > t.max_diff ? band : t.max_diff;
-    const size_t lds = ((size_t)(64 + t.max_len - 1) * KP + (size_t)t.K * 64 + (size_t)(2 * Wmax + 1) * 64) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorMemoryAllocation;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_generic_kernel), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)(tiles * S)), dim3(64), lds, st, mfcc, frame_pitch, frame_pitch, (unsigned)tiles,
-                       first_win, n_win, out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, t.T, 1, t.max_len, band, score_ref, scores, avg,
-                       static_cast<const float *>(nullptr), 0.f, wk.fix);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    // the gate must see reference-shaped avg scores: rescoring of the listed windows first
-    if (hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, band, score_ref, scores, avg, false, t.T, 1); e != hipSuccess) return e;
-    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)(tiles * (size_t)t.T * S)), dim3(64), lds, st, mfcc, frame_pitch, frame_pitch,
-                       (unsigned)tiles, first_win, n_win, out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, 0, t.T, t.max_len, band, score_ref,
-                       scores, avg, static_cast<const float *>(avg), avg_threshold, wk.fix);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, band, score_ref, scores, avg, false, 0, t.T);
 }
 
 // A handful of windows of ONE stream (the single-stream API), templates t_first .. t_first + t_count - 1 only (index T = the
@@ -1507,11 +1456,9 @@ static hipError_t launch_dtw_generic_gated_impl(hipStream_t st, const DtwWork &w
 hipError_t launch_dtw_single_part(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t frame_pitch, size_t first_win, size_t n_win,
                                   size_t out_win_pitch, int band, float score_ref, int t_first, int t_count, float *scores, float *avg) {
     if (n_win == 0 || t_count <= 0) return hipSuccess;
-    if (!(n_win <= 8 && t.max_diff == 0 && band >= 1 && 2 * band <= 16) || t_first + t_count > t.T + (t.has_avg ? 1 : 0)) return hipErrorNotSupported;
-    const int KP = t.K | 1;
-    const size_t lds = (2 * (size_t)t.max_len * KP + ((t.K + 3) & ~3) + (size_t)(2 * t.max_len + 2 * band + 16) * 2 * band) * sizeof(float);
-    if (lds > 64 * 1024) return hipErrorNotSupported;
-    hipLaunchKernelGGL(dtw_single_kernel, dim3((unsigned)(n_win * t_count)), dim3(64), lds, st, mfcc, frame_pitch, first_win, (unsigned)n_win,
+    const DtwRoute r = dtw_route(t, band, 1, n_win, false, true, score_ref);
+    if (!r.single_fits || t_first + t_count > t.T + (t.has_avg ? 1 : 0)) return hipErrorNotSupported;
+    hipLaunchKernelGGL(dtw_single_kernel, dim3((unsigned)(n_win * t_count)), dim3(64), r.single_lds, st, mfcc, frame_pitch, first_win, (unsigned)n_win,
                        out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, t_first, t_count, t.max_len, band, score_ref, scores, avg, t.raw, t.ref_only, wk.fix);
     return hipGetLastError();
 }
@@ -1673,6 +1620,48 @@ hipError_t launch_aggregate(hipStream_t st, const float *scores, size_t n_rows, 
 #undef RP_AGG_SORTED
     } else hipLaunchKernelGGL(aggregate_sorted_kernel, dim3((unsigned)blocks), dim3(64), 0, st, scores, n_rows, T, mode, agg, x);
     return hipGetLastError();
+}
+
+
+// -------------------------------------------------------------------- one scoring call: DTW, then aggregate
+bool dtw_score(Ctx &c, const DtwScore &q) {
+    const TemplatesDev &t = *q.t;
+    const size_t rows = q.S * q.n_win;
+    const DtwRoute r = dtw_route(t, q.band, q.S, q.n_win, q.padded_rows, q.with_avg, q.score_ref);
+    // The averaged-template gate as the reference runs it (wakeword_comp.rs:85-93): a window whose avg_score is below avg_threshold is
+    // never compared with the sample templates
+    const bool gated = q.with_avg && q.detect_only && (r.gate == kGateRegister || (r.gate == kGateGeneric && q.gate_generic)) &&
+                       (q.gate_one_stream || !(q.S == 1 && q.n_win <= 8));
+    // detect-only calls in ScoreMode::Max may also stop DTWs that can no longer reach `threshold` (GateList::abandon_nc)
+    const float abandon = (q.detect_only && q.score_mode == RP_SCORE_MAX) ? dtw_abandon_nc(q.threshold, q.score_ref) : __builtin_inff();
+    uint32_t *list = q.gate_list;
+    if (gated && !list) {
+        if (!c.ws_list.reserve((rows + 1) * sizeof(uint32_t) + 16)) return false;
+        list = c.ws_list.as<uint32_t>();
+    }
+    // ScoreMode::Max of a reference whose templates are one chunk of the matrix-core kernel, no averaged template scored: the DTW
+    // kernel writes the aggregate (and the flags) itself and the aggregate pass is skipped
+    DtwFusedAgg fz;
+    if (q.fuse_max && q.score_mode == RP_SCORE_MAX && !q.with_avg && rows && q.agg) { fz.agg = q.agg; fz.hot = q.hot; fz.threshold = q.threshold; }
+    const DtwWork wk = (q.ragged && !gated) ? c.dtw_work_for(q.S, rows * (size_t)(t.rag_count > 1 ? t.rag_count : 1)) : c.dtw_work();
+    if (q.timed) c.time_begin(kKernelDtw);
+    bool ok = gated ? hip_ok(launch_dtw_gated(c.stream, wk, t, r, q.mfcc, q.S, q.frame_pitch, q.first_win, q.n_win, q.band, q.score_ref, q.avg_threshold,
+                                              q.scores, q.avg, list, abandon),
+                             r.gate == kGateRegister ? "dtw kernels (gated)" : "dtw_generic_kernel (gated)")
+                    : hip_ok(launch_dtw(c.stream, wk, t, r, q.mfcc, q.S, q.frame_pitch, q.first_win, q.n_win, q.band, q.score_ref, q.with_avg, q.scores,
+                                        q.avg, q.padded_rows, abandon, fz.agg ? &fz : nullptr),
+                             "dtw kernel");
+    if (q.timed) c.time_end();
+    if (!ok || !q.agg || fz.done) return ok;
+    // the aggregate pass: 0 for the windows the gate rejected (their `scores` rows were never written) and, with `hot`, the flags
+    // that tell the scan which streams can fire at all
+    AggExtra ax;
+    if (q.hot) { ax.hot = q.hot; ax.threshold = q.threshold; ax.n_win = q.n_win; }
+    if (gated) { ax.gate_avg = q.avg; ax.gate_threshold = q.avg_threshold; }
+    if (q.timed) c.time_begin(kKernelAggregate);
+    ok = hip_ok(launch_aggregate(c.stream, q.scores, rows, t.T, q.score_mode, q.agg, ax), "aggregate_kernel");
+    if (q.timed) c.time_end();
+    return ok;
 }
 
 }  // namespace rp

@@ -239,7 +239,7 @@ __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { re
 // gate (1e-5) down to kDtwMfmaMinScoreRef (tools/probe_score_ref.py, tests/test_gpu_round4.py); below, the f32 register kernels score
 constexpr float kDtwMfmaMinScoreRef = 0.05f;
 bool dtw_mfma_supported(const TemplatesDev &t, int band, size_t n_win, bool from_global, int slots, float score_ref);
-// mfcc_size 13 / 16 at band 5: frames always from global memory (the caller's rows end with slack: launch_dtw's padded_rows)
+// mfcc_size 13 / 16 at band 5: frames always from global memory (the caller's rows end with slack: DtwScore::padded_rows)
 bool dtw_mfma_wide_supported(const TemplatesDev &t, int band, float score_ref);
 hipError_t launch_dtw_mfma_wide(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
                                 size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float *avg, const uint32_t *list,
@@ -335,32 +335,42 @@ hipError_t launch_mfcc_stream(hipStream_t st, const MfccTablesDev &tb, const voi
 hipError_t launch_mfcc_fmt(hipStream_t st, const MfccTablesDev &tb, const void *pcm, int fmt, size_t S, size_t n_samples,
                            size_t pcm_stride, size_t first_frame, size_t n_frames, size_t out_frame_pitch, float *mfcc);
 
-// scores [S][n_win][T]; avg [S][n_win] or nullptr.  mfcc rows have `frame_pitch` frames per stream.
-// abandon_nc (dtw_abandon_nc(threshold, score_ref), or +inf = off): DETECT-ONLY calls in ScoreMode::Max may stop a wave
-// whose windows x templates all cost more than any score above `threshold` allows; those rows get score 0 (GateList in
-// rp_dtw.hip).  Every window that can fire keeps exact scores, so the detections do not change.
-float dtw_abandon_nc(float threshold, float score_ref);
-hipError_t launch_dtw(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch,
-                      size_t first_win, size_t n_win, size_t out_win_pitch, int band, float score_ref, int with_avg,
-                      float *scores, float *avg, bool padded_rows = false, float abandon_nc = __builtin_inff(), DtwFusedAgg *fuse = nullptr);
+// One scoring call of a template set over S streams x n_win windows: the DTW launches, then the aggregate pass.  The caller describes
+// the call; rp_dtw.hip decides which kernels score it, whether the averaged-template gate runs and in which form, whether DTWs may be
+// abandoned and whether ScoreMode::Max is folded into the DTW kernel.  mfcc rows have `frame_pitch` frames per stream.
+struct Ctx;
+struct DtwScore {
+    const TemplatesDev *t = nullptr;
+    const float *mfcc = nullptr;
+    size_t S = 0, frame_pitch = 0, first_win = 0, n_win = 0;
+    int band = 0;
+    float score_ref = 0.f;
+    bool with_avg = false;   // score the averaged template (-> avg); the set has one
+    // no per-window score array is part of the call's result: the gate may leave rows unscored (wakeword_comp.rs:85-93) and, in
+    // ScoreMode::Max, DTWs that can no longer reach `threshold` may stop with score 0 (GateList::abandon_nc in rp_dtw.hip).  Every window
+    // that can fire keeps exact scores, so the detections do not change.
+    bool detect_only = false;
+    float avg_threshold = 0.f, threshold = 0.f;
+    int score_mode = 0;   // rp_score_mode
+    // outputs: scores [S][n_win][T], avg [S][n_win] (with_avg), agg [S][n_win] (null: no aggregate pass), hot [S] (null: none; else
+    // zero before the call, AggExtra), gate_list [1 + S * n_win] words (null: Ctx::ws_list, reserved when the gate runs)
+    float *scores = nullptr, *avg = nullptr, *agg = nullptr;
+    uint32_t *hot = nullptr, *gate_list = nullptr;
+    // How the entry points differ.  Each is kept as it was: harmonising them would change which kernels run.
+    bool gate_generic = false;      // the gate also runs behind dtw_generic_kernel (rp_batch_detect_fmt; the others score such sets ungated)
+    bool gate_one_stream = true;    // one stream with <= 8 windows is gated too (a live batch of one stream skips the gate's three passes)
+    bool fuse_max = false;          // ScoreMode::Max may be folded into the matrix-core kernel (the single-wakeword detect calls)
+    bool ragged = false;            // dtw_ragged_kernel's blocks are reserved for the ungated launch (whole-stream batches)
+    bool padded_rows = true;        // the frame array ends with slack; false keeps dtw_single_kernel for one stream
+    bool timed = true;              // inside the context's kKernelDtw / kKernelAggregate brackets (the single-stream handle times nothing)
+};
+// false with the error set (hip_ok): "dtw kernel", "dtw kernels (gated)", "dtw_generic_kernel (gated)" or "aggregate_kernel"
+bool dtw_score(Ctx &c, const DtwScore &q);
 
-// the same gate for template sets only dtw_generic_kernel serves (dtw_uses_generic), at wave granularity, and for the
-// single-stream API (one launch for the averaged template, one for the sample templates when a window passed)
-bool dtw_uses_generic(const TemplatesDev &t, int band, size_t S, size_t n_win);
-hipError_t launch_dtw_generic_gated(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                    size_t n_win, size_t out_win_pitch, int band, float score_ref, float avg_threshold, float *scores,
-                                    float *avg);
+// the single-stream handle's gate-first order (rp_detector.cpp): templates t_first .. t_first + t_count - 1 (index T = the averaged
+// template) of a handful of windows of one stream through dtw_single_kernel; hipErrorNotSupported when that kernel does not take the set
 hipError_t launch_dtw_single_part(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t frame_pitch, size_t first_win, size_t n_win,
                                   size_t out_win_pitch, int band, float score_ref, int t_first, int t_count, float *scores, float *avg);
-
-// The averaged-template gate as a skip (wakeword_comp.rs:85-93): every window against the averaged template (-> avg),
-// the rows with avg >= avg_threshold listed (list [S*n_win] / count: device workspaces), the sample templates on the
-// listed rows only (-> scores [S][n_win][T]; other rows are not written).  mfcc needs 64*K floats of slack behind the last stream.
-// hipErrorNotSupported when the template set has no register kernel for this (see dtw_gate_supported).
-bool dtw_gate_supported(const TemplatesDev &t, int band, size_t rows);
-hipError_t launch_dtw_gated(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                            size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
-                            uint32_t *count, bool few_windows = false, float abandon_nc = __builtin_inff());
 
 // Largest template tile the register DTW kernel is built for (0: only the generic kernel applies).
 int dtw_register_tile(int K, int band);
