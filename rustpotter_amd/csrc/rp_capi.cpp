@@ -80,6 +80,14 @@ template <class F> static int guarded(F &&f) {
     catch (...) { set_last_error("unknown error"); return -1; }
 }
 
+// one launch, timed as `kernel` when the context times its kernels (rp_ctx_timing_enable)
+template <class F> static bool timed(Ctx *c, int kernel, const char *what, F &&launch) {
+    c->time_begin(kernel);
+    const bool ok = hip_ok(launch(), what);
+    c->time_end();
+    return ok;
+}
+
 extern "C" {
 
 const char *rp_last_error(void) { return last_error().c_str(); }
@@ -281,10 +289,90 @@ struct Staged {  // host<->device staging for RP_CTX_HOST_POINTERS
         return hip_ok(hipMemcpyAsync(host_p, dev_p, bytes, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(D2H)");
     }
     bool finish() { return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize"); }
+    // det [S][max_det] and n_det [S], then the int32 column per detection `col` (det_wakeword / det_label) when there is one
+    bool back_detections(size_t S, int max_det, rp_batch_detection *det, const BatchDetection *dd, int32_t *n_det, const int32_t *dn,
+                         int32_t *col = nullptr, const int32_t *dcol = nullptr) {
+        return back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) && back(n_det, dn, S * sizeof(int32_t)) &&
+               (!dcol || back(col, dcol, S * (size_t)max_det * sizeof(int32_t)));
+    }
+};
+
+// whole-stream detection after detect_front: device det / n_det, the MFCC frames ws_mfcc [S][nf][K], windows per stream
+struct DetectFront {
+    BatchDetection *dd = nullptr;
+    int32_t *dn = nullptr;
+    float *dm = nullptr;
+    size_t nf = 0, n_win = 0, rows = 0;
 };
 }  // namespace
 
 static size_t sample_bytes(rp_sample_format f) { return f == RP_SAMPLE_I8 ? 1 : f == RP_SAMPLE_I16 ? 2 : 4; }
+static float vad_mode_value(rp_vad_mode m) { return m == RP_VAD_EASY ? 2.f : m == RP_VAD_MEDIUM ? 2.5f : 3.f; }  // src/config.rs:140-146
+
+static bool sample_format_ok(rp_sample_format fmt) {
+    if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return false; }
+    return true;
+}
+// whole streams of n_samples samples, pcm_stride apart
+static bool pcm_args_ok(rp_sample_format fmt, size_t n_samples, size_t pcm_stride) {
+    if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return false; }
+    return sample_format_ok(fmt);
+}
+static bool mlp_precision_ok(int p) {
+    if (p != RP_MLP_F32 && p != RP_MLP_BF16 && p != RP_MLP_F32_STRICT && p != RP_MLP_F32_FAST) { set_last_error("unknown MLP precision"); return false; }
+    return true;
+}
+static int widest_layer(const Model &m) {
+    int maxd = 0;
+    for (int d : m.dims) maxd = std::max(maxd, d);
+    return maxd;
+}
+
+// fpf 0: the ScanConfig default (whole streams, 30 ms frames)
+static ScanConfig scan_config(const rp_detector_config &cfg, int max_len, bool avg_enabled, int fpf = 0) {
+    ScanConfig sc;
+    sc.threshold = cfg.threshold; sc.avg_threshold = cfg.avg_threshold; sc.min_scores = (int)cfg.min_scores;
+    sc.eager = cfg.eager ? 1 : 0; sc.max_len = max_len; sc.avg_enabled = avg_enabled ? 1 : 0;
+    if (fpf) sc.fpf = fpf;
+    return sc;
+}
+
+// The front of whole-stream detection: checks the PCM arguments, stages the PCM in and det / n_det out and writes the MFCC frames of
+// every stream to ws_mfcc (timed).  Windows are max_len frames long.
+static bool detect_front(Ctx *c, Staged &sg, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, int K,
+                         int max_len, rp_batch_detection *det, int32_t *n_det, int max_det, DetectFront *f) {
+    if (!pcm_args_ok(fmt, n_samples, pcm_stride)) return false;
+    const MfccTablesDev *tb = c->tables_for(K);
+    if (!tb) return false;
+    f->nf = rp_mfcc_num_frames(n_samples);
+    f->n_win = f->nf >= (size_t)max_len ? f->nf - max_len + 1 : 0;
+    f->rows = S * f->n_win;
+    const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
+    f->dd = static_cast<BatchDetection *>(sg.out(det, S * (size_t)max_det * sizeof(BatchDetection), c->stage_out));
+    f->dn = static_cast<int32_t *>(sg.out(n_det, S * sizeof(int32_t), c->stage_out2));
+    if (S && (!dp || !f->dd || !f->dn)) return false;
+    if (!c->ws_mfcc.reserve(S * f->nf * K * sizeof(float) + 64 * K * sizeof(float))) return false;  // slack: the list kernel's band reads past a row
+    f->dm = c->ws_mfcc.as<float>();
+    return timed(c, kKernelMfcc, "mfcc_kernel", [&] { return launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, f->nf, f->nf, f->dm); });
+}
+
+// The tail of whole-stream detection: VAD values of the frames dm [S][nf][K] when vad_mode is on, then the timed scan -- launch_scan over
+// one wakeword's agg / avg (ww == nullptr), else launch_scan_multi over `ww` (dcol: each detection's wakeword or label)
+static bool detect_scan(Ctx *c, const rp_detector_config &cfg, const float *dm, size_t S, size_t nf, int K, const ScanConfig &sc,
+                        const float *dg, const float *da, uint32_t *hot, const ScanWakewords *ww, BatchDetection *dd, int32_t *dcol,
+                        int32_t *dn, int max_det) {
+    float *dv = nullptr;
+    if (cfg.vad_mode != RP_VAD_NONE) {
+        if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return false;
+        dv = c->ws_vad.as<float>();
+        if (!hip_ok(launch_vad_value(c->stream, dm, S * nf, K, dv), "vad_value_kernel")) return false;
+    }
+    const float vm = vad_mode_value(cfg.vad_mode);
+    return timed(c, kKernelScan, "scan_kernel", [&] {
+        return ww ? launch_scan_multi(c->stream, *ww, dv, vm, S, nf, sc, dd, dcol, dn, max_det)
+                  : launch_scan(c->stream, dg, da, dv, vm, S, nf, sc, dd, dn, max_det, hot);
+    });
+}
 
 int rp_mfcc_batch_fmt(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                       int K, float *mfcc) {
@@ -292,8 +380,7 @@ int rp_mfcc_batch_fmt(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t
         if (!ctx) { set_last_error("null handle"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
+        if (!pcm_args_ok(fmt, n_samples, pcm_stride)) return -1;
         const MfccTablesDev *tb = c->tables_for(K);
         if (!tb) return -1;
         const size_t nf = rp_mfcc_num_frames(n_samples);
@@ -301,10 +388,8 @@ int rp_mfcc_batch_fmt(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t
         const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
         float *dm = static_cast<float *>(sg.out(mfcc, S * nf * K * sizeof(float), c->stage_out));
         if ((S && nf) && (!dp || !dm)) return -1;
-        c->time_begin(kKernelMfcc);
-        bool ok = hip_ok(launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, nf, nf, dm), "mfcc_kernel");
-        c->time_end();
-        if (!ok) return -1;
+        if (!timed(c, kKernelMfcc, "mfcc_kernel", [&] { return launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, nf, nf, dm); }))
+            return -1;
         if (!sg.back(mfcc, dm, S * nf * K * sizeof(float)) || !sg.finish()) return -1;
         return 0;
     });
@@ -368,7 +453,7 @@ int rp_frontend_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         if (pcm_stride < n_samples || out_stride < n_samples) { set_last_error("stride smaller than n_samples"); return -1; }
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
+        if (!sample_format_ok(fmt)) return -1;
         if (!filters) { set_last_error("null argument"); return -1; }
         const rp_gain_normalization_config &g = filters->gain_normalizer;
         const rp_band_pass_config &b = filters->band_pass;
@@ -459,8 +544,6 @@ int rp_dtw_score_batch(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames
     });
 }
 
-static float vad_mode_value(rp_vad_mode m) { return m == RP_VAD_EASY ? 2.f : m == RP_VAD_MEDIUM ? 2.5f : 3.f; }  // src/config.rs:140-146
-
 int rp_detect_scan(rp_ctx *ctx, const float *agg, const float *avg, size_t S, size_t n_frames, int max_len,
                    const rp_detector_config *config, int avg_enabled, const float *mfcc, int K,
                    rp_batch_detection *det, int32_t *n_det, int max_det) {
@@ -472,28 +555,17 @@ int rp_detect_scan(rp_ctx *ctx, const float *agg, const float *avg, size_t S, si
         const bool vad = config->vad_mode != RP_VAD_NONE;
         if (vad && (!mfcc || K < 1)) { set_last_error("rp_detect_scan: vad_mode needs the MFCC frames"); return -1; }
         static_assert(sizeof(rp_batch_detection) == sizeof(BatchDetection), "layout");
-        ScanConfig sc;
-        sc.threshold = config->threshold; sc.avg_threshold = config->avg_threshold; sc.min_scores = (int)config->min_scores;
-        sc.eager = config->eager ? 1 : 0; sc.max_len = max_len; sc.avg_enabled = (avg_enabled && avg) ? 1 : 0;
+        const ScanConfig sc = scan_config(*config, max_len, avg_enabled && avg);
         const size_t n_win = n_frames >= (size_t)max_len ? n_frames - max_len + 1 : 0;
         Staged sg(c);
         const float *dg = static_cast<const float *>(sg.in(agg, S * n_win * sizeof(float), c->stage_in));
         const float *da = sc.avg_enabled ? static_cast<const float *>(sg.in(avg, S * n_win * sizeof(float), c->stage_out3)) : nullptr;
         BatchDetection *dd = static_cast<BatchDetection *>(sg.out(det, S * (size_t)max_det * sizeof(BatchDetection), c->stage_out));
         int32_t *dn = static_cast<int32_t *>(sg.out(n_det, S * sizeof(int32_t), c->stage_out2));
-        float *dv = nullptr;
-        if (vad) {
-            const float *dm = static_cast<const float *>(sg.in(mfcc, S * n_frames * K * sizeof(float), c->ws_mfcc));
-            if (!c->ws_vad.reserve(S * n_frames * sizeof(float) + 16) || (S * n_frames && !dm)) return -1;
-            dv = c->ws_vad.as<float>();
-            if (!hip_ok(launch_vad_value(c->stream, dm, S * n_frames, K, dv), "vad_value_kernel")) return -1;
-        }
-        c->time_begin(kKernelScan);
-        bool ok = hip_ok(launch_scan(c->stream, dg, da, dv, vad_mode_value(config->vad_mode), S, n_frames, sc, dd, dn, max_det), "scan_kernel");
-        c->time_end();
-        if (!ok) return -1;
-        if (!sg.back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) || !sg.back(n_det, dn, S * sizeof(int32_t)) || !sg.finish()) return -1;
-        return 0;
+        const float *dm = vad ? static_cast<const float *>(sg.in(mfcc, S * n_frames * K * sizeof(float), c->ws_mfcc)) : nullptr;
+        if (vad && S * n_frames && !dm) return -1;
+        if (!detect_scan(c, *config, dm, S, n_frames, K, sc, dg, da, nullptr, nullptr, dd, nullptr, dn, max_det)) return -1;
+        return sg.back_detections(S, max_det, det, dd, n_det, dn) && sg.finish() ? 0 : -1;
     });
 }
 
@@ -526,42 +598,28 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
         if (!config || (S && (!pcm || !det || !n_det))) { set_last_error("null argument"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
         const TemplatesDev &td = t->impl->dev;
-        const MfccTablesDev *tb = c->tables_for(td.K);
-        if (!tb) return -1;
-        const size_t nf = rp_mfcc_num_frames(n_samples);
-        const size_t n_win = nf >= (size_t)td.max_len ? nf - td.max_len + 1 : 0;
-        const size_t rows = S * n_win;
         const bool do_avg = td.has_avg && config->avg_threshold != 0.f;  // wakeword_comp.rs:85
         Staged sg(c);
         if (gather.device_pcm) sg.host = false;
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
-        const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
-        BatchDetection *dd = static_cast<BatchDetection *>(sg.out(det, S * (size_t)max_det * sizeof(BatchDetection), c->stage_out));
-        int32_t *dn = static_cast<int32_t *>(sg.out(n_det, S * sizeof(int32_t), c->stage_out2));
+        DetectFront f;
+        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, td.K, td.max_len, det, n_det, max_det, &f)) return -1;
+        const size_t nf = f.nf, n_win = f.n_win, rows = f.rows;
         if (gather.on) {  // results are produced in this context's own buffers and copied into the gathered block below
             if (!c->stage_out.reserve(S * (size_t)max_det * sizeof(BatchDetection) + 16) || !c->stage_out2.reserve(S * sizeof(int32_t) + 16)) return -1;
-            dd = c->stage_out.as<BatchDetection>(); dn = c->stage_out2.as<int32_t>();
+            f.dd = c->stage_out.as<BatchDetection>(); f.dn = c->stage_out2.as<int32_t>();
         }
         // caller-provided score arrays are used directly when they are device pointers
         float *ds = (scores && !sg.host) ? scores : nullptr, *dg = (agg && !sg.host) ? agg : nullptr;
-        if (!c->ws_mfcc.reserve(S * nf * td.K * sizeof(float) + 64 * td.K * sizeof(float))) return -1;  // slack: the list kernel's band reads past a row
         if (!ds) { if (!c->ws_scores.reserve(rows * td.T * sizeof(float) + 16)) return -1; ds = c->ws_scores.as<float>(); }
         if (!dg) { if (!c->ws_agg.reserve(rows * sizeof(float) + 16)) return -1; dg = c->ws_agg.as<float>(); }
         float *da = nullptr;
         if (do_avg) { if (!c->ws_avg.reserve(rows * sizeof(float) + 16)) return -1; da = c->ws_avg.as<float>(); }
-        if (S && (!dp || !dd || !dn)) return -1;
-        float *dm = c->ws_mfcc.as<float>();
-        c->time_begin(kKernelMfcc);
-        bool ok = hip_ok(launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, nf, nf, dm), "mfcc_kernel");
-        c->time_end();
-        if (!ok) return -1;
         // ws_mfcc ends with slack (padded rows): short streams (fewer than 64 windows each) are scored by cross-stream waves like
         // live-stream batches.  The averaged-template gate is taken when the caller did not ask for the per-window score arrays (those
         // are defined for every window) and RP_CTX_FULL_SCORES is not set.
         DtwScore q;
-        q.t = &td; q.mfcc = dm; q.S = S; q.frame_pitch = nf; q.n_win = n_win; q.band = config->band_size; q.score_ref = config->score_ref;
+        q.t = &td; q.mfcc = f.dm; q.S = S; q.frame_pitch = nf; q.n_win = n_win; q.band = config->band_size; q.score_ref = config->score_ref;
         q.with_avg = do_avg; q.detect_only = !scores && !agg && !(c->flags & RP_CTX_FULL_SCORES);
         q.avg_threshold = config->avg_threshold; q.threshold = config->threshold; q.score_mode = (int)config->score_mode;
         q.scores = ds; q.avg = da; q.agg = dg;
@@ -571,20 +629,9 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
             if (!q.hot) return -1;
         }
         if (!dtw_score(*c, q)) return -1;
-        ScanConfig sc;
-        sc.threshold = config->threshold; sc.avg_threshold = config->avg_threshold; sc.min_scores = (int)config->min_scores;
-        sc.eager = config->eager ? 1 : 0; sc.max_len = td.max_len; sc.avg_enabled = do_avg ? 1 : 0;
+        ScanConfig sc = scan_config(*config, td.max_len, do_avg);
         sc.stream_base = gather.stream_base;
-        float *dv = nullptr;
-        if (config->vad_mode != RP_VAD_NONE) {
-            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
-            dv = c->ws_vad.as<float>();
-            if (!hip_ok(launch_vad_value(c->stream, dm, S * nf, td.K, dv), "vad_value_kernel")) return -1;
-        }
-        c->time_begin(kKernelScan);
-        ok = hip_ok(launch_scan(c->stream, dg, da, dv, vad_mode_value(config->vad_mode), S, nf, sc, dd, dn, max_det, q.hot), "scan_kernel");
-        c->time_end();
-        if (!ok) return -1;
+        if (!detect_scan(c, *config, f.dm, S, nf, td.K, sc, dg, da, q.hot, nullptr, f.dd, nullptr, f.dn, max_det)) return -1;
         if (gather.on) {
             // final result gather: this shard's block into the gathered arrays -- device to host, or a peer
             // copy to the gathering device (xGMI between the GPUs of a node)
@@ -592,15 +639,15 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
             int32_t *gn = n_det + gather.stream_base;
             const size_t bd = S * (size_t)max_det * sizeof(BatchDetection), bn = S * sizeof(int32_t);
             if (gather.host) {
-                if (!hip_ok(hipMemcpyAsync(gd, dd, bd, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(gather)") ||
-                    !hip_ok(hipMemcpyAsync(gn, dn, bn, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(gather)")) return -1;
+                if (!hip_ok(hipMemcpyAsync(gd, f.dd, bd, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(gather)") ||
+                    !hip_ok(hipMemcpyAsync(gn, f.dn, bn, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(gather)")) return -1;
             } else {
-                if (!hip_ok(hipMemcpyPeerAsync(gd, gather.device, dd, c->device, bd, c->stream), "hipMemcpyPeerAsync(gather)") ||
-                    !hip_ok(hipMemcpyPeerAsync(gn, gather.device, dn, c->device, bn, c->stream), "hipMemcpyPeerAsync(gather)")) return -1;
+                if (!hip_ok(hipMemcpyPeerAsync(gd, gather.device, f.dd, c->device, bd, c->stream), "hipMemcpyPeerAsync(gather)") ||
+                    !hip_ok(hipMemcpyPeerAsync(gn, gather.device, f.dn, c->device, bn, c->stream), "hipMemcpyPeerAsync(gather)")) return -1;
             }
             return hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
         }
-        if (!sg.back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) || !sg.back(n_det, dn, S * sizeof(int32_t))) return -1;
+        if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
         if (sg.host && scores && !sg.back(scores, ds, rows * td.T * sizeof(float))) return -1;
         if (sg.host && agg && !sg.back(agg, dg, rows * sizeof(float))) return -1;
         return sg.finish() ? 0 : -1;
@@ -617,7 +664,7 @@ int rp_batch_detect_ingest(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, s
     return guarded([&]() -> int {
         if (!ctx || !t) { set_last_error("null handle"); return -1; }
         if (!config || (S && (!pcm || !det || !n_det))) { set_last_error("null argument"); return -1; }
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
+        if (!sample_format_ok(fmt)) return -1;
         if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
@@ -745,35 +792,22 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         if (n_wakewords < 1 || n_wakewords > (size_t)kScanMaxWakewords) { set_last_error("rp_batch_detect_multi: 1..8 wakewords"); return -1; }
-        if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
         const int K = t[0]->impl->dev.K;
         int max_len = 0;
+        size_t maxT = 1;
         for (size_t j = 0; j < n_wakewords; ++j) {
             const TemplatesDev &td = t[j]->impl->dev;
             if (td.K != K) { set_last_error("Usage of wakewords with different mfcc size is not supported, ignoring wakeword"); return -1; }
             max_len = std::max(max_len, td.max_len);  // on_wakeword_change, src/detector.rs:328-334: max over the wakewords' frame sizes
+            maxT = std::max<size_t>(maxT, (size_t)td.T);
         }
-        const MfccTablesDev *tb = c->tables_for(K);
-        if (!tb) return -1;
-        const size_t nf = rp_mfcc_num_frames(n_samples);
-        const size_t n_win = nf >= (size_t)max_len ? nf - max_len + 1 : 0, rows = S * n_win;
         Staged sg(c);
-        const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
-        BatchDetection *dd = static_cast<BatchDetection *>(sg.out(det, S * (size_t)max_det * sizeof(BatchDetection), c->stage_out));
-        int32_t *dn = static_cast<int32_t *>(sg.out(n_det, S * sizeof(int32_t), c->stage_out2));
+        DetectFront f;
+        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, K, max_len, det, n_det, max_det, &f)) return -1;
+        const size_t nf = f.nf, n_win = f.n_win, rows = f.rows;
         int32_t *dw = det_wakeword ? static_cast<int32_t *>(sg.out(det_wakeword, S * (size_t)max_det * sizeof(int32_t), c->stage_out3)) : nullptr;
-        if (S && (!dp || !dd || !dn)) return -1;
-        if (!c->ws_mfcc.reserve(S * nf * K * sizeof(float) + 64 * K * sizeof(float))) return -1;
-        float *dm = c->ws_mfcc.as<float>();
-        c->time_begin(kKernelMfcc);
-        bool ok = hip_ok(launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, nf, nf, dm), "mfcc_kernel");
-        c->time_end();
-        if (!ok) return -1;
         ScanWakewords ww{};
         ww.n = (int)n_wakewords;
-        size_t maxT = 1;
-        for (size_t j = 0; j < n_wakewords; ++j) maxT = std::max<size_t>(maxT, (size_t)t[j]->impl->dev.T);
         // one shared per-template score buffer, per wakeword its aggregate / avg rows
         if (!c->ws_scores.reserve(rows * maxT * sizeof(float) + 16) || !c->ws_agg.reserve(n_wakewords * rows * sizeof(float) + 16) ||
             !c->ws_avg.reserve(n_wakewords * rows * sizeof(float) + 16)) return -1;
@@ -786,7 +820,7 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
             float *dg = c->ws_agg.as<float>() + j * rows, *da = do_avg ? c->ws_avg.as<float>() + j * rows : nullptr;
             if (n_win) {
                 DtwScore q;
-                q.t = &td; q.mfcc = dm; q.S = S; q.frame_pitch = nf; q.n_win = n_win; q.band = config->band_size; q.score_ref = config->score_ref;
+                q.t = &td; q.mfcc = f.dm; q.S = S; q.frame_pitch = nf; q.n_win = n_win; q.band = config->band_size; q.score_ref = config->score_ref;
                 q.with_avg = do_avg; q.detect_only = !(c->flags & RP_CTX_FULL_SCORES);   // this entry point has no per-window outputs
                 q.avg_threshold = athr; q.threshold = thr; q.score_mode = (int)config->score_mode;
                 q.scores = ds; q.avg = da; q.agg = dg;
@@ -794,22 +828,9 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
             }
             ww.agg[j] = dg; ww.avg[j] = da; ww.threshold[j] = thr; ww.avg_threshold[j] = athr;
         }
-        ScanConfig sc;
-        sc.threshold = config->threshold; sc.avg_threshold = config->avg_threshold; sc.min_scores = (int)config->min_scores;
-        sc.eager = config->eager ? 1 : 0; sc.max_len = max_len; sc.avg_enabled = 0;
-        float *dv = nullptr;
-        if (config->vad_mode != RP_VAD_NONE) {
-            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
-            dv = c->ws_vad.as<float>();
-            if (!hip_ok(launch_vad_value(c->stream, dm, S * nf, K, dv), "vad_value_kernel")) return -1;
-        }
-        c->time_begin(kKernelScan);
-        ok = hip_ok(launch_scan_multi(c->stream, ww, dv, vad_mode_value(config->vad_mode), S, nf, sc, dd, dw, dn, max_det), "scan_kernel");
-        c->time_end();
-        if (!ok) return -1;
-        if (!sg.back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) || !sg.back(n_det, dn, S * sizeof(int32_t))) return -1;
-        if (dw && !sg.back(det_wakeword, dw, S * (size_t)max_det * sizeof(int32_t))) return -1;
-        return sg.finish() ? 0 : -1;
+        if (!detect_scan(c, *config, f.dm, S, nf, K, scan_config(*config, max_len, false), nullptr, nullptr, nullptr, &ww, f.dd, dw, f.dn, max_det))
+            return -1;
+        return sg.back_detections(S, max_det, det, f.dd, n_det, f.dn, det_wakeword, dw) && sg.finish() ? 0 : -1;
     });
 }
 
@@ -830,7 +851,7 @@ int rp_resample_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, int ch
         if (!ctx) { set_last_error("null handle"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
+        if (!sample_format_ok(fmt)) return -1;
         if (channels < 1) { set_last_error("Unsupported channel count"); return -1; }
         if (pcm_stride < n_samples * (size_t)channels) { set_last_error("pcm_stride smaller than n_samples * channels"); return -1; }
         const Resampler *rs = c->resampler_for(sample_rate);
@@ -842,20 +863,16 @@ int rp_resample_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, int ch
         const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
         float *dout = static_cast<float *>(sg.out(out, S * out_stride * sizeof(float), c->stage_out));
         if (!dp || !dout) return -1;
-        bool ok;
         if (resample_reads_in_place(rs->dev, dp, (int)fmt, pcm_stride, dout, out_stride)) {
-            c->time_begin(kKernelResample);
-            ok = hip_ok(launch_resample_in_place(c->stream, rs->dev, dp, (int)fmt, channels, pcm_stride, nullptr, nullptr, S, n_chunks, dout, out_stride), "resample48_fft_kernel");
-            c->time_end();
+            if (!timed(c, kKernelResample, "resample48_fft_kernel", [&] {
+                    return launch_resample_in_place(c->stream, rs->dev, dp, (int)fmt, channels, pcm_stride, nullptr, nullptr, S, n_chunks, dout, out_stride); }))
+                return -1;
         } else {
             if (!c->ws_resample.reserve(S * (1 + n_chunks) * (size_t)rs->dev.fi * sizeof(float) + 64)) return -1;
             float *xs = c->ws_resample.as<float>();
             if (!hip_ok(launch_resample_stage(c->stream, dp, (int)fmt, channels, S, n_chunks, rs->dev.fi, pcm_stride, nullptr, xs), "resample_stage_kernel")) return -1;
-            c->time_begin(kKernelResample);
-            ok = hip_ok(launch_resample(c->stream, rs->dev, xs, S, n_chunks, dout, out_stride), "resample kernel");
-            c->time_end();
+            if (!timed(c, kKernelResample, "resample kernel", [&] { return launch_resample(c->stream, rs->dev, xs, S, n_chunks, dout, out_stride); })) return -1;
         }
-        if (!ok) return -1;
         if (!sg.back(out, dout, S * out_stride * sizeof(float)) || !sg.finish()) return -1;
         return 0;
     });
@@ -953,45 +970,44 @@ int rp_stream_batch_reset(rp_stream_batch *b, long long stream) {
     });
 }
 
-static int stream_batch_process_impl(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
-                                     rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, int32_t *det_wakeword,
-                                     int32_t *det_label, bool *state_touched);
 static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float *now, size_t fill, size_t n_new, BatchDetection *dd,
                                     int32_t *dn, int max_det, int32_t *det_wakeword, int32_t *det_label);
 
-int rp_stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
-                            rp_batch_detection *det, int32_t *n_det, int max_det, float *agg) {
-    if (!b) { set_last_error("null handle"); return -1; }
-    if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
-    // The call advances device-resident state launch by launch (resampler tail, history chunk, MFCC rows, scan state);
-    // a failure after the first such step cannot be rolled back, so the batch refuses further work instead of pairing
-    // the wrong history with later chunks.
-    bool touched = false;
-    const int r = stream_batch_process_impl(b, pcm, fmt, n_chunks, pcm_stride, det, n_det, max_det, agg, nullptr, nullptr, &touched);
-    if (r != 0 && touched) b->poisoned = true;
-    return r;
+// The live tail: VAD values of this call's n_new frames per stream (from `frames`, rows b->cap frames apart) when vad_mode is on, then
+// the timed scan that carries every stream's state machine on -- launch_scan_stream over one reference's agg / avg (sw == nullptr), else
+// launch_scan_stream_multi over `sw` (dw / dl: each detection's wakeword and label)
+static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, const ScanWakewords *sw, const float *dg, const float *da,
+                      BatchDetection *dd, int32_t *dw, int32_t *dl, int32_t *dn, int max_det) {
+    Ctx *c = b->c;
+    float *dv = nullptr;
+    if (b->cfg.vad_mode != RP_VAD_NONE) {
+        dv = b->vad.as<float>();
+        if (!hip_ok(launch_vad_value_rows(c->stream, frames, b->S, n_new, b->cap, b->K, dv), "vad_value_kernel")) return false;
+    }
+    const ScanConfig sc = scan_config(b->cfg, b->max_len, da != nullptr, (int)b->fpf());
+    const float vm = vad_mode_value(b->cfg.vad_mode);
+    const long long f0 = (long long)b->fpf() * (long long)b->chunks_seen - 3;
+    return timed(c, kKernelScan, "scan_stream_kernel", [&] {
+        return sw ? launch_scan_stream_multi(c->stream, *sw, dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det)
+                  : launch_scan_stream(c->stream, dg, da, dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dn, max_det);
+    });
 }
 
-int rp_stream_batch_process_multi(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
-                                  rp_batch_detection *det, int32_t *det_wakeword, int32_t *det_label, int32_t *n_det, int max_det) {
+// Both live entry points.  A call advances device-resident state launch by launch (resampler tail, history chunk, MFCC rows, scan
+// state); a failure after the first such step cannot be rolled back, so the batch refuses further work instead of pairing the wrong
+// history with later chunks.
+static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
+                                rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, int32_t *det_wakeword, int32_t *det_label) {
     if (!b) { set_last_error("null handle"); return -1; }
     if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
     bool touched = false;
-    const int r = stream_batch_process_impl(b, pcm, fmt, n_chunks, pcm_stride, det, n_det, max_det, nullptr, det_wakeword, det_label, &touched);
-    if (r != 0 && touched) b->poisoned = true;
-    return r;
-}
-
-static int stream_batch_process_impl(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
-                                     rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, int32_t *det_wakeword,
-                                     int32_t *det_label, bool *state_touched) {
-    return guarded([&]() -> int {
+    const int r = guarded([&]() -> int {
         Ctx *c = b->c;
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         if (n_chunks == 0 || n_chunks > b->max_chunks) { set_last_error("rp_stream_batch_process: n_chunks out of range"); return -1; }
         const size_t in_chunk = b->in_len * (size_t)b->channels;
         if (pcm_stride < n_chunks * in_chunk) { set_last_error("pcm_stride smaller than n_chunks * samples per chunk"); return -1; }
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
+        if (!sample_format_ok(fmt)) return -1;
         const bool multi = !b->ww.empty();
         if (multi && agg) { set_last_error("rp_stream_batch_process: a batch of several wakewords has no single aggregate per window"); return -1; }
         static const TemplatesDev no_templates{};
@@ -1011,7 +1027,7 @@ static int stream_batch_process_impl(rp_stream_batch *b, const void *pcm, rp_sam
         if (!dp || !dd || !dn) { if (!pcm || !det || !n_det) set_last_error("null argument"); return -1; }
         const float *hp_old = b->pcm[b->pcur].as<float>();
         float *hp = b->pcm[b->pcur ^ 1].as<float>();
-        *state_touched = true;  // from here on every launch moves persistent state
+        touched = true;  // from here on every launch moves persistent state
         // 16 kHz mono input is read where it lies: the MFCC kernel takes [history chunk | new chunks] from two buffers and
         // leaves the last chunk as the next call's history.  Other inputs are staged into one row per stream first.
         bool staged = false;
@@ -1020,18 +1036,14 @@ static int stream_batch_process_impl(rp_stream_batch *b, const void *pcm, rp_sam
             float *ro = b->rs_out.as<float>();
             float *pv = b->rs_prev[b->rs_cur].as<float>(), *pn = b->rs_prev[b->rs_cur ^ 1].as<float>();
             if (resample_reads_in_place(b->rs->dev, dp, (int)fmt, pcm_stride, ro, new_len)) {
-                c->time_begin(kKernelResample);
-                bool okr = hip_ok(launch_resample_in_place(c->stream, b->rs->dev, dp, (int)fmt, b->channels, pcm_stride, pv, pn, S, n_chunks, ro, new_len), "resample48_fft_kernel");
-                c->time_end();
-                if (!okr) return -1;
+                if (!timed(c, kKernelResample, "resample48_fft_kernel", [&] {
+                        return launch_resample_in_place(c->stream, b->rs->dev, dp, (int)fmt, b->channels, pcm_stride, pv, pn, S, n_chunks, ro, new_len); }))
+                    return -1;
             } else {
                 if (!b->rs_xs.reserve(S * (1 + b->max_chunks) * fi * sizeof(float) + 64)) return -1;
                 float *xs = b->rs_xs.as<float>();
                 if (!hip_ok(launch_resample_stage(c->stream, dp, (int)fmt, b->channels, S, n_chunks, (int)fi, pcm_stride, pv, xs), "resample_stage_kernel")) return -1;
-                c->time_begin(kKernelResample);
-                bool okr = hip_ok(launch_resample(c->stream, b->rs->dev, xs, S, n_chunks, ro, new_len), "resample kernel");
-                c->time_end();
-                if (!okr) return -1;
+                if (!timed(c, kKernelResample, "resample kernel", [&] { return launch_resample(c->stream, b->rs->dev, xs, S, n_chunks, ro, new_len); })) return -1;
                 if (!hip_ok(launch_carry_rows(c->stream, xs, S, (1 + n_chunks) * fi, n_chunks * fi, fi, pn, fi), "carry_rows_kernel")) return -1;
             }
             b->rs_cur ^= 1;
@@ -1049,7 +1061,6 @@ static int stream_batch_process_impl(rp_stream_batch *b, const void *pcm, rp_sam
         }
         float *now = b->mfcc[b->cur].as<float>();
         const size_t fill = b->fill;
-        bool ok = true;
         if (!staged) {
             c->time_begin(kKernelMfcc);
             hipError_t e = launch_mfcc_stream(c->stream, *tb, dp, (int)fmt, S, n_chunks, pcm_stride, hp_old + b->last_off, pcm_pitch, hp, pitch,
@@ -1065,59 +1076,55 @@ static int stream_batch_process_impl(rp_stream_batch *b, const void *pcm, rp_sam
         }
         if (staged) {
             b->pcur ^= 1; b->last_off = new_len;  // the last 480 samples of this call are the extractor history of the next
-            c->time_begin(kKernelMfcc);
-            ok = hip_ok(launch_mfcc(c->stream, *tb, hp, S, n_samples, pcm_pitch, 0, n_new, pitch, now + fill * td.K), "mfcc_kernel");
-            c->time_end();
-            if (!ok) return -1;
+            if (!timed(c, kKernelMfcc, "mfcc_kernel", [&] { return launch_mfcc(c->stream, *tb, hp, S, n_samples, pcm_pitch, 0, n_new, pitch, now + fill * td.K); }))
+                return -1;
         }
         b->fill += n_new;
         if (multi) {
             if (stream_batch_score_multi(b, sg, now, fill, n_new, dd, dn, max_det, det_wakeword, det_label) != 0) return -1;
-            b->chunks_seen += n_chunks;
-            if (!sg.back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) || !sg.back(n_det, dn, S * sizeof(int32_t))) return -1;
-            return sg.finish() ? 0 : -1;
+        } else {
+            float *ds = b->scores.as<float>(), *dg = b->agg.as<float>(), *da = do_avg ? b->avg.as<float>() : nullptr;
+            DtwScore q;
+            q.t = &td_one; q.mfcc = now; q.S = S; q.frame_pitch = pitch; q.first_win = fill - hist; q.n_win = n_new; q.band = b->cfg.band_size;
+            q.score_ref = b->cfg.score_ref; q.with_avg = do_avg;
+            q.detect_only = !agg && !(c->flags & RP_CTX_FULL_SCORES);   // unless the caller wants every window's aggregate
+            q.avg_threshold = b->cfg.avg_threshold; q.threshold = b->cfg.threshold; q.score_mode = (int)b->cfg.score_mode;
+            q.scores = ds; q.avg = da; q.agg = dg; q.gate_list = b->list.as<uint32_t>();
+            // (a single live stream with a handful of windows skips the gate's three passes: the batch kernels score it when the matrix-core
+            // kernel serves its templates (a stream's bits must not depend on the batch it is in), else one wave per DTW)
+            q.gate_one_stream = false; q.fuse_max = true;
+            if (!dtw_score(*c, q)) return -1;
+            if (!live_scan(b, now + fill * td.K, n_new, nullptr, dg, da, dd, nullptr, nullptr, dn, max_det)) return -1;
         }
-        float *ds = b->scores.as<float>(), *dg = b->agg.as<float>(), *da = do_avg ? b->avg.as<float>() : nullptr;
-        DtwScore q;
-        q.t = &td_one; q.mfcc = now; q.S = S; q.frame_pitch = pitch; q.first_win = fill - hist; q.n_win = n_new; q.band = b->cfg.band_size;
-        q.score_ref = b->cfg.score_ref; q.with_avg = do_avg;
-        q.detect_only = !agg && !(c->flags & RP_CTX_FULL_SCORES);   // unless the caller wants every window's aggregate
-        q.avg_threshold = b->cfg.avg_threshold; q.threshold = b->cfg.threshold; q.score_mode = (int)b->cfg.score_mode;
-        q.scores = ds; q.avg = da; q.agg = dg; q.gate_list = b->list.as<uint32_t>();
-        // (a single live stream with a handful of windows skips the gate's three passes: the batch kernels score it when the matrix-core
-        // kernel serves its templates (a stream's bits must not depend on the batch it is in), else one wave per DTW)
-        q.gate_one_stream = false; q.fuse_max = true;
-        if (!dtw_score(*c, q)) return -1;
-        float *dv = nullptr;
-        if (b->cfg.vad_mode != RP_VAD_NONE) {
-            dv = b->vad.as<float>();
-        }
-        ScanConfig sc;
-        sc.threshold = b->cfg.threshold; sc.avg_threshold = b->cfg.avg_threshold; sc.min_scores = (int)b->cfg.min_scores;
-        sc.eager = b->cfg.eager ? 1 : 0; sc.max_len = td.max_len; sc.avg_enabled = do_avg ? 1 : 0; sc.fpf = (int)b->fpf();
-        if (dv && !hip_ok(launch_vad_value_rows(c->stream, now + fill * td.K, S, n_new, pitch, td.K, dv), "vad_value_kernel")) return -1;
-        c->time_begin(kKernelScan);
-        ok = hip_ok(launch_scan_stream(c->stream, dg, da, dv, vad_mode_value(b->cfg.vad_mode), S, (long long)b->fpf() * (long long)b->chunks_seen - 3, (int)n_new,
-                                       sc, b->state.p, dd, dn, max_det), "scan_stream_kernel");
-        c->time_end();
-        if (!ok) return -1;
         b->chunks_seen += n_chunks;
-        if (!sg.back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) || !sg.back(n_det, dn, S * sizeof(int32_t))) return -1;
-        if (det_wakeword || det_label) {   // one wakeword reference: wakeword 0, no label
+        if (!sg.back_detections(S, max_det, det, dd, n_det, dn)) return -1;
+        if (!multi && (det_wakeword || det_label)) {   // one wakeword reference: wakeword 0, no label
             const size_t nb = S * (size_t)max_det * sizeof(int32_t);
             if (sg.host) { if (det_wakeword) std::memset(det_wakeword, 0, nb); if (det_label) std::memset(det_label, 0xff, nb); }
             else if ((det_wakeword && !hip_ok(hipMemsetAsync(det_wakeword, 0, nb, c->stream), "hipMemsetAsync")) ||
                      (det_label && !hip_ok(hipMemsetAsync(det_label, 0xff, nb, c->stream), "hipMemsetAsync"))) return -1;
         }
-        if (agg) {
-            if (sg.host) { if (!sg.back(agg, dg, rows * sizeof(float))) return -1; }
-            else if (!hip_ok(hipMemcpyAsync(agg, dg, rows * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync(D2D)")) return -1;
+        if (agg) {   // (one reference: a batch of several wakewords was refused above)
+            if (sg.host) { if (!sg.back(agg, b->agg.as<float>(), rows * sizeof(float))) return -1; }
+            else if (!hip_ok(hipMemcpyAsync(agg, b->agg.p, rows * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync(D2D)")) return -1;
         }
         return sg.finish() ? 0 : -1;
     });
+    if (r != 0 && touched) b->poisoned = true;
+    return r;
 }
 
-static hipError_t mlp_rows_mfma(Ctx *c, const Model &m, const float *dx, size_t B, int precision, float *out);
+int rp_stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
+                            rp_batch_detection *det, int32_t *n_det, int max_det, float *agg) {
+    return stream_batch_process(b, pcm, fmt, n_chunks, pcm_stride, det, n_det, max_det, agg, nullptr, nullptr);
+}
+int rp_stream_batch_process_multi(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
+                                  rp_batch_detection *det, int32_t *det_wakeword, int32_t *det_label, int32_t *n_det, int max_det) {
+    return stream_batch_process(b, pcm, fmt, n_chunks, pcm_stride, det, n_det, max_det, nullptr, det_wakeword, det_label);
+}
+
+static bool window_logits(Ctx *c, const Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
+                          float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live);
 
 // ---- live-stream batches that hold several wakewords and / or a wakeword model (src/detector.rs:304-346,433-447)
 int rp_stream_batch_new_multi(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword_spec *wakewords, int mfcc_size,
@@ -1153,7 +1160,7 @@ int rp_stream_batch_new_multi(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword
                 const int nl = (int)e->m->dims.size() - 1;
                 if (e->m->dims[0] % mfcc_size != 0) { set_last_error("Usage of wakewords with different mfcc size is not supported, ignoring wakeword"); return -1; }
                 if (w.none_index >= e->m->dims[nl]) { set_last_error("none_index out of range"); return -1; }
-                if (w.precision != RP_MLP_F32 && w.precision != RP_MLP_BF16 && w.precision != RP_MLP_F32_STRICT && w.precision != RP_MLP_F32_FAST) { set_last_error("unknown MLP precision"); return -1; }
+                if (!mlp_precision_ok(w.precision)) return -1;
                 if (!e->m->mfma_ok && w.precision == RP_MLP_BF16) { set_last_error("this layer-1 shape has no bf16 MFMA kernel"); return -1; }
                 e->none_index = w.none_index; e->precision = w.precision;
                 b->max_len = std::max(b->max_len, e->m->dims[0] / mfcc_size);
@@ -1177,7 +1184,6 @@ static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float 
     const bool detect_only = !(c->flags & RP_CTX_FULL_SCORES);
     ScanWakewords sw{};
     sw.n = (int)b->ww.size();
-    bool ok = true;
     for (size_t j = 0; j < b->ww.size(); ++j) {
         StreamWakeword &w = *b->ww[j];
         float *dg = w.agg.as<float>();
@@ -1195,35 +1201,12 @@ static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float 
             sw.agg[j] = dg; sw.avg[j] = da; sw.threshold[j] = w.threshold; sw.avg_threshold[j] = w.avg_threshold; sw.label[j] = nullptr;
         } else {
             const Model &m = *w.m;
-            const int nl_layers = (int)m.dims.size() - 1, L = m.dims[0] / K, n_labels = m.dims[nl_layers];
+            const int L = m.dims[0] / K, n_labels = m.dims.back();
             if (!b->logits.reserve(rows * (size_t)n_labels * sizeof(float) + 16)) return -1;
             float *dlog = b->logits.as<float>();
-            const float *first = now + (fill - hist) * K;   // window i of stream s starts at frame s * pitch + i from here
-            const float *wsum = (m.mfma_ok && K % 4 == 0) ? const_cast<Model &>(m).wsum_for(K) : nullptr;  // as rp_batch_detect_model
-            if (wsum) {
-                if (!b->mean.reserve(rows * (size_t)K * sizeof(float) + 16)) return -1;
-                float *dmean = b->mean.as<float>();
-                if (!hip_ok(launch_window_means(c->stream, first, S, pitch, n_new, L, K, dmean), "window_means_kernel")) return -1;
-                c->time_begin(kKernelMlp);
-                uint32_t *redo = c->mlp_redo(rows);
-                if (!redo) return -1;
-                ok = hip_ok(launch_mlp_mfma_windows(c->stream, m.dev, first, S, pitch, n_new, K, dmean, wsum, dlog, redo, pitch, w.precision == RP_MLP_F32_STRICT ? (int)kMlpStrictF32 : w.precision == RP_MLP_F32_FAST ? (int)kMlpF16x2 : (int)kMlpF32), "mlp_mfma_kernel");
-                c->time_end();
-                if (!ok) return -1;
-            } else {
-                int maxd = 0;
-                for (int d : m.dims) maxd = std::max(maxd, d);
-                if (!b->xrows.reserve(rows * (size_t)m.dims[0] * sizeof(float) + 64)) return -1;
-                if (!m.mfma_ok && !b->xs2.reserve(2 * rows * (size_t)maxd * sizeof(float) + 16)) return -1;
-                float *dx = b->xrows.as<float>();
-                if (!hip_ok(launch_normalize_windows_batch(c->stream, first, pitch, n_new, 0, rows, L, K, dx), "normalize_windows_kernel")) return -1;
-                c->time_begin(kKernelMlp);
-                if (m.mfma_ok) ok = hip_ok(mlp_rows_mfma(c, m, dx, rows, w.precision, dlog), "mlp_mfma_kernel");
-                else ok = hip_ok(launch_mlp(c->stream, dx, rows, nl_layers, m.dims.data(), m.W.data(), m.B.data(), b->xs2.as<float>(),
-                                            b->xs2.as<float>() + rows * (size_t)maxd, dlog), "mlp_layer_kernel");
-                c->time_end();
-                if (!ok) return -1;
-            }
+            // window i of stream s starts at frame s * pitch + i from the first frame the longest wakeword scores
+            if (!window_logits(c, m, now + (fill - hist) * K, S, pitch, n_new, L, K, w.precision, dlog, b->mean, b->xrows, b->xs2, true))
+                return -1;
             float *da = w.avg.as<float>();
             int32_t *dlab = w.label.as<int32_t>();
             if (!hip_ok(launch_nn_score(c->stream, dlog, rows, n_labels, w.none_index, b->cfg.score_ref * 10.f, w.avg_threshold != 0.f ? 1 : 0,
@@ -1232,22 +1215,10 @@ static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float 
             sw.threshold[j] = -1.f; sw.avg_threshold[j] = -1.f;  // the gates were applied by nn_score_kernel (>=, not >)
         }
     }
-    float *dv = nullptr;
-    if (b->cfg.vad_mode != RP_VAD_NONE) {
-        dv = b->vad.as<float>();
-        if (!hip_ok(launch_vad_value_rows(c->stream, now + fill * K, S, n_new, pitch, K, dv), "vad_value_kernel")) return -1;
-    }
-    ScanConfig sc;
-    sc.threshold = b->cfg.threshold; sc.avg_threshold = b->cfg.avg_threshold; sc.min_scores = (int)b->cfg.min_scores;
-    sc.eager = b->cfg.eager ? 1 : 0; sc.max_len = b->max_len; sc.avg_enabled = 0; sc.fpf = (int)b->fpf();
     int32_t *dw = det_wakeword ? static_cast<int32_t *>(sg.out(det_wakeword, S * (size_t)max_det * sizeof(int32_t), b->det_ww)) : nullptr;
     int32_t *dl = det_label ? static_cast<int32_t *>(sg.out(det_label, S * (size_t)max_det * sizeof(int32_t), b->det_label)) : nullptr;
     if ((det_wakeword && !dw) || (det_label && !dl)) return -1;
-    c->time_begin(kKernelScan);
-    ok = hip_ok(launch_scan_stream_multi(c->stream, sw, dv, vad_mode_value(b->cfg.vad_mode), S, (long long)b->fpf() * (long long)b->chunks_seen - 3,
-                                         (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det), "scan_stream_kernel");
-    c->time_end();
-    if (!ok) return -1;
+    if (!live_scan(b, now + fill * K, n_new, &sw, nullptr, nullptr, dd, dw, dl, dn, max_det)) return -1;
     if ((dw && !sg.back(det_wakeword, dw, S * (size_t)max_det * sizeof(int32_t))) || (dl && !sg.back(det_label, dl, S * (size_t)max_det * sizeof(int32_t)))) return -1;
     return 0;
 }
@@ -1309,82 +1280,75 @@ int rp_mlp_forward_batch(rp_ctx *ctx, const rp_model *model, const float *x, siz
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         const Model &m = *model->impl;
         const int nl = (int)m.dims.size() - 1;
-        if (precision != RP_MLP_F32 && precision != RP_MLP_BF16 && precision != RP_MLP_F32_STRICT && precision != RP_MLP_F32_FAST) { set_last_error("unknown MLP precision"); return -1; }
+        if (!mlp_precision_ok(precision)) return -1;
         Staged sg(c);
         const float *dx = static_cast<const float *>(sg.in(x, B * (size_t)m.dims[0] * 4, c->stage_in));
         float *dl = static_cast<float *>(sg.out(logits, B * (size_t)m.dims[nl] * 4, c->stage_out));
         if (B && (!dx || !dl)) return -1;
-        bool ok;
         if (m.mfma_ok) {
-            c->time_begin(kKernelMlp);
-            ok = hip_ok(mlp_rows_mfma(c, m, dx, B, precision, dl), "mlp_mfma_kernel");
-            c->time_end();
+            if (!timed(c, kKernelMlp, "mlp_mfma_kernel", [&] { return mlp_rows_mfma(c, m, dx, B, precision, dl); })) return -1;
         } else {
             if (precision == RP_MLP_BF16) { set_last_error("this layer-1 shape has no bf16 MFMA kernel"); return -1; }
-            int maxd = 0;
-            for (int d : m.dims) maxd = std::max(maxd, d);
+            const int maxd = widest_layer(m);
             if (!c->stage_out2.reserve(B * (size_t)maxd * 4) || !c->stage_out3.reserve(B * (size_t)maxd * 4)) return -1;
-            c->time_begin(kKernelMlp);
-            ok = hip_ok(launch_mlp(c->stream, dx, B, nl, m.dims.data(), m.W.data(), m.B.data(), c->stage_out2.as<float>(),
-                                   c->stage_out3.as<float>(), dl), "mlp_layer_kernel");
-            c->time_end();
+            if (!timed(c, kKernelMlp, "mlp_layer_kernel", [&] {
+                    return launch_mlp(c->stream, dx, B, nl, m.dims.data(), m.W.data(), m.B.data(), c->stage_out2.as<float>(), c->stage_out3.as<float>(), dl); }))
+                return -1;
         }
-        if (!ok) return -1;
         if (!sg.back(logits, dl, B * (size_t)m.dims[nl] * 4) || !sg.finish()) return -1;
         return 0;
     });
 }
 
-// Logits of every window of L frames of S streams' MFCC rows dm [S][nf][K] (WakewordNN::run_detection's forward, window by window,
-// src/wakewords/nn/wakeword_nn.rs:101-159): dlog [S * n_win][labels].  Shared by rp_batch_detect_model and rp_mlp_forward_windows.
-static bool window_logits(Ctx *c, const Model &m, const float *dm, size_t S, size_t nf, size_t n_win, int L, int K, int precision, float *dlog) {
+// Logits of every window of L frames of S streams' MFCC rows (WakewordNN::run_detection's forward, window by window,
+// src/wakewords/nn/wakeword_nn.rs:101-159): dlog [S * n_win][labels].  Window w of stream s starts at frame s * pitch + w from `first`.
+// The workspaces: `mean` for the window means of the in-place form, `xrows` for the normalised rows and `scratch` for launch_mlp.
+// live (live-stream batches): all rows in one slab, so a call makes one launch, and rp_ctx_last_mlp_kernel is left as it is by the
+// in-place form.  Shared by rp_batch_detect_model, rp_mlp_forward_windows and the live batches' model wakewords.
+static bool window_logits(Ctx *c, const Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
+                          float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live) {
     const size_t rows = S * n_win;
     const int nl_layers = (int)m.dims.size() - 1, n_labels = m.dims[nl_layers];
-    bool ok = true;
-    {
-        // (RP_MLP_BF16 only permits bf16 inputs: the in-place window kernel is f32 and faster than materialising rows)
-        const float *wsum = (m.mfma_ok && K % 4 == 0) ? const_cast<Model &>(m).wsum_for(K) : nullptr;
-        if (wsum) {
-            // windows read in place from the frame array, the window mean taken out after layer 1
-            if (!c->ws_gain.reserve(rows * (size_t)K * sizeof(float) + 16)) return false;
-            float *dmean = c->ws_gain.as<float>();
-            if (!hip_ok(launch_window_means(c->stream, dm, S, nf, n_win, L, K, dmean), "window_means_kernel")) return false;
-            c->time_begin(kKernelMlp);
-            uint32_t *redo = c->mlp_redo(rows);
-            if (!redo) return false;
-            ok = hip_ok(launch_mlp_mfma_windows(c->stream, m.dev, dm, S, nf, n_win, K, dmean, wsum, dlog, redo, 0, precision == RP_MLP_F32_STRICT ? (int)kMlpStrictF32 : precision == RP_MLP_F32_FAST ? (int)kMlpF16x2 : (int)kMlpF32), "mlp_mfma_kernel");
-            c->time_end();
-            if (!ok) return false;
-            c->last_mlp_kernel = precision == RP_MLP_F32_STRICT ? "mlp_mfma_kernel<f32 matrix instructions>, windows read in place"
-                                 : (precision != RP_MLP_F32_FAST && mlp_windows_supported(m.dev, n_win, K, true) == 1) ? "mlp_windows_kernel<bf16x3 splits>"
-                                 : (precision != RP_MLP_F32_FAST && mlp_windows_supported(m.dev, n_win, K, true) == 2) ? "mlp_windows_wide_kernel<bf16x3 splits>"
-                                 : precision != RP_MLP_F32_FAST ? "mlp_mfma_kernel<bf16x3 splits>, windows read in place"
-                                 : mlp_windows_supported(m.dev, n_win, K) == 1 ? "mlp_windows_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows"
-                                 : mlp_windows_supported(m.dev, n_win, K) == 2 ? "mlp_windows_wide_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows"
-                                 : "mlp_mfma_kernel<f16x2 splits>, windows read in place, + mlp_mfma_kernel<f32> on listed rows";
-        } else {
-            // windows are materialised slab by slab (a row is dims[0] floats): <= 4 GiB of rows at a time
-            const size_t row_bytes = (size_t)m.dims[0] * sizeof(float);
-            size_t slab = std::max<size_t>(1, ((size_t)4 << 30) / row_bytes);
-            if (slab > rows) slab = rows;
-            int maxd = 0;
-            for (int d : m.dims) maxd = std::max(maxd, d);
-            if (!c->ws_scores.reserve(slab * row_bytes + 64)) return false;
-            if (!m.mfma_ok && !c->ws_gain.reserve(2 * slab * (size_t)maxd * sizeof(float) + 16)) return false;
-            float *dx = c->ws_scores.as<float>();
-            for (size_t r0 = 0; r0 < rows; r0 += slab) {
-                const size_t nr = std::min(slab, rows - r0);
-                if (!hip_ok(launch_normalize_windows_batch(c->stream, dm, nf, n_win, r0, nr, L, K, dx), "normalize_windows_kernel")) return false;
-                c->time_begin(kKernelMlp);
-                if (m.mfma_ok) ok = hip_ok(mlp_rows_mfma(c, m, dx, nr, precision, dlog + r0 * n_labels), "mlp_mfma_kernel");
-                else ok = hip_ok(launch_mlp(c->stream, dx, nr, nl_layers, m.dims.data(), m.W.data(), m.B.data(), c->ws_gain.as<float>(),
-                                            c->ws_gain.as<float>() + slab * (size_t)maxd, dlog + r0 * n_labels), "mlp_layer_kernel");
-                c->time_end();
-                if (!ok) return false;
-            }
-        }
+    // (RP_MLP_BF16 only permits bf16 inputs: the in-place window kernel is f32 and faster than materialising rows)
+    const float *wsum = (m.mfma_ok && K % 4 == 0) ? const_cast<Model &>(m).wsum_for(K) : nullptr;
+    if (wsum) {
+        // windows read in place from the frame array, the window mean taken out after layer 1
+        if (!mean.reserve(rows * (size_t)K * sizeof(float) + 16)) return false;
+        float *dmean = mean.as<float>();
+        if (!hip_ok(launch_window_means(c->stream, first, S, pitch, n_win, L, K, dmean), "window_means_kernel")) return false;
+        c->time_begin(kKernelMlp);
+        uint32_t *redo = c->mlp_redo(rows);
+        if (!redo) return false;
+        const int wprec = precision == RP_MLP_F32_STRICT ? (int)kMlpStrictF32 : precision == RP_MLP_F32_FAST ? (int)kMlpF16x2 : (int)kMlpF32;
+        const bool ok = hip_ok(launch_mlp_mfma_windows(c->stream, m.dev, first, S, pitch, n_win, K, dmean, wsum, dlog, redo, pitch, wprec), "mlp_mfma_kernel");
+        c->time_end();
+        if (!ok || live) return ok;
+        c->last_mlp_kernel = precision == RP_MLP_F32_STRICT ? "mlp_mfma_kernel<f32 matrix instructions>, windows read in place"
+                             : (precision != RP_MLP_F32_FAST && mlp_windows_supported(m.dev, n_win, K, true) == 1) ? "mlp_windows_kernel<bf16x3 splits>"
+                             : (precision != RP_MLP_F32_FAST && mlp_windows_supported(m.dev, n_win, K, true) == 2) ? "mlp_windows_wide_kernel<bf16x3 splits>"
+                             : precision != RP_MLP_F32_FAST ? "mlp_mfma_kernel<bf16x3 splits>, windows read in place"
+                             : mlp_windows_supported(m.dev, n_win, K) == 1 ? "mlp_windows_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows"
+                             : mlp_windows_supported(m.dev, n_win, K) == 2 ? "mlp_windows_wide_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows"
+                             : "mlp_mfma_kernel<f16x2 splits>, windows read in place, + mlp_mfma_kernel<f32> on listed rows";
+        return true;
     }
-    return ok;
+    // windows are materialised slab by slab (a row is dims[0] floats): <= 4 GiB of rows at a time
+    const size_t row_bytes = (size_t)m.dims[0] * sizeof(float);
+    const size_t slab = live ? rows : std::min(rows, std::max<size_t>(1, ((size_t)4 << 30) / row_bytes));
+    const int maxd = widest_layer(m);
+    if (!xrows.reserve(slab * row_bytes + 64)) return false;
+    if (!m.mfma_ok && !scratch.reserve(2 * slab * (size_t)maxd * sizeof(float) + 16)) return false;
+    float *dx = xrows.as<float>();
+    for (size_t r0 = 0; r0 < rows; r0 += slab) {
+        const size_t nr = std::min(slab, rows - r0);
+        if (!hip_ok(launch_normalize_windows_batch(c->stream, first, pitch, n_win, r0, nr, L, K, dx), "normalize_windows_kernel")) return false;
+        if (!timed(c, kKernelMlp, m.mfma_ok ? "mlp_mfma_kernel" : "mlp_layer_kernel", [&] {
+                return m.mfma_ok ? mlp_rows_mfma(c, m, dx, nr, precision, dlog + r0 * n_labels)
+                                 : launch_mlp(c->stream, dx, nr, nl_layers, m.dims.data(), m.W.data(), m.B.data(), scratch.as<float>(),
+                                              scratch.as<float>() + slab * (size_t)maxd, dlog + r0 * n_labels); }))
+            return false;
+    }
+    return true;
 }
 
 int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc, size_t S, size_t n_frames, int mfcc_size, int precision,
@@ -1395,7 +1359,7 @@ int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         const Model &m = *model->impl;
         const int nl = (int)m.dims.size() - 1, K = mfcc_size;
-        if (precision != RP_MLP_F32 && precision != RP_MLP_BF16 && precision != RP_MLP_F32_STRICT && precision != RP_MLP_F32_FAST) { set_last_error("unknown MLP precision"); return -1; }
+        if (!mlp_precision_ok(precision)) return -1;
         if (K < 1 || m.dims[0] % K != 0) { set_last_error("Model input size does not match the mfcc size"); return -1; }
         const int L = m.dims[0] / K;
         const size_t n_win = n_frames >= (size_t)L ? n_frames - L + 1 : 0, rows = S * n_win;
@@ -1405,7 +1369,7 @@ int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc
         const float *dm = static_cast<const float *>(sg.in(mfcc, S * n_frames * (size_t)K * 4, c->stage_in));
         float *dl = static_cast<float *>(sg.out(logits, rows * (size_t)m.dims[nl] * 4, c->stage_out));
         if (!dm || !dl) return -1;
-        if (!window_logits(c, m, dm, S, n_frames, n_win, L, K, precision, dl)) return -1;
+        if (!window_logits(c, m, dm, S, n_frames, n_win, L, K, precision, dl, c->ws_gain, c->ws_scores, c->ws_gain, false)) return -1;
         if (!sg.back(logits, dl, rows * (size_t)m.dims[nl] * 4) || !sg.finish()) return -1;
         return 0;
     });
@@ -1419,35 +1383,22 @@ int rp_batch_detect_model(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
         if (!config || (S && (!pcm || !det || !n_det))) { set_last_error("null argument"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
-        if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return -1; }
-        if (precision != RP_MLP_F32 && precision != RP_MLP_BF16 && precision != RP_MLP_F32_STRICT && precision != RP_MLP_F32_FAST) { set_last_error("unknown MLP precision"); return -1; }
+        if (!mlp_precision_ok(precision)) return -1;
         const Model &m = *model->impl;
-        const int nl_layers = (int)m.dims.size() - 1, K = mfcc_size;
+        const int K = mfcc_size;
         if (K < 1 || m.dims[0] % K != 0) { set_last_error("Incorrect model layers"); return -1; }
-        const int L = m.dims[0] / K, n_labels = m.dims[nl_layers];
+        const int L = m.dims[0] / K, n_labels = m.dims.back();
         if (none_index >= n_labels) { set_last_error("none_index out of range"); return -1; }
         if (!m.mfma_ok && precision == RP_MLP_BF16) { set_last_error("this layer-1 shape has no bf16 MFMA kernel"); return -1; }
-        const MfccTablesDev *tb = c->tables_for(K);
-        if (!tb) return -1;
-        const size_t nf = rp_mfcc_num_frames(n_samples);
-        const size_t n_win = nf >= (size_t)L ? nf - L + 1 : 0, rows = S * n_win;
         Staged sg(c);
-        const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
-        BatchDetection *dd = static_cast<BatchDetection *>(sg.out(det, S * (size_t)max_det * sizeof(BatchDetection), c->stage_out));
-        int32_t *dn = static_cast<int32_t *>(sg.out(n_det, S * sizeof(int32_t), c->stage_out2));
+        DetectFront f;
+        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, K, L, det, n_det, max_det, &f)) return -1;
+        const size_t nf = f.nf, n_win = f.n_win, rows = f.rows;
         int32_t *dl = det_label ? static_cast<int32_t *>(sg.out(det_label, S * (size_t)max_det * sizeof(int32_t), c->stage_out3)) : nullptr;
-        if (S && (!dp || !dd || !dn)) return -1;
-        if (!c->ws_mfcc.reserve(S * nf * K * sizeof(float) + 64)) return -1;
-        float *dm = c->ws_mfcc.as<float>();
-        c->time_begin(kKernelMfcc);
-        bool ok = hip_ok(launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, nf, nf, dm), "mfcc_kernel");
-        c->time_end();
-        if (!ok) return -1;
         if (!c->ws_ring.reserve(rows * (size_t)n_labels * sizeof(float) + 16) || !c->ws_agg.reserve(rows * sizeof(float) + 16) ||
             !c->ws_avg.reserve(rows * sizeof(float) + 16) || !c->ws_rms.reserve(rows * sizeof(int32_t) + 16)) return -1;
         float *dlog = c->ws_ring.as<float>();
-        if (!window_logits(c, m, dm, S, nf, n_win, L, K, precision, dlog)) return -1;
+        if (!window_logits(c, m, f.dm, S, nf, n_win, L, K, precision, dlog, c->ws_gain, c->ws_scores, c->ws_gain, false)) return -1;
         float *dg = c->ws_agg.as<float>(), *da = c->ws_avg.as<float>();
         int32_t *dlab = c->ws_rms.as<int32_t>();
         // nn_score_kernel also tells the scan which streams have a window that passed (a flag per stream, like the aggregate pass of
@@ -1462,22 +1413,9 @@ int rp_batch_detect_model(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
         ScanWakewords ww{};
         ww.n = 1; ww.agg[0] = dg; ww.avg[0] = da; ww.label[0] = dlab; ww.hot = hot;
         ww.threshold[0] = -1.f; ww.avg_threshold[0] = -1.f;  // the gates were applied by nn_score_kernel (>=, not >)
-        ScanConfig sc;
-        sc.threshold = config->threshold; sc.avg_threshold = config->avg_threshold; sc.min_scores = (int)config->min_scores;
-        sc.eager = config->eager ? 1 : 0; sc.max_len = L; sc.avg_enabled = 0;
-        float *dv = nullptr;
-        if (config->vad_mode != RP_VAD_NONE) {
-            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
-            dv = c->ws_vad.as<float>();
-            if (!hip_ok(launch_vad_value(c->stream, dm, S * nf, K, dv), "vad_value_kernel")) return -1;
-        }
-        c->time_begin(kKernelScan);
-        ok = hip_ok(launch_scan_multi(c->stream, ww, dv, vad_mode_value(config->vad_mode), S, nf, sc, dd, dl, dn, max_det), "scan_kernel");
-        c->time_end();
-        if (!ok) return -1;
-        if (!sg.back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) || !sg.back(n_det, dn, S * sizeof(int32_t))) return -1;
-        if (dl && !sg.back(det_label, dl, S * (size_t)max_det * sizeof(int32_t))) return -1;
-        return sg.finish() ? 0 : -1;
+        if (!detect_scan(c, *config, f.dm, S, nf, K, scan_config(*config, L, false), nullptr, nullptr, nullptr, &ww, f.dd, dl, f.dn, max_det))
+            return -1;
+        return sg.back_detections(S, max_det, det, f.dd, n_det, f.dn, det_label, dl) && sg.finish() ? 0 : -1;
     });
 }
 
