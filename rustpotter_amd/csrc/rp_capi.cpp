@@ -25,7 +25,7 @@ struct rp_model { std::unique_ptr<Model> impl; };
 // one wakeword of a live-stream batch that holds several (rp_stream_batch_new_multi): a reference or a model
 struct StreamWakeword {
     const Templates *t = nullptr;
-    const Model *m = nullptr;
+    Model *m = nullptr;
     int none_index = -1, precision = 0;
     float threshold = 0.f, avg_threshold = 0.f;   // the wakeword's own values (the config's where it has none)
     DevBuf agg, avg, label;                       // [S][frames per call] of this wakeword
@@ -1123,7 +1123,7 @@ int rp_stream_batch_process_multi(rp_stream_batch *b, const void *pcm, rp_sample
     return stream_batch_process(b, pcm, fmt, n_chunks, pcm_stride, det, n_det, max_det, nullptr, det_wakeword, det_label);
 }
 
-static bool window_logits(Ctx *c, const Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
+static bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
                           float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live);
 
 // ---- live-stream batches that hold several wakewords and / or a wakeword model (src/detector.rs:304-346,433-447)
@@ -1200,7 +1200,7 @@ static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float 
             if (!dtw_score(*c, q)) return -1;
             sw.agg[j] = dg; sw.avg[j] = da; sw.threshold[j] = w.threshold; sw.avg_threshold[j] = w.avg_threshold; sw.label[j] = nullptr;
         } else {
-            const Model &m = *w.m;
+            Model &m = *w.m;
             const int L = m.dims[0] / K, n_labels = m.dims.back();
             if (!b->logits.reserve(rows * (size_t)n_labels * sizeof(float) + 16)) return -1;
             float *dlog = b->logits.as<float>();
@@ -1238,63 +1238,27 @@ int rp_model_new(rp_ctx *ctx, int n_layers, const int *dims, const float *const 
 }
 void rp_model_free(rp_model *m) { delete m; }
 
-// Dense rows through layer 1 on the matrix cores: the line-streaming kernel (rp_mlp_stream.hip), where the pass is bound by the HBM
-// stream (bf16 inputs: 0.132 against 0.155 ms at BASELINE config C5; f32 callers: its f16 two-way split form).  With the f32 matrix
-// instructions themselves the f32 matrix rate binds and the register-fragment kernel's 24 waves per CU overlap better (0.198 against
-// 0.207 ms): RP_MLP_STREAM=0 forces that kernel, RP_MLP_STREAM=2 the streaming kernel in the caller's own precision (benchmarks, tests).
-// RP_MLP_STREAM (a tuning knob of benchmarks and tests, not an arithmetic switch -- the arithmetic is the call's `precision`): 0 = the
-// register-fragment kernel for every shape, 2 = the streaming kernel with the f32 matrix instructions for RP_MLP_F32_STRICT too.
-static int mlp_internal_precision(int precision) {
-    return precision == RP_MLP_F32 ? (int)kMlpBf16x3 : precision == RP_MLP_F32_FAST ? (int)kMlpF16x2 : precision == RP_MLP_F32_STRICT ? (int)kMlpStrictF32 : (int)kMlpBf16;
-}
-static hipError_t mlp_rows_mfma(Ctx *c, const Model &m, const float *dx, size_t B, int precision, float *out) {
-    const char *e = std::getenv("RP_MLP_STREAM");
-    const int mode = e ? (e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1) : 1;
-    MlpStreamPlan plan;
-    // f32 callers (RP_MLP_F32): the streaming kernel with three-part bf16 splits of inputs and weights (kMlpBf16x3: exact operands, f32
-    // accumulate) runs at the HBM stream's rate like the bf16 form, where the f32 matrix rate bound both exact kernels (0.19 ms at C5)
-    uint32_t *redo = c->mlp_redo(B);
-    if (!redo) return hipErrorOutOfMemory;
-    if (precision == RP_MLP_F32_STRICT && mode != 2) {   // the f32 matrix instructions for every row: the register-fragment kernel overlaps them best
-        c->last_mlp_kernel = "mlp_mfma_kernel<f32 matrix instructions>";
-        return launch_mlp_mfma(c->stream, m.dev, dx, B, kMlpStrictF32, out, redo);
-    }
-    const int iprec = mlp_internal_precision(precision);
-    const int sprec = iprec == kMlpStrictF32 ? (int)kMlpF32 : iprec;   // (the stream kernel's kMlpF32 IS the f32 matrix instructions)
-    if (mode != 0 && const_cast<Model &>(m).stream_plan(dx, B, sprec, &plan)) {
-        c->last_mlp_kernel = sprec == kMlpBf16x3 ? "mlp_stream_kernel<bf16x3 splits>"
-                             : sprec == kMlpF16x2 ? "mlp_stream_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows"
-                             : sprec == kMlpBf16 ? "mlp_stream_kernel<bf16>" : "mlp_stream_kernel<f32 matrix instructions>";
-        return launch_mlp_stream(c->stream, m.dev, plan, dx, B, sprec, out, c->n_cu, redo);
-    }
-    c->last_mlp_kernel = precision == RP_MLP_BF16 ? "mlp_mfma_kernel<bf16>"
-                         : (precision == RP_MLP_F32 && m.dev.w1t) ? "mlp_mfma_kernel<bf16x3 splits>"
-                         : (precision == RP_MLP_F32_FAST && m.dev.w1s) ? "mlp_mfma_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows" : "mlp_mfma_kernel<f32 matrix instructions>";
-    return launch_mlp_mfma(c->stream, m.dev, dx, B, precision == RP_MLP_BF16 ? (int)kMlpBf16 : precision == RP_MLP_F32 ? (int)kMlpF32 : iprec, out, redo);
-}
-
 int rp_mlp_forward_batch(rp_ctx *ctx, const rp_model *model, const float *x, size_t B, int precision, float *logits) {
     return guarded([&]() -> int {
         if (!ctx || !model) { set_last_error("null handle"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        const Model &m = *model->impl;
+        Model &m = *model->impl;
         const int nl = (int)m.dims.size() - 1;
         if (!mlp_precision_ok(precision)) return -1;
         Staged sg(c);
         const float *dx = static_cast<const float *>(sg.in(x, B * (size_t)m.dims[0] * 4, c->stage_in));
         float *dl = static_cast<float *>(sg.out(logits, B * (size_t)m.dims[nl] * 4, c->stage_out));
         if (B && (!dx || !dl)) return -1;
-        if (m.mfma_ok) {
-            if (!timed(c, kKernelMlp, "mlp_mfma_kernel", [&] { return mlp_rows_mfma(c, m, dx, B, precision, dl); })) return -1;
-        } else {
+        MlpForward q;
+        q.m = &m; q.precision = precision; q.x = dx; q.B = B; q.out = dl;
+        if (!m.mfma_ok) {
             if (precision == RP_MLP_BF16) { set_last_error("this layer-1 shape has no bf16 MFMA kernel"); return -1; }
             const int maxd = widest_layer(m);
             if (!c->stage_out2.reserve(B * (size_t)maxd * 4) || !c->stage_out3.reserve(B * (size_t)maxd * 4)) return -1;
-            if (!timed(c, kKernelMlp, "mlp_layer_kernel", [&] {
-                    return launch_mlp(c->stream, dx, B, nl, m.dims.data(), m.W.data(), m.B.data(), c->stage_out2.as<float>(), c->stage_out3.as<float>(), dl); }))
-                return -1;
+            q.scratch[0] = c->stage_out2.as<float>(); q.scratch[1] = c->stage_out3.as<float>();
         }
+        if (!mlp_forward(*c, q)) return -1;
         if (!sg.back(logits, dl, B * (size_t)m.dims[nl] * 4) || !sg.finish()) return -1;
         return 0;
     });
@@ -1302,50 +1266,39 @@ int rp_mlp_forward_batch(rp_ctx *ctx, const rp_model *model, const float *x, siz
 
 // Logits of every window of L frames of S streams' MFCC rows (WakewordNN::run_detection's forward, window by window,
 // src/wakewords/nn/wakeword_nn.rs:101-159): dlog [S * n_win][labels].  Window w of stream s starts at frame s * pitch + w from `first`.
-// The workspaces: `mean` for the window means of the in-place form, `xrows` for the normalised rows and `scratch` for launch_mlp.
+// The workspaces: `mean` for the window means of the in-place form, `xrows` for the normalised rows and `scratch` for the per-layer kernel.
 // live (live-stream batches): all rows in one slab, so a call makes one launch, and rp_ctx_last_mlp_kernel is left as it is by the
 // in-place form.  Shared by rp_batch_detect_model, rp_mlp_forward_windows and the live batches' model wakewords.
-static bool window_logits(Ctx *c, const Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
+static bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
                           float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live) {
     const size_t rows = S * n_win;
-    const int nl_layers = (int)m.dims.size() - 1, n_labels = m.dims[nl_layers];
-    // (RP_MLP_BF16 only permits bf16 inputs: the in-place window kernel is f32 and faster than materialising rows)
-    const float *wsum = (m.mfma_ok && K % 4 == 0) ? const_cast<Model &>(m).wsum_for(K) : nullptr;
-    if (wsum) {
-        // windows read in place from the frame array, the window mean taken out after layer 1
+    const int n_labels = m.dims.back();
+    MlpForward q;
+    q.m = &m; q.precision = precision;
+    // windows read in place from the frame array, the window mean taken out after layer 1
+    q.wsum = (m.mfma_ok && K % 4 == 0) ? m.wsum_for(K) : nullptr;
+    if (q.wsum) {
         if (!mean.reserve(rows * (size_t)K * sizeof(float) + 16)) return false;
-        float *dmean = mean.as<float>();
-        if (!hip_ok(launch_window_means(c->stream, first, S, pitch, n_win, L, K, dmean), "window_means_kernel")) return false;
-        c->time_begin(kKernelMlp);
-        uint32_t *redo = c->mlp_redo(rows);
-        if (!redo) return false;
-        const int wprec = precision == RP_MLP_F32_STRICT ? (int)kMlpStrictF32 : precision == RP_MLP_F32_FAST ? (int)kMlpF16x2 : (int)kMlpF32;
-        const bool ok = hip_ok(launch_mlp_mfma_windows(c->stream, m.dev, first, S, pitch, n_win, K, dmean, wsum, dlog, redo, pitch, wprec), "mlp_mfma_kernel");
-        c->time_end();
-        if (!ok || live) return ok;
-        c->last_mlp_kernel = precision == RP_MLP_F32_STRICT ? "mlp_mfma_kernel<f32 matrix instructions>, windows read in place"
-                             : (precision != RP_MLP_F32_FAST && mlp_windows_supported(m.dev, n_win, K, true) == 1) ? "mlp_windows_kernel<bf16x3 splits>"
-                             : (precision != RP_MLP_F32_FAST && mlp_windows_supported(m.dev, n_win, K, true) == 2) ? "mlp_windows_wide_kernel<bf16x3 splits>"
-                             : precision != RP_MLP_F32_FAST ? "mlp_mfma_kernel<bf16x3 splits>, windows read in place"
-                             : mlp_windows_supported(m.dev, n_win, K) == 1 ? "mlp_windows_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows"
-                             : mlp_windows_supported(m.dev, n_win, K) == 2 ? "mlp_windows_wide_kernel<f16x2 splits> + mlp_mfma_kernel<f32> on listed rows"
-                             : "mlp_mfma_kernel<f16x2 splits>, windows read in place, + mlp_mfma_kernel<f32> on listed rows";
-        return true;
+        if (!hip_ok(launch_window_means(c->stream, first, S, pitch, n_win, L, K, mean.as<float>()), "window_means_kernel")) return false;
+        q.windows = true; q.x = first; q.S = S; q.n_win = n_win; q.frame_pitch = pitch; q.K = K; q.mean = mean.as<float>(); q.out = dlog;
+        q.report = !live;
+        return mlp_forward(*c, q);
     }
     // windows are materialised slab by slab (a row is dims[0] floats): <= 4 GiB of rows at a time
     const size_t row_bytes = (size_t)m.dims[0] * sizeof(float);
     const size_t slab = live ? rows : std::min(rows, std::max<size_t>(1, ((size_t)4 << 30) / row_bytes));
     const int maxd = widest_layer(m);
     if (!xrows.reserve(slab * row_bytes + 64)) return false;
-    if (!m.mfma_ok && !scratch.reserve(2 * slab * (size_t)maxd * sizeof(float) + 16)) return false;
-    float *dx = xrows.as<float>();
+    if (!m.mfma_ok) {
+        if (!scratch.reserve(2 * slab * (size_t)maxd * sizeof(float) + 16)) return false;
+        q.scratch[0] = scratch.as<float>(); q.scratch[1] = scratch.as<float>() + slab * (size_t)maxd;
+    }
+    q.x = xrows.as<float>();
     for (size_t r0 = 0; r0 < rows; r0 += slab) {
-        const size_t nr = std::min(slab, rows - r0);
-        if (!hip_ok(launch_normalize_windows_batch(c->stream, first, pitch, n_win, r0, nr, L, K, dx), "normalize_windows_kernel")) return false;
-        if (!timed(c, kKernelMlp, m.mfma_ok ? "mlp_mfma_kernel" : "mlp_layer_kernel", [&] {
-                return m.mfma_ok ? mlp_rows_mfma(c, m, dx, nr, precision, dlog + r0 * n_labels)
-                                 : launch_mlp(c->stream, dx, nr, nl_layers, m.dims.data(), m.W.data(), m.B.data(), scratch.as<float>(),
-                                              scratch.as<float>() + slab * (size_t)maxd, dlog + r0 * n_labels); }))
+        q.B = std::min(slab, rows - r0);
+        q.out = dlog + r0 * n_labels;
+        if (!hip_ok(launch_normalize_windows_batch(c->stream, first, pitch, n_win, r0, q.B, L, K, xrows.as<float>()), "normalize_windows_kernel") ||
+            !mlp_forward(*c, q))
             return false;
     }
     return true;
@@ -1357,7 +1310,7 @@ int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc
         if (!ctx || !model) { set_last_error("null handle"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        const Model &m = *model->impl;
+        Model &m = *model->impl;
         const int nl = (int)m.dims.size() - 1, K = mfcc_size;
         if (!mlp_precision_ok(precision)) return -1;
         if (K < 1 || m.dims[0] % K != 0) { set_last_error("Model input size does not match the mfcc size"); return -1; }
@@ -1384,7 +1337,7 @@ int rp_batch_detect_model(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         if (!mlp_precision_ok(precision)) return -1;
-        const Model &m = *model->impl;
+        Model &m = *model->impl;
         const int K = mfcc_size;
         if (K < 1 || m.dims[0] % K != 0) { set_last_error("Incorrect model layers"); return -1; }
         const int L = m.dims[0] / K, n_labels = m.dims.back();

@@ -845,7 +845,6 @@ const float *Model::wsum_for(int K) {
 // bf16, or two (one per half) in f32.  Zero past dims[0] and past dims[1].  The image does not depend on where the rows
 // start (the kernel shifts its reads instead), so it is built once per precision.
 bool Model::stream_plan(const float *x, size_t B, int precision, MlpStreamPlan *plan) {
-    if (!mfma_ok || (precision != kMlpF32 && precision != kMlpBf16 && precision != kMlpF16x2 && precision != kMlpBf16x3) || !mlp_stream_supported(dev, x, precision)) return false;
     const int in = dims[0], n1 = dims[1], nt = dev.nt;
     const int q0 = (int)((reinterpret_cast<uintptr_t>(x) >> 4) & 7);
     const int par = ((in / 4) % 8) != 0;  // in % 16 == 0: the row pitch is 0 or 4 chunks mod 8

@@ -464,12 +464,13 @@ int Rustpotter::process_audio(float *buf, size_t n, Detection *out) {
                 int maxd = 0; for (int d : w.dims) maxd = std::max(maxd, d);
                 if (!nn_x_.reserve(cnt * (size_t)w.dims[0] * 4) || !nn_s0_.reserve(cnt * (size_t)maxd * 4) || !nn_s1_.reserve(cnt * (size_t)maxd * 4)) return -1;
                 if (!hip_ok(launch_normalize_windows(st, hist, first_win, cnt, L, K, nn_x_.as<float>()), "normalize_windows_kernel")) return -1;
-                // exact-f32 path (f32-input MFMA == fmaf chain); bf16 is only offered on the batched operator
-                if (w.net->mfma_ok) {
-                    uint32_t *redo = ctx_->mlp_redo(cnt);
-                    if (!redo || !hip_ok(launch_mlp_mfma(st, w.net->dev, nn_x_.as<float>(), cnt, kMlpF32, res + w.off_logits, redo), "mlp_mfma_kernel")) return -1;
-                } else if (!hip_ok(launch_mlp(st, nn_x_.as<float>(), cnt, w.n_layers, w.dims.data(), w.net->W.data(), w.net->B.data(),
-                                              nn_s0_.as<float>(), nn_s1_.as<float>(), res + w.off_logits), "mlp kernel")) return -1;
+                // RP_MLP_F32 (three bf16 parts: exact operands, f32 accumulate) on mlp_mfma_kernel, never the streaming kernel; bf16 is only
+                // offered on the batched operator
+                MlpForward q;
+                q.m = w.net.get(); q.precision = RP_MLP_F32; q.x = nn_x_.as<float>(); q.B = cnt; q.out = res + w.off_logits;
+                q.scratch[0] = nn_s0_.as<float>(); q.scratch[1] = nn_s1_.as<float>();
+                q.allow_stream = false; q.report = false; q.timed = false;
+                if (!mlp_forward(*ctx_, q)) return -1;
             }
         }
     }

@@ -462,29 +462,18 @@ struct MlpDev {
     float *tail = nullptr; // layers 2..n: W [out][in] then b [out], concatenated
     int tail_floats = 0;
 };
-// kMlpF16x2: layer 1 at the matrix cores' f16 rate -- inputs and weights as f16 two-way splits
-// (x = x0 + x1, w = w0 + w1, 22 significant bits each; x0 w0 + x1 w0 + x0 w1, f32 accumulate: the dropped x1 w1 is 2^-22 of a product):
-// RP_MLP_F32_FAST callers (through round 5 what RP_MLP_F32 meant)
-// kMlpStrictF32: the f32 matrix instructions for every row (RP_MLP_F32_STRICT callers).  kMlpRedoF32 (internal): only
-// the second pass of kMlpF16x2 -- the rows listed in `redo` again with the f32 matrix instructions (behind launch_mlp_stream).
-// redo (Ctx::mlp_redo): [2 + B] words, redo[0] = rows listed, redo[1] = workgroups of the second pass done, both zero between calls;
-// a row is listed when one of its features is beyond the f16 range (|x| > 65504, or not finite): the split cannot hold it, the f32
-// instructions can -- rp_mlp_forward_batch never answers NaN for finite input.
-// kMlpBf16x3: f32-grade layer 1 at the matrix cores' bf16 rate -- inputs and weights as THREE bf16 parts each (exact), six of the nine partial
-// products, f32 accumulate: what RP_MLP_F32 callers get (round 6; kMlpF16x2, 22-bit operands, is RP_MLP_F32_FAST).  No range limit, no second pass.
-enum { kMlpF32 = 0, kMlpBf16 = 1, kMlpF16x2 = 2, kMlpStrictF32 = 3, kMlpRedoF32 = 4, kMlpBf16x3 = 5 };
-// A launcher that fails between the split pass and the pass over the listed rows must not leave rows of THIS call listed for the next one
-// (the next call would append behind them and run its second pass on stale indices): the two counter words go back to zero behind
-// whatever was queued, as dtw_abort does for the DTW words.  Returns the error it was given.
-inline hipError_t mlp_redo_abort(hipStream_t st, uint32_t *redo, hipError_t e) {
-    if (redo) (void)hipMemsetAsync(redo, 0, 2 * sizeof(uint32_t), st);
-    (void)hipGetLastError();
-    return e;
-}
-// Fused forward of all layers; layer 1 on the matrix cores (f32-input MFMA: bit-for-bit an fmaf
-// chain; or bf16 inputs with f32 accumulation), tail layers + ReLU per row in f32.
-hipError_t launch_mlp_mfma(hipStream_t st, const MlpDev &m, const float *x, size_t B, int precision, float *out, uint32_t *redo);
-bool mlp_mfma_fits(const MlpDev &m);   // the fused kernel's LDS fits a CU (else: the per-layer kernel)
+// Operand forms of layer 1 on the matrix cores, the PREC of mlp_mfma_kernel / mlp_stream_kernel (mlp_route maps RP_MLP_* onto them):
+// kMlpF32: the f32 matrix instructions (RP_MLP_F32_STRICT; also the second pass of kMlpF16x2, and RP_MLP_F32 on a model whose three-part
+// weight groups do not fit the LDS).  kMlpBf16: inputs rounded to bf16 (RP_MLP_BF16).
+// kMlpF16x2 (RP_MLP_F32_FAST): inputs and weights as f16 two-way splits (x = x0 + x1, w = w0 + w1, 22 significant bits each;
+// x0 w0 + x1 w0 + x0 w1, f32 accumulate: the dropped x1 w1 is 2^-22 of a product).  A row with a feature beyond the f16 range (|x| > 65504,
+// or not finite) is listed in redo (Ctx::mlp_redo: [2 + B] words, redo[0] = rows listed, redo[1] = workgroups of the second pass done, both
+// zero between calls) and computed again by a second pass with the f32 matrix instructions -- rp_mlp_forward_batch never answers NaN for
+// finite input.
+// kMlpBf16x3 (RP_MLP_F32): inputs and weights as THREE bf16 parts each (exact), six of the nine partial products, f32 accumulate.  No range
+// limit, no second pass.
+enum { kMlpF32 = 0, kMlpBf16 = 1, kMlpF16x2 = 2, kMlpBf16x3 = 5 };
+bool mlp_mfma_fits(const MlpDev &m);   // mlp_mfma_kernel's LDS fits a CU (else: the per-layer kernel)
 // The same forward for dense rows with the rows streamed through LDS by LDS-DMA in whole 128-byte lines (rp_mlp_stream.hip):
 // layer-1 widths <= 32, row pitch a multiple of 64 bytes, x 16-byte aligned (mlp_stream_supported).  The plan holds the
 // layer-1 weights in MFMA-fragment order and the line phases of the rows (Model::stream_plan).
@@ -495,21 +484,33 @@ struct MlpStreamPlan {
     int par = 0;                               // 1: even and odd rows differ in phase -- a workgroup takes rows of one parity
     int nbt = 0;                               // workgroup tiles: 128 rows (256-row span of one parity when par)
 };
-bool mlp_stream_supported(const MlpDev &m, const float *x, int precision = kMlpF32);
+bool mlp_stream_supported(const MlpDev &m, const float *x, int precision);
 hipError_t launch_mlp_stream(hipStream_t st, const MlpDev &m, const MlpStreamPlan &p, const float *x, size_t B, int precision, float *out,
-                             int n_cu, uint32_t *redo);
-// The rows are windows of L = dims[0]/K frames read IN PLACE from mfcc [S][n_frames][K] (a window's flattened features
-// are a contiguous slice of the frame array), row = s * n_win + w; the window mean (MfccNormalizer::normalize) is taken
-// out after layer 1: W.(f - mu) = W.f - sum_k mu[k] * wsum[o][k], wsum[o][k] = sum_i W[o][i*K + k].  f32 MFMA.
-// mean [S*n_win][K] from launch_window_means, wsum [16*nt][K].
+                             int n_cu, uint32_t *redo);   // the streaming pass alone (kMlpF16x2: mlp_forward runs the second pass)
+// The rows may also be windows of L = dims[0]/K frames read IN PLACE from mfcc [S][frame_pitch][K] (window w of stream s starts at frame
+// s * frame_pitch + w): the window mean (MfccNormalizer::normalize) is taken out after layer 1, W.(f - mu) = W.f - sum_k mu[k] * wsum[o][k],
+// wsum[o][k] = sum_i W[o][i*K + k] (Model::wsum_for); mean [S*n_win][K] from launch_window_means.
 hipError_t launch_window_means(hipStream_t st, const float *mfcc, size_t S, size_t n_frames, size_t n_win, int L, int K, float *mean);
-// frame_pitch (0 = n_win + L - 1, whole streams): frames between the rows of two streams -- live-stream batches keep their
-// windows in longer rows (window w of stream s starts at frame s * frame_pitch + w, counted from `mfcc`)
-int mlp_windows_supported(const MlpDev &m, size_t n_win, int K, bool three_part = false);   // 1: mlp_windows_kernel, 2: mlp_windows_wide_kernel takes the call (0: mlp_mfma_kernel, rows read in place)
-hipError_t launch_mlp_mfma_windows(hipStream_t st, const MlpDev &m, const float *mfcc, size_t S, size_t n_frames, size_t n_win, int K,
-                                   const float *mean, const float *wsum, float *out, uint32_t *redo, size_t frame_pitch = 0,
-                                   int precision = kMlpF32);   // kMlpF32 (three bf16 parts, rows read in place) / kMlpF16x2 (RP_MLP_F32_FAST: the
-                                                               // staged-frame kernels) / kMlpStrictF32
+
+// One wakeword-model forward.  The caller describes the call; mlp_route (rp_mlp.hip) decides which kernels run it, in which operand form.
+struct Model;
+struct MlpForward {
+    Model *m = nullptr;
+    int precision = 0;               // rp_mlp_precision
+    const float *x = nullptr;        // dense rows x [B][dims[0]], or with `windows` the frames: S x n_win windows read in place
+    size_t B = 0, S = 0, n_win = 0, frame_pitch = 0;
+    bool windows = false;
+    int K = 0;
+    const float *mean = nullptr, *wsum = nullptr;
+    float *out = nullptr;            // logits [rows][dims[n_layers]]
+    float *scratch[2] = {nullptr, nullptr};   // the per-layer kernel's intermediates, [rows][widest layer] each (no mfma_ok only)
+    // How the callers differ.  Each is kept as it was: harmonising them would change which kernels run.
+    bool allow_stream = true;        // dense rows may take mlp_stream_kernel (the single-stream handle never does)
+    bool report = true;              // set Ctx::last_mlp_kernel (live batches' in-place windows and the single-stream handle leave it)
+    bool timed = true;               // inside the context's kKernelMlp bracket (the single-stream handle times nothing)
+};
+// false with the error set (hip_ok): "mlp_mfma_kernel" or "mlp_layer_kernel"
+bool mlp_forward(Ctx &c, const MlpForward &q);
 
 // WakewordModelTrain (src/wakewords/nn/wakeword_model_train.rs:204-209): act[l] / dz[l] are [B][dims[l+1]] device buffers
 hipError_t launch_train_forward(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
@@ -525,7 +526,5 @@ hipError_t launch_normalize_windows_batch(hipStream_t st, const float *mfcc, siz
 hipError_t launch_nn_score(hipStream_t st, const float *logits, size_t n_rows, int n_labels, int none_index, float score_ref10,
                            int calc_avg, float threshold, float avg_threshold, float *agg, float *avg, int32_t *label,
                            uint32_t *hot = nullptr, size_t rows_per_stream = 0);  // hot: a flag per stream (zeroed by the caller) raised by every window that passed
-hipError_t launch_mlp(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
-                      float *const *Bv, float *scratch0, float *scratch1, float *out);
 
 }  // namespace rp

@@ -2,6 +2,7 @@
 // mlp_mfma_kernel on the matrix cores, normalize_windows_kernel) and training (wakeword_model_train.rs:204-209).
 // DESIGN.md §4.4.
 #include "rp_device.h"
+#include "rp_host.h"
 
 namespace rp {
 
@@ -118,8 +119,8 @@ hipError_t launch_nn_score(hipStream_t st, const float *logits, size_t n_rows, i
     return hipGetLastError();
 }
 
-hipError_t launch_mlp(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
-                      float *const *Bv, float *scratch0, float *scratch1, float *out) {
+static hipError_t launch_mlp(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
+                             float *const *Bv, float *scratch0, float *scratch1, float *out) {
     if (B == 0) return hipSuccess;
     const float *cur = x;
     float *bufs[2] = {scratch0, scratch1};
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(64 * kMlpWaves, 3) void mlp_mfma_kernel(
     int redo_list) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int N1P = 16 * NT;
-    // redo (rp_kernels.h, MlpRedo): kMlpF16x2 lists the rows that hold a feature beyond the f16 range (redo[0] = rows listed, from
+    // redo (rp_kernels.h, kMlpF16x2): kMlpF16x2 lists the rows that hold a feature beyond the f16 range (redo[0] = rows listed, from
     // redo[2] on their indices); redo_list != 0: this launch computes exactly those rows (the f32 matrix instructions) and the last
     // workgroup to leave puts redo[0] and redo[1] back to zero
     const uint32_t *rlist = nullptr;
@@ -308,7 +309,7 @@ __global__ __launch_bounds__(64 * kMlpWaves, 3) void mlp_mfma_kernel(
     size_t r = row0 + li;
     if (r >= B) r = B - 1;  // rows past the end recompute the last row; their results are dropped
     r = row_of(r);
-    // row_stride != 0: rows are overlapping windows read in place from the frame array (launch_mlp_mfma_windows)
+    // row_stride != 0: rows are overlapping windows read in place from the frame array (MlpForward::windows)
     const float *xr = row_stride ? x + r * row_stride + (r / rows_per_stream) * stream_skip : x + r * in;
     float rng = 0.f;   // kMlpF16x2: largest |feature| this lane has seen
 
@@ -579,94 +580,87 @@ __global__ __launch_bounds__(64 * kMlpWaves, 3) void mlp_mfma_kernel(
     }
 }
 
-template <int NT>
-static hipError_t launch_mlp_nt(hipStream_t st, const MlpDev &m, const float *x, size_t B, int precision, float *out, uint32_t *redo,
-                                size_t row_stride = 0, size_t rows_per_stream = 1, size_t stream_skip = 0, const float *mean = nullptr,
-                                const float *wsum = nullptr, int K = 0) {
-    const size_t rows_per_block = (size_t)kMlpWaves * kMlpRowsPerWave;
-    const size_t blocks = (B + rows_per_block - 1) / rows_per_block;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+// The route of one forward (mlp_route): decided once per call from the model, the request and the tuning variables; the launchers read it.
+// kind: mlp_layer_kernel per layer, mlp_mfma_kernel on dense rows, mlp_stream_kernel, mlp_windows_kernel, mlp_windows_wide_kernel,
+// mlp_mfma_kernel reading the windows in place
+enum MlpKind { kMlpLayers, kMlpRows, kMlpStream, kMlpWindows, kMlpWindowsWide, kMlpInPlace };
+struct MlpRoute {
+    MlpKind kind = kMlpLayers;
+    int prec = kMlpF32;          // the operand form (PREC; the window kernels' P3 = kMlpBf16x3)
+    bool redo = false;           // kMlpF16x2: the listed rows follow with mlp_mfma_kernel<NT, kMlpF32>
+    MlpStreamPlan plan;          // kMlpStream
+    // mlp_mfma_kernel (the call's kernel or its second pass): LDS bytes, the staged weight group(s) and an h2 row in floats
+    size_t lds = 0, wbuf = 0;
     int h2w = 1;
-    for (int l2 = 2; l2 < m.n_layers; ++l2) h2w = m.dims[l2] + 1 > h2w ? m.dims[l2] + 1 : h2w;
-    h2w |= 1;
+    // the window kernels: 32-window row tiles per workgroup (NT), 32-output tiles (NQ, the wide form), frame slots, workgroups per
+    // stream, LDS bytes
+    int tiles = 0, nq = 0, slots = 0;
+    size_t bps = 0, win_lds = 0;
+    std::string report;          // what ran (Ctx::last_mlp_kernel); empty for the per-layer kernel, which leaves it as it is
+};
+
+// LDS of mlp_mfma_kernel in form prec: the tail weights; the staged layer-1 weight group(s) -- 16 NT rows x the bf16 pitch, in floats, for
+// the two f16 planes of kMlpF16x2 (f32 and bf16 groups are smaller; the three bf16 planes of kMlpBf16x3 take half again as much), double
+// buffered at NT <= 2 -- which later hold h1; and h2 [waves][16][h2w]
+static size_t mlp_mfma_lds(const MlpDev &m, int prec, int *h2w, size_t *wbuf) {
     static_assert(mlp_wpitch_bf16() >= mlp_wpitch_f32(), "staged weight group");
-    // the caller's precision (rp_kernels.h): kMlpF32 = RP_MLP_F32 = f32-grade products on the bf16 matrix instruction (three exact parts per
-    // operand, kMlpBf16x3); kMlpF16x2 = RP_MLP_F32_FAST (two f16 parts, 22-bit, + the f32 pass on listed rows); kMlpStrictF32 = the f32 matrix
-    // instructions for every row
-    if (precision == kMlpStrictF32) precision = kMlpF32;
-    else if (precision == kMlpF32 && m.w1t) precision = kMlpBf16x3;
-    else if (precision == kMlpF16x2 && !m.w1s) precision = kMlpF32;
-    // staged weight group(s): 16 NT rows x the bf16 pitch, in floats, for the two f16 planes of kMlpF16x2 (f32 and bf16 groups are smaller);
-    // the three bf16 planes of kMlpBf16x3 take half again as much -- a model whose three-part groups do not fit the CU's LDS beside its tail
-    // layers (the widest ones) runs the f32 matrix instructions instead: exact either way
-    size_t wbuf = 0, lds = 0;
-    for (;;) {
-        wbuf = (size_t)(precision == kMlpBf16x3 ? 24 : 16) * NT * mlp_wpitch_bf16() * (NT <= 2 ? 2 : 1);
-        const size_t h1 = (size_t)kMlpWaves * kMlpRowsPerWave * (16 * NT + 1);
-        if (h1 > wbuf) wbuf = h1;
-        wbuf = (wbuf + 3) & ~(size_t)3;
-        lds = ((size_t)((m.tail_floats + 3) & ~3) + wbuf + (size_t)kMlpWaves * kMlpRowsPerWave * h2w) * sizeof(float);
-        if (lds <= 160 * 1024) break;
-        if (precision != kMlpBf16x3) return hipErrorInvalidValue;
-        precision = kMlpF32;
-    }
+    *h2w = 1;
+    for (int l2 = 2; l2 < m.n_layers; ++l2) *h2w = std::max(*h2w, m.dims[l2] + 1);
+    *h2w |= 1;
+    *wbuf = std::max((size_t)(prec == kMlpBf16x3 ? 24 : 16) * m.nt * mlp_wpitch_bf16() * (m.nt <= 2 ? 2 : 1),
+                     (size_t)kMlpWaves * kMlpRowsPerWave * (16 * m.nt + 1));
+    *wbuf = (*wbuf + 3) & ~(size_t)3;
+    return ((size_t)((m.tail_floats + 3) & ~3) + *wbuf + (size_t)kMlpWaves * kMlpRowsPerWave * *h2w) * sizeof(float);
+}
+
+// wide hidden layers do not fit the CU's 160 KB and take the per-layer kernel instead (Model::create)
+bool mlp_mfma_fits(const MlpDev &m) {
+    int h2w;
+    size_t wbuf;
+    return mlp_mfma_lds(m, kMlpF32, &h2w, &wbuf) <= 160 * 1024;
+}
+
+// mlp_mfma_kernel<NT, PREC> over B rows (in-place windows: row = s * n_win + w, K floats apart, a new stream skips the rest of its row);
+// redo_list: only the rows listed in redo
+template <int NT, int PREC>
+static hipError_t launch_mlp_pass(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, size_t B, const void *w1h,
+                                  uint32_t *redo, int redo_list) {
+    const size_t blocks = (B + kMlpWaves * kMlpRowsPerWave - 1) / (kMlpWaves * kMlpRowsPerWave);
+    hipLaunchKernelGGL((mlp_mfma_kernel<NT, PREC>), dim3((unsigned)blocks), dim3(64 * kMlpWaves), r.lds, st, q.x, B, m.dims[0], m.kpad, m.w1f,
+                       static_cast<const __bf16 *>(w1h), m.b1, m.tail, m.tail_floats, m.n_layers, m.dims[1], m.dims[2], m.dims[3], m.dims[4],
+                       r.h2w, (int)r.wbuf, q.out, q.windows ? (size_t)q.K : 0, q.windows ? q.n_win : 1,
+                       q.windows ? (q.frame_pitch - q.n_win) * q.K : 0, q.mean, q.wsum, q.K, redo, redo_list);
+    return hipGetLastError();
+}
+
+// the route's mlp_mfma_kernel passes: the call itself (dense rows, windows in place), then the rows its split form listed
+template <int NT>
+static hipError_t launch_mlp_nt(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, size_t B, uint32_t *redo) {
     if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_mfma_kernel<NT, kMlpBf16>), 160 * 1024); e != hipSuccess) return e;
     if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_mfma_kernel<NT, kMlpF32>), 160 * 1024); e != hipSuccess) return e;
     if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_mfma_kernel<NT, kMlpF16x2>), 160 * 1024); e != hipSuccess) return e;
     if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_mfma_kernel<NT, kMlpBf16x3>), 160 * 1024); e != hipSuccess) return e;
-    if (B > 0xffffffffULL) return hipErrorInvalidValue;
-    uint32_t *const no_redo = nullptr;
-    if (precision == kMlpF16x2 || precision == kMlpRedoF32) {
-        if (!redo) return hipErrorInvalidValue;
-        if (precision == kMlpF16x2) {
-            hipLaunchKernelGGL((mlp_mfma_kernel<NT, kMlpF16x2>), dim3((unsigned)blocks), dim3(64 * kMlpWaves), lds, st, x, B, m.dims[0],
-                               m.kpad, m.w1f, static_cast<const __bf16 *>(m.w1s), m.b1, m.tail, m.tail_floats, m.n_layers,
-                               m.dims[1], m.dims[2], m.dims[3], m.dims[4], h2w, (int)wbuf, out, row_stride, rows_per_stream, stream_skip, mean, wsum, K, redo, 0);
-            if (hipError_t e = hipGetLastError(); e != hipSuccess) return mlp_redo_abort(st, redo, e);
+    if (B > 0xffffffffULL || r.lds > 160 * 1024) return hipErrorInvalidValue;
+    hipError_t e = hipSuccess;
+    if (r.kind == kMlpRows || r.kind == kMlpInPlace) {
+        switch (r.prec) {
+        case kMlpBf16: e = launch_mlp_pass<NT, kMlpBf16>(st, m, r, q, B, m.w1h, nullptr, 0); break;
+        case kMlpF16x2: e = launch_mlp_pass<NT, kMlpF16x2>(st, m, r, q, B, m.w1s, redo, 0); break;
+        case kMlpBf16x3: e = launch_mlp_pass<NT, kMlpBf16x3>(st, m, r, q, B, m.w1t, nullptr, 0); break;
+        default: e = launch_mlp_pass<NT, kMlpF32>(st, m, r, q, B, m.w1h, nullptr, 0);
         }
-        // the rows the split form listed (a feature beyond the f16 range), again with the f32 matrix instructions: sized for every row,
-        // workgroups past the list's end leave at once
-        hipLaunchKernelGGL((mlp_mfma_kernel<NT, kMlpF32>), dim3((unsigned)blocks), dim3(64 * kMlpWaves), lds, st, x, B, m.dims[0],
-                           m.kpad, m.w1f, static_cast<const __bf16 *>(m.w1h), m.b1, m.tail, m.tail_floats, m.n_layers,
-                           m.dims[1], m.dims[2], m.dims[3], m.dims[4], h2w, (int)wbuf, out, row_stride, rows_per_stream, stream_skip, mean, wsum, K, redo, 1);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return mlp_redo_abort(st, redo, e);
-        return hipSuccess;
-    } else if (precision == kMlpBf16x3)
-        hipLaunchKernelGGL((mlp_mfma_kernel<NT, kMlpBf16x3>), dim3((unsigned)blocks), dim3(64 * kMlpWaves), lds, st, x, B, m.dims[0],
-                           m.kpad, m.w1f, static_cast<const __bf16 *>(m.w1t), m.b1, m.tail, m.tail_floats, m.n_layers,
-                           m.dims[1], m.dims[2], m.dims[3], m.dims[4], h2w, (int)wbuf, out, row_stride, rows_per_stream, stream_skip, mean, wsum, K, no_redo, 0);
-    else if (precision == kMlpBf16)
-        hipLaunchKernelGGL((mlp_mfma_kernel<NT, kMlpBf16>), dim3((unsigned)blocks), dim3(64 * kMlpWaves), lds, st, x, B, m.dims[0],
-                           m.kpad, m.w1f, static_cast<const __bf16 *>(m.w1h), m.b1, m.tail, m.tail_floats, m.n_layers,
-                           m.dims[1], m.dims[2], m.dims[3], m.dims[4], h2w, (int)wbuf, out, row_stride, rows_per_stream, stream_skip, mean, wsum, K, no_redo, 0);
-    else
-        hipLaunchKernelGGL((mlp_mfma_kernel<NT, kMlpF32>), dim3((unsigned)blocks), dim3(64 * kMlpWaves), lds, st, x, B, m.dims[0],
-                           m.kpad, m.w1f, static_cast<const __bf16 *>(m.w1h), m.b1, m.tail, m.tail_floats, m.n_layers,
-                           m.dims[1], m.dims[2], m.dims[3], m.dims[4], h2w, (int)wbuf, out, row_stride, rows_per_stream, stream_skip, mean, wsum, K, no_redo, 0);
-    return hipGetLastError();
+    }
+    // sized for every row: workgroups past the list's end leave at once
+    if (e == hipSuccess && r.redo) e = launch_mlp_pass<NT, kMlpF32>(st, m, r, q, B, m.w1h, redo, 1);
+    return e;
 }
 
-// LDS of mlp_mfma_kernel for this model (tail weights + staged layer-1 group(s) / h1 + the hidden tail layer): wide hidden
-// layers do not fit the CU's 160 KB and take the per-layer kernel instead (Model::create)
-bool mlp_mfma_fits(const MlpDev &m) {
-    int h2w = 1;
-    for (int l2 = 2; l2 < m.n_layers; ++l2) h2w = m.dims[l2] + 1 > h2w ? m.dims[l2] + 1 : h2w;
-    h2w |= 1;
-    size_t wbuf = (size_t)16 * m.nt * mlp_wpitch_bf16() * (m.nt <= 2 ? 2 : 1);
-    const size_t h1 = (size_t)kMlpWaves * kMlpRowsPerWave * (16 * m.nt + 1);
-    if (h1 > wbuf) wbuf = h1;
-    wbuf = (wbuf + 3) & ~(size_t)3;
-    const size_t lds = ((size_t)((m.tail_floats + 3) & ~3) + wbuf + (size_t)kMlpWaves * kMlpRowsPerWave * h2w) * sizeof(float);
-    return lds <= 160 * 1024;
-}
-
-hipError_t launch_mlp_mfma(hipStream_t st, const MlpDev &m, const float *x, size_t B, int precision, float *out, uint32_t *redo) {
-    if (B == 0) return hipSuccess;
+static hipError_t launch_mlp_mfma(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, size_t B, uint32_t *redo) {
     switch (m.nt) {
-    case 1: return launch_mlp_nt<1>(st, m, x, B, precision, out, redo);
-    case 2: return launch_mlp_nt<2>(st, m, x, B, precision, out, redo);
-    case 5: return launch_mlp_nt<5>(st, m, x, B, precision, out, redo);
-    case 9: return launch_mlp_nt<9>(st, m, x, B, precision, out, redo);
+    case 1: return launch_mlp_nt<1>(st, m, r, q, B, redo);
+    case 2: return launch_mlp_nt<2>(st, m, r, q, B, redo);
+    case 5: return launch_mlp_nt<5>(st, m, r, q, B, redo);
+    case 9: return launch_mlp_nt<9>(st, m, r, q, B, redo);
     }
     return hipErrorInvalidValue;
 }
@@ -1184,136 +1178,152 @@ __global__ __launch_bounds__(64 * NQ, 2) void mlp_windows_wide_kernel(
     }
 }
 
-int mlp_windows_supported(const MlpDev &m, size_t n_win, int K, bool three_part) {
-    if (!(three_part ? m.wwin3 : m.wwin) || K != 16 || m.dims[0] % 16 != 0 || m.dims[1] > 160 || n_win < 32) return 0;
-    const int L = m.dims[0] / 16;
-    if (L > 256 || m.tail_floats > 6144) return 0;
-    for (int l2 = 2; l2 <= m.n_layers; ++l2) if (m.dims[l2] > 32) return 0;
-    const char *env = std::getenv("RP_MLP_WINDOWS");
-    if (env && env[0] == '0') return 0;
-    return m.dims[1] <= 32 ? 1 : 2;
+// mlp_windows_kernel / mlp_windows_wide_kernel `kernel` with `waves` waves per workgroup
+template <class Kernel>
+static hipError_t launch_mlp_windows_kernel(Kernel kernel, int waves, hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q,
+                                            bool p3, uint32_t *redo) {
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), 160 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(r.bps * q.S)), dim3(64 * waves), r.win_lds, st, q.x, q.frame_pitch, q.n_win, m.dims[0] / 16,
+                       (unsigned)r.bps, static_cast<const u32x4v *>(p3 ? m.wwin3 : m.wwin), r.slots, 16 * m.nt, m.b1, q.mean, q.wsum, m.tail,
+                       m.tail_floats, m.n_layers, m.dims[1], m.dims[2], m.dims[3], q.out, redo);
+    return hipGetLastError();
 }
 
 template <int NT, int NQ, bool P3>
-static hipError_t launch_mlp_windows_wide_nq(hipStream_t st, const MlpDev &m, const float *mfcc, size_t S, size_t n_win, const float *mean,
-                                             const float *wsum, float *out, uint32_t *redo, size_t pitch) {
-    const int L = m.dims[0] / 16;
-    const size_t bps = (n_win + NT * kWinTile - 1) / (NT * kWinTile), blocks = bps * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const int slots = (NT * kWinTile + L + 3) & ~3;
-    const size_t region = std::max((size_t)(P3 ? 6 : 4) * slots * 16, (size_t)32 * (32 * NQ + 1) * 4 + (size_t)32 * 33 * 4);
-    const size_t lds = (size_t)((m.tail_floats + 3) & ~3) * 4 + (size_t)slots * 4 + region;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_windows_wide_kernel<NT, NQ, P3>), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((mlp_windows_wide_kernel<NT, NQ, P3>), dim3((unsigned)blocks), dim3(64 * NQ), lds, st, mfcc, pitch, n_win, L, (unsigned)bps,
-                       static_cast<const u32x4v *>(P3 ? m.wwin3 : m.wwin), slots, 16 * m.nt, m.b1, mean, wsum, m.tail, m.tail_floats, m.n_layers, m.dims[1], m.dims[2],
-                       m.dims[3], out, redo);
-    return hipGetLastError();
+static hipError_t launch_mlp_windows_wide_nq(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
+    return launch_mlp_windows_kernel(mlp_windows_wide_kernel<NT, NQ, P3>, NQ, st, m, r, q, P3, redo);
 }
 
 template <int NT, bool P3>
-static hipError_t launch_mlp_windows_wide_nt(hipStream_t st, const MlpDev &m, const float *mfcc, size_t S, size_t n_win, const float *mean,
-                                             const float *wsum, float *out, uint32_t *redo, size_t pitch) {
-    switch ((m.dims[1] + 31) / 32) {
-    case 2: return launch_mlp_windows_wide_nq<NT, 2, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 3: return launch_mlp_windows_wide_nq<NT, 3, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 4: return launch_mlp_windows_wide_nq<NT, 4, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 5: return launch_mlp_windows_wide_nq<NT, 5, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
+static hipError_t launch_mlp_windows_wide_nt(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
+    switch (r.nq) {
+    case 2: return launch_mlp_windows_wide_nq<NT, 2, P3>(st, m, r, q, redo);
+    case 3: return launch_mlp_windows_wide_nq<NT, 3, P3>(st, m, r, q, redo);
+    case 4: return launch_mlp_windows_wide_nq<NT, 4, P3>(st, m, r, q, redo);
+    case 5: return launch_mlp_windows_wide_nq<NT, 5, P3>(st, m, r, q, redo);
     }
     return hipErrorInvalidValue;
 }
 
 template <bool P3>
-static hipError_t launch_mlp_windows_wide(hipStream_t st, const MlpDev &m, const float *mfcc, size_t S, size_t n_win, const float *mean,
-                                          const float *wsum, float *out, uint32_t *redo, size_t pitch) {
-    // row tiles per workgroup: 2 or 4 (measured per 8 192 streams x 202 windows, Medium / Large: 7 tiles 3.87 / 8.62 ms at two waves per SIMD,
-    // 4 tiles 3.36 / 7.90 at four, 2 tiles 3.84 / 11.2 -- the weights once per 64 rows)
-    const size_t tiles = (n_win + kWinTile - 1) / kWinTile, wgs = (tiles + 3) / 4, per = (tiles + wgs - 1) / wgs;
-    if (per <= 2) return launch_mlp_windows_wide_nt<2, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    return launch_mlp_windows_wide_nt<4, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
+static hipError_t launch_mlp_windows_wide(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
+    if (r.tiles <= 2) return launch_mlp_windows_wide_nt<2, P3>(st, m, r, q, redo);
+    return launch_mlp_windows_wide_nt<4, P3>(st, m, r, q, redo);
 }
 
 template <int NT, bool P3>
-static hipError_t launch_mlp_windows_nt(hipStream_t st, const MlpDev &m, const float *mfcc, size_t S, size_t n_win, const float *mean,
-                                        const float *wsum, float *out, uint32_t *redo, size_t pitch) {
-    const int L = m.dims[0] / 16;
-    const size_t bps = (n_win + NT * kWinTile - 1) / (NT * kWinTile), blocks = bps * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const int slots = (NT * kWinTile + L + 3) & ~3;
-    // frame planes (two or three parts x two k-halves); later the sums of the tiles (h1 of a tile in its place) + h2 of the four waves
-    const size_t region = std::max((size_t)(P3 ? 6 : 4) * slots * 16, (size_t)NT * 4096 + (size_t)kWinWaves * 4096);
-    const size_t lds = (size_t)((m.tail_floats + 3) & ~3) * 4 + (size_t)slots * 4 + region;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_windows_kernel<NT, P3>), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((mlp_windows_kernel<NT, P3>), dim3((unsigned)blocks), dim3(64 * kWinWaves), lds, st, mfcc, pitch, n_win, L, (unsigned)bps,
-                       static_cast<const u32x4v *>(P3 ? m.wwin3 : m.wwin), slots, 16 * m.nt, m.b1, mean, wsum, m.tail, m.tail_floats, m.n_layers, m.dims[1], m.dims[2],
-                       m.dims[3], out, redo);
-    return hipGetLastError();
+static hipError_t launch_mlp_windows_nt(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
+    return launch_mlp_windows_kernel(mlp_windows_kernel<NT, P3>, kWinWaves, st, m, r, q, P3, redo);
 }
 
 template <bool P3>
-static hipError_t launch_mlp_windows(hipStream_t st, const MlpDev &m, const float *mfcc, size_t S, size_t n_frames, size_t n_win, const float *mean,
-                                     const float *wsum, float *out, uint32_t *redo, size_t pitch) {
-    (void)n_frames;
-    // tiles per workgroup: as few workgroups per stream as 7 tiles each allow, the tiles spread evenly over them
-    static const int cap_env = std::getenv("RP_MLP_WIN_TILES") ? std::atoi(std::getenv("RP_MLP_WIN_TILES")) : kWinMaxTiles;   // experiments
-    const size_t cap = cap_env >= 1 && cap_env <= kWinMaxTiles ? (size_t)cap_env : (size_t)kWinMaxTiles;
-    const size_t tiles = (n_win + kWinTile - 1) / kWinTile, wgs = (tiles + cap - 1) / cap, per = (tiles + wgs - 1) / wgs;
-    switch (per) {
-    case 1: return launch_mlp_windows_nt<1, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 2: return launch_mlp_windows_nt<2, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 3: return launch_mlp_windows_nt<3, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 4: return launch_mlp_windows_nt<4, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 5: return launch_mlp_windows_nt<5, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 6: return launch_mlp_windows_nt<6, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
-    case 7: return launch_mlp_windows_nt<7, P3>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
+static hipError_t launch_mlp_windows(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
+    switch (r.tiles) {
+    case 1: return launch_mlp_windows_nt<1, P3>(st, m, r, q, redo);
+    case 2: return launch_mlp_windows_nt<2, P3>(st, m, r, q, redo);
+    case 3: return launch_mlp_windows_nt<3, P3>(st, m, r, q, redo);
+    case 4: return launch_mlp_windows_nt<4, P3>(st, m, r, q, redo);
+    case 5: return launch_mlp_windows_nt<5, P3>(st, m, r, q, redo);
+    case 6: return launch_mlp_windows_nt<6, P3>(st, m, r, q, redo);
+    case 7: return launch_mlp_windows_nt<7, P3>(st, m, r, q, redo);
     }
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_mlp_mfma_windows(hipStream_t st, const MlpDev &m, const float *mfcc, size_t S, size_t n_frames, size_t n_win, int K,
-                                   const float *mean, const float *wsum, float *out, uint32_t *redo, size_t frame_pitch, int precision) {
-    const size_t B = S * n_win;
-    if (B == 0) return hipSuccess;
-    if (K < 1 || K % 4 != 0 || m.dims[0] % K != 0) return hipErrorInvalidValue;  // 16-byte aligned window rows
-    const size_t L = (size_t)m.dims[0] / K;
-    // window w of stream s starts at frame s * pitch + w: rows advance by K floats, a new stream skips the rest of its row
-    const size_t pitch = frame_pitch ? frame_pitch : n_win + L - 1;
-    if (pitch < n_win) return hipErrorInvalidValue;
-    (void)n_frames;
-    const size_t skip = (pitch - n_win) * K;
-    // the staged-frame kernels (mlp_windows_kernel / mlp_windows_wide_kernel): three bf16 parts for RP_MLP_F32 (exact operands, nothing to
-    // list), two f16 parts for RP_MLP_F32_FAST (+ the listed rows again with the f32 instructions)
-    if (precision == kMlpF32 && redo) {
-        if (const int form = mlp_windows_supported(m, n_win, K, true)) {
-            if (S * n_win > 0xffffffffULL) return hipErrorInvalidValue;
-            return form == 1 ? launch_mlp_windows<true>(st, m, mfcc, S, n_frames, n_win, mean, wsum, out, redo, pitch)
-                             : launch_mlp_windows_wide<true>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch);
+static MlpRoute mlp_route(Model &md, const MlpForward &q) {
+    MlpRoute r;
+    if (!md.mfma_ok) return r;
+    const MlpDev &m = md.dev;
+    // RP_MLP_F32: three bf16 parts; RP_MLP_F32_FAST: two f16 parts (+ the listed rows with the f32 matrix instructions); RP_MLP_F32_STRICT: the
+    // f32 matrix instructions; RP_MLP_BF16: bf16 inputs -- for dense rows only (it permits bf16 inputs: the windows take RP_MLP_F32's form)
+    r.prec = q.precision == RP_MLP_F32_FAST ? kMlpF16x2 : q.precision == RP_MLP_F32_STRICT ? kMlpF32
+             : (q.precision == RP_MLP_BF16 && !q.windows) ? kMlpBf16 : kMlpBf16x3;
+    r.redo = r.prec == kMlpF16x2;
+    if (q.windows) {
+        // whole streams (or long runs of windows): the staged-frame kernels, the frames staged once per workgroup -- mfcc_size 16, layer 1
+        // <= 32 (mlp_windows_kernel) or <= 160 (mlp_windows_wide_kernel) wide, the tail layers <= 32
+        int form = 0;
+        if (r.prec != kMlpF32 && (r.prec == kMlpBf16x3 ? m.wwin3 : m.wwin) && q.K == 16 && m.dims[0] % 16 == 0 && m.dims[1] <= 160 &&
+            q.n_win >= 32 && m.dims[0] / 16 <= 256 && m.tail_floats <= 6144) {
+            form = m.dims[1] <= 32 ? 1 : 2;
+            for (int l2 = 2; l2 <= m.n_layers; ++l2) if (m.dims[l2] > 32) form = 0;
+            if (const char *env = std::getenv("RP_MLP_WINDOWS")) if (env[0] == '0') form = 0;
         }
-    }
-    if (const int form = (precision == kMlpF16x2 && redo) ? mlp_windows_supported(m, n_win, K, false) : 0) {
-        // whole streams (or long runs of windows): the frames staged once per workgroup; then the listed rows with the f32 instructions
-        if (S * n_win > 0xffffffffULL) return hipErrorInvalidValue;
-        if (hipError_t e = form == 1 ? launch_mlp_windows<false>(st, m, mfcc, S, n_frames, n_win, mean, wsum, out, redo, pitch)
-                                     : launch_mlp_windows_wide<false>(st, m, mfcc, S, n_win, mean, wsum, out, redo, pitch); e != hipSuccess)
-            return mlp_redo_abort(st, redo, e);
-        hipError_t e2 = hipErrorInvalidValue;   // (launch_mlp_nt puts the words back itself when ITS launch fails)
-        switch (m.nt) {
-        case 1: e2 = launch_mlp_nt<1>(st, m, mfcc, B, kMlpRedoF32, out, redo, (size_t)K, n_win, skip, mean, wsum, K); break;
-        case 2: e2 = launch_mlp_nt<2>(st, m, mfcc, B, kMlpRedoF32, out, redo, (size_t)K, n_win, skip, mean, wsum, K); break;
-        case 5: e2 = launch_mlp_nt<5>(st, m, mfcc, B, kMlpRedoF32, out, redo, (size_t)K, n_win, skip, mean, wsum, K); break;
-        case 9: e2 = launch_mlp_nt<9>(st, m, mfcc, B, kMlpRedoF32, out, redo, (size_t)K, n_win, skip, mean, wsum, K); break;
+        r.kind = form == 1 ? kMlpWindows : form == 2 ? kMlpWindowsWide : kMlpInPlace;
+        const size_t tiles = (q.n_win + kWinTile - 1) / kWinTile;
+        if (form == 1) {
+            // tiles per workgroup: as few workgroups per stream as 7 tiles each allow, the tiles spread evenly over them
+            static const int cap_env = std::getenv("RP_MLP_WIN_TILES") ? std::atoi(std::getenv("RP_MLP_WIN_TILES")) : kWinMaxTiles;   // experiments
+            const size_t cap = cap_env >= 1 && cap_env <= kWinMaxTiles ? (size_t)cap_env : (size_t)kWinMaxTiles, wgs = (tiles + cap - 1) / cap;
+            r.tiles = (int)((tiles + wgs - 1) / wgs);
+        } else if (form == 2) {
+            // 2 or 4 (measured per 8 192 streams x 202 windows, Medium / Large: 7 tiles 3.87 / 8.62 ms at two waves per SIMD, 4 tiles
+            // 3.36 / 7.90 at four, 2 tiles 3.84 / 11.2 -- the weights once per 64 rows)
+            const size_t wgs = (tiles + 3) / 4;
+            r.tiles = (tiles + wgs - 1) / wgs <= 2 ? 2 : 4;
+            r.nq = (m.dims[1] + 31) / 32;
         }
-        return e2 == hipSuccess ? e2 : mlp_redo_abort(st, redo, e2);
+        if (form) {
+            // frame planes (two or three parts x two k-halves); later the sums of the tiles (h1 of a tile in its place) + h2 of the
+            // four waves (the wide form: h1 of its NQ output tiles + h2)
+            r.bps = (q.n_win + r.tiles * kWinTile - 1) / (r.tiles * kWinTile);
+            r.slots = (r.tiles * kWinTile + m.dims[0] / 16 + 3) & ~3;
+            const size_t later = form == 1 ? (size_t)r.tiles * 4096 + (size_t)kWinWaves * 4096 : (size_t)32 * (32 * r.nq + 1) * 4 + (size_t)32 * 33 * 4;
+            r.win_lds = (size_t)((m.tail_floats + 3) & ~3) * 4 + (size_t)r.slots * 4 + std::max((size_t)(r.prec == kMlpBf16x3 ? 6 : 4) * r.slots * 16, later);
+        }
+    } else {
+        // RP_MLP_STREAM (a tuning knob of benchmarks and tests, not an arithmetic switch): 0 = mlp_mfma_kernel for every shape, 2 = the
+        // streaming kernel for RP_MLP_F32_STRICT too -- by default the f32 matrix rate binds there, and mlp_mfma_kernel's 24 waves per CU
+        // overlap it better (0.198 against 0.207 ms at BASELINE C5); the other forms stream at the HBM rate (bf16 0.132 against 0.155 ms)
+        const char *e = std::getenv("RP_MLP_STREAM");
+        const int mode = e ? (e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1) : 1;
+        const bool stream = q.allow_stream && mode != 0 && (r.prec != kMlpF32 || mode == 2) && mlp_stream_supported(m, q.x, r.prec) &&
+                            md.stream_plan(q.x, q.B, r.prec, &r.plan);
+        r.kind = stream ? kMlpStream : kMlpRows;
     }
-    const int prec = precision;
-    switch (m.nt) {
-    case 1: return launch_mlp_nt<1>(st, m, mfcc, B, prec, out, redo, (size_t)K, n_win, skip, mean, wsum, K);
-    case 2: return launch_mlp_nt<2>(st, m, mfcc, B, prec, out, redo, (size_t)K, n_win, skip, mean, wsum, K);
-    case 5: return launch_mlp_nt<5>(st, m, mfcc, B, prec, out, redo, (size_t)K, n_win, skip, mean, wsum, K);
-    case 9: return launch_mlp_nt<9>(st, m, mfcc, B, prec, out, redo, (size_t)K, n_win, skip, mean, wsum, K);
+    // a model whose three-part weight groups do not fit the CU's LDS beside its tail layers (the widest ones) runs the f32 matrix
+    // instructions instead: exact either way
+    const bool mfma = r.kind == kMlpRows || r.kind == kMlpInPlace;
+    r.lds = mlp_mfma_lds(m, mfma ? r.prec : kMlpF32, &r.h2w, &r.wbuf);
+    if (mfma && r.prec == kMlpBf16x3 && r.lds > 160 * 1024) r.lds = mlp_mfma_lds(m, r.prec = kMlpF32, &r.h2w, &r.wbuf);
+    static const char *const name[] = {"", "mlp_mfma_kernel", "mlp_stream_kernel", "mlp_windows_kernel", "mlp_windows_wide_kernel", "mlp_mfma_kernel"};
+    r.report = std::string(name[r.kind]) + (r.prec == kMlpF32 ? "<f32 matrix instructions>" : r.prec == kMlpBf16 ? "<bf16>" : r.prec == kMlpF16x2 ? "<f16x2 splits>" : "<bf16x3 splits>");
+    if (r.kind == kMlpInPlace) r.report += r.redo ? ", windows read in place," : ", windows read in place";
+    if (r.redo) r.report += " + mlp_mfma_kernel<f32> on listed rows";
+    return r;
+}
+
+bool mlp_forward(Ctx &c, const MlpForward &q) {
+    Model &md = *q.m;
+    const MlpDev &m = md.dev;
+    const size_t rows = q.windows ? q.S * q.n_win : q.B;
+    if (q.timed) c.time_begin(kKernelMlp);
+    const MlpRoute r = mlp_route(md, q);
+    uint32_t *redo = r.kind == kMlpLayers ? nullptr : c.mlp_redo(rows);
+    hipError_t e = (r.kind != kMlpLayers && !redo) ? hipErrorOutOfMemory : hipSuccess;
+    if (e == hipSuccess && rows) {
+        switch (r.kind) {
+        case kMlpLayers:
+            e = launch_mlp(c.stream, q.x, rows, (int)md.dims.size() - 1, md.dims.data(), md.W.data(), md.B.data(), q.scratch[0], q.scratch[1], q.out);
+            break;
+        case kMlpStream: e = launch_mlp_stream(c.stream, m, r.plan, q.x, rows, r.prec, q.out, c.n_cu, redo); break;
+        case kMlpWindows:
+        case kMlpWindowsWide:
+            if (rows > 0xffffffffULL || r.bps * q.S > 0x7fffffffULL || r.win_lds > 160 * 1024) e = hipErrorInvalidValue;
+            else if (r.prec == kMlpBf16x3) e = r.kind == kMlpWindows ? launch_mlp_windows<true>(c.stream, m, r, q, redo) : launch_mlp_windows_wide<true>(c.stream, m, r, q, redo);
+            else e = r.kind == kMlpWindows ? launch_mlp_windows<false>(c.stream, m, r, q, redo) : launch_mlp_windows_wide<false>(c.stream, m, r, q, redo);
+            break;
+        default: break;
+        }
+        // dense rows and windows in place, and the second pass of the split form
+        if (e == hipSuccess && (r.kind == kMlpRows || r.kind == kMlpInPlace || r.redo)) e = launch_mlp_mfma(c.stream, m, r, q, rows, redo);
+        // a failure between the split pass and the pass over the listed rows must not leave rows of THIS call listed for the next one:
+        // the two counter words go back to zero behind whatever was queued, as dtw_abort does for the DTW words
+        if (e != hipSuccess && redo) (void)hipMemsetAsync(redo, 0, 2 * sizeof(uint32_t), c.stream);
     }
-    return hipErrorInvalidValue;
+    if (e == hipSuccess && q.report && !r.report.empty()) c.last_mlp_kernel = r.report;
+    if (q.timed) c.time_end();
+    return hip_ok(e, r.kind == kMlpLayers ? "mlp_layer_kernel" : "mlp_mfma_kernel");
 }
 
 }  // namespace rp

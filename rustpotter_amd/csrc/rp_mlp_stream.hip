@@ -405,22 +405,10 @@ bool mlp_stream_supported(const MlpDev &m, const float *x, int precision) {
     return stream_lds_bytes(m.nt, precision == kMlpBf16x3 ? (int)kMlpBf16x3 : (int)kMlpF32, 1, tail_lds, h2p) <= 160 * 1024;
 }
 
-static hipError_t launch_mlp_stream_pass(hipStream_t st, const MlpDev &m, const MlpStreamPlan &p, const float *x, size_t B, int precision, float *out, int n_cu,
-                                         uint32_t *redo);
-
 hipError_t launch_mlp_stream(hipStream_t st, const MlpDev &m, const MlpStreamPlan &p, const float *x, size_t B, int precision, float *out, int n_cu,
                              uint32_t *redo) {
     if (B == 0) return hipSuccess;
     if (precision == kMlpF16x2 && (!redo || B > 0xffffffffULL)) return hipErrorInvalidValue;
-    if (hipError_t e = launch_mlp_stream_pass(st, m, p, x, B, precision, out, n_cu, redo); e != hipSuccess || precision != kMlpF16x2)
-        return e == hipSuccess ? e : mlp_redo_abort(st, redo, e);
-    // the rows the split form listed (a feature beyond the f16 range) again, with the f32 matrix instructions of mlp_mfma_kernel
-    const hipError_t e = launch_mlp_mfma(st, m, x, B, kMlpRedoF32, out, redo);
-    return e == hipSuccess ? e : mlp_redo_abort(st, redo, e);
-}
-
-static hipError_t launch_mlp_stream_pass(hipStream_t st, const MlpDev &m, const MlpStreamPlan &p, const float *x, size_t B, int precision, float *out, int n_cu,
-                                         uint32_t *redo) {
     int h2p = 4;
     const int tail_lds = stream_tail_lds(m, &h2p);
     int depth = stream_lds_bytes(m.nt, precision, 2, tail_lds, h2p) <= 160 * 1024 ? 2 : 1;

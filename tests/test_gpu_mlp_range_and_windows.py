@@ -237,3 +237,68 @@ def test_window_logits_edges(ra, ctx):
     assert L_.rp_mlp_forward_windows(dctx._h, dmodel._h, x.data_ptr(), 5, 300, K, 0, out.data_ptr()) == 0
     dctx.synchronize()
     assert out.cpu().numpy().tobytes() == host.tobytes()
+
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the route of a forward (mlp_route, rp_mlp.hip): rp_ctx_last_mlp_kernel names what ran, and every route agrees with the oracle
+_FORM = {"f32": "bf16x3 splits", "bf16": "bf16", "f32_strict": "f32 matrix instructions", "f32_fast": "f16x2 splits"}
+_LISTED = " + mlp_mfma_kernel<f32> on listed rows"
+
+
+@pytest.mark.parametrize("dims,nt", [((3120, 13, 2), 1), ((3120, 32, 16, 2), 2), ((3120, 80, 40, 3), 5), ((1040, 144, 32, 2), 9),
+                                     ((4096, 20, 255, 4), 0),       # a hidden layer too wide for the fused kernels: the per-layer kernel
+                                     ((3120, 144, 64, 2), -9)])     # three-part weight groups beyond the LDS: the f32 instructions
+@pytest.mark.parametrize("prec", ["f32", "bf16", "f32_strict", "f32_fast"])
+def test_mlp_route_table_dense_rows(ra, ctx, dims, nt, prec):
+    """rp_mlp_forward_batch under RP_MLP_STREAM 0 / 1 / 2: the kernel the route names (the per-layer kernel leaves the name as it was), and
+    the oracle's logits (f32 forms 1e-5, bf16 against the bf16-rounding oracle 1e-3)."""
+    rng = np.random.default_rng(sum(dims) + nt)
+    ws, bs = _window_model(rng, 1, dims[0], dims[1:-1], dims[-1])
+    x = rng.standard_normal((300, dims[0])).astype(np.float32)
+    model = ra.Model(ctx, ws, bs)
+    ref, tol = (orc.mlp_forward(x, ws, bs, bf16_layer1=True), 1e-3) if prec == "bf16" else (orc.mlp_forward(x, ws, bs), 1e-5)
+    for mode in "012":
+        if nt == 0 and prec == "bf16":
+            with pytest.raises(ra.RustpotterError, match="no bf16 MFMA kernel"):
+                ctx.mlp_forward(x, model, precision=prec)
+            continue
+        before, os.environ["RP_MLP_STREAM"] = ctx.last_mlp_kernel(), mode
+        try:
+            got = ctx.mlp_forward(x, model, precision=prec)
+        finally:
+            os.environ.pop("RP_MLP_STREAM")
+        assert np.allclose(got, ref, rtol=tol, atol=tol), (mode, np.abs(got - ref).max())
+        name = "mlp_stream_kernel<" if nt in (1, 2) and mode != "0" and (prec != "f32_strict" or mode == "2") else "mlp_mfma_kernel<"
+        form = "f32 matrix instructions" if nt < 0 and prec == "f32" else _FORM[prec]
+        assert ctx.last_mlp_kernel() == (before if nt == 0 else name + form + ">" + (_LISTED if prec == "f32_fast" else "")), mode
+
+
+@pytest.mark.parametrize("hidden", [(32, 16), (65, 32), (144, 64)])   # (144, 64): no staged-frame kernel, three-part groups beyond the LDS
+@pytest.mark.parametrize("prec", ["f32", "bf16", "f32_strict", "f32_fast"])
+def test_mlp_route_table_windows(ra, ctx, hidden, prec):
+    """rp_mlp_forward_windows with n_win 31 / 40 and RP_MLP_WINDOWS 0 / 1: the staged-frame kernels or mlp_mfma_kernel reading the windows
+    in place, against the oracle at 1e-5 of the larger of the logit and the largest centred feature."""
+    K, L = 16, 195
+    rng = np.random.default_rng(hidden[0])
+    ws, bs = _window_model(rng, L, K, hidden, 2)
+    model = ra.Model(ctx, ws, bs)
+    for n_win in (31, 40):
+        mfcc = (rng.standard_normal((2, L - 1 + n_win, K)) + rng.uniform(-30.0, 30.0, K)).astype(np.float32)
+        ref = _window_logits_oracle(mfcc, L, ws, bs).astype(np.float64)
+        spread = max(np.abs(mfcc[s, w:w + L] - mfcc[s, w:w + L].mean(axis=0)).max() for s in range(2) for w in range(n_win))
+        for env in "01":
+            os.environ["RP_MLP_WINDOWS"] = env
+            try:
+                got = ctx.mlp_forward_windows(mfcc, model, precision=prec)
+            finally:
+                os.environ.pop("RP_MLP_WINDOWS")
+            assert (np.abs(got - ref) <= 1e-5 * np.maximum(np.abs(ref), spread)).all(), (n_win, env)
+            form = _FORM["f32" if prec == "bf16" else prec]
+            listed = _LISTED if prec == "f32_fast" else ""
+            if n_win >= 32 and env == "1" and prec != "f32_strict" and hidden[1] <= 32:
+                want = ("mlp_windows_wide_kernel<" if hidden[0] > 32 else "mlp_windows_kernel<") + form + ">" + listed
+            else:
+                form = "f32 matrix instructions" if hidden[1] > 32 and prec in ("f32", "bf16") else form
+                want = "mlp_mfma_kernel<" + form + ">, windows read in place" + ("," if listed else "") + listed
+            assert ctx.last_mlp_kernel() == want, (n_win, env)
