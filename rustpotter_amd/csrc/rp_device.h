@@ -195,6 +195,18 @@ template <> struct SampleIn<int32_t> {
     static __device__ __forceinline__ float4 load4(const int32_t *p) { return cvt4(ldraw(p)); }
 };
 
+// ------------------------------------------------------------------ matrix-core DTW (rp_dtw_mfma*.hip, rp_dtw_ragged.hip)
+// operands and accumulator of the v_mfma_f32_32x32x16 instructions
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned pkrtz(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lo, hi)); }
+// x0 = rtz_f16(x) as f32: x with the low 13 mantissa bits cleared (one full-rate v_and instead of a half-rate v_cvt_f32_f16; below the f16
+// normal range, |x| < 6.1e-5, the two differ by less than the f16 subnormal spacing 6e-8 -- far below the kernels' error)
+__device__ __forceinline__ float x0f(float x) { return __uint_as_float(__float_as_uint(x) & 0xffffe000u); }
+
 // The SECOND part of an f16 two-way split on the window side, x1 = f16(x - x0) (x0 = x truncated to 11 significant bits): truncated
 // like x0 (v_cvt_pkrtz_f16_f32).  Rounding it to nearest (v_cvt_pk_f16_f32, RP_SPLIT_RTN builds) was measured in round 4: the instruction
 // issues at less than half pkrtz's rate (dtw_mfma_kernel 11.70 -> 12.17 ms at C3) for a third less error.  The truncation makes every
@@ -202,7 +214,7 @@ template <> struct SampleIn<int32_t> {
 // rp_ctx.cpp) and rounds both of its parts to nearest, which also makes the dropped x1 a1 term zero-mean.
 __device__ __forceinline__ unsigned pk_f16_second(float lo, float hi) {
 #ifndef RP_SPLIT_RTN
-    return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lo, hi));
+    return pkrtz(lo, hi);
 #else
     typedef _Float16 h2_ __attribute__((ext_vector_type(2)));
     typedef float f2_ __attribute__((ext_vector_type(2)));
@@ -224,6 +236,49 @@ __device__ __forceinline__ void mlp_redo_append(uint32_t *redo, uint32_t row, si
 __device__ __forceinline__ void dtw_fix_append(uint32_t *fix, size_t row, uint32_t spec) {
     const uint32_t i = atomicAdd(fix, 1u);
     if (i < kDtwFixCap) reinterpret_cast<unsigned long long *>(fix + 2)[i] = ((unsigned long long)row << 24) | spec;
+}
+
+// The reference's score of a DTW cost nc = cost / (m + n): MfccComparator::compute_probability, src/mfcc/comparator.rs:25.
+__device__ __forceinline__ float dtw_logistic(float nc, float score_ref) { return 1.f / (1.f + expf((nc - score_ref) / score_ref)); }
+
+// ---- the frame of the matrix-core DTW kernels (dtw_mfma_kernel, dtw_mfma_wide_kernel, dtw_mfma_wide3_kernel) around their column pipelines.
+// Every helper takes the values the kernel already holds (tid, lane, wave, ...): recomputed from threadIdx inside, they change the kernel's code.
+
+// a chunk's A image (n16 16-byte units at aimg + off) -> LDS at dst, by the NT threads of the workgroup
+template <int NT>
+__device__ __forceinline__ void dtw_load_aimg(unsigned char *dst, const uint4 *aimg, int off, int n16, int tid) {
+    const u32x4 *asrc = reinterpret_cast<const u32x4 *>(aimg) + off;
+    u32x4 *adst = reinterpret_cast<u32x4 *>(dst);
+    for (int i = tid; i < n16; i += NT) adst[i] = asrc[i];
+}
+
+// Tiles are handed out per chunk (the host's side: mfma_grid, rp_kernels.h).  A wave's first static_rounds tiles are its own index among the
+// chunk's chunk_waves waves (+ a round's worth each time); the following ones come from the chunk's atomic counter next_tile[0]: 3 072 waves
+// asking one address for a ticket at the same moment queue up behind each other (a launch of two tiles per wave -- a live-stream call -- lost
+// a quarter of its time there), while a static split of a small batch leaves most of the chip waiting for the waves that got one tile more
+// (BASELINE config C2: 3.09 tiles per wave).
+template <int NW>
+__device__ __forceinline__ size_t dtw_next_tile(uint32_t *next_tile, unsigned &round, unsigned static_rounds, size_t chunk_waves, unsigned n_chunks,
+                                                int wave, int lane) {
+    if (round < static_rounds) {
+        const size_t tile = (size_t)round * chunk_waves + (size_t)(blockIdx.x / n_chunks) * NW + (size_t)wave;
+        ++round;
+        return tile;
+    }
+    unsigned ticket = 0;
+    if (lane == 0) ticket = atomicAdd(next_tile, 1u);
+    return (size_t)__builtin_amdgcn_readfirstlane(ticket) + (size_t)static_rounds * chunk_waves;
+}
+// After the workgroup's last barrier: the counter words are zero between launches -- the chunk's last workgroup to finish (next_tile[1]
+// counts them) puts both back.
+__device__ __forceinline__ void dtw_release_tiles(uint32_t *next_tile, unsigned n_groups, int tid) {
+    if (tid == 0) {
+        __threadfence();
+        if (atomicAdd(next_tile + 1, 1u) == n_groups - 1) {
+            next_tile[0] = 0;
+            next_tile[1] = 0;
+        }
+    }
 }
 
 }  // namespace rp

@@ -268,7 +268,7 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_kernel(
             if (t < ch->count) {
                 const float cost = (t & 1) ? P[t / 2][W + 1].y : P[t / 2][W + 1].x;  // D[m-1][n] for m == n
                 const float nc = cost / denom;
-                const float sc = 1.f / (1.f + expf((nc - score_ref) / score_ref));
+                const float sc = dtw_logistic(nc, score_ref);
                 const int tid = ch->tid[t];
                 if (tid < T) scores[row * T + tid] = sc;
                 else avg[row] = sc;
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
             const size_t row = s[e] * out_win_pitch + (size_t)w[e];
             const float cost = e ? P[W + 1].y : P[W + 1].x;  // D[m-1][n] for m == n
             const float nc = cost / denom;
-            const float sc = 1.f / (1.f + expf((nc - score_ref) / score_ref));
+            const float sc = dtw_logistic(nc, score_ref);
             if (tid < T) scores[row * T + tid] = sc;
             else avg[row] = sc;
             if ((e ? chk.y : chk.x) > kDtwFixLimit) dtw_fix_append(gl.fix, row, (uint32_t)(chunk_base + (int)ci));
@@ -648,7 +648,7 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_wide_kernel(
             if (t < ch->count) {
                 const float cost = P[t][W + 1];  // D[m-1][n] for m == n
                 const float nc = cost / denom;
-                const float sc = 1.f / (1.f + expf((nc - score_ref) / score_ref));
+                const float sc = dtw_logistic(nc, score_ref);
                 const int tid = ch->tid[t];
                 if (tid < T) scores[row * T + tid] = sc;
                 else avg[row] = sc;
@@ -737,7 +737,7 @@ __global__ __launch_bounds__(64) void dtw_generic_kernel(
         const int qs = n - (m - 1 - W);  // column n of row m-1
         float cost = (qs >= 0 && qs < B) ? Pb[qs * 64 + lane] : RP_INF;
         float nc = cost / (float)(m + n);
-        float sc = 1.f / (1.f + expf((nc - score_ref) / score_ref));
+        float sc = dtw_logistic(nc, score_ref);
         size_t row = s * out_win_pitch + (size_t)tile * 64 + lane;
         if (t < T) scores[row * T + t] = sc;
         else avg[row] = sc;
@@ -840,7 +840,7 @@ __global__ __launch_bounds__(64) void dtw_ref_kernel(
             const int qs = n - (m - 1 - W);  // column n of row m-1
             const float cost = (qs >= 0 && qs < B) ? Pb[qs * 64 + lane] : RP_INF;
             const float nc = cost / (float)(m + n);
-            const float sc = 1.f / (1.f + expf((nc - score_ref) / score_ref));
+            const float sc = dtw_logistic(nc, score_ref);
             if (t < T) { scores[row * T + t] = sc; best = fmaxf(best, sc); }
             else avg[row] = sc;
         }
@@ -1124,7 +1124,7 @@ __global__ __launch_bounds__(64) void dtw_single_kernel(
     }
     if (lane == W + 1) {  // D[m-1][n]
         const float nc = cur / (float)(L + L);
-        const float sc = 1.f / (1.f + expf((nc - score_ref) / score_ref));
+        const float sc = dtw_logistic(nc, score_ref);
         const size_t row = (size_t)wi;  // S == 1
         if (t < T) scores[row * T + t] = sc;
         else avg[row] = sc;

@@ -49,11 +49,6 @@ namespace rp {
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x6 __attribute__((ext_vector_type(6)));   // the window side's run of six registers (P3)
 
 constexpr int kMK = 5;         // MFCC coefficients per frame
@@ -70,8 +65,8 @@ constexpr int mfma_acc_reg(int nt, int slot, int p, int e) {
     return nt == 8 ? 4 * (slot % 4) + 2 * p + e : 4 * ((slot % 8) >> 1) + 2 * (slot & 1) + e;
 }
 
-__device__ __forceinline__ unsigned pkrtz(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lo, hi)); }
 #ifdef RP_MFMA_CVT_BACK  // A/B build only: x0 as f32 by converting the f16 back (see RP_X0F)
+typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float lo_f32(unsigned p) { return (float)__builtin_bit_cast(fp16x2, p)[0]; }
 __device__ __forceinline__ float hi_f32(unsigned p) { return (float)__builtin_bit_cast(fp16x2, p)[1]; }
 #endif
@@ -154,11 +149,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
     const int a_bytes = (max_len + kMSlotsMax) * kRowBytes;
     const int xs_floats = dtw_mfma_stage_floats(max_len);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {
-        const u32x4 *asrc = reinterpret_cast<const u32x4 *>(aimg) + (P3 ? ch->aimg3_off : ch->aimg_off);
-        u32x4 *adst = reinterpret_cast<u32x4 *>(smem);
-        for (int i = tid; i < (L + kMSlotsMax) * kRowBytes / 16; i += 64 * NW) adst[i] = asrc[i];
-    }
+    dtw_load_aimg<64 * NW>(smem, aimg, P3 ? ch->aimg3_off : ch->aimg_off, (L + kMSlotsMax) * kRowBytes / 16, tid);
     __syncthreads();
     RP_TRACE(1);
     float *xs = reinterpret_cast<float *>(smem + a_bytes) + wave * xs_floats;
@@ -188,26 +179,11 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
         slot_avg[e] = slot_real[e] && ch->tid[2 * NP * h + e] >= T;
     }
 
-    // Tiles are handed out by an atomic counter per chunk (sched[2 ci]): a small batch is a few tiles per wave, and a static
-    // split leaves most of the chip waiting for the waves that got one tile more (BASELINE config C2: 3.09 tiles per wave).
-    // The last workgroup of a chunk to finish (sched[2 ci + 1] counts them) puts both words back to zero for the next launch.
     uint32_t *next_tile = sched + 2 * (chunk_base + ci);
     unsigned round = 0;
     const size_t chunk_waves = (size_t)n_groups * NW;  // waves working on this chunk
     for (;;) {
-        // the first static_rounds tiles of a wave are its own index among the chunk's waves (+ a round's worth each time), the following
-        // ones come from the counter: 3 072 waves asking one address for a ticket at the same moment queue up behind each other (a
-        // launch of two tiles per wave -- a live-stream call -- lost a quarter of its time there); the host keeps the counter for the
-        // rounds in which balancing matters (mfma_static_rounds)
-        size_t tile;
-        if (round < static_rounds) {
-            tile = (size_t)round * chunk_waves + (size_t)(blockIdx.x / n_chunks) * NW + (size_t)wave;
-            ++round;
-        } else {
-            unsigned ticket = 0;
-            if (lane == 0) ticket = atomicAdd(next_tile, 1u);
-            tile = (size_t)__builtin_amdgcn_readfirstlane(ticket) + (size_t)static_rounds * chunk_waves;
-        }
+        const size_t tile = dtw_next_tile<NW>(next_tile, round, static_rounds, chunk_waves, n_chunks, wave, lane);
         if (tile >= total_tiles) break;
         // ---- lanes -> (stream, window) ----
         const size_t f0 = tile * kMWin;
@@ -229,10 +205,9 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             const int nA = (int)n_win - wA < kMWin ? (int)n_win - wA : kMWin;
             const int nB = (nA < kMWin && sA + 1 < n_streams) ? kMWin - nA : 0;
             const int segA = nA + L + 3;
-#ifndef RP_AB_STAGE1   // A/B builds: the one-load-per-wait staging loop of round 3
             // four loads in flight per wait: left one by one, a tile's ~11 loads per lane were as many L2 round trips -- nothing covers
             // them in the first round of a short launch, where every wave of the chip stages at the same time
-            auto stage = [&](const float *src, size_t g0, int n_floats, float *dst) {
+            auto stage =[&](const float *src, size_t g0, int n_floats, float *dst) {
                 for (int i0 = lane; i0 < n_floats; i0 += 256) {
                     float v[4];
 #pragma unroll
@@ -247,24 +222,6 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             };
             stage(mfcc + sA * frame_pitch * K, first_win + wA, segA * K, xs);
             if (nB > 0) stage(mfcc + (sA + 1) * frame_pitch * K, first_win, (nB + L + 3) * K, xs + segA * K);
-#else
-            {
-                const float *src = mfcc + sA * frame_pitch * K;
-                const size_t g0 = first_win + wA;
-                for (int i = lane; i < segA * K; i += 64) {
-                    const int f = i / K;
-                    xs[i] = g0 + f < n_frames_total ? src[g0 * K + i] : 0.f;
-                }
-            }
-            if (nB > 0) {
-                const float *src = mfcc + (sA + 1) * frame_pitch * K;
-                const int segB = nB + L + 3;
-                for (int i = lane; i < segB * K; i += 64) {
-                    const int f = i / K;
-                    xs[segA * K + i] = first_win + f < n_frames_total ? src[first_win * K + i] : 0.f;
-                }
-            }
-#endif
             wave_lds_sync();
             const bool inA = n < nA;
             valid = inA || (n - nA < nB);
@@ -333,10 +290,9 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 #define RP_BSET(par, i, v) bv[par][i] = (v)
 #define RP_P6(cc, par) if (P3) { x0a_ = RP_AND(ua_, 0xffff0000u); x0b_ = RP_AND(ub_, 0xffff0000u); x0c_ = RP_AND(u2_, 0xffff0000u); RP_BSET(par, 2, RP_HI2(ub_, ua_)); } \
                        else { bop[par].x = pkrtz(ua_, ub_); bop[par].z = bop[par].x; }
-// x1 = rtz_f16(x - x0): x0 as f32 is x with the low 13 mantissa bits cleared (one full-rate v_and instead of a half-rate v_cvt_f32_f16;
-// below the f16 normal range, |x| < 6.1e-5, the two differ by less than the f16 subnormal spacing 6e-8 -- far below the kernel's error)
+// x1 = rtz_f16(x - x0), x0 as f32 (rp_device.h x0f)
 #ifndef RP_MFMA_CVT_BACK
-#define RP_X0F(x, packed, hi) __uint_as_float(__float_as_uint(x) & 0xffffe000u)
+#define RP_X0F(x, packed, hi) x0f(x)
 #else
 #define RP_X0F(x, packed, hi) ((hi) ? hi_f32(packed) : lo_f32(packed))
 #endif
@@ -516,7 +472,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
                     if (slot < ch->count) {
                         const float cost = e ? Q[p][W - 2].y : Q[p][W - 2].x;
                         const float nc = cost / denom;
-                        const float sc = dead ? 0.f : 1.f / (1.f + expf((nc - score_ref) / score_ref));
+                        const float sc = dead ? 0.f : dtw_logistic(nc, score_ref);
                         const int t = ch->tid[slot];
                         if (t < T) { scores[row * T + t] = sc; best = fmaxf(best, sc); }
                         else if (!dead) avg[row] = sc;
@@ -540,13 +496,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
     RP_TRACE(5);
     __syncthreads();
     RP_TRACE(6);
-    if (tid == 0) {
-        __threadfence();
-        if (atomicAdd(next_tile + 1, 1u) == n_groups - 1) {  // every workgroup of this chunk has taken its last ticket
-            next_tile[0] = 0;
-            next_tile[1] = 0;
-        }
-    }
+    dtw_release_tiles(next_tile, n_groups, tid);
 }
 
 bool dtw_mfma_supported(const TemplatesDev &t, int band, size_t n_win, bool from_global, int slots, float score_ref) {
@@ -590,19 +540,13 @@ hipError_t launch_dtw_mfma(hipStream_t st, const DtwWork &wk, const TemplatesDev
     }
     const size_t lds = dtw_mfma_lds_bytes(t.max_len, nw, row_bytes);
     const void *image = p3 ? t.aimg3 : t.aimg;
-    // one workgroup per CU and chunk group; the waves take tiles from the chunk's counter
     if (!wk.sched || !wk.fix) return hipErrorInvalidValue;
-    size_t groups = (size_t)device_cu_count() / (size_t)n_chunks;
-    if (groups < 1) groups = 1;
-    const size_t need = (total_tiles + nw - 1) / nw;
-    if (groups > need) groups = need;
-    const size_t blocks = groups * (size_t)n_chunks;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const unsigned static_rounds = mfma_static_rounds(total_tiles, groups * (size_t)nw, list != nullptr);
+    unsigned blocks, static_rounds;
+    if (hipError_t e = mfma_grid(total_tiles, n_chunks, nw, list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
 #define RP_LAUNCH_MFMA_P(WW, NW, GXV, NT, PP)                                                                                       \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_kernel<WW, NW, GXV, NT, PP>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_kernel<WW, NW, GXV, NT, PP>), dim3((unsigned)blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, frame_pitch, \
+        hipLaunchKernelGGL((dtw_mfma_kernel<WW, NW, GXV, NT, PP>), dim3(blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, frame_pitch, \
                            total_tiles, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch, t.chunks,                   \
                            reinterpret_cast<const uint4 *>(image), t.T, score_ref, scores, avg, S, t.max_len, list, count, dense_min, \
                            abandon_nc, wk.sched, static_rounds, agg_out, agg_hot, agg_threshold, wk.fix);                                            \

@@ -23,14 +23,7 @@ namespace rp {
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kGK = 5, kGWin = 32, kGSlots = 12, kGTiles = 3, kGWaves = 12, kGAhead = 8;   // kGAhead: columns staged behind the window (built, never used)
-
-__device__ __forceinline__ unsigned pkrtz_g(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lo, hi)); }
-__device__ __forceinline__ float x0f_g(float x) { return __uint_as_float(__float_as_uint(x) & 0xffffe000u); }
 
 template <int W>
 __host__ __device__ constexpr int group_last_use(int u, int g) {
@@ -181,10 +174,10 @@ __global__ __launch_bounds__(64 * kGWaves, 1) void dtw_mfma_group_kernel(
                 bb_ = fmaf(d2_, d2_, __uint_as_float(sw_[0]) + __uint_as_float(sw_[1])); }
 #define GP4() inv_ = bb_ > 0.f ? __builtin_amdgcn_rsqf(bb_) : 0.f;
 #define GP5() ua_ = da_ * inv_; ub_ = db_ * inv_; u2_ = d2_ * inv_;
-#define GP6() o_.x = pkrtz_g(ua_, ub_); o_.z = o_.x;
-#define GP7() o_.y = pk_f16_second(ua_ - x0f_g(ua_), ub_ - x0f_g(ub_));
+#define GP6() o_.x = pkrtz(ua_, ub_); o_.z = o_.x;
+#define GP7() o_.y = pk_f16_second(ua_ - x0f(ua_), ub_ - x0f(ub_));
 #define GP8() if (cp_ <= L + 2) chk_ = fmaxf(fmaxf(chk_, inv_), bb_);   /* the norm-range test covers the columns dtw_mfma_kernel's does */
-#define GP9(pos, wb) { const float x0_ = x0f_g(u2_); o_.w = __builtin_amdgcn_perm(0x3c000000u, pk_f16_second(x0_, u2_ - x0_), sel_one); \
+#define GP9(pos, wb) { const float x0_ = x0f(u2_); o_.w = __builtin_amdgcn_perm(0x3c000000u, pk_f16_second(x0_, u2_ - x0_), sel_one); \
                        *reinterpret_cast<u32x4 *>(ring + (wb) + (pos) * 1024 + lane * 16) = o_; }
 #define RG_PRODUCE(pos, cbase, wb) do { GP0(pos, cbase) GP1() GP2() GP3() GP4() GP5() GP6() GP7() GP8() GP9(pos, wb) } while (0)
 #define RG_AREF(cc, uu, GUARD)                                                                                                \
@@ -301,7 +294,7 @@ __global__ __launch_bounds__(64 * kGWaves, 1) void dtw_mfma_group_kernel(
                     if (slot < ch->count) {
                         const float cost = e ? Q[p][W - 2].y : Q[p][W - 2].x;
                         const float nc = cost / denom;
-                        const float sc = 1.f / (1.f + expf((nc - score_ref) / score_ref));
+                        const float sc = dtw_logistic(nc, score_ref);
                         const int t = ch->tid[slot];
                         if (t < T) scores[row * T + t] = sc;
                     }
@@ -336,15 +329,12 @@ hipError_t launch_dtw_mfma_group(hipStream_t st, const DtwWork &wk, const Templa
     {
         const int sh = 4, first = 0, count = t.grp_count;
         const size_t lds = dtw_mfma_group_lds_bytes(t.grp4_max_len, sh);
-        size_t groups = (size_t)device_cu_count() / (size_t)count;
-        if (groups < 1) groups = 1;
-        const size_t n_tg = (total_tiles + (size_t)(kGWaves / sh) - 1) / (size_t)(kGWaves / sh);
-        if (groups > n_tg) groups = n_tg;
-        const size_t blocks = groups * (size_t)count;
+        unsigned blocks, static_rounds;   // (tile groups are handed out by index: the static rounds are not used)
+        if (hipError_t e = mfma_grid(total_tiles, count, kGWaves / sh, false, blocks, static_rounds); e != hipSuccess) return e;
 #define RP_LAUNCH_GROUP(WW, SHH)                                                                                                    \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_group_kernel<WW, SHH>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_group_kernel<WW, SHH>), dim3((unsigned)blocks), dim3(64 * kGWaves), lds, st, mfcc, frame_pitch, frame_pitch, total_tiles, \
+        hipLaunchKernelGGL((dtw_mfma_group_kernel<WW, SHH>), dim3(blocks), dim3(64 * kGWaves), lds, st, mfcc, frame_pitch, frame_pitch, total_tiles, \
                            (unsigned)count, t.grp_first + first, first_win, n_win, out_win_pitch, t.chunks, reinterpret_cast<const uint4 *>(t.aimg), t.T, \
                            score_ref, scores, S, wk.fix);                                                                           \
     } while (0)

@@ -22,17 +22,7 @@ namespace rp {
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWWin = 32, kWSlots = 12, kWTiles = 3;
-
-__device__ __forceinline__ unsigned pkrtz(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lo, hi)); }
-// x0 = rtz_f16(x) as f32: x with the low 13 mantissa bits cleared (a full-rate v_and; below the f16 normal range the two differ by less
-// than the f16 subnormal spacing, 6e-8)
-__device__ __forceinline__ float x0f(float x) { return __uint_as_float(__float_as_uint(x) & 0xffffe000u); }
 
 template <int W>
 __host__ __device__ constexpr int wide_last_use(int u, int g) {
@@ -101,11 +91,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide_kernel(
     const DtwChunk *ch = chunks + chunk_base + ci;
     const int L = ch->len;  // m == n == L
     const int tid = threadIdx.x, lane = tid & 63;
-    {
-        const u32x4 *asrc = reinterpret_cast<const u32x4 *>(aimg) + ch->aimg_off;
-        u32x4 *adst = reinterpret_cast<u32x4 *>(smem);
-        for (int i = tid; i < (L + 16) * kRowBytes / 16; i += 64 * NW) adst[i] = asrc[i];
-    }
+    dtw_load_aimg<64 * NW>(smem, aimg, ch->aimg_off, (L + 16) * kRowBytes / 16, tid);
     __syncthreads();
     const int n = lane & 31, h = lane >> 5;
     const int mrow = lane & 31, jj = mrow >> 3, tA = ((mrow >> 2) & 1) * 4 + (mrow & 3);
@@ -124,19 +110,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide_kernel(
     unsigned round = 0;
     const size_t chunk_waves = (size_t)n_groups * NW;  // waves working on this chunk
     for (;;) {
-        // the first static_rounds tiles of a wave are its own index among the chunk's waves (+ a round's worth each time), the following
-        // ones come from the counter: 3 072 waves asking one address for a ticket at the same moment queue up behind each other (a
-        // launch of two tiles per wave -- a live-stream call -- lost a quarter of its time there); the host keeps the counter for the
-        // rounds in which balancing matters (mfma_static_rounds)
-        size_t tile;
-        if (round < static_rounds) {
-            tile = (size_t)round * chunk_waves + (size_t)(blockIdx.x / n_chunks) * NW + (size_t)(tid >> 6);
-            ++round;
-        } else {
-            unsigned ticket = 0;
-            if (lane == 0) ticket = atomicAdd(next_tile, 1u);
-            tile = (size_t)__builtin_amdgcn_readfirstlane(ticket) + (size_t)static_rounds * chunk_waves;
-        }
+        const size_t tile = dtw_next_tile<NW>(next_tile, round, static_rounds, chunk_waves, n_chunks, tid >> 6, lane);
         if (tile >= total_tiles) break;
         size_t f = tile * kWWin + n;
         const bool valid = f < total_entries;
@@ -335,7 +309,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide_kernel(
                     if (slot < ch->count) {
                         const float cost = e ? Q[p][W - 2].y : Q[p][W - 2].x;
                         const float nc = cost / denom;
-                        const float sc = dead ? 0.f : 1.f / (1.f + expf((nc - score_ref) / score_ref));
+                        const float sc = dead ? 0.f : dtw_logistic(nc, score_ref);
                         const int t = ch->tid[slot];
                         if (t < T) scores[row * T + t] = sc;
                         else if (!dead) avg[row] = sc;
@@ -347,13 +321,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide_kernel(
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        __threadfence();
-        if (atomicAdd(next_tile + 1, 1u) == n_groups - 1) {
-            next_tile[0] = 0;
-            next_tile[1] = 0;
-        }
-    }
+    dtw_release_tiles(next_tile, n_groups, tid);
 }
 
 bool dtw_mfma_wide_supported(const TemplatesDev &t, int band, float score_ref) {
@@ -373,17 +341,12 @@ hipError_t launch_dtw_mfma_wide(hipStream_t st, const DtwWork &wk, const Templat
     const size_t total_tiles = (S * n_win + kWWin - 1) / kWWin;
     constexpr int NW = 8;
     const size_t lds = (size_t)(t.max_len + 16) * dtw_mfma_wide_row_bytes(t.K);
-    size_t groups = (size_t)device_cu_count() / (size_t)n_chunks;
-    if (groups < 1) groups = 1;
-    const size_t need = (total_tiles + NW - 1) / NW;
-    if (groups > need) groups = need;
-    const size_t blocks = groups * (size_t)n_chunks;
-    const unsigned static_rounds = mfma_static_rounds(total_tiles, groups * (size_t)NW, list != nullptr);
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    unsigned blocks, static_rounds;
+    if (hipError_t e = mfma_grid(total_tiles, n_chunks, NW, list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
 #define RP_LAUNCH_WIDE(KK)                                                                                                          \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_wide_kernel<KK, 5, NW>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_wide_kernel<KK, 5, NW>), dim3((unsigned)blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, total_tiles, \
+        hipLaunchKernelGGL((dtw_mfma_wide_kernel<KK, 5, NW>), dim3(blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, total_tiles, \
                            (unsigned)n_chunks, t.wide8_first, first_win, n_win, out_win_pitch, t.chunks, reinterpret_cast<const uint4 *>(t.aimg), \
                            t.T, score_ref, scores, avg, S, list, count, dense_min, abandon_nc, wk.sched, static_rounds, wk.fix);         \
     } while (0)

@@ -33,9 +33,6 @@ namespace rp {
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x12 __attribute__((ext_vector_type(12)));
 
 // k-step ks of the window side's operand: a four-register piece of the half's run of twelve (see above)
@@ -110,11 +107,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide3_kernel(
     const DtwChunk *ch = chunks + chunk_base + ci;
     const int L = ch->len;  // m == n == L
     const int tid = threadIdx.x, lane = tid & 63;
-    {
-        const u32x4 *asrc = reinterpret_cast<const u32x4 *>(aimg) + ch->aimg3_off;
-        u32x4 *adst = reinterpret_cast<u32x4 *>(smem);
-        for (int i = tid; i < (L + 16) * kRowBytes / 16; i += 64 * NW) adst[i] = asrc[i];
-    }
+    dtw_load_aimg<64 * NW>(smem, aimg, ch->aimg3_off, (L + 16) * kRowBytes / 16, tid);
     __syncthreads();
     const int n = lane & 31, h = lane >> 5;
     // A operand: this lane supplies row m = lane & 31 of a tile, k half = lane >> 5: m = 8 G + 4 h' + 2 sp + e = (row slot 2 G + sp, template 2 h' + e)
@@ -131,15 +124,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide3_kernel(
     unsigned round = 0;
     const size_t chunk_waves = (size_t)n_groups * NW;  // waves working on this chunk
     for (;;) {
-        size_t tile;
-        if (round < static_rounds) {   // as dtw_mfma_kernel: the first round(s) by index, the rest from the chunk's counter
-            tile = (size_t)round * chunk_waves + (size_t)(blockIdx.x / n_chunks) * NW + (size_t)(tid >> 6);
-            ++round;
-        } else {
-            unsigned ticket = 0;
-            if (lane == 0) ticket = atomicAdd(next_tile, 1u);
-            tile = (size_t)__builtin_amdgcn_readfirstlane(ticket) + (size_t)static_rounds * chunk_waves;
-        }
+        const size_t tile = dtw_next_tile<NW>(next_tile, round, static_rounds, chunk_waves, n_chunks, tid >> 6, lane);
         if (tile >= total_tiles) break;
         size_t f = tile * kW3Win + n;
         const bool valid = f < total_entries;
@@ -347,7 +332,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide3_kernel(
                 if (slot < ch->count) {
                     const float cost = e ? Q[W - 2].y : Q[W - 2].x;   // D[m - 1][n]: band position W - 2 (dtw.rs:101)
                     const float nc = cost / denom;
-                    const float sc = dead ? 0.f : 1.f / (1.f + expf((nc - score_ref) / score_ref));
+                    const float sc = dead ? 0.f : dtw_logistic(nc, score_ref);
                     const int t = ch->tid[slot];
                     if (t < T) scores[row * T + t] = sc;
                     else if (!dead) avg[row] = sc;
@@ -358,13 +343,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_wide3_kernel(
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        __threadfence();
-        if (atomicAdd(next_tile + 1, 1u) == n_groups - 1) {
-            next_tile[0] = 0;
-            next_tile[1] = 0;
-        }
-    }
+    dtw_release_tiles(next_tile, n_groups, tid);
 }
 
 bool dtw_mfma_wide3_supported(const TemplatesDev &t, int band) {
@@ -383,17 +362,12 @@ hipError_t launch_dtw_mfma_wide3(hipStream_t st, const DtwWork &wk, const Templa
     const size_t total_tiles = (S * n_win + kW3Win - 1) / kW3Win;
     constexpr int NW = 8;
     const size_t lds = (size_t)(t.max_len + 16) * kDtwWide3RowBytes;
-    size_t groups = (size_t)device_cu_count() / (size_t)n_chunks;
-    if (groups < 1) groups = 1;
-    const size_t need = (total_tiles + NW - 1) / NW;
-    if (groups > need) groups = need;
-    const size_t blocks = groups * (size_t)n_chunks;
-    const unsigned static_rounds = mfma_static_rounds(total_tiles, groups * (size_t)NW, list != nullptr);
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    unsigned blocks, static_rounds;
+    if (hipError_t e = mfma_grid(total_tiles, n_chunks, NW, list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
 #define RP_LAUNCH_WIDE3(KK)                                                                                                         \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_wide3_kernel<KK, 5, NW>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_wide3_kernel<KK, 5, NW>), dim3((unsigned)blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, total_tiles, \
+        hipLaunchKernelGGL((dtw_mfma_wide3_kernel<KK, 5, NW>), dim3(blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, total_tiles, \
                            (unsigned)n_chunks, t.wide4_first, first_win, n_win, out_win_pitch, t.chunks, reinterpret_cast<const uint4 *>(t.aimg3), \
                            t.T, score_ref, scores, avg, S, list, count, dense_min, abandon_nc, wk.sched, static_rounds, wk.fix);         \
     } while (0)

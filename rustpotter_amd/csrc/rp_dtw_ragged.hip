@@ -42,17 +42,12 @@ namespace rp {
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRK = 5;                          // MFCC coefficients per frame
 constexpr int kRSlots = 16;                     // circular row slots of a template (band + neighbours: 2 W + 2 <= 16)
 constexpr int kRTile = 64 * kDtwRaggedWaves;    // windows per workgroup tile
 constexpr float kRRatio = 32.f;                 // |x_f - o| / |x_f - mu| above which a (window, template) is rescored by dtw_ref_kernel
 constexpr float kRKappaMax = 7.5f;              // 1 / (s |x_f - mu|) above which the second f16 parts are subnormal (abs error 2^-24 each)
 
-__device__ __forceinline__ unsigned pkrtz(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(lo, hi)); }
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -380,7 +375,7 @@ __global__ __launch_bounds__(64 * kDtwRaggedWaves, 4) void dtw_ragged_kernel(
 #undef RG_NORM
             // D[m - 1][n] with m == n == L (dtw.rs:101): band position q = W - 2
             const float nc = Q[W - 2] / (float)(L + L);
-            const float sc = dead ? 0.f : 1.f / (1.f + expf((nc - score_ref) / score_ref));
+            const float sc = dead ? 0.f : dtw_logistic(nc, score_ref);
             if (valid) scores[(strm * out_win_pitch + (size_t)w) * T + tcol] = sc;
             listed = listed || kmax > klim;
         }

@@ -124,6 +124,21 @@ inline unsigned mfma_static_rounds(size_t total_tiles, size_t chunk_waves, bool 
     if (const char *e = std::getenv("RP_MFMA_STATIC_ROUNDS")) return (unsigned)std::atoi(e);  // A/B runs: 0 = every tile from the counter
     return (list || r > 3 || r < 1) ? 1u : (unsigned)r;
 }
+// compute units of the current device (cached per device)
+int device_cu_count();
+// Grid of the matrix-core DTW kernels: the CUs split over the n_chunks chunks (at least one workgroup each), a chunk's workgroups no more
+// than its rounds of `waves` tiles; and the rounds a wave takes by index.  The tile counter words (DtwWork::sched) are zero between
+// launches; the kernels' side of that protocol is dtw_next_tile / dtw_release_tiles (rp_device.h).
+inline hipError_t mfma_grid(size_t total_tiles, int n_chunks, int waves, bool list, unsigned &blocks, unsigned &static_rounds) {
+    size_t groups = (size_t)device_cu_count() / (size_t)n_chunks;
+    if (groups < 1) groups = 1;
+    const size_t need = (total_tiles + waves - 1) / waves;
+    if (groups > need) groups = need;
+    if (groups * (size_t)n_chunks > 0x7fffffffULL) return hipErrorInvalidValue;
+    blocks = (unsigned)(groups * (size_t)n_chunks);
+    static_rounds = mfma_static_rounds(total_tiles, groups * (size_t)waves, list);
+    return hipSuccess;
+}
 inline size_t dtw_mfma_lds_bytes(int max_len, int waves, int row_bytes = kDtwMfmaRowBytes) {
     return (size_t)(max_len + 16) * (size_t)row_bytes + (size_t)waves * (size_t)dtw_mfma_stage_floats(max_len) * sizeof(float);
 }
@@ -284,8 +299,6 @@ hipError_t launch_dtw_ragged(hipStream_t st, const DtwWork &wk, const TemplatesD
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a process that drives several GPUs
 // (one rp_ctx per device) has to set it on each of them.  Sets it once per (current device, kernel), thread-safe.
 hipError_t allow_dynamic_lds(const void *kernel, int bytes);
-// compute units of the current device (cached per device)
-int device_cu_count();
 
 enum KernelId { kKernelMfcc = 0, kKernelDtw = 1, kKernelAggregate = 2, kKernelScan = 3, kKernelMlp = 4, kKernelResample = 5, kKernelCount = 6 };
 
