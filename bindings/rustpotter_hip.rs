@@ -188,6 +188,8 @@ extern "C" {
     pub fn rp_stream_batch_samples_per_chunk(b: *const rp_stream_batch) -> usize;
     pub fn rp_stream_batch_reset(b: *mut rp_stream_batch, stream: i64) -> c_int;
     pub fn rp_stream_batch_chunks_seen(b: *const rp_stream_batch) -> usize;
+    pub fn rp_stream_batch_set_filters(b: *mut rp_stream_batch, filters: *const rp_filters_config, rms_level_ref: f32) -> c_int;
+    pub fn rp_stream_batch_levels(b: *mut rp_stream_batch, rms: *mut f32, gains: *mut f32) -> c_int;
     pub fn rp_stream_batch_new_multi(ctx: *mut rp_ctx, n_wakewords: usize, wakewords: *const rp_wakeword_spec, mfcc_size: c_int,
                                      config: *const rp_detector_config, S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
     pub fn rp_stream_batch_process_multi(b: *mut rp_stream_batch, pcm: *const c_void, fmt: c_int, n_chunks: usize, pcm_stride: usize,
@@ -621,7 +623,7 @@ impl HipContext {
 
 /// S live streams that each receive a few 30 ms chunks per call: the batched form of S `Rustpotter` handles
 /// (INTEGRATION.md §4).  Borrows the context and the templates, like the C handle does.
-pub struct StreamBatch<'a> { h: *mut rp_stream_batch, n_streams: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
+pub struct StreamBatch<'a> { h: *mut rp_stream_batch, n_streams: usize, last_chunks: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
 /// One wakeword of a detector that holds several (`Rustpotter::add_wakeword_ref` / `add_wakeword_model`, src/detector.rs:144-150)
 pub enum BatchWakeword<'a> {
     /// a reference with its own `threshold` / `avg_threshold` options (`WakewordRef::threshold`, `::avg_threshold`)
@@ -635,7 +637,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new(ctx.h, t.h, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// S detectors that each hold `wakewords` (references and / or models sharing `mfcc_size`): the best score of the wakewords
     /// whose own thresholds pass wins a frame (`run_wakeword_detectors`, src/detector.rs:433-447)
@@ -652,7 +654,7 @@ impl<'a> StreamBatch<'a> {
         }).collect();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_multi(ctx.h, specs.len(), specs.as_ptr(), mfcc_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// `process` that also tells which wakeword fired and, for a model, which label: (detections, wakeword indices, label indices or -1)
     pub fn process_multi(&mut self, pcm: &[f32], n_chunks: usize, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>, Vec<Vec<i32>>), String> {
@@ -665,12 +667,26 @@ impl<'a> StreamBatch<'a> {
             rp_stream_batch_process_multi(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_chunks, stride, det.as_mut_ptr(), which.as_mut_ptr(),
                                           label.as_mut_ptr(), n_det.as_mut_ptr(), max_det as c_int)
         })?;
+        self.last_chunks = n_chunks;
         let cut = |v: &Vec<i32>| -> Vec<Vec<i32>> { (0..self.n_streams).map(|s| v[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect() };
         let (w, l) = (cut(&which), cut(&label));
         Ok((split_detections(det, n_det, max_det), w, l))
     }
     /// `RustpotterConfig.fmt` of the streams (sample rate, channels); before the first `process`
     pub fn set_input(&mut self, sample_rate: usize, channels: u16) -> Result<(), String> { status(unsafe { rp_stream_batch_set_input(self.h, sample_rate, channels as c_int) }) }
+    /// `RustpotterConfig.filters` of the streams (gain normaliser + band-pass, src/detector.rs:358-371), state kept per stream on the
+    /// device; before the first `process`.  `rms_level_ref`: the largest `rms_level` of the wakewords (NaN: none)
+    pub fn set_filters(&mut self, filters: &FiltersConfig, rms_level_ref: f32) -> Result<(), String> {
+        let f: rp_filters_config = filters.into();
+        status(unsafe { rp_stream_batch_set_filters(self.h, &f, rms_level_ref) })
+    }
+    /// `get_rms_level()` / `get_gain()` of every chunk of the last `process` / `process_multi` call: (rms, gains), each `[S][n_chunks]`
+    pub fn levels(&mut self) -> Result<(Vec<f32>, Vec<f32>), String> {
+        let n = self.n_streams * self.last_chunks.max(1);
+        let (mut rms, mut gains) = (vec![0f32; n], vec![0f32; n]);
+        status(unsafe { rp_stream_batch_levels(self.h, rms.as_mut_ptr(), gains.as_mut_ptr()) })?;
+        Ok((rms, gains))
+    }
     pub fn samples_per_chunk(&self) -> usize { unsafe { rp_stream_batch_samples_per_chunk(self.h) } }
     pub fn chunks_seen(&self) -> usize { unsafe { rp_stream_batch_chunks_seen(self.h) } }
     /// `process_samples` once per chunk on every stream: pcm `[S][n_chunks * samples_per_chunk()]` f32
@@ -683,6 +699,7 @@ impl<'a> StreamBatch<'a> {
             rp_stream_batch_process(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_chunks, stride, det.as_mut_ptr(), n_det.as_mut_ptr(),
                                     max_det as c_int, std::ptr::null_mut())
         })?;
+        self.last_chunks = n_chunks;
         Ok(split_detections(det, n_det, max_det))
     }
     /// `Rustpotter::reset` of one stream (`None` = all)

@@ -463,6 +463,24 @@ size_t rp_stream_batch_samples_per_chunk(const rp_stream_batch *b);
 int rp_stream_batch_reset(rp_stream_batch *b, long long stream);
 /* chunks consumed so far (per stream) */
 size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b);
+/* RustpotterConfig.filters for the streams of a batch (src/detector.rs:358-371).  To be called before the first
+ * rp_stream_batch_process (like rp_stream_batch_set_input; either order of the two).  rms_level_ref: what
+ * on_wakeword_change would set (src/detector.rs:328-338: the largest rms_level of the detector's wakewords; NaN =
+ * none, the gain then stays 1) -- ignored when filters->gain_normalizer.has_gain_ref.  The window of the gain
+ * normaliser is max_mfcc_frames / 3 (0 -> 1) with max_mfcc_frames the batch's longest wakeword, as :337.
+ * Per encoded 480-sample chunk and stream, as process_audio does: RMS level of the unfiltered chunk, gain normaliser,
+ * band-pass, then MFCC.  The state of both filters (the window of chunk levels, the biquad's last two inputs and
+ * outputs) lives on the device per stream for the life of the batch and is NOT touched by rp_stream_batch_reset
+ * (Rustpotter::reset leaves the filters alone).  With both filters disabled the batch runs as if this had not been
+ * called, except that rp_stream_batch_levels reports the chunk levels (gains of 1).  Not available together with the
+ * 40 ms input frames of 11.025 / 22.05 kHz input: whichever of this and rp_stream_batch_set_input comes second fails. */
+int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref);
+/* get_rms_level() / get_gain() of every chunk of the LAST rp_stream_batch_process[_multi] call of a batch that has had
+ * rp_stream_batch_set_filters: rms, gains [S][n_chunks of that call] (either may be NULL); host or device arrays as
+ * the context says.  RustpotterDetection::gain of a detection is the gain of the chunk in which its best window was scored
+ * (src/detector.rs:411-414): with f = det.window + max_mfcc_frames - 1 the last frame of that window, chunk (f + fpf) / fpf counted
+ * from the batch's first chunk (fpf = 3), i.e. the chunk whose frames contain f.  -1 before the first process call. */
+int rp_stream_batch_levels(rp_stream_batch *b, float *rms, float *gains);
 
 /* Live-stream batches whose detectors hold SEVERAL wakewords and / or wakeword MODELS (add_wakeword*, run_wakeword_detectors:
  * src/detector.rs:304-346,433-447): every wakeword whose own thresholds pass proposes a detection for the frame and the best

@@ -111,6 +111,7 @@ SYMBOLS = [
     "rp_wakeword_model_train", "rp_stream_batch_set_input", "rp_stream_batch_samples_per_chunk",
     "rp_batch_detect_multi", "rp_batch_detect_model", "rp_batch_detect_sharded",
     "rp_stream_batch_new_multi", "rp_stream_batch_process_multi",
+    "rp_stream_batch_set_filters", "rp_stream_batch_levels",
 ]
 
 
@@ -217,6 +218,8 @@ def load_library():
     L.rp_stream_batch_process.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, vp, vp, C.c_int, vp]
     L.rp_stream_batch_reset.argtypes = [vp, C.c_longlong]
     L.rp_stream_batch_set_input.argtypes = [vp, C.c_size_t, C.c_int]
+    L.rp_stream_batch_set_filters.argtypes = [vp, C.POINTER(_FiltersCfg), C.c_float]
+    L.rp_stream_batch_levels.argtypes = [vp, vp, vp]
     L.rp_stream_batch_samples_per_chunk.argtypes = [vp]
     L.rp_stream_batch_samples_per_chunk.restype = C.c_size_t
     L.rp_stream_batch_chunks_seen.argtypes = [vp]
@@ -504,10 +507,12 @@ class StreamBatch:
     Rustpotter::process_samples on S instances sharing one wakeword and config."""
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
-                 mfcc_size=None):
+                 mfcc_size=None, filters=None, rms_level_ref=float("nan")):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
-        with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required."""
+        with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
+        filters (rp_stream_batch_set_filters): a FiltersConfig for the streams, with rms_level_ref the largest rms_level of the
+        wakewords (NaN: none); levels() then reports every chunk's RMS level and gain."""
         self._L = load_library()
         self.ctx, self.templates, self.S, self.max_chunks = ctx, templates, S, max_chunks_per_call
         h = C.c_void_p()
@@ -530,7 +535,10 @@ class StreamBatch:
         self._h = h
         if (sample_rate, channels) != (16000, 1) and self._L.rp_stream_batch_set_input(h, sample_rate, channels) < 0:
             raise _err()
+        if filters is not None:
+            self.set_filters(filters, rms_level_ref)
         self.samples_per_chunk = self._L.rp_stream_batch_samples_per_chunk(h)
+        self._last_chunks = 0
         # MFCC frames a stream gains per input frame: 3 (30 ms frames) or 4 (the 40 ms frames of 11.025 / 22.05 kHz input)
         self.frames_per_chunk = resampler_frame_lengths(sample_rate)[1] // 160
 
@@ -542,6 +550,32 @@ class StreamBatch:
     @property
     def chunks_seen(self):
         return self._L.rp_stream_batch_chunks_seen(self._h)
+
+    def set_input(self, sample_rate, channels=1):
+        """rp_stream_batch_set_input (before the first process call)"""
+        if self._L.rp_stream_batch_set_input(self._h, sample_rate, channels) < 0:
+            raise _err()
+        self.samples_per_chunk = self._L.rp_stream_batch_samples_per_chunk(self._h)
+        self.frames_per_chunk = resampler_frame_lengths(sample_rate)[1] // 160
+
+    def set_filters(self, filters, rms_level_ref=float("nan")):
+        """rp_stream_batch_set_filters (before the first process call)"""
+        rc = RustpotterConfig()
+        rc.filters = filters
+        f = rc._filters_c()
+        if self._L.rp_stream_batch_set_filters(self._h, C.byref(f), rms_level_ref) < 0:
+            raise _err()
+
+    def levels(self):
+        """rp_stream_batch_levels -> (rms, gains), each [S][n_chunks of the last process call]"""
+        import numpy as np
+        assert self.ctx.host
+        n = max(self._last_chunks, 1)
+        rms = np.empty((self.S, n), np.float32)
+        gains = np.empty((self.S, n), np.float32)
+        if self._L.rp_stream_batch_levels(self._h, rms.ctypes.data, gains.ctypes.data) < 0:
+            raise _err()
+        return rms, gains
 
     def process(self, pcm, max_det=4, want_agg=False, n_chunks=None):
         """pcm [S][n_chunks*480] numpy (i8 / i16 / i32 / f32) -> (det, n_det[, agg]) for these chunks.  With n_chunks
@@ -563,6 +597,7 @@ class StreamBatch:
         if self._L.rp_stream_batch_process(self._h, pcm.ctypes.data, fmt, nc, N, det.ctypes.data, n_det.ctypes.data, max_det,
                                            None if agg is None else agg.ctypes.data) < 0:
             raise _err()
+        self._last_chunks = nc
         return (det, n_det, agg) if want_agg else (det, n_det)
 
     def process_multi(self, pcm, max_det=4, n_chunks=None):
@@ -585,11 +620,13 @@ class StreamBatch:
         if self._L.rp_stream_batch_process_multi(self._h, pcm.ctypes.data, fmt, nc, N, det.ctypes.data, dww.ctypes.data, dlab.ctypes.data,
                                                  n_det.ctypes.data, max_det) < 0:
             raise _err()
+        self._last_chunks = nc
         return det, dww, dlab, n_det
 
     def process_dev(self, pcm_ptr, fmt, n_chunks, stride, det_ptr, n_det_ptr, max_det, agg_ptr=None):
         if self._L.rp_stream_batch_process(self._h, pcm_ptr, fmt, n_chunks, stride, det_ptr, n_det_ptr, max_det, agg_ptr) < 0:
             raise _err()
+        self._last_chunks = n_chunks
 
     def reset(self, stream=-1):
         if self._L.rp_stream_batch_reset(self._h, stream) < 0:

@@ -57,6 +57,15 @@ struct rp_stream_batch {
     const Resampler *rs = nullptr;
     DevBuf rs_prev[2], rs_xs, rs_out;
     int rs_cur = 0;
+    // RustpotterConfig.filters of the streams (rp_stream_batch_set_filters): both filters' state by stream, and the chunk levels /
+    // gains [S][levels_chunks] of the last call
+    bool has_filters = false;
+    rp_filters_config filt{};
+    float rms_level_ref = 0.f, bq[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    int gain_window = 1;
+    DevBuf filt_state, lv_rms, lv_gain;
+    size_t levels_chunks = 0;
+    bool filters_on() const { return has_filters && (filt.gain_normalizer.enabled || filt.band_pass.enabled); }
 };
 
 static void fill_detection(rp_detector *d, const Detection &src, rp_detection *out) {
@@ -445,6 +454,21 @@ int rp_wakeword_model_train(rp_ctx *ctx, const rp_train_options *options, size_t
     });
 }
 
+// BandPassFilter::new, band_pass_filter.rs:31-55 (f32, sample rate 16 kHz): q = a0 a1 a2 b1 b2, zeros when the filter is off
+static void band_pass_coefficients(const rp_band_pass_config &b, float q[5]) {
+    float a0 = 0, a1 = 0, a2 = 0, b1 = 0, b2 = 0;
+    if (b.enabled) {
+        const float kPi = 3.14159274101257324f, sample_rate = 16000.f;
+        const float omega_low = 2.0f * kPi * b.low_cutoff / sample_rate, omega_high = 2.0f * kPi * b.high_cutoff / sample_rate;
+        const float cos_low = std::cos(omega_low), cos_high = std::cos(omega_high);
+        const float alpha_low = std::sin(omega_low) / 2.0f, alpha_high = std::sin(omega_high) / 2.0f;
+        a0 = 1.0f / (1.0f + alpha_high - alpha_low);
+        a1 = -2.0f * cos_low * a0; a2 = (1.0f - alpha_high - alpha_low) * a0;
+        b1 = -2.0f * cos_high * a0; b2 = (1.0f - alpha_high + alpha_low) * a0;
+    }
+    q[0] = a0; q[1] = a1; q[2] = a2; q[3] = b1; q[4] = b2;
+}
+
 int rp_frontend_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                       const rp_filters_config *filters, float rms_level_ref, size_t window_size, float *pcm_out,
                       size_t out_stride, float *rms, float *gains) {
@@ -460,17 +484,9 @@ int rp_frontend_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t
         if (g.enabled && g.has_gain_ref) rms_level_ref = g.gain_ref;  // fixed_rms_level, gain_normalizer_filter.rs:56-66
         if (window_size == 0) window_size = 1;                           // set_rms_level_ref :47
         if (window_size > 1u << 20) { set_last_error("window_size too large"); return -1; }
-        // BandPassFilter::new, band_pass_filter.rs:31-55 (f32, sample rate 16 kHz)
-        float a0 = 0, a1 = 0, a2 = 0, b1 = 0, b2 = 0;
-        if (b.enabled) {
-            const float kPi = 3.14159274101257324f, sample_rate = 16000.f;
-            const float omega_low = 2.0f * kPi * b.low_cutoff / sample_rate, omega_high = 2.0f * kPi * b.high_cutoff / sample_rate;
-            const float cos_low = std::cos(omega_low), cos_high = std::cos(omega_high);
-            const float alpha_low = std::sin(omega_low) / 2.0f, alpha_high = std::sin(omega_high) / 2.0f;
-            a0 = 1.0f / (1.0f + alpha_high - alpha_low);
-            a1 = -2.0f * cos_low * a0; a2 = (1.0f - alpha_high - alpha_low) * a0;
-            b1 = -2.0f * cos_high * a0; b2 = (1.0f - alpha_high + alpha_low) * a0;
-        }
+        float q[5];
+        band_pass_coefficients(b, q);
+        const float a0 = q[0], a1 = q[1], a2 = q[2], b1 = q[3], b2 = q[4];
         const size_t n_chunks = n_samples / 480;
         Staged sg(c);
         const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
@@ -930,6 +946,9 @@ int rp_stream_batch_new(rp_ctx *ctx, const rp_templates *t, const rp_detector_co
 void rp_stream_batch_free(rp_stream_batch *b) { delete b; }
 size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b) { return b ? b->chunks_seen : 0; }
 
+static const char kFiltersNeed30ms[] = "filters on a live-stream batch need 30 ms input frames: not available with the 40 ms frames of "
+                                       "11.025 / 22.05 kHz input (rp_stream_batch_set_filters / rp_stream_batch_set_input)";
+
 int rp_stream_batch_set_input(rp_stream_batch *b, size_t sample_rate, int channels) {
     return guarded([&]() -> int {
         if (!b) { set_last_error("null handle"); return -1; }
@@ -939,6 +958,7 @@ int rp_stream_batch_set_input(rp_stream_batch *b, size_t sample_rate, int channe
         if (channels < 1) { set_last_error("Unsupported channel count"); return -1; }
         size_t fi = 480, fo = 480;
         if (!resampler_frame_lengths(sample_rate, &fi, &fo)) { set_last_error("Unsupported sample rate, unable to initialize the resampler"); return -1; }
+        if (b->has_filters && fo != 480) { set_last_error(kFiltersNeed30ms); return -1; }
         b->channels = channels; b->in_len = fi; b->rs = nullptr;
         if (fo != b->out_len) {  // 11.025 / 22.05 kHz: 40 ms frames of four 10 ms shifts
             b->out_len = fo;
@@ -957,6 +977,54 @@ int rp_stream_batch_set_input(rp_stream_batch *b, size_t sample_rate, int channe
     });
 }
 size_t rp_stream_batch_samples_per_chunk(const rp_stream_batch *b) { return b ? b->in_len * (size_t)b->channels : 0; }
+
+int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref) {
+    return guarded([&]() -> int {
+        if (!b) { set_last_error("null handle"); return -1; }
+        if (!filters) { set_last_error("null argument"); return -1; }
+        Ctx *c = b->c;
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
+        if (b->chunks_seen) { set_last_error("rp_stream_batch_set_filters: the streams have already received audio"); return -1; }
+        if (b->out_len != 480) { set_last_error(kFiltersNeed30ms); return -1; }
+        const rp_gain_normalization_config &g = filters->gain_normalizer;
+        const int window = std::max(b->max_len / 3, 1);   // on_wakeword_change, src/detector.rs:337; set_rms_level_ref :47
+        const size_t lv = b->S * b->max_chunks * sizeof(float) + 16, st = stream_filter_state_bytes(b->S, window);
+        if (!b->filt_state.reserve(st) || !b->lv_rms.reserve(lv) || !b->lv_gain.reserve(lv)) return -1;
+        if (!hip_ok(hipMemsetAsync(b->filt_state.p, 0, st, c->stream), "hipMemsetAsync")) return -1;
+        b->filt = *filters;
+        b->rms_level_ref = g.enabled && g.has_gain_ref ? g.gain_ref : rms_level_ref;  // fixed_rms_level, gain_normalizer_filter.rs:56-66
+        b->gain_window = window;
+        band_pass_coefficients(filters->band_pass, b->bq);
+        b->has_filters = true;
+        return 0;
+    });
+}
+
+int rp_stream_batch_levels(rp_stream_batch *b, float *rms, float *gains) {
+    return guarded([&]() -> int {
+        if (!b) { set_last_error("null handle"); return -1; }
+        Ctx *c = b->c;
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
+        if (!b->has_filters) { set_last_error("rp_stream_batch_levels: the batch has had no rp_stream_batch_set_filters"); return -1; }
+        if (!b->levels_chunks) { set_last_error("rp_stream_batch_levels: the streams have not received audio yet"); return -1; }
+        const size_t n = b->S * b->levels_chunks;
+        const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
+        const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (rms && !hip_ok(hipMemcpyAsync(rms, b->lv_rms.p, n * sizeof(float), kind, c->stream), "hipMemcpyAsync")) return -1;
+        if (gains) {
+            if (b->filters_on()) {
+                if (!hip_ok(hipMemcpyAsync(gains, b->lv_gain.p, n * sizeof(float), kind, c->stream), "hipMemcpyAsync")) return -1;
+            } else {  // both filters off: every chunk has gain 1
+                std::vector<float> ones(n, 1.f);
+                if (host) std::memcpy(gains, ones.data(), n * sizeof(float));
+                else if (!hip_ok(hipMemcpy(gains, ones.data(), n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) return -1;
+            }
+        }
+        return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
+    });
+}
 
 int rp_stream_batch_reset(rp_stream_batch *b, long long stream) {
     return guarded([&]() -> int {
@@ -1031,6 +1099,15 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
         // 16 kHz mono input is read where it lies: the MFCC kernel takes [history chunk | new chunks] from two buffers and
         // leaves the last chunk as the next call's history.  Other inputs are staged into one row per stream first.
         bool staged = false;
+        const bool filtered = b->filters_on();
+        // with filters, ONE launch in the place of launch_stream_stage: history chunk | the new chunks decoded and filtered, levels kept
+        auto stage_filtered = [&](const void *src, int src_fmt, int src_channels, size_t src_stride) {
+            const rp_gain_normalization_config &g = b->filt.gain_normalizer;
+            return hip_ok(launch_stream_filters(c->stream, src, src_fmt, src_channels, S, n_chunks, src_stride, hp_old, b->last_off, hp, pcm_pitch,
+                                                g.enabled ? 1 : 0, b->rms_level_ref, g.min_gain, g.max_gain, b->gain_window,
+                                                b->filt.band_pass.enabled ? 1 : 0, b->bq[0], b->bq[1], b->bq[2], b->bq[3], b->bq[4],
+                                                b->filt_state.as<float>(), b->lv_rms.as<float>(), b->lv_gain.as<float>()), "stream_filters_kernel");
+        };
         if (b->rs) {  // previous input frame | new input frames -> 16 kHz (the resampler never resets, src/detector.rs:290-302)
             const size_t fi = b->in_len;
             float *ro = b->rs_out.as<float>();
@@ -1047,7 +1124,11 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
                 if (!hip_ok(launch_carry_rows(c->stream, xs, S, (1 + n_chunks) * fi, n_chunks * fi, fi, pn, fi), "carry_rows_kernel")) return -1;
             }
             b->rs_cur ^= 1;
-            if (!hip_ok(launch_stream_stage(c->stream, ro, 3, 1, S, new_len, new_len, hp_old, b->last_off, hp, pcm_pitch), "stream_stage_kernel")) return -1;
+            if (filtered) { if (!stage_filtered(ro, 3, 1, new_len)) return -1; }
+            else if (!hip_ok(launch_stream_stage(c->stream, ro, 3, 1, S, new_len, new_len, hp_old, b->last_off, hp, pcm_pitch), "stream_stage_kernel")) return -1;
+            staged = true;
+        } else if (filtered) {
+            if (!stage_filtered(dp, (int)fmt, b->channels, pcm_stride)) return -1;
             staged = true;
         } else if (b->channels != 1) {  // previous chunk | new chunks (first channel), decoded to f32
             if (!hip_ok(launch_stream_stage(c->stream, dp, (int)fmt, b->channels, S, new_len, pcm_stride, hp_old, b->last_off, hp, pcm_pitch), "stream_stage_kernel")) return -1;
@@ -1080,6 +1161,13 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
                 return -1;
         }
         b->fill += n_new;
+        if (b->has_filters) {
+            // filters configured but both off: today's launches above, and the levels of the unfiltered chunks for rp_stream_batch_levels
+            if (!filtered && !hip_ok(staged ? launch_chunk_rms(c->stream, hp + 480, 3, S, n_chunks, pcm_pitch, b->lv_rms.as<float>())
+                                            : launch_chunk_rms(c->stream, dp, (int)fmt, S, n_chunks, pcm_stride, b->lv_rms.as<float>()),
+                                     "chunk_rms_kernel")) return -1;
+            b->levels_chunks = n_chunks;
+        }
         if (multi) {
             if (stream_batch_score_multi(b, sg, now, fill, n_new, dd, dn, max_det, det_wakeword, det_label) != 0) return -1;
         } else {

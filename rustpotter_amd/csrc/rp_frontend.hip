@@ -1,5 +1,7 @@
 // rp_frontend.hip -- decode + GainNormalizerFilter + BandPassFilter over whole streams
 // (src/audio/gain_normalizer_filter.rs:14-55, src/audio/band_pass_filter.rs:19-55, src/detector.rs:358-371).
+#include <type_traits>
+
 #include "rp_device.h"
 
 namespace rp {
@@ -396,5 +398,281 @@ hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, s
 #undef RP_FE
     return hipErrorInvalidValue;
 }
+
+// The chunk RMS alone (get_rms_level) of rows that hold whole chunks: what a live-stream batch reports when its filters are
+// configured but both disabled.
+hipError_t launch_chunk_rms(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_chunks, size_t pcm_stride, float *rms) {
+    const size_t n = S * n_chunks;
+    if (n == 0) return hipSuccess;
+    if ((n + 255) / 256 > 0x7fffffffULL) return hipErrorInvalidValue;
+#define RP_RMS(T)                                                                                                                       \
+    do {                                                                                                                                \
+        const int vec4 = reinterpret_cast<uintptr_t>(pcm) % (4 * sizeof(T)) == 0 && pcm_stride % 4 == 0;                               \
+        hipLaunchKernelGGL(chunk_rms_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const T *>(pcm), S,    \
+                           n_chunks, pcm_stride, vec4, rms);                                                                            \
+    } while (0)
+    switch (fmt) {
+    case 0: RP_RMS(int8_t); break;
+    case 1: RP_RMS(int16_t); break;
+    case 2: RP_RMS(int32_t); break;
+    case 3: RP_RMS(float); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef RP_RMS
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------- live-stream batches
+// The same filters for the streams of a live batch (rp_stream_batch_set_filters): ONE launch per process call that copies the history
+// chunk of every stream into its new row, decodes the call's n_chunks new chunks (first channel), computes each chunk's RMS, advances
+// the gain window, applies gain + biquad and writes the f32 result behind the history chunk -- the row launch_stream_stage writes for a
+// batch without filters -- with the state of both filters carried per stream from call to call (StreamFilterState, arrays by stream).
+// A wave owns 64 streams, lane = stream, and walks time serially; HBM is read and written along time through an LDS tile of 64 rows x
+// 96 samples (the slice and pitch of chunk_rms_staged_kernel: five slices per chunk, rows filled 24 lanes at a time, columns walked with
+// conflict-free 16-byte reads), the next slice travelling while this one is walked.
+// The gain of a chunk exists only after its 480 samples are summed.  Of the three ways to have the samples again afterwards -- the whole
+// chunk of 64 streams in LDS as f32 (124 KB: one wave per CU), 32 streams per wave (62 KB, half the lanes of the serial walk idle), or a
+// second read of the chunk -- this kernel takes the second read: the 61 KB (i16) / 123 KB (f32) a wave has just summed are in L2 when it
+// comes back for them, the tile stays at 25.6 KB (six waves per CU where the batch has that many; 65 536 streams are one wave per SIMD),
+// and input that is not i16 needs no other arrangement.  With the gain normaliser off (GAIN false) there is nothing to wait for: the RMS
+// is summed in the walk that filters, one pass.
+// Sums as the reference orders them, per lane: sum_squared over a chunk's samples in index order, the window mean oldest first.
+struct StreamFilterState {
+    float *x1, *x2, *y1, *y2;  // BandPassFilter [S] each
+    float *ring;               // GainNormalizerFilter::rms_level_window as a ring [window_size][S]
+    int *head, *len;           // [S]: the oldest entry and the number of entries
+};
+
+template <class TIN, bool VEC, bool GAIN, bool BP>
+__global__ __launch_bounds__(64) void stream_filters_kernel(const TIN *__restrict__ pcm, int channels, size_t S, size_t n_chunks,
+                                                            size_t pcm_stride, const float *__restrict__ old_hist, size_t old_off,
+                                                            float *__restrict__ hist, size_t hist_pitch, float rms_level_ref,
+                                                            float min_gain, float max_gain, int window_size, BiquadCoef q,
+                                                            StreamFilterState fs, float *__restrict__ rms, float *__restrict__ gains) {
+    constexpr int NSL = kFrame / kRmsSlice, LPR = kRmsSlice / 4, PASSES = GAIN ? 2 : 1;
+    static_assert(kRmsMoves % 3 == 0 && 192 % LPR == 0, "three moves cover whole rows");
+    __shared__ __attribute__((aligned(16))) float tile[64 * kRmsPitch];
+    const int lane = threadIdx.x;
+    const size_t s0 = (size_t)blockIdx.x * 64, s = s0 + lane;
+    const unsigned rows_here = s0 + 64 <= S ? 64u : (unsigned)(S - s0);  // the last workgroup may hold fewer than 64 streams:
+    const bool live = (unsigned)lane < rows_here;                         // its loads clamp the row, its stores test it
+    const size_t s_c = live ? s : S - 1;
+
+    // move it = 3 m + j of a slice: 16-byte group it * 64 + lane -> row 8 m + row3[j], column group c43[j].  Addresses are wave-uniform
+    // bases plus 32-bit lane offsets (the host checks that 64 rows fit): three of each kind serve the 24 moves
+    const bool FULL = rows_here == 64;  // workgroup-uniform
+    const unsigned in_pitch = (unsigned)pcm_stride, out_pitch = (unsigned)hist_pitch;
+    unsigned row3[3], c43[3], in3[3], out3[3], lds3[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        row3[j] = (64u * j + lane) / LPR; c43[j] = (64u * j + lane) % LPR;
+        in3[j] = row3[j] * in_pitch + 4 * c43[j] * (unsigned)channels;
+        out3[j] = row3[j] * out_pitch + 4 * c43[j];
+        lds3[j] = row3[j] * kRmsPitch + 4 * c43[j];
+    }
+    const TIN *in_base = pcm + s0 * pcm_stride;
+    float *out_base = hist + s0 * hist_pitch + kFrame;
+    using Raw4 = typename SampleIn<TIN>::Raw4;
+    typename std::conditional<VEC, Raw4, float4>::type r[kRmsMoves];
+    auto fetch = [&](size_t t) {
+        const size_t c = t / (PASSES * NSL), col = c * kFrame + (t % NSL) * kRmsSlice;
+#pragma unroll
+        for (int it = 0; it < kRmsMoves; ++it) {
+            const TIN *p;
+            if (FULL) p = in_base + ((size_t)(8 * (it / 3)) * pcm_stride + col * (size_t)channels) + in3[it % 3];
+            else {  // rows past S re-read the last stream
+                const unsigned row = 8u * (it / 3) + row3[it % 3], rc = row < rows_here ? row : rows_here - 1;
+                p = in_base + col * (size_t)channels + (rc * in_pitch + 4 * c43[it % 3] * (unsigned)channels);
+            }
+            if constexpr (VEC) r[it] = SampleIn<TIN>::ldraw(p);
+            else r[it] = make_float4(SampleIn<TIN>::cvt(p[0]), SampleIn<TIN>::cvt(p[channels]), SampleIn<TIN>::cvt(p[2 * channels]),
+                                     SampleIn<TIN>::cvt(p[3 * channels]));
+        }
+    };
+    float x1 = 0.f, x2 = 0.f, y1 = 0.f, y2 = 0.f;
+    if (BP) { x1 = fs.x1[s_c]; x2 = fs.x2[s_c]; y1 = fs.y1[s_c]; y2 = fs.y2[s_c]; }
+    int head = 0, len = 0;
+    if (GAIN) { head = fs.head[s_c]; len = fs.len[s_c]; }
+    float *w = fs.ring + s_c;  // entry i of this stream: w[i * S]
+    const float rms_level_sqrt = sqrtf(rms_level_ref);
+    float g = 1.f, sum_squared = 0.f;
+    auto one = [&](float v) {  // as apply_filters_lines_kernel
+        if (GAIN) {
+            float u = v * g; u = u < -1.f ? -1.f : u; u = u > 1.f ? 1.f : u;
+            v = g != 1.f ? u : v;
+        }
+        if (BP) {
+            const float f = q.a0 * v + q.a1 * x1 + q.a2 * x2 - q.b1 * y1 - q.b2 * y2;
+            x2 = x1; x1 = v; y2 = y1; y1 = f;
+            v = f;
+        }
+        return v;
+    };
+    float *mine = tile + lane * kRmsPitch;
+    const size_t n_steps = n_chunks * PASSES * NSL;
+    fetch(0);
+    {   // the history chunk: the last 480 samples of the previous call's row open this call's row; kHistMoves loads in flight per lane
+        // (one at a time, the 120 moves of a lane cost a 30 ms call more than all the rest of this kernel)
+        constexpr unsigned kHistMoves = 12, kRowMoves = kFrame / 4;
+        const unsigned lim = rows_here * kRowMoves;
+        const float *src = old_hist + s0 * hist_pitch + old_off;
+        float *dst = hist + s0 * hist_pitch;
+#pragma unroll 1
+        for (unsigned g0 = lane; g0 < 64 * kRowMoves; g0 += 64 * kHistMoves) {
+            f32x4 v[kHistMoves];
+            unsigned off[kHistMoves];
+#pragma unroll
+            for (unsigned i = 0; i < kHistMoves; ++i) {
+                const unsigned gi = g0 + 64 * i, row = gi / kRowMoves;
+                off[i] = row * out_pitch + 4 * (gi - row * kRowMoves);
+                if (gi < lim) v[i] = *reinterpret_cast<const f32x4 *>(src + off[i]);
+            }
+#pragma unroll
+            for (unsigned i = 0; i < kHistMoves; ++i)
+                if (g0 + 64 * i < lim) *reinterpret_cast<f32x4 *>(dst + off[i]) = v[i];
+        }
+    }
+#pragma unroll 1
+    for (size_t t = 0; t < n_steps; ++t) {
+        const size_t c = t / (PASSES * NSL);
+        const int ph = (int)(t - c * (PASSES * NSL)), sl = ph % NSL;
+        const bool summing = !GAIN || ph < NSL, applying = !GAIN || ph >= NSL;
+#pragma unroll
+        for (int it = 0; it < kRmsMoves; ++it) {
+            float4 f;
+            if constexpr (VEC) f = SampleIn<TIN>::cvt4(r[it]);
+            else f = r[it];
+            *reinterpret_cast<f32x4 *>(&tile[8 * (it / 3) * kRmsPitch + lds3[it % 3]]) = f32x4{f.x, f.y, f.z, f.w};
+        }
+        if (t + 1 < n_steps) fetch(t + 1);
+        wave_lds_sync();
+        if (ph == 0) sum_squared = 0.f;
+        if (GAIN && summing) {
+#pragma unroll
+            for (int k0 = 0; k0 < kRmsSlice; k0 += 24) {
+                f32x4 v[6];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) v[j] = *reinterpret_cast<const f32x4 *>(mine + k0 + 4 * j);
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    sum_squared += v[j].x * v[j].x; sum_squared += v[j].y * v[j].y;
+                    sum_squared += v[j].z * v[j].z; sum_squared += v[j].w * v[j].w;
+                }
+            }
+        } else {
+#pragma unroll 1
+            for (int k0 = 0; k0 < kRmsSlice; k0 += 16) {
+                f32x4 v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const f32x4 *>(mine + k0 + 4 * j);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!GAIN) {
+                        sum_squared += v[j].x * v[j].x; sum_squared += v[j].y * v[j].y;
+                        sum_squared += v[j].z * v[j].z; sum_squared += v[j].w * v[j].w;
+                    }
+                    v[j].x = one(v[j].x); v[j].y = one(v[j].y); v[j].z = one(v[j].z); v[j].w = one(v[j].w);
+                    *reinterpret_cast<f32x4 *>(mine + k0 + 4 * j) = v[j];
+                }
+            }
+        }
+        wave_lds_sync();
+        if (summing && sl == NSL - 1) {  // get_rms_level of the unfiltered chunk, then GainNormalizerFilter::filter as gain_kernel
+            const float level = sqrtf(sum_squared / (float)kFrame);
+            float gain = 1.f;
+            if (GAIN && live && !(rms_level_ref != rms_level_ref) && level != 0.f) {
+                if (len < window_size) { const int u = head + len; w[(size_t)(u >= window_size ? u - window_size : u) * S] = level; ++len; }
+                else { w[(size_t)head * S] = level; head = head + 1 == window_size ? 0 : head + 1; }  // push + drain(0..1)
+                float sum = 0.f;  // oldest first, the order of iter().sum()
+                int u = head;
+                for (int i = 0; i < len; ++i) { sum += w[(size_t)u * S]; u = u + 1 == window_size ? 0 : u + 1; }
+                const float frame_rms_level = sum / (float)len;
+                gain = rms_level_sqrt / sqrtf(frame_rms_level);
+                gain = roundf(gain * 10.f) / 10.f;
+                gain = gain < min_gain ? min_gain : gain;  // f32::clamp
+                gain = gain > max_gain ? max_gain : gain;
+            }
+            g = gain;
+            if (live) { rms[s * n_chunks + c] = level; gains[s * n_chunks + c] = gain; }
+        }
+        if (applying) {  // the filtered slice: LDS rows -> the batch's row, behind the history chunk
+            const size_t col = c * kFrame + (size_t)sl * kRmsSlice;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                f32x4 o[kRmsMoves / 2];
+#pragma unroll
+                for (int i = 0; i < kRmsMoves / 2; ++i) {
+                    const int it = h * (kRmsMoves / 2) + i;
+                    o[i] = *reinterpret_cast<const f32x4 *>(&tile[8 * (it / 3) * kRmsPitch + lds3[it % 3]]);
+                }
+#pragma unroll
+                for (int i = 0; i < kRmsMoves / 2; ++i) {
+                    const int it = h * (kRmsMoves / 2) + i;
+                    float *p = out_base + ((size_t)(8 * (it / 3)) * hist_pitch + col) + out3[it % 3];
+                    if (FULL || 8u * (it / 3) + row3[it % 3] < rows_here) *reinterpret_cast<f32x4 *>(p) = o[i];
+                }
+            }
+            wave_lds_sync();
+        }
+    }
+    if (live) {
+        if (BP) { fs.x1[s] = x1; fs.x2[s] = x2; fs.y1[s] = y1; fs.y2[s] = y2; }
+        if (GAIN) { fs.head[s] = head; fs.len[s] = len; }
+    }
+}
+
+template <class TIN>
+static hipError_t launch_stream_filters_t(hipStream_t st, const TIN *pcm, int channels, size_t S, size_t n_chunks, size_t pcm_stride,
+                                          const float *old_hist, size_t old_off, float *hist, size_t hist_pitch, int gain_on,
+                                          float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass,
+                                          BiquadCoef q, const StreamFilterState &fs, float *rms, float *gains) {
+    const bool vec = channels == 1 && reinterpret_cast<uintptr_t>(pcm) % (4 * sizeof(TIN)) == 0 && pcm_stride % 4 == 0;
+    const dim3 grid((unsigned)((S + 63) / 64)), block(64);
+#define RP_SF(V, G, B)                                                                                                                  \
+    hipLaunchKernelGGL((stream_filters_kernel<TIN, V, G, B>), grid, block, 0, st, pcm, channels, S, n_chunks, pcm_stride, old_hist,     \
+                       old_off, hist, hist_pitch, rms_level_ref, min_gain, max_gain, window_size, q, fs, rms, gains)
+#define RP_SF_V(G, B)                                                                                                                   \
+    do {                                                                                                                                \
+        if (vec) RP_SF(true, G, B);                                                                                                     \
+        else RP_SF(false, G, B);                                                                                                        \
+    } while (0)
+    if (gain_on && band_pass) RP_SF_V(true, true);
+    else if (gain_on) RP_SF_V(true, false);
+    else RP_SF_V(false, true);
+#undef RP_SF_V
+#undef RP_SF
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_filters(hipStream_t st, const void *pcm, int fmt, int channels, size_t S, size_t n_chunks, size_t pcm_stride,
+                                 const float *old_hist, size_t old_off, float *hist, size_t hist_pitch, int gain_on,
+                                 float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
+                                 float a1, float a2, float b1, float b2, float *filter_state, float *rms, float *gains) {
+    if (S == 0 || n_chunks == 0) return hipSuccess;
+    if (!gain_on && !band_pass) return hipErrorInvalidValue;  // such a batch keeps its unfiltered launches
+    if (channels < 1 || window_size < 1 || (S + 63) / 64 > 0x7fffffffULL) return hipErrorInvalidValue;
+    // 32-bit lane offsets inside a wave's 64 rows
+    if (pcm_stride >= kStreamFiltersMaxPitch || hist_pitch >= kStreamFiltersMaxPitch || (size_t)channels > kStreamFiltersMaxPitch / 512)
+        return hipErrorInvalidValue;
+    // 16-byte accesses to the batch's rows
+    if (hist_pitch % 4 || old_off % 4 || reinterpret_cast<uintptr_t>(hist) % 16 || reinterpret_cast<uintptr_t>(old_hist) % 16)
+        return hipErrorInvalidValue;
+    StreamFilterState fs;
+    fs.x1 = filter_state; fs.x2 = fs.x1 + S; fs.y1 = fs.x2 + S; fs.y2 = fs.y1 + S;
+    fs.head = reinterpret_cast<int *>(fs.y2 + S); fs.len = fs.head + S;
+    fs.ring = reinterpret_cast<float *>(fs.len + S);
+    BiquadCoef q{a0, a1, a2, b1, b2};
+#define RP_SFT(T) launch_stream_filters_t<T>(st, static_cast<const T *>(pcm), channels, S, n_chunks, pcm_stride, old_hist, old_off, hist, \
+                                             hist_pitch, gain_on, rms_level_ref, min_gain, max_gain, window_size, band_pass, q, fs, rms, gains)
+    switch (fmt) {
+    case 0: return RP_SFT(int8_t);
+    case 1: return RP_SFT(int16_t);
+    case 2: return RP_SFT(int32_t);
+    case 3: return RP_SFT(float);
+    }
+#undef RP_SFT
+    return hipErrorInvalidValue;
+}
+size_t stream_filter_state_bytes(size_t S, int window_size) { return (6 + (size_t)window_size) * S * sizeof(float); }
 
 }  // namespace rp

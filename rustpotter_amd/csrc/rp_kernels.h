@@ -417,6 +417,19 @@ hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, s
                            float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
                            float a1, float a2, float b1, float b2, float *ring, float *rms, float *gains, float *out,
                            size_t out_stride);
+// get_rms_level of every chunk alone: rms [S][n_chunks] of rows pcm_stride samples apart
+hipError_t launch_chunk_rms(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_chunks, size_t pcm_stride, float *rms);
+// The same filters for the streams of a live batch, state carried from call to call: ONE launch that writes hist rows
+// [the last chunk of the previous call (old_hist row + old_off) | the n_chunks new chunks decoded (first of `channels`) and filtered]
+// -- launch_stream_stage's row, filtered -- and rms / gains [S][n_chunks] of the new chunks.  filter_state: stream_filter_state_bytes()
+// of device memory, zero before a stream's first chunk (biquad x1 x2 y1 y2, gain window head / length, the window ring, by stream).
+// At least one of gain_on / band_pass.
+hipError_t launch_stream_filters(hipStream_t st, const void *pcm, int fmt, int channels, size_t S, size_t n_chunks, size_t pcm_stride,
+                                 const float *old_hist, size_t old_off, float *hist, size_t hist_pitch, int gain_on,
+                                 float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
+                                 float a1, float a2, float b1, float b2, float *filter_state, float *rms, float *gains);
+size_t stream_filter_state_bytes(size_t S, int window_size);
+constexpr size_t kStreamFiltersMaxPitch = (size_t)1 << 25;  // rows (pcm_stride, hist_pitch) must be shorter than this many samples
 
 // Resampler front-end.  Stage: decode + first channel + history -> xs [S][(1+n_chunks)*fi] f32 (prev [S][fi] or
 // nullptr = silence before the stream); resample: xs -> out [S][n_chunks*fo].
