@@ -2,12 +2,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <system_error>
 #include <chrono>
 #include <thread>
 
-#include "rp_host.h"
+#include "rp_capi.h"
 
 namespace rp { const std::string &last_error(); }
 
@@ -18,54 +17,6 @@ struct rp_detector {
     // storage backing the last rp_detection handed out
     Detection last;
     std::vector<const char *> name_ptrs;
-};
-struct rp_ctx { std::unique_ptr<Ctx> impl; };
-struct rp_templates { std::unique_ptr<Templates> impl; };
-struct rp_model { std::unique_ptr<Model> impl; };
-// one wakeword of a live-stream batch that holds several (rp_stream_batch_new_multi): a reference or a model
-struct StreamWakeword {
-    const Templates *t = nullptr;
-    Model *m = nullptr;
-    int none_index = -1, precision = 0;
-    float threshold = 0.f, avg_threshold = 0.f;   // the wakeword's own values (the config's where it has none)
-    DevBuf agg, avg, label;                       // [S][frames per call] of this wakeword
-};
-
-struct rp_stream_batch {
-    Ctx *c = nullptr;
-    const Templates *t = nullptr;                 // the one wakeword reference of rp_stream_batch_new; nullptr with `ww`
-    std::vector<std::unique_ptr<StreamWakeword>> ww;  // rp_stream_batch_new_multi: 1..8 wakewords
-    int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
-    DevBuf det_ww, det_label, logits, mean, xrows, xs2;
-    rp_detector_config cfg{};
-    size_t S = 0, max_chunks = 0, chunks_seen = 0, hist_frames = 0;
-    bool poisoned = false;   // a launch failed after part of the persistent state had advanced
-    // MFCC window: rows of `cap` frames; a call appends its frames behind the `fill` valid ones and only when a row
-    // is full are the last max_len-1 frames moved to the front of the other buffer
-    int cur = 0;
-    size_t cap = 0, fill = 0;
-    // previous chunk | new chunks (f32), ping-pong so that one kernel both carries the old chunk and decodes the new
-    int pcur = 0;
-    size_t last_off = 0;     // where the last chunk of the previous call sits in pcm[pcur]'s rows
-    DevBuf pcm[2], mfcc[2], state, scores, agg, avg, vad, list;
-    // AudioEncoder of the streams (src/audio/encoder.rs): channel count and, for input that is not 16 kHz, the
-    // resampler plan with every stream's previous input frame
-    int channels = 1;
-    size_t in_len = 480;
-    size_t out_len = 480;    // encoded (16 kHz) samples per input frame: 480, or 640 for the 11.025 / 22.05 kHz family
-    size_t fpf() const { return out_len / 160; }  // MFCC frames a stream gains per input frame (3 or 4)
-    const Resampler *rs = nullptr;
-    DevBuf rs_prev[2], rs_xs, rs_out;
-    int rs_cur = 0;
-    // RustpotterConfig.filters of the streams (rp_stream_batch_set_filters): both filters' state by stream, and the chunk levels /
-    // gains [S][levels_chunks] of the last call
-    bool has_filters = false;
-    rp_filters_config filt{};
-    float rms_level_ref = 0.f, bq[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    int gain_window = 1;
-    DevBuf filt_state, lv_rms, lv_gain;
-    size_t levels_chunks = 0;
-    bool filters_on() const { return has_filters && (filt.gain_normalizer.enabled || filt.band_pass.enabled); }
 };
 
 static void fill_detection(rp_detector *d, const Detection &src, rp_detection *out) {
@@ -80,21 +31,6 @@ static void fill_detection(rp_detector *d, const Detection &src, rp_detection *o
     out->scores = d->last.scores.data();
     out->counter = d->last.counter;
     out->gain = d->last.gain;
-}
-
-template <class F> static int guarded(F &&f) {
-    try { return f(); }
-    catch (const std::bad_alloc &) { set_last_error("out of host memory"); return -1; }
-    catch (const std::exception &e) { set_last_error(e.what()); return -1; }
-    catch (...) { set_last_error("unknown error"); return -1; }
-}
-
-// one launch, timed as `kernel` when the context times its kernels (rp_ctx_timing_enable)
-template <class F> static bool timed(Ctx *c, int kernel, const char *what, F &&launch) {
-    c->time_begin(kernel);
-    const bool ok = hip_ok(launch(), what);
-    c->time_end();
-    return ok;
 }
 
 extern "C" {
@@ -279,33 +215,6 @@ size_t rp_mfcc_num_frames(size_t n_samples) {
 }
 
 namespace {
-struct Staged {  // host<->device staging for RP_CTX_HOST_POINTERS
-    Ctx *c;
-    bool host;
-    explicit Staged(Ctx *ctx) : c(ctx), host((ctx->flags & RP_CTX_HOST_POINTERS) != 0) {}
-    const void *in(const void *p, size_t bytes, DevBuf &buf) {
-        if (!host || !p) return p;
-        if (!buf.reserve(bytes)) return nullptr;
-        if (!hip_ok(hipMemcpyAsync(buf.p, p, bytes, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(H2D)")) return nullptr;
-        return buf.p;
-    }
-    void *out(void *p, size_t bytes, DevBuf &buf) {
-        if (!host || !p) return p;
-        return buf.reserve(bytes) ? buf.p : nullptr;
-    }
-    bool back(void *host_p, const void *dev_p, size_t bytes) {
-        if (!host || !host_p) return true;
-        return hip_ok(hipMemcpyAsync(host_p, dev_p, bytes, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(D2H)");
-    }
-    bool finish() { return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize"); }
-    // det [S][max_det] and n_det [S], then the int32 column per detection `col` (det_wakeword / det_label) when there is one
-    bool back_detections(size_t S, int max_det, rp_batch_detection *det, const BatchDetection *dd, int32_t *n_det, const int32_t *dn,
-                         int32_t *col = nullptr, const int32_t *dcol = nullptr) {
-        return back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) && back(n_det, dn, S * sizeof(int32_t)) &&
-               (!dcol || back(col, dcol, S * (size_t)max_det * sizeof(int32_t)));
-    }
-};
-
 // whole-stream detection after detect_front: device det / n_det, the MFCC frames ws_mfcc [S][nf][K], windows per stream
 struct DetectFront {
     BatchDetection *dd = nullptr;
@@ -315,35 +224,15 @@ struct DetectFront {
 };
 }  // namespace
 
-static size_t sample_bytes(rp_sample_format f) { return f == RP_SAMPLE_I8 ? 1 : f == RP_SAMPLE_I16 ? 2 : 4; }
-static float vad_mode_value(rp_vad_mode m) { return m == RP_VAD_EASY ? 2.f : m == RP_VAD_MEDIUM ? 2.5f : 3.f; }  // src/config.rs:140-146
-
-static bool sample_format_ok(rp_sample_format fmt) {
-    if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return false; }
-    return true;
-}
 // whole streams of n_samples samples, pcm_stride apart
 static bool pcm_args_ok(rp_sample_format fmt, size_t n_samples, size_t pcm_stride) {
     if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return false; }
     return sample_format_ok(fmt);
 }
-static bool mlp_precision_ok(int p) {
-    if (p != RP_MLP_F32 && p != RP_MLP_BF16 && p != RP_MLP_F32_STRICT && p != RP_MLP_F32_FAST) { set_last_error("unknown MLP precision"); return false; }
-    return true;
-}
 static int widest_layer(const Model &m) {
     int maxd = 0;
     for (int d : m.dims) maxd = std::max(maxd, d);
     return maxd;
-}
-
-// fpf 0: the ScanConfig default (whole streams, 30 ms frames)
-static ScanConfig scan_config(const rp_detector_config &cfg, int max_len, bool avg_enabled, int fpf = 0) {
-    ScanConfig sc;
-    sc.threshold = cfg.threshold; sc.avg_threshold = cfg.avg_threshold; sc.min_scores = (int)cfg.min_scores;
-    sc.eager = cfg.eager ? 1 : 0; sc.max_len = max_len; sc.avg_enabled = avg_enabled ? 1 : 0;
-    if (fpf) sc.fpf = fpf;
-    return sc;
 }
 
 // The front of whole-stream detection: checks the PCM arguments, stages the PCM in and det / n_det out and writes the MFCC frames of
@@ -452,21 +341,6 @@ int rp_wakeword_model_train(rp_ctx *ctx, const rp_train_options *options, size_t
         *out_rpw = p; *out_len = bytes.size();
         return 0;
     });
-}
-
-// BandPassFilter::new, band_pass_filter.rs:31-55 (f32, sample rate 16 kHz): q = a0 a1 a2 b1 b2, zeros when the filter is off
-static void band_pass_coefficients(const rp_band_pass_config &b, float q[5]) {
-    float a0 = 0, a1 = 0, a2 = 0, b1 = 0, b2 = 0;
-    if (b.enabled) {
-        const float kPi = 3.14159274101257324f, sample_rate = 16000.f;
-        const float omega_low = 2.0f * kPi * b.low_cutoff / sample_rate, omega_high = 2.0f * kPi * b.high_cutoff / sample_rate;
-        const float cos_low = std::cos(omega_low), cos_high = std::cos(omega_high);
-        const float alpha_low = std::sin(omega_low) / 2.0f, alpha_high = std::sin(omega_high) / 2.0f;
-        a0 = 1.0f / (1.0f + alpha_high - alpha_low);
-        a1 = -2.0f * cos_low * a0; a2 = (1.0f - alpha_high - alpha_low) * a0;
-        b1 = -2.0f * cos_high * a0; b2 = (1.0f - alpha_high + alpha_low) * a0;
-    }
-    q[0] = a0; q[1] = a1; q[2] = a2; q[3] = b1; q[4] = b2;
 }
 
 int rp_frontend_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
@@ -598,16 +472,6 @@ int rp_batch_detect(rp_ctx *ctx, const float *pcm, size_t S, size_t n_samples, s
 struct GatherTo { bool on = false, host = true; int device = 0; int stream_base = 0; bool device_pcm = false; };   // device_pcm: pcm is a device pointer whatever the context's flags say (rp_batch_detect_ingest)
 static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                              const rp_templates *t, const rp_detector_config *config, rp_batch_detection *det, int32_t *n_det,
-                             int max_det, float *scores, float *agg, const GatherTo &gather);
-
-int rp_batch_detect_fmt(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
-                        const rp_templates *t, const rp_detector_config *config, rp_batch_detection *det, int32_t *n_det,
-                        int max_det, float *scores, float *agg) {
-    return batch_detect_impl(ctx, pcm, fmt, S, n_samples, pcm_stride, t, config, det, n_det, max_det, scores, agg, GatherTo{});
-}
-
-static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
-                             const rp_templates *t, const rp_detector_config *config, rp_batch_detection *det, int32_t *n_det,
                              int max_det, float *scores, float *agg, const GatherTo &gather) {
     return guarded([&]() -> int {
         if (!ctx || !t) { set_last_error("null handle"); return -1; }
@@ -668,6 +532,12 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
         if (sg.host && agg && !sg.back(agg, dg, rows * sizeof(float))) return -1;
         return sg.finish() ? 0 : -1;
     });
+}
+
+int rp_batch_detect_fmt(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                        const rp_templates *t, const rp_detector_config *config, rp_batch_detection *det, int32_t *n_det,
+                        int max_det, float *scores, float *agg) {
+    return batch_detect_impl(ctx, pcm, fmt, S, n_samples, pcm_stride, t, config, det, n_det, max_det, scores, agg, GatherTo{});
 }
 
 // how the last rp_batch_detect_sharded of this thread gathered its results (rp_sharded_gather_info)
@@ -879,436 +749,10 @@ int rp_resample_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, int ch
         const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
         float *dout = static_cast<float *>(sg.out(out, S * out_stride * sizeof(float), c->stage_out));
         if (!dp || !dout) return -1;
-        if (resample_reads_in_place(rs->dev, dp, (int)fmt, pcm_stride, dout, out_stride)) {
-            if (!timed(c, kKernelResample, "resample48_fft_kernel", [&] {
-                    return launch_resample_in_place(c->stream, rs->dev, dp, (int)fmt, channels, pcm_stride, nullptr, nullptr, S, n_chunks, dout, out_stride); }))
-                return -1;
-        } else {
-            if (!c->ws_resample.reserve(S * (1 + n_chunks) * (size_t)rs->dev.fi * sizeof(float) + 64)) return -1;
-            float *xs = c->ws_resample.as<float>();
-            if (!hip_ok(launch_resample_stage(c->stream, dp, (int)fmt, channels, S, n_chunks, rs->dev.fi, pcm_stride, nullptr, xs), "resample_stage_kernel")) return -1;
-            if (!timed(c, kKernelResample, "resample kernel", [&] { return launch_resample(c->stream, rs->dev, xs, S, n_chunks, dout, out_stride); })) return -1;
-        }
+        if (!resample_rows(c, rs->dev, dp, (int)fmt, channels, pcm_stride, nullptr, nullptr, S, n_chunks, c->ws_resample, n_chunks, dout, out_stride)) return -1;
         if (!sg.back(out, dout, S * out_stride * sizeof(float)) || !sg.finish()) return -1;
         return 0;
     });
-}
-
-// buffers of a fresh batch, sized for the current input frame length (30 ms frames: 3 MFCC frames each, 40 ms: 4)
-static bool stream_batch_alloc(rp_stream_batch *b) {
-    Ctx *c = b->c;
-    struct { int K, T; } td{b->K, b->Tmax};
-    const size_t S = b->S, fpf = b->fpf();
-    b->cap = b->hist_frames + fpf * b->max_chunks * 8;  // compaction every 8 full-size calls
-    const size_t pitch = b->cap, rows = S * fpf * b->max_chunks;
-    const size_t slack = 64 * (size_t)td.K * sizeof(float);  // the DTW band reads up to band_size frames past a row
-    const size_t pcm_bytes = S * (480 + b->max_chunks * b->out_len) * sizeof(float);
-    for (auto &w : b->ww)
-        if (!w->agg.reserve(rows * sizeof(float) + 16) || !w->avg.reserve(rows * sizeof(float) + 16) || !w->label.reserve(rows * sizeof(int32_t) + 16))
-            return false;
-    if (!b->pcm[0].reserve(pcm_bytes) || !b->pcm[1].reserve(pcm_bytes) || !b->mfcc[0].reserve(S * pitch * td.K * sizeof(float) + slack) ||
-        !b->mfcc[1].reserve(S * pitch * td.K * sizeof(float) + slack) || !b->state.reserve(S * stream_state_bytes()) ||
-        !b->scores.reserve(rows * td.T * sizeof(float) + 16) || !b->agg.reserve(rows * sizeof(float) + 16) ||
-        !b->avg.reserve(rows * sizeof(float) + 16) || !b->vad.reserve(rows * sizeof(float) + 16) ||
-        !b->list.reserve((rows + 1) * sizeof(uint32_t) + 16))
-        return false;
-    if (!hip_ok(hipMemsetAsync(b->pcm[0].p, 0, b->pcm[0].cap, c->stream), "hipMemsetAsync") ||
-        !hip_ok(hipMemsetAsync(b->pcm[1].p, 0, b->pcm[1].cap, c->stream), "hipMemsetAsync") ||
-        !hip_ok(hipMemsetAsync(b->mfcc[0].p, 0, b->mfcc[0].cap, c->stream), "hipMemsetAsync") ||
-        !hip_ok(hipMemsetAsync(b->mfcc[1].p, 0, b->mfcc[1].cap, c->stream), "hipMemsetAsync") ||
-        !hip_ok(launch_stream_state_init(c->stream, b->state.p, S), "stream_state_init_kernel"))
-        return false;
-    b->cur = 0; b->fill = b->hist_frames;  // an all-zero history nobody scores against (frames < 0)
-    b->pcur = 0; b->last_off = 0;
-    return true;
-}
-
-int rp_stream_batch_new(rp_ctx *ctx, const rp_templates *t, const rp_detector_config *config, size_t S,
-                        size_t max_chunks_per_call, rp_stream_batch **out) {
-    return guarded([&]() -> int {
-        if (!ctx || !t) { set_last_error("null handle"); return -1; }
-        if (!config || !out) { set_last_error("null argument"); return -1; }
-        *out = nullptr;
-        Ctx *c = ctx->impl.get();
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new: S and max_chunks_per_call must be >= 1"); return -1; }
-        const TemplatesDev &td = t->impl->dev;
-        if (!c->tables_for(td.K)) return -1;
-        std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
-        b->c = c; b->t = t->impl.get(); b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
-        b->K = td.K; b->max_len = td.max_len; b->Tmax = td.T;
-        b->hist_frames = (size_t)td.max_len - 1;
-        if (!stream_batch_alloc(b.get())) return -1;
-        *out = b.release();
-        return 0;
-    });
-}
-void rp_stream_batch_free(rp_stream_batch *b) { delete b; }
-size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b) { return b ? b->chunks_seen : 0; }
-
-static const char kFiltersNeed30ms[] = "filters on a live-stream batch need 30 ms input frames: not available with the 40 ms frames of "
-                                       "11.025 / 22.05 kHz input (rp_stream_batch_set_filters / rp_stream_batch_set_input)";
-
-int rp_stream_batch_set_input(rp_stream_batch *b, size_t sample_rate, int channels) {
-    return guarded([&]() -> int {
-        if (!b) { set_last_error("null handle"); return -1; }
-        Ctx *c = b->c;
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (b->chunks_seen) { set_last_error("rp_stream_batch_set_input: the streams have already received audio"); return -1; }
-        if (channels < 1) { set_last_error("Unsupported channel count"); return -1; }
-        size_t fi = 480, fo = 480;
-        if (!resampler_frame_lengths(sample_rate, &fi, &fo)) { set_last_error("Unsupported sample rate, unable to initialize the resampler"); return -1; }
-        if (b->has_filters && fo != 480) { set_last_error(kFiltersNeed30ms); return -1; }
-        b->channels = channels; b->in_len = fi; b->rs = nullptr;
-        if (fo != b->out_len) {  // 11.025 / 22.05 kHz: 40 ms frames of four 10 ms shifts
-            b->out_len = fo;
-            if (!stream_batch_alloc(b)) return -1;
-        }
-        if (sample_rate != 16000) {
-            b->rs = c->resampler_for(sample_rate);
-            if (!b->rs) return -1;
-            if (!b->rs_prev[0].reserve(b->S * fi * sizeof(float)) || !b->rs_prev[1].reserve(b->S * fi * sizeof(float)) ||
-                !b->rs_out.reserve(b->S * b->max_chunks * fo * sizeof(float))) return -1;
-            if (!b->rs->dev.fft48 && !b->rs_xs.reserve(b->S * (1 + b->max_chunks) * fi * sizeof(float) + 64)) return -1;
-            if (!hip_ok(hipMemsetAsync(b->rs_prev[0].p, 0, b->S * fi * sizeof(float), c->stream), "hipMemsetAsync")) return -1;
-            b->rs_cur = 0;
-        }
-        return 0;
-    });
-}
-size_t rp_stream_batch_samples_per_chunk(const rp_stream_batch *b) { return b ? b->in_len * (size_t)b->channels : 0; }
-
-int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref) {
-    return guarded([&]() -> int {
-        if (!b) { set_last_error("null handle"); return -1; }
-        if (!filters) { set_last_error("null argument"); return -1; }
-        Ctx *c = b->c;
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
-        if (b->chunks_seen) { set_last_error("rp_stream_batch_set_filters: the streams have already received audio"); return -1; }
-        if (b->out_len != 480) { set_last_error(kFiltersNeed30ms); return -1; }
-        const rp_gain_normalization_config &g = filters->gain_normalizer;
-        const int window = std::max(b->max_len / 3, 1);   // on_wakeword_change, src/detector.rs:337; set_rms_level_ref :47
-        const size_t lv = b->S * b->max_chunks * sizeof(float) + 16, st = stream_filter_state_bytes(b->S, window);
-        if (!b->filt_state.reserve(st) || !b->lv_rms.reserve(lv) || !b->lv_gain.reserve(lv)) return -1;
-        if (!hip_ok(hipMemsetAsync(b->filt_state.p, 0, st, c->stream), "hipMemsetAsync")) return -1;
-        b->filt = *filters;
-        b->rms_level_ref = g.enabled && g.has_gain_ref ? g.gain_ref : rms_level_ref;  // fixed_rms_level, gain_normalizer_filter.rs:56-66
-        b->gain_window = window;
-        band_pass_coefficients(filters->band_pass, b->bq);
-        b->has_filters = true;
-        return 0;
-    });
-}
-
-int rp_stream_batch_levels(rp_stream_batch *b, float *rms, float *gains) {
-    return guarded([&]() -> int {
-        if (!b) { set_last_error("null handle"); return -1; }
-        Ctx *c = b->c;
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
-        if (!b->has_filters) { set_last_error("rp_stream_batch_levels: the batch has had no rp_stream_batch_set_filters"); return -1; }
-        if (!b->levels_chunks) { set_last_error("rp_stream_batch_levels: the streams have not received audio yet"); return -1; }
-        const size_t n = b->S * b->levels_chunks;
-        const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
-        const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (rms && !hip_ok(hipMemcpyAsync(rms, b->lv_rms.p, n * sizeof(float), kind, c->stream), "hipMemcpyAsync")) return -1;
-        if (gains) {
-            if (b->filters_on()) {
-                if (!hip_ok(hipMemcpyAsync(gains, b->lv_gain.p, n * sizeof(float), kind, c->stream), "hipMemcpyAsync")) return -1;
-            } else {  // both filters off: every chunk has gain 1
-                std::vector<float> ones(n, 1.f);
-                if (host) std::memcpy(gains, ones.data(), n * sizeof(float));
-                else if (!hip_ok(hipMemcpy(gains, ones.data(), n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) return -1;
-            }
-        }
-        return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
-    });
-}
-
-int rp_stream_batch_reset(rp_stream_batch *b, long long stream) {
-    return guarded([&]() -> int {
-        if (!b) { set_last_error("null handle"); return -1; }
-        Ctx *c = b->c;
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
-        if (stream >= (long long)b->S) { set_last_error("rp_stream_batch_reset: no such stream"); return -1; }
-        // the next chunk only refills the extractor: its three frames (3C-3 .. 3C-1) are never emitted
-        return hip_ok(launch_stream_state_reset(c->stream, b->state.p, b->S, stream, (long long)b->fpf() * (long long)b->chunks_seen), "stream_state_reset_kernel") ? 0 : -1;
-    });
-}
-
-static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float *now, size_t fill, size_t n_new, BatchDetection *dd,
-                                    int32_t *dn, int max_det, int32_t *det_wakeword, int32_t *det_label);
-
-// The live tail: VAD values of this call's n_new frames per stream (from `frames`, rows b->cap frames apart) when vad_mode is on, then
-// the timed scan that carries every stream's state machine on -- launch_scan_stream over one reference's agg / avg (sw == nullptr), else
-// launch_scan_stream_multi over `sw` (dw / dl: each detection's wakeword and label)
-static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, const ScanWakewords *sw, const float *dg, const float *da,
-                      BatchDetection *dd, int32_t *dw, int32_t *dl, int32_t *dn, int max_det) {
-    Ctx *c = b->c;
-    float *dv = nullptr;
-    if (b->cfg.vad_mode != RP_VAD_NONE) {
-        dv = b->vad.as<float>();
-        if (!hip_ok(launch_vad_value_rows(c->stream, frames, b->S, n_new, b->cap, b->K, dv), "vad_value_kernel")) return false;
-    }
-    const ScanConfig sc = scan_config(b->cfg, b->max_len, da != nullptr, (int)b->fpf());
-    const float vm = vad_mode_value(b->cfg.vad_mode);
-    const long long f0 = (long long)b->fpf() * (long long)b->chunks_seen - 3;
-    return timed(c, kKernelScan, "scan_stream_kernel", [&] {
-        return sw ? launch_scan_stream_multi(c->stream, *sw, dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det)
-                  : launch_scan_stream(c->stream, dg, da, dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dn, max_det);
-    });
-}
-
-// Both live entry points.  A call advances device-resident state launch by launch (resampler tail, history chunk, MFCC rows, scan
-// state); a failure after the first such step cannot be rolled back, so the batch refuses further work instead of pairing the wrong
-// history with later chunks.
-static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
-                                rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, int32_t *det_wakeword, int32_t *det_label) {
-    if (!b) { set_last_error("null handle"); return -1; }
-    if (b->poisoned) { set_last_error("stream batch is in a failed state (an earlier call failed half way); free it and create a new one"); return -1; }
-    bool touched = false;
-    const int r = guarded([&]() -> int {
-        Ctx *c = b->c;
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (n_chunks == 0 || n_chunks > b->max_chunks) { set_last_error("rp_stream_batch_process: n_chunks out of range"); return -1; }
-        const size_t in_chunk = b->in_len * (size_t)b->channels;
-        if (pcm_stride < n_chunks * in_chunk) { set_last_error("pcm_stride smaller than n_chunks * samples per chunk"); return -1; }
-        if (!sample_format_ok(fmt)) return -1;
-        const bool multi = !b->ww.empty();
-        if (multi && agg) { set_last_error("rp_stream_batch_process: a batch of several wakewords has no single aggregate per window"); return -1; }
-        static const TemplatesDev no_templates{};
-        const TemplatesDev &td_one = multi ? no_templates : b->t->dev;
-        struct { int K, T, max_len, has_avg; } td{b->K, td_one.T, b->max_len, td_one.has_avg};
-        const MfccTablesDev *tb = c->tables_for(td.K);
-        if (!tb) return -1;
-        const size_t fo = b->out_len, new_len = n_chunks * fo;  // encoded samples this call adds to every stream
-        const size_t S = b->S, n_new = b->fpf() * n_chunks, hist = b->hist_frames, pitch = b->cap, rows = S * n_new;
-        // a row is [the last 480 encoded samples of the previous call | the new ones]
-        const size_t n_samples = 480 + new_len, pcm_pitch = 480 + b->max_chunks * fo;
-        const bool do_avg = td.has_avg && b->cfg.avg_threshold != 0.f;
-        Staged sg(c);
-        const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
-        BatchDetection *dd = static_cast<BatchDetection *>(sg.out(det, S * (size_t)max_det * sizeof(BatchDetection), c->stage_out));
-        int32_t *dn = static_cast<int32_t *>(sg.out(n_det, S * sizeof(int32_t), c->stage_out2));
-        if (!dp || !dd || !dn) { if (!pcm || !det || !n_det) set_last_error("null argument"); return -1; }
-        const float *hp_old = b->pcm[b->pcur].as<float>();
-        float *hp = b->pcm[b->pcur ^ 1].as<float>();
-        touched = true;  // from here on every launch moves persistent state
-        // 16 kHz mono input is read where it lies: the MFCC kernel takes [history chunk | new chunks] from two buffers and
-        // leaves the last chunk as the next call's history.  Other inputs are staged into one row per stream first.
-        bool staged = false;
-        const bool filtered = b->filters_on();
-        // with filters, ONE launch in the place of launch_stream_stage: history chunk | the new chunks decoded and filtered, levels kept
-        auto stage_filtered = [&](const void *src, int src_fmt, int src_channels, size_t src_stride) {
-            const rp_gain_normalization_config &g = b->filt.gain_normalizer;
-            return hip_ok(launch_stream_filters(c->stream, src, src_fmt, src_channels, S, n_chunks, src_stride, hp_old, b->last_off, hp, pcm_pitch,
-                                                g.enabled ? 1 : 0, b->rms_level_ref, g.min_gain, g.max_gain, b->gain_window,
-                                                b->filt.band_pass.enabled ? 1 : 0, b->bq[0], b->bq[1], b->bq[2], b->bq[3], b->bq[4],
-                                                b->filt_state.as<float>(), b->lv_rms.as<float>(), b->lv_gain.as<float>()), "stream_filters_kernel");
-        };
-        if (b->rs) {  // previous input frame | new input frames -> 16 kHz (the resampler never resets, src/detector.rs:290-302)
-            const size_t fi = b->in_len;
-            float *ro = b->rs_out.as<float>();
-            float *pv = b->rs_prev[b->rs_cur].as<float>(), *pn = b->rs_prev[b->rs_cur ^ 1].as<float>();
-            if (resample_reads_in_place(b->rs->dev, dp, (int)fmt, pcm_stride, ro, new_len)) {
-                if (!timed(c, kKernelResample, "resample48_fft_kernel", [&] {
-                        return launch_resample_in_place(c->stream, b->rs->dev, dp, (int)fmt, b->channels, pcm_stride, pv, pn, S, n_chunks, ro, new_len); }))
-                    return -1;
-            } else {
-                if (!b->rs_xs.reserve(S * (1 + b->max_chunks) * fi * sizeof(float) + 64)) return -1;
-                float *xs = b->rs_xs.as<float>();
-                if (!hip_ok(launch_resample_stage(c->stream, dp, (int)fmt, b->channels, S, n_chunks, (int)fi, pcm_stride, pv, xs), "resample_stage_kernel")) return -1;
-                if (!timed(c, kKernelResample, "resample kernel", [&] { return launch_resample(c->stream, b->rs->dev, xs, S, n_chunks, ro, new_len); })) return -1;
-                if (!hip_ok(launch_carry_rows(c->stream, xs, S, (1 + n_chunks) * fi, n_chunks * fi, fi, pn, fi), "carry_rows_kernel")) return -1;
-            }
-            b->rs_cur ^= 1;
-            if (filtered) { if (!stage_filtered(ro, 3, 1, new_len)) return -1; }
-            else if (!hip_ok(launch_stream_stage(c->stream, ro, 3, 1, S, new_len, new_len, hp_old, b->last_off, hp, pcm_pitch), "stream_stage_kernel")) return -1;
-            staged = true;
-        } else if (filtered) {
-            if (!stage_filtered(dp, (int)fmt, b->channels, pcm_stride)) return -1;
-            staged = true;
-        } else if (b->channels != 1) {  // previous chunk | new chunks (first channel), decoded to f32
-            if (!hip_ok(launch_stream_stage(c->stream, dp, (int)fmt, b->channels, S, new_len, pcm_stride, hp_old, b->last_off, hp, pcm_pitch), "stream_stage_kernel")) return -1;
-            staged = true;
-        }
-        // MFCC window rows: [.. valid frames .. | the 3*n_chunks new frames]; a full row keeps its last max_len-1 frames
-        if (b->fill + n_new > b->cap) {
-            if (!hip_ok(launch_carry_rows(c->stream, b->mfcc[b->cur].as<float>(), S, pitch * td.K, (b->fill - hist) * td.K, hist * td.K,
-                                          b->mfcc[b->cur ^ 1].as<float>(), pitch * td.K), "carry_rows_kernel")) return -1;
-            b->cur ^= 1; b->fill = hist;
-        }
-        float *now = b->mfcc[b->cur].as<float>();
-        const size_t fill = b->fill;
-        if (!staged) {
-            c->time_begin(kKernelMfcc);
-            hipError_t e = launch_mfcc_stream(c->stream, *tb, dp, (int)fmt, S, n_chunks, pcm_stride, hp_old + b->last_off, pcm_pitch, hp, pitch,
-                                              now + fill * td.K);
-            c->time_end();
-            if (e == hipErrorNotSupported) {  // rows that do not allow 4-sample loads
-                if (!hip_ok(launch_stream_stage(c->stream, dp, (int)fmt, 1, S, new_len, pcm_stride, hp_old, b->last_off, hp, pcm_pitch), "stream_stage_kernel")) return -1;
-                staged = true;
-            } else {
-                if (!hip_ok(e, "mfcc_kernel")) return -1;
-                b->pcur ^= 1; b->last_off = 0;  // hist_out: the last chunk of this call at the start of the other buffer's rows
-            }
-        }
-        if (staged) {
-            b->pcur ^= 1; b->last_off = new_len;  // the last 480 samples of this call are the extractor history of the next
-            if (!timed(c, kKernelMfcc, "mfcc_kernel", [&] { return launch_mfcc(c->stream, *tb, hp, S, n_samples, pcm_pitch, 0, n_new, pitch, now + fill * td.K); }))
-                return -1;
-        }
-        b->fill += n_new;
-        if (b->has_filters) {
-            // filters configured but both off: today's launches above, and the levels of the unfiltered chunks for rp_stream_batch_levels
-            if (!filtered && !hip_ok(staged ? launch_chunk_rms(c->stream, hp + 480, 3, S, n_chunks, pcm_pitch, b->lv_rms.as<float>())
-                                            : launch_chunk_rms(c->stream, dp, (int)fmt, S, n_chunks, pcm_stride, b->lv_rms.as<float>()),
-                                     "chunk_rms_kernel")) return -1;
-            b->levels_chunks = n_chunks;
-        }
-        if (multi) {
-            if (stream_batch_score_multi(b, sg, now, fill, n_new, dd, dn, max_det, det_wakeword, det_label) != 0) return -1;
-        } else {
-            float *ds = b->scores.as<float>(), *dg = b->agg.as<float>(), *da = do_avg ? b->avg.as<float>() : nullptr;
-            DtwScore q;
-            q.t = &td_one; q.mfcc = now; q.S = S; q.frame_pitch = pitch; q.first_win = fill - hist; q.n_win = n_new; q.band = b->cfg.band_size;
-            q.score_ref = b->cfg.score_ref; q.with_avg = do_avg;
-            q.detect_only = !agg && !(c->flags & RP_CTX_FULL_SCORES);   // unless the caller wants every window's aggregate
-            q.avg_threshold = b->cfg.avg_threshold; q.threshold = b->cfg.threshold; q.score_mode = (int)b->cfg.score_mode;
-            q.scores = ds; q.avg = da; q.agg = dg; q.gate_list = b->list.as<uint32_t>();
-            // (a single live stream with a handful of windows skips the gate's three passes: the batch kernels score it when the matrix-core
-            // kernel serves its templates (a stream's bits must not depend on the batch it is in), else one wave per DTW)
-            q.gate_one_stream = false; q.fuse_max = true;
-            if (!dtw_score(*c, q)) return -1;
-            if (!live_scan(b, now + fill * td.K, n_new, nullptr, dg, da, dd, nullptr, nullptr, dn, max_det)) return -1;
-        }
-        b->chunks_seen += n_chunks;
-        if (!sg.back_detections(S, max_det, det, dd, n_det, dn)) return -1;
-        if (!multi && (det_wakeword || det_label)) {   // one wakeword reference: wakeword 0, no label
-            const size_t nb = S * (size_t)max_det * sizeof(int32_t);
-            if (sg.host) { if (det_wakeword) std::memset(det_wakeword, 0, nb); if (det_label) std::memset(det_label, 0xff, nb); }
-            else if ((det_wakeword && !hip_ok(hipMemsetAsync(det_wakeword, 0, nb, c->stream), "hipMemsetAsync")) ||
-                     (det_label && !hip_ok(hipMemsetAsync(det_label, 0xff, nb, c->stream), "hipMemsetAsync"))) return -1;
-        }
-        if (agg) {   // (one reference: a batch of several wakewords was refused above)
-            if (sg.host) { if (!sg.back(agg, b->agg.as<float>(), rows * sizeof(float))) return -1; }
-            else if (!hip_ok(hipMemcpyAsync(agg, b->agg.p, rows * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync(D2D)")) return -1;
-        }
-        return sg.finish() ? 0 : -1;
-    });
-    if (r != 0 && touched) b->poisoned = true;
-    return r;
-}
-
-int rp_stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
-                            rp_batch_detection *det, int32_t *n_det, int max_det, float *agg) {
-    return stream_batch_process(b, pcm, fmt, n_chunks, pcm_stride, det, n_det, max_det, agg, nullptr, nullptr);
-}
-int rp_stream_batch_process_multi(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
-                                  rp_batch_detection *det, int32_t *det_wakeword, int32_t *det_label, int32_t *n_det, int max_det) {
-    return stream_batch_process(b, pcm, fmt, n_chunks, pcm_stride, det, n_det, max_det, nullptr, det_wakeword, det_label);
-}
-
-static bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
-                          float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live);
-
-// ---- live-stream batches that hold several wakewords and / or a wakeword model (src/detector.rs:304-346,433-447)
-int rp_stream_batch_new_multi(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword_spec *wakewords, int mfcc_size,
-                              const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
-    return guarded([&]() -> int {
-        if (!ctx) { set_last_error("null handle"); return -1; }
-        if (!config || !out || !wakewords) { set_last_error("null argument"); return -1; }
-        *out = nullptr;
-        Ctx *c = ctx->impl.get();
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new: S and max_chunks_per_call must be >= 1"); return -1; }
-        if (n_wakewords < 1 || n_wakewords > (size_t)kScanMaxWakewords) { set_last_error("rp_stream_batch_new_multi: 1..8 wakewords"); return -1; }
-        if (mfcc_size < 1) { set_last_error("rp_stream_batch_new_multi: mfcc_size must be >= 1"); return -1; }
-        std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
-        b->c = c; b->t = nullptr; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
-        b->K = mfcc_size; b->max_len = 0; b->Tmax = 1;
-        for (size_t j = 0; j < n_wakewords; ++j) {
-            const rp_wakeword_spec &w = wakewords[j];
-            if ((w.templates != nullptr) == (w.model != nullptr)) { set_last_error("rp_stream_batch_new_multi: every wakeword is a reference OR a model"); return -1; }
-            std::unique_ptr<StreamWakeword> e(new StreamWakeword());
-            e->threshold = std::isnan(w.threshold) ? config->threshold : w.threshold;
-            e->avg_threshold = std::isnan(w.avg_threshold) ? config->avg_threshold : w.avg_threshold;
-            if (w.templates) {
-                e->t = w.templates->impl.get();
-                if (e->t->ctx != c) { set_last_error("rp_stream_batch_new_multi: the wakewords must have been created on this context"); return -1; }
-                // add_wakeword, src/detector.rs:316-319
-                if (e->t->dev.K != mfcc_size) { set_last_error("Usage of wakewords with different mfcc size is not supported, ignoring wakeword"); return -1; }
-                b->max_len = std::max(b->max_len, e->t->dev.max_len);
-                b->Tmax = std::max(b->Tmax, e->t->dev.T);
-            } else {
-                e->m = w.model->impl.get();
-                if (e->m->ctx != c) { set_last_error("rp_stream_batch_new_multi: the wakewords must have been created on this context"); return -1; }
-                const int nl = (int)e->m->dims.size() - 1;
-                if (e->m->dims[0] % mfcc_size != 0) { set_last_error("Usage of wakewords with different mfcc size is not supported, ignoring wakeword"); return -1; }
-                if (w.none_index >= e->m->dims[nl]) { set_last_error("none_index out of range"); return -1; }
-                if (!mlp_precision_ok(w.precision)) return -1;
-                if (!e->m->mfma_ok && w.precision == RP_MLP_BF16) { set_last_error("this layer-1 shape has no bf16 MFMA kernel"); return -1; }
-                e->none_index = w.none_index; e->precision = w.precision;
-                b->max_len = std::max(b->max_len, e->m->dims[0] / mfcc_size);
-            }
-            b->ww.push_back(std::move(e));
-        }
-        if (!c->tables_for(b->K)) return -1;
-        b->hist_frames = (size_t)b->max_len - 1;   // on_wakeword_change, src/detector.rs:328-334: the longest wakeword sets the window
-        if (!stream_batch_alloc(b.get())) return -1;
-        *out = b.release();
-        return 0;
-    });
-}
-
-// scores of this call's n_new windows per stream for every wakeword, then the state machine over all of them
-static int stream_batch_score_multi(rp_stream_batch *b, Staged &sg, const float *now, size_t fill, size_t n_new, BatchDetection *dd,
-                                    int32_t *dn, int max_det, int32_t *det_wakeword, int32_t *det_label) {
-    Ctx *c = b->c;
-    const size_t S = b->S, hist = b->hist_frames, pitch = b->cap, rows = S * n_new;
-    const int K = b->K;
-    const bool detect_only = !(c->flags & RP_CTX_FULL_SCORES);
-    ScanWakewords sw{};
-    sw.n = (int)b->ww.size();
-    for (size_t j = 0; j < b->ww.size(); ++j) {
-        StreamWakeword &w = *b->ww[j];
-        float *dg = w.agg.as<float>();
-        if (w.t) {
-            const TemplatesDev &td = w.t->dev;
-            const bool do_avg = td.has_avg && w.avg_threshold != 0.f;  // wakeword_comp.rs:85
-            float *da = do_avg ? w.avg.as<float>() : nullptr, *ds = b->scores.as<float>();
-            // the window starts where the longest wakeword's does and this one scores its oldest frames (wakeword_comp.rs:22-27)
-            DtwScore q;
-            q.t = &td; q.mfcc = now; q.S = S; q.frame_pitch = pitch; q.first_win = fill - hist; q.n_win = n_new; q.band = b->cfg.band_size;
-            q.score_ref = b->cfg.score_ref; q.with_avg = do_avg; q.detect_only = detect_only;
-            q.avg_threshold = w.avg_threshold; q.threshold = w.threshold; q.score_mode = (int)b->cfg.score_mode;
-            q.scores = ds; q.avg = da; q.agg = dg; q.gate_list = b->list.as<uint32_t>();
-            if (!dtw_score(*c, q)) return -1;
-            sw.agg[j] = dg; sw.avg[j] = da; sw.threshold[j] = w.threshold; sw.avg_threshold[j] = w.avg_threshold; sw.label[j] = nullptr;
-        } else {
-            Model &m = *w.m;
-            const int L = m.dims[0] / K, n_labels = m.dims.back();
-            if (!b->logits.reserve(rows * (size_t)n_labels * sizeof(float) + 16)) return -1;
-            float *dlog = b->logits.as<float>();
-            // window i of stream s starts at frame s * pitch + i from the first frame the longest wakeword scores
-            if (!window_logits(c, m, now + (fill - hist) * K, S, pitch, n_new, L, K, w.precision, dlog, b->mean, b->xrows, b->xs2, true))
-                return -1;
-            float *da = w.avg.as<float>();
-            int32_t *dlab = w.label.as<int32_t>();
-            if (!hip_ok(launch_nn_score(c->stream, dlog, rows, n_labels, w.none_index, b->cfg.score_ref * 10.f, w.avg_threshold != 0.f ? 1 : 0,
-                                        w.threshold, w.avg_threshold, dg, da, dlab), "nn_score_kernel")) return -1;
-            sw.agg[j] = dg; sw.avg[j] = da; sw.label[j] = dlab;
-            sw.threshold[j] = -1.f; sw.avg_threshold[j] = -1.f;  // the gates were applied by nn_score_kernel (>=, not >)
-        }
-    }
-    int32_t *dw = det_wakeword ? static_cast<int32_t *>(sg.out(det_wakeword, S * (size_t)max_det * sizeof(int32_t), b->det_ww)) : nullptr;
-    int32_t *dl = det_label ? static_cast<int32_t *>(sg.out(det_label, S * (size_t)max_det * sizeof(int32_t), b->det_label)) : nullptr;
-    if ((det_wakeword && !dw) || (det_label && !dl)) return -1;
-    if (!live_scan(b, now + fill * K, n_new, &sw, nullptr, nullptr, dd, dw, dl, dn, max_det)) return -1;
-    if ((dw && !sg.back(det_wakeword, dw, S * (size_t)max_det * sizeof(int32_t))) || (dl && !sg.back(det_label, dl, S * (size_t)max_det * sizeof(int32_t)))) return -1;
-    return 0;
 }
 
 int rp_model_new(rp_ctx *ctx, int n_layers, const int *dims, const float *const *weights, const float *const *biases,
@@ -1350,46 +794,6 @@ int rp_mlp_forward_batch(rp_ctx *ctx, const rp_model *model, const float *x, siz
         if (!sg.back(logits, dl, B * (size_t)m.dims[nl] * 4) || !sg.finish()) return -1;
         return 0;
     });
-}
-
-// Logits of every window of L frames of S streams' MFCC rows (WakewordNN::run_detection's forward, window by window,
-// src/wakewords/nn/wakeword_nn.rs:101-159): dlog [S * n_win][labels].  Window w of stream s starts at frame s * pitch + w from `first`.
-// The workspaces: `mean` for the window means of the in-place form, `xrows` for the normalised rows and `scratch` for the per-layer kernel.
-// live (live-stream batches): all rows in one slab, so a call makes one launch, and rp_ctx_last_mlp_kernel is left as it is by the
-// in-place form.  Shared by rp_batch_detect_model, rp_mlp_forward_windows and the live batches' model wakewords.
-static bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
-                          float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live) {
-    const size_t rows = S * n_win;
-    const int n_labels = m.dims.back();
-    MlpForward q;
-    q.m = &m; q.precision = precision;
-    // windows read in place from the frame array, the window mean taken out after layer 1
-    q.wsum = (m.mfma_ok && K % 4 == 0) ? m.wsum_for(K) : nullptr;
-    if (q.wsum) {
-        if (!mean.reserve(rows * (size_t)K * sizeof(float) + 16)) return false;
-        if (!hip_ok(launch_window_means(c->stream, first, S, pitch, n_win, L, K, mean.as<float>()), "window_means_kernel")) return false;
-        q.windows = true; q.x = first; q.S = S; q.n_win = n_win; q.frame_pitch = pitch; q.K = K; q.mean = mean.as<float>(); q.out = dlog;
-        q.report = !live;
-        return mlp_forward(*c, q);
-    }
-    // windows are materialised slab by slab (a row is dims[0] floats): <= 4 GiB of rows at a time
-    const size_t row_bytes = (size_t)m.dims[0] * sizeof(float);
-    const size_t slab = live ? rows : std::min(rows, std::max<size_t>(1, ((size_t)4 << 30) / row_bytes));
-    const int maxd = widest_layer(m);
-    if (!xrows.reserve(slab * row_bytes + 64)) return false;
-    if (!m.mfma_ok) {
-        if (!scratch.reserve(2 * slab * (size_t)maxd * sizeof(float) + 16)) return false;
-        q.scratch[0] = scratch.as<float>(); q.scratch[1] = scratch.as<float>() + slab * (size_t)maxd;
-    }
-    q.x = xrows.as<float>();
-    for (size_t r0 = 0; r0 < rows; r0 += slab) {
-        q.B = std::min(slab, rows - r0);
-        q.out = dlog + r0 * n_labels;
-        if (!hip_ok(launch_normalize_windows_batch(c->stream, first, pitch, n_win, r0, q.B, L, K, xrows.as<float>()), "normalize_windows_kernel") ||
-            !mlp_forward(*c, q))
-            return false;
-    }
-    return true;
 }
 
 int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc, size_t S, size_t n_frames, int mfcc_size, int precision,
@@ -1497,3 +901,74 @@ int rp_ctx_timing_read(rp_ctx *ctx, int kernel, double *avg_ms, int *launches) {
 }
 
 }  // extern "C"
+
+// BandPassFilter::new, band_pass_filter.rs:31-55 (f32, sample rate 16 kHz): q = a0 a1 a2 b1 b2, zeros when the filter is off
+void rp::band_pass_coefficients(const rp_band_pass_config &b, float q[5]) {
+    float a0 = 0, a1 = 0, a2 = 0, b1 = 0, b2 = 0;
+    if (b.enabled) {
+        const float kPi = 3.14159274101257324f, sample_rate = 16000.f;
+        const float omega_low = 2.0f * kPi * b.low_cutoff / sample_rate, omega_high = 2.0f * kPi * b.high_cutoff / sample_rate;
+        const float cos_low = std::cos(omega_low), cos_high = std::cos(omega_high);
+        const float alpha_low = std::sin(omega_low) / 2.0f, alpha_high = std::sin(omega_high) / 2.0f;
+        a0 = 1.0f / (1.0f + alpha_high - alpha_low);
+        a1 = -2.0f * cos_low * a0; a2 = (1.0f - alpha_high - alpha_low) * a0;
+        b1 = -2.0f * cos_high * a0; b2 = (1.0f - alpha_high + alpha_low) * a0;
+    }
+    q[0] = a0; q[1] = a1; q[2] = a2; q[3] = b1; q[4] = b2;
+}
+
+// Logits of every window of L frames of S streams' MFCC rows (WakewordNN::run_detection's forward, window by window,
+// src/wakewords/nn/wakeword_nn.rs:101-159): dlog [S * n_win][labels].  Window w of stream s starts at frame s * pitch + w from `first`.
+// The workspaces: `mean` for the window means of the in-place form, `xrows` for the normalised rows and `scratch` for the per-layer kernel.
+// live (live-stream batches): all rows in one slab, so a call makes one launch, and rp_ctx_last_mlp_kernel is left as it is by the
+// in-place form.  Shared by rp_batch_detect_model, rp_mlp_forward_windows and the live batches' model wakewords.
+bool rp::window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
+                       float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live) {
+    const size_t rows = S * n_win;
+    const int n_labels = m.dims.back();
+    MlpForward q;
+    q.m = &m; q.precision = precision;
+    // windows read in place from the frame array, the window mean taken out after layer 1
+    q.wsum = (m.mfma_ok && K % 4 == 0) ? m.wsum_for(K) : nullptr;
+    if (q.wsum) {
+        if (!mean.reserve(rows * (size_t)K * sizeof(float) + 16)) return false;
+        if (!hip_ok(launch_window_means(c->stream, first, S, pitch, n_win, L, K, mean.as<float>()), "window_means_kernel")) return false;
+        q.windows = true; q.x = first; q.S = S; q.n_win = n_win; q.frame_pitch = pitch; q.K = K; q.mean = mean.as<float>(); q.out = dlog;
+        q.report = !live;
+        return mlp_forward(*c, q);
+    }
+    // windows are materialised slab by slab (a row is dims[0] floats): <= 4 GiB of rows at a time
+    const size_t row_bytes = (size_t)m.dims[0] * sizeof(float);
+    const size_t slab = live ? rows : std::min(rows, std::max<size_t>(1, ((size_t)4 << 30) / row_bytes));
+    const int maxd = widest_layer(m);
+    if (!xrows.reserve(slab * row_bytes + 64)) return false;
+    if (!m.mfma_ok) {
+        if (!scratch.reserve(2 * slab * (size_t)maxd * sizeof(float) + 16)) return false;
+        q.scratch[0] = scratch.as<float>(); q.scratch[1] = scratch.as<float>() + slab * (size_t)maxd;
+    }
+    q.x = xrows.as<float>();
+    for (size_t r0 = 0; r0 < rows; r0 += slab) {
+        q.B = std::min(slab, rows - r0);
+        q.out = dlog + r0 * n_labels;
+        if (!hip_ok(launch_normalize_windows_batch(c->stream, first, pitch, n_win, r0, q.B, L, K, xrows.as<float>()), "normalize_windows_kernel") ||
+            !mlp_forward(*c, q))
+            return false;
+    }
+    return true;
+}
+
+// S rows of n_chunks input frames -> 16 kHz rows `out` (rp_resample_batch, the live batches' encode stage): read where they lie when the
+// FFT kernel can, else staged into xs_buf, reserved here for xs_chunks frames a row.  prev / prev_out (live streams; nullptr = silence
+// before the rows): every stream's previous input frame, and where the last frame of this call is kept for the next.
+bool rp::resample_rows(Ctx *c, const ResamplerDev &rs, const void *pcm, int fmt, int channels, size_t pcm_stride, const float *prev,
+                       float *prev_out, size_t S, size_t n_chunks, DevBuf &xs_buf, size_t xs_chunks, float *out, size_t out_stride) {
+    if (resample_reads_in_place(rs, pcm, fmt, pcm_stride, out, out_stride))
+        return timed(c, kKernelResample, "resample48_fft_kernel", [&] {
+            return launch_resample_in_place(c->stream, rs, pcm, fmt, channels, pcm_stride, prev, prev_out, S, n_chunks, out, out_stride); });
+    const size_t fi = (size_t)rs.fi;
+    if (!xs_buf.reserve(S * (1 + xs_chunks) * fi * sizeof(float) + 64)) return false;
+    float *xs = xs_buf.as<float>();
+    return hip_ok(launch_resample_stage(c->stream, pcm, fmt, channels, S, n_chunks, rs.fi, pcm_stride, prev, xs), "resample_stage_kernel") &&
+           timed(c, kKernelResample, "resample kernel", [&] { return launch_resample(c->stream, rs, xs, S, n_chunks, out, out_stride); }) &&
+           (!prev_out || hip_ok(launch_carry_rows(c->stream, xs, S, (1 + n_chunks) * fi, n_chunks * fi, fi, prev_out, fi), "carry_rows_kernel"));
+}

@@ -1,0 +1,83 @@
+// rp_capi.h -- what the files of the extern "C" surface share (rp_capi.cpp, rp_stream_batch.cpp).  Not installed.
+#pragma once
+#include <new>
+
+#include "rp_host.h"
+
+struct rp_ctx { std::unique_ptr<rp::Ctx> impl; };
+struct rp_templates { std::unique_ptr<rp::Templates> impl; };
+struct rp_model { std::unique_ptr<rp::Model> impl; };
+
+namespace rp {
+
+template <class F> int guarded(F &&f) {
+    try { return f(); }
+    catch (const std::bad_alloc &) { set_last_error("out of host memory"); return -1; }
+    catch (const std::exception &e) { set_last_error(e.what()); return -1; }
+    catch (...) { set_last_error("unknown error"); return -1; }
+}
+
+// one launch, timed as `kernel` when the context times its kernels (rp_ctx_timing_enable)
+template <class F> bool timed(Ctx *c, int kernel, const char *what, F &&launch) {
+    c->time_begin(kernel);
+    const bool ok = hip_ok(launch(), what);
+    c->time_end();
+    return ok;
+}
+
+struct Staged {  // host<->device staging for RP_CTX_HOST_POINTERS
+    Ctx *c;
+    bool host;
+    explicit Staged(Ctx *ctx) : c(ctx), host((ctx->flags & RP_CTX_HOST_POINTERS) != 0) {}
+    const void *in(const void *p, size_t bytes, DevBuf &buf) {
+        if (!host || !p) return p;
+        if (!buf.reserve(bytes)) return nullptr;
+        if (!hip_ok(hipMemcpyAsync(buf.p, p, bytes, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(H2D)")) return nullptr;
+        return buf.p;
+    }
+    void *out(void *p, size_t bytes, DevBuf &buf) {
+        if (!host || !p) return p;
+        return buf.reserve(bytes) ? buf.p : nullptr;
+    }
+    bool back(void *host_p, const void *dev_p, size_t bytes) {
+        if (!host || !host_p) return true;
+        return hip_ok(hipMemcpyAsync(host_p, dev_p, bytes, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(D2H)");
+    }
+    bool finish() { return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize"); }
+    // det [S][max_det] and n_det [S], then the int32 column per detection `col` (det_wakeword / det_label) when there is one
+    bool back_detections(size_t S, int max_det, rp_batch_detection *det, const BatchDetection *dd, int32_t *n_det, const int32_t *dn,
+                         int32_t *col = nullptr, const int32_t *dcol = nullptr) {
+        return back(det, dd, S * (size_t)max_det * sizeof(BatchDetection)) && back(n_det, dn, S * sizeof(int32_t)) &&
+               (!dcol || back(col, dcol, S * (size_t)max_det * sizeof(int32_t)));
+    }
+};
+
+inline size_t sample_bytes(rp_sample_format f) { return f == RP_SAMPLE_I8 ? 1 : f == RP_SAMPLE_I16 ? 2 : 4; }
+inline float vad_mode_value(rp_vad_mode m) { return m == RP_VAD_EASY ? 2.f : m == RP_VAD_MEDIUM ? 2.5f : 3.f; }  // src/config.rs:140-146
+
+inline bool sample_format_ok(rp_sample_format fmt) {
+    if ((int)fmt < 0 || (int)fmt > 3) { set_last_error("unknown sample format"); return false; }
+    return true;
+}
+inline bool mlp_precision_ok(int p) {
+    if (p != RP_MLP_F32 && p != RP_MLP_BF16 && p != RP_MLP_F32_STRICT && p != RP_MLP_F32_FAST) { set_last_error("unknown MLP precision"); return false; }
+    return true;
+}
+
+// fpf 0: the ScanConfig default (whole streams, 30 ms frames)
+inline ScanConfig scan_config(const rp_detector_config &cfg, int max_len, bool avg_enabled, int fpf = 0) {
+    ScanConfig sc;
+    sc.threshold = cfg.threshold; sc.avg_threshold = cfg.avg_threshold; sc.min_scores = (int)cfg.min_scores;
+    sc.eager = cfg.eager ? 1 : 0; sc.max_len = max_len; sc.avg_enabled = avg_enabled ? 1 : 0;
+    if (fpf) sc.fpf = fpf;
+    return sc;
+}
+
+// rp_capi.cpp
+bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
+                   float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live);
+void band_pass_coefficients(const rp_band_pass_config &b, float q[5]);
+bool resample_rows(Ctx *c, const ResamplerDev &rs, const void *pcm, int fmt, int channels, size_t pcm_stride, const float *prev,
+                   float *prev_out, size_t S, size_t n_chunks, DevBuf &xs_buf, size_t xs_chunks, float *out, size_t out_stride);
+
+}  // namespace rp

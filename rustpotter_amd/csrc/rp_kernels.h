@@ -1,5 +1,5 @@
 // rp_kernels.h -- launchers of the gfx950 kernels (rp_mfcc / rp_dtw / rp_scan / rp_resample / rp_frontend / rp_mlp .hip) used by the
-// host-side mirror (rp_detector.cpp) and the C ABI (rp_capi.cpp).
+// host-side mirror (rp_detector.cpp) and the C ABI (rp_capi.cpp, rp_stream_batch.cpp).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime.h>
@@ -444,7 +444,7 @@ hipError_t launch_resample_in_place(hipStream_t st, const ResamplerDev &rs, cons
 hipError_t launch_resample(hipStream_t st, const ResamplerDev &rs, const float *xs, size_t S, size_t n_chunks, float *out,
                            size_t out_stride);
 
-// streaming batches (state carried between calls; rp_stream.cpp)
+// streaming batches (state carried between calls; rp_stream_batch.cpp)
 hipError_t launch_stream_stage(hipStream_t st, const void *pcm, int fmt, int channels, size_t S, size_t n_new, size_t pcm_stride,
                                const float *old_hist, size_t old_off, float *hist, size_t hist_pitch);
 hipError_t launch_carry_rows(hipStream_t st, const float *src, size_t S, size_t src_pitch, size_t src_off, size_t count, float *dst,
@@ -452,11 +452,8 @@ hipError_t launch_carry_rows(hipStream_t st, const float *src, size_t S, size_t 
 hipError_t launch_stream_state_init(hipStream_t st, void *state, size_t S);
 size_t stream_state_bytes();
 hipError_t launch_stream_state_reset(hipStream_t st, void *state, size_t S, long long stream, long long resume);
-hipError_t launch_scan_stream(hipStream_t st, const float *agg, const float *avg, const float *vad_value, float vad_mode_value,
-                              size_t S, long long f0, int n_new, const ScanConfig &cfg, void *state, BatchDetection *det,
-                              int32_t *n_det, int max_det);
-// the same for a detector that holds several wakewords (references and / or models); det_ww / det_label (optional): the
-// wakeword a detection belongs to and, when that wakeword is a model, its label index (else -1)
+// the state machine over this call's n_new frames for a detector that holds 1..8 wakewords (references and / or models); det_ww /
+// det_label (optional): the wakeword a detection belongs to and, when that wakeword is a model, its label index (else -1)
 hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, const float *vad_value, float vad_mode_value, size_t S,
                                     long long f0, int n_new, const ScanConfig &cfg, void *state, BatchDetection *det, int32_t *det_ww,
                                     int32_t *det_label, int32_t *n_det, int max_det);

@@ -392,7 +392,7 @@ __global__ __launch_bounds__(64) void scan_stream_kernel(ScanWakewords ww, const
     for (int i = nd; i < max_det; ++i) {
         det[s * (size_t)max_det + i] = BatchDetection{};
         if (det_ww) det_ww[s * (size_t)max_det + i] = 0;
-        if (det_label) det_label[s * (size_t)max_det + i] = -1;   // "no label", as the header says and the single-wakeword path fills
+        if (det_label) det_label[s * (size_t)max_det + i] = -1;   // "no label", as the header says
     }
 }
 
@@ -404,16 +404,6 @@ hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, con
     hipLaunchKernelGGL(scan_stream_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, ww, vad_value, vad_mode_value, S, f0, n_new, cfg,
                        static_cast<StreamState *>(state), det, det_ww, det_label, n_det, max_det);
     return hipGetLastError();
-}
-
-hipError_t launch_scan_stream(hipStream_t st, const float *agg, const float *avg, const float *vad_value, float vad_mode_value,
-                              size_t S, long long f0, int n_new, const ScanConfig &cfg, void *state, BatchDetection *det,
-                              int32_t *n_det, int max_det) {
-    ScanWakewords ww{};
-    ww.n = 1;
-    ww.agg[0] = agg; ww.avg[0] = cfg.avg_enabled ? avg : nullptr;
-    ww.threshold[0] = cfg.threshold; ww.avg_threshold[0] = cfg.avg_threshold;
-    return launch_scan_stream_multi(st, ww, vad_value, vad_mode_value, S, f0, n_new, cfg, state, det, nullptr, nullptr, n_det, max_det);
 }
 
 }  // namespace rp

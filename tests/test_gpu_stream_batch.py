@@ -244,6 +244,24 @@ def test_stream_batch_multi_refuses_bad_specs(ra, ctx):
     one = ra.StreamBatch(ctx, tm5, cfg, 2)
     det, dww, dlab, n_det = one.process_multi(np.zeros((2, 480), np.float32))
     assert n_det.sum() == 0 and (dww == 0).all() and (dlab == -1).all()
+    # ... also where it fires: a golden recording through process_multi and, on a second batch, through process -- the same
+    # detection records bit for bit, wakeword 0 / label -1 in fired and unfired slots alike
+    w = rpw_py.load_rpw(os.path.join(G, "oye_casa_g.rpw"))
+    tm = ra.Templates(ctx, list(w["samples_features"].values()), avg=w["avg_features"])
+    z = np.zeros(16000, np.float32)
+    x = np.concatenate([z, _rd("oye_casa_g_1.wav"), z, z])
+    x = x[:len(x) // 480 * 480]
+    pcm = np.stack([x, np.roll(x, 480 * 7)])
+    cfg.threshold, cfg.avg_threshold, cfg.min_scores = 0.5, 0.2, 3
+    multi, plain = ra.StreamBatch(ctx, tm, cfg, 2, max_chunks_per_call=3), ra.StreamBatch(ctx, tm, cfg, 2, max_chunks_per_call=3)
+    fired = 0
+    for pos in range(0, pcm.shape[1], 480 * 3):
+        det, dww, dlab, n_det = multi.process_multi(pcm[:, pos:pos + 480 * 3])
+        det1, n_det1 = plain.process(pcm[:, pos:pos + 480 * 3])
+        assert det.tobytes() == det1.tobytes() and np.array_equal(n_det, n_det1)
+        assert (dww == 0).all() and (dlab == -1).all()
+        fired += int(n_det.sum())
+    assert fired >= 2
 
 
 def test_live_multi_sweep_few_cases(ra, ctx):
