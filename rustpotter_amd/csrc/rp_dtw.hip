@@ -21,35 +21,6 @@ namespace rp {
 // reproduces the reference's "magnitude == 0 -> similarity 0".
 constexpr int kDtwWin = 64;   // windows per wave
 
-// The averaged-template gate's hand-over to the template kernels (launch_dtw_gated).  count == nullptr: no gate, every
-// window is scored.  list != nullptr: LIST mode -- the lanes take the listed rows (windows that passed) and read their frames
-// from global memory; the launch does nothing when the list is dense (*count >= dense_min).  list == nullptr with a count:
-// DENSE mode -- the ordinary LDS-staged launch over every window, which does nothing unless the list is dense.  (Nearly
-// everything passing is the common case at the reference's default threshold; scoring all rows through the staged kernel is
-// then ~6 % cheaper than gathering them one by one.  Both launches are always issued; one of them exits on a scalar compare.)
-struct GateList {
-    const uint32_t *list = nullptr, *count = nullptr;
-    uint32_t dense_min = 0;
-    // entries the list may hold per row of the call (1: the gate lists a row once; dtw_ragged_kernel's list holds a window once per ragged
-    // chunk that could not resolve it): the list-mode grids cover S x n_win x list_mult entries
-    uint32_t list_mult = 1;
-    // Early abandon (detect-only calls in ScoreMode::Max): a DTW whose cheapest band cell already costs more than
-    // abandon_nc * (m + n) cannot end with a score above the detection threshold (cell costs are >= 0 and every warping
-    // path crosses every row), so a wave whose 64 windows x templates are ALL past that bound stops and reports score 0 for
-    // them.  Windows that can still fire are never touched: their wave runs to the end, with every template exact.
-    // +inf: off (the per-window score arrays are part of the call's result).  See dtw_abandon_nc().
-    float abandon_nc = __builtin_inff();
-    const DtwFusedAgg *fuse = nullptr;  // ScoreMode::Max folded into the matrix-core kernel (rp_kernels.h); set by launch_dtw only
-    // DtwWork::fix: windows with a frame whose squared norm leaves kDtwNormLo..kDtwFixLimit are listed for dtw_ref_kernel (the
-    // reference's sqrt(dot_a * dot_b) is not scale invariant there, comparator.rs:42-47); every launcher sets it
-    uint32_t *fix = nullptr;
-    uint32_t *sched = nullptr;   // DtwWork::sched for the matrix-core launches
-    uint32_t *ran = nullptr;     // DtwWork::ran
-    DtwWork wk_all;              // the call's whole DtwWork (dtw_ragged_kernel's blocks)
-    bool padded = false;         // the frame array ends with slack: the register kernels' list mode may follow dtw_ragged_kernel
-    DtwWork work() const { DtwWork w = wk_all; w.sched = sched; w.fix = fix; w.ran = ran; return w; }
-};
-
 // One wave = 64 consecutive windows of one stream x one chunk of TC same-length templates.
 // Per lane: the window's column means, a ring of the 2W unit-length window frames inside the
 // band (shared by all TC templates), and TC bands of 2W+1 running costs held as register pairs of
@@ -867,11 +838,10 @@ static hipError_t dtw_abort(hipStream_t st, const DtwWork &wk, hipError_t e) {
 
 // The pass behind every fast launch: rescoring of the listed pairs (see dtw_ref_kernel).  force_all: every window x templates
 // t_first .. t_first + t_count - 1 (index T = the averaged template).
-static hipError_t launch_dtw_ref(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const float *mfcc, size_t S, size_t frame_pitch,
-                                 size_t first_win, size_t n_win, size_t out_win_pitch, int band, float score_ref, float *scores, float *avg,
-                                 bool force_all, int t_first, int t_count, const DtwFusedAgg *fuse = nullptr) {
-    if (!wk.fix || !t.raw) return hipErrorInvalidValue;
-    const int Wmax = band > t.max_diff ? band : t.max_diff;
+static hipError_t launch_dtw_ref(const DtwCall &c, bool force_all, int t_first, int t_count, const DtwFusedAgg *fuse = nullptr) {
+    const TemplatesDev &t = *c.t;
+    if (!c.wk.fix || !t.raw) return hipErrorInvalidValue;
+    const int Wmax = c.band > t.max_diff ? c.band : t.max_diff;
     const size_t lds = ((size_t)t.K * 64 + (size_t)(2 * Wmax + 1) * 64) * sizeof(float);
     if (lds > 160 * 1024) return hipErrorMemoryAllocation;
     if (lds > 64 * 1024)
@@ -880,133 +850,119 @@ static hipError_t launch_dtw_ref(hipStream_t st, const DtwWork &wk, const Templa
     // (kDtwFixCap: pathological input) the kernel falls back to every window of the call, and a grid of one workgroup per CU would
     // walk them sixteen thousand lanes wide
     size_t blocks = 4 * (size_t)device_cu_count();
-    if (force_all) dtw_mark(wk, kDtwRanRefAll);
+    if (force_all) dtw_mark(c.wk, kDtwRanRefAll);
     if (force_all) {
-        const size_t need = (S * n_win * (size_t)(fuse ? 1 : t_count) + 63) / 64;
+        const size_t need = (c.S * c.n_win * (size_t)(fuse ? 1 : t_count) + 63) / 64;
         blocks = need < 8 * (size_t)device_cu_count() ? (need ? need : 1) : 8 * (size_t)device_cu_count();
     }
     const bool fused = fuse && fuse->agg;
-    hipLaunchKernelGGL(dtw_ref_kernel, dim3((unsigned)blocks), dim3(64), lds, st, mfcc, frame_pitch, frame_pitch, first_win, n_win, out_win_pitch, S,
-                       t.lens, t.raw, t.Lpad, t.K, t.T, t.max_len, band, Wmax, score_ref, t.chunks, scores, avg, wk.fix, force_all ? 1 : 0, t_first,
-                       t_count, fused ? fuse->agg : nullptr, fused ? fuse->hot : nullptr, fused ? fuse->threshold : 0.f);
+    hipLaunchKernelGGL(dtw_ref_kernel, dim3((unsigned)blocks), dim3(64), lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch, c.first_win, c.n_win,
+                       c.out_win_pitch, c.S, t.lens, t.raw, t.Lpad, t.K, t.T, t.max_len, c.band, Wmax, c.score_ref, t.chunks, c.scores, c.avg, c.wk.fix,
+                       force_all ? 1 : 0, t_first, t_count, fused ? fuse->agg : nullptr, fused ? fuse->hot : nullptr, fused ? fuse->threshold : 0.f);
     return hipGetLastError();
 }
 
-template <int K, int W, int TC>
-static hipError_t launch_dtw_class(hipStream_t st, const TemplatesDev &t, int chunk_base, int n_chunks, const float *mfcc, size_t S,
-                                   size_t frame_pitch, size_t tiles, size_t first_win, size_t n_win, size_t out_win_pitch,
-                                   float score_ref, float *scores, float *avg, bool few_windows, GateList gl = GateList{}) {
-    if (n_chunks <= 0) return hipSuccess;
-    dtw_mark(gl.work(), kDtwRanRegister);
-    constexpr int KP = (K % 2 == 0) ? K + 1 : K;
-    if ((few_windows || gl.list) && KP == K) {
-        // streams contribute fewer than 64 windows each (or the windows come from a list): lanes of a wave span many
-        // streams and read their frames from global memory (the caller guarantees W*K floats of slack after the last
-        // stream's frames)
-        const size_t ft = (S * n_win * (gl.list ? (size_t)gl.list_mult : 1) + kDtwWin - 1) / kDtwWin;
-        const size_t blocks = ft * (size_t)n_chunks;
-        if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((dtw_band_kernel<K, W, TC, (KP == K)>), dim3((unsigned)blocks), dim3(kDtwWin), 0, st, mfcc, frame_pitch,
-                           frame_pitch, (unsigned)ft, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch,
-                           t.chunks, t.dup, t.T, score_ref, scores, avg, 1, S, gl);
-        return hipGetLastError();
-    }
-    if (gl.list) return hipErrorNotSupported;
-    // flattened (stream, window) tiling when every stream has at least one full tile of windows
-    const int flat = (n_win >= (size_t)kDtwWin && S > 1) ? 1 : 0;
-    const size_t ft = flat ? (S * n_win + kDtwWin - 1) / kDtwWin : tiles;
-    const size_t blocks = flat ? ft * (size_t)n_chunks : tiles * (size_t)n_chunks * S;
+// Grid of one register-kernel launch over n_chunks chunks, NW windows per wave.  from_global (streams contribute fewer windows than a wave
+// holds, or the windows come from the gate's list): the lanes of a wave are consecutive entries of the flattened (stream, window) space --
+// of the list, list_mult entries per row -- and read their frames from global memory (the caller guarantees W*K floats of slack after the
+// last stream's frames).  Staged: the same flattened tiling when the kernel knows it (may_flat) and every stream has at least one full
+// tile of windows, else tiles that never cross a stream.
+struct BandGrid {
+    int flat = 0;
+    unsigned ft = 0, blocks = 0;   // tiles (flat: of the call, else of one stream), workgroups
+};
+static hipError_t dtw_band_grid(const DtwCall &c, size_t NW, int n_chunks, bool from_global, size_t list_mult, bool may_flat, BandGrid &g) {
+    g.flat = (from_global || (may_flat && c.n_win >= NW && c.S > 1)) ? 1 : 0;
+    const size_t ft = g.flat ? (c.S * c.n_win * list_mult + NW - 1) / NW : (c.n_win + NW - 1) / NW;
+    const size_t blocks = ft * (size_t)n_chunks * (g.flat ? 1 : c.S);
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const size_t lds = (size_t)(kDtwWin + 2 * (t.max_len + W)) * KP * sizeof(float);
-    if (lds > 64 * 1024)
-        if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_band_kernel<K, W, TC, false>), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((dtw_band_kernel<K, W, TC, false>), dim3((unsigned)blocks), dim3(kDtwWin), lds, st, mfcc, frame_pitch,
-                       frame_pitch, (unsigned)ft, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch,
-                       t.chunks, t.dup, t.T, score_ref, scores, avg, flat, S, gl);
+    g.ft = (unsigned)ft;
+    g.blocks = (unsigned)blocks;
+    return hipSuccess;
+}
+// LDS of a staged register launch: a wave's NW windows and `segs` stream segments of max_len + W frames, pitch mfcc_size | 1
+static hipError_t dtw_band_lds(const DtwCall &c, const void *kernel, int NW, int segs, int W, size_t &lds) {
+    lds = (size_t)(NW + segs * (c.t->max_len + W)) * (size_t)(c.t->K | 1) * sizeof(float);
+    return lds > 64 * 1024 ? allow_dynamic_lds(kernel, 160 * 1024) : hipSuccess;
+}
+
+// dtw_band_kernel (NW = 64 windows per wave) or dtw_band2_kernel (128: chunks of ONE template, two windows per lane) at mfcc_size 5 over
+// chunks chunk_base .. chunk_base + n_chunks - 1: `global` is the kernel's form that reads frames from global memory (mfcc_size 5 is odd:
+// the pitch of the frames in memory is the conflict-free one), `staged` the LDS-staged form
+using BandKernel = void (*)(const float *, size_t, size_t, unsigned, unsigned, int, size_t, size_t, size_t, const DtwChunk *, const float *, int,
+                            float, float *, float *, int, size_t, GateList);
+static hipError_t launch_dtw_band(const DtwCall &c, int NW, int W, BandKernel global, BandKernel staged, int chunk_base, int n_chunks, bool few,
+                                  GateList gl) {
+    if (n_chunks <= 0) return hipSuccess;
+    dtw_mark(c.wk, kDtwRanRegister);
+    const TemplatesDev &t = *c.t;
+    gl.fix = c.wk.fix;
+    const bool from_global = few || gl.list;
+    const BandKernel kernel = from_global ? global : staged;
+    BandGrid g;
+    if (hipError_t e = dtw_band_grid(c, (size_t)NW, n_chunks, from_global, gl.list ? (size_t)gl.list_mult : 1, true, g); e != hipSuccess) return e;
+    size_t lds = 0;
+    if (!from_global)
+        if (hipError_t e = dtw_band_lds(c, reinterpret_cast<const void *>(staged), NW, 2, W, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(kDtwWin), lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch, g.ft,
+                       (unsigned)n_chunks, chunk_base, c.first_win, c.n_win, c.out_win_pitch, t.chunks, t.dup, t.T, c.score_ref, c.scores, c.avg,
+                       g.flat, c.S, gl);
+    return hipGetLastError();
+}
+template <int W, int TC>
+static hipError_t launch_dtw_class(const DtwCall &c, int chunk_base, int n_chunks, bool few, const GateList &gl) {
+    return launch_dtw_band(c, kDtwWin, W, dtw_band_kernel<5, W, TC, true>, dtw_band_kernel<5, W, TC, false>, chunk_base, n_chunks, few, gl);
+}
+template <int W>
+static hipError_t launch_dtw_single_chunks(const DtwCall &c, int chunk_base, int n_chunks, bool few, const GateList &gl) {
+    return launch_dtw_band(c, 2 * kDtwWin, W, dtw_band2_kernel<5, W, true>, dtw_band2_kernel<5, W, false>, chunk_base, n_chunks, few, gl);
+}
+
+// dtw_band_wide_kernel (mfcc_size 13 / 16): no flattened staged tiling, one stream segment per staged tile.  (Its list-mode grid covers
+// S x n_win entries, not list_mult times as many: it is only reached with list_mult == 1 -- dtw_ragged_kernel, mfcc_size 5, alone
+// lists a row more than once.)
+template <int K, int W, int TC>
+static hipError_t launch_dtw_wide(const DtwCall &c, int chunk_base, int n_chunks, bool few, GateList gl) {
+    if (n_chunks <= 0) return hipSuccess;
+    dtw_mark(c.wk, kDtwRanRegister);
+    const TemplatesDev &t = *c.t;
+    gl.fix = c.wk.fix;
+    const bool from_global = few || gl.list;
+    const auto kernel = from_global ? dtw_band_wide_kernel<K, W, TC, true> : dtw_band_wide_kernel<K, W, TC, false>;
+    BandGrid g;
+    if (hipError_t e = dtw_band_grid(c, (size_t)kDtwWin, n_chunks, from_global, 1, false, g); e != hipSuccess) return e;
+    size_t lds = 0;
+    if (!from_global)
+        if (hipError_t e = dtw_band_lds(c, reinterpret_cast<const void *>(kernel), kDtwWin, 1, W, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(kDtwWin), lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch, g.ft, (unsigned)n_chunks, chunk_base,
+                       c.first_win, c.n_win, c.out_win_pitch, t.chunks, t.dup, t.T, c.score_ref, c.scores, c.avg, from_global ? c.S : (size_t)0, gl);
     return hipGetLastError();
 }
 
-// chunks of ONE template: two windows per lane (dtw_band2_kernel)
+// the averaged template alone: the last of the single-template chunks (class 3)
 template <int K, int W>
-static hipError_t launch_dtw_single_chunks(hipStream_t st, const TemplatesDev &t, int chunk_base, int n_chunks, const float *mfcc, size_t S,
-                                           size_t frame_pitch, size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref,
-                                           float *scores, float *avg, bool few_windows, GateList gl = GateList{}) {
-    if (n_chunks <= 0) return hipSuccess;
-    dtw_mark(gl.work(), kDtwRanRegister);
-    constexpr int KP = (K % 2 == 0) ? K + 1 : K;
-    constexpr int NW = 2 * kDtwWin;
-    if ((few_windows || gl.list) && KP == K) {
-        const size_t ft = (S * n_win * (gl.list ? (size_t)gl.list_mult : 1) + NW - 1) / NW;
-        const size_t blocks = ft * (size_t)n_chunks;
-        if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((dtw_band2_kernel<K, W, (KP == K)>), dim3((unsigned)blocks), dim3(kDtwWin), 0, st, mfcc, frame_pitch,
-                           frame_pitch, (unsigned)ft, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch,
-                           t.chunks, t.dup, t.T, score_ref, scores, avg, 1, S, gl);
-        return hipGetLastError();
-    }
-    if (gl.list) return hipErrorNotSupported;
-    const size_t tiles = (n_win + NW - 1) / NW;
-    const int flat = (n_win >= (size_t)NW && S > 1) ? 1 : 0;
-    const size_t ft = flat ? (S * n_win + NW - 1) / NW : tiles;
-    const size_t blocks = flat ? ft * (size_t)n_chunks : tiles * (size_t)n_chunks * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const size_t lds = (size_t)(NW + 2 * (t.max_len + W)) * KP * sizeof(float);
-    if (lds > 64 * 1024)
-        if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_band2_kernel<K, W, false>), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((dtw_band2_kernel<K, W, false>), dim3((unsigned)blocks), dim3(kDtwWin), lds, st, mfcc, frame_pitch,
-                       frame_pitch, (unsigned)ft, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch,
-                       t.chunks, t.dup, t.T, score_ref, scores, avg, flat, S, gl);
-    return hipGetLastError();
-}
-
-template <int K, int W, int TC>
-static hipError_t launch_dtw_wide(hipStream_t st, const TemplatesDev &t, int cls, int n_chunks, const float *mfcc, size_t S,
-                                  size_t frame_pitch, size_t tiles, size_t first_win, size_t n_win, size_t out_win_pitch,
-                                  float score_ref, float *scores, float *avg, bool few_windows = false, GateList gl = GateList{}, int chunk_base = -1) {
-    if (n_chunks <= 0) return hipSuccess;
-    dtw_mark(gl.work(), kDtwRanRegister);
-    if (chunk_base < 0) chunk_base = t.class_first[cls];
-    if (few_windows || gl.list) {
-        // lanes span streams (few windows per stream) or come from the gate's list: frames read from global memory
-        const size_t ft = (S * n_win + kDtwWin - 1) / kDtwWin;
-        const size_t blocks = ft * (size_t)n_chunks;
-        if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((dtw_band_wide_kernel<K, W, TC, true>), dim3((unsigned)blocks), dim3(kDtwWin), 0, st, mfcc, frame_pitch,
-                           frame_pitch, (unsigned)ft, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch,
-                           t.chunks, t.dup, t.T, score_ref, scores, avg, S, gl);
-        return hipGetLastError();
-    }
-    const size_t blocks = tiles * (size_t)n_chunks * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    constexpr int KP = (K % 2 == 0) ? K + 1 : K;
-    const size_t lds = (size_t)(kDtwWin + t.max_len + W) * KP * sizeof(float);
-    if (lds > 64 * 1024)
-        if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_band_wide_kernel<K, W, TC, false>), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((dtw_band_wide_kernel<K, W, TC, false>), dim3((unsigned)blocks), dim3(kDtwWin), lds, st, mfcc, frame_pitch,
-                       frame_pitch, (unsigned)tiles, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch,
-                       t.chunks, t.dup, t.T, score_ref, scores, avg, (size_t)0, gl);
-    return hipGetLastError();
+static hipError_t launch_dtw_avg_chunk(const DtwCall &c, bool few, const GateList &gl) {
+    const int avg_chunk = c.t->class_first[3] + c.t->class_count[3] - 1;
+    if constexpr (K == 5) return launch_dtw_single_chunks<W>(c, avg_chunk, 1, few, gl);
+    else return launch_dtw_wide<K, W, 1>(c, avg_chunk, 1, few, gl);
 }
 
 // wide frames (mfcc_size 13 / 16): single-template chunks (class 3, n1 of them) one template per lane, pairs (class 0) two
 template <int K, int W>
-static hipError_t launch_dtw_wide_all(hipStream_t st, const TemplatesDev &t, int n1, const float *mfcc, size_t S, size_t frame_pitch,
-                                      size_t tiles, size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref, float *scores,
-                                      float *avg, bool few, GateList gl = GateList{}, bool padded = false) {
+static hipError_t launch_dtw_wide_all(const DtwCall &c, int n1, bool few, const GateList &gl) {
+    const TemplatesDev &t = *c.t;
     // every length at least three times, band 5, rows with slack behind them: the sample templates on the matrix cores
     // (rp_dtw_mfma_wide.hip), the averaged template -- if it is to be scored here -- through the one-template register kernel
-    const bool rows_ok = W == 5 && (padded || few || gl.list);
-    const bool three_part = rows_ok && dtw_mfma_wide3_supported(t, W);                       // the default arithmetic: chunks of four
-    const bool two_part = rows_ok && !three_part && dtw_mfma_wide_supported(t, W, score_ref);  // RP_ARITH_FAST_SPLIT: chunks of eight
+    const bool rows_ok = W == 5 && (c.padded_rows || few || gl.list);
+    const bool three_part = rows_ok && dtw_mfma_wide3_supported(t, W);                         // the default arithmetic: chunks of four
+    const bool two_part = rows_ok && !three_part && dtw_mfma_wide_supported(t, W, c.score_ref);  // RP_ARITH_FAST_SPLIT: chunks of eight
     if (three_part || two_part) {
         if (t.has_avg && n1 == t.class_count[3])
-            if (hipError_t e = launch_dtw_wide<K, W, 1>(st, t, 3, 1, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg,
-                                                        few, gl, t.class_first[3] + t.class_count[3] - 1); e != hipSuccess) return e;
-        return (three_part ? launch_dtw_mfma_wide3 : launch_dtw_mfma_wide)(st, gl.work(), t, W, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref,
-                                                                          scores, avg, gl.list, gl.count, gl.dense_min, gl.abandon_nc);
+            if (hipError_t e = launch_dtw_avg_chunk<K, W>(c, few, gl); e != hipSuccess) return e;
+        return (three_part ? launch_dtw_mfma_wide3 : launch_dtw_mfma_wide)(c, gl);
     }
-    if (hipError_t e = launch_dtw_wide<K, W, 1>(st, t, 3, n1, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl); e != hipSuccess) return e;
-    return launch_dtw_wide<K, W, 2>(st, t, 0, t.class_count[0], mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
+    if (hipError_t e = launch_dtw_wide<K, W, 1>(c, t.class_first[3], n1, few, gl); e != hipSuccess) return e;
+    return launch_dtw_wide<K, W, 2>(c, t.class_first[0], t.class_count[0], few, gl);
 }
 
 // Largest template tile the register kernels are built for at this (mfcc_size, band) (0 = only the generic
@@ -1137,57 +1093,63 @@ int dtw_register_tile(int K, int band) {
     return 0;
 }
 
+// dtw_single_kernel over the call's windows (one stream) x templates t_first .. t_first + t_count - 1; lds: DtwRoute::single_lds
+static hipError_t launch_dtw_single(const DtwCall &c, size_t lds, int t_first, int t_count) {
+    const TemplatesDev &t = *c.t;
+    hipLaunchKernelGGL(dtw_single_kernel, dim3((unsigned)(c.n_win * t_count)), dim3(64), lds, c.st, c.mfcc, c.frame_pitch, c.first_win,
+                       (unsigned)c.n_win, c.out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, t_first, t_count, t.max_len, c.band, c.score_ref,
+                       c.scores, c.avg, t.raw, t.ref_only, c.wk.fix);
+    return hipGetLastError();
+}
+
 template <int W>
-static hipError_t launch_dtw_k5(hipStream_t st, const TemplatesDev &t, int n1, const float *mfcc, size_t S, size_t frame_pitch,
-                                size_t tiles, size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref,
-                                float *scores, float *avg, bool few, GateList gl = GateList{}) {
+static hipError_t launch_dtw_k5(const DtwCall &c, int n1, bool few, const GateList &gl) {
+    const TemplatesDev &t = *c.t;
+    const size_t S = c.S, n_win = c.n_win;
     hipError_t e;
     // templates whose length occurs once or twice: the matrix-core kernel for unequal lengths (rp_dtw_ragged.hip) when every window of
-    // the call is scored from LDS-staged tiles; the averaged template (its own output array) keeps its register launch.  The windows that
-    // kernel lists (a frame it cannot resolve within the parity gate: digital silence behind speech, wild scales) are scored again by the
-    // register kernels in list mode -- two launches that leave at once when nothing is listed -- or, without slack behind the frame
-    // array, by dtw_ref_kernel
-    if (!few && !gl.list && !gl.count && t.rag_count > 0 && W <= 5 && gl.wk_all.rag_prep && gl.wk_all.rag_streams >= S &&
-        dtw_ragged_supported(t, W, n_win, score_ref)) {
-        const int n_avg = (t.has_avg && n1 == t.class_count[3] && n1 > 0) ? 1 : 0;
-        if (n_avg)
-            if ((e = launch_dtw_single_chunks<5, W>(st, t, t.class_first[3] + t.class_count[3] - 1, 1, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl)) != hipSuccess) return e;
+    // the call is scored from LDS-staged tiles (never behind the gate: !gl.count); the averaged template (its own output array) keeps its
+    // register launch.  The windows that kernel lists (a frame it cannot resolve within the parity gate: digital silence behind speech, wild
+    // scales) are scored again by the register kernels in list mode -- two launches that leave at once when nothing is listed -- or,
+    // without slack behind the frame array, by dtw_ref_kernel
+    if (!few && !gl.list && !gl.count && t.rag_count > 0 && W <= 5 && c.wk.rag_prep && c.wk.rag_streams >= S &&
+        dtw_ragged_supported(t, W, n_win, c.score_ref)) {
+        if (t.has_avg && n1 == t.class_count[3] && n1 > 0)
+            if ((e = launch_dtw_avg_chunk<5, W>(c, few, gl)) != hipSuccess) return e;
         // (every ragged chunk lists on its own: a window may be listed once per chunk -- the list holds rows x chunks entries)
-        const bool list_rows = gl.padded && gl.wk_all.rag_list && gl.wk_all.rag_rows >= S * n_win * (size_t)t.rag_count && out_win_pitch == n_win;
-        if ((e = launch_dtw_ragged(st, gl.work(), t, W, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref, scores, gl.abandon_nc, list_rows)) != hipSuccess) return e;
+        const bool list_rows = c.padded_rows && c.wk.rag_list && c.wk.rag_rows >= S * n_win * (size_t)t.rag_count && c.out_win_pitch == n_win;
+        if ((e = launch_dtw_ragged(c, gl.abandon_nc, list_rows)) != hipSuccess) return e;
         if (list_rows) {
             GateList g2 = gl;
-            g2.list = gl.wk_all.rag_list + 1; g2.count = gl.wk_all.rag_list; g2.dense_min = 0; g2.fuse = nullptr;
+            g2.list = c.wk.rag_list + 1; g2.count = c.wk.rag_list; g2.dense_min = 0; g2.fuse = nullptr;
             g2.list_mult = (uint32_t)t.rag_count;   // every ragged chunk lists on its own (round-5 advice: a grid for S x n_win entries dropped the tail)
-            if ((e = launch_dtw_single_chunks<5, W>(st, t, t.class_first[3], t.class_count[3] - (t.has_avg ? 1 : 0), mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref, scores, avg, false, g2)) != hipSuccess) return e;
-            if ((e = launch_dtw_class<5, W, 2>(st, t, t.class_first[0], t.class_count[0], mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, false, g2)) != hipSuccess) return e;
+            if ((e = launch_dtw_single_chunks<W>(c, t.class_first[3], t.class_count[3] - (t.has_avg ? 1 : 0), false, g2)) != hipSuccess) return e;
+            if ((e = launch_dtw_class<W, 2>(c, t.class_first[0], t.class_count[0], false, g2)) != hipSuccess) return e;
         }
     } else {
         // n1: single-template chunks to score (class 3; the averaged template is its last chunk)
-        if ((e = launch_dtw_single_chunks<5, W>(st, t, t.class_first[3], n1, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl)) != hipSuccess) return e;
-        if ((e = launch_dtw_class<5, W, 2>(st, t, t.class_first[0], t.class_count[0], mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl)) != hipSuccess) return e;
+        if ((e = launch_dtw_single_chunks<W>(c, t.class_first[3], n1, few, gl)) != hipSuccess) return e;
+        if ((e = launch_dtw_class<W, 2>(c, t.class_first[0], t.class_count[0], few, gl)) != hipSuccess) return e;
     }
     // chunks of 3..8 templates: the matrix-core kernel (rp_dtw_mfma.hip) in every mode (LDS-staged, frames from global memory for
     // live-stream batches and the gate's list, early abandon): 5..8 templates at band 3..5 with eight template slots per wave, 3..4 at
     // band 5 with four.
     {
         const bool from_global = few || gl.list != nullptr;
-        if (t.class_count[1] > 0 && dtw_mfma_supported(t, W, n_win, from_global, 4, score_ref)) {
-            if ((e = launch_dtw_mfma(st, gl.work(), t, W, 4, t.class_first[1], t.class_count[1], mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref,
-                                     scores, avg, from_global, gl.list, gl.count, gl.dense_min, gl.abandon_nc, gl.fuse)) != hipSuccess) return e;
-        } else if ((e = launch_dtw_class<5, W, 4>(st, t, t.class_first[1], t.class_count[1], mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl)) != hipSuccess) return e;
-        if (t.class_count[2] > 0 && dtw_mfma_supported(t, W, n_win, from_global, 8, score_ref)) {
+        if (t.class_count[1] > 0 && dtw_mfma_supported(t, W, n_win, from_global, 4, c.score_ref)) {
+            if ((e = launch_dtw_mfma(c, 4, t.class_first[1], t.class_count[1], from_global, gl)) != hipSuccess) return e;
+        } else if ((e = launch_dtw_class<W, 4>(c, t.class_first[1], t.class_count[1], few, gl)) != hipSuccess) return e;
+        if (t.class_count[2] > 0 && dtw_mfma_supported(t, W, n_win, from_global, 8, c.score_ref)) {
             // several chunks of one length, every window of a long batch scored: the workgroups that share a column's B operand among four
             // (two) chunks (rp_dtw_mfma_group.hip: same bits); the chunks outside a group, and every other mode, keep dtw_mfma_kernel
-            if (!from_global && !gl.count && !gl.fuse && !(gl.abandon_nc < RP_INF) && dtw_mfma_group_supported(t, W, n_win, S, score_ref)) {
-                if ((e = launch_dtw_mfma_group(st, gl.work(), t, W, mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref, scores)) != hipSuccess) return e;
+            // (gl is then no gate, no abandon and no fuse)
+            if (!from_global && !gl.count && !gl.fuse && !(gl.abandon_nc < RP_INF) && dtw_mfma_group_supported(t, W, n_win, S, c.score_ref)) {
+                if ((e = launch_dtw_mfma_group(c)) != hipSuccess) return e;
                 for (int r = 0; r < t.rest_runs; ++r)
-                    if ((e = launch_dtw_mfma(st, gl.work(), t, W, 8, t.rest_first[r], t.rest_count[r], mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref,
-                                             scores, avg, false, nullptr, nullptr, 0, gl.abandon_nc, nullptr)) != hipSuccess) return e;
+                    if ((e = launch_dtw_mfma(c, 8, t.rest_first[r], t.rest_count[r], false, gl)) != hipSuccess) return e;
                 return hipSuccess;
             }
-            return launch_dtw_mfma(st, gl.work(), t, W, 8, t.class_first[2], t.class_count[2], mfcc, S, frame_pitch, first_win, n_win, out_win_pitch, score_ref,
-                                   scores, avg, from_global, gl.list, gl.count, gl.dense_min, gl.abandon_nc, gl.fuse);
+            return launch_dtw_mfma(c, 8, t.class_first[2], t.class_count[2], from_global, gl);
         }
     }
     // Small batches: tc-8 waves run two per SIMD; a launch that fills those slots 2.x times leaves the chip mostly idle in
@@ -1197,10 +1159,9 @@ static hipError_t launch_dtw_k5(hipStream_t st, const TemplatesDev &t, int n1, c
         const double waves8 = (double)((S * n_win + kDtwWin - 1) / kDtwWin) * t.class_count[2];
         const double slots = 4.0 * device_cu_count();
         const double cost8 = std::ceil(waves8 / (2.0 * slots)), cost4 = 0.85 * std::ceil(2.0 * waves8 / (3.0 * slots));
-        if (waves8 < 3.0 * 2.0 * slots && cost4 < cost8)
-            return launch_dtw_class<5, W, 4>(st, t, t.split_first, t.split_count, mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
+        if (waves8 < 3.0 * 2.0 * slots && cost4 < cost8) return launch_dtw_class<W, 4>(c, t.split_first, t.split_count, few, gl);
     }
-    return launch_dtw_class<5, W, 8>(st, t, t.class_first[2], t.class_count[2], mfcc, S, frame_pitch, tiles, first_win, n_win, out_win_pitch, score_ref, scores, avg, few, gl);
+    return launch_dtw_class<W, 8>(c, t.class_first[2], t.class_count[2], few, gl);
 }
 
 // ---- the averaged-template gate as a skip (wakeword_comp.rs:85-93) -------------------------------------------------
@@ -1293,94 +1254,89 @@ static DtwRoute dtw_route(const TemplatesDev &t, int band, size_t S, size_t n_wi
 // e = CALL(K, W) on the (mfcc_size, band) pairs the register kernels are built for (dtw_register_tile > 0).  (A switch, not a generic
 // lambda: it keeps the order in which the kernel templates are instantiated, and with it the layout of the code object.)
 #define RP_BAND_DISPATCH(e, CALL, KK) \
-    switch (band) { case 3: e = CALL(KK, 3); break; case 4: e = CALL(KK, 4); break; case 5: e = CALL(KK, 5); break; default: e = CALL(KK, 6); }
-#define RP_REGISTER_DISPATCH(e, CALL)                                                                                                            \
-    do {                                                                                                                                         \
-        if (t.K == 5) { RP_BAND_DISPATCH(e, CALL, 5) } else if (t.K == 16) { RP_BAND_DISPATCH(e, CALL, 16) } else { RP_BAND_DISPATCH(e, CALL, 13) } \
-    } while (0)
+    switch (c.band) { case 3: e = CALL(KK, 3); break; case 4: e = CALL(KK, 4); break; case 5: e = CALL(KK, 5); break; default: e = CALL(KK, 6); }
 
-// the register family of (K, W): n1 single-template chunks, then the chunks of several templates
-template <int K, int W>
-static hipError_t launch_dtw_register(hipStream_t st, const TemplatesDev &t, int n1, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                      size_t n_win, float score_ref, float *scores, float *avg, bool few, const GateList &gl, bool padded) {
-    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin;
-    if constexpr (K == 5) return launch_dtw_k5<W>(st, t, n1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, few, gl);
-    else return launch_dtw_wide_all<K, W>(st, t, n1, mfcc, S, frame_pitch, tiles, first_win, n_win, n_win, score_ref, scores, avg, few, gl, padded);
+// The register family of the call's (mfcc_size, band): the averaged template's chunk alone (AVG_ONLY), or n1 single-template chunks and
+// then the chunks of several templates.  (AVG_ONLY is a template parameter for the same reason as the switch: the gate names <true>
+// first, so every one-template kernel is still instantiated before the others.)
+template <bool AVG_ONLY, int K, int W>
+static hipError_t launch_dtw_register_kw(const DtwCall &c, int n1, bool few, const GateList &gl) {
+    if constexpr (AVG_ONLY) return launch_dtw_avg_chunk<K, W>(c, few, gl);
+    else if constexpr (K == 5) return launch_dtw_k5<W>(c, n1, few, gl);
+    else return launch_dtw_wide_all<K, W>(c, n1, few, gl);
+}
+template <bool AVG_ONLY>
+static hipError_t launch_dtw_register(const DtwCall &c, int n1, bool few, const GateList &gl) {
+    hipError_t e;
+#define RP_REGISTER(KK, WW) launch_dtw_register_kw<AVG_ONLY, KK, WW>(c, n1, few, gl)
+    if (c.t->K == 5) { RP_BAND_DISPATCH(e, RP_REGISTER, 5) } else if (c.t->K == 16) { RP_BAND_DISPATCH(e, RP_REGISTER, 16) } else { RP_BAND_DISPATCH(e, RP_REGISTER, 13) }
+#undef RP_REGISTER
+    return e;
 }
 
 // The gate behind the register kernels (few: DtwRoute::few -- live-stream batches score the few newest windows of every stream: then
-// pass 1 also reads its frames from global memory); scores / avg rows have pitch n_win.
-template <int K, int W>
-static hipError_t gated_register(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, bool few, const float *mfcc, size_t S, size_t frame_pitch,
-                                 size_t first_win, size_t n_win, float score_ref, float avg_threshold, float *scores, float *avg, uint32_t *list,
-                                 uint32_t *count, float abandon_nc) {
-    const size_t rows = S * n_win;
-    const int avg_chunk = t.class_first[3] + t.class_count[3] - 1;  // the averaged template: last of the single-template chunks
+// pass 1 also reads its frames from global memory); list [1 + S * n_win] words, the first the count.
+static hipError_t gated_register(const DtwCall &c, bool few, float avg_threshold, uint32_t *list, float abandon_nc) {
+    const TemplatesDev &t = *c.t;
+    const size_t rows = c.S * c.n_win;
+    hipError_t e;
+    if ((e = hipMemsetAsync(list, 0, sizeof(uint32_t), c.st)) != hipSuccess) return e;
     // pass 1: the averaged template over every window (and, before the gate looks at them, the reference-shaped rescoring of the
     // windows whose frames left the norm range: dtw_ref_kernel)
-    GateList g1;
-    g1.fix = wk.fix; g1.sched = wk.sched; g1.ran = wk.ran;
-    hipError_t e;
-    if constexpr (K == 5) e = launch_dtw_single_chunks<5, W>(st, t, avg_chunk, 1, mfcc, S, frame_pitch, first_win, n_win, n_win, score_ref, scores, avg, few, g1);
-    else e = launch_dtw_wide<K, W, 1>(st, t, 3, 1, mfcc, S, frame_pitch, (n_win + kDtwWin - 1) / kDtwWin, first_win, n_win, n_win, score_ref, scores, avg, few, g1, avg_chunk);
-    if (e != hipSuccess) return e;
-    if ((e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, W, score_ref, scores, avg, false, t.T, 1)) != hipSuccess) return e;
+    if ((e = launch_dtw_register<true>(c, 0, few, GateList{})) != hipSuccess) return e;
+    if ((e = launch_dtw_ref(c, false, t.T, 1)) != hipSuccess) return e;
     // pass 2: list the rows whose avg_score is not below the threshold
     const size_t waves = (rows + 1023) / 1024, blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL(gate_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, st, avg, rows, avg_threshold, list, count);
+    hipLaunchKernelGGL(gate_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st, c.avg, rows, avg_threshold, list + 1, list);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // pass 3: the sample templates on the listed rows -- or, when (nearly) every row is listed, on all rows through the
     // ordinary staged launch (GateList; with few windows per stream both forms read global memory: list mode only)
     GateList gl;
-    gl.list = list; gl.count = count; gl.abandon_nc = abandon_nc; gl.fix = wk.fix; gl.sched = wk.sched; gl.ran = wk.ran;
+    gl.list = list + 1; gl.count = list; gl.abandon_nc = abandon_nc;
     gl.dense_min = few ? 0u : (uint32_t)(rows - rows / 10);
-    e = launch_dtw_register<K, W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, first_win, n_win, score_ref, scores, avg, false, gl, true);
-    if (e != hipSuccess) return e;
+    if ((e = launch_dtw_register<false>(c, t.class_count[3] - 1, false, gl)) != hipSuccess) return e;
     if (!few) {
         gl.list = nullptr;
-        if ((e = launch_dtw_register<K, W>(st, t, t.class_count[3] - 1, mfcc, S, frame_pitch, first_win, n_win, score_ref, scores, avg, false, gl, true)) != hipSuccess) return e;
+        if ((e = launch_dtw_register<false>(c, t.class_count[3] - 1, false, gl)) != hipSuccess) return e;
     }
-    return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, W, score_ref, scores, avg, false, 0, t.T);
+    return launch_dtw_ref(c, false, 0, t.T);
+}
+
+// dtw_generic_kernel over templates t_first .. t_first + t_count - 1 (index T = the averaged template); gate_avg: each wave leaves at once
+// when none of its 64 windows has gate_avg[row] >= gate_threshold
+static hipError_t launch_dtw_generic(const DtwCall &c, const DtwRoute &r, int t_first, int t_count, const float *gate_avg, float gate_threshold) {
+    const TemplatesDev &t = *c.t;
+    const size_t tiles = (c.n_win + kDtwWin - 1) / kDtwWin, blocks = tiles * (size_t)t_count * c.S;
+    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    if (r.generic_lds > 160 * 1024) return hipErrorMemoryAllocation;  // reported as "template too long" by the callers' hip_ok text
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_generic_kernel), 160 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)blocks), dim3(64), r.generic_lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch, (unsigned)tiles,
+                       c.first_win, c.n_win, c.out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, t_first, t_count, t.max_len, c.band, c.score_ref,
+                       c.scores, c.avg, gate_avg, gate_threshold, c.wk.fix);
+    return hipGetLastError();
 }
 
 // The gate behind the generic kernel: pass 1 scores every window against the averaged template (-> avg), pass 2 the sample
 // templates, each wave leaving at once when none of its 64 windows passed (scores of such rows are not written; the aggregate
 // pass gives them 0).
-static hipError_t gated_generic(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
-                                size_t first_win, size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg) {
+static hipError_t gated_generic(const DtwCall &c, const DtwRoute &r, float avg_threshold) {
+    const TemplatesDev &t = *c.t;
+    hipError_t e;
     if (t.ref_only) {  // a template row outside the norm range: every window reference-shaped, no skipping (the aggregate pass writes 0 for rejected rows)
-        if (hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, true, t.T, 1); e != hipSuccess) return e;
-        return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, true, 0, t.T);
+        if ((e = launch_dtw_ref(c, true, t.T, 1)) != hipSuccess) return e;
+        return launch_dtw_ref(c, true, 0, t.T);
     }
-    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin;
-    if (tiles * (size_t)t.T * S > 0x7fffffffULL) return hipErrorInvalidValue;
-    if (r.generic_lds > 160 * 1024) return hipErrorMemoryAllocation;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_generic_kernel), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)(tiles * S)), dim3(64), r.generic_lds, st, mfcc, frame_pitch, frame_pitch, (unsigned)tiles,
-                       first_win, n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, t.T, 1, t.max_len, band, score_ref, scores, avg,
-                       static_cast<const float *>(nullptr), 0.f, wk.fix);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if ((e = launch_dtw_generic(c, r, t.T, 1, nullptr, 0.f)) != hipSuccess) return e;
     // the gate must see reference-shaped avg scores: rescoring of the listed windows first
-    if (hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, false, t.T, 1); e != hipSuccess) return e;
-    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)(tiles * (size_t)t.T * S)), dim3(64), r.generic_lds, st, mfcc, frame_pitch, frame_pitch,
-                       (unsigned)tiles, first_win, n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, 0, t.T, t.max_len, band, score_ref,
-                       scores, avg, static_cast<const float *>(avg), avg_threshold, wk.fix);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    return launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, false, 0, t.T);
+    if ((e = launch_dtw_ref(c, false, t.T, 1)) != hipSuccess) return e;
+    if ((e = launch_dtw_generic(c, r, 0, t.T, c.avg, avg_threshold)) != hipSuccess) return e;
+    return launch_dtw_ref(c, false, 0, t.T);
 }
 
-// The averaged-template gate in the form the route names (r.gate != kGateNone): list [1 + S * n_win] words, the first the count.
-static hipError_t launch_dtw_gated(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
-                                   size_t first_win, size_t n_win, int band, float score_ref, float avg_threshold, float *scores, float *avg,
-                                   uint32_t *list, float abandon_nc) {
-    hipError_t e;
-    if (r.gate == kGateGeneric) e = gated_generic(st, wk, t, r, mfcc, S, frame_pitch, first_win, n_win, band, score_ref, avg_threshold, scores, avg);
-    else if ((e = hipMemsetAsync(list, 0, sizeof(uint32_t), st)) == hipSuccess) {
-#define RP_GATED(KK, WW) gated_register<KK, WW>(st, wk, t, r.few, mfcc, S, frame_pitch, first_win, n_win, score_ref, avg_threshold, scores, avg, list + 1, list, abandon_nc)
-        RP_REGISTER_DISPATCH(e, RP_GATED);
-#undef RP_GATED
-    }
-    return e == hipSuccess ? e : dtw_abort(st, wk, e);
+// The averaged-template gate in the form the route names (r.gate != kGateNone)
+static hipError_t launch_dtw_gated(const DtwCall &c, const DtwRoute &r, float avg_threshold, uint32_t *list, float abandon_nc) {
+    const hipError_t e = r.gate == kGateGeneric ? gated_generic(c, r, avg_threshold) : gated_register(c, r.few, avg_threshold, list, abandon_nc);
+    return e == hipSuccess ? e : dtw_abort(c.st, c.wk, e);
 }
 
 // Normalised-cost bound above which a DTW cannot reach `threshold` any more: score = 1 / (1 + exp((nc - ref) / ref)) > thr
@@ -1394,60 +1350,42 @@ static float dtw_abandon_nc(float threshold, float score_ref) {
 
 // The ungated fast launches: dtw_single_kernel, the register kernels or dtw_generic_kernel.  fuse: the caller's ScoreMode::Max outputs;
 // `done` is set when the matrix-core kernel writes them.
-static hipError_t launch_dtw_fast(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
-                                  size_t first_win, size_t n_win, int band, float score_ref, int Ttot, float *scores, float *avg, bool padded_rows,
-                                  float abandon_nc, DtwFusedAgg *fuse) {
+static hipError_t launch_dtw_fast(const DtwCall &c, const DtwRoute &r, int Ttot, float abandon_nc, DtwFusedAgg *fuse) {
+    const TemplatesDev &t = *c.t;
     if (r.single) {
-        hipLaunchKernelGGL(dtw_single_kernel, dim3((unsigned)(n_win * Ttot)), dim3(64), r.single_lds, st, mfcc, frame_pitch, first_win,
-                           (unsigned)n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, 0, Ttot, t.max_len, band, score_ref,
-                           scores, avg, t.raw, t.ref_only, wk.fix);
-        dtw_mark(wk, kDtwRanSingle);
-        return hipGetLastError();
+        dtw_mark(c.wk, kDtwRanSingle);
+        return launch_dtw_single(c, r.single_lds, 0, Ttot);
     }
     if (r.reg) {
         GateList gl;
-        gl.abandon_nc = abandon_nc; gl.fix = wk.fix; gl.sched = wk.sched; gl.ran = wk.ran; gl.wk_all = wk; gl.padded = padded_rows;
+        gl.abandon_nc = abandon_nc;
         if (fuse && fuse->agg && r.fuse_max) {
             gl.fuse = fuse;
             fuse->done = true;
         }
         // single-template chunks to score: the averaged template is the last of them, scored when Ttot counts it
-        const int n1 = t.class_count[3] - ((t.has_avg && Ttot == t.T) ? 1 : 0);
-        hipError_t e;
-#define RP_REGISTER(KK, WW) launch_dtw_register<KK, WW>(st, t, n1, mfcc, S, frame_pitch, first_win, n_win, score_ref, scores, avg, r.few, gl, padded_rows)
-        RP_REGISTER_DISPATCH(e, RP_REGISTER);
-#undef RP_REGISTER
-        return e;
+        return launch_dtw_register<false>(c, t.class_count[3] - ((t.has_avg && Ttot == t.T) ? 1 : 0), r.few, gl);
     }
-    const size_t tiles = (n_win + kDtwWin - 1) / kDtwWin, blocks = tiles * (size_t)Ttot * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    if (r.generic_lds > 160 * 1024) return hipErrorMemoryAllocation;  // reported as "template too long" by the callers' hip_ok text
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_generic_kernel), 160 * 1024); e != hipSuccess) return e;
-    dtw_mark(wk, kDtwRanGeneric);
-    hipLaunchKernelGGL(dtw_generic_kernel, dim3((unsigned)blocks), dim3(64), r.generic_lds, st, mfcc, frame_pitch, frame_pitch,
-                       (unsigned)tiles, first_win, n_win, n_win, t.lens, t.unit, t.Lpad, t.K, t.T, 0, Ttot,
-                       t.max_len, band, score_ref, scores, avg, static_cast<const float *>(nullptr), 0.f, wk.fix);
-    return hipGetLastError();
+    const hipError_t e = launch_dtw_generic(c, r, 0, Ttot, nullptr, 0.f);
+    if (e == hipSuccess) dtw_mark(c.wk, kDtwRanGeneric);
+    return e;
 }
 
 // The ungated call: the fast launches, then dtw_ref_kernel's pass over the windows they listed (a frame outside the norm range) -- or
 // over every window for a template set with such a row.
-static hipError_t launch_dtw(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, const DtwRoute &r, const float *mfcc, size_t S, size_t frame_pitch,
-                             size_t first_win, size_t n_win, int band, float score_ref, bool with_avg, float *scores, float *avg, bool padded_rows,
-                             float abandon_nc, DtwFusedAgg *fuse) {
+static hipError_t launch_dtw(const DtwCall &c, const DtwRoute &r, bool with_avg, float abandon_nc, DtwFusedAgg *fuse) {
+    const TemplatesDev &t = *c.t;
     if (fuse) fuse->done = false;
-    if (S == 0 || n_win == 0) return hipSuccess;
-    if (!wk.fix || !wk.sched) return hipErrorInvalidValue;
+    if (c.S == 0 || c.n_win == 0) return hipSuccess;
+    if (!c.wk.fix || !c.wk.sched) return hipErrorInvalidValue;
     if (t.n_chunks_total > kDtwSchedChunks) return hipErrorInvalidValue;
     const int Ttot = t.T + ((with_avg && t.has_avg) ? 1 : 0);
     if (r.single || !t.ref_only) {   // (dtw_single_kernel takes a ref-only set itself)
-        if (hipError_t e = launch_dtw_fast(st, wk, t, r, mfcc, S, frame_pitch, first_win, n_win, band, score_ref, Ttot, scores, avg, padded_rows,
-                                           abandon_nc, fuse); e != hipSuccess) return dtw_abort(st, wk, e);
+        if (hipError_t e = launch_dtw_fast(c, r, Ttot, abandon_nc, fuse); e != hipSuccess) return dtw_abort(c.st, c.wk, e);
         if (r.single) return hipSuccess;
     }
-    const hipError_t e = launch_dtw_ref(st, wk, t, mfcc, S, frame_pitch, first_win, n_win, n_win, band, score_ref, scores, avg, t.ref_only != 0, 0, Ttot,
-                                        (fuse && fuse->done) ? fuse : nullptr);
-    return e == hipSuccess ? e : dtw_abort(st, wk, e);
+    const hipError_t e = launch_dtw_ref(c, t.ref_only != 0, 0, Ttot, (fuse && fuse->done) ? fuse : nullptr);
+    return e == hipSuccess ? e : dtw_abort(c.st, c.wk, e);
 }
 
 // A handful of windows of ONE stream (the single-stream API), templates t_first .. t_first + t_count - 1 only (index T = the
@@ -1458,9 +1396,10 @@ hipError_t launch_dtw_single_part(hipStream_t st, const DtwWork &wk, const Templ
     if (n_win == 0 || t_count <= 0) return hipSuccess;
     const DtwRoute r = dtw_route(t, band, 1, n_win, false, true, score_ref);
     if (!r.single_fits || t_first + t_count > t.T + (t.has_avg ? 1 : 0)) return hipErrorNotSupported;
-    hipLaunchKernelGGL(dtw_single_kernel, dim3((unsigned)(n_win * t_count)), dim3(64), r.single_lds, st, mfcc, frame_pitch, first_win, (unsigned)n_win,
-                       out_win_pitch, t.lens, t.unit, t.Lpad, t.K, t.T, t_first, t_count, t.max_len, band, score_ref, scores, avg, t.raw, t.ref_only, wk.fix);
-    return hipGetLastError();
+    DtwCall c;
+    c.st = st; c.wk = wk; c.t = &t; c.mfcc = mfcc; c.S = 1; c.frame_pitch = frame_pitch; c.first_win = first_win; c.n_win = n_win;
+    c.out_win_pitch = out_win_pitch; c.band = band; c.score_ref = score_ref; c.scores = scores; c.avg = avg;
+    return launch_dtw_single(c, r.single_lds, t_first, t_count);
 }
 
 // -------------------------------------------------------------------- aggregate
@@ -1643,14 +1582,16 @@ bool dtw_score(Ctx &c, const DtwScore &q) {
     // kernel writes the aggregate (and the flags) itself and the aggregate pass is skipped
     DtwFusedAgg fz;
     if (q.fuse_max && q.score_mode == RP_SCORE_MAX && !q.with_avg && rows && q.agg) { fz.agg = q.agg; fz.hot = q.hot; fz.threshold = q.threshold; }
-    const DtwWork wk = (q.ragged && !gated) ? c.dtw_work_for(q.S, rows * (size_t)(t.rag_count > 1 ? t.rag_count : 1)) : c.dtw_work();
+    // (dtw_ragged_kernel's blocks are reserved for the ungated launch only)
+    DtwCall call;
+    call.st = c.stream;
+    call.wk = (q.ragged && !gated) ? c.dtw_work_for(q.S, rows * (size_t)(t.rag_count > 1 ? t.rag_count : 1)) : c.dtw_work();
+    call.t = &t; call.mfcc = q.mfcc; call.S = q.S; call.frame_pitch = q.frame_pitch; call.first_win = q.first_win; call.n_win = q.n_win;
+    call.out_win_pitch = q.n_win; call.band = q.band; call.score_ref = q.score_ref; call.scores = q.scores; call.avg = q.avg;
+    call.padded_rows = q.padded_rows;
     if (q.timed) c.time_begin(kKernelDtw);
-    bool ok = gated ? hip_ok(launch_dtw_gated(c.stream, wk, t, r, q.mfcc, q.S, q.frame_pitch, q.first_win, q.n_win, q.band, q.score_ref, q.avg_threshold,
-                                              q.scores, q.avg, list, abandon),
-                             r.gate == kGateRegister ? "dtw kernels (gated)" : "dtw_generic_kernel (gated)")
-                    : hip_ok(launch_dtw(c.stream, wk, t, r, q.mfcc, q.S, q.frame_pitch, q.first_win, q.n_win, q.band, q.score_ref, q.with_avg, q.scores,
-                                        q.avg, q.padded_rows, abandon, fz.agg ? &fz : nullptr),
-                             "dtw kernel");
+    bool ok = gated ? hip_ok(launch_dtw_gated(call, r, q.avg_threshold, list, abandon), r.gate == kGateRegister ? "dtw kernels (gated)" : "dtw_generic_kernel (gated)")
+                    : hip_ok(launch_dtw(call, r, q.with_avg, abandon, fz.agg ? &fz : nullptr), "dtw kernel");
     if (q.timed) c.time_end();
     if (!ok || !q.agg || fz.done) return ok;
     // the aggregate pass: 0 for the windows the gate rejected (their `scores` rows were never written) and, with `hot`, the flags

@@ -87,7 +87,7 @@ __host__ __device__ constexpr int mfma_last_use(int u, int g) {
 // (n_win >= 32).  GX = true: lanes read their window's frames from global memory (live-stream batches: a few windows per
 // stream; LIST mode of the averaged-template gate: list[] holds the rows that passed, *count of them).  list == nullptr with a
 // count: DENSE mode of the gate -- the launch does nothing unless *count >= dense_min; LIST mode does nothing when the list is
-// dense (rp_dtw.hip GateList).  abandon_nc < inf: early abandon of detect-only calls -- every 12 (16) columns a wave stops when the
+// dense (GateList, rp_kernels.h).  abandon_nc < inf: early abandon of detect-only calls -- every 12 (16) columns a wave stops when the
 // cheapest band cell of every (window, template) it holds is past abandon_nc * (m + n), writing score 0 (cell costs are >= 0 and
 // every warping path crosses every column, so that cell bounds the final cost from below; the averaged template never stops).
 // static_rounds: tiles a wave takes by its own index before it turns to the counter (mfma_static_rounds, rp_kernels.h).  agg_out != null:
@@ -514,19 +514,19 @@ bool dtw_mfma_supported(const TemplatesDev &t, int band, size_t n_win, bool from
     return dtw_mfma_lds_bytes(t.max_len, 8, p3 ? kDtwMfma3RowBytes : kDtwMfmaRowBytes) <= 160 * 1024;
 }
 
-hipError_t launch_dtw_mfma(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, int slots, int chunk_base, int n_chunks, const float *mfcc, size_t S,
-                           size_t frame_pitch, size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float *avg,
-                           bool from_global, const uint32_t *list, const uint32_t *count, uint32_t dense_min, float abandon_nc,
-                           const DtwFusedAgg *fuse) {
-    if (n_chunks <= 0 || S == 0 || n_win == 0) return hipSuccess;
+hipError_t launch_dtw_mfma(const DtwCall &c, int slots, int chunk_base, int n_chunks, bool from_global, const GateList &gate) {
+    const TemplatesDev &t = *c.t;
+    const DtwWork &wk = c.wk;
+    const DtwFusedAgg *fuse = gate.fuse;
+    if (n_chunks <= 0 || c.S == 0 || c.n_win == 0) return hipSuccess;
     const bool p3 = t.arith_mode() != kArithFastSplit;
     dtw_mark(wk, kDtwRanMfma | (p3 ? kDtwRanBf16x3 : kDtwRanF16x2));
-    if (fuse && (n_chunks != 1 || list || count)) return hipErrorInvalidValue;  // launch_dtw only asks for it with one chunk, every row scored
+    if (fuse && (n_chunks != 1 || gate.list || gate.count)) return hipErrorInvalidValue;  // launch_dtw only asks for it with one chunk, every row scored
     float *agg_out = fuse ? fuse->agg : nullptr;
     uint32_t *agg_hot = fuse ? fuse->hot : nullptr;
     const float agg_threshold = fuse ? fuse->threshold : 0.f;
-    if (list && !from_global) return hipErrorNotSupported;
-    const size_t total_tiles = (S * n_win + kMWin - 1) / kMWin;
+    if (gate.list && !from_global) return hipErrorNotSupported;
+    const size_t total_tiles = (c.S * c.n_win + kMWin - 1) / kMWin;
     const int row_bytes = p3 ? kDtwMfma3RowBytes : kDtwMfmaRowBytes;
     int nw = dtw_mfma_lds_bytes(t.max_len, 12, row_bytes) <= 160 * 1024 ? 12 : 8;
     if (p3 && slots == 8) {
@@ -542,14 +542,14 @@ hipError_t launch_dtw_mfma(hipStream_t st, const DtwWork &wk, const TemplatesDev
     const void *image = p3 ? t.aimg3 : t.aimg;
     if (!wk.sched || !wk.fix) return hipErrorInvalidValue;
     unsigned blocks, static_rounds;
-    if (hipError_t e = mfma_grid(total_tiles, n_chunks, nw, list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
+    if (hipError_t e = mfma_grid(total_tiles, n_chunks, nw, gate.list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
 #define RP_LAUNCH_MFMA_P(WW, NW, GXV, NT, PP)                                                                                       \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_kernel<WW, NW, GXV, NT, PP>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_kernel<WW, NW, GXV, NT, PP>), dim3(blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, frame_pitch, \
-                           total_tiles, (unsigned)n_chunks, chunk_base, first_win, n_win, out_win_pitch, t.chunks,                   \
-                           reinterpret_cast<const uint4 *>(image), t.T, score_ref, scores, avg, S, t.max_len, list, count, dense_min, \
-                           abandon_nc, wk.sched, static_rounds, agg_out, agg_hot, agg_threshold, wk.fix);                                            \
+        hipLaunchKernelGGL((dtw_mfma_kernel<WW, NW, GXV, NT, PP>), dim3(blocks), dim3(64 * NW), lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch, \
+                           total_tiles, (unsigned)n_chunks, chunk_base, c.first_win, c.n_win, c.out_win_pitch, t.chunks,             \
+                           reinterpret_cast<const uint4 *>(image), t.T, c.score_ref, c.scores, c.avg, c.S, t.max_len, gate.list, gate.count, \
+                           gate.dense_min, gate.abandon_nc, wk.sched, static_rounds, agg_out, agg_hot, agg_threshold, wk.fix);      \
     } while (0)
 #define RP_LAUNCH_MFMA(WW, NW, GXV, NT)                                                                                             \
     do {                                                                                                                            \
@@ -561,10 +561,10 @@ hipError_t launch_dtw_mfma(hipStream_t st, const DtwWork &wk, const TemplatesDev
         else { if (nw == 12) RP_LAUNCH_MFMA(WW, 12, false, NT); else RP_LAUNCH_MFMA(WW, 8, false, NT); }                            \
     } while (0)
     if (slots == 4) {
-        if (band != 5) return hipErrorNotSupported;
+        if (c.band != 5) return hipErrorNotSupported;
         RP_LAUNCH_MFMA_W(5, 4);
     } else {
-        switch (band) {
+        switch (c.band) {
         case 3: RP_LAUNCH_MFMA_W(3, 8); break;
         case 4: RP_LAUNCH_MFMA_W(4, 8); break;
         case 5: RP_LAUNCH_MFMA_W(5, 8); break;

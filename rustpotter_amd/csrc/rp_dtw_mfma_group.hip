@@ -319,12 +319,13 @@ bool dtw_mfma_group_supported(const TemplatesDev &t, int band, size_t n_win, siz
 }
 
 // Scores the chunk groups t.grp_* (rp_ctx.cpp: runs of 4 class-2 chunks of one length); the caller sends the other chunks to dtw_mfma_kernel.
-hipError_t launch_dtw_mfma_group(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch,
-                                 size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref, float *scores) {
-    if (t.grp_count <= 0 || S == 0 || n_win == 0) return hipSuccess;
+hipError_t launch_dtw_mfma_group(const DtwCall &c) {
+    const TemplatesDev &t = *c.t;
+    const DtwWork &wk = c.wk;
+    if (t.grp_count <= 0 || c.S == 0 || c.n_win == 0) return hipSuccess;
     if (!wk.fix) return hipErrorInvalidValue;
     dtw_mark(wk, kDtwRanMfmaGroup | kDtwRanF16x2);
-    const size_t total_tiles = (S * n_win + kGWin - 1) / kGWin;
+    const size_t total_tiles = (c.S * c.n_win + kGWin - 1) / kGWin;
     // every group is a run of FOUR chunks of one length (rp_ctx.cpp builds no other shape: see below)
     {
         const int sh = 4, first = 0, count = t.grp_count;
@@ -334,13 +335,13 @@ hipError_t launch_dtw_mfma_group(hipStream_t st, const DtwWork &wk, const Templa
 #define RP_LAUNCH_GROUP(WW, SHH)                                                                                                    \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_group_kernel<WW, SHH>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_group_kernel<WW, SHH>), dim3(blocks), dim3(64 * kGWaves), lds, st, mfcc, frame_pitch, frame_pitch, total_tiles, \
-                           (unsigned)count, t.grp_first + first, first_win, n_win, out_win_pitch, t.chunks, reinterpret_cast<const uint4 *>(t.aimg), t.T, \
-                           score_ref, scores, S, wk.fix);                                                                           \
+        hipLaunchKernelGGL((dtw_mfma_group_kernel<WW, SHH>), dim3(blocks), dim3(64 * kGWaves), lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch, total_tiles, \
+                           (unsigned)count, t.grp_first + first, c.first_win, c.n_win, c.out_win_pitch, t.chunks, reinterpret_cast<const uint4 *>(t.aimg), t.T, \
+                           c.score_ref, c.scores, c.S, wk.fix);                                                                           \
     } while (0)
         // (the two-chunk shape, SH = 2, compiles and passes the same tests; measured 3.32 against 2.95 ms for dtw_mfma_kernel at 8 192 streams x
         // 16 templates -- half the sharing does not pay for the ring and the lockstep -- so rp_ctx.cpp builds no pairs and it is not instantiated)
-        switch (band * 10 + sh) {
+        switch (c.band * 10 + sh) {
         case 34: RP_LAUNCH_GROUP(3, 4); break;
         case 44: RP_LAUNCH_GROUP(4, 4); break;
         case 54: RP_LAUNCH_GROUP(5, 4); break;

@@ -331,24 +331,24 @@ bool dtw_mfma_wide_supported(const TemplatesDev &t, int band, float score_ref) {
     return (size_t)(t.max_len + 16) * dtw_mfma_wide_row_bytes(t.K) <= 160 * 1024;
 }
 
-hipError_t launch_dtw_mfma_wide(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float *avg, const uint32_t *list,
-                                const uint32_t *count, uint32_t dense_min, float abandon_nc) {
+hipError_t launch_dtw_mfma_wide(const DtwCall &c, const GateList &gate) {
+    const TemplatesDev &t = *c.t;
+    const DtwWork &wk = c.wk;
     const int n_chunks = t.wide8_count;
-    if (n_chunks <= 0 || S == 0 || n_win == 0) return hipSuccess;
-    if (band != 5 || !wk.sched || !wk.fix) return hipErrorNotSupported;
+    if (n_chunks <= 0 || c.S == 0 || c.n_win == 0) return hipSuccess;
+    if (c.band != 5 || !wk.sched || !wk.fix) return hipErrorNotSupported;
     dtw_mark(wk, kDtwRanMfmaWide | kDtwRanF16x2);
-    const size_t total_tiles = (S * n_win + kWWin - 1) / kWWin;
+    const size_t total_tiles = (c.S * c.n_win + kWWin - 1) / kWWin;
     constexpr int NW = 8;
     const size_t lds = (size_t)(t.max_len + 16) * dtw_mfma_wide_row_bytes(t.K);
     unsigned blocks, static_rounds;
-    if (hipError_t e = mfma_grid(total_tiles, n_chunks, NW, list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
+    if (hipError_t e = mfma_grid(total_tiles, n_chunks, NW, gate.list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
 #define RP_LAUNCH_WIDE(KK)                                                                                                          \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_wide_kernel<KK, 5, NW>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_wide_kernel<KK, 5, NW>), dim3(blocks), dim3(64 * NW), lds, st, mfcc, frame_pitch, total_tiles, \
-                           (unsigned)n_chunks, t.wide8_first, first_win, n_win, out_win_pitch, t.chunks, reinterpret_cast<const uint4 *>(t.aimg), \
-                           t.T, score_ref, scores, avg, S, list, count, dense_min, abandon_nc, wk.sched, static_rounds, wk.fix);         \
+        hipLaunchKernelGGL((dtw_mfma_wide_kernel<KK, 5, NW>), dim3(blocks), dim3(64 * NW), lds, c.st, c.mfcc, c.frame_pitch, total_tiles, \
+                           (unsigned)n_chunks, t.wide8_first, c.first_win, c.n_win, c.out_win_pitch, t.chunks, reinterpret_cast<const uint4 *>(t.aimg), \
+                           t.T, c.score_ref, c.scores, c.avg, c.S, gate.list, gate.count, gate.dense_min, gate.abandon_nc, wk.sched, static_rounds, wk.fix);         \
     } while (0)
     if (t.K == 16) RP_LAUNCH_WIDE(16);
     else RP_LAUNCH_WIDE(13);

@@ -408,8 +408,10 @@ bool dtw_ragged_supported(const TemplatesDev &t, int band, size_t n_win, float s
     return dtw_ragged_lds_bytes(t, n_win, nullptr) <= 160 * 1024;   // (two workgroups per CU up to 80 KB: BASELINE-sized calls)
 }
 
-hipError_t launch_dtw_ragged(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch,
-                             size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float abandon_nc, bool list_rows) {
+hipError_t launch_dtw_ragged(const DtwCall &c, float abandon_nc, bool list_rows) {
+    const TemplatesDev &t = *c.t;
+    const DtwWork &wk = c.wk;
+    const size_t S = c.S, n_win = c.n_win;
     if (t.rag_count <= 0 || S == 0 || n_win == 0) return hipSuccess;
     if (!wk.fix || !wk.rag_prep || wk.rag_streams < S) return hipErrorInvalidValue;
     if (list_rows && (!wk.rag_list || wk.rag_rows < S * n_win * (size_t)t.rag_count || S * n_win > 0xffffffffULL)) return hipErrorInvalidValue;
@@ -423,19 +425,19 @@ hipError_t launch_dtw_ragged(hipStream_t st, const DtwWork &wk, const TemplatesD
     const size_t blocks = groups * (size_t)t.rag_count;
     uint32_t *rows_list = list_rows ? wk.rag_list : nullptr;
     if (rows_list)
-        if (hipError_t e = hipMemsetAsync(rows_list, 0, sizeof(uint32_t), st); e != hipSuccess) return e;
+        if (hipError_t e = hipMemsetAsync(rows_list, 0, sizeof(uint32_t), c.st); e != hipSuccess) return e;
     const size_t n_frames = n_win + (size_t)t.max_len - 1;   // frames of a stream the call scores
-    hipLaunchKernelGGL(ragged_prep_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, mfcc, frame_pitch, S, first_win,
-                       first_win + n_frames <= frame_pitch ? n_frames : frame_pitch - first_win, wk.rag_prep);
+    hipLaunchKernelGGL(ragged_prep_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, c.st, c.mfcc, c.frame_pitch, S, c.first_win,
+                       c.first_win + n_frames <= c.frame_pitch ? n_frames : c.frame_pitch - c.first_win, wk.rag_prep);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
 #define RP_LAUNCH_RAGGED(WW)                                                                                                        \
     do {                                                                                                                            \
         if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_ragged_kernel<WW>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_ragged_kernel<WW>), dim3((unsigned)blocks), dim3(64 * kDtwRaggedWaves), lds, st, mfcc, frame_pitch, S, first_win, \
-                           n_win, out_win_pitch, t.chunks, t.rag_first, (unsigned)t.rag_count, t.lens, t.rag_off, reinterpret_cast<const uint4 *>(t.rimg), \
-                           t.unit, t.Lpad, t.T, score_ref, scores, t.max_len, F, t.rag_a_cap, abandon_nc, wk.rag_prep, rows_list, wk.fix); \
+        hipLaunchKernelGGL((dtw_ragged_kernel<WW>), dim3((unsigned)blocks), dim3(64 * kDtwRaggedWaves), lds, c.st, c.mfcc, c.frame_pitch, S, c.first_win, \
+                           n_win, c.out_win_pitch, t.chunks, t.rag_first, (unsigned)t.rag_count, t.lens, t.rag_off, reinterpret_cast<const uint4 *>(t.rimg), \
+                           t.unit, t.Lpad, t.T, c.score_ref, c.scores, t.max_len, F, t.rag_a_cap, abandon_nc, wk.rag_prep, rows_list, wk.fix); \
     } while (0)
-    switch (band) {
+    switch (c.band) {
     case 3: RP_LAUNCH_RAGGED(3); break;
     case 4: RP_LAUNCH_RAGGED(4); break;
     case 5: RP_LAUNCH_RAGGED(5); break;

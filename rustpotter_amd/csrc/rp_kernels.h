@@ -246,24 +246,6 @@ inline void dtw_mark(const DtwWork &wk, uint32_t bit) { if (wk.ran) *wk.ran |= b
 __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { return reinterpret_cast<unsigned long long *>(fix + 2 + 2 * (size_t)kDtwFixCap); }
 // (dtw_fix_append, the kernels' side of the list: rp_device.h)
 
-// The matrix-core DTW kernel (rp_dtw_mfma.hip) for the chunks of class 2 (5..8 templates; slots = 8, band 3..5) and class 1 (3..4
-// templates; slots = 4, band 5) at mfcc_size 5.  from_global: lanes read their frames from global memory (live-stream batches, LIST mode
-// of the averaged-template gate) instead of an LDS stage (needs n_win >= 32).  list / count / dense_min / abandon_nc: as GateList in
-// rp_dtw.hip.
-// score_ref: the relative error of a score is (1 - score) x d(cost / (m + n)) / score_ref; the split products keep it within the parity
-// gate (1e-5) down to kDtwMfmaMinScoreRef (tools/probe_score_ref.py, tests/test_gpu_round4.py); below, the f32 register kernels score
-constexpr float kDtwMfmaMinScoreRef = 0.05f;
-bool dtw_mfma_supported(const TemplatesDev &t, int band, size_t n_win, bool from_global, int slots, float score_ref);
-// mfcc_size 13 / 16 at band 5: frames always from global memory (the caller's rows end with slack: DtwScore::padded_rows)
-bool dtw_mfma_wide_supported(const TemplatesDev &t, int band, float score_ref);
-hipError_t launch_dtw_mfma_wide(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float *avg, const uint32_t *list,
-                                const uint32_t *count, uint32_t dense_min, float abandon_nc);
-// the same shapes in the default arithmetic (three bf16 parts per operand, no score_ref floor): chunks of up to four templates
-bool dtw_mfma_wide3_supported(const TemplatesDev &t, int band);
-hipError_t launch_dtw_mfma_wide3(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch, size_t first_win,
-                                 size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float *avg, const uint32_t *list,
-                                 const uint32_t *count, uint32_t dense_min, float abandon_nc);
 // ScoreMode::Max folded into the matrix-core DTW kernel when ONE chunk holds every sample template of the reference and no averaged
 // template is scored in the call (BASELINE C2 / C3, a live-stream call with same-length templates): the lane pair of a window holds all
 // its scores, so the kernel also writes agg[row] = max_t score and raises the stream's `hot` flag like agg_store (rp_dtw.hip) -- the
@@ -274,14 +256,63 @@ struct DtwFusedAgg {
     float threshold = 0.f;
     bool done = false;
 };
+
+// The gate / abandon mode of ONE launch: the averaged-template gate's hand-over to the template kernels (launch_dtw_gated).  count ==
+// nullptr: no gate, every window is scored.  list != nullptr: LIST mode -- the lanes take the listed rows (windows that passed) and read
+// their frames from global memory; the launch does nothing when the list is dense (*count >= dense_min).  list == nullptr with a count:
+// DENSE mode -- the ordinary LDS-staged launch over every window, which does nothing unless the list is dense.  (Nearly everything
+// passing is the common case at the reference's default threshold; scoring all rows through the staged kernel is then ~6 % cheaper than
+// gathering them one by one.  Both launches are always issued; one of them exits on a scalar compare.)
+// The register kernels of rp_dtw.hip take it by value: the fields keep their offsets.
+struct GateList {
+    const uint32_t *list = nullptr, *count = nullptr;
+    uint32_t dense_min = 0;
+    // entries the list may hold per row of the call (1: the gate lists a row once; dtw_ragged_kernel's list holds a window once per ragged
+    // chunk that could not resolve it): the list-mode grids cover S x n_win x list_mult entries
+    uint32_t list_mult = 1;
+    // Early abandon (detect-only calls in ScoreMode::Max): a DTW whose cheapest band cell already costs more than
+    // abandon_nc * (m + n) cannot end with a score above the detection threshold (cell costs are >= 0 and every warping
+    // path crosses every row), so a wave whose 64 windows x templates are ALL past that bound stops and reports score 0 for
+    // them.  Windows that can still fire are never touched: their wave runs to the end, with every template exact.
+    // +inf: off (the per-window score arrays are part of the call's result).  See dtw_abandon_nc().
+    float abandon_nc = __builtin_inff();
+    const DtwFusedAgg *fuse = nullptr;  // ScoreMode::Max folded into the matrix-core kernel; set by launch_dtw_fast only
+    // DtwWork::fix for the register kernels: windows with a frame whose squared norm leaves kDtwNormLo..kDtwFixLimit are listed for
+    // dtw_ref_kernel (the reference's sqrt(dot_a * dot_b) is not scale invariant there, comparator.rs:42-47); their launchers set it
+    uint32_t *fix = nullptr;
+};
+
+// What is fixed for one scoring call: dtw_score builds it once and every launcher below it takes it, plus what varies per launch (chunk
+// range, template slots, from_global, the GateList).  mfcc rows have frame_pitch frames per stream, scores / avg rows out_win_pitch windows.
+struct DtwCall {
+    hipStream_t st = nullptr;
+    DtwWork wk;
+    const TemplatesDev *t = nullptr;
+    const float *mfcc = nullptr;
+    size_t S = 0, frame_pitch = 0, first_win = 0, n_win = 0, out_win_pitch = 0;
+    int band = 0;
+    float score_ref = 0.f;
+    float *scores = nullptr, *avg = nullptr;
+    bool padded_rows = false;   // the frame array ends with slack (DtwScore::padded_rows)
+};
+
+// The matrix-core DTW kernel (rp_dtw_mfma.hip) for the chunks of class 2 (5..8 templates; slots = 8, band 3..5) and class 1 (3..4
+// templates; slots = 4, band 5) at mfcc_size 5.  from_global: lanes read their frames from global memory (live-stream batches, LIST mode
+// of the averaged-template gate) instead of an LDS stage (needs n_win >= 32).
+// score_ref: the relative error of a score is (1 - score) x d(cost / (m + n)) / score_ref; the split products keep it within the parity
+// gate (1e-5) down to kDtwMfmaMinScoreRef (tools/probe_score_ref.py, tests/test_gpu_round4.py); below, the f32 register kernels score
+constexpr float kDtwMfmaMinScoreRef = 0.05f;
+bool dtw_mfma_supported(const TemplatesDev &t, int band, size_t n_win, bool from_global, int slots, float score_ref);
+hipError_t launch_dtw_mfma(const DtwCall &c, int slots, int chunk_base, int n_chunks, bool from_global, const GateList &gate);
+// mfcc_size 13 / 16 at band 5: frames always from global memory (the caller's rows end with slack: DtwScore::padded_rows)
+bool dtw_mfma_wide_supported(const TemplatesDev &t, int band, float score_ref);
+hipError_t launch_dtw_mfma_wide(const DtwCall &c, const GateList &gate);
+// the same shapes in the default arithmetic (three bf16 parts per operand, no score_ref floor): chunks of up to four templates
+bool dtw_mfma_wide3_supported(const TemplatesDev &t, int band);
+hipError_t launch_dtw_mfma_wide3(const DtwCall &c, const GateList &gate);
 size_t dtw_mfma_group_lds_bytes(int L, int sh);
 bool dtw_mfma_group_supported(const TemplatesDev &t, int band, size_t n_win, size_t S, float score_ref);
-hipError_t launch_dtw_mfma_group(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch,
-                                 size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref, float *scores);
-hipError_t launch_dtw_mfma(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, int slots, int chunk_base, int n_chunks, const float *mfcc, size_t S,
-                           size_t frame_pitch, size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float *avg,
-                           bool from_global, const uint32_t *list, const uint32_t *count, uint32_t dense_min, float abandon_nc,
-                           const DtwFusedAgg *fuse = nullptr);
+hipError_t launch_dtw_mfma_group(const DtwCall &c);
 
 // The matrix-core DTW kernel for templates of unequal length (rp_dtw_ragged.hip): the ragged chunks of `t` over every window of the call
 // (LDS-staged tiles of 512 windows: needs n_win >= 64; live-stream batches and the gate's list keep the register kernels).
@@ -293,8 +324,7 @@ bool dtw_ragged_supported(const TemplatesDev &t, int band, size_t n_win, float s
 size_t dtw_ragged_lds_bytes(const TemplatesDev &t, size_t n_win, int *frames_cap);
 // list_rows: windows the kernel cannot score within the parity gate go to wk.rag_list (the caller runs the register kernels' list mode on it);
 // else to wk.fix (dtw_ref_kernel)
-hipError_t launch_dtw_ragged(hipStream_t st, const DtwWork &wk, const TemplatesDev &t, int band, const float *mfcc, size_t S, size_t frame_pitch,
-                             size_t first_win, size_t n_win, size_t out_win_pitch, float score_ref, float *scores, float abandon_nc, bool list_rows);
+hipError_t launch_dtw_ragged(const DtwCall &c, float abandon_nc, bool list_rows);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a process that drives several GPUs
 // (one rp_ctx per device) has to set it on each of them.  Sets it once per (current device, kernel), thread-safe.
@@ -360,7 +390,7 @@ struct DtwScore {
     float score_ref = 0.f;
     bool with_avg = false;   // score the averaged template (-> avg); the set has one
     // no per-window score array is part of the call's result: the gate may leave rows unscored (wakeword_comp.rs:85-93) and, in
-    // ScoreMode::Max, DTWs that can no longer reach `threshold` may stop with score 0 (GateList::abandon_nc in rp_dtw.hip).  Every window
+    // ScoreMode::Max, DTWs that can no longer reach `threshold` may stop with score 0 (GateList::abandon_nc).  Every window
     // that can fire keeps exact scores, so the detections do not change.
     bool detect_only = false;
     float avg_threshold = 0.f, threshold = 0.f;
