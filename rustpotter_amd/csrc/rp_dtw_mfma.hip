@@ -17,10 +17,10 @@
 //     x0 a0, x1 a0, x0 a1 for the five components (15) and 1.0 x 1.0, accumulated in f32 on C = 0: the instruction leaves
 //     1 - a.x with an error below 2^-20 (measured against the f32 CPU restatement: scores within 1e-6; the parity gate is 1e-5).
 //     Lane (n, h) centres, scales and splits only components (0, 1) or (3, 4) and component 2; the two partial squared norms
-//     meet through v_permlane32_swap.
+//     meet through v_permlane32_swap.  (The three-part form builds a WHOLE frame per lane every two columns instead: RP_W_*, below.)
 //   * Software pipeline per column c: the A tile of column c+1 is re-read, the cells of column c run (two independent chains of
 //     v_min3_f32 x2 + add x2 per cell), each tile's MFMA for column c+1 is issued right after the last cell that reads the tile, and
-//     the frame of column c+2 is prepared in ten pieces between the cells.  Columns are unrolled 12 at a time so that every
+//     the frame of column c+2 is prepared in ten pieces between the cells (three-part form: the frames of a column PAIR, nine pieces over two columns).  Columns are unrolled 12 at a time so that every
 //     slot, tile and band index is a compile-time register.
 //   * Two arithmetics (P3, round 6; chosen by the context, rp_ctx_set_arithmetic).  P3 = true, the default (RP_ARITH_F32_MATRIX): f32-GRADE products.
 //     Both operands are split into THREE bf16 parts, exactly (x0 = x & 0xffff0000, r = x - x0, x1 = r & 0xffff0000, x2 = r - x1: 3 x 8 significant
@@ -29,7 +29,7 @@
 //     after the first).  What is dropped (x1 a2 + x2 a1 + x2 a2) is below 2^-22 of a product, 2^-25.7 rms -- an f32 multiply rounds by up to
 //     2^-24; tests/test_gpu_dtw_f64.py holds the scores to the strict-f32 oracle's own distance from an f64 evaluation.  The window side's two
 //     operands are one run of six registers (the middle two shared), the A image is 512 bytes per template row (append_mfma_image3,
-//     rp_ctx.cpp); 219 registers = two waves per SIMD, eight per workgroup (a twelve-wave build exists: RP_MFMA3_WAVES=12, see the launcher).  P3 = false (RP_ARITH_FAST_SPLIT, opt-in): the two-part f16 form
+//     rp_ctx.cpp); 221 registers = two waves per SIMD, eight per workgroup (a twelve-wave build exists: RP_MFMA3_WAVES=12, see the launcher).  P3 = false (RP_ARITH_FAST_SPLIT, opt-in): the two-part f16 form
 //     described above, 22-bit products.
 //   * Two shapes (NT): eight template slots as described (chunks of 5..8 templates, band 3..5), or four (chunks of 3..4, band 5): a
 //     tile is then 8 row slots x 4 templates, 16 circular row slots = 2 tiles, one template pair per lane, columns unrolled 16 at a time, twelve
@@ -79,6 +79,14 @@ __host__ __device__ constexpr int mfma_last_use(int u, int g) {
         if (((u + q + mfma_slots(NT) - W + 2) % mfma_slots(NT)) / (32 / NT) == g) last = q;
     return last;
 }
+
+// Which instantiations build the window operand one whole frame per lane and column pair (RP_W_*, in the kernel): the builds of the three-part
+// form but one.  Its cost is a few registers -- 221 against 219 in the headline build; in the 168-register twelve-wave builds 58 spilled values
+// against 49 (eight slots, opt-in) and 16 against 11 (four slots), inside the bounds of tests/test_kernel_resources.py and faster all the same
+//  -- except in the twelve-wave eight-slot build that reads its frames from global memory (RP_MFMA3_WAVES=12 in a live-stream
+// call), where the pair ring of ten registers turns 60 spilled values into 204: that one keeps the per-column build (RP_P*), as does the
+// two-part form, whose split is two conversions per component pair and not what this saves on.
+constexpr bool mfma_whole_frame(int nw, bool gx, int nt, bool p3) { return p3 && !(gx && nw == 12 && nt == 8); }
 
 }  // namespace
 
@@ -131,6 +139,10 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
     constexpr int PD = GX ? RP_MFMA_GX_PD : 1;
 #endif
     static_assert(NS % PD == 0, "the frame ring's slot must be a compile-time index");
+    // WF: the window operand is built one WHOLE frame per lane and column pair (RP_W_*, below); false: every lane builds its half of every column (RP_P*)
+    constexpr bool WF = mfma_whole_frame(NW, GX, NT, P3);
+    constexpr int PP = GX ? 2 : 1;  // WF: pairs a frame pair is requested ahead of its use
+    static_assert(NS % (2 * PP) == 0, "the pair ring's slot must be a compile-time index");
     static_assert(NT == 8 || NT == 4, "template slots per chunk");
     static_assert(B + 2 <= NS, "the band and its two neighbours must fit the circular row slots");
     size_t total_entries = n_streams * n_win;
@@ -197,7 +209,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             if (list) f = list[valid ? f : total_entries - 1];  // row ids s * n_win + w of the windows that passed the gate
             s = valid ? f / n_win : 0;
             w = valid ? (int)(f - s * n_win) : 0;
-            xw = mfcc + (s * frame_pitch + first_win + (size_t)w) * K;  // the caller leaves W * K floats of slack after the last frame
+            xw = mfcc + (s * frame_pitch + first_win + (size_t)w) * K;  // columns up to L + 8 are read ahead: the caller's frame array ends with 64 frames of slack
         } else {
             // stage the frames of up to two stream segments (columns L + 1 .. L + 3 are read ahead, never used)
             const size_t sA = f0 / n_win;
@@ -243,6 +255,18 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 #pragma unroll kMeanUnroll
         for (int i = 0; i < L; ++i) { mua += xa[i * K]; mub += xa[i * K + 1]; mu2 += x2[i * K]; }
         mua = mua / (float)L; mub = mub / (float)L; mu2 = mu2 / (float)L;
+        // WF: the lane centres all five components; the two means it did not sum come from the other half (same sums, same order, same bits)
+        float mu_[K] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        (void)mu_;
+        if (WF) {
+            const auto sa_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(mua), __float_as_uint(mua), false, false);
+            const auto sb_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(mub), __float_as_uint(mub), false, false);
+            mu_[0] = __uint_as_float(sa_[0]); mu_[3] = __uint_as_float(sa_[1]);
+            mu_[1] = __uint_as_float(sb_[0]); mu_[4] = __uint_as_float(sb_[1]);
+            mu_[2] = mu2;
+        }
+        const float *xh = xw + h * K;  // WF: half h holds the second column of a pair
+        (void)xh;
         if (round == 1) RP_TRACE(2);
 
         // Q[p][q] = D[(c - 1) - W + 1 + q][c - 1] of the template pair p (band position, as P[] of dtw_band_kernel with rows and
@@ -311,6 +335,53 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 // (x0, x1) of component 2 against (a1, a1) in half 0, the constant (1.0, 0) in half 1
 #define RP_P10(cc, par) if (P3) { bv[par][4] = bv[par][2]; bv[par][5] = h ? 0x00003f80u : bv[par][1]; }
 #define RP_PREP_ALL(cc, par) RP_P0(cc, (cc) % PD) RP_P1(cc, (cc) % PD) RP_P2(cc) RP_P3(cc) RP_P4(cc) RP_P5(cc) RP_P6(cc, par) RP_P7(cc, par) RP_P8(cc) RP_P9(cc, par) RP_P10(cc, par)
+// WF (mfma_whole_frame): 32 frames per column over 64 lanes are one whole frame per lane every two columns.  Lane (n, h) builds the frame of
+// window n for column cc + h of the pair (cc, cc + 1), cc odd: all five components centred, ONE norm, guard, v_rsq and range test, one split
+// without per-half masks.  It packs both k-halves' runs of its column -- lo_[0..3] what half 0 supplies (components 0, 1 and (x0, x1) of
+// component 2), up_[0..3] what half 1 supplies (components 3, 4 and (x2, x0) of component 2), slot for slot what RP_P6..RP_P9 put there -- and
+// one v_permlane32_swap per register hands half 0's upper run of column cc to half 1 and half 1's lower run of column cc + 1 to half 0:
+// every lane then holds its own k-half of both columns (bv[1] the odd column, bv[0] the even one).  Registers 4 and 5 of a run are copies:
+// filled after the swap.  bb_ is the same operations in the same order as own_ / swap / bb_ of RP_P2..RP_P3: every value is bit-identical.
+// The pieces of pair (c + 3, c + 4) start in the even column c (phase u odd) right after the swap of pair (c + 1, c + 2) -- whose two runs
+// are free only then: column c + 1's run is read to the end of column c - 1, column c + 2's to the end of column c -- and end in column
+// c + 1.  Frames up to column L + 4 are read (L even; L + 3 for odd L): the stage holds L + 3 frames past a segment's windows, i.e. columns up
+// to L + 4 of its last window.
+// The frame ring g_[PP]: the pair (cc, cc + 1) sits in slot rs = ((cc - 1) / 2) mod PP, spelled out by the caller (c0 - 1 is a multiple of NS and
+// 2 PP divides NS: a compile-time register).  LDS-staged tiles request a pair two band cells before they centre it; frames from global memory (GX) two pairs = four columns
+// before, right after the slot's last pair is centred (the per-column build looks three or four columns ahead: RP_P0).  GX reads frames up to
+// column L + 8 of a window; the frame array of a GX call ends with 64 frames of slack (DtwScore::padded_rows).
+#define RP_W_LOAD(cc, rs) g_[rs][0] = xh[((cc) - 1) * K]; g_[rs][1] = xh[((cc) - 1) * K + 1]; g_[rs][2] = xh[((cc) - 1) * K + 2];                 \
+                          g_[rs][3] = xh[((cc) - 1) * K + 3]; g_[rs][4] = xh[((cc) - 1) * K + 4];
+#define RP_W_NEAR(cc, rs) if (!GX) { RP_W_LOAD(cc, rs) }
+#define RP_W_CENTRE(cc, rs) d_[0] = g_[rs][0] - mu_[0]; d_[1] = g_[rs][1] - mu_[1]; d_[2] = g_[rs][2] - mu_[2]; d_[3] = g_[rs][3] - mu_[3];         \
+                            d_[4] = g_[rs][4] - mu_[4]; if (GX) { RP_W_LOAD((cc) + 2 * PP, rs) }
+#define RP_W_NORM() bb_ = fmaf(d_[2], d_[2], fmaf(d_[0], d_[0], d_[1] * d_[1]) + fmaf(d_[3], d_[3], d_[4] * d_[4]));
+#define RP_W_SCALE() w_[0] = d_[0] * inv_; w_[1] = d_[1] * inv_; w_[2] = d_[2] * inv_; w_[3] = d_[3] * inv_; w_[4] = d_[4] * inv_;
+#ifndef RP_AB_NO_RANGE_TEST
+#define RP_W_CHK(in_window) if (in_window) chk_ = fmaxf(fmaxf(chk_, inv_), bb_);
+#else
+#define RP_W_CHK(in_window)
+#endif
+#define RP_W_X0() x0_[0] = RP_AND(w_[0], 0xffff0000u); x0_[1] = RP_AND(w_[1], 0xffff0000u); x0_[2] = RP_AND(w_[2], 0xffff0000u);         \
+                  x0_[3] = RP_AND(w_[3], 0xffff0000u); x0_[4] = RP_AND(w_[4], 0xffff0000u);                                              \
+                  lo_[2] = RP_HI2(w_[1], w_[0]); up_[2] = RP_HI2(w_[4], w_[3]);
+#define RP_W_R1() r_[0] = w_[0] - x0_[0]; r_[1] = w_[1] - x0_[1]; r_[2] = w_[2] - x0_[2]; r_[3] = w_[3] - x0_[3]; r_[4] = w_[4] - x0_[4]; \
+                  lo_[3] = RP_HI2(r_[1], r_[0]); up_[3] = RP_HI2(r_[4], r_[3]); lo_[1] = RP_HI2(r_[2], w_[2]);
+#define RP_W_X1() y_[0] = RP_AND(r_[0], 0xffff0000u); y_[1] = RP_AND(r_[1], 0xffff0000u); y_[2] = RP_AND(r_[2], 0xffff0000u);            \
+                  y_[3] = RP_AND(r_[3], 0xffff0000u); y_[4] = RP_AND(r_[4], 0xffff0000u);
+#define RP_W_X2() lo_[0] = RP_HI2(r_[1] - y_[1], r_[0] - y_[0]); up_[0] = RP_HI2(r_[4] - y_[4], r_[3] - y_[3]);                          \
+                  up_[1] = __builtin_amdgcn_perm(__float_as_uint(r_[2] - y_[2]), __float_as_uint(w_[2]), 0x03020706u);
+#define RP_W_SWAP()                                                                                                           \
+    {                                                                                                                         \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                       \
+            const auto sw_ = __builtin_amdgcn_permlane32_swap(lo_[i], up_[i], false, false);                                  \
+            bv[1][i] = sw_[0]; bv[0][i] = sw_[1];                                                                             \
+        }                                                                                                                     \
+        bv[1][4] = bv[1][2]; bv[1][5] = h ? 0x00003f80u : bv[1][1];                                                           \
+        bv[0][4] = bv[0][2]; bv[0][5] = h ? 0x00003f80u : bv[0][1];                                                           \
+    }
+#define RP_W_FIRST(cc, rs) RP_W_NEAR(cc, rs) RP_W_CENTRE(cc, rs) RP_W_NORM() RP_P4(cc) RP_W_SCALE()
+#define RP_W_SECOND(in_window) RP_W_CHK(in_window) RP_W_X0() RP_W_R1() RP_W_X1() RP_W_X2()
 // the A tile that receives template row cc + W (cc = 1 + uu mod 12)
 #define RP_AREF(cc, uu, GUARD)                                                                                                \
     {                                                                                                                         \
@@ -338,7 +409,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 #define RP_P3_GAP 1
 #endif
 // column c (c = 1 + u mod 12): rows r_q = c - W + 1 + q, q = 0..2W-1, sit in MFMA row slot (u + q + 14 - W) mod 12
-#define RP_STEP(GUARD)                                                                                                        \
+#define RP_STEP(GUARD, TAIL)                                                                                                      \
     do {                                                                                                                      \
         RP_AREF(c + 1, (u + 1) % NS, GUARD)                                                                                   \
         v2f up[2] = {(v2f){RP_INF, RP_INF}, (v2f){RP_INF, RP_INF}};                                                           \
@@ -356,7 +427,15 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             }                                                                                                                 \
             /* piece k of the frame of column c + 2 after cell (k B) / 10 (its values were requested one column earlier, P0): the  \
                pieces fill the wait states between a cell's adds and the next cell's v_min3 */                                                                                  \
-            if (!P3) {                                                                                                        \
+            if (WF) { /* nine pieces over the two columns of a pair, from the swap at the head of the even column (u odd) */  \
+            const int gi = (u & 1) ? q : B + q;                                                                              \
+            if (gi == 0) { RP_W_SWAP() RP_W_NEAR(c + 3, ((u + 3) / 2) % PP) }                                                 \
+            if (gi == (1 * 2 * B) / 9) { RP_W_CENTRE(c + 3, ((u + 3) / 2) % PP) }                                             \
+            if (gi == (2 * 2 * B) / 9) { RP_W_NORM() } if (gi == (3 * 2 * B) / 9) { RP_P4(c + 3) } if (gi == (4 * 2 * B) / 9) { RP_W_SCALE() } \
+            /* from here on u is even: the pair is (c + 2, c + 3); the range test covers columns 1 .. L + 2, as the per-column build's */ \
+            if (gi == (5 * 2 * B) / 9) { RP_W_CHK(!(TAIL) || c + h <= L) RP_W_X0() } if (gi == (6 * 2 * B) / 9) { RP_W_R1() }  \
+            if (gi == (7 * 2 * B) / 9) { RP_W_X1() } if (gi == (8 * 2 * B) / 9) { RP_W_X2() }                                 \
+            } else if (!P3) {                                                                                                 \
             if (q == (0 * B) / 10) { RP_P1(c + 2, (u + 3) % PD) RP_P0(c + 2 + PD, (u + 3) % PD) } if (q == (2 * B) / 10) { RP_P2(c + 2) }                       \
             if (q == (3 * B) / 10) { RP_P3(c + 2) } if (q == (4 * B) / 10) { RP_P4(c + 2) } if (q == (5 * B) / 10) { RP_P5(c + 2) } \
             if (q == (6 * B) / 10) { RP_P6(c + 2, (u + 1) & 1) } if (q == (7 * B) / 10) { RP_P7(c + 2, (u + 1) & 1) }         \
@@ -383,21 +462,31 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
         float fa_[PD], fb_[PD], f2_[PD], da_, db_, d2_, own_, bb_, inv_, ua_, ub_, u2_, chk_ = 0.f;
         float x0a_ = 0.f, x0b_ = 0.f, x0c_ = 0.f, r1a_ = 0.f, r1b_ = 0.f, r1c_ = 0.f, x1a_ = 0.f, x1b_ = 0.f, tc_ = 0.f;   // P3 only
         (void)x0a_; (void)x0b_; (void)x0c_; (void)r1a_; (void)r1b_; (void)r1c_; (void)x1a_; (void)x1b_; (void)tc_;
+        float g_[PP][K], d_[K], w_[K], x0_[K], r_[K], y_[K];   // WF only: the lane's frames (ring), one centred, scaled, and the parts of its split
+        unsigned lo_[4], up_[4];                           // WF only: its column's two k-half runs before the swap
+        (void)g_; (void)d_; (void)w_; (void)x0_; (void)r_; (void)y_; (void)lo_; (void)up_; (void)da_; (void)db_; (void)d2_; (void)own_; (void)ua_; (void)ub_; (void)u2_;
         RP_AREF(1, 0, true)
-        RP_PREP_ALL(1, 1)
+        if (WF) {   // columns 1 and 2
+            if (GX) { RP_W_LOAD(1, 0) RP_W_LOAD(3, 1 % PP) }
+            RP_W_FIRST(1, 0) RP_W_SECOND(true) RP_W_SWAP()
+        }
+        else { RP_PREP_ALL(1, 1) }
         RP_MFMA(0, 1); RP_MFMA(1, 1);
         if (NTILE > 2) RP_MFMA(NTILE - 1, 1);
         RP_MFMA2(0, 1); RP_MFMA2(1, 1);
         if (NTILE > 2) RP_MFMA2(NTILE - 1, 1);
-        RP_PREP_ALL(2, 0)
+        if (WF) { RP_W_FIRST(3, 1 % PP) }   // what column 0 (u = -1) would have done for the pair (3, 4)
+        else {
+            RP_PREP_ALL(2, 0)
 #pragma unroll
-        for (int a = 0; a < PD; ++a) { RP_P0(3 + a, (3 + a) % PD) }
+            for (int a = 0; a < PD; ++a) { RP_P0(3 + a, (3 + a) % PD) }
+        }
         __builtin_amdgcn_sched_barrier(0);
         int c0 = 1;
         bool dead = false;
         {   // first block: cells of rows < 1 stay +inf (L >= NS)
 #pragma unroll
-            for (int u = 0; u < NS; ++u) { const int c = c0 + u; RP_STEP(true); }
+            for (int u = 0; u < NS; ++u) { const int c = c0 + u; RP_STEP(true, false); }
         }
 // early abandon: wave-uniform, once per 12 columns.  (RP_MFMA_PRICE_NO_ABANDON: tools/isa_mix.py prices the hot loop as the headline call
 // runs it -- abandon_nc = +inf jumps over this block with one scalar branch -- by compiling the block out; never defined in the product.)
@@ -421,7 +510,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             RP_ABANDON_CHECK()
             if (dead) break;
 #pragma unroll
-            for (int u = 0; u < NS; ++u) { const int c = c0 + u; RP_STEP(false); }
+            for (int u = 0; u < NS; ++u) { const int c = c0 + u; RP_STEP(false, false); }
         }
         if (!dead && c0 <= L) {
             RP_ABANDON_CHECK()
@@ -429,7 +518,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 #pragma unroll
                 for (int u = 0; u < NS - 1; ++u) {  // the last L mod 12 columns
                     const int c = c0 + u;
-                    if (c <= L) RP_STEP(false);
+                    if (c <= L) RP_STEP(false, true);
                 }
             }
         }
@@ -439,6 +528,19 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 #undef RP_MFMA
 #undef RP_MFMA2
 #undef RP_P10
+#undef RP_W_LOAD
+#undef RP_W_NEAR
+#undef RP_W_CENTRE
+#undef RP_W_NORM
+#undef RP_W_SCALE
+#undef RP_W_CHK
+#undef RP_W_X0
+#undef RP_W_R1
+#undef RP_W_X1
+#undef RP_W_X2
+#undef RP_W_SWAP
+#undef RP_W_FIRST
+#undef RP_W_SECOND
 #undef RP_HI2
 #undef RP_AND
 #undef RP_BSET
@@ -460,6 +562,10 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 
         if (round == 1) RP_TRACE(3);
         // D[m - 1][n] with m == n == L (dtw.rs:101): band position q = (L - 1) - (L - W + 1) = W - 2
+        if (WF) {  // a lane tested its own columns of every pair: the window's verdict is the larger of the two halves'
+            const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(chk_), __float_as_uint(chk_), false, false);
+            chk_ = fmaxf(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));
+        }
         float best = 0.f;  // ScoreMode::Max over this lane's templates (scores are > 0; an abandoned wave reports 0 like its scores)
         if (valid) {
             const size_t row = s * out_win_pitch + (size_t)w;
@@ -479,7 +585,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
                     }
                 }
             }
-            // a frame outside the norm range (both lane halves saw the same squared norms): listed for dtw_ref_kernel
+            // a frame outside the norm range (both lane halves hold the same verdict): listed for dtw_ref_kernel
             if (h == 0 && chk_ > kDtwFixLimit) dtw_fix_append(fix, row, (uint32_t)(chunk_base + (int)ci));
         }
         if (agg_out) {  // the chunk holds every sample template (launch_dtw): the two lanes of a window hold all its scores
@@ -530,8 +636,9 @@ hipError_t launch_dtw_mfma(const DtwCall &c, int slots, int chunk_base, int n_ch
     const int row_bytes = p3 ? kDtwMfma3RowBytes : kDtwMfmaRowBytes;
     int nw = dtw_mfma_lds_bytes(t.max_len, 12, row_bytes) <= 160 * 1024 ? 12 : 8;
     if (p3 && slots == 8) {
-        // the three-part form runs two waves per SIMD (8 per workgroup, 219 registers, nothing spilled).  Its twelve-wave build (168 registers,
-        // 49 values spilled) is 1.3 % faster at BASELINE C3 -- 14.93-14.94 ms against 15.11-15.21, alternated three times -- and pays for it with
+        // the three-part form runs two waves per SIMD (8 per workgroup, 221 registers, nothing spilled).  Its twelve-wave build (168 registers,
+        // 58 values spilled) measured 1.3 % faster at BASELINE C3 before the whole-frame operand -- 14.93-14.94 ms against 15.11-15.21, alternated three
+        // times; with it 14.35-14.37 against 14.30-14.69 -- and pays for it with
         // three scratch stores and three reloads per 12-column block that reach the HBM: 5.7 GB per launch against 1.47 (the algorithmic bytes
         // are 1.17 GB).  Harmless for the time (0.38 TB/s), but it is waste on the one counter this path is judged against: not the default.
         // RP_MFMA3_WAVES=12 selects it (same bits)
