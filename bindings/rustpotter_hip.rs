@@ -73,6 +73,8 @@ pub const RP_DTW_KERNEL_REF_ALL: c_int = 64;
 pub const RP_DTW_KERNEL_MFMA_GROUP: c_int = 128;
 pub const RP_DTW_PRODUCTS_BF16X3: c_int = 256;
 pub const RP_DTW_PRODUCTS_F16X2: c_int = 512;
+pub const RP_DTW_MFMA_WAVES_8: c_int = 1024;
+pub const RP_DTW_MFMA_WAVES_12: c_int = 2048;
 pub const RP_MLP_F32: c_int = 0;
 pub const RP_MLP_BF16: c_int = 1;
 pub const RP_MLP_F32_STRICT: c_int = 2;

@@ -229,7 +229,10 @@ enum {
     RP_DTW_KERNEL_MFMA_GROUP = 128, /* dtw_mfma_group_kernel: several chunks of one template length share a column's operand (same bits as MFMA) */
     /* the product arithmetic of the matrix-core launches among the above */
     RP_DTW_PRODUCTS_BF16X3 = 256,  /* three bf16 parts per operand: f32-grade (RP_ARITH_F32_MATRIX) */
-    RP_DTW_PRODUCTS_F16X2 = 512    /* two f16 parts per operand: 22 bits (RP_ARITH_FAST_SPLIT) */
+    RP_DTW_PRODUCTS_F16X2 = 512,   /* two f16 parts per operand: 22 bits (RP_ARITH_FAST_SPLIT) */
+    /* the builds of dtw_mfma_kernel launched among the above: waves per workgroup (same results either way) */
+    RP_DTW_MFMA_WAVES_8 = 1024,    /* two waves per SIMD */
+    RP_DTW_MFMA_WAVES_12 = 2048    /* three waves per SIMD */
 };
 int rp_ctx_dtw_kernels(rp_ctx *ctx);
 /* Which build this library is (replaces nothing): the target architecture and the compiler flags it differs by from the

@@ -778,11 +778,13 @@ class BatchContext:
     DTW_KERNELS = {1: "dtw_mfma_kernel", 2: "dtw_mfma_wide_kernel", 4: "dtw_ragged_kernel", 8: "register kernels", 16: "dtw_generic_kernel",
                    32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel"}
     DTW_PRODUCTS = {256: "bf16x3", 512: "f16x2"}
+    DTW_MFMA_WAVES = {1024: 8, 2048: 12}
 
     def dtw_kernels(self):
         """Names of the DTW kernel families this context launched since the last call of this method (rp_ctx_dtw_kernels)."""
         m = int(self._L.rp_ctx_dtw_kernels(self._h))
         self.last_dtw_products = [n for b, n in self.DTW_PRODUCTS.items() if m & b]   # the matrix-core launches' product arithmetic
+        self.last_dtw_mfma_waves = [n for b, n in self.DTW_MFMA_WAVES.items() if m & b]   # waves per workgroup of the dtw_mfma_kernel launches
         return [n for b, n in self.DTW_KERNELS.items() if m & b]
 
     # --- numpy convenience (host_pointers=True)

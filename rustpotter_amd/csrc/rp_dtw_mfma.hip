@@ -29,11 +29,21 @@
 //     after the first).  What is dropped (x1 a2 + x2 a1 + x2 a2) is below 2^-22 of a product, 2^-25.7 rms -- an f32 multiply rounds by up to
 //     2^-24; tests/test_gpu_dtw_f64.py holds the scores to the strict-f32 oracle's own distance from an f64 evaluation.  The window side's two
 //     operands are one run of six registers (the middle two shared), the A image is 512 bytes per template row (append_mfma_image3,
-//     rp_ctx.cpp); 221 registers = two waves per SIMD, eight per workgroup (a twelve-wave build exists: RP_MFMA3_WAVES=12, see the launcher).  P3 = false (RP_ARITH_FAST_SPLIT, opt-in): the two-part f16 form
+//     rp_ctx.cpp); twelve waves per workgroup = three per SIMD at 168 registers with nothing spilled where twelve waves' frame stages fit beside
+//     the A image, eight (184 registers) where they do not, in a live-stream call, or under RP_MFMA3_WAVES=8 (see the launcher; THREE WAVES below).  P3 = false (RP_ARITH_FAST_SPLIT, opt-in): the two-part f16 form
 //     described above, 22-bit products.
 //   * Two shapes (NT): eight template slots as described (chunks of 5..8 templates, band 3..5), or four (chunks of 3..4, band 5): a
 //     tile is then 8 row slots x 4 templates, 16 circular row slots = 2 tiles, one template pair per lane, columns unrolled 16 at a time, twelve
 //     waves per workgroup (eight where twelve waves' frame stages no longer fit beside the A image) in both arithmetics.  mfcc_size 13 / 16 have their own K axis: rp_dtw_mfma_wide3.hip / rp_dtw_mfma_wide.hip.
+//   * THREE WAVES (168 registers): the third wave per SIMD hides the cell-to-cell dependence of the recurrence, and a column's state -- band
+//     costs 40, accumulators 48, A operands 24, window operands 12 -- is 124 registers before anything else.  What makes the rest fit: (1) nothing
+//     that is only a function of the lane or of a kernel argument is HELD -- lane constants come from fresh_lane_id() once per tile and per part of
+//     the column sweep, the output row is worked out again behind the columns, float forms and reciprocals of uniform values are made where they are
+//     used (not_hoisted) -- the compiler otherwise computes them once per kernel and spills them; (2) the early abandon of detect-only calls is a
+//     kernel of its own for these builds (mfma_abandon_apart, dtw_mfma_abandon_kernel): its state is ten values across the column loop; (3) the
+//     staged eight-slot build holds the second k-step's A operand only for the tile that takes the column's new row and reads the two others'
+//     from LDS a cell before their matrix instructions (mfma_late_a2: +2 ds_read_b128 per column, -8 registers); (4) a frame's split runs in two
+//     pieces instead of four, so that x0_ and y_ never cross a band cell.  No floating-point operation moved: bits as before.
 //   * BUILD: the 12 / 16-column blocks are `#pragma unroll` loops whose bodies exceed the compiler's budget for pragma-requested full
 //     unrolling; this file is compiled with -mllvm -pragma-unroll-threshold=200000 (Makefile FILE_FLAGS_rp_dtw_mfma.hip).  Without it the
 //     three-part four-slot build keeps a rolled loop, indexes its accumulators at run time and spills 13 709 values.
@@ -50,6 +60,24 @@ namespace rp {
 namespace {
 
 typedef unsigned u32x6 __attribute__((ext_vector_type(6)));   // the window side's run of six registers (P3)
+
+// The lane's index in its wave from nothing that lives in a register: two v_mbcnt on a mask the compiler takes for unknown, so that two calls
+// are two values and neither is kept from one to the other (threadIdx.x & 63 is ONE value, alive from the kernel's entry to its last use).
+__device__ __forceinline__ int fresh_lane_id() {
+    unsigned ones = ~0u;
+    asm volatile("" : "+s"(ones));
+    return (int)__builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0u));
+}
+// a wave-uniform value as the compiler must take it where it stands: what is computed from it (a float form, a reciprocal: vector registers)
+// is computed there and not once per kernel
+template <class T> __device__ __forceinline__ T not_hoisted(T v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+// a 64-bit value every lane holds alike, moved to scalar registers
+__device__ __forceinline__ size_t wave_uniform(size_t v) {
+    return ((size_t)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) | (size_t)__builtin_amdgcn_readfirstlane((unsigned)v);
+}
 
 constexpr int kMK = 5;         // MFCC coefficients per frame
 constexpr int kMWin = 32;      // windows per wave
@@ -81,12 +109,28 @@ __host__ __device__ constexpr int mfma_last_use(int u, int g) {
 }
 
 // Which instantiations build the window operand one whole frame per lane and column pair (RP_W_*, in the kernel): the builds of the three-part
-// form but one.  Its cost is a few registers -- 221 against 219 in the headline build; in the 168-register twelve-wave builds 58 spilled values
-// against 49 (eight slots, opt-in) and 16 against 11 (four slots), inside the bounds of tests/test_kernel_resources.py and faster all the same
-//  -- except in the twelve-wave eight-slot build that reads its frames from global memory (RP_MFMA3_WAVES=12 in a live-stream
-// call), where the pair ring of ten registers turns 60 spilled values into 204: that one keeps the per-column build (RP_P*), as does the
-// two-part form, whose split is two conversions per component pair and not what this saves on.
+// form but one -- the twelve-wave eight-slot build that reads its frames from global memory (RP_MFMA3_WAVES=12 in a live-stream call), where
+// the pair ring of ten registers does not fit 168 registers (59 spilled values without it): that one keeps the per-column build (RP_P*), as does
+// the two-part form, whose split is two conversions per component pair and not what this saves on.
 constexpr bool mfma_whole_frame(int nw, bool gx, int nt, bool p3) { return p3 && !(gx && nw == 12 && nt == 8); }
+// Which instantiations read the second k-step's A operand of a tile from LDS right before its matrix instruction instead of holding it: the staged
+// twelve-wave eight-slot builds of the three-part form.  Only the tile that takes a column's new row is re-read at the head of the column (RP_AREF);
+// the two others hold rows that sit where they sat, at an offset that is the same for every lane but for jj rows: one address register + an
+// immediate, two more 16-byte reads per column, and eight registers of operand held no longer.
+constexpr bool mfma_late_a2(int nw, bool gx, int nt, bool p3) { return p3 && nw == 12 && nt == 8 && !gx; }
+// the band cell of column phase u after which tile g's second-step operand is requested: one cell before the tile's first matrix instruction
+template <int W, int NT>
+__host__ __device__ constexpr int mfma_a2_request(int u, int g) {
+    const int lu = mfma_last_use<W, NT>(u, g);
+    return lu < 0 ? 2 * W - 2 : (lu < 1 ? 0 : lu - 1);
+}
+// rows between the newest row (slot sn) and the one row slot 0 + jj of tile g holds, plus jj (g is not sn's tile: no lane wraps differently)
+constexpr int mfma_a2_back(int sn, int g, int nt) { return sn - (32 / nt) * g < 0 ? sn - (32 / nt) * g + mfma_slots(nt) : sn - (32 / nt) * g; }
+
+// Which instantiations leave the early abandon of detect-only calls to a kernel of its own (dtw_mfma_abandon_kernel): the twelve-wave builds of
+// the whole-frame form.  At 168 registers the abandon state -- which of a lane's templates are real, which the averaged one, the cost bound, the
+// wave's verdict -- is ten values held across the column loop, and a call whose result is its score arrays (abandon_nc = +inf) never reads them.
+constexpr bool mfma_abandon_apart(int nw, bool gx, int nt, bool p3) { return nw == 12 && mfma_whole_frame(nw, gx, nt, p3); }
 
 }  // namespace
 
@@ -124,13 +168,19 @@ constexpr bool mfma_whole_frame(int nw, bool gx, int nt, bool p3) { return p3 &&
 #else
 #define RP_MFMA_OCC
 #endif
-template <int W, int NW, bool GX, int NT, bool P3>
-RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
-    const float *__restrict__ mfcc, size_t frame_pitch, size_t n_frames_total, size_t total_tiles, unsigned n_chunks, int chunk_base,
-    size_t first_win, size_t n_win, size_t out_win_pitch, const DtwChunk *__restrict__ chunks, const uint4 *__restrict__ aimg, int T,
-    float score_ref, float *__restrict__ scores, float *__restrict__ avg, size_t n_streams, int max_len, const uint32_t *__restrict__ list,
-    const uint32_t *__restrict__ count, uint32_t dense_min, float abandon_nc, uint32_t *__restrict__ sched, unsigned static_rounds,
-    float *__restrict__ agg_out, uint32_t *__restrict__ agg_hot, float agg_threshold, uint32_t *__restrict__ fix) {
+// the kernel's parameters, once for the body and the two kernels around it
+#define RP_MFMA_PARAMS                                                                                                                       \
+    const float *__restrict__ mfcc, size_t frame_pitch, size_t n_frames_total, size_t total_tiles, unsigned n_chunks, int chunk_base,        \
+    size_t first_win, size_t n_win, size_t out_win_pitch, const DtwChunk *__restrict__ chunks, const uint4 *__restrict__ aimg, int T,        \
+    float score_ref, float *__restrict__ scores, float *__restrict__ avg, size_t n_streams, int max_len, const uint32_t *__restrict__ list, \
+    const uint32_t *__restrict__ count, uint32_t dense_min, float abandon_nc, uint32_t *__restrict__ sched, unsigned static_rounds,         \
+    float *__restrict__ agg_out, uint32_t *__restrict__ agg_hot, float agg_threshold, uint32_t *__restrict__ fix
+#define RP_MFMA_ARGS                                                                                                                         \
+    mfcc, frame_pitch, n_frames_total, total_tiles, n_chunks, chunk_base, first_win, n_win, out_win_pitch, chunks, aimg, T, score_ref,      \
+    scores, avg, n_streams, max_len, list, count, dense_min, abandon_nc, sched, static_rounds, agg_out, agg_hot, agg_threshold, fix
+// AB: early abandon compiled in (abandon_nc < inf then switches it on); false: the call's score arrays are its result, nothing stops early
+template <int W, int NW, bool GX, int NT, bool P3, bool AB>
+__device__ __forceinline__ void dtw_mfma_body(RP_MFMA_PARAMS) {
     constexpr int K = kMK, B = 2 * W, NS = mfma_slots(NT), NTILE = mfma_tiles(NT), SPT = 32 / NT, NP = NT / 4;
     constexpr int kRowBytes = P3 ? kDtwMfma3RowBytes : kDtwMfmaRowBytes;
 #ifndef RP_MFMA_GX_PD  // A/B builds: 1 = the one-column look-ahead of the staged form
@@ -142,6 +192,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
     // WF: the window operand is built one WHOLE frame per lane and column pair (RP_W_*, below); false: every lane builds its half of every column (RP_P*)
     constexpr bool WF = mfma_whole_frame(NW, GX, NT, P3);
     constexpr int PP = GX ? 2 : 1;  // WF: pairs a frame pair is requested ahead of its use
+    constexpr bool A2L = mfma_late_a2(NW, GX, NT, P3);
     static_assert(NS % (2 * PP) == 0, "the pair ring's slot must be a compile-time index");
     static_assert(NT == 8 || NT == 4, "template slots per chunk");
     static_assert(B + 2 <= NS, "the band and its two neighbours must fit the circular row slots");
@@ -160,67 +211,70 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
     const int L = ch->len;  // m == n == L
     const int a_bytes = (max_len + kMSlotsMax) * kRowBytes;
     const int xs_floats = dtw_mfma_stage_floats(max_len);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     dtw_load_aimg<64 * NW>(smem, aimg, P3 ? ch->aimg3_off : ch->aimg_off, (L + kMSlotsMax) * kRowBytes / 16, tid);
     __syncthreads();
     RP_TRACE(1);
     float *xs = reinterpret_cast<float *>(smem + a_bytes) + wave * xs_floats;
     (void)xs;
-    const int n = lane & 31, h = lane >> 5;
-    // A operand: this lane supplies row m = lane & 31 of a tile, k half = lane >> 5.  NT = 8: m = 8 jj + 4 h' + r' = (row slot jj of the
-    // tile, template 4 h' + r'); NT = 4: m = 8 G + 4 h' + 2 sp + e = (row slot 2 G + sp, template 2 h' + e).
-    const int mrow = lane & 31;
-    const int jj = NT == 8 ? mrow >> 3 : 2 * (mrow >> 3) + ((mrow >> 1) & 1);
-    const int tA = NT == 8 ? ((mrow >> 2) & 1) * 4 + (mrow & 3) : ((mrow >> 2) & 1) * 2 + (mrow & 1);
-    const unsigned a_lane = (unsigned)(h * 128 + tA * 16);
-    unsigned dl[SPT];  // byte offset back to the row this lane's slot holds when the newest row sits in slot e of its tile
-#pragma unroll
-    for (int e = 0; e < SPT; ++e) dl[e] = (unsigned)(((e - jj + NS) % NS) * kRowBytes);
-    const unsigned sel_one = h ? 0x07060100u : 0x03020100u;  // slot 7: x1 of component 2 (half 0) / the constant 1.0 (half 1)
-    // P3 (three bf16 parts): register 3 of the first operand holds (x0, x1) of component 2 in half 0 and (x2, x0) in half 1 -- one v_perm
-    // of (t, x0) with a per-half selector, t = r1 - (r1 & mask_c2): r1 itself in half 0 (its upper 16 bits ARE x1), x2 in half 1
-    const unsigned sel_c2 = h ? 0x03020706u : 0x07060302u;
-    const unsigned mask_c2 = h ? 0xffff0000u : 0u;
-    (void)sel_c2; (void)mask_c2;
+    // The early abandon's state, once per kernel (AB only): the template ids are loads from global memory, and a round trip to it in every tile is
+    // 2.5 % of a live-stream call of eight chunks
+    const int hAb = fresh_lane_id() >> 5;
     const float abandon_cost = abandon_nc * (float)(L + L);
     // which of this lane's templates (NT / 2 of them) can keep a wave alive: real ones; the averaged template (tid >= T) always does
     bool slot_real[2 * NP], slot_avg[2 * NP];
 #pragma unroll
     for (int e = 0; e < 2 * NP; ++e) {
-        slot_real[e] = 2 * NP * h + e < ch->count;
-        slot_avg[e] = slot_real[e] && ch->tid[2 * NP * h + e] >= T;
+        slot_real[e] = 2 * NP * hAb + e < ch->count;
+        slot_avg[e] = slot_real[e] && ch->tid[2 * NP * hAb + e] >= T;
     }
 
     uint32_t *next_tile = sched + 2 * (chunk_base + ci);
     unsigned round = 0;
     const size_t chunk_waves = (size_t)n_groups * NW;  // waves working on this chunk
     for (;;) {
-        const size_t tile = dtw_next_tile<NW>(next_tile, round, static_rounds, chunk_waves, n_chunks, wave, lane);
-        if (tile >= total_tiles) break;
-        // ---- lanes -> (stream, window) ----
+        const size_t tile = wave_uniform(dtw_next_tile<NW>(next_tile, round, static_rounds, chunk_waves, n_chunks, wave, fresh_lane_id()));
+        if (tile >= not_hoisted(total_tiles)) break;  // a 64-bit >= is a vector compare: no copy of the bound in vector registers across tiles
+        // The lane's constants are derived per tile, and per phase of a tile, from lane ids the compiler cannot trace back: computed once per
+        // kernel they are a dozen registers held (at three waves per SIMD: spilled) across every tile for the sake of a dozen instructions
+        const int lane_ = fresh_lane_id();
+        const int n = lane_ & 31, h = lane_ >> 5;
+        // ---- lanes -> (stream, window): here for the frames and, in LDS-staged tiles, once more behind the columns for the output row -- the
+        // stream, the window and the validity of a lane are four registers that nothing in between reads, and a few scalar operations to make
+        // again.  From global memory (GX) they are a list lookup and a 64-bit division per lane (2 % of a live-stream call when made twice): kept.
         const size_t f0 = tile * kMWin;
-        bool valid;
-        size_t s;
-        int w;
+        const size_t n_win_ = not_hoisted(n_win);  // the division's reciprocal is per tile, not three vector registers per kernel
+        // LDS-staged tiles: the tile's first (stream, window) and its up to two stream segments, wave-uniform
+        const size_t sA = GX ? 0 : f0 / n_win_;
+        const int wA = GX ? 0 : (int)(f0 - sA * n_win_);
+        const int nA = (int)n_win_ - wA < kMWin ? (int)n_win_ - wA : kMWin;
+        const int nB = (nA < kMWin && sA + 1 < n_streams) ? kMWin - nA : 0;
+        const int segA = nA + L + 3;
+        auto locate = [&](int n_, size_t &s_, int &w_) -> bool {
+            if (GX) {
+                size_t f = f0 + n_;
+                const bool valid_ = f < total_entries;
+                if (list) f = list[valid_ ? f : total_entries - 1];  // row ids s * n_win_ + w of the windows that passed the gate
+                s_ = valid_ ? f / n_win_ : 0;
+                w_ = valid_ ? (int)(f - s_ * n_win_) : 0;
+                return valid_;
+            }
+            const bool inA = n_ < nA;
+            s_ = inA ? sA : sA + 1;
+            w_ = inA ? wA + n_ : n_ - nA;
+            return inA || (n_ - nA < nB);
+        };
         const float *xw;
-        if (GX) {
-            size_t f = f0 + n;
-            valid = f < total_entries;
-            if (list) f = list[valid ? f : total_entries - 1];  // row ids s * n_win + w of the windows that passed the gate
-            s = valid ? f / n_win : 0;
-            w = valid ? (int)(f - s * n_win) : 0;
-            xw = mfcc + (s * frame_pitch + first_win + (size_t)w) * K;  // columns up to L + 8 are read ahead: the caller's frame array ends with 64 frames of slack
-        } else {
+        size_t s_gx;
+        int w_gx;
+        const bool valid = locate(n, s_gx, w_gx);
+        if (GX) xw = mfcc + (s_gx * frame_pitch + first_win + (size_t)w_gx) * K;  // columns up to L + 8 are read ahead: the caller's frame array ends with 64 frames of slack
+        if (!GX) {
             // stage the frames of up to two stream segments (columns L + 1 .. L + 3 are read ahead, never used)
-            const size_t sA = f0 / n_win;
-            const int wA = (int)(f0 - sA * n_win);
-            const int nA = (int)n_win - wA < kMWin ? (int)n_win - wA : kMWin;
-            const int nB = (nA < kMWin && sA + 1 < n_streams) ? kMWin - nA : 0;
-            const int segA = nA + L + 3;
             // four loads in flight per wait: left one by one, a tile's ~11 loads per lane were as many L2 round trips -- nothing covers
             // them in the first round of a short launch, where every wave of the chip stages at the same time
             auto stage =[&](const float *src, size_t g0, int n_floats, float *dst) {
-                for (int i0 = lane; i0 < n_floats; i0 += 256) {
+                for (int i0 = lane_; i0 < n_floats; i0 += 256) {
                     float v[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -235,11 +289,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             stage(mfcc + sA * frame_pitch * K, first_win + wA, segA * K, xs);
             if (nB > 0) stage(mfcc + (sA + 1) * frame_pitch * K, first_win, (nB + L + 3) * K, xs + segA * K);
             wave_lds_sync();
-            const bool inA = n < nA;
-            valid = inA || (n - nA < nB);
-            s = inA ? sA : sA + 1;
-            w = inA ? wA + n : n - nA;
-            xw = xs + (inA ? n : (valid ? segA + n - nA : 0)) * K;
+            xw = xs + (n < nA ? n : (valid ? segA + n - nA : 0)) * K;
         }
         const float *xa = xw + (h ? 3 : 0);  // this half's two components; component 2 at xw + 2
         const float *x2 = xw + 2;
@@ -254,7 +304,8 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
         constexpr int kMeanUnroll = GX ? RP_MFMA_GX_MEAN_UNROLL : RP_MFMA_MEAN_UNROLL;  // from global memory: 20 frames in flight per wait (an L2 round trip each), sums in the same order
 #pragma unroll kMeanUnroll
         for (int i = 0; i < L; ++i) { mua += xa[i * K]; mub += xa[i * K + 1]; mu2 += x2[i * K]; }
-        mua = mua / (float)L; mub = mub / (float)L; mu2 = mu2 / (float)L;
+        const float fL = (float)not_hoisted(L);
+        mua = mua / fL; mub = mub / fL; mu2 = mu2 / fL;
         // WF: the lane centres all five components; the two means it did not sum come from the other half (same sums, same order, same bits)
         float mu_[K] = {0.f, 0.f, 0.f, 0.f, 0.f};
         (void)mu_;
@@ -267,6 +318,30 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
         }
         const float *xh = xw + h * K;  // WF: half h holds the second column of a pair
         (void)xh;
+        // The lane's constants of the columns, from a lane id of their own -- those of the staging above are dead by here -- and once more for
+        // each part of the column sweep (the guarded first block, the blocks of the loop, the tail): what one part has derived from them,
+        // addresses mostly, is not held through the next.
+        // A operand: this lane supplies row m = lane & 31 of a tile, k half = lane >> 5.  NT = 8: m = 8 jj + 4 h' + r' = (row slot jj of the
+        // tile, template 4 h' + r'); NT = 4: m = 8 G + 4 h' + 2 sp + e = (row slot 2 G + sp, template 2 h' + e).
+        // dl[e]: byte offset back to the row this lane's slot holds when the newest row sits in slot e of its tile.
+        // P3 without whole frames: register 3 of the first operand holds (x0, x1) of component 2 in half 0 and (x2, x0) in half 1 -- one v_perm
+        // of (t, x0) with a per-half selector, t = r1 - (r1 & mask_c2): r1 itself in half 0 (its upper 16 bits ARE x1), x2 in half 1
+#define RP_LANE_CONSTS()                                                                                                      \
+        const int laneA_ = fresh_lane_id();                                                                                   \
+        const int hA = laneA_ >> 5;                                                                                           \
+        const bool upper = hA != 0;                                                                                           \
+        const int mrow = laneA_ & 31;                                                                                         \
+        const int jj = NT == 8 ? mrow >> 3 : 2 * (mrow >> 3) + ((mrow >> 1) & 1);                                             \
+        const int tA = NT == 8 ? ((mrow >> 2) & 1) * 4 + (mrow & 3) : ((mrow >> 2) & 1) * 2 + (mrow & 1);                     \
+        const unsigned a_lane = (unsigned)(hA * 128 + tA * 16);                                                               \
+        const unsigned a2_lane = a_lane + 256u + (unsigned)jj * kRowBytes;  /* A2L: second-step operand of the row jj slots behind */ \
+        unsigned dl[SPT];                                                                                                     \
+        _Pragma("unroll") for (int e = 0; e < SPT; ++e) dl[e] = (unsigned)(((e - jj + NS) % NS) * kRowBytes);                 \
+        const unsigned sel_one = upper ? 0x07060100u : 0x03020100u;  /* slot 7: x1 of component 2 (half 0) / the constant 1.0 (half 1) */ \
+        const unsigned sel_c2 = upper ? 0x03020706u : 0x07060302u;                                                            \
+        const unsigned mask_c2 = upper ? 0xffff0000u : 0u;                                                                    \
+        (void)a2_lane; (void)dl; (void)sel_one; (void)sel_c2; (void)mask_c2;
+        RP_LANE_CONSTS()
         if (round == 1) RP_TRACE(2);
 
         // Q[p][q] = D[(c - 1) - W + 1 + q][c - 1] of the template pair p (band position, as P[] of dtw_band_kernel with rows and
@@ -333,7 +408,7 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
                          bop[par].w = __builtin_amdgcn_perm(0x3c000000u, pk_f16_second(x0_, u2_ - x0_), sel_one); }
 // P3: the second k-step's operand: (x0, x0 | x1, x1 | x0, x0) of the half's two components against (a1, a1 | a1, a1 | a2, a2), and register 3 =
 // (x0, x1) of component 2 against (a1, a1) in half 0, the constant (1.0, 0) in half 1
-#define RP_P10(cc, par) if (P3) { bv[par][4] = bv[par][2]; bv[par][5] = h ? 0x00003f80u : bv[par][1]; }
+#define RP_P10(cc, par) if (P3) { bv[par][4] = bv[par][2]; bv[par][5] = upper ? 0x00003f80u : bv[par][1]; }
 #define RP_PREP_ALL(cc, par) RP_P0(cc, (cc) % PD) RP_P1(cc, (cc) % PD) RP_P2(cc) RP_P3(cc) RP_P4(cc) RP_P5(cc) RP_P6(cc, par) RP_P7(cc, par) RP_P8(cc) RP_P9(cc, par) RP_P10(cc, par)
 // WF (mfma_whole_frame): 32 frames per column over 64 lanes are one whole frame per lane every two columns.  Lane (n, h) builds the frame of
 // window n for column cc + h of the pair (cc, cc + 1), cc odd: all five components centred, ONE norm, guard, v_rsq and range test, one split
@@ -377,8 +452,8 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             const auto sw_ = __builtin_amdgcn_permlane32_swap(lo_[i], up_[i], false, false);                                  \
             bv[1][i] = sw_[0]; bv[0][i] = sw_[1];                                                                             \
         }                                                                                                                     \
-        bv[1][4] = bv[1][2]; bv[1][5] = h ? 0x00003f80u : bv[1][1];                                                           \
-        bv[0][4] = bv[0][2]; bv[0][5] = h ? 0x00003f80u : bv[0][1];                                                           \
+        bv[1][4] = bv[1][2]; bv[1][5] = upper ? 0x00003f80u : bv[1][1];                                                           \
+        bv[0][4] = bv[0][2]; bv[0][5] = upper ? 0x00003f80u : bv[0][1];                                                           \
     }
 #define RP_W_FIRST(cc, rs) RP_W_NEAR(cc, rs) RP_W_CENTRE(cc, rs) RP_W_NORM() RP_P4(cc) RP_W_SCALE()
 #define RP_W_SECOND(in_window) RP_W_CHK(in_window) RP_W_X0() RP_W_R1() RP_W_X1() RP_W_X2()
@@ -400,10 +475,20 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
         else acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Areg[g]), __builtin_bit_cast(f16x8, bop[par]), zero16, 0, 0, 0); \
     } while (0)
 // P3: the second k-step on the same accumulator, one band cell after the first (its eight passes are over by then)
-#define RP_MFMA2(g, par)                                                                                                      \
+#define RP_MFMA2X(g, par, A2)                                                                                                 \
     do {                                                                                                                      \
-        if (P3) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Areg2[g]), __builtin_bit_cast(bf16x8, RP_B2(par)), acc[g], 0, 0, 0); \
+        if (P3) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A2), __builtin_bit_cast(bf16x8, RP_B2(par)), acc[g], 0, 0, 0); \
     } while (0)
+#define RP_MFMA2(g, par) RP_MFMA2X(g, par, Areg2[g])
+// A2L, in column c (phase u) for column c + 1, whose newest row c + 1 + W sits in slot sn of tile gn_: tile g != gn_ holds row
+// c + 1 + W - (back - jj) in this lane's slot
+#define RP_A2_LATE(g, GUARD)                                                                                                  \
+    {                                                                                                                         \
+        int off = (c + W - mfma_a2_back((u + 2 + W) % NS, g, NT)) * kRowBytes;                                                \
+        if (GUARD) off = off + (int)(jj * kRowBytes) < 0 ? -(int)(jj * kRowBytes) : off;                                      \
+        a2l[g] = *reinterpret_cast<const u32x4 *>(smem + a2_lane + off);                                                      \
+    }
+#define RP_MFMA2S(g, par) do { if (A2L && g != gn_) RP_MFMA2X(g, par, a2l[g]); else RP_MFMA2(g, par); } while (0)
 
 #ifndef RP_P3_GAP   // band cells between a tile's two k-steps (A/B builds)
 #define RP_P3_GAP 1
@@ -413,6 +498,9 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
     do {                                                                                                                      \
         RP_AREF(c + 1, (u + 1) % NS, GUARD)                                                                                   \
         v2f up[2] = {(v2f){RP_INF, RP_INF}, (v2f){RP_INF, RP_INF}};                                                           \
+        const int gn_ = ((u + 2 + W) % NS) / SPT;  /* the tile RP_AREF has just re-read */                                    \
+        u32x4 a2l[NTILE];                                                                                                     \
+        (void)gn_; (void)a2l;                                                                                                 \
         _Pragma("unroll") for (int q = 0; q < B; ++q) {                                                                       \
             const int sl = (u + q + NS - W + 2) % NS;                                                                         \
             _Pragma("unroll") for (int p = 0; p < NP; ++p) { /* NT = 8: two independent chains, interleaved */                \
@@ -433,8 +521,10 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             if (gi == (1 * 2 * B) / 9) { RP_W_CENTRE(c + 3, ((u + 3) / 2) % PP) }                                             \
             if (gi == (2 * 2 * B) / 9) { RP_W_NORM() } if (gi == (3 * 2 * B) / 9) { RP_P4(c + 3) } if (gi == (4 * 2 * B) / 9) { RP_W_SCALE() } \
             /* from here on u is even: the pair is (c + 2, c + 3); the range test covers columns 1 .. L + 2, as the per-column build's */ \
-            if (gi == (5 * 2 * B) / 9) { RP_W_CHK(!(TAIL) || c + h <= L) RP_W_X0() } if (gi == (6 * 2 * B) / 9) { RP_W_R1() }  \
-            if (gi == (7 * 2 * B) / 9) { RP_W_X1() } if (gi == (8 * 2 * B) / 9) { RP_W_X2() }                                 \
+            /* twelve waves: the split in two pieces instead of four -- x0_ and y_ then never live across a cell (ten registers at the loop's fullest) */ \
+            if (gi == (5 * 2 * B) / 9) { RP_W_CHK(!(TAIL) || c + (upper ? 1 : 0) <= L) RP_W_X0() if (NW == 12) { RP_W_R1() } }  \
+            if (NW != 12 && gi == (6 * 2 * B) / 9) { RP_W_R1() }                                                              \
+            if (gi == (7 * 2 * B) / 9) { RP_W_X1() if (NW == 12) { RP_W_X2() } } if (NW != 12 && gi == (8 * 2 * B) / 9) { RP_W_X2() } \
             } else if (!P3) {                                                                                                 \
             if (q == (0 * B) / 10) { RP_P1(c + 2, (u + 3) % PD) RP_P0(c + 2 + PD, (u + 3) % PD) } if (q == (2 * B) / 10) { RP_P2(c + 2) }                       \
             if (q == (3 * B) / 10) { RP_P3(c + 2) } if (q == (4 * B) / 10) { RP_P4(c + 2) } if (q == (5 * B) / 10) { RP_P5(c + 2) } \
@@ -448,14 +538,15 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             if (q == (9 * B) / 11) { RP_P10(c + 2, (u + 1) & 1) }                                                             \
             }                                                                                                                 \
             _Pragma("unroll") for (int g = 0; g < NTILE; ++g) {                                                               \
+                if (A2L && g != gn_ && mfma_a2_request<W, NT>(u, g) == q) RP_A2_LATE(g, GUARD)                                \
                 if (mfma_last_use<W, NT>(u, g) == q) RP_MFMA(g, u & 1);                                                       \
-                if (q >= RP_P3_GAP && mfma_last_use<W, NT>(u, g) == q - RP_P3_GAP) RP_MFMA2(g, u & 1);                        \
+                if (q >= RP_P3_GAP && mfma_last_use<W, NT>(u, g) == q - RP_P3_GAP) RP_MFMA2S(g, u & 1);                       \
             }                                                                                                                 \
             __builtin_amdgcn_sched_barrier(0);                                                                                \
         }                                                                                                                     \
         _Pragma("unroll") for (int g = 0; g < NTILE; ++g) {                                                                   \
-            if (mfma_last_use<W, NT>(u, g) < 0) { RP_MFMA(g, u & 1); RP_MFMA2(g, u & 1); }                                    \
-            else if (RP_P3_GAP > 0 && mfma_last_use<W, NT>(u, g) > B - 1 - RP_P3_GAP) RP_MFMA2(g, u & 1);                     \
+            if (mfma_last_use<W, NT>(u, g) < 0) { RP_MFMA(g, u & 1); RP_MFMA2S(g, u & 1); }                                   \
+            else if (RP_P3_GAP > 0 && mfma_last_use<W, NT>(u, g) > B - 1 - RP_P3_GAP) RP_MFMA2S(g, u & 1);                    \
         }                                                                                                                     \
     } while (0)
 
@@ -491,9 +582,9 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 // early abandon: wave-uniform, once per 12 columns.  (RP_MFMA_PRICE_NO_ABANDON: tools/isa_mix.py prices the hot loop as the headline call
 // runs it -- abandon_nc = +inf jumps over this block with one scalar branch -- by compiling the block out; never defined in the product.)
 #ifdef RP_MFMA_PRICE_NO_ABANDON
-#define RP_ABANDON_ON false
+#define RP_ABANDON_ON (AB && false)
 #else
-#define RP_ABANDON_ON (abandon_nc < RP_INF)
+#define RP_ABANDON_ON (AB && abandon_nc < RP_INF)
 #endif
 #define RP_ABANDON_CHECK()                                                                                                    \
     if (RP_ABANDON_ON) {                                                                                                \
@@ -506,15 +597,19 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
         }                                                                                                                     \
         if (!__any(alive && valid)) dead = true;                                                                              \
     }
-        for (c0 = 1 + NS; c0 + NS - 1 <= L; c0 += NS) {
-            RP_ABANDON_CHECK()
-            if (dead) break;
+        {
+            RP_LANE_CONSTS()
+            for (c0 = 1 + NS; c0 + NS - 1 <= L; c0 += NS) {
+                RP_ABANDON_CHECK()
+                if (dead) break;
 #pragma unroll
-            for (int u = 0; u < NS; ++u) { const int c = c0 + u; RP_STEP(false, false); }
+                for (int u = 0; u < NS; ++u) { const int c = c0 + u; RP_STEP(false, false); }
+            }
         }
         if (!dead && c0 <= L) {
             RP_ABANDON_CHECK()
             if (!dead) {
+                RP_LANE_CONSTS()
 #pragma unroll
                 for (int u = 0; u < NS - 1; ++u) {  // the last L mod 12 columns
                     const int c = c0 + u;
@@ -523,10 +618,14 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
             }
         }
 #undef RP_ABANDON_CHECK
+#undef RP_LANE_CONSTS
 #undef RP_ABANDON_ON
 #undef RP_STEP
 #undef RP_MFMA
 #undef RP_MFMA2
+#undef RP_MFMA2X
+#undef RP_MFMA2S
+#undef RP_A2_LATE
 #undef RP_P10
 #undef RP_W_LOAD
 #undef RP_W_NEAR
@@ -562,19 +661,25 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
 
         if (round == 1) RP_TRACE(3);
         // D[m - 1][n] with m == n == L (dtw.rs:101): band position q = (L - 1) - (L - W + 1) = W - 2
+        // the lane's output row, from a lane id of its own (see the head of the tile)
+        const int lane2_ = fresh_lane_id();
+        const int h2 = lane2_ >> 5;
+        size_t s = s_gx;
+        int w = w_gx;
+        const bool valid2 = GX ? valid : locate(lane2_ & 31, s, w);
         if (WF) {  // a lane tested its own columns of every pair: the window's verdict is the larger of the two halves'
             const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(chk_), __float_as_uint(chk_), false, false);
             chk_ = fmaxf(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));
         }
         float best = 0.f;  // ScoreMode::Max over this lane's templates (scores are > 0; an abandoned wave reports 0 like its scores)
-        if (valid) {
+        if (valid2) {
             const size_t row = s * out_win_pitch + (size_t)w;
-            const float denom = (float)(L + L);
+            const float denom = (float)not_hoisted(L + L);
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const int slot = 2 * NP * h + 2 * p + e;
+                    const int slot = 2 * NP * h2 + 2 * p + e;
                     if (slot < ch->count) {
                         const float cost = e ? Q[p][W - 2].y : Q[p][W - 2].x;
                         const float nc = cost / denom;
@@ -586,12 +691,12 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
                 }
             }
             // a frame outside the norm range (both lane halves hold the same verdict): listed for dtw_ref_kernel
-            if (h == 0 && chk_ > kDtwFixLimit) dtw_fix_append(fix, row, (uint32_t)(chunk_base + (int)ci));
+            if (h2 == 0 && chk_ > kDtwFixLimit) dtw_fix_append(fix, row, (uint32_t)(chunk_base + (int)ci));
         }
         if (agg_out) {  // the chunk holds every sample template (launch_dtw): the two lanes of a window hold all its scores
             const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(best), __float_as_uint(best), false, false);
             const float m = fmaxf(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));
-            if (valid && h == 0) {
+            if (valid2 && h2 == 0) {
                 agg_out[s * out_win_pitch + (size_t)w] = m;
                 if (agg_hot && m > agg_threshold) agg_hot[s] = 1u;  // as agg_store: every writer stores the same value
             }
@@ -602,7 +707,25 @@ RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(
     RP_TRACE(5);
     __syncthreads();
     RP_TRACE(6);
-    dtw_release_tiles(next_tile, n_groups, tid);
+    dtw_release_tiles(next_tile, n_groups, not_hoisted(wave) * 64 + fresh_lane_id());
+}
+
+// The kernel of an instantiation; where mfma_abandon_apart, without the early abandon: dtw_mfma_abandon_kernel is then what a detect-only call runs
+template <int W, int NW, bool GX, int NT, bool P3>
+RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_kernel(RP_MFMA_PARAMS) {
+    dtw_mfma_body<W, NW, GX, NT, P3, !mfma_abandon_apart(NW, GX, NT, P3)>(RP_MFMA_ARGS);
+}
+template <int W, int NW, bool GX, int NT, bool P3>
+RP_MFMA_OCC __global__ __launch_bounds__(64 * NW, 1) void dtw_mfma_abandon_kernel(RP_MFMA_PARAMS) {
+    dtw_mfma_body<W, NW, GX, NT, P3, true>(RP_MFMA_ARGS);
+}
+#undef RP_MFMA_PARAMS
+#undef RP_MFMA_ARGS
+// what a call with early abandon launches (inside a template so that only the builds of mfma_abandon_apart get a second kernel)
+template <int W, int NW, bool GX, int NT, bool P3>
+constexpr auto mfma_abandon_entry() {
+    if constexpr (mfma_abandon_apart(NW, GX, NT, P3)) return dtw_mfma_abandon_kernel<W, NW, GX, NT, P3>;
+    else return dtw_mfma_kernel<W, NW, GX, NT, P3>;
 }
 
 bool dtw_mfma_supported(const TemplatesDev &t, int band, size_t n_win, bool from_global, int slots, float score_ref) {
@@ -636,15 +759,15 @@ hipError_t launch_dtw_mfma(const DtwCall &c, int slots, int chunk_base, int n_ch
     const int row_bytes = p3 ? kDtwMfma3RowBytes : kDtwMfmaRowBytes;
     int nw = dtw_mfma_lds_bytes(t.max_len, 12, row_bytes) <= 160 * 1024 ? 12 : 8;
     if (p3 && slots == 8) {
-        // the three-part form runs two waves per SIMD (8 per workgroup, 221 registers, nothing spilled).  Its twelve-wave build (168 registers,
-        // 58 values spilled) measured 1.3 % faster at BASELINE C3 before the whole-frame operand -- 14.93-14.94 ms against 15.11-15.21, alternated three
-        // times; with it 14.35-14.37 against 14.30-14.69 -- and pays for it with
-        // three scratch stores and three reloads per 12-column block that reach the HBM: 5.7 GB per launch against 1.47 (the algorithmic bytes
-        // are 1.17 GB).  Harmless for the time (0.38 TB/s), but it is waste on the one counter this path is judged against: not the default.
-        // RP_MFMA3_WAVES=12 selects it (same bits)
+        // The three-part eight-slot form: twelve waves (three per SIMD, 168 registers, nothing spilled, no scratch) where their frame stages fit;
+        // at BASELINE C3 13.9-14.1 ms against 14.4-14.8 for the eight-wave build of the commit before, six alternations on one box, four boxes
+        // (profiles/dtw_three_waves.txt).  Eight waves stay where the twelve-wave build spills: a live-stream call (frames from
+        // global memory: 59 values) and a detect-only call with early abandon (dtw_mfma_abandon_kernel<5, 12, false, 8, true>: 7 values).
+        // RP_MFMA3_WAVES=8 / =12 (read once per process) forces a build; both give the same bits (tests/test_gpu_dtw_mfma_waves.py)
         static const int env_nw = [] { const char *e = std::getenv("RP_MFMA3_WAVES"); return e ? std::atoi(e) : 0; }();
-        if (env_nw != 12) nw = 8;
+        if ((from_global || gate.abandon_nc < RP_INF) ? env_nw != 12 : env_nw == 8) nw = 8;
     }
+    if (nw == 12) dtw_mark(wk, kDtwRanWaves12); else dtw_mark(wk, kDtwRanWaves8);
     const size_t lds = dtw_mfma_lds_bytes(t.max_len, nw, row_bytes);
     const void *image = p3 ? t.aimg3 : t.aimg;
     if (!wk.sched || !wk.fix) return hipErrorInvalidValue;
@@ -652,8 +775,9 @@ hipError_t launch_dtw_mfma(const DtwCall &c, int slots, int chunk_base, int n_ch
     if (hipError_t e = mfma_grid(total_tiles, n_chunks, nw, gate.list != nullptr, blocks, static_rounds); e != hipSuccess) return e;
 #define RP_LAUNCH_MFMA_P(WW, NW, GXV, NT, PP)                                                                                       \
     do {                                                                                                                            \
-        if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(dtw_mfma_kernel<WW, NW, GXV, NT, PP>), 160 * 1024); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dtw_mfma_kernel<WW, NW, GXV, NT, PP>), dim3(blocks), dim3(64 * NW), lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch, \
+        const auto kernel = gate.abandon_nc < RP_INF ? mfma_abandon_entry<WW, NW, GXV, NT, PP>() : dtw_mfma_kernel<WW, NW, GXV, NT, PP>; \
+        if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), 160 * 1024); e != hipSuccess) return e;        \
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * NW), lds, c.st, c.mfcc, c.frame_pitch, c.frame_pitch,                    \
                            total_tiles, (unsigned)n_chunks, chunk_base, c.first_win, c.n_win, c.out_win_pitch, t.chunks,             \
                            reinterpret_cast<const uint4 *>(image), t.T, c.score_ref, c.scores, c.avg, c.S, t.max_len, gate.list, gate.count, \
                            gate.dense_min, gate.abandon_nc, wk.sched, static_rounds, agg_out, agg_hot, agg_threshold, wk.fix);      \

@@ -241,7 +241,9 @@ struct DtwWork {
 // == RP_DTW_KERNEL_* (include/rustpotter_hip.h)
 enum : uint32_t { kDtwRanMfma = 1u, kDtwRanMfmaWide = 2u, kDtwRanRagged = 4u, kDtwRanRegister = 8u, kDtwRanGeneric = 16u, kDtwRanSingle = 32u, kDtwRanRefAll = 64u, kDtwRanMfmaGroup = 128u,
                   // the product arithmetic of the matrix-core launches: three bf16 parts (f32-grade) / two f16 parts (22-bit)
-                  kDtwRanBf16x3 = 256u, kDtwRanF16x2 = 512u };
+                  kDtwRanBf16x3 = 256u, kDtwRanF16x2 = 512u,
+                  // waves per workgroup of the dtw_mfma_kernel launches (two / three per SIMD)
+                  kDtwRanWaves8 = 1024u, kDtwRanWaves12 = 2048u };
 inline void dtw_mark(const DtwWork &wk, uint32_t bit) { if (wk.ran) *wk.ran |= bit; }
 __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { return reinterpret_cast<unsigned long long *>(fix + 2 + 2 * (size_t)kDtwFixCap); }
 // (dtw_fix_append, the kernels' side of the list: rp_device.h)
