@@ -142,6 +142,12 @@ extern "C" {
                                  sample_names: *const *const c_char, wav_buffers: *const *const u8, wav_lens: *const usize,
                                  mfcc_size: u16, rms_from_files: c_int, out_rpw: *mut *mut u8, out_len: *mut usize) -> c_int;
     pub fn rp_buffer_free(buffer: *mut u8);
+    pub fn rp_mfcc_average_batch(ctx: *mut rp_ctx, n_wakewords: usize, mfcc_size: c_int, counts: *const i32, lens: *const i32,
+                                 feats: *const f32, avg: *mut f32) -> c_int;
+    pub fn rp_wakeword_ref_build_batch(ctx: *mut rp_ctx, n_wakewords: usize, names: *const *const c_char, thresholds: *const f32,
+                                       avg_thresholds: *const f32, counts: *const usize, sample_names: *const *const c_char,
+                                       wav_buffers: *const *const u8, wav_lens: *const usize, mfcc_size: u16, rms_from_files: c_int,
+                                       out_rpw: *mut *mut u8, out_lens: *mut usize) -> c_int;
     pub fn rp_wakeword_model_train(ctx: *mut rp_ctx, options: *const rp_train_options, n_train: usize, train_names: *const *const c_char,
                                    train_wavs: *const *const u8, train_lens: *const usize, n_test: usize, test_names: *const *const c_char,
                                    test_wavs: *const *const u8, test_lens: *const usize, prev_model: *const u8, prev_model_len: usize,
@@ -758,6 +764,56 @@ pub fn wakeword_ref_from_sample_buffers(name: &str, threshold: Option<f32>, avg_
                               name_ptrs.as_ptr(), bufs.as_ptr(), lens.as_ptr(), mfcc_size, 0, &mut out, &mut out_len)
     };
     take_buffer(r, out, out_len)
+}
+/// One wakeword of a batched enrolment: its name, the optional thresholds and its samples (name, wav bytes) in the order the
+/// reference would insert them into its `HashMap` (a repeated name replaces the earlier sample).
+pub struct WakewordSamples {
+    pub name: String,
+    pub threshold: Option<f32>,
+    pub avg_threshold: Option<f32>,
+    pub samples: Vec<(String, Vec<u8>)>,
+}
+/// `wakeword_ref_from_sample_buffers` for many wakewords in ONE call: one MFCC launch over all samples, normalisation and the
+/// DTW-aligned averaging on the device; returns the `.rpw` bytes of every wakeword, byte for byte what the single call gives.
+/// One wakeword that cannot be built fails the whole call (the error names its index).
+pub fn wakeword_refs_from_sample_buffers(ctx: &HipContext, wakewords: &[WakewordSamples], mfcc_size: u16) -> Result<Vec<Vec<u8>>, String> {
+    let names: Vec<CString> = wakewords.iter().map(|w| CString::new(w.name.as_str()).map_err(|e| e.to_string())).collect::<Result<_, _>>()?;
+    let name_ptrs: Vec<*const c_char> = names.iter().map(|n| n.as_ptr()).collect();
+    let thr: Vec<f32> = wakewords.iter().map(|w| w.threshold.unwrap_or(f32::NAN)).collect();
+    let athr: Vec<f32> = wakewords.iter().map(|w| w.avg_threshold.unwrap_or(f32::NAN)).collect();
+    let counts: Vec<usize> = wakewords.iter().map(|w| w.samples.len()).collect();
+    let snames: Vec<CString> = wakewords.iter().flat_map(|w| w.samples.iter()).map(|s| CString::new(s.0.as_str()).unwrap()).collect();
+    let sname_ptrs: Vec<*const c_char> = snames.iter().map(|n| n.as_ptr()).collect();
+    let bufs: Vec<*const u8> = wakewords.iter().flat_map(|w| w.samples.iter()).map(|s| s.1.as_ptr()).collect();
+    let lens: Vec<usize> = wakewords.iter().flat_map(|w| w.samples.iter()).map(|s| s.1.len()).collect();
+    let mut out: Vec<*mut u8> = vec![std::ptr::null_mut(); wakewords.len()];
+    let mut out_lens = vec![0usize; wakewords.len()];
+    status(unsafe {
+        rp_wakeword_ref_build_batch(ctx.h, wakewords.len(), name_ptrs.as_ptr(), thr.as_ptr(), athr.as_ptr(), counts.as_ptr(), sname_ptrs.as_ptr(),
+                                    bufs.as_ptr(), lens.as_ptr(), mfcc_size, 0, out.as_mut_ptr(), out_lens.as_mut_ptr())
+    })?;
+    out.into_iter().zip(out_lens).map(|(p, n)| take_buffer(0, p, n)).collect()
+}
+/// `MfccAverager::average` (src/mfcc/averager.rs:5-37) for many wakewords in one call: every wakeword is its templates
+/// ([len][K], all of one K) in fold order -- the first is the origin the others are folded into; returns one averaged
+/// template ([len of the first][K]) per wakeword, with the bits of the reference's f32 arithmetic.
+pub fn mfcc_average_batch(ctx: &HipContext, wakewords: &[Vec<Vec<Vec<f32>>>]) -> Result<Vec<Vec<Vec<f32>>>, String> {
+    let k = wakewords.iter().flat_map(|w| w.iter()).flat_map(|t| t.iter()).map(|r| r.len()).next().unwrap_or(0);
+    if wakewords.iter().any(|w| w.is_empty()) || k == 0 { return Err("a wakeword needs at least one template with frames".to_string()); }
+    let counts: Vec<i32> = wakewords.iter().map(|w| w.len() as i32).collect();
+    let lens: Vec<i32> = wakewords.iter().flat_map(|w| w.iter()).map(|t| t.len() as i32).collect();
+    let feats: Vec<f32> = wakewords.iter().flat_map(|w| w.iter()).flat_map(|t| t.iter()).flat_map(|r| r.iter().copied()).collect();
+    if feats.len() != lens.iter().map(|&l| l as usize).sum::<usize>() * k { return Err("every row must hold the same number of coefficients".to_string()); }
+    let rows: usize = wakewords.iter().map(|w| w[0].len()).sum();
+    let mut avg = vec![0f32; rows * k];
+    status(unsafe { rp_mfcc_average_batch(ctx.h, wakewords.len(), k as c_int, counts.as_ptr(), lens.as_ptr(), feats.as_ptr(), avg.as_mut_ptr()) })?;
+    let mut at = 0usize;
+    Ok(wakewords.iter().map(|w| {
+        let m = w[0].len();
+        let t: Vec<Vec<f32>> = avg[at * k..(at + m) * k].chunks(k).map(|r| r.to_vec()).collect();
+        at += m;
+        t
+    }).collect())
 }
 /// `WakewordModelTrain::train_from_buffers` + `save_to_buffer` (src/wakewords/nn/wakeword_model_train.rs:44-168):
 /// `m_type` 0..3 = ModelType::Tiny..Large; returns (`.rpw` bytes, last loss, test accuracy).

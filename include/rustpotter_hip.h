@@ -274,6 +274,25 @@ int rp_wakeword_ref_build(rp_ctx *ctx, const char *name, const float *threshold,
                           uint16_t mfcc_size, int rms_from_files, uint8_t **out_rpw, size_t *out_len);
 void rp_buffer_free(uint8_t *buffer);
 
+/* MfccAverager::average (src/mfcc/averager.rs:5-37: DTW-aligned mean of templates, folded one after the other into the first) for W
+ * wakewords at once, on the device, with the bits of the reference's f32 arithmetic.  counts [W] (>= 1): templates per wakeword; lens
+ * [sum counts]: rows of each template, in FOLD order (the first of a wakeword is the origin); feats: all rows concatenated, [sum lens][K];
+ * avg receives, concatenated, lens[first template of w] rows of K floats per wakeword (a wakeword of one template: that template).  HOST
+ * arrays, like rp_templates_new.  Features must be finite. */
+int rp_mfcc_average_batch(rp_ctx *ctx, size_t n_wakewords, int mfcc_size, const int32_t *counts, const int32_t *lens,
+                          const float *feats, float *avg);
+
+/* rp_wakeword_ref_build for W wakewords in one call: every wav parsed on the host, ONE MFCC launch over all samples, normalisation and
+ * averaging on the device, one copy back.  names / thresholds / avg_thresholds / counts are [W] (NaN = None; either threshold array may be
+ * NULL = all None); the samples of all wakewords follow each other in sample_names / wav_buffers / wav_lens [sum counts].  out_rpw /
+ * out_lens [W]: one .rpw per wakeword -- the bytes rp_wakeword_ref_build gives for it -- each to be freed with rp_buffer_free.  A wakeword
+ * the single call would refuse fails the whole call: the error is the single call's, prefixed "wakeword <index> (<name>): ", every
+ * out_rpw[w] is NULL and nothing needs freeing. */
+int rp_wakeword_ref_build_batch(rp_ctx *ctx, size_t n_wakewords, const char *const *names, const float *thresholds,
+                                const float *avg_thresholds, const size_t *counts, const char *const *sample_names,
+                                const uint8_t *const *wav_buffers, const size_t *wav_lens, uint16_t mfcc_size, int rms_from_files,
+                                uint8_t **out_rpw, size_t *out_lens);
+
 /* WakewordModelTrain::train_from_buffers (src/wakewords/nn/wakeword_model_train.rs:44-168) followed by
  * save_to_buffer: trains a wakeword model on the device from labelled wav samples and returns it as .rpw bytes.
  * A sample's label is the lower-cased text between '[' and ']' in its name ("none" without one).  Features =

@@ -104,6 +104,7 @@ SYMBOLS = [
     "rp_process_samples_i8", "rp_process_samples_i16", "rp_process_samples_i32", "rp_process_samples_f32",
     "rp_update_config", "rp_update_detector_config", "rp_update_filters_config", "rp_reset", "rp_last_error",
     "rp_ctx_new", "rp_ctx_free", "rp_ctx_set_stream", "rp_ctx_synchronize", "rp_ctx_dtw_ref_pairs", "rp_ctx_dtw_kernels", "rp_ctx_set_arithmetic", "rp_ctx_arithmetic", "rp_ctx_last_mlp_kernel", "rp_build_info", "rp_sharded_gather_info", "rp_mfcc_num_frames", "rp_mfcc_batch", "rp_mfcc_batch_fmt", "rp_batch_detect_fmt", "rp_batch_detect_ingest", "rp_frontend_batch", "rp_wakeword_ref_build", "rp_buffer_free",
+    "rp_mfcc_average_batch", "rp_wakeword_ref_build_batch",
     "rp_templates_new", "rp_templates_free", "rp_templates_max_len", "rp_dtw_score_batch", "rp_detect_scan", "rp_batch_detect",
     "rp_model_new", "rp_model_free", "rp_mlp_forward_batch", "rp_mlp_forward_windows", "rp_synth_pcm_batch", "rp_ctx_timing_enable", "rp_ctx_timing_read", "rp_ctx_timing_reset",
     "rp_version", "rp_stream_batch_new", "rp_stream_batch_free", "rp_stream_batch_process", "rp_stream_batch_reset",
@@ -192,6 +193,10 @@ def load_library():
     L.rp_wakeword_ref_build.argtypes = [vp, C.c_char_p, fp, fp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                         C.POINTER(C.c_size_t), C.c_uint16, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rp_buffer_free.argtypes = [vp]
+    L.rp_mfcc_average_batch.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp, fp]
+    L.rp_wakeword_ref_build_batch.argtypes = [vp, C.c_size_t, C.POINTER(C.c_char_p), fp, fp, C.POINTER(C.c_size_t), C.POINTER(C.c_char_p),
+                                              C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint16, C.c_int, C.POINTER(vp),
+                                              C.POINTER(C.c_size_t)]
     L.rp_templates_new.argtypes = [vp, C.c_int, C.c_int, ip, fp, C.c_int, fp, C.POINTER(vp)]
     L.rp_templates_free.argtypes = [vp]
     L.rp_templates_max_len.argtypes = [vp]
@@ -824,6 +829,58 @@ class BatchContext:
         data = C.string_at(out, out_len.value)
         self._L.rp_buffer_free(out)
         return data
+
+    def average_templates(self, wakewords):
+        """MfccAverager::average for many wakewords in one call (rp_mfcc_average_batch): wakewords = list of lists of [len][K]
+        arrays, each list in FOLD order (the first template is the origin the others are folded into); returns one
+        [len of the first][K] array per wakeword."""
+        import numpy as np
+        if not wakewords:
+            return []
+        tmpl = [[np.ascontiguousarray(t, np.float32) for t in ww] for ww in wakewords]
+        if any(len(ww) == 0 for ww in tmpl):
+            raise RustpotterError("a wakeword needs at least one template")
+        K = tmpl[0][0].shape[1]
+        if any(t.ndim != 2 or t.shape[1] != K for ww in tmpl for t in ww):
+            raise RustpotterError("templates must be [len][K] arrays of one K")
+        counts = np.array([len(ww) for ww in tmpl], np.int32)
+        lens = np.array([t.shape[0] for ww in tmpl for t in ww], np.int32)
+        feats = np.ascontiguousarray(np.concatenate([t for ww in tmpl for t in ww], axis=0))
+        out_lens = [ww[0].shape[0] for ww in tmpl]
+        avg = np.empty((sum(out_lens), K), np.float32)
+        i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        if self._L.rp_mfcc_average_batch(self._h, len(tmpl), K, counts.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
+                                         feats.ctypes.data_as(fp), avg.ctypes.data_as(fp)) < 0:
+            raise _err()
+        ends = np.cumsum(out_lens)
+        return [avg[e - n:e].copy() for e, n in zip(ends, out_lens)]
+
+    def build_wakeword_refs(self, wakewords, mfcc_size, from_files=True):
+        """build_wakeword_ref for many wakewords in one call (rp_wakeword_ref_build_batch): wakewords = list of
+        (name, ordered {sample name: wav bytes}, threshold or None, avg_threshold or None); returns the .rpw bytes of each,
+        byte for byte what build_wakeword_ref gives.  One wakeword that cannot be built fails the whole call."""
+        W = len(wakewords)
+        nan = float("nan")
+        names = (C.c_char_p * W)(*[w[0].encode() for w in wakewords])
+        thr = (C.c_float * W)(*[nan if w[2] is None else w[2] for w in wakewords])
+        athr = (C.c_float * W)(*[nan if w[3] is None else w[3] for w in wakewords])
+        counts = (C.c_size_t * W)(*[len(w[1]) for w in wakewords])
+        snames = [k.encode() for w in wakewords for k in w[1]]
+        bufs = [bytes(v) for w in wakewords for v in w[1].values()]
+        n = len(snames)
+        c_names = (C.c_char_p * n)(*snames)
+        c_bufs = (C.c_char_p * n)(*bufs)
+        c_lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+        out = (C.c_void_p * W)()
+        out_lens = (C.c_size_t * W)()
+        if self._L.rp_wakeword_ref_build_batch(self._h, W, names, thr, athr, counts, c_names, c_bufs, c_lens, mfcc_size,
+                                               1 if from_files else 0, out, out_lens) < 0:
+            raise _err()
+        res = []
+        for w in range(W):
+            res.append(C.string_at(out[w], out_lens[w]))
+            self._L.rp_buffer_free(out[w])
+        return res
 
     def train_wakeword_model(self, train, test, m_type="medium", learning_rate=0.027, epochs=10, test_epochs=10, mfcc_size=16,
                              seed=1, prev_model=None):

@@ -2,12 +2,18 @@
 // new_from_sample_files (src/wakewords/comp/wakeword_ref_build.rs), MfccWavFileExtractor::compute_mfccs
 // (src/mfcc/wav_file_extractor.rs:18-69), MfccAverager::average (src/mfcc/averager.rs) with the unbanded
 // Dtw + back-trace (src/mfcc/dtw.rs:11-55,106-138), and WakewordSave (src/wakewords/wakeword_file.rs:10-26,
-// CBOR as ciborium writes it).  The MFCC frames come from the HIP kernel; the averaging is a short
-// sequential host computation over a handful of templates (offline tooling in the reference too).
+// CBOR as ciborium writes it).  rp_wakeword_ref_build: the MFCC frames come from the HIP kernel, one sample at a time, and the averaging
+// is a short sequential host computation over a handful of templates (offline tooling in the reference too).  The batched forms at the
+// end of the file (build_wakeword_refs, average_templates_batch) enrol many wakewords per call: one MFCC launch over all samples, the
+// normalisation and the averaging on the device (rp_average.hip), bit for bit what the host code here computes.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <atomic>
+#include <exception>
+#include <map>
+#include <thread>
 
 #include "rp_host.h"
 
@@ -62,6 +68,37 @@ float rms_level_of(const float *s, int n) {
     float sum_squared = 0.0f;
     for (int i = 0; i < n; ++i) sum_squared += s[i] * s[i];
     return std::sqrt(sum_squared / (float)n);
+}
+
+// the sample's level, wav_file_extractor.rs:54-58: the median RMS of the encoded buffers (0 without a whole one)
+float median_chunk_rms(const std::vector<float> &mono, size_t enc_chunk) {
+    std::vector<float> rms;
+    for (size_t c = 0; c + enc_chunk <= (mono.size() / enc_chunk) * enc_chunk; c += enc_chunk) rms.push_back(rms_level_of(&mono[c], enc_chunk));
+    if (rms.empty()) return 0.f;
+    std::sort(rms.begin(), rms.end());
+    return rms[rms.size() / 2];
+}
+// frames of an encoded sample: chunks_exact(output frame) drops a tail shorter than 30 ms, the extractor's first frame needs four shifts
+size_t wav_mfcc_frames(size_t encoded_samples) {
+    const size_t n = (encoded_samples / 480) * 480;
+    return n >= 480 ? 3 * (n / 480) - 3 : 0;
+}
+// the wakeword's level: files take the median sample level (wakeword_ref_build.rs:80-81), buffers the maximum (:24-26)
+float wakeword_rms_level(const std::vector<float> &levels, bool rms_median) {
+    if (rms_median) { std::vector<float> s(levels); std::sort(s.begin(), s.end()); return s[s.size() / 2]; }
+    float mx = 0.f;
+    for (float v : levels) if (v > mx) mx = v;
+    return mx;
+}
+// the fold order of compute_avg_samples_features (wakeword_ref_build.rs:90-110): longest template first, equal lengths by name
+std::vector<size_t> fold_order(const WakewordRefData &r) {
+    std::vector<size_t> order(r.tnames.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        if (r.lens[a] != r.lens[b]) return r.lens[a] > r.lens[b];
+        return r.tnames[a] < r.tnames[b];
+    });
+    return order;
 }
 
 // ------------------------------------------------------------------ averager
@@ -172,11 +209,9 @@ bool compute_wav_mfccs(Ctx *ctx, const uint8_t *buf, size_t len, int K, std::vec
         w.mono.swap(enc);
         enc_chunk = fo;
     }
-    std::vector<float> rms;
-    for (size_t c = 0; c + enc_chunk <= (w.mono.size() / enc_chunk) * enc_chunk; c += enc_chunk) rms.push_back(rms_level_of(&w.mono[c], enc_chunk));
-    if (!rms.empty()) { std::sort(rms.begin(), rms.end()); *rms_level = rms[rms.size() / 2]; }  // :54-58
+    if (w.mono.size() >= enc_chunk) *rms_level = median_chunk_rms(w.mono, enc_chunk);  // :54-58
     const size_t n = (w.mono.size() / 480) * 480;  // chunks_exact(output frame): a tail shorter than 30 ms is dropped
-    const size_t nf = n >= 480 ? 3 * (n / 480) - 3 : 0;
+    const size_t nf = wav_mfcc_frames(w.mono.size());
     *frames = (int)nf;
     mfcc->assign(nf * K, 0.f);
     if (nf == 0) return true;
@@ -200,12 +235,7 @@ bool compute_wav_mfccs(Ctx *ctx, const uint8_t *buf, size_t len, int K, std::vec
 static bool average_templates(const WakewordRefData &r, std::vector<float> *avg, int *avg_len) {
     const size_t T = r.tnames.size();
     if (T <= 1) return false;
-    std::vector<size_t> order(T);
-    for (size_t i = 0; i < T; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        if (r.lens[a] != r.lens[b]) return r.lens[a] > r.lens[b];
-        return r.tnames[a] < r.tnames[b];
-    });
+    const std::vector<size_t> order = fold_order(r);
     *avg = r.feats[order[0]];
     *avg_len = r.lens[order[0]];
     for (size_t i = 1; i < T; ++i) average_step(*avg, *avg_len, r.feats[order[i]], r.lens[order[i]], r.mfcc_size);
@@ -234,8 +264,7 @@ bool build_wakeword_ref(Ctx *ctx, const std::string &name, const float *threshol
         else { r.tnames.push_back(sample_names[i]); r.feats.push_back(std::move(m)); r.lens.push_back(frames); levels.push_back(level); }
     }
     if (r.tnames.empty()) { set_last_error("Can not create an empty wakeword"); return false; }  // wakeword_ref.rs:52-54
-    if (rms_median) { std::vector<float> s(levels); std::sort(s.begin(), s.end()); r.rms_level = s[s.size() / 2]; }
-    else { float mx = 0.f; for (float v : levels) if (v > mx) mx = v; r.rms_level = mx; }
+    r.rms_level = wakeword_rms_level(levels, rms_median);
     r.has_avg = average_templates(r, &r.avg, &r.avg_len);
     *out = std::move(r);
     return true;
@@ -277,6 +306,321 @@ std::vector<uint8_t> serialize_wakeword_model(const WakewordModelData &m) {
     }
     c.text("rms_level"); c.f32(m.rms_level);
     return c.out;
+}
+
+// ------------------------------------------------------------- batched forms
+namespace {
+
+// The host's share of a batch (wav decoding, levels, CBOR) is independent per sample / per wakeword: up to 16 threads take indices from
+// one counter.  The first exception of a worker is rethrown on the calling thread.
+template <class F> void parallel_for(size_t n, F &&f) {
+    const size_t nt = std::min<size_t>({(size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency()), n / 4});
+    if (nt <= 1) { for (size_t i = 0; i < n; ++i) f(i); return; }
+    std::atomic<size_t> next{0};
+    std::atomic<bool> failed{false};
+    std::exception_ptr error;
+    auto work = [&] {
+        try {
+            for (size_t i; !failed.load() && (i = next.fetch_add(1)) < n;) f(i);
+        } catch (...) {
+            if (!failed.exchange(true)) error = std::current_exception();
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (size_t t = 1; t < nt; ++t) pool.emplace_back(work);
+    } catch (...) {}   // fewer threads than asked for: the others take the work
+    work();
+    for (std::thread &t : pool) t.join();
+    if (error) std::rethrow_exception(error);
+}
+
+// The averaging kernel's index arrays for W wakewords whose templates lie, in fold order, in one array of rows.
+struct AvgPlan {
+    size_t W = 0, nT = 0, rows = 0, avg_rows = 0;
+    std::vector<int32_t> i32;   // lens [nT] | first [W] | count [W] | wakewords with the matrix in LDS [n_lds] | ... in the workspace [n_ws]
+    std::vector<int64_t> i64;   // row_off [nT] | out_row [W] (-1: no average)
+    size_t n_lds = 0, n_ws = 0, lds_bytes = 0, ws_lds_bytes = 0, ws_slice = 0;
+    const int32_t *lens() const { return i32.data(); }
+    const int32_t *first() const { return i32.data() + nT; }
+    const int32_t *count() const { return i32.data() + nT + W; }
+    const int64_t *row_off() const { return i64.data(); }
+    const int64_t *out_row() const { return i64.data() + nT; }
+};
+
+// every_wakeword: a wakeword of one template gets rows in the output too (the caller copies that template); else only those that fold
+bool plan_average(size_t W, int K, const int32_t *counts, const int32_t *lens, bool every_wakeword, AvgPlan *p) {
+    size_t nT = 0;
+    for (size_t w = 0; w < W; ++w) {
+        if (counts[w] < 1) { set_last_error("wakeword " + std::to_string(w) + ": a wakeword needs at least one template"); return false; }
+        nT += (size_t)counts[w];
+    }
+    if (W > 0x7fffffffULL || nT > 0x7fffffffULL) { set_last_error("too many templates for one call"); return false; }
+    p->W = W; p->nT = nT;
+    p->i32.assign(lens, lens + nT);
+    p->i32.resize(nT + 2 * W);
+    p->i64.assign(nT + W, -1);
+    std::vector<int32_t> in_lds, in_ws;
+    size_t t = 0;
+    for (size_t w = 0; w < W; ++w) {
+        const int T = counts[w], m = lens[t];
+        int n_max = 1;
+        for (int f = 0; f < T; ++f) {
+            if (lens[t + f] < 1) { set_last_error("wakeword " + std::to_string(w) + ": a template without frames"); return false; }
+            if (f) n_max = std::max(n_max, lens[t + f]);
+            p->i64[t + f] = (int64_t)p->rows;
+            p->rows += (size_t)lens[t + f];
+        }
+        p->i32[nT + w] = (int32_t)t;
+        p->i32[nT + W + w] = T;
+        if (T >= 2 || every_wakeword) { p->i64[nT + w] = (int64_t)p->avg_rows; p->avg_rows += (size_t)m; }
+        if (T >= 2) {
+            const size_t with_matrix = average_lds_bytes(m, n_max, K, true), without = average_lds_bytes(m, n_max, K, false);
+            if (with_matrix <= kAvgLdsBudget) { in_lds.push_back((int32_t)w); p->lds_bytes = std::max(p->lds_bytes, with_matrix); }
+            else if (without <= 160 * 1024) {
+                in_ws.push_back((int32_t)w);
+                p->ws_lds_bytes = std::max(p->ws_lds_bytes, without);
+                p->ws_slice = std::max(p->ws_slice, average_matrix_floats(m, n_max));
+            } else { set_last_error("wakeword " + std::to_string(w) + ": templates too long for the averaging kernel"); return false; }
+        }
+        t += (size_t)T;
+    }
+    p->n_lds = in_lds.size(); p->n_ws = in_ws.size();
+    p->i32.insert(p->i32.end(), in_lds.begin(), in_lds.end());
+    p->i32.insert(p->i32.end(), in_ws.begin(), in_ws.end());
+    return true;
+}
+
+// the launches: feats [plan.rows][K] and avg [plan.avg_rows][K] on the device
+bool run_average(Ctx *ctx, int K, const AvgPlan &p, const float *feats, float *avg) {
+    if (p.n_lds + p.n_ws == 0) return true;
+    if (!ctx->ws_enrol_i32.reserve(p.i32.size() * 4) || !ctx->ws_enrol_i64.reserve(p.i64.size() * 8)) return false;
+    if (!hip_ok(hipMemcpyAsync(ctx->ws_enrol_i32.p, p.i32.data(), p.i32.size() * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync") ||
+        !hip_ok(hipMemcpyAsync(ctx->ws_enrol_i64.p, p.i64.data(), p.i64.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))
+        return false;
+    const int32_t *d32 = ctx->ws_enrol_i32.as<int32_t>();
+    const int64_t *d64 = ctx->ws_enrol_i64.as<int64_t>();
+    AverageBatch b;
+    b.feats = feats; b.avg = avg; b.K = K;
+    b.lens = d32; b.first = d32 + p.nT; b.count = d32 + p.nT + p.W;
+    b.row_off = d64; b.out_row = d64 + p.nT;
+    const int32_t *list = d32 + p.nT + 2 * p.W;
+    const size_t cus = (size_t)std::max(ctx->n_cu, 1);
+    if (p.n_lds && !hip_ok(launch_average(ctx->stream, b, list, p.n_lds, true, p.lds_bytes, (unsigned)std::min(p.n_lds, 2 * cus), nullptr, 0),
+                           "average_kernel"))
+        return false;
+    if (p.n_ws) {
+        // a matrix per WORKGROUP, not per wakeword; when the device cannot give that much, one workgroup takes them in turn
+        size_t blocks = std::min(p.n_ws, cus);
+        if (!ctx->ws_avg_matrix.reserve(blocks * p.ws_slice * 4)) {
+            blocks = 1;
+            if (!ctx->ws_avg_matrix.reserve(p.ws_slice * 4)) {
+                set_last_error("the cost matrix of a template pair (" + std::to_string(p.ws_slice * 4) + " bytes) exceeds the workspace the context can allocate");
+                return false;
+            }
+        }
+        if (!hip_ok(launch_average(ctx->stream, b, list + p.n_lds, p.n_ws, false, p.ws_lds_bytes, (unsigned)blocks,
+                                   ctx->ws_avg_matrix.as<float>(), p.ws_slice), "average_kernel (workspace)"))
+            return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+bool average_templates_batch(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32_t *lens, const float *feats, float *avg) {
+    if (W == 0) return true;
+    if (K < 1) { set_last_error("mfcc_size must be >= 1"); return false; }
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return false;
+    AvgPlan p;
+    if (!plan_average(W, K, counts, lens, true, &p)) return false;
+    if (p.n_lds + p.n_ws) {
+        if (!ctx->ws_enrol.reserve((p.rows + p.avg_rows) * (size_t)K * 4)) return false;
+        float *d_feats = ctx->ws_enrol.as<float>(), *d_avg = d_feats + p.rows * (size_t)K;
+        if (!hip_ok(hipMemcpyAsync(d_feats, feats, p.rows * (size_t)K * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync") ||
+            !run_average(ctx, K, p, d_feats, d_avg) ||
+            !hip_ok(hipMemcpyAsync(avg, d_avg, p.avg_rows * (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync") ||
+            !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+            return false;
+    }
+    for (size_t w = 0; w < W; ++w)   // MfccAverager::average of one template: that template
+        if (p.count()[w] == 1) {
+            const size_t t = (size_t)p.first()[w];
+            std::memcpy(avg + (size_t)p.out_row()[w] * K, feats + (size_t)p.row_off()[t] * K, (size_t)p.lens()[t] * K * 4);
+        }
+    return true;
+}
+
+// build_wakeword_ref for W wakewords.  What a wakeword's bytes depend on is computed as the single call computes it: the same wav
+// decoding and chunk levels on the host, the same resampler pair and MFCC kernel (over all samples at once: a frame sees its own
+// sample only), the same normalisation and fold, restated on the device.
+bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const float *thresholds, const float *avg_thresholds,
+                         const size_t *counts, const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens,
+                         int mfcc_size, bool rms_median, std::vector<WakewordRefData> *out) {
+    out->clear();
+    if (W == 0) return true;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return false;
+    const int K = mfcc_size;
+    auto refuse = [&](size_t w, const std::string &text) {
+        set_last_error("wakeword " + std::to_string(w) + " (" + names[w] + "): " + text);
+        return false;
+    };
+    // 1. every wav parsed on the host; what the single call refuses is refused here, in its order
+    struct Sample { std::vector<float> mono; const Resampler *rs = nullptr; size_t enc_chunk = 480; int frames = 0; float level = 0.f; bool live = true; int64_t dst_row = 0; };
+    std::vector<Sample> smp;
+    std::vector<WakewordRefData> refs(W);
+    std::vector<std::vector<size_t>> slot_sample(W);   // per template slot (file order) its sample
+    const MfccTablesDev *tb = nullptr;
+    size_t total = 0;
+    for (size_t w = 0; w < W; ++w) total += counts[w];
+    for (size_t g = 0; g < total; ++g)
+        if (!sample_names[g] || (!wavs[g] && wav_lens[g])) { set_last_error("null argument"); return false; }
+    struct Parsed { Wav wav; std::string err; bool ok = false; };
+    std::vector<Parsed> parsed(total);
+    parallel_for(total, [&](size_t g) { parsed[g].ok = parse_wav(wavs[g], wav_lens[g], &parsed[g].wav, &parsed[g].err); });
+    for (size_t w = 0, g = 0; w < W; ++w) {
+        if (!names[w]) { set_last_error("null argument"); return false; }
+        if (mfcc_size < 1) return refuse(w, "mfcc_size must be >= 1");
+        WakewordRefData &r = refs[w];
+        r.name = names[w];
+        r.mfcc_size = mfcc_size;
+        r.has_threshold = thresholds && !std::isnan(thresholds[w]); r.threshold = r.has_threshold ? thresholds[w] : 0.f;
+        r.has_avg_threshold = avg_thresholds && !std::isnan(avg_thresholds[w]); r.avg_threshold = r.has_avg_threshold ? avg_thresholds[w] : 0.f;
+        for (size_t i = 0; i < counts[w]; ++i, ++g) {
+            if (!parsed[g].ok) return refuse(w, parsed[g].err);
+            Wav &wv = parsed[g].wav;
+            smp.emplace_back();
+            Sample &s = smp.back();
+            s.mono = std::move(wv.mono);
+            size_t encoded = s.mono.size();
+            if (wv.rate != 16000) {
+                s.rs = ctx->resampler_for(wv.rate);
+                if (!s.rs) return refuse(w, std::string(last_error()));
+                s.enc_chunk = (size_t)s.rs->dev.fo;
+                encoded = (s.mono.size() / (size_t)s.rs->dev.fi) * (size_t)s.rs->dev.fo;
+            }
+            s.frames = (int)wav_mfcc_frames(encoded);
+            if (s.frames == 0) return refuse(w, std::string("sample too short: ") + sample_names[g]);
+            if (!tb && !(tb = ctx->tables_for(K))) return refuse(w, std::string(last_error()));
+            // HashMap::insert: a repeated name replaces the earlier sample
+            auto it = std::find(r.tnames.begin(), r.tnames.end(), sample_names[g]);
+            if (it != r.tnames.end()) { size_t k = (size_t)(it - r.tnames.begin()); smp[slot_sample[w][k]].live = false; smp[slot_sample[w][k]].mono = {}; slot_sample[w][k] = smp.size() - 1; }
+            else { r.tnames.push_back(sample_names[g]); slot_sample[w].push_back(smp.size() - 1); }
+        }
+        if (r.tnames.empty()) return refuse(w, "Can not create an empty wakeword");  // wakeword_ref.rs:52-54
+        r.lens.resize(r.tnames.size());
+        for (size_t k = 0; k < r.tnames.size(); ++k) r.lens[k] = smp[slot_sample[w][k]].frames;
+    }
+    std::vector<Parsed>().swap(parsed);
+    // 2. samples that are not 16 kHz: the single call's resample pair, once per rate over all samples of that rate (a row per sample,
+    //    padded with silence to the longest; an output frame reads its own and the previous input frame only)
+    std::map<const Resampler *, std::vector<size_t>> by_rate;
+    for (size_t i = 0; i < smp.size(); ++i) if (smp[i].live && smp[i].rs) by_rate[smp[i].rs].push_back(i);
+    for (auto &grp : by_rate) {
+        const size_t fi = (size_t)grp.first->dev.fi, fo = (size_t)grp.first->dev.fo, S = grp.second.size();
+        size_t nch = 0;
+        for (size_t i : grp.second) nch = std::max(nch, smp[i].mono.size() / fi);
+        std::vector<float> in(S * nch * fi, 0.f), enc(S * nch * fo);
+        for (size_t q = 0; q < S; ++q) { const Sample &s = smp[grp.second[q]]; std::memcpy(&in[q * nch * fi], s.mono.data(), (s.mono.size() / fi) * fi * 4); }
+        DevBuf din, dxs, dout;
+        if (!din.reserve(in.size() * 4) || !dxs.reserve(S * (1 + nch) * fi * 4 + 64) || !dout.reserve(enc.size() * 4)) return false;
+        if (!hip_ok(hipMemcpyAsync(din.p, in.data(), in.size() * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync") ||
+            !hip_ok(launch_resample_stage(ctx->stream, din.p, 3, 1, S, nch, (int)fi, nch * fi, nullptr, dxs.as<float>()), "resample_stage_kernel") ||
+            !hip_ok(launch_resample(ctx->stream, grp.first->dev, dxs.as<float>(), S, nch, dout.as<float>(), nch * fo), "resample_mfma_kernel") ||
+            !hip_ok(hipMemcpyAsync(enc.data(), dout.p, enc.size() * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync") ||
+            !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+            return false;
+        for (size_t q = 0; q < S; ++q) {
+            Sample &s = smp[grp.second[q]];
+            const size_t own = (s.mono.size() / fi) * fo;
+            s.mono.assign(enc.begin() + q * nch * fo, enc.begin() + q * nch * fo + own);
+        }
+    }
+    // 3. levels on the host, then ONE MFCC launch over all encoded samples, a row per sample padded to the longest
+    std::vector<size_t> live;
+    size_t n_max = 0;
+    for (size_t i = 0; i < smp.size(); ++i) if (smp[i].live) {
+        live.push_back(i);
+        n_max = std::max(n_max, (smp[i].mono.size() / 480) * 480);
+    }
+    const size_t S = live.size(), nf_max = wav_mfcc_frames(n_max);
+    // 5. (host side) name replacement is done; the templates of a wakeword lie in fold order: longest first, equal lengths by name
+    std::vector<int32_t> tcounts(W), flens;
+    for (size_t w = 0; w < W; ++w) {
+        tcounts[w] = (int32_t)refs[w].tnames.size();
+        for (size_t k : fold_order(refs[w])) flens.push_back(refs[w].lens[k]);
+    }
+    AvgPlan plan;
+    if (!plan_average(W, K, tcounts.data(), flens.data(), false, &plan)) return false;
+    for (size_t w = 0, t = 0; w < W; ++w)
+        for (size_t k : fold_order(refs[w])) smp[slot_sample[w][k]].dst_row = plan.row_off()[t++];
+    std::vector<float> all((plan.rows + plan.avg_rows) * (size_t)K);
+    {
+        std::vector<int32_t> nf(S);
+        std::vector<int64_t> dst(S);
+        DevBuf &dpcm = ctx->ws_enrol_pcm, &draw = ctx->ws_enrol_raw, &dnf = ctx->ws_enrol_nf, &ddst = ctx->ws_enrol_dst;
+        // the padded rows pass through page-locked memory the context keeps, a slab of at most 128 MB at a time: fresh pageable memory
+        // for all rows cost more in page faults and unmapping than everything the device does in this call
+        const size_t slab_rows = std::max<size_t>(1, std::min(S, ((size_t)128 << 20) / (n_max * 4)));
+        if (!dpcm.reserve(S * n_max * 4) || !draw.reserve(S * nf_max * (size_t)K * 4) || !dnf.reserve(S * 4) || !ddst.reserve(S * 8) ||
+            !ctx->ws_enrol.reserve(all.size() * 4) || !ctx->enrol_stage.reserve(slab_rows * n_max * 4))
+            return false;
+        float *stage = ctx->enrol_stage.as<float>();
+        for (size_t q0 = 0; q0 < S; q0 += slab_rows) {
+            const size_t rows = std::min(slab_rows, S - q0);
+            parallel_for(rows, [&](size_t i) {   // every row is written whole by the thread that takes it
+                Sample &s = smp[live[q0 + i]];
+                s.level = median_chunk_rms(s.mono, s.enc_chunk);
+                const size_t own = (s.mono.size() / 480) * 480;
+                std::memcpy(stage + i * n_max, s.mono.data(), own * 4);
+                std::memset(stage + i * n_max + own, 0, (n_max - own) * 4);
+                std::vector<float>().swap(s.mono);
+                nf[q0 + i] = s.frames; dst[q0 + i] = s.dst_row;
+            });
+            if (!hip_ok(hipMemcpyAsync(dpcm.as<float>() + q0 * n_max, stage, rows * n_max * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync") ||
+                !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))   // the slab is free again
+                return false;
+        }
+        float *d_tmpl = ctx->ws_enrol.as<float>(), *d_avg = d_tmpl + plan.rows * (size_t)K;
+        if (!hip_ok(hipMemcpyAsync(dnf.p, nf.data(), S * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync") ||
+            !hip_ok(hipMemcpyAsync(ddst.p, dst.data(), S * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync") ||
+            !hip_ok(launch_mfcc(ctx->stream, *tb, dpcm.as<float>(), S, n_max, n_max, 0, nf_max, nf_max, draw.as<float>()), "mfcc_kernel") ||
+            // 4. MfccNormalizer::normalize over every sample's own frames, into the fold-ordered template array
+            !hip_ok(launch_normalize_samples(ctx->stream, draw.as<float>(), S, nf_max, K, dnf.as<int32_t>(), ddst.as<int64_t>(), d_tmpl), "normalize_samples_kernel") ||
+            // 6. the averaging kernel over all wakewords with two or more templates
+            !run_average(ctx, K, plan, d_tmpl, d_avg) ||
+            // 7. one copy back of the templates and averages
+            !hip_ok(hipMemcpyAsync(all.data(), d_tmpl, all.size() * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync") ||
+            !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+            return false;
+    }
+    // 8. levels and the data the writer takes
+    parallel_for(W, [&](size_t w) {
+        WakewordRefData &r = refs[w];
+        std::vector<float> levels;
+        r.feats.resize(r.tnames.size());
+        for (size_t k = 0; k < r.tnames.size(); ++k) {
+            const Sample &s = smp[slot_sample[w][k]];
+            levels.push_back(s.level);
+            r.feats[k].assign(all.begin() + (size_t)s.dst_row * K, all.begin() + ((size_t)s.dst_row + (size_t)s.frames) * K);
+        }
+        r.rms_level = wakeword_rms_level(levels, rms_median);
+        const int64_t row = plan.out_row()[w];
+        r.has_avg = row >= 0;
+        if (r.has_avg) {
+            r.avg_len = plan.lens()[plan.first()[w]];
+            const float *a = all.data() + (plan.rows + (size_t)row) * K;
+            r.avg.assign(a, a + (size_t)r.avg_len * K);
+        }
+    });
+    *out = std::move(refs);
+    return true;
+}
+
+std::vector<std::vector<uint8_t>> serialize_wakeword_refs(const std::vector<WakewordRefData> &refs) {
+    std::vector<std::vector<uint8_t>> out(refs.size());
+    parallel_for(refs.size(), [&](size_t w) { out[w] = serialize_wakeword_ref(refs[w]); });
+    return out;
 }
 
 }  // namespace rp

@@ -316,6 +316,43 @@ int rp_wakeword_ref_build(rp_ctx *ctx, const char *name, const float *threshold,
 }
 void rp_buffer_free(uint8_t *buffer) { std::free(buffer); }
 
+int rp_mfcc_average_batch(rp_ctx *ctx, size_t n_wakewords, int mfcc_size, const int32_t *counts, const int32_t *lens, const float *feats,
+                          float *avg) {
+    return guarded([&]() -> int {
+        if (!ctx) { set_last_error("null handle"); return -1; }
+        if (n_wakewords && (!counts || !lens || !feats || !avg)) { set_last_error("null argument"); return -1; }
+        return average_templates_batch(ctx->impl.get(), n_wakewords, mfcc_size, counts, lens, feats, avg) ? 0 : -1;
+    });
+}
+
+int rp_wakeword_ref_build_batch(rp_ctx *ctx, size_t n_wakewords, const char *const *names, const float *thresholds,
+                                const float *avg_thresholds, const size_t *counts, const char *const *sample_names,
+                                const uint8_t *const *wav_buffers, const size_t *wav_lens, uint16_t mfcc_size, int rms_from_files,
+                                uint8_t **out_rpw, size_t *out_lens) {
+    return guarded([&]() -> int {
+        if (!ctx) { set_last_error("null handle"); return -1; }
+        if (n_wakewords && (!names || !counts || !out_rpw || !out_lens)) { set_last_error("null argument"); return -1; }
+        size_t total = 0;
+        for (size_t w = 0; w < n_wakewords; ++w) { out_rpw[w] = nullptr; out_lens[w] = 0; total += counts[w]; }
+        if (total && (!sample_names || !wav_buffers || !wav_lens)) { set_last_error("null argument"); return -1; }
+        std::vector<WakewordRefData> refs;
+        if (!build_wakeword_refs(ctx->impl.get(), n_wakewords, names, thresholds, avg_thresholds, counts, sample_names, wav_buffers, wav_lens,
+                                 (int)mfcc_size, rms_from_files != 0, &refs)) return -1;
+        const std::vector<std::vector<uint8_t>> bytes = serialize_wakeword_refs(refs);   // everything that can throw comes before the first buffer is handed out
+        for (size_t w = 0; w < n_wakewords; ++w) {
+            uint8_t *p = static_cast<uint8_t *>(std::malloc(bytes[w].size()));
+            if (!p) {
+                for (size_t v = 0; v < w; ++v) { std::free(out_rpw[v]); out_rpw[v] = nullptr; out_lens[v] = 0; }
+                set_last_error("out of host memory");
+                return -1;
+            }
+            std::memcpy(p, bytes[w].data(), bytes[w].size());
+            out_rpw[w] = p; out_lens[w] = bytes[w].size();
+        }
+        return 0;
+    });
+}
+
 int rp_wakeword_model_train(rp_ctx *ctx, const rp_train_options *options, size_t n_train, const char *const *train_names,
                             const uint8_t *const *train_wavs, const size_t *train_lens, size_t n_test,
                             const char *const *test_names, const uint8_t *const *test_wavs, const size_t *test_lens,

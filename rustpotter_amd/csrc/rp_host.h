@@ -56,7 +56,15 @@ bool compute_wav_mfccs(Ctx *ctx, const uint8_t *buf, size_t len, int K, std::vec
 bool build_wakeword_ref(Ctx *ctx, const std::string &name, const float *threshold, const float *avg_threshold, size_t n,
                         const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens, int mfcc_size,
                         bool rms_median, WakewordRefData *out);
+// the batched forms: MfccAverager::average for W wakewords (HOST arrays: counts [W], lens [sum counts] in fold order, feats [sum lens][K];
+// avg: lens[first template of w] rows per wakeword), and build_wakeword_ref for W wakewords with one MFCC launch, the normalisation and
+// the averaging on the device (rp_average.hip)
+bool average_templates_batch(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32_t *lens, const float *feats, float *avg);
+bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const float *thresholds, const float *avg_thresholds,
+                         const size_t *counts, const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens,
+                         int mfcc_size, bool rms_median, std::vector<WakewordRefData> *out);
 std::vector<uint8_t> serialize_wakeword_ref(const WakewordRefData &r);
+std::vector<std::vector<uint8_t>> serialize_wakeword_refs(const std::vector<WakewordRefData> &refs);   // the same, on several host threads
 std::vector<uint8_t> serialize_wakeword_model(const WakewordModelData &m);
 // trainer (rp_train.cpp)
 bool model_dims(int m_type, size_t input_len, int mfcc_size, size_t n_labels, std::vector<int> *dims);
@@ -66,6 +74,7 @@ bool train_wakeword_model(Ctx *ctx, const rp_train_options &opt, size_t n_train,
                           WakewordModelData *out, float *final_loss, float *test_accuracy);
 
 void set_last_error(const std::string &msg);
+const std::string &last_error();
 bool hip_ok(hipError_t e, const char *what);
 
 struct DevBuf {
@@ -134,6 +143,11 @@ struct Ctx {
     // only means that kernel is not taken)
     DevBuf ws_rag;
     DtwWork dtw_work_for(size_t S, size_t rows);
+    // enrolment batches (rp_builder.cpp): the call's templates and averages; its padded samples, their frame counts, their places among the
+    // templates and their raw frames; the averaging kernel's index arrays; the cost matrices of the wakewords whose matrix does not fit the
+    // LDS (one slice per workgroup of that launch); page-locked staging (at most 128 MB) the padded samples pass through
+    DevBuf ws_enrol, ws_enrol_pcm, ws_enrol_nf, ws_enrol_dst, ws_enrol_raw, ws_enrol_i32, ws_enrol_i64, ws_avg_matrix;
+    PinBuf enrol_stage;
 
     static Ctx *create(int device, int flags);
     ~Ctx();

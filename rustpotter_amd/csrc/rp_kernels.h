@@ -1,4 +1,4 @@
-// rp_kernels.h -- launchers of the gfx950 kernels (rp_mfcc / rp_dtw / rp_scan / rp_resample / rp_frontend / rp_mlp .hip) used by the
+// rp_kernels.h -- launchers of the gfx950 kernels (rp_mfcc / rp_dtw / rp_scan / rp_resample / rp_frontend / rp_mlp / rp_average .hip) used by the
 // host-side mirror (rp_detector.cpp) and the C ABI (rp_capi.cpp, rp_stream_batch.cpp).
 #pragma once
 #include <cstdlib>
@@ -492,6 +492,31 @@ hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, con
 
 hipError_t launch_synth(hipStream_t st, uint64_t seed, uint64_t first_stream, size_t S, size_t n_samples,
                         size_t pcm_stride, float *pcm);
+
+// Enrolment (rp_average.hip).  MfccNormalizer::normalize over whole samples: sample s owns the first nf[s] frames of raw
+// [S][frame_pitch][K]; its normalised rows go to out + dst_row[s] * K.
+hipError_t launch_normalize_samples(hipStream_t st, const float *raw, size_t S, size_t frame_pitch, int K, const int32_t *nf,
+                                    const int64_t *dst_row, float *out);
+// MfccAverager::average for many wakewords: wakeword w folds the templates first[w] .. first[w] + count[w] - 1 in that order (the first is
+// the origin); template t is lens[t] rows of K floats at feats + row_off[t] * K; the result (lens[first[w]] rows) goes to avg +
+// out_row[w] * K.  All device pointers.
+struct AverageBatch {
+    const float *feats = nullptr;
+    const int32_t *lens = nullptr, *first = nullptr, *count = nullptr;
+    const int64_t *row_off = nullptr, *out_row = nullptr;
+    float *avg = nullptr;
+    int K = 0;
+};
+// What a workgroup keeps in LDS for an origin of m rows and frames of up to n: both templates, their norms, the path's runs and --
+// lds_matrix -- the m x n cost matrix; average_matrix_floats: the matrix alone (a workgroup's workspace slice otherwise).
+size_t average_matrix_floats(int m, int n);
+size_t average_lds_bytes(int m, int n, int K, bool lds_matrix);
+// Two workgroups per CU share its 160 KB: a wakeword whose average_lds_bytes(.., true) is within this keeps its matrix in LDS
+constexpr size_t kAvgLdsBudget = 80 * 1024;
+// One launch over the listed wakewords (`blocks` workgroups stride over them).  lds_bytes: the largest average_lds_bytes of the list;
+// ws: blocks x ws_slice floats (the matrices of a launch with lds_matrix false).
+hipError_t launch_average(hipStream_t st, const AverageBatch &b, const int32_t *list, size_t n_list, bool lds_matrix, size_t lds_bytes,
+                          unsigned blocks, float *ws, size_t ws_slice);
 
 // x [B][dims[0]] -> out [B][dims[n_layers]]; W/Bv device pointers per layer.
 // MfccNormalizer::normalize of windows [w, w+L) flattened row-major to x [n_win][L*K]
