@@ -75,6 +75,8 @@ pub const RP_DTW_PRODUCTS_BF16X3: c_int = 256;
 pub const RP_DTW_PRODUCTS_F16X2: c_int = 512;
 pub const RP_DTW_MFMA_WAVES_8: c_int = 1024;
 pub const RP_DTW_MFMA_WAVES_12: c_int = 2048;
+pub const RP_DTW_KERNEL_BANK: c_int = 4096;
+pub const RP_WAKEWORD_BANK_MAX_TEMPLATES: c_int = 32;
 pub const RP_MLP_F32: c_int = 0;
 pub const RP_MLP_BF16: c_int = 1;
 pub const RP_MLP_F32_STRICT: c_int = 2;
@@ -96,6 +98,7 @@ pub enum rp_ctx {}
 pub enum rp_templates {}
 pub enum rp_stream_batch {}
 pub enum rp_model {}
+pub enum rp_wakeword_bank {}
 
 // every function of include/rustpotter_hip.h, in the header's order
 extern "C" {
@@ -183,6 +186,21 @@ extern "C" {
                                  n_wakewords: usize, t: *const *const rp_templates, config: *const rp_detector_config,
                                  thresholds: *const f32, avg_thresholds: *const f32, det: *mut rp_batch_detection,
                                  det_wakeword: *mut i32, n_det: *mut i32, max_det: c_int) -> c_int;
+    /// wakeword banks: W references uploaded once, every stream scored against its own (stream_wakeword [S], -1 = none)
+    pub fn rp_wakeword_bank_new(ctx: *mut rp_ctx, n_wakewords: usize, mfcc_size: c_int, counts: *const i32, lens: *const i32, feats: *const f32,
+                                avg_lens: *const i32, avg_feats: *const f32, thresholds: *const f32, avg_thresholds: *const f32,
+                                out: *mut *mut rp_wakeword_bank) -> c_int;
+    pub fn rp_wakeword_bank_new_from_rpw(ctx: *mut rp_ctx, n_wakewords: usize, rpw_buffers: *const *const u8, rpw_lens: *const usize,
+                                         out: *mut *mut rp_wakeword_bank) -> c_int;
+    pub fn rp_wakeword_bank_free(bank: *mut rp_wakeword_bank);
+    pub fn rp_wakeword_bank_max_len(bank: *const rp_wakeword_bank, wakeword: i64) -> c_int;
+    pub fn rp_dtw_score_bank(ctx: *mut rp_ctx, mfcc: *const f32, S: usize, n_frames: usize, bank: *const rp_wakeword_bank,
+                             stream_wakeword: *const i32, score_ref: f32, band_size: c_int, score_mode: c_int, with_avg: c_int, avg: *mut f32,
+                             agg: *mut f32, win_pitch: usize) -> c_int;
+    pub fn rp_batch_detect_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                bank: *const rp_wakeword_bank, stream_wakeword: *const i32, config: *const rp_detector_config,
+                                det: *mut rp_batch_detection, n_det: *mut i32, max_det: c_int, agg: *mut f32, avg: *mut f32,
+                                win_pitch: usize) -> c_int;
     pub fn rp_resampler_frame_lengths(sample_rate: usize, in_len: *mut usize, out_len: *mut usize) -> c_int;
     pub fn rp_resample_batch(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, channels: c_int, sample_rate: usize, S: usize,
                              n_samples: usize, pcm_stride: usize, out: *mut f32, out_stride: usize) -> c_int;
@@ -373,6 +391,19 @@ impl Drop for Templates { fn drop(&mut self) { unsafe { rp_templates_free(self.h
 impl Templates {
     pub fn max_len(&self) -> usize { unsafe { rp_templates_max_len(self.h) as usize } }
 }
+/// A bank of personal wakeword references on the device: stream `s` of a bank call carries wakeword `stream_wakeword[s]` (-1: none) --
+/// one `Rustpotter` per thread, each with its own wakeword (src/detector.rs:304-346), as one batch.  Borrows the context it was made on.
+pub struct WakewordBank { h: *mut rp_wakeword_bank, pub n_wakewords: usize }
+impl Drop for WakewordBank { fn drop(&mut self) { unsafe { rp_wakeword_bank_free(self.h) } } }
+impl WakewordBank {
+    /// window length of one wakeword (`get_mfcc_frame_size`, src/wakewords/comp/wakeword_comp.rs:69-75)
+    pub fn max_len(&self, wakeword: usize) -> Result<usize, String> {
+        let r = unsafe { rp_wakeword_bank_max_len(self.h, wakeword as i64) };
+        if r < 0 { Err(last_error()) } else { Ok(r as usize) }
+    }
+    /// the longest window length in the bank
+    pub fn longest(&self) -> usize { unsafe { rp_wakeword_bank_max_len(self.h, -1) }.max(0) as usize }
+}
 /// A wakeword model on the device (`WakewordNN`, src/wakewords/nn/wakeword_nn.rs:17-37).
 pub struct Model { h: *mut rp_model, pub dims: Vec<c_int> }
 impl Drop for Model { fn drop(&mut self) { unsafe { rp_model_free(self.h) } } }
@@ -543,6 +574,58 @@ impl HipContext {
         })?;
         let w = (0..n_streams).map(|s| which[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect();
         Ok((split_detections(det, n_det, max_det), w))
+    }
+    /// A bank from wakeword references: per wakeword its sample templates (`[len][mfcc_size]` rows, flattened per template), its averaged
+    /// template (empty: none) and its own `(threshold, avg_threshold)` options.
+    pub fn wakeword_bank(&self, mfcc_size: u16, wakewords: &[(Vec<Vec<f32>>, Vec<f32>, Option<f32>, Option<f32>)]) -> Result<WakewordBank, String> {
+        let k = mfcc_size as usize;
+        let counts: Vec<i32> = wakewords.iter().map(|w| w.0.len() as i32).collect();
+        let lens: Vec<i32> = wakewords.iter().flat_map(|w| w.0.iter().map(|t| (t.len() / k) as i32)).collect();
+        let feats: Vec<f32> = wakewords.iter().flat_map(|w| w.0.iter().flatten().copied()).collect();
+        let avg_lens: Vec<i32> = wakewords.iter().map(|w| (w.1.len() / k) as i32).collect();
+        let avg_feats: Vec<f32> = wakewords.iter().flat_map(|w| w.1.iter().copied()).collect();
+        let thr: Vec<f32> = wakewords.iter().map(|w| w.2.unwrap_or(f32::NAN)).collect();
+        let athr: Vec<f32> = wakewords.iter().map(|w| w.3.unwrap_or(f32::NAN)).collect();
+        let mut h = std::ptr::null_mut();
+        status(unsafe {
+            rp_wakeword_bank_new(self.h, wakewords.len(), mfcc_size as c_int, counts.as_ptr(), lens.as_ptr(), feats.as_ptr(), avg_lens.as_ptr(),
+                                 avg_feats.as_ptr(), thr.as_ptr(), athr.as_ptr(), &mut h)
+        })?;
+        Ok(WakewordBank { h, n_wakewords: wakewords.len() })
+    }
+    /// A bank from `.rpw` bytes (what `wakeword_ref_build_batch` returns); every wakeword keeps its own threshold options.
+    pub fn wakeword_bank_from_rpw(&self, rpw: &[Vec<u8>]) -> Result<WakewordBank, String> {
+        let ptrs: Vec<*const u8> = rpw.iter().map(|b| b.as_ptr()).collect();
+        let lens: Vec<usize> = rpw.iter().map(|b| b.len()).collect();
+        let mut h = std::ptr::null_mut();
+        status(unsafe { rp_wakeword_bank_new_from_rpw(self.h, rpw.len(), ptrs.as_ptr(), lens.as_ptr(), &mut h) })?;
+        Ok(WakewordBank { h, n_wakewords: rpw.len() })
+    }
+    /// `dtw_score_batch` for a bank: (avg, agg) as rows of `win_pitch` floats per stream -- the stream's windows, zeros behind them.
+    pub fn dtw_score_bank(&self, mfcc: &[f32], n_streams: usize, n_frames: usize, bank: &WakewordBank, stream_wakeword: &[i32], score_ref: f32,
+                          band_size: u16, score_mode: ScoreMode, with_avg: bool, win_pitch: usize) -> Result<(Vec<f32>, Vec<f32>), String> {
+        assert!(stream_wakeword.len() == n_streams);
+        let mut avg = vec![0f32; if with_avg { n_streams * win_pitch } else { 0 }];
+        let mut agg = vec![0f32; n_streams * win_pitch];
+        status(unsafe {
+            rp_dtw_score_bank(self.h, mfcc.as_ptr(), n_streams, n_frames, bank.h, stream_wakeword.as_ptr(), score_ref, band_size as c_int,
+                              score_mode_to_c(score_mode), with_avg as c_int, if with_avg { avg.as_mut_ptr() } else { std::ptr::null_mut() },
+                              agg.as_mut_ptr(), win_pitch)
+        })?;
+        Ok((avg, agg))
+    }
+    /// `batch_detect` where stream `s` carries its own wakeword `bank[stream_wakeword[s]]` (-1: none): detect-only.
+    pub fn batch_detect_bank(&self, pcm: &[f32], n_streams: usize, n_samples: usize, bank: &WakewordBank, stream_wakeword: &[i32],
+                             config: &DetectorConfig, max_det: usize) -> Result<Detections, String> {
+        assert!(pcm.len() >= n_streams * n_samples && stream_wakeword.len() == n_streams);
+        let c: rp_detector_config = config.into();
+        let mut det = vec![rp_batch_detection::default(); n_streams * max_det];
+        let mut n_det = vec![0i32; n_streams];
+        status(unsafe {
+            rp_batch_detect_bank(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, bank.h, stream_wakeword.as_ptr(),
+                                 &c, det.as_mut_ptr(), n_det.as_mut_ptr(), max_det as c_int, std::ptr::null_mut(), std::ptr::null_mut(), 0)
+        })?;
+        Ok(split_detections(det, n_det, max_det))
     }
     /// Upload a wakeword model: `weights[l]` = `[dims[l+1]][dims[l]]` row-major (candle `Linear`), `biases[l]` = `[dims[l+1]]`.
     pub fn model(&self, dims: &[c_int], weights: &[Vec<f32>], biases: &[Vec<f32>]) -> Result<Model, String> {

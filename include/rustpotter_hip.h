@@ -232,7 +232,8 @@ enum {
     RP_DTW_PRODUCTS_F16X2 = 512,   /* two f16 parts per operand: 22 bits (RP_ARITH_FAST_SPLIT) */
     /* the builds of dtw_mfma_kernel launched among the above: waves per workgroup (same results either way) */
     RP_DTW_MFMA_WAVES_8 = 1024,    /* two waves per SIMD */
-    RP_DTW_MFMA_WAVES_12 = 2048    /* three waves per SIMD */
+    RP_DTW_MFMA_WAVES_12 = 2048,   /* three waves per SIMD */
+    RP_DTW_KERNEL_BANK = 4096      /* dtw_bank_kernel: every stream against its own wakeword of a bank (rp_dtw_score_bank, rp_batch_detect_bank) */
 };
 int rp_ctx_dtw_kernels(rp_ctx *ctx);
 /* Which build this library is (replaces nothing): the target architecture and the compiler flags it differs by from the
@@ -434,6 +435,59 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
                           size_t n_wakewords, const rp_templates *const *t, const rp_detector_config *config,
                           const float *thresholds, const float *avg_thresholds, rp_batch_detection *det,
                           int32_t *det_wakeword, int32_t *n_det, int max_det);
+
+/* Personal wakewords: a wakeword BANK -- W wakeword references uploaded once -- and calls in which stream s carries its own wakeword
+ * stream_wakeword[s].  The batched form of one `Rustpotter` per thread, each holding one wakeword (src/detector.rs:304-346): enrol
+ * (rp_wakeword_ref_build_batch) -> bank -> detect.  A bank borrows `ctx`, which must outlive it, and is used with that context only.
+ * Arithmetic: bank calls always score with f32 vector FMAs, the arithmetic of RP_ARITH_STRICT_F32, whatever rp_ctx_set_arithmetic says
+ * (the setting is neither read nor changed); a stream gets the bits rp_batch_detect / rp_dtw_score_batch give it under RP_ARITH_STRICT_F32
+ * with its wakeword as rp_templates.  rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK.
+ * Limits (refused with an error that names them): at most RP_WAKEWORD_BANK_MAX_TEMPLATES sample templates per wakeword; mfcc_size 5, 13 or
+ * 16 with band_size 3..6 (the pairs the register kernels are built for), or band_size 0 (every score 0, as everywhere); an averaged
+ * template no longer than the wakeword's longest sample template (src/mfcc/averager.rs:5-37 folds into the first sample: never a longer one).  Wakeword
+ * models cannot be part of a bank. */
+enum { RP_WAKEWORD_BANK_MAX_TEMPLATES = 32 };
+typedef struct rp_wakeword_bank rp_wakeword_bank;
+/* WakewordRef (src/wakewords/wakeword_ref.rs:12-20) x n_wakewords from HOST arrays in the flat layout of rp_mfcc_average_batch: counts
+ * [W] (1..RP_WAKEWORD_BANK_MAX_TEMPLATES) sample templates per wakeword, lens [sum counts] (>= 1) rows of each, feats [sum lens][mfcc_size]
+ * (finite; already mean-normalised, as stored in a .rpw); avg_lens [W] rows of each wakeword's averaged template, 0 = none, and avg_feats
+ * [sum avg_lens][mfcc_size] (both may be NULL: no averaged templates); thresholds / avg_thresholds [W]: the wakeword's own Option<f32>,
+ * NaN = None = the value of the call's config applies, as in rp_batch_detect_multi (either array may be NULL).  A wakeword that is refused
+ * fails the call with "wakeword <index>: <reason>". */
+int rp_wakeword_bank_new(rp_ctx *ctx, size_t n_wakewords, int mfcc_size, const int32_t *counts, const int32_t *lens, const float *feats,
+                         const int32_t *avg_lens, const float *avg_feats, const float *thresholds, const float *avg_thresholds,
+                         rp_wakeword_bank **out);
+/* The same from .rpw bytes (WakewordLoad::load_from_buffer, src/wakewords/wakeword_file.rs:38; src/detector.rs:152-176) -- what
+ * rp_wakeword_ref_build_batch returns goes straight in.  Each wakeword keeps its own threshold / avg_threshold Options.  A wakeword model,
+ * a file the reader refuses or a wakeword whose mfcc_size differs from the first one's fails the whole call: "wakeword <index>: <reason>"
+ * (src/detector.rs:310-320: "Usage of wakewords with different mfcc size is not supported, ignoring wakeword"). */
+int rp_wakeword_bank_new_from_rpw(rp_ctx *ctx, size_t n_wakewords, const uint8_t *const *rpw_buffers, const size_t *rpw_lens,
+                                  rp_wakeword_bank **out);
+void rp_wakeword_bank_free(rp_wakeword_bank *bank);
+/* WakewordComparator::get_mfcc_frame_size (src/wakewords/comp/wakeword_comp.rs:69-75): the longest sample template of that wakeword = its
+ * window length; wakeword < 0: the longest in the bank (0 for an empty bank).  -1 for a NULL bank or an index outside the bank. */
+int rp_wakeword_bank_max_len(const rp_wakeword_bank *bank, long long wakeword);
+/* rp_dtw_score_batch for a bank (src/wakewords/comp/wakeword_comp.rs:22-37,77-139 per stream with its own wakeword): mfcc [S][n_frames][K],
+ * stream_wakeword [S] int32 (-1: the stream has no wakeword).  agg and avg (avg may be NULL) are [S][win_pitch]: row s holds
+ * n_win_s = n_frames - max_len(wakeword of s) + 1 values (the score_mode aggregate; the averaged template's score when with_avg != 0 and
+ * the wakeword has one, else 0) and zeros behind them up to win_pitch; a stream without a wakeword or shorter than its window has an
+ * all-zero row.  win_pitch smaller than the largest n_win_s of the call is an error.  With RP_CTX_HOST_POINTERS an index outside
+ * [-1, n_wakewords) is an error, found before anything is launched; with device arrays the kernels treat such an index as -1 and win_pitch
+ * must hold the largest window count any wakeword of the bank gives. */
+int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames, const rp_wakeword_bank *bank, const int32_t *stream_wakeword,
+                      float score_ref, int band_size, rp_score_mode score_mode, int with_avg, float *avg, float *agg, size_t win_pitch);
+/* rp_batch_detect for a bank: stream s = Rustpotter::new(config) + add_wakeword(bank[stream_wakeword[s]]) + process_samples over the
+ * stream (src/detector.rs:304-346,347-454): max_mfcc_frames is that wakeword's longest sample template, every template scores the oldest
+ * `len` frames of the window (wakeword_comp.rs:22-27), the wakeword's own thresholds override config's, the averaged-template test runs
+ * only when the wakeword has an averaged template and its effective avg_threshold != 0 (:83-93), the countdown is max_len / 2; reset and
+ * VAD as in rp_batch_detect.  stream_wakeword[s] == -1: a Rustpotter without wakewords -- n_det[s] = 0 (indices as in rp_dtw_score_bank).
+ * det [S][max_det], n_det [S] as in rp_detect_scan.  agg / avg (either may be NULL) [S][win_pitch] as in rp_dtw_score_bank, with the
+ * semantics of rp_batch_detect's agg: when either is requested, or the context has RP_CTX_FULL_SCORES, every window is fully scored;
+ * otherwise (detect-only) a wave of 64 windows none of which passes the averaged-template gate skips the sample templates -- the
+ * detections are the same either way.  win_pitch is only read when agg or avg is requested. */
+int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                         const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config,
+                         rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, float *avg, size_t win_pitch);
 
 /* Sample-rate conversion in front of the path: AudioEncoder::new / reencode_to_mono_with_sample_rate
  * (src/audio/encoder.rs:41-60,63-83), i.e. rubato's FftFixedInOut<f32>::new(sample_rate, 16000, 480, 1) and one

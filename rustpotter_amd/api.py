@@ -113,6 +113,8 @@ SYMBOLS = [
     "rp_batch_detect_multi", "rp_batch_detect_model", "rp_batch_detect_sharded",
     "rp_stream_batch_new_multi", "rp_stream_batch_process_multi",
     "rp_stream_batch_set_filters", "rp_stream_batch_levels",
+    "rp_wakeword_bank_new", "rp_wakeword_bank_new_from_rpw", "rp_wakeword_bank_free", "rp_wakeword_bank_max_len", "rp_dtw_score_bank",
+    "rp_batch_detect_bank",
 ]
 
 
@@ -237,6 +239,15 @@ def load_library():
     L.rp_ctx_timing_enable.argtypes = [vp, C.c_int]
     L.rp_ctx_timing_read.argtypes = [vp, C.c_int, C.POINTER(C.c_double), ip]
     L.rp_ctx_timing_reset.argtypes = [vp]
+    i32p = C.POINTER(C.c_int32)
+    L.rp_wakeword_bank_new.argtypes = [vp, C.c_size_t, C.c_int, i32p, i32p, fp, i32p, fp, fp, fp, C.POINTER(vp)]
+    L.rp_wakeword_bank_new_from_rpw.argtypes = [vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(vp)]
+    L.rp_wakeword_bank_free.argtypes = [vp]
+    L.rp_wakeword_bank_free.restype = None
+    L.rp_wakeword_bank_max_len.argtypes = [vp, C.c_longlong]
+    L.rp_dtw_score_bank.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t]
+    L.rp_batch_detect_bank.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(_DetectorConfig), vp, vp, C.c_int,
+                                       vp, vp, C.c_size_t]
     _LIB = L
     return L
 
@@ -501,6 +512,58 @@ class Model:
     def __del__(self):
         if getattr(self, "_h", None):
             self._L.rp_model_free(self._h)
+            self._h = None
+
+
+class WakewordBank:
+    """rp_wakeword_bank: W wakeword references resident on the device, scored per stream through an index
+    (BatchContext.dtw_scores_bank / batch_detect_bank).  Exactly one of
+    wakewords = [(templates, avg or None, threshold or None, avg_threshold or None), ...] with templates a list of [len][K] arrays, or
+    rpw = [bytes of a wakeword reference .rpw, ...] (what BatchContext.build_wakeword_refs returns)."""
+
+    def __init__(self, ctx, wakewords=None, rpw=None):
+        import numpy as np
+        if (wakewords is None) == (rpw is None):
+            raise RustpotterError("WakewordBank takes either wakewords or rpw")
+        self._L = load_library()
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        if rpw is not None:
+            W = len(rpw)
+            bufs = [bytes(b) for b in rpw]
+            r = self._L.rp_wakeword_bank_new_from_rpw(ctx._h, W, (C.c_char_p * W)(*bufs), (C.c_size_t * W)(*[len(b) for b in bufs]), C.byref(self._h))
+        else:
+            W = len(wakewords)
+            nan = float("nan")
+            tmpl = [[np.ascontiguousarray(t, np.float32) for t in w[0]] for w in wakewords]
+            avgs = [None if w[1] is None else np.ascontiguousarray(w[1], np.float32) for w in wakewords]
+            K = tmpl[0][0].shape[1] if W else 1
+            counts = np.array([len(t) for t in tmpl], np.int32)
+            lens = np.array([t.shape[0] for ww in tmpl for t in ww], np.int32)
+            feats = np.ascontiguousarray(np.concatenate([t.reshape(-1) for ww in tmpl for t in ww]) if lens.size else np.zeros(0, np.float32), np.float32)
+            avg_lens = np.array([0 if a is None else a.shape[0] for a in avgs], np.int32)
+            some = [a.reshape(-1) for a in avgs if a is not None]
+            avg_feats = np.ascontiguousarray(np.concatenate(some), np.float32) if some else None
+            thr = np.array([nan if w[2] is None else w[2] for w in wakewords], np.float32)
+            athr = np.array([nan if w[3] is None else w[3] for w in wakewords], np.float32)
+            r = self._L.rp_wakeword_bank_new(ctx._h, W, K, counts.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), feats.ctypes.data_as(fp),
+                                             avg_lens.ctypes.data_as(i32p), None if avg_feats is None else avg_feats.ctypes.data_as(fp),
+                                             thr.ctypes.data_as(fp), athr.ctypes.data_as(fp), C.byref(self._h))
+        if r < 0:
+            self._h = None
+            raise _err()
+        self.W = W
+        self.max_lens = [int(self._L.rp_wakeword_bank_max_len(self._h, w)) for w in range(W)]   # window length of every wakeword
+        self.max_len = int(self._L.rp_wakeword_bank_max_len(self._h, -1))
+
+    def n_win(self, n_frames, stream_wakeword):
+        """windows each stream of a call has: n_frames - max_len(its wakeword) + 1, 0 without a wakeword"""
+        return [max(0, n_frames - self.max_lens[w] + 1) if w >= 0 else 0 for w in stream_wakeword]
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.rp_wakeword_bank_free(self._h)
             self._h = None
 
 
@@ -781,7 +844,7 @@ class BatchContext:
         return int(v.value)
 
     DTW_KERNELS = {1: "dtw_mfma_kernel", 2: "dtw_mfma_wide_kernel", 4: "dtw_ragged_kernel", 8: "register kernels", 16: "dtw_generic_kernel",
-                   32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel"}
+                   32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel", 4096: "dtw_bank_kernel"}
     DTW_PRODUCTS = {256: "bf16x3", 512: "f16x2"}
     DTW_MFMA_WAVES = {1024: 8, 2048: 12}
 
@@ -988,6 +1051,64 @@ class BatchContext:
         if r < 0:
             raise _err()
         return (det, n_det, scores, agg) if want_scores else (det, n_det)
+
+    def dtw_scores_bank(self, mfcc, bank, stream_wakeword, score_ref=0.22, band_size=5, score_mode=ScoreMode.Max, with_avg=False, win_pitch=None):
+        """rp_dtw_score_bank: stream s against bank wakeword stream_wakeword[s] (-1: none) -> (avg or None, agg), rows of win_pitch
+        floats (default: the largest window count of the call): the stream's windows, zeros behind them."""
+        import numpy as np
+        assert self.host
+        mfcc = np.ascontiguousarray(mfcc, np.float32)
+        if mfcc.ndim == 2:
+            mfcc = mfcc[None]
+        S, nf, _ = mfcc.shape
+        idx = np.ascontiguousarray(stream_wakeword, np.int32)
+        assert idx.shape == (S,)
+        if win_pitch is None:
+            win_pitch = max([0] + [max(0, nf - bank.max_lens[w] + 1) for w in idx if 0 <= w < bank.W])
+        agg = np.empty((S, win_pitch), np.float32)
+        avg = np.empty((S, win_pitch), np.float32) if with_avg else None
+        r = self._L.rp_dtw_score_bank(self._h, mfcc.ctypes.data, S, nf, bank._h, idx.ctypes.data, score_ref, band_size, int(score_mode),
+                                      1 if with_avg else 0, None if avg is None else avg.ctypes.data, agg.ctypes.data, win_pitch)
+        if r < 0:
+            raise _err()
+        return avg, agg
+
+    def batch_detect_bank(self, pcm, bank, stream_wakeword, detector_config, max_det=8, want_agg=False, win_pitch=None):
+        """rp_batch_detect_bank: the whole path with stream s carrying bank wakeword stream_wakeword[s] (-1: none) -> (det, n_det), with
+        want_agg also (agg, avg) as rows of win_pitch floats (see dtw_scores_bank)."""
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        nf = mfcc_num_frames(N)
+        idx = np.ascontiguousarray(stream_wakeword, np.int32)
+        assert idx.shape == (S,)
+        det = np.zeros((S, max_det), dtype=DET_DTYPE)
+        n_det = np.zeros(S, np.int32)
+        agg = avg = None
+        if want_agg:
+            if win_pitch is None:
+                win_pitch = max([0] + [max(0, nf - bank.max_lens[w] + 1) for w in idx if 0 <= w < bank.W])
+            agg = np.empty((S, win_pitch), np.float32)
+            avg = np.empty((S, win_pitch), np.float32)
+        c = detector_config._c()
+        r = self._L.rp_batch_detect_bank(self._h, pcm.ctypes.data, fmt, S, N, N, bank._h, idx.ctypes.data, C.byref(c), det.ctypes.data,
+                                         n_det.ctypes.data, max_det, None if agg is None else agg.ctypes.data,
+                                         None if avg is None else avg.ctypes.data, win_pitch or 0)
+        if r < 0:
+            raise _err()
+        return (det, n_det, agg, avg) if want_agg else (det, n_det)
+
+    def batch_detect_bank_dev(self, pcm_ptr, fmt, S, N, stride, bank, idx_ptr, detector_config, det_ptr, n_det_ptr, max_det):
+        """device pointers, detect-only (tools/bench_bank.py)"""
+        c = detector_config._c()
+        if self._L.rp_batch_detect_bank(self._h, pcm_ptr, fmt, S, N, stride, bank._h, idx_ptr, C.byref(c), det_ptr, n_det_ptr, max_det, None, None, 0) < 0:
+            raise _err()
 
     def resample(self, pcm, sample_rate, channels=1):
         """pcm [S][n_samples*channels] (i8 / i16 / i32 / f32, interleaved) at sample_rate -> [S][n_out] f32 at 16 kHz."""

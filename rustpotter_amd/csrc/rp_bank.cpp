@@ -1,0 +1,336 @@
+// rp_bank.cpp -- wakeword banks: W personal wakeword references resident on the device and the calls that score every stream against
+// ITS wakeword (rp_wakeword_bank_*, rp_dtw_score_bank, rp_batch_detect_bank; kernels: rp_dtw_bank.hip, scan_bank_kernel in rp_scan.hip).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "rp_capi.h"
+
+using namespace rp;
+
+namespace rp {
+
+Bank::~Bank() {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipFree(dev.ww); (void)hipFree(dev.tlen); (void)hipFree(dev.trow); (void)hipFree(dev.unit); (void)hipFree(dev.raw);
+}
+
+template <class T> static bool upload(T **dst, const std::vector<T> &v, const char *what) {
+    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);   // an empty bank still owns valid pointers
+    if (!hip_ok(hipMalloc(reinterpret_cast<void **>(dst), bytes), what)) return false;
+    return v.empty() || hip_ok(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), what);
+}
+
+Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32_t *lens, const float *feats, const int32_t *avg_lens,
+                   const float *avg_feats, const float *thresholds, const float *avg_thresholds) {
+    if (K < 1) { set_last_error("mfcc_size must be >= 1"); return nullptr; }
+    if (W > 0x7fffffffULL) { set_last_error("too many wakewords"); return nullptr; }
+    auto fail = [](size_t w, const std::string &why) { set_last_error("wakeword " + std::to_string(w) + ": " + why); return nullptr; };
+    std::unique_ptr<Bank> bk(new Bank());
+    BankDev &d = bk->dev;
+    d.W = (int)W; d.K = K;
+    size_t n_templates = 0, n_rows = 0, n_avg = 0, n_avg_rows = 0;
+    for (size_t w = 0; w < W; ++w) {
+        if (counts[w] < 1) return fail(w, "Can not create an empty wakeword");   // wakeword_ref.rs:53
+        if (counts[w] > kBankMaxTemplates) return fail(w, std::to_string(counts[w]) + " templates; a bank takes at most " + std::to_string(kBankMaxTemplates) + " per wakeword");
+        for (int32_t t = 0; t < counts[w]; ++t) {
+            if (lens[n_templates + t] < 1) return fail(w, "wakeword template without frames");
+            n_rows += (size_t)lens[n_templates + t];
+        }
+        n_templates += (size_t)counts[w];
+        if (avg_lens && avg_lens[w] < 0) return fail(w, "negative avg_lens");
+        if (avg_lens && avg_lens[w] > 0) { ++n_avg; n_avg_rows += (size_t)avg_lens[w]; }
+    }
+    if (n_avg && !avg_feats) { set_last_error("null argument"); return nullptr; }
+    if (n_templates + n_avg > 0x7fffffffULL) { set_last_error("too many templates"); return nullptr; }
+    // entries: the sample templates wakeword after wakeword, then the averaged templates; rows in the same order
+    std::vector<int> tlen(n_templates + n_avg);
+    std::vector<long long> trow(n_templates + n_avg);
+    std::vector<float> unit((n_rows + n_avg_rows) * (size_t)K), raw((n_rows + n_avg_rows) * (size_t)K);
+    bk->ww.resize(W);
+    // Template rows are scaled to unit L2 norm in f64 and rounded once to f32, an all-zero row stays zero: exactly Templates::create, so that a
+    // wakeword in a bank and the same wakeword as rp_templates give the same bits
+    auto put_rows = [&](const float *src, int L, size_t row0, bool *ref_only) -> bool {
+        for (int r = 0; r < L; ++r) {
+            double nn = 0.0;
+            float nf = 0.f;
+            for (int k = 0; k < K; ++k) {
+                const float v = src[(size_t)r * K + k];
+                if (!std::isfinite(v)) return false;
+                nn += (double)v * (double)v;
+            }
+            for (int k = 0; k < K; ++k) nf += src[(size_t)r * K + k] * src[(size_t)r * K + k];
+            const double inv = (nf > 0.f && nn > 0.0) ? 1.0 / std::sqrt(nn) : 0.0;
+            for (int k = 0; k < K; ++k) {
+                unit[(row0 + r) * K + k] = (float)((double)src[(size_t)r * K + k] * inv);
+                raw[(row0 + r) * K + k] = src[(size_t)r * K + k];
+            }
+            if (!(nf == 0.f || (nf >= kDtwNormLo && nf <= kDtwNormHiRow))) *ref_only = true;   // TemplatesDev::ref_only
+        }
+        return true;
+    };
+    size_t e = 0, row = 0, avg_e = n_templates, avg_row = n_rows, avg_src = 0;
+    d.max_len = 0; d.min_len = 0;
+    for (size_t w = 0; w < W; ++w) {
+        BankWakeword &bw = bk->ww[w];
+        bw.first = (int)e; bw.count = counts[w]; bw.max_len = 0; bw.avg = -1; bw.ref_only = 0; bw.pad = 0;
+        bw.threshold = thresholds ? thresholds[w] : NAN;
+        bw.avg_threshold = avg_thresholds ? avg_thresholds[w] : NAN;
+        bool ref_only = false;
+        for (int32_t t = 0; t < counts[w]; ++t, ++e) {
+            const int L = lens[e];
+            tlen[e] = L; trow[e] = (long long)row;
+            if (!put_rows(feats + row * K, L, row, &ref_only)) return fail(w, "template features must be finite");
+            row += (size_t)L;
+            bw.max_len = std::max(bw.max_len, L);
+        }
+        const int al = avg_lens ? avg_lens[w] : 0;
+        if (al > 0) {
+            // dtw.rs:64-67 widens the band to |m - n| for an averaged template longer than the window; the reference's builder never makes one
+            // (the average has the first sample's length) and dtw_bank_kernel is built for m == n only
+            if (al > bw.max_len) return fail(w, "averaged template of " + std::to_string(al) + " frames is longer than the longest sample template (" +
+                                                    std::to_string(bw.max_len) + " frames): a bank takes averaged templates up to the window length");
+            tlen[avg_e] = al; trow[avg_e] = (long long)avg_row;
+            if (!put_rows(avg_feats + avg_src * K, al, avg_row, &ref_only)) return fail(w, "template features must be finite");
+            bw.avg = (int)avg_e;
+            ++avg_e; avg_row += (size_t)al; avg_src += (size_t)al;
+        }
+        bw.ref_only = ref_only ? 1 : 0;
+        if (dtw_bank_lds_bytes(K, bw.max_len) > 160 * 1024) {
+            const size_t fixed = ((size_t)kBankMaxTemplates * 64 + 13 * 64) * sizeof(float);
+            const size_t lim = (160 * 1024 - fixed) / ((size_t)(K | 1) * sizeof(float)) - 70;
+            return fail(w, "wakeword template of " + std::to_string(bw.max_len) + " frames is too long for the device kernels (limit " + std::to_string(lim) +
+                               " frames at mfcc_size " + std::to_string(K) + ")");
+        }
+        d.max_len = std::max(d.max_len, bw.max_len);
+        d.min_len = w == 0 ? bw.max_len : std::min(d.min_len, bw.max_len);
+    }
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return nullptr;
+    bk->ctx = ctx;   // from here on the destructor frees what was allocated
+    if (!upload(&d.ww, bk->ww, "hipMalloc(bank)") || !upload(&d.tlen, tlen, "hipMalloc(bank)") || !upload(&d.trow, trow, "hipMalloc(bank)") ||
+        !upload(&d.unit, unit, "hipMalloc(bank templates)") || !upload(&d.raw, raw, "hipMalloc(bank templates)")) return nullptr;
+    return bk.release();
+}
+
+}  // namespace rp
+
+namespace {
+
+// The per-stream indices of a call: with host arrays every index is checked before anything is launched and the largest window count a
+// stream of the call has is known; with device arrays the kernels treat an index outside [0, W) as "no wakeword" and win_pitch must hold the
+// bank's largest window count.  Returns the device pointer (null on error, *ok false).
+const int32_t *stage_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok) {
+    *ok = false;
+    const BankDev &d = bk.dev;
+    auto n_win_of = [&](int len) { return n_frames >= (size_t)len ? n_frames - (size_t)len + 1 : (size_t)0; };
+    *max_n_win = 0;
+    if (!sg.host) {
+        if (d.W > 0) *max_n_win = n_win_of(d.min_len);
+        *ok = true;
+        return idx;
+    }
+    for (size_t s = 0; s < S; ++s) {
+        if (idx[s] < -1 || idx[s] >= d.W) {
+            set_last_error("stream " + std::to_string(s) + ": wakeword index " + std::to_string(idx[s]) + " is outside the bank (-1 .. " + std::to_string(d.W - 1) + ")");
+            return nullptr;
+        }
+        if (idx[s] >= 0) *max_n_win = std::max(*max_n_win, n_win_of(bk.ww[(size_t)idx[s]].max_len));
+    }
+    if (S == 0) { *ok = true; return nullptr; }
+    const void *p = sg.in(idx, S * sizeof(int32_t), c->ws_bank_idx);
+    if (!p) return nullptr;
+    *ok = true;
+    return static_cast<const int32_t *>(p);
+}
+
+bool band_ok(const BankDev &d, int band_size) {
+    if (band_size < 0) { set_last_error("band_size must be >= 0"); return false; }
+    if (band_size != 0 && dtw_register_tile(d.K, band_size) <= 0) {
+        set_last_error("wakeword bank: mfcc_size " + std::to_string(d.K) + " with band_size " + std::to_string(band_size) +
+                       " is not built (dtw_bank_kernel takes mfcc_size 5, 13 or 16 with band_size 3..6, or band_size 0)");
+        return false;
+    }
+    return true;
+}
+
+bool pitch_ok(size_t win_pitch, size_t max_n_win) {
+    if (win_pitch < max_n_win) {
+        set_last_error("win_pitch " + std::to_string(win_pitch) + " is smaller than the largest window count of the call (" + std::to_string(max_n_win) + ")");
+        return false;
+    }
+    return true;
+}
+
+// the timed launch (kernel 1 of rp_ctx_timing_read); band_size 0: no cell lies in the band and every score is 0 (dtw.rs:64-75)
+bool score_bank(Ctx *c, const Bank &bk, BankScore &q) {
+    if (q.S == 0 || q.win_pitch == 0) return true;
+    if (q.band == 0) {
+        if (!hip_ok(hipMemsetAsync(q.agg, 0, q.S * q.win_pitch * sizeof(float), c->stream), "hipMemsetAsync")) return false;
+        return !q.avg || hip_ok(hipMemsetAsync(q.avg, 0, q.S * q.win_pitch * sizeof(float), c->stream), "hipMemsetAsync");
+    }
+    const DtwWork wk = c->dtw_work();
+    q.fix = wk.fix;
+    dtw_mark(wk, kDtwRanBank);
+    return timed(c, kKernelDtw, "dtw_bank_kernel", [&] { return launch_dtw_bank(c->stream, bk.dev, q); });
+}
+
+int bank_from(rp_ctx *ctx, std::unique_ptr<Bank> b, rp_wakeword_bank **out) {
+    (void)ctx;
+    if (!b) return -1;
+    rp_wakeword_bank *h = new rp_wakeword_bank();
+    h->impl = std::move(b);
+    *out = h;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+static_assert(RP_DTW_KERNEL_BANK == (int)kDtwRanBank && RP_WAKEWORD_BANK_MAX_TEMPLATES == kBankMaxTemplates, "rustpotter_hip.h mirrors rp_kernels.h");
+
+int rp_wakeword_bank_new(rp_ctx *ctx, size_t n_wakewords, int mfcc_size, const int32_t *counts, const int32_t *lens, const float *feats,
+                         const int32_t *avg_lens, const float *avg_feats, const float *thresholds, const float *avg_thresholds,
+                         rp_wakeword_bank **out) {
+    return guarded([&]() -> int {
+        if (!ctx || !out) { set_last_error("null argument"); return -1; }
+        *out = nullptr;
+        if (n_wakewords && (!counts || !lens || !feats)) { set_last_error("null argument"); return -1; }
+        return bank_from(ctx, std::unique_ptr<Bank>(Bank::create(ctx->impl.get(), n_wakewords, mfcc_size, counts, lens, feats, avg_lens, avg_feats,
+                                                                 thresholds, avg_thresholds)), out);
+    });
+}
+
+int rp_wakeword_bank_new_from_rpw(rp_ctx *ctx, size_t n_wakewords, const uint8_t *const *rpw_buffers, const size_t *rpw_lens,
+                                  rp_wakeword_bank **out) {
+    return guarded([&]() -> int {
+        if (!ctx || !out) { set_last_error("null argument"); return -1; }
+        *out = nullptr;
+        if (n_wakewords && (!rpw_buffers || !rpw_lens)) { set_last_error("null argument"); return -1; }
+        std::vector<int32_t> counts, lens, avg_lens;
+        std::vector<float> feats, avg_feats, thr, athr;
+        int K = 0;
+        for (size_t w = 0; w < n_wakewords; ++w) {
+            auto fail = [&](const std::string &why) { set_last_error("wakeword " + std::to_string(w) + ": " + why); return -1; };
+            if (!rpw_buffers[w]) return fail("null buffer");
+            RpwKind kind;
+            WakewordRefData ref;
+            WakewordModelData model;
+            std::string err;
+            if (!parse_rpw(rpw_buffers[w], rpw_lens[w], &kind, &ref, &model, &err)) return fail(err);
+            if (kind != RpwKind::Ref) return fail("a wakeword model cannot be part of a bank (wakeword references only)");
+            if (w == 0) K = ref.mfcc_size;
+            else if (ref.mfcc_size != K) return fail("Usage of wakewords with different mfcc size is not supported, ignoring wakeword");
+            counts.push_back((int32_t)ref.lens.size());
+            for (size_t t = 0; t < ref.lens.size(); ++t) {
+                lens.push_back(ref.lens[t]);
+                feats.insert(feats.end(), ref.feats[t].begin(), ref.feats[t].end());
+            }
+            avg_lens.push_back(ref.has_avg ? ref.avg_len : 0);
+            if (ref.has_avg) avg_feats.insert(avg_feats.end(), ref.avg.begin(), ref.avg.end());
+            thr.push_back(ref.has_threshold ? ref.threshold : NAN);
+            athr.push_back(ref.has_avg_threshold ? ref.avg_threshold : NAN);
+        }
+        if (n_wakewords == 0) K = 1;
+        return bank_from(ctx, std::unique_ptr<Bank>(Bank::create(ctx->impl.get(), n_wakewords, K, counts.data(), lens.data(), feats.data(), avg_lens.data(),
+                                                                 avg_feats.data(), thr.data(), athr.data())), out);
+    });
+}
+
+void rp_wakeword_bank_free(rp_wakeword_bank *bank) { delete bank; }
+
+int rp_wakeword_bank_max_len(const rp_wakeword_bank *bank, long long wakeword) {
+    if (!bank) { set_last_error("null handle"); return -1; }
+    const Bank &b = *bank->impl;
+    if (wakeword < 0) return b.dev.max_len;
+    if (wakeword >= (long long)b.dev.W) { set_last_error("wakeword index outside the bank"); return -1; }
+    return b.ww[(size_t)wakeword].max_len;
+}
+
+int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames, const rp_wakeword_bank *bank, const int32_t *stream_wakeword,
+                      float score_ref, int band_size, rp_score_mode score_mode, int with_avg, float *avg, float *agg, size_t win_pitch) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (S && (!mfcc || !stream_wakeword || !agg)) { set_last_error("null argument"); return -1; }
+        Ctx *c = ctx->impl.get();
+        const Bank &bk = *bank->impl;
+        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (!band_ok(bk.dev, band_size)) return -1;
+        Staged sg(c);
+        size_t max_n_win = 0;
+        bool ok = false;
+        const int32_t *di = stage_indices(c, sg, bk, stream_wakeword, S, n_frames, &max_n_win, &ok);
+        if (!ok || !pitch_ok(win_pitch, max_n_win)) return -1;
+        if (S == 0 || win_pitch == 0) return 0;
+        const size_t out_bytes = S * win_pitch * sizeof(float);
+        BankScore q;
+        q.mfcc = static_cast<const float *>(sg.in(mfcc, S * n_frames * bk.dev.K * sizeof(float), c->stage_in));
+        q.agg = static_cast<float *>(sg.out(agg, out_bytes, c->stage_out3));
+        q.avg = avg ? static_cast<float *>(sg.out(avg, out_bytes, c->stage_out2)) : nullptr;
+        if ((n_frames && !q.mfcc) || !q.agg || (avg && !q.avg)) return -1;
+        q.S = S; q.n_frames = n_frames; q.win_pitch = win_pitch; q.stream_wakeword = di; q.band = band_size; q.score_mode = (int)score_mode;
+        q.score_ref = score_ref; q.avg_mode = with_avg ? 1 : 0;
+        if (!score_bank(c, bk, q)) return -1;
+        return sg.back(agg, q.agg, out_bytes) && sg.back(avg, q.avg, out_bytes) && sg.finish() ? 0 : -1;
+    });
+}
+
+int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                         const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config,
+                         rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, float *avg, size_t win_pitch) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (!config || (S && (!pcm || !stream_wakeword || !det || !n_det))) { set_last_error("null argument"); return -1; }
+        Ctx *c = ctx->impl.get();
+        const Bank &bk = *bank->impl;
+        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (!band_ok(bk.dev, (int)config->band_size)) return -1;
+        Staged sg(c);
+        const size_t nf = rp_mfcc_num_frames(n_samples);
+        size_t max_n_win = 0;
+        bool ok = false;
+        const int32_t *di = stage_indices(c, sg, bk, stream_wakeword, S, nf, &max_n_win, &ok);
+        if (!ok) return -1;
+        const bool wants = agg || avg;
+        if (wants && !pitch_ok(win_pitch, max_n_win)) return -1;
+        const size_t pitch = wants ? win_pitch : std::max<size_t>(max_n_win, 1);   // the call's own rows when nothing is handed out
+        DetectFront f;
+        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, bk.dev.K, std::max(bk.dev.min_len, 1), det, n_det, max_det, &f)) return -1;
+        // caller-provided arrays are used directly when they are device pointers
+        const size_t out_bytes = S * pitch * sizeof(float);
+        float *dg = (agg && !sg.host) ? agg : nullptr, *da = (avg && !sg.host) ? avg : nullptr;
+        if (!dg) { if (!c->ws_agg.reserve(out_bytes + 16)) return -1; dg = c->ws_agg.as<float>(); }
+        if (!da) { if (!c->ws_avg.reserve(out_bytes + 16)) return -1; da = c->ws_avg.as<float>(); }
+        uint32_t *hot = nullptr;
+        if (S && pitch) {
+            BankScore q;
+            q.mfcc = f.dm; q.S = S; q.n_frames = nf; q.win_pitch = pitch; q.stream_wakeword = di; q.band = (int)config->band_size;
+            q.score_mode = (int)config->score_mode; q.score_ref = config->score_ref; q.avg_mode = 2;
+            q.gate = (!wants && !(c->flags & RP_CTX_FULL_SCORES)) ? 1 : 0;   // detect-only
+            q.threshold = config->threshold; q.avg_threshold = config->avg_threshold;
+            q.agg = dg; q.avg = da;
+            q.hot = hot = c->hot_flags(S);   // zero: the scan below puts every flag it reads back
+            if (!hot) return -1;
+            if (!score_bank(c, bk, q)) return -1;
+        }
+        float *dv = nullptr;
+        if (config->vad_mode != RP_VAD_NONE) {
+            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
+            dv = c->ws_vad.as<float>();
+            if (!hip_ok(launch_vad_value(c->stream, f.dm, S * nf, bk.dev.K, dv), "vad_value_kernel")) return -1;
+        }
+        const ScanConfig sc = scan_config(*config, 0, true);   // window length, thresholds and the avg test come from the bank, per stream
+        if (!timed(c, kKernelScan, "scan_bank_kernel", [&] {
+                return launch_scan_bank(c->stream, bk.dev, di, dg, da, pitch, dv, vad_mode_value(config->vad_mode), S, nf, sc, f.dd, f.dn, max_det, hot);
+            })) return -1;
+        if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
+        if (sg.host && agg && !sg.back(agg, dg, out_bytes)) return -1;
+        if (sg.host && avg && !sg.back(avg, da, out_bytes)) return -1;
+        return sg.finish() ? 0 : -1;
+    });
+}
+
+}  // extern "C"

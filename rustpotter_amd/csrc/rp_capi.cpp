@@ -214,16 +214,6 @@ size_t rp_mfcc_num_frames(size_t n_samples) {
     return chunks >= 1 ? 3 * chunks - 3 : 0;
 }
 
-namespace {
-// whole-stream detection after detect_front: device det / n_det, the MFCC frames ws_mfcc [S][nf][K], windows per stream
-struct DetectFront {
-    BatchDetection *dd = nullptr;
-    int32_t *dn = nullptr;
-    float *dm = nullptr;
-    size_t nf = 0, n_win = 0, rows = 0;
-};
-}  // namespace
-
 // whole streams of n_samples samples, pcm_stride apart
 static bool pcm_args_ok(rp_sample_format fmt, size_t n_samples, size_t pcm_stride) {
     if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return false; }
@@ -237,8 +227,9 @@ static int widest_layer(const Model &m) {
 
 // The front of whole-stream detection: checks the PCM arguments, stages the PCM in and det / n_det out and writes the MFCC frames of
 // every stream to ws_mfcc (timed).  Windows are max_len frames long.
-static bool detect_front(Ctx *c, Staged &sg, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, int K,
-                         int max_len, rp_batch_detection *det, int32_t *n_det, int max_det, DetectFront *f) {
+// (DetectFront: rp_capi.h -- rp_bank.cpp shares this front)
+extern "C++" bool rp::detect_front(Ctx *c, Staged &sg, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, int K,
+                                   int max_len, rp_batch_detection *det, int32_t *n_det, int max_det, DetectFront *f) {
     if (!pcm_args_ok(fmt, n_samples, pcm_stride)) return false;
     const MfccTablesDev *tb = c->tables_for(K);
     if (!tb) return false;

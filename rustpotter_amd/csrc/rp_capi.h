@@ -7,6 +7,7 @@
 struct rp_ctx { std::unique_ptr<rp::Ctx> impl; };
 struct rp_templates { std::unique_ptr<rp::Templates> impl; };
 struct rp_model { std::unique_ptr<rp::Model> impl; };
+struct rp_wakeword_bank { std::unique_ptr<rp::Bank> impl; };
 
 namespace rp {
 
@@ -74,6 +75,15 @@ inline ScanConfig scan_config(const rp_detector_config &cfg, int max_len, bool a
 }
 
 // rp_capi.cpp
+// whole-stream detection after detect_front: device det / n_det, the MFCC frames ws_mfcc [S][nf][K], windows per stream
+struct DetectFront {
+    BatchDetection *dd = nullptr;
+    int32_t *dn = nullptr;
+    float *dm = nullptr;
+    size_t nf = 0, n_win = 0, rows = 0;
+};
+bool detect_front(Ctx *c, Staged &sg, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, int K,
+                  int max_len, rp_batch_detection *det, int32_t *n_det, int max_det, DetectFront *f);
 bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch, size_t n_win, int L, int K, int precision,
                    float *dlog, DevBuf &mean, DevBuf &xrows, DevBuf &scratch, bool live);
 void band_pass_coefficients(const rp_band_pass_config &b, float q[5]);

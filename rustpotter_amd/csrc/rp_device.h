@@ -241,6 +241,27 @@ __device__ __forceinline__ void dtw_fix_append(uint32_t *fix, size_t row, uint32
 // The reference's score of a DTW cost nc = cost / (m + n): MfccComparator::compute_probability, src/mfcc/comparator.rs:25.
 __device__ __forceinline__ float dtw_logistic(float nc, float score_ref) { return 1.f / (1.f + expf((nc - score_ref) / score_ref)); }
 
+// get_percentile of src/wakewords/comp/wakeword_comp.rs:38-49 over n ascending values `stride` floats apart (1: a plain array; 64: a
+// lane's column of a lane-minor LDS block), and the percentile a rp_score_mode stands for (:108-139).
+__device__ inline float percentile_sorted(const float *v, int n, float percentile, int stride = 1) {
+    float index = percentile / 100.0f * (float)(n - 1);
+    float fl = floorf(index);
+    if (fl == index) return v[(int)index * stride];
+    int i = (int)fl;
+    float d = index - fl;
+    return v[i * stride] * (1.0f - d) + v[(i + 1) * stride] * d;
+}
+__device__ __forceinline__ float percentile_of_mode(int mode) {
+    switch (mode) {
+    case 3: return 25.f;
+    case 5: return 75.f;
+    case 6: return 80.f;
+    case 7: return 90.f;
+    case 8: return 95.f;
+    default: return 50.f;  // Median, P50
+    }
+}
+
 // ---- the frame of the matrix-core DTW kernels (dtw_mfma_kernel, dtw_mfma_wide_kernel, dtw_mfma_wide3_kernel) around their column pipelines.
 // Every helper takes the values the kernel already holds (tid, lane, wave, ...): recomputed from threadIdx inside, they change the kernel's code.
 

@@ -1404,14 +1404,7 @@ hipError_t launch_dtw_single_part(hipStream_t st, const DtwWork &wk, const Templ
 
 // -------------------------------------------------------------------- aggregate
 // src/wakewords/comp/wakeword_comp.rs:38-49 (get_percentile) and :108-139
-__device__ inline float percentile_sorted(const float *v, int n, float percentile) {
-    float index = percentile / 100.0f * (float)(n - 1);
-    float fl = floorf(index);
-    if (fl == index) return v[(int)index];
-    int i = (int)fl;
-    float d = index - fl;
-    return v[i] * (1.0f - d) + v[i + 1] * d;
-}
+// (percentile_sorted and percentile_of_mode: rp_device.h, shared with dtw_bank_kernel)
 
 constexpr int kAggMaxT = 256;
 
@@ -1477,17 +1470,6 @@ template <int NT> __device__ __forceinline__ void bitonic_sort(float (&v)[NT]) {
                     v[l] = up ? hi : lo;
                 }
             }
-}
-
-__device__ __forceinline__ float percentile_of_mode(int mode) {
-    switch (mode) {
-    case 3: return 25.f;
-    case 5: return 75.f;
-    case 6: return 80.f;
-    case 7: return 90.f;
-    case 8: return 95.f;
-    default: return 50.f;  // Median, P50
-    }
 }
 
 template <int NT>

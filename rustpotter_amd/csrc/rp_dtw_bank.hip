@@ -1,0 +1,273 @@
+// rp_dtw_bank.hip -- dtw_bank_kernel: window scoring where stream s carries its OWN wakeword, bank[stream_wakeword[s]] -- the batched form of
+// one `Rustpotter` per thread, each holding one personal wakeword (src/detector.rs:304-346; scoring as rp_dtw.hip: src/mfcc/dtw.rs:56-105 +
+// comparator.rs + normalizer.rs + wakeword_comp.rs:22-27,77-139).  DESIGN.md §4.2c.
+#include "rp_device.h"
+
+namespace rp {
+
+// One DTW of the lane's window against one template of L rows (m == n == L: the window is cut to the template's length keeping the oldest
+// frames), with the arithmetic of the register kernels of rp_dtw.hip OPERATION FOR OPERATION -- sequential column sums / L, unit-length frame by
+// rsqrtf of the fma-chained squared norm, d = fmaf(-a[k], y[k], d) chained from 1, v = d + min3, cost / (m + n), dtw_logistic -- so that a
+// window gets the bits it gets from dtw_band_kernel / dtw_band2_kernel / dtw_band_wide_kernel.  The form is dtw_band_wide_kernel's with one
+// template: the ring of the 2W unit-length frames inside the band as register pairs, two band cells per packed FMA, the template row a
+// wave-uniform read (scalar loads), rows unrolled 2W at a time so that every ring slot and band index is a compile-time register.
+// chk: max over the frames loaded of (squared norm, its reciprocal square root) -- the norm-range test of those kernels, same columns.
+template <int K, int W, int KP>
+__device__ __forceinline__ float bank_dtw(const float *xl, int L, const float *__restrict__ rows, float score_ref, float &chk_out) {
+    constexpr int B = 2 * W;
+    constexpr int MEAN_UNROLL = K <= 5 ? 10 : 4;   // frames in flight per wait, as the register kernels
+    // MfccNormalizer::normalize, src/mfcc/normalizer.rs:17-29: sequential column sums
+    float mu[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) mu[k] = 0.f;
+#pragma unroll MEAN_UNROLL
+    for (int i = 0; i < L; ++i) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) mu[k] += xl[i * KP + k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) mu[k] = mu[k] / (float)L;
+
+    v2f ring[B / 2][K];  // ring[j][k] = { y_slot(2j)[k], y_slot(2j+1)[k] }
+#pragma unroll
+    for (int j = 0; j < B / 2; ++j)
+#pragma unroll
+        for (int k = 0; k < K; ++k) ring[j][k] = (v2f){0.f, 0.f};
+
+    float chk = 0.f;
+#define RP_LOAD_COL(c, slot)                                                              \
+    do {                                                                                  \
+        float y_[K], bb_ = 0.f;                                                           \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
+            y_[k] = xl[((c)-1) * KP + k] - mu[k];                                         \
+            bb_ = fmaf(y_[k], y_[k], bb_);                                                \
+        }                                                                                 \
+        const float inv_ = bb_ > 0.f ? rsqrtf(bb_) : 0.f;                                 \
+        chk = fmaxf(fmaxf(chk, inv_), bb_);                                               \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
+            if (((slot)&1) == 0) ring[(slot) / 2][k].x = y_[k] * inv_;                    \
+            else ring[(slot) / 2][k].y = y_[k] * inv_;                                    \
+        }                                                                                 \
+    } while (0)
+
+#pragma unroll
+    for (int c = 1; c < W; ++c) RP_LOAD_COL(c, c % B);
+
+    // P[q] = D[r-1][(r-1-W)+q]; row 0 has D[0][0] = 0 at q = W
+    float P[B + 1];
+#pragma unroll
+    for (int q = 0; q <= B; ++q) P[q] = RP_INF;
+    P[W] = 0.f;
+
+    // columns c > n are never read back by an in-range cell and stay unguarded, as in the register kernels (the stage holds W frames of slack)
+#define RP_ROWS(GUARD)                                                                                 \
+    _Pragma("unroll") for (int u = 0; u < B; ++u) {                                                    \
+        const int r = r0 + u;                                                                          \
+        if (r < L) { /* rows 1..m-1 only: row m is never read (dtw.rs:101) */                          \
+            RP_LOAD_COL(r + W - 1, (u + W) % B);                                                       \
+            const float *arow = rows + (size_t)(r - 1) * K;                                            \
+            v2f dd[B / 2];                                                                             \
+            _Pragma("unroll") for (int j = 0; j < B / 2; ++j) dd[j] = (v2f){1.f, 1.f};                 \
+            _Pragma("unroll") for (int k = 0; k < K; ++k) {                                            \
+                const v2f a2 = (v2f){arow[k], arow[k]};                                                \
+                _Pragma("unroll") for (int j = 0; j < B / 2; ++j)                                      \
+                    dd[j] = __builtin_elementwise_fma(-a2, ring[j][k], dd[j]);                         \
+            }                                                                                          \
+            float left = RP_INF;                                                                       \
+            _Pragma("unroll") for (int q = 0; q < B; ++q) {                                            \
+                const int slot = (1 + u + q + B - W) % B;                                              \
+                const float d = (slot & 1) ? dd[slot / 2].y : dd[slot / 2].x;                          \
+                float v = d + fminf(fminf(P[q + 1], left), P[q]);                                      \
+                if (GUARD) v = (r - W + q >= 1) ? v : RP_INF;                                          \
+                P[q] = v;                                                                              \
+                left = v;                                                                              \
+            }                                                                                          \
+        }                                                                                              \
+    }
+
+    {
+        const int r0 = 1;
+        RP_ROWS(true)
+    }
+    for (int r0 = 1 + B; r0 < L; r0 += B) { RP_ROWS(false) }
+#undef RP_ROWS
+#undef RP_LOAD_COL
+    chk_out = chk;
+    return dtw_logistic(P[W + 1] / (float)(L + L), score_ref);   // D[m-1][n] for m == n
+}
+
+// The same DTW with the reference-shaped cell of dtw_ref_kernel (comparator.rs:28-48: three sequential dot products of the template row AS
+// GIVEN and the mean-normalised frame, one sqrt, one divide), for windows with a frame outside kDtwNormLo..kDtwFixLimit and wakewords with a
+// row outside kDtwNormLo..kDtwNormHiRow.  Band in LDS, lane-minor; the whole wave walks it, the lanes that need it keep the result.
+template <int K, int W, int KP>
+__device__ __noinline__ float bank_dtw_ref(const float *xl, int L, const float *__restrict__ raw, float score_ref, float *Pb, int lane) {
+    constexpr int B = 2 * W;
+    float mu[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) mu[k] = 0.f;
+    for (int i = 0; i < L; ++i) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) mu[k] += xl[i * KP + k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) mu[k] = mu[k] / (float)L;
+    for (int q = 0; q <= B; ++q) Pb[q * 64 + lane] = RP_INF;
+    Pb[W * 64 + lane] = 0.f;
+    for (int r = 1; r < L; ++r) {
+        float left = RP_INF;
+        for (int q = 0; q < B; ++q) {
+            const int c = r - W + q;
+            float v = RP_INF;
+            if (c >= 1 && c <= L) {
+                float dot_ab = 0.f, dot_a = 0.f, dot_b = 0.f;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const float ca = raw[(size_t)(r - 1) * K + k];
+                    const float cb = xl[(c - 1) * KP + k] - mu[k];
+                    dot_ab += ca * cb;   // -ffp-contract=off: a multiply and an add, as the reference
+                    dot_a += ca * ca;
+                    dot_b += cb * cb;
+                }
+                const float magnitude = sqrtf(dot_a * dot_b);
+                const float sim = magnitude == 0.f ? 0.f : dot_ab / magnitude;
+                v = (1.f - sim) + fminf(fminf(Pb[(q + 1) * 64 + lane], left), Pb[q * 64 + lane]);
+            }
+            Pb[q * 64 + lane] = v;
+            left = v;
+        }
+    }
+    return dtw_logistic(Pb[(W + 1) * 64 + lane] / (float)(L + L), score_ref);   // column n of row m-1 sits at band offset W + 1
+}
+
+// One wave = one (stream, tile of 64 consecutive windows); lane = window.  The tile's 64 + max_len + W frames are staged in LDS once; the wave
+// then walks its stream's wakeword: the averaged template first when it is to be scored, then the sample templates, folding the score_mode
+// aggregate as it goes (running max / sum; the percentile modes keep the lane's scores in LDS, lane-minor).  The wakeword index is
+// wave-uniform, so everything read through it -- the wakeword's record, template lengths, template rows -- is a scalar load.
+// Written per stream row of win_pitch floats: agg (and avg) of the windows the stream has, zeros behind them and for streams without a wakeword.
+// (The bank's arrays and the call's are separate __restrict__ parameters, not members of the structs: only then does the compiler know that
+// the kernel's own stores cannot touch them and reads them with scalar loads.)
+template <int K, int W>
+__global__ __launch_bounds__(64) void dtw_bank_kernel(const BankWakeword *__restrict__ bank_ww, const int *__restrict__ bank_tlen,
+                                                      const long long *__restrict__ bank_trow, const float *__restrict__ bank_unit,
+                                                      const float *__restrict__ bank_raw, const float *__restrict__ mfcc,
+                                                      const int32_t *__restrict__ stream_wakeword, float *__restrict__ agg, float *__restrict__ avg,
+                                                      uint32_t *__restrict__ hot, uint32_t *__restrict__ fix, BankDev b, BankScore q, unsigned tiles) {
+    constexpr int KP = (K % 2 == 0) ? K + 1 : K;  // odd pitch: conflict-free lane-strided LDS reads
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *xs = reinterpret_cast<float *>(smem);               // [64 + b.max_len + 6][KP]
+    float *sl = xs + (size_t)(64 + b.max_len + 6) * KP;        // [kBankMaxTemplates][64]: a lane's scores (percentile modes)
+    float *Pb = sl + kBankMaxTemplates * 64;                   // [13][64]: band of the reference-shaped cell
+
+    const unsigned tile = blockIdx.x % tiles;
+    const size_t s = blockIdx.x / tiles;
+    const int lane = threadIdx.x;
+    const size_t wl = (size_t)tile * 64 + lane;
+    float *agg_row = agg + s * q.win_pitch;
+    float *avg_row = avg ? avg + s * q.win_pitch : nullptr;
+    const int wi = stream_wakeword[s];
+    const bool none = wi < 0 || wi >= b.W;   // an index outside the bank is "no wakeword" here (the host checks it where it can see it)
+    const BankWakeword *bw = bank_ww + (none ? 0 : wi);
+    const int max_len = none ? 0 : bw->max_len;
+    const size_t n_win = (!none && q.n_frames >= (size_t)max_len) ? q.n_frames - (size_t)max_len + 1 : 0;
+    if ((size_t)tile * 64 >= n_win) {
+        if (wl < q.win_pitch) {
+            agg_row[wl] = 0.f;
+            if (avg_row) avg_row[wl] = 0.f;
+        }
+        return;
+    }
+    {
+        const int n_stage = 64 + max_len + W;
+        const float *src = mfcc + s * q.n_frames * K;
+        const size_t w0 = (size_t)tile * 64;
+        for (int i = lane; i < n_stage * K; i += 64) {
+            const int f = i / K, k = i - f * K;
+            const size_t g = w0 + f;
+            xs[f * KP + k] = g < q.n_frames ? src[g * K + k] : 0.f;
+        }
+    }
+    __syncthreads();
+    const float *xl = xs + lane * KP;
+    const bool valid = wl < n_win;
+    const float own_thr = bw->threshold, own_athr = bw->avg_threshold;
+    const float thr = own_thr == own_thr ? own_thr : q.threshold;
+    const float athr = own_athr == own_athr ? own_athr : q.avg_threshold;
+    const int avg_e = bw->avg, T = bw->count, first = bw->first, ref_only = bw->ref_only;
+    const bool do_avg = avg_e >= 0 && (q.avg_mode == 1 || (q.avg_mode == 2 && athr != 0.f));   // wakeword_comp.rs:85
+    const int mode = q.score_mode;
+
+    float acc = 0.f, avg_sc = 0.f;
+    bool scored = true;
+    for (int ti = do_avg ? -1 : 0; ti < T; ++ti) {
+        const int e = ti < 0 ? avg_e : first + ti;
+        const int L = bank_tlen[e];
+        const size_t off = (size_t)bank_trow[e] * K;
+        float chk;
+        float sc = bank_dtw<K, W, KP>(xl, L, bank_unit + off, q.score_ref, chk);
+        const bool slow = valid && (ref_only || chk > kDtwFixLimit);
+        const unsigned long long slow_mask = __ballot(slow);
+        if (slow_mask) {   // wave-uniform
+            const float rs = bank_dtw_ref<K, W, KP>(xl, L, bank_raw + off, q.score_ref, Pb, lane);
+            if (slow) sc = rs;
+            if (lane == 0 && fix) atomicAdd(dtw_fix_stats(fix), (unsigned long long)__popcll(slow_mask));   // rp_ctx_dtw_ref_pairs
+        }
+        if (ti < 0) {
+            avg_sc = sc;
+            // the averaged-template gate (wakeword_comp.rs:85-93) at wave granularity, as dtw_generic_kernel: when none of the wave's windows
+            // passed, the sample templates are not compared at all
+            if (q.gate && !__any(valid && !(sc < athr))) { scored = false; break; }
+        } else if (mode == 1) acc = ti == 0 ? sc : fmaxf(acc, sc);   // Max
+        else if (mode == 0) acc += sc;                               // Average: sequential sum in template order
+        else sl[ti * 64 + lane] = sc;
+    }
+    float a = 0.f;
+    if (scored) {
+        if (mode == 1) a = acc;
+        else if (mode == 0) a = acc / (float)T;
+        else {   // Median / percentiles: the lane sorts its column ascending, then the reference's f32 interpolation
+            for (int i = 1; i < T; ++i) {
+                const float x = sl[i * 64 + lane];
+                int j = i - 1;
+                while (j >= 0 && sl[j * 64 + lane] > x) { sl[(j + 1) * 64 + lane] = sl[j * 64 + lane]; --j; }
+                sl[(j + 1) * 64 + lane] = x;
+            }
+            a = percentile_sorted(sl + lane, T, percentile_of_mode(mode), 64);
+        }
+    }
+    // agg_store's rules (rp_dtw.hip): a window the gate rejected was never compared -> aggregate 0; a window that can fire raises the stream's flag
+    const bool gated = q.gate && do_avg && avg_sc < athr;
+    if (gated) a = 0.f;
+    if (wl < q.win_pitch) {
+        agg_row[wl] = valid ? a : 0.f;
+        if (avg_row) avg_row[wl] = (valid && do_avg) ? avg_sc : 0.f;
+    }
+    if (hot && __any(valid && !gated && a > thr) && lane == 0) hot[s] = 1u;
+}
+
+template <int K, int W>
+static hipError_t launch_bank_kw(hipStream_t st, const BankDev &b, const BankScore &q, unsigned blocks, unsigned tiles, size_t lds) {
+    const auto kernel = dtw_bank_kernel<K, W>;
+    if (lds > 64 * 1024)
+        if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), 160 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), lds, st, b.ww, b.tlen, b.trow, b.unit, b.raw, q.mfcc, q.stream_wakeword, q.agg, q.avg, q.hot, q.fix, b, q, tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_dtw_bank(hipStream_t st, const BankDev &b, const BankScore &q) {
+    if (q.S == 0 || q.win_pitch == 0) return hipSuccess;
+    if (dtw_register_tile(b.K, q.band) <= 0) return hipErrorNotSupported;
+    const size_t tiles = (q.win_pitch + 63) / 64, blocks = tiles * q.S;
+    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    const size_t lds = dtw_bank_lds_bytes(b.K, b.max_len);
+    if (lds > 160 * 1024) return hipErrorMemoryAllocation;
+#define RP_BANK(KK, WW) launch_bank_kw<KK, WW>(st, b, q, (unsigned)blocks, (unsigned)tiles, lds)
+#define RP_BANK_BAND(KK) \
+    switch (q.band) { case 3: return RP_BANK(KK, 3); case 4: return RP_BANK(KK, 4); case 5: return RP_BANK(KK, 5); default: return RP_BANK(KK, 6); }
+    if (b.K == 5) { RP_BANK_BAND(5) }
+    if (b.K == 13) { RP_BANK_BAND(13) }
+    RP_BANK_BAND(16)
+#undef RP_BANK_BAND
+#undef RP_BANK
+}
+
+}  // namespace rp

@@ -122,6 +122,7 @@ struct Ctx {
     DevBuf stage_in, stage_out, stage_out2, stage_out3;
     // intermediates of rp_batch_detect
     DevBuf ws_mfcc, ws_scores, ws_agg, ws_avg, ws_vad, ws_ring, ws_rms, ws_gain, ws_list, ws_hot;
+    DevBuf ws_bank_idx;  // the per-stream wakeword indices of a bank call with RP_CTX_HOST_POINTERS
     DevBuf ws_dtw;  // [2 * kDtwSchedChunks | 2 + 2 * kDtwFixCap] uint32: tile counters and fix list of the DTW launchers, zero between calls
     // rp_batch_detect_ingest: copy stream, two device blocks of PCM, per block "copy landed" / "kernels done with it" events
     hipStream_t copy_stream = nullptr;
@@ -173,6 +174,18 @@ struct Templates {
     static Templates *create(Ctx *ctx, int T, int K, const int *lens, const float *feats, int avg_len,
                              const float *avg);
     ~Templates();
+};
+
+// A wakeword bank (rp_bank.cpp): W wakeword references uploaded once, scored per stream through an index (rp_dtw_bank.hip).  Borrows the context.
+struct Bank {
+    Ctx *ctx = nullptr;
+    BankDev dev;
+    std::vector<BankWakeword> ww;   // the host's copy of dev.ww
+    // HOST arrays in the flat layout of rp_mfcc_average_batch: counts [W], lens [sum counts], feats [sum lens][K]; avg_lens [W] (0: none) and
+    // avg_feats [sum avg_lens][K] (both may be null); thresholds / avg_thresholds [W] (null or NaN: none)
+    static Bank *create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32_t *lens, const float *feats, const int32_t *avg_lens,
+                        const float *avg_feats, const float *thresholds, const float *avg_thresholds);
+    ~Bank();
 };
 
 struct Model {

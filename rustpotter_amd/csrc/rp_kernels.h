@@ -243,7 +243,9 @@ enum : uint32_t { kDtwRanMfma = 1u, kDtwRanMfmaWide = 2u, kDtwRanRagged = 4u, kD
                   // the product arithmetic of the matrix-core launches: three bf16 parts (f32-grade) / two f16 parts (22-bit)
                   kDtwRanBf16x3 = 256u, kDtwRanF16x2 = 512u,
                   // waves per workgroup of the dtw_mfma_kernel launches (two / three per SIMD)
-                  kDtwRanWaves8 = 1024u, kDtwRanWaves12 = 2048u };
+                  kDtwRanWaves8 = 1024u, kDtwRanWaves12 = 2048u,
+                  // dtw_bank_kernel (rp_dtw_bank.hip): per-stream wakewords from a bank
+                  kDtwRanBank = 4096u };
 inline void dtw_mark(const DtwWork &wk, uint32_t bit) { if (wk.ran) *wk.ran |= bit; }
 __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { return reinterpret_cast<unsigned long long *>(fix + 2 + 2 * (size_t)kDtwFixCap); }
 // (dtw_fix_append, the kernels' side of the list: rp_device.h)
@@ -327,6 +329,49 @@ size_t dtw_ragged_lds_bytes(const TemplatesDev &t, size_t n_win, int *frames_cap
 // list_rows: windows the kernel cannot score within the parity gate go to wk.rag_list (the caller runs the register kernels' list mode on it);
 // else to wk.fix (dtw_ref_kernel)
 hipError_t launch_dtw_ragged(const DtwCall &c, float abandon_nc, bool list_rows);
+
+// ---- wakeword bank (rp_dtw_bank.hip, rp_bank.cpp): W wakeword references resident on the device, scored per stream through an index.
+// Every template of the bank (the sample templates of wakeword 0, of wakeword 1, ..., then the averaged templates) is one entry of tlen /
+// trow; its rows lie at unit / raw + trow * K (unit: scaled to unit length as in TemplatesDev; raw: as given, for the reference-shaped cell).
+constexpr int kBankMaxTemplates = 32;   // sample templates per wakeword: the LDS block of the percentile modes is [32][64] floats
+struct BankWakeword {
+    int first;        // entry of its first sample template
+    int count;        // sample templates, 1..kBankMaxTemplates
+    int max_len;      // longest sample template = the window length (get_mfcc_frame_size, wakeword_comp.rs:69-75)
+    int avg;          // entry of its averaged template, -1: none
+    int ref_only;     // a row outside kDtwNormLo..kDtwNormHiRow: every window of this wakeword takes the reference-shaped cell
+    float threshold, avg_threshold;   // the wakeword's own Option<f32>: NaN = the value of the call's config
+    int pad;
+};
+struct BankDev {
+    int W = 0, K = 0;
+    int max_len = 0, min_len = 0;     // longest / shortest window length over the wakewords (0 / 0 for an empty bank)
+    BankWakeword *ww = nullptr;       // [W]
+    int *tlen = nullptr;              // [entries]
+    long long *trow = nullptr;        // [entries]
+    float *unit = nullptr, *raw = nullptr;
+};
+// One scoring call of a bank: stream s scores the windows of its own wakeword stream_wakeword[s] (outside [0, W): none).  Outputs are rows of
+// win_pitch floats per stream: the windows the stream has, zeros behind them.
+struct BankScore {
+    const float *mfcc = nullptr;      // [S][n_frames][K]
+    size_t S = 0, n_frames = 0, win_pitch = 0;
+    const int32_t *stream_wakeword = nullptr;
+    int band = 0, score_mode = 0;
+    float score_ref = 0.f;
+    int avg_mode = 0;                 // the averaged template is scored: 0 never, 1 where a wakeword has one, 2 ... and its effective avg_threshold != 0
+    int gate = 0;                     // detect-only: a wave none of whose windows passes avg_threshold skips the sample templates; rejected windows get aggregate 0
+    float threshold = 0.f, avg_threshold = 0.f;   // the config's values (a wakeword's own override them)
+    float *agg = nullptr, *avg = nullptr;         // [S][win_pitch]; avg may be null
+    uint32_t *hot = nullptr;          // [S] (optional), zero before the call: raised for streams with a window that can fire
+    uint32_t *fix = nullptr;          // DtwWork::fix: its statistics words count the pairs scored with the reference-shaped cell
+};
+// LDS of one wave: the staged frames of a tile for the bank's longest window, the percentile block, the band of the reference-shaped cell
+inline size_t dtw_bank_lds_bytes(int K, int max_len) {
+    return ((size_t)(64 + max_len + 6) * (size_t)(K | 1) + (size_t)kBankMaxTemplates * 64 + 13 * 64) * sizeof(float);
+}
+// built for dtw_register_tile(K, band) > 0 (hipErrorNotSupported otherwise; band 0 is the caller's: all-zero scores)
+hipError_t launch_dtw_bank(hipStream_t st, const BankDev &b, const BankScore &q);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a process that drives several GPUs
 // (one rp_ctx per device) has to set it on each of them.  Sets it once per (current device, kernel), thread-safe.
@@ -442,6 +487,10 @@ hipError_t launch_scan_multi(hipStream_t st, const ScanWakewords &ww, const floa
 hipError_t launch_scan(hipStream_t st, const float *agg, const float *avg, const float *vad_value, float vad_mode_value,
                        size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det, int32_t *n_det, int max_det,
                        uint32_t *hot = nullptr);
+// scan_kernel for a wakeword bank: per stream the window length, thresholds and avg test of its wakeword, rows win_pitch apart (rp_scan.hip)
+hipError_t launch_scan_bank(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg, size_t win_pitch,
+                            const float *vad_value, float vad_mode_value, size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det,
+                            int32_t *n_det, int max_det, uint32_t *hot);
 
 // Decode + GainNormalizerFilter + BandPassFilter over whole streams.  ring [S][window_size], rms / gains
 // [S][n_samples/480] are device workspaces; biquad coefficients as BandPassFilter::new computes them.

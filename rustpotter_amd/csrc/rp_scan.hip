@@ -207,6 +207,112 @@ hipError_t launch_scan(hipStream_t st, const float *agg, const float *avg, const
     return launch_scan_multi(st, ww, vad_value, vad_mode_value, S, n_frames, cfg, det, nullptr, n_det, max_det);
 }
 
+// scan_kernel for a wakeword bank (rp_dtw_bank.hip): stream s runs the state machine of a `Rustpotter` that holds the one wakeword
+// bank[stream_wakeword[s]] -- its window length (max_mfcc_frames), its countdown max_len / 2, its own thresholds over the config's, the
+// avg test only when it has an averaged template and the effective avg_threshold != 0 -- over its rows agg / avg + s * win_pitch.  A stream
+// without a wakeword (index outside the bank) reports nothing.  `hot` as in scan_kernel: the flags dtw_bank_kernel raised, put back to 0 here.
+// A kernel of its own: scan_kernel's front (the sweep of 64 contiguous score rows, up to eight wakewords per stream with one window length
+// for the block) does not apply, and here the window length is a per-lane value.
+__global__ __launch_bounds__(64) void scan_bank_kernel(BankDev b, const int32_t *__restrict__ stream_wakeword, const float *__restrict__ agg,
+                                                       const float *__restrict__ avg, size_t win_pitch, const float *__restrict__ vad_value,
+                                                       float vad_mode_value, size_t S, size_t n_frames, ScanConfig cfg,
+                                                       BatchDetection *__restrict__ det, int32_t *__restrict__ n_det, int max_det,
+                                                       uint32_t *__restrict__ hot) {
+    __shared__ float vwin[50][64];  // VadDetector::window, one column per stream (lane)
+    const int lane = threadIdx.x;
+    const size_t s = (size_t)blockIdx.x * 64 + lane;
+    if (s >= S) return;
+    bool candidate = true;
+    if (hot) {
+        candidate = hot[s] != 0u;
+        if (candidate) hot[s] = 0u;   // consumed (Ctx::hot_flags)
+    }
+    const int wi = stream_wakeword[s];
+    const bool none = wi < 0 || wi >= b.W;
+    const long max_len = none ? 0 : b.ww[wi].max_len;
+    auto clear_from = [&](int from) {
+        BatchDetection zero{};
+        for (int i = from; i < max_det; ++i) det[s * (size_t)max_det + i] = zero;
+    };
+    if (none || !candidate || (long)n_frames < max_len) { n_det[s] = 0; clear_from(0); return; }
+    const float own_thr = b.ww[wi].threshold, own_athr = b.ww[wi].avg_threshold;
+    const float thr = own_thr == own_thr ? own_thr : cfg.threshold;
+    const float athr = own_athr == own_athr ? own_athr : cfg.avg_threshold;
+    const bool avg_on = avg && b.ww[wi].avg >= 0 && athr != 0.f;   // wakeword_comp.rs:85
+    const size_t row0 = s * win_pitch;
+    const float *vv = vad_value ? vad_value + s * n_frames : nullptr;
+    int vad_index = 0, voice_countdown = 0;
+    if (vv)
+        for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
+    long win_start = 0, resume = 0;
+    bool has_partial = false;
+    float p_score = 0.f, p_avg = 0.f;
+    int p_counter = 0, p_window = 0, countdown = 0, nd = 0;
+    for (long f = 0; f < (long)n_frames; ++f) {
+        if (f < resume) continue;
+        // process_new_mfccs :379-383: the VAD only sees a frame while no partial detection exists
+        bool should_run = true;
+        if (vv && !has_partial) {
+            vwin[vad_index][lane] = vv[f];
+            vad_index = vad_index >= 49 ? 0 : vad_index + 1;
+            float mn = RP_INF;
+            for (int i = 0; i < 50; ++i) { float w = vwin[i][lane]; if (w == w && w < mn) mn = w; }
+            mn = fmaxf(mn, 0.01f);
+            const float th = mn * vad_mode_value;
+            int n_high = 0;
+            for (int i = 0; i < 50; ++i) n_high += vwin[i][lane] > th ? 1 : 0;
+            if (n_high > 10) voice_countdown = 500;
+            if (voice_countdown > 0) { voice_countdown -= 1; should_run = true; } else should_run = false;
+        }
+        if (f - win_start + 1 < max_len) continue;
+        if (!should_run) continue;
+        const long w = f - max_len + 1;
+        if (countdown != 0) countdown -= 1;
+        if (has_partial) {
+            bool done = countdown == 0 ? true : (cfg.eager && p_counter >= cfg.min_scores);
+            if (done) {
+                has_partial = false;  // take()
+                if (p_counter >= cfg.min_scores) {
+                    if (nd < max_det) {
+                        BatchDetection d;
+                        d.stream = (int32_t)s + cfg.stream_base; d.frame = (int32_t)f; d.window = p_window; d.counter = p_counter;
+                        d.avg_score = p_avg; d.score = p_score;
+                        det[s * (size_t)max_det + nd] = d;
+                    }
+                    ++nd;
+                    win_start = resume = cfg.fpf * ((f + 3) / cfg.fpf + 1);  // reset()
+                    if (vv) {  // vad.reset()
+                        for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
+                        vad_index = 0; voice_countdown = 0;
+                    }
+                    continue;
+                }
+            }
+        }
+        const float sc = agg[row0 + w];
+        float av = 0.f;
+        bool pass = true;
+        if (avg_on) { av = avg[row0 + w]; pass = !(av < athr); }
+        if (pass && sc > thr) {
+            int counter = has_partial ? p_counter + 1 : 1;
+            if (!has_partial || p_score < sc) { p_score = sc; p_avg = av; p_window = (int)w; has_partial = true; }
+            p_counter = counter;
+            countdown = (int)(max_len / 2);
+        }
+    }
+    n_det[s] = nd;
+    clear_from(nd < max_det ? nd : max_det);
+}
+
+hipError_t launch_scan_bank(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg, size_t win_pitch,
+                            const float *vad_value, float vad_mode_value, size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det,
+                            int32_t *n_det, int max_det, uint32_t *hot) {
+    if (S == 0) return hipSuccess;
+    hipLaunchKernelGGL(scan_bank_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, b, stream_wakeword, agg, avg, win_pitch, vad_value,
+                       vad_mode_value, S, n_frames, cfg, det, n_det, max_det, hot);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------- streaming batches
 // State of one live stream between rp_stream_batch_process calls: the detector's countdown / partial
 // detection / window bookkeeping (src/detector.rs:62-79) in absolute frame numbers, and the VadDetector.
