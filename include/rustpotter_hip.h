@@ -441,11 +441,17 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
  * (rp_wakeword_ref_build_batch) -> bank -> detect.  A bank borrows `ctx`, which must outlive it, and is used with that context only.
  * Arithmetic: bank calls always score with f32 vector FMAs, the arithmetic of RP_ARITH_STRICT_F32, whatever rp_ctx_set_arithmetic says
  * (the setting is neither read nor changed); a stream gets the bits rp_batch_detect / rp_dtw_score_batch give it under RP_ARITH_STRICT_F32
- * with its wakeword as rp_templates.  rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK.
+ * with its wakeword as rp_templates.  (One exception, in the last bits only: a window whose only frame outside the norm range of the fast
+ * cosine lies within band_size - 2 frames BEHIND its end is rescored with the reference-shaped cosine by a bank call, and not by an
+ * rp_dtw_score_batch call of one stream with at most 8 windows, RP_DTW_KERNEL_SINGLE, which never loads those frames.  Both are within
+ * the parity bar.)  rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK.
  * Limits (refused with an error that names them): at most RP_WAKEWORD_BANK_MAX_TEMPLATES sample templates per wakeword; mfcc_size 5, 13 or
  * 16 with band_size 3..6 (the pairs the register kernels are built for), or band_size 0 (every score 0, as everywhere); an averaged
- * template no longer than the wakeword's longest sample template (src/mfcc/averager.rs:5-37 folds into the first sample: never a longer one).  Wakeword
- * models cannot be part of a bank. */
+ * template no longer than the wakeword's longest sample template (src/mfcc/averager.rs:5-37 folds into the first sample: never a longer one); a
+ * longest sample template of at most 7546 / 2859 / 2170 frames at mfcc_size 5 / 13 / 16 (a tile's frames for it fill the 160 KB of LDS;
+ * other sizes: the limit the error names).  Wakeword models cannot be part of a bank.
+ * An empty bank (n_wakewords == 0) is a Rustpotter without wakewords: calls succeed for any band_size with every index -1, report no
+ * detection and write zero rows. */
 enum { RP_WAKEWORD_BANK_MAX_TEMPLATES = 32 };
 typedef struct rp_wakeword_bank rp_wakeword_bank;
 /* WakewordRef (src/wakewords/wakeword_ref.rs:12-20) x n_wakewords from HOST arrays in the flat layout of rp_mfcc_average_batch: counts

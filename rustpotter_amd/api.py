@@ -1104,10 +1104,18 @@ class BatchContext:
             raise _err()
         return (det, n_det, agg, avg) if want_agg else (det, n_det)
 
-    def batch_detect_bank_dev(self, pcm_ptr, fmt, S, N, stride, bank, idx_ptr, detector_config, det_ptr, n_det_ptr, max_det):
-        """device pointers, detect-only (tools/bench_bank.py)"""
+    def batch_detect_bank_dev(self, pcm_ptr, fmt, S, N, stride, bank, idx_ptr, detector_config, det_ptr, n_det_ptr, max_det,
+                              agg_ptr=None, avg_ptr=None, win_pitch=0):
+        """device pointers; detect-only unless agg_ptr / avg_ptr ([S][win_pitch] floats) are given (tools/bench_bank.py)"""
         c = detector_config._c()
-        if self._L.rp_batch_detect_bank(self._h, pcm_ptr, fmt, S, N, stride, bank._h, idx_ptr, C.byref(c), det_ptr, n_det_ptr, max_det, None, None, 0) < 0:
+        if self._L.rp_batch_detect_bank(self._h, pcm_ptr, fmt, S, N, stride, bank._h, idx_ptr, C.byref(c), det_ptr, n_det_ptr, max_det,
+                                        agg_ptr, avg_ptr, win_pitch) < 0:
+            raise _err()
+
+    def dtw_scores_bank_dev(self, mfcc_ptr, S, n_frames, bank, idx_ptr, score_ref, band_size, score_mode, with_avg, avg_ptr, agg_ptr, win_pitch):
+        """rp_dtw_score_bank on device pointers: avg_ptr (may be None) and agg_ptr are [S][win_pitch] floats"""
+        if self._L.rp_dtw_score_bank(self._h, mfcc_ptr, S, n_frames, bank._h, idx_ptr, score_ref, band_size, int(score_mode),
+                                     int(with_avg), avg_ptr, agg_ptr, win_pitch) < 0:
             raise _err()
 
     def resample(self, pcm, sample_rate, channels=1):

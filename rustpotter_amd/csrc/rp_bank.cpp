@@ -74,7 +74,7 @@ Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32
     d.max_len = 0; d.min_len = 0;
     for (size_t w = 0; w < W; ++w) {
         BankWakeword &bw = bk->ww[w];
-        bw.first = (int)e; bw.count = counts[w]; bw.max_len = 0; bw.avg = -1; bw.ref_only = 0; bw.pad = 0;
+        bw.first = (int)e; bw.count = counts[w]; bw.max_len = 0; bw.avg = -1; bw.ref_only = 0; bw.window_chk = 0;
         bw.threshold = thresholds ? thresholds[w] : NAN;
         bw.avg_threshold = avg_thresholds ? avg_thresholds[w] : NAN;
         bool ref_only = false;
@@ -97,6 +97,7 @@ Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32
             ++avg_e; avg_row += (size_t)al; avg_src += (size_t)al;
         }
         bw.ref_only = ref_only ? 1 : 0;
+        bw.window_chk = dtw_register_staged(K, bw.max_len) ? 0 : 1;
         if (dtw_bank_lds_bytes(K, bw.max_len) > 160 * 1024) {
             const size_t fixed = ((size_t)kBankMaxTemplates * 64 + 13 * 64) * sizeof(float);
             const size_t lim = (160 * 1024 - fixed) / ((size_t)(K | 1) * sizeof(float)) - 70;
@@ -146,6 +147,7 @@ const int32_t *stage_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *
 
 bool band_ok(const BankDev &d, int band_size) {
     if (band_size < 0) { set_last_error("band_size must be >= 0"); return false; }
+    if (d.W == 0) return true;   // an empty bank scores nothing (its mfcc_size is a placeholder): a Rustpotter without wakewords
     if (band_size != 0 && dtw_register_tile(d.K, band_size) <= 0) {
         set_last_error("wakeword bank: mfcc_size " + std::to_string(d.K) + " with band_size " + std::to_string(band_size) +
                        " is not built (dtw_bank_kernel takes mfcc_size 5, 13 or 16 with band_size 3..6, or band_size 0)");
@@ -162,10 +164,11 @@ bool pitch_ok(size_t win_pitch, size_t max_n_win) {
     return true;
 }
 
-// the timed launch (kernel 1 of rp_ctx_timing_read); band_size 0: no cell lies in the band and every score is 0 (dtw.rs:64-75)
+// the timed launch (kernel 1 of rp_ctx_timing_read); band_size 0: no cell lies in the band and every score is 0 (dtw.rs:64-75); an empty
+// bank: no stream has a wakeword, every row is zero
 bool score_bank(Ctx *c, const Bank &bk, BankScore &q) {
     if (q.S == 0 || q.win_pitch == 0) return true;
-    if (q.band == 0) {
+    if (q.band == 0 || bk.dev.W == 0) {
         if (!hip_ok(hipMemsetAsync(q.agg, 0, q.S * q.win_pitch * sizeof(float), c->stream), "hipMemsetAsync")) return false;
         return !q.avg || hip_ok(hipMemsetAsync(q.avg, 0, q.S * q.win_pitch * sizeof(float), c->stream), "hipMemsetAsync");
     }
@@ -263,7 +266,7 @@ int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames,
         bool ok = false;
         const int32_t *di = stage_indices(c, sg, bk, stream_wakeword, S, n_frames, &max_n_win, &ok);
         if (!ok || !pitch_ok(win_pitch, max_n_win)) return -1;
-        if (S == 0 || win_pitch == 0) return 0;
+        if (S == 0 || win_pitch == 0) return sg.finish() ? 0 : -1;   // (the indices may be on their way to the device)
         const size_t out_bytes = S * win_pitch * sizeof(float);
         BankScore q;
         q.mfcc = static_cast<const float *>(sg.in(mfcc, S * n_frames * bk.dev.K * sizeof(float), c->stage_in));
@@ -297,6 +300,18 @@ int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, siz
         const bool wants = agg || avg;
         if (wants && !pitch_ok(win_pitch, max_n_win)) return -1;
         const size_t pitch = wants ? win_pitch : std::max<size_t>(max_n_win, 1);   // the call's own rows when nothing is handed out
+        if (bk.dev.W == 0) {   // a Rustpotter without wakewords: no stream reports anything, every row is zero (the bank's mfcc_size is a placeholder)
+            if (!sample_format_ok(fmt)) return -1;
+            if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
+            if (max_det < 0) { set_last_error("max_det must be >= 0"); return -1; }
+            auto zero = [&](void *p, size_t bytes) {
+                if (!p || !bytes) return true;
+                if (sg.host) { std::memset(p, 0, bytes); return true; }
+                return hip_ok(hipMemsetAsync(p, 0, bytes, c->stream), "hipMemsetAsync");
+            };
+            return zero(det, S * (size_t)max_det * sizeof(rp_batch_detection)) && zero(n_det, S * sizeof(int32_t)) &&
+                   zero(agg, S * win_pitch * sizeof(float)) && zero(avg, S * win_pitch * sizeof(float)) && sg.finish() ? 0 : -1;
+        }
         DetectFront f;
         if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, bk.dev.K, std::max(bk.dev.min_len, 1), det, n_det, max_det, &f)) return -1;
         // caller-provided arrays are used directly when they are device pointers

@@ -1234,8 +1234,12 @@ static DtwRoute dtw_route(const TemplatesDev &t, int band, size_t S, size_t n_wi
     // (a register kernel stages 64..128 windows + two template lengths of frames in LDS: templates beyond ~4 000 frames at
     // mfcc_size 5 -- 40 s -- do not fit the CU's 160 KB; the generic kernel stages one length and takes them up to ~8 000)
     const bool reg_built = dtw_register_tile(t.K, band) > 0 && t.max_diff == 0 && t.chunks;
-    const bool reg_staged = reg_built && (size_t)(2 * kDtwWin + 2 * (t.max_len + 8)) * (size_t)(t.K | 1) * sizeof(float) <= 160 * 1024;
-    r.reg = !r.single && !t.ref_only && reg_built && (r.few || reg_staged);
+    static_assert(kDtwWin == 64, "dtw_register_staged");
+    const bool reg_staged = reg_built && dtw_register_staged(t.K, t.max_len);
+    // (a window past the staging goes to dtw_generic_kernel whatever the call's shape, also where `few` would let the register kernels read
+    // it from global memory: which frames a window's norm-range test sees -- the register kernels' include the W - 2 loaded behind its end,
+    // the generic kernel's do not -- then depends on the template set alone, and a wakeword bank can follow it: BankWakeword::window_chk)
+    r.reg = !r.single && !t.ref_only && reg_built && reg_staged;
     // the band is widened to |m-n| inside the generic kernel; size for the worst case over templates
     const int KP = t.K | 1, Wmax = band > t.max_diff ? band : t.max_diff;
     r.generic_lds = ((size_t)(64 + t.max_len - 1) * KP + (size_t)t.K * 64 + (size_t)(2 * Wmax + 1) * 64) * sizeof(float);

@@ -96,6 +96,33 @@ __device__ __forceinline__ float bank_dtw(const float *xl, int L, const float *_
     return dtw_logistic(P[W + 1] / (float)(L + L), score_ref);   // D[m-1][n] for m == n
 }
 
+// chk of bank_dtw over the window's own L frames only (the same sums, the same fma chain): what dtw_generic_kernel tests, which loads no frame
+// behind the window's end.  For wakewords past the register kernels' staging (BankWakeword::window_chk), and only once a lane was flagged.
+template <int K, int KP>
+__device__ __noinline__ float bank_chk_window(const float *xl, int L) {
+    float mu[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) mu[k] = 0.f;
+    for (int i = 0; i < L; ++i) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) mu[k] += xl[i * KP + k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) mu[k] = mu[k] / (float)L;
+    float chk = 0.f;
+    for (int i = 0; i < L; ++i) {
+        float bb = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float y = xl[i * KP + k] - mu[k];
+            bb = fmaf(y, y, bb);
+        }
+        const float inv = bb > 0.f ? rsqrtf(bb) : 0.f;
+        chk = fmaxf(fmaxf(chk, inv), bb);
+    }
+    return chk;
+}
+
 // The same DTW with the reference-shaped cell of dtw_ref_kernel (comparator.rs:28-48: three sequential dot products of the template row AS
 // GIVEN and the mean-normalised frame, one sqrt, one divide), for windows with a frame outside kDtwNormLo..kDtwFixLimit and wakewords with a
 // row outside kDtwNormLo..kDtwNormHiRow.  Band in LDS, lane-minor; the whole wave walks it, the lanes that need it keep the result.
@@ -192,7 +219,7 @@ __global__ __launch_bounds__(64) void dtw_bank_kernel(const BankWakeword *__rest
     const float own_thr = bw->threshold, own_athr = bw->avg_threshold;
     const float thr = own_thr == own_thr ? own_thr : q.threshold;
     const float athr = own_athr == own_athr ? own_athr : q.avg_threshold;
-    const int avg_e = bw->avg, T = bw->count, first = bw->first, ref_only = bw->ref_only;
+    const int avg_e = bw->avg, T = bw->count, first = bw->first, ref_only = bw->ref_only, window_chk = bw->window_chk;
     const bool do_avg = avg_e >= 0 && (q.avg_mode == 1 || (q.avg_mode == 2 && athr != 0.f));   // wakeword_comp.rs:85
     const int mode = q.score_mode;
 
@@ -204,6 +231,7 @@ __global__ __launch_bounds__(64) void dtw_bank_kernel(const BankWakeword *__rest
         const size_t off = (size_t)bank_trow[e] * K;
         float chk;
         float sc = bank_dtw<K, W, KP>(xl, L, bank_unit + off, q.score_ref, chk);
+        if (window_chk && __any(valid && chk > kDtwFixLimit)) chk = bank_chk_window<K, KP>(xl, L);   // wave-uniform
         const bool slow = valid && (ref_only || chk > kDtwFixLimit);
         const unsigned long long slow_mask = __ballot(slow);
         if (slow_mask) {   // wave-uniform

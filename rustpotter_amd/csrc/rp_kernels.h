@@ -341,7 +341,7 @@ struct BankWakeword {
     int avg;          // entry of its averaged template, -1: none
     int ref_only;     // a row outside kDtwNormLo..kDtwNormHiRow: every window of this wakeword takes the reference-shaped cell
     float threshold, avg_threshold;   // the wakeword's own Option<f32>: NaN = the value of the call's config
-    int pad;
+    int window_chk;   // the norm-range test reads the window's own frames only, as dtw_generic_kernel: !dtw_register_staged(K, max_len)
 };
 struct BankDev {
     int W = 0, K = 0;
@@ -366,6 +366,13 @@ struct BankScore {
     uint32_t *hot = nullptr;          // [S] (optional), zero before the call: raised for streams with a window that can fire
     uint32_t *fix = nullptr;          // DtwWork::fix: its statistics words count the pairs scored with the reference-shaped cell
 };
+// Do the register kernels take a window of max_len frames?  They stage two tiles of 64 windows + two window lengths of frames in the CU's
+// 160 KB (windows up to 4 024 / 1 503 / 1 132 frames at mfcc_size 5 / 13 / 16); rp_templates with a longer window are scored by
+// dtw_generic_kernel in every call shape (dtw_route), which loads no frame behind a window's end -- so its norm-range test never sees one, and a bank wakeword
+// of that length must not either if it is to give the same bits (BankWakeword::window_chk).
+inline bool dtw_register_staged(int K, int max_len) {
+    return (size_t)(2 * 64 + 2 * (max_len + 8)) * (size_t)(K | 1) * sizeof(float) <= 160 * 1024;
+}
 // LDS of one wave: the staged frames of a tile for the bank's longest window, the percentile block, the band of the reference-shaped cell
 inline size_t dtw_bank_lds_bytes(int K, int max_len) {
     return ((size_t)(64 + max_len + 6) * (size_t)(K | 1) + (size_t)kBankMaxTemplates * 64 + 13 * 64) * sizeof(float);
