@@ -346,7 +346,8 @@ int rp_templates_max_len(const rp_templates *t);
  * src/mfcc/dtw.rs:56-105 + src/mfcc/normalizer.rs.  n_win = n_frames - max_len + 1.
  * scores [S][n_win][T]; avg [S][n_win] (NULL or ignored when the template set has no
  * avg template / with_avg == 0); agg [S][n_win] = score_mode aggregate.  band_size 0 is
- * legal as in the reference (u16): no cell lies in the band and every score is 0. */
+ * legal as in the reference (u16): no cell lies in the band and every score is 0.  The aggregate takes at most 256 sample
+ * templates: with agg != NULL (and in every detect call) a template set of more is an error that names the limit. */
 int rp_dtw_score_batch(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames, const rp_templates *t,
                        float score_ref, int band_size, rp_score_mode score_mode, int with_avg,
                        float *scores, float *avg, float *agg);
@@ -366,7 +367,8 @@ typedef struct {
  * the VadDetector gate (src/mfcc/vad.rs:11-36, :379-383) is evaluated per stream from `mfcc`
  * ([S][n_frames][K], required then; may be NULL otherwise).
  * det [S][max_det] (device or host per ctx flag), n_det [S] (may exceed max_det: only the first max_det detections of a
- * stream are stored; slots behind a stream's detections are zero). */
+ * stream are stored; slots behind a stream's detections are zero).  agg / avg are [S][n_win] with n_win = n_frames - max_len + 1
+ * (0 when n_frames < max_len); max_len < 1 and max_det < 0 are errors. */
 int rp_detect_scan(rp_ctx *ctx, const float *agg, const float *avg, size_t S, size_t n_frames, int max_len,
                    const rp_detector_config *config, int avg_enabled, const float *mfcc, int K,
                    rp_batch_detection *det, int32_t *n_det, int max_det);

@@ -468,6 +468,9 @@ int rp_detect_scan(rp_ctx *ctx, const float *agg, const float *avg, size_t S, si
     return guarded([&]() -> int {
         if (!ctx) { set_last_error("null handle"); return -1; }
         if (!config || (S && (!agg || !det || !n_det))) { set_last_error("null argument"); return -1; }
+        // a window of no frames would give every stream n_frames + 1 rows: more than the caller's agg / avg hold
+        if (max_len < 1) { set_last_error("rp_detect_scan: max_len must be >= 1"); return -1; }
+        if (max_det < 0) { set_last_error("rp_detect_scan: max_det must be >= 0"); return -1; }
         Ctx *c = ctx->impl.get();
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         const bool vad = config->vad_mode != RP_VAD_NONE;

@@ -487,6 +487,7 @@ int Rustpotter::process_audio(float *buf, size_t n, Detection *out) {
             if (!any) continue;   // every window of this chunk is `None` for this wakeword
             any_passed = true;
             const int T = (int)w->ref.lens.size();
+            if (!aggregate_fits(T)) return -1;
             if (!hip_ok(launch_dtw_single_part(st, ctx_->dtw_work(), w->tmpl->dev, hist, frames_valid, first_win, cnt, cnt, det_.band_size, det_.score_ref, 0, T,
                                                res + w->off_scores, res + w->off_avg), "dtw kernel")) return -1;
             if (!hip_ok(launch_aggregate(st, res + w->off_scores, cnt, T, (int)det_.score_mode, res + w->off_agg), "aggregate_kernel")) return -1;

@@ -1410,7 +1410,12 @@ hipError_t launch_dtw_single_part(hipStream_t st, const DtwWork &wk, const Templ
 // src/wakewords/comp/wakeword_comp.rs:38-49 (get_percentile) and :108-139
 // (percentile_sorted and percentile_of_mode: rp_device.h, shared with dtw_bank_kernel)
 
-constexpr int kAggMaxT = 256;
+bool aggregate_fits(int T) {
+    if (T <= kAggMaxT) return true;
+    set_last_error("a wakeword reference of " + std::to_string(T) + " templates exceeds the " + std::to_string(kAggMaxT) +
+                   "-template limit of the score aggregate");
+    return false;
+}
 
 // Max / Average: no sort buffer, so no scratch memory to set up (the single-stream path launches this for 3 rows).
 // A workgroup owns 64 consecutive rows: the [64][T] block of scores is one contiguous range, copied to LDS with
@@ -1531,9 +1536,15 @@ hipError_t launch_aggregate(hipStream_t st, const float *scores, size_t n_rows, 
     if (T < 1 || T > kAggMaxT) return hipErrorInvalidValue;
     size_t blocks = (n_rows + 63) / 64;
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    if (mode == 0 || mode == 1)
-        hipLaunchKernelGGL(aggregate_kernel, dim3((unsigned)blocks), dim3(64), (size_t)64 * (T + 1) * sizeof(float), st, scores, n_rows, T, mode, agg, x);
-    else if (T <= 64) {
+    if (mode == 0 || mode == 1) {
+        // T = 256 asks for 65 792 bytes.  The runtime on gfx950 bounds a launch by the device's 160 KB per workgroup and ran it unasked
+        // (tests/test_gpu_aggregate_builds.py at 256 templates); the opt-in HIP documents above 64 KB is made anyway, as for every other
+        // kernel of the library that can pass it
+        const size_t lds = (size_t)64 * (T + 1) * sizeof(float);
+        if (lds > 64 * 1024)
+            if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(aggregate_kernel), 160 * 1024); e != hipSuccess) return e;
+        hipLaunchKernelGGL(aggregate_kernel, dim3((unsigned)blocks), dim3(64), lds, st, scores, n_rows, T, mode, agg, x);
+    } else if (T <= 64) {
         const size_t lds = (size_t)64 * (T + 1) * sizeof(float);
 #define RP_AGG_SORTED(NT) hipLaunchKernelGGL(aggregate_sorted_reg_kernel<NT>, dim3((unsigned)blocks), dim3(64), lds, st, scores, n_rows, T, mode, agg, x)
         if (T <= 2) RP_AGG_SORTED(2);
@@ -1552,6 +1563,7 @@ hipError_t launch_aggregate(hipStream_t st, const float *scores, size_t n_rows, 
 bool dtw_score(Ctx &c, const DtwScore &q) {
     const TemplatesDev &t = *q.t;
     const size_t rows = q.S * q.n_win;
+    if (q.agg && !aggregate_fits(t.T)) return false;
     const DtwRoute r = dtw_route(t, q.band, q.S, q.n_win, q.padded_rows, q.with_avg, q.score_ref);
     // The averaged-template gate as the reference runs it (wakeword_comp.rs:85-93): a window whose avg_score is below avg_threshold is
     // never compared with the sample templates

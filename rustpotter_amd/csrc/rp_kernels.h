@@ -483,6 +483,10 @@ struct AggExtra {
     size_t n_win = 1;
 };
 hipError_t launch_aggregate(hipStream_t st, const float *scores, size_t n_rows, int T, int mode, float *agg, AggExtra x = AggExtra{});
+// a row of launch_aggregate holds at most kAggMaxT scores (the sort buffer of the percentile modes): false with the error set for a
+// reference with more sample templates, asked before anything of the scoring call is launched
+constexpr int kAggMaxT = 256;
+bool aggregate_fits(int T);
 
 // vad_value [S][n_frames] = mean |mfcc| per frame (launch_vad_value) or nullptr (no VAD);
 // vad_mode_value = VADMode::get_value (2 / 2.5 / 3, src/config.rs:140-146)
