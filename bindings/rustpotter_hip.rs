@@ -76,6 +76,7 @@ pub const RP_DTW_PRODUCTS_F16X2: c_int = 512;
 pub const RP_DTW_MFMA_WAVES_8: c_int = 1024;
 pub const RP_DTW_MFMA_WAVES_12: c_int = 2048;
 pub const RP_DTW_KERNEL_BANK: c_int = 4096;
+pub const RP_DTW_KERNEL_BANK_STREAM: c_int = 8192;
 pub const RP_WAKEWORD_BANK_MAX_TEMPLATES: c_int = 32;
 pub const RP_MLP_F32: c_int = 0;
 pub const RP_MLP_BF16: c_int = 1;
@@ -220,6 +221,9 @@ extern "C" {
                                      config: *const rp_detector_config, S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
     pub fn rp_stream_batch_process_multi(b: *mut rp_stream_batch, pcm: *const c_void, fmt: c_int, n_chunks: usize, pcm_stride: usize,
                                          det: *mut rp_batch_detection, det_wakeword: *mut i32, det_label: *mut i32, n_det: *mut i32, max_det: c_int) -> c_int;
+    pub fn rp_stream_batch_new_bank(ctx: *mut rp_ctx, bank: *const rp_wakeword_bank, stream_wakeword: *const i32, config: *const rp_detector_config,
+                                    S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
+    pub fn rp_stream_batch_set_wakewords(b: *mut rp_stream_batch, first_stream: usize, n: usize, wakewords: *const i32) -> c_int;
     pub fn rp_model_new(ctx: *mut rp_ctx, n_layers: c_int, dims: *const c_int, weights: *const *const f32, biases: *const *const f32,
                         out: *mut *mut rp_model) -> c_int;
     pub fn rp_model_free(m: *mut rp_model);
@@ -746,6 +750,19 @@ impl<'a> StreamBatch<'a> {
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_multi(ctx.h, specs.len(), specs.as_ptr(), mfcc_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
         Ok(StreamBatch { h, n_streams, last_chunks: 0, _ctx: ctx, _t: std::marker::PhantomData })
+    }
+    /// Personal wakewords on live streams: stream `s` holds the one wakeword `bank[stream_wakeword[s]]` (-1: none) with its own window
+    /// length and thresholds -- `batch_detect_bank` with the state carried between calls.  `process_multi` reports the bank index.
+    pub fn new_bank(ctx: &'a HipContext, bank: &'a WakewordBank, stream_wakeword: &[i32], config: &DetectorConfig, max_chunks_per_call: usize)
+                    -> Result<StreamBatch<'a>, String> {
+        let c: rp_detector_config = config.into();
+        let mut h = std::ptr::null_mut();
+        status(unsafe { rp_stream_batch_new_bank(ctx.h, bank.h, stream_wakeword.as_ptr(), &c, stream_wakeword.len(), max_chunks_per_call, &mut h) })?;
+        Ok(StreamBatch { h, n_streams: stream_wakeword.len(), last_chunks: 0, _ctx: ctx, _t: std::marker::PhantomData })
+    }
+    /// Connect / disconnect of device slots (a batch of `new_bank`): streams `first_stream ..` get new bank indices and are reset
+    pub fn set_wakewords(&mut self, first_stream: usize, wakewords: &[i32]) -> Result<(), String> {
+        status(unsafe { rp_stream_batch_set_wakewords(self.h, first_stream, wakewords.len(), wakewords.as_ptr()) })
     }
     /// `process` that also tells which wakeword fired and, for a model, which label: (detections, wakeword indices, label indices or -1)
     pub fn process_multi(&mut self, pcm: &[f32], n_chunks: usize, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>, Vec<Vec<i32>>), String> {

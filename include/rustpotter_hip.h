@@ -233,7 +233,8 @@ enum {
     /* the builds of dtw_mfma_kernel launched among the above: waves per workgroup (same results either way) */
     RP_DTW_MFMA_WAVES_8 = 1024,    /* two waves per SIMD */
     RP_DTW_MFMA_WAVES_12 = 2048,   /* three waves per SIMD */
-    RP_DTW_KERNEL_BANK = 4096      /* dtw_bank_kernel: every stream against its own wakeword of a bank (rp_dtw_score_bank, rp_batch_detect_bank) */
+    RP_DTW_KERNEL_BANK = 4096,     /* dtw_bank_kernel: every stream against its own wakeword of a bank (rp_dtw_score_bank, rp_batch_detect_bank) */
+    RP_DTW_KERNEL_BANK_STREAM = 8192 /* dtw_bank_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank) */
 };
 int rp_ctx_dtw_kernels(rp_ctx *ctx);
 /* Which build this library is (replaces nothing): the target architecture and the compiler flags it differs by from the
@@ -590,6 +591,35 @@ int rp_stream_batch_new_multi(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword
  * the detections of rp_batch_detect_multi / rp_batch_detect_model over the concatenation. */
 int rp_stream_batch_process_multi(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
                                   rp_batch_detection *det, int32_t *det_wakeword, int32_t *det_label, int32_t *n_det, int max_det);
+
+/* Personal wakewords on LIVE streams: a live-stream batch over a wakeword bank -- enrol (rp_wakeword_ref_build_batch) -> bank -> live
+ * detect, every stream's detector state on the device.  Stream s behaves as Rustpotter::new(config) + add_wakeword(bank[stream_wakeword[s]])
+ * + process_samples per chunk: rp_batch_detect_bank's semantics with the state carried between calls -- its own window length (the
+ * wakeword's longest sample template) and countdown max_len / 2, the wakeword's own thresholds over config's, the averaged-template test
+ * only when the wakeword has an averaged template and its effective avg_threshold != 0.  stream_wakeword[s] == -1: a detector without
+ * wakewords, which never reports.  Fed the same audio piece by piece a stream reports the detections of rp_batch_detect_bank over the
+ * concatenation, bit for bit (with the last-bits exception of the bank calls above: a window with a frame outside the norm range of the
+ * fast cosine within band_size - 2 frames behind its end may be rescored by one call and not the other; both within the parity bar).
+ * The batch borrows `ctx` and `bank` (the bank must belong to `ctx`) and keeps its own device copy of the indices.  stream_wakeword [S]: a
+ * host array under RP_CTX_HOST_POINTERS -- an index outside [-1, n_wakewords) is then an error that names the stream, found before
+ * anything is allocated -- else a device array, copied; the kernels treat such an index as -1.  Every stream keeps an MFCC history of
+ * rp_wakeword_bank_max_len(bank, -1) - 1 frames; the window ending at a new frame starts max_len(s) - 1 frames before it.
+ * Limits as the bank calls: mfcc_size 5, 13 or 16 with band_size 3..6, or band_size 0 (every score 0, no detection); an empty bank or all
+ * indices -1: calls succeed and report nothing.  Arithmetic: f32 vector FMAs whatever rp_ctx_set_arithmetic says (neither read nor
+ * changed); rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK_STREAM.
+ * rp_stream_batch_process / _process_multi work on such a batch: agg [S][frames per call] is the score_mode aggregate of the stream's OWN
+ * window ending at each new frame (a zero row for a stream without a wakeword; windows reaching before frame 0 are unspecified);
+ * det_wakeword is the stream's bank index, det_label -1.  Without agg and without RP_CTX_FULL_SCORES a window below its avg_threshold is
+ * not compared with the sample templates; the detections are the same either way.  rp_stream_batch_set_input works as on any batch.
+ * rp_stream_batch_set_filters takes the band-pass filter alone: with gain_normalizer.enabled it fails (the gain window and rms_level_ref
+ * are per detector, here they would be per stream). */
+int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config,
+                             size_t S, size_t max_chunks_per_call, rp_stream_batch **out);
+/* Connect / disconnect of device slots, at any time between process calls: streams first_stream .. first_stream + n - 1 get the indices
+ * wakewords [n] (host or device array, checked as above; -1: none) and each is reset exactly as rp_stream_batch_reset(b, s) does
+ * (add_wakeword on a detector without wakewords calls reset(), src/detector.rs:304-307; the filters' state and the resampler are not
+ * touched).  A refused index changes nothing.  An error on a batch not made by rp_stream_batch_new_bank. */
+int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *wakewords);
 
 /* A wakeword model (src/wakewords/wakeword_model.rs:11-18) resident on the device.  weights are
  * HOST arrays W_l [dims[l+1]][dims[l]] (candle Linear: x.W^T + b), biases b_l [dims[l+1]]; 1..3 layers. */

@@ -114,7 +114,7 @@ SYMBOLS = [
     "rp_stream_batch_new_multi", "rp_stream_batch_process_multi",
     "rp_stream_batch_set_filters", "rp_stream_batch_levels",
     "rp_wakeword_bank_new", "rp_wakeword_bank_new_from_rpw", "rp_wakeword_bank_free", "rp_wakeword_bank_max_len", "rp_dtw_score_bank",
-    "rp_batch_detect_bank",
+    "rp_batch_detect_bank", "rp_stream_batch_new_bank", "rp_stream_batch_set_wakewords",
 ]
 
 
@@ -248,6 +248,8 @@ def load_library():
     L.rp_dtw_score_bank.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t]
     L.rp_batch_detect_bank.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(_DetectorConfig), vp, vp, C.c_int,
                                        vp, vp, C.c_size_t]
+    L.rp_stream_batch_new_bank.argtypes = [vp, vp, vp, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.rp_stream_batch_set_wakewords.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
     _LIB = L
     return L
 
@@ -572,20 +574,27 @@ DET_DTYPE = [("stream", "<i4"), ("frame", "<i4"), ("window", "<i4"), ("counter",
 
 class StreamBatch:
     """S live streams fed chunk by chunk (rp_stream_batch_*): the batched form of calling
-    Rustpotter::process_samples on S instances sharing one wakeword and config."""
+    Rustpotter::process_samples on S instances sharing one wakeword and config -- or, over a WakewordBank, each holding its own."""
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
-                 mfcc_size=None, filters=None, rms_level_ref=float("nan")):
+                 mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
         with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
         filters (rp_stream_batch_set_filters): a FiltersConfig for the streams, with rms_level_ref the largest rms_level of the
-        wakewords (NaN: none); levels() then reports every chunk's RMS level and gain."""
+        wakewords (NaN: none); levels() then reports every chunk's RMS level and gain.
+        bank + stream_wakeword (rp_stream_batch_new_bank; templates is then None): stream s holds the one wakeword
+        bank[stream_wakeword[s]], -1 = none; stream_wakeword is [S] int32 (with device pointers: the address of a device array)."""
         self._L = load_library()
         self.ctx, self.templates, self.S, self.max_chunks = ctx, templates, S, max_chunks_per_call
         h = C.c_void_p()
         c = detector_config._c()
-        if wakewords is None:
+        if bank is not None:
+            self._keep = bank   # the batch borrows the bank
+            idx, ptr = self._indices(stream_wakeword)
+            if self._L.rp_stream_batch_new_bank(ctx._h, bank._h, ptr, C.byref(c), S, max_chunks_per_call, C.byref(h)) < 0:
+                raise _err()
+        elif wakewords is None:
             if self._L.rp_stream_batch_new(ctx._h, templates._h, C.byref(c), S, max_chunks_per_call, C.byref(h)) < 0:
                 raise _err()
         else:
@@ -614,6 +623,21 @@ class StreamBatch:
         if getattr(self, "_h", None):
             self._L.rp_stream_batch_free(self._h)
             self._h = None
+
+    def _indices(self, idx):
+        """wakeword indices as the context takes them: a host int32 array, or the address of a device one"""
+        import numpy as np
+        if idx is None or isinstance(idx, int):
+            return None, idx
+        a = np.ascontiguousarray(idx, np.int32)
+        return a, a.ctypes.data
+
+    def set_wakewords(self, first_stream, stream_wakeword, n=None):
+        """rp_stream_batch_set_wakewords: streams first_stream .. get the bank indices stream_wakeword (-1: none) and are reset; between
+        process calls.  With device pointers stream_wakeword is the address of a device int32 array of n indices."""
+        idx, ptr = self._indices(stream_wakeword)
+        if self._L.rp_stream_batch_set_wakewords(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
+            raise _err()
 
     @property
     def chunks_seen(self):
@@ -693,6 +717,11 @@ class StreamBatch:
 
     def process_dev(self, pcm_ptr, fmt, n_chunks, stride, det_ptr, n_det_ptr, max_det, agg_ptr=None):
         if self._L.rp_stream_batch_process(self._h, pcm_ptr, fmt, n_chunks, stride, det_ptr, n_det_ptr, max_det, agg_ptr) < 0:
+            raise _err()
+        self._last_chunks = n_chunks
+
+    def process_multi_dev(self, pcm_ptr, fmt, n_chunks, stride, det_ptr, det_ww_ptr, det_label_ptr, n_det_ptr, max_det):
+        if self._L.rp_stream_batch_process_multi(self._h, pcm_ptr, fmt, n_chunks, stride, det_ptr, det_ww_ptr, det_label_ptr, n_det_ptr, max_det) < 0:
             raise _err()
         self._last_chunks = n_chunks
 
@@ -844,7 +873,8 @@ class BatchContext:
         return int(v.value)
 
     DTW_KERNELS = {1: "dtw_mfma_kernel", 2: "dtw_mfma_wide_kernel", 4: "dtw_ragged_kernel", 8: "register kernels", 16: "dtw_generic_kernel",
-                   32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel", 4096: "dtw_bank_kernel"}
+                   32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel", 4096: "dtw_bank_kernel",
+                   8192: "dtw_bank_stream_kernel"}
     DTW_PRODUCTS = {256: "bf16x3", 512: "f16x2"}
     DTW_MFMA_WAVES = {1024: 8, 2048: 12}
 

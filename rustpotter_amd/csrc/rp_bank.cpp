@@ -114,6 +114,18 @@ Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32
     return bk.release();
 }
 
+// the (mfcc_size, band_size) pairs the bank kernels are built for; every bank entry point refuses the others with this wording
+bool bank_band_ok(const BankDev &d, int band_size) {
+    if (band_size < 0) { set_last_error("band_size must be >= 0"); return false; }
+    if (d.W == 0) return true;   // an empty bank scores nothing (its mfcc_size is a placeholder): a Rustpotter without wakewords
+    if (band_size != 0 && dtw_register_tile(d.K, band_size) <= 0) {
+        set_last_error("wakeword bank: mfcc_size " + std::to_string(d.K) + " with band_size " + std::to_string(band_size) +
+                       " is not built (dtw_bank_kernel takes mfcc_size 5, 13 or 16 with band_size 3..6, or band_size 0)");
+        return false;
+    }
+    return true;
+}
+
 }  // namespace rp
 
 namespace {
@@ -143,17 +155,6 @@ const int32_t *stage_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *
     if (!p) return nullptr;
     *ok = true;
     return static_cast<const int32_t *>(p);
-}
-
-bool band_ok(const BankDev &d, int band_size) {
-    if (band_size < 0) { set_last_error("band_size must be >= 0"); return false; }
-    if (d.W == 0) return true;   // an empty bank scores nothing (its mfcc_size is a placeholder): a Rustpotter without wakewords
-    if (band_size != 0 && dtw_register_tile(d.K, band_size) <= 0) {
-        set_last_error("wakeword bank: mfcc_size " + std::to_string(d.K) + " with band_size " + std::to_string(band_size) +
-                       " is not built (dtw_bank_kernel takes mfcc_size 5, 13 or 16 with band_size 3..6, or band_size 0)");
-        return false;
-    }
-    return true;
 }
 
 bool pitch_ok(size_t win_pitch, size_t max_n_win) {
@@ -191,7 +192,7 @@ int bank_from(rp_ctx *ctx, std::unique_ptr<Bank> b, rp_wakeword_bank **out) {
 
 extern "C" {
 
-static_assert(RP_DTW_KERNEL_BANK == (int)kDtwRanBank && RP_WAKEWORD_BANK_MAX_TEMPLATES == kBankMaxTemplates, "rustpotter_hip.h mirrors rp_kernels.h");
+static_assert(RP_DTW_KERNEL_BANK == (int)kDtwRanBank && RP_DTW_KERNEL_BANK_STREAM == (int)kDtwRanBankStream && RP_WAKEWORD_BANK_MAX_TEMPLATES == kBankMaxTemplates, "rustpotter_hip.h mirrors rp_kernels.h");
 
 int rp_wakeword_bank_new(rp_ctx *ctx, size_t n_wakewords, int mfcc_size, const int32_t *counts, const int32_t *lens, const float *feats,
                          const int32_t *avg_lens, const float *avg_feats, const float *thresholds, const float *avg_thresholds,
@@ -260,7 +261,7 @@ int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames,
         const Bank &bk = *bank->impl;
         if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!band_ok(bk.dev, band_size)) return -1;
+        if (!bank_band_ok(bk.dev, band_size)) return -1;
         Staged sg(c);
         size_t max_n_win = 0;
         bool ok = false;
@@ -290,7 +291,7 @@ int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, siz
         const Bank &bk = *bank->impl;
         if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!band_ok(bk.dev, (int)config->band_size)) return -1;
+        if (!bank_band_ok(bk.dev, (int)config->band_size)) return -1;
         Staged sg(c);
         const size_t nf = rp_mfcc_num_frames(n_samples);
         size_t max_n_win = 0;

@@ -89,5 +89,7 @@ bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch,
 void band_pass_coefficients(const rp_band_pass_config &b, float q[5]);
 bool resample_rows(Ctx *c, const ResamplerDev &rs, const void *pcm, int fmt, int channels, size_t pcm_stride, const float *prev,
                    float *prev_out, size_t S, size_t n_chunks, DevBuf &xs_buf, size_t xs_chunks, float *out, size_t out_stride);
+// rp_bank.cpp
+bool bank_band_ok(const BankDev &d, int band_size);
 
 }  // namespace rp

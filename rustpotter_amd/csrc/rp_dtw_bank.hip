@@ -1,6 +1,7 @@
 // rp_dtw_bank.hip -- dtw_bank_kernel: window scoring where stream s carries its OWN wakeword, bank[stream_wakeword[s]] -- the batched form of
 // one `Rustpotter` per thread, each holding one personal wakeword (src/detector.rs:304-346; scoring as rp_dtw.hip: src/mfcc/dtw.rs:56-105 +
-// comparator.rs + normalizer.rs + wakeword_comp.rs:22-27,77-139).  DESIGN.md §4.2c.
+// comparator.rs + normalizer.rs + wakeword_comp.rs:22-27,77-139), and dtw_bank_stream_kernel: the same for the new windows of a live-stream
+// batch, lanes = rows of many streams.  DESIGN.md §4.2c.
 #include "rp_device.h"
 
 namespace rp {
@@ -289,6 +290,113 @@ hipError_t launch_dtw_bank(hipStream_t st, const BankDev &b, const BankScore &q)
     const size_t lds = dtw_bank_lds_bytes(b.K, b.max_len);
     if (lds > 160 * 1024) return hipErrorMemoryAllocation;
 #define RP_BANK(KK, WW) launch_bank_kw<KK, WW>(st, b, q, (unsigned)blocks, (unsigned)tiles, lds)
+#define RP_BANK_BAND(KK) \
+    switch (q.band) { case 3: return RP_BANK(KK, 3); case 4: return RP_BANK(KK, 4); case 5: return RP_BANK(KK, 5); default: return RP_BANK(KK, 6); }
+    if (b.K == 5) { RP_BANK_BAND(5) }
+    if (b.K == 13) { RP_BANK_BAND(13) }
+    RP_BANK_BAND(16)
+#undef RP_BANK_BAND
+#undef RP_BANK
+}
+
+// dtw_bank_kernel for a live-stream batch (rp_stream_batch_new_bank).  A stream brings only 3 * n_chunks new windows per call, so a wave per
+// (stream, 64 windows) would leave most lanes idle; here, as in the GX forms of rp_dtw.hip, the wave's 64 lanes are consecutive rows of the
+// flattened [S][n_new] space: a wave straddles streams and therefore wakewords.  Every lane reads its stream's index and wakeword record,
+// points at its window in the batch's MFCC rows in global memory (frame_pitch frames a stream) and walks ITS wakeword -- the averaged
+// template first when it is to be scored, then the sample templates -- so template count, template length and template rows are per-lane
+// values: the template loop runs to the wave's largest count, bank_dtw's row loop to the wave's longest template, both under the lane mask,
+// and template rows come by vector loads.  The cell arithmetic is bank_dtw's, operation for operation: a stream gets the bits dtw_bank_kernel
+// gives it.  Norm-range test, reference-shaped rescoring (the lanes that need it only) and the percentile block as there; the gate is per lane.
+template <int K, int W>
+__global__ __launch_bounds__(64) void dtw_bank_stream_kernel(const BankWakeword *__restrict__ bank_ww, const int *__restrict__ bank_tlen,
+                                                             const long long *__restrict__ bank_trow, const float *__restrict__ bank_unit,
+                                                             const float *__restrict__ bank_raw, const float *__restrict__ mfcc,
+                                                             const int32_t *__restrict__ stream_wakeword, float *__restrict__ agg,
+                                                             float *__restrict__ avg, uint32_t *__restrict__ fix, int bank_W, BankStreamScore q) {
+    __shared__ float sl[kBankMaxTemplates * 64];   // a lane's scores (percentile modes), lane-minor
+    __shared__ float Pb[13 * 64];                  // band of the reference-shaped cell
+    const int lane = threadIdx.x;
+    const uint32_t row = blockIdx.x * 64u + lane, n_new = (uint32_t)q.n_new;
+    const bool valid = row < (uint32_t)(q.S * q.n_new);
+    const uint32_t s = valid ? row / n_new : 0u, i = row - s * n_new;
+    const int wi = valid ? stream_wakeword[s] : -1;
+    const bool live = wi >= 0 && wi < bank_W;   // an index outside the bank is "no wakeword" (the host checks it where it can see it)
+    const BankWakeword *bw = bank_ww + (live ? wi : 0);
+    // the window ending at new frame i: max_len frames, the oldest first
+    const float *xl = mfcc + (live ? ((size_t)s * q.frame_pitch + (q.first_new + i + 1 - (size_t)bw->max_len)) * K : (size_t)0);
+    const float own_athr = bw->avg_threshold;
+    const float athr = own_athr == own_athr ? own_athr : q.avg_threshold;
+    const int avg_e = bw->avg, T = live ? bw->count : 0, first = bw->first, ref_only = bw->ref_only, window_chk = bw->window_chk;
+    const bool do_avg = live && avg_e >= 0 && athr != 0.f;   // wakeword_comp.rs:85
+    const int mode = q.score_mode;
+
+    float acc = 0.f, avg_sc = 0.f;
+    bool scored = live;
+    for (int ti = -1; __any(scored && ti < T); ++ti) {
+        const bool act = scored && ti < T && (ti >= 0 || do_avg);
+        float sc = 0.f, chk = 0.f;
+        int L = 1;
+        size_t off = 0;
+        if (act) {
+            const int e = ti < 0 ? avg_e : first + ti;
+            L = bank_tlen[e];
+            off = (size_t)bank_trow[e] * K;
+            sc = bank_dtw<K, W, K>(xl, L, bank_unit + off, q.score_ref, chk);
+            // (dtw_bank_kernel recomputes for the whole wave once one lane is flagged: over fewer frames an unflagged lane stays unflagged)
+            if (window_chk && chk > kDtwFixLimit) chk = bank_chk_window<K, K>(xl, L);
+        }
+        const bool slow = act && (ref_only || chk > kDtwFixLimit);
+        const unsigned long long slow_mask = __ballot(slow);
+        if (slow_mask) {   // wave-uniform
+            if (slow) sc = bank_dtw_ref<K, W, K>(xl, L, bank_raw + off, q.score_ref, Pb, lane);
+            if (lane == 0 && fix) atomicAdd(dtw_fix_stats(fix), (unsigned long long)__popcll(slow_mask));   // rp_ctx_dtw_ref_pairs
+        }
+        if (act) {
+            if (ti < 0) {
+                avg_sc = sc;
+                // the averaged-template gate (wakeword_comp.rs:85-93), per lane: a window that did not pass leaves the walk, and the wave
+                // stops once no lane has a template left
+                if (q.gate && sc < athr) scored = false;
+            } else if (mode == 1) acc = ti == 0 ? sc : fmaxf(acc, sc);   // Max
+            else if (mode == 0) acc += sc;                               // Average: sequential sum in template order
+            else sl[ti * 64 + lane] = sc;
+        }
+    }
+    float a = 0.f;
+    if (scored) {
+        if (mode == 1) a = acc;
+        else if (mode == 0) a = acc / (float)T;
+        else {   // Median / percentiles: the lane sorts its column ascending, then the reference's f32 interpolation
+            for (int j = 1; j < T; ++j) {
+                const float x = sl[j * 64 + lane];
+                int p = j - 1;
+                while (p >= 0 && sl[p * 64 + lane] > x) { sl[(p + 1) * 64 + lane] = sl[p * 64 + lane]; --p; }
+                sl[(p + 1) * 64 + lane] = x;
+            }
+            a = percentile_sorted(sl + lane, T, percentile_of_mode(mode), 64);
+        }
+    }
+    // a window the gate rejected was never compared -> aggregate 0 (agg_store's rule, rp_dtw.hip); a stream without a wakeword: zero rows
+    if (valid) {
+        agg[row] = a;
+        avg[row] = do_avg ? avg_sc : 0.f;
+    }
+}
+
+template <int K, int W>
+static hipError_t launch_bank_stream_kw(hipStream_t st, const BankDev &b, const BankStreamScore &q, unsigned blocks) {
+    hipLaunchKernelGGL((dtw_bank_stream_kernel<K, W>), dim3(blocks), dim3(64), 0, st, b.ww, b.tlen, b.trow, b.unit, b.raw, q.mfcc, q.stream_wakeword,
+                       q.agg, q.avg, q.fix, b.W, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_dtw_bank_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q) {
+    if (q.S == 0 || q.n_new == 0) return hipSuccess;
+    if (b.W < 1 || dtw_register_tile(b.K, q.band) <= 0) return hipErrorNotSupported;
+    // rows are 32-bit in the kernel; no window may start before its stream's row
+    if (q.S > 0x7fffffffULL / q.n_new || q.first_new + 1 < (size_t)b.max_len || q.first_new + q.n_new > q.frame_pitch) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((q.S * q.n_new + 63) / 64);
+#define RP_BANK(KK, WW) launch_bank_stream_kw<KK, WW>(st, b, q, blocks)
 #define RP_BANK_BAND(KK) \
     switch (q.band) { case 3: return RP_BANK(KK, 3); case 4: return RP_BANK(KK, 4); case 5: return RP_BANK(KK, 5); default: return RP_BANK(KK, 6); }
     if (b.K == 5) { RP_BANK_BAND(5) }

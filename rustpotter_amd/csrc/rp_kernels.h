@@ -245,7 +245,9 @@ enum : uint32_t { kDtwRanMfma = 1u, kDtwRanMfmaWide = 2u, kDtwRanRagged = 4u, kD
                   // waves per workgroup of the dtw_mfma_kernel launches (two / three per SIMD)
                   kDtwRanWaves8 = 1024u, kDtwRanWaves12 = 2048u,
                   // dtw_bank_kernel (rp_dtw_bank.hip): per-stream wakewords from a bank
-                  kDtwRanBank = 4096u };
+                  kDtwRanBank = 4096u,
+                  // dtw_bank_stream_kernel (rp_dtw_bank.hip): the same for the new windows of a live-stream batch
+                  kDtwRanBankStream = 8192u };
 inline void dtw_mark(const DtwWork &wk, uint32_t bit) { if (wk.ran) *wk.ran |= bit; }
 __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { return reinterpret_cast<unsigned long long *>(fix + 2 + 2 * (size_t)kDtwFixCap); }
 // (dtw_fix_append, the kernels' side of the list: rp_device.h)
@@ -379,6 +381,23 @@ inline size_t dtw_bank_lds_bytes(int K, int max_len) {
 }
 // built for dtw_register_tile(K, band) > 0 (hipErrorNotSupported otherwise; band 0 is the caller's: all-zero scores)
 hipError_t launch_dtw_bank(hipStream_t st, const BankDev &b, const BankScore &q);
+// One call of a live-stream batch over a bank (rp_stream_batch_new_bank): stream s scores, against its own wakeword, the n_new windows that
+// end at its new frames first_new .. first_new + n_new - 1 of its MFCC row (frame_pitch frames a stream, as the GX forms of rp_dtw.hip; the
+// window of max_len(s) frames starts max_len(s) - 1 frames before its last one, so first_new >= the bank's max_len - 1).  The band reads up
+// to `band` frames behind a window's end: the rows end with that slack.  agg / avg [S][n_new]; a stream without a wakeword gets zero rows.
+// The averaged template is scored where a wakeword has one and its effective avg_threshold != 0 (BankScore::avg_mode 2).
+struct BankStreamScore {
+    const float *mfcc = nullptr;      // [S][frame_pitch][K]
+    size_t S = 0, frame_pitch = 0, first_new = 0, n_new = 0;
+    const int32_t *stream_wakeword = nullptr;
+    int band = 0, score_mode = 0;
+    float score_ref = 0.f;
+    int gate = 0;                     // detect-only: a window below its avg_threshold is not compared with the sample templates (aggregate 0)
+    float avg_threshold = 0.f;        // the config's value (a wakeword's own overrides it)
+    float *agg = nullptr, *avg = nullptr;   // [S][n_new]
+    uint32_t *fix = nullptr;          // DtwWork::fix, as BankScore::fix
+};
+hipError_t launch_dtw_bank_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a process that drives several GPUs
 // (one rp_ctx per device) has to set it on each of them.  Sets it once per (current device, kernel), thread-safe.
@@ -544,11 +563,18 @@ hipError_t launch_carry_rows(hipStream_t st, const float *src, size_t S, size_t 
 hipError_t launch_stream_state_init(hipStream_t st, void *state, size_t S);
 size_t stream_state_bytes();
 hipError_t launch_stream_state_reset(hipStream_t st, void *state, size_t S, long long stream, long long resume);
+// the same for streams first .. first + n - 1 (first + n <= S)
+hipError_t launch_stream_state_reset_range(hipStream_t st, void *state, size_t S, size_t first, size_t n, long long resume);
 // the state machine over this call's n_new frames for a detector that holds 1..8 wakewords (references and / or models); det_ww /
 // det_label (optional): the wakeword a detection belongs to and, when that wakeword is a model, its label index (else -1)
 hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, const float *vad_value, float vad_mode_value, size_t S,
                                     long long f0, int n_new, const ScanConfig &cfg, void *state, BatchDetection *det, int32_t *det_ww,
                                     int32_t *det_label, int32_t *n_det, int max_det);
+// the same state machine for a batch over a wakeword bank: per stream the window length, countdown, thresholds and avg test of its own
+// wakeword (as launch_scan_bank) over agg / avg [S][n_new]; det_ww: the stream's bank index, det_label: -1 (both optional)
+hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg,
+                                   const float *vad_value, float vad_mode_value, size_t S, long long f0, int n_new, const ScanConfig &cfg,
+                                   void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det);
 
 hipError_t launch_synth(hipStream_t st, uint64_t seed, uint64_t first_stream, size_t S, size_t n_samples,
                         size_t pcm_stride, float *pcm);

@@ -392,20 +392,26 @@ size_t stream_state_bytes() { return sizeof(StreamState); }
 
 // Rustpotter::reset (src/detector.rs:290-302) for one stream (or all, stream < 0): the next chunk only refills
 // the extractor, so the next frame seen is `resume`.
-__global__ __launch_bounds__(64) void stream_state_reset_kernel(StreamState *__restrict__ st, size_t S, long long stream, long long resume) {
-    const size_t s = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (s >= S || (stream >= 0 && (size_t)stream != s)) return;
+__global__ __launch_bounds__(64) void stream_state_reset_kernel(StreamState *__restrict__ st, size_t first, size_t n, long long resume) {
+    const size_t s = first + (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (s >= first + n) return;
     StreamState z = st[s];
     z.win_start = z.resume = resume;
     z.has_partial = 0; z.p_counter = 0; z.countdown = 0; z.vad_index = 0; z.voice_countdown = 0;
     for (int i = 0; i < 50; ++i) z.vad_window[i] = __builtin_nanf("");
     st[s] = z;
 }
-hipError_t launch_stream_state_reset(hipStream_t st, void *state, size_t S, long long stream, long long resume) {
-    if (S == 0) return hipSuccess;
-    hipLaunchKernelGGL(stream_state_reset_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, static_cast<StreamState *>(state), S,
-                       stream, resume);
+hipError_t launch_stream_state_reset_range(hipStream_t st, void *state, size_t S, size_t first, size_t n, long long resume) {
+    if (n == 0) return hipSuccess;
+    if (first > S || n > S - first) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_state_reset_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, static_cast<StreamState *>(state), first, n,
+                       resume);
     return hipGetLastError();
+}
+hipError_t launch_stream_state_reset(hipStream_t st, void *state, size_t S, long long stream, long long resume) {
+    if (stream >= 0 && (size_t)stream >= S) return hipSuccess;   // no such stream: nothing to reset, as before
+    return stream < 0 ? launch_stream_state_reset_range(st, state, S, 0, S, resume)
+                      : launch_stream_state_reset_range(st, state, S, (size_t)stream, 1, resume);
 }
 
 // scan_kernel over the n_new frames of this call with carried state.  Frame i of the call is absolute frame
@@ -509,6 +515,113 @@ hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, con
     if (ww.n < 1 || ww.n > kScanMaxWakewords) return hipErrorInvalidValue;
     hipLaunchKernelGGL(scan_stream_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, ww, vad_value, vad_mode_value, S, f0, n_new, cfg,
                        static_cast<StreamState *>(state), det, det_ww, det_label, n_det, max_det);
+    return hipGetLastError();
+}
+
+// scan_stream_kernel for a batch over a wakeword bank (rp_stream_batch_new_bank): the carried state machine with scan_bank_kernel's per-lane
+// rules -- stream s holds the one wakeword bank[stream_wakeword[s]]: its window length, its countdown max_len / 2, its own thresholds over
+// the config's, the avg test only when it has an averaged template and the effective avg_threshold != 0.  agg / avg [S][n_new]: row i is the
+// stream's own window ending at new frame i.  A detection reports the stream's bank index as its wakeword and label -1.  A stream without a
+// wakeword (index outside the bank) reports nothing and keeps its state as it is (rp_stream_batch_set_wakewords resets a stream it re-targets).
+__global__ __launch_bounds__(64) void scan_bank_stream_kernel(BankDev b, const int32_t *__restrict__ stream_wakeword, const float *__restrict__ agg,
+                                                              const float *__restrict__ avg, const float *__restrict__ vad_value,
+                                                              float vad_mode_value, size_t S, long long f0, int n_new, ScanConfig cfg,
+                                                              StreamState *__restrict__ state, BatchDetection *__restrict__ det,
+                                                              int32_t *__restrict__ det_ww, int32_t *__restrict__ det_label,
+                                                              int32_t *__restrict__ n_det, int max_det) {
+    __shared__ float vwin[50][64];
+    const int lane = threadIdx.x;
+    const size_t s = (size_t)blockIdx.x * 64 + lane;
+    if (s >= S) return;
+    constexpr size_t kHead = offsetof(StreamState, vad_window);   // as scan_stream_kernel: the VAD window travels only with a VAD
+    static_assert(kHead == 64, "StreamState head");
+    const int wi = stream_wakeword[s];
+    const bool none = wi < 0 || wi >= b.W;
+    int nd = 0;
+    if (!none) {
+        StreamState *sp = state + s;
+        StreamState z;
+        __builtin_memcpy(&z, sp, kHead);
+        const long long max_len = b.ww[wi].max_len;
+        const float own_thr = b.ww[wi].threshold, own_athr = b.ww[wi].avg_threshold;
+        const float thr = own_thr == own_thr ? own_thr : cfg.threshold;
+        const float athr = own_athr == own_athr ? own_athr : cfg.avg_threshold;
+        const bool avg_on = b.ww[wi].avg >= 0 && athr != 0.f;   // wakeword_comp.rs:85
+        const size_t row0 = s * (size_t)n_new;
+        const float *vv = vad_value ? vad_value + row0 : nullptr;
+        if (vv)
+            for (int i = 0; i < 50; ++i) vwin[i][lane] = sp->vad_window[i];
+        for (int i = 0; i < n_new; ++i) {
+            const long long f = f0 + i;
+            if (f < 0 || f < z.resume) continue;  // frames the extractor never emits (first chunk, refill after a reset)
+            bool should_run = true;
+            if (vv && !z.has_partial) {
+                vwin[z.vad_index][lane] = vv[i];
+                z.vad_index = z.vad_index >= 49 ? 0 : z.vad_index + 1;
+                float mn = RP_INF;
+                for (int j = 0; j < 50; ++j) { float w = vwin[j][lane]; if (w == w && w < mn) mn = w; }
+                mn = fmaxf(mn, 0.01f);
+                const float th = mn * vad_mode_value;
+                int n_high = 0;
+                for (int j = 0; j < 50; ++j) n_high += vwin[j][lane] > th ? 1 : 0;
+                if (n_high > 10) z.voice_countdown = 500;
+                if (z.voice_countdown > 0) { z.voice_countdown -= 1; should_run = true; } else should_run = false;
+            }
+            if (f - z.win_start + 1 < max_len) continue;
+            if (!should_run) continue;
+            if (z.countdown != 0) z.countdown -= 1;
+            if (z.has_partial) {
+                const bool done = z.countdown == 0 ? true : (cfg.eager && z.p_counter >= cfg.min_scores);
+                if (done) {
+                    z.has_partial = 0;
+                    if (z.p_counter >= cfg.min_scores) {
+                        if (nd < max_det) {
+                            BatchDetection d;
+                            d.stream = (int32_t)s; d.frame = (int32_t)f; d.window = (int32_t)z.p_window; d.counter = z.p_counter;
+                            d.avg_score = z.p_avg; d.score = z.p_score;
+                            det[s * (size_t)max_det + nd] = d;
+                            if (det_ww) det_ww[s * (size_t)max_det + nd] = z.p_ww;
+                            if (det_label) det_label[s * (size_t)max_det + nd] = -1;
+                        }
+                        ++nd;
+                        z.win_start = z.resume = cfg.fpf * ((f + 3) / cfg.fpf + 1);
+                        if (vv) { for (int j = 0; j < 50; ++j) vwin[j][lane] = __builtin_nanf(""); z.vad_index = 0; z.voice_countdown = 0; }
+                        continue;
+                    }
+                }
+            }
+            const float sc = agg[row0 + i];
+            float av = 0.f;
+            bool pass = true;
+            if (avg_on) { av = avg[row0 + i]; pass = !(av < athr); }
+            if (pass && sc > thr) {
+                const int counter = z.has_partial ? z.p_counter + 1 : 1;
+                if (!z.has_partial || z.p_score < sc) {
+                    z.p_score = sc; z.p_avg = av; z.p_window = f - max_len + 1; z.has_partial = 1;
+                    z.p_ww = wi; z.p_label = -1;
+                }
+                z.p_counter = counter;
+                z.countdown = (int)(max_len / 2);
+            }
+        }
+        if (vv)
+            for (int i = 0; i < 50; ++i) sp->vad_window[i] = vwin[i][lane];
+        __builtin_memcpy(sp, &z, kHead);
+    }
+    n_det[s] = nd;
+    for (int i = nd; i < max_det; ++i) {
+        det[s * (size_t)max_det + i] = BatchDetection{};
+        if (det_ww) det_ww[s * (size_t)max_det + i] = 0;
+        if (det_label) det_label[s * (size_t)max_det + i] = -1;
+    }
+}
+
+hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg,
+                                   const float *vad_value, float vad_mode_value, size_t S, long long f0, int n_new, const ScanConfig &cfg,
+                                   void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det) {
+    if (S == 0) return hipSuccess;
+    hipLaunchKernelGGL(scan_bank_stream_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, b, stream_wakeword, agg, avg, vad_value,
+                       vad_mode_value, S, f0, n_new, cfg, static_cast<StreamState *>(state), det, det_ww, det_label, n_det, max_det);
     return hipGetLastError();
 }
 

@@ -20,6 +20,10 @@ struct rp_stream_batch {
     std::vector<std::unique_ptr<StreamWakeword>> ww;  // 1..8 wakewords; the one reference of rp_stream_batch_new
     // made by rp_stream_batch_new: `agg` may be asked for, and its scoring keeps the kernel choice of that entry point (score_reference)
     bool single = false;
+    // made by rp_stream_batch_new_bank: stream s holds the one wakeword bank[bank_idx[s]] (`ww` is empty); max_len is then the bank's longest
+    // window, the history every stream keeps, and bank_agg / bank_avg [S][frames per call] are the streams' own windows' scores
+    const Bank *bank = nullptr;
+    DevBuf bank_idx, bank_agg, bank_avg;
     int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
     DevBuf det_ww, det_label, logits, mean, xrows, xs2;
     rp_detector_config cfg{};
@@ -74,6 +78,7 @@ static bool stream_batch_alloc(rp_stream_batch *b) {
         if (!w->agg.reserve(rows * sizeof(float) + 16) || !w->avg.reserve(rows * sizeof(float) + 16) ||
             (w->m && !w->label.reserve(rows * sizeof(int32_t) + 16)))
             return false;
+    if (b->bank && (!b->bank_agg.reserve(rows * sizeof(float) + 16) || !b->bank_avg.reserve(rows * sizeof(float) + 16))) return false;
     if (!b->pcm[0].reserve(pcm_bytes) || !b->pcm[1].reserve(pcm_bytes) || !b->mfcc[0].reserve(S * pitch * K * sizeof(float) + slack) ||
         !b->mfcc[1].reserve(S * pitch * K * sizeof(float) + slack) || !b->state.reserve(S * stream_state_bytes()) ||
         !b->scores.reserve(rows * (size_t)b->Tmax * sizeof(float) + 16) || !b->vad.reserve(rows * sizeof(float) + 16) ||
@@ -138,6 +143,29 @@ static int stream_batch_new(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword_s
         *out = b.release();
         return 0;
     });
+}
+
+// Wakeword indices of streams first .. first + n - 1 of a batch over a bank.  A host array (RP_CTX_HOST_POINTERS) is checked: an index outside
+// [-1, W) is an error that names the stream; a device array is taken as it is and the kernels treat such an index as -1, as the bank calls do.
+static bool bank_indices_ok(const Ctx *c, const Bank &bk, size_t first, size_t n, const int32_t *idx) {
+    if (!(c->flags & RP_CTX_HOST_POINTERS)) return true;
+    const int W = bk.dev.W;
+    for (size_t i = 0; i < n; ++i)
+        if (idx[i] < -1 || idx[i] >= W) {
+            set_last_error("stream " + std::to_string(first + i) + ": wakeword index " + std::to_string(idx[i]) + " is outside the bank (-1 .. " + std::to_string(W - 1) + ")");
+            return false;
+        }
+    return true;
+}
+// ... -> the batch's own device copy
+static bool bank_indices_put(rp_stream_batch *b, size_t first, size_t n, const int32_t *idx) {
+    Ctx *c = b->c;
+    const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
+    if (!b->bank_idx.reserve(b->S * sizeof(int32_t))) return false;
+    if (!hip_ok(hipMemcpyAsync(b->bank_idx.as<int32_t>() + first, idx, n * sizeof(int32_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream),
+                "hipMemcpyAsync(wakeword indices)")) return false;
+    // the caller's host array is the caller's again when the call returns
+    return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
 }
 
 // what the MFCC front of a call reads: the caller's chunks where they lie on the device, or the resampler's 16 kHz output
@@ -266,6 +294,7 @@ static bool score_model(rp_stream_batch *b, StreamWakeword &w, const NewFrames &
 
 // The live tail: VAD values of this call's n_new frames per stream (from `frames`, rows b->cap frames apart) when vad_mode is on, then
 // the timed scan that carries every stream's state machine on over the wakewords `sw` (dw / dl: each detection's wakeword and label)
+// (a batch over a bank: every stream's own wakeword, scores in bank_agg / bank_avg; `sw` is not read)
 static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, const ScanWakewords &sw, BatchDetection *dd, int32_t *dw,
                       int32_t *dl, int32_t *dn, int max_det) {
     Ctx *c = b->c;
@@ -274,12 +303,37 @@ static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, con
         dv = b->vad.as<float>();
         if (!hip_ok(launch_vad_value_rows(c->stream, frames, b->S, n_new, b->cap, b->K, dv), "vad_value_kernel")) return false;
     }
-    const ScanConfig sc = scan_config(b->cfg, b->max_len, false, (int)b->fpf());
     const float vm = vad_mode_value(b->cfg.vad_mode);
     const long long f0 = (long long)b->fpf() * (long long)b->chunks_seen - 3;
+    if (b->bank) {
+        const ScanConfig sc = scan_config(b->cfg, 0, true, (int)b->fpf());   // window length, thresholds and the avg test come from the bank, per stream
+        return timed(c, kKernelScan, "scan_bank_stream_kernel", [&] {
+            return launch_scan_bank_stream(c->stream, b->bank->dev, b->bank_idx.as<int32_t>(), b->bank_agg.as<float>(), b->bank_avg.as<float>(), dv, vm,
+                                           b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det);
+        });
+    }
+    const ScanConfig sc = scan_config(b->cfg, b->max_len, false, (int)b->fpf());
     return timed(c, kKernelScan, "scan_stream_kernel", [&] {
         return launch_scan_stream_multi(c->stream, sw, dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det);
     });
+}
+
+// A batch over a bank: every stream's n_new new windows against its own wakeword -> bank_agg / bank_avg.  band_size 0: no cell lies in the
+// band and every score is 0 (dtw.rs:64-75); an empty bank: no stream has a wakeword -- zero rows either way, as rp_batch_detect_bank.
+static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new, bool detect_only) {
+    Ctx *c = b->c;
+    const BankDev &bd = b->bank->dev;
+    const size_t bytes = b->S * n_new * sizeof(float);
+    if (b->cfg.band_size == 0 || bd.W == 0)
+        return hip_ok(hipMemsetAsync(b->bank_agg.p, 0, bytes, c->stream), "hipMemsetAsync") && hip_ok(hipMemsetAsync(b->bank_avg.p, 0, bytes, c->stream), "hipMemsetAsync");
+    BankStreamScore q;
+    q.mfcc = f.rows; q.S = b->S; q.frame_pitch = b->cap; q.first_new = f.fill; q.n_new = n_new; q.stream_wakeword = b->bank_idx.as<int32_t>();
+    q.band = (int)b->cfg.band_size; q.score_mode = (int)b->cfg.score_mode; q.score_ref = b->cfg.score_ref; q.gate = detect_only ? 1 : 0;
+    q.avg_threshold = b->cfg.avg_threshold; q.agg = b->bank_agg.as<float>(); q.avg = b->bank_avg.as<float>();
+    const DtwWork wk = c->dtw_work();
+    q.fix = wk.fix;
+    dtw_mark(wk, kDtwRanBankStream);
+    return timed(c, kKernelDtw, "dtw_bank_stream_kernel", [&] { return launch_dtw_bank_stream(c->stream, bd, q); });
 }
 
 // Score + scan stage: scores of this call's n_new windows per stream for every wakeword, then the state machine over all of them.
@@ -288,6 +342,7 @@ static bool stream_score_and_scan(rp_stream_batch *b, Staged &sg, const NewFrame
                                   int32_t *dn, int max_det, int32_t *det_wakeword, int32_t *det_label) {
     ScanWakewords sw{};
     sw.n = (int)b->ww.size();
+    if (b->bank && !score_bank_stream(b, f, n_new, detect_only)) return false;
     for (size_t j = 0; j < b->ww.size(); ++j)
         if (!(b->ww[j]->t ? score_reference(b, *b->ww[j], f, n_new, detect_only, sw, j) : score_model(b, *b->ww[j], f, n_new, sw, j))) return false;
     const size_t col = b->S * (size_t)max_det * sizeof(int32_t);
@@ -311,7 +366,7 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
         const size_t in_chunk = b->in_len * (size_t)b->channels;
         if (pcm_stride < n_chunks * in_chunk) { set_last_error("pcm_stride smaller than n_chunks * samples per chunk"); return -1; }
         if (!sample_format_ok(fmt)) return -1;
-        if (!b->single && agg) { set_last_error("rp_stream_batch_process: a batch of several wakewords has no single aggregate per window"); return -1; }
+        if (!b->single && !b->bank && agg) { set_last_error("rp_stream_batch_process: a batch of several wakewords has no single aggregate per window"); return -1; }
         const MfccTablesDev *tb = c->tables_for(b->K);
         if (!tb) return -1;
         const size_t S = b->S, n_new = b->fpf() * n_chunks;
@@ -329,8 +384,8 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
             !stream_score_and_scan(b, sg, f, n_new, detect_only, dd, dn, max_det, det_wakeword, det_label)) return -1;
         b->chunks_seen += n_chunks;
         if (!sg.back_detections(S, max_det, det, dd, n_det, dn)) return -1;
-        if (agg) {   // (one reference: a batch of several wakewords was refused above)
-            const DevBuf &dg = b->ww[0]->agg;
+        if (agg) {   // (one reference, or every stream's own wakeword: a batch of several wakewords was refused above)
+            const DevBuf &dg = b->bank ? b->bank_agg : b->ww[0]->agg;
             if (sg.host) { if (!sg.back(agg, dg.p, S * n_new * sizeof(float))) return -1; }
             else if (!hip_ok(hipMemcpyAsync(agg, dg.p, S * n_new * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync(D2D)")) return -1;
         }
@@ -355,6 +410,33 @@ int rp_stream_batch_new(rp_ctx *ctx, const rp_templates *t, const rp_detector_co
 int rp_stream_batch_new_multi(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword_spec *wakewords, int mfcc_size,
                               const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
     return stream_batch_new(ctx, n_wakewords, wakewords, mfcc_size, config, S, max_chunks_per_call, false, out);
+}
+// live-stream batches in which stream s holds its own wakeword bank[stream_wakeword[s]] (personal wakewords; rp_batch_detect_bank with the
+// state carried between calls)
+int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config, size_t S,
+                             size_t max_chunks_per_call, rp_stream_batch **out) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (!config || !out || !stream_wakeword) { set_last_error("null argument"); return -1; }
+        *out = nullptr;
+        Ctx *c = ctx->impl.get();
+        const Bank &bk = *bank->impl;
+        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new_bank: S and max_chunks_per_call must be >= 1"); return -1; }
+        if (!bank_band_ok(bk.dev, (int)config->band_size) || !bank_indices_ok(c, bk, 0, S, stream_wakeword)) return -1;   // before anything is allocated
+        std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
+        b->c = c; b->bank = &bk; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
+        // (an empty bank: no history; its mfcc_size is a placeholder -- the encode and frames stages run all the same, at the default size,
+        // and nobody reads their frames)
+        b->K = bk.dev.W ? bk.dev.K : 5; b->max_len = std::max(bk.dev.max_len, 1); b->Tmax = 1;
+        if (!bank_indices_put(b.get(), 0, S, stream_wakeword)) return -1;
+        if (!c->tables_for(b->K)) return -1;
+        b->hist_frames = (size_t)b->max_len - 1;   // every stream keeps the history of the bank's longest window; its own starts max_len(s) - 1 frames back
+        if (!stream_batch_alloc(b.get())) return -1;
+        *out = b.release();
+        return 0;
+    });
 }
 void rp_stream_batch_free(rp_stream_batch *b) { delete b; }
 size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b) { return b ? b->chunks_seen : 0; }
@@ -395,6 +477,11 @@ int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *fil
         if (b->chunks_seen) { set_last_error("rp_stream_batch_set_filters: the streams have already received audio"); return -1; }
         if (b->out_len != 480) { set_last_error(kFiltersNeed30ms); return -1; }
         const rp_gain_normalization_config &g = filters->gain_normalizer;
+        if (b->bank && g.enabled) {
+            set_last_error("rp_stream_batch_set_filters: the gain normaliser is not available on a batch over a wakeword bank (its window and "
+                           "rms_level_ref would be per stream, stream_filters_kernel takes one value of each); the band-pass filter alone is");
+            return -1;
+        }
         const int window = std::max(b->max_len / 3, 1);   // on_wakeword_change, src/detector.rs:337; set_rms_level_ref :47
         const size_t lv = b->S * b->max_chunks * sizeof(float) + 16, st = stream_filter_state_bytes(b->S, window);
         if (!b->filt_state.reserve(st) || !b->lv_rms.reserve(lv) || !b->lv_gain.reserve(lv)) return -1;
@@ -439,6 +526,31 @@ int rp_stream_batch_reset(rp_stream_batch *b, long long stream) {
         // the next chunk only refills the extractor: its three frames (3C-3 .. 3C-1) are never emitted
         return hip_ok(launch_stream_state_reset(c->stream, b->state.p, b->S, stream, (long long)b->fpf() * (long long)b->chunks_seen), "stream_state_reset_kernel") ? 0 : -1;
     });
+}
+
+// connect / disconnect of device slots: new indices for streams first_stream .. first_stream + n - 1, each reset as rp_stream_batch_reset does
+// (add_wakeword on a detector without wakewords calls reset(), src/detector.rs:304-307)
+int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *wakewords) {
+    bool touched = false;
+    const int r = guarded([&]() -> int {
+        Ctx *c = stream_batch_enter(b, true);
+        if (!c) return -1;
+        if (!b->bank) { set_last_error("rp_stream_batch_set_wakewords: the batch was not made by rp_stream_batch_new_bank"); return -1; }
+        if (first_stream > b->S || n > b->S - first_stream) {
+            set_last_error("rp_stream_batch_set_wakewords: streams " + std::to_string(first_stream) + " .. " + std::to_string(first_stream) + " + " +
+                           std::to_string(n) + " reach past the batch's " + std::to_string(b->S) + " streams");
+            return -1;
+        }
+        if (n == 0) return 0;
+        if (!wakewords) { set_last_error("null argument"); return -1; }
+        if (!bank_indices_ok(c, *b->bank, first_stream, n, wakewords)) return -1;   // a refused index leaves the batch as it was
+        touched = true;
+        if (!bank_indices_put(b, first_stream, n, wakewords)) return -1;
+        return hip_ok(launch_stream_state_reset_range(c->stream, b->state.p, b->S, first_stream, n, (long long)b->fpf() * (long long)b->chunks_seen),
+                      "stream_state_reset_kernel") ? 0 : -1;
+    });
+    if (r != 0 && touched) b->poisoned = true;
+    return r;
 }
 
 int rp_stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
