@@ -7,6 +7,7 @@
 #include <cstring>
 #include <fstream>
 
+#include "rp_capi.h"
 #include "rp_host.h"
 
 namespace rp {
@@ -87,7 +88,7 @@ Rustpotter *Rustpotter::create(const rp_config &cfg) {
     r->det_ = cfg.detector;
     r->filt_ = cfg.filters;
     r->has_vad_ = cfg.detector.vad_mode != RP_VAD_NONE;
-    r->vad_.mode_value = cfg.detector.vad_mode == RP_VAD_EASY ? 2.f : cfg.detector.vad_mode == RP_VAD_MEDIUM ? 2.5f : 3.f;
+    r->vad_.mode_value = vad_mode_value(cfg.detector.vad_mode);
     r->vad_.reset();
     r->configure_filters();
     return r.release();
@@ -133,7 +134,7 @@ void Rustpotter::reset() {
 void Rustpotter::update_detector_config(const rp_detector_config &c) {  // src/detector.rs:263-281
     det_ = c;
     has_vad_ = c.vad_mode != RP_VAD_NONE;
-    vad_.mode_value = c.vad_mode == RP_VAD_EASY ? 2.f : c.vad_mode == RP_VAD_MEDIUM ? 2.5f : 3.f;
+    vad_.mode_value = vad_mode_value(c.vad_mode);
     vad_.reset();
     reset();
 }

@@ -1,27 +1,26 @@
-// rp_scan.hip -- the detection state machine over precomputed window scores: vad_value_kernel, scan_kernel
-// (src/detector.rs:290-302,377-454, src/mfcc/vad.rs) and the live-stream variants that carry their state between calls.
+// rp_scan.hip -- the detection state machine over precomputed window scores (src/detector.rs:290-302,377-454, src/mfcc/vad.rs).
+// scan_frames is the state machine -- VAD gate, countdown, partial detection, reset after an emit -- and the only copy of it.  The four scan
+// kernels run it, one lane per stream, and add what is their own: scan_kernel the whole recording of a detector with up to eight wakewords,
+// scan_bank_kernel the same for a stream that holds one wakeword of a bank, scan_stream_kernel / scan_bank_stream_kernel the two over the new
+// frames of a live call with the state carried between calls.  Also here: the VAD value kernels and the staging of live-stream batches.
 #include "rp_device.h"
 
 #include <cstddef>
 
 namespace rp {
 
-// ------------------------------------------------------------------------- scan
-// The partial-detection / countdown state machine of src/detector.rs:377-454 with
-// reset() of :290-302, one lane per stream, over precomputed window scores.  Frame f
-// is emitted while chunk c = f/3 + 1 is processed; after an emit the extractor and the
-// window are cleared, the rest of that chunk's frames are dropped (find_map, :372-375),
-// chunk c+1 only refills the extractor, so the next frame seen is 3*(f/3) + 6.  In general, with fpf frames per
-// input frame (4 behind the 11.025 / 22.05 kHz resampler): frame f's last shift f+3 lies in chunk c = (f+3)/fpf, the
-// refill starts with shift fpf*(c+1) and its fourth shift completes frame fpf*(c+1).
-// mean(|mfcc|) of every frame, summed in coefficient order like VadDetector::is_voice (src/mfcc/vad.rs:12)
+// ------------------------------------------------------------------------- VAD value
+// mean(|mfcc|) of one frame, summed in coefficient order like VadDetector::is_voice (src/mfcc/vad.rs:12)
+__device__ __forceinline__ float vad_value_of(const float *__restrict__ v, int K) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s += fabsf(v[k]);
+    return s / (float)K;
+}
+
 __global__ __launch_bounds__(256) void vad_value_kernel(const float *__restrict__ mfcc, size_t n, int K, float *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float *v = mfcc + i * K;
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s += fabsf(v[k]);
-    out[i] = s / (float)K;
+    out[i] = vad_value_of(mfcc + i * K, K);
 }
 
 hipError_t launch_vad_value(hipStream_t st, const float *mfcc, size_t n_frames_total, int K, float *out) {
@@ -38,10 +37,7 @@ __global__ __launch_bounds__(256) void vad_value_rows_kernel(const float *__rest
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= S * n) return;
     const size_t s = i / n, f = i - s * n;
-    const float *v = mfcc + (s * pitch + f) * K;
-    float a = 0.f;
-    for (int k = 0; k < K; ++k) a += fabsf(v[k]);
-    out[i] = a / (float)K;
+    out[i] = vad_value_of(mfcc + (s * pitch + f) * K, K);
 }
 hipError_t launch_vad_value_rows(hipStream_t st, const float *mfcc, size_t S, size_t n, size_t pitch, int K, float *out) {
     if (S * n == 0) return hipSuccess;
@@ -51,6 +47,183 @@ hipError_t launch_vad_value_rows(hipStream_t st, const float *mfcc, size_t S, si
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------- lane state
+// The detector state of one stream: the countdown / partial detection / window bookkeeping (src/detector.rs:62-79) in absolute frame
+// numbers, and the VadDetector's scalars (its window lies in LDS while a kernel runs).  A whole-recording kernel starts from a fresh one;
+// a live stream carries it between rp_stream_batch_process calls as the head of its StreamState.
+struct ScanLane {
+    long long win_start, resume;
+    int has_partial, p_counter, countdown, vad_index, voice_countdown;
+    int p_ww;        // wakeword the partial detection belongs to (detectors that hold several)
+    int p_label;     // its label index when that wakeword is a model, else -1
+    int pad;
+    long long p_window;
+    float p_score, p_avg;
+};
+struct StreamState {
+    ScanLane lane;
+    float vad_window[50];
+};
+static_assert(sizeof(ScanLane) == 64 && sizeof(StreamState) == 264, "the carried state: a 64-byte head and the VAD window");
+
+// Rustpotter::reset (src/detector.rs:290-302) without the VAD window: no partial detection, an empty VAD, the next chunk only refills the
+// extractor, so the next frame seen is `resume`
+__device__ __forceinline__ void lane_reset(ScanLane &z, long long resume) {
+    z.win_start = z.resume = resume;
+    z.has_partial = 0; z.p_counter = 0; z.countdown = 0; z.vad_index = 0; z.voice_countdown = 0;
+}
+__device__ __forceinline__ ScanLane fresh_lane() {
+    ScanLane z;
+    lane_reset(z, 0);
+    z.p_ww = 0; z.p_label = -1; z.pad = 0;
+    z.p_window = 0; z.p_score = 0.f; z.p_avg = 0.f;
+    return z;
+}
+
+// ------------------------------------------------------------------------- output
+// The detections of a call, [S][max_det] with n_det [S]; det_ww / det_label (optional) are int32 columns beside det.
+struct ScanOut {
+    BatchDetection *det;
+    int32_t *det_ww, *det_label, *n_det;
+    int max_det;
+    // detection number nd of stream s, dropped when the stream's slots are full
+    __device__ __forceinline__ void put(size_t s, int nd, int32_t stream, long long f, const ScanLane &z, int32_t ww, int32_t label) const {
+        if (nd >= max_det) return;
+        BatchDetection d;
+        d.stream = stream; d.frame = (int32_t)f; d.window = (int32_t)z.p_window; d.counter = z.p_counter;
+        d.avg_score = z.p_avg; d.score = z.p_score;
+        const size_t slot = s * (size_t)max_det + nd;
+        det[slot] = d;
+        if (det_ww) det_ww[slot] = ww;
+        if (det_label) det_label[slot] = label;
+    }
+    // slots behind the detections a stream reports are zeroed (label -1, "no label"): the output block is a function of the input alone
+    __device__ __forceinline__ void finish(size_t s, int nd) const {
+        n_det[s] = nd;
+        for (int i = nd; i < max_det; ++i) {
+            det[s * (size_t)max_det + i] = BatchDetection{};
+            if (det_ww) det_ww[s * (size_t)max_det + i] = 0;
+            if (det_label) det_label[s * (size_t)max_det + i] = -1;
+        }
+    }
+};
+
+// ------------------------------------------------------------------------- proposals
+// What the wakewords of a lane say about one window: `found` when one proposes a detection
+struct Proposal {
+    bool found;
+    float score, avg;
+    int ww, label;   // the proposing wakeword and its label for this window (-1: not a model)
+};
+// run_wakeword_detectors, src/detector.rs:433-447: every wakeword whose own thresholds pass proposes a detection, the best score wins
+// (the first of equals).  `row` is the window's element of every wakeword's agg / avg / label.
+__device__ __forceinline__ Proposal propose_best(const ScanWakewords &ww, size_t row) {
+    Proposal p{false, 0.f, 0.f, -1, -1};
+    for (int j = 0; j < ww.n; ++j) {
+        const float sj = ww.agg[j][row];
+        float aj = 0.f;
+        bool pass = true;
+        if (ww.avg[j]) { aj = ww.avg[j][row]; pass = !(aj < ww.avg_threshold[j]); }
+        if (pass && sj > ww.threshold[j] && (p.ww < 0 || sj > p.score)) { p.ww = j; p.score = sj; p.avg = aj; }
+    }
+    p.found = p.ww >= 0;
+    if (p.found && ww.label[p.ww]) p.label = ww.label[p.ww][row];
+    return p;
+}
+// How a stream that holds the one wakeword bank[wi] runs the state machine, as a `Rustpotter` with that wakeword alone: its window length
+// (max_mfcc_frames; the countdown is max_len / 2), its own thresholds over the config's, the avg test only when it has an averaged template
+// and the effective avg_threshold != 0 (wakeword_comp.rs:85).  none: wi is outside the bank, the stream has no wakeword.
+struct BankLane {
+    bool none, avg_on;
+    int max_len;
+    float thr, athr;
+};
+__device__ __forceinline__ BankLane bank_lane(const BankDev &b, int wi, const ScanConfig &cfg) {
+    BankLane r{true, false, 0, 0.f, 0.f};
+    if (wi < 0 || wi >= b.W) return r;
+    const float own_thr = b.ww[wi].threshold, own_athr = b.ww[wi].avg_threshold;
+    r.none = false;
+    r.max_len = b.ww[wi].max_len;
+    r.thr = own_thr == own_thr ? own_thr : cfg.threshold;   // NaN: the wakeword has none of its own
+    r.athr = own_athr == own_athr ? own_athr : cfg.avg_threshold;
+    r.avg_on = b.ww[wi].avg >= 0 && r.athr != 0.f;
+    return r;
+}
+// the one wakeword wi of such a stream: `row` is the window's element of the stream's agg / avg
+__device__ __forceinline__ Proposal propose_one(const float *__restrict__ agg, const float *__restrict__ avg, size_t row, float thr, float athr,
+                                                bool avg_on, int wi) {
+    Proposal p{false, agg[row], 0.f, wi, -1};
+    bool pass = true;
+    if (avg_on) { p.avg = avg[row]; pass = !(p.avg < athr); }
+    p.found = pass && p.score > thr;
+    return p;
+}
+
+// ------------------------------------------------------------------------- the state machine
+// The partial-detection / countdown state machine of src/detector.rs:377-454 with reset() of :290-302 for one lane, over the frames
+// f0 .. f0+n-1 (i = 0 .. n-1; vv[i] is frame f0+i's VAD value, vwin[.][lane] the lane's VadDetector::window).  propose(f, i) is what the
+// lane's wakewords say about the window of max_len frames that ends at frame f, emit(nd, f, z) reports detection number nd of this call.
+// Returns the detections emitted.
+// Frame f is emitted while chunk c = f/3 + 1 is processed; after an emit the extractor and the window are cleared, the rest of that
+// chunk's frames are dropped (find_map, :372-375), chunk c+1 only refills the extractor, so the next frame seen is 3*(f/3) + 6.  In
+// general, with fpf frames per input frame (4 behind the 11.025 / 22.05 kHz resampler): frame f's last shift f+3 lies in chunk
+// c = (f+3)/fpf, the refill starts with shift fpf*(c+1) and its fourth shift completes frame fpf*(c+1).
+template <class Propose, class Emit>
+__device__ __forceinline__ int scan_frames(ScanLane &z, float (*vwin)[64], int lane, const float *__restrict__ vv, float vad_mode_value,
+                                           long long f0, int n, int max_len, const ScanConfig &cfg, Propose propose, Emit emit) {
+    int nd = 0;
+    for (int i = 0; i < n; ++i) {
+        const long long f = f0 + i;
+        if (f < 0 || f < z.resume) continue;  // frames the extractor never emits (first chunk of a live stream, refill after a reset)
+        // process_new_mfccs :379-383: the VAD only sees a frame while no partial detection exists (VadDetector, src/mfcc/vad.rs:3-50)
+        bool should_run = true;
+        if (vv && !z.has_partial) {
+            vwin[z.vad_index][lane] = vv[i];
+            z.vad_index = z.vad_index >= 49 ? 0 : z.vad_index + 1;
+            float mn = RP_INF;
+            for (int j = 0; j < 50; ++j) { float w = vwin[j][lane]; if (w == w && w < mn) mn = w; }
+            mn = fmaxf(mn, 0.01f);
+            const float th = mn * vad_mode_value;
+            int n_high = 0;
+            for (int j = 0; j < 50; ++j) n_high += vwin[j][lane] > th ? 1 : 0;
+            if (n_high > 10) z.voice_countdown = 500;
+            if (z.voice_countdown > 0) { z.voice_countdown -= 1; should_run = true; } else should_run = false;
+        }
+        if (f - z.win_start + 1 < max_len) continue;
+        if (!should_run) continue;
+        if (z.countdown != 0) z.countdown -= 1;
+        if (z.has_partial) {
+            const bool done = z.countdown == 0 ? true : (cfg.eager && z.p_counter >= cfg.min_scores);
+            if (done) {
+                z.has_partial = 0;  // take()
+                if (z.p_counter >= cfg.min_scores) {
+                    emit(nd, f, z);
+                    ++nd;
+                    lane_reset(z, cfg.fpf * ((f + 3) / cfg.fpf + 1));
+                    if (vv)
+                        for (int j = 0; j < 50; ++j) vwin[j][lane] = __builtin_nanf("");
+                    continue;
+                }
+            }
+        }
+        const Proposal p = propose(f, i);
+        if (p.found) {
+            const int counter = z.has_partial ? z.p_counter + 1 : 1;
+            if (!z.has_partial || z.p_score < p.score) {
+                z.p_score = p.score; z.p_avg = p.avg; z.p_window = f - max_len + 1; z.has_partial = 1;
+                z.p_ww = p.ww; z.p_label = p.label;
+            }
+            z.p_counter = counter;
+            z.countdown = (int)(max_len / 2);
+        }
+    }
+    return nd;
+}
+
+// ------------------------------------------------------------------------- whole recordings
+// One detector with ww.n wakewords of one window length over S recordings of n_frames frames; the window ending at frame f is element
+// f - max_len + 1 of the stream's row of n_win scores.  Its own: the front that finds the streams with a window that can fire.  det_ww
+// gets the window's label where the winning wakeword is a model, else the wakeword's index.
 __global__ __launch_bounds__(64) void scan_kernel(ScanWakewords ww, const float *__restrict__ vad_value, float vad_mode_value,
                                                   size_t S, size_t n_frames, ScanConfig cfg, BatchDetection *__restrict__ det,
                                                   int32_t *__restrict__ det_ww, int32_t *__restrict__ n_det, int max_det) {
@@ -99,97 +272,26 @@ __global__ __launch_bounds__(64) void scan_kernel(ScanWakewords ww, const float 
     }
     size_t s = (size_t)blockIdx.x * 64 + lane;
     if (s >= S) return;
-    // slots behind the detections a stream reports are zeroed: the output block is a function of the input alone
-    auto clear_from = [&](int from) {
-        BatchDetection zero{};
-        for (int i = from; i < max_det; ++i) {
-            det[s * (size_t)max_det + i] = zero;
-            if (det_ww) det_ww[s * (size_t)max_det + i] = 0;
-        }
-    };
-    if (!candidate) { n_det[s] = 0; clear_from(0); return; }
+    const ScanOut out{det, det_ww, nullptr, n_det, max_det};
+    if (!candidate) { out.finish(s, 0); return; }
     const size_t row0 = s * (size_t)(n_win > 0 ? n_win : 0);
     const float *vv = vad_value ? vad_value + s * n_frames : nullptr;
-    // VadDetector state (src/mfcc/vad.rs:3-50)
-    int vad_index = 0, voice_countdown = 0;
     if (vv)
         for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
-    long win_start = 0, resume = 0;
-    bool has_partial = false;
-    float p_score = 0.f, p_avg = 0.f;
-    int p_ww = 0;
-    int p_counter = 0, p_window = 0, countdown = 0, nd = 0;
-    for (long f = 0; f < (long)n_frames; ++f) {
-        if (f < resume) continue;
-        // process_new_mfccs :379-383: the VAD only sees a frame while no partial detection exists
-        bool should_run = true;
-        if (vv && !has_partial) {
-            vwin[vad_index][lane] = vv[f];
-            vad_index = vad_index >= 49 ? 0 : vad_index + 1;
-            float mn = RP_INF;
-            for (int i = 0; i < 50; ++i) { float w = vwin[i][lane]; if (w == w && w < mn) mn = w; }
-            mn = fmaxf(mn, 0.01f);
-            const float th = mn * vad_mode_value;
-            int n_high = 0;
-            for (int i = 0; i < 50; ++i) n_high += vwin[i][lane] > th ? 1 : 0;
-            if (n_high > 10) voice_countdown = 500;
-            if (voice_countdown > 0) { voice_countdown -= 1; should_run = true; } else should_run = false;
-        }
-        if (f - win_start + 1 < max_len) continue;
-        if (!should_run) continue;
-        const long w = f - max_len + 1;
-        if (countdown != 0) countdown -= 1;
-        if (has_partial) {
-            bool done = countdown == 0 ? true : (cfg.eager && p_counter >= cfg.min_scores);
-            if (done) {
-                has_partial = false;  // take()
-                if (p_counter >= cfg.min_scores) {
-                    if (nd < max_det) {
-                        BatchDetection d;
-                        d.stream = (int32_t)s + cfg.stream_base; d.frame = (int32_t)f; d.window = p_window; d.counter = p_counter;
-                        d.avg_score = p_avg; d.score = p_score;
-                        det[s * (size_t)max_det + nd] = d;
-                        if (det_ww) det_ww[s * (size_t)max_det + nd] = p_ww;
-                    }
-                    ++nd;
-                    win_start = resume = cfg.fpf * ((f + 3) / cfg.fpf + 1);  // reset()
-                    if (vv) {  // vad.reset()
-                        for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
-                        vad_index = 0; voice_countdown = 0;
-                    }
-                    continue;
-                }
-            }
-        }
-        // run_wakeword_detectors, src/detector.rs:433-447: every wakeword whose own thresholds pass proposes a
-        // detection, the best score wins (the first of equals)
-        float sc = 0.f, av = 0.f;
-        int best = -1;
-        for (int j = 0; j < ww.n; ++j) {
-            const float sj = ww.agg[j][row0 + w];
-            float aj = 0.f;
-            bool pass = true;
-            if (ww.avg[j]) { aj = ww.avg[j][row0 + w]; pass = !(aj < ww.avg_threshold[j]); }
-            if (pass && sj > ww.threshold[j] && (best < 0 || sj > sc)) { best = j; sc = sj; av = aj; }
-        }
-        if (best >= 0) {
-            int counter = has_partial ? p_counter + 1 : 1;
-            if (!has_partial || p_score < sc) {
-                p_score = sc; p_avg = av; p_window = (int)w; has_partial = true;
-                p_ww = ww.label[best] ? ww.label[best][row0 + w] : best;
-            }
-            p_counter = counter;
-            countdown = (int)(max_len / 2);
-        }
-    }
-    n_det[s] = nd;
-    clear_from(nd < max_det ? nd : max_det);
+    ScanLane z = fresh_lane();
+    const int nd = scan_frames(
+        z, vwin, lane, vv, vad_mode_value, 0, (int)n_frames, cfg.max_len, cfg,
+        [&](long long f, int) { return propose_best(ww, row0 + (size_t)(f - max_len + 1)); },
+        [&](int nd, long long f, const ScanLane &z) {
+            out.put(s, nd, (int32_t)s + cfg.stream_base, f, z, ww.label[z.p_ww] ? z.p_label : z.p_ww, -1);
+        });
+    out.finish(s, nd);
 }
 
 hipError_t launch_scan_multi(hipStream_t st, const ScanWakewords &ww, const float *vad_value, float vad_mode_value, size_t S,
                              size_t n_frames, const ScanConfig &cfg, BatchDetection *det, int32_t *det_ww, int32_t *n_det, int max_det) {
     if (S == 0) return hipSuccess;
-    if (ww.n < 1 || ww.n > kScanMaxWakewords) return hipErrorInvalidValue;
+    if (ww.n < 1 || ww.n > kScanMaxWakewords || n_frames > 0x7fffffffULL) return hipErrorInvalidValue;   // a detection's frame is an int32
     size_t blocks = (S + 63) / 64;
     hipLaunchKernelGGL(scan_kernel, dim3((unsigned)blocks), dim3(64), 0, st, ww, vad_value, vad_mode_value, S, n_frames, cfg, det, det_ww,
                        n_det, max_det);
@@ -207,12 +309,9 @@ hipError_t launch_scan(hipStream_t st, const float *agg, const float *avg, const
     return launch_scan_multi(st, ww, vad_value, vad_mode_value, S, n_frames, cfg, det, nullptr, n_det, max_det);
 }
 
-// scan_kernel for a wakeword bank (rp_dtw_bank.hip): stream s runs the state machine of a `Rustpotter` that holds the one wakeword
-// bank[stream_wakeword[s]] -- its window length (max_mfcc_frames), its countdown max_len / 2, its own thresholds over the config's, the
-// avg test only when it has an averaged template and the effective avg_threshold != 0 -- over its rows agg / avg + s * win_pitch.  A stream
-// without a wakeword (index outside the bank) reports nothing.  `hot` as in scan_kernel: the flags dtw_bank_kernel raised, put back to 0 here.
-// A kernel of its own: scan_kernel's front (the sweep of 64 contiguous score rows, up to eight wakewords per stream with one window length
-// for the block) does not apply, and here the window length is a per-lane value.
+// The same for a wakeword bank (rp_dtw_bank.hip): stream s holds the one wakeword bank[stream_wakeword[s]] (bank_lane), so the window
+// length is a per-lane value; its rows are agg / avg + s * win_pitch.  A stream without a wakeword, or with fewer frames than its
+// window, reports nothing.  `hot` as in scan_kernel: the flags dtw_bank_kernel raised, put back to 0 here.
 __global__ __launch_bounds__(64) void scan_bank_kernel(BankDev b, const int32_t *__restrict__ stream_wakeword, const float *__restrict__ agg,
                                                        const float *__restrict__ avg, size_t win_pitch, const float *__restrict__ vad_value,
                                                        float vad_mode_value, size_t S, size_t n_frames, ScanConfig cfg,
@@ -228,105 +327,34 @@ __global__ __launch_bounds__(64) void scan_bank_kernel(BankDev b, const int32_t 
         if (candidate) hot[s] = 0u;   // consumed (Ctx::hot_flags)
     }
     const int wi = stream_wakeword[s];
-    const bool none = wi < 0 || wi >= b.W;
-    const long max_len = none ? 0 : b.ww[wi].max_len;
-    auto clear_from = [&](int from) {
-        BatchDetection zero{};
-        for (int i = from; i < max_det; ++i) det[s * (size_t)max_det + i] = zero;
-    };
-    if (none || !candidate || (long)n_frames < max_len) { n_det[s] = 0; clear_from(0); return; }
-    const float own_thr = b.ww[wi].threshold, own_athr = b.ww[wi].avg_threshold;
-    const float thr = own_thr == own_thr ? own_thr : cfg.threshold;
-    const float athr = own_athr == own_athr ? own_athr : cfg.avg_threshold;
-    const bool avg_on = avg && b.ww[wi].avg >= 0 && athr != 0.f;   // wakeword_comp.rs:85
+    const BankLane r = bank_lane(b, wi, cfg);
+    const int max_len = r.max_len;
+    const ScanOut out{det, nullptr, nullptr, n_det, max_det};
+    if (r.none || !candidate || n_frames < (size_t)max_len) { out.finish(s, 0); return; }
+    const bool avg_on = avg && r.avg_on;
     const size_t row0 = s * win_pitch;
     const float *vv = vad_value ? vad_value + s * n_frames : nullptr;
-    int vad_index = 0, voice_countdown = 0;
     if (vv)
         for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
-    long win_start = 0, resume = 0;
-    bool has_partial = false;
-    float p_score = 0.f, p_avg = 0.f;
-    int p_counter = 0, p_window = 0, countdown = 0, nd = 0;
-    for (long f = 0; f < (long)n_frames; ++f) {
-        if (f < resume) continue;
-        // process_new_mfccs :379-383: the VAD only sees a frame while no partial detection exists
-        bool should_run = true;
-        if (vv && !has_partial) {
-            vwin[vad_index][lane] = vv[f];
-            vad_index = vad_index >= 49 ? 0 : vad_index + 1;
-            float mn = RP_INF;
-            for (int i = 0; i < 50; ++i) { float w = vwin[i][lane]; if (w == w && w < mn) mn = w; }
-            mn = fmaxf(mn, 0.01f);
-            const float th = mn * vad_mode_value;
-            int n_high = 0;
-            for (int i = 0; i < 50; ++i) n_high += vwin[i][lane] > th ? 1 : 0;
-            if (n_high > 10) voice_countdown = 500;
-            if (voice_countdown > 0) { voice_countdown -= 1; should_run = true; } else should_run = false;
-        }
-        if (f - win_start + 1 < max_len) continue;
-        if (!should_run) continue;
-        const long w = f - max_len + 1;
-        if (countdown != 0) countdown -= 1;
-        if (has_partial) {
-            bool done = countdown == 0 ? true : (cfg.eager && p_counter >= cfg.min_scores);
-            if (done) {
-                has_partial = false;  // take()
-                if (p_counter >= cfg.min_scores) {
-                    if (nd < max_det) {
-                        BatchDetection d;
-                        d.stream = (int32_t)s + cfg.stream_base; d.frame = (int32_t)f; d.window = p_window; d.counter = p_counter;
-                        d.avg_score = p_avg; d.score = p_score;
-                        det[s * (size_t)max_det + nd] = d;
-                    }
-                    ++nd;
-                    win_start = resume = cfg.fpf * ((f + 3) / cfg.fpf + 1);  // reset()
-                    if (vv) {  // vad.reset()
-                        for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
-                        vad_index = 0; voice_countdown = 0;
-                    }
-                    continue;
-                }
-            }
-        }
-        const float sc = agg[row0 + w];
-        float av = 0.f;
-        bool pass = true;
-        if (avg_on) { av = avg[row0 + w]; pass = !(av < athr); }
-        if (pass && sc > thr) {
-            int counter = has_partial ? p_counter + 1 : 1;
-            if (!has_partial || p_score < sc) { p_score = sc; p_avg = av; p_window = (int)w; has_partial = true; }
-            p_counter = counter;
-            countdown = (int)(max_len / 2);
-        }
-    }
-    n_det[s] = nd;
-    clear_from(nd < max_det ? nd : max_det);
+    ScanLane z = fresh_lane();
+    const int nd = scan_frames(
+        z, vwin, lane, vv, vad_mode_value, 0, (int)n_frames, max_len, cfg,
+        [&](long long f, int) { return propose_one(agg, avg, row0 + (size_t)(f - max_len + 1), r.thr, r.athr, avg_on, wi); },
+        [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s + cfg.stream_base, f, z, 0, -1); });
+    out.finish(s, nd);
 }
 
 hipError_t launch_scan_bank(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg, size_t win_pitch,
                             const float *vad_value, float vad_mode_value, size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det,
                             int32_t *n_det, int max_det, uint32_t *hot) {
     if (S == 0) return hipSuccess;
+    if (n_frames > 0x7fffffffULL) return hipErrorInvalidValue;   // a detection's frame is an int32
     hipLaunchKernelGGL(scan_bank_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, b, stream_wakeword, agg, avg, win_pitch, vad_value,
                        vad_mode_value, S, n_frames, cfg, det, n_det, max_det, hot);
     return hipGetLastError();
 }
 
 // ------------------------------------------------------------- streaming batches
-// State of one live stream between rp_stream_batch_process calls: the detector's countdown / partial
-// detection / window bookkeeping (src/detector.rs:62-79) in absolute frame numbers, and the VadDetector.
-struct StreamState {
-    long long win_start, resume;
-    int has_partial, p_counter, countdown, vad_index, voice_countdown;
-    int p_ww;        // wakeword the partial detection belongs to (detectors that hold several)
-    int p_label;     // its label index when that wakeword is a model, else -1
-    int pad;
-    long long p_window;
-    float p_score, p_avg;
-    float vad_window[50];
-};
-
 // hist [S][hist_pitch] = the last 480-sample chunk of the previous call (old_hist row + old_off) | the new chunks decoded
 template <class TIN>
 __global__ __launch_bounds__(256) void stream_stage_kernel(const TIN *__restrict__ pcm, int channels, size_t S, size_t n_new,
@@ -377,9 +405,7 @@ __global__ __launch_bounds__(64) void stream_state_init_kernel(StreamState *__re
     const size_t s = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (s >= S) return;
     StreamState z;
-    z.win_start = 0; z.resume = 0; z.has_partial = 0; z.p_counter = 0; z.countdown = 0; z.vad_index = 0; z.voice_countdown = 0; z.pad = 0;
-    z.p_ww = 0; z.p_label = -1;
-    z.p_window = 0; z.p_score = 0.f; z.p_avg = 0.f;
+    z.lane = fresh_lane();
     for (int i = 0; i < 50; ++i) z.vad_window[i] = __builtin_nanf("");
     st[s] = z;
 }
@@ -396,8 +422,7 @@ __global__ __launch_bounds__(64) void stream_state_reset_kernel(StreamState *__r
     const size_t s = first + (size_t)blockIdx.x * 64 + threadIdx.x;
     if (s >= first + n) return;
     StreamState z = st[s];
-    z.win_start = z.resume = resume;
-    z.has_partial = 0; z.p_counter = 0; z.countdown = 0; z.vad_index = 0; z.voice_countdown = 0;
+    lane_reset(z.lane, resume);
     for (int i = 0; i < 50; ++i) z.vad_window[i] = __builtin_nanf("");
     st[s] = z;
 }
@@ -414,9 +439,23 @@ hipError_t launch_stream_state_reset(hipStream_t st, void *state, size_t S, long
                       : launch_stream_state_reset_range(st, state, S, (size_t)stream, 1, resume);
 }
 
-// scan_kernel over the n_new frames of this call with carried state.  Frame i of the call is absolute frame
-// f0 + i; the window ending at it is row i of every wakeword's agg / avg (the history prefix is max_len-1 frames long).
-// Several wakewords as in scan_kernel (run_wakeword_detectors, src/detector.rs:433-447).
+// The live kernels run scan_frames over the n_new frames of this call with the stream's carried state.  Frame i of the call is absolute
+// frame f0 + i; the window ending at it is row i of the stream's agg / avg (the history prefix is max_len-1 frames long).  The 64-byte
+// head of the state travels every call, the 200 bytes of the VAD window only in detectors that have a VAD (as one struct copy each way a
+// call moved 34 MB in 264-byte strides for 65 536 streams: 0.019 of a 0.32 ms live call).
+__device__ __forceinline__ void stream_state_load(const StreamState *sp, ScanLane &z, float (*vwin)[64], int lane, bool vad) {
+    __builtin_memcpy(&z, &sp->lane, sizeof(ScanLane));
+    if (vad)
+        for (int i = 0; i < 50; ++i) vwin[i][lane] = sp->vad_window[i];
+}
+__device__ __forceinline__ void stream_state_store(StreamState *sp, const ScanLane &z, float (*vwin)[64], int lane, bool vad) {
+    if (vad)
+        for (int i = 0; i < 50; ++i) sp->vad_window[i] = vwin[i][lane];
+    __builtin_memcpy(&sp->lane, &z, sizeof(ScanLane));
+}
+
+// scan_kernel's detector (several wakewords, run_wakeword_detectors) on live streams: det_ww gets the winning wakeword's index,
+// det_label the window's label where that wakeword is a model, else -1.
 __global__ __launch_bounds__(64) void scan_stream_kernel(ScanWakewords ww, const float *__restrict__ vad_value, float vad_mode_value, size_t S,
                                                          long long f0, int n_new, ScanConfig cfg, StreamState *__restrict__ state,
                                                          BatchDetection *__restrict__ det, int32_t *__restrict__ det_ww,
@@ -425,87 +464,17 @@ __global__ __launch_bounds__(64) void scan_stream_kernel(ScanWakewords ww, const
     const int lane = threadIdx.x;
     const size_t s = (size_t)blockIdx.x * 64 + lane;
     if (s >= S) return;
-    // the 64-byte head of the state travels every call, the 200 bytes of the VAD window only in detectors that have a VAD (as one struct
-    // copy each way a call moved 34 MB in 264-byte strides for 65 536 streams: 0.019 of a 0.32 ms live call)
-    constexpr size_t kHead = offsetof(StreamState, vad_window);
-    static_assert(kHead == 64, "StreamState head");
-    StreamState *sp = state + s;
-    StreamState z;
-    __builtin_memcpy(&z, sp, kHead);
-    const long long max_len = cfg.max_len;
+    const ScanOut out{det, det_ww, det_label, n_det, max_det};
     const size_t row0 = s * (size_t)n_new;
-    const float *vv = vad_value ? vad_value + s * (size_t)n_new : nullptr;
-    if (vv)
-        for (int i = 0; i < 50; ++i) vwin[i][lane] = sp->vad_window[i];
-    int nd = 0;
-    for (int i = 0; i < n_new; ++i) {
-        const long long f = f0 + i;
-        if (f < 0 || f < z.resume) continue;  // frames the extractor never emits (first chunk, refill after a reset)
-        bool should_run = true;
-        if (vv && !z.has_partial) {
-            vwin[z.vad_index][lane] = vv[i];
-            z.vad_index = z.vad_index >= 49 ? 0 : z.vad_index + 1;
-            float mn = RP_INF;
-            for (int j = 0; j < 50; ++j) { float w = vwin[j][lane]; if (w == w && w < mn) mn = w; }
-            mn = fmaxf(mn, 0.01f);
-            const float th = mn * vad_mode_value;
-            int n_high = 0;
-            for (int j = 0; j < 50; ++j) n_high += vwin[j][lane] > th ? 1 : 0;
-            if (n_high > 10) z.voice_countdown = 500;
-            if (z.voice_countdown > 0) { z.voice_countdown -= 1; should_run = true; } else should_run = false;
-        }
-        if (f - z.win_start + 1 < max_len) continue;
-        if (!should_run) continue;
-        if (z.countdown != 0) z.countdown -= 1;
-        if (z.has_partial) {
-            const bool done = z.countdown == 0 ? true : (cfg.eager && z.p_counter >= cfg.min_scores);
-            if (done) {
-                z.has_partial = 0;
-                if (z.p_counter >= cfg.min_scores) {
-                    if (nd < max_det) {
-                        BatchDetection d;
-                        d.stream = (int32_t)s; d.frame = (int32_t)f; d.window = (int32_t)z.p_window; d.counter = z.p_counter;
-                        d.avg_score = z.p_avg; d.score = z.p_score;
-                        det[s * (size_t)max_det + nd] = d;
-                        if (det_ww) det_ww[s * (size_t)max_det + nd] = z.p_ww;
-                        if (det_label) det_label[s * (size_t)max_det + nd] = z.p_label;
-                    }
-                    ++nd;
-                    z.win_start = z.resume = cfg.fpf * ((f + 3) / cfg.fpf + 1);
-                    if (vv) { for (int j = 0; j < 50; ++j) vwin[j][lane] = __builtin_nanf(""); z.vad_index = 0; z.voice_countdown = 0; }
-                    continue;
-                }
-            }
-        }
-        // every wakeword whose own thresholds pass proposes a detection, the best score wins (the first of equals)
-        float sc = 0.f, av = 0.f;
-        int best = -1;
-        for (int j = 0; j < ww.n; ++j) {
-            const float sj = ww.agg[j][row0 + i];
-            float aj = 0.f;
-            bool pass = true;
-            if (ww.avg[j]) { aj = ww.avg[j][row0 + i]; pass = !(aj < ww.avg_threshold[j]); }
-            if (pass && sj > ww.threshold[j] && (best < 0 || sj > sc)) { best = j; sc = sj; av = aj; }
-        }
-        if (best >= 0) {
-            const int counter = z.has_partial ? z.p_counter + 1 : 1;
-            if (!z.has_partial || z.p_score < sc) {
-                z.p_score = sc; z.p_avg = av; z.p_window = f - max_len + 1; z.has_partial = 1;
-                z.p_ww = best; z.p_label = ww.label[best] ? ww.label[best][row0 + i] : -1;
-            }
-            z.p_counter = counter;
-            z.countdown = (int)(max_len / 2);
-        }
-    }
-    if (vv)
-        for (int i = 0; i < 50; ++i) sp->vad_window[i] = vwin[i][lane];
-    __builtin_memcpy(sp, &z, kHead);
-    n_det[s] = nd;
-    for (int i = nd; i < max_det; ++i) {
-        det[s * (size_t)max_det + i] = BatchDetection{};
-        if (det_ww) det_ww[s * (size_t)max_det + i] = 0;
-        if (det_label) det_label[s * (size_t)max_det + i] = -1;   // "no label", as the header says
-    }
+    const float *vv = vad_value ? vad_value + row0 : nullptr;
+    ScanLane z;
+    stream_state_load(state + s, z, vwin, lane, vv != nullptr);
+    const int nd = scan_frames(
+        z, vwin, lane, vv, vad_mode_value, f0, n_new, cfg.max_len, cfg,
+        [&](long long, int i) { return propose_best(ww, row0 + i); },
+        [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s, f, z, z.p_ww, z.p_label); });
+    stream_state_store(state + s, z, vwin, lane, vv != nullptr);
+    out.finish(s, nd);
 }
 
 hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, const float *vad_value, float vad_mode_value, size_t S,
@@ -518,11 +487,9 @@ hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, con
     return hipGetLastError();
 }
 
-// scan_stream_kernel for a batch over a wakeword bank (rp_stream_batch_new_bank): the carried state machine with scan_bank_kernel's per-lane
-// rules -- stream s holds the one wakeword bank[stream_wakeword[s]]: its window length, its countdown max_len / 2, its own thresholds over
-// the config's, the avg test only when it has an averaged template and the effective avg_threshold != 0.  agg / avg [S][n_new]: row i is the
-// stream's own window ending at new frame i.  A detection reports the stream's bank index as its wakeword and label -1.  A stream without a
-// wakeword (index outside the bank) reports nothing and keeps its state as it is (rp_stream_batch_set_wakewords resets a stream it re-targets).
+// scan_bank_kernel's detector on live streams (rp_stream_batch_new_bank): stream s holds the one wakeword bank[stream_wakeword[s]]
+// (bank_lane); agg / avg [S][n_new].  A detection reports the stream's bank index as its wakeword and label -1.  A stream without a
+// wakeword reports nothing and keeps its state as it is (rp_stream_batch_set_wakewords resets a stream it re-targets).
 __global__ __launch_bounds__(64) void scan_bank_stream_kernel(BankDev b, const int32_t *__restrict__ stream_wakeword, const float *__restrict__ agg,
                                                               const float *__restrict__ avg, const float *__restrict__ vad_value,
                                                               float vad_mode_value, size_t S, long long f0, int n_new, ScanConfig cfg,
@@ -533,87 +500,22 @@ __global__ __launch_bounds__(64) void scan_bank_stream_kernel(BankDev b, const i
     const int lane = threadIdx.x;
     const size_t s = (size_t)blockIdx.x * 64 + lane;
     if (s >= S) return;
-    constexpr size_t kHead = offsetof(StreamState, vad_window);   // as scan_stream_kernel: the VAD window travels only with a VAD
-    static_assert(kHead == 64, "StreamState head");
+    const ScanOut out{det, det_ww, det_label, n_det, max_det};
     const int wi = stream_wakeword[s];
-    const bool none = wi < 0 || wi >= b.W;
+    const BankLane r = bank_lane(b, wi, cfg);
     int nd = 0;
-    if (!none) {
-        StreamState *sp = state + s;
-        StreamState z;
-        __builtin_memcpy(&z, sp, kHead);
-        const long long max_len = b.ww[wi].max_len;
-        const float own_thr = b.ww[wi].threshold, own_athr = b.ww[wi].avg_threshold;
-        const float thr = own_thr == own_thr ? own_thr : cfg.threshold;
-        const float athr = own_athr == own_athr ? own_athr : cfg.avg_threshold;
-        const bool avg_on = b.ww[wi].avg >= 0 && athr != 0.f;   // wakeword_comp.rs:85
+    if (!r.none) {
         const size_t row0 = s * (size_t)n_new;
         const float *vv = vad_value ? vad_value + row0 : nullptr;
-        if (vv)
-            for (int i = 0; i < 50; ++i) vwin[i][lane] = sp->vad_window[i];
-        for (int i = 0; i < n_new; ++i) {
-            const long long f = f0 + i;
-            if (f < 0 || f < z.resume) continue;  // frames the extractor never emits (first chunk, refill after a reset)
-            bool should_run = true;
-            if (vv && !z.has_partial) {
-                vwin[z.vad_index][lane] = vv[i];
-                z.vad_index = z.vad_index >= 49 ? 0 : z.vad_index + 1;
-                float mn = RP_INF;
-                for (int j = 0; j < 50; ++j) { float w = vwin[j][lane]; if (w == w && w < mn) mn = w; }
-                mn = fmaxf(mn, 0.01f);
-                const float th = mn * vad_mode_value;
-                int n_high = 0;
-                for (int j = 0; j < 50; ++j) n_high += vwin[j][lane] > th ? 1 : 0;
-                if (n_high > 10) z.voice_countdown = 500;
-                if (z.voice_countdown > 0) { z.voice_countdown -= 1; should_run = true; } else should_run = false;
-            }
-            if (f - z.win_start + 1 < max_len) continue;
-            if (!should_run) continue;
-            if (z.countdown != 0) z.countdown -= 1;
-            if (z.has_partial) {
-                const bool done = z.countdown == 0 ? true : (cfg.eager && z.p_counter >= cfg.min_scores);
-                if (done) {
-                    z.has_partial = 0;
-                    if (z.p_counter >= cfg.min_scores) {
-                        if (nd < max_det) {
-                            BatchDetection d;
-                            d.stream = (int32_t)s; d.frame = (int32_t)f; d.window = (int32_t)z.p_window; d.counter = z.p_counter;
-                            d.avg_score = z.p_avg; d.score = z.p_score;
-                            det[s * (size_t)max_det + nd] = d;
-                            if (det_ww) det_ww[s * (size_t)max_det + nd] = z.p_ww;
-                            if (det_label) det_label[s * (size_t)max_det + nd] = -1;
-                        }
-                        ++nd;
-                        z.win_start = z.resume = cfg.fpf * ((f + 3) / cfg.fpf + 1);
-                        if (vv) { for (int j = 0; j < 50; ++j) vwin[j][lane] = __builtin_nanf(""); z.vad_index = 0; z.voice_countdown = 0; }
-                        continue;
-                    }
-                }
-            }
-            const float sc = agg[row0 + i];
-            float av = 0.f;
-            bool pass = true;
-            if (avg_on) { av = avg[row0 + i]; pass = !(av < athr); }
-            if (pass && sc > thr) {
-                const int counter = z.has_partial ? z.p_counter + 1 : 1;
-                if (!z.has_partial || z.p_score < sc) {
-                    z.p_score = sc; z.p_avg = av; z.p_window = f - max_len + 1; z.has_partial = 1;
-                    z.p_ww = wi; z.p_label = -1;
-                }
-                z.p_counter = counter;
-                z.countdown = (int)(max_len / 2);
-            }
-        }
-        if (vv)
-            for (int i = 0; i < 50; ++i) sp->vad_window[i] = vwin[i][lane];
-        __builtin_memcpy(sp, &z, kHead);
+        ScanLane z;
+        stream_state_load(state + s, z, vwin, lane, vv != nullptr);
+        nd = scan_frames(
+            z, vwin, lane, vv, vad_mode_value, f0, n_new, r.max_len, cfg,
+            [&](long long, int i) { return propose_one(agg, avg, row0 + i, r.thr, r.athr, r.avg_on, wi); },
+            [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s, f, z, z.p_ww, -1); });
+        stream_state_store(state + s, z, vwin, lane, vv != nullptr);
     }
-    n_det[s] = nd;
-    for (int i = nd; i < max_det; ++i) {
-        det[s * (size_t)max_det + i] = BatchDetection{};
-        if (det_ww) det_ww[s * (size_t)max_det + i] = 0;
-        if (det_label) det_label[s * (size_t)max_det + i] = -1;
-    }
+    out.finish(s, nd);
 }
 
 hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg,
