@@ -195,6 +195,11 @@ extern "C" {
                                          out: *mut *mut rp_wakeword_bank) -> c_int;
     pub fn rp_wakeword_bank_free(bank: *mut rp_wakeword_bank);
     pub fn rp_wakeword_bank_max_len(bank: *const rp_wakeword_bank, wakeword: i64) -> c_int;
+    pub fn rp_wakeword_bank_set_rms_levels(bank: *mut rp_wakeword_bank, rms_levels: *const f32) -> c_int;
+    pub fn rp_wakeword_bank_rms_level(bank: *const rp_wakeword_bank, wakeword: i64) -> f32;
+    pub fn rp_frontend_batch_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                  filters: *const rp_filters_config, bank: *const rp_wakeword_bank, stream_wakeword: *const i32,
+                                  pcm_out: *mut f32, out_stride: usize, rms: *mut f32, gains: *mut f32) -> c_int;
     pub fn rp_dtw_score_bank(ctx: *mut rp_ctx, mfcc: *const f32, S: usize, n_frames: usize, bank: *const rp_wakeword_bank,
                              stream_wakeword: *const i32, score_ref: f32, band_size: c_int, score_mode: c_int, with_avg: c_int, avg: *mut f32,
                              agg: *mut f32, win_pitch: usize) -> c_int;
@@ -224,6 +229,7 @@ extern "C" {
     pub fn rp_stream_batch_new_bank(ctx: *mut rp_ctx, bank: *const rp_wakeword_bank, stream_wakeword: *const i32, config: *const rp_detector_config,
                                     S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
     pub fn rp_stream_batch_set_wakewords(b: *mut rp_stream_batch, first_stream: usize, n: usize, wakewords: *const i32) -> c_int;
+    pub fn rp_stream_batch_set_filters_bank(b: *mut rp_stream_batch, filters: *const rp_filters_config) -> c_int;
     pub fn rp_model_new(ctx: *mut rp_ctx, n_layers: c_int, dims: *const c_int, weights: *const *const f32, biases: *const *const f32,
                         out: *mut *mut rp_model) -> c_int;
     pub fn rp_model_free(m: *mut rp_model);
@@ -407,6 +413,13 @@ impl WakewordBank {
     }
     /// the longest window length in the bank
     pub fn longest(&self) -> usize { unsafe { rp_wakeword_bank_max_len(self.h, -1) }.max(0) as usize }
+    /// `WakewordRef::rms_level` of one wakeword, the level its stream's gain normaliser works towards; NaN: none (the gain stays 1)
+    pub fn rms_level(&self, wakeword: usize) -> f32 { unsafe { rp_wakeword_bank_rms_level(self.h, wakeword as i64) } }
+    /// new levels for all wakewords (NaN: none), in force from the next call that uses the bank
+    pub fn set_rms_levels(&mut self, rms_levels: &[f32]) -> Result<(), String> {
+        assert!(rms_levels.len() == self.n_wakewords);
+        status(unsafe { rp_wakeword_bank_set_rms_levels(self.h, rms_levels.as_ptr()) })
+    }
 }
 /// A wakeword model on the device (`WakewordNN`, src/wakewords/nn/wakeword_nn.rs:17-37).
 pub struct Model { h: *mut rp_model, pub dims: Vec<c_int> }
@@ -687,6 +700,21 @@ impl HipContext {
         })?;
         Ok((out, rms, gains))
     }
+    /// `frontend_batch` in front of `batch_detect_bank`: the gain normaliser of stream `s` works towards the `rms_level` of
+    /// `bank[stream_wakeword[s]]` over that wakeword's window of `max_len / 3` chunk levels (-1: no wakeword, gain 1)
+    pub fn frontend_batch_bank(&self, pcm: &[f32], n_samples: usize, filters: &FiltersConfig, bank: &WakewordBank, stream_wakeword: &[i32])
+                               -> Result<(Vec<f32>, Vec<f32>, Vec<f32>), String> {
+        let n_streams = stream_wakeword.len();
+        assert!(pcm.len() >= n_streams * n_samples);
+        let f: rp_filters_config = filters.into();
+        let nch = n_samples / 480;
+        let (mut out, mut rms, mut gains) = (vec![0f32; n_streams * n_samples], vec![0f32; n_streams * nch], vec![0f32; n_streams * nch]);
+        status(unsafe {
+            rp_frontend_batch_bank(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, &f, bank.h,
+                                   stream_wakeword.as_ptr(), out.as_mut_ptr(), n_samples, rms.as_mut_ptr(), gains.as_mut_ptr())
+        })?;
+        Ok((out, rms, gains))
+    }
     /// `AudioEncoder::reencode_to_mono_with_sample_rate` (src/audio/encoder.rs:41-60) for whole streams: f32 input at `sample_rate`
     /// with `channels` interleaved channels -> 16 kHz mono.
     pub fn resample_batch(&self, pcm: &[f32], channels: u16, sample_rate: usize, n_streams: usize, n_samples: usize) -> Result<Vec<f32>, String> {
@@ -763,6 +791,12 @@ impl<'a> StreamBatch<'a> {
     /// Connect / disconnect of device slots (a batch of `new_bank`): streams `first_stream ..` get new bank indices and are reset
     pub fn set_wakewords(&mut self, first_stream: usize, wakewords: &[i32]) -> Result<(), String> {
         status(unsafe { rp_stream_batch_set_wakewords(self.h, first_stream, wakewords.len(), wakewords.as_ptr()) })
+    }
+    /// `set_filters` for a batch of `new_bank`: every stream's gain normaliser works towards its own wakeword's `rms_level` over its own
+    /// window; before the first audio
+    pub fn set_filters_bank(&mut self, filters: &FiltersConfig) -> Result<(), String> {
+        let f: rp_filters_config = filters.into();
+        status(unsafe { rp_stream_batch_set_filters_bank(self.h, &f) })
     }
     /// `process` that also tells which wakeword fired and, for a model, which label: (detections, wakeword indices, label indices or -1)
     pub fn process_multi(&mut self, pcm: &[f32], n_chunks: usize, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>, Vec<Vec<i32>>), String> {

@@ -1,6 +1,9 @@
 /* personal_wakewords.c -- a wakeword bank from plain C: every stream carries its OWN wakeword, the batched form of one Rustpotter
  * per user (src/detector.rs:95-176,304-346: Rustpotter::new -> add_wakeword_from_file -> process_samples, once per user).
  *   rp_wakeword_bank_new_from_rpw(all users' .rpw files) -> rp_batch_detect_bank(streams, stream_wakeword[s] = user of stream s)
+ * and then the same streams live, eight chunks per call, with the gain normaliser on: every user enrolled at their own loudness (the
+ * .rpw records it), and every stream is normalised to ITS wakeword's level over its own window
+ *   rp_stream_batch_new_bank -> rp_stream_batch_set_filters_bank -> rp_stream_batch_process per call (+ rp_stream_batch_levels)
  *
  *   gcc -std=c99 -Iinclude examples/personal_wakewords.c -Lrustpotter_amd -lrustpotter_hip -Wl,-rpath,$PWD/rustpotter_amd -o personal_wakewords
  *   ./personal_wakewords tests/golden/oye_casa_g.rpw tests/golden/alexa.rpw tests/golden/oye_casa_g_1.wav tests/golden/alexa.wav
@@ -69,6 +72,46 @@ int main(int argc, char **argv) {
             printf("    frame %d window %d score %.7f avg_score %.7f counter %d\n", (int)d->frame, (int)d->window, d->score, d->avg_score, (int)d->counter);
         }
     }
+
+    /* Live: the same two streams fed eight 30 ms chunks per call, every detector's state on the device, gain normaliser on. */
+    enum { CALL_CHUNKS = 8 };
+    rp_stream_batch *batch = NULL;
+    cfg.filters.gain_normalizer.enabled = true;
+    cfg.filters.gain_normalizer.min_gain = 0.5f;
+    cfg.filters.gain_normalizer.max_gain = 2.0f;
+    if (rp_stream_batch_new_bank(ctx, bank, stream_wakeword, &cfg.detector, N_USERS, CALL_CHUNKS, &batch) < 0 ||
+        rp_stream_batch_set_filters_bank(batch, &cfg.filters) < 0) {
+        fprintf(stderr, "live batch: %s\n", rp_last_error());
+        rp_stream_batch_free(batch); rp_wakeword_bank_free(bank); rp_ctx_free(ctx);
+        return 1;
+    }
+    for (int u = 0; u < N_USERS; ++u) printf("wakeword %d: enrolled at rms level %.4f\n", u, rp_wakeword_bank_rms_level(bank, u));
+    int16_t *part = (int16_t *)malloc((size_t)N_USERS * CALL_CHUNKS * CHUNK * sizeof(int16_t));
+    if (!part) {
+        rp_stream_batch_free(batch); rp_wakeword_bank_free(bank); rp_ctx_free(ctx);
+        free(pcm);
+        return 1;
+    }
+    const size_t total_chunks = n_samples / CHUNK;
+    for (size_t c = 0; c < total_chunks; c += CALL_CHUNKS) {
+        const size_t n = total_chunks - c < CALL_CHUNKS ? total_chunks - c : CALL_CHUNKS;
+        for (int u = 0; u < N_USERS; ++u) memcpy(part + (size_t)u * n * CHUNK, pcm + (size_t)u * n_samples + c * CHUNK, n * CHUNK * sizeof(int16_t));
+        float gains[N_USERS * CALL_CHUNKS];
+        if (rp_stream_batch_process(batch, part, RP_SAMPLE_I16, n, n * CHUNK, det, n_det, MAX_DET, NULL) < 0 ||
+            rp_stream_batch_levels(batch, NULL, gains) < 0) {
+            fprintf(stderr, "rp_stream_batch_process: %s\n", rp_last_error());
+            rp_stream_batch_free(batch); rp_wakeword_bank_free(bank); rp_ctx_free(ctx);
+            return 1;
+        }
+        for (int s = 0; s < N_USERS; ++s)
+            for (int i = 0; i < n_det[s] && i < MAX_DET; ++i) {
+                const rp_batch_detection *d = &det[s * MAX_DET + i];
+                printf("live: slot %d (wakeword %d) chunk %d: score %.7f avg_score %.7f counter %d, gain of the call's last chunk %.1f\n", s,
+                       (int)stream_wakeword[s], (int)d->frame / 3 + 1, d->score, d->avg_score, (int)d->counter, gains[(size_t)s * n + n - 1]);
+            }
+    }
+    free(part);
+    rp_stream_batch_free(batch);   /* the batch borrows the bank and the context */
     rp_wakeword_bank_free(bank);   /* the bank borrows the context: free it first */
     rp_ctx_free(ctx);
     free(pcm);

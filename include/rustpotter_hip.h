@@ -476,6 +476,26 @@ void rp_wakeword_bank_free(rp_wakeword_bank *bank);
 /* WakewordComparator::get_mfcc_frame_size (src/wakewords/comp/wakeword_comp.rs:69-75): the longest sample template of that wakeword = its
  * window length; wakeword < 0: the longest in the bank (0 for an empty bank).  -1 for a NULL bank or an index outside the bank. */
 int rp_wakeword_bank_max_len(const rp_wakeword_bank *bank, long long wakeword);
+/* WakewordRef::rms_level of every wakeword (src/wakewords/wakeword_ref.rs:12-20), the reference level the gain normaliser of a detector
+ * that holds that wakeword works towards (on_wakeword_change, src/detector.rs:328-338): kept from the .rpw files by
+ * rp_wakeword_bank_new_from_rpw, NaN for every wakeword of a bank made by rp_wakeword_bank_new (NaN = no reference level: the gain stays 1,
+ * gain_normalizer_filter.rs:15).  rms_levels: a HOST array [n_wakewords], NaN allowed, whatever the pointer flag of the context; the write
+ * is ordered on the context's stream and holds from the next call that uses the bank (rp_frontend_batch_bank, a live-stream batch with
+ * rp_stream_batch_set_filters_bank). */
+int rp_wakeword_bank_set_rms_levels(rp_wakeword_bank *bank, const float *rms_levels);
+/* ... of one wakeword as last set; NaN for a NULL bank or an index outside the bank. */
+float rp_wakeword_bank_rms_level(const rp_wakeword_bank *bank, long long wakeword);
+/* rp_frontend_batch with every stream's OWN gain-normaliser parameters, what goes in front of rp_batch_detect_bank: stream s works towards
+ * rms_level_ref = the rms_level of bank[stream_wakeword[s]] (filters->gain_normalizer.gain_ref for every stream when has_gain_ref) over a
+ * window of max(max_len(s) / 3, 1) chunk levels (src/detector.rs:337).  stream_wakeword[s] == -1 is a detector without wakewords, whose
+ * process_audio returns before the filters (src/detector.rs:348-350): its gain is 1 for every chunk and its samples pass the gain stage
+ * unchanged; the band-pass filter, when enabled, runs on such a stream like on any other and its chunk levels are reported -- what a
+ * live-stream batch over a bank does.  stream_wakeword [S] int32, checked as in rp_dtw_score_bank: with RP_CTX_HOST_POINTERS an index
+ * outside [-1, n_wakewords) is an error found before anything is launched or written; with device arrays the kernels treat it as -1.
+ * Everything else as rp_frontend_batch. */
+int rp_frontend_batch_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                           const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakeword,
+                           float *pcm_out, size_t out_stride, float *rms, float *gains);
 /* rp_dtw_score_batch for a bank (src/wakewords/comp/wakeword_comp.rs:22-37,77-139 per stream with its own wakeword): mfcc [S][n_frames][K],
  * stream_wakeword [S] int32 (-1: the stream has no wakeword).  agg and avg (avg may be NULL) are [S][win_pitch]: row s holds
  * n_win_s = n_frames - max_len(wakeword of s) + 1 values (the score_mode aggregate; the averaged template's score when with_avg != 0 and
@@ -611,8 +631,8 @@ int rp_stream_batch_process_multi(rp_stream_batch *b, const void *pcm, rp_sample
  * window ending at each new frame (a zero row for a stream without a wakeword; windows reaching before frame 0 are unspecified);
  * det_wakeword is the stream's bank index, det_label -1.  Without agg and without RP_CTX_FULL_SCORES a window below its avg_threshold is
  * not compared with the sample templates; the detections are the same either way.  rp_stream_batch_set_input works as on any batch.
- * rp_stream_batch_set_filters takes the band-pass filter alone: with gain_normalizer.enabled it fails (the gain window and rms_level_ref
- * are per detector, here they would be per stream). */
+ * rp_stream_batch_set_filters takes the band-pass filter alone: with gain_normalizer.enabled it fails (its one rms_level_ref has no
+ * per-stream meaning); rp_stream_batch_set_filters_bank below gives every stream the gain normaliser of its own wakeword. */
 int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config,
                              size_t S, size_t max_chunks_per_call, rp_stream_batch **out);
 /* Connect / disconnect of device slots, at any time between process calls: streams first_stream .. first_stream + n - 1 get the indices
@@ -620,6 +640,17 @@ int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const in
  * (add_wakeword on a detector without wakewords calls reset(), src/detector.rs:304-307; the filters' state and the resampler are not
  * touched).  A refused index changes nothing.  An error on a batch not made by rp_stream_batch_new_bank. */
 int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *wakewords);
+/* rp_stream_batch_set_filters for a batch made by rp_stream_batch_new_bank (an error on any other): the gain normaliser of stream s works
+ * towards the rms_level of ITS wakeword (rp_wakeword_bank_rms_level; filters->gain_normalizer.gain_ref for every stream when
+ * has_gain_ref) over a window of max(max_len(s) / 3, 1) chunk levels, both read from the bank at the start of every process call.  The
+ * rules of rp_stream_batch_set_filters hold: before the first audio, 30 ms chunks only, either order with rp_stream_batch_set_input;
+ * rp_stream_batch_levels works as on any filtered batch; with the band-pass alone it is rp_stream_batch_set_filters.
+ * A slot that changes wakeword (rp_stream_batch_set_wakewords) does what remove_wakeword + add_wakeword do (on_wakeword_change ->
+ * set_rms_level_ref, gain_normalizer_filter.rs:42-48): new level and window size, the window of chunk levels is neither cleared nor
+ * shortened -- filter() pushes one level and drops one only when the window is longer than window_size, so a window that was longer
+ * keeps its length.  A stream with index -1 does not advance its window and has gain 1; connected again, its window goes on from what
+ * it held.  rp_stream_batch_reset leaves the filters alone, as everywhere. */
+int rp_stream_batch_set_filters_bank(rp_stream_batch *b, const rp_filters_config *filters);
 
 /* A wakeword model (src/wakewords/wakeword_model.rs:11-18) resident on the device.  weights are
  * HOST arrays W_l [dims[l+1]][dims[l]] (candle Linear: x.W^T + b), biases b_l [dims[l+1]]; 1..3 layers. */

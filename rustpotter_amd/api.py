@@ -115,6 +115,7 @@ SYMBOLS = [
     "rp_stream_batch_set_filters", "rp_stream_batch_levels",
     "rp_wakeword_bank_new", "rp_wakeword_bank_new_from_rpw", "rp_wakeword_bank_free", "rp_wakeword_bank_max_len", "rp_dtw_score_bank",
     "rp_batch_detect_bank", "rp_stream_batch_new_bank", "rp_stream_batch_set_wakewords",
+    "rp_wakeword_bank_set_rms_levels", "rp_wakeword_bank_rms_level", "rp_frontend_batch_bank", "rp_stream_batch_set_filters_bank",
 ]
 
 
@@ -245,6 +246,11 @@ def load_library():
     L.rp_wakeword_bank_free.argtypes = [vp]
     L.rp_wakeword_bank_free.restype = None
     L.rp_wakeword_bank_max_len.argtypes = [vp, C.c_longlong]
+    L.rp_wakeword_bank_set_rms_levels.argtypes = [vp, fp]
+    L.rp_wakeword_bank_rms_level.argtypes = [vp, C.c_longlong]
+    L.rp_wakeword_bank_rms_level.restype = C.c_float
+    L.rp_frontend_batch_bank.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(_FiltersCfg), vp, vp, vp, C.c_size_t, vp, vp]
+    L.rp_stream_batch_set_filters_bank.argtypes = [vp, C.POINTER(_FiltersCfg)]
     L.rp_dtw_score_bank.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t]
     L.rp_batch_detect_bank.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(_DetectorConfig), vp, vp, C.c_int,
                                        vp, vp, C.c_size_t]
@@ -559,6 +565,21 @@ class WakewordBank:
         self.max_lens = [int(self._L.rp_wakeword_bank_max_len(self._h, w)) for w in range(W)]   # window length of every wakeword
         self.max_len = int(self._L.rp_wakeword_bank_max_len(self._h, -1))
 
+    @property
+    def rms_levels(self):
+        """rp_wakeword_bank_rms_level of every wakeword: [W] float32, NaN = no reference level"""
+        import numpy as np
+        return np.array([self._L.rp_wakeword_bank_rms_level(self._h, w) for w in range(self.W)], np.float32)
+
+    def set_rms_levels(self, rms_levels):
+        """rp_wakeword_bank_set_rms_levels: [W] levels (NaN: none), in force from the next call that uses the bank"""
+        import numpy as np
+        a = np.ascontiguousarray(rms_levels, np.float32)
+        if a.shape != (self.W,):
+            raise ValueError("rms_levels must be [W]")
+        if self._L.rp_wakeword_bank_set_rms_levels(self._h, a.ctypes.data_as(C.POINTER(C.c_float))) < 0:
+            raise _err()
+
     def n_win(self, n_frames, stream_wakeword):
         """windows each stream of a call has: n_frames - max_len(its wakeword) + 1, 0 without a wakeword"""
         return [max(0, n_frames - self.max_lens[w] + 1) if w >= 0 else 0 for w in stream_wakeword]
@@ -577,14 +598,16 @@ class StreamBatch:
     Rustpotter::process_samples on S instances sharing one wakeword and config -- or, over a WakewordBank, each holding its own."""
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
-                 mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None):
+                 mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None, bank_filters=None):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
         with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
         filters (rp_stream_batch_set_filters): a FiltersConfig for the streams, with rms_level_ref the largest rms_level of the
         wakewords (NaN: none); levels() then reports every chunk's RMS level and gain.
         bank + stream_wakeword (rp_stream_batch_new_bank; templates is then None): stream s holds the one wakeword
-        bank[stream_wakeword[s]], -1 = none; stream_wakeword is [S] int32 (with device pointers: the address of a device array)."""
+        bank[stream_wakeword[s]], -1 = none; stream_wakeword is [S] int32 (with device pointers: the address of a device array).
+        bank_filters (rp_stream_batch_set_filters_bank, with bank): a FiltersConfig whose gain normaliser works per stream, towards
+        the rms_level of the stream's own wakeword over its own window."""
         self._L = load_library()
         self.ctx, self.templates, self.S, self.max_chunks = ctx, templates, S, max_chunks_per_call
         h = C.c_void_p()
@@ -614,6 +637,8 @@ class StreamBatch:
             raise _err()
         if filters is not None:
             self.set_filters(filters, rms_level_ref)
+        if bank_filters is not None:
+            self.set_filters_bank(bank_filters)
         self.samples_per_chunk = self._L.rp_stream_batch_samples_per_chunk(h)
         self._last_chunks = 0
         # MFCC frames a stream gains per input frame: 3 (30 ms frames) or 4 (the 40 ms frames of 11.025 / 22.05 kHz input)
@@ -656,6 +681,14 @@ class StreamBatch:
         rc.filters = filters
         f = rc._filters_c()
         if self._L.rp_stream_batch_set_filters(self._h, C.byref(f), rms_level_ref) < 0:
+            raise _err()
+
+    def set_filters_bank(self, filters):
+        """rp_stream_batch_set_filters_bank (a batch over a bank, before the first process call)"""
+        rc = RustpotterConfig()
+        rc.filters = filters
+        f = rc._filters_c()
+        if self._L.rp_stream_batch_set_filters_bank(self._h, C.byref(f)) < 0:
             raise _err()
 
     def levels(self):
@@ -1017,6 +1050,40 @@ class BatchContext:
                                      out.ctypes.data, N, rms.ctypes.data, gains.ctypes.data) < 0:
             raise _err()
         return out, rms, gains
+
+    def frontend_bank(self, pcm, filters_config, bank, stream_wakeword):
+        """rp_frontend_batch_bank: frontend() with the gain normaliser of stream s working towards the rms_level of
+        bank[stream_wakeword[s]] over that wakeword's window (-1: no wakeword, gain 1) -> (pcm f32, rms, gains)."""
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        idx = np.ascontiguousarray(stream_wakeword, np.int32)
+        assert idx.shape == (S,)
+        rc = RustpotterConfig()
+        rc.filters = filters_config
+        f = rc._filters_c()
+        out = np.empty((S, N), np.float32)
+        rms = np.empty((S, N // 480), np.float32)
+        gains = np.empty((S, N // 480), np.float32)
+        if self._L.rp_frontend_batch_bank(self._h, pcm.ctypes.data, fmt, S, N, N, C.byref(f), bank._h, idx.ctypes.data,
+                                          out.ctypes.data, N, rms.ctypes.data, gains.ctypes.data) < 0:
+            raise _err()
+        return out, rms, gains
+
+    def frontend_bank_dev(self, pcm_ptr, fmt, S, n_samples, pcm_stride, filters_config, bank, idx_ptr, out_ptr, out_stride, rms_ptr, gains_ptr):
+        """rp_frontend_batch_bank with device pointers"""
+        rc = RustpotterConfig()
+        rc.filters = filters_config
+        f = rc._filters_c()
+        if self._L.rp_frontend_batch_bank(self._h, pcm_ptr, fmt, S, n_samples, pcm_stride, C.byref(f), bank._h, idx_ptr, out_ptr, out_stride,
+                                          rms_ptr, gains_ptr) < 0:
+            raise _err()
 
     def dtw_scores(self, mfcc, templates, score_ref=0.22, band_size=5, score_mode=ScoreMode.Max, with_avg=False):
         import numpy as np

@@ -14,6 +14,16 @@ Bank::~Bank() {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipFree(dev.ww); (void)hipFree(dev.tlen); (void)hipFree(dev.trow); (void)hipFree(dev.unit); (void)hipFree(dev.raw);
+    (void)hipFree(rms_level);
+}
+
+bool Bank::set_rms_levels(const float *levels) {
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return false;
+    if (rms_levels.empty()) return true;
+    std::copy(levels, levels + rms_levels.size(), rms_levels.begin());
+    // behind whatever the context's stream still runs with the old levels; the host copy is the bank's own, so it may change again at once
+    return hip_ok(hipMemcpyAsync(rms_level, rms_levels.data(), rms_levels.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream),
+                  "hipMemcpyAsync(rms levels)") && hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
 }
 
 template <class T> static bool upload(T **dst, const std::vector<T> &v, const char *what) {
@@ -111,6 +121,8 @@ Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32
     bk->ctx = ctx;   // from here on the destructor frees what was allocated
     if (!upload(&d.ww, bk->ww, "hipMalloc(bank)") || !upload(&d.tlen, tlen, "hipMalloc(bank)") || !upload(&d.trow, trow, "hipMalloc(bank)") ||
         !upload(&d.unit, unit, "hipMalloc(bank templates)") || !upload(&d.raw, raw, "hipMalloc(bank templates)")) return nullptr;
+    bk->rms_levels.assign(W, NAN);   // no reference level until rp_wakeword_bank_set_rms_levels / the .rpw files give one
+    if (!upload(&bk->rms_level, bk->rms_levels, "hipMalloc(bank)")) return nullptr;
     return bk.release();
 }
 
@@ -128,12 +140,12 @@ bool bank_band_ok(const BankDev &d, int band_size) {
 
 }  // namespace rp
 
-namespace {
+namespace rp {
 
 // The per-stream indices of a call: with host arrays every index is checked before anything is launched and the largest window count a
 // stream of the call has is known; with device arrays the kernels treat an index outside [0, W) as "no wakeword" and win_pitch must hold the
 // bank's largest window count.  Returns the device pointer (null on error, *ok false).
-const int32_t *stage_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok) {
+const int32_t *stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok) {
     *ok = false;
     const BankDev &d = bk.dev;
     auto n_win_of = [&](int len) { return n_frames >= (size_t)len ? n_frames - (size_t)len + 1 : (size_t)0; };
@@ -156,6 +168,10 @@ const int32_t *stage_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *
     *ok = true;
     return static_cast<const int32_t *>(p);
 }
+
+}  // namespace rp
+
+namespace {
 
 bool pitch_ok(size_t win_pitch, size_t max_n_win) {
     if (win_pitch < max_n_win) {
@@ -213,7 +229,7 @@ int rp_wakeword_bank_new_from_rpw(rp_ctx *ctx, size_t n_wakewords, const uint8_t
         *out = nullptr;
         if (n_wakewords && (!rpw_buffers || !rpw_lens)) { set_last_error("null argument"); return -1; }
         std::vector<int32_t> counts, lens, avg_lens;
-        std::vector<float> feats, avg_feats, thr, athr;
+        std::vector<float> feats, avg_feats, thr, athr, levels;
         int K = 0;
         for (size_t w = 0; w < n_wakewords; ++w) {
             auto fail = [&](const std::string &why) { set_last_error("wakeword " + std::to_string(w) + ": " + why); return -1; };
@@ -235,11 +251,27 @@ int rp_wakeword_bank_new_from_rpw(rp_ctx *ctx, size_t n_wakewords, const uint8_t
             if (ref.has_avg) avg_feats.insert(avg_feats.end(), ref.avg.begin(), ref.avg.end());
             thr.push_back(ref.has_threshold ? ref.threshold : NAN);
             athr.push_back(ref.has_avg_threshold ? ref.avg_threshold : NAN);
+            levels.push_back(ref.rms_level);
         }
         if (n_wakewords == 0) K = 1;
-        return bank_from(ctx, std::unique_ptr<Bank>(Bank::create(ctx->impl.get(), n_wakewords, K, counts.data(), lens.data(), feats.data(), avg_lens.data(),
-                                                                 avg_feats.data(), thr.data(), athr.data())), out);
+        std::unique_ptr<Bank> bk(Bank::create(ctx->impl.get(), n_wakewords, K, counts.data(), lens.data(), feats.data(), avg_lens.data(),
+                                              avg_feats.data(), thr.data(), athr.data()));
+        if (bk && !bk->set_rms_levels(levels.data())) return -1;
+        return bank_from(ctx, std::move(bk), out);
     });
+}
+
+int rp_wakeword_bank_set_rms_levels(rp_wakeword_bank *bank, const float *rms_levels) {
+    return guarded([&]() -> int {
+        if (!bank) { set_last_error("null handle"); return -1; }
+        if (!rms_levels && bank->impl->dev.W) { set_last_error("null argument"); return -1; }
+        return bank->impl->set_rms_levels(rms_levels) ? 0 : -1;
+    });
+}
+
+float rp_wakeword_bank_rms_level(const rp_wakeword_bank *bank, long long wakeword) {
+    if (!bank || wakeword < 0 || wakeword >= (long long)bank->impl->dev.W) return NAN;
+    return bank->impl->rms_levels[(size_t)wakeword];
 }
 
 void rp_wakeword_bank_free(rp_wakeword_bank *bank) { delete bank; }
@@ -265,7 +297,7 @@ int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames,
         Staged sg(c);
         size_t max_n_win = 0;
         bool ok = false;
-        const int32_t *di = stage_indices(c, sg, bk, stream_wakeword, S, n_frames, &max_n_win, &ok);
+        const int32_t *di = stage_bank_indices(c, sg, bk, stream_wakeword, S, n_frames, &max_n_win, &ok);
         if (!ok || !pitch_ok(win_pitch, max_n_win)) return -1;
         if (S == 0 || win_pitch == 0) return sg.finish() ? 0 : -1;   // (the indices may be on their way to the device)
         const size_t out_bytes = S * win_pitch * sizeof(float);
@@ -278,6 +310,20 @@ int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames,
         q.score_ref = score_ref; q.avg_mode = with_avg ? 1 : 0;
         if (!score_bank(c, bk, q)) return -1;
         return sg.back(agg, q.agg, out_bytes) && sg.back(avg, q.avg, out_bytes) && sg.finish() ? 0 : -1;
+    });
+}
+
+// rp_frontend_batch with every stream's own gain window and reference level (gain_per_stream_kernel); the chunk RMS and apply kernels are
+// those of rp_frontend_batch -- they take per-chunk gains
+int rp_frontend_batch_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                           const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakeword,
+                           float *pcm_out, size_t out_stride, float *rms, float *gains) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (S && !stream_wakeword) { set_last_error("null argument"); return -1; }
+        if (bank->impl->ctx != ctx->impl.get()) { set_last_error("the bank belongs to another context"); return -1; }
+        return frontend_batch(ctx->impl.get(), pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, 0, bank->impl.get(), stream_wakeword, pcm_out,
+                              out_stride, rms, gains);
     });
 }
 
@@ -296,7 +342,7 @@ int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, siz
         const size_t nf = rp_mfcc_num_frames(n_samples);
         size_t max_n_win = 0;
         bool ok = false;
-        const int32_t *di = stage_indices(c, sg, bk, stream_wakeword, S, nf, &max_n_win, &ok);
+        const int32_t *di = stage_bank_indices(c, sg, bk, stream_wakeword, S, nf, &max_n_win, &ok);
         if (!ok) return -1;
         const bool wants = agg || avg;
         if (wants && !pitch_ok(win_pitch, max_n_win)) return -1;

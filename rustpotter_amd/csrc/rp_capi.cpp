@@ -33,6 +33,63 @@ static void fill_detection(rp_detector *d, const Detection &src, rp_detection *o
     out->gain = d->last.gain;
 }
 
+namespace rp {
+
+int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, const rp_filters_config *filters,
+                   float rms_level_ref, size_t window_size, const Bank *bank, const int32_t *stream_wakeword, float *pcm_out, size_t out_stride,
+                   float *rms, float *gains) {
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+    if (pcm_stride < n_samples || out_stride < n_samples) { set_last_error("stride smaller than n_samples"); return -1; }
+    if (!sample_format_ok(fmt)) return -1;
+    if (!filters) { set_last_error("null argument"); return -1; }
+    const rp_gain_normalization_config &g = filters->gain_normalizer;
+    const rp_band_pass_config &b = filters->band_pass;
+    if (bank) window_size = (size_t)std::max(bank->dev.max_len / 3, 1);   // the ring's capacity: the bank's largest window (src/detector.rs:337)
+    else if (g.enabled && g.has_gain_ref) rms_level_ref = g.gain_ref;    // fixed_rms_level, gain_normalizer_filter.rs:56-66
+    if (window_size == 0) window_size = 1;                                // set_rms_level_ref :47
+    if (window_size > 1u << 20) { set_last_error("window_size too large"); return -1; }
+    float q[5];
+    band_pass_coefficients(b, q);
+    const float a0 = q[0], a1 = q[1], a2 = q[2], b1 = q[3], b2 = q[4];
+    const size_t n_chunks = n_samples / 480;
+    Staged sg(c);
+    PerStreamGain per;
+    if (bank) {  // a refused index: before anything is launched or written
+        size_t unused = 0;
+        bool ok = false;
+        per.stream_wakeword = stage_bank_indices(c, sg, *bank, stream_wakeword, S, 0, &unused, &ok);
+        if (!ok) return -1;
+        per.ww = bank->dev.ww; per.rms_level = bank->rms_level; per.W = bank->dev.W;
+        per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
+    }
+    const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
+    float *dout = static_cast<float *>(sg.out(pcm_out, S * out_stride * sizeof(float), c->stage_out));
+    if (S && (!dp || !dout)) { if (!pcm || !pcm_out) set_last_error("null argument"); return -1; }
+    if (!c->ws_rms.reserve(S * n_chunks * 4 + 16) || !c->ws_gain.reserve(S * n_chunks * 4 + 16) ||
+        !c->ws_ring.reserve(S * window_size * 4 + 16)) return -1;
+    const hipError_t e = bank ? launch_frontend_per_stream(c->stream, dp, (int)fmt, S, n_samples, pcm_stride, g.enabled ? 1 : 0, per, (int)window_size,
+                                                           g.min_gain, g.max_gain, b.enabled ? 1 : 0, a0, a1, a2, b1, b2, c->ws_ring.as<float>(),
+                                                           c->ws_rms.as<float>(), c->ws_gain.as<float>(), dout, out_stride)
+                              : launch_frontend(c->stream, dp, (int)fmt, S, n_samples, pcm_stride, g.enabled ? 1 : 0, rms_level_ref, g.min_gain,
+                                                g.max_gain, (int)window_size, b.enabled ? 1 : 0, a0, a1, a2, b1, b2, c->ws_ring.as<float>(),
+                                                c->ws_rms.as<float>(), c->ws_gain.as<float>(), dout, out_stride);
+    if (!hip_ok(e, "front-end kernels")) return -1;
+    auto copy_out = [&](float *dst, const float *src_dev, bool valid) {
+        if (!dst) return true;
+        if (!valid) {  // gain filter off: every chunk has gain 1
+            std::vector<float> ones(S * n_chunks, 1.f);
+            return hip_ok(hipMemcpyAsync(dst, ones.data(), ones.size() * 4, sg.host ? hipMemcpyHostToHost : hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync") &&
+                   hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        }
+        return hip_ok(hipMemcpyAsync(dst, src_dev, S * n_chunks * 4, sg.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync");
+    };
+    if (!copy_out(rms, c->ws_rms.as<float>(), true) || !copy_out(gains, c->ws_gain.as<float>(), g.enabled)) return -1;
+    if (!sg.back(pcm_out, dout, S * out_stride * sizeof(float))) return -1;
+    return hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
+}
+
+}  // namespace rp
+
 extern "C" {
 
 const char *rp_last_error(void) { return last_error().c_str(); }
@@ -376,41 +433,8 @@ int rp_frontend_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t
                       size_t out_stride, float *rms, float *gains) {
     return guarded([&]() -> int {
         if (!ctx) { set_last_error("null handle"); return -1; }
-        Ctx *c = ctx->impl.get();
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (pcm_stride < n_samples || out_stride < n_samples) { set_last_error("stride smaller than n_samples"); return -1; }
-        if (!sample_format_ok(fmt)) return -1;
-        if (!filters) { set_last_error("null argument"); return -1; }
-        const rp_gain_normalization_config &g = filters->gain_normalizer;
-        const rp_band_pass_config &b = filters->band_pass;
-        if (g.enabled && g.has_gain_ref) rms_level_ref = g.gain_ref;  // fixed_rms_level, gain_normalizer_filter.rs:56-66
-        if (window_size == 0) window_size = 1;                           // set_rms_level_ref :47
-        if (window_size > 1u << 20) { set_last_error("window_size too large"); return -1; }
-        float q[5];
-        band_pass_coefficients(b, q);
-        const float a0 = q[0], a1 = q[1], a2 = q[2], b1 = q[3], b2 = q[4];
-        const size_t n_chunks = n_samples / 480;
-        Staged sg(c);
-        const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
-        float *dout = static_cast<float *>(sg.out(pcm_out, S * out_stride * sizeof(float), c->stage_out));
-        if (S && (!dp || !dout)) return -1;
-        if (!c->ws_rms.reserve(S * n_chunks * 4 + 16) || !c->ws_gain.reserve(S * n_chunks * 4 + 16) ||
-            !c->ws_ring.reserve(S * window_size * 4 + 16)) return -1;
-        if (!hip_ok(launch_frontend(c->stream, dp, (int)fmt, S, n_samples, pcm_stride, g.enabled ? 1 : 0, rms_level_ref, g.min_gain,
-                                    g.max_gain, (int)window_size, b.enabled ? 1 : 0, a0, a1, a2, b1, b2, c->ws_ring.as<float>(),
-                                    c->ws_rms.as<float>(), c->ws_gain.as<float>(), dout, out_stride), "front-end kernels")) return -1;
-        auto copy_out = [&](float *dst, const float *src_dev, bool valid) {
-            if (!dst) return true;
-            if (!valid) {  // gain filter off: every chunk has gain 1
-                std::vector<float> ones(S * n_chunks, 1.f);
-                return hip_ok(hipMemcpyAsync(dst, ones.data(), ones.size() * 4, sg.host ? hipMemcpyHostToHost : hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync") &&
-                       hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-            }
-            return hip_ok(hipMemcpyAsync(dst, src_dev, S * n_chunks * 4, sg.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync");
-        };
-        if (!copy_out(rms, c->ws_rms.as<float>(), true) || !copy_out(gains, c->ws_gain.as<float>(), g.enabled)) return -1;
-        if (!sg.back(pcm_out, dout, S * out_stride * sizeof(float))) return -1;
-        return hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
+        return frontend_batch(ctx->impl.get(), pcm, fmt, S, n_samples, pcm_stride, filters, rms_level_ref, window_size, nullptr, nullptr, pcm_out,
+                              out_stride, rms, gains);
     });
 }
 

@@ -91,5 +91,12 @@ bool resample_rows(Ctx *c, const ResamplerDev &rs, const void *pcm, int fmt, int
                    float *prev_out, size_t S, size_t n_chunks, DevBuf &xs_buf, size_t xs_chunks, float *out, size_t out_stride);
 // rp_bank.cpp
 bool bank_band_ok(const BankDev &d, int band_size);
+// the per-stream wakeword indices of a bank call, checked (host arrays) and on the device; see rp_bank.cpp
+const int32_t *stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok);
+// rp_frontend_batch and rp_frontend_batch_bank (rp_capi.cpp): with `bank`, every stream takes its gain window and reference level from its own
+// wakeword bank[stream_wakeword[s]] and rms_level_ref / window_size are not read
+int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, const rp_filters_config *filters,
+                   float rms_level_ref, size_t window_size, const Bank *bank, const int32_t *stream_wakeword, float *pcm_out, size_t out_stride,
+                   float *rms, float *gains);
 
 }  // namespace rp

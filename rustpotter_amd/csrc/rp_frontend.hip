@@ -140,6 +140,62 @@ __global__ __launch_bounds__(64) void gain_kernel(const float *__restrict__ rms,
     }
 }
 
+// What the gain normaliser of stream s works with when every stream holds its own wakeword of a bank (PerStreamGain, rp_kernels.h):
+// set_rms_level_ref(rms_level, max_mfcc_frames / 3) of that wakeword, gain_normalizer_filter.rs:42-48.  An index outside [0, W) is a
+// detector without wakewords: no reference level (NaN), so filter() leaves the window alone and the gain is 1.
+struct LaneGain { int window_size; float rms_level_ref; };
+__device__ __forceinline__ LaneGain lane_gain(const PerStreamGain &p, size_t s) {
+    const int wi = p.stream_wakeword[s];
+    LaneGain g{1, __builtin_nanf("")};
+    if (wi >= 0 && wi < p.W) {
+        const int ws = p.ww[wi].max_len / 3;
+        g.window_size = ws != 0 ? ws : 1;
+        g.rms_level_ref = p.has_fixed_ref ? p.fixed_ref : p.rms_level[wi];
+    }
+    return g;
+}
+
+// gain_kernel with per-lane window_size and rms_level_ref (rp_frontend_batch_bank).  The ring holds `cap` = the bank's largest window
+// entries per stream ([cap][64] in LDS, else [S][cap]); a lane wraps at its own window_size and sums its own `len` entries oldest first
+// -- the trip counts diverge inside a wave, the order and count of the additions are gain_kernel's for that window.
+__global__ __launch_bounds__(64) void gain_per_stream_kernel(const float *__restrict__ rms, size_t S, size_t n_chunks, PerStreamGain p,
+                                                             float min_gain, float max_gain, int cap, int ring_in_lds,
+                                                             float *__restrict__ ring, float *__restrict__ gains) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const size_t s = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (s >= S) return;
+    float *w = ring_in_lds ? reinterpret_cast<float *>(smem) + threadIdx.x : ring + s * (size_t)cap;
+    const int pitch = ring_in_lds ? 64 : 1;
+    const LaneGain lg = lane_gain(p, s);
+    const int window_size = lg.window_size < cap ? lg.window_size : cap;   // (the bank's largest window: never smaller than a lane's)
+    const float rms_level_ref = lg.rms_level_ref, rms_level_sqrt = sqrtf(rms_level_ref);
+    int len = 0, head = 0;
+    for (size_t c = 0; c < n_chunks; ++c) {
+        const float r = rms[s * n_chunks + c];
+        float gain = 1.f;
+        if (!(rms_level_ref != rms_level_ref) && r != 0.f) {
+            if (len < window_size) { const int t = head + len; w[(t >= window_size ? t - window_size : t) * pitch] = r; ++len; }
+            else { w[head * pitch] = r; head = head + 1 == window_size ? 0 : head + 1; }  // push + drain(0..1)
+            float sum = 0.f;  // oldest first, the order of iter().sum(); four reads in flight per step
+            int i = 0, t = head;
+            auto step = [&](int u) { const int n = u + 1; return n >= window_size ? n - window_size : n; };
+            for (; i + 4 <= len; i += 4) {
+                const int t1 = step(t), t2 = step(t1), t3 = step(t2);
+                const float a = w[t * pitch], b = w[t1 * pitch], c2 = w[t2 * pitch], d = w[t3 * pitch];
+                sum += a; sum += b; sum += c2; sum += d;
+                t = step(t3);
+            }
+            for (; i < len; ++i) { sum += w[t * pitch]; t = step(t); }
+            const float frame_rms_level = sum / (float)len;
+            gain = rms_level_sqrt / sqrtf(frame_rms_level);
+            gain = roundf(gain * 10.f) / 10.f;
+            gain = gain < min_gain ? min_gain : gain;  // f32::clamp
+            gain = gain > max_gain ? max_gain : gain;
+        }
+        gains[s * n_chunks + c] = gain;
+    }
+}
+
 struct BiquadCoef { float a0, a1, a2, b1, b2; };
 
 // gain (+clamp) and BandPassFilter::filter (band_pass_filter.rs:19-30) along the stream, one lane per stream
@@ -337,8 +393,8 @@ __global__ __launch_bounds__(64 * W) void apply_filters_lines_kernel(const TIN *
 
 template <class TIN>
 static hipError_t launch_frontend_t(hipStream_t st, const TIN *pcm, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
-                                    float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass,
-                                    BiquadCoef q, float *ring, float *rms, float *gains, float *out, size_t out_stride) {
+                                    float rms_level_ref, float min_gain, float max_gain, int window_size, const PerStreamGain *per,
+                                    int band_pass, BiquadCoef q, float *ring, float *rms, float *gains, float *out, size_t out_stride) {
     const size_t n_chunks = n_samples / kFrame;
     if (S == 0) return hipSuccess;
     const int vec4 = (reinterpret_cast<uintptr_t>(pcm) % (4 * sizeof(TIN)) == 0) && (pcm_stride % 4 == 0) &&
@@ -354,8 +410,12 @@ static hipError_t launch_frontend_t(hipStream_t st, const TIN *pcm, size_t S, si
         if (gain_on) {
             const size_t ring_lds = (size_t)window_size * 64 * sizeof(float);
             const int in_lds = ring_lds <= 48 * 1024;
-            hipLaunchKernelGGL(gain_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), in_lds ? ring_lds : 0, st, rms, S, n_chunks,
-                               rms_level_ref, min_gain, max_gain, window_size, in_lds, ring, gains);
+            if (per)  // every stream its own window (at most window_size entries) and reference level
+                hipLaunchKernelGGL(gain_per_stream_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), in_lds ? ring_lds : 0, st, rms, S,
+                                   n_chunks, *per, min_gain, max_gain, window_size, in_lds, ring, gains);
+            else
+                hipLaunchKernelGGL(gain_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), in_lds ? ring_lds : 0, st, rms, S, n_chunks,
+                                   rms_level_ref, min_gain, max_gain, window_size, in_lds, ring, gains);
         }
     }
     if (vec4 && pcm_stride < (1u << 29) && out_stride < (1u << 29)) {  // 32-bit lane offsets inside a wave's rows
@@ -382,13 +442,11 @@ static hipError_t launch_frontend_t(hipStream_t st, const TIN *pcm, size_t S, si
     return hipGetLastError();
 }
 
-hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
-                           float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
-                           float a1, float a2, float b1, float b2, float *ring, float *rms, float *gains, float *out,
-                           size_t out_stride) {
-    BiquadCoef q{a0, a1, a2, b1, b2};
+static hipError_t launch_frontend_any(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
+                                      float rms_level_ref, float min_gain, float max_gain, int window_size, const PerStreamGain *per,
+                                      int band_pass, BiquadCoef q, float *ring, float *rms, float *gains, float *out, size_t out_stride) {
 #define RP_FE(T) launch_frontend_t<T>(st, static_cast<const T *>(pcm), S, n_samples, pcm_stride, gain_on, rms_level_ref, min_gain, \
-                                      max_gain, window_size, band_pass, q, ring, rms, gains, out, out_stride)
+                                      max_gain, window_size, per, band_pass, q, ring, rms, gains, out, out_stride)
     switch (fmt) {
     case 0: return RP_FE(int8_t);
     case 1: return RP_FE(int16_t);
@@ -397,6 +455,22 @@ hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, s
     }
 #undef RP_FE
     return hipErrorInvalidValue;
+}
+hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
+                           float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
+                           float a1, float a2, float b1, float b2, float *ring, float *rms, float *gains, float *out,
+                           size_t out_stride) {
+    return launch_frontend_any(st, pcm, fmt, S, n_samples, pcm_stride, gain_on, rms_level_ref, min_gain, max_gain, window_size, nullptr,
+                               band_pass, BiquadCoef{a0, a1, a2, b1, b2}, ring, rms, gains, out, out_stride);
+}
+// ... with every stream's own gain window and reference level (ring [S][max_window])
+hipError_t launch_frontend_per_stream(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
+                                      const PerStreamGain &per, int max_window, float min_gain, float max_gain, int band_pass, float a0,
+                                      float a1, float a2, float b1, float b2, float *ring, float *rms, float *gains, float *out,
+                                      size_t out_stride) {
+    if (max_window < 1) return hipErrorInvalidValue;
+    return launch_frontend_any(st, pcm, fmt, S, n_samples, pcm_stride, gain_on, 0.f, min_gain, max_gain, max_window, &per, band_pass,
+                               BiquadCoef{a0, a1, a2, b1, b2}, ring, rms, gains, out, out_stride);
 }
 
 // The chunk RMS alone (get_rms_level) of rows that hold whole chunks: what a live-stream batch reports when its filters are
@@ -443,12 +517,19 @@ struct StreamFilterState {
     int *head, *len;           // [S]: the oldest entry and the number of entries
 };
 
-template <class TIN, bool VEC, bool GAIN, bool BP>
+// PER (a batch over a wakeword bank, rp_stream_batch_set_filters_bank; always with GAIN): a lane reads its own window_size and rms_level_ref
+// at the start of the call, through its stream's bank index; the kernel's window_size is then the ring's capacity, the bank's largest
+// window.  A stream whose wakeword changed between calls keeps the entries it has: filter() pushes one level and drops one only when the
+// window is longer than window_size, so the ring grows while len < window_size(s), else the newest entry replaces the oldest -- wrapped by
+// the capacity, compared with the lane's window_size.  With one wakeword for all, capacity == window_size and this is the shared form.
+template <class TIN, bool VEC, bool GAIN, bool BP, bool PER = false>
 __global__ __launch_bounds__(64) void stream_filters_kernel(const TIN *__restrict__ pcm, int channels, size_t S, size_t n_chunks,
                                                             size_t pcm_stride, const float *__restrict__ old_hist, size_t old_off,
                                                             float *__restrict__ hist, size_t hist_pitch, float rms_level_ref,
                                                             float min_gain, float max_gain, int window_size, BiquadCoef q,
-                                                            StreamFilterState fs, float *__restrict__ rms, float *__restrict__ gains) {
+                                                            StreamFilterState fs, float *__restrict__ rms, float *__restrict__ gains,
+                                                            PerStreamGain per) {
+    static_assert(!PER || GAIN, "per-stream parameters belong to the gain normaliser");
     constexpr int NSL = kFrame / kRmsSlice, LPR = kRmsSlice / 4, PASSES = GAIN ? 2 : 1;
     static_assert(kRmsMoves % 3 == 0 && 192 % LPR == 0, "three moves cover whole rows");
     __shared__ __attribute__((aligned(16))) float tile[64 * kRmsPitch];
@@ -494,6 +575,12 @@ __global__ __launch_bounds__(64) void stream_filters_kernel(const TIN *__restric
     int head = 0, len = 0;
     if (GAIN) { head = fs.head[s_c]; len = fs.len[s_c]; }
     float *w = fs.ring + s_c;  // entry i of this stream: w[i * S]
+    int lane_window = window_size;
+    if (PER) {
+        const LaneGain lg = lane_gain(per, s_c);
+        lane_window = lg.window_size < window_size ? lg.window_size : window_size;
+        rms_level_ref = lg.rms_level_ref;
+    }
     const float rms_level_sqrt = sqrtf(rms_level_ref);
     float g = 1.f, sum_squared = 0.f;
     auto one = [&](float v) {  // as apply_filters_lines_kernel
@@ -581,7 +668,13 @@ __global__ __launch_bounds__(64) void stream_filters_kernel(const TIN *__restric
             const float level = sqrtf(sum_squared / (float)kFrame);
             float gain = 1.f;
             if (GAIN && live && !(rms_level_ref != rms_level_ref) && level != 0.f) {
-                if (len < window_size) { const int u = head + len; w[(size_t)(u >= window_size ? u - window_size : u) * S] = level; ++len; }
+                if (PER) {  // the newest entry goes behind the len the ring holds (len == capacity: onto the oldest)
+                    const int u = head + len;
+                    w[(size_t)(u >= window_size ? u - window_size : u) * S] = level;
+                    if (len < lane_window) ++len;
+                    else head = head + 1 == window_size ? 0 : head + 1;
+                }
+                else if (len < window_size) { const int u = head + len; w[(size_t)(u >= window_size ? u - window_size : u) * S] = level; ++len; }
                 else { w[(size_t)head * S] = level; head = head + 1 == window_size ? 0 : head + 1; }  // push + drain(0..1)
                 float sum = 0.f;  // oldest first, the order of iter().sum()
                 int u = head;
@@ -625,20 +718,25 @@ template <class TIN>
 static hipError_t launch_stream_filters_t(hipStream_t st, const TIN *pcm, int channels, size_t S, size_t n_chunks, size_t pcm_stride,
                                           const float *old_hist, size_t old_off, float *hist, size_t hist_pitch, int gain_on,
                                           float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass,
-                                          BiquadCoef q, const StreamFilterState &fs, float *rms, float *gains) {
+                                          BiquadCoef q, const StreamFilterState &fs, float *rms, float *gains, const PerStreamGain *per) {
     const bool vec = channels == 1 && reinterpret_cast<uintptr_t>(pcm) % (4 * sizeof(TIN)) == 0 && pcm_stride % 4 == 0;
     const dim3 grid((unsigned)((S + 63) / 64)), block(64);
-#define RP_SF(V, G, B)                                                                                                                  \
-    hipLaunchKernelGGL((stream_filters_kernel<TIN, V, G, B>), grid, block, 0, st, pcm, channels, S, n_chunks, pcm_stride, old_hist,     \
-                       old_off, hist, hist_pitch, rms_level_ref, min_gain, max_gain, window_size, q, fs, rms, gains)
-#define RP_SF_V(G, B)                                                                                                                   \
+    const PerStreamGain pg = per ? *per : PerStreamGain{};
+#define RP_SF(V, G, B, P)                                                                                                               \
+    hipLaunchKernelGGL((stream_filters_kernel<TIN, V, G, B, P>), grid, block, 0, st, pcm, channels, S, n_chunks, pcm_stride, old_hist,  \
+                       old_off, hist, hist_pitch, rms_level_ref, min_gain, max_gain, window_size, q, fs, rms, gains, pg)
+#define RP_SF_V(G, B, P)                                                                                                                \
     do {                                                                                                                                \
-        if (vec) RP_SF(true, G, B);                                                                                                     \
-        else RP_SF(false, G, B);                                                                                                        \
+        if (vec) RP_SF(true, G, B, P);                                                                                                  \
+        else RP_SF(false, G, B, P);                                                                                                     \
     } while (0)
-    if (gain_on && band_pass) RP_SF_V(true, true);
-    else if (gain_on) RP_SF_V(true, false);
-    else RP_SF_V(false, true);
+    if (gain_on && per) {  // every stream its own window and reference level
+        if (band_pass) RP_SF_V(true, true, true);
+        else RP_SF_V(true, false, true);
+    }
+    else if (gain_on && band_pass) RP_SF_V(true, true, false);
+    else if (gain_on) RP_SF_V(true, false, false);
+    else RP_SF_V(false, true, false);
 #undef RP_SF_V
 #undef RP_SF
     return hipGetLastError();
@@ -647,7 +745,8 @@ static hipError_t launch_stream_filters_t(hipStream_t st, const TIN *pcm, int ch
 hipError_t launch_stream_filters(hipStream_t st, const void *pcm, int fmt, int channels, size_t S, size_t n_chunks, size_t pcm_stride,
                                  const float *old_hist, size_t old_off, float *hist, size_t hist_pitch, int gain_on,
                                  float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
-                                 float a1, float a2, float b1, float b2, float *filter_state, float *rms, float *gains) {
+                                 float a1, float a2, float b1, float b2, float *filter_state, float *rms, float *gains,
+                                 const PerStreamGain *per) {
     if (S == 0 || n_chunks == 0) return hipSuccess;
     if (!gain_on && !band_pass) return hipErrorInvalidValue;  // such a batch keeps its unfiltered launches
     if (channels < 1 || window_size < 1 || (S + 63) / 64 > 0x7fffffffULL) return hipErrorInvalidValue;
@@ -663,7 +762,7 @@ hipError_t launch_stream_filters(hipStream_t st, const void *pcm, int fmt, int c
     fs.ring = reinterpret_cast<float *>(fs.len + S);
     BiquadCoef q{a0, a1, a2, b1, b2};
 #define RP_SFT(T) launch_stream_filters_t<T>(st, static_cast<const T *>(pcm), channels, S, n_chunks, pcm_stride, old_hist, old_off, hist, \
-                                             hist_pitch, gain_on, rms_level_ref, min_gain, max_gain, window_size, band_pass, q, fs, rms, gains)
+                                             hist_pitch, gain_on, rms_level_ref, min_gain, max_gain, window_size, band_pass, q, fs, rms, gains, per)
     switch (fmt) {
     case 0: return RP_SFT(int8_t);
     case 1: return RP_SFT(int16_t);

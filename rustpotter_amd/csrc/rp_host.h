@@ -181,6 +181,11 @@ struct Bank {
     Ctx *ctx = nullptr;
     BankDev dev;
     std::vector<BankWakeword> ww;   // the host's copy of dev.ww
+    // WakewordRef::rms_level of every wakeword (NaN: none), beside dev.ww on the device: what the per-stream gain normaliser reads through a
+    // stream's index (PerStreamGain)
+    std::vector<float> rms_levels;
+    float *rms_level = nullptr;     // [W], device
+    bool set_rms_levels(const float *levels);   // HOST array [W]; ordered on the context's stream
     // HOST arrays in the flat layout of rp_mfcc_average_batch: counts [W], lens [sum counts], feats [sum lens][K]; avg_lens [W] (0: none) and
     // avg_feats [sum avg_lens][K] (both may be null); thresholds / avg_thresholds [W] (null or NaN: none)
     static Bank *create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32_t *lens, const float *feats, const int32_t *avg_lens,

@@ -522,23 +522,40 @@ hipError_t launch_scan_bank(hipStream_t st, const BankDev &b, const int32_t *str
                             const float *vad_value, float vad_mode_value, size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det,
                             int32_t *n_det, int max_det, uint32_t *hot);
 
+// The gain normaliser's parameters per stream, through the stream's index into a wakeword bank (rp_frontend_batch_bank,
+// rp_stream_batch_set_filters_bank): stream s works towards rms_level[w(s)] (fixed_ref for every stream when has_fixed_ref:
+// GainNormalizationConfig::gain_ref) over a window of max(ww[w(s)].max_len / 3, 1) chunk levels; an index outside [0, W): no wakeword, gain 1.
+struct PerStreamGain {
+    const int32_t *stream_wakeword = nullptr;   // [S], device
+    const BankWakeword *ww = nullptr;           // [W], device (BankDev::ww)
+    const float *rms_level = nullptr;           // [W], device (Bank::rms_level), NaN: none
+    int W = 0, has_fixed_ref = 0;
+    float fixed_ref = 0.f;
+};
 // Decode + GainNormalizerFilter + BandPassFilter over whole streams.  ring [S][window_size], rms / gains
 // [S][n_samples/480] are device workspaces; biquad coefficients as BandPassFilter::new computes them.
 hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
                            float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
                            float a1, float a2, float b1, float b2, float *ring, float *rms, float *gains, float *out,
                            size_t out_stride);
+// ... with every stream's own window and reference level; max_window: the bank's largest window, ring [S][max_window]
+hipError_t launch_frontend_per_stream(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
+                                      const PerStreamGain &per, int max_window, float min_gain, float max_gain, int band_pass, float a0,
+                                      float a1, float a2, float b1, float b2, float *ring, float *rms, float *gains, float *out,
+                                      size_t out_stride);
 // get_rms_level of every chunk alone: rms [S][n_chunks] of rows pcm_stride samples apart
 hipError_t launch_chunk_rms(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_chunks, size_t pcm_stride, float *rms);
 // The same filters for the streams of a live batch, state carried from call to call: ONE launch that writes hist rows
 // [the last chunk of the previous call (old_hist row + old_off) | the n_chunks new chunks decoded (first of `channels`) and filtered]
 // -- launch_stream_stage's row, filtered -- and rms / gains [S][n_chunks] of the new chunks.  filter_state: stream_filter_state_bytes()
 // of device memory, zero before a stream's first chunk (biquad x1 x2 y1 y2, gain window head / length, the window ring, by stream).
-// At least one of gain_on / band_pass.
+// At least one of gain_on / band_pass.  per (optional, read with gain_on): every stream its own gain window and reference level; window_size is
+// then the capacity of a stream's ring, the largest window any stream may have, and rms_level_ref is not read.
 hipError_t launch_stream_filters(hipStream_t st, const void *pcm, int fmt, int channels, size_t S, size_t n_chunks, size_t pcm_stride,
                                  const float *old_hist, size_t old_off, float *hist, size_t hist_pitch, int gain_on,
                                  float rms_level_ref, float min_gain, float max_gain, int window_size, int band_pass, float a0,
-                                 float a1, float a2, float b1, float b2, float *filter_state, float *rms, float *gains);
+                                 float a1, float a2, float b1, float b2, float *filter_state, float *rms, float *gains,
+                                 const PerStreamGain *per = nullptr);
 size_t stream_filter_state_bytes(size_t S, int window_size);
 constexpr size_t kStreamFiltersMaxPitch = (size_t)1 << 25;  // rows (pcm_stride, hist_pitch) must be shorter than this many samples
 

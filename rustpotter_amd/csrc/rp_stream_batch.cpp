@@ -53,6 +53,9 @@ struct rp_stream_batch {
     rp_filters_config filt{};
     float rms_level_ref = 0.f, bq[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     int gain_window = 1;
+    // rp_stream_batch_set_filters_bank: the gain normaliser of stream s takes its reference level and window size from its own wakeword of the
+    // bank, read through bank_idx at the start of every call; gain_window is then the capacity of a stream's ring, the bank's largest window
+    bool per_stream_gain = false;
     DevBuf filt_state, lv_rms, lv_gain;
     size_t levels_chunks = 0;
     bool filters_on() const { return has_filters && (filt.gain_normalizer.enabled || filt.band_pass.enabled); }
@@ -207,10 +210,16 @@ static bool stream_frames(rp_stream_batch *b, const MfccTablesDev &tb, const Str
     if (b->filters_on()) {
         // with filters, ONE launch in the place of launch_stream_stage: history chunk | the new chunks decoded and filtered, levels kept
         const rp_gain_normalization_config &g = b->filt.gain_normalizer;
+        PerStreamGain per;
+        if (b->per_stream_gain) {
+            per.stream_wakeword = b->bank_idx.as<int32_t>(); per.ww = b->bank->dev.ww; per.rms_level = b->bank->rms_level; per.W = b->bank->dev.W;
+            per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;   // fixed_rms_level, gain_normalizer_filter.rs:56-66
+        }
         if (!hip_ok(launch_stream_filters(c->stream, in.p, in.fmt, in.channels, S, n_chunks, in.stride, hp_old, b->last_off, hp, pcm_pitch,
                                           g.enabled ? 1 : 0, b->rms_level_ref, g.min_gain, g.max_gain, b->gain_window,
                                           b->filt.band_pass.enabled ? 1 : 0, b->bq[0], b->bq[1], b->bq[2], b->bq[3], b->bq[4],
-                                          b->filt_state.as<float>(), b->lv_rms.as<float>(), b->lv_gain.as<float>()), "stream_filters_kernel")) return false;
+                                          b->filt_state.as<float>(), b->lv_rms.as<float>(), b->lv_gain.as<float>(),
+                                          b->per_stream_gain ? &per : nullptr), "stream_filters_kernel")) return false;
     } else if (staged && !stage()) return false;
     // MFCC window rows: [.. valid frames .. | the 3*n_chunks new frames]; a full row keeps its last max_len-1 frames
     if (b->fill + n_new > b->cap) {
@@ -469,19 +478,24 @@ int rp_stream_batch_set_input(rp_stream_batch *b, size_t sample_rate, int channe
 }
 size_t rp_stream_batch_samples_per_chunk(const rp_stream_batch *b) { return b ? b->in_len * (size_t)b->channels : 0; }
 
-int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref) {
+// Both filter calls; per_stream: rp_stream_batch_set_filters_bank (rms_level_ref is then not read)
+static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref, bool per_stream) {
     return guarded([&]() -> int {
+        const std::string name = per_stream ? "rp_stream_batch_set_filters_bank" : "rp_stream_batch_set_filters";
         if (b && !filters) { set_last_error("null argument"); return -1; }
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
-        if (b->chunks_seen) { set_last_error("rp_stream_batch_set_filters: the streams have already received audio"); return -1; }
+        if (per_stream && !b->bank) { set_last_error(name + ": the batch was not made by rp_stream_batch_new_bank"); return -1; }
+        if (b->chunks_seen) { set_last_error(name + ": the streams have already received audio"); return -1; }
         if (b->out_len != 480) { set_last_error(kFiltersNeed30ms); return -1; }
         const rp_gain_normalization_config &g = filters->gain_normalizer;
-        if (b->bank && g.enabled) {
+        if (b->bank && g.enabled && !per_stream) {
             set_last_error("rp_stream_batch_set_filters: the gain normaliser is not available on a batch over a wakeword bank (its window and "
-                           "rms_level_ref would be per stream, stream_filters_kernel takes one value of each); the band-pass filter alone is");
+                           "rms_level_ref would be per stream, stream_filters_kernel takes one value of each); the band-pass filter alone is, "
+                           "and rp_stream_batch_set_filters_bank gives every stream the gain normaliser of its own wakeword");
             return -1;
         }
+        // (a batch over a bank: the bank's largest window, the capacity of every stream's ring)
         const int window = std::max(b->max_len / 3, 1);   // on_wakeword_change, src/detector.rs:337; set_rms_level_ref :47
         const size_t lv = b->S * b->max_chunks * sizeof(float) + 16, st = stream_filter_state_bytes(b->S, window);
         if (!b->filt_state.reserve(st) || !b->lv_rms.reserve(lv) || !b->lv_gain.reserve(lv)) return -1;
@@ -489,10 +503,18 @@ int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *fil
         b->filt = *filters;
         b->rms_level_ref = g.enabled && g.has_gain_ref ? g.gain_ref : rms_level_ref;  // fixed_rms_level, gain_normalizer_filter.rs:56-66
         b->gain_window = window;
+        b->per_stream_gain = per_stream && g.enabled;
         band_pass_coefficients(filters->band_pass, b->bq);
         b->has_filters = true;
         return 0;
     });
+}
+
+int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref) {
+    return stream_batch_set_filters(b, filters, rms_level_ref, false);
+}
+int rp_stream_batch_set_filters_bank(rp_stream_batch *b, const rp_filters_config *filters) {
+    return stream_batch_set_filters(b, filters, NAN, true);
 }
 
 int rp_stream_batch_levels(rp_stream_batch *b, float *rms, float *gains) {
