@@ -197,6 +197,19 @@ extern "C" {
     pub fn rp_wakeword_bank_max_len(bank: *const rp_wakeword_bank, wakeword: i64) -> c_int;
     pub fn rp_wakeword_bank_set_rms_levels(bank: *mut rp_wakeword_bank, rms_levels: *const f32) -> c_int;
     pub fn rp_wakeword_bank_rms_level(bank: *const rp_wakeword_bank, wakeword: i64) -> f32;
+    pub fn rp_wakeword_bank_reserve(bank: *mut rp_wakeword_bank, max_len: c_int, n_wakewords: usize, n_rows: usize) -> c_int;
+    pub fn rp_wakeword_bank_size(bank: *const rp_wakeword_bank) -> c_int;
+    pub fn rp_wakeword_bank_reserved_len(bank: *const rp_wakeword_bank) -> c_int;
+    pub fn rp_wakeword_bank_pool_growths(bank: *const rp_wakeword_bank) -> c_int;
+    pub fn rp_wakeword_bank_put(bank: *mut rp_wakeword_bank, first: usize, n: usize, counts: *const i32, lens: *const i32, feats: *const f32,
+                                avg_lens: *const i32, avg_feats: *const f32, thresholds: *const f32, avg_thresholds: *const f32,
+                                rms_levels: *const f32) -> c_int;
+    pub fn rp_wakeword_bank_put_from_rpw(bank: *mut rp_wakeword_bank, first: usize, n: usize, rpw_buffers: *const *const u8,
+                                         rpw_lens: *const usize) -> c_int;
+    pub fn rp_wakeword_bank_enrol(bank: *mut rp_wakeword_bank, first: usize, n: usize, names: *const *const c_char, thresholds: *const f32,
+                                  avg_thresholds: *const f32, counts: *const usize, sample_names: *const *const c_char,
+                                  wav_buffers: *const *const u8, wav_lens: *const usize, rms_from_files: c_int, out_rpw: *mut *mut u8,
+                                  out_lens: *mut usize) -> c_int;
     pub fn rp_frontend_batch_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
                                   filters: *const rp_filters_config, bank: *const rp_wakeword_bank, stream_wakeword: *const i32,
                                   pcm_out: *mut f32, out_stride: usize, rms: *mut f32, gains: *mut f32) -> c_int;
@@ -403,6 +416,7 @@ impl Templates {
 }
 /// A bank of personal wakeword references on the device: stream `s` of a bank call carries wakeword `stream_wakeword[s]` (-1: none) --
 /// one `Rustpotter` per thread, each with its own wakeword (src/detector.rs:304-346), as one batch.  Borrows the context it was made on.
+/// `n_wakewords` is the count at creation; a bank that has been put or enrolled into reports the current one through `size()`.
 pub struct WakewordBank { h: *mut rp_wakeword_bank, pub n_wakewords: usize }
 impl Drop for WakewordBank { fn drop(&mut self) { unsafe { rp_wakeword_bank_free(self.h) } } }
 impl WakewordBank {
@@ -417,8 +431,66 @@ impl WakewordBank {
     pub fn rms_level(&self, wakeword: usize) -> f32 { unsafe { rp_wakeword_bank_rms_level(self.h, wakeword as i64) } }
     /// new levels for all wakewords (NaN: none), in force from the next call that uses the bank
     pub fn set_rms_levels(&mut self, rms_levels: &[f32]) -> Result<(), String> {
-        assert!(rms_levels.len() == self.n_wakewords);
+        assert!(rms_levels.len() == self.size());
         status(unsafe { rp_wakeword_bank_set_rms_levels(self.h, rms_levels.as_ptr()) })
+    }
+    /// wakewords in the bank now
+    pub fn size(&self) -> usize { unsafe { rp_wakeword_bank_size(self.h) }.max(0) as usize }
+    /// the longest window the bank may ever hold (`reserve`), 0: not reserved
+    pub fn reserved_len(&self) -> usize { unsafe { rp_wakeword_bank_reserved_len(self.h) }.max(0) as usize }
+    /// how often the template pools were replaced by larger ones
+    pub fn pool_growths(&self) -> usize { unsafe { rp_wakeword_bank_pool_growths(self.h) }.max(0) as usize }
+    // The calls below change the bank through `&self`: a `StreamBatch` borrows its bank for life, and changing the bank under a live batch
+    // is what they are for.  The library orders every update on the context's stream and returns when it is complete.
+    /// Declares the longest window the bank will ever hold (what a live batch over it keeps room for; 0: leave) and pre-sizes the pools
+    /// (hints; 0: leave).  Refused below the current longest window, and for a new value while a stream batch over the bank exists.
+    pub fn reserve(&self, max_len: usize, n_wakewords: usize, n_rows: usize) -> Result<(), String> {
+        status(unsafe { rp_wakeword_bank_reserve(self.h, max_len as c_int, n_wakewords, n_rows) })
+    }
+    /// Wakewords as `HipContext::wakeword_bank` takes them into the slots `first .. first + n - 1`: replaced below `size()`, appended at it.
+    /// `rms_levels`: one per wakeword, or empty for none (NaN).  A refused call leaves the bank as it was.
+    pub fn put(&self, first: usize, mfcc_size: u16, wakewords: &[(Vec<Vec<f32>>, Vec<f32>, Option<f32>, Option<f32>)], rms_levels: &[f32]) -> Result<(), String> {
+        assert!(rms_levels.is_empty() || rms_levels.len() == wakewords.len());
+        let k = mfcc_size as usize;
+        let counts: Vec<i32> = wakewords.iter().map(|w| w.0.len() as i32).collect();
+        let lens: Vec<i32> = wakewords.iter().flat_map(|w| w.0.iter().map(|t| (t.len() / k) as i32)).collect();
+        let feats: Vec<f32> = wakewords.iter().flat_map(|w| w.0.iter().flatten().copied()).collect();
+        let avg_lens: Vec<i32> = wakewords.iter().map(|w| (w.1.len() / k) as i32).collect();
+        let avg_feats: Vec<f32> = wakewords.iter().flat_map(|w| w.1.iter().copied()).collect();
+        let thr: Vec<f32> = wakewords.iter().map(|w| w.2.unwrap_or(f32::NAN)).collect();
+        let athr: Vec<f32> = wakewords.iter().map(|w| w.3.unwrap_or(f32::NAN)).collect();
+        status(unsafe {
+            rp_wakeword_bank_put(self.h, first, wakewords.len(), counts.as_ptr(), lens.as_ptr(), feats.as_ptr(), avg_lens.as_ptr(), avg_feats.as_ptr(),
+                                 thr.as_ptr(), athr.as_ptr(), if rms_levels.is_empty() { std::ptr::null() } else { rms_levels.as_ptr() })
+        })
+    }
+    /// `.rpw` bytes into the slots `first .. first + n - 1`; each wakeword keeps its file's thresholds and rms_level.
+    pub fn put_from_rpw(&self, first: usize, rpw: &[Vec<u8>]) -> Result<(), String> {
+        let ptrs: Vec<*const u8> = rpw.iter().map(|b| b.as_ptr()).collect();
+        let lens: Vec<usize> = rpw.iter().map(|b| b.len()).collect();
+        status(unsafe { rp_wakeword_bank_put_from_rpw(self.h, first, rpw.len(), ptrs.as_ptr(), lens.as_ptr()) })
+    }
+    /// Enrolment straight into the slots `first .. first + n - 1` (`wakeword_refs_from_sample_buffers` without the feature round trip);
+    /// `want_rpw`: also the `.rpw` bytes of every wakeword, exactly what that function returns (else an empty vector).
+    pub fn enrol(&self, first: usize, wakewords: &[WakewordSamples], want_rpw: bool) -> Result<Vec<Vec<u8>>, String> {
+        let names: Vec<CString> = wakewords.iter().map(|w| CString::new(w.name.as_str()).map_err(|e| e.to_string())).collect::<Result<_, _>>()?;
+        let name_ptrs: Vec<*const c_char> = names.iter().map(|n| n.as_ptr()).collect();
+        let thr: Vec<f32> = wakewords.iter().map(|w| w.threshold.unwrap_or(f32::NAN)).collect();
+        let athr: Vec<f32> = wakewords.iter().map(|w| w.avg_threshold.unwrap_or(f32::NAN)).collect();
+        let counts: Vec<usize> = wakewords.iter().map(|w| w.samples.len()).collect();
+        let snames: Vec<CString> = wakewords.iter().flat_map(|w| w.samples.iter()).map(|s| CString::new(s.0.as_str()).unwrap()).collect();
+        let sname_ptrs: Vec<*const c_char> = snames.iter().map(|n| n.as_ptr()).collect();
+        let bufs: Vec<*const u8> = wakewords.iter().flat_map(|w| w.samples.iter()).map(|s| s.1.as_ptr()).collect();
+        let lens: Vec<usize> = wakewords.iter().flat_map(|w| w.samples.iter()).map(|s| s.1.len()).collect();
+        let mut out: Vec<*mut u8> = vec![std::ptr::null_mut(); wakewords.len()];
+        let mut out_lens = vec![0usize; wakewords.len()];
+        let (po, pl) = if want_rpw { (out.as_mut_ptr(), out_lens.as_mut_ptr()) } else { (std::ptr::null_mut(), std::ptr::null_mut()) };
+        status(unsafe {
+            rp_wakeword_bank_enrol(self.h, first, wakewords.len(), name_ptrs.as_ptr(), thr.as_ptr(), athr.as_ptr(), counts.as_ptr(), sname_ptrs.as_ptr(),
+                                   bufs.as_ptr(), lens.as_ptr(), 0, po, pl)
+        })?;
+        if !want_rpw { return Ok(Vec::new()); }
+        out.into_iter().zip(out_lens).map(|(p, n)| take_buffer(0, p, n)).collect()
     }
 }
 /// A wakeword model on the device (`WakewordNN`, src/wakewords/nn/wakeword_nn.rs:17-37).

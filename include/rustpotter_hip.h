@@ -485,6 +485,55 @@ int rp_wakeword_bank_max_len(const rp_wakeword_bank *bank, long long wakeword);
 int rp_wakeword_bank_set_rms_levels(rp_wakeword_bank *bank, const float *rms_levels);
 /* ... of one wakeword as last set; NaN for a NULL bank or an index outside the bank. */
 float rp_wakeword_bank_rms_level(const rp_wakeword_bank *bank, long long wakeword);
+/* ---- A bank that changes: enrol and replace wakewords, also under live-stream batches.
+ * rp_wakeword_bank_put / _put_from_rpw / _enrol write the wakewords first .. first + n - 1.  first <= rp_wakeword_bank_size is required (a bank
+ * has no holes): indices below the size are REPLACED, indices at or above it extend the bank; n == 0 succeeds and changes nothing.  Every
+ * limit and wording of rp_wakeword_bank_new / _new_from_rpw applies per wakeword ("wakeword <index>: <reason>", <index> = the bank index
+ * first + i): 1..RP_WAKEWORD_BANK_MAX_TEMPLATES templates, finite features, an averaged template no longer than the window, the length limit of
+ * the device kernels, no wakeword models, one mfcc_size (the bank's; a .rpw of another is refused with the reference's "different mfcc size"
+ * text.  Only an empty bank without a reserved length and without a stream batch takes the mfcc_size of the first file put into it).  A call
+ * that is refused or fails leaves the bank exactly as it was: size, longest window, rms levels, every score.
+ * Storage: the bank's device arrays are pools.  New templates are appended, a replaced wakeword's old ones stay behind as garbage, and a full
+ * pool is replaced by one of at least twice the size into which only the live templates move (on the device) -- growth is the compaction.
+ * Ordering: every update is enqueued on the context's stream behind whatever still reads the bank, and the call returns after it has
+ * completed (as rp_wakeword_bank_set_rms_levels).  The next call that uses the bank sees the new contents, the next rp_stream_batch_process
+ * of a live batch over it included; nothing in flight ever sees a half-written wakeword.
+ * Live-stream batches: a batch sizes every stream's MFCC history and gain ring once, so the bank must never come to hold a window longer than
+ * a live batch has room for.  rp_wakeword_bank_reserve(max_len) declares the longest window the bank will ever hold: put / enrol refuse a
+ * longer one, and rp_stream_batch_new_bank keeps room for max(reserved, longest now, 1) frames.  Without a reserved length, while a batch
+ * over the bank exists, a wakeword longer than the current longest is refused (the error says to call rp_wakeword_bank_reserve before
+ * creating the batch); without either, any admissible length goes.  The bank counts its batches (a batch is freed before its bank).
+ * The bank does not touch batches: a stream that holds an index while that index is replaced scores the new templates from the next call on,
+ * with the detector state it has (and the gain normaliser of rp_stream_batch_set_filters_bank reads the new level and window size, as
+ * it reads them at the start of every call).  For the reference's remove_wakeword + add_wakeword, call rp_stream_batch_set_wakewords for
+ * those streams: it resets them as it always does.  Removing a wakeword is not offered: disconnect its streams; the next put reuses the slot. */
+/* max_len > 0: no wakeword's window may become longer.  At least the current longest and within the length limit of the device kernels for the
+ * bank's mfcc_size; it can change only while no stream batch over the bank exists.  max_len == 0 leaves it as it is.  n_wakewords / n_rows
+ * pre-size the pools for that many wakewords / template rows (averaged templates included) in all; 0 leaves them; hints, never limits.
+ * A reserved bank of n_wakewords == 0 is the natural starting state of a service: a batch over it takes the bank's declared mfcc_size, and
+ * its (mfcc_size, band_size) pair is checked although it is empty. */
+int rp_wakeword_bank_reserve(rp_wakeword_bank *bank, int max_len, size_t n_wakewords, size_t n_rows);
+/* wakewords in the bank; -1 for a NULL bank */
+int rp_wakeword_bank_size(const rp_wakeword_bank *bank);
+/* the reserved length, 0 = none; -1 for a NULL bank */
+int rp_wakeword_bank_reserved_len(const rp_wakeword_bank *bank);
+/* how often the template pools have been replaced by larger ones so far (tests and capacity planning); -1 for a NULL bank */
+int rp_wakeword_bank_pool_growths(const rp_wakeword_bank *bank);
+/* HOST arrays in the flat layout of rp_wakeword_bank_new for the n wakewords, whatever the pointer flag of the context; rms_levels [n]: each
+ * wakeword's reference level (NULL = NaN for all, as rp_wakeword_bank_new leaves them).  The rows are prepared on the device
+ * (bank_put_kernel) with the bits rp_wakeword_bank_new gives them. */
+int rp_wakeword_bank_put(rp_wakeword_bank *bank, size_t first, size_t n, const int32_t *counts, const int32_t *lens, const float *feats,
+                         const int32_t *avg_lens, const float *avg_feats, const float *thresholds, const float *avg_thresholds,
+                         const float *rms_levels);
+/* The same from .rpw bytes, as rp_wakeword_bank_new_from_rpw: each wakeword keeps its file's thresholds and rms_level. */
+int rp_wakeword_bank_put_from_rpw(rp_wakeword_bank *bank, size_t first, size_t n, const uint8_t *const *rpw_buffers, const size_t *rpw_lens);
+/* Enrolment straight into bank slots: the arguments of rp_wakeword_ref_build_batch (mfcc_size is the bank's; thresholds NaN = None), the same
+ * stages up to the averaged template, and from there the templates go from the enrolment workspace into the bank on the device -- no feature
+ * round trip.  Each wakeword's rms_level is what rp_wakeword_bank_new_from_rpw would take from its file.  out_rpw / out_lens [n] may both be
+ * NULL; given, they receive exactly rp_wakeword_ref_build_batch's bytes (free each with rp_buffer_free), and on failure every entry is NULL. */
+int rp_wakeword_bank_enrol(rp_wakeword_bank *bank, size_t first, size_t n, const char *const *names, const float *thresholds,
+                           const float *avg_thresholds, const size_t *counts, const char *const *sample_names,
+                           const uint8_t *const *wav_buffers, const size_t *wav_lens, int rms_from_files, uint8_t **out_rpw, size_t *out_lens);
 /* rp_frontend_batch with every stream's OWN gain-normaliser parameters, what goes in front of rp_batch_detect_bank: stream s works towards
  * rms_level_ref = the rms_level of bank[stream_wakeword[s]] (filters->gain_normalizer.gain_ref for every stream when has_gain_ref) over a
  * window of max(max_len(s) / 3, 1) chunk levels (src/detector.rs:337).  stream_wakeword[s] == -1 is a detector without wakewords, whose
@@ -623,7 +672,8 @@ int rp_stream_batch_process_multi(rp_stream_batch *b, const void *pcm, rp_sample
  * The batch borrows `ctx` and `bank` (the bank must belong to `ctx`) and keeps its own device copy of the indices.  stream_wakeword [S]: a
  * host array under RP_CTX_HOST_POINTERS -- an index outside [-1, n_wakewords) is then an error that names the stream, found before
  * anything is allocated -- else a device array, copied; the kernels treat such an index as -1.  Every stream keeps an MFCC history of
- * rp_wakeword_bank_max_len(bank, -1) - 1 frames; the window ending at a new frame starts max_len(s) - 1 frames before it.
+ * rp_wakeword_bank_max_len(bank, -1) - 1 frames (of max(that, rp_wakeword_bank_reserved_len(bank)) - 1 for a reserved bank, which may then
+ * change under the batch: see rp_wakeword_bank_reserve); the window ending at a new frame starts max_len(s) - 1 frames before it.
  * Limits as the bank calls: mfcc_size 5, 13 or 16 with band_size 3..6, or band_size 0 (every score 0, no detection); an empty bank or all
  * indices -1: calls succeed and report nothing.  Arithmetic: f32 vector FMAs whatever rp_ctx_set_arithmetic says (neither read nor
  * changed); rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK_STREAM.
@@ -638,7 +688,9 @@ int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const in
 /* Connect / disconnect of device slots, at any time between process calls: streams first_stream .. first_stream + n - 1 get the indices
  * wakewords [n] (host or device array, checked as above; -1: none) and each is reset exactly as rp_stream_batch_reset(b, s) does
  * (add_wakeword on a detector without wakewords calls reset(), src/detector.rs:304-307; the filters' state and the resampler are not
- * touched).  A refused index changes nothing.  An error on a batch not made by rp_stream_batch_new_bank. */
+ * touched).  A refused index changes nothing.  An error on a batch not made by rp_stream_batch_new_bank.
+ * Replacing a wakeword in the bank (rp_wakeword_bank_put / _enrol) does not touch the streams that hold its index: they score the new
+ * templates from the next call with the state they have.  Call this function for them to get remove_wakeword + add_wakeword. */
 int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *wakewords);
 /* rp_stream_batch_set_filters for a batch made by rp_stream_batch_new_bank (an error on any other): the gain normaliser of stream s works
  * towards the rms_level of ITS wakeword (rp_wakeword_bank_rms_level; filters->gain_normalizer.gain_ref for every stream when

@@ -116,6 +116,8 @@ SYMBOLS = [
     "rp_wakeword_bank_new", "rp_wakeword_bank_new_from_rpw", "rp_wakeword_bank_free", "rp_wakeword_bank_max_len", "rp_dtw_score_bank",
     "rp_batch_detect_bank", "rp_stream_batch_new_bank", "rp_stream_batch_set_wakewords",
     "rp_wakeword_bank_set_rms_levels", "rp_wakeword_bank_rms_level", "rp_frontend_batch_bank", "rp_stream_batch_set_filters_bank",
+    "rp_wakeword_bank_reserve", "rp_wakeword_bank_size", "rp_wakeword_bank_reserved_len", "rp_wakeword_bank_pool_growths",
+    "rp_wakeword_bank_put", "rp_wakeword_bank_put_from_rpw", "rp_wakeword_bank_enrol",
 ]
 
 
@@ -249,6 +251,14 @@ def load_library():
     L.rp_wakeword_bank_set_rms_levels.argtypes = [vp, fp]
     L.rp_wakeword_bank_rms_level.argtypes = [vp, C.c_longlong]
     L.rp_wakeword_bank_rms_level.restype = C.c_float
+    L.rp_wakeword_bank_reserve.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t]
+    L.rp_wakeword_bank_size.argtypes = [vp]
+    L.rp_wakeword_bank_reserved_len.argtypes = [vp]
+    L.rp_wakeword_bank_pool_growths.argtypes = [vp]
+    L.rp_wakeword_bank_put.argtypes = [vp, C.c_size_t, C.c_size_t, i32p, i32p, fp, i32p, fp, fp, fp, fp]
+    L.rp_wakeword_bank_put_from_rpw.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
+    L.rp_wakeword_bank_enrol.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p), fp, fp, C.POINTER(C.c_size_t), C.POINTER(C.c_char_p),
+                                         C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rp_frontend_batch_bank.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(_FiltersCfg), vp, vp, vp, C.c_size_t, vp, vp]
     L.rp_stream_batch_set_filters_bank.argtypes = [vp, C.POINTER(_FiltersCfg)]
     L.rp_dtw_score_bank.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t]
@@ -527,10 +537,29 @@ class WakewordBank:
     """rp_wakeword_bank: W wakeword references resident on the device, scored per stream through an index
     (BatchContext.dtw_scores_bank / batch_detect_bank).  Exactly one of
     wakewords = [(templates, avg or None, threshold or None, avg_threshold or None), ...] with templates a list of [len][K] arrays, or
-    rpw = [bytes of a wakeword reference .rpw, ...] (what BatchContext.build_wakeword_refs returns)."""
+    rpw = [bytes of a wakeword reference .rpw, ...] (what BatchContext.build_wakeword_refs returns).  mfcc_size: what an empty list of
+    wakewords declares (a bank to enrol into later: reserve / put / put_rpw / enrol)."""
 
-    def __init__(self, ctx, wakewords=None, rpw=None):
+    @staticmethod
+    def _flat(wakewords):
+        """the flat arrays of rp_wakeword_bank_new / _put: (W, K, counts, lens, feats, avg_lens, avg_feats or None, thr, athr)"""
         import numpy as np
+        W = len(wakewords)
+        nan = float("nan")
+        tmpl = [[np.ascontiguousarray(t, np.float32) for t in w[0]] for w in wakewords]
+        avgs = [None if w[1] is None else np.ascontiguousarray(w[1], np.float32) for w in wakewords]
+        K = tmpl[0][0].shape[1] if W else 1
+        counts = np.array([len(t) for t in tmpl], np.int32)
+        lens = np.array([t.shape[0] for ww in tmpl for t in ww], np.int32)
+        feats = np.ascontiguousarray(np.concatenate([t.reshape(-1) for ww in tmpl for t in ww]) if lens.size else np.zeros(0, np.float32), np.float32)
+        avg_lens = np.array([0 if a is None else a.shape[0] for a in avgs], np.int32)
+        some = [a.reshape(-1) for a in avgs if a is not None]
+        avg_feats = np.ascontiguousarray(np.concatenate(some), np.float32) if some else None
+        thr = np.array([nan if w[2] is None else w[2] for w in wakewords], np.float32)
+        athr = np.array([nan if w[3] is None else w[3] for w in wakewords], np.float32)
+        return W, K, counts, lens, feats, avg_lens, avg_feats, thr, athr
+
+    def __init__(self, ctx, wakewords=None, rpw=None, mfcc_size=None):
         if (wakewords is None) == (rpw is None):
             raise RustpotterError("WakewordBank takes either wakewords or rpw")
         self._L = load_library()
@@ -542,28 +571,89 @@ class WakewordBank:
             bufs = [bytes(b) for b in rpw]
             r = self._L.rp_wakeword_bank_new_from_rpw(ctx._h, W, (C.c_char_p * W)(*bufs), (C.c_size_t * W)(*[len(b) for b in bufs]), C.byref(self._h))
         else:
-            W = len(wakewords)
-            nan = float("nan")
-            tmpl = [[np.ascontiguousarray(t, np.float32) for t in w[0]] for w in wakewords]
-            avgs = [None if w[1] is None else np.ascontiguousarray(w[1], np.float32) for w in wakewords]
-            K = tmpl[0][0].shape[1] if W else 1
-            counts = np.array([len(t) for t in tmpl], np.int32)
-            lens = np.array([t.shape[0] for ww in tmpl for t in ww], np.int32)
-            feats = np.ascontiguousarray(np.concatenate([t.reshape(-1) for ww in tmpl for t in ww]) if lens.size else np.zeros(0, np.float32), np.float32)
-            avg_lens = np.array([0 if a is None else a.shape[0] for a in avgs], np.int32)
-            some = [a.reshape(-1) for a in avgs if a is not None]
-            avg_feats = np.ascontiguousarray(np.concatenate(some), np.float32) if some else None
-            thr = np.array([nan if w[2] is None else w[2] for w in wakewords], np.float32)
-            athr = np.array([nan if w[3] is None else w[3] for w in wakewords], np.float32)
+            W, K, counts, lens, feats, avg_lens, avg_feats, thr, athr = self._flat(wakewords)
+            if W == 0 and mfcc_size is not None:
+                K = int(mfcc_size)
             r = self._L.rp_wakeword_bank_new(ctx._h, W, K, counts.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), feats.ctypes.data_as(fp),
                                              avg_lens.ctypes.data_as(i32p), None if avg_feats is None else avg_feats.ctypes.data_as(fp),
                                              thr.ctypes.data_as(fp), athr.ctypes.data_as(fp), C.byref(self._h))
         if r < 0:
             self._h = None
             raise _err()
-        self.W = W
-        self.max_lens = [int(self._L.rp_wakeword_bank_max_len(self._h, w)) for w in range(W)]   # window length of every wakeword
+        self._refresh()
+
+    def _refresh(self):
+        self.W = int(self._L.rp_wakeword_bank_size(self._h))
+        self.max_lens = [int(self._L.rp_wakeword_bank_max_len(self._h, w)) for w in range(self.W)]   # window length of every wakeword
         self.max_len = int(self._L.rp_wakeword_bank_max_len(self._h, -1))
+
+    @property
+    def reserved_len(self):
+        """rp_wakeword_bank_reserved_len: the longest window the bank may ever hold, 0 = not reserved"""
+        return int(self._L.rp_wakeword_bank_reserved_len(self._h))
+
+    @property
+    def pool_growths(self):
+        return int(self._L.rp_wakeword_bank_pool_growths(self._h))
+
+    def reserve(self, max_len=0, n_wakewords=0, n_rows=0):
+        """rp_wakeword_bank_reserve: the longest window the bank will ever hold (what a live batch over it keeps room for) and pool size hints"""
+        r = self._L.rp_wakeword_bank_reserve(self._h, max_len, n_wakewords, n_rows)
+        self._refresh()
+        if r < 0:
+            raise _err()
+
+    def put(self, first, wakewords, rms_levels=None):
+        """rp_wakeword_bank_put: `wakewords` (as the constructor's) become the wakewords first .. first + n - 1 -- replaced below W, appended at W"""
+        import numpy as np
+        i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        n, _, counts, lens, feats, avg_lens, avg_feats, thr, athr = self._flat(wakewords)
+        lv = None if rms_levels is None else np.ascontiguousarray(rms_levels, np.float32)
+        if lv is not None and lv.shape != (n,):
+            raise ValueError("rms_levels must be [n]")
+        r = self._L.rp_wakeword_bank_put(self._h, first, n, counts.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), feats.ctypes.data_as(fp),
+                                         avg_lens.ctypes.data_as(i32p), None if avg_feats is None else avg_feats.ctypes.data_as(fp),
+                                         thr.ctypes.data_as(fp), athr.ctypes.data_as(fp), None if lv is None else lv.ctypes.data_as(fp))
+        self._refresh()
+        if r < 0:
+            raise _err()
+
+    def put_rpw(self, first, rpw):
+        """rp_wakeword_bank_put_from_rpw: .rpw bytes into the slots first .. first + n - 1, thresholds and rms_level from each file"""
+        n = len(rpw)
+        bufs = [bytes(b) for b in rpw]
+        r = self._L.rp_wakeword_bank_put_from_rpw(self._h, first, n, (C.c_char_p * n)(*bufs), (C.c_size_t * n)(*[len(b) for b in bufs]))
+        self._refresh()
+        if r < 0:
+            raise _err()
+
+    def enrol(self, first, wakewords, from_files=True, want_rpw=False):
+        """rp_wakeword_bank_enrol: wakewords as BatchContext.build_wakeword_refs takes them -- (name, ordered {sample name: wav bytes},
+        threshold or None, avg_threshold or None) -- enrolled straight into the slots first .. first + n - 1.  want_rpw: also return the
+        .rpw bytes of each (what build_wakeword_refs gives); else None."""
+        n = len(wakewords)
+        nan = float("nan")
+        names = (C.c_char_p * n)(*[w[0].encode() for w in wakewords])
+        thr = (C.c_float * n)(*[nan if w[2] is None else w[2] for w in wakewords])
+        athr = (C.c_float * n)(*[nan if w[3] is None else w[3] for w in wakewords])
+        counts = (C.c_size_t * n)(*[len(w[1]) for w in wakewords])
+        snames = [k.encode() for w in wakewords for k in w[1]]
+        bufs = [bytes(v) for w in wakewords for v in w[1].values()]
+        m = len(snames)
+        out = (C.c_void_p * n)() if want_rpw else None
+        out_lens = (C.c_size_t * n)() if want_rpw else None
+        r = self._L.rp_wakeword_bank_enrol(self._h, first, n, names, thr, athr, counts, (C.c_char_p * m)(*snames), (C.c_char_p * m)(*bufs),
+                                           (C.c_size_t * m)(*[len(b) for b in bufs]), 1 if from_files else 0, out, out_lens)
+        self._refresh()
+        if r < 0:
+            raise _err()
+        if not want_rpw:
+            return None
+        res = []
+        for w in range(n):
+            res.append(C.string_at(out[w], out_lens[w]))
+            self._L.rp_buffer_free(out[w])
+        return res
 
     @property
     def rms_levels(self):
@@ -644,10 +734,14 @@ class StreamBatch:
         # MFCC frames a stream gains per input frame: 3 (30 ms frames) or 4 (the 40 ms frames of 11.025 / 22.05 kHz input)
         self.frames_per_chunk = resampler_frame_lengths(sample_rate)[1] // 160
 
-    def __del__(self):
+    def close(self):
+        """rp_stream_batch_free now (a bank counts the batches over it: see WakewordBank.reserve)"""
         if getattr(self, "_h", None):
             self._L.rp_stream_batch_free(self._h)
             self._h = None
+
+    def __del__(self):
+        self.close()
 
     def _indices(self, idx):
         """wakeword indices as the context takes them: a host int32 array, or the address of a device one"""

@@ -453,23 +453,28 @@ bool average_templates_batch(Ctx *ctx, size_t W, int K, const int32_t *counts, c
 
 // build_wakeword_ref for W wakewords.  What a wakeword's bytes depend on is computed as the single call computes it: the same wav
 // decoding and chunk levels on the host, the same resampler pair and MFCC kernel (over all samples at once: a frame sees its own
-// sample only), the same normalisation and fold, restated on the device.
-bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const float *thresholds, const float *avg_thresholds,
-                         const size_t *counts, const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens,
-                         int mfcc_size, bool rms_median, std::vector<WakewordRefData> *out) {
-    out->clear();
+// sample only), the same normalisation and fold, restated on the device.  enrol_front is the part up to and including the fold: it leaves
+// the templates and averages in ctx->ws_enrol and everything the host knows in `out`.  Two tails take it from
+// there: enrol_fetch (the copy back the .rpw writer needs) and Bank::put_rows (rp_wakeword_bank_enrol: straight into a bank, whose index
+// of the call's first wakeword, first_index, the refusals count from).
+bool enrol_front(Ctx *ctx, size_t W, const char *const *names, const float *thresholds, const float *avg_thresholds,
+                 const size_t *counts, const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens,
+                 int mfcc_size, bool rms_median, size_t first_index, EnrolBatch *out) {
+    *out = EnrolBatch();
     if (W == 0) return true;
     if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return false;
     const int K = mfcc_size;
     auto refuse = [&](size_t w, const std::string &text) {
-        set_last_error("wakeword " + std::to_string(w) + " (" + names[w] + "): " + text);
+        set_last_error("wakeword " + std::to_string(first_index + w) + " (" + names[w] + "): " + text);
         return false;
     };
     // 1. every wav parsed on the host; what the single call refuses is refused here, in its order
-    struct Sample { std::vector<float> mono; const Resampler *rs = nullptr; size_t enc_chunk = 480; int frames = 0; float level = 0.f; bool live = true; int64_t dst_row = 0; };
-    std::vector<Sample> smp;
-    std::vector<WakewordRefData> refs(W);
-    std::vector<std::vector<size_t>> slot_sample(W);   // per template slot (file order) its sample
+    typedef EnrolSample Sample;
+    std::vector<Sample> &smp = out->smp;
+    std::vector<WakewordRefData> &refs = out->refs;
+    std::vector<std::vector<size_t>> &slot_sample = out->slot_sample;   // per template slot (file order) its sample
+    refs.resize(W);
+    slot_sample.resize(W);
     const MfccTablesDev *tb = nullptr;
     size_t total = 0;
     for (size_t w = 0; w < W; ++w) total += counts[w];
@@ -554,7 +559,7 @@ bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const flo
     if (!plan_average(W, K, tcounts.data(), flens.data(), false, &plan)) return false;
     for (size_t w = 0, t = 0; w < W; ++w)
         for (size_t k : fold_order(refs[w])) smp[slot_sample[w][k]].dst_row = plan.row_off()[t++];
-    std::vector<float> all((plan.rows + plan.avg_rows) * (size_t)K);
+    const size_t all_bytes = (plan.rows + plan.avg_rows) * (size_t)K * 4;
     {
         std::vector<int32_t> nf(S);
         std::vector<int64_t> dst(S);
@@ -563,7 +568,7 @@ bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const flo
         // for all rows cost more in page faults and unmapping than everything the device does in this call
         const size_t slab_rows = std::max<size_t>(1, std::min(S, ((size_t)128 << 20) / (n_max * 4)));
         if (!dpcm.reserve(S * n_max * 4) || !draw.reserve(S * nf_max * (size_t)K * 4) || !dnf.reserve(S * 4) || !ddst.reserve(S * 8) ||
-            !ctx->ws_enrol.reserve(all.size() * 4) || !ctx->enrol_stage.reserve(slab_rows * n_max * 4))
+            !ctx->ws_enrol.reserve(all_bytes) || !ctx->enrol_stage.reserve(slab_rows * n_max * 4))
             return false;
         float *stage = ctx->enrol_stage.as<float>();
         for (size_t q0 = 0; q0 < S; q0 += slab_rows) {
@@ -589,31 +594,55 @@ bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const flo
             !hip_ok(launch_normalize_samples(ctx->stream, draw.as<float>(), S, nf_max, K, dnf.as<int32_t>(), ddst.as<int64_t>(), d_tmpl), "normalize_samples_kernel") ||
             // 6. the averaging kernel over all wakewords with two or more templates
             !run_average(ctx, K, plan, d_tmpl, d_avg) ||
-            // 7. one copy back of the templates and averages
-            !hip_ok(hipMemcpyAsync(all.data(), d_tmpl, all.size() * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync") ||
-            !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+            !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))   // (the index arrays above are this function's own)
             return false;
     }
-    // 8. levels and the data the writer takes
-    parallel_for(W, [&](size_t w) {
+    // 8. levels, and where a tail finds every wakeword's average
+    out->rows = plan.rows; out->avg_rows = plan.avg_rows;
+    for (size_t w = 0; w < W; ++w) {
         WakewordRefData &r = refs[w];
         std::vector<float> levels;
+        for (size_t k = 0; k < r.tnames.size(); ++k) levels.push_back(smp[slot_sample[w][k]].level);
+        r.rms_level = wakeword_rms_level(levels, rms_median);
+        r.has_avg = plan.out_row()[w] >= 0;
+        if (r.has_avg) r.avg_len = plan.lens()[plan.first()[w]];
+        out->avg_row.push_back(plan.out_row()[w]);
+    }
+    return true;
+}
+
+// 7. one copy back of the templates and averages, and the data the writer takes
+bool enrol_fetch(Ctx *ctx, int K, EnrolBatch *b) {
+    if (b->refs.empty()) return true;
+    std::vector<float> all((b->rows + b->avg_rows) * (size_t)K);
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice") ||
+        !hip_ok(hipMemcpyAsync(all.data(), ctx->ws_enrol.p, all.size() * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync") ||
+        !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+        return false;
+    parallel_for(b->refs.size(), [&](size_t w) {
+        WakewordRefData &r = b->refs[w];
         r.feats.resize(r.tnames.size());
         for (size_t k = 0; k < r.tnames.size(); ++k) {
-            const Sample &s = smp[slot_sample[w][k]];
-            levels.push_back(s.level);
+            const EnrolSample &s = b->smp[b->slot_sample[w][k]];
             r.feats[k].assign(all.begin() + (size_t)s.dst_row * K, all.begin() + ((size_t)s.dst_row + (size_t)s.frames) * K);
         }
-        r.rms_level = wakeword_rms_level(levels, rms_median);
-        const int64_t row = plan.out_row()[w];
-        r.has_avg = row >= 0;
         if (r.has_avg) {
-            r.avg_len = plan.lens()[plan.first()[w]];
-            const float *a = all.data() + (plan.rows + (size_t)row) * K;
+            const float *a = all.data() + (b->rows + (size_t)b->avg_row[w]) * K;
             r.avg.assign(a, a + (size_t)r.avg_len * K);
         }
     });
-    *out = std::move(refs);
+    return true;
+}
+
+bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const float *thresholds, const float *avg_thresholds,
+                         const size_t *counts, const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens,
+                         int mfcc_size, bool rms_median, std::vector<WakewordRefData> *out) {
+    out->clear();
+    EnrolBatch b;
+    if (!enrol_front(ctx, W, names, thresholds, avg_thresholds, counts, sample_names, wavs, wav_lens, mfcc_size, rms_median, 0, &b) ||
+        !enrol_fetch(ctx, mfcc_size, &b))
+        return false;
+    *out = std::move(b.refs);
     return true;
 }
 

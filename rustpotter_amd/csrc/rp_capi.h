@@ -90,7 +90,7 @@ void band_pass_coefficients(const rp_band_pass_config &b, float q[5]);
 bool resample_rows(Ctx *c, const ResamplerDev &rs, const void *pcm, int fmt, int channels, size_t pcm_stride, const float *prev,
                    float *prev_out, size_t S, size_t n_chunks, DevBuf &xs_buf, size_t xs_chunks, float *out, size_t out_stride);
 // rp_bank.cpp
-bool bank_band_ok(const BankDev &d, int band_size);
+bool bank_band_ok(const Bank &bk, int band_size);
 // the per-stream wakeword indices of a bank call, checked (host arrays) and on the device; see rp_bank.cpp
 const int32_t *stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok);
 // rp_frontend_batch and rp_frontend_batch_bank (rp_capi.cpp): with `bank`, every stream takes its gain window and reference level from its own

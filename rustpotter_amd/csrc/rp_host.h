@@ -1,6 +1,8 @@
 // rp_host.h -- host side of librustpotter_hip: constant tables, .rpw reader, device
 // context, and the C++ mirror of the reference's `Rustpotter` (src/detector.rs).
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <map>
 #include <tuple>
 #include <memory>
@@ -63,6 +65,21 @@ bool average_templates_batch(Ctx *ctx, size_t W, int K, const int32_t *counts, c
 bool build_wakeword_refs(Ctx *ctx, size_t W, const char *const *names, const float *thresholds, const float *avg_thresholds,
                          const size_t *counts, const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens,
                          int mfcc_size, bool rms_median, std::vector<WakewordRefData> *out);
+// build_wakeword_refs in two parts.  enrol_front: everything up to and including the fold -- the call's templates (fold order) and averages
+// lie in ctx->ws_enrol, [rows][K] | [avg_rows][K], and `refs` holds what the host knows of every wakeword (name, thresholds, template names
+// and lengths in file order, rms_level, has_avg / avg_len; no features).  enrol_fetch: the copy back that fills the features in.
+struct EnrolSample { std::vector<float> mono; const struct Resampler *rs = nullptr; size_t enc_chunk = 480; int frames = 0; float level = 0.f; bool live = true; int64_t dst_row = 0; };
+struct EnrolBatch {
+    std::vector<WakewordRefData> refs;
+    std::vector<EnrolSample> smp;                    // dst_row: a sample's first row among the templates
+    std::vector<std::vector<size_t>> slot_sample;    // per wakeword and template slot (file order) its sample
+    size_t rows = 0, avg_rows = 0;
+    std::vector<int64_t> avg_row;                    // per wakeword the first row of its average among the averages, -1: none
+};
+bool enrol_front(Ctx *ctx, size_t W, const char *const *names, const float *thresholds, const float *avg_thresholds,
+                 const size_t *counts, const char *const *sample_names, const uint8_t *const *wavs, const size_t *wav_lens,
+                 int mfcc_size, bool rms_median, size_t first_index, EnrolBatch *out);
+bool enrol_fetch(Ctx *ctx, int K, EnrolBatch *b);
 std::vector<uint8_t> serialize_wakeword_ref(const WakewordRefData &r);
 std::vector<std::vector<uint8_t>> serialize_wakeword_refs(const std::vector<WakewordRefData> &refs);   // the same, on several host threads
 std::vector<uint8_t> serialize_wakeword_model(const WakewordModelData &m);
@@ -191,6 +208,37 @@ struct Bank {
     static Bank *create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32_t *lens, const float *feats, const int32_t *avg_lens,
                         const float *avg_feats, const float *thresholds, const float *avg_thresholds);
     ~Bank();
+
+    // ---- a bank that grows (rp_wakeword_bank_reserve / _put / _put_from_rpw / _enrol).  The five device arrays and rms_level are pools:
+    // new entries and rows are appended behind n_entries / n_rows, a replaced wakeword's old ones stay behind as garbage (dead_*), and a full
+    // pool is replaced by a larger one into which only the live entries and rows move (bank_move_kernel).  Everything is enqueued on the
+    // context's stream, so a launch that took the old BankDev by value finishes on the old pools before they are freed.
+    std::vector<int> tlen;          // the host's copy of dev.tlen / dev.trow, [n_entries]
+    std::vector<long long> trow;
+    size_t n_entries = 0, n_rows = 0, dead_entries = 0, dead_rows = 0;
+    size_t cap_ww = 0, cap_entries = 0, cap_rows = 0;
+    size_t grown = 0;               // how often the entry / row pools were replaced (tests)
+    int ceiling = 0;                // rp_wakeword_bank_reserve: no wakeword's window may be longer (0: none)
+    mutable int live_batches = 0;   // stream batches over this bank (rp_stream_batch_new_bank .. _free)
+    DevBuf put_ws;                  // index tables and flags of a put / a move
+    // one wakeword of a put: its sample templates in the wakeword's own order (frames, first row in the source), its averaged template
+    struct PutItem {
+        std::vector<int> lens;
+        std::vector<long long> src;
+        int avg_len = 0;
+        long long avg_src = 0;
+        float threshold = NAN, avg_threshold = NAN, rms_level = NAN;
+        int max_len() const { int m = 0; for (int l : lens) m = l > m ? l : m; return m; }
+    };
+    // the host's share of Bank::create's checks for wakewords first .. first + items.size() - 1; changes nothing
+    bool put_check(size_t first, const std::vector<PutItem> &items) const;
+    // d_src: DEVICE rows [..][K] the items' src point into.  Prepares the rows in the pool tail (bank_put_kernel), reads the kernel's
+    // verdict, and only then commits ww[] / rms_level; returns after the stream has drained.  A refusal leaves the bank as it was.
+    bool put_rows(size_t first, const std::vector<PutItem> &items, const float *d_src);
+    bool reserve(int max_len, size_t n_wakewords, size_t rows);
+    bool grow_ww(size_t cap);                           // dev.ww / rms_level with room for `cap` wakewords
+    bool repool(size_t entries_cap, size_t rows_cap);   // new entry and row pools of these capacities, the live entries moved over
+    int max_window() const { return std::max(std::max(ceiling, dev.max_len), 1); }   // what a stream batch over the bank keeps room for
 };
 
 struct Model {

@@ -399,6 +399,32 @@ struct BankStreamScore {
 };
 hipError_t launch_dtw_bank_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q);
 
+// ---- a bank that changes (rp_bank_put.hip).  One put prepares n_rows template rows of n_entries new entries, as put_rows of Bank::create does
+// on the host: row r of the call belongs to the entry e with erow[e] <= r < erow[e + 1] (erow [n_entries + 1], the last = n_rows), is read
+// from src + (esrc[e] + r - erow[e]) * K and written to unit / raw + r * K (the caller passes the pool tail).  flags [wakewords of the call],
+// zero before: the kernel ORs in what the host decides on before it commits anything.  All device pointers.
+constexpr uint32_t kBankPutNotFinite = 1u, kBankPutRefOnly = 2u;
+struct BankPut {
+    const float *src = nullptr;
+    const long long *erow = nullptr, *esrc = nullptr;
+    const int32_t *eww = nullptr;     // [n_entries] the wakeword of the call an entry belongs to
+    size_t n_entries = 0, n_rows = 0;
+    int K = 0;
+    float *unit = nullptr, *raw = nullptr;
+    uint32_t *flags = nullptr;
+};
+hipError_t launch_bank_put(hipStream_t st, const BankPut &p);
+// Growth and compaction of the row pools: live entry e has len[e] rows at row src_row[e] of the old pools and gets row dst_row[e] of the new.
+struct BankMove {
+    const float *unit_old = nullptr, *raw_old = nullptr;
+    float *unit_new = nullptr, *raw_new = nullptr;
+    const long long *src_row = nullptr, *dst_row = nullptr;
+    const int32_t *len = nullptr;
+    size_t n_entries = 0;
+    int K = 0;
+};
+hipError_t launch_bank_move(hipStream_t st, const BankMove &m);
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a process that drives several GPUs
 // (one rp_ctx per device) has to set it on each of them.  Sets it once per (current device, kernel), thread-safe.
 hipError_t allow_dynamic_lds(const void *kernel, int bytes);

@@ -22,7 +22,10 @@ struct rp_stream_batch {
     bool single = false;
     // made by rp_stream_batch_new_bank: stream s holds the one wakeword bank[bank_idx[s]] (`ww` is empty); max_len is then the bank's longest
     // window, the history every stream keeps, and bank_agg / bank_avg [S][frames per call] are the streams' own windows' scores
+    // The bank may change under the batch (rp_wakeword_bank_put / _enrol): every call reads bank->dev and bank->rms_level afresh, and the bank
+    // counts its batches so that no window longer than max_len gets in (Bank::put_check)
     const Bank *bank = nullptr;
+    ~rp_stream_batch() { if (bank) --bank->live_batches; }
     DevBuf bank_idx, bank_agg, bank_avg;
     int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
     DevBuf det_ww, det_label, logits, mean, xrows, xs2;
@@ -433,12 +436,12 @@ int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const in
         if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
         if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new_bank: S and max_chunks_per_call must be >= 1"); return -1; }
-        if (!bank_band_ok(bk.dev, (int)config->band_size) || !bank_indices_ok(c, bk, 0, S, stream_wakeword)) return -1;   // before anything is allocated
+        if (!bank_band_ok(bk, (int)config->band_size) || !bank_indices_ok(c, bk, 0, S, stream_wakeword)) return -1;   // before anything is allocated
         std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
-        b->c = c; b->bank = &bk; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
+        b->c = c; b->bank = &bk; ++bk.live_batches; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
         // (an empty bank: no history; its mfcc_size is a placeholder -- the encode and frames stages run all the same, at the default size,
-        // and nobody reads their frames)
-        b->K = bk.dev.W ? bk.dev.K : 5; b->max_len = std::max(bk.dev.max_len, 1); b->Tmax = 1;
+        // and nobody reads their frames.  A reserved bank declares its mfcc_size and the longest window it will ever hold, empty or not)
+        b->K = (bk.dev.W || bk.ceiling) ? bk.dev.K : 5; b->max_len = bk.max_window(); b->Tmax = 1;
         if (!bank_indices_put(b.get(), 0, S, stream_wakeword)) return -1;
         if (!c->tables_for(b->K)) return -1;
         b->hist_frames = (size_t)b->max_len - 1;   // every stream keeps the history of the bank's longest window; its own starts max_len(s) - 1 frames back
