@@ -1463,6 +1463,21 @@ class BatchContext:
         if self._L.rp_mfcc_batch(self._h, pcm_ptr, S, N, stride, K, out_ptr) < 0:
             raise _err()
 
+    def mfcc_dev_fmt(self, pcm_ptr, fmt, S, N, stride, K, out_ptr):
+        """rp_mfcc_batch_fmt with device pointers: rows of fmt samples (SampleFormat), `stride` samples apart"""
+        if self._L.rp_mfcc_batch_fmt(self._h, pcm_ptr, int(fmt), S, N, stride, K, out_ptr) < 0:
+            raise _err()
+
+    def frontend_dev(self, pcm_ptr, fmt, S, n_samples, pcm_stride, filters_config, rms_level_ref, window_size, out_ptr, out_stride,
+                     rms_ptr=None, gains_ptr=None):
+        """rp_frontend_batch with device pointers"""
+        rc = RustpotterConfig()
+        rc.filters = filters_config
+        f = rc._filters_c()
+        if self._L.rp_frontend_batch(self._h, pcm_ptr, int(fmt), S, n_samples, pcm_stride, C.byref(f), rms_level_ref, window_size, out_ptr,
+                                     out_stride, rms_ptr, gains_ptr) < 0:
+            raise _err()
+
     def dtw_dev(self, mfcc_ptr, S, n_frames, templates, score_ref, band_size, score_mode, with_avg, scores_ptr, avg_ptr, agg_ptr):
         if self._L.rp_dtw_score_batch(self._h, mfcc_ptr, S, n_frames, templates._h, score_ref, band_size, int(score_mode),
                                       int(with_avg), scores_ptr, avg_ptr, agg_ptr) < 0:
