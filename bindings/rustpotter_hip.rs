@@ -77,6 +77,10 @@ pub const RP_DTW_MFMA_WAVES_8: c_int = 1024;
 pub const RP_DTW_MFMA_WAVES_12: c_int = 2048;
 pub const RP_DTW_KERNEL_BANK: c_int = 4096;
 pub const RP_DTW_KERNEL_BANK_STREAM: c_int = 8192;
+pub const RP_DTW_KERNEL_BANK_SETS: c_int = 16384;
+pub const RP_DTW_KERNEL_BANK_SETS_STREAM: c_int = 32768;
+/// wakewords a stream's set may hold (`stream_wakewords [S][set_size]`)
+pub const RP_WAKEWORD_SET_MAX: c_int = 8;
 pub const RP_WAKEWORD_BANK_MAX_TEMPLATES: c_int = 32;
 pub const RP_MLP_F32: c_int = 0;
 pub const RP_MLP_BF16: c_int = 1;
@@ -220,6 +224,13 @@ extern "C" {
                                 bank: *const rp_wakeword_bank, stream_wakeword: *const i32, config: *const rp_detector_config,
                                 det: *mut rp_batch_detection, n_det: *mut i32, max_det: c_int, agg: *mut f32, avg: *mut f32,
                                 win_pitch: usize) -> c_int;
+    pub fn rp_dtw_score_bank_sets(ctx: *mut rp_ctx, mfcc: *const f32, S: usize, n_frames: usize, bank: *const rp_wakeword_bank,
+                                  stream_wakewords: *const i32, set_size: c_int, score_ref: f32, band_size: c_int, score_mode: c_int,
+                                  with_avg: c_int, avg: *mut f32, agg: *mut f32, win_pitch: usize) -> c_int;
+    pub fn rp_batch_detect_bank_sets(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                     bank: *const rp_wakeword_bank, stream_wakewords: *const i32, set_size: c_int,
+                                     config: *const rp_detector_config, det: *mut rp_batch_detection, det_wakeword: *mut i32, n_det: *mut i32,
+                                     max_det: c_int, agg: *mut f32, avg: *mut f32, win_pitch: usize) -> c_int;
     pub fn rp_resampler_frame_lengths(sample_rate: usize, in_len: *mut usize, out_len: *mut usize) -> c_int;
     pub fn rp_resample_batch(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, channels: c_int, sample_rate: usize, S: usize,
                              n_samples: usize, pcm_stride: usize, out: *mut f32, out_stride: usize) -> c_int;
@@ -243,6 +254,10 @@ extern "C" {
                                     S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
     pub fn rp_stream_batch_set_wakewords(b: *mut rp_stream_batch, first_stream: usize, n: usize, wakewords: *const i32) -> c_int;
     pub fn rp_stream_batch_set_filters_bank(b: *mut rp_stream_batch, filters: *const rp_filters_config) -> c_int;
+    pub fn rp_stream_batch_new_bank_sets(ctx: *mut rp_ctx, bank: *const rp_wakeword_bank, stream_wakewords: *const i32, set_size: c_int,
+                                         config: *const rp_detector_config, S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
+    pub fn rp_stream_batch_set_wakeword_sets(b: *mut rp_stream_batch, first_stream: usize, n: usize, stream_wakewords: *const i32) -> c_int;
+    pub fn rp_stream_batch_slot_scores(b: *mut rp_stream_batch, agg: *mut f32, avg: *mut f32) -> c_int;
     pub fn rp_model_new(ctx: *mut rp_ctx, n_layers: c_int, dims: *const c_int, weights: *const *const f32, biases: *const *const f32,
                         out: *mut *mut rp_model) -> c_int;
     pub fn rp_model_free(m: *mut rp_model);
@@ -716,6 +731,38 @@ impl HipContext {
         })?;
         Ok(split_detections(det, n_det, max_det))
     }
+    /// `dtw_score_bank` where stream `s` carries the SET `stream_wakewords[s * set_size ..][..set_size]` (-1: an empty slot): (avg, agg), each
+    /// `[streams][set_size][win_pitch]` -- a slot's windows of `Lmax(s)` frames, zeros behind them.
+    pub fn dtw_score_bank_sets(&self, mfcc: &[f32], n_streams: usize, n_frames: usize, bank: &WakewordBank, stream_wakewords: &[i32], set_size: usize,
+                               score_ref: f32, band_size: u16, score_mode: ScoreMode, with_avg: bool, win_pitch: usize)
+                               -> Result<(Vec<f32>, Vec<f32>), String> {
+        assert!(stream_wakewords.len() == n_streams * set_size);
+        let mut avg = vec![0f32; if with_avg { n_streams * set_size * win_pitch } else { 0 }];
+        let mut agg = vec![0f32; n_streams * set_size * win_pitch];
+        status(unsafe {
+            rp_dtw_score_bank_sets(self.h, mfcc.as_ptr(), n_streams, n_frames, bank.h, stream_wakewords.as_ptr(), set_size as c_int, score_ref,
+                                   band_size as c_int, score_mode_to_c(score_mode), with_avg as c_int,
+                                   if with_avg { avg.as_mut_ptr() } else { std::ptr::null_mut() }, agg.as_mut_ptr(), win_pitch)
+        })?;
+        Ok((avg, agg))
+    }
+    /// `batch_detect_bank` where every stream holds a set of wakewords (`add_wakeword` x n per user, src/detector.rs:304-346,433-447):
+    /// detect-only; returns the detections and, per detection, the bank index of the wakeword that won.
+    pub fn batch_detect_bank_sets(&self, pcm: &[f32], n_streams: usize, n_samples: usize, bank: &WakewordBank, stream_wakewords: &[i32],
+                                  set_size: usize, config: &DetectorConfig, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>), String> {
+        assert!(pcm.len() >= n_streams * n_samples && stream_wakewords.len() == n_streams * set_size);
+        let c: rp_detector_config = config.into();
+        let mut det = vec![rp_batch_detection::default(); n_streams * max_det];
+        let mut which = vec![0i32; n_streams * max_det];
+        let mut n_det = vec![0i32; n_streams];
+        status(unsafe {
+            rp_batch_detect_bank_sets(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, bank.h,
+                                      stream_wakewords.as_ptr(), set_size as c_int, &c, det.as_mut_ptr(), which.as_mut_ptr(), n_det.as_mut_ptr(),
+                                      max_det as c_int, std::ptr::null_mut(), std::ptr::null_mut(), 0)
+        })?;
+        let w = (0..n_streams).map(|s| which[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect();
+        Ok((split_detections(det, n_det, max_det), w))
+    }
     /// Upload a wakeword model: `weights[l]` = `[dims[l+1]][dims[l]]` row-major (candle `Linear`), `biases[l]` = `[dims[l+1]]`.
     pub fn model(&self, dims: &[c_int], weights: &[Vec<f32>], biases: &[Vec<f32>]) -> Result<Model, String> {
         assert!(dims.len() == weights.len() + 1 && weights.len() == biases.len());
@@ -818,7 +865,9 @@ impl HipContext {
 
 /// S live streams that each receive a few 30 ms chunks per call: the batched form of S `Rustpotter` handles
 /// (INTEGRATION.md §4).  Borrows the context and the templates, like the C handle does.
-pub struct StreamBatch<'a> { h: *mut rp_stream_batch, n_streams: usize, last_chunks: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
+pub struct StreamBatch<'a> { h: *mut rp_stream_batch, n_streams: usize, last_chunks: usize,
+                            /// wakewords per stream of a `new_bank_sets` batch, 0 for every other batch; MFCC frames a stream gains per chunk (3, or 4 with 40 ms input frames)
+                            set_size: usize, frames_per_chunk: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
 /// One wakeword of a detector that holds several (`Rustpotter::add_wakeword_ref` / `add_wakeword_model`, src/detector.rs:144-150)
 pub enum BatchWakeword<'a> {
     /// a reference with its own `threshold` / `avg_threshold` options (`WakewordRef::threshold`, `::avg_threshold`)
@@ -832,7 +881,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new(ctx.h, t.h, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// S detectors that each hold `wakewords` (references and / or models sharing `mfcc_size`): the best score of the wakewords
     /// whose own thresholds pass wins a frame (`run_wakeword_detectors`, src/detector.rs:433-447)
@@ -849,7 +898,7 @@ impl<'a> StreamBatch<'a> {
         }).collect();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_multi(ctx.h, specs.len(), specs.as_ptr(), mfcc_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Personal wakewords on live streams: stream `s` holds the one wakeword `bank[stream_wakeword[s]]` (-1: none) with its own window
     /// length and thresholds -- `batch_detect_bank` with the state carried between calls.  `process_multi` reports the bank index.
@@ -858,7 +907,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_bank(ctx.h, bank.h, stream_wakeword.as_ptr(), &c, stream_wakeword.len(), max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams: stream_wakeword.len(), last_chunks: 0, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams: stream_wakeword.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Connect / disconnect of device slots (a batch of `new_bank`): streams `first_stream ..` get new bank indices and are reset
     pub fn set_wakewords(&mut self, first_stream: usize, wakewords: &[i32]) -> Result<(), String> {
@@ -869,6 +918,33 @@ impl<'a> StreamBatch<'a> {
     pub fn set_filters_bank(&mut self, filters: &FiltersConfig) -> Result<(), String> {
         let f: rp_filters_config = filters.into();
         status(unsafe { rp_stream_batch_set_filters_bank(self.h, &f) })
+    }
+    /// Wakeword sets on live streams: stream `s` holds `stream_wakewords[s * set_size ..][..set_size]` (-1: an empty slot) --
+    /// `batch_detect_bank_sets` with the state carried between calls.  `process_multi` reports the winner's bank index.
+    pub fn new_bank_sets(ctx: &'a HipContext, bank: &'a WakewordBank, stream_wakewords: &[i32], set_size: usize, config: &DetectorConfig,
+                         max_chunks_per_call: usize) -> Result<StreamBatch<'a>, String> {
+        assert!(set_size >= 1 && set_size <= RP_WAKEWORD_SET_MAX as usize && stream_wakewords.len() % set_size == 0);
+        let c: rp_detector_config = config.into();
+        let n_streams = stream_wakewords.len() / set_size;
+        let mut h = std::ptr::null_mut();
+        status(unsafe { rp_stream_batch_new_bank_sets(ctx.h, bank.h, stream_wakewords.as_ptr(), set_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
+    }
+    /// Re-target the streams `first_stream ..` of a `new_bank_sets` batch, one row of the batch's `set_size` indices per stream: remove-all
+    /// plus add-in-order, each stream reset.  An error on any other batch.
+    pub fn set_wakeword_sets(&mut self, first_stream: usize, stream_wakewords: &[i32]) -> Result<(), String> {
+        if self.set_size == 0 { return Err("set_wakeword_sets: the batch was not made by new_bank_sets".to_string()); }
+        assert!(stream_wakewords.len() % self.set_size == 0, "rows of set_size indices");
+        status(unsafe { rp_stream_batch_set_wakeword_sets(self.h, first_stream, stream_wakewords.len() / self.set_size, stream_wakewords.as_ptr()) })
+    }
+    /// The slot scores of the last `process` / `process_multi` call of a `new_bank_sets` batch: (agg, avg), each
+    /// `[streams][set_size][frames of that call]`.  An error on any other batch and before the first call.
+    pub fn slot_scores(&mut self) -> Result<(Vec<f32>, Vec<f32>), String> {
+        if self.set_size == 0 { return Err("slot_scores: the batch was not made by new_bank_sets".to_string()); }
+        let n = self.n_streams * self.set_size * self.last_chunks.max(1) * self.frames_per_chunk;
+        let (mut agg, mut avg) = (vec![0f32; n], vec![0f32; n]);
+        status(unsafe { rp_stream_batch_slot_scores(self.h, agg.as_mut_ptr(), avg.as_mut_ptr()) })?;
+        Ok((agg, avg))
     }
     /// `process` that also tells which wakeword fired and, for a model, which label: (detections, wakeword indices, label indices or -1)
     pub fn process_multi(&mut self, pcm: &[f32], n_chunks: usize, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>, Vec<Vec<i32>>), String> {
@@ -887,7 +963,11 @@ impl<'a> StreamBatch<'a> {
         Ok((split_detections(det, n_det, max_det), w, l))
     }
     /// `RustpotterConfig.fmt` of the streams (sample rate, channels); before the first `process`
-    pub fn set_input(&mut self, sample_rate: usize, channels: u16) -> Result<(), String> { status(unsafe { rp_stream_batch_set_input(self.h, sample_rate, channels as c_int) }) }
+    pub fn set_input(&mut self, sample_rate: usize, channels: u16) -> Result<(), String> {
+        status(unsafe { rp_stream_batch_set_input(self.h, sample_rate, channels as c_int) })?;
+        self.frames_per_chunk = resampler_frame_lengths(sample_rate)?.1 / 160;   // 480 encoded samples a chunk: 3 frames; 640 (11.025 / 22.05 kHz): 4
+        Ok(())
+    }
     /// `RustpotterConfig.filters` of the streams (gain normaliser + band-pass, src/detector.rs:358-371), state kept per stream on the
     /// device; before the first `process`.  `rms_level_ref`: the largest `rms_level` of the wakewords (NaN: none)
     pub fn set_filters(&mut self, filters: &FiltersConfig, rms_level_ref: f32) -> Result<(), String> {

@@ -234,7 +234,9 @@ enum {
     RP_DTW_MFMA_WAVES_8 = 1024,    /* two waves per SIMD */
     RP_DTW_MFMA_WAVES_12 = 2048,   /* three waves per SIMD */
     RP_DTW_KERNEL_BANK = 4096,     /* dtw_bank_kernel: every stream against its own wakeword of a bank (rp_dtw_score_bank, rp_batch_detect_bank) */
-    RP_DTW_KERNEL_BANK_STREAM = 8192 /* dtw_bank_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank) */
+    RP_DTW_KERNEL_BANK_STREAM = 8192, /* dtw_bank_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank) */
+    RP_DTW_KERNEL_BANK_SETS = 16384,  /* dtw_set_kernel: every stream against its own SET of wakewords of a bank (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets) */
+    RP_DTW_KERNEL_BANK_SETS_STREAM = 32768 /* dtw_set_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank_sets) */
 };
 int rp_ctx_dtw_kernels(rp_ctx *ctx);
 /* Which build this library is (replaces nothing): the target architecture and the compiler flags it differs by from the
@@ -567,6 +569,40 @@ int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, siz
                          const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config,
                          rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, float *avg, size_t win_pitch);
 
+/* Wakeword SETS: several personal wakewords per stream over a bank.  stream_wakewords [S][set_size] (set_size 1..RP_WAKEWORD_SET_MAX) holds
+ * up to set_size bank indices per stream; -1 marks an empty slot, anywhere in the row, and a row of all -1 is a detector without wakewords.
+ * Stream s behaves as Rustpotter::new(config) followed by add_wakeword(bank[i]) for its live slots in slot order, then process_samples
+ * (add_wakeword, on_wakeword_change, run_wakeword_detectors: src/detector.rs:304-346,433-447): max_mfcc_frames = Lmax(s), the longest
+ * window over the stream's live slots; every wakeword scores the OLDEST len frames of that window (wakeword_comp.rs:22-27) with its own
+ * thresholds over the config's, the averaged-template test only where it has an averaged template and its effective avg_threshold != 0
+ * (wakeword_comp.rs:85); the best passing score wins, of equal scores the first slot; the countdown is Lmax(s) / 2; a detection reports
+ * window = frame - Lmax(s) + 1 and the BANK index of the winner.  Duplicate indices in a row are allowed and change nothing.  Arithmetic
+ * and limits are those of the bank calls above: f32 vector FMAs whatever rp_ctx_set_arithmetic says, mfcc_size 5 / 13 / 16 with band_size
+ * 3..6, or band_size 0 (every score 0, no detection); empty banks and all -1 rows succeed and report nothing.  With RP_CTX_HOST_POINTERS an
+ * index outside [-1, n_wakewords) is an error that names stream and slot, found before anything is allocated or launched; with device arrays
+ * the kernels treat such an index as -1 (and win_pitch must then hold the window count of the bank's shortest wakeword).
+ * rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK_SETS. */
+enum { RP_WAKEWORD_SET_MAX = 8 };
+/* rp_dtw_score_bank over sets: agg and avg (avg may be NULL; scored with with_avg where a wakeword has an averaged template) are
+ * [S][set_size][win_pitch].  Row (s, j) holds n_win_s = n_frames - Lmax(s) + 1 values, the scores of wakeword set[s][j] for the windows
+ * that start at frames 0 .. n_win_s - 1 -- the first n_win_s values of rp_dtw_score_bank's row for that wakeword, bit for bit -- and zeros
+ * behind them; an empty slot has an all-zero row.  A stream shorter than Lmax(s) has all-zero rows in every slot although a shorter
+ * wakeword of its set would fit: the reference's window never fills (src/detector.rs:377-392).  win_pitch below the largest n_win_s of
+ * the call is refused. */
+int rp_dtw_score_bank_sets(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames, const rp_wakeword_bank *bank,
+                           const int32_t *stream_wakewords, int set_size, float score_ref, int band_size, rp_score_mode score_mode, int with_avg,
+                           float *avg, float *agg, size_t win_pitch);
+/* rp_batch_detect_bank over sets (run_wakeword_detectors, src/detector.rs:433-447, per stream): det_wakeword [S][max_det] (NULL to skip)
+ * is the bank index of the wakeword each detection belongs to.  agg / avg (either may be NULL) are the per-slot rows
+ * [S][set_size][win_pitch] laid out as in rp_dtw_score_bank_sets, avg scored where a wakeword's test runs.  Detection itself never
+ * materialises them: the kernel folds every window's proposal (best passing score, its avg score, its bank index) into three rows
+ * [S][n_win].  Detect-only calls (agg == avg == NULL, no RP_CTX_FULL_SCORES) may leave windows below their avg_threshold uncompared, as
+ * rp_batch_detect_bank; the detections are the same either way.  VAD and the reset after a detection as everywhere. */
+int rp_batch_detect_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                              const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size, const rp_detector_config *config,
+                              rp_batch_detection *det, int32_t *det_wakeword, int32_t *n_det, int max_det, float *agg, float *avg,
+                              size_t win_pitch);
+
 /* Sample-rate conversion in front of the path: AudioEncoder::new / reencode_to_mono_with_sample_rate
  * (src/audio/encoder.rs:41-60,63-83), i.e. rubato's FftFixedInOut<f32>::new(sample_rate, 16000, 480, 1) and one
  * process_into_buffer per input frame.  rp_resampler_frame_lengths gives AudioEncoder's
@@ -703,6 +739,29 @@ int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_
  * keeps its length.  A stream with index -1 does not advance its window and has gain 1; connected again, its window goes on from what
  * it held.  rp_stream_batch_reset leaves the filters alone, as everywhere. */
 int rp_stream_batch_set_filters_bank(rp_stream_batch *b, const rp_filters_config *filters);
+
+/* Wakeword sets on LIVE streams: rp_stream_batch_new_bank with stream_wakewords [S][set_size] (see rp_batch_detect_bank_sets for what a
+ * set means: add_wakeword x n per user, src/detector.rs:304-346,433-447).  Fed the same audio piece by piece a stream reports the
+ * detections of rp_batch_detect_bank_sets over the concatenation.  History, reserve rules and the bank's count of batches are those of
+ * rp_stream_batch_new_bank; the bank may change under the batch in the same way: Lmax(s) and every threshold are read from the bank in
+ * every call.  rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK_SETS_STREAM.
+ * On such a batch rp_stream_batch_process works without agg (with agg it is refused: a batch of several wakewords has no single aggregate
+ * per window; see rp_stream_batch_slot_scores), rp_stream_batch_process_multi reports det_wakeword = the winner's bank index and det_label
+ * -1; rp_stream_batch_set_input, _reset and rp_stream_batch_set_filters with the band-pass alone work as on a bank batch;
+ * rp_stream_batch_set_wakewords and rp_stream_batch_set_filters_bank fail (the gain normaliser on sets is not built). */
+int rp_stream_batch_new_bank_sets(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size,
+                                  const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out);
+/* rp_stream_batch_set_wakewords for a sets batch (an error on any other), at any time between process calls: streams first_stream ..
+ * first_stream + n - 1 get the rows stream_wakewords [n][set_size] and each is reset exactly as rp_stream_batch_set_wakewords resets.  A
+ * refused row changes nothing.  This is remove-all plus add-in-order (remove_wakeword for every wakeword, then add_wakeword slot by slot:
+ * the first add on the emptied detector resets it, src/detector.rs:304-307).  The reference's add_wakeword on a NON-empty detector, which
+ * does not reset, is not offered. */
+int rp_stream_batch_set_wakeword_sets(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *stream_wakewords);
+/* The slot scores of the last process call of a sets batch, modelled on rp_stream_batch_levels: agg and avg [S][set_size][frames of that
+ * call] (either may be NULL), the score of wakeword set[s][j] for the window of Lmax(s) frames that ends at each new frame, zero rows for
+ * empty slots.  The windows are fully scored only under RP_CTX_FULL_SCORES; otherwise a window below its avg_threshold holds aggregate 0.
+ * Returns -1 before the first process call and on a batch that is not a sets batch. */
+int rp_stream_batch_slot_scores(rp_stream_batch *b, float *agg, float *avg);
 
 /* A wakeword model (src/wakewords/wakeword_model.rs:11-18) resident on the device.  weights are
  * HOST arrays W_l [dims[l+1]][dims[l]] (candle Linear: x.W^T + b), biases b_l [dims[l+1]]; 1..3 layers. */

@@ -118,6 +118,8 @@ SYMBOLS = [
     "rp_wakeword_bank_set_rms_levels", "rp_wakeword_bank_rms_level", "rp_frontend_batch_bank", "rp_stream_batch_set_filters_bank",
     "rp_wakeword_bank_reserve", "rp_wakeword_bank_size", "rp_wakeword_bank_reserved_len", "rp_wakeword_bank_pool_growths",
     "rp_wakeword_bank_put", "rp_wakeword_bank_put_from_rpw", "rp_wakeword_bank_enrol",
+    "rp_dtw_score_bank_sets", "rp_batch_detect_bank_sets", "rp_stream_batch_new_bank_sets", "rp_stream_batch_set_wakeword_sets",
+    "rp_stream_batch_slot_scores",
 ]
 
 
@@ -266,6 +268,12 @@ def load_library():
                                        vp, vp, C.c_size_t]
     L.rp_stream_batch_new_bank.argtypes = [vp, vp, vp, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.rp_stream_batch_set_wakewords.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
+    L.rp_dtw_score_bank_sets.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t]
+    L.rp_batch_detect_bank_sets.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_int, C.POINTER(_DetectorConfig), vp, vp, vp,
+                                            C.c_int, vp, vp, C.c_size_t]
+    L.rp_stream_batch_new_bank_sets.argtypes = [vp, vp, vp, C.c_int, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.rp_stream_batch_set_wakeword_sets.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
+    L.rp_stream_batch_slot_scores.argtypes = [vp, vp, vp]
     _LIB = L
     return L
 
@@ -688,7 +696,8 @@ class StreamBatch:
     Rustpotter::process_samples on S instances sharing one wakeword and config -- or, over a WakewordBank, each holding its own."""
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
-                 mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None, bank_filters=None):
+                 mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None, bank_filters=None,
+                 stream_wakewords=None, set_size=None):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
         with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
@@ -697,12 +706,21 @@ class StreamBatch:
         bank + stream_wakeword (rp_stream_batch_new_bank; templates is then None): stream s holds the one wakeword
         bank[stream_wakeword[s]], -1 = none; stream_wakeword is [S] int32 (with device pointers: the address of a device array).
         bank_filters (rp_stream_batch_set_filters_bank, with bank): a FiltersConfig whose gain normaliser works per stream, towards
-        the rms_level of the stream's own wakeword over its own window."""
+        the rms_level of the stream's own wakeword over its own window.
+        bank + stream_wakewords (rp_stream_batch_new_bank_sets): stream s holds the SET of wakewords stream_wakewords[s], [S][set_size]
+        int32 with -1 = an empty slot (with device pointers: the address of a device array and set_size)."""
         self._L = load_library()
+        self.set_size = 0
         self.ctx, self.templates, self.S, self.max_chunks = ctx, templates, S, max_chunks_per_call
         h = C.c_void_p()
         c = detector_config._c()
-        if bank is not None:
+        if bank is not None and stream_wakewords is not None:
+            self._keep = bank   # the batch borrows the bank
+            idx, ptr = self._indices(stream_wakewords)
+            self.set_size = int(idx.shape[1] if set_size is None else set_size)
+            if self._L.rp_stream_batch_new_bank_sets(ctx._h, bank._h, ptr, self.set_size, C.byref(c), S, max_chunks_per_call, C.byref(h)) < 0:
+                raise _err()
+        elif bank is not None:
             self._keep = bank   # the batch borrows the bank
             idx, ptr = self._indices(stream_wakeword)
             if self._L.rp_stream_batch_new_bank(ctx._h, bank._h, ptr, C.byref(c), S, max_chunks_per_call, C.byref(h)) < 0:
@@ -756,6 +774,28 @@ class StreamBatch:
         process calls.  With device pointers stream_wakeword is the address of a device int32 array of n indices."""
         idx, ptr = self._indices(stream_wakeword)
         if self._L.rp_stream_batch_set_wakewords(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
+            raise _err()
+
+    def set_wakeword_sets(self, first_stream, stream_wakewords, n=None):
+        """rp_stream_batch_set_wakeword_sets: streams first_stream .. get the rows stream_wakewords [n][set_size] (-1: an empty slot) and are
+        reset -- remove-all plus add-in-order; between process calls.  With device pointers: the address of a device int32 array of n rows."""
+        idx, ptr = self._indices(stream_wakewords)
+        if self._L.rp_stream_batch_set_wakeword_sets(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
+            raise _err()
+
+    def slot_scores(self):
+        """rp_stream_batch_slot_scores -> (agg, avg), each [S][set_size][frames of the last process call]"""
+        import numpy as np
+        assert self.ctx.host
+        n = max(self._last_chunks, 1) * self.frames_per_chunk
+        agg = np.empty((self.S, max(self.set_size, 1), n), np.float32)
+        avg = np.empty_like(agg)
+        if self._L.rp_stream_batch_slot_scores(self._h, agg.ctypes.data, avg.ctypes.data) < 0:
+            raise _err()
+        return agg, avg
+
+    def slot_scores_dev(self, agg_ptr, avg_ptr):
+        if self._L.rp_stream_batch_slot_scores(self._h, agg_ptr, avg_ptr) < 0:
             raise _err()
 
     @property
@@ -1001,7 +1041,7 @@ class BatchContext:
 
     DTW_KERNELS = {1: "dtw_mfma_kernel", 2: "dtw_mfma_wide_kernel", 4: "dtw_ragged_kernel", 8: "register kernels", 16: "dtw_generic_kernel",
                    32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel", 4096: "dtw_bank_kernel",
-                   8192: "dtw_bank_stream_kernel"}
+                   8192: "dtw_bank_stream_kernel", 16384: "dtw_set_kernel", 32768: "dtw_set_stream_kernel"}
     DTW_PRODUCTS = {256: "bf16x3", 512: "f16x2"}
     DTW_MFMA_WAVES = {1024: 8, 2048: 12}
 
@@ -1307,6 +1347,82 @@ class BatchContext:
         """rp_dtw_score_bank on device pointers: avg_ptr (may be None) and agg_ptr are [S][win_pitch] floats"""
         if self._L.rp_dtw_score_bank(self._h, mfcc_ptr, S, n_frames, bank._h, idx_ptr, score_ref, band_size, int(score_mode),
                                      int(with_avg), avg_ptr, agg_ptr, win_pitch) < 0:
+            raise _err()
+
+    @staticmethod
+    def _set_pitch(bank, sets, nf):
+        """the largest window count of a call over sets: a stream's window is as long as its longest live slot"""
+        lmax = [max([0] + [bank.max_lens[w] for w in row if 0 <= w < bank.W]) for row in sets]
+        return max([0] + [max(0, nf - l + 1) for l in lmax if l > 0])
+
+    def dtw_scores_bank_sets(self, mfcc, bank, stream_wakewords, score_ref=0.22, band_size=5, score_mode=ScoreMode.Max, with_avg=False, win_pitch=None):
+        """rp_dtw_score_bank_sets: stream s against the set of bank wakewords stream_wakewords[s] ([S][set_size], -1: an empty slot) ->
+        (avg or None, agg), each [S][set_size][win_pitch] (default: the largest window count of the call): a slot's windows, zeros behind."""
+        import numpy as np
+        assert self.host
+        mfcc = np.ascontiguousarray(mfcc, np.float32)
+        if mfcc.ndim == 2:
+            mfcc = mfcc[None]
+        S, nf, _ = mfcc.shape
+        idx = np.ascontiguousarray(stream_wakewords, np.int32)
+        assert idx.ndim == 2 and idx.shape[0] == S
+        n = idx.shape[1]
+        if win_pitch is None:
+            win_pitch = self._set_pitch(bank, idx, nf)
+        agg = np.empty((S, n, win_pitch), np.float32)
+        avg = np.empty((S, n, win_pitch), np.float32) if with_avg else None
+        r = self._L.rp_dtw_score_bank_sets(self._h, mfcc.ctypes.data, S, nf, bank._h, idx.ctypes.data, n, score_ref, band_size, int(score_mode),
+                                           1 if with_avg else 0, None if avg is None else avg.ctypes.data, agg.ctypes.data, win_pitch)
+        if r < 0:
+            raise _err()
+        return avg, agg
+
+    def batch_detect_bank_sets(self, pcm, bank, stream_wakewords, detector_config, max_det=8, want_agg=False, win_pitch=None):
+        """rp_batch_detect_bank_sets: the whole path with stream s carrying the set stream_wakewords[s] -> (det, det_wakeword, n_det), with
+        want_agg also (agg, avg), each [S][set_size][win_pitch] (see dtw_scores_bank_sets).  det_wakeword: the winner's bank index."""
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        nf = mfcc_num_frames(N)
+        idx = np.ascontiguousarray(stream_wakewords, np.int32)
+        assert idx.ndim == 2 and idx.shape[0] == S
+        n = idx.shape[1]
+        det = np.zeros((S, max_det), dtype=DET_DTYPE)
+        dww = np.zeros((S, max_det), np.int32)
+        n_det = np.zeros(S, np.int32)
+        agg = avg = None
+        if want_agg:
+            if win_pitch is None:
+                win_pitch = self._set_pitch(bank, idx, nf)
+            agg = np.empty((S, n, win_pitch), np.float32)
+            avg = np.empty((S, n, win_pitch), np.float32)
+        c = detector_config._c()
+        r = self._L.rp_batch_detect_bank_sets(self._h, pcm.ctypes.data, fmt, S, N, N, bank._h, idx.ctypes.data, n, C.byref(c), det.ctypes.data,
+                                              dww.ctypes.data, n_det.ctypes.data, max_det, None if agg is None else agg.ctypes.data,
+                                              None if avg is None else avg.ctypes.data, win_pitch or 0)
+        if r < 0:
+            raise _err()
+        return (det, dww, n_det, agg, avg) if want_agg else (det, dww, n_det)
+
+    def batch_detect_bank_sets_dev(self, pcm_ptr, fmt, S, N, stride, bank, idx_ptr, set_size, detector_config, det_ptr, det_ww_ptr, n_det_ptr, max_det,
+                                   agg_ptr=None, avg_ptr=None, win_pitch=0):
+        """device pointers; detect-only unless agg_ptr / avg_ptr ([S][set_size][win_pitch] floats) are given (tools/bench_bank_sets.py)"""
+        c = detector_config._c()
+        if self._L.rp_batch_detect_bank_sets(self._h, pcm_ptr, fmt, S, N, stride, bank._h, idx_ptr, set_size, C.byref(c), det_ptr, det_ww_ptr,
+                                             n_det_ptr, max_det, agg_ptr, avg_ptr, win_pitch) < 0:
+            raise _err()
+
+    def dtw_scores_bank_sets_dev(self, mfcc_ptr, S, n_frames, bank, idx_ptr, set_size, score_ref, band_size, score_mode, with_avg, avg_ptr, agg_ptr,
+                                 win_pitch):
+        """rp_dtw_score_bank_sets on device pointers: avg_ptr (may be None) and agg_ptr are [S][set_size][win_pitch] floats"""
+        if self._L.rp_dtw_score_bank_sets(self._h, mfcc_ptr, S, n_frames, bank._h, idx_ptr, set_size, score_ref, band_size, int(score_mode),
+                                          int(with_avg), avg_ptr, agg_ptr, win_pitch) < 0:
             raise _err()
 
     def resample(self, pcm, sample_rate, channels=1):

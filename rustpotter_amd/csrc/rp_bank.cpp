@@ -1,5 +1,6 @@
 // rp_bank.cpp -- wakeword banks: W personal wakeword references resident on the device and the calls that score every stream against
-// ITS wakeword (rp_wakeword_bank_*, rp_dtw_score_bank, rp_batch_detect_bank; kernels: rp_dtw_bank.hip, scan_bank_kernel in rp_scan.hip).
+// ITS wakeword (rp_wakeword_bank_*, rp_dtw_score_bank, rp_batch_detect_bank; kernels: rp_dtw_bank.hip, scan_bank_kernel in rp_scan.hip) or
+// against its own SET of wakewords (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets; kernels: rp_dtw_set.hip, rp_scan_set.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -397,6 +398,56 @@ const int32_t *stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int3
     return static_cast<const int32_t *>(p);
 }
 
+// The same for sets, idx [S][set_size]: the window count of a stream is that of its longest live slot; errors name stream and slot.
+const int32_t *stage_set_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, size_t *max_n_win,
+                                 bool *ok) {
+    *ok = false;
+    const BankDev &d = bk.dev;
+    auto n_win_of = [&](int len) { return n_frames >= (size_t)len ? n_frames - (size_t)len + 1 : (size_t)0; };
+    *max_n_win = 0;
+    if (!sg.host) {
+        if (d.W > 0) *max_n_win = n_win_of(d.min_len);
+        *ok = true;
+        return idx;
+    }
+    if (!set_indices_ok(bk, 0, S, set_size, idx)) return nullptr;
+    for (size_t s = 0; s < S; ++s) {
+        int lmax = 0;
+        for (int j = 0; j < set_size; ++j) {
+            const int32_t wi = idx[s * (size_t)set_size + j];
+            if (wi >= 0) lmax = std::max(lmax, bk.ww[(size_t)wi].max_len);
+        }
+        if (lmax > 0) *max_n_win = std::max(*max_n_win, n_win_of(lmax));
+    }
+    if (S == 0) { *ok = true; return nullptr; }
+    const void *p = sg.in(idx, S * (size_t)set_size * sizeof(int32_t), c->ws_bank_idx);
+    if (!p) return nullptr;
+    *ok = true;
+    return static_cast<const int32_t *>(p);
+}
+
+bool set_indices_ok(const Bank &bk, size_t first, size_t n, int set_size, const int32_t *idx) {
+    const int W = bk.dev.W;
+    for (size_t i = 0; i < n; ++i)
+        for (int j = 0; j < set_size; ++j) {
+            const int32_t wi = idx[i * (size_t)set_size + j];
+            if (wi < -1 || wi >= W) {
+                set_last_error("stream " + std::to_string(first + i) + ", slot " + std::to_string(j) + ": wakeword index " + std::to_string(wi) +
+                               " is outside the bank (-1 .. " + std::to_string(W - 1) + ")");
+                return false;
+            }
+        }
+    return true;
+}
+
+bool set_size_ok(int set_size) {
+    if (set_size < 1 || set_size > RP_WAKEWORD_SET_MAX) {
+        set_last_error("set_size " + std::to_string(set_size) + " is outside 1 .. " + std::to_string((int)RP_WAKEWORD_SET_MAX) + " (RP_WAKEWORD_SET_MAX)");
+        return false;
+    }
+    return true;
+}
+
 }  // namespace rp
 
 namespace {
@@ -421,6 +472,20 @@ bool score_bank(Ctx *c, const Bank &bk, BankScore &q) {
     q.fix = wk.fix;
     dtw_mark(wk, kDtwRanBank);
     return timed(c, kKernelDtw, "dtw_bank_kernel", [&] { return launch_dtw_bank(c->stream, bk.dev, q); });
+}
+
+// the same for a call over sets (dtw_set_kernel); zero rows for band_size 0 and an empty bank, proposals "nobody" (-1)
+bool score_bank_sets(Ctx *c, const Bank &bk, BankSetScore &q) {
+    if (q.S == 0 || q.win_pitch == 0) return true;
+    if (q.band == 0 || bk.dev.W == 0) {
+        const size_t row = q.S * q.win_pitch * sizeof(float), slots = row * (size_t)q.set_size;
+        auto fill = [&](void *p, int v, size_t bytes) { return !p || hip_ok(hipMemsetAsync(p, v, bytes, c->stream), "hipMemsetAsync"); };
+        return fill(q.best, 0, row) && fill(q.best_avg, 0, row) && fill(q.best_ww, 0xff, row) && fill(q.slot_agg, 0, slots) && fill(q.slot_avg, 0, slots);
+    }
+    const DtwWork wk = c->dtw_work();
+    q.fix = wk.fix;
+    dtw_mark(wk, kDtwRanBankSets);
+    return timed(c, kKernelDtw, "dtw_set_kernel", [&] { return launch_dtw_set(c->stream, bk.dev, q); });
 }
 
 // W wakeword reference files in the flat layout of rp_wakeword_bank_new.  *K 0: the first file's mfcc_size is taken; every other file (all
@@ -500,6 +565,7 @@ int bank_from(rp_ctx *ctx, std::unique_ptr<Bank> b, rp_wakeword_bank **out) {
 
 extern "C" {
 
+static_assert(RP_DTW_KERNEL_BANK_SETS == (int)kDtwRanBankSets && RP_DTW_KERNEL_BANK_SETS_STREAM == (int)kDtwRanBankSetsStream && RP_WAKEWORD_SET_MAX == kScanMaxWakewords, "rustpotter_hip.h mirrors rp_kernels.h");
 static_assert(RP_DTW_KERNEL_BANK == (int)kDtwRanBank && RP_DTW_KERNEL_BANK_STREAM == (int)kDtwRanBankStream && RP_WAKEWORD_BANK_MAX_TEMPLATES == kBankMaxTemplates, "rustpotter_hip.h mirrors rp_kernels.h");
 
 int rp_wakeword_bank_new(rp_ctx *ctx, size_t n_wakewords, int mfcc_size, const int32_t *counts, const int32_t *lens, const float *feats,
@@ -688,6 +754,36 @@ int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames,
     });
 }
 
+int rp_dtw_score_bank_sets(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames, const rp_wakeword_bank *bank, const int32_t *stream_wakewords,
+                           int set_size, float score_ref, int band_size, rp_score_mode score_mode, int with_avg, float *avg, float *agg, size_t win_pitch) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (!set_size_ok(set_size)) return -1;
+        if (S && (!mfcc || !stream_wakewords || !agg)) { set_last_error("null argument"); return -1; }
+        Ctx *c = ctx->impl.get();
+        const Bank &bk = *bank->impl;
+        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (!bank_band_ok(bk, band_size)) return -1;
+        Staged sg(c);
+        size_t max_n_win = 0;
+        bool ok = false;
+        const int32_t *di = stage_set_indices(c, sg, bk, stream_wakewords, S, set_size, n_frames, &max_n_win, &ok);
+        if (!ok || !pitch_ok(win_pitch, max_n_win)) return -1;
+        if (S == 0 || win_pitch == 0) return sg.finish() ? 0 : -1;
+        const size_t out_bytes = S * (size_t)set_size * win_pitch * sizeof(float);
+        BankSetScore q;
+        q.mfcc = static_cast<const float *>(sg.in(mfcc, S * n_frames * bk.dev.K * sizeof(float), c->stage_in));
+        q.slot_agg = static_cast<float *>(sg.out(agg, out_bytes, c->stage_out3));
+        q.slot_avg = avg ? static_cast<float *>(sg.out(avg, out_bytes, c->stage_out2)) : nullptr;
+        if ((n_frames && !q.mfcc) || !q.slot_agg || (avg && !q.slot_avg)) return -1;
+        q.S = S; q.n_frames = n_frames; q.win_pitch = win_pitch; q.stream_wakewords = di; q.set_size = set_size; q.band = band_size;
+        q.score_mode = (int)score_mode; q.score_ref = score_ref; q.avg_mode = with_avg ? 1 : 0;
+        if (!score_bank_sets(c, bk, q)) return -1;
+        return sg.back(agg, q.slot_agg, out_bytes) && sg.back(avg, q.slot_avg, out_bytes) && sg.finish() ? 0 : -1;
+    });
+}
+
 // rp_frontend_batch with every stream's own gain window and reference level (gain_per_stream_kernel); the chunk RMS and apply kernels are
 // those of rp_frontend_batch -- they take per-chunk gains
 int rp_frontend_batch_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
@@ -766,6 +862,87 @@ int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, siz
         if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
         if (sg.host && agg && !sg.back(agg, dg, out_bytes)) return -1;
         if (sg.host && avg && !sg.back(avg, da, out_bytes)) return -1;
+        return sg.finish() ? 0 : -1;
+    });
+}
+
+int rp_batch_detect_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                              const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size, const rp_detector_config *config,
+                              rp_batch_detection *det, int32_t *det_wakeword, int32_t *n_det, int max_det, float *agg, float *avg, size_t win_pitch) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (!set_size_ok(set_size)) return -1;
+        if (!config || (S && (!pcm || !stream_wakewords || !det || !n_det))) { set_last_error("null argument"); return -1; }
+        Ctx *c = ctx->impl.get();
+        const Bank &bk = *bank->impl;
+        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (!bank_band_ok(bk, (int)config->band_size)) return -1;
+        Staged sg(c);
+        const size_t nf = rp_mfcc_num_frames(n_samples);
+        size_t max_n_win = 0;
+        bool ok = false;
+        const int32_t *di = stage_set_indices(c, sg, bk, stream_wakewords, S, set_size, nf, &max_n_win, &ok);
+        if (!ok) return -1;
+        const bool wants = agg || avg;
+        if (wants && !pitch_ok(win_pitch, max_n_win)) return -1;
+        const size_t pitch = wants ? win_pitch : std::max<size_t>(max_n_win, 1);   // the call's own rows when nothing is handed out
+        const size_t col = S * (size_t)(max_det > 0 ? max_det : 0) * sizeof(int32_t), slot_bytes = S * (size_t)set_size * pitch * sizeof(float);
+        if (bk.dev.W == 0) {   // a Rustpotter without wakewords: no stream reports anything, every row is zero (the bank's mfcc_size is a placeholder)
+            if (!sample_format_ok(fmt)) return -1;
+            if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
+            if (max_det < 0) { set_last_error("max_det must be >= 0"); return -1; }
+            auto zero = [&](void *p, size_t bytes) {
+                if (!p || !bytes) return true;
+                if (sg.host) { std::memset(p, 0, bytes); return true; }
+                return hip_ok(hipMemsetAsync(p, 0, bytes, c->stream), "hipMemsetAsync");
+            };
+            return zero(det, S * (size_t)max_det * sizeof(rp_batch_detection)) && zero(n_det, S * sizeof(int32_t)) && zero(det_wakeword, col) &&
+                   zero(agg, slot_bytes) && zero(avg, slot_bytes) && sg.finish() ? 0 : -1;
+        }
+        DetectFront f;
+        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, bk.dev.K, std::max(bk.dev.min_len, 1), det, n_det, max_det, &f)) return -1;
+        int32_t *dw = det_wakeword ? static_cast<int32_t *>(sg.out(det_wakeword, col, c->stage_out3)) : nullptr;
+        if (det_wakeword && !dw) return -1;
+        // the proposals' three rows are the call's own; the per-slot rows exist only when asked for (caller's arrays when they are device pointers)
+        const size_t row_bytes = S * pitch * sizeof(float);
+        if (!c->ws_agg.reserve(row_bytes + 16) || !c->ws_avg.reserve(row_bytes + 16) || !c->ws_set_ww.reserve(row_bytes + 16)) return -1;
+        float *dg = nullptr, *da = nullptr;
+        if (wants) {
+            // (the averaged-template scores travel with the aggregates: a caller that asks for avg alone gets the kernel's aggregate rows too)
+            dg = (agg && !sg.host) ? agg : nullptr;
+            da = (avg && !sg.host) ? avg : nullptr;
+            if (!dg) { if (!c->ws_set_agg.reserve(slot_bytes + 16)) return -1; dg = c->ws_set_agg.as<float>(); }
+            if (avg && !da) { if (!c->ws_set_avg.reserve(slot_bytes + 16)) return -1; da = c->ws_set_avg.as<float>(); }
+        }
+        uint32_t *hot = nullptr;
+        if (S && pitch) {
+            BankSetScore q;
+            q.mfcc = f.dm; q.S = S; q.n_frames = nf; q.win_pitch = pitch; q.stream_wakewords = di; q.set_size = set_size; q.band = (int)config->band_size;
+            q.score_mode = (int)config->score_mode; q.score_ref = config->score_ref; q.avg_mode = 2;
+            q.gate = (!wants && !(c->flags & RP_CTX_FULL_SCORES)) ? 1 : 0;   // detect-only
+            q.threshold = config->threshold; q.avg_threshold = config->avg_threshold;
+            q.best = c->ws_agg.as<float>(); q.best_avg = c->ws_avg.as<float>(); q.best_ww = c->ws_set_ww.as<int32_t>();
+            q.slot_agg = dg; q.slot_avg = da;
+            q.hot = hot = c->hot_flags(S);   // zero: the scan below puts every flag it reads back
+            if (!hot) return -1;
+            if (!score_bank_sets(c, bk, q)) return -1;
+        }
+        float *dv = nullptr;
+        if (config->vad_mode != RP_VAD_NONE) {
+            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
+            dv = c->ws_vad.as<float>();
+            if (!hip_ok(launch_vad_value(c->stream, f.dm, S * nf, bk.dev.K, dv), "vad_value_kernel")) return -1;
+        }
+        const ScanConfig sc = scan_config(*config, 0, true);   // window length, thresholds and the avg test come from the bank, per stream
+        if (!timed(c, kKernelScan, "scan_set_kernel", [&] {
+                return launch_scan_set(c->stream, bk.dev, di, set_size, c->ws_agg.as<float>(), c->ws_avg.as<float>(), c->ws_set_ww.as<int32_t>(), pitch, dv,
+                                       vad_mode_value(config->vad_mode), S, nf, sc, f.dd, dw, f.dn, max_det, hot);
+            })) return -1;
+        if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
+        if (dw && !sg.back(det_wakeword, dw, col)) return -1;
+        if (sg.host && agg && !sg.back(agg, dg, slot_bytes)) return -1;
+        if (sg.host && avg && !sg.back(avg, da, slot_bytes)) return -1;
         return sg.finish() ? 0 : -1;
     });
 }

@@ -93,6 +93,12 @@ bool resample_rows(Ctx *c, const ResamplerDev &rs, const void *pcm, int fmt, int
 bool bank_band_ok(const Bank &bk, int band_size);
 // the per-stream wakeword indices of a bank call, checked (host arrays) and on the device; see rp_bank.cpp
 const int32_t *stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok);
+// wakeword sets, idx [n][set_size]: set_size within 1..RP_WAKEWORD_SET_MAX; every index of a HOST array within [-1, W), else an error that
+// names stream first + i and the slot; the indices of a whole-recording call checked and on the device as stage_bank_indices
+bool set_size_ok(int set_size);
+bool set_indices_ok(const Bank &bk, size_t first, size_t n, int set_size, const int32_t *idx);
+const int32_t *stage_set_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, size_t *max_n_win,
+                                 bool *ok);
 // rp_frontend_batch and rp_frontend_batch_bank (rp_capi.cpp): with `bank`, every stream takes its gain window and reference level from its own
 // wakeword bank[stream_wakeword[s]] and rms_level_ref / window_size are not read
 int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, const rp_filters_config *filters,

@@ -140,6 +140,7 @@ struct Ctx {
     // intermediates of rp_batch_detect
     DevBuf ws_mfcc, ws_scores, ws_agg, ws_avg, ws_vad, ws_ring, ws_rms, ws_gain, ws_list, ws_hot;
     DevBuf ws_bank_idx;  // the per-stream wakeword indices of a bank call with RP_CTX_HOST_POINTERS
+    DevBuf ws_set_ww, ws_set_agg, ws_set_avg;  // wakeword-set calls: the proposals' bank indices [S][n_win]; the per-slot rows of a call with host pointers
     DevBuf ws_dtw;  // [2 * kDtwSchedChunks | 2 + 2 * kDtwFixCap] uint32: tile counters and fix list of the DTW launchers, zero between calls
     // rp_batch_detect_ingest: copy stream, two device blocks of PCM, per block "copy landed" / "kernels done with it" events
     hipStream_t copy_stream = nullptr;

@@ -247,7 +247,9 @@ enum : uint32_t { kDtwRanMfma = 1u, kDtwRanMfmaWide = 2u, kDtwRanRagged = 4u, kD
                   // dtw_bank_kernel (rp_dtw_bank.hip): per-stream wakewords from a bank
                   kDtwRanBank = 4096u,
                   // dtw_bank_stream_kernel (rp_dtw_bank.hip): the same for the new windows of a live-stream batch
-                  kDtwRanBankStream = 8192u };
+                  kDtwRanBankStream = 8192u,
+                  // dtw_set_kernel / dtw_set_stream_kernel (rp_dtw_set.hip): a set of wakewords of a bank per stream
+                  kDtwRanBankSets = 16384u, kDtwRanBankSetsStream = 32768u };
 inline void dtw_mark(const DtwWork &wk, uint32_t bit) { if (wk.ran) *wk.ran |= bit; }
 __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { return reinterpret_cast<unsigned long long *>(fix + 2 + 2 * (size_t)kDtwFixCap); }
 // (dtw_fix_append, the kernels' side of the list: rp_device.h)
@@ -618,6 +620,45 @@ hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, con
 hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg,
                                    const float *vad_value, float vad_mode_value, size_t S, long long f0, int n_new, const ScanConfig &cfg,
                                    void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det);
+
+// ---- wakeword sets (rp_dtw_set.hip, rp_scan_set.hip): stream s holds up to kScanMaxWakewords wakewords of a bank, stream_wakewords
+// [S][set_size] (outside [0, W): an empty slot) -- a `Rustpotter` with several add_wakeword calls.  Its window is Lmax(s) frames, the longest
+// of its set; every wakeword scores the oldest frames of it.
+// One scoring call over whole recordings; the BankScore fields mean what they mean there.  Stream s has n_win_s = n_frames - Lmax(s) + 1 windows.
+struct BankSetScore {
+    const float *mfcc = nullptr;      // [S][n_frames][K]
+    size_t S = 0, n_frames = 0, win_pitch = 0;
+    const int32_t *stream_wakewords = nullptr;    // [S][set_size]
+    int set_size = 0;
+    int band = 0, score_mode = 0;
+    float score_ref = 0.f;
+    int avg_mode = 0, gate = 0;
+    float threshold = 0.f, avg_threshold = 0.f;
+    // the proposal of every window, [S][win_pitch] each (all three or none): the best passing aggregate, its averaged-template score, its
+    // bank index (-1: no wakeword proposes; the first slot of equals wins); zeros / -1 behind a stream's windows
+    float *best = nullptr, *best_avg = nullptr;
+    int32_t *best_ww = nullptr;
+    // the scores slot by slot, [S][set_size][win_pitch] (optional; slot_avg only with slot_agg): zeros behind a stream's windows and in empty slots
+    float *slot_agg = nullptr, *slot_avg = nullptr;
+    uint32_t *hot = nullptr;          // [S] (optional), zero before the call: raised for streams with a proposal
+    uint32_t *fix = nullptr;          // DtwWork::fix
+};
+// built for dtw_register_tile(K, band) > 0, as launch_dtw_bank
+hipError_t launch_dtw_set(hipStream_t st, const BankDev &b, const BankSetScore &q);
+// One call of a live-stream batch over sets: q as for launch_dtw_bank_stream with q.stream_wakeword [S][set_size] and q.agg / q.avg
+// [S][set_size][n_new]; the window of stream s that ends at a new frame starts Lmax(s) - 1 frames before it
+hipError_t launch_dtw_set_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size);
+// the state machine of a stream that holds a set over the proposal rows of launch_dtw_set (window f - Lmax(s) + 1 of rows win_pitch apart);
+// det_ww (optional): the bank index of each detection's wakeword.  `hot` as in launch_scan_bank.
+hipError_t launch_scan_set(hipStream_t st, const BankDev &b, const int32_t *stream_wakewords, int set_size, const float *best, const float *best_avg,
+                           const int32_t *best_ww, size_t win_pitch, const float *vad_value, float vad_mode_value, size_t S, size_t n_frames,
+                           const ScanConfig &cfg, BatchDetection *det, int32_t *det_ww, int32_t *n_det, int max_det, uint32_t *hot);
+// ... on live streams over the slot scores agg / avg [S][set_size][n_new] of launch_dtw_set_stream: per frame the best proposal of the stream's
+// slots, each with its own thresholds (bank_lane); det_ww: the winner's bank index, det_label: -1 (both optional)
+hipError_t launch_scan_set_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakewords, int set_size, const float *agg,
+                                  const float *avg, const float *vad_value, float vad_mode_value, size_t S, long long f0, int n_new,
+                                  const ScanConfig &cfg, void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det,
+                                  int max_det);
 
 hipError_t launch_synth(hipStream_t st, uint64_t seed, uint64_t first_stream, size_t S, size_t n_samples,
                         size_t pcm_stride, float *pcm);

@@ -27,6 +27,11 @@ struct rp_stream_batch {
     const Bank *bank = nullptr;
     ~rp_stream_batch() { if (bank) --bank->live_batches; }
     DevBuf bank_idx, bank_agg, bank_avg;
+    // made by rp_stream_batch_new_bank_sets (set_size 1..8; 0: not a sets batch): stream s holds the set bank_idx[s][0 .. set_size), -1 an
+    // empty slot; bank_agg / bank_avg are then the slot scores [S][set_size][frames per call] and slot_frames the frames of the last call
+    int set_size = 0;
+    size_t slot_frames = 0;
+    size_t slots() const { return set_size ? (size_t)set_size : 1; }
     int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
     DevBuf det_ww, det_label, logits, mean, xrows, xs2;
     rp_detector_config cfg{};
@@ -84,7 +89,7 @@ static bool stream_batch_alloc(rp_stream_batch *b) {
         if (!w->agg.reserve(rows * sizeof(float) + 16) || !w->avg.reserve(rows * sizeof(float) + 16) ||
             (w->m && !w->label.reserve(rows * sizeof(int32_t) + 16)))
             return false;
-    if (b->bank && (!b->bank_agg.reserve(rows * sizeof(float) + 16) || !b->bank_avg.reserve(rows * sizeof(float) + 16))) return false;
+    if (b->bank && (!b->bank_agg.reserve(rows * b->slots() * sizeof(float) + 16) || !b->bank_avg.reserve(rows * b->slots() * sizeof(float) + 16))) return false;
     if (!b->pcm[0].reserve(pcm_bytes) || !b->pcm[1].reserve(pcm_bytes) || !b->mfcc[0].reserve(S * pitch * K * sizeof(float) + slack) ||
         !b->mfcc[1].reserve(S * pitch * K * sizeof(float) + slack) || !b->state.reserve(S * stream_state_bytes()) ||
         !b->scores.reserve(rows * (size_t)b->Tmax * sizeof(float) + 16) || !b->vad.reserve(rows * sizeof(float) + 16) ||
@@ -163,12 +168,13 @@ static bool bank_indices_ok(const Ctx *c, const Bank &bk, size_t first, size_t n
         }
     return true;
 }
-// ... -> the batch's own device copy
+// ... -> the batch's own device copy (a sets batch: rows of set_size indices)
 static bool bank_indices_put(rp_stream_batch *b, size_t first, size_t n, const int32_t *idx) {
     Ctx *c = b->c;
     const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
-    if (!b->bank_idx.reserve(b->S * sizeof(int32_t))) return false;
-    if (!hip_ok(hipMemcpyAsync(b->bank_idx.as<int32_t>() + first, idx, n * sizeof(int32_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream),
+    const size_t row = b->slots();
+    if (!b->bank_idx.reserve(b->S * row * sizeof(int32_t))) return false;
+    if (!hip_ok(hipMemcpyAsync(b->bank_idx.as<int32_t>() + first * row, idx, n * row * sizeof(int32_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream),
                 "hipMemcpyAsync(wakeword indices)")) return false;
     // the caller's host array is the caller's again when the call returns
     return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
@@ -319,6 +325,11 @@ static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, con
     const long long f0 = (long long)b->fpf() * (long long)b->chunks_seen - 3;
     if (b->bank) {
         const ScanConfig sc = scan_config(b->cfg, 0, true, (int)b->fpf());   // window length, thresholds and the avg test come from the bank, per stream
+        if (b->set_size)
+            return timed(c, kKernelScan, "scan_set_stream_kernel", [&] {
+                return launch_scan_set_stream(c->stream, b->bank->dev, b->bank_idx.as<int32_t>(), b->set_size, b->bank_agg.as<float>(), b->bank_avg.as<float>(),
+                                              dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det);
+            });
         return timed(c, kKernelScan, "scan_bank_stream_kernel", [&] {
             return launch_scan_bank_stream(c->stream, b->bank->dev, b->bank_idx.as<int32_t>(), b->bank_agg.as<float>(), b->bank_avg.as<float>(), dv, vm,
                                            b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det);
@@ -335,7 +346,8 @@ static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, con
 static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new, bool detect_only) {
     Ctx *c = b->c;
     const BankDev &bd = b->bank->dev;
-    const size_t bytes = b->S * n_new * sizeof(float);
+    const size_t bytes = b->S * b->slots() * n_new * sizeof(float);
+    b->slot_frames = n_new;
     if (b->cfg.band_size == 0 || bd.W == 0)
         return hip_ok(hipMemsetAsync(b->bank_agg.p, 0, bytes, c->stream), "hipMemsetAsync") && hip_ok(hipMemsetAsync(b->bank_avg.p, 0, bytes, c->stream), "hipMemsetAsync");
     BankStreamScore q;
@@ -344,6 +356,10 @@ static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_n
     q.avg_threshold = b->cfg.avg_threshold; q.agg = b->bank_agg.as<float>(); q.avg = b->bank_avg.as<float>();
     const DtwWork wk = c->dtw_work();
     q.fix = wk.fix;
+    if (b->set_size) {   // every slot of every stream's set is a row
+        dtw_mark(wk, kDtwRanBankSetsStream);
+        return timed(c, kKernelDtw, "dtw_set_stream_kernel", [&] { return launch_dtw_set_stream(c->stream, bd, q, b->set_size); });
+    }
     dtw_mark(wk, kDtwRanBankStream);
     return timed(c, kKernelDtw, "dtw_bank_stream_kernel", [&] { return launch_dtw_bank_stream(c->stream, bd, q); });
 }
@@ -378,7 +394,7 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
         const size_t in_chunk = b->in_len * (size_t)b->channels;
         if (pcm_stride < n_chunks * in_chunk) { set_last_error("pcm_stride smaller than n_chunks * samples per chunk"); return -1; }
         if (!sample_format_ok(fmt)) return -1;
-        if (!b->single && !b->bank && agg) { set_last_error("rp_stream_batch_process: a batch of several wakewords has no single aggregate per window"); return -1; }
+        if (!b->single && (!b->bank || b->set_size) && agg) { set_last_error("rp_stream_batch_process: a batch of several wakewords has no single aggregate per window"); return -1; }
         const MfccTablesDev *tb = c->tables_for(b->K);
         if (!tb) return -1;
         const size_t S = b->S, n_new = b->fpf() * n_chunks;
@@ -425,19 +441,25 @@ int rp_stream_batch_new_multi(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword
 }
 // live-stream batches in which stream s holds its own wakeword bank[stream_wakeword[s]] (personal wakewords; rp_batch_detect_bank with the
 // state carried between calls)
-int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config, size_t S,
-                             size_t max_chunks_per_call, rp_stream_batch **out) {
+// Both constructors over a bank; sets: rp_stream_batch_new_bank_sets, rows of set_size indices per stream (else one index, set_size not read)
+static int stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakeword, bool sets, int set_size,
+                                 const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
     return guarded([&]() -> int {
+        const std::string name = sets ? "rp_stream_batch_new_bank_sets" : "rp_stream_batch_new_bank";
         if (!ctx || !bank) { set_last_error("null handle"); return -1; }
         if (!config || !out || !stream_wakeword) { set_last_error("null argument"); return -1; }
         *out = nullptr;
+        if (sets && !set_size_ok(set_size)) return -1;
         Ctx *c = ctx->impl.get();
         const Bank &bk = *bank->impl;
         if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
         if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new_bank: S and max_chunks_per_call must be >= 1"); return -1; }
-        if (!bank_band_ok(bk, (int)config->band_size) || !bank_indices_ok(c, bk, 0, S, stream_wakeword)) return -1;   // before anything is allocated
+        if (S == 0 || max_chunks_per_call == 0) { set_last_error(name + ": S and max_chunks_per_call must be >= 1"); return -1; }
+        if (!bank_band_ok(bk, (int)config->band_size)) return -1;
+        // before anything is allocated
+        if (sets ? ((c->flags & RP_CTX_HOST_POINTERS) && !set_indices_ok(bk, 0, S, set_size, stream_wakeword)) : !bank_indices_ok(c, bk, 0, S, stream_wakeword)) return -1;
         std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
+        b->set_size = sets ? set_size : 0;
         b->c = c; b->bank = &bk; ++bk.live_batches; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
         // (an empty bank: no history; its mfcc_size is a placeholder -- the encode and frames stages run all the same, at the default size,
         // and nobody reads their frames.  A reserved bank declares its mfcc_size and the longest window it will ever hold, empty or not)
@@ -449,6 +471,15 @@ int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const in
         *out = b.release();
         return 0;
     });
+}
+int rp_stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config, size_t S,
+                             size_t max_chunks_per_call, rp_stream_batch **out) {
+    return stream_batch_new_bank(ctx, bank, stream_wakeword, false, 0, config, S, max_chunks_per_call, out);
+}
+// ... in which stream s holds the SET of wakewords bank[stream_wakewords[s][0 .. set_size)] (rp_batch_detect_bank_sets with the state carried)
+int rp_stream_batch_new_bank_sets(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size,
+                                  const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
+    return stream_batch_new_bank(ctx, bank, stream_wakewords, true, set_size, config, S, max_chunks_per_call, out);
 }
 void rp_stream_batch_free(rp_stream_batch *b) { delete b; }
 size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b) { return b ? b->chunks_seen : 0; }
@@ -489,6 +520,11 @@ static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config 
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
         if (per_stream && !b->bank) { set_last_error(name + ": the batch was not made by rp_stream_batch_new_bank"); return -1; }
+        if (per_stream && b->set_size) {
+            set_last_error(name + ": the gain normaliser is not available on a batch over wakeword sets (its level and window would come from "
+                                  "several wakewords per stream); rp_stream_batch_set_filters takes the band-pass filter alone");
+            return -1;
+        }
         if (b->chunks_seen) { set_last_error(name + ": the streams have already received audio"); return -1; }
         if (b->out_len != 480) { set_last_error(kFiltersNeed30ms); return -1; }
         const rp_gain_normalization_config &g = filters->gain_normalizer;
@@ -555,20 +591,24 @@ int rp_stream_batch_reset(rp_stream_batch *b, long long stream) {
 
 // connect / disconnect of device slots: new indices for streams first_stream .. first_stream + n - 1, each reset as rp_stream_batch_reset does
 // (add_wakeword on a detector without wakewords calls reset(), src/detector.rs:304-307)
-int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *wakewords) {
+// Both re-targeting calls; sets: rp_stream_batch_set_wakeword_sets, rows of set_size indices -- remove-all plus add-in-order
+static int stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *wakewords, bool sets) {
     bool touched = false;
     const int r = guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (sets && !b->set_size) { set_last_error("rp_stream_batch_set_wakeword_sets: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
         if (!b->bank) { set_last_error("rp_stream_batch_set_wakewords: the batch was not made by rp_stream_batch_new_bank"); return -1; }
+        if (!sets && b->set_size) { set_last_error("rp_stream_batch_set_wakewords: the batch holds wakeword sets (rp_stream_batch_new_bank_sets); use rp_stream_batch_set_wakeword_sets"); return -1; }
         if (first_stream > b->S || n > b->S - first_stream) {
-            set_last_error("rp_stream_batch_set_wakewords: streams " + std::to_string(first_stream) + " .. " + std::to_string(first_stream) + " + " +
+            set_last_error(std::string(sets ? "rp_stream_batch_set_wakeword_sets" : "rp_stream_batch_set_wakewords") + ": streams " + std::to_string(first_stream) + " .. " + std::to_string(first_stream) + " + " +
                            std::to_string(n) + " reach past the batch's " + std::to_string(b->S) + " streams");
             return -1;
         }
         if (n == 0) return 0;
         if (!wakewords) { set_last_error("null argument"); return -1; }
-        if (!bank_indices_ok(c, *b->bank, first_stream, n, wakewords)) return -1;   // a refused index leaves the batch as it was
+        // a refused index leaves the batch as it was
+        if (sets ? ((c->flags & RP_CTX_HOST_POINTERS) && !set_indices_ok(*b->bank, first_stream, n, b->set_size, wakewords)) : !bank_indices_ok(c, *b->bank, first_stream, n, wakewords)) return -1;
         touched = true;
         if (!bank_indices_put(b, first_stream, n, wakewords)) return -1;
         return hip_ok(launch_stream_state_reset_range(c->stream, b->state.p, b->S, first_stream, n, (long long)b->fpf() * (long long)b->chunks_seen),
@@ -576,6 +616,28 @@ int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_
     });
     if (r != 0 && touched) b->poisoned = true;
     return r;
+}
+
+int rp_stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *wakewords) {
+    return stream_batch_set_wakewords(b, first_stream, n, wakewords, false);
+}
+int rp_stream_batch_set_wakeword_sets(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *stream_wakewords) {
+    return stream_batch_set_wakewords(b, first_stream, n, stream_wakewords, true);
+}
+
+int rp_stream_batch_slot_scores(rp_stream_batch *b, float *agg, float *avg) {
+    return guarded([&]() -> int {
+        Ctx *c = stream_batch_enter(b, true);
+        if (!c) return -1;
+        if (!b->set_size) { set_last_error("rp_stream_batch_slot_scores: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
+        if (!b->slot_frames) { set_last_error("rp_stream_batch_slot_scores: the streams have not received audio yet"); return -1; }
+        const size_t bytes = b->S * (size_t)b->set_size * b->slot_frames * sizeof(float);
+        const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
+        const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (agg && !hip_ok(hipMemcpyAsync(agg, b->bank_agg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
+        if (avg && !hip_ok(hipMemcpyAsync(avg, b->bank_avg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
+        return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
+    });
 }
 
 int rp_stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_format fmt, size_t n_chunks, size_t pcm_stride,
