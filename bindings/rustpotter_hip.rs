@@ -104,6 +104,7 @@ pub enum rp_templates {}
 pub enum rp_stream_batch {}
 pub enum rp_model {}
 pub enum rp_wakeword_bank {}
+pub enum rp_model_bank {}
 
 // every function of include/rustpotter_hip.h, in the header's order
 extern "C" {
@@ -266,6 +267,19 @@ extern "C" {
     pub fn rp_batch_detect_model(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
                                  model: *const rp_model, mfcc_size: c_int, none_index: c_int, config: *const rp_detector_config,
                                  precision: c_int, det: *mut rp_batch_detection, det_label: *mut i32, n_det: *mut i32, max_det: c_int) -> c_int;
+    pub fn rp_model_bank_new(ctx: *mut rp_ctx, n_models: usize, models: *const *const rp_model, mfcc_size: c_int, none_index: *const i32,
+                             out: *mut *mut rp_model_bank) -> c_int;
+    pub fn rp_model_bank_new_from_rpw(ctx: *mut rp_ctx, n_models: usize, rpw_buffers: *const *const u8, rpw_lens: *const usize,
+                                      out: *mut *mut rp_model_bank) -> c_int;
+    pub fn rp_model_bank_free(bank: *mut rp_model_bank);
+    pub fn rp_model_bank_size(bank: *const rp_model_bank) -> c_int;
+    pub fn rp_model_bank_train_size(bank: *const rp_model_bank, model: i64) -> c_int;
+    pub fn rp_model_bank_labels(bank: *const rp_model_bank, model: i64) -> c_int;
+    pub fn rp_mlp_forward_windows_bank(ctx: *mut rp_ctx, bank: *const rp_model_bank, stream_model: *const i32, mfcc: *const f32, S: usize,
+                                       n_frames: usize, precision: c_int, logits: *mut f32, win_pitch: usize) -> c_int;
+    pub fn rp_batch_detect_model_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                      bank: *const rp_model_bank, stream_model: *const i32, config: *const rp_detector_config, precision: c_int,
+                                      det: *mut rp_batch_detection, det_label: *mut i32, n_det: *mut i32, max_det: c_int) -> c_int;
     pub fn rp_synth_pcm_batch(ctx: *mut rp_ctx, seed: u64, first_stream: u64, S: usize, n_samples: usize, pcm_stride: usize, pcm: *mut f32) -> c_int;
     pub fn rp_ctx_timing_enable(ctx: *mut rp_ctx, enable: c_int) -> c_int;
     pub fn rp_ctx_timing_read(ctx: *mut rp_ctx, kernel: c_int, avg_ms: *mut f64, launches: *mut c_int) -> c_int;
@@ -428,6 +442,21 @@ pub struct Templates { h: *mut rp_templates, pub n_templates: usize, pub mfcc_si
 impl Drop for Templates { fn drop(&mut self) { unsafe { rp_templates_free(self.h) } } }
 impl Templates {
     pub fn max_len(&self) -> usize { unsafe { rp_templates_max_len(self.h) as usize } }
+}
+/// A bank of personal wakeword MODELS on the device: stream `s` of a bank call is run by model `stream_model[s]` (-1: none).  Immutable;
+/// borrows the context it was made on.
+pub struct ModelBank { h: *mut rp_model_bank }
+impl Drop for ModelBank { fn drop(&mut self) { unsafe { rp_model_bank_free(self.h) } } }
+impl ModelBank {
+    /// models in the bank
+    pub fn size(&self) -> usize { unsafe { rp_model_bank_size(self.h) }.max(0) as usize }
+    /// window length (train_size) of one model
+    pub fn train_size(&self, model: usize) -> Result<usize, String> {
+        let r = unsafe { rp_model_bank_train_size(self.h, model as i64) };
+        if r < 0 { Err(last_error()) } else { Ok(r as usize) }
+    }
+    /// the largest label count in the bank: the label pitch of `mlp_forward_windows_bank`
+    pub fn labels(&self) -> usize { unsafe { rp_model_bank_labels(self.h, -1) }.max(0) as usize }
 }
 /// A bank of personal wakeword references on the device: stream `s` of a bank call carries wakeword `stream_wakeword[s]` (-1: none) --
 /// one `Rustpotter` per thread, each with its own wakeword (src/detector.rs:304-346), as one batch.  Borrows the context it was made on.
@@ -801,6 +830,50 @@ impl HipContext {
             rp_batch_detect_model(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, m.h, mfcc_size as c_int,
                                   none_index.map_or(-1, |i| i as c_int), &c, if bf16 { RP_MLP_BF16 } else { RP_MLP_F32 }, det.as_mut_ptr(),
                                   label.as_mut_ptr(), n_det.as_mut_ptr(), max_det as c_int)
+        })?;
+        let l = (0..n_streams).map(|s| label[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect();
+        Ok((split_detections(det, n_det, max_det), l))
+    }
+    /// A bank of personal wakeword MODELS: copies what it needs of every model, so `models` may be dropped afterwards.  `none_index[i]`: the
+    /// index of model i's "none" label.  mfcc_size 16, windows <= 256 frames, layers <= 32 wide (Tiny, Small up to 197 frames).
+    pub fn model_bank(&self, models: &[&Model], mfcc_size: u16, none_index: &[Option<usize>]) -> Result<ModelBank, String> {
+        assert!(models.len() == none_index.len());
+        let hs: Vec<*const rp_model> = models.iter().map(|m| m.h as *const rp_model).collect();
+        let ni: Vec<i32> = none_index.iter().map(|n| n.map_or(-1, |i| i as i32)).collect();
+        let mut h = std::ptr::null_mut();
+        status(unsafe { rp_model_bank_new(self.h, models.len(), hs.as_ptr(), mfcc_size as c_int, ni.as_ptr(), &mut h) })?;
+        Ok(ModelBank { h })
+    }
+    /// The same from wakeword-model `.rpw` bytes (labels -> none_index, mfcc_size from the files).
+    pub fn model_bank_from_rpw(&self, rpw: &[Vec<u8>]) -> Result<ModelBank, String> {
+        let ptrs: Vec<*const u8> = rpw.iter().map(|b| b.as_ptr()).collect();
+        let lens: Vec<usize> = rpw.iter().map(|b| b.len()).collect();
+        let mut h = std::ptr::null_mut();
+        status(unsafe { rp_model_bank_new_from_rpw(self.h, rpw.len(), ptrs.as_ptr(), lens.as_ptr(), &mut h) })?;
+        Ok(ModelBank { h })
+    }
+    /// `mlp_forward_windows` where stream `s` is run by `bank[stream_model[s]]` (-1: none): logits `[streams][win_pitch][bank.labels()]`, a
+    /// stream's windows and its model's labels, zeros behind both.
+    pub fn mlp_forward_windows_bank(&self, bank: &ModelBank, stream_model: &[i32], mfcc: &[f32], n_streams: usize, n_frames: usize,
+                                    win_pitch: usize) -> Result<Vec<f32>, String> {
+        assert!(stream_model.len() == n_streams && mfcc.len() >= n_streams * n_frames * 16);
+        let mut out = vec![0f32; n_streams * win_pitch * bank.labels()];
+        status(unsafe {
+            rp_mlp_forward_windows_bank(self.h, bank.h, stream_model.as_ptr(), mfcc.as_ptr(), n_streams, n_frames, RP_MLP_F32, out.as_mut_ptr(), win_pitch)
+        })?;
+        Ok(out)
+    }
+    /// `batch_detect_model` where stream `s` is run by its own model `bank[stream_model[s]]` (-1: none); returns detections and their labels.
+    pub fn batch_detect_model_bank(&self, pcm: &[f32], n_streams: usize, n_samples: usize, bank: &ModelBank, stream_model: &[i32],
+                                   config: &DetectorConfig, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>), String> {
+        assert!(pcm.len() >= n_streams * n_samples && stream_model.len() == n_streams);
+        let c: rp_detector_config = config.into();
+        let mut det = vec![rp_batch_detection::default(); n_streams * max_det];
+        let mut label = vec![0i32; n_streams * max_det];
+        let mut n_det = vec![0i32; n_streams];
+        status(unsafe {
+            rp_batch_detect_model_bank(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, bank.h,
+                                       stream_model.as_ptr(), &c, RP_MLP_F32, det.as_mut_ptr(), label.as_mut_ptr(), n_det.as_mut_ptr(), max_det as c_int)
         })?;
         let l = (0..n_streams).map(|s| label[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect();
         Ok((split_detections(det, n_det, max_det), l))

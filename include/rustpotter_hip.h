@@ -454,7 +454,7 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
  * 16 with band_size 3..6 (the pairs the register kernels are built for), or band_size 0 (every score 0, as everywhere); an averaged
  * template no longer than the wakeword's longest sample template (src/mfcc/averager.rs:5-37 folds into the first sample: never a longer one); a
  * longest sample template of at most 7546 / 2859 / 2170 frames at mfcc_size 5 / 13 / 16 (a tile's frames for it fill the 160 KB of LDS;
- * other sizes: the limit the error names).  Wakeword models cannot be part of a bank.
+ * other sizes: the limit the error names).  Wakeword models cannot be part of a wakeword bank: they have a bank of their own, rp_model_bank.
  * An empty bank (n_wakewords == 0) is a Rustpotter without wakewords: calls succeed for any band_size with every index -1, report no
  * detection and write zero rows. */
 enum { RP_WAKEWORD_BANK_MAX_TEMPLATES = 32 };
@@ -807,6 +807,59 @@ int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc
 int rp_batch_detect_model(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                           const rp_model *model, int mfcc_size, int none_index, const rp_detector_config *config, int precision,
                           rp_batch_detection *det, int32_t *det_label, int32_t *n_det, int max_det);
+
+/* Personal wakeword MODELS: a model BANK -- W wakeword models resident on the device -- and whole-recording calls in which stream s runs its
+ * own model stream_model[s].  The batched form of one `Rustpotter` per thread, each holding one wakeword model; the model counterpart of
+ * rp_wakeword_bank.  The bank COPIES what it needs of every model (device to device), so the rp_model handles may be freed once the bank
+ * exists; it borrows `ctx`, which must outlive it, is used with that context only, and is immutable.  A model has no thresholds of its own
+ * (run_wakeword_detectors, src/detector.rs:433-447, passes the detector's): every stream takes the call's config.
+ * Limits (refused with an error that names them) -- the shapes whose whole-recording forward is mlp_windows_kernel: mfcc_size 16 with an
+ * input of whole frames; windows (train_size) of at most 256 frames; layer 1 at most 32 wide (every Tiny model, Small models up to 197
+ * frames); tail layers at most 32 wide; a packed tail of at most 6144 floats.  Medium and Large models are refused.  Within the limits a
+ * bank may mix window lengths, widths, layer counts and label counts freely.  An empty bank (n_models == 0) is a Rustpotter without
+ * wakewords: calls succeed with every index -1, report no detection and write zero rows.
+ * Arithmetic: RP_MLP_F32 (three bf16 parts) only, one forward launch per call; RP_MLP_BF16 is accepted and computes the same, as in
+ * rp_mlp_forward_windows; RP_MLP_F32_FAST and RP_MLP_F32_STRICT are refused.  rp_ctx_last_mlp_kernel reports
+ * "mlp_windows_bank_kernel<bf16x3 splits>".
+ * BITS: a stream is cut into workgroups from its OWN window count n_win(s) = n_frames - train_size(s) + 1 by the rule of the shared-model
+ * path, so a bank call gives stream s exactly the bits rp_mlp_forward_windows / rp_batch_detect_model give that stream alone with its model
+ * under RP_MLP_F32, in any batch, order and mixture -- whenever n_win(s) >= 32.  (One exception, in the last bits only: a stream with fewer
+ * than 32 windows is one partial tile of the same kernel here, where the shared-model path reads such windows in place with each window's
+ * own mean, mlp_mfma_kernel; the two agree within 2e-6 on scores, the figure of INTEGRATION.md section 3 for that pair of kernels, and
+ * both are within the parity bar.) */
+typedef struct rp_model_bank rp_model_bank;
+/* models [n_models]: handles of this context.  none_index [n_models]: index of each model's "none" label, -1 without one (NULL: every -1).
+ * A model that is refused fails the call with "model <index>: <reason>". */
+int rp_model_bank_new(rp_ctx *ctx, size_t n_models, const rp_model *const *models, int mfcc_size, const int32_t *none_index, rp_model_bank **out);
+/* The same from wakeword-model .rpw bytes (what rp_wakeword_model_train returns): the layers by model type, none_index from the labels,
+ * mfcc_size from the files -- all equal, else "wakeword <index>: Usage of wakewords with different mfcc size is not supported, ignoring
+ * wakeword" (src/detector.rs:310-320).  A wakeword reference or a file the reader refuses fails the call: "wakeword <index>: <reason>". */
+int rp_model_bank_new_from_rpw(rp_ctx *ctx, size_t n_models, const uint8_t *const *rpw_buffers, const size_t *rpw_lens, rp_model_bank **out);
+void rp_model_bank_free(rp_model_bank *bank);
+/* models in the bank; -1 for a NULL bank */
+int rp_model_bank_size(const rp_model_bank *bank);
+/* train_size (the window length in frames) of one model; model < 0: the largest in the bank (0 for an empty bank).  -1 for a NULL bank or
+ * an index outside the bank. */
+int rp_model_bank_train_size(const rp_model_bank *bank, long long model);
+/* label count of one model; model < 0: the largest in the bank = the label pitch of rp_mlp_forward_windows_bank.  -1 as above. */
+int rp_model_bank_labels(const rp_model_bank *bank, long long model);
+/* rp_mlp_forward_windows with stream s run by model stream_model[s] [S] (-1: none): mfcc [S][n_frames][16] ->
+ * logits [S][win_pitch][rp_model_bank_labels(bank, -1)].  Row (s, w) holds the labels of s's model, zeros behind them; windows behind
+ * n_win(s), streams without a model and streams shorter than their window are zero rows.  win_pitch below the largest n_win(s) of the call
+ * is refused (device arrays: below the largest window count any model of the bank has).  Indices: with RP_CTX_HOST_POINTERS an index outside
+ * [-1, W) is an error that names the stream, found before anything is launched or written; with device arrays the kernels treat such an
+ * index as -1. */
+int rp_mlp_forward_windows_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, const float *mfcc, size_t S, size_t n_frames,
+                                int precision, float *logits, size_t win_pitch);
+/* rp_batch_detect_model with stream s run by model stream_model[s]: stream s behaves as Rustpotter::new(config) +
+ * add_wakeword(models[stream_model[s]]) + process_samples -- its window is its model's train_size, its countdown train_size / 2; VAD, reset
+ * and the score / label logic as in rp_batch_detect_model, none_index from the bank.  A stream with index -1, or shorter than its window,
+ * reports n_det = 0.  det_label [S][max_det] (NULL to skip): label index of each detection, 0 behind a stream's detections (as
+ * rp_batch_detect_model).  Index rules as rp_mlp_forward_windows_bank.  Every detection equals that of rp_batch_detect_model over the
+ * stream alone with its model (scores bit for bit under BITS above). */
+int rp_batch_detect_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                               const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, int precision,
+                               rp_batch_detection *det, int32_t *det_label, int32_t *n_det, int max_det);
 
 /* Synthetic benchmark input of BASELINE.md §2, generated on the device:
  * pcm[s][i] = (splitmix64(seed ^ ((first_stream+s)<<32 + i)) >> 40) / 2^24 - 0.5 */

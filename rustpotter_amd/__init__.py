@@ -7,6 +7,6 @@ the shared library is missing, or no HIP device is usable, the calls raise.
 """
 from .api import (  # noqa: F401
     AudioFmt, BandPassConfig, BatchContext, DetectorConfig, Endianness, FiltersConfig,
-    GainNormalizationConfig, Model, Rustpotter, RustpotterConfig, RustpotterDetection, RustpotterError,
+    GainNormalizationConfig, Model, ModelBank, Rustpotter, RustpotterConfig, RustpotterDetection, RustpotterError,
     SampleFormat, ScoreMode, StreamBatch, Templates, VADMode, WakewordBank, arithmetic_all, batch_detect_sharded, batch_detect_sharded_dev, build_info, sharded_gather_info, lib_path, load_library, mfcc_num_frames, resampler_frame_lengths,
 )

@@ -120,6 +120,8 @@ SYMBOLS = [
     "rp_wakeword_bank_put", "rp_wakeword_bank_put_from_rpw", "rp_wakeword_bank_enrol",
     "rp_dtw_score_bank_sets", "rp_batch_detect_bank_sets", "rp_stream_batch_new_bank_sets", "rp_stream_batch_set_wakeword_sets",
     "rp_stream_batch_slot_scores",
+    "rp_model_bank_new", "rp_model_bank_new_from_rpw", "rp_model_bank_free", "rp_model_bank_size", "rp_model_bank_train_size",
+    "rp_model_bank_labels", "rp_mlp_forward_windows_bank", "rp_batch_detect_model_bank",
 ]
 
 
@@ -250,6 +252,16 @@ def load_library():
     L.rp_wakeword_bank_free.argtypes = [vp]
     L.rp_wakeword_bank_free.restype = None
     L.rp_wakeword_bank_max_len.argtypes = [vp, C.c_longlong]
+    L.rp_model_bank_new.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.c_int, i32p, C.POINTER(vp)]
+    L.rp_model_bank_new_from_rpw.argtypes = [vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(vp)]
+    L.rp_model_bank_free.argtypes = [vp]
+    L.rp_model_bank_free.restype = None
+    L.rp_model_bank_size.argtypes = [vp]
+    L.rp_model_bank_train_size.argtypes = [vp, C.c_longlong]
+    L.rp_model_bank_labels.argtypes = [vp, C.c_longlong]
+    L.rp_mlp_forward_windows_bank.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t]
+    L.rp_batch_detect_model_bank.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(_DetectorConfig), C.c_int,
+                                             vp, vp, vp, C.c_int]
     L.rp_wakeword_bank_set_rms_levels.argtypes = [vp, fp]
     L.rp_wakeword_bank_rms_level.argtypes = [vp, C.c_longlong]
     L.rp_wakeword_bank_rms_level.restype = C.c_float
@@ -538,6 +550,43 @@ class Model:
     def __del__(self):
         if getattr(self, "_h", None):
             self._L.rp_model_free(self._h)
+            self._h = None
+
+
+class ModelBank:
+    """rp_model_bank: W wakeword models resident on the device, run per stream through an index (BatchContext.mlp_forward_windows_bank /
+    batch_detect_model_bank).  Exactly one of models = [Model, ...] with none_index = [index of each model's "none" label or -1, ...]
+    (default: every -1), or rpw = [bytes of a wakeword-model .rpw, ...].  The bank copies what it needs: the Model objects may go."""
+
+    def __init__(self, ctx, models=None, none_index=None, mfcc_size=16, rpw=None):
+        import numpy as np
+        if (models is None) == (rpw is None):
+            raise RustpotterError("ModelBank takes either models or rpw")
+        self._L = load_library()
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        if rpw is not None:
+            W = len(rpw)
+            bufs = [bytes(b) for b in rpw]
+            r = self._L.rp_model_bank_new_from_rpw(ctx._h, W, (C.c_char_p * W)(*bufs), (C.c_size_t * W)(*[len(b) for b in bufs]), C.byref(self._h))
+        else:
+            W = len(models)
+            ni = np.full(W, -1, np.int32) if none_index is None else np.ascontiguousarray(none_index, np.int32)
+            assert ni.shape == (W,)
+            hs = (C.c_void_p * W)(*[m._h for m in models])
+            r = self._L.rp_model_bank_new(ctx._h, W, hs, int(mfcc_size), ni.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self._h))
+        if r < 0:
+            self._h = None
+            raise _err()
+        self.W = int(self._L.rp_model_bank_size(self._h))
+        self.train_sizes = [int(self._L.rp_model_bank_train_size(self._h, w)) for w in range(self.W)]   # window length of every model
+        self.labels = [int(self._L.rp_model_bank_labels(self._h, w)) for w in range(self.W)]
+        self.max_train_size = int(self._L.rp_model_bank_train_size(self._h, -1))
+        self.label_pitch = int(self._L.rp_model_bank_labels(self._h, -1))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.rp_model_bank_free(self._h)
             self._h = None
 
 
@@ -1561,6 +1610,72 @@ class BatchContext:
         if self._L.rp_mlp_forward_windows(self._h, model._h, mfcc.ctypes.data, S, nf, K, MLP_PRECISION[precision], out.ctypes.data) < 0:
             raise _err()
         return out
+
+    def model_bank(self, models=None, none_index=None, mfcc_size=16, rpw=None):
+        """rp_model_bank_new / _new_from_rpw: a ModelBank on this context"""
+        return ModelBank(self, models=models, none_index=none_index, mfcc_size=mfcc_size, rpw=rpw)
+
+    def mlp_forward_windows_bank(self, mfcc, bank, stream_model, precision="f32", win_pitch=None):
+        """rp_mlp_forward_windows_bank: mfcc [S][n_frames][16] -> logits [S][win_pitch][bank.label_pitch]; row (s, w) holds the labels of
+        stream s's model bank[stream_model[s]] (-1: none) for its own windows, zeros behind both.  win_pitch defaults to the largest window
+        count of the call."""
+        import numpy as np
+        assert self.host
+        mfcc = np.ascontiguousarray(mfcc, np.float32)
+        S, nf, K = mfcc.shape
+        assert K == 16
+        idx = np.ascontiguousarray(stream_model, np.int32)
+        assert idx.shape == (S,)
+        if win_pitch is None:
+            win_pitch = max([0] + [max(0, nf - bank.train_sizes[w] + 1) for w in idx if 0 <= w < bank.W])
+        out = np.full((S, win_pitch, bank.label_pitch), np.nan, np.float32)
+        if self._L.rp_mlp_forward_windows_bank(self._h, bank._h, idx.ctypes.data, mfcc.ctypes.data, S, nf, MLP_PRECISION[precision],
+                                               out.ctypes.data, win_pitch) < 0:
+            raise _err()
+        return out
+
+    def mlp_forward_windows_bank_dev(self, bank, idx_ptr, mfcc_ptr, S, n_frames, precision, out_ptr, win_pitch):
+        """rp_mlp_forward_windows_bank on device pointers"""
+        if self._L.rp_mlp_forward_windows_bank(self._h, bank._h, idx_ptr, mfcc_ptr, S, n_frames, MLP_PRECISION[precision], out_ptr, win_pitch) < 0:
+            raise _err()
+
+    def batch_detect_model_bank(self, pcm, bank, stream_model, detector_config, precision="f32", max_det=8):
+        """rp_batch_detect_model_bank: the whole path with stream s run by its own model bank[stream_model[s]] (-1: none)
+        -> (det, det_label, n_det)."""
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        idx = np.ascontiguousarray(stream_model, np.int32)
+        assert idx.shape == (S,)
+        det = np.zeros((S, max_det), dtype=DET_DTYPE)
+        dlab = np.zeros((S, max_det), np.int32)
+        n_det = np.zeros(S, np.int32)
+        c = detector_config._c()
+        if self._L.rp_batch_detect_model_bank(self._h, pcm.ctypes.data, fmt, S, N, N, bank._h, idx.ctypes.data, C.byref(c),
+                                              MLP_PRECISION[precision], det.ctypes.data, dlab.ctypes.data, n_det.ctypes.data, max_det) < 0:
+            raise _err()
+        return det, dlab, n_det
+
+    def batch_detect_model_dev(self, pcm_ptr, fmt, S, N, stride, model, mfcc_size, none_index, detector_config, precision, det_ptr, label_ptr,
+                               n_det_ptr, max_det):
+        """rp_batch_detect_model on device pointers (tools/bench_model_bank.py)"""
+        c = detector_config._c()
+        if self._L.rp_batch_detect_model(self._h, pcm_ptr, int(fmt), S, N, stride, model._h, mfcc_size, none_index, C.byref(c),
+                                         MLP_PRECISION[precision], det_ptr, label_ptr, n_det_ptr, max_det) < 0:
+            raise _err()
+
+    def batch_detect_model_bank_dev(self, pcm_ptr, fmt, S, N, stride, bank, idx_ptr, detector_config, precision, det_ptr, label_ptr, n_det_ptr, max_det):
+        """rp_batch_detect_model_bank on device pointers (tools/bench_model_bank.py)"""
+        c = detector_config._c()
+        if self._L.rp_batch_detect_model_bank(self._h, pcm_ptr, int(fmt), S, N, stride, bank._h, idx_ptr, C.byref(c), MLP_PRECISION[precision],
+                                              det_ptr, label_ptr, n_det_ptr, max_det) < 0:
+            raise _err()
 
     def mlp_dev(self, model, x_ptr, B, precision, out_ptr):
         if self._L.rp_mlp_forward_batch(self._h, model._h, x_ptr, B, MLP_PRECISION[precision], out_ptr) < 0:

@@ -8,6 +8,7 @@ struct rp_ctx { std::unique_ptr<rp::Ctx> impl; };
 struct rp_templates { std::unique_ptr<rp::Templates> impl; };
 struct rp_model { std::unique_ptr<rp::Model> impl; };
 struct rp_wakeword_bank { std::unique_ptr<rp::Bank> impl; };
+struct rp_model_bank { std::unique_ptr<rp::ModelBank> impl; };
 
 namespace rp {
 

@@ -14,7 +14,6 @@ namespace rp {
 
 namespace {
 constexpr float kPi = 3.14159274101257324f;
-constexpr const char *kNoneLabel = "none";  // src/constants.rs:12
 
 // GainNormalizerFilter::get_rms_level, src/audio/gain_normalizer_filter.rs:49-55
 float rms_level_of(const float *s, int n) {
@@ -206,34 +205,9 @@ bool Rustpotter::add_wakeword_model(const std::string &key, WakewordModelData &&
     std::unique_ptr<Wakeword> w(new Wakeword());
     w->is_model = true;
     w->model = std::move(model);
-    // init_model, src/wakewords/nn/wakeword_nn.rs:165-389: Tiny has ln1,ln2; the others ln1..ln3
-    std::string mt = w->model.m_type;
-    std::transform(mt.begin(), mt.end(), mt.begin(), ::tolower);
-    w->n_layers = mt == "tiny" ? 2 : (mt == "small" || mt == "medium" || mt == "large") ? 3 : 0;
-    if (w->n_layers == 0) { set_last_error("Unknown model type"); return false; }
-    std::vector<const float *> wp, bp;
-    for (int l = 0; l < w->n_layers; ++l) {
-        auto wi = w->model.weights.find("ln" + std::to_string(l + 1) + ".weight");
-        auto bi = w->model.weights.find("ln" + std::to_string(l + 1) + ".bias");
-        if (wi == w->model.weights.end() || bi == w->model.weights.end() || wi->second.first.size() != 2) {
-            set_last_error("Incorrect model layers");  // wakeword_nn.rs:252-256
-            return false;
-        }
-        if (l == 0) w->dims.push_back((int)wi->second.first[1]);
-        else if ((int)wi->second.first[1] != w->dims.back()) { set_last_error("Incorrect model layers"); return false; }
-        w->dims.push_back((int)wi->second.first[0]);
-        if (bi->second.second.size() != wi->second.first[0]) { set_last_error("Incorrect model layers"); return false; }
-        // the tensor must hold exactly out x in values (the dims are attacker-controlled: Model::create copies out*in floats)
-        if (wi->second.first[0] == 0 || wi->second.first[1] == 0 || wi->second.first[0] > 0x7fffffffULL || wi->second.first[1] > 0x7fffffffULL ||
-            wi->second.second.size() / wi->second.first[0] != wi->second.first[1] ||
-            wi->second.second.size() % wi->second.first[0] != 0) { set_last_error("Incorrect model layers"); return false; }
-        wp.push_back(wi->second.second.data());
-        bp.push_back(bi->second.second.data());
-    }
-    w->net.reset(Model::create(ctx_.get(), w->n_layers, w->dims.data(), wp.data(), bp.data()));
+    // init_model, src/wakewords/nn/wakeword_nn.rs:165-389 (model_from_data, shared with the model bank)
+    w->net.reset(model_from_data(ctx_.get(), w->model, &w->n_layers, &w->dims, &w->none_index));
     if (!w->net) return false;
-    if (w->dims.back() != (int)w->model.labels.size()) { set_last_error("Incorrect model layers"); return false; }
-    for (size_t i = 0; i < w->model.labels.size(); ++i) if (w->model.labels[i] == kNoneLabel) { w->none_index = (int)i; break; }
     bool replaced = false;
     for (auto &kv : wakewords_) if (kv.first == key) { kv.second = std::move(w); replaced = true; break; }
     if (!replaced) wakewords_.emplace_back(key, std::move(w));

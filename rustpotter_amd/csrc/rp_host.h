@@ -260,6 +260,24 @@ struct Model {
     ~Model();
 };
 
+// init_model of a parsed wakeword model (src/wakewords/nn/wakeword_nn.rs:165-389, "Incorrect model layers" :252-256): its layers by type
+// (Tiny: ln1, ln2; the others ln1..ln3), the tensors checked against their declared shapes, the index of the "none" label (-1: none).
+// nullptr with the error set.  (rp_model_bank.cpp; the single-stream detector and the model bank load .rpw models through it)
+Model *model_from_data(Ctx *ctx, const WakewordModelData &model, int *n_layers, std::vector<int> *dims, int *none_index);
+
+// A model bank (rp_model_bank.cpp): W wakeword models copied into pools on the device, run per stream through an index
+// (mlp_windows_bank_kernel in rp_mlp.hip).  Borrows the context; immutable.
+struct ModelBank {
+    Ctx *ctx = nullptr;
+    ModelBankDev dev;
+    std::vector<ModelBankEntry> e;   // the host's copy of dev.e
+    DevBuf d_e, d_wimg, d_b1, d_wsum, d_tail, d_ww;
+    BankDev scan;                    // W and a BankWakeword per model for scan_bank_kernel: max_len = L, avg set, both thresholds -1
+    int max_L = 0, min_L = 0;
+    // models: W handles of this context; none_index [W] (null: every -1); false with the error set
+    static ModelBank *create(Ctx *ctx, size_t W, Model *const *models, int mfcc_size, const int32_t *none_index);
+};
+
 // ------------------------------------------------------------ `Rustpotter` mirror
 struct Detection {  // src/detector.rs:488-501
     std::string name;

@@ -777,4 +777,38 @@ hipError_t launch_nn_score(hipStream_t st, const float *logits, size_t n_rows, i
                            int calc_avg, float threshold, float avg_threshold, float *agg, float *avg, int32_t *label,
                            uint32_t *hot = nullptr, size_t rows_per_stream = 0);  // hot: a flag per stream (zeroed by the caller) raised by every window that passed
 
+// ---- model bank (rp_model_bank.cpp; kernels in rp_mlp.hip): W wakeword models resident on the device, stream s runs its own model
+// stream_model[s] (outside [0, W): none).  The bank holds copies of what mlp_windows_kernel's three-part form reads of a model, in pools:
+// the lane-ordered image MlpDev::wwin3, b1, wsum for mfcc_size 16 and the packed tail; a descriptor per model says where.
+struct ModelBankEntry {
+    long long wimg;          // first 16-byte piece of its image in ModelBankDev::wimg
+    long long b1, wsum, tail;   // first float in the three float pools
+    int L, n1p;              // window length (train_size); rows of b1 / wsum (16 or 32)
+    int n_layers, d1, d2, d3;
+    int tail_floats, n_labels, none_index, pad;
+};
+struct ModelBankDev {
+    int W = 0, label_pitch = 0;           // label_pitch: the largest label count
+    const ModelBankEntry *e = nullptr;    // [W]
+    const void *wimg = nullptr;           // 16-byte pieces
+    const float *b1 = nullptr, *wsum = nullptr, *tail = nullptr;
+};
+// The shape of one call's launch: NT = the most tiles a workgroup of the call owns, bps = the most workgroups a stream has, LDS bytes for the
+// largest staging.  model_bank_shape works it out from the window lengths / tail sizes of the models the call may use.
+struct ModelBankShape { int nt = 0; unsigned bps = 0; size_t lds = 0; };
+void model_bank_shape_add(ModelBankShape *sh, size_t n_frames, int L, int tail_floats);
+// window means of every stream's own window length, mean [S][win_pitch][16] (the sums of launch_window_means, frame order)
+hipError_t launch_window_means_bank(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *mfcc, size_t S, size_t n_frames,
+                                    size_t win_pitch, float *mean);
+// logits [S][win_pitch][label_pitch], zeroed here: row (s, w) gets the labels of s's model for w < n_win(s)
+hipError_t launch_mlp_windows_bank(hipStream_t st, const ModelBankDev &b, const ModelBankShape &sh, const int32_t *stream_model, const float *mfcc,
+                                   size_t S, size_t n_frames, const float *mean, size_t win_pitch, float *logits);
+// launch_nn_score with the label count and none_index of each row's model; rows without a window: agg -2, avg 0, label -1
+hipError_t launch_nn_score_bank(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *logits, size_t S, size_t n_frames,
+                                size_t win_pitch, float score_ref10, int calc_avg, float threshold, float avg_threshold, float *agg, float *avg,
+                                int32_t *label, uint32_t *hot);
+// det_label [S][max_det] = the label of each detection's window (label [S][win_pitch]), 0 behind a stream's detections
+hipError_t launch_model_bank_labels(hipStream_t st, const BatchDetection *det, const int32_t *n_det, const int32_t *label, size_t S, size_t win_pitch,
+                                    int max_det, int32_t *det_label);
+
 }  // namespace rp

@@ -77,13 +77,9 @@ __device__ __forceinline__ float nn_inverse_similarity(float n1, float n2, float
 
 // get_label (:47-60: max_by(total_cmp) keeps the LAST maximum), run_detection_by_label (:61-99: second_prob is the
 // smallest other logit), validate_scores (:113-123)
-__global__ __launch_bounds__(256) void nn_score_kernel(const float *__restrict__ logits, size_t n_rows, int nl, int none_index,
-                                                       float ref, int calc_avg, float threshold, float avg_threshold,
-                                                       float *__restrict__ agg, float *__restrict__ avg, int32_t *__restrict__ label,
-                                                       uint32_t *__restrict__ hot, size_t rows_per_stream) {
-    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rows) return;
-    const float *lg = logits + r * nl;
+// one window's logits lg [nl] -> its label, score (-2: no valid detection) and avg score
+__device__ __forceinline__ void nn_score_row(const float *__restrict__ lg, int nl, int none_index, float ref, int calc_avg, float threshold,
+                                             float avg_threshold, float *score_out, float *avg_out, int *label_out) {
     int bi = 0;
     for (int i = 1; i < nl; ++i) if (!(lg[i] < lg[bi])) bi = i;
     float score = -2.f, av = 0.f;
@@ -102,9 +98,78 @@ __global__ __launch_bounds__(256) void nn_score_kernel(const float *__restrict__
         const float sc = nn_inverse_similarity(label_prob, none_prob, ref);
         if (sc >= threshold && av >= avg_threshold) score = sc;
     }
+    *score_out = score; *avg_out = av; *label_out = bi;
+}
+
+__global__ __launch_bounds__(256) void nn_score_kernel(const float *__restrict__ logits, size_t n_rows, int nl, int none_index,
+                                                       float ref, int calc_avg, float threshold, float avg_threshold,
+                                                       float *__restrict__ agg, float *__restrict__ avg, int32_t *__restrict__ label,
+                                                       uint32_t *__restrict__ hot, size_t rows_per_stream) {
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_rows) return;
+    float score, av;
+    int bi;
+    nn_score_row(logits + r * nl, nl, none_index, ref, calc_avg, threshold, avg_threshold, &score, &av, &bi);
     agg[r] = score; avg[r] = av; label[r] = bi;
     // a stream with no window that passed cannot fire (detector.rs:411-429): the scan skips it (every writer stores the same value)
     if (hot && score != -2.f) hot[r / rows_per_stream] = 1u;
+}
+
+// The same where stream s runs its own model of a bank: label count and none_index come from the model of the row's stream, rows are
+// [S][win_pitch] with logits label_pitch floats apart.  A row that is no window of its stream can never fire.
+__global__ __launch_bounds__(256) void nn_score_bank_kernel(ModelBankDev b, const int32_t *__restrict__ stream_model, const float *__restrict__ logits,
+                                                            size_t S, size_t n_frames, size_t win_pitch, float ref, int calc_avg, float threshold,
+                                                            float avg_threshold, float *__restrict__ agg, float *__restrict__ avg,
+                                                            int32_t *__restrict__ label, uint32_t *__restrict__ hot) {
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= S * win_pitch) return;
+    const size_t s = r / win_pitch, w = r - s * win_pitch;
+    const int mi = stream_model[s];
+    float score = -2.f, av = 0.f;
+    int bi = -1;
+    if (mi >= 0 && mi < b.W) {
+        const ModelBankEntry e = b.e[mi];
+        if (n_frames >= (size_t)e.L && w < n_frames - (size_t)e.L + 1)
+            nn_score_row(logits + r * (size_t)b.label_pitch, e.n_labels, e.none_index, ref, calc_avg, threshold, avg_threshold, &score, &av, &bi);
+    }
+    agg[r] = score; avg[r] = av; label[r] = bi;
+    if (hot && score != -2.f) hot[s] = 1u;
+}
+
+hipError_t launch_nn_score_bank(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *logits, size_t S, size_t n_frames,
+                                size_t win_pitch, float score_ref10, int calc_avg, float threshold, float avg_threshold, float *agg, float *avg,
+                                int32_t *label, uint32_t *hot) {
+    const size_t blocks = (S * win_pitch + 255) / 256;
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nn_score_bank_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b, stream_model, logits, S, n_frames, win_pitch, score_ref10,
+                       calc_avg, threshold, avg_threshold, agg, avg, label, hot);
+    return hipGetLastError();
+}
+
+// the label of every detection's window, gathered behind the scan; 0 behind a stream's detections, as rp_batch_detect_model leaves them
+__global__ __launch_bounds__(256) void model_bank_labels_kernel(const BatchDetection *__restrict__ det, const int32_t *__restrict__ n_det,
+                                                                const int32_t *__restrict__ label, size_t S, size_t win_pitch, int max_det,
+                                                                int32_t *__restrict__ det_label) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * (size_t)max_det) return;
+    const size_t s = i / (size_t)max_det;
+    const int j = (int)(i - s * (size_t)max_det);
+    int32_t v = 0;
+    if (j < n_det[s]) {
+        const int32_t w = det[i].window;
+        if (w >= 0 && (size_t)w < win_pitch) v = label[s * win_pitch + (size_t)w];
+    }
+    det_label[i] = v;
+}
+
+hipError_t launch_model_bank_labels(hipStream_t st, const BatchDetection *det, const int32_t *n_det, const int32_t *label, size_t S, size_t win_pitch,
+                                    int max_det, int32_t *det_label) {
+    if (S == 0 || max_det <= 0) return hipSuccess;
+    const size_t blocks = (S * (size_t)max_det + 255) / 256;
+    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(model_bank_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, st, det, n_det, label, S, win_pitch, max_det, det_label);
+    return hipGetLastError();
 }
 
 hipError_t launch_nn_score(hipStream_t st, const float *logits, size_t n_rows, int n_labels, int none_index, float score_ref10,
@@ -728,27 +793,64 @@ typedef float f32x16w __attribute__((ext_vector_type(16)));
 // P3 (round 6, RP_MLP_F32): the frames are staged as THREE bf16 parts (exact) and a frame step is six v_mfma_f32_32x32x16_bf16 per tile
 // (x_i w_j, i + j <= 2, smallest first) against the three-part weight image MlpDev::wwin3 -- f32-grade products, no f16 range, nothing listed;
 // three planes of frames and seven accumulator tiles take two waves per SIMD.  !P3: two f16 parts (RP_MLP_F32_FAST), as described above.
+// The kernel is a thin front of mlp_windows_body, which mlp_windows_bank_kernel (per-stream models) shares.
+
+// The cut of a stream's n_win windows into workgroups, the one rule of mlp_route (host) and mlp_windows_bank_kernel (device, per stream): as
+// few workgroups per stream as `cap` <= 7 tiles of 32 windows each allow, the tiles spread evenly over them.  A window's bits depend on
+// this cut (BITS above), so it exists once.
+struct WinCut { int tiles; unsigned bps; };   // tiles per workgroup, workgroups per stream
+__host__ __device__ inline WinCut mlp_windows_cut(size_t n_win, int cap = kWinMaxTiles) {
+    const size_t tiles = (n_win + kWinTile - 1) / kWinTile;
+    if (tiles == 0) return WinCut{0, 0u};
+    const size_t wgs = (tiles + cap - 1) / cap, per = (tiles + wgs - 1) / wgs;
+    return WinCut{(int)per, (unsigned)((n_win + per * kWinTile - 1) / (per * kWinTile))};
+}
+// frame slots of a workgroup of `tiles` tiles over windows of L frames
+__host__ __device__ inline int mlp_windows_slots(int tiles, int L) { return (tiles * kWinTile + L + 3) & ~3; }
+
+// What a workgroup of the window kernels works with.  The model: mlp_windows_kernel gets it as kernel arguments (every stream shares it),
+// mlp_windows_bank_kernel from the descriptor of its stream's model.
+struct WinModel {
+    int L;
+    const u32x4v *wimg;   // MlpDev::wwin3 (P3) / wwin
+    int n1p;              // rows of b1 / wsum
+    const float *b1, *wsum, *tail;
+    int tail_floats, n_layers, d1, d2, d3;
+};
+// Its share of one stream: windows w0 .. of the stream's n_win, nt_here <= NT tiles of them
+struct WinWork {
+    const float *src;     // frame w0 of the stream
+    const float *mean;    // the stream's window means [n_win][16]
+    float *out;           // the stream's logit rows, out_pitch floats apart
+    size_t out_pitch, w0, n_win;
+    int slots, nt_here;
+    uint32_t *redo;       // !P3: the list of rows for the f32 pass; a row's number is redo_row0 + its window, of redo_rows in the call
+    size_t redo_row0, redo_rows;
+};
+
+// The body of both kernels.  nt_here: the tiles this workgroup owns -- the constant NT in mlp_windows_kernel (every test on it folds away),
+// the stream's own count in mlp_windows_bank_kernel, whose NT is the largest of its call: tiles behind nt_here are skipped, wave-uniformly.
 template <int NT, bool P3>
-__global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel(
-    const float *__restrict__ mfcc, size_t frame_pitch, size_t n_win, int L, unsigned blocks_per_stream, const u32x4v *__restrict__ wimg, int slots,
-    int n1p, const float *__restrict__ b1, const float *__restrict__ mean, const float *__restrict__ wsum, const float *__restrict__ tail,
-    int tail_floats, int n_layers, int d1, int d2, int d3, float *__restrict__ out, uint32_t *redo) {
+__device__ __forceinline__ void mlp_windows_body(const WinModel &m, const WinWork &k) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int L = m.L, slots = k.slots, nt_here = k.nt_here, n1p = m.n1p, tail_floats = m.tail_floats, n_layers = m.n_layers;
+    const int d1 = m.d1, d2 = m.d2, d3 = m.d3;
+    const u32x4v *__restrict__ wimg = m.wimg;
+    const float *__restrict__ b1 = m.b1, *__restrict__ wsum = m.wsum, *__restrict__ tail = m.tail, *__restrict__ mean = k.mean;
     float *tl = reinterpret_cast<float *>(smem);                                   // tail weights
     unsigned *flag = reinterpret_cast<unsigned *>(tl + ((tail_floats + 3) & ~3));   // [slots] frame holds a value beyond the f16 range
     u32x4v *A = reinterpret_cast<u32x4v *>(flag + slots);                           // [2 parts][2 k-halves][slots]; later the partial sums
     const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, lr = l & 31, lh = l >> 5;
-    const size_t s = blockIdx.x / blocks_per_stream;
-    const size_t w0 = (size_t)(blockIdx.x - s * blocks_per_stream) * (NT * kWinTile);   // first window of this workgroup
-    const size_t rows_here = n_win - w0 < (size_t)(NT * kWinTile) ? n_win - w0 : (size_t)(NT * kWinTile);
+    const size_t w0 = k.w0;                                                             // first window of this workgroup
+    const size_t rows_here = k.n_win - w0 < (size_t)(nt_here * kWinTile) ? k.n_win - w0 : (size_t)(nt_here * kWinTile);
     const int n_real = (int)rows_here + L - 1;                                          // frames w0 .. w0 + n_real - 1 exist
     for (int i = tid; i < tail_floats; i += 64 * kWinWaves) tl[i] = tail[i];
     // ---- frames -> the two f16 parts, once.  The window mean is taken out after layer 1 (W.(f - mu) = W.f - sum_k mu[k] wsum[k]); MFCC
     // coefficients sit on offsets many times their spread, and summing W.f with the offsets inside costs the sum their size in f32
     // rounding.  So the frames are staged minus c = the mean of the workgroup's middle window -- every window here overlaps or
     // adjoins it, so mu - c is small -- and the correction uses mu - c: W.(f - mu) = W.(f - c) - sum_k (mu - c)[k] wsum[k].
-    const float *src = mfcc + (s * frame_pitch + w0) * 16;
-    const float4 *cmid = reinterpret_cast<const float4 *>(mean + (s * n_win + w0 + rows_here / 2) * 16);
+    const float *__restrict__ src = k.src;
+    const float4 *cmid = reinterpret_cast<const float4 *>(mean + (w0 + rows_here / 2) * 16);
     {
         // a thread's items are (frame i / 2, k-half i & 1 = tid & 1) for i = tid, tid + 256, ..: every load goes out before the first split
         constexpr int MAXI = (2 * (kWinMaxTiles * kWinTile + 256) + 64 * kWinWaves - 1) / (64 * kWinWaves);
@@ -825,7 +927,8 @@ __global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel
                         wfetch(f + kWinAhead, j);
 #pragma unroll
                         for (int t = 0; t < NT; t += 2) {
-                            const bool two = t + 1 < NT;
+                            if (t >= nt_here) break;   // wave-uniform
+                            const bool two = t + 1 < NT && t + 1 < nt_here;
                             const bf16x8 x0 = __builtin_bit_cast(bf16x8, A0[t * kWinTile + f]), x1 = __builtin_bit_cast(bf16x8, A1[t * kWinTile + f]),
                                          x2 = __builtin_bit_cast(bf16x8, A2[t * kWinTile + f]);
                             bf16x8 y0 = x0, y1 = x1, y2 = x2;
@@ -847,7 +950,8 @@ __global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel
                     // per SIMD), and the three products of a tile are one other matrix instruction apart
 #pragma unroll
                     for (int t = 0; t < NT; t += 2) {
-                        const bool two = t + 1 < NT;
+                        if (t >= nt_here) break;   // wave-uniform
+                        const bool two = t + 1 < NT && t + 1 < nt_here;
                         const f16x8 p0 = __builtin_bit_cast(f16x8, A0[t * kWinTile + f]), p1 = __builtin_bit_cast(f16x8, A1[t * kWinTile + f]);
                         f16x8 q0 = p0, q1 = p1;
                         if (two) { q0 = __builtin_bit_cast(f16x8, A0[(t + 1) * kWinTile + f]); q1 = __builtin_bit_cast(f16x8, A1[(t + 1) * kWinTile + f]); }
@@ -870,13 +974,14 @@ __global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) R[(t * 4 + e4) * 64 + l] = f32x4{acc[t][4 * e4], acc[t][4 * e4 + 1], acc[t][4 * e4 + 2], acc[t][4 * e4 + 3]};
+            for (int e4 = 0; e4 < 4; ++e4) if (t < nt_here) R[(t * 4 + e4) * 64 + l] = f32x4{acc[t][4 * e4], acc[t][4 * e4 + 1], acc[t][4 * e4 + 2], acc[t][4 * e4 + 3]};
     };
     auto add = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int e4 = 0; e4 < 4; ++e4) {
+                if (t >= nt_here) continue;   // wave-uniform
                 const f32x4 v = R[(t * 4 + e4) * 64 + l];
                 acc[t][4 * e4] = v.x + acc[t][4 * e4]; acc[t][4 * e4 + 1] = v.y + acc[t][4 * e4 + 1];
                 acc[t][4 * e4 + 2] = v.z + acc[t][4 * e4 + 2]; acc[t][4 * e4 + 3] = v.w + acc[t][4 * e4 + 3];
@@ -918,7 +1023,7 @@ __global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel
                 const int row = 8 * e4 + 4 * lh + ee;
                 size_t rr = wrow0 + row;
                 if (rr >= rows_here) rr = rows_here - 1;
-                const float4 *mu = reinterpret_cast<const float4 *>(mean + (s * n_win + w0 + rr) * 16);
+                const float4 *mu = reinterpret_cast<const float4 *>(mean + (w0 + rr) * 16);
                 float corr = 0.f;   // - sum_k (mu[row][k] - c[k]) * wsum[o][k]
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -935,17 +1040,17 @@ __global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel
         // tail layers: lane = (row lr, output phase lh), outputs strided by 2 over the phases; sums in mlp_mfma_kernel's order
         {
             const bool row_ok = wrow0 + lr < rows_here;
-            const size_t orow = s * n_win + w0 + wrow0 + lr;
+            const size_t orow = w0 + wrow0 + lr;   // the window within its stream
             if (!P3 && lh == 0 && row_ok) {   // a window holding a frame beyond the f16 range: listed for the f32 pass
                 unsigned far = 0u;
                 for (int f = 0; f < L; ++f) far |= flag[wrow0 + lr + f];
-                if (far) mlp_redo_append(redo, (uint32_t)orow, (size_t)(gridDim.x / blocks_per_stream) * n_win);
+                if (far) mlp_redo_append(k.redo, (uint32_t)(k.redo_row0 + orow), k.redo_rows);
             }
             const int dd[4] = {d1, d2, d3, 0};
             const float *hin = h1 + lr * 32;
             const float *wp = tl;
             int cur_in = d1;
-            float *dst = out + orow * (size_t)dd[n_layers - 1];
+            float *dst = k.out + orow * k.out_pitch;
             if (n_layers == 1 && row_ok)
                 for (int o = lh; o < d1; o += 2) dst[o] = hin[(o + lr) & 31];
             for (int layer = 1; layer < n_layers; ++layer) {
@@ -969,6 +1074,20 @@ __global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel
         }
         wave_lds_sync();
     }
+}
+
+template <int NT, bool P3>
+__global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel(
+    const float *__restrict__ mfcc, size_t frame_pitch, size_t n_win, int L, unsigned blocks_per_stream, const u32x4v *__restrict__ wimg, int slots,
+    int n1p, const float *__restrict__ b1, const float *__restrict__ mean, const float *__restrict__ wsum, const float *__restrict__ tail,
+    int tail_floats, int n_layers, int d1, int d2, int d3, float *__restrict__ out, uint32_t *redo) {
+    const size_t s = blockIdx.x / blocks_per_stream;
+    const size_t w0 = (size_t)(blockIdx.x - s * blocks_per_stream) * (NT * kWinTile);
+    const size_t nl = (size_t)(n_layers == 1 ? d1 : n_layers == 2 ? d2 : d3);
+    const WinModel m{L, wimg, n1p, b1, wsum, tail, tail_floats, n_layers, d1, d2, d3};
+    const WinWork k{mfcc + (s * frame_pitch + w0) * 16, mean + s * n_win * 16, out + s * n_win * nl, nl, w0, n_win, slots, NT,
+                    redo, s * n_win, (size_t)(gridDim.x / blocks_per_stream) * n_win};
+    mlp_windows_body<NT, P3>(m, k);
 }
 
 // The same for layer 1 wider than 32 (the Medium and Large model types: 65 / 130 outputs for 195 frames): NQ = 2 .. 5 waves, wave q owns
@@ -1230,6 +1349,120 @@ static hipError_t launch_mlp_windows(hipStream_t st, const MlpDev &m, const MlpR
     return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Model bank (rp_model_bank.cpp): stream s runs its OWN model bank[stream_model[s]].  mlp_windows_kernel's three-part form with the model
+// read through the stream's index: a workgroup is (stream s, block b of ITS windows), cut by mlp_windows_cut from the stream's own window
+// count n_frames - L(s) + 1 -- the cut rp_mlp_forward_windows gives that stream alone, hence its bits.  The grid is S x the most
+// workgroups a stream of the call has, NT the most tiles a workgroup of the call owns; a workgroup behind its stream's own count leaves at
+// once, tiles behind its own are skipped.  The layer-1 image (3 KB a frame of L) comes from the model's place in the bank's pool: one
+// stream's workgroups share it through L2, streams of different models share nothing.  A stream with fewer than 32 windows is one partial
+// tile here (the shared-model route takes mlp_mfma_kernel there: 2e-6 on scores).
+template <int NT>
+__global__ __launch_bounds__(64 * kWinWaves, 2) void mlp_windows_bank_kernel(ModelBankDev bank, const int32_t *__restrict__ stream_model,
+                                                                             const float *__restrict__ mfcc, size_t n_frames, unsigned grid_bps,
+                                                                             const float *__restrict__ mean, size_t win_pitch,
+                                                                             float *__restrict__ out) {
+    const size_t s = blockIdx.x / grid_bps;
+    const unsigned b = blockIdx.x - (unsigned)s * grid_bps;
+    const int mi = stream_model[s];
+    if (mi < 0 || mi >= bank.W) return;   // no model: the row stays zero
+    const ModelBankEntry e = bank.e[mi];
+    if (n_frames < (size_t)e.L) return;
+    const size_t n_win = n_frames - (size_t)e.L + 1;
+    const WinCut cut = mlp_windows_cut(n_win);
+    if (b >= cut.bps || cut.tiles > NT) return;
+    const size_t w0 = (size_t)b * (size_t)(cut.tiles * kWinTile);
+    const WinModel m{e.L, static_cast<const u32x4v *>(bank.wimg) + e.wimg, e.n1p, bank.b1 + e.b1, bank.wsum + e.wsum, bank.tail + e.tail,
+                     e.tail_floats, e.n_layers, e.d1, e.d2, e.d3};
+    const WinWork k{mfcc + (s * n_frames + w0) * 16, mean + s * win_pitch * 16, out + s * win_pitch * (size_t)bank.label_pitch,
+                    (size_t)bank.label_pitch, w0, n_win, mlp_windows_slots(cut.tiles, e.L), cut.tiles, nullptr, 0, 0};
+    mlp_windows_body<NT, true>(m, k);
+}
+
+// LDS of a workgroup of `tiles` tiles in the three-part form: tail weights, a flag per frame slot, the three frame planes in two k-halves --
+// later the sums of nt tiles and h2 of the four waves (mlp_route's win_lds)
+static size_t mlp_windows_lds3(int tail_floats, int slots, int nt) {
+    return (size_t)((tail_floats + 3) & ~3) * 4 + (size_t)slots * 4 + std::max((size_t)6 * slots * 16, (size_t)nt * 4096 + (size_t)kWinWaves * 4096);
+}
+
+void model_bank_shape_add(ModelBankShape *sh, size_t n_frames, int L, int tail_floats) {
+    if (L < 1 || n_frames < (size_t)L) return;
+    const WinCut cut = mlp_windows_cut(n_frames - (size_t)L + 1);
+    sh->nt = std::max(sh->nt, cut.tiles);
+    sh->bps = std::max(sh->bps, cut.bps);
+    // sized with the call's NT below: the sums region grows with it
+    sh->lds = std::max(sh->lds, mlp_windows_lds3(tail_floats, mlp_windows_slots(cut.tiles, L), kWinMaxTiles));
+}
+
+template <int NT>
+static hipError_t launch_mlp_windows_bank_nt(hipStream_t st, const ModelBankDev &b, const ModelBankShape &sh, const int32_t *stream_model,
+                                             const float *mfcc, size_t S, size_t n_frames, const float *mean, size_t win_pitch, float *logits) {
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_windows_bank_kernel<NT>), 160 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(mlp_windows_bank_kernel<NT>, dim3((unsigned)(S * sh.bps)), dim3(64 * kWinWaves), sh.lds, st, b, stream_model, mfcc, n_frames,
+                       sh.bps, mean, win_pitch, logits);
+    return hipGetLastError();
+}
+
+hipError_t launch_mlp_windows_bank(hipStream_t st, const ModelBankDev &b, const ModelBankShape &sh, const int32_t *stream_model, const float *mfcc,
+                                   size_t S, size_t n_frames, const float *mean, size_t win_pitch, float *logits) {
+    if (S == 0 || win_pitch == 0 || b.label_pitch == 0) return hipSuccess;
+    if (hipError_t e = hipMemsetAsync(logits, 0, S * win_pitch * (size_t)b.label_pitch * sizeof(float), st); e != hipSuccess) return e;
+    if (sh.nt == 0 || sh.bps == 0) return hipSuccess;   // no stream of the call has a window
+    if (S * sh.bps > 0x7fffffffULL || sh.lds > 160 * 1024) return hipErrorInvalidValue;
+    switch (sh.nt) {
+    case 1: return launch_mlp_windows_bank_nt<1>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
+    case 2: return launch_mlp_windows_bank_nt<2>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
+    case 3: return launch_mlp_windows_bank_nt<3>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
+    case 4: return launch_mlp_windows_bank_nt<4>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
+    case 5: return launch_mlp_windows_bank_nt<5>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
+    case 6: return launch_mlp_windows_bank_nt<6>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
+    case 7: return launch_mlp_windows_bank_nt<7>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
+    }
+    return hipErrorInvalidValue;
+}
+
+// window_means_kernel with every stream's own window length (mfcc_size 16): the same sums in frame order, hence the same bits; 64
+// consecutive windows of a stream per block, blocks behind a stream's windows leave
+__global__ __launch_bounds__(256) void window_means_bank_kernel(ModelBankDev b, const int32_t *__restrict__ stream_model, const float *__restrict__ mfcc,
+                                                                size_t n_frames, unsigned tiles, size_t win_pitch, float *__restrict__ mean) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *fs = reinterpret_cast<float *>(smem);  // [64 + L - 1][16]
+    const size_t s = blockIdx.x / tiles;
+    const size_t w0 = (size_t)(blockIdx.x - s * tiles) * 64;
+    const int mi = stream_model[s];
+    if (mi < 0 || mi >= b.W) return;
+    const int L = b.e[mi].L;
+    if (n_frames < (size_t)L) return;
+    const size_t n_win = n_frames - (size_t)L + 1;
+    if (w0 >= n_win) return;
+    const size_t nw = n_win - w0 < 64 ? n_win - w0 : 64;
+    const float *src = mfcc + (s * n_frames + w0) * 16;
+    const int nfr = (int)nw + L - 1;
+#pragma unroll 8
+    for (int i = threadIdx.x; i < nfr * 16; i += 256) fs[i] = src[i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < (int)nw * 4; i += 256) {
+        const int w = i / 4, q = i - w * 4;
+        f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+        const float *col = fs + w * 16 + 4 * q;
+#pragma unroll 8
+        for (int f = 0; f < L; ++f) sum += *reinterpret_cast<const f32x4 *>(col + f * 16);   // sequential sums, as MfccNormalizer::normalize
+        const float n = (float)L;
+        *reinterpret_cast<f32x4 *>(mean + (s * win_pitch + w0 + w) * 16 + 4 * q) = f32x4{sum.x / n, sum.y / n, sum.z / n, sum.w / n};
+    }
+}
+
+hipError_t launch_window_means_bank(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *mfcc, size_t S, size_t n_frames,
+                                    size_t win_pitch, float *mean) {
+    if (S == 0 || win_pitch == 0 || b.W == 0) return hipSuccess;
+    const size_t tiles = (win_pitch + 63) / 64, blocks = tiles * S;
+    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    const size_t lds = (size_t)(64 + 256 - 1) * 16 * sizeof(float);   // the bank's longest window: 256 frames
+    hipLaunchKernelGGL(window_means_bank_kernel, dim3((unsigned)blocks), dim3(256), lds, st, b, stream_model, mfcc, n_frames, (unsigned)tiles, win_pitch,
+                       mean);
+    return hipGetLastError();
+}
+
 static MlpRoute mlp_route(Model &md, const MlpForward &q) {
     MlpRoute r;
     if (!md.mfma_ok) return r;
@@ -1254,8 +1487,7 @@ static MlpRoute mlp_route(Model &md, const MlpForward &q) {
         if (form == 1) {
             // tiles per workgroup: as few workgroups per stream as 7 tiles each allow, the tiles spread evenly over them
             static const int cap_env = std::getenv("RP_MLP_WIN_TILES") ? std::atoi(std::getenv("RP_MLP_WIN_TILES")) : kWinMaxTiles;   // experiments
-            const size_t cap = cap_env >= 1 && cap_env <= kWinMaxTiles ? (size_t)cap_env : (size_t)kWinMaxTiles, wgs = (tiles + cap - 1) / cap;
-            r.tiles = (int)((tiles + wgs - 1) / wgs);
+            r.tiles = mlp_windows_cut(q.n_win, cap_env >= 1 && cap_env <= kWinMaxTiles ? cap_env : kWinMaxTiles).tiles;
         } else if (form == 2) {
             // 2 or 4 (measured per 8 192 streams x 202 windows, Medium / Large: 7 tiles 3.87 / 8.62 ms at two waves per SIMD, 4 tiles
             // 3.36 / 7.90 at four, 2 tiles 3.84 / 11.2 -- the weights once per 64 rows)
@@ -1267,7 +1499,7 @@ static MlpRoute mlp_route(Model &md, const MlpForward &q) {
             // frame planes (two or three parts x two k-halves); later the sums of the tiles (h1 of a tile in its place) + h2 of the
             // four waves (the wide form: h1 of its NQ output tiles + h2)
             r.bps = (q.n_win + r.tiles * kWinTile - 1) / (r.tiles * kWinTile);
-            r.slots = (r.tiles * kWinTile + m.dims[0] / 16 + 3) & ~3;
+            r.slots = mlp_windows_slots(r.tiles, m.dims[0] / 16);
             const size_t later = form == 1 ? (size_t)r.tiles * 4096 + (size_t)kWinWaves * 4096 : (size_t)32 * (32 * r.nq + 1) * 4 + (size_t)32 * 33 * 4;
             r.win_lds = (size_t)((m.tail_floats + 3) & ~3) * 4 + (size_t)r.slots * 4 + std::max((size_t)(r.prec == kMlpBf16x3 ? 6 : 4) * r.slots * 16, later);
         }
