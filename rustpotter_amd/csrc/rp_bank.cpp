@@ -1,6 +1,5 @@
-// rp_bank.cpp -- wakeword banks: W personal wakeword references resident on the device and the calls that score every stream against
-// ITS wakeword (rp_wakeword_bank_*, rp_dtw_score_bank, rp_batch_detect_bank; kernels: rp_dtw_bank.hip, scan_bank_kernel in rp_scan.hip) or
-// against its own SET of wakewords (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets; kernels: rp_dtw_set.hip, rp_scan_set.hip).
+// rp_bank.cpp -- the wakeword bank object: W personal wakeword references resident on the device (rp_wakeword_bank_*): create, growth, put,
+// enrol and the accessors.  The calls that score streams over a bank are in rp_bank_calls.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -34,7 +33,6 @@ template <class T> static bool upload(T **dst, const std::vector<T> &v, const ch
     return v.empty() || hip_ok(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), what);
 }
 
-// the wording of two refusals, shared by Bank::create and Bank::put_check
 static std::string avg_too_long(int al, int max_len) {
     return "averaged template of " + std::to_string(al) + " frames is longer than the longest sample template (" + std::to_string(max_len) +
            " frames): a bank takes averaged templates up to the window length";
@@ -46,24 +44,43 @@ static std::string window_too_long(int K, int max_len) {
            " frames at mfcc_size " + std::to_string(K) + ")";
 }
 
+// What a bank refuses in wakeword w, for a new bank (ceiling, live_batches and bank_max_len 0) and for a put alike: `count` sample templates
+// of lens[] frames, an averaged template of avg_len frames (0: none).  The first fault in the order below is the one reported; a call
+// with faults in several wakewords names the first wakeword that has one -- that precedence is not part of the contract.
+static bool wakeword_ok(size_t w, int K, long long count, const int *lens, int avg_len, int ceiling, int live_batches, int bank_max_len) {
+    auto fail = [&](const std::string &why) { set_last_error("wakeword " + std::to_string(w) + ": " + why); return false; };
+    if (count < 1) return fail("Can not create an empty wakeword");   // wakeword_ref.rs:53
+    if (count > kBankMaxTemplates) return fail(std::to_string(count) + " templates; a bank takes at most " + std::to_string(kBankMaxTemplates) + " per wakeword");
+    int ml = 0;
+    for (long long t = 0; t < count; ++t) {
+        if (lens[t] < 1) return fail("wakeword template without frames");
+        ml = std::max(ml, lens[t]);
+    }
+    if (avg_len < 0) return fail("negative avg_lens");
+    // dtw.rs:64-67 widens the band to |m - n| for an averaged template longer than the window; the reference's builder never makes one
+    // (the average has the first sample's length) and dtw_bank_kernel is built for m == n only
+    if (avg_len > ml) return fail(avg_too_long(avg_len, ml));
+    if (dtw_bank_lds_bytes(K, ml) > 160 * 1024) return fail(window_too_long(K, ml));
+    // a stream batch sized its MFCC history and gain ring once: the bank never comes to hold a window it has no room for
+    if (ceiling && ml > ceiling) return fail("window of " + std::to_string(ml) + " frames is longer than the bank's reserved length (" + std::to_string(ceiling) + " frames, rp_wakeword_bank_reserve)");
+    if (!ceiling && live_batches && ml > bank_max_len)
+        return fail("window of " + std::to_string(ml) + " frames is longer than the bank's longest (" + std::to_string(bank_max_len) +
+                    " frames) while a stream batch runs over the bank: call rp_wakeword_bank_reserve before creating the batch");
+    return true;
+}
+
 Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32_t *lens, const float *feats, const int32_t *avg_lens,
                    const float *avg_feats, const float *thresholds, const float *avg_thresholds) {
     if (K < 1) { set_last_error("mfcc_size must be >= 1"); return nullptr; }
     if (W > 0x7fffffffULL) { set_last_error("too many wakewords"); return nullptr; }
-    auto fail = [](size_t w, const std::string &why) { set_last_error("wakeword " + std::to_string(w) + ": " + why); return nullptr; };
     std::unique_ptr<Bank> bk(new Bank());
     BankDev &d = bk->dev;
     d.W = (int)W; d.K = K;
     size_t n_templates = 0, n_rows = 0, n_avg = 0, n_avg_rows = 0;
     for (size_t w = 0; w < W; ++w) {
-        if (counts[w] < 1) return fail(w, "Can not create an empty wakeword");   // wakeword_ref.rs:53
-        if (counts[w] > kBankMaxTemplates) return fail(w, std::to_string(counts[w]) + " templates; a bank takes at most " + std::to_string(kBankMaxTemplates) + " per wakeword");
-        for (int32_t t = 0; t < counts[w]; ++t) {
-            if (lens[n_templates + t] < 1) return fail(w, "wakeword template without frames");
-            n_rows += (size_t)lens[n_templates + t];
-        }
+        if (!wakeword_ok(w, K, counts[w], lens + n_templates, avg_lens ? avg_lens[w] : 0, 0, 0, 0)) return nullptr;
+        for (int32_t t = 0; t < counts[w]; ++t) n_rows += (size_t)lens[n_templates + t];
         n_templates += (size_t)counts[w];
-        if (avg_lens && avg_lens[w] < 0) return fail(w, "negative avg_lens");
         if (avg_lens && avg_lens[w] > 0) { ++n_avg; n_avg_rows += (size_t)avg_lens[w]; }
     }
     if (n_avg && !avg_feats) { set_last_error("null argument"); return nullptr; }
@@ -73,26 +90,13 @@ Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32
     std::vector<long long> trow(n_templates + n_avg);
     std::vector<float> unit((n_rows + n_avg_rows) * (size_t)K), raw((n_rows + n_avg_rows) * (size_t)K);
     bk->ww.resize(W);
-    // Template rows are scaled to unit L2 norm in f64 and rounded once to f32, an all-zero row stays zero: exactly Templates::create, so that a
-    // wakeword in a bank and the same wakeword as rp_templates give the same bits
-    auto put_rows = [&](const float *src, int L, size_t row0, bool *ref_only) -> bool {
-        for (int r = 0; r < L; ++r) {
-            double nn = 0.0;
-            float nf = 0.f;
-            for (int k = 0; k < K; ++k) {
-                const float v = src[(size_t)r * K + k];
-                if (!std::isfinite(v)) return false;
-                nn += (double)v * (double)v;
-            }
-            for (int k = 0; k < K; ++k) nf += src[(size_t)r * K + k] * src[(size_t)r * K + k];
-            const double inv = (nf > 0.f && nn > 0.0) ? 1.0 / std::sqrt(nn) : 0.0;
-            for (int k = 0; k < K; ++k) {
-                unit[(row0 + r) * K + k] = (float)((double)src[(size_t)r * K + k] * inv);
-                raw[(row0 + r) * K + k] = src[(size_t)r * K + k];
-            }
-            if (!(nf == 0.f || (nf >= kDtwNormLo && nf <= kDtwNormHiRow))) *ref_only = true;   // TemplatesDev::ref_only
-        }
-        return true;
+    // the rows prepared as Templates::create prepares them (prepare_template_row), so that a wakeword in a bank and the same wakeword as
+    // rp_templates give the same bits; false: a value is not finite
+    auto put_rows = [&](const float *src, int L, size_t row0, bool *ref_only) {
+        bool finite = true;
+        for (int r = 0; r < L; ++r)
+            finite &= prepare_template_row(src + (size_t)r * K, K, &unit[(row0 + r) * K], &raw[(row0 + r) * K], ref_only);
+        return finite;
     };
     size_t e = 0, row = 0, avg_e = n_templates, avg_row = n_rows, avg_src = 0;
     d.max_len = 0; d.min_len = 0;
@@ -101,27 +105,24 @@ Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32
         bw.first = (int)e; bw.count = counts[w]; bw.max_len = 0; bw.avg = -1; bw.ref_only = 0; bw.window_chk = 0;
         bw.threshold = thresholds ? thresholds[w] : NAN;
         bw.avg_threshold = avg_thresholds ? avg_thresholds[w] : NAN;
-        bool ref_only = false;
+        bool ref_only = false, finite = true;
         for (int32_t t = 0; t < counts[w]; ++t, ++e) {
             const int L = lens[e];
             tlen[e] = L; trow[e] = (long long)row;
-            if (!put_rows(feats + row * K, L, row, &ref_only)) return fail(w, "template features must be finite");
+            finite &= put_rows(feats + row * K, L, row, &ref_only);
             row += (size_t)L;
             bw.max_len = std::max(bw.max_len, L);
         }
         const int al = avg_lens ? avg_lens[w] : 0;
         if (al > 0) {
-            // dtw.rs:64-67 widens the band to |m - n| for an averaged template longer than the window; the reference's builder never makes one
-            // (the average has the first sample's length) and dtw_bank_kernel is built for m == n only
-            if (al > bw.max_len) return fail(w, avg_too_long(al, bw.max_len));
             tlen[avg_e] = al; trow[avg_e] = (long long)avg_row;
-            if (!put_rows(avg_feats + avg_src * K, al, avg_row, &ref_only)) return fail(w, "template features must be finite");
+            finite &= put_rows(avg_feats + avg_src * K, al, avg_row, &ref_only);
             bw.avg = (int)avg_e;
             ++avg_e; avg_row += (size_t)al; avg_src += (size_t)al;
         }
+        if (!finite) { set_last_error("wakeword " + std::to_string(w) + ": template features must be finite"); return nullptr; }
         bw.ref_only = ref_only ? 1 : 0;
         bw.window_chk = dtw_register_staged(K, bw.max_len) ? 0 : 1;
-        if (dtw_bank_lds_bytes(K, bw.max_len) > 160 * 1024) return fail(w, window_too_long(K, bw.max_len));
         d.max_len = std::max(d.max_len, bw.max_len);
         d.min_len = w == 0 ? bw.max_len : std::min(d.min_len, bw.max_len);
     }
@@ -139,28 +140,13 @@ Bank *Bank::create(Ctx *ctx, size_t W, int K, const int32_t *counts, const int32
 
 // ---------------------------------------------------------------------------------------------------------------- a bank that grows
 bool Bank::put_check(size_t first, const std::vector<PutItem> &items) const {
-    auto fail = [](size_t w, const std::string &why) { set_last_error("wakeword " + std::to_string(w) + ": " + why); return false; };
     if (first > (size_t)dev.W) {
         set_last_error("first wakeword index " + std::to_string(first) + " is past the bank's " + std::to_string(dev.W) + " wakewords: a bank has no holes");
         return false;
     }
     if (items.size() > 0x7fffffffULL - first) { set_last_error("too many wakewords"); return false; }
-    for (size_t i = 0; i < items.size(); ++i) {
-        const PutItem &it = items[i];
-        const size_t w = first + i;
-        if (it.lens.empty()) return fail(w, "Can not create an empty wakeword");   // wakeword_ref.rs:53
-        if (it.lens.size() > (size_t)kBankMaxTemplates) return fail(w, std::to_string(it.lens.size()) + " templates; a bank takes at most " + std::to_string(kBankMaxTemplates) + " per wakeword");
-        for (int l : it.lens) if (l < 1) return fail(w, "wakeword template without frames");
-        if (it.avg_len < 0) return fail(w, "negative avg_lens");
-        const int ml = it.max_len();
-        if (it.avg_len > ml) return fail(w, avg_too_long(it.avg_len, ml));
-        if (dtw_bank_lds_bytes(dev.K, ml) > 160 * 1024) return fail(w, window_too_long(dev.K, ml));
-        // a stream batch sized its MFCC history and gain ring once: the bank never comes to hold a window it has no room for
-        if (ceiling && ml > ceiling) return fail(w, "window of " + std::to_string(ml) + " frames is longer than the bank's reserved length (" + std::to_string(ceiling) + " frames, rp_wakeword_bank_reserve)");
-        if (!ceiling && live_batches && ml > dev.max_len)
-            return fail(w, "window of " + std::to_string(ml) + " frames is longer than the bank's longest (" + std::to_string(dev.max_len) +
-                               " frames) while a stream batch runs over the bank: call rp_wakeword_bank_reserve before creating the batch");
-    }
+    for (size_t i = 0; i < items.size(); ++i)
+        if (!wakeword_ok(first + i, dev.K, (long long)items[i].lens.size(), items[i].lens.data(), items[i].avg_len, ceiling, live_batches, dev.max_len)) return false;
     return true;
 }
 
@@ -367,79 +353,6 @@ bool bank_band_ok(const Bank &bk, int band_size) {
     return true;
 }
 
-}  // namespace rp
-
-namespace rp {
-
-// The per-stream indices of a call: with host arrays every index is checked before anything is launched and the largest window count a
-// stream of the call has is known; with device arrays the kernels treat an index outside [0, W) as "no wakeword" and win_pitch must hold the
-// bank's largest window count.  Returns the device pointer (null on error, *ok false).
-const int32_t *stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok) {
-    *ok = false;
-    const BankDev &d = bk.dev;
-    auto n_win_of = [&](int len) { return n_frames >= (size_t)len ? n_frames - (size_t)len + 1 : (size_t)0; };
-    *max_n_win = 0;
-    if (!sg.host) {
-        if (d.W > 0) *max_n_win = n_win_of(d.min_len);
-        *ok = true;
-        return idx;
-    }
-    for (size_t s = 0; s < S; ++s) {
-        if (idx[s] < -1 || idx[s] >= d.W) {
-            set_last_error("stream " + std::to_string(s) + ": wakeword index " + std::to_string(idx[s]) + " is outside the bank (-1 .. " + std::to_string(d.W - 1) + ")");
-            return nullptr;
-        }
-        if (idx[s] >= 0) *max_n_win = std::max(*max_n_win, n_win_of(bk.ww[(size_t)idx[s]].max_len));
-    }
-    if (S == 0) { *ok = true; return nullptr; }
-    const void *p = sg.in(idx, S * sizeof(int32_t), c->ws_bank_idx);
-    if (!p) return nullptr;
-    *ok = true;
-    return static_cast<const int32_t *>(p);
-}
-
-// The same for sets, idx [S][set_size]: the window count of a stream is that of its longest live slot; errors name stream and slot.
-const int32_t *stage_set_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, size_t *max_n_win,
-                                 bool *ok) {
-    *ok = false;
-    const BankDev &d = bk.dev;
-    auto n_win_of = [&](int len) { return n_frames >= (size_t)len ? n_frames - (size_t)len + 1 : (size_t)0; };
-    *max_n_win = 0;
-    if (!sg.host) {
-        if (d.W > 0) *max_n_win = n_win_of(d.min_len);
-        *ok = true;
-        return idx;
-    }
-    if (!set_indices_ok(bk, 0, S, set_size, idx)) return nullptr;
-    for (size_t s = 0; s < S; ++s) {
-        int lmax = 0;
-        for (int j = 0; j < set_size; ++j) {
-            const int32_t wi = idx[s * (size_t)set_size + j];
-            if (wi >= 0) lmax = std::max(lmax, bk.ww[(size_t)wi].max_len);
-        }
-        if (lmax > 0) *max_n_win = std::max(*max_n_win, n_win_of(lmax));
-    }
-    if (S == 0) { *ok = true; return nullptr; }
-    const void *p = sg.in(idx, S * (size_t)set_size * sizeof(int32_t), c->ws_bank_idx);
-    if (!p) return nullptr;
-    *ok = true;
-    return static_cast<const int32_t *>(p);
-}
-
-bool set_indices_ok(const Bank &bk, size_t first, size_t n, int set_size, const int32_t *idx) {
-    const int W = bk.dev.W;
-    for (size_t i = 0; i < n; ++i)
-        for (int j = 0; j < set_size; ++j) {
-            const int32_t wi = idx[i * (size_t)set_size + j];
-            if (wi < -1 || wi >= W) {
-                set_last_error("stream " + std::to_string(first + i) + ", slot " + std::to_string(j) + ": wakeword index " + std::to_string(wi) +
-                               " is outside the bank (-1 .. " + std::to_string(W - 1) + ")");
-                return false;
-            }
-        }
-    return true;
-}
-
 bool set_size_ok(int set_size) {
     if (set_size < 1 || set_size > RP_WAKEWORD_SET_MAX) {
         set_last_error("set_size " + std::to_string(set_size) + " is outside 1 .. " + std::to_string((int)RP_WAKEWORD_SET_MAX) + " (RP_WAKEWORD_SET_MAX)");
@@ -451,42 +364,6 @@ bool set_size_ok(int set_size) {
 }  // namespace rp
 
 namespace {
-
-bool pitch_ok(size_t win_pitch, size_t max_n_win) {
-    if (win_pitch < max_n_win) {
-        set_last_error("win_pitch " + std::to_string(win_pitch) + " is smaller than the largest window count of the call (" + std::to_string(max_n_win) + ")");
-        return false;
-    }
-    return true;
-}
-
-// the timed launch (kernel 1 of rp_ctx_timing_read); band_size 0: no cell lies in the band and every score is 0 (dtw.rs:64-75); an empty
-// bank: no stream has a wakeword, every row is zero
-bool score_bank(Ctx *c, const Bank &bk, BankScore &q) {
-    if (q.S == 0 || q.win_pitch == 0) return true;
-    if (q.band == 0 || bk.dev.W == 0) {
-        if (!hip_ok(hipMemsetAsync(q.agg, 0, q.S * q.win_pitch * sizeof(float), c->stream), "hipMemsetAsync")) return false;
-        return !q.avg || hip_ok(hipMemsetAsync(q.avg, 0, q.S * q.win_pitch * sizeof(float), c->stream), "hipMemsetAsync");
-    }
-    const DtwWork wk = c->dtw_work();
-    q.fix = wk.fix;
-    dtw_mark(wk, kDtwRanBank);
-    return timed(c, kKernelDtw, "dtw_bank_kernel", [&] { return launch_dtw_bank(c->stream, bk.dev, q); });
-}
-
-// the same for a call over sets (dtw_set_kernel); zero rows for band_size 0 and an empty bank, proposals "nobody" (-1)
-bool score_bank_sets(Ctx *c, const Bank &bk, BankSetScore &q) {
-    if (q.S == 0 || q.win_pitch == 0) return true;
-    if (q.band == 0 || bk.dev.W == 0) {
-        const size_t row = q.S * q.win_pitch * sizeof(float), slots = row * (size_t)q.set_size;
-        auto fill = [&](void *p, int v, size_t bytes) { return !p || hip_ok(hipMemsetAsync(p, v, bytes, c->stream), "hipMemsetAsync"); };
-        return fill(q.best, 0, row) && fill(q.best_avg, 0, row) && fill(q.best_ww, 0xff, row) && fill(q.slot_agg, 0, slots) && fill(q.slot_avg, 0, slots);
-    }
-    const DtwWork wk = c->dtw_work();
-    q.fix = wk.fix;
-    dtw_mark(wk, kDtwRanBankSets);
-    return timed(c, kKernelDtw, "dtw_set_kernel", [&] { return launch_dtw_set(c->stream, bk.dev, q); });
-}
 
 // W wakeword reference files in the flat layout of rp_wakeword_bank_new.  *K 0: the first file's mfcc_size is taken; every other file (all
 // of them, for a *K given) must have it.  Errors name the bank index first + w.
@@ -723,228 +600,6 @@ int rp_wakeword_bank_max_len(const rp_wakeword_bank *bank, long long wakeword) {
     if (wakeword < 0) return b.dev.max_len;
     if (wakeword >= (long long)b.dev.W) { set_last_error("wakeword index outside the bank"); return -1; }
     return b.ww[(size_t)wakeword].max_len;
-}
-
-int rp_dtw_score_bank(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames, const rp_wakeword_bank *bank, const int32_t *stream_wakeword,
-                      float score_ref, int band_size, rp_score_mode score_mode, int with_avg, float *avg, float *agg, size_t win_pitch) {
-    return guarded([&]() -> int {
-        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
-        if (S && (!mfcc || !stream_wakeword || !agg)) { set_last_error("null argument"); return -1; }
-        Ctx *c = ctx->impl.get();
-        const Bank &bk = *bank->impl;
-        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!bank_band_ok(bk, band_size)) return -1;
-        Staged sg(c);
-        size_t max_n_win = 0;
-        bool ok = false;
-        const int32_t *di = stage_bank_indices(c, sg, bk, stream_wakeword, S, n_frames, &max_n_win, &ok);
-        if (!ok || !pitch_ok(win_pitch, max_n_win)) return -1;
-        if (S == 0 || win_pitch == 0) return sg.finish() ? 0 : -1;   // (the indices may be on their way to the device)
-        const size_t out_bytes = S * win_pitch * sizeof(float);
-        BankScore q;
-        q.mfcc = static_cast<const float *>(sg.in(mfcc, S * n_frames * bk.dev.K * sizeof(float), c->stage_in));
-        q.agg = static_cast<float *>(sg.out(agg, out_bytes, c->stage_out3));
-        q.avg = avg ? static_cast<float *>(sg.out(avg, out_bytes, c->stage_out2)) : nullptr;
-        if ((n_frames && !q.mfcc) || !q.agg || (avg && !q.avg)) return -1;
-        q.S = S; q.n_frames = n_frames; q.win_pitch = win_pitch; q.stream_wakeword = di; q.band = band_size; q.score_mode = (int)score_mode;
-        q.score_ref = score_ref; q.avg_mode = with_avg ? 1 : 0;
-        if (!score_bank(c, bk, q)) return -1;
-        return sg.back(agg, q.agg, out_bytes) && sg.back(avg, q.avg, out_bytes) && sg.finish() ? 0 : -1;
-    });
-}
-
-int rp_dtw_score_bank_sets(rp_ctx *ctx, const float *mfcc, size_t S, size_t n_frames, const rp_wakeword_bank *bank, const int32_t *stream_wakewords,
-                           int set_size, float score_ref, int band_size, rp_score_mode score_mode, int with_avg, float *avg, float *agg, size_t win_pitch) {
-    return guarded([&]() -> int {
-        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
-        if (!set_size_ok(set_size)) return -1;
-        if (S && (!mfcc || !stream_wakewords || !agg)) { set_last_error("null argument"); return -1; }
-        Ctx *c = ctx->impl.get();
-        const Bank &bk = *bank->impl;
-        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!bank_band_ok(bk, band_size)) return -1;
-        Staged sg(c);
-        size_t max_n_win = 0;
-        bool ok = false;
-        const int32_t *di = stage_set_indices(c, sg, bk, stream_wakewords, S, set_size, n_frames, &max_n_win, &ok);
-        if (!ok || !pitch_ok(win_pitch, max_n_win)) return -1;
-        if (S == 0 || win_pitch == 0) return sg.finish() ? 0 : -1;
-        const size_t out_bytes = S * (size_t)set_size * win_pitch * sizeof(float);
-        BankSetScore q;
-        q.mfcc = static_cast<const float *>(sg.in(mfcc, S * n_frames * bk.dev.K * sizeof(float), c->stage_in));
-        q.slot_agg = static_cast<float *>(sg.out(agg, out_bytes, c->stage_out3));
-        q.slot_avg = avg ? static_cast<float *>(sg.out(avg, out_bytes, c->stage_out2)) : nullptr;
-        if ((n_frames && !q.mfcc) || !q.slot_agg || (avg && !q.slot_avg)) return -1;
-        q.S = S; q.n_frames = n_frames; q.win_pitch = win_pitch; q.stream_wakewords = di; q.set_size = set_size; q.band = band_size;
-        q.score_mode = (int)score_mode; q.score_ref = score_ref; q.avg_mode = with_avg ? 1 : 0;
-        if (!score_bank_sets(c, bk, q)) return -1;
-        return sg.back(agg, q.slot_agg, out_bytes) && sg.back(avg, q.slot_avg, out_bytes) && sg.finish() ? 0 : -1;
-    });
-}
-
-// rp_frontend_batch with every stream's own gain window and reference level (gain_per_stream_kernel); the chunk RMS and apply kernels are
-// those of rp_frontend_batch -- they take per-chunk gains
-int rp_frontend_batch_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
-                           const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakeword,
-                           float *pcm_out, size_t out_stride, float *rms, float *gains) {
-    return guarded([&]() -> int {
-        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
-        if (S && !stream_wakeword) { set_last_error("null argument"); return -1; }
-        if (bank->impl->ctx != ctx->impl.get()) { set_last_error("the bank belongs to another context"); return -1; }
-        return frontend_batch(ctx->impl.get(), pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, 0, bank->impl.get(), stream_wakeword, pcm_out,
-                              out_stride, rms, gains);
-    });
-}
-
-int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
-                         const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config,
-                         rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, float *avg, size_t win_pitch) {
-    return guarded([&]() -> int {
-        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
-        if (!config || (S && (!pcm || !stream_wakeword || !det || !n_det))) { set_last_error("null argument"); return -1; }
-        Ctx *c = ctx->impl.get();
-        const Bank &bk = *bank->impl;
-        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!bank_band_ok(bk, (int)config->band_size)) return -1;
-        Staged sg(c);
-        const size_t nf = rp_mfcc_num_frames(n_samples);
-        size_t max_n_win = 0;
-        bool ok = false;
-        const int32_t *di = stage_bank_indices(c, sg, bk, stream_wakeword, S, nf, &max_n_win, &ok);
-        if (!ok) return -1;
-        const bool wants = agg || avg;
-        if (wants && !pitch_ok(win_pitch, max_n_win)) return -1;
-        const size_t pitch = wants ? win_pitch : std::max<size_t>(max_n_win, 1);   // the call's own rows when nothing is handed out
-        if (bk.dev.W == 0) {   // a Rustpotter without wakewords: no stream reports anything, every row is zero (the bank's mfcc_size is a placeholder)
-            if (!sample_format_ok(fmt)) return -1;
-            if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
-            if (max_det < 0) { set_last_error("max_det must be >= 0"); return -1; }
-            auto zero = [&](void *p, size_t bytes) {
-                if (!p || !bytes) return true;
-                if (sg.host) { std::memset(p, 0, bytes); return true; }
-                return hip_ok(hipMemsetAsync(p, 0, bytes, c->stream), "hipMemsetAsync");
-            };
-            return zero(det, S * (size_t)max_det * sizeof(rp_batch_detection)) && zero(n_det, S * sizeof(int32_t)) &&
-                   zero(agg, S * win_pitch * sizeof(float)) && zero(avg, S * win_pitch * sizeof(float)) && sg.finish() ? 0 : -1;
-        }
-        DetectFront f;
-        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, bk.dev.K, std::max(bk.dev.min_len, 1), det, n_det, max_det, &f)) return -1;
-        // caller-provided arrays are used directly when they are device pointers
-        const size_t out_bytes = S * pitch * sizeof(float);
-        float *dg = (agg && !sg.host) ? agg : nullptr, *da = (avg && !sg.host) ? avg : nullptr;
-        if (!dg) { if (!c->ws_agg.reserve(out_bytes + 16)) return -1; dg = c->ws_agg.as<float>(); }
-        if (!da) { if (!c->ws_avg.reserve(out_bytes + 16)) return -1; da = c->ws_avg.as<float>(); }
-        uint32_t *hot = nullptr;
-        if (S && pitch) {
-            BankScore q;
-            q.mfcc = f.dm; q.S = S; q.n_frames = nf; q.win_pitch = pitch; q.stream_wakeword = di; q.band = (int)config->band_size;
-            q.score_mode = (int)config->score_mode; q.score_ref = config->score_ref; q.avg_mode = 2;
-            q.gate = (!wants && !(c->flags & RP_CTX_FULL_SCORES)) ? 1 : 0;   // detect-only
-            q.threshold = config->threshold; q.avg_threshold = config->avg_threshold;
-            q.agg = dg; q.avg = da;
-            q.hot = hot = c->hot_flags(S);   // zero: the scan below puts every flag it reads back
-            if (!hot) return -1;
-            if (!score_bank(c, bk, q)) return -1;
-        }
-        float *dv = nullptr;
-        if (config->vad_mode != RP_VAD_NONE) {
-            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
-            dv = c->ws_vad.as<float>();
-            if (!hip_ok(launch_vad_value(c->stream, f.dm, S * nf, bk.dev.K, dv), "vad_value_kernel")) return -1;
-        }
-        const ScanConfig sc = scan_config(*config, 0, true);   // window length, thresholds and the avg test come from the bank, per stream
-        if (!timed(c, kKernelScan, "scan_bank_kernel", [&] {
-                return launch_scan_bank(c->stream, bk.dev, di, dg, da, pitch, dv, vad_mode_value(config->vad_mode), S, nf, sc, f.dd, f.dn, max_det, hot);
-            })) return -1;
-        if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
-        if (sg.host && agg && !sg.back(agg, dg, out_bytes)) return -1;
-        if (sg.host && avg && !sg.back(avg, da, out_bytes)) return -1;
-        return sg.finish() ? 0 : -1;
-    });
-}
-
-int rp_batch_detect_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
-                              const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size, const rp_detector_config *config,
-                              rp_batch_detection *det, int32_t *det_wakeword, int32_t *n_det, int max_det, float *agg, float *avg, size_t win_pitch) {
-    return guarded([&]() -> int {
-        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
-        if (!set_size_ok(set_size)) return -1;
-        if (!config || (S && (!pcm || !stream_wakewords || !det || !n_det))) { set_last_error("null argument"); return -1; }
-        Ctx *c = ctx->impl.get();
-        const Bank &bk = *bank->impl;
-        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!bank_band_ok(bk, (int)config->band_size)) return -1;
-        Staged sg(c);
-        const size_t nf = rp_mfcc_num_frames(n_samples);
-        size_t max_n_win = 0;
-        bool ok = false;
-        const int32_t *di = stage_set_indices(c, sg, bk, stream_wakewords, S, set_size, nf, &max_n_win, &ok);
-        if (!ok) return -1;
-        const bool wants = agg || avg;
-        if (wants && !pitch_ok(win_pitch, max_n_win)) return -1;
-        const size_t pitch = wants ? win_pitch : std::max<size_t>(max_n_win, 1);   // the call's own rows when nothing is handed out
-        const size_t col = S * (size_t)(max_det > 0 ? max_det : 0) * sizeof(int32_t), slot_bytes = S * (size_t)set_size * pitch * sizeof(float);
-        if (bk.dev.W == 0) {   // a Rustpotter without wakewords: no stream reports anything, every row is zero (the bank's mfcc_size is a placeholder)
-            if (!sample_format_ok(fmt)) return -1;
-            if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
-            if (max_det < 0) { set_last_error("max_det must be >= 0"); return -1; }
-            auto zero = [&](void *p, size_t bytes) {
-                if (!p || !bytes) return true;
-                if (sg.host) { std::memset(p, 0, bytes); return true; }
-                return hip_ok(hipMemsetAsync(p, 0, bytes, c->stream), "hipMemsetAsync");
-            };
-            return zero(det, S * (size_t)max_det * sizeof(rp_batch_detection)) && zero(n_det, S * sizeof(int32_t)) && zero(det_wakeword, col) &&
-                   zero(agg, slot_bytes) && zero(avg, slot_bytes) && sg.finish() ? 0 : -1;
-        }
-        DetectFront f;
-        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, bk.dev.K, std::max(bk.dev.min_len, 1), det, n_det, max_det, &f)) return -1;
-        int32_t *dw = det_wakeword ? static_cast<int32_t *>(sg.out(det_wakeword, col, c->stage_out3)) : nullptr;
-        if (det_wakeword && !dw) return -1;
-        // the proposals' three rows are the call's own; the per-slot rows exist only when asked for (caller's arrays when they are device pointers)
-        const size_t row_bytes = S * pitch * sizeof(float);
-        if (!c->ws_agg.reserve(row_bytes + 16) || !c->ws_avg.reserve(row_bytes + 16) || !c->ws_set_ww.reserve(row_bytes + 16)) return -1;
-        float *dg = nullptr, *da = nullptr;
-        if (wants) {
-            // (the averaged-template scores travel with the aggregates: a caller that asks for avg alone gets the kernel's aggregate rows too)
-            dg = (agg && !sg.host) ? agg : nullptr;
-            da = (avg && !sg.host) ? avg : nullptr;
-            if (!dg) { if (!c->ws_set_agg.reserve(slot_bytes + 16)) return -1; dg = c->ws_set_agg.as<float>(); }
-            if (avg && !da) { if (!c->ws_set_avg.reserve(slot_bytes + 16)) return -1; da = c->ws_set_avg.as<float>(); }
-        }
-        uint32_t *hot = nullptr;
-        if (S && pitch) {
-            BankSetScore q;
-            q.mfcc = f.dm; q.S = S; q.n_frames = nf; q.win_pitch = pitch; q.stream_wakewords = di; q.set_size = set_size; q.band = (int)config->band_size;
-            q.score_mode = (int)config->score_mode; q.score_ref = config->score_ref; q.avg_mode = 2;
-            q.gate = (!wants && !(c->flags & RP_CTX_FULL_SCORES)) ? 1 : 0;   // detect-only
-            q.threshold = config->threshold; q.avg_threshold = config->avg_threshold;
-            q.best = c->ws_agg.as<float>(); q.best_avg = c->ws_avg.as<float>(); q.best_ww = c->ws_set_ww.as<int32_t>();
-            q.slot_agg = dg; q.slot_avg = da;
-            q.hot = hot = c->hot_flags(S);   // zero: the scan below puts every flag it reads back
-            if (!hot) return -1;
-            if (!score_bank_sets(c, bk, q)) return -1;
-        }
-        float *dv = nullptr;
-        if (config->vad_mode != RP_VAD_NONE) {
-            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
-            dv = c->ws_vad.as<float>();
-            if (!hip_ok(launch_vad_value(c->stream, f.dm, S * nf, bk.dev.K, dv), "vad_value_kernel")) return -1;
-        }
-        const ScanConfig sc = scan_config(*config, 0, true);   // window length, thresholds and the avg test come from the bank, per stream
-        if (!timed(c, kKernelScan, "scan_set_kernel", [&] {
-                return launch_scan_set(c->stream, bk.dev, di, set_size, c->ws_agg.as<float>(), c->ws_avg.as<float>(), c->ws_set_ww.as<int32_t>(), pitch, dv,
-                                       vad_mode_value(config->vad_mode), S, nf, sc, f.dd, dw, f.dn, max_det, hot);
-            })) return -1;
-        if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
-        if (dw && !sg.back(det_wakeword, dw, col)) return -1;
-        if (sg.host && agg && !sg.back(agg, dg, slot_bytes)) return -1;
-        if (sg.host && avg && !sg.back(avg, da, slot_bytes)) return -1;
-        return sg.finish() ? 0 : -1;
-    });
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // rp_bank_put.hip -- the device side of a wakeword bank that changes (rp_wakeword_bank_put / _put_from_rpw / _enrol, rp_bank.cpp):
-// bank_put_kernel prepares template rows the way the host loop put_rows of Bank::create does, operation for operation (-ffp-contract=off:
+// bank_put_kernel prepares template rows the way the host's prepare_template_row (rp_ctx.cpp) does, operation for operation (-ffp-contract=off:
 // nothing is fused; the f64 square root and division are the correctly rounded ones), so that a wakeword put into a bank and the same
 // wakeword in a bank made by rp_wakeword_bank_new give the same bits; bank_move_kernel carries the live entries of a full pool into a
 // larger one.

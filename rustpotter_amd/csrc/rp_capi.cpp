@@ -55,10 +55,9 @@ int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size
     Staged sg(c);
     PerStreamGain per;
     if (bank) {  // a refused index: before anything is launched or written
-        size_t unused = 0;
-        bool ok = false;
-        per.stream_wakeword = stage_bank_indices(c, sg, *bank, stream_wakeword, S, 0, &unused, &ok);
-        if (!ok) return -1;
+        BankIndices bi;
+        if (!stage_bank_indices(c, sg, *bank, stream_wakeword, S, 0, 0, &bi)) return -1;
+        per.stream_wakeword = bi.dev;
         per.ww = bank->dev.ww; per.rms_level = bank->rms_level; per.W = bank->dev.W;
         per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
     }
@@ -284,7 +283,7 @@ static int widest_layer(const Model &m) {
 
 // The front of whole-stream detection: checks the PCM arguments, stages the PCM in and det / n_det out and writes the MFCC frames of
 // every stream to ws_mfcc (timed).  Windows are max_len frames long.
-// (DetectFront: rp_capi.h -- rp_bank.cpp shares this front)
+// (DetectFront: rp_capi.h -- rp_bank_calls.cpp shares this front)
 extern "C++" bool rp::detect_front(Ctx *c, Staged &sg, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, int K,
                                    int max_len, rp_batch_detection *det, int32_t *n_det, int max_det, DetectFront *f) {
     if (!pcm_args_ok(fmt, n_samples, pcm_stride)) return false;
@@ -302,19 +301,12 @@ extern "C++" bool rp::detect_front(Ctx *c, Staged &sg, const void *pcm, rp_sampl
     return timed(c, kKernelMfcc, "mfcc_kernel", [&] { return launch_mfcc_fmt(c->stream, *tb, dp, (int)fmt, S, n_samples, pcm_stride, 0, f->nf, f->nf, f->dm); });
 }
 
-// The tail of whole-stream detection: VAD values of the frames dm [S][nf][K] when vad_mode is on, then the timed scan -- launch_scan over
-// one wakeword's agg / avg (ww == nullptr), else launch_scan_multi over `ww` (dcol: each detection's wakeword or label)
+// detect_scan (rp_capi.h) with launch_scan over one wakeword's agg / avg (ww == nullptr), else launch_scan_multi over `ww` (dcol: each
+// detection's wakeword or label)
 static bool detect_scan(Ctx *c, const rp_detector_config &cfg, const float *dm, size_t S, size_t nf, int K, const ScanConfig &sc,
                         const float *dg, const float *da, uint32_t *hot, const ScanWakewords *ww, BatchDetection *dd, int32_t *dcol,
                         int32_t *dn, int max_det) {
-    float *dv = nullptr;
-    if (cfg.vad_mode != RP_VAD_NONE) {
-        if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return false;
-        dv = c->ws_vad.as<float>();
-        if (!hip_ok(launch_vad_value(c->stream, dm, S * nf, K, dv), "vad_value_kernel")) return false;
-    }
-    const float vm = vad_mode_value(cfg.vad_mode);
-    return timed(c, kKernelScan, "scan_kernel", [&] {
+    return detect_scan(c, cfg, dm, S, nf, K, "scan_kernel", [&](const float *dv, float vm) {
         return ww ? launch_scan_multi(c->stream, *ww, dv, vm, S, nf, sc, dd, dcol, dn, max_det)
                   : launch_scan(c->stream, dg, da, dv, vm, S, nf, sc, dd, dn, max_det, hot);
     });

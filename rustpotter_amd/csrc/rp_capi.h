@@ -1,4 +1,4 @@
-// rp_capi.h -- what the files of the extern "C" surface share (rp_capi.cpp, rp_stream_batch.cpp).  Not installed.
+// rp_capi.h -- what the files of the extern "C" surface share (rp_capi.cpp, rp_bank.cpp, rp_bank_calls.cpp, rp_model_bank.cpp, rp_stream_batch.cpp).  Not installed.
 #pragma once
 #include <new>
 
@@ -90,16 +90,40 @@ bool window_logits(Ctx *c, Model &m, const float *first, size_t S, size_t pitch,
 void band_pass_coefficients(const rp_band_pass_config &b, float q[5]);
 bool resample_rows(Ctx *c, const ResamplerDev &rs, const void *pcm, int fmt, int channels, size_t pcm_stride, const float *prev,
                    float *prev_out, size_t S, size_t n_chunks, DevBuf &xs_buf, size_t xs_chunks, float *out, size_t out_stride);
+// The tail of whole-stream detection: VAD values of the frames dm [S][nf][K] when vad_mode is on (dv, else null), then the timed scan
+// launch(dv, vad_mode_value); `what` names the scan kernel in an error
+template <class F> bool detect_scan(Ctx *c, const rp_detector_config &cfg, const float *dm, size_t S, size_t nf, int K, const char *what, F &&launch) {
+    float *dv = nullptr;
+    if (cfg.vad_mode != RP_VAD_NONE) {
+        if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return false;
+        dv = c->ws_vad.as<float>();
+        if (!hip_ok(launch_vad_value(c->stream, dm, S * nf, K, dv), "vad_value_kernel")) return false;
+    }
+    const float vm = vad_mode_value(cfg.vad_mode);
+    return timed(c, kKernelScan, what, [&] { return launch(dv, vm); });
+}
 // rp_bank.cpp
 bool bank_band_ok(const Bank &bk, int band_size);
-// the per-stream wakeword indices of a bank call, checked (host arrays) and on the device; see rp_bank.cpp
-const int32_t *stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, size_t n_frames, size_t *max_n_win, bool *ok);
-// wakeword sets, idx [n][set_size]: set_size within 1..RP_WAKEWORD_SET_MAX; every index of a HOST array within [-1, W), else an error that
-// names stream first + i and the slot; the indices of a whole-recording call checked and on the device as stage_bank_indices
-bool set_size_ok(int set_size);
-bool set_indices_ok(const Bank &bk, size_t first, size_t n, int set_size, const int32_t *idx);
-const int32_t *stage_set_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, size_t *max_n_win,
-                                 bool *ok);
+bool set_size_ok(int set_size);   // within 1 .. RP_WAKEWORD_SET_MAX
+// rp_bank_calls.cpp
+// after the null-handle test of a call over a bank: the bank's owner must be the call's context, whose device becomes current; null with the error set
+inline Ctx *bank_call_ctx(rp_ctx *ctx, const Ctx *owner) {
+    Ctx *c = ctx->impl.get();
+    if (owner != c) { set_last_error("the bank belongs to another context"); return nullptr; }
+    return hip_ok(hipSetDevice(c->device), "hipSetDevice") ? c : nullptr;
+}
+// Bank indices of n streams in a HOST array, idx [n] (set_size 0) or [n][set_size]: every one within [-1, W), else an error that names stream
+// first + i (and the slot) and the index, `what` being "wakeword index" or "model index"
+bool bank_indices_ok(int W, size_t first, size_t n, int set_size, const int32_t *idx, const char *what = "wakeword index");
+// The per-stream indices of a whole-recording call.  Host arrays are checked before anything is launched and copied to ws_bank_idx;
+// max_n_win is the window count of the longest window a stream of the call has (sets: of its longest live slot).  Device arrays are taken
+// as they are: the kernels treat an index outside [0, W) as "none", and max_n_win is the window count of the bank's shortest window.
+// S == 0 succeeds with dev null.
+struct BankIndices {
+    const int32_t *dev = nullptr;
+    size_t max_n_win = 0;
+};
+bool stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, BankIndices *bi);
 // rp_frontend_batch and rp_frontend_batch_bank (rp_capi.cpp): with `bank`, every stream takes its gain window and reference level from its own
 // wakeword bank[stream_wakeword[s]] and rms_level_ref / window_size are not read
 int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, const rp_filters_config *filters,

@@ -451,8 +451,28 @@ static void append_mfma_wide3_image(std::vector<uint16_t> &img, const DtwChunk &
             }
 }
 
-// Template rows are scaled to unit L2 norm in f64 and rounded once to f32; an all-zero
-// row stays zero so that its cosine similarity is 0 (src/mfcc/comparator.rs:43-47).
+// One template row src [K] -> unit [K], scaled to unit L2 norm in f64 and rounded once to f32, and raw [K] as given.  An all-zero row
+// stays zero so that its cosine similarity is 0 (src/mfcc/comparator.rs:43-47).  *ref_only is set (never cleared) for a row outside the
+// range in which the reference's sqrt(dot_a * dot_b) is what a unit-length row gives (TemplatesDev::ref_only).  false: a value is not
+// finite (the row is written all the same).  Templates::create, Bank::create and, on the device, bank_put_kernel must agree bit for bit:
+// nn is summed in index order, nf in a loop of its own, and -ffp-contract stays off.
+bool prepare_template_row(const float *src, int K, float *unit, float *raw, bool *ref_only) {
+    bool finite = true;
+    double nn = 0.0;
+    for (int k = 0; k < K; ++k) {
+        finite &= std::isfinite(src[k]);
+        nn += (double)src[k] * (double)src[k];
+    }
+    // the reference tests sqrt(dot_a*dot_b) == 0 in f32; a row whose f32 squared norm is 0 is a zero row
+    float nf = 0.f;
+    for (int k = 0; k < K; ++k) nf += src[k] * src[k];
+    const double inv = (nf > 0.f && nn > 0.0) ? 1.0 / std::sqrt(nn) : 0.0;
+    for (int k = 0; k < K; ++k) unit[k] = (float)((double)src[k] * inv);
+    for (int k = 0; k < K; ++k) raw[k] = src[k];
+    if (!(nf == 0.f || (nf >= kDtwNormLo && nf <= kDtwNormHiRow))) *ref_only = true;
+    return finite;
+}
+
 Templates *Templates::create(Ctx *ctx, int T, int K, const int *lens, const float *feats, int avg_len,
                              const float *avg) {
     if (T < 1 || K < 1) { set_last_error("Can not create an empty wakeword"); return nullptr; }  // wakeword_ref.rs:53
@@ -490,18 +510,8 @@ Templates *Templates::create(Ctx *ctx, int T, int K, const int *lens, const floa
         const float *src = t < T ? feats + off : avg;
         const int L = t < T ? lens[t] : avg_len;
         hl[t] = L;
-        for (int r = 0; r < L; ++r) {
-            double nn = 0.0;
-            for (int k = 0; k < K; ++k) nn += (double)src[(size_t)r * K + k] * (double)src[(size_t)r * K + k];
-            // the reference tests sqrt(dot_a*dot_b) == 0 in f32; a row whose f32 squared norm is 0 is a zero row
-            float nf = 0.f;
-            for (int k = 0; k < K; ++k) nf += src[(size_t)r * K + k] * src[(size_t)r * K + k];
-            double inv = (nf > 0.f && nn > 0.0) ? 1.0 / std::sqrt(nn) : 0.0;
-            for (int k = 0; k < K; ++k) unit[((size_t)t * Lpad + r) * K + k] = (float)((double)src[(size_t)r * K + k] * inv);
-            for (int k = 0; k < K; ++k) raw[((size_t)t * Lpad + r) * K + k] = src[(size_t)r * K + k];
-            // outside this range the reference's sqrt(dot_a * dot_b) is not what a unit-length row gives (TemplatesDev::ref_only)
-            if (!(nf == 0.f || (nf >= kDtwNormLo && nf <= kDtwNormHiRow))) ref_only = true;
-        }
+        for (int r = 0; r < L; ++r)   // (a value that is not finite is not refused here)
+            (void)prepare_template_row(src + (size_t)r * K, K, &unit[((size_t)t * Lpad + r) * K], &raw[((size_t)t * Lpad + r) * K], &ref_only);
         if (t < T) off += (size_t)L * K;
     }
     std::unique_ptr<Templates> tp(new Templates());

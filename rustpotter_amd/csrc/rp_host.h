@@ -186,6 +186,9 @@ struct Resampler {
     static Resampler *create(Ctx *ctx, size_t fs_in);
 };
 
+// one template row as the DTW kernels read it: unit [K] and raw [K]; see rp_ctx.cpp
+bool prepare_template_row(const float *src, int K, float *unit, float *raw, bool *ref_only);
+
 struct Templates {
     Ctx *ctx = nullptr;
     TemplatesDev dev;
@@ -194,7 +197,7 @@ struct Templates {
     ~Templates();
 };
 
-// A wakeword bank (rp_bank.cpp): W wakeword references uploaded once, scored per stream through an index (rp_dtw_bank.hip).  Borrows the context.
+// A wakeword bank (rp_bank.cpp; its calls: rp_bank_calls.cpp): W wakeword references uploaded once, scored per stream through an index (rp_dtw_bank.hip).  Borrows the context.
 struct Bank {
     Ctx *ctx = nullptr;
     BankDev dev;
@@ -231,7 +234,7 @@ struct Bank {
         float threshold = NAN, avg_threshold = NAN, rms_level = NAN;
         int max_len() const { int m = 0; for (int l : lens) m = l > m ? l : m; return m; }
     };
-    // the host's share of Bank::create's checks for wakewords first .. first + items.size() - 1; changes nothing
+    // what Bank::create checks in a wakeword, for wakewords first .. first + items.size() - 1, and `first` itself; changes nothing
     bool put_check(size_t first, const std::vector<PutItem> &items) const;
     // d_src: DEVICE rows [..][K] the items' src point into.  Prepares the rows in the pool tail (bank_put_kernel), reads the kernel's
     // verdict, and only then commits ww[] / rms_level; returns after the stream has drained.  A refusal leaves the bank as it was.
@@ -265,7 +268,7 @@ struct Model {
 // nullptr with the error set.  (rp_model_bank.cpp; the single-stream detector and the model bank load .rpw models through it)
 Model *model_from_data(Ctx *ctx, const WakewordModelData &model, int *n_layers, std::vector<int> *dims, int *none_index);
 
-// A model bank (rp_model_bank.cpp): W wakeword models copied into pools on the device, run per stream through an index
+// A model bank (rp_model_bank.cpp; its calls: rp_bank_calls.cpp): W wakeword models copied into pools on the device, run per stream through an index
 // (mlp_windows_bank_kernel in rp_mlp.hip).  Borrows the context; immutable.
 struct ModelBank {
     Ctx *ctx = nullptr;

@@ -1,7 +1,6 @@
-// rp_model_bank.cpp -- personal wakeword MODELS: a bank of W wakeword models resident on the device and whole-recording calls in which stream
-// s runs ITS model (rp_model_bank_*, rp_mlp_forward_windows_bank, rp_batch_detect_model_bank; kernels: mlp_windows_bank_kernel,
-// window_means_bank_kernel, nn_score_bank_kernel in rp_mlp.hip, scan_bank_kernel in rp_scan.hip).  The model counterpart of rp_bank.cpp.
-// DESIGN.md section 4.4.
+// rp_model_bank.cpp -- personal wakeword MODELS: a bank of W wakeword models resident on the device (rp_model_bank_*): model_from_data,
+// ModelBank::create and the accessors.  The calls in which stream s runs ITS model are in rp_bank_calls.cpp.  The model counterpart of
+// rp_bank.cpp.  DESIGN.md section 4.4.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -123,67 +122,6 @@ ModelBank *ModelBank::create(Ctx *ctx, size_t W, Model *const *models, int mfcc_
 
 namespace {
 
-// One call over a model bank: the per-stream indices checked (host arrays: before anything is launched) and on the device, the largest
-// window count a stream of the call can have, the launch shape.  With device arrays the kernels treat an index outside [0, W) as "no
-// model" and the shape covers every model of the bank.
-struct BankCall {
-    const int32_t *di = nullptr;
-    size_t max_n_win = 0;
-    ModelBankShape shape;
-};
-bool stage_model_indices(Ctx *c, Staged &sg, const ModelBank &bk, const int32_t *idx, size_t S, size_t n_frames, BankCall *q) {
-    const int W = bk.dev.W;
-    auto add = [&](const ModelBankEntry &e) {
-        if (n_frames >= (size_t)e.L) q->max_n_win = std::max(q->max_n_win, n_frames - (size_t)e.L + 1);
-        model_bank_shape_add(&q->shape, n_frames, e.L, e.tail_floats);
-    };
-    if (!sg.host) {
-        for (const ModelBankEntry &e : bk.e) add(e);
-        q->di = idx;
-        return true;
-    }
-    std::vector<char> used((size_t)W, 0);
-    for (size_t s = 0; s < S; ++s) {
-        if (idx[s] < -1 || idx[s] >= W) {
-            set_last_error("stream " + std::to_string(s) + ": model index " + std::to_string(idx[s]) + " is outside the bank (-1 .. " + std::to_string(W - 1) + ")");
-            return false;
-        }
-        if (idx[s] >= 0) used[(size_t)idx[s]] = 1;
-    }
-    for (int w = 0; w < W; ++w) if (used[(size_t)w]) add(bk.e[(size_t)w]);
-    if (S == 0) return true;
-    q->di = static_cast<const int32_t *>(sg.in(idx, S * sizeof(int32_t), c->ws_bank_idx));
-    return q->di != nullptr;
-}
-
-// RP_MLP_F32, or RP_MLP_BF16 computed as RP_MLP_F32 (as rp_mlp_forward_windows); the forms with a second pass over listed rows or with
-// the f32 matrix instructions are not built for a bank
-bool bank_precision_ok(int precision) {
-    if (!mlp_precision_ok(precision)) return false;
-    if (precision == RP_MLP_F32_FAST || precision == RP_MLP_F32_STRICT) {
-        set_last_error("model bank calls take RP_MLP_F32 (three bf16 parts; RP_MLP_BF16 computes the same): RP_MLP_F32_FAST and RP_MLP_F32_STRICT are not built for a bank");
-        return false;
-    }
-    return true;
-}
-
-bool zero_out(Ctx *c, Staged &sg, void *p, size_t bytes) {
-    if (!p || !bytes) return true;
-    if (sg.host) { std::memset(p, 0, bytes); return true; }
-    return hip_ok(hipMemsetAsync(p, 0, bytes, c->stream), "hipMemsetAsync");
-}
-
-// window means, then the forward inside the context's kKernelMlp bracket: dlog [S][pitch][label_pitch]
-bool bank_logits(Ctx *c, const ModelBank &bk, const BankCall &q, const float *dm, size_t S, size_t nf, size_t pitch, float *dlog) {
-    if (!c->ws_gain.reserve(S * pitch * 16 * sizeof(float) + 16)) return false;
-    float *mean = c->ws_gain.as<float>();
-    if (!hip_ok(launch_window_means_bank(c->stream, bk.dev, q.di, dm, S, nf, pitch, mean), "window_means_bank_kernel")) return false;
-    if (!timed(c, kKernelMlp, "mlp_windows_bank_kernel", [&] { return launch_mlp_windows_bank(c->stream, bk.dev, q.shape, q.di, dm, S, nf, mean, pitch, dlog); }))
-        return false;
-    c->last_mlp_kernel = "mlp_windows_bank_kernel<bf16x3 splits>";
-    return true;
-}
-
 int bank_handle(std::unique_ptr<ModelBank> b, rp_model_bank **out) {
     if (!b) return -1;
     rp_model_bank *h = new rp_model_bank();
@@ -252,90 +190,6 @@ int rp_model_bank_train_size(const rp_model_bank *bank, long long model) {
 int rp_model_bank_labels(const rp_model_bank *bank, long long model) {
     if (!bank || model >= (long long)bank->impl->dev.W) return -1;
     return model < 0 ? bank->impl->dev.label_pitch : bank->impl->e[(size_t)model].n_labels;
-}
-
-int rp_mlp_forward_windows_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, const float *mfcc, size_t S, size_t n_frames,
-                                int precision, float *logits, size_t win_pitch) {
-    return guarded([&]() -> int {
-        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
-        if (S && !stream_model) { set_last_error("null argument"); return -1; }
-        Ctx *c = ctx->impl.get();
-        const ModelBank &bk = *bank->impl;
-        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!bank_precision_ok(precision)) return -1;
-        Staged sg(c);
-        BankCall q;
-        if (!stage_model_indices(c, sg, bk, stream_model, S, n_frames, &q)) return -1;
-        if (win_pitch < q.max_n_win) {
-            set_last_error("win_pitch " + std::to_string(win_pitch) + " is smaller than the largest window count of the call, " + std::to_string(q.max_n_win));
-            return -1;
-        }
-        const size_t out_bytes = S * win_pitch * (size_t)bk.dev.label_pitch * sizeof(float);
-        if (out_bytes == 0) return sg.finish() ? 0 : -1;
-        if (!logits || (n_frames && !mfcc)) { set_last_error("null argument"); return -1; }
-        const float *dm = static_cast<const float *>(sg.in(mfcc, S * n_frames * 16 * sizeof(float), c->stage_in));
-        float *dl = static_cast<float *>(sg.out(logits, out_bytes, c->stage_out));
-        if ((n_frames && !dm) || !dl) return -1;
-        if (!bank_logits(c, bk, q, dm, S, n_frames, win_pitch, dl)) return -1;
-        return sg.back(logits, dl, out_bytes) && sg.finish() ? 0 : -1;
-    });
-}
-
-int rp_batch_detect_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
-                               const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, int precision,
-                               rp_batch_detection *det, int32_t *det_label, int32_t *n_det, int max_det) {
-    return guarded([&]() -> int {
-        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
-        if (!config || (S && (!pcm || !stream_model || !det || !n_det))) { set_last_error("null argument"); return -1; }
-        Ctx *c = ctx->impl.get();
-        const ModelBank &bk = *bank->impl;
-        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
-        if (!bank_precision_ok(precision)) return -1;
-        if (max_det < 0) { set_last_error("max_det must be >= 0"); return -1; }
-        Staged sg(c);
-        const size_t nf = rp_mfcc_num_frames(n_samples);
-        BankCall q;
-        if (!stage_model_indices(c, sg, bk, stream_model, S, nf, &q)) return -1;
-        if (bk.dev.W == 0) {   // a Rustpotter without wakewords: no stream reports anything
-            if (!sample_format_ok(fmt)) return -1;
-            if (pcm_stride < n_samples) { set_last_error("pcm_stride smaller than n_samples"); return -1; }
-            return zero_out(c, sg, det, S * (size_t)max_det * sizeof(rp_batch_detection)) && zero_out(c, sg, n_det, S * sizeof(int32_t)) &&
-                   zero_out(c, sg, det_label, S * (size_t)max_det * sizeof(int32_t)) && sg.finish() ? 0 : -1;
-        }
-        DetectFront f;
-        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, 16, std::max(bk.min_L, 1), det, n_det, max_det, &f)) return -1;
-        int32_t *dl = det_label ? static_cast<int32_t *>(sg.out(det_label, S * (size_t)max_det * sizeof(int32_t), c->stage_out3)) : nullptr;
-        if (det_label && S && max_det && !dl) return -1;
-        const size_t pitch = std::max<size_t>(q.max_n_win, 1), rows = S * pitch;
-        if (!c->ws_ring.reserve(rows * (size_t)bk.dev.label_pitch * sizeof(float) + 16) || !c->ws_agg.reserve(rows * sizeof(float) + 16) ||
-            !c->ws_avg.reserve(rows * sizeof(float) + 16) || !c->ws_rms.reserve(rows * sizeof(int32_t) + 16)) return -1;
-        float *dlog = c->ws_ring.as<float>(), *dg = c->ws_agg.as<float>(), *da = c->ws_avg.as<float>();
-        int32_t *dlab = c->ws_rms.as<int32_t>();
-        uint32_t *hot = nullptr;
-        if (S) {
-            if (!bank_logits(c, bk, q, f.dm, S, nf, pitch, dlog)) return -1;
-            // nn_score_bank_kernel raises a flag per stream with a window that passed: the scan skips the others and puts the flags back
-            hot = c->hot_flags(S);
-            if (!hot) return -1;
-            if (!hip_ok(launch_nn_score_bank(c->stream, bk.dev, q.di, dlog, S, nf, pitch, config->score_ref * 10.f, config->avg_threshold != 0.f ? 1 : 0,
-                                             config->threshold, config->avg_threshold, dg, da, dlab, hot), "nn_score_bank_kernel")) return -1;
-        }
-        float *dv = nullptr;
-        if (config->vad_mode != RP_VAD_NONE) {
-            if (!c->ws_vad.reserve(S * nf * sizeof(float) + 16)) return -1;
-            dv = c->ws_vad.as<float>();
-            if (!hip_ok(launch_vad_value(c->stream, f.dm, S * nf, 16, dv), "vad_value_kernel")) return -1;
-        }
-        // window length (countdown L / 2) per stream from the bank's scan entries; their thresholds are -1: the gates were applied above
-        const ScanConfig sc = scan_config(*config, 0, true);
-        if (!timed(c, kKernelScan, "scan_bank_kernel", [&] {
-                return launch_scan_bank(c->stream, bk.scan, q.di, dg, da, pitch, dv, vad_mode_value(config->vad_mode), S, nf, sc, f.dd, f.dn, max_det, hot);
-            })) return -1;
-        if (dl && !hip_ok(launch_model_bank_labels(c->stream, f.dd, f.dn, dlab, S, pitch, max_det, dl), "model_bank_labels_kernel")) return -1;
-        return sg.back_detections(S, max_det, det, f.dd, n_det, f.dn, det_label, dl) && sg.finish() ? 0 : -1;
-    });
 }
 
 }  // extern "C"

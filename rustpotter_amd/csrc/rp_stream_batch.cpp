@@ -156,17 +156,11 @@ static int stream_batch_new(rp_ctx *ctx, size_t n_wakewords, const rp_wakeword_s
     });
 }
 
-// Wakeword indices of streams first .. first + n - 1 of a batch over a bank.  A host array (RP_CTX_HOST_POINTERS) is checked: an index outside
-// [-1, W) is an error that names the stream; a device array is taken as it is and the kernels treat such an index as -1, as the bank calls do.
-static bool bank_indices_ok(const Ctx *c, const Bank &bk, size_t first, size_t n, const int32_t *idx) {
-    if (!(c->flags & RP_CTX_HOST_POINTERS)) return true;
-    const int W = bk.dev.W;
-    for (size_t i = 0; i < n; ++i)
-        if (idx[i] < -1 || idx[i] >= W) {
-            set_last_error("stream " + std::to_string(first + i) + ": wakeword index " + std::to_string(idx[i]) + " is outside the bank (-1 .. " + std::to_string(W - 1) + ")");
-            return false;
-        }
-    return true;
+// Wakeword indices of streams first .. first + n - 1 of a batch over a bank (set_size 0: one index a stream).  A host array
+// (RP_CTX_HOST_POINTERS) is checked (bank_indices_ok); a device array is taken as it is and the kernels treat an index outside [0, W) as -1,
+// as the bank calls do.
+static bool batch_indices_ok(const Ctx *c, const Bank &bk, size_t first, size_t n, int set_size, const int32_t *idx) {
+    return !(c->flags & RP_CTX_HOST_POINTERS) || bank_indices_ok(bk.dev.W, first, n, set_size, idx);
 }
 // ... -> the batch's own device copy (a sets batch: rows of set_size indices)
 static bool bank_indices_put(rp_stream_batch *b, size_t first, size_t n, const int32_t *idx) {
@@ -450,14 +444,13 @@ static int stream_batch_new_bank(rp_ctx *ctx, const rp_wakeword_bank *bank, cons
         if (!config || !out || !stream_wakeword) { set_last_error("null argument"); return -1; }
         *out = nullptr;
         if (sets && !set_size_ok(set_size)) return -1;
-        Ctx *c = ctx->impl.get();
         const Bank &bk = *bank->impl;
-        if (bk.ctx != c) { set_last_error("the bank belongs to another context"); return -1; }
-        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        Ctx *c = bank_call_ctx(ctx, bk.ctx);
+        if (!c) return -1;
         if (S == 0 || max_chunks_per_call == 0) { set_last_error(name + ": S and max_chunks_per_call must be >= 1"); return -1; }
         if (!bank_band_ok(bk, (int)config->band_size)) return -1;
         // before anything is allocated
-        if (sets ? ((c->flags & RP_CTX_HOST_POINTERS) && !set_indices_ok(bk, 0, S, set_size, stream_wakeword)) : !bank_indices_ok(c, bk, 0, S, stream_wakeword)) return -1;
+        if (!batch_indices_ok(c, bk, 0, S, sets ? set_size : 0, stream_wakeword)) return -1;
         std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
         b->set_size = sets ? set_size : 0;
         b->c = c; b->bank = &bk; ++bk.live_batches; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
@@ -608,7 +601,7 @@ static int stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, s
         if (n == 0) return 0;
         if (!wakewords) { set_last_error("null argument"); return -1; }
         // a refused index leaves the batch as it was
-        if (sets ? ((c->flags & RP_CTX_HOST_POINTERS) && !set_indices_ok(*b->bank, first_stream, n, b->set_size, wakewords)) : !bank_indices_ok(c, *b->bank, first_stream, n, wakewords)) return -1;
+        if (!batch_indices_ok(c, *b->bank, first_stream, n, b->set_size, wakewords)) return -1;
         touched = true;
         if (!bank_indices_put(b, first_stream, n, wakewords)) return -1;
         return hip_ok(launch_stream_state_reset_range(c->stream, b->state.p, b->S, first_stream, n, (long long)b->fpf() * (long long)b->chunks_seen),
