@@ -2,7 +2,7 @@
 // rp_batch_detect_bank, rp_frontend_batch_bank; kernels: rp_dtw_bank.hip, scan_bank_kernel in rp_scan.hip), against its own SET of wakewords
 // (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets; rp_dtw_set.hip, rp_scan_set.hip), or is run by ITS model of a model bank
 // (rp_mlp_forward_windows_bank, rp_batch_detect_model_bank; mlp_windows_bank_kernel, window_means_bank_kernel, nn_score_bank_kernel in
-// rp_mlp.hip).  Every call reads: arguments, staged indices, the empty-bank answer, front, score, scan, copy back.  The banks themselves are
+// rp_mlp_windows.hip / rp_mlp.hip).  Every call reads: arguments, staged indices, the empty-bank answer, front, score, scan, copy back.  The banks themselves are
 // rp_bank.cpp and rp_model_bank.cpp; DESIGN.md sections 4.2 - 4.4.
 #include <algorithm>
 #include <cstring>

@@ -269,7 +269,7 @@ struct Model {
 Model *model_from_data(Ctx *ctx, const WakewordModelData &model, int *n_layers, std::vector<int> *dims, int *none_index);
 
 // A model bank (rp_model_bank.cpp; its calls: rp_bank_calls.cpp): W wakeword models copied into pools on the device, run per stream through an index
-// (mlp_windows_bank_kernel in rp_mlp.hip).  Borrows the context; immutable.
+// (mlp_windows_bank_kernel in rp_mlp_windows.hip).  Borrows the context; immutable.
 struct ModelBank {
     Ctx *ctx = nullptr;
     ModelBankDev dev;

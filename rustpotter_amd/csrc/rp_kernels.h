@@ -777,7 +777,7 @@ hipError_t launch_nn_score(hipStream_t st, const float *logits, size_t n_rows, i
                            int calc_avg, float threshold, float avg_threshold, float *agg, float *avg, int32_t *label,
                            uint32_t *hot = nullptr, size_t rows_per_stream = 0);  // hot: a flag per stream (zeroed by the caller) raised by every window that passed
 
-// ---- model bank (rp_model_bank.cpp; kernels in rp_mlp.hip): W wakeword models resident on the device, stream s runs its own model
+// ---- model bank (rp_model_bank.cpp; kernels in rp_mlp_windows.hip, scoring in rp_mlp.hip): W wakeword models resident on the device, stream s runs its own model
 // stream_model[s] (outside [0, W): none).  The bank holds copies of what mlp_windows_kernel's three-part form reads of a model, in pools:
 // the lane-ordered image MlpDev::wwin3, b1, wsum for mfcc_size 16 and the packed tail; a descriptor per model says where.
 struct ModelBankEntry {

@@ -1,7 +1,8 @@
 // rp_mlp.hip -- the wakeword model: forward (src/wakewords/nn/wakeword_nn.rs:101-163,305-389; mlp_layer_kernel,
-// mlp_mfma_kernel on the matrix cores, normalize_windows_kernel) and training (wakeword_model_train.rs:204-209).
+// mlp_mfma_kernel on the matrix cores, normalize_windows_batch_kernel), its route (mlp_route, mlp_forward), scoring and training
+// (wakeword_model_train.rs:204-209).  The staged-frame kernels are in rp_mlp_windows.hip, the streaming one in rp_mlp_stream.hip.
 // DESIGN.md §4.4.
-#include "rp_device.h"
+#include "rp_mlp_dev.h"
 #include "rp_host.h"
 
 namespace rp {
@@ -29,26 +30,7 @@ __global__ __launch_bounds__(64) void mlp_layer_kernel(const float *__restrict__
     out[b * on + o] = s;
 }
 
-__global__ __launch_bounds__(64) void normalize_windows_kernel(const float *__restrict__ mfcc, size_t first_win,
-                                                                size_t n_win, int L, int K, float *__restrict__ x) {
-    const size_t w = blockIdx.x;
-    const float *src = mfcc + (first_win + w) * K;
-    float *dst = x + w * (size_t)L * K;
-    for (int k = threadIdx.x; k < K; k += 64) {
-        float sum = 0.f;
-        for (int i = 0; i < L; ++i) sum += src[(size_t)i * K + k];
-        for (int i = 0; i < L; ++i) dst[(size_t)i * K + k] = src[(size_t)i * K + k] - sum / (float)L;
-    }
-}
-
-hipError_t launch_normalize_windows(hipStream_t st, const float *mfcc, size_t first_win, size_t n_win, int L, int K,
-                                    float *x) {
-    if (n_win == 0) return hipSuccess;
-    hipLaunchKernelGGL(normalize_windows_kernel, dim3((unsigned)n_win), dim3(64), 0, st, mfcc, first_win, n_win, L, K, x);
-    return hipGetLastError();
-}
-
-// the same for windows of many streams: row = s * n_win + w
+// MfccNormalizer::normalize of the windows of many streams, one window per block: row = s * n_win + w, rows first_row .. of the call
 __global__ __launch_bounds__(64) void normalize_windows_batch_kernel(const float *__restrict__ mfcc, size_t frame_pitch, size_t n_win,
                                                                       size_t first_row, int L, int K, float *__restrict__ x) {
     const size_t row = first_row + blockIdx.x;
@@ -68,6 +50,12 @@ hipError_t launch_normalize_windows_batch(hipStream_t st, const float *mfcc, siz
     if (n_rows > 0x7fffffffULL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(normalize_windows_batch_kernel, dim3((unsigned)n_rows), dim3(64), 0, st, mfcc, frame_pitch, n_win, first_row, L, K, x);
     return hipGetLastError();
+}
+
+// windows first_win .. first_win + n_win of ONE run of frames: a single stream of first_win + n_win windows
+hipError_t launch_normalize_windows(hipStream_t st, const float *mfcc, size_t first_win, size_t n_win, int L, int K,
+                                    float *x) {
+    return launch_normalize_windows_batch(st, mfcc, 0, first_win + n_win, first_win, n_win, L, K, x);
 }
 
 // calc_inverse_similarity, wakeword_nn.rs:161-163
@@ -184,13 +172,14 @@ hipError_t launch_nn_score(hipStream_t st, const float *logits, size_t n_rows, i
     return hipGetLastError();
 }
 
-static hipError_t launch_mlp(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
-                             float *const *Bv, float *scratch0, float *scratch1, float *out) {
+// mlp_layer_kernel layer after layer; layer l writes dst_of(l)
+template <class DstOf>
+static hipError_t launch_mlp_layers(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
+                                    float *const *Bv, DstOf dst_of) {
     if (B == 0) return hipSuccess;
     const float *cur = x;
-    float *bufs[2] = {scratch0, scratch1};
     for (int l = 0; l < n_layers; ++l) {
-        float *dst = (l + 1 == n_layers) ? out : bufs[l & 1];
+        float *dst = dst_of(l);
         dim3 grid((unsigned)B, (unsigned)((dims[l + 1] + 63) / 64));
         size_t lds = (size_t)dims[l] * sizeof(float);
         if (lds > 64 * 1024) return hipErrorInvalidValue;
@@ -203,27 +192,18 @@ static hipError_t launch_mlp(hipStream_t st, const float *x, size_t B, int n_lay
     return hipSuccess;
 }
 
+// the forward: hidden layers through the two scratch buffers in turn
+static hipError_t launch_mlp(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
+                             float *const *Bv, float *scratch0, float *scratch1, float *out) {
+    float *bufs[2] = {scratch0, scratch1};
+    return launch_mlp_layers(st, x, B, n_layers, dims, W, Bv, [&](int l) { return l + 1 == n_layers ? out : bufs[l & 1]; });
+}
+
 // ------------------------------------------------------------------ MLP training
 // WakewordModelTrain's loop (src/wakewords/nn/wakeword_model_train.rs:204-209): full-batch forward,
 // log_softmax + nll (mean over the batch), backward, plain SGD.  The matrices are tiny (tens of recordings x a few
-// thousand features): one thread per result element, reductions along the batch / the layer width in a loop.
-__global__ __launch_bounds__(64) void train_forward_kernel(const float *__restrict__ x, size_t B, int in, int on,
-                                                           const float *__restrict__ W, const float *__restrict__ bias, int relu,
-                                                           float *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *xr = reinterpret_cast<float *>(smem);
-    const size_t b = blockIdx.x;
-    const int o = blockIdx.y * 64 + threadIdx.x;
-    for (int i = threadIdx.x; i < in; i += 64) xr[i] = x[b * in + i];
-    __syncthreads();
-    if (o >= on) return;
-    const float *w = W + (size_t)o * in;
-    float s = 0.f;
-    for (int i = 0; i < in; ++i) s += xr[i] * w[i];
-    s += bias[o];
-    if (relu && s < 0.f) s = 0.f;
-    out[b * on + o] = s;
-}
+// thousand features): one thread per result element, reductions along the batch / the layer width in a loop.  The forward is
+// mlp_layer_kernel's, every layer's output kept (launch_train_forward).
 
 // per row: log_softmax (x - max - ln(sum exp(x - max))), loss_row = -log_sm[label], dlogits = (softmax - onehot) / B
 __global__ __launch_bounds__(64) void train_softmax_grad_kernel(const float *__restrict__ logits, const int32_t *__restrict__ labels,
@@ -274,19 +254,7 @@ __global__ __launch_bounds__(256) void train_update_kernel(const float *__restri
 
 hipError_t launch_train_forward(hipStream_t st, const float *x, size_t B, int n_layers, const int *dims, float *const *W,
                                 float *const *Bv, float *const *act) {
-    if (B == 0) return hipSuccess;
-    const float *cur = x;
-    for (int l = 0; l < n_layers; ++l) {
-        dim3 grid((unsigned)B, (unsigned)((dims[l + 1] + 63) / 64));
-        const size_t lds = (size_t)dims[l] * sizeof(float);
-        if (lds > 64 * 1024) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(train_forward_kernel, grid, dim3(64), lds, st, cur, B, dims[l], dims[l + 1], W[l], Bv[l],
-                           l + 1 < n_layers ? 1 : 0, act[l]);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        cur = act[l];
-    }
-    return hipSuccess;
+    return launch_mlp_layers(st, x, B, n_layers, dims, W, Bv, [&](int l) { return act[l]; });
 }
 
 // act[l] = output of layer l (post-ReLU for hidden layers, logits for the last); dz[l] same shapes
@@ -326,9 +294,6 @@ hipError_t launch_train_step(hipStream_t st, const float *x, const int32_t *labe
 //  bf16 variant: v_mfma_f32_16x16x32_bf16, inputs rounded to bf16 (RNE) in registers, f32 accumulate.
 // The tail layers (<= 130 x 32 weights) run per row from LDS.  HBM-bound by construction: 4*in bytes
 // per row against 2*in*N1 flops (12 480 B/row, ceiling 0.64 G rows/s at 8 TB/s).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 constexpr int kMlpWaves = 8;
 constexpr int kMlpRowsPerWave = 16;
 constexpr int kMlpKG = 128;  // k-group staged per step
@@ -507,16 +472,9 @@ __global__ __launch_bounds__(64 * kMlpWaves, 3) void mlp_mfma_kernel(
             for (int u = 0; u < NA / 2; ++u) {
                 const float4 lo = a[2 * u], hi = a[2 * u + 1];
                 const float xs[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                unsigned h0[4], h1[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float p = xs[2 * e], q = xs[2 * e + 1];
-                    rng = fmaxf(fmaxf(rng, fabsf(p)), fabsf(q));
-                    h0[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p, q));
-                    h1[e] = pk_f16_second(p - __uint_as_float(__float_as_uint(p) & 0xffffe000u), q - __uint_as_float(__float_as_uint(q) & 0xffffe000u));
-                }
-                const f16x8 av0 = __builtin_bit_cast(f16x8, (u32x4v){h0[0], h0[1], h0[2], h0[3]});
-                const f16x8 av1 = __builtin_bit_cast(f16x8, (u32x4v){h1[0], h1[1], h1[2], h1[3]});
+                u32x4 h0, h1;
+                mlp_split_f16x2(xs, h0, h1, rng);
+                const f16x8 av0 = __builtin_bit_cast(f16x8, h0), av1 = __builtin_bit_cast(f16x8, h1);
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
                     const f16x8 b0 = *reinterpret_cast<const f16x8 *>(wb + (16 * n + li) * PH + 32 * u + 8 * lk);
@@ -535,19 +493,9 @@ __global__ __launch_bounds__(64 * kMlpWaves, 3) void mlp_mfma_kernel(
             for (int u = 0; u < NA / 2; ++u) {
                 const float4 lo = a[2 * u], hi = a[2 * u + 1];
                 const float xs[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                unsigned h0[4], h1[4], h2[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float p = xs[2 * e], q = xs[2 * e + 1];
-                    const float rp = p - __uint_as_float(__float_as_uint(p) & 0xffff0000u), rq = q - __uint_as_float(__float_as_uint(q) & 0xffff0000u);
-                    h0[e] = __builtin_amdgcn_perm(__float_as_uint(q), __float_as_uint(p), 0x07060302u);
-                    h1[e] = __builtin_amdgcn_perm(__float_as_uint(rq), __float_as_uint(rp), 0x07060302u);
-                    h2[e] = __builtin_amdgcn_perm(__float_as_uint(rq - __uint_as_float(__float_as_uint(rq) & 0xffff0000u)),
-                                                  __float_as_uint(rp - __uint_as_float(__float_as_uint(rp) & 0xffff0000u)), 0x07060302u);
-                }
-                const bf16x8 av0 = __builtin_bit_cast(bf16x8, (u32x4v){h0[0], h0[1], h0[2], h0[3]});
-                const bf16x8 av1 = __builtin_bit_cast(bf16x8, (u32x4v){h1[0], h1[1], h1[2], h1[3]});
-                const bf16x8 av2 = __builtin_bit_cast(bf16x8, (u32x4v){h2[0], h2[1], h2[2], h2[3]});
+                u32x4 h0, h1, h2;
+                mlp_split_bf16x3(xs, h0, h1, h2);
+                const bf16x8 av0 = __builtin_bit_cast(bf16x8, h0), av1 = __builtin_bit_cast(bf16x8, h1), av2 = __builtin_bit_cast(bf16x8, h2);
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
                     const bf16x8 b0 = *reinterpret_cast<const bf16x8 *>(wb + (16 * n + li) * PH + 32 * u + 8 * lk);
@@ -612,32 +560,9 @@ __global__ __launch_bounds__(64 * kMlpWaves, 3) void mlp_mfma_kernel(
             rng = fmaxf(rng, __shfl_xor(rng, 32));
             if (ph == 0 && row_ok && !(rng <= 65504.f)) mlp_redo_append(redo, (uint32_t)orow, B);
         }
-        const float *hin = h1 + rr * (N1P + 1);
-        float *h2 = h2_all + (wave * kMlpRowsPerWave + rr) * h2w;
         const int dd[5] = {in, d1, d2, d3, d4};
-        const float *wp = tl;
-        int cur_in = d1;
-        float *dst = out + orow * (size_t)dd[n_layers];
-        if (n_layers == 1 && row_ok)
-            for (int o = ph; o < d1; o += 4) dst[o] = hin[o];
-        for (int layer = 1; layer < n_layers; ++layer) {
-            const int on = dd[layer + 1];
-            const bool last = layer + 1 == n_layers;
-            for (int o = ph; o < on; o += 4) {
-                const float *wr = wp + (size_t)o * cur_in;
-                float s0 = 0.f, s1 = 0.f;
-                int i = 0;
-                for (; i + 1 < cur_in; i += 2) { s0 = fmaf(hin[i], wr[i], s0); s1 = fmaf(hin[i + 1], wr[i + 1], s1); }
-                if (i < cur_in) s0 = fmaf(hin[i], wr[i], s0);
-                float sacc = (s0 + s1) + wp[(size_t)on * cur_in + o];
-                if (!last && sacc < 0.f) sacc = 0.f;
-                if (last) { if (row_ok) dst[o] = sacc; } else h2[o] = sacc;
-            }
-            wave_lds_sync();  // the hidden layer is complete before anyone reads it
-            wp += (size_t)on * cur_in + on;
-            cur_in = on;
-            hin = h2;  // n_layers <= 3: at most one hidden tail layer
-        }
+        mlp_tail_layers<4>(tl, n_layers, d1, d2, d3, d4, h1 + rr * (N1P + 1), h2_all + (wave * kMlpRowsPerWave + rr) * h2w, ph, row_ok,
+                           out + orow * (size_t)dd[n_layers], [](int i) { return i; }, [] { wave_lds_sync(); });
     }
     if (redo_list) {
         __syncthreads();
@@ -657,10 +582,7 @@ struct MlpRoute {
     // mlp_mfma_kernel (the call's kernel or its second pass): LDS bytes, the staged weight group(s) and an h2 row in floats
     size_t lds = 0, wbuf = 0;
     int h2w = 1;
-    // the window kernels: 32-window row tiles per workgroup (NT), 32-output tiles (NQ, the wide form), frame slots, workgroups per
-    // stream, LDS bytes
-    int tiles = 0, nq = 0, slots = 0;
-    size_t bps = 0, win_lds = 0;
+    WinRoute win;                // the staged-frame kernels (rp_mlp_dev.h)
     std::string report;          // what ran (Ctx::last_mlp_kernel); empty for the per-layer kernel, which leaves it as it is
 };
 
@@ -730,739 +652,6 @@ static hipError_t launch_mlp_mfma(hipStream_t st, const MlpDev &m, const MlpRout
     return hipErrorInvalidValue;
 }
 
-// per window the column means over its L frames, summed in frame order like MfccNormalizer::normalize
-// (src/mfcc/normalizer.rs:3-31); one lane per (window, coefficient), 64 consecutive windows of a stream per block
-__global__ __launch_bounds__(256) void window_means_kernel(const float *__restrict__ mfcc, size_t n_frames, size_t n_win, unsigned tiles,
-                                                           int L, int K, float *__restrict__ mean) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *fs = reinterpret_cast<float *>(smem);  // [64 + L - 1][K]
-    const size_t s = blockIdx.x / tiles;
-    const size_t w0 = (size_t)(blockIdx.x - s * tiles) * 64;
-    const size_t nw = n_win - w0 < 64 ? n_win - w0 : 64;
-    const float *src = mfcc + (s * n_frames + w0) * K;
-    const int nfr = (int)nw + L - 1;
-    // (eight loads in flight per wait in both loops; the kernel is bound by the LDS reads of the sums -- 64 x K x L per block, each
-    // window summed in frame order as MfccNormalizer::normalize does -- 0.22 ms for 4 096 streams x 202 windows either way)
-#pragma unroll 8
-    for (int i = threadIdx.x; i < nfr * K; i += 256) fs[i] = src[i];
-    __syncthreads();
-    // four coefficients per lane (K % 4 == 0, launch_window_means): 16-byte LDS reads move twice the bytes per LDS cycle of 4-byte ones
-    // and a lane's four sums are independent chains (round 4: 1.81 -> 1.02 ms for 32 768 streams x 202 windows)
-    const int K4 = K / 4;
-    for (int i = threadIdx.x; i < (int)nw * K4; i += 256) {
-        const int w = i / K4, q = i - w * K4;
-        f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-        const float *col = fs + w * K + 4 * q;
-#pragma unroll 8
-        for (int f = 0; f < L; ++f) sum += *reinterpret_cast<const f32x4 *>(col + f * K);   // sequential sums, as MfccNormalizer::normalize
-        const float n = (float)L;
-        *reinterpret_cast<f32x4 *>(mean + (s * n_win + w0 + w) * K + 4 * q) = f32x4{sum.x / n, sum.y / n, sum.z / n, sum.w / n};
-    }
-}
-
-hipError_t launch_window_means(hipStream_t st, const float *mfcc, size_t S, size_t n_frames, size_t n_win, int L, int K, float *mean) {
-    if (S == 0 || n_win == 0) return hipSuccess;
-    const size_t tiles = (n_win + 63) / 64, blocks = tiles * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const size_t lds = (size_t)(64 + L - 1) * K * sizeof(float);
-    if (lds > 64 * 1024 || K % 4 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(window_means_kernel, dim3((unsigned)blocks), dim3(256), lds, st, mfcc, n_frames, n_win, (unsigned)tiles, L, K, mean);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Layer 1 over ALL windows of a stream from one staging of its frames (round 4).  mlp_mfma_kernel in window mode reads every window's
-// 3 120 features through the vector cache and splits each of them into its two f16 parts again -- a frame belongs to L = 195 windows,
-// so the same split is done 195 times: 57 % of the SIMD cycles of that kernel are vector instructions, 24 % matrix ones (PMC, 32 768
-// streams: 7.6 ms), and every 64 rows stage the 400 KB of split weights again.  Here a workgroup owns NT <= 7 tiles of 32 consecutive
-// windows of ONE stream: their frames (32 NT + L - 1) are split once into LDS, part p / k-half h / frame in 16-byte slots (a wave's 32
-// rows read 32 consecutive slots: conflict-free), and window row w at k-step f (= frame f of the window: mfcc_size 16 is one
-// v_mfma_f32_32x32x16_f16 step) is simply slot w + f.  The four waves split the FRAMES of the window, not the rows: wave q runs
-// frames [q L/4, (q+1) L/4) for all NT tiles, so a weight fragment is fetched once per workgroup -- straight from the lane-ordered image
-// (MlpDev::wwin) into registers, four frames ahead -- and used NT times; there is no barrier inside the loop (the first version staged
-// weight groups through LDS for 2 tiles per wave: 39 barriers per workgroup, 52 % matrix-pipe occupancy, 4.9 ms).  The four partial
-// sums of a tile meet in LDS in a fixed order ((q0 + q1) + (q2 + q3)).  Same products as kMlpF16x2 (x0 w0 + x1 w0 + x0 w1), same mean
-// correction, bias, ReLU and tail layers as mlp_mfma_kernel; rows holding a frame beyond the f16 range are listed for the f32 pass.
-// Shapes: mfcc_size 16, layer 1 <= 32 wide, tail layers <= 32 wide, n_win >= 32.
-// BITS: the frames are staged minus the mean of the workgroup's middle window (below), so a window's logits depend on how its stream is cut
-// into workgroups -- which is a function of the stream's window count alone: the same stream gives the same bits alone, in any batch and
-// on every repetition (tests/test_gpu_model_pin.py), but NOT the bits of mlp_mfma_kernel, which live-stream calls with fewer than 32 new
-// windows per stream take (the row's own mean): those agree within the logit gate, 2e-6 on scores.
-constexpr int kWinWaves = 4, kWinTile = 32, kWinMaxTiles = 7, kWinAhead = 3;
-typedef float f32x16w __attribute__((ext_vector_type(16)));
-// P3 (round 6, RP_MLP_F32): the frames are staged as THREE bf16 parts (exact) and a frame step is six v_mfma_f32_32x32x16_bf16 per tile
-// (x_i w_j, i + j <= 2, smallest first) against the three-part weight image MlpDev::wwin3 -- f32-grade products, no f16 range, nothing listed;
-// three planes of frames and seven accumulator tiles take two waves per SIMD.  !P3: two f16 parts (RP_MLP_F32_FAST), as described above.
-// The kernel is a thin front of mlp_windows_body, which mlp_windows_bank_kernel (per-stream models) shares.
-
-// The cut of a stream's n_win windows into workgroups, the one rule of mlp_route (host) and mlp_windows_bank_kernel (device, per stream): as
-// few workgroups per stream as `cap` <= 7 tiles of 32 windows each allow, the tiles spread evenly over them.  A window's bits depend on
-// this cut (BITS above), so it exists once.
-struct WinCut { int tiles; unsigned bps; };   // tiles per workgroup, workgroups per stream
-__host__ __device__ inline WinCut mlp_windows_cut(size_t n_win, int cap = kWinMaxTiles) {
-    const size_t tiles = (n_win + kWinTile - 1) / kWinTile;
-    if (tiles == 0) return WinCut{0, 0u};
-    const size_t wgs = (tiles + cap - 1) / cap, per = (tiles + wgs - 1) / wgs;
-    return WinCut{(int)per, (unsigned)((n_win + per * kWinTile - 1) / (per * kWinTile))};
-}
-// frame slots of a workgroup of `tiles` tiles over windows of L frames
-__host__ __device__ inline int mlp_windows_slots(int tiles, int L) { return (tiles * kWinTile + L + 3) & ~3; }
-
-// What a workgroup of the window kernels works with.  The model: mlp_windows_kernel gets it as kernel arguments (every stream shares it),
-// mlp_windows_bank_kernel from the descriptor of its stream's model.
-struct WinModel {
-    int L;
-    const u32x4v *wimg;   // MlpDev::wwin3 (P3) / wwin
-    int n1p;              // rows of b1 / wsum
-    const float *b1, *wsum, *tail;
-    int tail_floats, n_layers, d1, d2, d3;
-};
-// Its share of one stream: windows w0 .. of the stream's n_win, nt_here <= NT tiles of them
-struct WinWork {
-    const float *src;     // frame w0 of the stream
-    const float *mean;    // the stream's window means [n_win][16]
-    float *out;           // the stream's logit rows, out_pitch floats apart
-    size_t out_pitch, w0, n_win;
-    int slots, nt_here;
-    uint32_t *redo;       // !P3: the list of rows for the f32 pass; a row's number is redo_row0 + its window, of redo_rows in the call
-    size_t redo_row0, redo_rows;
-};
-
-// The body of both kernels.  nt_here: the tiles this workgroup owns -- the constant NT in mlp_windows_kernel (every test on it folds away),
-// the stream's own count in mlp_windows_bank_kernel, whose NT is the largest of its call: tiles behind nt_here are skipped, wave-uniformly.
-template <int NT, bool P3>
-__device__ __forceinline__ void mlp_windows_body(const WinModel &m, const WinWork &k) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int L = m.L, slots = k.slots, nt_here = k.nt_here, n1p = m.n1p, tail_floats = m.tail_floats, n_layers = m.n_layers;
-    const int d1 = m.d1, d2 = m.d2, d3 = m.d3;
-    const u32x4v *__restrict__ wimg = m.wimg;
-    const float *__restrict__ b1 = m.b1, *__restrict__ wsum = m.wsum, *__restrict__ tail = m.tail, *__restrict__ mean = k.mean;
-    float *tl = reinterpret_cast<float *>(smem);                                   // tail weights
-    unsigned *flag = reinterpret_cast<unsigned *>(tl + ((tail_floats + 3) & ~3));   // [slots] frame holds a value beyond the f16 range
-    u32x4v *A = reinterpret_cast<u32x4v *>(flag + slots);                           // [2 parts][2 k-halves][slots]; later the partial sums
-    const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, lr = l & 31, lh = l >> 5;
-    const size_t w0 = k.w0;                                                             // first window of this workgroup
-    const size_t rows_here = k.n_win - w0 < (size_t)(nt_here * kWinTile) ? k.n_win - w0 : (size_t)(nt_here * kWinTile);
-    const int n_real = (int)rows_here + L - 1;                                          // frames w0 .. w0 + n_real - 1 exist
-    for (int i = tid; i < tail_floats; i += 64 * kWinWaves) tl[i] = tail[i];
-    // ---- frames -> the two f16 parts, once.  The window mean is taken out after layer 1 (W.(f - mu) = W.f - sum_k mu[k] wsum[k]); MFCC
-    // coefficients sit on offsets many times their spread, and summing W.f with the offsets inside costs the sum their size in f32
-    // rounding.  So the frames are staged minus c = the mean of the workgroup's middle window -- every window here overlaps or
-    // adjoins it, so mu - c is small -- and the correction uses mu - c: W.(f - mu) = W.(f - c) - sum_k (mu - c)[k] wsum[k].
-    const float *__restrict__ src = k.src;
-    const float4 *cmid = reinterpret_cast<const float4 *>(mean + (w0 + rows_here / 2) * 16);
-    {
-        // a thread's items are (frame i / 2, k-half i & 1 = tid & 1) for i = tid, tid + 256, ..: every load goes out before the first split
-        constexpr int MAXI = (2 * (kWinMaxTiles * kWinTile + 256) + 64 * kWinWaves - 1) / (64 * kWinWaves);
-        const int h = tid & 1;
-        const float4 cl = cmid[2 * h], ch = cmid[2 * h + 1];
-        float4 lo[MAXI], hi[MAXI];
-#pragma unroll
-        for (int v = 0; v < MAXI; ++v) {
-            const int i = tid + v * 64 * kWinWaves, fr = i >> 1;
-            if (i < 2 * slots && fr < n_real) {
-                lo[v] = *reinterpret_cast<const float4 *>(src + (size_t)fr * 16 + 8 * h);
-                hi[v] = *reinterpret_cast<const float4 *>(src + (size_t)fr * 16 + 8 * h + 4);
-            } else { lo[v] = cl; hi[v] = ch; }   // past the real frames: zero after the offset leaves
-        }
-#pragma unroll
-        for (int v = 0; v < MAXI; ++v) {
-            const int i = tid + v * 64 * kWinWaves, fr = i >> 1;
-            if (i < 2 * slots) {
-                const float xs[8] = {lo[v].x - cl.x, lo[v].y - cl.y, lo[v].z - cl.z, lo[v].w - cl.w, hi[v].x - ch.x, hi[v].y - ch.y, hi[v].z - ch.z, hi[v].w - ch.w};
-                u32x4v p0, p1, p2;
-                float rng = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a = xs[2 * e], b = xs[2 * e + 1];
-                    if (P3) {   // a = a0 + a1 + a2 exactly: a0 = a & 0xffff0000 (a bf16), r = a - a0, a1 = r & 0xffff0000, a2 = r - a1; a packed register = two upper halves
-                        const float ra = a - __uint_as_float(__float_as_uint(a) & 0xffff0000u), rb = b - __uint_as_float(__float_as_uint(b) & 0xffff0000u);
-                        p0[e] = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-                        p1[e] = __builtin_amdgcn_perm(__float_as_uint(rb), __float_as_uint(ra), 0x07060302u);
-                        p2[e] = __builtin_amdgcn_perm(__float_as_uint(rb - __uint_as_float(__float_as_uint(rb) & 0xffff0000u)),
-                                                      __float_as_uint(ra - __uint_as_float(__float_as_uint(ra) & 0xffff0000u)), 0x07060302u);
-                    } else {
-                        rng = fmaxf(fmaxf(rng, fabsf(a)), fabsf(b));
-                        p0[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b));
-                        p1[e] = pk_f16_second(a - __uint_as_float(__float_as_uint(a) & 0xffffe000u), b - __uint_as_float(__float_as_uint(b) & 0xffffe000u));
-                    }
-                }
-                A[(0 * 2 + h) * slots + fr] = p0;
-                A[(1 * 2 + h) * slots + fr] = p1;
-                if (P3) A[(2 * 2 + h) * slots + fr] = p2;
-                if (h == 0) flag[fr] = 0u;   // the two halves of a frame belong to neighbouring lanes of one wave: its LDS stores keep their order
-                if (!(rng <= 65504.f)) flag[fr] = 1u;
-            }
-        }
-    }
-    __syncthreads();
-    // ---- this wave's quarter of the frames, all NT tiles
-    const int Lq = (L + kWinWaves - 1) / kWinWaves, fb = wave * Lq, fe = fb + Lq < L ? fb + Lq : L;
-    f32x16w acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-    constexpr int NPART = P3 ? 3 : 2;
-    u32x4v wq0[kWinAhead], wq1[kWinAhead], wq2[P3 ? kWinAhead : 1];   // the weight fragments of the next kWinAhead frames: [frame][part][k-half][output] 16 bytes
-    auto wfetch = [&](int f, int j) __attribute__((always_inline)) {
-        const int fc = f < fe ? f : fe - 1;
-        wq0[j] = wimg[(((size_t)fc * NPART + 0) * 2 + lh) * 32 + lr];
-        wq1[j] = wimg[(((size_t)fc * NPART + 1) * 2 + lh) * 32 + lr];
-        if (P3) wq2[j] = wimg[(((size_t)fc * NPART + 2) * 2 + lh) * 32 + lr];
-    };
-    if (fb < fe) {
-#pragma unroll
-        for (int j = 0; j < kWinAhead; ++j) wfetch(fb + j, j);
-        const u32x4v *A0 = A + (0 * 2 + lh) * slots + lr, *A1 = A + (1 * 2 + lh) * slots + lr;
-        const u32x4v *A2 = A + ((P3 ? 2 : 0) * 2 + lh) * slots + lr;
-        (void)A2;
-        for (int f0 = fb; f0 < fe; f0 += kWinAhead) {
-#pragma unroll
-            for (int j = 0; j < kWinAhead; ++j) {
-                const int f = f0 + j;
-                if (f < fe) {   // wave-uniform
-                    if (P3) {   // six products per tile, smallest first; tiles in pairs so that consecutive matrix instructions do not wait on each other
-                        const bf16x8 c0 = __builtin_bit_cast(bf16x8, wq0[j]), c1 = __builtin_bit_cast(bf16x8, wq1[j]), c2 = __builtin_bit_cast(bf16x8, wq2[j]);
-                        wfetch(f + kWinAhead, j);
-#pragma unroll
-                        for (int t = 0; t < NT; t += 2) {
-                            if (t >= nt_here) break;   // wave-uniform
-                            const bool two = t + 1 < NT && t + 1 < nt_here;
-                            const bf16x8 x0 = __builtin_bit_cast(bf16x8, A0[t * kWinTile + f]), x1 = __builtin_bit_cast(bf16x8, A1[t * kWinTile + f]),
-                                         x2 = __builtin_bit_cast(bf16x8, A2[t * kWinTile + f]);
-                            bf16x8 y0 = x0, y1 = x1, y2 = x2;
-                            if (two) {
-                                y0 = __builtin_bit_cast(bf16x8, A0[(t + 1) * kWinTile + f]); y1 = __builtin_bit_cast(bf16x8, A1[(t + 1) * kWinTile + f]);
-                                y2 = __builtin_bit_cast(bf16x8, A2[(t + 1) * kWinTile + f]);
-                            }
-#define RP_WIN6(XA, XB, WB)                                                                                            \
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(XA, WB, acc[t], 0, 0, 0);                 \
-                            if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(XB, WB, acc[t + 1], 0, 0, 0);
-                            RP_WIN6(x0, y0, c2) RP_WIN6(x1, y1, c1) RP_WIN6(x2, y2, c0) RP_WIN6(x0, y0, c1) RP_WIN6(x1, y1, c0) RP_WIN6(x0, y0, c0)
-#undef RP_WIN6
-                        }
-                        continue;
-                    }
-                    const f16x8 b0 = __builtin_bit_cast(f16x8, wq0[j]), b1v = __builtin_bit_cast(f16x8, wq1[j]);
-                    wfetch(f + kWinAhead, j);
-                    // tiles in pairs: the two parts of two tiles live at a time (all NT at once cost 8 NT registers and the third wave
-                    // per SIMD), and the three products of a tile are one other matrix instruction apart
-#pragma unroll
-                    for (int t = 0; t < NT; t += 2) {
-                        if (t >= nt_here) break;   // wave-uniform
-                        const bool two = t + 1 < NT && t + 1 < nt_here;
-                        const f16x8 p0 = __builtin_bit_cast(f16x8, A0[t * kWinTile + f]), p1 = __builtin_bit_cast(f16x8, A1[t * kWinTile + f]);
-                        f16x8 q0 = p0, q1 = p1;
-                        if (two) { q0 = __builtin_bit_cast(f16x8, A0[(t + 1) * kWinTile + f]); q1 = __builtin_bit_cast(f16x8, A1[(t + 1) * kWinTile + f]); }
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p0, b0, acc[t], 0, 0, 0);
-                        if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0, b0, acc[t + 1], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, b0, acc[t], 0, 0, 0);
-                        if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q1, b0, acc[t + 1], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p0, b1v, acc[t], 0, 0, 0);
-                        if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0, b1v, acc[t + 1], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();   // every wave is done with the frame planes: the region becomes the partial sums
-    // ---- ((q3 + q2) + q1) + q0 through one set of sums R[tile][e / 4][lane] (16 bytes each): a wave adds what is there to its own
-    // and puts the result back; one set, and h1 of a tile in that tile's own 4 KB, keep the workgroup at 48 KB = three per CU
-    f32x4 *R = reinterpret_cast<f32x4 *>(A);
-    auto put = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) if (t < nt_here) R[(t * 4 + e4) * 64 + l] = f32x4{acc[t][4 * e4], acc[t][4 * e4 + 1], acc[t][4 * e4 + 2], acc[t][4 * e4 + 3]};
-    };
-    auto add = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) {
-                if (t >= nt_here) continue;   // wave-uniform
-                const f32x4 v = R[(t * 4 + e4) * 64 + l];
-                acc[t][4 * e4] = v.x + acc[t][4 * e4]; acc[t][4 * e4 + 1] = v.y + acc[t][4 * e4 + 1];
-                acc[t][4 * e4 + 2] = v.z + acc[t][4 * e4 + 2]; acc[t][4 * e4 + 3] = v.w + acc[t][4 * e4 + 3];
-            }
-    };
-    if (wave == 3) put();
-    __syncthreads();
-    if (wave == 2) { add(); put(); }
-    __syncthreads();
-    if (wave == 1) { add(); put(); }
-    __syncthreads();
-    if (wave == 0) { add(); put(); }
-    __syncthreads();
-    // ---- bias, mean correction, ReLU, tail layers: tile t by wave t % 4.  h1 [32][32] takes the place of the tile's sums, h2 [32][32] of
-    // the wave sits behind the sums; column i of row r lives at (i + r) % 32: a lane walking its own row and the 32 lanes writing one
-    // row both touch 32 different banks
-    float *h2 = reinterpret_cast<float *>(R + NT * 4 * 64) + wave * 32 * 32;
-    const bool relu1 = n_layers > 1;
-    float4 ws4[4], c4[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        ws4[k] = lr < n1p ? *reinterpret_cast<const float4 *>(wsum + (size_t)lr * 16 + 4 * k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        c4[k] = cmid[k];
-    }
-    const float bias1 = lr < n1p ? b1[lr] : 0.f;
-    for (int t = wave; t < NT; t += kWinWaves) {
-        const size_t wrow0 = (size_t)t * kWinTile;   // first row of the tile inside the workgroup
-        if (wrow0 >= rows_here) break;                // wave-uniform
-        float *h1 = reinterpret_cast<float *>(R + t * 4 * 64);
-        f32x4 sums[4];
-#pragma unroll
-        for (int e4 = 0; e4 < 4; ++e4) sums[e4] = R[(t * 4 + e4) * 64 + l];
-        wave_lds_sync();
-        // C/D layout of the 32x32 tile: lane (column lr, half lh) holds rows 8 * (e / 4) + 4 * lh + e % 4
-#pragma unroll
-        for (int e4 = 0; e4 < 4; ++e4) {
-#pragma unroll
-            for (int ee = 0; ee < 4; ++ee) {
-                const int row = 8 * e4 + 4 * lh + ee;
-                size_t rr = wrow0 + row;
-                if (rr >= rows_here) rr = rows_here - 1;
-                const float4 *mu = reinterpret_cast<const float4 *>(mean + (w0 + rr) * 16);
-                float corr = 0.f;   // - sum_k (mu[row][k] - c[k]) * wsum[o][k]
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float4 m4 = mu[k], w4 = ws4[k], c = c4[k];
-                    corr = fmaf(m4.x - c.x, w4.x, corr); corr = fmaf(m4.y - c.y, w4.y, corr); corr = fmaf(m4.z - c.z, w4.z, corr); corr = fmaf(m4.w - c.w, w4.w, corr);
-                }
-                float v = sums[e4][ee] - corr;
-                v += bias1;
-                if (relu1 && v < 0.f) v = 0.f;
-                h1[row * 32 + ((lr + row) & 31)] = v;
-            }
-        }
-        wave_lds_sync();
-        // tail layers: lane = (row lr, output phase lh), outputs strided by 2 over the phases; sums in mlp_mfma_kernel's order
-        {
-            const bool row_ok = wrow0 + lr < rows_here;
-            const size_t orow = w0 + wrow0 + lr;   // the window within its stream
-            if (!P3 && lh == 0 && row_ok) {   // a window holding a frame beyond the f16 range: listed for the f32 pass
-                unsigned far = 0u;
-                for (int f = 0; f < L; ++f) far |= flag[wrow0 + lr + f];
-                if (far) mlp_redo_append(k.redo, (uint32_t)(k.redo_row0 + orow), k.redo_rows);
-            }
-            const int dd[4] = {d1, d2, d3, 0};
-            const float *hin = h1 + lr * 32;
-            const float *wp = tl;
-            int cur_in = d1;
-            float *dst = k.out + orow * k.out_pitch;
-            if (n_layers == 1 && row_ok)
-                for (int o = lh; o < d1; o += 2) dst[o] = hin[(o + lr) & 31];
-            for (int layer = 1; layer < n_layers; ++layer) {
-                const int on = dd[layer];
-                const bool last = layer + 1 == n_layers;
-                for (int o = lh; o < on; o += 2) {
-                    const float *wr = wp + (size_t)o * cur_in;
-                    float s0 = 0.f, s1 = 0.f;
-                    int i = 0;
-                    for (; i + 1 < cur_in; i += 2) { s0 = fmaf(hin[(i + lr) & 31], wr[i], s0); s1 = fmaf(hin[(i + 1 + lr) & 31], wr[i + 1], s1); }
-                    if (i < cur_in) s0 = fmaf(hin[(i + lr) & 31], wr[i], s0);
-                    float sacc = (s0 + s1) + wp[(size_t)on * cur_in + o];
-                    if (!last && sacc < 0.f) sacc = 0.f;
-                    if (last) { if (row_ok) dst[o] = sacc; } else h2[lr * 32 + ((o + lr) & 31)] = sacc;
-                }
-                wave_lds_sync();
-                wp += (size_t)on * cur_in + on;
-                cur_in = on;
-                hin = h2 + lr * 32;
-            }
-        }
-        wave_lds_sync();
-    }
-}
-
-template <int NT, bool P3>
-__global__ __launch_bounds__(64 * kWinWaves, P3 ? 2 : 3) void mlp_windows_kernel(
-    const float *__restrict__ mfcc, size_t frame_pitch, size_t n_win, int L, unsigned blocks_per_stream, const u32x4v *__restrict__ wimg, int slots,
-    int n1p, const float *__restrict__ b1, const float *__restrict__ mean, const float *__restrict__ wsum, const float *__restrict__ tail,
-    int tail_floats, int n_layers, int d1, int d2, int d3, float *__restrict__ out, uint32_t *redo) {
-    const size_t s = blockIdx.x / blocks_per_stream;
-    const size_t w0 = (size_t)(blockIdx.x - s * blocks_per_stream) * (NT * kWinTile);
-    const size_t nl = (size_t)(n_layers == 1 ? d1 : n_layers == 2 ? d2 : d3);
-    const WinModel m{L, wimg, n1p, b1, wsum, tail, tail_floats, n_layers, d1, d2, d3};
-    const WinWork k{mfcc + (s * frame_pitch + w0) * 16, mean + s * n_win * 16, out + s * n_win * nl, nl, w0, n_win, slots, NT,
-                    redo, s * n_win, (size_t)(gridDim.x / blocks_per_stream) * n_win};
-    mlp_windows_body<NT, P3>(m, k);
-}
-
-// The same for layer 1 wider than 32 (the Medium and Large model types: 65 / 130 outputs for 195 frames): NQ = 2 .. 5 waves, wave q owns
-// the 32-output tile q for all NT row tiles and ALL frames of the window (its own slice of the weight image, four frames ahead, used NT
-// times) -- no partial sums to add up; the tiles then meet in LDS row tile by row tile ([32][32 NQ + 1] floats) for the tail layers, which
-// every lane of the workgroup shares (row, output phase).  mlp_mfma_kernel in window mode, which these shapes had until now: 5.6 ms
-// (Medium) / 13.5 ms (Large) per 8 192 streams.
-template <int NT, int NQ, bool P3>
-__global__ __launch_bounds__(64 * NQ, 2) void mlp_windows_wide_kernel(
-    const float *__restrict__ mfcc, size_t frame_pitch, size_t n_win, int L, unsigned blocks_per_stream, const u32x4v *__restrict__ wimg, int slots,
-    int n1p, const float *__restrict__ b1, const float *__restrict__ mean, const float *__restrict__ wsum, const float *__restrict__ tail,
-    int tail_floats, int n_layers, int d1, int d2, int d3, float *__restrict__ out, uint32_t *redo) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NTHR = 64 * NQ, P1 = 32 * NQ + 1;
-    float *tl = reinterpret_cast<float *>(smem);                                   // tail weights
-    unsigned *flag = reinterpret_cast<unsigned *>(tl + ((tail_floats + 3) & ~3));   // [slots] frame holds a value beyond the f16 range
-    u32x4v *A = reinterpret_cast<u32x4v *>(flag + slots);                           // [2 parts][2 k-halves][slots]; later h1 / h2 of a row tile
-    const int tid = threadIdx.x, q = tid >> 6, l = tid & 63, lr = l & 31, lh = l >> 5;
-    const size_t s = blockIdx.x / blocks_per_stream;
-    const size_t w0 = (size_t)(blockIdx.x - s * blocks_per_stream) * (NT * kWinTile);
-    const size_t rows_here = n_win - w0 < (size_t)(NT * kWinTile) ? n_win - w0 : (size_t)(NT * kWinTile);
-    const int n_real = (int)rows_here + L - 1;
-    for (int i = tid; i < tail_floats; i += NTHR) tl[i] = tail[i];
-    // ---- frames minus the middle window's mean -> the two f16 parts, once (as mlp_windows_kernel)
-    const float *src = mfcc + (s * frame_pitch + w0) * 16;
-    const float4 *cmid = reinterpret_cast<const float4 *>(mean + (s * n_win + w0 + rows_here / 2) * 16);
-    {
-        constexpr int MAXI = (2 * (kWinMaxTiles * kWinTile + 256) + NTHR - 1) / NTHR;
-        const int h = tid & 1;
-        const float4 cl = cmid[2 * h], ch = cmid[2 * h + 1];
-        float4 lo[MAXI], hi[MAXI];
-#pragma unroll
-        for (int v = 0; v < MAXI; ++v) {
-            const int i = tid + v * NTHR, fr = i >> 1;
-            if (i < 2 * slots && fr < n_real) {
-                lo[v] = *reinterpret_cast<const float4 *>(src + (size_t)fr * 16 + 8 * h);
-                hi[v] = *reinterpret_cast<const float4 *>(src + (size_t)fr * 16 + 8 * h + 4);
-            } else { lo[v] = cl; hi[v] = ch; }
-        }
-#pragma unroll
-        for (int v = 0; v < MAXI; ++v) {
-            const int i = tid + v * NTHR, fr = i >> 1;
-            if (i < 2 * slots) {
-                const float xs[8] = {lo[v].x - cl.x, lo[v].y - cl.y, lo[v].z - cl.z, lo[v].w - cl.w, hi[v].x - ch.x, hi[v].y - ch.y, hi[v].z - ch.z, hi[v].w - ch.w};
-                u32x4v p0, p1, p2;
-                float rng = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a = xs[2 * e], b = xs[2 * e + 1];
-                    if (P3) {   // a = a0 + a1 + a2 exactly: a0 = a & 0xffff0000 (a bf16), r = a - a0, a1 = r & 0xffff0000, a2 = r - a1; a packed register = two upper halves
-                        const float ra = a - __uint_as_float(__float_as_uint(a) & 0xffff0000u), rb = b - __uint_as_float(__float_as_uint(b) & 0xffff0000u);
-                        p0[e] = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-                        p1[e] = __builtin_amdgcn_perm(__float_as_uint(rb), __float_as_uint(ra), 0x07060302u);
-                        p2[e] = __builtin_amdgcn_perm(__float_as_uint(rb - __uint_as_float(__float_as_uint(rb) & 0xffff0000u)),
-                                                      __float_as_uint(ra - __uint_as_float(__float_as_uint(ra) & 0xffff0000u)), 0x07060302u);
-                    } else {
-                        rng = fmaxf(fmaxf(rng, fabsf(a)), fabsf(b));
-                        p0[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b));
-                        p1[e] = pk_f16_second(a - __uint_as_float(__float_as_uint(a) & 0xffffe000u), b - __uint_as_float(__float_as_uint(b) & 0xffffe000u));
-                    }
-                }
-                A[(0 * 2 + h) * slots + fr] = p0;
-                A[(1 * 2 + h) * slots + fr] = p1;
-                if (P3) A[(2 * 2 + h) * slots + fr] = p2;
-                if (h == 0) flag[fr] = 0u;
-                if (!(rng <= 65504.f)) flag[fr] = 1u;
-            }
-        }
-    }
-    __syncthreads();
-    // ---- every frame, this wave's 32 outputs, all NT tiles
-    f32x16w acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-    constexpr int NPART = P3 ? 3 : 2;
-    u32x4v wq0[kWinAhead], wq1[kWinAhead], wq2[P3 ? kWinAhead : 1];
-    auto wfetch = [&](int f, int j) __attribute__((always_inline)) {
-        const int fc = f < L ? f : L - 1;
-        wq0[j] = wimg[((((size_t)fc * NQ + q) * NPART + 0) * 2 + lh) * 32 + lr];
-        wq1[j] = wimg[((((size_t)fc * NQ + q) * NPART + 1) * 2 + lh) * 32 + lr];
-        if (P3) wq2[j] = wimg[((((size_t)fc * NQ + q) * NPART + 2) * 2 + lh) * 32 + lr];
-    };
-    {
-#pragma unroll
-        for (int j = 0; j < kWinAhead; ++j) wfetch(j, j);
-        const u32x4v *A0 = A + (0 * 2 + lh) * slots + lr, *A1 = A + (1 * 2 + lh) * slots + lr;
-        const u32x4v *A2 = A + ((P3 ? 2 : 0) * 2 + lh) * slots + lr;
-        (void)A2;
-        for (int f0 = 0; f0 < L; f0 += kWinAhead) {
-#pragma unroll
-            for (int j = 0; j < kWinAhead; ++j) {
-                const int f = f0 + j;
-                if (f < L) {   // wave-uniform
-                    if (P3) {
-                        const bf16x8 c0 = __builtin_bit_cast(bf16x8, wq0[j]), c1 = __builtin_bit_cast(bf16x8, wq1[j]), c2 = __builtin_bit_cast(bf16x8, wq2[j]);
-                        wfetch(f + kWinAhead, j);
-#pragma unroll
-                        for (int t = 0; t < NT; t += 2) {
-                            const bool two = t + 1 < NT;
-                            const bf16x8 x0 = __builtin_bit_cast(bf16x8, A0[t * kWinTile + f]), x1 = __builtin_bit_cast(bf16x8, A1[t * kWinTile + f]),
-                                         x2 = __builtin_bit_cast(bf16x8, A2[t * kWinTile + f]);
-                            bf16x8 y0 = x0, y1 = x1, y2 = x2;
-                            if (two) {
-                                y0 = __builtin_bit_cast(bf16x8, A0[(t + 1) * kWinTile + f]); y1 = __builtin_bit_cast(bf16x8, A1[(t + 1) * kWinTile + f]);
-                                y2 = __builtin_bit_cast(bf16x8, A2[(t + 1) * kWinTile + f]);
-                            }
-#define RP_WIN6(XA, XB, WB)                                                                                            \
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(XA, WB, acc[t], 0, 0, 0);                 \
-                            if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(XB, WB, acc[t + 1], 0, 0, 0);
-                            RP_WIN6(x0, y0, c2) RP_WIN6(x1, y1, c1) RP_WIN6(x2, y2, c0) RP_WIN6(x0, y0, c1) RP_WIN6(x1, y1, c0) RP_WIN6(x0, y0, c0)
-#undef RP_WIN6
-                        }
-                        continue;
-                    }
-                    const f16x8 b0 = __builtin_bit_cast(f16x8, wq0[j]), b1v = __builtin_bit_cast(f16x8, wq1[j]);
-                    wfetch(f + kWinAhead, j);
-#pragma unroll
-                    for (int t = 0; t < NT; t += 2) {
-                        const bool two = t + 1 < NT;
-                        const f16x8 p0 = __builtin_bit_cast(f16x8, A0[t * kWinTile + f]), p1 = __builtin_bit_cast(f16x8, A1[t * kWinTile + f]);
-                        f16x8 q0 = p0, q1 = p1;
-                        if (two) { q0 = __builtin_bit_cast(f16x8, A0[(t + 1) * kWinTile + f]); q1 = __builtin_bit_cast(f16x8, A1[(t + 1) * kWinTile + f]); }
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p0, b0, acc[t], 0, 0, 0);
-                        if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0, b0, acc[t + 1], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, b0, acc[t], 0, 0, 0);
-                        if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q1, b0, acc[t + 1], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p0, b1v, acc[t], 0, 0, 0);
-                        if (two) acc[t + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0, b1v, acc[t + 1], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();   // every wave is done with the frame planes: the region becomes h1 [32][P1] and h2 [32][33] of one row tile at a time
-    float *h1 = reinterpret_cast<float *>(A), *h2 = h1 + 32 * P1;
-    const bool relu1 = n_layers > 1;
-    const int col = 32 * q + lr;
-    float4 ws4[4], c4[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        ws4[k] = col < n1p ? *reinterpret_cast<const float4 *>(wsum + (size_t)col * 16 + 4 * k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        c4[k] = cmid[k];
-    }
-    const float bias1 = col < n1p ? b1[col] : 0.f;
-    const int prow = tid & 31, ph = tid >> 5;   // tail layers: lane = (row, output phase), 2 NQ phases
-    constexpr int NPH = 2 * NQ;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const size_t wrow0 = (size_t)t * kWinTile;
-        if (wrow0 >= rows_here) break;   // workgroup-uniform
-        // C/D layout of the 32x32 tile: lane (column lr, half lh) holds rows 8 * (e / 4) + 4 * lh + e % 4
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int row = 8 * (e >> 2) + 4 * lh + (e & 3);
-            size_t rr = wrow0 + row;
-            if (rr >= rows_here) rr = rows_here - 1;
-            const float4 *mu = reinterpret_cast<const float4 *>(mean + (s * n_win + w0 + rr) * 16);
-            float corr = 0.f;   // - sum_k (mu[row][k] - c[k]) * wsum[o][k]
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 m4 = mu[k], w4 = ws4[k], c = c4[k];
-                corr = fmaf(m4.x - c.x, w4.x, corr); corr = fmaf(m4.y - c.y, w4.y, corr); corr = fmaf(m4.z - c.z, w4.z, corr); corr = fmaf(m4.w - c.w, w4.w, corr);
-            }
-            float v = acc[t][e] - corr;
-            v += bias1;
-            if (relu1 && v < 0.f) v = 0.f;
-            h1[row * P1 + col] = v;
-        }
-        __syncthreads();
-        const bool row_ok = wrow0 + prow < rows_here;
-        const size_t orow = s * n_win + w0 + wrow0 + prow;
-        if (!P3 && ph == 0 && row_ok) {   // a window holding a frame beyond the f16 range: listed for the f32 pass
-            unsigned far = 0u;
-            for (int f = 0; f < L; ++f) far |= flag[wrow0 + prow + f];
-            if (far) mlp_redo_append(redo, (uint32_t)orow, (size_t)(gridDim.x / blocks_per_stream) * n_win);
-        }
-        const int dd[4] = {d1, d2, d3, 0};
-        float *dst = out + orow * (size_t)dd[n_layers - 1];
-        const float *hin = h1 + prow * P1;
-        if (n_layers == 1) {
-            if (row_ok) for (int o = ph; o < d1; o += NPH) dst[o] = hin[o];
-        } else {
-            const float *wp = tl;
-            int cur_in = d1;
-            for (int layer = 1; layer < n_layers; ++layer) {
-                const int on = dd[layer];
-                const bool last = layer + 1 == n_layers;
-                for (int o = ph; o < on; o += NPH) {   // sums in mlp_mfma_kernel's order
-                    const float *wr = wp + (size_t)o * cur_in;
-                    float s0 = 0.f, s1 = 0.f;
-                    int i = 0;
-                    for (; i + 1 < cur_in; i += 2) { s0 = fmaf(hin[i], wr[i], s0); s1 = fmaf(hin[i + 1], wr[i + 1], s1); }
-                    if (i < cur_in) s0 = fmaf(hin[i], wr[i], s0);
-                    float sacc = (s0 + s1) + wp[(size_t)on * cur_in + o];
-                    if (!last && sacc < 0.f) sacc = 0.f;
-                    if (last) { if (row_ok) dst[o] = sacc; } else h2[prow * 33 + o] = sacc;
-                }
-                __syncthreads();
-                wp += (size_t)on * cur_in + on;
-                cur_in = on;
-                hin = h2 + prow * 33;
-            }
-        }
-        __syncthreads();   // h1 / h2 are free for the next row tile
-    }
-}
-
-// mlp_windows_kernel / mlp_windows_wide_kernel `kernel` with `waves` waves per workgroup
-template <class Kernel>
-static hipError_t launch_mlp_windows_kernel(Kernel kernel, int waves, hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q,
-                                            bool p3, uint32_t *redo) {
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(r.bps * q.S)), dim3(64 * waves), r.win_lds, st, q.x, q.frame_pitch, q.n_win, m.dims[0] / 16,
-                       (unsigned)r.bps, static_cast<const u32x4v *>(p3 ? m.wwin3 : m.wwin), r.slots, 16 * m.nt, m.b1, q.mean, q.wsum, m.tail,
-                       m.tail_floats, m.n_layers, m.dims[1], m.dims[2], m.dims[3], q.out, redo);
-    return hipGetLastError();
-}
-
-template <int NT, int NQ, bool P3>
-static hipError_t launch_mlp_windows_wide_nq(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
-    return launch_mlp_windows_kernel(mlp_windows_wide_kernel<NT, NQ, P3>, NQ, st, m, r, q, P3, redo);
-}
-
-template <int NT, bool P3>
-static hipError_t launch_mlp_windows_wide_nt(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
-    switch (r.nq) {
-    case 2: return launch_mlp_windows_wide_nq<NT, 2, P3>(st, m, r, q, redo);
-    case 3: return launch_mlp_windows_wide_nq<NT, 3, P3>(st, m, r, q, redo);
-    case 4: return launch_mlp_windows_wide_nq<NT, 4, P3>(st, m, r, q, redo);
-    case 5: return launch_mlp_windows_wide_nq<NT, 5, P3>(st, m, r, q, redo);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <bool P3>
-static hipError_t launch_mlp_windows_wide(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
-    if (r.tiles <= 2) return launch_mlp_windows_wide_nt<2, P3>(st, m, r, q, redo);
-    return launch_mlp_windows_wide_nt<4, P3>(st, m, r, q, redo);
-}
-
-template <int NT, bool P3>
-static hipError_t launch_mlp_windows_nt(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
-    return launch_mlp_windows_kernel(mlp_windows_kernel<NT, P3>, kWinWaves, st, m, r, q, P3, redo);
-}
-
-template <bool P3>
-static hipError_t launch_mlp_windows(hipStream_t st, const MlpDev &m, const MlpRoute &r, const MlpForward &q, uint32_t *redo) {
-    switch (r.tiles) {
-    case 1: return launch_mlp_windows_nt<1, P3>(st, m, r, q, redo);
-    case 2: return launch_mlp_windows_nt<2, P3>(st, m, r, q, redo);
-    case 3: return launch_mlp_windows_nt<3, P3>(st, m, r, q, redo);
-    case 4: return launch_mlp_windows_nt<4, P3>(st, m, r, q, redo);
-    case 5: return launch_mlp_windows_nt<5, P3>(st, m, r, q, redo);
-    case 6: return launch_mlp_windows_nt<6, P3>(st, m, r, q, redo);
-    case 7: return launch_mlp_windows_nt<7, P3>(st, m, r, q, redo);
-    }
-    return hipErrorInvalidValue;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Model bank (rp_model_bank.cpp): stream s runs its OWN model bank[stream_model[s]].  mlp_windows_kernel's three-part form with the model
-// read through the stream's index: a workgroup is (stream s, block b of ITS windows), cut by mlp_windows_cut from the stream's own window
-// count n_frames - L(s) + 1 -- the cut rp_mlp_forward_windows gives that stream alone, hence its bits.  The grid is S x the most
-// workgroups a stream of the call has, NT the most tiles a workgroup of the call owns; a workgroup behind its stream's own count leaves at
-// once, tiles behind its own are skipped.  The layer-1 image (3 KB a frame of L) comes from the model's place in the bank's pool: one
-// stream's workgroups share it through L2, streams of different models share nothing.  A stream with fewer than 32 windows is one partial
-// tile here (the shared-model route takes mlp_mfma_kernel there: 2e-6 on scores).
-template <int NT>
-__global__ __launch_bounds__(64 * kWinWaves, 2) void mlp_windows_bank_kernel(ModelBankDev bank, const int32_t *__restrict__ stream_model,
-                                                                             const float *__restrict__ mfcc, size_t n_frames, unsigned grid_bps,
-                                                                             const float *__restrict__ mean, size_t win_pitch,
-                                                                             float *__restrict__ out) {
-    const size_t s = blockIdx.x / grid_bps;
-    const unsigned b = blockIdx.x - (unsigned)s * grid_bps;
-    const int mi = stream_model[s];
-    if (mi < 0 || mi >= bank.W) return;   // no model: the row stays zero
-    const ModelBankEntry e = bank.e[mi];
-    if (n_frames < (size_t)e.L) return;
-    const size_t n_win = n_frames - (size_t)e.L + 1;
-    const WinCut cut = mlp_windows_cut(n_win);
-    if (b >= cut.bps || cut.tiles > NT) return;
-    const size_t w0 = (size_t)b * (size_t)(cut.tiles * kWinTile);
-    const WinModel m{e.L, static_cast<const u32x4v *>(bank.wimg) + e.wimg, e.n1p, bank.b1 + e.b1, bank.wsum + e.wsum, bank.tail + e.tail,
-                     e.tail_floats, e.n_layers, e.d1, e.d2, e.d3};
-    const WinWork k{mfcc + (s * n_frames + w0) * 16, mean + s * win_pitch * 16, out + s * win_pitch * (size_t)bank.label_pitch,
-                    (size_t)bank.label_pitch, w0, n_win, mlp_windows_slots(cut.tiles, e.L), cut.tiles, nullptr, 0, 0};
-    mlp_windows_body<NT, true>(m, k);
-}
-
-// LDS of a workgroup of `tiles` tiles in the three-part form: tail weights, a flag per frame slot, the three frame planes in two k-halves --
-// later the sums of nt tiles and h2 of the four waves (mlp_route's win_lds)
-static size_t mlp_windows_lds3(int tail_floats, int slots, int nt) {
-    return (size_t)((tail_floats + 3) & ~3) * 4 + (size_t)slots * 4 + std::max((size_t)6 * slots * 16, (size_t)nt * 4096 + (size_t)kWinWaves * 4096);
-}
-
-void model_bank_shape_add(ModelBankShape *sh, size_t n_frames, int L, int tail_floats) {
-    if (L < 1 || n_frames < (size_t)L) return;
-    const WinCut cut = mlp_windows_cut(n_frames - (size_t)L + 1);
-    sh->nt = std::max(sh->nt, cut.tiles);
-    sh->bps = std::max(sh->bps, cut.bps);
-    // sized with the call's NT below: the sums region grows with it
-    sh->lds = std::max(sh->lds, mlp_windows_lds3(tail_floats, mlp_windows_slots(cut.tiles, L), kWinMaxTiles));
-}
-
-template <int NT>
-static hipError_t launch_mlp_windows_bank_nt(hipStream_t st, const ModelBankDev &b, const ModelBankShape &sh, const int32_t *stream_model,
-                                             const float *mfcc, size_t S, size_t n_frames, const float *mean, size_t win_pitch, float *logits) {
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(mlp_windows_bank_kernel<NT>), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(mlp_windows_bank_kernel<NT>, dim3((unsigned)(S * sh.bps)), dim3(64 * kWinWaves), sh.lds, st, b, stream_model, mfcc, n_frames,
-                       sh.bps, mean, win_pitch, logits);
-    return hipGetLastError();
-}
-
-hipError_t launch_mlp_windows_bank(hipStream_t st, const ModelBankDev &b, const ModelBankShape &sh, const int32_t *stream_model, const float *mfcc,
-                                   size_t S, size_t n_frames, const float *mean, size_t win_pitch, float *logits) {
-    if (S == 0 || win_pitch == 0 || b.label_pitch == 0) return hipSuccess;
-    if (hipError_t e = hipMemsetAsync(logits, 0, S * win_pitch * (size_t)b.label_pitch * sizeof(float), st); e != hipSuccess) return e;
-    if (sh.nt == 0 || sh.bps == 0) return hipSuccess;   // no stream of the call has a window
-    if (S * sh.bps > 0x7fffffffULL || sh.lds > 160 * 1024) return hipErrorInvalidValue;
-    switch (sh.nt) {
-    case 1: return launch_mlp_windows_bank_nt<1>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
-    case 2: return launch_mlp_windows_bank_nt<2>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
-    case 3: return launch_mlp_windows_bank_nt<3>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
-    case 4: return launch_mlp_windows_bank_nt<4>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
-    case 5: return launch_mlp_windows_bank_nt<5>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
-    case 6: return launch_mlp_windows_bank_nt<6>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
-    case 7: return launch_mlp_windows_bank_nt<7>(st, b, sh, stream_model, mfcc, S, n_frames, mean, win_pitch, logits);
-    }
-    return hipErrorInvalidValue;
-}
-
-// window_means_kernel with every stream's own window length (mfcc_size 16): the same sums in frame order, hence the same bits; 64
-// consecutive windows of a stream per block, blocks behind a stream's windows leave
-__global__ __launch_bounds__(256) void window_means_bank_kernel(ModelBankDev b, const int32_t *__restrict__ stream_model, const float *__restrict__ mfcc,
-                                                                size_t n_frames, unsigned tiles, size_t win_pitch, float *__restrict__ mean) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *fs = reinterpret_cast<float *>(smem);  // [64 + L - 1][16]
-    const size_t s = blockIdx.x / tiles;
-    const size_t w0 = (size_t)(blockIdx.x - s * tiles) * 64;
-    const int mi = stream_model[s];
-    if (mi < 0 || mi >= b.W) return;
-    const int L = b.e[mi].L;
-    if (n_frames < (size_t)L) return;
-    const size_t n_win = n_frames - (size_t)L + 1;
-    if (w0 >= n_win) return;
-    const size_t nw = n_win - w0 < 64 ? n_win - w0 : 64;
-    const float *src = mfcc + (s * n_frames + w0) * 16;
-    const int nfr = (int)nw + L - 1;
-#pragma unroll 8
-    for (int i = threadIdx.x; i < nfr * 16; i += 256) fs[i] = src[i];
-    __syncthreads();
-    for (int i = threadIdx.x; i < (int)nw * 4; i += 256) {
-        const int w = i / 4, q = i - w * 4;
-        f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-        const float *col = fs + w * 16 + 4 * q;
-#pragma unroll 8
-        for (int f = 0; f < L; ++f) sum += *reinterpret_cast<const f32x4 *>(col + f * 16);   // sequential sums, as MfccNormalizer::normalize
-        const float n = (float)L;
-        *reinterpret_cast<f32x4 *>(mean + (s * win_pitch + w0 + w) * 16 + 4 * q) = f32x4{sum.x / n, sum.y / n, sum.z / n, sum.w / n};
-    }
-}
-
-hipError_t launch_window_means_bank(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *mfcc, size_t S, size_t n_frames,
-                                    size_t win_pitch, float *mean) {
-    if (S == 0 || win_pitch == 0 || b.W == 0) return hipSuccess;
-    const size_t tiles = (win_pitch + 63) / 64, blocks = tiles * S;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    const size_t lds = (size_t)(64 + 256 - 1) * 16 * sizeof(float);   // the bank's longest window: 256 frames
-    hipLaunchKernelGGL(window_means_bank_kernel, dim3((unsigned)blocks), dim3(256), lds, st, b, stream_model, mfcc, n_frames, (unsigned)tiles, win_pitch,
-                       mean);
-    return hipGetLastError();
-}
-
 static MlpRoute mlp_route(Model &md, const MlpForward &q) {
     MlpRoute r;
     if (!md.mfma_ok) return r;
@@ -1487,21 +676,18 @@ static MlpRoute mlp_route(Model &md, const MlpForward &q) {
         if (form == 1) {
             // tiles per workgroup: as few workgroups per stream as 7 tiles each allow, the tiles spread evenly over them
             static const int cap_env = std::getenv("RP_MLP_WIN_TILES") ? std::atoi(std::getenv("RP_MLP_WIN_TILES")) : kWinMaxTiles;   // experiments
-            r.tiles = mlp_windows_cut(q.n_win, cap_env >= 1 && cap_env <= kWinMaxTiles ? cap_env : kWinMaxTiles).tiles;
+            r.win.tiles = mlp_windows_cut(q.n_win, cap_env >= 1 && cap_env <= kWinMaxTiles ? cap_env : kWinMaxTiles).tiles;
         } else if (form == 2) {
             // 2 or 4 (measured per 8 192 streams x 202 windows, Medium / Large: 7 tiles 3.87 / 8.62 ms at two waves per SIMD, 4 tiles
             // 3.36 / 7.90 at four, 2 tiles 3.84 / 11.2 -- the weights once per 64 rows)
             const size_t wgs = (tiles + 3) / 4;
-            r.tiles = (tiles + wgs - 1) / wgs <= 2 ? 2 : 4;
-            r.nq = (m.dims[1] + 31) / 32;
+            r.win.tiles = (tiles + wgs - 1) / wgs <= 2 ? 2 : 4;
+            r.win.nq = (m.dims[1] + 31) / 32;
         }
         if (form) {
-            // frame planes (two or three parts x two k-halves); later the sums of the tiles (h1 of a tile in its place) + h2 of the
-            // four waves (the wide form: h1 of its NQ output tiles + h2)
-            r.bps = (q.n_win + r.tiles * kWinTile - 1) / (r.tiles * kWinTile);
-            r.slots = mlp_windows_slots(r.tiles, m.dims[0] / 16);
-            const size_t later = form == 1 ? (size_t)r.tiles * 4096 + (size_t)kWinWaves * 4096 : (size_t)32 * (32 * r.nq + 1) * 4 + (size_t)32 * 33 * 4;
-            r.win_lds = (size_t)((m.tail_floats + 3) & ~3) * 4 + (size_t)r.slots * 4 + std::max((size_t)(r.prec == kMlpBf16x3 ? 6 : 4) * r.slots * 16, later);
+            r.win.bps = (q.n_win + r.win.tiles * kWinTile - 1) / (r.win.tiles * kWinTile);
+            r.win.slots = mlp_windows_slots(r.win.tiles, m.dims[0] / 16);
+            r.win.lds = mlp_windows_lds(m.tail_floats, r.win.slots, r.win.tiles, r.prec == kMlpBf16x3 ? 3 : 2, r.win.nq);
         }
     } else {
         // RP_MLP_STREAM (a tuning knob of benchmarks and tests, not an arithmetic switch): 0 = mlp_mfma_kernel for every shape, 2 = the
@@ -1541,9 +727,8 @@ bool mlp_forward(Ctx &c, const MlpForward &q) {
         case kMlpStream: e = launch_mlp_stream(c.stream, m, r.plan, q.x, rows, r.prec, q.out, c.n_cu, redo); break;
         case kMlpWindows:
         case kMlpWindowsWide:
-            if (rows > 0xffffffffULL || r.bps * q.S > 0x7fffffffULL || r.win_lds > 160 * 1024) e = hipErrorInvalidValue;
-            else if (r.prec == kMlpBf16x3) e = r.kind == kMlpWindows ? launch_mlp_windows<true>(c.stream, m, r, q, redo) : launch_mlp_windows_wide<true>(c.stream, m, r, q, redo);
-            else e = r.kind == kMlpWindows ? launch_mlp_windows<false>(c.stream, m, r, q, redo) : launch_mlp_windows_wide<false>(c.stream, m, r, q, redo);
+            if (rows > 0xffffffffULL || r.win.bps * q.S > 0x7fffffffULL || r.win.lds > 160 * 1024) e = hipErrorInvalidValue;
+            else e = (r.kind == kMlpWindows ? launch_mlp_windows : launch_mlp_windows_wide)(c.stream, m, r.win, q, r.prec == kMlpBf16x3, redo);
             break;
         default: break;
         }

@@ -24,16 +24,13 @@
 // vmcnt discipline: every wait names the number of DMA instructions issued after the unit it waits for; the kernel's
 // only other vector-memory traffic is the stores of finished rows, and a store that is still pending only makes a wait
 // stricter.  s_barrier is the raw instruction (a __syncthreads() would drain the DMA queue).
-#include "rp_device.h"
+#include "rp_mlp_dev.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace rp {
 
-typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8s __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 #define RP_LDSP(p) ((__attribute__((address_space(3))) void *)(p))
 
 constexpr int kStreamWavesMax = 8;
@@ -178,66 +175,46 @@ __global__ __launch_bounds__(64 * kStreamWaves, 8 / kStreamWaves) void mlp_strea
 #pragma unroll
                 for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], wf.w[NT + n][e], acc[n], 0, 0, 0);
         } else if (PREC == kMlpF16x2) {   // pieces: [part][n], eight f16 each: w0 then w1
-            // x0 = rtz_f16(x), x1 = rtz_f16(x - x0): x0 as f32 is x with 13 mantissa bits cleared (below the f16 normal range the two
-            // differ by less than an f16 subnormal step, 6e-8)
+            // x0 = rtz_f16(x), x1 = rtz_f16(x - x0) (mlp_split_f16x2); a row beyond the f16 range is listed (epilogue) and computed again
+            // with the f32 matrix instructions (launch_mlp_stream)
             const float xs[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-            unsigned h0[4], h1[4];
+            u32x4 h0, h1;
+            mlp_split_f16x2(xs, h0, h1, rng);
+            const f16x8 av0 = __builtin_bit_cast(f16x8, h0), av1 = __builtin_bit_cast(f16x8, h1);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                // beyond the f16 range (features are MFCC coefficients, orders of magnitude below) a split would be silently wrong: such
-                // a row is listed (epilogue) and computed again with the f32 matrix instructions (launch_mlp_stream)
-                const float p = xs[2 * e], q = xs[2 * e + 1];
-                rng = fmaxf(fmaxf(rng, fabsf(p)), fabsf(q));
-                h0[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p, q));
-                h1[e] = pk_f16_second(p - __uint_as_float(__float_as_uint(p) & 0xffffe000u), q - __uint_as_float(__float_as_uint(q) & 0xffffe000u));
-            }
-            const f16x8s av0 = __builtin_bit_cast(f16x8s, (u32x4s){h0[0], h0[1], h0[2], h0[3]});
-            const f16x8s av1 = __builtin_bit_cast(f16x8s, (u32x4s){h1[0], h1[1], h1[2], h1[3]});
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av0, __builtin_bit_cast(f16x8, wf.w[n]), acc[n], 0, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av0, __builtin_bit_cast(f16x8s, wf.w[n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av1, __builtin_bit_cast(f16x8, wf.w[n]), acc[n], 0, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av1, __builtin_bit_cast(f16x8s, wf.w[n]), acc[n], 0, 0, 0);
-#pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av0, __builtin_bit_cast(f16x8s, wf.w[NT + n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av0, __builtin_bit_cast(f16x8, wf.w[NT + n]), acc[n], 0, 0, 0);
         } else if (PREC == kMlpBf16x3) {   // pieces: [part][n], eight bf16 each: w0, w1, w2 (w = w0 + w1 + w2 exactly, Model::stream_plan)
-            // f32-grade products (RP_MLP_F32): x = x0 + x1 + x2 exactly -- x0 = x & 0xffff0000 (a bf16), r = x - x0, x1 = r & 0xffff0000,
-            // x2 = r - x1 (at most 8 significant bits: a bf16 too) -- and the six partial products x_i w_j with i + j <= 2 (what is dropped
-            // is below 2^-22 of a product, 2^-25.7 rms; an f32 multiply rounds by up to 2^-24).  bf16 has the f32 exponent range: no row is
-            // out of range, nothing is listed for a second pass.
+            // f32-grade products (RP_MLP_F32): x = x0 + x1 + x2 exactly (mlp_split_bf16x3) and the six partial products x_i w_j with
+            // i + j <= 2 (what is dropped is below 2^-22 of a product, 2^-25.7 rms; an f32 multiply rounds by up to 2^-24).  bf16 has the
+            // f32 exponent range: no row is out of range, nothing is listed for a second pass.
             const float xs[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-            unsigned h0[4], h1[4], h2[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float p = xs[2 * e], q = xs[2 * e + 1];
-                const float rp = p - __uint_as_float(__float_as_uint(p) & 0xffff0000u), rq = q - __uint_as_float(__float_as_uint(q) & 0xffff0000u);
-                h0[e] = __builtin_amdgcn_perm(__float_as_uint(q), __float_as_uint(p), 0x07060302u);
-                h1[e] = __builtin_amdgcn_perm(__float_as_uint(rq), __float_as_uint(rp), 0x07060302u);
-                h2[e] = __builtin_amdgcn_perm(__float_as_uint(rq - __uint_as_float(__float_as_uint(rq) & 0xffff0000u)),
-                                              __float_as_uint(rp - __uint_as_float(__float_as_uint(rp) & 0xffff0000u)), 0x07060302u);
-            }
-            const bf16x8s av0 = __builtin_bit_cast(bf16x8s, (u32x4s){h0[0], h0[1], h0[2], h0[3]});
-            const bf16x8s av1 = __builtin_bit_cast(bf16x8s, (u32x4s){h1[0], h1[1], h1[2], h1[3]});
-            const bf16x8s av2 = __builtin_bit_cast(bf16x8s, (u32x4s){h2[0], h2[1], h2[2], h2[3]});
+            u32x4 h0, h1, h2;
+            mlp_split_bf16x3(xs, h0, h1, h2);
+            const bf16x8 av0 = __builtin_bit_cast(bf16x8, h0), av1 = __builtin_bit_cast(bf16x8, h1), av2 = __builtin_bit_cast(bf16x8, h2);
             // smallest terms first, so that they meet before the large ones take the accumulator's low bits (a second accumulator chain for
             // half of the six measured the same time, 0.154-0.156 ms at C5, and a larger worst-case error against f64: one chain it is)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av0, __builtin_bit_cast(bf16x8s, wf.w[2 * NT + n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av0, __builtin_bit_cast(bf16x8, wf.w[2 * NT + n]), acc[n], 0, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av1, __builtin_bit_cast(bf16x8s, wf.w[NT + n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av1, __builtin_bit_cast(bf16x8, wf.w[NT + n]), acc[n], 0, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av2, __builtin_bit_cast(bf16x8s, wf.w[n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av2, __builtin_bit_cast(bf16x8, wf.w[n]), acc[n], 0, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av0, __builtin_bit_cast(bf16x8s, wf.w[NT + n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av0, __builtin_bit_cast(bf16x8, wf.w[NT + n]), acc[n], 0, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av1, __builtin_bit_cast(bf16x8s, wf.w[n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av1, __builtin_bit_cast(bf16x8, wf.w[n]), acc[n], 0, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av0, __builtin_bit_cast(bf16x8s, wf.w[n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av0, __builtin_bit_cast(bf16x8, wf.w[n]), acc[n], 0, 0, 0);
         } else {                 // pieces: [n], eight bf16 each
-            bf16x8s av;
+            bf16x8 av;
             av[0] = (__bf16)a0.x; av[1] = (__bf16)a0.y; av[2] = (__bf16)a0.z; av[3] = (__bf16)a0.w;
             av[4] = (__bf16)a1.x; av[5] = (__bf16)a1.y; av[6] = (__bf16)a1.z; av[7] = (__bf16)a1.w;
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf16x8s, wf.w[n]), acc[n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf16x8, wf.w[n]), acc[n], 0, 0, 0);
         }
     };
 

@@ -190,6 +190,35 @@ def test_window_logits_with_a_frame_beyond_the_f16_range(ra, ctx):
     assert ctx.last_mlp_kernel() != ""
 
 
+@pytest.mark.parametrize("hidden,nf,hot_frame,kernel", [
+    ((32, 16), 89, 60, "mlp_windows_kernel"),        # 70 windows: one workgroup of three row tiles, the last one 6 rows
+    ((40, 20), 89, 60, "mlp_windows_wide_kernel"),   # three row tiles in one workgroup: the four-tile build, its fourth tile empty
+    ((65, 32), 52, 40, "mlp_windows_wide_kernel"),   # 33 windows: the two-tile build, the second tile one row; three output tiles
+])
+def test_window_logits_f16x2_listing_at_small_tile_counts(ra, ctx, hidden, nf, hot_frame, kernel):
+    """The two-part f16 form of the staged-frame kernels (RP_MLP_F32_FAST) at small tile counts, the wide kernel included, with one frame
+    of stream 1 holding 1e6: the windows that contain it are listed and come from the f32 matrix instructions -- finite, right, different
+    from the clean run -- and every other window keeps the clean run's bits.  The hot frame lies outside the workgroup's middle window
+    (window rows / 2 = 35 / 16: frames 35 .. 54 / 16 .. 35), whose mean every staged frame is taken relative to."""
+    K, L, S = 16, 20, 2
+    rng = np.random.default_rng(nf * 100 + hidden[0])
+    ws, bs = _window_model(rng, L, K, hidden, 2)
+    model = ra.Model(ctx, ws, bs)
+    mfcc = rng.standard_normal((S, nf, K)).astype(np.float32)
+    clean = ctx.mlp_forward_windows(mfcc, model, precision="f32_fast")
+    hot = mfcc.copy()
+    hot[1, hot_frame, 5] = 1e6
+    got = ctx.mlp_forward_windows(hot, model, precision="f32_fast")
+    assert ctx.last_mlp_kernel() == kernel + "<f16x2 splits>" + _LISTED
+    ref = _window_logits_oracle(hot, L, ws, bs).astype(np.float64)
+    assert got.shape == ref.shape and np.isfinite(got).all()
+    inside = np.zeros((S, nf - L + 1), bool)
+    inside[1, hot_frame - L + 1:hot_frame + 1] = True
+    assert got[~inside].tobytes() == clean[~inside].tobytes()
+    tol = 2e-5 * np.maximum(np.abs(ref), 1e6)
+    assert (np.abs(got - ref)[inside] <= tol[inside]).all() and not np.array_equal(got[inside], clean[inside])
+
+
 @pytest.mark.parametrize("K,L,hidden,nf", [(8, 120, (32, 16), 300), (12, 70, (20,), 160), (20, 50, (65, 32), 130), (4, 200, (13,), 260)])
 def test_window_logits_other_mfcc_sizes(ra, ctx, K, L, hidden, nf):
     """The same for mfcc sizes other than 16 (mlp_mfma_kernel with the rows read in place: the window's own mean leaves each feature as

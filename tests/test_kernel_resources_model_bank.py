@@ -1,4 +1,4 @@
-"""mlp_windows_bank_kernel (rustpotter_amd/csrc/rp_mlp.hip), the model bank's forward: every build <1..7> exists, spills nothing, uses no
+"""mlp_windows_bank_kernel (rustpotter_amd/csrc/rp_mlp_windows.hip), the model bank's forward: every build <1..7> exists, spills nothing, uses no
 scratch memory and keeps the two waves per SIMD the three-part form of mlp_windows_kernel is built for (three planes of frames and up to
 seven accumulator tiles).  It shares its body with mlp_windows_kernel; the model comes through the stream's descriptor and the tiles behind
 the stream's own are skipped by run-time tests -- an accumulator array the compiler indexes at run time would go to scratch memory, and
@@ -25,7 +25,7 @@ KERNELS = {
 @pytest.fixture(scope="module")
 def remarks():
     out = {}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), "rp_mlp.hip", "mlp_windows_bank_kernel"], capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), "rp_mlp_windows.hip", "mlp_windows_bank_kernel"], capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     for line in r.stdout.splitlines()[1:]:
