@@ -259,6 +259,10 @@ extern "C" {
                                          config: *const rp_detector_config, S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
     pub fn rp_stream_batch_set_wakeword_sets(b: *mut rp_stream_batch, first_stream: usize, n: usize, stream_wakewords: *const i32) -> c_int;
     pub fn rp_stream_batch_slot_scores(b: *mut rp_stream_batch, agg: *mut f32, avg: *mut f32) -> c_int;
+    pub fn rp_stream_batch_new_model_bank(ctx: *mut rp_ctx, bank: *const rp_model_bank, stream_model: *const i32, config: *const rp_detector_config,
+                                          S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
+    pub fn rp_stream_batch_set_models(b: *mut rp_stream_batch, first_stream: usize, n: usize, models: *const i32) -> c_int;
+    pub fn rp_stream_batch_logits(b: *mut rp_stream_batch, logits: *mut f32) -> c_int;
     pub fn rp_model_new(ctx: *mut rp_ctx, n_layers: c_int, dims: *const c_int, weights: *const *const f32, biases: *const *const f32,
                         out: *mut *mut rp_model) -> c_int;
     pub fn rp_model_free(m: *mut rp_model);
@@ -940,7 +944,9 @@ impl HipContext {
 /// (INTEGRATION.md §4).  Borrows the context and the templates, like the C handle does.
 pub struct StreamBatch<'a> { h: *mut rp_stream_batch, n_streams: usize, last_chunks: usize,
                             /// wakewords per stream of a `new_bank_sets` batch, 0 for every other batch; MFCC frames a stream gains per chunk (3, or 4 with 40 ms input frames)
-                            set_size: usize, frames_per_chunk: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
+                            set_size: usize, frames_per_chunk: usize,
+                            /// label pitch of the bank of a `new_model_bank` batch, 0 for every other batch
+                            label_pitch: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
 /// One wakeword of a detector that holds several (`Rustpotter::add_wakeword_ref` / `add_wakeword_model`, src/detector.rs:144-150)
 pub enum BatchWakeword<'a> {
     /// a reference with its own `threshold` / `avg_threshold` options (`WakewordRef::threshold`, `::avg_threshold`)
@@ -954,7 +960,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new(ctx.h, t.h, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// S detectors that each hold `wakewords` (references and / or models sharing `mfcc_size`): the best score of the wakewords
     /// whose own thresholds pass wins a frame (`run_wakeword_detectors`, src/detector.rs:433-447)
@@ -971,7 +977,7 @@ impl<'a> StreamBatch<'a> {
         }).collect();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_multi(ctx.h, specs.len(), specs.as_ptr(), mfcc_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Personal wakewords on live streams: stream `s` holds the one wakeword `bank[stream_wakeword[s]]` (-1: none) with its own window
     /// length and thresholds -- `batch_detect_bank` with the state carried between calls.  `process_multi` reports the bank index.
@@ -980,7 +986,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_bank(ctx.h, bank.h, stream_wakeword.as_ptr(), &c, stream_wakeword.len(), max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams: stream_wakeword.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams: stream_wakeword.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Connect / disconnect of device slots (a batch of `new_bank`): streams `first_stream ..` get new bank indices and are reset
     pub fn set_wakewords(&mut self, first_stream: usize, wakewords: &[i32]) -> Result<(), String> {
@@ -1001,7 +1007,7 @@ impl<'a> StreamBatch<'a> {
         let n_streams = stream_wakewords.len() / set_size;
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_bank_sets(ctx.h, bank.h, stream_wakewords.as_ptr(), set_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Re-target the streams `first_stream ..` of a `new_bank_sets` batch, one row of the batch's `set_size` indices per stream: remove-all
     /// plus add-in-order, each stream reset.  An error on any other batch.
@@ -1018,6 +1024,28 @@ impl<'a> StreamBatch<'a> {
         let (mut agg, mut avg) = (vec![0f32; n], vec![0f32; n]);
         status(unsafe { rp_stream_batch_slot_scores(self.h, agg.as_mut_ptr(), avg.as_mut_ptr()) })?;
         Ok((agg, avg))
+    }
+    /// Personal wakeword models on live streams: stream `s` runs its own model `bank[stream_model[s]]` (-1: none) -- `batch_detect_model_bank`
+    /// with the state carried between calls.  `process_multi` reports the model index and the label index of a detection's best window.
+    pub fn new_model_bank(ctx: &'a HipContext, bank: &'a ModelBank, stream_model: &[i32], config: &DetectorConfig, max_chunks_per_call: usize)
+                          -> Result<StreamBatch<'a>, String> {
+        let c: rp_detector_config = config.into();
+        let mut h = std::ptr::null_mut();
+        status(unsafe { rp_stream_batch_new_model_bank(ctx.h, bank.h, stream_model.as_ptr(), &c, stream_model.len(), max_chunks_per_call, &mut h) })?;
+        Ok(StreamBatch { h, n_streams: stream_model.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: bank.labels(), _ctx: ctx,
+                         _t: std::marker::PhantomData })
+    }
+    /// Connect / disconnect / retarget slots of a `new_model_bank` batch: streams `first_stream ..` get new model indices and are reset.
+    /// An error on any other batch.
+    pub fn set_models(&mut self, first_stream: usize, models: &[i32]) -> Result<(), String> {
+        status(unsafe { rp_stream_batch_set_models(self.h, first_stream, models.len(), models.as_ptr()) })
+    }
+    /// The logits of the last `process` / `process_multi` call of a `new_model_bank` batch, `[streams][frames of that call][label pitch of
+    /// the bank]`, zeros behind a model's labels.  An error on any other batch and before the first call.
+    pub fn logits(&mut self) -> Result<Vec<f32>, String> {
+        let mut out = vec![0f32; self.n_streams * self.last_chunks.max(1) * self.frames_per_chunk * self.label_pitch];
+        status(unsafe { rp_stream_batch_logits(self.h, out.as_mut_ptr()) })?;
+        Ok(out)
     }
     /// `process` that also tells which wakeword fired and, for a model, which label: (detections, wakeword indices, label indices or -1)
     pub fn process_multi(&mut self, pcm: &[f32], n_chunks: usize, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>, Vec<Vec<i32>>), String> {

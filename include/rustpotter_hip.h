@@ -861,6 +861,39 @@ int rp_batch_detect_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fm
                                const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, int precision,
                                rp_batch_detection *det, int32_t *det_label, int32_t *n_det, int max_det);
 
+/* Personal wakeword models on LIVE streams: a live-stream batch in which stream s runs its own model bank[stream_model[s]] [S] (-1: none).
+ * Stream s behaves as Rustpotter::new(config) + add_wakeword(models[stream_model[s]]) + process_samples per chunk -- the semantics of
+ * rp_batch_detect_model_bank with the detector state carried between calls on the device.  Thresholds come from `config` (a model has none of
+ * its own), mfcc_size is 16, the arithmetic is RP_MLP_F32, and a process call makes ONE forward launch (mlp_bank_stream_kernel) whatever
+ * the number of models.  Every stream keeps a history of rp_model_bank_train_size(bank, -1) - 1 frames; its own window starts
+ * train_size(s) - 1 frames before the new frame.  Index rules are those of rp_stream_batch_new_bank: a host array is checked before
+ * anything is allocated (an index outside [-1, W) is an error that names the stream), a device array is copied and the kernels treat such
+ * an index as -1.  An empty bank, or every index -1: calls succeed and report nothing.  The batch borrows `ctx` and `bank`, which must
+ * outlive it; the bank must belong to `ctx`.
+ * BITS: every window is computed row by row with the arithmetic of mlp_mfma_kernel's three-part form reading the window in place with its
+ * own mean -- what rp_mlp_forward_windows gives for fewer than 32 windows and what a shared-model live batch (rp_stream_batch_new_multi)
+ * gives for fewer than 32 new windows a call.  So a stream's logits, scores and detections do not depend on how the caller cuts the audio
+ * into calls, on the batch or on the stream's place in it, and equal those of rp_stream_batch_new_multi with that one model (calls of at
+ * most 10 chunks).  Against rp_batch_detect_model_bank over the concatenation (mlp_windows_bank_kernel, frames staged relative to a
+ * workgroup's middle window): equal detections, scores within 2e-6.
+ * On such a batch rp_stream_batch_process works without agg (with agg it is refused: the per-window output is the logits, see
+ * rp_stream_batch_logits); rp_stream_batch_process_multi reports det_wakeword = the stream's model index and det_label = the label index
+ * of the detection's best window; rp_stream_batch_set_input, _reset and _chunks_seen work as everywhere; rp_stream_batch_set_filters takes
+ * the band-pass filter alone (with the gain normaliser enabled it is refused: a per-model rms_level is not built); VAD works as on every
+ * live batch.  rp_stream_batch_set_wakewords, _set_wakeword_sets, _set_filters_bank and _slot_scores are refused with an error that says
+ * why. */
+int rp_stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, size_t S,
+                                   size_t max_chunks_per_call, rp_stream_batch **out);
+/* Connect, disconnect and retarget slots of a model-bank batch, at any time between process calls: streams first_stream .. first_stream +
+ * n - 1 get the model indices models [n] (-1: none) and each is reset exactly as rp_stream_batch_set_wakewords resets.  A refused index
+ * (host arrays) names its stream and changes nothing.  An error on any other kind of batch. */
+int rp_stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *models);
+/* The logits of the last process call of a model-bank batch, modelled on rp_stream_batch_slot_scores: logits [S][frames of that
+ * call][rp_model_bank_labels(bank, -1)], row (s, i) for the window of train_size(s) frames that ends at new frame i.  Values behind a
+ * model's labels are zero, rows of streams without a model are zero.  Windows that reach before frame 0 or before the stream's last reset
+ * are unspecified.  Returns -1 before the first process call and on any other kind of batch. */
+int rp_stream_batch_logits(rp_stream_batch *b, float *logits);
+
 /* Synthetic benchmark input of BASELINE.md §2, generated on the device:
  * pcm[s][i] = (splitmix64(seed ^ ((first_stream+s)<<32 + i)) >> 40) / 2^24 - 0.5 */
 int rp_synth_pcm_batch(rp_ctx *ctx, uint64_t seed, uint64_t first_stream, size_t S, size_t n_samples, size_t pcm_stride,

@@ -122,6 +122,7 @@ SYMBOLS = [
     "rp_stream_batch_slot_scores",
     "rp_model_bank_new", "rp_model_bank_new_from_rpw", "rp_model_bank_free", "rp_model_bank_size", "rp_model_bank_train_size",
     "rp_model_bank_labels", "rp_mlp_forward_windows_bank", "rp_batch_detect_model_bank",
+    "rp_stream_batch_new_model_bank", "rp_stream_batch_set_models", "rp_stream_batch_logits",
 ]
 
 
@@ -286,6 +287,9 @@ def load_library():
     L.rp_stream_batch_new_bank_sets.argtypes = [vp, vp, vp, C.c_int, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.rp_stream_batch_set_wakeword_sets.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
     L.rp_stream_batch_slot_scores.argtypes = [vp, vp, vp]
+    L.rp_stream_batch_new_model_bank.argtypes = [vp, vp, vp, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.rp_stream_batch_set_models.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
+    L.rp_stream_batch_logits.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -746,7 +750,7 @@ class StreamBatch:
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
                  mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None, bank_filters=None,
-                 stream_wakewords=None, set_size=None):
+                 stream_wakewords=None, set_size=None, model_bank=None, stream_model=None):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
         with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
@@ -757,13 +761,22 @@ class StreamBatch:
         bank_filters (rp_stream_batch_set_filters_bank, with bank): a FiltersConfig whose gain normaliser works per stream, towards
         the rms_level of the stream's own wakeword over its own window.
         bank + stream_wakewords (rp_stream_batch_new_bank_sets): stream s holds the SET of wakewords stream_wakewords[s], [S][set_size]
-        int32 with -1 = an empty slot (with device pointers: the address of a device array and set_size)."""
+        int32 with -1 = an empty slot (with device pointers: the address of a device array and set_size).
+        model_bank + stream_model (rp_stream_batch_new_model_bank; templates is then None): stream s runs its own model
+        model_bank[stream_model[s]], -1 = none; set_models() re-targets streams, logits() returns the last call's logits."""
         self._L = load_library()
         self.set_size = 0
+        self.label_pitch = 0
         self.ctx, self.templates, self.S, self.max_chunks = ctx, templates, S, max_chunks_per_call
         h = C.c_void_p()
         c = detector_config._c()
-        if bank is not None and stream_wakewords is not None:
+        if model_bank is not None:
+            self._keep = model_bank   # the batch borrows the bank
+            self.label_pitch = model_bank.label_pitch
+            idx, ptr = self._indices(stream_model)
+            if self._L.rp_stream_batch_new_model_bank(ctx._h, model_bank._h, ptr, C.byref(c), S, max_chunks_per_call, C.byref(h)) < 0:
+                raise _err()
+        elif bank is not None and stream_wakewords is not None:
             self._keep = bank   # the batch borrows the bank
             idx, ptr = self._indices(stream_wakewords)
             self.set_size = int(idx.shape[1] if set_size is None else set_size)
@@ -830,6 +843,26 @@ class StreamBatch:
         reset -- remove-all plus add-in-order; between process calls.  With device pointers: the address of a device int32 array of n rows."""
         idx, ptr = self._indices(stream_wakewords)
         if self._L.rp_stream_batch_set_wakeword_sets(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
+            raise _err()
+
+    def set_models(self, first_stream, stream_model, n=None):
+        """rp_stream_batch_set_models (a batch over a ModelBank): streams first_stream .. get the model indices stream_model (-1: none) and are
+        reset; between process calls.  With device pointers stream_model is the address of a device int32 array of n indices."""
+        idx, ptr = self._indices(stream_model)
+        if self._L.rp_stream_batch_set_models(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
+            raise _err()
+
+    def logits(self):
+        """rp_stream_batch_logits -> [S][frames of the last process call][label pitch of the bank]"""
+        import numpy as np
+        assert self.ctx.host
+        out = np.empty((self.S, max(self._last_chunks, 1) * self.frames_per_chunk, self.label_pitch), np.float32)
+        if self._L.rp_stream_batch_logits(self._h, out.ctypes.data) < 0:
+            raise _err()
+        return out
+
+    def logits_dev(self, logits_ptr):
+        if self._L.rp_stream_batch_logits(self._h, logits_ptr) < 0:
             raise _err()
 
     def slot_scores(self):

@@ -619,7 +619,8 @@ hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, con
 // wakeword (as launch_scan_bank) over agg / avg [S][n_new]; det_ww: the stream's bank index, det_label: -1 (both optional)
 hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg,
                                    const float *vad_value, float vad_mode_value, size_t S, long long f0, int n_new, const ScanConfig &cfg,
-                                   void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det);
+                                   void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det,
+                                   const int32_t *label = nullptr);   // label [S][n_new] (a model bank's batch): det_label is the label of the detection's best window
 
 // ---- wakeword sets (rp_dtw_set.hip, rp_scan_set.hip): stream s holds up to kScanMaxWakewords wakewords of a bank, stream_wakewords
 // [S][set_size] (outside [0, W): an empty slot) -- a `Rustpotter` with several add_wakeword calls.  Its window is Lmax(s) frames, the longest
@@ -810,5 +811,17 @@ hipError_t launch_nn_score_bank(hipStream_t st, const ModelBankDev &b, const int
 // det_label [S][max_det] = the label of each detection's window (label [S][win_pitch]), 0 behind a stream's detections
 hipError_t launch_model_bank_labels(hipStream_t st, const BatchDetection *det, const int32_t *n_det, const int32_t *label, size_t S, size_t win_pitch,
                                     int max_det, int32_t *det_label);
+
+// ---- live batches over a model bank (rp_mlp_bank_stream.hip; rp_stream_batch_new_model_bank): the n_new new windows of every stream, frame rows
+// [S][cap][16] with the first new frame at `fill` (>= max_L - 1, the bank's longest window, and fill + n_new <= cap); the window of stream s
+// that ends at new frame i starts L(s) - 1 frames before it.  mean [S][n_new][16], logits [S][n_new][label_pitch] (every row written: zeros
+// behind a model's labels and for a stream without a model).  Row by row the arithmetic of mlp_mfma_kernel<NT, kMlpBf16x3> in window mode.
+hipError_t launch_window_means_bank_stream(hipStream_t st, const ModelBankDev &b, int max_L, const int32_t *stream_model, const float *frames, size_t S,
+                                           size_t cap, size_t fill, size_t n_new, float *mean);
+hipError_t launch_mlp_bank_stream(hipStream_t st, const ModelBankDev &b, int max_L, const int32_t *stream_model, const float *frames, size_t S,
+                                  size_t cap, size_t fill, size_t n_new, const float *mean, float *logits);
+// launch_nn_score_bank over those rows: logits [S][n_new][label_pitch] -> agg / avg / label [S][n_new]; a stream without a model: -2, 0, -1
+hipError_t launch_nn_score_bank_stream(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *logits, size_t S, size_t n_new,
+                                       float score_ref10, int calc_avg, float threshold, float avg_threshold, float *agg, float *avg, int32_t *label);
 
 }  // namespace rp

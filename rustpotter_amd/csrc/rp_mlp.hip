@@ -1,6 +1,7 @@
 // rp_mlp.hip -- the wakeword model: forward (src/wakewords/nn/wakeword_nn.rs:101-163,305-389; mlp_layer_kernel,
 // mlp_mfma_kernel on the matrix cores, normalize_windows_batch_kernel), its route (mlp_route, mlp_forward), scoring and training
-// (wakeword_model_train.rs:204-209).  The staged-frame kernels are in rp_mlp_windows.hip, the streaming one in rp_mlp_stream.hip.
+// (wakeword_model_train.rs:204-209).  The staged-frame kernels are in rp_mlp_windows.hip, the streaming one in rp_mlp_stream.hip, the live
+// model bank's in rp_mlp_bank_stream.hip.
 // DESIGN.md §4.4.
 #include "rp_mlp_dev.h"
 #include "rp_host.h"
@@ -132,6 +133,32 @@ hipError_t launch_nn_score_bank(hipStream_t st, const ModelBankDev &b, const int
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nn_score_bank_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b, stream_model, logits, S, n_frames, win_pitch, score_ref10,
                        calc_avg, threshold, avg_threshold, agg, avg, label, hot);
+    return hipGetLastError();
+}
+
+// The same over the new windows of a live call (rp_stream_batch_new_model_bank): rows [S][n_new], every one a window of its stream
+__global__ __launch_bounds__(256) void nn_score_bank_stream_kernel(ModelBankDev b, const int32_t *__restrict__ stream_model, const float *__restrict__ logits,
+                                                                   size_t S, size_t n_new, float ref, int calc_avg, float threshold, float avg_threshold,
+                                                                   float *__restrict__ agg, float *__restrict__ avg, int32_t *__restrict__ label) {
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= S * n_new) return;
+    const int mi = stream_model[r / n_new];
+    float score = -2.f, av = 0.f;
+    int bi = -1;
+    if (mi >= 0 && mi < b.W) {
+        const ModelBankEntry e = b.e[mi];
+        nn_score_row(logits + r * (size_t)b.label_pitch, e.n_labels, e.none_index, ref, calc_avg, threshold, avg_threshold, &score, &av, &bi);
+    }
+    agg[r] = score; avg[r] = av; label[r] = bi;
+}
+
+hipError_t launch_nn_score_bank_stream(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *logits, size_t S, size_t n_new,
+                                       float score_ref10, int calc_avg, float threshold, float avg_threshold, float *agg, float *avg, int32_t *label) {
+    const size_t blocks = (S * n_new + 255) / 256;
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nn_score_bank_stream_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b, stream_model, logits, S, n_new, score_ref10, calc_avg,
+                       threshold, avg_threshold, agg, avg, label);
     return hipGetLastError();
 }
 

@@ -329,12 +329,15 @@ hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, con
 // scan_bank_kernel's detector on live streams (rp_stream_batch_new_bank): stream s holds the one wakeword bank[stream_wakeword[s]]
 // (bank_lane); agg / avg [S][n_new].  A detection reports the stream's bank index as its wakeword and label -1.  A stream without a
 // wakeword reports nothing and keeps its state as it is (rp_stream_batch_set_wakewords resets a stream it re-targets).
+// label (optional, [S][n_new]; a batch over a model bank, b = ModelBank::scan): the label of every window; the proposing window's travels in
+// the stream's state (p_label, as in scan_stream_kernel), so a detection reports the label of its best window even when an earlier call
+// scored it.
 __global__ __launch_bounds__(64) void scan_bank_stream_kernel(BankDev b, const int32_t *__restrict__ stream_wakeword, const float *__restrict__ agg,
                                                               const float *__restrict__ avg, const float *__restrict__ vad_value,
                                                               float vad_mode_value, size_t S, long long f0, int n_new, ScanConfig cfg,
                                                               StreamState *__restrict__ state, BatchDetection *__restrict__ det,
                                                               int32_t *__restrict__ det_ww, int32_t *__restrict__ det_label,
-                                                              int32_t *__restrict__ n_det, int max_det) {
+                                                              int32_t *__restrict__ n_det, int max_det, const int32_t *__restrict__ label) {
     __shared__ float vwin[50][64];
     const int lane = threadIdx.x;
     const size_t s = (size_t)blockIdx.x * 64 + lane;
@@ -350,8 +353,12 @@ __global__ __launch_bounds__(64) void scan_bank_stream_kernel(BankDev b, const i
         stream_state_load(state + s, z, vwin, lane, vv != nullptr);
         nd = scan_frames(
             z, vwin, lane, vv, vad_mode_value, f0, n_new, r.max_len, cfg,
-            [&](long long, int i) { return propose_one(agg, avg, row0 + i, r.thr, r.athr, r.avg_on, wi); },
-            [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s, f, z, z.p_ww, -1); });
+            [&](long long, int i) {
+                Proposal p = propose_one(agg, avg, row0 + i, r.thr, r.athr, r.avg_on, wi);
+                if (label) p.label = label[row0 + i];
+                return p;
+            },
+            [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s, f, z, z.p_ww, label ? z.p_label : -1); });
         stream_state_store(state + s, z, vwin, lane, vv != nullptr);
     }
     out.finish(s, nd);
@@ -359,10 +366,11 @@ __global__ __launch_bounds__(64) void scan_bank_stream_kernel(BankDev b, const i
 
 hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg,
                                    const float *vad_value, float vad_mode_value, size_t S, long long f0, int n_new, const ScanConfig &cfg,
-                                   void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det) {
+                                   void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det,
+                                   const int32_t *label) {
     if (S == 0) return hipSuccess;
     hipLaunchKernelGGL(scan_bank_stream_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, b, stream_wakeword, agg, avg, vad_value,
-                       vad_mode_value, S, f0, n_new, cfg, static_cast<StreamState *>(state), det, det_ww, det_label, n_det, max_det);
+                       vad_mode_value, S, f0, n_new, cfg, static_cast<StreamState *>(state), det, det_ww, det_label, n_det, max_det, label);
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
 // rp_stream_batch.cpp -- live-stream batches (rp_stream_batch_*): S streams fed a few chunks per call, every stream's state on the device.
+// A batch holds shared wakewords (references and / or models), or every stream its own: of a wakeword bank, or of a model bank.
 #include <cmath>
 #include <cstring>
 
@@ -31,6 +32,12 @@ struct rp_stream_batch {
     // empty slot; bank_agg / bank_avg are then the slot scores [S][set_size][frames per call] and slot_frames the frames of the last call
     int set_size = 0;
     size_t slot_frames = 0;
+    // made by rp_stream_batch_new_model_bank: stream s runs the one model mbank[bank_idx[s]] (`ww` is empty, `bank` null).  max_len is the bank's
+    // longest window; bank_agg / bank_avg / bank_label [S][frames per call] are the scores and labels of the streams' own windows, `logits`
+    // [S][logit_frames][label_pitch] those of the last call (rp_stream_batch_logits).  The bank is immutable.
+    const ModelBank *mbank = nullptr;
+    DevBuf bank_label;
+    size_t logit_frames = 0;
     size_t slots() const { return set_size ? (size_t)set_size : 1; }
     int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
     DevBuf det_ww, det_label, logits, mean, xrows, xs2;
@@ -90,6 +97,9 @@ static bool stream_batch_alloc(rp_stream_batch *b) {
             (w->m && !w->label.reserve(rows * sizeof(int32_t) + 16)))
             return false;
     if (b->bank && (!b->bank_agg.reserve(rows * b->slots() * sizeof(float) + 16) || !b->bank_avg.reserve(rows * b->slots() * sizeof(float) + 16))) return false;
+    if (b->mbank && (!b->bank_agg.reserve(rows * sizeof(float) + 16) || !b->bank_avg.reserve(rows * sizeof(float) + 16) ||
+                     !b->bank_label.reserve(rows * sizeof(int32_t) + 16) || !b->mean.reserve(rows * 16 * sizeof(float) + 16) ||
+                     !b->logits.reserve(rows * (size_t)b->mbank->dev.label_pitch * sizeof(float) + 16))) return false;
     if (!b->pcm[0].reserve(pcm_bytes) || !b->pcm[1].reserve(pcm_bytes) || !b->mfcc[0].reserve(S * pitch * K * sizeof(float) + slack) ||
         !b->mfcc[1].reserve(S * pitch * K * sizeof(float) + slack) || !b->state.reserve(S * stream_state_bytes()) ||
         !b->scores.reserve(rows * (size_t)b->Tmax * sizeof(float) + 16) || !b->vad.reserve(rows * sizeof(float) + 16) ||
@@ -317,6 +327,14 @@ static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, con
     }
     const float vm = vad_mode_value(b->cfg.vad_mode);
     const long long f0 = (long long)b->fpf() * (long long)b->chunks_seen - 3;
+    if (b->mbank) {
+        // window length (countdown L / 2) per stream from the bank's scan entries; their thresholds are -1: nn_score_bank_stream_kernel applied the gates
+        const ScanConfig sc = scan_config(b->cfg, 0, true, (int)b->fpf());
+        return timed(c, kKernelScan, "scan_bank_stream_kernel", [&] {
+            return launch_scan_bank_stream(c->stream, b->mbank->scan, b->bank_idx.as<int32_t>(), b->bank_agg.as<float>(), b->bank_avg.as<float>(), dv, vm,
+                                           b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det, b->bank_label.as<int32_t>());
+        });
+    }
     if (b->bank) {
         const ScanConfig sc = scan_config(b->cfg, 0, true, (int)b->fpf());   // window length, thresholds and the avg test come from the bank, per stream
         if (b->set_size)
@@ -358,6 +376,25 @@ static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_n
     return timed(c, kKernelDtw, "dtw_bank_stream_kernel", [&] { return launch_dtw_bank_stream(c->stream, bd, q); });
 }
 
+// A batch over a model bank: the logits of every stream's n_new new windows with its own model (one forward launch, inside the context's
+// kKernelMlp bracket), then their scores and labels -> bank_agg / bank_avg / bank_label.  An empty bank: no stream has a model, nothing runs
+// and the scan reports nothing.
+static bool score_model_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new) {
+    Ctx *c = b->c;
+    const ModelBank &bk = *b->mbank;
+    b->logit_frames = n_new;
+    if (bk.dev.W == 0) return true;
+    const int32_t *idx = b->bank_idx.as<int32_t>();
+    float *mean = b->mean.as<float>(), *dlog = b->logits.as<float>();
+    if (!hip_ok(launch_window_means_bank_stream(c->stream, bk.dev, bk.max_L, idx, f.rows, b->S, b->cap, f.fill, n_new, mean), "window_means_bank_stream_kernel"))
+        return false;
+    if (!timed(c, kKernelMlp, "mlp_bank_stream_kernel", [&] {
+            return launch_mlp_bank_stream(c->stream, bk.dev, bk.max_L, idx, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); })) return false;
+    return hip_ok(launch_nn_score_bank_stream(c->stream, bk.dev, idx, dlog, b->S, n_new, b->cfg.score_ref * 10.f, b->cfg.avg_threshold != 0.f ? 1 : 0,
+                                              b->cfg.threshold, b->cfg.avg_threshold, b->bank_agg.as<float>(), b->bank_avg.as<float>(),
+                                              b->bank_label.as<int32_t>()), "nn_score_bank_stream_kernel");
+}
+
 // Score + scan stage: scores of this call's n_new windows per stream for every wakeword, then the state machine over all of them.
 // detect_only: nobody reads the per-window arrays.
 static bool stream_score_and_scan(rp_stream_batch *b, Staged &sg, const NewFrames &f, size_t n_new, bool detect_only, BatchDetection *dd,
@@ -365,6 +402,7 @@ static bool stream_score_and_scan(rp_stream_batch *b, Staged &sg, const NewFrame
     ScanWakewords sw{};
     sw.n = (int)b->ww.size();
     if (b->bank && !score_bank_stream(b, f, n_new, detect_only)) return false;
+    if (b->mbank && !score_model_bank_stream(b, f, n_new)) return false;
     for (size_t j = 0; j < b->ww.size(); ++j)
         if (!(b->ww[j]->t ? score_reference(b, *b->ww[j], f, n_new, detect_only, sw, j) : score_model(b, *b->ww[j], f, n_new, sw, j))) return false;
     const size_t col = b->S * (size_t)max_det * sizeof(int32_t);
@@ -388,6 +426,10 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
         const size_t in_chunk = b->in_len * (size_t)b->channels;
         if (pcm_stride < n_chunks * in_chunk) { set_last_error("pcm_stride smaller than n_chunks * samples per chunk"); return -1; }
         if (!sample_format_ok(fmt)) return -1;
+        if (b->mbank && agg) {
+            set_last_error("rp_stream_batch_process: a batch over a model bank has no aggregate per window; its per-window output is the logits (rp_stream_batch_logits)");
+            return -1;
+        }
         if (!b->single && (!b->bank || b->set_size) && agg) { set_last_error("rp_stream_batch_process: a batch of several wakewords has no single aggregate per window"); return -1; }
         const MfccTablesDev *tb = c->tables_for(b->K);
         if (!tb) return -1;
@@ -474,6 +516,31 @@ int rp_stream_batch_new_bank_sets(rp_ctx *ctx, const rp_wakeword_bank *bank, con
                                   const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
     return stream_batch_new_bank(ctx, bank, stream_wakewords, true, set_size, config, S, max_chunks_per_call, out);
 }
+// live-stream batches in which stream s runs its own model bank[stream_model[s]] (personal wakeword models; rp_batch_detect_model_bank with
+// the state carried between calls).  Thresholds are the config's, mfcc_size is 16, the arithmetic RP_MLP_F32.
+int rp_stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, size_t S,
+                                   size_t max_chunks_per_call, rp_stream_batch **out) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (!config || !out || !stream_model) { set_last_error("null argument"); return -1; }
+        *out = nullptr;
+        const ModelBank &bk = *bank->impl;
+        Ctx *c = bank_call_ctx(ctx, bk.ctx);
+        if (!c) return -1;
+        if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new_model_bank: S and max_chunks_per_call must be >= 1"); return -1; }
+        // before anything is allocated
+        if ((c->flags & RP_CTX_HOST_POINTERS) && !bank_indices_ok(bk.dev.W, 0, S, 0, stream_model, "model index")) return -1;
+        std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
+        b->c = c; b->mbank = &bk; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
+        b->K = 16; b->max_len = std::max(bk.max_L, 1); b->Tmax = 1;
+        if (!bank_indices_put(b.get(), 0, S, stream_model)) return -1;
+        if (!c->tables_for(b->K)) return -1;
+        b->hist_frames = (size_t)b->max_len - 1;   // every stream keeps the history of the bank's longest window; its own starts L(s) - 1 frames back
+        if (!stream_batch_alloc(b.get())) return -1;
+        *out = b.release();
+        return 0;
+    });
+}
 void rp_stream_batch_free(rp_stream_batch *b) { delete b; }
 size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b) { return b ? b->chunks_seen : 0; }
 
@@ -512,6 +579,11 @@ static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config 
         if (b && !filters) { set_last_error("null argument"); return -1; }
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (per_stream && b->mbank) {
+            set_last_error(name + ": the gain normaliser per model is not built for a batch over a model bank (a model's rms_level is not part of the "
+                                  "bank); rp_stream_batch_set_filters takes the band-pass filter alone");
+            return -1;
+        }
         if (per_stream && !b->bank) { set_last_error(name + ": the batch was not made by rp_stream_batch_new_bank"); return -1; }
         if (per_stream && b->set_size) {
             set_last_error(name + ": the gain normaliser is not available on a batch over wakeword sets (its level and window would come from "
@@ -521,6 +593,11 @@ static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config 
         if (b->chunks_seen) { set_last_error(name + ": the streams have already received audio"); return -1; }
         if (b->out_len != 480) { set_last_error(kFiltersNeed30ms); return -1; }
         const rp_gain_normalization_config &g = filters->gain_normalizer;
+        if (b->mbank && g.enabled) {
+            set_last_error("rp_stream_batch_set_filters: the gain normaliser is not available on a batch over a model bank (its window and "
+                           "rms_level_ref would be per stream, and a model's rms_level is not part of the bank); the band-pass filter alone is");
+            return -1;
+        }
         if (b->bank && g.enabled && !per_stream) {
             set_last_error("rp_stream_batch_set_filters: the gain normaliser is not available on a batch over a wakeword bank (its window and "
                            "rms_level_ref would be per stream, stream_filters_kernel takes one value of each); the band-pass filter alone is, "
@@ -590,6 +667,11 @@ static int stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, s
     const int r = guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (b->mbank) {
+            set_last_error(std::string(sets ? "rp_stream_batch_set_wakeword_sets" : "rp_stream_batch_set_wakewords") +
+                           ": the batch runs over a model bank (rp_stream_batch_new_model_bank), whose streams are re-targeted with rp_stream_batch_set_models");
+            return -1;
+        }
         if (sets && !b->set_size) { set_last_error("rp_stream_batch_set_wakeword_sets: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
         if (!b->bank) { set_last_error("rp_stream_batch_set_wakewords: the batch was not made by rp_stream_batch_new_bank"); return -1; }
         if (!sets && b->set_size) { set_last_error("rp_stream_batch_set_wakewords: the batch holds wakeword sets (rp_stream_batch_new_bank_sets); use rp_stream_batch_set_wakeword_sets"); return -1; }
@@ -618,10 +700,52 @@ int rp_stream_batch_set_wakeword_sets(rp_stream_batch *b, size_t first_stream, s
     return stream_batch_set_wakewords(b, first_stream, n, stream_wakewords, true);
 }
 
+// connect / disconnect / retarget slots of a batch over a model bank: as rp_stream_batch_set_wakewords, each touched stream reset
+int rp_stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *models) {
+    bool touched = false;
+    const int r = guarded([&]() -> int {
+        Ctx *c = stream_batch_enter(b, true);
+        if (!c) return -1;
+        if (!b->mbank) { set_last_error("rp_stream_batch_set_models: the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
+        if (first_stream > b->S || n > b->S - first_stream) {
+            set_last_error("rp_stream_batch_set_models: streams " + std::to_string(first_stream) + " .. " + std::to_string(first_stream) + " + " +
+                           std::to_string(n) + " reach past the batch's " + std::to_string(b->S) + " streams");
+            return -1;
+        }
+        if (n == 0) return 0;
+        if (!models) { set_last_error("null argument"); return -1; }
+        // a refused index leaves the batch as it was
+        if ((c->flags & RP_CTX_HOST_POINTERS) && !bank_indices_ok(b->mbank->dev.W, first_stream, n, 0, models, "model index")) return -1;
+        touched = true;
+        if (!bank_indices_put(b, first_stream, n, models)) return -1;
+        return hip_ok(launch_stream_state_reset_range(c->stream, b->state.p, b->S, first_stream, n, (long long)b->fpf() * (long long)b->chunks_seen),
+                      "stream_state_reset_kernel") ? 0 : -1;
+    });
+    if (r != 0 && touched) b->poisoned = true;
+    return r;
+}
+
+// the logits of the last process call of a batch over a model bank, [S][frames of that call][rp_model_bank_labels(bank, -1)]
+int rp_stream_batch_logits(rp_stream_batch *b, float *logits) {
+    return guarded([&]() -> int {
+        Ctx *c = stream_batch_enter(b, true);
+        if (!c) return -1;
+        if (!b->mbank) { set_last_error("rp_stream_batch_logits: the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
+        if (!b->logit_frames) { set_last_error("rp_stream_batch_logits: the streams have not received audio yet"); return -1; }
+        const size_t bytes = b->S * b->logit_frames * (size_t)b->mbank->dev.label_pitch * sizeof(float);
+        if (bytes == 0) return 0;   // an empty bank has no labels
+        if (!logits) { set_last_error("null argument"); return -1; }
+        const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
+        if (!hip_ok(hipMemcpyAsync(logits, b->logits.p, bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync")) return -1;
+        return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
+    });
+}
+
 int rp_stream_batch_slot_scores(rp_stream_batch *b, float *agg, float *avg) {
     return guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (b->mbank) { set_last_error("rp_stream_batch_slot_scores: a batch over a model bank has one model per stream and no slots; rp_stream_batch_logits returns its per-window output"); return -1; }
         if (!b->set_size) { set_last_error("rp_stream_batch_slot_scores: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
         if (!b->slot_frames) { set_last_error("rp_stream_batch_slot_scores: the streams have not received audio yet"); return -1; }
         const size_t bytes = b->S * (size_t)b->set_size * b->slot_frames * sizeof(float);
