@@ -527,6 +527,13 @@ float orc_calc_inverse_similarity(float n1, float n2, float reference) {
     return 1.f - (1.f / (1.f + expf(((n1 - n2) - reference) / reference)));
 }
 
+/* the integer f32::total_cmp orders by: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN */
+static int32_t total_cmp_key(float x) {
+    int32_t b;
+    memcpy(&b, &x, 4);
+    return b ^ (int32_t)((uint32_t)(b >> 31) >> 1);
+}
+
 /* WakewordNN::run_detection, src/wakewords/nn/wakeword_nn.rs:39-159 */
 static int nn_run_detection(const orc_wakeword *w, int wi, const float *window, int wn, float avg_threshold,
                             float threshold, float score_ref, orc_detection *out) {
@@ -539,7 +546,7 @@ static int nn_run_detection(const orc_wakeword *w, int wi, const float *window, 
     free(norm);
     /* get_label :47-60: max_by total_cmp returns the LAST maximum */
     int best = 0;
-    for (int i = 1; i < w->n_labels; ++i) if (!(logits[i] < logits[best])) best = i;
+    for (int i = 1; i < w->n_labels; ++i) if (!(total_cmp_key(logits[i]) < total_cmp_key(logits[best]))) best = i;
     if (best == w->none_index) return 0;
     float ref = score_ref * 10.f; /* :39 */
     float none_prob = w->none_index >= 0 ? logits[w->none_index] : 0.f;
@@ -552,7 +559,7 @@ static int nn_run_detection(const orc_wakeword *w, int wi, const float *window, 
         int found = 0;
         for (int i = 0; i < w->n_labels; ++i) {
             if (logits[i] == label_prob) continue;
-            if (!found || !(logits[i] > second)) { second = logits[i]; found = 1; }
+            if (!found || !(total_cmp_key(logits[i]) > total_cmp_key(second))) { second = logits[i]; found = 1; }
         }
         if (!found) second = 0.f;
     }

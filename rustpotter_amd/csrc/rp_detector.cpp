@@ -25,6 +25,12 @@ float rms_level_of(const float *s, int n) {
 float calc_inverse_similarity(float n1, float n2, float reference) {
     return 1.f - (1.f / (1.f + std::exp(((n1 - n2) - reference) / reference)));
 }
+// the integer f32::total_cmp orders by (a NaN logit: see nn_score_row in rp_mlp.hip)
+int32_t total_cmp_key(float x) {
+    int32_t b;
+    std::memcpy(&b, &x, 4);
+    return b ^ (int32_t)((uint32_t)(b >> 31) >> 1);
+}
 }  // namespace
 
 struct Rustpotter::Wakeword {
@@ -536,7 +542,7 @@ bool Rustpotter::run_detection(int slot, Detection *out) {
             const size_t nl = w.model.labels.size();
             const float *logits = res + w.off_logits + (size_t)slot * nl;
             size_t bi = 0;
-            for (size_t i = 1; i < nl; ++i) if (!(logits[i] < logits[bi])) bi = i;  // max_by(total_cmp): last maximum
+            for (size_t i = 1; i < nl; ++i) if (!(total_cmp_key(logits[i]) < total_cmp_key(logits[bi]))) bi = i;  // max_by(total_cmp): last maximum
             if ((int)bi == w.none_index) continue;
             const float ref = det_.score_ref * 10.f;
             const float none_prob = w.none_index >= 0 ? logits[w.none_index] : 0.f;
@@ -547,7 +553,7 @@ bool Rustpotter::run_detection(int slot, Detection *out) {
                 bool any = false;
                 for (size_t i = 0; i < nl; ++i) {
                     if (logits[i] == label_prob) continue;
-                    if (!any || !(logits[i] > second)) { second = logits[i]; any = true; }
+                    if (!any || !(total_cmp_key(logits[i]) > total_cmp_key(second))) { second = logits[i]; any = true; }
                 }
                 if (!any) second = 0.f;
             }

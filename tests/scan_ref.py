@@ -54,18 +54,20 @@ class _Vad:  # src/mfcc/vad.rs
         return False
 
 
-def scan_ref(agg, avg, n_frames, max_len, threshold, avg_threshold, min_scores, eager, vad_values, vad_mode_value, fpf=3):
+def scan_ref(agg, avg, n_frames, max_len, threshold, avg_threshold, min_scores, eager, vad_values, vad_mode_value, fpf=3, label=None):
     """-> [(frame, window, counter, avg_score, score)]: the detections of one stream, `frame` the MFCC frame whose processing returned it.
 
     agg / avg: the stream's rows (avg None: no averaged-template test, avg_score 0); vad_values: vad_values_ref of the stream's frames or
-    None (no VAD).  fpf: MFCC frames a chunk of input adds (3 for 480-sample chunks)."""
+    None (no VAD).  fpf: MFCC frames a chunk of input adds (3 for 480-sample chunks).  label: a row like agg, what each window's detection
+    carries besides its scores (a model's label); a detection then has a sixth entry, the label of the window that holds its score -- the
+    partial detection is replaced as a whole or only counted up (detector.rs:416-428), so it is the label of `window`."""
     agg = list(np.asarray(agg, F32))
     avg = None if avg is None else list(np.asarray(avg, F32))
     threshold, avg_threshold = F32(threshold), F32(avg_threshold)
     vad = None if vad_values is None else _Vad(vad_mode_value)
     out = []
     window_len = 0            # audio_mfcc_window.len()
-    partial = None            # [window, counter, avg_score, score]
+    partial = None            # [window, counter, avg_score, score, label]
     countdown = 0
     # MfccExtractor: frame f is the four hops f .. f + 3 of 160 samples, a chunk brings fpf hops, so frame f comes out of chunk
     # c = (f + 3) // fpf.  A detection in chunk c drops the rest of c (find_map) and resets the extractor; it starts again with the
@@ -86,7 +88,7 @@ def scan_ref(agg, avg, n_frames, max_len, threshold, avg_threshold, min_scores, 
             if partial is not None and (countdown == 0 or (eager and partial[1] >= min_scores)):
                 taken, partial = partial, None
                 if taken[1] >= min_scores:
-                    out.append((f, taken[0], taken[1], taken[2], taken[3]))
+                    out.append((f, taken[0], taken[1], taken[2], taken[3]) + (() if label is None else (taken[4],)))
                     # reset()
                     window_len = 0
                     if vad is not None:
@@ -102,7 +104,7 @@ def scan_ref(agg, avg, n_frames, max_len, threshold, avg_threshold, min_scores, 
                 if found:
                     counter = 1 if partial is None else partial[1] + 1
                     if partial is None or partial[3] < score:
-                        partial = [w, counter, avg_score, score]
+                        partial = [w, counter, avg_score, score, None if label is None else label[w]]
                     else:
                         partial[1] = counter
                     countdown = max_len // 2
