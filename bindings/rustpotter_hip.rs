@@ -161,6 +161,15 @@ extern "C" {
                                    train_wavs: *const *const u8, train_lens: *const usize, n_test: usize, test_names: *const *const c_char,
                                    test_wavs: *const *const u8, test_lens: *const usize, prev_model: *const u8, prev_model_len: usize,
                                    out_rpw: *mut *mut u8, out_len: *mut usize, final_loss: *mut f32, test_accuracy: *mut f32) -> c_int;
+    pub fn rp_wakeword_model_train_batch(ctx: *mut rp_ctx, options: *const rp_train_options, n_models: usize, seeds: *const u64,
+                                         train_counts: *const usize, train_names: *const *const c_char, train_wavs: *const *const u8,
+                                         train_lens: *const usize, test_counts: *const usize, test_names: *const *const c_char,
+                                         test_wavs: *const *const u8, test_lens: *const usize, prev_models: *const *const u8,
+                                         prev_model_lens: *const usize, out_rpw: *mut *mut u8, out_lens: *mut usize, final_loss: *mut f32,
+                                         test_accuracy: *mut f32) -> c_int;
+    pub fn rp_mlp_train_batch(ctx: *mut rp_ctx, n_models: usize, n_layers: *const i32, dims: *const i32, n_rows: *const i32,
+                              x: *const f32, labels: *const i32, params: *mut f32, learning_rate: f32, epochs: usize, final_loss: *mut f32) -> c_int;
+    pub fn rp_train_batch_last_profile(ctx: *mut rp_ctx, feature_ms: *mut f64, longest_launch_ms: *mut f64, launches: *mut c_int) -> c_int;
     pub fn rp_frontend_batch(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
                              filters: *const rp_filters_config, rms_level_ref: f32, window_size: usize, pcm_out: *mut f32,
                              out_stride: usize, rms: *mut f32, gains: *mut f32) -> c_int;
@@ -1223,4 +1232,79 @@ pub fn wakeword_model_train_from_buffers(m_type: c_int, train: &HashMap<String, 
                                 tel.as_ptr(), pm, pl, &mut out, &mut out_len, &mut loss, &mut acc)
     };
     take_buffer(r, out, out_len).map(|b| (b, loss, acc))
+}
+/// One model of a batched training: its labelled train and test samples (name, wav bytes) in order, the seed of its initial weights
+/// and, to continue a training, the `.rpw` bytes of the model to start from.
+pub struct ModelSamples {
+    pub train: Vec<(String, Vec<u8>)>,
+    pub test: Vec<(String, Vec<u8>)>,
+    pub seed: u64,
+    pub prev_model: Option<Vec<u8>>,
+}
+/// `wakeword_model_train_from_buffers` for many models in ONE call: the epochs of all models run side by side on the device, a
+/// workgroup per model; returns (`.rpw` bytes, last loss, test accuracy) per model, the bytes the single call gives for that model's
+/// samples, seed and previous model.  One model that cannot be trained fails the whole call (the error names its index).
+pub fn wakeword_models_train_from_buffers(ctx: &HipContext, m_type: c_int, models: &[ModelSamples], learning_rate: f64, epochs: usize,
+                                          mfcc_size: u16) -> Result<Vec<(Vec<u8>, f32, f32)>, String> {
+    fn flat(sets: Vec<&Vec<(String, Vec<u8>)>>) -> (Vec<usize>, Vec<CString>, Vec<*const u8>, Vec<usize>) {
+        (sets.iter().map(|s| s.len()).collect(), sets.iter().flat_map(|s| s.iter()).map(|s| CString::new(s.0.as_str()).unwrap()).collect(),
+         sets.iter().flat_map(|s| s.iter()).map(|s| s.1.as_ptr()).collect(), sets.iter().flat_map(|s| s.iter()).map(|s| s.1.len()).collect())
+    }
+    let (trc, trn, trb, trl) = flat(models.iter().map(|m| &m.train).collect());
+    let (tec, ten, teb, tel) = flat(models.iter().map(|m| &m.test).collect());
+    let trp: Vec<*const c_char> = trn.iter().map(|n| n.as_ptr()).collect();
+    let tep: Vec<*const c_char> = ten.iter().map(|n| n.as_ptr()).collect();
+    let seeds: Vec<u64> = models.iter().map(|m| m.seed).collect();
+    let prev: Vec<*const u8> = models.iter().map(|m| m.prev_model.as_ref().map_or(std::ptr::null(), |p| p.as_ptr())).collect();
+    let prev_lens: Vec<usize> = models.iter().map(|m| m.prev_model.as_ref().map_or(0, |p| p.len())).collect();
+    let opt = rp_train_options { m_type, learning_rate: learning_rate as f32, epochs, test_epochs: 0, mfcc_size, seed: 1 };
+    let n = models.len();
+    let mut out: Vec<*mut u8> = vec![std::ptr::null_mut(); n];
+    let (mut out_lens, mut loss, mut acc) = (vec![0usize; n], vec![0f32; n], vec![0f32; n]);
+    status(unsafe {
+        rp_wakeword_model_train_batch(ctx.h, &opt, n, seeds.as_ptr(), trc.as_ptr(), trp.as_ptr(), trb.as_ptr(), trl.as_ptr(), tec.as_ptr(),
+                                      tep.as_ptr(), teb.as_ptr(), tel.as_ptr(), prev.as_ptr(), prev_lens.as_ptr(), out.as_mut_ptr(),
+                                      out_lens.as_mut_ptr(), loss.as_mut_ptr(), acc.as_mut_ptr())
+    })?;
+    out.into_iter().zip(out_lens).zip(loss.into_iter().zip(acc)).map(|((p, n), (l, a))| take_buffer(0, p, n).map(|b| (b, l, a))).collect()
+}
+/// One MLP of `mlp_train_batch`: layer widths (input first, label count last; 2 to 5 entries), its rows ([rows][dims[0]], flat),
+/// their labels and its parameters -- per layer, weight [out][in] then bias [out] -- which the call updates in place.
+pub struct MlpTraining {
+    pub dims: Vec<i32>,
+    pub x: Vec<f32>,
+    pub labels: Vec<i32>,
+    pub params: Vec<f32>,
+}
+/// The epochs alone for many MLPs in one call (the arithmetic of the model trainer); returns the loss of the last epoch per model.
+pub fn mlp_train_batch(ctx: &HipContext, models: &mut [MlpTraining], learning_rate: f32, epochs: usize) -> Result<Vec<f32>, String> {
+    if models.iter().any(|m| m.dims.len() < 2 || m.dims.len() > 5) { return Err("an MLP of 1 to 4 layers is required".to_string()); }
+    let n_layers: Vec<i32> = models.iter().map(|m| m.dims.len() as i32 - 1).collect();
+    let dims: Vec<i32> = models.iter().flat_map(|m| (0..5).map(move |l| m.dims.get(l).copied().unwrap_or(0))).collect();
+    let n_rows: Vec<i32> = models.iter().map(|m| m.labels.len() as i32).collect();
+    if models.iter().any(|m| m.x.len() != m.labels.len() * m.dims[0].max(0) as usize) { return Err("x must hold [rows][dims[0]] floats".to_string()); }
+    let want = |m: &MlpTraining| m.dims.windows(2).map(|d| (d[0].max(0) as usize + 1) * d[1].max(0) as usize).sum::<usize>();
+    if models.iter().any(|m| m.params.len() != want(m)) { return Err("params must hold every layer's weight and bias".to_string()); }
+    let x: Vec<f32> = models.iter().flat_map(|m| m.x.iter().copied()).collect();
+    let labels: Vec<i32> = models.iter().flat_map(|m| m.labels.iter().copied()).collect();
+    let mut params: Vec<f32> = models.iter().flat_map(|m| m.params.iter().copied()).collect();
+    let mut loss = vec![0f32; models.len()];
+    status(unsafe {
+        rp_mlp_train_batch(ctx.h, models.len(), n_layers.as_ptr(), dims.as_ptr(), n_rows.as_ptr(), x.as_ptr(), labels.as_ptr(), params.as_mut_ptr(),
+                           learning_rate, epochs, loss.as_mut_ptr())
+    })?;
+    let mut at = 0usize;
+    for m in models.iter_mut() {
+        let n = m.params.len();
+        m.params.copy_from_slice(&params[at..at + n]);
+        at += n;
+    }
+    Ok(loss)
+}
+/// What the context's last batched training spent: (ms of the feature stage on the host, ms of its longest kernel launch -- 0 unless
+/// timing was enabled on the context --, number of launches).
+pub fn train_batch_last_profile(ctx: &HipContext) -> Result<(f64, f64, i32), String> {
+    let (mut feature_ms, mut longest_ms, mut launches) = (0f64, 0f64, 0 as c_int);
+    status(unsafe { rp_train_batch_last_profile(ctx.h, &mut feature_ms, &mut longest_ms, &mut launches) })?;
+    Ok((feature_ms, longest_ms, launches))
 }

@@ -323,6 +323,38 @@ int rp_wakeword_model_train(rp_ctx *ctx, const rp_train_options *options, size_t
                             const uint8_t *prev_model, size_t prev_model_len, uint8_t **out_rpw, size_t *out_len,
                             float *final_loss, float *test_accuracy);
 
+/* rp_wakeword_model_train for W models in one call: enrol -> model bank (rp_model_bank_new_from_rpw) -> detect.  The epochs of all models
+ * run side by side in one kernel, a workgroup per model, cut into launches of a bounded number of epochs (RP_TRAIN_EPOCHS_PER_LAUNCH, read
+ * per call, replaces the default bound).  options holds what the models share (m_type, learning_rate, epochs, mfcc_size); the models may
+ * differ in everything else: their samples, labels, window length and, through prev_models, type and mfcc_size.  train_counts /
+ * test_counts [W]: samples per model; the samples of all models follow each other in train_names / train_wavs / train_lens [sum
+ * train_counts] and test_names / test_wavs / test_lens [sum test_counts].  out_rpw / out_lens [W]: out_rpw[w] holds the bytes
+ * rp_wakeword_model_train gives for model w's samples with options->seed replaced by seeds[w] (seeds NULL: options->seed + w) and
+ * prev_models[w] (prev_models NULL or an entry NULL: none; prev_model_lens [W]); free each with rp_buffer_free.  final_loss /
+ * test_accuracy: [W] or NULL.  A model the single call would refuse fails the whole call: the error is the single call's, prefixed
+ * "model <index>: ", every out_rpw[w] is NULL and nothing needs freeing.  n_models == 0 succeeds and does nothing.  HOST arrays. */
+int rp_wakeword_model_train_batch(rp_ctx *ctx, const rp_train_options *options, size_t n_models, const uint64_t *seeds,
+                                  const size_t *train_counts, const char *const *train_names, const uint8_t *const *train_wavs,
+                                  const size_t *train_lens, const size_t *test_counts, const char *const *test_names,
+                                  const uint8_t *const *test_wavs, const size_t *test_lens, const uint8_t *const *prev_models,
+                                  const size_t *prev_model_lens, uint8_t **out_rpw, size_t *out_lens, float *final_loss,
+                                  float *test_accuracy);
+
+/* The epochs alone (as rp_mfcc_average_batch is the averaging alone): W MLPs, each with its own shape and rows, `epochs` full-batch steps
+ * of log_softmax + nll + SGD(learning_rate) with the arithmetic of rp_wakeword_model_train.  n_layers [W] (1..4); dims [W][5]: layer
+ * widths, dims[w][0] the input, dims[w][n_layers[w]] the label count; n_rows [W] (>= 1); x: every model's rows concatenated ([n_rows][dims[0]]
+ * each); labels likewise ([n_rows], 0 .. label count - 1); params in / out: per model, per layer, weight [out][in] then bias [out],
+ * concatenated.  final_loss [W] or NULL: the loss of the last epoch (NaN for 0 epochs).  A model that cannot be trained fails the whole
+ * call ("model <index>: ...") and leaves params as they were.  HOST arrays. */
+int rp_mlp_train_batch(rp_ctx *ctx, size_t n_models, const int32_t *n_layers, const int32_t *dims, const int32_t *n_rows,
+                       const float *x, const int32_t *labels, float *params, float learning_rate, size_t epochs, float *final_loss);
+
+/* What the context's last rp_wakeword_model_train_batch / rp_mlp_train_batch call spent (tools/bench_train_batch.py): feature_ms, the
+ * host's time in the feature stage (wav decoding, resampling and MFCCs, one sample after the other; 0 for rp_mlp_train_batch);
+ * launches, the kernel launches of its epochs; longest_launch_ms, the longest of them, timed with hipEvents -- 0 unless
+ * rp_ctx_timing_enable was on during the call.  Any of the three may be NULL. */
+int rp_train_batch_last_profile(rp_ctx *ctx, double *feature_ms, double *longest_launch_ms, int *launches);
+
 /* The audio front-end of Rustpotter::process_audio for whole streams (src/detector.rs:358-371): sample
  * decode, GainNormalizerFilter (src/audio/gain_normalizer_filter.rs:14-55: per 480-sample chunk, gain =
  * round(10*sqrt(ref)/sqrt(mean of the last `window_size` chunk RMS values))/10, clamped, samples clamped to

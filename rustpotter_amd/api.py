@@ -109,7 +109,7 @@ SYMBOLS = [
     "rp_model_new", "rp_model_free", "rp_mlp_forward_batch", "rp_mlp_forward_windows", "rp_synth_pcm_batch", "rp_ctx_timing_enable", "rp_ctx_timing_read", "rp_ctx_timing_reset",
     "rp_version", "rp_stream_batch_new", "rp_stream_batch_free", "rp_stream_batch_process", "rp_stream_batch_reset",
     "rp_stream_batch_chunks_seen", "rp_resampler_frame_lengths", "rp_resample_batch",
-    "rp_wakeword_model_train", "rp_stream_batch_set_input", "rp_stream_batch_samples_per_chunk",
+    "rp_wakeword_model_train", "rp_wakeword_model_train_batch", "rp_mlp_train_batch", "rp_train_batch_last_profile", "rp_stream_batch_set_input", "rp_stream_batch_samples_per_chunk",
     "rp_batch_detect_multi", "rp_batch_detect_model", "rp_batch_detect_sharded",
     "rp_stream_batch_new_multi", "rp_stream_batch_process_multi",
     "rp_stream_batch_set_filters", "rp_stream_batch_levels",
@@ -216,6 +216,13 @@ def load_library():
     L.rp_wakeword_model_train.argtypes = [vp, C.POINTER(_TrainOptions), C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                           C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                           C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), fp, fp]
+    L.rp_wakeword_model_train_batch.argtypes = [vp, C.POINTER(_TrainOptions), C.c_size_t, C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t), fp, fp]
+    L.rp_mlp_train_batch.argtypes = [vp, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp,
+                                     C.POINTER(C.c_int32), fp, C.c_float, C.c_size_t, fp]
+    L.rp_train_batch_last_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.rp_batch_detect_multi.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp),
                                         C.POINTER(_DetectorConfig), fp, fp, vp, vp, vp, C.c_int]
     L.rp_batch_detect_sharded.argtypes = [C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(C.c_size_t), C.c_size_t,
@@ -1244,6 +1251,89 @@ class BatchContext:
         data = C.string_at(out, out_len.value)
         self._L.rp_buffer_free(out)
         return data, loss.value, acc.value
+
+    def train_wakeword_models(self, models, m_type="medium", learning_rate=0.027, epochs=10, mfcc_size=16, seeds=None, prev_models=None):
+        """train_wakeword_model for many models in one call (rp_wakeword_model_train_batch): models = list of (train, test), each an
+        ordered {file name: wav bytes}; seeds: one per model (None: 1 + index); prev_models: .rpw bytes or None per model (None: none
+        at all).  Returns [(.rpw bytes, last loss, test accuracy)], per model what train_wakeword_model gives for its samples, seed and
+        previous model.  One model that cannot be trained fails the whole call."""
+        W = len(models)
+
+        def pack(sets):
+            names = [k.encode() for d in sets for k in d]
+            bufs = [bytes(v) for d in sets for v in d.values()]
+            n = len(names)
+            return ((C.c_size_t * W)(*[len(d) for d in sets]), (C.c_char_p * n)(*names), (C.c_char_p * n)(*bufs),
+                    (C.c_size_t * n)(*[len(b) for b in bufs]))
+        trc, trn, trb, trl = pack([m[0] for m in models])
+        tec, ten, teb, tel = pack([m[1] for m in models])
+        c_seeds = None if seeds is None else (C.c_uint64 * W)(*seeds)
+        prev = prev_lens = None
+        if prev_models is not None:
+            prev = (C.c_char_p * W)(*[None if p is None else bytes(p) for p in prev_models])
+            prev_lens = (C.c_size_t * W)(*[0 if p is None else len(p) for p in prev_models])
+        opt = _TrainOptions({"tiny": 0, "small": 1, "medium": 2, "large": 3}[m_type], learning_rate, epochs, 0, mfcc_size, 1)
+        out, out_lens = (C.c_void_p * W)(), (C.c_size_t * W)()
+        loss, acc = (C.c_float * W)(), (C.c_float * W)()
+        if self._L.rp_wakeword_model_train_batch(self._h, C.byref(opt), W, c_seeds, trc, trn, trb, trl, tec, ten, teb, tel, prev, prev_lens,
+                                                 out, out_lens, loss, acc) < 0:
+            raise _err()
+        res = []
+        for w in range(W):
+            res.append((C.string_at(out[w], out_lens[w]), loss[w], acc[w]))
+            self._L.rp_buffer_free(out[w])
+        return res
+
+    def mlp_train_batch(self, dims, x, labels, params, learning_rate, epochs):
+        """The epochs alone for many MLPs in one call (rp_mlp_train_batch): per model dims = its layer widths (input first, label count
+        last), x [rows][dims[0]], labels [rows] and params = [(weight [out][in], bias [out]) per layer].  Returns (params in the same
+        form, [loss of the last epoch per model])."""
+        import numpy as np
+        W = len(dims)
+        i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        n_layers = np.array([len(d) - 1 for d in dims], np.int32)
+        cdims = np.zeros((W, 5), np.int32)
+        for w, d in enumerate(dims):
+            if not 2 <= len(d) <= 5:
+                raise RustpotterError("an MLP of 1 to 4 layers is required")
+            cdims[w, :len(d)] = d
+        xs = [np.ascontiguousarray(a, np.float32).reshape(-1, d[0]) for a, d in zip(x, dims)]
+        n_rows = np.array([a.shape[0] for a in xs], np.int32)
+        cx = np.ascontiguousarray(np.concatenate([a.ravel() for a in xs])) if W else np.zeros(0, np.float32)
+        cl = np.ascontiguousarray(np.concatenate([np.asarray(l, np.int32).ravel() for l in labels])) if W else np.zeros(0, np.int32)
+        if cl.size != int(n_rows.sum()):
+            raise RustpotterError("one label per row is required")
+        flat = []
+        for w, d in enumerate(dims):
+            for l, (wt, b) in enumerate(params[w]):
+                wt, b = np.asarray(wt, np.float32), np.asarray(b, np.float32)
+                if wt.shape != (d[l + 1], d[l]) or b.shape != (d[l + 1],):
+                    raise RustpotterError("model %d layer %d: weight [out][in] and bias [out] are required" % (w, l))
+                flat += [wt.ravel(), b.ravel()]
+            if len(params[w]) != len(d) - 1:
+                raise RustpotterError("model %d: one (weight, bias) per layer is required" % w)
+        cp = np.ascontiguousarray(np.concatenate(flat)) if W else np.zeros(0, np.float32)
+        loss = np.zeros(W, np.float32)
+        if self._L.rp_mlp_train_batch(self._h, W, n_layers.ctypes.data_as(i32p), cdims.ctypes.data_as(i32p), n_rows.ctypes.data_as(i32p),
+                                      cx.ctypes.data_as(fp), cl.ctypes.data_as(i32p), cp.ctypes.data_as(fp), learning_rate, epochs,
+                                      loss.ctypes.data_as(fp)) < 0:
+            raise _err()
+        out, at = [], 0
+        for d in dims:
+            layers = []
+            for l in range(len(d) - 1):
+                nw, nb = d[l] * d[l + 1], d[l + 1]
+                layers.append((cp[at:at + nw].reshape(d[l + 1], d[l]).copy(), cp[at + nw:at + nw + nb].copy()))
+                at += nw + nb
+            out.append(layers)
+        return out, loss
+
+    def train_batch_profile(self):
+        """(ms of the feature stage, ms of the longest launch -- 0 unless timing is enabled --, launches) of the last batched training"""
+        f, m, n = C.c_double(), C.c_double(), C.c_int()
+        if self._L.rp_train_batch_last_profile(self._h, C.byref(f), C.byref(m), C.byref(n)) < 0:
+            raise _err()
+        return f.value, m.value, n.value
 
     def frontend(self, pcm, filters_config, rms_level_ref, window_size):
         """Decode + gain normaliser + band-pass over whole streams -> (pcm f32, rms, gains)."""

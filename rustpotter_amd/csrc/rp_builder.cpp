@@ -311,30 +311,6 @@ std::vector<uint8_t> serialize_wakeword_model(const WakewordModelData &m) {
 // ------------------------------------------------------------- batched forms
 namespace {
 
-// The host's share of a batch (wav decoding, levels, CBOR) is independent per sample / per wakeword: up to 16 threads take indices from
-// one counter.  The first exception of a worker is rethrown on the calling thread.
-template <class F> void parallel_for(size_t n, F &&f) {
-    const size_t nt = std::min<size_t>({(size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency()), n / 4});
-    if (nt <= 1) { for (size_t i = 0; i < n; ++i) f(i); return; }
-    std::atomic<size_t> next{0};
-    std::atomic<bool> failed{false};
-    std::exception_ptr error;
-    auto work = [&] {
-        try {
-            for (size_t i; !failed.load() && (i = next.fetch_add(1)) < n;) f(i);
-        } catch (...) {
-            if (!failed.exchange(true)) error = std::current_exception();
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (size_t t = 1; t < nt; ++t) pool.emplace_back(work);
-    } catch (...) {}   // fewer threads than asked for: the others take the work
-    work();
-    for (std::thread &t : pool) t.join();
-    if (error) std::rethrow_exception(error);
-}
-
 // The averaging kernel's index arrays for W wakewords whose templates lie, in fold order, in one array of rows.
 struct AvgPlan {
     size_t W = 0, nT = 0, rows = 0, avg_rows = 0;

@@ -420,6 +420,95 @@ int rp_wakeword_model_train(rp_ctx *ctx, const rp_train_options *options, size_t
     });
 }
 
+int rp_wakeword_model_train_batch(rp_ctx *ctx, const rp_train_options *options, size_t n_models, const uint64_t *seeds,
+                                  const size_t *train_counts, const char *const *train_names, const uint8_t *const *train_wavs,
+                                  const size_t *train_lens, const size_t *test_counts, const char *const *test_names,
+                                  const uint8_t *const *test_wavs, const size_t *test_lens, const uint8_t *const *prev_models,
+                                  const size_t *prev_model_lens, uint8_t **out_rpw, size_t *out_lens, float *final_loss, float *test_accuracy) {
+    return guarded([&]() -> int {
+        if (!ctx) { set_last_error("null handle"); return -1; }
+        if (n_models && (!options || !train_counts || !test_counts || !out_rpw || !out_lens || (prev_models && !prev_model_lens))) {
+            set_last_error("null argument");
+            return -1;
+        }
+        size_t n_train = 0, n_test = 0;
+        for (size_t w = 0; w < n_models; ++w) { out_rpw[w] = nullptr; out_lens[w] = 0; n_train += train_counts[w]; n_test += test_counts[w]; }
+        if ((n_train && (!train_names || !train_wavs || !train_lens)) || (n_test && (!test_names || !test_wavs || !test_lens))) {
+            set_last_error("null argument");
+            return -1;
+        }
+        std::vector<WakewordModelData> prev(prev_models ? n_models : 0), models;
+        std::vector<const WakewordModelData *> prev_of(n_models, nullptr);
+        for (size_t w = 0; prev_models && w < n_models; ++w) {
+            if (!prev_models[w]) continue;
+            RpwKind kind; WakewordRefData ref; std::string err;
+            if (!parse_rpw(prev_models[w], prev_model_lens[w], &kind, &ref, &prev[w], &err)) { set_last_error("model " + std::to_string(w) + ": " + err); return -1; }
+            if (kind != RpwKind::Model) { set_last_error("model " + std::to_string(w) + ": the file to train from is not a wakeword model"); return -1; }
+            prev_of[w] = &prev[w];
+        }
+        if (!train_wakeword_models(ctx->impl.get(), *options, n_models, seeds, train_counts, train_names, train_wavs, train_lens, test_counts,
+                                   test_names, test_wavs, test_lens, prev_of.data(), &models, final_loss, test_accuracy)) return -1;
+        std::vector<std::vector<uint8_t>> bytes(n_models);   // everything that can throw comes before the first buffer is handed out
+        parallel_for(n_models, [&](size_t w) { bytes[w] = serialize_wakeword_model(models[w]); });
+        for (size_t w = 0; w < n_models; ++w) {
+            uint8_t *p = static_cast<uint8_t *>(std::malloc(bytes[w].size()));
+            if (!p) {
+                for (size_t v = 0; v < w; ++v) { std::free(out_rpw[v]); out_rpw[v] = nullptr; out_lens[v] = 0; }
+                set_last_error("out of host memory");
+                return -1;
+            }
+            std::memcpy(p, bytes[w].data(), bytes[w].size());
+            out_rpw[w] = p; out_lens[w] = bytes[w].size();
+        }
+        return 0;
+    });
+}
+
+int rp_mlp_train_batch(rp_ctx *ctx, size_t n_models, const int32_t *n_layers, const int32_t *dims, const int32_t *n_rows, const float *x,
+                       const int32_t *labels, float *params, float learning_rate, size_t epochs, float *final_loss) {
+    return guarded([&]() -> int {
+        if (!ctx) { set_last_error("null handle"); return -1; }
+        if (n_models && (!n_layers || !dims || !n_rows || !x || !labels || !params)) { set_last_error("null argument"); return -1; }
+        ctx->impl->train_feature_ms = 0.0;
+        std::vector<MlpTrainItem> items(n_models);
+        std::vector<std::vector<float>> loss_rows(n_models);
+        size_t x_at = 0, row_at = 0, param_at = 0;
+        for (size_t w = 0; w < n_models; ++w) {
+            MlpTrainItem &it = items[w];
+            const std::string who = "model " + std::to_string(w) + ": ";
+            if (n_layers[w] < 1 || n_layers[w] > kTrainMaxLayers) { set_last_error(who + "an MLP of 1 to 4 layers is required"); return -1; }
+            if (n_rows[w] < 1) { set_last_error(who + "no rows to train on"); return -1; }
+            it.n_layers = n_layers[w];
+            for (int l = 0; l <= it.n_layers; ++l) {
+                it.dims[l] = dims[w * (kTrainMaxLayers + 1) + l];
+                if (it.dims[l] < 1) { set_last_error(who + "layer widths must be >= 1"); return -1; }
+            }
+            it.B = (size_t)n_rows[w];
+            it.x = x + x_at; it.labels = labels + row_at; it.params = params + param_at;
+            loss_rows[w].assign(it.B, 0.f);
+            it.loss_rows = loss_rows[w].data();
+            x_at += it.B * (size_t)it.dims[0]; row_at += it.B;
+            for (int l = 0; l < it.n_layers; ++l) param_at += ((size_t)it.dims[l] + 1) * (size_t)it.dims[l + 1];
+        }
+        if (!train_mlp_batch(ctx->impl.get(), items, learning_rate, epochs)) return -1;
+        for (size_t w = 0; final_loss && w < n_models; ++w) {   // the mean over the rows, summed in order (train_wakeword_model)
+            float s = 0.f;
+            for (float v : loss_rows[w]) s += v;
+            final_loss[w] = epochs ? s / (float)items[w].B : NAN;
+        }
+        return 0;
+    });
+}
+
+int rp_train_batch_last_profile(rp_ctx *ctx, double *feature_ms, double *longest_launch_ms, int *launches) {
+    if (!ctx) { set_last_error("null handle"); return -1; }
+    const Ctx *c = ctx->impl.get();
+    if (feature_ms) *feature_ms = c->train_feature_ms;
+    if (longest_launch_ms) *longest_launch_ms = c->train_longest_launch_ms;
+    if (launches) *launches = c->train_launches;
+    return 0;
+}
+
 int rp_frontend_batch(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                       const rp_filters_config *filters, float rms_level_ref, size_t window_size, float *pcm_out,
                       size_t out_stride, float *rms, float *gains) {

@@ -2,8 +2,11 @@
 // context, and the C++ mirror of the reference's `Rustpotter` (src/detector.rs).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <exception>
 #include <map>
+#include <thread>
 #include <tuple>
 #include <memory>
 #include <string>
@@ -89,6 +92,49 @@ bool train_wakeword_model(Ctx *ctx, const rp_train_options &opt, size_t n_train,
                           const uint8_t *const *train_wavs, const size_t *train_lens, size_t n_test, const char *const *test_names,
                           const uint8_t *const *test_wavs, const size_t *test_lens, const WakewordModelData *prev,
                           WakewordModelData *out, float *final_loss, float *test_accuracy);
+// train_wakeword_model for W models in one call: the samples of all models follow each other (train_counts / test_counts [W]); seeds [W]
+// (null: opt.seed + w); prev [W] (null or an entry null: none).  The epochs of all models run in train_batch_kernel.  A model the single
+// call refuses fails the call with that error behind "model <index>: ".
+bool train_wakeword_models(Ctx *ctx, const rp_train_options &opt, size_t W, const uint64_t *seeds, const size_t *train_counts,
+                           const char *const *train_names, const uint8_t *const *train_wavs, const size_t *train_lens,
+                           const size_t *test_counts, const char *const *test_names, const uint8_t *const *test_wavs, const size_t *test_lens,
+                           const WakewordModelData *const *prev, std::vector<WakewordModelData> *out, float *final_loss, float *test_accuracy);
+// The epochs alone: one MLP per item, HOST arrays.  params in / out: per layer, weight [out][in] then bias [out]; loss_rows [B] (null: not
+// wanted): the rows of the last epoch's loss; tlog [Bt][dims[n_layers]] (null: no test forward): the logits of the test rows xt under the
+// final weights.  One upload and one download on the context's stream; launches of at most E epochs (rp_train.cpp).
+struct MlpTrainItem {
+    int n_layers = 0;
+    int dims[kTrainMaxLayers + 1] = {0, 0, 0, 0, 0};
+    size_t B = 0, Bt = 0;
+    const float *x = nullptr, *xt = nullptr;
+    const int32_t *labels = nullptr;
+    float *params = nullptr, *loss_rows = nullptr, *tlog = nullptr;
+};
+bool train_mlp_batch(Ctx *ctx, const std::vector<MlpTrainItem> &items, float learning_rate, size_t epochs);
+
+// The host's share of a batch (wav decoding, levels, weight draws, CBOR) is independent per sample / per wakeword / per model: up to 16 threads take indices from
+// one counter.  The first exception of a worker is rethrown on the calling thread.
+template <class F> void parallel_for(size_t n, F &&f) {
+    const size_t nt = std::min<size_t>({(size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency()), n / 4});
+    if (nt <= 1) { for (size_t i = 0; i < n; ++i) f(i); return; }
+    std::atomic<size_t> next{0};
+    std::atomic<bool> failed{false};
+    std::exception_ptr error;
+    auto work = [&] {
+        try {
+            for (size_t i; !failed.load() && (i = next.fetch_add(1)) < n;) f(i);
+        } catch (...) {
+            if (!failed.exchange(true)) error = std::current_exception();
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (size_t t = 1; t < nt; ++t) pool.emplace_back(work);
+    } catch (...) {}   // fewer threads than asked for: the others take the work
+    work();
+    for (std::thread &t : pool) t.join();
+    if (error) std::rethrow_exception(error);
+}
 
 void set_last_error(const std::string &msg);
 const std::string &last_error();
@@ -167,6 +213,11 @@ struct Ctx {
     // LDS (one slice per workgroup of that launch); page-locked staging (at most 128 MB) the padded samples pass through
     DevBuf ws_enrol, ws_enrol_pcm, ws_enrol_nf, ws_enrol_dst, ws_enrol_raw, ws_enrol_i32, ws_enrol_i64, ws_avg_matrix;
     PinBuf enrol_stage;
+    // batched training (rp_train.cpp): the job table and every model's rows, weights and intermediates (TrainJob, rp_kernels.h); what the
+    // last call spent (rp_train_batch_last_profile): its feature stage on the host clock and, with timing enabled, its launches
+    DevBuf ws_train;
+    double train_feature_ms = 0.0, train_longest_launch_ms = 0.0;
+    int train_launches = 0;
 
     static Ctx *create(int device, int flags);
     ~Ctx();

@@ -768,6 +768,24 @@ hipError_t launch_train_forward(hipStream_t st, const float *x, size_t B, int n_
                                 float *const *Bv, float *const *act);
 hipError_t launch_train_step(hipStream_t st, const float *x, const int32_t *labels, size_t B, int n_layers, const int *dims,
                              float *const *W, float *const *Bv, float *const *act, float *const *dz, float lr, float *loss_rows);
+// The same for many models in one launch (train_batch_kernel, rp_train_batch.hip): one workgroup per job, the epochs inside
+// the kernel.  A job's state lies in its own pieces of one workspace `ws` of floats; every offset counts floats from ws and is a multiple
+// of 4 (16 bytes).  x [B][dims[0]] and xt [Bt][dims[0]]: train and test rows; labels [B] int32; w[l] [dims[l+1]][dims[l]] and b[l]
+// [dims[l+1]]; act[l] [max(B, Bt)][dims[l+1]]; dz[l] [B][dims[l+1]]; loss [B]: the rows of the last epoch's loss; tlog [Bt][dims[n_layers]]:
+// the test rows' logits under the weights as the launch leaves them.
+constexpr int kTrainBatchThreads = 1024;
+constexpr int kTrainMaxLayers = 4;
+struct TrainJob {
+    int n_layers, B, Bt, pad0;
+    int dims[kTrainMaxLayers + 1], pad1[3];
+    long long x, xt, labels, loss, tlog, pad2;
+    long long w[kTrainMaxLayers], b[kTrainMaxLayers], act[kTrainMaxLayers], dz[kTrainMaxLayers];
+};
+static_assert(sizeof(TrainJob) % 16 == 0, "the job table precedes 16-byte aligned rows in the workspace");
+// `epochs` steps of every job (the bits of launch_train_step, whatever the cut into launches), then, with test_forward, the forward of
+// the test rows into tlog.  grid workgroups walk the n_jobs jobs; nothing but the workgroup of a job touches its pieces.
+hipError_t launch_train_batch(hipStream_t st, const TrainJob *jobs, size_t n_jobs, unsigned grid, float *ws, float lr, int epochs,
+                              int test_forward);
 // WakewordNN::run_detection (src/wakewords/nn/wakeword_nn.rs:39-159) over whole batches: windows of L frames cut from
 // mfcc [S][frame_pitch][K] and mean-normalised into rows (first_row .. first_row+n_rows of the S*n_win windows), and the
 // label / score logic on the logits: agg = score where the detection is valid (label != none, score >= threshold,

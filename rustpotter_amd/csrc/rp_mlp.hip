@@ -247,18 +247,7 @@ __global__ __launch_bounds__(64) void train_softmax_grad_kernel(const float *__r
                                                                 size_t B, int C, float *__restrict__ dz, float *__restrict__ loss_rows) {
     const size_t b = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const float *x = logits + b * C;
-    float mx = x[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
-    const float lse = logf(se);
-    const int lab = labels[b];
-    for (int c = 0; c < C; ++c) {
-        const float lsm = (x[c] - mx) - lse;
-        if (c == lab) loss_rows[b] = -lsm;
-        dz[b * C + c] = (expf(lsm) - (c == lab ? 1.f : 0.f)) / (float)B;
-    }
+    train_softmax_row(logits + b * C, labels[b], B, C, dz + b * C, loss_rows + b);
 }
 
 // dZprev[b][i] = A_prev[b][i] > 0 ? sum_o dZ[b][o] * W[o][i] : 0     (ReLU backward through the layer's input)

@@ -1,4 +1,4 @@
-// rp_mlp_dev.h -- private to the wakeword-model kernels (rp_mlp.hip, rp_mlp_windows.hip, rp_mlp_stream.hip, rp_mlp_bank_stream.hip): the
+// rp_mlp_dev.h -- private to the wakeword-model kernels (rp_mlp.hip, rp_mlp_windows.hip, rp_mlp_stream.hip, rp_mlp_bank_stream.hip, rp_train_batch.hip): the
 // operand splits, the tail layers, the window means' sums, pieces of the staged-frame kernels, and what mlp_route (rp_mlp.hip) needs from
 // rp_mlp_windows.hip.  DESIGN.md §4.4.
 #pragma once
@@ -218,6 +218,21 @@ __device__ __forceinline__ float mlp_windows_layer1(float sum, const float4 *mu,
     v += bias1;
     if (relu1 && v < 0.f) v = 0.f;
     return v;
+}
+
+// ---- one row of the trainer's loss (train_softmax_grad_kernel in rp_mlp.hip, train_batch_kernel in rp_train_batch.hip): log_softmax
+// (x - max - ln(sum exp(x - max))), loss_row = -log_sm[label], dlogits = (softmax - onehot) / B
+__device__ __forceinline__ void train_softmax_row(const float *x, int lab, size_t B, int C, float *dz, float *loss_row) {
+    float mx = x[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
+    const float lse = logf(se);
+    for (int c = 0; c < C; ++c) {
+        const float lsm = (x[c] - mx) - lse;
+        if (c == lab) *loss_row = -lsm;
+        dz[c] = (expf(lsm) - (c == lab ? 1.f : 0.f)) / (float)B;
+    }
 }
 
 }  // namespace rp
