@@ -7,6 +7,10 @@ ragged tail.  The bar is the one of tests/test_gpu_parity.py: detections exact i
 relative.  A case whose decision hangs on a score closer than 1e-5 to a threshold is counted as a tie, not a failure.
 
     python tests/sweep_parity.py --cases 300 --seed 1        # on the GPU box
+
+The bank family (wakeword banks, wakeword sets, live batches over them) has sweeps of its own further down: run_bank_sweep,
+run_bank_sets_sweep, run_live_bank_sweep, run_live_bank_sets_sweep.  Their cases steer the thresholds from the oracle's scores so that
+streams fire, and a case is set aside only by the oracle's verdict, before the device runs (see BANK_MARGIN).
 """
 import argparse
 import os
@@ -1157,8 +1161,1212 @@ def run_model_sweep(ra, n_cases, seed, verbose=False, ctx=None):
     return n_cases, total
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# The bank family: wakeword banks, wakeword sets and live batches over them against the oracle's chunked single-stream
+# detector (orc.Detector, one per stream) -- the only yardstick for decisions here.  A case is built, its thresholds are
+# steered from the ORACLE's own scores so that streams fire, and whether it may be set aside is decided from the oracle
+# alone before the product runs: a case whose oracle events change when every threshold is scaled by 1 +- 1e-4 (ten times
+# the 1e-5 parity gate) is threshold-sensitive, skipped and counted.  Every case that is kept must match exactly in its
+# events and within 1e-5 in its scores; there is no allowance for ties on kept cases.
+BANK_MARGIN = 1e-4
+BANK_FAMILIES = ("bank", "bank_sets", "live_bank", "live_bank_sets", "model_bank")
+# what runs in the suite: (seed, cases, {case: (streams, chunks)}) -- the last case has 70 streams, more than one 64-row workgroup of
+# the per-stream kernels.  The seeds are chosen so that the oracle sets no case aside and the cases exercise the decisions
+# (tests/test_bank_sweep_cases.py, CPU only).  A few drawn values are pinned per case so that six cases reach every mfcc_size, the bands 3
+# and 6, eager, a percentile mode and an exact twin pair in a set; everything else is as drawn.
+# The live families also pin: a call of 11 chunks (33 new windows: past two 16-row tiles and the 32-window route change), both kinds of
+# replacement, an input rate behind the resampler; the 70-stream case has events and templates of 63 / 64 / 65 frames.
+_BANK_PINS = {0: dict(K=5, band=3, eager=True), 1: dict(K=13, band=6, score_mode="p90", max_cpc=11), 2: dict(K=16, band=4, twin="exact", rate=16000, filters="none"),
+              3: dict(K=5, band=6, filters="gain"), 4: dict(K=16, band=5, rate=48000, replace=True), 5: dict(S=70, n_chunks=60, vad_mode=None, events=True, edge=True)}
+_MODEL_PINS = {0: dict(eager=True, max_cpc=11), 1: dict(fmt="f32", events=False), 3: dict(S=70, n_chunks=40, vad_mode=None, events=True)}
+BANK_SUITE = {"bank": (4, 6, _BANK_PINS), "bank_sets": (4, 6, _BANK_PINS), "live_bank": (2, 6, _BANK_PINS), "live_bank_sets": (5, 6, _BANK_PINS),
+              "model_bank": (1, 4, _MODEL_PINS)}
+_BANK_SALT = {"bank": 101, "bank_sets": 102, "live_bank": 103, "live_bank_sets": 104, "model_bank": 105}
+_BANK_MEMO = {}
+
+
+def rel_close(got, want, tol=1e-5):
+    """the project's parity gate: |got - want| <= tol * |want|"""
+    return abs(float(got) - float(want)) <= tol * abs(float(want))
+
+
+def _bank_wakeword(rng, K, name, T=None, top=100, force_len=None):
+    from collections import OrderedDict
+    from oracle import rp_oracle as orc
+    if T is None:
+        T = int(rng.integers(1, 7))
+    edge = [63, 64, 65]
+    if rng.random() < 0.35:
+        lens = np.full(T, int(rng.choice(edge + [int(rng.integers(12, top + 1))])))
+    else:
+        lens = np.array([int(rng.choice(edge)) if rng.random() < 0.2 else int(rng.integers(12, top + 1)) for _ in range(T)])
+    lens = np.minimum(lens, top)   # (the short streams of the 70-stream cases: windows that fit)
+    if force_len:   # (a pinned case: every template at a 64-frame edge)
+        lens = np.full(T, int(force_len))
+    us = [_utterance(rng, 480 * ((int(L) + 5) // 3)) for L in lens]
+    feats = OrderedDict(("s%02d.wav" % i, orc.normalize(orc.mfcc_stream(u, K))[:int(L)]) for i, (u, L) in enumerate(zip(us, lens)))
+    kind = int(rng.integers(3))   # no averaged template; the builder's; a prefix shorter than the window
+    avg = None
+    if kind == 1:
+        avg = orc.average_templates(feats)
+    elif kind == 2 and int(lens.max()) > 10:
+        avg = feats["s%02d.wav" % int(np.argmax(lens))][:int(rng.integers(10, int(lens.max())))].copy()
+    # the own thresholds are steered later (True: this wakeword gets a value of its own)
+    return {"name": name, "samples_features": feats, "avg_features": avg, "threshold": bool(rng.random() < 0.4),
+            "avg_threshold": bool(rng.random() < 0.4), "rms_level": float(rng.uniform(0.01, 0.2)), "utts": us, "max_len": int(lens.max())}
+
+
+def _bank_twin(rng, w, name, exact=None):
+    """another bank entry that passes where `w` passes: an exact copy (equal proposals: the first slot of a set wins) or the
+    same utterances a little louder"""
+    from collections import OrderedDict
+    from oracle import rp_oracle as orc
+    t = dict(w, name=name)
+    if rng.random() < 0.5 and not exact:
+        K = next(iter(w["samples_features"].values())).shape[1]
+        us = [(u * np.float32(1.1) + (rng.standard_normal(len(u)) * 0.002).astype(np.float32)).astype(np.float32) for u in w["utts"]]
+        t["samples_features"] = OrderedDict((k, orc.normalize(orc.mfcc_stream(u, K))[:len(f)]) for (k, f), u in zip(w["samples_features"].items(), us))
+        t["utts"] = us
+        if w["avg_features"] is not None:
+            t["avg_features"] = w["avg_features"].copy()
+    return t
+
+
+def _plant(rng, x, u, at):
+    u = u * np.float32(rng.uniform(0.7, 1.2))
+    at = max(0, min(int(at), len(x) - len(u)))
+    x[at:at + len(u)] += u[:len(x) - at]
+
+
+def _quantile_or(values, q, default):
+    """the q-quantile of the scores, moved into the middle of the widest gap between the few scores around it: a threshold taken
+    from the scores themselves would otherwise sit ON one of them"""
+    v = np.sort(np.concatenate([np.ravel(a) for a in values]).astype(np.float64)) if len(values) else np.zeros(0)
+    if v.size < 2:
+        return default
+    i = int(q * (v.size - 1))
+    lo, hi = max(0, i - 3), min(v.size - 1, i + 4)
+    g = int(np.argmax(np.diff(v[lo:hi + 1]))) + lo
+    return float(0.5 * (v[g] + v[g + 1]))
+
+
+def make_bank_case(rng, models=False, S=None, n_chunks=None, pin=None):
+    """One case of the bank family: a bank of W wakewords, a detector config, S streams with per-stream indices and rows of
+    a set, the plan of a live run (pieces, resets, re-targets, puts, filters, input rate) and thresholds steered from the
+    oracle's scores.  S / n_chunks: fixed by the caller (the 70-stream cases of the suite).  pin: values that replace what was
+    drawn for K, band, eager, score_mode, vad_mode, twin ("exact"), filters ("gain") -- the suite pins a few so that its six cases reach every build."""
+    from oracle import rp_oracle as orc
+    if models:
+        return _make_model_bank_case(rng, S=S, n_chunks=n_chunks, pin=pin)
+    pin = pin or {}
+    K = int(rng.choice([5, 5, 13, 16]))
+    band = 0 if rng.random() < 1.0 / 15 else int(rng.choice([3, 4, 5, 5, 6]))
+    K, band = pin.get("K", K), pin.get("band", band)
+    W = int(rng.integers(1, 9))
+    if pin.get("twin"):
+        W = max(W, 2)
+    if pin.get("replace"):   # (room for a wakeword that no stream holds)
+        W = max(W, 6)
+    top = 100 if n_chunks is None else max(12, min(100, n_chunks - n_chunks // 6))
+    big = int(rng.integers(W)) if rng.random() < 1.0 / 8 else -1
+    bank = []
+    for wi in range(W):
+        if wi == 1 and (rng.random() < 0.5 or pin.get("twin")):
+            bank.append(_bank_twin(rng, bank[0], "w1", exact=True if pin.get("twin") == "exact" else None))
+        else:
+            bank.append(_bank_wakeword(rng, K, "w%d" % wi, T=32 if wi == big else None, top=top, force_len=(63 + (W + wi) % 3) if pin.get("edge") and wi in (0, 2) else None))
+    cfg = dict(threshold=0.5, avg_threshold=0.0, min_scores=int(rng.integers(1, 7)), eager=bool(rng.random() < 0.3),
+               score_ref=float(rng.uniform(0.15, 0.3)), band_size=band, score_mode=str(rng.choice(MODES)),
+               vad_mode=[None, None, None, "easy", "medium", "hard"][int(rng.integers(6))])
+    cfg.update({k: pin[k] for k in ("eager", "score_mode", "vad_mode") if k in pin})
+    wide = S is not None
+    if S is None:
+        S = int(rng.integers(3, 10))
+    # what joins a running bank later: appended wakewords, and replacements of held / unheld ones
+    extra = [_bank_wakeword(rng, K, "x%d" % i, top=top) for i in range(int(rng.integers(1, 3)))] if rng.random() < 0.5 else []
+    repl = [_bank_wakeword(rng, K, "r%d" % i, top=top) for i in range(2)] if (rng.random() < 0.5 or pin.get("replace")) else []
+    # indices: two streams share a wakeword, one has -1, one an index >= W ("no wakeword"), the others are random
+    idx = [int(v) for v in rng.integers(0, W, size=S)]
+    idx[1] = idx[0]
+    idx[2] = -1
+    outside = int(rng.integers(S)) if S > 3 else -1
+    if outside in (0, 1, 2):
+        outside = 3 if S > 3 else -1
+    # sets: rows with empty slots in the middle, one row all empty, wakewords of different window lengths in a row
+    set_size = int(rng.integers(1, 9))
+    rows = np.full((S, set_size), -1, np.int32)
+    for s in range(S):
+        for j in range(set_size):
+            if rng.random() < 0.6:
+                rows[s, j] = int(rng.integers(W))
+        if idx[s] >= 0 and not (rows[s] == idx[s]).any():
+            rows[s, int(rng.integers(set_size))] = idx[s]
+        if set_size >= 3:
+            rows[s, int(rng.integers(1, set_size - 1))] = -1
+    rows[2] = -1
+    if W >= 2 and set_size >= 2:   # the twin pair in one row, in both orders
+        rows[0, 0], rows[0, set_size - 1] = 0, 1
+        rows[1, 0], rows[1, set_size - 1] = 1, 0
+    # the live plan: a stream's wakeword over time
+    lens_s = [int(n_chunks or rng.integers(60, 141)) for _ in range(S)]
+    n_max = max(lens_s)
+    max_cpc = int(pin.get("max_cpc", rng.integers(2, 12)))
+    cuts, pos = [], 0
+    while pos < n_max:
+        n = min(int(rng.integers(1, max_cpc + 1)), n_max - pos)
+        if "max_cpc" in pin and len(cuts) % 4 == 3:   # (a pinned case: calls of the pinned size do occur)
+            n = min(max_cpc, n_max - pos)
+        cuts.append(pos)
+        pos += n
+    cuts.append(n_max)
+    events = {}   # position in chunks (one of `cuts`) -> operations in order
+
+    def at_cut(lo, hi):
+        c = [p for p in cuts[1:-1] if lo <= p < hi]
+        return int(c[int(rng.integers(len(c)))]) if c else None
+
+    plants = [[] for _ in range(S)]   # (chunk, wakeword dict)
+    hold = list(idx)   # the plan's state
+    all_ww = bank + extra
+    n_ev = 0 if ((wide and not pin.get("events")) or rng.random() < 0.3) else int(rng.integers(1, 5))
+    if pin.get("events") or pin.get("replace"):
+        n_ev = max(n_ev, 4)
+    first_app = None
+    if extra and n_ev:
+        first_app = at_cut(5, n_max // 2)
+        if first_app is not None:
+            events.setdefault(first_app, []).append(("append", list(range(W, W + len(extra))), bool(rng.random() < 0.4)))
+    touched = set()
+    retarget = {}
+    replaced, targets = set(), set()
+    for ei in range(n_ev):
+        s = int(rng.integers(S))
+        forced = ["replace_held", "replace_unheld"][ei] if pin.get("replace") and ei < 2 else None   # (a pinned case: both kinds of replacement)
+        if forced:
+            s = next((t for t in range(S) if t not in touched and t != outside and (forced == "replace_unheld" or (hold[t] >= 0 and hold[t] != big))), s)
+        if s in touched or s == outside:
+            continue
+        p = at_cut(8, max(9, lens_s[s] - min(45, lens_s[s] // 2)))
+        if p is None:
+            continue
+        kind = forced or str(rng.choice(["reset", "retarget", "retarget", "gap", "replace_held", "replace_unheld"]))
+        touched.add(s)
+        if kind == "reset":
+            events.setdefault(p, []).append(("reset", s))
+            retarget[s] = (p, hold[s])
+        elif kind == "retarget":
+            pool = W + len(extra) if (first_app is not None and p > first_app) else W
+            j = int(rng.integers(pool))
+            if j in replaced:
+                continue
+            targets.add(j)
+            events.setdefault(p, []).append(("set", s, j))
+            retarget[s] = (p, j)
+        elif kind == "gap":
+            q = at_cut(p + 1, p + 12)
+            if q is None:
+                continue
+            j = hold[s] if hold[s] >= 0 else int(rng.integers(W))
+            if j in replaced:
+                continue
+            targets.add(j)
+            events.setdefault(p, []).append(("set", s, -1))
+            events.setdefault(q, []).append(("set", s, j))
+            retarget[s] = (q, j)
+        elif repl and kind == "replace_held" and hold[s] >= 0 and hold[s] != big:
+            w = hold[s]
+            if w in replaced or w in targets:
+                continue
+            who = [t for t in range(S) if hold[t] == w and t != outside]
+            if any(t in touched for t in who if t != s):
+                continue
+            touched.update(who)
+            replaced.add(w)
+            events.setdefault(p, []).append(("replace", w, 0, who))
+            for t in who:
+                retarget[t] = (p, ("r", 0))
+        elif repl and kind == "replace_unheld":
+            free = [w for w in range(W) if w not in hold and w not in targets and w not in replaced]
+            if free:
+                replaced.add(free[0])
+                events.setdefault(p, []).append(("replace", free[0], 1, []))
+    # audio: noise + utterances of the stream's own wakeword and of another one; behind a reset / re-target an utterance
+    # of the wakeword the stream then holds
+    pcm = np.zeros((S, 480 * n_max), np.float32)
+    for s in range(S):
+        n = 480 * lens_s[s]
+        x = (rng.standard_normal(n) * rng.uniform(0.0005, 0.01)).astype(np.float32)
+        own = [bank[w] for w in ([idx[s]] if idx[s] >= 0 else []) + [int(v) for v in rows[s] if v >= 0][:2]]
+        split = retarget[s][0] if s in retarget else lens_s[s]
+        for w in own:
+            for _ in range(int(rng.integers(1, 3)) if not wide else 1):
+                u = w["utts"][int(rng.integers(len(w["utts"])))]
+                # (room behind it for the countdown of half a window, so that the detection is reported)
+                hi = max(1, 480 * split - len(u) - 160 * (w["max_len"] // 2 + 8))
+                _plant(rng, x, u, rng.integers(min(480 * 10, hi - 1), hi))   # (and noise in front of it: what a VAD calls background)
+        other = bank[int(rng.integers(W))]
+        _plant(rng, x, other["utts"][0], rng.integers(0, max(1, n - len(other["utts"][0]))))
+        if s in retarget:
+            p, j = retarget[s]
+            w = repl[j[1]] if isinstance(j, tuple) else (all_ww[j] if j >= 0 else None)
+            if w is not None:
+                u = w["utts"][int(rng.integers(len(w["utts"])))]
+                _plant(rng, x, u, 480 * (p + int(rng.integers(0, 3))))
+                if rng.random() < 0.5:
+                    _plant(rng, x, w["utts"][0], 480 * p + len(u) + 480 * int(rng.integers(20, 40)))
+        pcm[s, :n] = x
+        pcm[s, n:] = (rng.standard_normal(480 * n_max - n) * 0.001).astype(np.float32)
+    fmt = str(rng.choice(["f32", "i16", "i8", "i32"]))
+    raw = pcm
+    if fmt != "f32":
+        info = np.iinfo({"i16": np.int16, "i8": np.int8, "i32": np.int32}[fmt])
+        raw = np.clip(np.round(pcm.astype(np.float64) * (8.0 if fmt == "i8" else 1.0) * info.max), info.min, info.max).astype(info.dtype)
+    filters = None
+    if rng.random() < 1.0 / 3:
+        which = int(rng.integers(3))
+        filters = dict(gain_normalizer=which != 1, gain_ref=None, min_gain=float(rng.uniform(0.1, 0.5)), max_gain=float(rng.uniform(1.0, 3.0)),
+                       band_pass=which != 0, low_cutoff=float(rng.uniform(60, 200)), high_cutoff=float(rng.uniform(300, 3000)))
+    rate = int(rng.choice([48000, 22050, 8000])) if rng.random() < 0.25 else 16000
+    rate = int(pin.get("rate", rate))
+    if pin.get("filters") == "none":
+        filters = None
+    if pin.get("filters") == "gain":   # the gain normaliser alone at 16 kHz, where its levels can be held against the oracle's bit for bit
+        filters = dict(filters or dict(min_gain=0.2, max_gain=3.0, low_cutoff=80.0, high_cutoff=400.0), gain_normalizer=True, gain_ref=None, band_pass=False)
+        rate = 16000
+    if filters is not None and rate == 22050:   # (filters on a live batch need 30 ms input frames: the batch refuses them at 22.05 kHz)
+        rate = 48000
+    # thresholds: quantiles of the oracle's own scores of this case (never the product's)
+    dec = _to_f32(raw)
+    mf = [orc.mfcc_stream(dec[s], K) for s in range(S)]
+    # (a partial detection needs min_scores windows above the threshold: the more it needs, the lower the quantile)
+    q = float(rng.uniform(0.90, 0.995 - 0.015 * (cfg["min_scores"] - 1)))
+    if wide:   # short streams: an utterance's peak is a tenth of a stream's windows
+        q = float(rng.uniform(0.90, 0.91))
+    qa = float(rng.uniform(0.2, 0.7))
+    agg_of, avg_of = {}, {}
+    for s in range(S):
+        ever = set(([idx[s]] if idx[s] >= 0 else []) + [int(v) for v in rows[s] if v >= 0][:2])
+        if s in retarget:   # what the stream holds later in the live plan
+            j = retarget[s][1]
+            ever.add(W + len(extra) + j[1] if isinstance(j, tuple) else j)
+        for w in sorted(v for v in ever if v >= 0):
+            d = (all_ww + repl)[w]
+            tm = list(d["samples_features"].values())
+            agg_of.setdefault(w, []).append(orc.score_stream(mf[s], tm, band, cfg["score_ref"], cfg["score_mode"])[1])
+            if d["avg_features"] is not None:
+                L = d["max_len"]
+                avg_of.setdefault(w, []).append(np.array([orc.score_window(mf[s][i:i + L], d["avg_features"], band, cfg["score_ref"])
+                                                          for i in range(0, max(0, len(mf[s]) - L + 1))], np.float32))
+    # the config's threshold: the lowest of the wakewords' own q-quantiles, so that the wakeword that scores lowest still fires
+    cfg["threshold"] = min([_quantile_or(v, q, 0.5) for v in agg_of.values()] + [1.0]) if agg_of else 0.5
+    cfg["avg_threshold"] = 0.0 if rng.random() < 0.5 else _quantile_or([a for v in avg_of.values() for a in v], qa, 0.0)
+    for w, d in enumerate(all_ww + repl):
+        d["threshold"] = _quantile_or(agg_of.get(w, []), float(rng.uniform(0.90, q)), cfg["threshold"]) if d["threshold"] else None
+        d["avg_threshold"] = (0.0 if rng.random() < 0.4 else _quantile_or(avg_of.get(w, []), qa, 0.0)) if d["avg_threshold"] else None
+    if W >= 2 and bank[1]["utts"] is bank[0]["utts"]:   # the exact twin proposes exactly what its original proposes
+        bank[1]["threshold"], bank[1]["avg_threshold"] = bank[0]["threshold"], bank[0]["avg_threshold"]
+    # sets: an index outside the bank in a slot that is empty anyway (device arrays only: a host array refuses it)
+    rows_out = rows.copy()
+    if outside >= 0 and (rows[outside] < 0).any():
+        rows_out[outside, int(np.flatnonzero(rows[outside] < 0)[-1])] = W + 2
+    return dict(K=K, W=W, bank=bank, extra=extra, repl=repl, cfg=cfg, S=S, idx=idx, outside=outside, rows=rows, rows_out=rows_out, set_size=set_size,
+                pcm=raw, lens=lens_s, fmt=fmt, cuts=cuts, max_cpc=max_cpc, events=events, filters=filters, rate=rate, wide=wide)
+
+
+def bank_case(family, seed, ci, pin=None):
+    """the case of a sweep, memoised: the oracle-only test and the device sweeps of one process share it"""
+    pin = dict(pin or {})
+    key = (family, seed, ci, tuple(sorted(pin.items(), key=str)))
+    if key not in _BANK_MEMO:
+        S, n_chunks = pin.pop("S", None), pin.pop("n_chunks", None)
+        _BANK_MEMO[key] = make_bank_case(np.random.default_rng([seed, _BANK_SALT[family], ci]), models=family == "model_bank", S=S, n_chunks=n_chunks, pin=pin)
+    return _BANK_MEMO[key]
+
+
+def _scaled_ww(w, k):
+    return dict(w, threshold=None if w["threshold"] is None else w["threshold"] * k,
+                avg_threshold=None if w["avg_threshold"] is None else w["avg_threshold"] * k)
+
+
+def _bank_live_flags(case, family):
+    """what of the live plan a family uses: (events, filters, rate).  Sets take no gain normaliser (the batch refuses it); every
+    event of the plan runs under a sets batch too, the puts included."""
+    if not family.startswith("live"):
+        return {}, None, 16000
+    f = case["filters"]
+    if family == "live_bank_sets" and f is not None:
+        f = dict(f, gain_normalizer=False) if f["band_pass"] else None
+    return case["events"], f, case["rate"]
+
+
+def _set_row_after(case, s, j):
+    """the row a stream of the sets family is re-targeted to when the bank family's plan says `set s j`"""
+    row = case["rows"][s].copy()
+    if j < 0:
+        row[:] = -1
+    else:   # (an appended wakeword included: the plan re-targets to it only behind the put)
+        row[0] = j
+    return row
+
+
+def _stretch(x, rate, fi):
+    m = int(len(x) * rate / 16000) // fi * fi
+    y = np.interp(np.arange(m) * (16000.0 / rate), np.arange(len(x)), x).astype(np.float32)
+    return y
+
+
+def bank_live_input(case, family):
+    """-> (input [S][frames * fi] as the batch gets it, decoded f32 for the oracle, fi, MFCC frames per input frame)"""
+    _, _, rate = _bank_live_flags(case, family)
+    raw = case["pcm"]
+    if rate == 16000:
+        return raw, _to_f32(raw), 480, 3
+    fi, fo = {48000: (1440, 480), 22050: (882, 640), 8000: (240, 480)}[rate]
+    base = _to_f32(raw)
+    x = np.stack([_stretch(base[s], rate, fi) for s in range(case["S"])])
+    # no digital silence behind a resampler (see run_live_rate_sweep); the i8 cases are loud enough already
+    if raw.dtype == np.float32:
+        return x, x, fi, fo // 160
+    q = np.clip(np.round(x * 32767.0), -32768, 32767).astype(np.int16)
+    return q, q.astype(np.float32) / np.float32(32767.0), fi, fo // 160
+
+
+def bank_oracle_events(case, family, scale=1.0, detail=None):
+    """The oracle's side of a family: one orc.Detector per stream, fed chunk by chunk, with the plan's operations modelled as the
+    hand-written tests model them (reset: Detector.reset; re-target and a replaced wakeword: remove + add_ref, as
+    tests/test_gpu_bank_filters.py::test_slots_keep_their_window; a set: remove all + add in slot order).
+    -> per stream [(input frame, counter, wakeword name, score, avg_score)].  detail: a dict that receives, per stream, the input
+    frames of its resets / re-targets."""
+    from oracle import rp_oracle as orc
+    c = case["cfg"]
+    events, filters, rate = _bank_live_flags(case, family)
+    sets = family.endswith("sets")
+    _, dec, fi, fpf = bank_live_input(case, family)
+    S = case["S"]
+    if rate != 16000:   # orc.Resampler + process_resampled, with the resampler's output computed once for the three passes
+        if "enc" not in case:
+            case["enc"] = [orc.resample_stream(dec[s], rate) for s in range(S)]
+        enc, fo = case["enc"], 160 * fpf
+    fkw = {} if filters is None else filters
+    every = {}
+    for d in case["bank"] + case["extra"] + case["repl"]:
+        every[d["name"]] = _scaled_ww(d, scale)
+    cur = [every[d["name"]] for d in case["bank"]]   # the bank as it stands
+    out = [[] for _ in range(S)]
+    dets, held = [], []
+    for s in range(S):
+        d = orc.Detector(avg_threshold=c["avg_threshold"] * scale, threshold=c["threshold"] * scale, min_scores=c["min_scores"], eager=c["eager"],
+                         score_ref=c["score_ref"], band_size=c["band_size"], score_mode=c["score_mode"], vad_mode=c["vad_mode"], **fkw)
+        row = [int(v) for v in case["rows"][s]] if sets else [case["idx"][s] if s != case["outside"] else -1]
+        row = [w for w in row if w >= 0]
+        for w in row:
+            d.add_ref(cur[w])
+        dets.append(d)
+        held.append(row)
+    pos_of = lambda p: p if rate == 16000 else int(p * 480 * rate / 16000) // fi   # a plan position in input frames
+    ev_at = {}
+    for p, ops in events.items():
+        ev_at.setdefault(pos_of(p), []).extend(ops)
+
+    def retarget(s, row):
+        for _ in held[s]:
+            dets[s].remove(0)
+        held[s] = [w for w in row if w >= 0]
+        for w in held[s]:
+            dets[s].add_ref(cur[w])
+        if detail is not None:
+            detail.setdefault(s, []).append(k)
+
+    n_in = dec.shape[1] // fi
+    for k in range(n_in):
+        for op in ev_at.get(k, []):
+            if op[0] == "reset":
+                dets[op[1]].reset()
+                if detail is not None:
+                    detail.setdefault(op[1], []).append(k)
+            elif op[0] == "set":
+                retarget(op[1], [int(v) for v in _set_row_after(case, op[1], op[2])] if sets else [op[2]])
+            elif op[0] == "append":
+                cur += [every[case["extra"][w - case["W"]]["name"]] for w in op[1]]
+            elif op[0] == "replace":
+                cur[op[1]] = every[case["repl"][op[2]]["name"]]
+                # the reference's remove + add for the streams that hold it: under sets every stream whose row has it, with its row as it stands
+                for s in ([t for t in range(S) if op[1] in held[t]] if sets else op[3]):
+                    retarget(s, list(held[s]) if sets else [op[1]])
+        for s in range(S):
+            x = dec[s, k * fi:(k + 1) * fi]
+            r = dets[s].process_chunk(enc[s][k * fo:(k + 1) * fo]) if rate != 16000 else dets[s].process_f32(x)
+            if r is not None:
+                out[s].append((k, int(r["counter"]), r["name"], float(r["score"]), float(r["avg_score"])))
+    return out
+
+
+def bank_oracle(case, family):
+    """-> (events at scale 1, threshold-sensitive?, detail); memoised in the case"""
+    key = "oracle_" + family
+    if key not in case:
+        detail = {}
+        short = lambda e: [[t[:3] for t in s] for s in e]
+        if family == "model_bank":   # the live plan and, where it has events, the whole recordings without them
+            ev = _model_oracle_events(case, True, 1.0, detail)
+            whole = _model_oracle_events(case, False) if case["events"] else ev
+            case["oracle_model_bank_whole"] = whole
+            sens = any(short(_model_oracle_events(case, live, k)) != short(e) for k in (1.0 + BANK_MARGIN, 1.0 - BANK_MARGIN)
+                       for live, e in ([(True, ev), (False, whole)] if case["events"] else [(True, ev)]))
+            case[key] = (ev, sens, detail)
+            return case[key]
+        ev = bank_oracle_events(case, family, 1.0, detail)
+        sens = any(short(bank_oracle_events(case, family, k)) != short(ev) for k in (1.0 + BANK_MARGIN, 1.0 - BANK_MARGIN))
+        case[key] = (ev, sens, detail)
+    return case[key]
+
+
+def _bank_cfg(ra, c):
+    dc = ra.DetectorConfig()
+    dc.avg_threshold, dc.threshold, dc.min_scores, dc.eager = c["avg_threshold"], c["threshold"], c["min_scores"], c["eager"]
+    dc.score_ref, dc.band_size = c["score_ref"], c["band_size"]
+    dc.score_mode = getattr(ra.ScoreMode, c["score_mode"].capitalize())
+    dc.vad_mode = {None: None, "easy": ra.VADMode.Easy, "medium": ra.VADMode.Medium, "hard": ra.VADMode.Hard}[c["vad_mode"]]
+    return dc
+
+
+def _bank_tuple(w):
+    return (list(w["samples_features"].values()), w["avg_features"], w["threshold"], w["avg_threshold"])
+
+
+def _bank_rpw(w):
+    import rpw_py
+    return rpw_py.dump_rpw_ref(w["name"], w["samples_features"], w["avg_features"], w["threshold"], w["avg_threshold"], w["rms_level"])
+
+
+def _new_bank(ra, ctx, case):
+    bank = ra.WakewordBank(ctx, wakewords=[_bank_tuple(w) for w in case["bank"]])
+    bank.set_rms_levels([w["rms_level"] for w in case["bank"]])
+    assert bank.max_lens == [w["max_len"] for w in case["bank"]]
+    return bank
+
+
+def _bank_same(where, s, got, want):
+    """got / want: [(chunk, counter, name, score, avg_score)] of one stream: events exact, scores within the parity gate"""
+    assert [g[:3] for g in got] == [w[:3] for w in want], "%s stream %d: events differ\noracle %r\ndevice %r" % (where, s, want, got)
+    for g, w in zip(got, want):
+        assert rel_close(g[3], w[3]) and (rel_close(g[4], w[4]) if w[4] != 0 else g[4] == 0), "%s stream %d: scores differ\noracle %r\ndevice %r" % (where, s, w, g)
+
+
+def _bank_sweep_loop(family, n_cases, seed, verbose, body, shapes=None):
+    """runs body(case, ci, where) over the cases that the oracle keeps -> (cases, detections, cases set aside, seconds)"""
+    import time
+    t0 = time.time()
+    total = aside = 0
+    for ci in range(n_cases):
+        case = bank_case(family, seed, ci, (shapes or {}).get(ci))
+        ref, sens, _ = bank_oracle(case, family)
+        if sens:
+            aside += 1
+            continue
+        body(case, ref, "%s sweep seed %d case %d (%r, K %d, W %d, S %d, %s)" % (family, seed, ci, case["cfg"], case["K"], case["W"], case["S"], case["fmt"]))
+        total += sum(len(r) for r in ref)
+        if shapes is None:
+            _BANK_MEMO.clear()
+        if verbose and ci % 20 == 0:
+            print("%s case %d ok, %d detections so far, %d cases set aside" % (family, ci, total, aside), flush=True)
+    assert 10 * aside <= n_cases, "%s sweep seed %d: %d of %d cases are threshold-sensitive for the oracle" % (family, seed, aside, n_cases)
+    return n_cases, total, aside, time.time() - t0
+
+
+def _host_indices(ra, ctx, case, call, text="is outside the bank"):
+    """a host array refuses an index >= W; on a device array it means "no wakeword" (_dev_detect).  The refusal is checked, then the
+    stream goes as -1 on the host-pointer context."""
+    idx = np.array(case["idx"], np.int32)
+    if case["outside"] >= 0:
+        bad = idx.copy()
+        bad[case["outside"]] = case["W"] + 1
+        try:
+            call(bad)
+            raise AssertionError("an index outside the bank was accepted")
+        except ra.RustpotterError as e:
+            assert text in str(e), str(e)
+        idx[case["outside"]] = -1
+    return idx
+
+
+_DEV = {}
+
+
+def _dev_ctx(ra):
+    """a context without RP_CTX_HOST_POINTERS, one per process"""
+    if "ctx" not in _DEV:
+        _DEV["ctx"] = ra.BatchContext(device=0, host_pointers=False)
+    return _DEV["ctx"]
+
+
+def _dev_detect(ra, pcm, idx, max_det, call):
+    """A whole-recording detect call on the device-pointer context: audio, indices and outputs on the device, where an index outside
+    the bank reaches the kernels and means "no wakeword".  call(pcm, fmt, S, N, idx, det, second, n_det): the entry point on device
+    pointers -> (det [S][max_det], the second int32 output [S][max_det], n_det [S])"""
+    import torch
+    pcm = np.ascontiguousarray(pcm)
+    fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype, 3)
+    S, N = pcm.shape
+    size = np.dtype(ra.api.DET_DTYPE).itemsize
+    d_pcm = torch.from_numpy(pcm).cuda()
+    d_idx = torch.from_numpy(np.ascontiguousarray(idx, np.int32)).cuda()
+    d_det = torch.zeros(S * max_det * size, dtype=torch.uint8, device="cuda")
+    d_second = torch.zeros((S, max_det), dtype=torch.int32, device="cuda")
+    d_n = torch.zeros(S, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    call(d_pcm.data_ptr(), fmt, S, N, d_idx.data_ptr(), d_det.data_ptr(), d_second.data_ptr(), d_n.data_ptr())
+    _dev_ctx(ra).synchronize()
+    det = np.frombuffer(d_det.cpu().numpy().tobytes(), dtype=ra.api.DET_DTYPE).reshape(S, max_det)
+    return det, d_second.cpu().numpy(), d_n.cpu().numpy()
+
+
+def _same_records(where, det, n_det, det2, n_det2, second=None, second2=None):
+    """two runs of the product: the same detections bit for bit"""
+    assert np.array_equal(n_det, n_det2), "%s: %r against %r detections" % (where, n_det, n_det2)
+    for s in range(len(n_det)):
+        n = int(n_det[s])
+        assert det[s][:n].tobytes() == det2[s][:n].tobytes(), "%s stream %d: %r against %r" % (where, s, det[s][:n], det2[s][:n])
+        assert second is None or np.array_equal(second[s][:n], second2[s][:n]), "%s stream %d: %r against %r" % (where, s, second[s][:n], second2[s][:n])
+
+
+def run_bank_sweep(ra, ctx, n_cases, seed, verbose=False, shapes=None):
+    """rp_batch_detect_bank / rp_dtw_score_bank over whole recordings against one orc.Detector per stream."""
+    from oracle import rp_oracle as orc
+
+    def body(case, ref, where):
+        c, K, S = case["cfg"], case["K"], case["S"]
+        dc = _bank_cfg(ra, c)
+        bank = _new_bank(ra, ctx, case)
+        pcm = case["pcm"]
+        idx = _host_indices(ra, ctx, case, lambda bad: ctx.batch_detect_bank(pcm, bank, bad, dc))
+        nf = ra.mfcc_num_frames(pcm.shape[1])
+        need = max([0] + bank.n_win(nf, idx))
+        rng = np.random.default_rng([seed, 7, S, K])
+        pitch = need + int(rng.integers(0, 9))
+        det, n_det, agg, avg = ctx.batch_detect_bank(pcm, bank, idx, dc, max_det=kMaxDet, want_agg=True, win_pitch=pitch)
+        det2, n_det2 = ctx.batch_detect_bank(pcm, bank, idx, dc, max_det=kMaxDet)
+        assert np.array_equal(n_det, n_det2) and det.tobytes() == det2.tobytes(), "%s: the detect-only call differs from the fully scored one" % where
+        if case["outside"] >= 0:
+            # device arrays: the index outside the bank reaches the kernels and means "no wakeword"; every stream as on the host context
+            dctx = _dev_ctx(ra)
+            dbank = _new_bank(ra, dctx, case)
+            out = idx.copy()
+            out[case["outside"]] = case["W"] + 1 + case["outside"]
+            ddet, _, dn = _dev_detect(ra, pcm, out, kMaxDet, lambda p, f, S_, N, i, d, w, n: dctx.batch_detect_bank_dev(p, f, S_, N, N, dbank, i, dc, d, n, kMaxDet))
+            assert dn[case["outside"]] == 0, where
+            _same_records("%s [device arrays, stream %d holds index %d]" % (where, case["outside"], out[case["outside"]]), det, n_det, ddet, dn)
+        for s in range(S):
+            w = int(idx[s])
+            assert int(n_det[s]) <= kMaxDet, where
+            got = [(int(d["frame"]) // 3 + 1, int(d["counter"]), "w%d" % w, float(d["score"]), float(d["avg_score"])) for d in det[s][:n_det[s]]]
+            assert all(int(d["stream"]) == s for d in det[s][:n_det[s]]), where
+            if w < 0:
+                assert not got and not agg[s].any() and not avg[s].any(), "%s stream %d: a stream without a wakeword reports something" % (where, s)
+            _bank_same(where, s, got, ref[s])
+        # the scores themselves, on the oracle's MFCCs: aggregates and averaged-template scores at every seventh window
+        mf = np.stack([orc.mfcc_stream(_to_f32(pcm[s]), K) for s in range(S)])
+        mode = getattr(ra.ScoreMode, c["score_mode"].capitalize())
+        v2, a2 = ctx.dtw_scores_bank(mf, bank, idx, c["score_ref"], c["band_size"], mode, with_avg=True, win_pitch=pitch)
+        for s in range(S):
+            w = int(idx[s])
+            nw = 0 if w < 0 else max(0, nf - bank.max_lens[w] + 1)
+            assert not a2[s][nw:].any() and not v2[s][nw:].any() and not agg[s][nw:].any() and not avg[s][nw:].any(), "%s stream %d: rows behind the windows are not zero" % (where, s)
+            if w < 0 or s >= 12:
+                continue
+            d = case["bank"][w]
+            L = d["max_len"]
+            tm = list(d["samples_features"].values())
+            for i in range(int(rng.integers(7)), nw, 7):
+                want = orc.aggregate([orc.score_window(mf[s][i:i + L], t, c["band_size"], c["score_ref"]) for t in tm], c["score_mode"])
+                assert rel_close(a2[s][i], want) or (want == 0 and a2[s][i] == 0), "%s stream %d window %d: aggregate %r, oracle %r" % (where, s, i, a2[s][i], want)
+                if d["avg_features"] is not None:
+                    want = orc.score_window(mf[s][i:i + L], d["avg_features"], c["band_size"], c["score_ref"])
+                    assert rel_close(v2[s][i], want) or (want == 0 and v2[s][i] == 0), "%s stream %d window %d: averaged-template score %r, oracle %r" % (where, s, i, v2[s][i], want)
+
+    return _bank_sweep_loop("bank", n_cases, seed, verbose, body, shapes)
+
+
+def run_bank_sets_sweep(ra, ctx, n_cases, seed, verbose=False, shapes=None):
+    """rp_batch_detect_bank_sets against an orc.Detector holding the set's wakewords in slot order: det_wakeword is the bank index
+    of the oracle's winner."""
+    def body(case, ref, where):
+        dc = _bank_cfg(ra, case["cfg"])
+        bank = _new_bank(ra, ctx, case)
+        pcm, rows = case["pcm"], case["rows"]
+        det, dww, n_det = ctx.batch_detect_bank_sets(pcm, bank, rows, dc, max_det=kMaxDet)
+        for s in range(case["S"]):
+            assert int(n_det[s]) <= kMaxDet, where
+            got = [(int(d["frame"]) // 3 + 1, int(d["counter"]), "w%d" % int(dww[s][j]), float(d["score"]), float(d["avg_score"]))
+                   for j, d in enumerate(det[s][:n_det[s]])]
+            # the exact twin shares its original's name on neither side: the oracle names the winner's slot
+            _bank_same(where, s, got, ref[s])
+        if not np.array_equal(case["rows_out"], rows):
+            # device arrays: an index outside the bank in one slot reaches the kernels and is an empty slot
+            dctx = _dev_ctx(ra)
+            dbank = _new_bank(ra, dctx, case)
+            n_set = rows.shape[1]
+            ddet, dw2, dn = _dev_detect(ra, pcm, case["rows_out"], kMaxDet, lambda p, f, S_, N, i, d, w, n: dctx.batch_detect_bank_sets_dev(
+                p, f, S_, N, N, dbank, i, n_set, dc, d, w, n, kMaxDet))
+            _same_records("%s [device arrays, a slot of stream %d outside the bank]" % (where, case["outside"]), det, n_det, ddet, dn, dww, dw2)
+
+    return _bank_sweep_loop("bank_sets", n_cases, seed, verbose, body, shapes)
+
+
+def _run_live(ra, ctx, case, ref, where, family, seed, slots=False):
+    """a live batch over the bank (per-stream index or sets) through the case's plan -> nothing; asserts"""
+    from oracle import rp_oracle as orc
+    sets = family.endswith("sets")
+    c, K, S, W = case["cfg"], case["K"], case["S"], case["W"]
+    events, filters, rate = _bank_live_flags(case, family)
+    dc = _bank_cfg(ra, c)
+    raw, dec, fi, fpf = bank_live_input(case, family)
+    bank = _new_bank(ra, ctx, case)
+    names = [w["name"] for w in case["bank"]]
+    longest = max(w["max_len"] for w in case["bank"] + case["extra"] + case["repl"])
+    has_put = any(op[0] in ("append", "replace") for ops in events.values() for op in ops)
+    bank.reserve(max_len=longest)   # pools as created: exactly full, so what is put later makes them grow
+    grown0 = bank.pool_growths
+    kw = {}
+    if filters is not None:
+        f = ra.FiltersConfig()
+        g, b = f.gain_normalizer, f.band_pass
+        g.enabled, g.gain_ref, g.min_gain, g.max_gain = filters["gain_normalizer"], filters["gain_ref"], filters["min_gain"], filters["max_gain"]
+        b.enabled, b.low_cutoff, b.high_cutoff = filters["band_pass"], filters["low_cutoff"], filters["high_cutoff"]
+        kw = dict(filters=f) if sets else dict(bank_filters=f)
+    if sets:
+        sb = ra.StreamBatch(ctx, None, dc, S, max_chunks_per_call=case["max_cpc"], sample_rate=rate, bank=bank, stream_wakewords=case["rows"], **kw)
+    else:
+        idx = _host_indices(ra, ctx, case, lambda bad: ra.StreamBatch(ctx, None, dc, S, bank=bank, stream_wakeword=bad))
+        sb = ra.StreamBatch(ctx, None, dc, S, max_chunks_per_call=case["max_cpc"], sample_rate=rate, bank=bank, stream_wakeword=idx, **kw)
+    assert sb.samples_per_chunk == fi and sb.frames_per_chunk == fpf, where
+    pos_of = lambda p: p if rate == 16000 else int(p * 480 * rate / 16000) // fi
+    n_in = raw.shape[1] // fi
+    cuts = sorted(set(min(pos_of(p), n_in) for p in case["cuts"]) | {n_in})
+    ev_at = {}
+    for p, ops in events.items():
+        ev_at.setdefault(pos_of(p), []).extend(ops)
+    got = [[] for _ in range(S)]
+    recs = [[] for _ in range(S)]
+    touched, retargeted = set(), set()
+    rowstate = case["rows"].copy()   # (sets: every stream's row as it stands)
+    plain = rate == 16000 and filters is None
+    # the gain normaliser at 16 kHz: every chunk's level and gain against the oracle's front-end with the stream's own reference level
+    # and window, bit for bit as in tests/test_gpu_bank_filters.py (streams that no event re-targeted)
+    check_levels = (not sets) and rate == 16000 and filters is not None and filters["gain_normalizer"]
+    levels = []
+    mf = {}
+    rng = np.random.default_rng([seed, 9, S, K])
+    for a, b_ in zip(cuts[:-1], cuts[1:]):
+        if b_ <= a:
+            continue
+        for op in ev_at.get(a, []):
+            if op[0] == "reset":
+                sb.reset(op[1])   # (a reset leaves the gain normaliser's levels alone)
+                touched.add(op[1])
+            elif op[0] == "set":
+                if sets:
+                    rowstate[op[1]] = _set_row_after(case, op[1], op[2])
+                    sb.set_wakeword_sets(op[1], [rowstate[op[1]]])
+                else:
+                    sb.set_wakewords(op[1], [op[2]])
+                touched.add(op[1])
+                retargeted.add(op[1])
+            elif op[0] == "append":
+                new = [case["extra"][w - W] for w in op[1]]
+                assert op[1][0] == bank.W, where
+                if op[2]:
+                    bank.put_rpw(bank.W, [_bank_rpw(w) for w in new])
+                else:
+                    bank.put(bank.W, [_bank_tuple(w) for w in new], rms_levels=[w["rms_level"] for w in new])
+                names += [w["name"] for w in new]
+            elif op[0] == "replace":
+                w = case["repl"][op[2]]
+                bank.put(op[1], [_bank_tuple(w)], rms_levels=[w["rms_level"]])
+                names[op[1]] = w["name"]
+                for s in ([t for t in range(S) if (rowstate[t] == op[1]).any()] if sets else op[3]):
+                    if sets:
+                        sb.set_wakeword_sets(s, [rowstate[s]])
+                    else:
+                        sb.set_wakewords(s, [op[1]])
+                    touched.add(s)
+                    retargeted.add(s)
+        assert b_ - a <= case["max_cpc"], where
+        det, dww, dlab, n_det = sb.process_multi(np.ascontiguousarray(raw[:, a * fi:b_ * fi]), max_det=16)
+        if check_levels:
+            levels.append(sb.levels())
+        for s in range(S):
+            for j in range(int(n_det[s])):
+                d = det[s][j]
+                assert int(d["stream"]) == s and int(dlab[s][j]) == -1, where
+                chunk = int(d["frame"]) // 3 + 1 if rate == 16000 else (int(d["frame"]) + 3) // fpf
+                got[s].append((chunk, int(d["counter"]), names[int(dww[s][j])], float(d["score"]), float(d["avg_score"])))
+                recs[s].append((d.copy(), int(dww[s][j])))
+        if slots and plain and b_ > 40:
+            # the slots' scores of this call at every seventh frame against the oracle's per-wakeword scores (streams nobody touched)
+            agg, avg = sb.slot_scores()
+            for s in range(min(S, 6)):
+                live = [int(v) for v in case["rows"][s] if v >= 0]
+                if s in touched or not live:
+                    continue
+                if s not in mf:
+                    mf[s] = orc.mfcc_stream(dec[s], K)
+                Ls = max(case["bank"][w]["max_len"] for w in live)
+                for col in range(int(rng.integers(7)), agg.shape[2], 7):
+                    fr = 3 * a + col - 3   # column j of a call's rows is frame j - 3 of the stream
+                    if fr - Ls + 1 < 0 or fr >= len(mf[s]):
+                        continue
+                    win = mf[s][fr - Ls + 1:fr + 1]
+                    for j, w in enumerate(case["rows"][s]):
+                        if w < 0:
+                            assert agg[s, j, col] == 0 and avg[s, j, col] == 0, "%s stream %d slot %d: an empty slot has a score" % (where, s, j)
+                            continue
+                        d = case["bank"][int(w)]
+                        want = orc.aggregate([orc.score_window(win, t, c["band_size"], c["score_ref"]) for t in d["samples_features"].values()], c["score_mode"])
+                        assert rel_close(agg[s, j, col], want) or (want == 0 and agg[s, j, col] == 0), "%s stream %d slot %d frame %d: slot score %r, oracle %r" % (
+                            where, s, j, fr, agg[s, j, col], want)
+    for s in range(S):
+        _bank_same(where, s, got[s], ref[s])
+    if check_levels:
+        rms, gains = np.concatenate([l[0] for l in levels], axis=1), np.concatenate([l[1] for l in levels], axis=1)
+        for s in range(S):
+            if s in retargeted:
+                continue
+            w = int(idx[s])
+            okw = dict(filters, rms_level_ref=case["bank"][w]["rms_level"], window_size=max(1, case["bank"][w]["max_len"] // 3)) if w >= 0 else dict(filters, gain_normalizer=False)
+            _, rr, rg = orc.frontend_stream(dec[s], **okw)
+            assert np.array_equal(rms[s].view(np.uint32), rr.view(np.uint32)), "%s stream %d: chunk levels differ from the oracle's" % (where, s)
+            assert np.array_equal(gains[s].view(np.uint32), rg.view(np.uint32)), "%s stream %d (wakeword %d): gains differ from the oracle's in chunks %r" % (
+                where, s, w, np.flatnonzero(gains[s] != rg)[:8])
+    if has_put:
+        assert bank.pool_growths > grown0, "%s: the puts did not make the pools grow" % where
+    if plain and not events:
+        # no mid-run events: the whole-recording call over the same streams, bit for bit (record bytes without the stream field)
+        if sets:
+            det, dww, n_det = ctx.batch_detect_bank_sets(raw, bank, case["rows"], dc, max_det=kMaxDet)
+        else:
+            det, n_det = ctx.batch_detect_bank(raw, bank, idx, dc, max_det=kMaxDet)
+            dww = None
+        for s in range(S):
+            assert len(recs[s]) == int(n_det[s]) <= kMaxDet, "%s stream %d: %d live against %d offline detections" % (where, s, len(recs[s]), n_det[s])
+            for j, (d, w) in enumerate(recs[s]):
+                assert d.tobytes()[4:] == det[s][j].tobytes()[4:] and (dww is None or w == dww[s][j]), "%s stream %d detection %d: live %r offline %r" % (where, s, j, d, det[s][j])
+    sb.close()
+
+
+def run_live_bank_sweep(ra, ctx, n_cases, seed, verbose=False, shapes=None):
+    """StreamBatch(bank=, stream_wakeword=) fed in random pieces, with resets, re-targets, puts under the running batch, per-stream
+    filters and resampled input, against one orc.Detector per stream; cases without events also against rp_batch_detect_bank bit for bit."""
+    return _bank_sweep_loop("live_bank", n_cases, seed, verbose, lambda case, ref, where: _run_live(ra, ctx, case, ref, where, "live_bank", seed), shapes)
+
+
+def run_live_bank_sets_sweep(ra, ctx, n_cases, seed, verbose=False, shapes=None):
+    """the same over stream_wakewords / set_wakeword_sets.  Every other case runs on a context with RP_CTX_FULL_SCORES (a context
+    without it scores only the windows that can fire) and has slot_scores() checked at every seventh frame against the oracle's
+    per-wakeword scores; the others run on the caller's context."""
+    full = ra.BatchContext(device=0, host_pointers=True, full_scores=True)
+    count = [0]
+
+    def body(case, ref, where):
+        count[0] += 1
+        if count[0] % 2:
+            _run_live(ra, full, case, ref, where + " [full scores]", "live_bank_sets", seed, slots=True)
+        else:
+            _run_live(ra, ctx, case, ref, where, "live_bank_sets", seed)
+
+    return _bank_sweep_loop("live_bank_sets", n_cases, seed, verbose, body, shapes)
+
+
+# ---- the models variant: a model bank, whole recordings and a live batch with set_models events against orc.Detector.add_model
+MODEL_GATE = 1e-4   # scores of models: 1e-4 relative with floor 1e-3, the gate of run_live_multi_sweep
+
+
+def _model_layers(m):
+    n = len([k for k in m["weights"] if k.endswith(".weight")])
+    return [m["weights"]["ln%d.weight" % (i + 1)] for i in range(n)], [m["weights"]["ln%d.bias" % (i + 1)] for i in range(n)]
+
+
+def _model_logits(m, mf):
+    """the oracle's logits of every window of a stream's MFCC rows [n_win][labels]"""
+    from oracle import rp_oracle as orc
+    L = m["train_size"]
+    if len(mf) < L:
+        return np.zeros((0, len(m["labels"])), np.float32)
+    X = np.stack([orc.normalize(mf[w:w + L]).reshape(-1) for w in range(len(mf) - L + 1)])
+    return np.asarray(orc.mlp_forward(X, *_model_layers(m)), np.float32)
+
+
+def _model_margin(m, lg):
+    """per window what the score is a function of: the best label's logit minus the "none" logit (minus 0 without one)"""
+    ni = m["labels"].index("none") if "none" in m["labels"] else -1
+    if ni < 0:
+        return lg.max(axis=1).astype(np.float64)
+    return np.delete(lg, ni, axis=1).max(axis=1).astype(np.float64) - lg[:, ni]
+
+
+def _make_model_bank_case(rng, S=None, n_chunks=None, pin=None):
+    """The models variant of make_bank_case: a bank of 1..6 models within the model bank's limits (mfcc_size 16, two or three Linear
+    layers -- Tiny and Small --, every layer at most 32 wide, windows of different lengths), 2..4 labels with "none" at a random place or
+    absent.  Random weights alone almost never fire at a given threshold, so every model's logits are steered
+    (tests/nn_decide_ref.py steers logits for the same reason): the bias of its "none" label (of every label, without one) is moved until a drawn quantile of the ORACLE's scores of
+    the case's streams sits at the config's threshold; the threshold then goes into the widest gap between the scores around it."""
+    from oracle import rp_oracle as orc
+    pin = pin or {}
+    K = 16
+    M = int(rng.integers(1, 7))
+    wide = S is not None
+    top = 120 if n_chunks is None else max(20, min(120, n_chunks))
+    models = []
+    for mi in range(M):
+        L = int(rng.integers(20, top + 1))
+        hidden = [int(rng.integers(2, 33))] if rng.random() < 0.5 else [int(rng.integers(4, 33)), int(rng.integers(2, 17))]
+        labels = ["alpha", "beta", "gamma"][:int(rng.integers(1, 4))]
+        if rng.random() < 0.75 or len(labels) == 1:
+            labels.insert(int(rng.integers(len(labels) + 1)), "none")
+        dims = [L * K] + hidden + [len(labels)]
+        weights = {}
+        for i in range(len(dims) - 1):
+            gain = 2.5 if i == len(dims) - 2 else 1.0   # (a last layer that makes the scores move from window to window)
+            weights["ln%d.weight" % (i + 1)] = (rng.standard_normal((dims[i + 1], dims[i])) * (gain * 1.5 / np.sqrt(dims[i]))).astype(np.float32)
+            weights["ln%d.bias" % (i + 1)] = (rng.standard_normal(dims[i + 1]) * 0.1).astype(np.float32)
+        models.append({"labels": labels, "train_size": L, "mfcc_size": K, "m_type": "tiny" if len(hidden) == 1 else "small", "weights": weights,
+                       "rms_level": float(rng.uniform(0.01, 0.2))})
+    cfg = dict(threshold=float(rng.uniform(0.35, 0.7)), avg_threshold=0.0, min_scores=int(rng.integers(1, 7)), eager=bool(rng.random() < 0.3),
+               score_ref=float(rng.uniform(0.15, 0.3)), band_size=5, score_mode="max",
+               vad_mode=[None, None, None, "easy", "medium", "hard"][int(rng.integers(6))])
+    cfg.update({k: pin[k] for k in ("eager", "vad_mode") if k in pin})
+    if S is None:
+        S = int(rng.integers(3, 10))
+    idx = [int(v) for v in rng.integers(0, M, size=S)]
+    idx[1] = idx[0]
+    idx[2] = -1
+    outside = int(rng.integers(S)) if S > 3 else -1
+    if outside in (0, 1, 2):
+        outside = 3 if S > 3 else -1
+    lens_s = [int(n_chunks or rng.integers(60, 141)) for _ in range(S)]
+    n_max = max(lens_s)
+    max_cpc = int(pin.get("max_cpc", rng.integers(2, 12)))
+    cuts, pos = [], 0
+    while pos < n_max:
+        cuts.append(pos)
+        pos += min(max_cpc if "max_cpc" in pin and len(cuts) % 4 == 3 else int(rng.integers(1, max_cpc + 1)), n_max - pos)
+    cuts.append(n_max)
+    events, retarget, touched = {}, {}, set()
+
+    def at_cut(lo, hi):
+        c = [p for p in cuts[1:-1] if lo <= p < hi]
+        return int(c[int(rng.integers(len(c)))]) if c else None
+
+    n_ev = 0 if ((wide and not pin.get("events")) or rng.random() < 0.3) else int(rng.integers(1, 5))
+    if pin.get("events") is not None:
+        n_ev = max(n_ev, 3) if pin["events"] else 0
+    for _ in range(n_ev):
+        s = int(rng.integers(S))
+        if s in touched or s == outside:
+            continue
+        p = at_cut(8, max(9, lens_s[s] - min(45, lens_s[s] // 2)))
+        if p is None:
+            continue
+        kind = str(rng.choice(["reset", "retarget", "retarget", "gap"]))
+        touched.add(s)
+        if kind == "reset":
+            events.setdefault(p, []).append(("reset", s))
+            retarget[s] = (p, idx[s])
+        elif kind == "retarget":
+            j = int(rng.integers(M))
+            events.setdefault(p, []).append(("set", s, j))
+            retarget[s] = (p, j)
+        else:
+            q = at_cut(p + 1, p + 12)
+            if q is None:
+                continue
+            j = idx[s] if idx[s] >= 0 else int(rng.integers(M))
+            events.setdefault(p, []).append(("set", s, -1))
+            events.setdefault(q, []).append(("set", s, j))
+            retarget[s] = (q, j)
+    # audio as make_model_case: speech-like utterances back to back, in noise
+    pcm = np.zeros((S, 480 * n_max), np.float32)
+    for s in range(S):
+        x = np.concatenate([_utterance(rng, 480 * 20) for _ in range((n_max + 19) // 20)])[:480 * n_max]
+        pcm[s] = x + (rng.standard_normal(len(x)) * rng.uniform(0.0005, 0.02)).astype(np.float32)
+        pcm[s, 480 * lens_s[s]:] *= np.float32(0.05)
+    fmt = str(rng.choice(["f32", "f32", "i16", "i8", "i32"]))
+    fmt = pin.get("fmt", fmt)
+    raw = pcm
+    if fmt != "f32":
+        info = np.iinfo({"i16": np.int16, "i8": np.int8, "i32": np.int32}[fmt])
+        raw = np.clip(np.round(pcm.astype(np.float64) * (8.0 if fmt == "i8" else 1.0) * info.max), info.min, info.max).astype(info.dtype)
+    # steering, from the oracle's logits of the streams that ever hold the model
+    dec = _to_f32(raw)
+    mf = [orc.mfcc_stream(dec[s], K) for s in range(S)]
+    rf = float(np.float32(cfg["score_ref"]) * np.float32(10.0))
+    T = cfg["threshold"]
+    want = rf * (1.0 + np.log(T / (1.0 - T)))   # the margin whose score is T
+    logits = {}
+    for s in range(S):
+        for mi in set(([idx[s]] if idx[s] >= 0 and s != outside else []) + ([retarget[s][1]] if s in retarget and retarget[s][1] >= 0 else [])):
+            logits.setdefault(mi, []).append(_model_logits(models[mi], mf[s]))
+    scores, avgs = [], []
+    score_of = lambda d: 1.0 - 1.0 / (1.0 + np.exp((d - rf) / rf))
+    for mi, lgs in sorted(logits.items()):
+        m = models[mi]
+        lg = np.concatenate(lgs)
+        if not len(lg):
+            continue
+        # (a detection ends after half a window without a passing window: few windows may pass)
+        q = float(rng.uniform(0.92, 0.97)) - 0.02 * (cfg["min_scores"] - 1) - (0.05 if wide else 0.0)
+        move = float(np.quantile(_model_margin(m, lg), q) - want)
+        nb = len(_model_layers(m)[0])
+        b = m["weights"]["ln%d.bias" % nb]
+        if "none" in m["labels"]:
+            b[m["labels"].index("none")] += np.float32(move)
+            lg[:, m["labels"].index("none")] += np.float32(move)
+        else:
+            b -= np.float32(move)
+            lg -= np.float32(move)
+        d = _model_margin(m, lg)
+        scores.append(score_of(d[d > 0]))
+        avgs.append(score_of(lg.max(axis=1).astype(np.float64) - lg.min(axis=1)))
+    if scores:
+        v = np.sort(np.concatenate(scores))
+        if v.size >= 2:
+            cfg["threshold"] = _quantile_or([v], float(np.searchsorted(v, T)) / (v.size - 1), T)
+        if rng.random() < 0.5:
+            # (a low quantile of the avg scores, and below where they saturate: scaled by 1 + 1e-4 a threshold at 1 passes nothing)
+            va = np.sort(np.concatenate(avgs))
+            ta = min(float(np.quantile(va, float(rng.uniform(0.05, 0.3)))), float(rng.uniform(0.5, 0.9)))
+            cfg["avg_threshold"] = _quantile_or([va], float(np.searchsorted(va, ta)) / max(1, va.size - 1), ta)
+    return dict(models=models, K=K, W=M, cfg=cfg, S=S, idx=idx, outside=outside, pcm=raw, lens=lens_s, fmt=fmt, cuts=cuts, max_cpc=max_cpc,
+                events=events, wide=wide)
+
+
+def _model_oracle_events(case, live, scale=1.0, detail=None):
+    """one orc.Detector per stream holding the stream's model (add_model), fed chunk by chunk; live: with the plan's resets and re-targets
+    (remove + add_model, as a wakeword's) -> per stream [(chunk, counter, "m<model>:<label>", score, avg_score)]"""
+    from oracle import rp_oracle as orc
+    c, S = case["cfg"], case["S"]
+    dec = _to_f32(case["pcm"])
+    dets, held = [], []
+    for s in range(S):
+        d = orc.Detector(avg_threshold=c["avg_threshold"] * scale, threshold=c["threshold"] * scale, min_scores=c["min_scores"], eager=c["eager"],
+                         score_ref=c["score_ref"], vad_mode=c["vad_mode"])
+        mi = case["idx"][s] if s != case["outside"] else -1
+        if mi >= 0:
+            d.add_model(case["models"][mi])
+        dets.append(d)
+        held.append(mi)
+    out = [[] for _ in range(S)]
+    for k in range(dec.shape[1] // 480):
+        for op in (case["events"].get(k, []) if live else []):
+            s = op[1]
+            if op[0] == "reset":
+                dets[s].reset()
+            else:
+                if held[s] >= 0:
+                    dets[s].remove(0)
+                held[s] = op[2]
+                if held[s] >= 0:
+                    dets[s].add_model(case["models"][held[s]])
+            if detail is not None:
+                detail.setdefault(s, []).append(k)
+        for s in range(S):
+            r = dets[s].process_f32(dec[s, 480 * k:480 * (k + 1)])
+            if r is not None:
+                out[s].append((k, int(r["counter"]), "m%d:%s" % (held[s], r["name"]), float(r["score"]), float(r["avg_score"])))
+    return out
+
+
+def _model_same(where, s, got, want):
+    assert [g[:3] for g in got] == [w[:3] for w in want], "%s stream %d: events differ\noracle %r\ndevice %r" % (where, s, want, got)
+    for g, w in zip(got, want):
+        assert all(abs(g[i] - w[i]) <= MODEL_GATE * max(abs(w[i]), 1e-3) for i in (3, 4)), "%s stream %d: scores differ\noracle %r\ndevice %r" % (where, s, w, g)
+
+
+def run_model_bank_sweep(ra, ctx, n_cases, seed, verbose=False, shapes=None):
+    """rp_batch_detect_model_bank over whole recordings, and a live batch over the model bank fed in random pieces with resets and set_models
+    events, each against one orc.Detector.add_model per stream: labels exact, scores within 1e-4 (floor 1e-3).  The whole-recording call
+    also runs on device arrays, where one stream holds an index outside the bank.  Live logits of cases without events (f32 input): bit
+    for bit those of rp_mlp_forward_windows with the stream's own model over runs of fewer than 32 windows -- the yardstick the header
+    gives for mlp_bank_stream_kernel's arithmetic (rp_mlp_forward_windows_bank stages its frames otherwise and differs in the last bits)."""
+    def body(case, ref, where):
+        c, S, M = case["cfg"], case["S"], case["W"]
+        dc = _bank_cfg(ra, c)
+        pcm, models = case["pcm"], case["models"]
+        none_index = [m["labels"].index("none") if "none" in m["labels"] else -1 for m in models]
+        handles = [ra.Model(ctx, *_model_layers(m)) for m in models]
+        bank = ra.ModelBank(ctx, models=handles, none_index=none_index)
+        idx = _host_indices(ra, ctx, case, lambda bad: ctx.batch_detect_model_bank(pcm, bank, bad, dc), text="stream %d" % case["outside"])
+        name = lambda mi, lab: "m%d:%s" % (mi, models[mi]["labels"][lab])
+        # whole recordings
+        det, dlab, n_det = ctx.batch_detect_model_bank(pcm, bank, idx, dc, max_det=kMaxDet)
+        whole = case["oracle_model_bank_whole"]
+        for s in range(S):
+            assert int(n_det[s]) <= kMaxDet, where
+            got = [(int(d["frame"]) // 3 + 1, int(d["counter"]), name(int(idx[s]), int(dlab[s][j])), float(d["score"]), float(d["avg_score"]))
+                   for j, d in enumerate(det[s][:n_det[s]])]
+            _model_same(where + " [whole recordings]", s, got, whole[s])
+        if case["outside"] >= 0:
+            dctx = _dev_ctx(ra)
+            dbank = ra.ModelBank(dctx, models=[ra.Model(dctx, *_model_layers(m)) for m in models], none_index=none_index)
+            out = idx.copy()
+            out[case["outside"]] = M + 1
+            ddet, dl2, dn = _dev_detect(ra, pcm, out, kMaxDet, lambda p, f, S_, N, i, d, w, n: dctx.batch_detect_model_bank_dev(
+                p, f, S_, N, N, dbank, i, dc, "f32", d, w, n, kMaxDet))
+            _same_records("%s [device arrays, stream %d holds index %d]" % (where, case["outside"], M + 1), det, n_det, ddet, dn, dlab, dl2)
+        # live
+        sb = ra.StreamBatch(ctx, None, dc, S, max_chunks_per_call=case["max_cpc"], model_bank=bank, stream_model=idx)
+        got = [[] for _ in range(S)]
+        held = [int(v) for v in idx]
+        lgs = []
+        for a, b_ in zip(case["cuts"][:-1], case["cuts"][1:]):
+            for op in case["events"].get(a, []):
+                if op[0] == "reset":
+                    sb.reset(op[1])
+                else:
+                    sb.set_models(op[1], np.array([op[2]], np.int32))
+                    held[op[1]] = op[2]
+            dets, dww, dl, nd = sb.process_multi(np.ascontiguousarray(pcm[:, 480 * a:480 * b_]), max_det=16)
+            lgs.append(sb.logits())
+            for s in range(S):
+                for j in range(int(nd[s])):
+                    d = dets[s][j]
+                    assert int(d["stream"]) == s and int(dww[s][j]) == held[s], where
+                    got[s].append((int(d["frame"]) // 3 + 1, int(d["counter"]), name(held[s], int(dl[s][j])), float(d["score"]), float(d["avg_score"])))
+        for s in range(S):
+            _model_same(where + " [live]", s, got[s], ref[s])
+        if not case["events"] and case["fmt"] == "f32":
+            lg = np.concatenate(lgs, axis=1)
+            mfcc = ctx.mfcc(pcm, 16)
+            n_live = lg.shape[1] - 3   # frames 0 .. n_live - 1 have been seen
+            for s in range(min(S, 12)):
+                mi = int(idx[s])
+                if mi < 0:
+                    assert not lg[s].any(), "%s stream %d: logits of a stream without a model" % (where, s)
+                    continue
+                L, nl = models[mi]["train_size"], len(models[mi]["labels"])
+                assert not lg[s, :, nl:].any(), where
+                for f0, n in ((L - 1, 31), (n_live - 20, 20)):
+                    if f0 < L - 1 or f0 + n > n_live:
+                        continue
+                    want = ctx.mlp_forward_windows(mfcc[s:s + 1, f0 - L + 1:f0 + n], handles[mi])[0]
+                    g = lg[s, f0 + 3:f0 + 3 + n, :nl]
+                    assert want.shape == g.shape and np.array_equal(g.view(np.uint32), want.view(np.uint32)), "%s stream %d: live logits of the windows that end at frames %d.. differ from rp_mlp_forward_windows" % (where, s, f0)
+        sb.close()
+
+    return _bank_sweep_loop("model_bank", n_cases, seed, verbose, body, shapes)
+
+
+def model_case_facts(case):
+    """what a model-bank case exercises, from the oracle alone"""
+    ev, sens, detail = bank_oracle(case, "model_bank")
+    whole = case["oracle_model_bank_whole"]
+    S, models = case["S"], case["models"]
+    holds = [case["idx"][s] >= 0 and s != case["outside"] for s in range(S)]
+    ni = [m["labels"].index("none") if "none" in m["labels"] else -1 for m in models]
+    fired_models = {int(t[2][1:].split(":")[0]) for e in ev + whole for t in e}
+    soon = any(0 <= (t[0] - k) * 3 <= 2 * models[int(t[2][1:].split(":")[0])]["train_size"] for s, ks in detail.items() for k in ks for t in ev[s])
+    return dict(sensitive=sens, holders=sum(holds), fired=sum(1 for s in range(S) if holds[s] and ev[s] and whole[s]), twice=any(len(e) >= 2 for e in ev),
+                soon=soon, eager=case["cfg"]["eager"], detections=sum(len(e) for e in ev), layers={len(_model_layers(m)[0]) for m in models},
+                lengths={m["train_size"] for m in models}, other_none=any(ni[mi] != ni[0] for mi in fired_models), no_none=any(ni[mi] < 0 for mi in fired_models),
+                logits_checked=not case["events"] and case["fmt"] == "f32", has_set=any(op[0] == "set" for ops in case["events"].values() for op in ops),
+                max_piece=max(b - a for a, b in zip(case["cuts"][:-1], case["cuts"][1:])), streams=S)
+
+
+def bank_case_facts(case, family):
+    """What a family's case exercises, from the oracle alone (tests/test_bank_sweep_cases.py asserts these over the suite's seeds)."""
+    from oracle import rp_oracle as orc
+    ev, sens, detail = bank_oracle(case, family)
+    sets = family.endswith("sets")
+    S = case["S"]
+    holds = [bool((case["rows"][s] >= 0).any()) if sets else (case["idx"][s] >= 0 and s != case["outside"]) for s in range(S)]
+    _, _, rate = _bank_live_flags(case, family)
+    fpf = {16000: 3, 48000: 3, 8000: 3, 22050: 4}[rate]
+    length = {w["name"]: w["max_len"] for w in case["bank"] + case["extra"] + case["repl"]}
+    soon = any(0 <= (t[0] - k) * fpf <= 2 * length[t[2]] for s, ks in detail.items() for k in ks for t in ev[s])
+    both = False
+    if sets and case["cfg"]["band_size"] and family == "bank_sets" or (sets and case["cfg"]["band_size"] and rate == 16000 and _bank_live_flags(case, family)[1] is None):
+        # a frame where two wakewords of a row both pass, read from the oracle's per-wakeword scores: two slots of equal window length whose
+        # aggregates of the window that ends at one frame both reach their thresholds, in a stream that reports one of the two
+        c = case["cfg"]
+        dec = _to_f32(case["pcm"])
+        for s in range(S):
+            live = sorted({int(v) for v in case["rows"][s] if v >= 0})
+            named = {t[2] for t in ev[s]}
+            if both or len(live) < 2 or not named or s in detail:
+                continue
+            mf = orc.mfcc_stream(dec[s], case["K"])
+            passing = {}
+            for w in live:
+                d = case["bank"][w]
+                thr = c["threshold"] if d["threshold"] is None else d["threshold"]
+                agg = orc.score_stream(mf, list(d["samples_features"].values()), c["band_size"], c["score_ref"], c["score_mode"])[1]
+                passing[w] = (d["max_len"], np.asarray(agg) >= np.float32(thr))
+            for i, w in enumerate(live):
+                for v in live[i + 1:]:
+                    if passing[w][0] == passing[v][0] and (passing[w][1] & passing[v][1]).any() and named & {case["bank"][w]["name"], case["bank"][v]["name"]}:
+                        both = True
+    ops = [op for o in _bank_live_flags(case, family)[0].values() for op in o]
+    lens = {int(len(t)) for w in case["bank"] for t in w["samples_features"].values()}
+    return dict(sensitive=sens, holders=sum(holds), fired=sum(1 for s in range(S) if holds[s] and ev[s]), twice=any(len(e) >= 2 for e in ev),
+                soon=soon, eager=case["cfg"]["eager"], percentile=case["cfg"]["score_mode"].startswith("p"), band=case["cfg"]["band_size"],
+                K=case["K"], both=both, detections=sum(len(e) for e in ev), streams=S, rate=rate, has_events=bool(ops),
+                replace_held=any(op[0] == "replace" and op[3] for op in ops), replace_unheld=any(op[0] == "replace" and not op[3] for op in ops),
+                append=any(op[0] == "append" for op in ops), max_piece=max(b - a for a, b in zip(case["cuts"][:-1], case["cuts"][1:])),
+                edge_len=bool(lens & {63, 64, 65}))
+
+
+def bank_suite_problems(family, seed, n, shapes):
+    """What the suite's cases of a family must exercise (sections 3 and 4 of the sweeps' brief), judged from the oracle alone -> (what is
+    missing, the facts)"""
+    if family == "model_bank":
+        facts = [model_case_facts(bank_case(family, seed, ci, shapes.get(ci))) for ci in range(n)]
+    else:
+        facts = [bank_case_facts(bank_case(family, seed, ci, shapes.get(ci)), family) for ci in range(n)]
+    bad = []
+    need = lambda ok, text: None if ok else bad.append(text)
+    need(not any(f["sensitive"] for f in facts), "a case is threshold-sensitive")
+    holders, fired = sum(f["holders"] for f in facts), sum(f["fired"] for f in facts)
+    need(10 * fired >= 6 * holders, "%d of %d streams that hold a wakeword, set or model fire" % (fired, holders))
+    small = [f for f in facts if f["streams"] < 70]
+    need(10 * sum(f["fired"] for f in small) >= 6 * sum(f["holders"] for f in small), "fewer than 60 %% of the holders fire without the 70-stream case")
+    need(all(f["fired"] > 0 for f in facts if f.get("band", 5) != 0), "a case never fires: fired per case %r" % [f["fired"] for f in facts])
+    need(any(f["twice"] for f in facts), "no stream with two or more detections")
+    need(any(f["eager"] for f in facts), "no case with eager on")
+    need(any(f["streams"] >= 70 for f in facts), "no case with 70 streams")
+    live = family.startswith("live") or family == "model_bank"
+    if live:   # (whole recordings have no resets or re-targets)
+        need(any(f["soon"] for f in facts), "no detection within two window lengths of a reset or re-target")
+        need(any(f["max_piece"] >= 11 for f in facts), "no call of 11 chunks")
+    if family == "model_bank":
+        # (a model bank takes mfcc_size 16 only and has neither a band nor a score mode)
+        need(any(f["other_none"] for f in facts), "no firing model whose none index differs from model 0's")
+        need(any(f["no_none"] for f in facts), "no firing model without a none label")
+        need(any(f["logits_checked"] for f in facts), "no case whose live logits are compared")
+        need(any(f["has_set"] for f in facts), "no set_models event")
+        need({2, 3} <= set().union(*[f["layers"] for f in facts]), "not both layer counts")
+        need(any(f["streams"] >= 70 and f["has_set"] for f in facts), "the 70-stream case has no events")
+        return bad, facts
+    need(any(f["percentile"] for f in facts), "no percentile score mode")
+    need({3, 6} <= {f["band"] for f in facts}, "not both bands 3 and 6")
+    need({5, 13, 16} <= {f["K"] for f in facts}, "not every mfcc_size")
+    need(any(f["streams"] >= 70 and f["edge_len"] for f in facts), "no template of 63 / 64 / 65 frames in the 70-stream case")
+    if family.endswith("sets"):
+        need(any(f["both"] for f in facts), "no frame where two wakewords of a set both pass")
+    if family.startswith("live"):
+        need(any(f["replace_held"] for f in facts) and any(f["replace_unheld"] for f in facts), "not both kinds of replacement")
+        need(any(f["append"] for f in facts), "no put that appends")
+        need(any(f["rate"] in (48000, 8000) for f in facts), "no 48 kHz or 8 kHz input")
+        need(any(f["streams"] >= 70 and f["has_events"] for f in facts), "the 70-stream case has no events")
+    return bad, facts
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bank-cases", type=int, default=0, help="whole recordings over a wakeword bank (rp_batch_detect_bank, rp_dtw_score_bank)")
+    ap.add_argument("--bank-sets-cases", type=int, default=0, help="whole recordings over wakeword sets (rp_batch_detect_bank_sets)")
+    ap.add_argument("--live-bank-cases", type=int, default=0, help="live batches over a bank: resets, re-targets, puts, filters, resampled input")
+    ap.add_argument("--live-bank-sets-cases", type=int, default=0, help="live batches over wakeword sets, with slot scores")
+    ap.add_argument("--model-bank-cases", type=int, default=0, help="a model bank: whole recordings and live batches with set_models events")
     ap.add_argument("--cases", type=int, default=100)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--min-level-exp", type=float, default=-2.0, help="MFCC sweep: signal levels 10^[this, 0.5]")
@@ -1213,6 +2421,14 @@ if __name__ == "__main__":
         ("live multi sweep", a.live_multi_cases, lambda n: run_live_multi_sweep(ra, ctx, n, a.seed, verbose=True),
          lambda r: "%d cases, %d detections equal to the oracle's (references-only cases also bitwise equal to the offline batch), %d cases with a model, %d near-tie cases" % r),
         ("model sweep", a.model_cases, lambda n: run_model_sweep(ra, n, a.seed, verbose=True, ctx=ctx), lambda r: "%d cases, %d detections compared" % r),
+    ]
+    bank_line = lambda r: "%d cases, %d detections equal to the oracle's, %d threshold-sensitive cases set aside, %.0f s" % r
+    families += [
+        ("bank sweep", a.bank_cases, lambda n: run_bank_sweep(ra, ctx, n, a.seed, verbose=True), bank_line),
+        ("bank sets sweep", a.bank_sets_cases, lambda n: run_bank_sets_sweep(ra, ctx, n, a.seed, verbose=True), bank_line),
+        ("live bank sweep", a.live_bank_cases, lambda n: run_live_bank_sweep(ra, ctx, n, a.seed, verbose=True), bank_line),
+        ("live bank sets sweep", a.live_bank_sets_cases, lambda n: run_live_bank_sets_sweep(ra, ctx, n, a.seed, verbose=True), bank_line),
+        ("model bank sweep", a.model_bank_cases, lambda n: run_model_bank_sweep(ra, ctx, n, a.seed, verbose=True), bank_line),
     ]
     failed = 0
     for name, n, run, text in families:
