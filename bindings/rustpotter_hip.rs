@@ -288,6 +288,19 @@ extern "C" {
     pub fn rp_model_bank_size(bank: *const rp_model_bank) -> c_int;
     pub fn rp_model_bank_train_size(bank: *const rp_model_bank, model: i64) -> c_int;
     pub fn rp_model_bank_labels(bank: *const rp_model_bank, model: i64) -> c_int;
+    pub fn rp_model_bank_reserve(bank: *mut rp_model_bank, max_train_size: c_int, max_labels: c_int, n_models: usize, n_frames: usize) -> c_int;
+    pub fn rp_model_bank_reserved(bank: *const rp_model_bank, max_train_size: *mut c_int, max_labels: *mut c_int) -> c_int;
+    pub fn rp_model_bank_pool_growths(bank: *const rp_model_bank) -> c_int;
+    pub fn rp_model_bank_put(bank: *mut rp_model_bank, first: usize, n: usize, models: *const *const rp_model, none_index: *const i32) -> c_int;
+    pub fn rp_model_bank_put_from_rpw(bank: *mut rp_model_bank, first: usize, n: usize, rpw_buffers: *const *const u8, rpw_lens: *const usize) -> c_int;
+    pub fn rp_model_bank_train(bank: *mut rp_model_bank, first: usize, n: usize, options: *const rp_train_options, seeds: *const u64,
+                               train_counts: *const usize, train_names: *const *const c_char, train_wavs: *const *const u8,
+                               train_lens: *const usize, test_counts: *const usize, test_names: *const *const c_char,
+                               test_wavs: *const *const u8, test_lens: *const usize, prev_models: *const *const u8,
+                               prev_model_lens: *const usize, out_rpw: *mut *mut u8, out_lens: *mut usize, final_loss: *mut f32,
+                               test_accuracy: *mut f32) -> c_int;
+    pub fn rp_model_bank_read_image(bank: *const rp_model_bank, model: i64, out: *mut c_void, cap: usize, need: *mut usize) -> c_int;
+    pub fn rp_model_bank_last_put_ms(bank: *const rp_model_bank) -> f64;
     pub fn rp_mlp_forward_windows_bank(ctx: *mut rp_ctx, bank: *const rp_model_bank, stream_model: *const i32, mfcc: *const f32, S: usize,
                                        n_frames: usize, precision: c_int, logits: *mut f32, win_pitch: usize) -> c_int;
     pub fn rp_batch_detect_model_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
@@ -456,8 +469,8 @@ impl Drop for Templates { fn drop(&mut self) { unsafe { rp_templates_free(self.h
 impl Templates {
     pub fn max_len(&self) -> usize { unsafe { rp_templates_max_len(self.h) as usize } }
 }
-/// A bank of personal wakeword MODELS on the device: stream `s` of a bank call is run by model `stream_model[s]` (-1: none).  Immutable;
-/// borrows the context it was made on.
+/// A bank of personal wakeword MODELS on the device: stream `s` of a bank call is run by model `stream_model[s]` (-1: none).  Borrows the
+/// context it was made on.
 pub struct ModelBank { h: *mut rp_model_bank }
 impl Drop for ModelBank { fn drop(&mut self) { unsafe { rp_model_bank_free(self.h) } } }
 impl ModelBank {
@@ -468,8 +481,74 @@ impl ModelBank {
         let r = unsafe { rp_model_bank_train_size(self.h, model as i64) };
         if r < 0 { Err(last_error()) } else { Ok(r as usize) }
     }
-    /// the largest label count in the bank: the label pitch of `mlp_forward_windows_bank`
+    /// the label pitch of `mlp_forward_windows_bank` and of a live batch's logits: max(reserved label count, the largest in the bank)
     pub fn labels(&self) -> usize { unsafe { rp_model_bank_labels(self.h, -1) }.max(0) as usize }
+    /// (train size, label count) the bank may ever hold (`reserve`), 0: not reserved
+    pub fn reserved(&self) -> (usize, usize) {
+        let (mut l, mut c): (c_int, c_int) = (0, 0);
+        unsafe { rp_model_bank_reserved(self.h, &mut l, &mut c) };
+        (l.max(0) as usize, c.max(0) as usize)
+    }
+    /// how often the pools were replaced by larger ones
+    pub fn pool_growths(&self) -> usize { unsafe { rp_model_bank_pool_growths(self.h) }.max(0) as usize }
+    /// the put kernel's own time in the last put, in milliseconds (0 unless the context times its kernels)
+    pub fn last_put_ms(&self) -> f64 { unsafe { rp_model_bank_last_put_ms(self.h) } }
+    // The calls below change the bank through `&self`: a `StreamBatch` borrows its bank for life, and changing the bank under a live batch
+    // is what they are for.  The library orders every update on the context's stream and returns when it is complete.
+    /// Declares the largest window and label count the bank will ever hold (what a live batch over it keeps room for; 0: leave) and
+    /// pre-sizes the pools (hints; 0: leave).  Refused below the current largest, and for a new value while a stream batch over the bank exists.
+    pub fn reserve(&self, max_train_size: usize, max_labels: usize, n_models: usize, n_frames: usize) -> Result<(), String> {
+        status(unsafe { rp_model_bank_reserve(self.h, max_train_size as c_int, max_labels as c_int, n_models, n_frames) })
+    }
+    /// Models of the bank's context into the slots `first .. first + n - 1`: replaced below `size()`, appended at it.  `none_index`: one per
+    /// model, or empty for none (-1).  A refused call leaves the bank as it was.
+    pub fn put(&self, first: usize, models: &[&Model], none_index: &[i32]) -> Result<(), String> {
+        assert!(none_index.is_empty() || none_index.len() == models.len());
+        let hs: Vec<*const rp_model> = models.iter().map(|m| m.h as *const rp_model).collect();
+        status(unsafe { rp_model_bank_put(self.h, first, models.len(), hs.as_ptr(), if none_index.is_empty() { std::ptr::null() } else { none_index.as_ptr() }) })
+    }
+    /// Wakeword-model `.rpw` bytes into the slots `first .. first + n - 1`.
+    pub fn put_from_rpw(&self, first: usize, rpw: &[Vec<u8>]) -> Result<(), String> {
+        let ptrs: Vec<*const u8> = rpw.iter().map(|b| b.as_ptr()).collect();
+        let lens: Vec<usize> = rpw.iter().map(|b| b.len()).collect();
+        status(unsafe { rp_model_bank_put_from_rpw(self.h, first, rpw.len(), ptrs.as_ptr(), lens.as_ptr()) })
+    }
+    /// Training straight into the slots `first .. first + n - 1` (`wakeword_models_train_from_buffers` without the parameter round trip);
+    /// returns (`.rpw` bytes -- empty unless `want_rpw` --, last loss, test accuracy) per model.
+    pub fn train(&self, first: usize, m_type: c_int, models: &[ModelSamples], learning_rate: f64, epochs: usize, want_rpw: bool)
+                 -> Result<Vec<(Vec<u8>, f32, f32)>, String> {
+        fn flat(sets: Vec<&Vec<(String, Vec<u8>)>>) -> (Vec<usize>, Vec<CString>, Vec<*const u8>, Vec<usize>) {
+            (sets.iter().map(|s| s.len()).collect(), sets.iter().flat_map(|s| s.iter()).map(|s| CString::new(s.0.as_str()).unwrap()).collect(),
+             sets.iter().flat_map(|s| s.iter()).map(|s| s.1.as_ptr()).collect(), sets.iter().flat_map(|s| s.iter()).map(|s| s.1.len()).collect())
+        }
+        let (trc, trn, trb, trl) = flat(models.iter().map(|m| &m.train).collect());
+        let (tec, ten, teb, tel) = flat(models.iter().map(|m| &m.test).collect());
+        let trp: Vec<*const c_char> = trn.iter().map(|n| n.as_ptr()).collect();
+        let tep: Vec<*const c_char> = ten.iter().map(|n| n.as_ptr()).collect();
+        let seeds: Vec<u64> = models.iter().map(|m| m.seed).collect();
+        let prev: Vec<*const u8> = models.iter().map(|m| m.prev_model.as_ref().map_or(std::ptr::null(), |p| p.as_ptr())).collect();
+        let prev_lens: Vec<usize> = models.iter().map(|m| m.prev_model.as_ref().map_or(0, |p| p.len())).collect();
+        let opt = rp_train_options { m_type, learning_rate: learning_rate as f32, epochs, test_epochs: 0, mfcc_size: 16, seed: 1 };
+        let n = models.len();
+        let mut out: Vec<*mut u8> = vec![std::ptr::null_mut(); n];
+        let (mut out_lens, mut loss, mut acc) = (vec![0usize; n], vec![0f32; n], vec![0f32; n]);
+        let (po, pl) = if want_rpw { (out.as_mut_ptr(), out_lens.as_mut_ptr()) } else { (std::ptr::null_mut(), std::ptr::null_mut()) };
+        status(unsafe {
+            rp_model_bank_train(self.h, first, n, &opt, seeds.as_ptr(), trc.as_ptr(), trp.as_ptr(), trb.as_ptr(), trl.as_ptr(), tec.as_ptr(),
+                                tep.as_ptr(), teb.as_ptr(), tel.as_ptr(), prev.as_ptr(), prev_lens.as_ptr(), po, pl, loss.as_mut_ptr(),
+                                acc.as_mut_ptr())
+        })?;
+        if !want_rpw { return Ok(loss.into_iter().zip(acc).map(|(l, a)| (Vec::new(), l, a)).collect()); }
+        out.into_iter().zip(out_lens).zip(loss.into_iter().zip(acc)).map(|((p, n), (l, a))| take_buffer(0, p, n).map(|b| (b, l, a))).collect()
+    }
+    /// The bank image of one model as the kernels read it: wimg | b1 | wsum | tail (padded to a multiple of 4 floats).
+    pub fn read_image(&self, model: usize) -> Result<Vec<u8>, String> {
+        let mut need = 0usize;
+        status(unsafe { rp_model_bank_read_image(self.h, model as i64, std::ptr::null_mut(), 0, &mut need) })?;
+        let mut buf = vec![0u8; need];
+        status(unsafe { rp_model_bank_read_image(self.h, model as i64, buf.as_mut_ptr() as *mut c_void, need, std::ptr::null_mut()) })?;
+        Ok(buf)
+    }
 }
 /// A bank of personal wakeword references on the device: stream `s` of a bank call carries wakeword `stream_wakeword[s]` (-1: none) --
 /// one `Rustpotter` per thread, each with its own wakeword (src/detector.rs:304-346), as one batch.  Borrows the context it was made on.

@@ -843,7 +843,7 @@ int rp_batch_detect_model(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
 /* Personal wakeword MODELS: a model BANK -- W wakeword models resident on the device -- and whole-recording calls in which stream s runs its
  * own model stream_model[s].  The batched form of one `Rustpotter` per thread, each holding one wakeword model; the model counterpart of
  * rp_wakeword_bank.  The bank COPIES what it needs of every model (device to device), so the rp_model handles may be freed once the bank
- * exists; it borrows `ctx`, which must outlive it, is used with that context only, and is immutable.  A model has no thresholds of its own
+ * exists; it borrows `ctx`, which must outlive it, and is used with that context only.  A model has no thresholds of its own
  * (run_wakeword_detectors, src/detector.rs:433-447, passes the detector's): every stream takes the call's config.
  * Limits (refused with an error that names them) -- the shapes whose whole-recording forward is mlp_windows_kernel: mfcc_size 16 with an
  * input of whole frames; windows (train_size) of at most 256 frames; layer 1 at most 32 wide (every Tiny model, Small models up to 197
@@ -873,8 +873,70 @@ int rp_model_bank_size(const rp_model_bank *bank);
 /* train_size (the window length in frames) of one model; model < 0: the largest in the bank (0 for an empty bank).  -1 for a NULL bank or
  * an index outside the bank. */
 int rp_model_bank_train_size(const rp_model_bank *bank, long long model);
-/* label count of one model; model < 0: the largest in the bank = the label pitch of rp_mlp_forward_windows_bank.  -1 as above. */
+/* label count of one model; model < 0: the label pitch of rp_mlp_forward_windows_bank and rp_stream_batch_logits = max(reserved label count,
+ * the largest in the bank), so the largest in the bank for a bank nobody reserved (while a stream batch over the bank exists the pitch
+ * never shrinks: a replaced model may leave it larger than the bank needs until the batches are gone and the next put).  -1 as above. */
 int rp_model_bank_labels(const rp_model_bank *bank, long long model);
+/* ---- A model bank that changes: train, add and replace models, also under live-stream batches.  The model counterpart of "A bank that
+ * changes" above (rp_wakeword_bank_reserve / _put / _put_from_rpw / _enrol).
+ * rp_model_bank_put / _put_from_rpw / _train write the models first .. first + n - 1.  first <= rp_model_bank_size is required (a bank has no
+ * holes): indices below the size are REPLACED, indices at or above it extend the bank; n == 0 succeeds and changes nothing.  Every limit and
+ * wording of rp_model_bank_new applies per model ("model <index>: <reason>", <index> = the bank index first + i; the .rpw route says
+ * "wakeword <index>: <reason>" as rp_model_bank_new_from_rpw does).  These calls also refuse parameters that are not finite ("model <index>:
+ * parameters must be finite"); rp_model_bank_new stays as it is.  A call that is refused or fails leaves the bank exactly as it was: size,
+ * largest window, label pitch, every image byte.
+ * The models' bank images are built ON THE DEVICE from the raw f32 parameters (model_bank_put_kernel, one launch per call whatever n) with
+ * exactly the bits rp_model_bank_new gives them: the three-part bf16 image of layer 1, its bias, the per-coefficient weight sums and the
+ * packed tail layers.
+ * Storage: the bank's device arrays are pools.  New entries are appended, a replaced model's old ones stay behind as garbage, and a full pool
+ * is replaced by one of at least twice the size into which only the live models move (on the device) -- growth is the compaction.
+ * Ordering: every update is enqueued on the context's stream behind whatever still reads the bank, and the call returns after it has
+ * completed.  The next call that uses the bank sees the new contents, the next rp_stream_batch_process of a live batch over it included;
+ * nothing in flight ever sees a half-written model, and an old pool is freed only after the move out of it has completed.
+ * Live-stream batches: a model-bank batch sizes every stream's MFCC history (the largest train_size - 1 frames) and its logits (the label
+ * pitch) once, at creation, and keeps both as its own from then on; so the bank must never come to hold a window longer or a label count
+ * larger than a live batch has room for.  rp_model_bank_reserve declares the largest the bank will ever hold: a put refuses what exceeds it,
+ * and rp_stream_batch_new_model_bank keeps room for max(reserved, current, 1).  Without a reservation, while a batch over the bank exists, a
+ * window longer or a label count larger than the current largest is refused (the error says to call rp_model_bank_reserve before creating the
+ * batch); without either, anything within the bank's limits goes.  The bank counts its batches (a batch is freed before its bank).  A
+ * reserved bank of 0 models is the natural starting state of a service.
+ * The bank does not touch batches: a stream that holds an index while that index is replaced runs the new model from the next call on, with
+ * the detector state it has; its window becomes the new train_size, read from the history the stream already holds.  For the reference's
+ * remove_wakeword + add_wakeword, call rp_stream_batch_set_models for those streams: it resets them as it always does.  Removing a model is not
+ * offered: disconnect its streams; the next put reuses the slot.
+ * All host arrays of these calls are HOST arrays, whatever the pointer flag of the context. */
+/* max_train_size > 0: no model's window may become longer; at least the current largest, at most 256.  max_labels > 0: no model may have more
+ * labels; at least the current largest, at most 32 (the limit on tail-layer width).  Both can change only while no stream batch over the bank
+ * exists; 0 leaves a value as it is.  n_models / n_frames (the sum of the models' windows) pre-size the pools; hints, never limits. */
+int rp_model_bank_reserve(rp_model_bank *bank, int max_train_size, int max_labels, size_t n_models, size_t n_frames);
+/* the reserved train size and label count (either pointer may be NULL), 0 = none; returns 0, -1 for a NULL bank */
+int rp_model_bank_reserved(const rp_model_bank *bank, int *max_train_size, int *max_labels);
+/* how often the pools have been replaced by larger ones so far (tests and capacity planning); -1 for a NULL bank */
+int rp_model_bank_pool_growths(const rp_model_bank *bank);
+/* models [n]: handles of the bank's context, read through their raw device parameters; none_index [n] as in rp_model_bank_new. */
+int rp_model_bank_put(rp_model_bank *bank, size_t first, size_t n, const rp_model *const *models, const int32_t *none_index);
+/* The same from wakeword-model .rpw bytes, with the rules of rp_model_bank_new_from_rpw (one mfcc_size, 16): the files are parsed on the host,
+ * the raw parameters of all n models go to the device in one upload, and no rp_model is created. */
+int rp_model_bank_put_from_rpw(rp_model_bank *bank, size_t first, size_t n, const uint8_t *const *rpw_buffers, const size_t *rpw_lens);
+/* Training straight into bank slots: the arguments of rp_wakeword_model_train_batch from `seeds` on, unchanged, and the same stages; the
+ * trained parameters then go from the training workspace into the bank on the device -- no parameter round trip.  Labels, none_index and
+ * train_size are the trained model's.  options->mfcc_size other than 16, or a previous model of another mfcc_size, is refused with the bank's
+ * wording; a training set the single call refuses fails the call with that error behind "model <index>: " (the bank index); a model that
+ * trains to parameters that are not finite fails it with "model <index>: parameters must be finite".  out_rpw / out_lens [n] may both be
+ * NULL; given, they receive exactly rp_wakeword_model_train_batch's bytes (free each with rp_buffer_free), and on failure every entry is
+ * NULL. */
+int rp_model_bank_train(rp_model_bank *bank, size_t first, size_t n, const rp_train_options *options, const uint64_t *seeds,
+                        const size_t *train_counts, const char *const *train_names, const uint8_t *const *train_wavs, const size_t *train_lens,
+                        const size_t *test_counts, const char *const *test_names, const uint8_t *const *test_wavs, const size_t *test_lens,
+                        const uint8_t *const *prev_models, const size_t *prev_model_lens, uint8_t **out_rpw, size_t *out_lens, float *final_loss,
+                        float *test_accuracy);
+/* The bank image of one model as the kernels read it, copied to the HOST buffer `out` of `cap` bytes: wimg (train_size * 192 pieces of 16
+ * bytes, [frame][part 3][k-half][output < 32][8 k] bf16) | b1 | wsum [rows][16] | tail, zero padded to a multiple of 4 floats.  *need (may
+ * be NULL) receives the byte count; out == NULL only queries it.  It exists so that the prepared bits can be compared directly. */
+int rp_model_bank_read_image(const rp_model_bank *bank, long long model, void *out, size_t cap, size_t *need);
+/* model_bank_put_kernel's own time in the bank's last put, in milliseconds, by events around its launch; 0 unless the context times its
+ * kernels (rp_ctx_timing_enable).  0 for a NULL bank. */
+double rp_model_bank_last_put_ms(const rp_model_bank *bank);
 /* rp_mlp_forward_windows with stream s run by model stream_model[s] [S] (-1: none): mfcc [S][n_frames][16] ->
  * logits [S][win_pitch][rp_model_bank_labels(bank, -1)].  Row (s, w) holds the labels of s's model, zeros behind them; windows behind
  * n_win(s), streams without a model and streams shorter than their window are zero rows.  win_pitch below the largest n_win(s) of the call
@@ -897,7 +959,7 @@ int rp_batch_detect_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fm
  * Stream s behaves as Rustpotter::new(config) + add_wakeword(models[stream_model[s]]) + process_samples per chunk -- the semantics of
  * rp_batch_detect_model_bank with the detector state carried between calls on the device.  Thresholds come from `config` (a model has none of
  * its own), mfcc_size is 16, the arithmetic is RP_MLP_F32, and a process call makes ONE forward launch (mlp_bank_stream_kernel) whatever
- * the number of models.  Every stream keeps a history of rp_model_bank_train_size(bank, -1) - 1 frames; its own window starts
+ * the number of models.  Every stream keeps a history of max(reserved, rp_model_bank_train_size(bank, -1), 1) - 1 frames; its own window starts
  * train_size(s) - 1 frames before the new frame.  Index rules are those of rp_stream_batch_new_bank: a host array is checked before
  * anything is allocated (an index outside [-1, W) is an error that names the stream), a device array is copied and the kernels treat such
  * an index as -1.  An empty bank, or every index -1: calls succeed and report nothing.  The batch borrows `ctx` and `bank`, which must

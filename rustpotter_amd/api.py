@@ -122,6 +122,8 @@ SYMBOLS = [
     "rp_stream_batch_slot_scores",
     "rp_model_bank_new", "rp_model_bank_new_from_rpw", "rp_model_bank_free", "rp_model_bank_size", "rp_model_bank_train_size",
     "rp_model_bank_labels", "rp_mlp_forward_windows_bank", "rp_batch_detect_model_bank",
+    "rp_model_bank_reserve", "rp_model_bank_reserved", "rp_model_bank_pool_growths", "rp_model_bank_put", "rp_model_bank_put_from_rpw",
+    "rp_model_bank_train", "rp_model_bank_read_image", "rp_model_bank_last_put_ms",
     "rp_stream_batch_new_model_bank", "rp_stream_batch_set_models", "rp_stream_batch_logits",
 ]
 
@@ -267,6 +269,18 @@ def load_library():
     L.rp_model_bank_size.argtypes = [vp]
     L.rp_model_bank_train_size.argtypes = [vp, C.c_longlong]
     L.rp_model_bank_labels.argtypes = [vp, C.c_longlong]
+    L.rp_model_bank_reserve.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t]
+    L.rp_model_bank_reserved.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.rp_model_bank_pool_growths.argtypes = [vp]
+    L.rp_model_bank_put.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(vp), i32p]
+    L.rp_model_bank_put_from_rpw.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
+    L.rp_model_bank_train.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_TrainOptions), C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t), fp, fp]
+    L.rp_model_bank_read_image.argtypes = [vp, C.c_longlong, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rp_model_bank_last_put_ms.argtypes = [vp]
+    L.rp_model_bank_last_put_ms.restype = C.c_double
     L.rp_mlp_forward_windows_bank.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t]
     L.rp_batch_detect_model_bank.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(_DetectorConfig), C.c_int,
                                              vp, vp, vp, C.c_int]
@@ -567,7 +581,8 @@ class Model:
 class ModelBank:
     """rp_model_bank: W wakeword models resident on the device, run per stream through an index (BatchContext.mlp_forward_windows_bank /
     batch_detect_model_bank).  Exactly one of models = [Model, ...] with none_index = [index of each model's "none" label or -1, ...]
-    (default: every -1), or rpw = [bytes of a wakeword-model .rpw, ...].  The bank copies what it needs: the Model objects may go."""
+    (default: every -1), or rpw = [bytes of a wakeword-model .rpw, ...].  The bank copies what it needs: the Model objects may go.
+    models=[] is an empty bank to reserve and fill later (reserve / put / put_rpw / train), also under a live StreamBatch."""
 
     def __init__(self, ctx, models=None, none_index=None, mfcc_size=16, rpw=None):
         import numpy as np
@@ -589,11 +604,103 @@ class ModelBank:
         if r < 0:
             self._h = None
             raise _err()
+        self._refresh()
+
+    def _refresh(self):
         self.W = int(self._L.rp_model_bank_size(self._h))
         self.train_sizes = [int(self._L.rp_model_bank_train_size(self._h, w)) for w in range(self.W)]   # window length of every model
         self.labels = [int(self._L.rp_model_bank_labels(self._h, w)) for w in range(self.W)]
         self.max_train_size = int(self._L.rp_model_bank_train_size(self._h, -1))
         self.label_pitch = int(self._L.rp_model_bank_labels(self._h, -1))
+
+    @property
+    def reserved(self):
+        """rp_model_bank_reserved: (train size, label count) the bank may ever hold, 0 = not reserved"""
+        a, b = C.c_int(), C.c_int()
+        if self._L.rp_model_bank_reserved(self._h, C.byref(a), C.byref(b)) < 0:
+            raise _err()
+        return a.value, b.value
+
+    @property
+    def pool_growths(self):
+        return int(self._L.rp_model_bank_pool_growths(self._h))
+
+    @property
+    def last_put_ms(self):
+        """model_bank_put_kernel's time in the last put (0 unless the context times its kernels)"""
+        return float(self._L.rp_model_bank_last_put_ms(self._h))
+
+    def reserve(self, max_train_size=0, max_labels=0, n_models=0, n_frames=0):
+        """rp_model_bank_reserve: the largest window and label count the bank will ever hold (what a live batch over it keeps room for)
+        and pool size hints"""
+        r = self._L.rp_model_bank_reserve(self._h, max_train_size, max_labels, n_models, n_frames)
+        self._refresh()
+        if r < 0:
+            raise _err()
+
+    def put(self, first, models, none_index=None):
+        """rp_model_bank_put: Model objects become the models first .. first + n - 1 -- replaced below W, appended at W"""
+        import numpy as np
+        n = len(models)
+        ni = np.full(n, -1, np.int32) if none_index is None else np.ascontiguousarray(none_index, np.int32)
+        assert ni.shape == (n,)
+        r = self._L.rp_model_bank_put(self._h, first, n, (C.c_void_p * n)(*[m._h for m in models]), ni.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._refresh()
+        if r < 0:
+            raise _err()
+
+    def put_rpw(self, first, rpw):
+        """rp_model_bank_put_from_rpw: wakeword-model .rpw bytes into the slots first .. first + n - 1"""
+        n = len(rpw)
+        bufs = [bytes(b) for b in rpw]
+        r = self._L.rp_model_bank_put_from_rpw(self._h, first, n, (C.c_char_p * n)(*bufs), (C.c_size_t * n)(*[len(b) for b in bufs]))
+        self._refresh()
+        if r < 0:
+            raise _err()
+
+    def train(self, first, models, m_type="tiny", learning_rate=0.027, epochs=10, mfcc_size=16, seeds=None, prev_models=None, want_rpw=True):
+        """rp_model_bank_train: models as BatchContext.train_wakeword_models takes them, trained straight into the slots first .. first +
+        n - 1.  Returns [(.rpw bytes or None, last loss, test accuracy)]."""
+        W = len(models)
+
+        def pack(sets):
+            names = [k.encode() for d in sets for k in d]
+            bufs = [bytes(v) for d in sets for v in d.values()]
+            n = len(names)
+            return ((C.c_size_t * W)(*[len(d) for d in sets]), (C.c_char_p * n)(*names), (C.c_char_p * n)(*bufs),
+                    (C.c_size_t * n)(*[len(b) for b in bufs]))
+        trc, trn, trb, trl = pack([m[0] for m in models])
+        tec, ten, teb, tel = pack([m[1] for m in models])
+        c_seeds = None if seeds is None else (C.c_uint64 * W)(*seeds)
+        prev = prev_lens = None
+        if prev_models is not None:
+            prev = (C.c_char_p * W)(*[None if p is None else bytes(p) for p in prev_models])
+            prev_lens = (C.c_size_t * W)(*[0 if p is None else len(p) for p in prev_models])
+        opt = _TrainOptions({"tiny": 0, "small": 1, "medium": 2, "large": 3}[m_type], learning_rate, epochs, 0, mfcc_size, 1)
+        out = (C.c_void_p * W)() if want_rpw else None
+        out_lens = (C.c_size_t * W)() if want_rpw else None
+        loss, acc = (C.c_float * W)(), (C.c_float * W)()
+        r = self._L.rp_model_bank_train(self._h, first, W, C.byref(opt), c_seeds, trc, trn, trb, trl, tec, ten, teb, tel, prev, prev_lens,
+                                        out, out_lens, loss, acc)
+        self._refresh()
+        if r < 0:
+            raise _err()
+        res = []
+        for w in range(W):
+            res.append((C.string_at(out[w], out_lens[w]) if want_rpw else None, loss[w], acc[w]))
+            if want_rpw:
+                self._L.rp_buffer_free(out[w])
+        return res
+
+    def read_image(self, model):
+        """rp_model_bank_read_image: the bank image of one model as the kernels read it (wimg | b1 | wsum | padded tail), bytes"""
+        need = C.c_size_t()
+        if self._L.rp_model_bank_read_image(self._h, model, None, 0, C.byref(need)) < 0:
+            raise _err()
+        buf = C.create_string_buffer(max(need.value, 1))
+        if self._L.rp_model_bank_read_image(self._h, model, buf, need.value, None) < 0:
+            raise _err()
+        return buf.raw[:need.value]
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -98,7 +98,12 @@ bool train_wakeword_model(Ctx *ctx, const rp_train_options &opt, size_t n_train,
 bool train_wakeword_models(Ctx *ctx, const rp_train_options &opt, size_t W, const uint64_t *seeds, const size_t *train_counts,
                            const char *const *train_names, const uint8_t *const *train_wavs, const size_t *train_lens,
                            const size_t *test_counts, const char *const *test_names, const uint8_t *const *test_wavs, const size_t *test_lens,
-                           const WakewordModelData *const *prev, std::vector<WakewordModelData> *out, float *final_loss, float *test_accuracy);
+                           const WakewordModelData *const *prev, std::vector<WakewordModelData> *out, float *final_loss, float *test_accuracy,
+                           size_t first_index = 0, struct TrainLeft *left = nullptr);
+// What a training call leaves on the device for a caller that goes on there (rp_model_bank_train): the trained layer l of model w lies at
+// ctx->ws_train + jobs[w].w[l] / jobs[w].b[l] (floats, 16-byte aligned) until the next call that uses the workspace.  first_index: the
+// index a refusal names model 0 of the call by.
+struct TrainLeft { std::vector<TrainJob> jobs; };
 // The epochs alone: one MLP per item, HOST arrays.  params in / out: per layer, weight [out][in] then bias [out]; loss_rows [B] (null: not
 // wanted): the rows of the last epoch's loss; tlog [Bt][dims[n_layers]] (null: no test forward): the logits of the test rows xt under the
 // final weights.  One upload and one download on the context's stream; launches of at most E epochs (rp_train.cpp).
@@ -110,7 +115,7 @@ struct MlpTrainItem {
     const int32_t *labels = nullptr;
     float *params = nullptr, *loss_rows = nullptr, *tlog = nullptr;
 };
-bool train_mlp_batch(Ctx *ctx, const std::vector<MlpTrainItem> &items, float learning_rate, size_t epochs);
+bool train_mlp_batch(Ctx *ctx, const std::vector<MlpTrainItem> &items, float learning_rate, size_t epochs, TrainLeft *left = nullptr);
 
 // The host's share of a batch (wav decoding, levels, weight draws, CBOR) is independent per sample / per wakeword / per model: up to 16 threads take indices from
 // one counter.  The first exception of a worker is rethrown on the calling thread.
@@ -320,17 +325,53 @@ struct Model {
 Model *model_from_data(Ctx *ctx, const WakewordModelData &model, int *n_layers, std::vector<int> *dims, int *none_index);
 
 // A model bank (rp_model_bank.cpp; its calls: rp_bank_calls.cpp): W wakeword models copied into pools on the device, run per stream through an index
-// (mlp_windows_bank_kernel in rp_mlp_windows.hip).  Borrows the context; immutable.
+// (mlp_windows_bank_kernel in rp_mlp_windows.hip).  Borrows the context.
 struct ModelBank {
     Ctx *ctx = nullptr;
-    ModelBankDev dev;
+    ModelBankDev dev;                // label_pitch: max(res_labels, the largest label count)
     std::vector<ModelBankEntry> e;   // the host's copy of dev.e
     DevBuf d_e, d_wimg, d_b1, d_wsum, d_tail, d_ww;
     BankDev scan;                    // W and a BankWakeword per model for scan_bank_kernel: max_len = L, avg set, both thresholds -1
     int max_L = 0, min_L = 0;
     // models: W handles of this context; none_index [W] (null: every -1); false with the error set
     static ModelBank *create(Ctx *ctx, size_t W, Model *const *models, int mfcc_size, const int32_t *none_index);
+
+    // ---- a bank that grows (rp_model_bank_reserve / _put / _put_from_rpw / _train), after Bank's.  The six device arrays are pools: a put
+    // appends its entries behind used[] (model_bank_put_kernel builds them there), a replaced model's old ones stay behind as garbage
+    // (dead[]), and a full pool is replaced by one of at least twice the size into which only the live models move
+    // (model_bank_move_kernel).  Everything is enqueued on the context's stream, so a launch that took the old ModelBankDev by value finishes
+    // on the old pools before they are freed.
+    enum { kImg = 0, kB1 = 1, kWsum = 2, kTail = 3 };   // wimg counts 16-byte pieces, the others floats
+    size_t used[4] = {0, 0, 0, 0}, dead[4] = {0, 0, 0, 0}, cap[4] = {0, 0, 0, 0};
+    size_t cap_models = 0;           // rows d_e / d_ww have room for
+    size_t grown = 0;                // how often the four pools were replaced (tests)
+    int res_L = 0, res_labels = 0;   // rp_model_bank_reserve: no model's window / label count may be larger (0: none)
+    mutable int live_batches = 0;    // stream batches over this bank (rp_stream_batch_new_model_bank .. _free)
+    DevBuf put_ws;                   // item table and flags of a put, entry tables of a move
+    // one model of a put: its raw parameters on the DEVICE and its shape (entry: everything but the four pool places)
+    struct PutItem {
+        const float *w[3] = {nullptr, nullptr, nullptr}, *b[3] = {nullptr, nullptr, nullptr};
+        ModelBankEntry entry{};
+    };
+    // What the bank refuses in a model of these layer widths, as ModelBank::create words it (`why` without the "model <index>: "), and its
+    // entry's shape.  image_ok: the handle's verdict on its three-part image; -1: worked out from the shape, as Model::create does.
+    static bool entry_of(const std::vector<int> &dims, int none_index, int image_ok, ModelBankEntry *e, std::string *why);
+    // `first` itself and what a reservation or a live batch adds to entry_of, for models first .. first + items.size() - 1; `who`: "model" or
+    // "wakeword".  Changes nothing.
+    bool put_check(size_t first, const std::vector<PutItem> &items, const char *who) const;
+    // Builds the entries in the pool tails, reads the kernel's verdict and only then commits the descriptors; returns after the stream has
+    // drained.  A refusal leaves the bank as it was.
+    bool put(size_t first, const std::vector<PutItem> &items, const char *who);
+    bool reserve(int max_train_size, int max_labels, size_t n_models, size_t n_frames);
+    bool grow_models(size_t n);                    // d_e / d_ww with room for n models
+    bool repool(const size_t want[4]);             // new pools of these capacities, the live models moved over
+    int max_window() const { return std::max(std::max(res_L, max_L), 1); }   // what a stream batch over the bank keeps room for
+    double last_put_ms = 0.0;                      // with rp_ctx_timing_enable: model_bank_put_kernel's time in the last put
 };
+// The layers of a parsed wakeword model as model_from_data checks them: layer count by type, widths, the tensors (pointers into `model`),
+// the index of the "none" label.  False with the error set.
+bool model_layers(const WakewordModelData &model, int *n_layers, std::vector<int> *dims, std::vector<const float *> *weights,
+                  std::vector<const float *> *biases, int *none_index);
 
 // ------------------------------------------------------------ `Rustpotter` mirror
 struct Detection {  // src/detector.rs:488-501

@@ -830,6 +830,37 @@ hipError_t launch_nn_score_bank(hipStream_t st, const ModelBankDev &b, const int
 hipError_t launch_model_bank_labels(hipStream_t st, const BatchDetection *det, const int32_t *n_det, const int32_t *label, size_t S, size_t win_pitch,
                                     int max_det, int32_t *det_label);
 
+// ---- a model bank that changes (rp_model_bank_put.hip).  One put prepares the pool entries of n models from their raw f32 parameters on the
+// device -- per layer weights [out][in] and biases [out]: an rp_model's plain copies, a staged upload or the training workspace -- with the bits
+// Model::create + Model::wsum_for(16) + ModelBank::create give on the host: the three-part layer-1 image (bf16_split3 of rp_ctx.cpp, operation
+// for operation), b1, wsum (f64 sums in frame order) and the packed tail.  `e` says where in the pools (the caller passes the pool bases; the
+// entries lie in the pool tails, which nothing in flight reads).  flags [n], zero before: the kernel ORs in what the host decides on before it
+// commits anything.  All device pointers.
+constexpr uint32_t kModelPutNotFinite = 1u;
+struct ModelPutItem {
+    const float *w[3], *b[3];   // layers 1..n_layers; 16-byte aligned
+    ModelBankEntry e;
+};
+struct ModelBankPut {
+    const ModelPutItem *items = nullptr;
+    size_t n = 0;
+    int max_L = 0, max_tail = 0;   // the longest window and the largest tail pitch among the items: the launch's workgroups per model
+    void *wimg = nullptr;
+    float *b1 = nullptr, *wsum = nullptr, *tail = nullptr;
+    uint32_t *flags = nullptr;
+};
+hipError_t launch_model_bank_put(hipStream_t st, const ModelBankPut &p);
+// Growth and compaction of the four pools: live model i has its entries where from[i] says in the old pools and gets those of to[i] in the new.
+struct ModelBankMove {
+    const ModelBankEntry *from = nullptr, *to = nullptr;
+    size_t n = 0;
+    const void *wimg_old = nullptr;
+    const float *b1_old = nullptr, *wsum_old = nullptr, *tail_old = nullptr;
+    void *wimg_new = nullptr;
+    float *b1_new = nullptr, *wsum_new = nullptr, *tail_new = nullptr;
+};
+hipError_t launch_model_bank_move(hipStream_t st, const ModelBankMove &m);
+
 // ---- live batches over a model bank (rp_mlp_bank_stream.hip; rp_stream_batch_new_model_bank): the n_new new windows of every stream, frame rows
 // [S][cap][16] with the first new frame at `fill` (>= max_L - 1, the bank's longest window, and fill + n_new <= cap); the window of stream s
 // that ends at new frame i starts L(s) - 1 frames before it.  mean [S][n_new][16], logits [S][n_new][label_pitch] (every row written: zeros

@@ -26,7 +26,7 @@ struct rp_stream_batch {
     // The bank may change under the batch (rp_wakeword_bank_put / _enrol): every call reads bank->dev and bank->rms_level afresh, and the bank
     // counts its batches so that no window longer than max_len gets in (Bank::put_check)
     const Bank *bank = nullptr;
-    ~rp_stream_batch() { if (bank) --bank->live_batches; }
+    ~rp_stream_batch() { if (bank) --bank->live_batches; if (mbank) --mbank->live_batches; }
     DevBuf bank_idx, bank_agg, bank_avg;
     // made by rp_stream_batch_new_bank_sets (set_size 1..8; 0: not a sets batch): stream s holds the set bank_idx[s][0 .. set_size), -1 an
     // empty slot; bank_agg / bank_avg are then the slot scores [S][set_size][frames per call] and slot_frames the frames of the last call
@@ -34,8 +34,11 @@ struct rp_stream_batch {
     size_t slot_frames = 0;
     // made by rp_stream_batch_new_model_bank: stream s runs the one model mbank[bank_idx[s]] (`ww` is empty, `bank` null).  max_len is the bank's
     // longest window; bank_agg / bank_avg / bank_label [S][frames per call] are the scores and labels of the streams' own windows, `logits`
-    // [S][logit_frames][label_pitch] those of the last call (rp_stream_batch_logits).  The bank is immutable.
+    // [S][logit_frames][label_pitch] those of the last call (rp_stream_batch_logits).  The bank may change under the batch (rp_model_bank_put /
+    // _train): every call reads mbank->dev afresh; max_len and label_pitch are the batch's own, fixed at creation (the bank's reservation or
+    // what it held then), and the bank counts its batches so that no longer window and no larger label count gets in (ModelBank::put_check)
     const ModelBank *mbank = nullptr;
+    int label_pitch = 0;
     DevBuf bank_label;
     size_t logit_frames = 0;
     size_t slots() const { return set_size ? (size_t)set_size : 1; }
@@ -99,7 +102,7 @@ static bool stream_batch_alloc(rp_stream_batch *b) {
     if (b->bank && (!b->bank_agg.reserve(rows * b->slots() * sizeof(float) + 16) || !b->bank_avg.reserve(rows * b->slots() * sizeof(float) + 16))) return false;
     if (b->mbank && (!b->bank_agg.reserve(rows * sizeof(float) + 16) || !b->bank_avg.reserve(rows * sizeof(float) + 16) ||
                      !b->bank_label.reserve(rows * sizeof(int32_t) + 16) || !b->mean.reserve(rows * 16 * sizeof(float) + 16) ||
-                     !b->logits.reserve(rows * (size_t)b->mbank->dev.label_pitch * sizeof(float) + 16))) return false;
+                     !b->logits.reserve(rows * (size_t)b->label_pitch * sizeof(float) + 16))) return false;
     if (!b->pcm[0].reserve(pcm_bytes) || !b->pcm[1].reserve(pcm_bytes) || !b->mfcc[0].reserve(S * pitch * K * sizeof(float) + slack) ||
         !b->mfcc[1].reserve(S * pitch * K * sizeof(float) + slack) || !b->state.reserve(S * stream_state_bytes()) ||
         !b->scores.reserve(rows * (size_t)b->Tmax * sizeof(float) + 16) || !b->vad.reserve(rows * sizeof(float) + 16) ||
@@ -383,7 +386,10 @@ static bool score_model_bank_stream(rp_stream_batch *b, const NewFrames &f, size
     Ctx *c = b->c;
     const ModelBank &bk = *b->mbank;
     b->logit_frames = n_new;
-    if (bk.dev.W == 0) return true;
+    // no model yet (a reserved empty bank): rp_stream_batch_logits answers zero rows
+    if (bk.dev.W == 0)
+        return !b->label_pitch || hip_ok(hipMemsetAsync(b->logits.p, 0, b->S * n_new * (size_t)b->label_pitch * sizeof(float), c->stream), "hipMemsetAsync");
+    if (bk.dev.label_pitch != b->label_pitch || bk.max_L > b->max_len) { set_last_error("stream batch: the model bank outgrew what the batch was sized for"); return false; }
     const int32_t *idx = b->bank_idx.as<int32_t>();
     float *mean = b->mean.as<float>(), *dlog = b->logits.as<float>();
     if (!hip_ok(launch_window_means_bank_stream(c->stream, bk.dev, bk.max_L, idx, f.rows, b->S, b->cap, f.fill, n_new, mean), "window_means_bank_stream_kernel"))
@@ -531,8 +537,8 @@ int rp_stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const
         // before anything is allocated
         if ((c->flags & RP_CTX_HOST_POINTERS) && !bank_indices_ok(bk.dev.W, 0, S, 0, stream_model, "model index")) return -1;
         std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
-        b->c = c; b->mbank = &bk; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
-        b->K = 16; b->max_len = std::max(bk.max_L, 1); b->Tmax = 1;
+        b->c = c; b->mbank = &bk; ++bk.live_batches; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
+        b->K = 16; b->max_len = bk.max_window(); b->label_pitch = bk.dev.label_pitch; b->Tmax = 1;
         if (!bank_indices_put(b.get(), 0, S, stream_model)) return -1;
         if (!c->tables_for(b->K)) return -1;
         b->hist_frames = (size_t)b->max_len - 1;   // every stream keeps the history of the bank's longest window; its own starts L(s) - 1 frames back
@@ -732,7 +738,7 @@ int rp_stream_batch_logits(rp_stream_batch *b, float *logits) {
         if (!c) return -1;
         if (!b->mbank) { set_last_error("rp_stream_batch_logits: the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
         if (!b->logit_frames) { set_last_error("rp_stream_batch_logits: the streams have not received audio yet"); return -1; }
-        const size_t bytes = b->S * b->logit_frames * (size_t)b->mbank->dev.label_pitch * sizeof(float);
+        const size_t bytes = b->S * b->logit_frames * (size_t)b->label_pitch * sizeof(float);
         if (bytes == 0) return 0;   // an empty bank has no labels
         if (!logits) { set_last_error("null argument"); return -1; }
         const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;

@@ -283,7 +283,8 @@ size_t epochs_per_launch(const std::vector<MlpTrainItem> &items, size_t grid) {
 size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
 }  // namespace
 
-bool train_mlp_batch(Ctx *ctx, const std::vector<MlpTrainItem> &items, float learning_rate, size_t epochs) {
+bool train_mlp_batch(Ctx *ctx, const std::vector<MlpTrainItem> &items, float learning_rate, size_t epochs, TrainLeft *left) {
+    if (left) left->jobs.clear();
     const size_t W = items.size();
     ctx->train_longest_launch_ms = 0.0; ctx->train_launches = 0;
     if (W == 0) return true;
@@ -400,14 +401,17 @@ bool train_mlp_batch(Ctx *ctx, const std::vector<MlpTrainItem> &items, float lea
         if (it.loss_rows && epochs) std::memcpy(it.loss_rows, img.data() + j.loss, it.B * sizeof(float));
         if (j.Bt) std::memcpy(it.tlog, img.data() + j.tlog, (size_t)j.Bt * (size_t)it.dims[it.n_layers] * sizeof(float));
     });
+    if (left) left->jobs = std::move(jobs);   // the parameters stay where the last launch left them
     return true;
 }
 
 bool train_wakeword_models(Ctx *ctx, const rp_train_options &opt, size_t W, const uint64_t *seeds, const size_t *train_counts,
                            const char *const *train_names, const uint8_t *const *train_wavs, const size_t *train_lens,
                            const size_t *test_counts, const char *const *test_names, const uint8_t *const *test_wavs, const size_t *test_lens,
-                           const WakewordModelData *const *prev, std::vector<WakewordModelData> *out, float *final_loss, float *test_accuracy) {
+                           const WakewordModelData *const *prev, std::vector<WakewordModelData> *out, float *final_loss, float *test_accuracy,
+                           size_t first_index, TrainLeft *left) {
     out->clear();
+    if (left) left->jobs.clear();
     ctx->train_feature_ms = 0.0;
     if (W == 0) { ctx->train_longest_launch_ms = 0.0; ctx->train_launches = 0; return true; }
     // prepare.  The features go through compute_wav_mfccs one sample after the other: it works on the context's stream and caches, and a
@@ -423,7 +427,7 @@ bool train_wakeword_models(Ctx *ctx, const rp_train_options &opt, size_t W, cons
         // what the single call's launches refuse: a layer whose input row does not fit mlp_layer_kernel's 64 KB of LDS
         for (int l = 0; ok && l < prep[w].n_layers(); ++l)
             if ((size_t)prep[w].dims[l] * sizeof(float) > 64 * 1024) ok = hip_ok(hipErrorInvalidValue, opt.epochs ? "training step" : "test forward");
-        if (!ok) { set_last_error("model " + std::to_string(w) + ": " + last_error()); return false; }
+        if (!ok) { set_last_error("model " + std::to_string(first_index + w) + ": " + last_error()); return false; }
         tr += train_counts[w]; te += test_counts[w];
     }
     ctx->train_feature_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -439,7 +443,7 @@ bool train_wakeword_models(Ctx *ctx, const rp_train_options &opt, size_t W, cons
         it.x = p.xtr.data(); it.xt = p.xte.data(); it.labels = p.ytr.data();
         it.params = p.params.data(); it.loss_rows = p.loss_rows.data(); it.tlog = p.tlog.data();
     }
-    if (!train_mlp_batch(ctx, items, opt.learning_rate, opt.epochs)) return false;
+    if (!train_mlp_batch(ctx, items, opt.learning_rate, opt.epochs, left)) return false;
     // finish
     out->resize(W);
     parallel_for(W, [&](size_t w) {
