@@ -81,6 +81,7 @@ pub const RP_DTW_KERNEL_BANK_SETS: c_int = 16384;
 pub const RP_DTW_KERNEL_BANK_SETS_STREAM: c_int = 32768;
 /// wakewords a stream's set may hold (`stream_wakewords [S][set_size]`)
 pub const RP_WAKEWORD_SET_MAX: c_int = 8;
+pub const RP_MODEL_SET_MAX: c_int = 8;
 pub const RP_WAKEWORD_BANK_MAX_TEMPLATES: c_int = 32;
 pub const RP_MLP_F32: c_int = 0;
 pub const RP_MLP_BF16: c_int = 1;
@@ -272,6 +273,15 @@ extern "C" {
                                           S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
     pub fn rp_stream_batch_set_models(b: *mut rp_stream_batch, first_stream: usize, n: usize, models: *const i32) -> c_int;
     pub fn rp_stream_batch_logits(b: *mut rp_stream_batch, logits: *mut f32) -> c_int;
+    pub fn rp_mlp_forward_windows_bank_sets(ctx: *mut rp_ctx, bank: *const rp_model_bank, stream_models: *const i32, set_size: c_int, mfcc: *const f32,
+                                            S: usize, n_frames: usize, precision: c_int, logits: *mut f32, win_pitch: usize) -> c_int;
+    pub fn rp_batch_detect_model_bank_sets(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                           bank: *const rp_model_bank, stream_models: *const i32, set_size: c_int, config: *const rp_detector_config,
+                                           precision: c_int, det: *mut rp_batch_detection, det_model: *mut i32, det_label: *mut i32, n_det: *mut i32,
+                                           max_det: c_int) -> c_int;
+    pub fn rp_stream_batch_new_model_bank_sets(ctx: *mut rp_ctx, bank: *const rp_model_bank, stream_models: *const i32, set_size: c_int,
+                                               config: *const rp_detector_config, S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
+    pub fn rp_stream_batch_set_model_sets(b: *mut rp_stream_batch, first_stream: usize, n: usize, stream_models: *const i32) -> c_int;
     pub fn rp_model_new(ctx: *mut rp_ctx, n_layers: c_int, dims: *const c_int, weights: *const *const f32, biases: *const *const f32,
                         out: *mut *mut rp_model) -> c_int;
     pub fn rp_model_free(m: *mut rp_model);
@@ -970,6 +980,39 @@ impl HipContext {
         let l = (0..n_streams).map(|s| label[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect();
         Ok((split_detections(det, n_det, max_det), l))
     }
+    /// `mlp_forward_windows_bank` over model sets: stream `s` holds `stream_models[s * set_size ..][..set_size]` (-1: an empty slot); logits
+    /// `[streams][set_size][win_pitch][bank.labels()]`, the windows counted from the set's longest model.
+    pub fn mlp_forward_windows_bank_sets(&self, bank: &ModelBank, stream_models: &[i32], set_size: usize, mfcc: &[f32], n_streams: usize,
+                                         n_frames: usize, win_pitch: usize) -> Result<Vec<f32>, String> {
+        assert!(set_size >= 1 && set_size <= RP_MODEL_SET_MAX as usize && stream_models.len() == n_streams * set_size && mfcc.len() >= n_streams * n_frames * 16);
+        let mut out = vec![0f32; n_streams * set_size * win_pitch * bank.labels()];
+        status(unsafe {
+            rp_mlp_forward_windows_bank_sets(self.h, bank.h, stream_models.as_ptr(), set_size as c_int, mfcc.as_ptr(), n_streams, n_frames, RP_MLP_F32,
+                                             out.as_mut_ptr(), win_pitch)
+        })?;
+        Ok(out)
+    }
+    /// `batch_detect_model_bank` where stream `s` holds a set of models, as a `Rustpotter` with several `add_wakeword_model` calls; returns
+    /// detections, the winners' bank indices and their labels.
+    pub fn batch_detect_model_bank_sets(&self, pcm: &[f32], n_streams: usize, n_samples: usize, bank: &ModelBank, stream_models: &[i32],
+                                        set_size: usize, config: &DetectorConfig, max_det: usize)
+                                        -> Result<(Detections, Vec<Vec<i32>>, Vec<Vec<i32>>), String> {
+        assert!(set_size >= 1 && set_size <= RP_MODEL_SET_MAX as usize && pcm.len() >= n_streams * n_samples && stream_models.len() == n_streams * set_size);
+        let c: rp_detector_config = config.into();
+        let mut det = vec![rp_batch_detection::default(); n_streams * max_det];
+        let (mut which, mut label) = (vec![0i32; n_streams * max_det], vec![0i32; n_streams * max_det]);
+        let mut n_det = vec![0i32; n_streams];
+        status(unsafe {
+            rp_batch_detect_model_bank_sets(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, bank.h,
+                                            stream_models.as_ptr(), set_size as c_int, &c, RP_MLP_F32, det.as_mut_ptr(), which.as_mut_ptr(),
+                                            label.as_mut_ptr(), n_det.as_mut_ptr(), max_det as c_int)
+        })?;
+        let cut = |v: &Vec<i32>| -> Vec<Vec<i32>> {
+            (0..n_streams).map(|s| v[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect()
+        };
+        let (w, l) = (cut(&which), cut(&label));
+        Ok((split_detections(det, n_det, max_det), w, l))
+    }
     /// The audio front-end of `Rustpotter::process_audio` (gain normaliser + band-pass, src/detector.rs:358-371) for whole streams:
     /// returns (filtered audio, per-chunk rms levels, per-chunk gains).
     pub fn frontend_batch(&self, pcm: &[f32], n_streams: usize, n_samples: usize, filters: &FiltersConfig, rms_level_ref: f32,
@@ -1128,10 +1171,29 @@ impl<'a> StreamBatch<'a> {
     pub fn set_models(&mut self, first_stream: usize, models: &[i32]) -> Result<(), String> {
         status(unsafe { rp_stream_batch_set_models(self.h, first_stream, models.len(), models.as_ptr()) })
     }
+    /// Model sets on live streams: stream `s` holds the models `stream_models[s * set_size ..][..set_size]` (-1: an empty slot) --
+    /// `batch_detect_model_bank_sets` with the state carried between calls.  `process_multi` reports the winner's bank index and label.
+    pub fn new_model_bank_sets(ctx: &'a HipContext, bank: &'a ModelBank, stream_models: &[i32], set_size: usize, config: &DetectorConfig,
+                               max_chunks_per_call: usize) -> Result<StreamBatch<'a>, String> {
+        assert!(set_size >= 1 && set_size <= RP_MODEL_SET_MAX as usize && stream_models.len() % set_size == 0);
+        let c: rp_detector_config = config.into();
+        let n_streams = stream_models.len() / set_size;
+        let mut h = std::ptr::null_mut();
+        status(unsafe { rp_stream_batch_new_model_bank_sets(ctx.h, bank.h, stream_models.as_ptr(), set_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, label_pitch: bank.labels(), _ctx: ctx, _t: std::marker::PhantomData })
+    }
+    /// Re-target the streams `first_stream ..` of a `new_model_bank_sets` batch, one row of the batch's `set_size` indices per stream:
+    /// remove-all plus add-in-order, each stream reset.  An error on any other batch.
+    pub fn set_model_sets(&mut self, first_stream: usize, stream_models: &[i32]) -> Result<(), String> {
+        if self.set_size == 0 { return Err("set_model_sets: the batch was not made by new_model_bank_sets".to_string()); }
+        assert!(stream_models.len() % self.set_size == 0, "rows of set_size indices");
+        status(unsafe { rp_stream_batch_set_model_sets(self.h, first_stream, stream_models.len() / self.set_size, stream_models.as_ptr()) })
+    }
     /// The logits of the last `process` / `process_multi` call of a `new_model_bank` batch, `[streams][frames of that call][label pitch of
-    /// the bank]`, zeros behind a model's labels.  An error on any other batch and before the first call.
+    /// the bank]` (a `new_model_bank_sets` batch: `[streams][set_size][frames][label pitch]`), zeros behind a model's labels.  An error on
+    /// any other batch and before the first call.
     pub fn logits(&mut self) -> Result<Vec<f32>, String> {
-        let mut out = vec![0f32; self.n_streams * self.last_chunks.max(1) * self.frames_per_chunk * self.label_pitch];
+        let mut out = vec![0f32; self.n_streams * self.set_size.max(1) * self.last_chunks.max(1) * self.frames_per_chunk * self.label_pitch];
         status(unsafe { rp_stream_batch_logits(self.h, out.as_mut_ptr()) })?;
         Ok(out)
     }

@@ -988,6 +988,48 @@ int rp_stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size_t n
  * are unspecified.  Returns -1 before the first process call and on any other kind of batch. */
 int rp_stream_batch_logits(rp_stream_batch *b, float *logits);
 
+/* Model SETS: several personal wakeword models per stream over a model bank.  stream_models [S][set_size] (set_size 1..RP_MODEL_SET_MAX) holds
+ * bank indices, -1 an empty slot anywhere in a row; stream s behaves as Rustpotter::new(config), add_wakeword(models[i]) for each live slot
+ * of its row in slot order, process_samples (src/detector.rs:304-346, 433-447, wakeword_nn.rs:137):
+ *  - its window is Lmax(s) frames, the longest train_size of its live slots, its countdown Lmax(s) / 2; it has n_win_s = n_frames - Lmax(s) + 1
+ *    windows;
+ *  - slot j scores the OLDEST train_size(j) frames of that window, with the thresholds of `config` (a model has none of its own; >=);
+ *  - the best passing score wins, the first slot of equal scores; a detection reports window = frame - Lmax(s) + 1, the winner's BANK index
+ *    and the label index of its best window.
+ * A row of all -1 is a detector without wakewords; duplicate indices change nothing.  Limits, arithmetic (RP_MLP_F32; RP_MLP_BF16 computes
+ * the same; the others are refused), empty-bank behaviour and index rules are those of the model-bank calls: with RP_CTX_HOST_POINTERS an index
+ * outside [-1, W) is an error that names the stream and the slot, found before anything is allocated or launched; with device arrays the
+ * kernels treat such an index as -1. */
+enum { RP_MODEL_SET_MAX = 8 };
+/* rp_mlp_forward_windows_bank over sets: logits [S][set_size][win_pitch][rp_model_bank_labels(bank, -1)]; row (s, j, w) holds model
+ * stream_models[s][j] on the train_size(j) frames from frame w, for w < n_win_s.  Rows are zero behind a model's labels, behind n_win_s, in
+ * empty slots and in EVERY slot of a stream shorter than Lmax(s), even where a shorter model of the set would fit (as
+ * rp_dtw_score_bank_sets).  win_pitch rules as rp_mlp_forward_windows_bank.  BITS: row (s, j) equals rp_mlp_forward_windows_bank over the
+ * first n_frames - (Lmax(s) - train_size(j)) frames of stream s with that model alone (the same kernel body with the same cut). */
+int rp_mlp_forward_windows_bank_sets(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_models, int set_size, const float *mfcc, size_t S,
+                                     size_t n_frames, int precision, float *logits, size_t win_pitch);
+/* rp_batch_detect_model_bank over sets.  det_model / det_label [S][max_det] (NULL to skip): each detection's bank index and label index;
+ * behind a stream's detections 0 and -1.  VAD and the reset after a detection as everywhere. */
+int rp_batch_detect_model_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                    const rp_model_bank *bank, const int32_t *stream_models, int set_size, const rp_detector_config *config,
+                                    int precision, rp_batch_detection *det, int32_t *det_model, int32_t *det_label, int32_t *n_det, int max_det);
+/* Model sets on LIVE streams: rp_stream_batch_new_model_bank with stream_models [S][set_size].  History, reservation rules, the bank's count
+ * of batches and the behaviour under rp_model_bank_put / _put_from_rpw / _train are those of rp_stream_batch_new_model_bank; Lmax(s) is read
+ * from the bank in every call.  A process call makes ONE forward launch (mlp_set_stream_kernel) over (stream, slot, row tile); the first
+ * window of a call starts Lmax(s) - 1 frames before the first new frame for every slot.  A stream fed in pieces reports the detections of
+ * rp_batch_detect_model_bank_sets over the concatenation, scores within 2e-6; its logits do not depend on the cut
+ * into calls and equal, slot by slot, those of rp_stream_batch_new_multi with the live slots' models (calls of at most 10 chunks).
+ * rp_stream_batch_process works without agg and is refused with agg; rp_stream_batch_process_multi reports det_wakeword = the winner's bank
+ * index and det_label; rp_stream_batch_logits returns [S][set_size][frames of the call][label pitch]; rp_stream_batch_set_input, _reset,
+ * _chunks_seen and the band-pass-only rp_stream_batch_set_filters work as on a model-bank batch.  The gain normaliser, _set_models,
+ * _set_wakewords, _set_wakeword_sets, _set_filters_bank and _slot_scores are refused, each with an error that says why. */
+int rp_stream_batch_new_model_bank_sets(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_models, int set_size,
+                                        const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out);
+/* Re-target streams first_stream .. first_stream + n - 1 of such a batch: stream_models [n][set_size].  All slots are removed, the new ones
+ * added in order and the stream reset, as rp_stream_batch_set_wakeword_sets does.  A refused row (host arrays) names its stream and slot and
+ * changes nothing.  An error on any other kind of batch. */
+int rp_stream_batch_set_model_sets(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *stream_models);
+
 /* Synthetic benchmark input of BASELINE.md §2, generated on the device:
  * pcm[s][i] = (splitmix64(seed ^ ((first_stream+s)<<32 + i)) >> 40) / 2^24 - 0.5 */
 int rp_synth_pcm_batch(rp_ctx *ctx, uint64_t seed, uint64_t first_stream, size_t S, size_t n_samples, size_t pcm_stride,

@@ -125,6 +125,7 @@ SYMBOLS = [
     "rp_model_bank_reserve", "rp_model_bank_reserved", "rp_model_bank_pool_growths", "rp_model_bank_put", "rp_model_bank_put_from_rpw",
     "rp_model_bank_train", "rp_model_bank_read_image", "rp_model_bank_last_put_ms",
     "rp_stream_batch_new_model_bank", "rp_stream_batch_set_models", "rp_stream_batch_logits",
+    "rp_mlp_forward_windows_bank_sets", "rp_batch_detect_model_bank_sets", "rp_stream_batch_new_model_bank_sets", "rp_stream_batch_set_model_sets",
 ]
 
 
@@ -311,6 +312,11 @@ def load_library():
     L.rp_stream_batch_new_model_bank.argtypes = [vp, vp, vp, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.rp_stream_batch_set_models.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
     L.rp_stream_batch_logits.argtypes = [vp, vp]
+    L.rp_mlp_forward_windows_bank_sets.argtypes = [vp, vp, vp, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t]
+    L.rp_batch_detect_model_bank_sets.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_int, C.POINTER(_DetectorConfig), C.c_int,
+                                                  vp, vp, vp, vp, C.c_int]
+    L.rp_stream_batch_new_model_bank_sets.argtypes = [vp, vp, vp, C.c_int, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.rp_stream_batch_set_model_sets.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
     _LIB = L
     return L
 
@@ -864,7 +870,7 @@ class StreamBatch:
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
                  mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None, bank_filters=None,
-                 stream_wakewords=None, set_size=None, model_bank=None, stream_model=None):
+                 stream_wakewords=None, set_size=None, model_bank=None, stream_model=None, stream_models=None):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
         with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
@@ -877,14 +883,24 @@ class StreamBatch:
         bank + stream_wakewords (rp_stream_batch_new_bank_sets): stream s holds the SET of wakewords stream_wakewords[s], [S][set_size]
         int32 with -1 = an empty slot (with device pointers: the address of a device array and set_size).
         model_bank + stream_model (rp_stream_batch_new_model_bank; templates is then None): stream s runs its own model
-        model_bank[stream_model[s]], -1 = none; set_models() re-targets streams, logits() returns the last call's logits."""
+        model_bank[stream_model[s]], -1 = none; set_models() re-targets streams, logits() returns the last call's logits.
+        model_bank + stream_models (rp_stream_batch_new_model_bank_sets): stream s holds the SET of models stream_models[s], [S][set_size]
+        int32 with -1 = an empty slot (with device pointers: the address of a device array and set_size); set_model_sets() re-targets
+        streams, logits() is then [S][set_size][frames][label pitch]."""
         self._L = load_library()
         self.set_size = 0
         self.label_pitch = 0
         self.ctx, self.templates, self.S, self.max_chunks = ctx, templates, S, max_chunks_per_call
         h = C.c_void_p()
         c = detector_config._c()
-        if model_bank is not None:
+        if model_bank is not None and stream_models is not None:
+            self._keep = model_bank   # the batch borrows the bank
+            self.label_pitch = model_bank.label_pitch
+            idx, ptr = self._indices(stream_models)
+            self.set_size = int(idx.shape[1] if set_size is None else set_size)
+            if self._L.rp_stream_batch_new_model_bank_sets(ctx._h, model_bank._h, ptr, self.set_size, C.byref(c), S, max_chunks_per_call, C.byref(h)) < 0:
+                raise _err()
+        elif model_bank is not None:
             self._keep = model_bank   # the batch borrows the bank
             self.label_pitch = model_bank.label_pitch
             idx, ptr = self._indices(stream_model)
@@ -966,11 +982,20 @@ class StreamBatch:
         if self._L.rp_stream_batch_set_models(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
             raise _err()
 
+    def set_model_sets(self, first_stream, stream_models, n=None):
+        """rp_stream_batch_set_model_sets: streams first_stream .. get the rows stream_models [n][set_size] (-1: an empty slot) and are
+        reset -- remove-all plus add-in-order; between process calls.  With device pointers: the address of a device int32 array of n rows."""
+        idx, ptr = self._indices(stream_models)
+        if self._L.rp_stream_batch_set_model_sets(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
+            raise _err()
+
     def logits(self):
-        """rp_stream_batch_logits -> [S][frames of the last process call][label pitch of the bank]"""
+        """rp_stream_batch_logits -> [S][frames of the last process call][label pitch of the bank]; a batch over model sets:
+        [S][set_size][frames][label pitch]"""
         import numpy as np
         assert self.ctx.host
-        out = np.empty((self.S, max(self._last_chunks, 1) * self.frames_per_chunk, self.label_pitch), np.float32)
+        n = max(self._last_chunks, 1) * self.frames_per_chunk
+        out = np.empty((self.S, self.set_size, n, self.label_pitch) if self.set_size else (self.S, n, self.label_pitch), np.float32)
         if self._L.rp_stream_batch_logits(self._h, out.ctypes.data) < 0:
             raise _err()
         return out
@@ -1891,6 +1916,65 @@ class BatchContext:
                                               MLP_PRECISION[precision], det.ctypes.data, dlab.ctypes.data, n_det.ctypes.data, max_det) < 0:
             raise _err()
         return det, dlab, n_det
+
+    def mlp_forward_windows_bank_sets(self, mfcc, bank, stream_models, precision="f32", win_pitch=None):
+        """rp_mlp_forward_windows_bank_sets: mfcc [S][n_frames][16] -> logits [S][set_size][win_pitch][bank.label_pitch]; row (s, j, w) holds
+        model stream_models[s][j] (-1: an empty slot) on the window that starts at frame w, for w < n_frames - Lmax(s) + 1.  win_pitch
+        defaults to the largest window count of the call."""
+        import numpy as np
+        assert self.host
+        mfcc = np.ascontiguousarray(mfcc, np.float32)
+        S, nf, K = mfcc.shape
+        assert K == 16
+        idx = np.ascontiguousarray(stream_models, np.int32)
+        assert idx.ndim == 2 and idx.shape[0] == S
+        if win_pitch is None:
+            lmax = [max([0] + [bank.train_sizes[w] for w in row if 0 <= w < bank.W]) for row in idx]
+            win_pitch = max([0] + [max(0, nf - l + 1) for l in lmax if l])
+        out = np.full((S, idx.shape[1], win_pitch, bank.label_pitch), np.nan, np.float32)
+        if self._L.rp_mlp_forward_windows_bank_sets(self._h, bank._h, idx.ctypes.data, idx.shape[1], mfcc.ctypes.data, S, nf, MLP_PRECISION[precision],
+                                                    out.ctypes.data, win_pitch) < 0:
+            raise _err()
+        return out
+
+    def mlp_forward_windows_bank_sets_dev(self, bank, idx_ptr, set_size, mfcc_ptr, S, n_frames, precision, out_ptr, win_pitch):
+        """rp_mlp_forward_windows_bank_sets on device pointers"""
+        if self._L.rp_mlp_forward_windows_bank_sets(self._h, bank._h, idx_ptr, set_size, mfcc_ptr, S, n_frames, MLP_PRECISION[precision], out_ptr,
+                                                    win_pitch) < 0:
+            raise _err()
+
+    def batch_detect_model_bank_sets(self, pcm, bank, stream_models, detector_config, precision="f32", max_det=8):
+        """rp_batch_detect_model_bank_sets: the whole path with stream s holding the set of models stream_models[s] ([S][set_size], -1: an
+        empty slot) -> (det, det_model, det_label, n_det).  det_model: the winner's bank index."""
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        idx = np.ascontiguousarray(stream_models, np.int32)
+        assert idx.ndim == 2 and idx.shape[0] == S
+        det = np.zeros((S, max_det), dtype=DET_DTYPE)
+        dmod = np.zeros((S, max_det), np.int32)
+        dlab = np.zeros((S, max_det), np.int32)
+        n_det = np.zeros(S, np.int32)
+        c = detector_config._c()
+        if self._L.rp_batch_detect_model_bank_sets(self._h, pcm.ctypes.data, fmt, S, N, N, bank._h, idx.ctypes.data, idx.shape[1], C.byref(c),
+                                                   MLP_PRECISION[precision], det.ctypes.data, dmod.ctypes.data, dlab.ctypes.data, n_det.ctypes.data,
+                                                   max_det) < 0:
+            raise _err()
+        return det, dmod, dlab, n_det
+
+    def batch_detect_model_bank_sets_dev(self, pcm_ptr, fmt, S, N, stride, bank, idx_ptr, set_size, detector_config, precision, det_ptr, model_ptr,
+                                         label_ptr, n_det_ptr, max_det):
+        """rp_batch_detect_model_bank_sets on device pointers (tools/bench_model_bank_sets.py)"""
+        c = detector_config._c()
+        if self._L.rp_batch_detect_model_bank_sets(self._h, pcm_ptr, int(fmt), S, N, stride, bank._h, idx_ptr, set_size, C.byref(c),
+                                                   MLP_PRECISION[precision], det_ptr, model_ptr, label_ptr, n_det_ptr, max_det) < 0:
+            raise _err()
 
     def batch_detect_model_dev(self, pcm_ptr, fmt, S, N, stride, model, mfcc_size, none_index, detector_config, precision, det_ptr, label_ptr,
                                n_det_ptr, max_det):

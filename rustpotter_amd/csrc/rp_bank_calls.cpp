@@ -58,6 +58,14 @@ bool stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, 
     return stage_indices(c, sg, bk.dev.W, bk.dev.min_len, [&](size_t w) { return bk.ww[w].max_len; }, "wakeword index", idx, S, set_size, n_frames, bi);
 }
 
+bool model_set_size_ok(int set_size) {
+    if (set_size < 1 || set_size > RP_MODEL_SET_MAX) {
+        set_last_error("set_size " + std::to_string(set_size) + " is outside 1 .. " + std::to_string((int)RP_MODEL_SET_MAX) + " (RP_MODEL_SET_MAX)");
+        return false;
+    }
+    return true;
+}
+
 }  // namespace rp
 
 namespace {
@@ -73,6 +81,28 @@ bool stage_model_indices(Ctx *c, Staged &sg, const ModelBank &bk, const int32_t 
     if (!stage_indices(c, sg, bk.dev.W, bk.min_L, [&](size_t w) { return bk.e[w].L; }, "model index", idx, S, 0, n_frames, &q->idx, &used)) return false;
     for (size_t w = 0; w < bk.e.size(); ++w)
         if (used[w]) model_bank_shape_add(&q->shape, n_frames, bk.e[w].L, bk.e[w].tail_floats);
+    return true;
+}
+
+// The same for rows of set_size indices (model sets): Lmax(s), the longest window of a row's live slots, decides the stream's window count
+// and cut, every live slot's own window the staging -- host arrays: of the rows as they are; device arrays: of every pair the bank allows
+bool stage_model_set_indices(Ctx *c, Staged &sg, const ModelBank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, ModelBankCall *q) {
+    if (!stage_indices(c, sg, bk.dev.W, bk.min_L, [&](size_t w) { return bk.e[w].L; }, "model index", idx, S, set_size, n_frames, &q->idx)) return false;
+    if (sg.host) {
+        for (size_t s = 0; s < S; ++s) {
+            const int32_t *row = idx + s * (size_t)set_size;
+            int lmax = 0;
+            for (int j = 0; j < set_size; ++j) if (row[j] >= 0) lmax = std::max(lmax, bk.e[(size_t)row[j]].L);
+            for (int j = 0; j < set_size; ++j)
+                if (row[j] >= 0) model_set_shape_add(&q->shape, n_frames, lmax, bk.e[(size_t)row[j]].L, bk.e[(size_t)row[j]].tail_floats);
+        }
+        return true;
+    }
+    std::vector<char> is_len(257, 0);   // a bank's windows are at most 256 frames
+    for (const ModelBankEntry &e : bk.e) if (e.L >= 1 && e.L <= 256) is_len[(size_t)e.L] = 1;
+    for (int lmax = 1; lmax <= 256; ++lmax)
+        if (is_len[(size_t)lmax])
+            for (const ModelBankEntry &e : bk.e) model_set_shape_add(&q->shape, n_frames, lmax, e.L, e.tail_floats);
     return true;
 }
 
@@ -155,6 +185,18 @@ bool bank_logits(Ctx *c, const ModelBank &bk, const ModelBankCall &q, const floa
     if (!timed(c, kKernelMlp, "mlp_windows_bank_kernel", [&] { return launch_mlp_windows_bank(c->stream, bk.dev, q.shape, q.idx.dev, dm, S, nf, mean, pitch, dlog); }))
         return false;
     c->last_mlp_kernel = "mlp_windows_bank_kernel<bf16x3 splits>";
+    return true;
+}
+
+// the same over the rows (s, j) of a call over model sets: dlog [S][set_size][pitch][label_pitch], one forward launch
+bool bank_set_logits(Ctx *c, const ModelBank &bk, const ModelBankCall &q, int set_size, const float *dm, size_t S, size_t nf, size_t pitch, float *dlog) {
+    if (!c->ws_gain.reserve(S * (size_t)set_size * pitch * 16 * sizeof(float) + 16)) return false;
+    float *mean = c->ws_gain.as<float>();
+    if (!hip_ok(launch_window_means_model_set(c->stream, bk.dev, q.idx.dev, set_size, dm, S, nf, pitch, mean), "window_means_model_set_kernel")) return false;
+    if (!timed(c, kKernelMlp, "mlp_windows_model_set_kernel", [&] {
+            return launch_mlp_windows_model_set(c->stream, bk.dev, q.shape, q.idx.dev, set_size, dm, S, nf, mean, pitch, dlog); }))
+        return false;
+    c->last_mlp_kernel = "mlp_windows_model_set_kernel<bf16x3 splits>";
     return true;
 }
 
@@ -386,6 +428,82 @@ int rp_batch_detect_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fm
             })) return -1;
         if (dl && !hip_ok(launch_model_bank_labels(c->stream, f.dd, f.dn, dlab, S, pitch, max_det, dl), "model_bank_labels_kernel")) return -1;
         return sg.back_detections(S, max_det, det, f.dd, n_det, f.dn, det_label, dl) && sg.finish() ? 0 : -1;
+    });
+}
+
+int rp_mlp_forward_windows_bank_sets(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_models, int set_size, const float *mfcc, size_t S,
+                                     size_t n_frames, int precision, float *logits, size_t win_pitch) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (!model_set_size_ok(set_size)) return -1;
+        if (S && !stream_models) { set_last_error("null argument"); return -1; }
+        const ModelBank &bk = *bank->impl;
+        Ctx *c = bank_call_ctx(ctx, bk.ctx);
+        if (!c || !bank_precision_ok(precision)) return -1;
+        Staged sg(c);
+        ModelBankCall q;
+        if (!stage_model_set_indices(c, sg, bk, stream_models, S, set_size, n_frames, &q) || !pitch_ok(win_pitch, q.idx.max_n_win, true)) return -1;
+        const size_t out_bytes = S * (size_t)set_size * win_pitch * (size_t)bk.dev.label_pitch * sizeof(float);
+        if (out_bytes == 0) return sg.finish() ? 0 : -1;
+        if (!logits || (n_frames && !mfcc)) { set_last_error("null argument"); return -1; }
+        const float *dm = static_cast<const float *>(sg.in(mfcc, S * n_frames * 16 * sizeof(float), c->stage_in));
+        float *dl = static_cast<float *>(sg.out(logits, out_bytes, c->stage_out));
+        if ((n_frames && !dm) || !dl) return -1;
+        if (!bank_set_logits(c, bk, q, set_size, dm, S, n_frames, win_pitch, dl)) return -1;
+        return sg.back(logits, dl, out_bytes) && sg.finish() ? 0 : -1;
+    });
+}
+
+int rp_batch_detect_model_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                    const rp_model_bank *bank, const int32_t *stream_models, int set_size, const rp_detector_config *config,
+                                    int precision, rp_batch_detection *det, int32_t *det_model, int32_t *det_label, int32_t *n_det, int max_det) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (!model_set_size_ok(set_size)) return -1;
+        if (!config || (S && (!pcm || !stream_models || !det || !n_det))) { set_last_error("null argument"); return -1; }
+        const ModelBank &bk = *bank->impl;
+        Ctx *c = bank_call_ctx(ctx, bk.ctx);
+        if (!c || !bank_precision_ok(precision)) return -1;
+        if (max_det < 0) { set_last_error("max_det must be >= 0"); return -1; }
+        Staged sg(c);
+        const size_t nf = rp_mfcc_num_frames(n_samples);
+        ModelBankCall q;
+        if (!stage_model_set_indices(c, sg, bk, stream_models, S, set_size, nf, &q)) return -1;
+        const size_t col = S * (size_t)max_det * sizeof(int32_t);
+        if (bk.dev.W == 0) return empty_bank_answer(c, sg, fmt, S, n_samples, pcm_stride, det, n_det, max_det, {{det_model, col}, {det_label, col}});
+        DetectFront f;
+        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, 16, std::max(bk.min_L, 1), det, n_det, max_det, &f)) return -1;
+        // the two int32 columns: the caller's arrays on the device, else the halves of one staging buffer
+        int32_t *dw = det_model, *dl = det_label;
+        if (sg.host && col && (det_model || det_label)) {
+            if (!c->stage_out3.reserve(2 * col)) return -1;
+            if (det_model) dw = c->stage_out3.as<int32_t>();
+            if (det_label) dl = c->stage_out3.as<int32_t>() + S * (size_t)max_det;
+        }
+        const size_t pitch = std::max<size_t>(q.idx.max_n_win, 1), rows = S * pitch;
+        if (!c->ws_ring.reserve(rows * (size_t)set_size * (size_t)bk.dev.label_pitch * sizeof(float) + 16) || !c->ws_agg.reserve(rows * sizeof(float) + 16) ||
+            !c->ws_avg.reserve(rows * sizeof(float) + 16) || !c->ws_set_ww.reserve(rows * sizeof(int32_t) + 16) ||
+            !c->ws_rms.reserve(rows * sizeof(int32_t) + 16)) return -1;
+        float *dlog = c->ws_ring.as<float>(), *best = c->ws_agg.as<float>(), *best_avg = c->ws_avg.as<float>();
+        int32_t *best_ww = c->ws_set_ww.as<int32_t>(), *best_label = c->ws_rms.as<int32_t>();
+        uint32_t *hot = nullptr;
+        if (S) {
+            if (!bank_set_logits(c, bk, q, set_size, f.dm, S, nf, pitch, dlog)) return -1;
+            // nn_score_model_set_kernel raises a flag per stream with a proposal: the scan skips the others and puts the flags back
+            hot = c->hot_flags(S);
+            if (!hot) return -1;
+            if (!hip_ok(launch_nn_score_model_set(c->stream, bk.dev, q.idx.dev, set_size, dlog, S, nf, pitch, config->score_ref * 10.f,
+                                                  config->avg_threshold != 0.f ? 1 : 0, config->threshold, config->avg_threshold, best, best_avg, best_ww,
+                                                  best_label, hot), "nn_score_model_set_kernel")) return -1;
+        }
+        // Lmax(s) (countdown Lmax(s) / 2) from the bank's scan entries; the gates were applied above
+        const ScanConfig sc = scan_config(*config, 0, true);
+        if (!detect_scan(c, *config, f.dm, S, nf, 16, "scan_model_set_kernel", [&](const float *dv, float vm) {
+                return launch_scan_model_set(c->stream, bk.scan, q.idx.dev, set_size, best, best_avg, best_ww, best_label, pitch, dv, vm, S, nf, sc, f.dd, dw, dl,
+                                             f.dn, max_det, hot);
+            })) return -1;
+        if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
+        return sg.back(det_model, dw, col) && sg.back(det_label, dl, col) && sg.finish() ? 0 : -1;
     });
 }
 

@@ -106,6 +106,7 @@ template <class F> bool detect_scan(Ctx *c, const rp_detector_config &cfg, const
 bool bank_band_ok(const Bank &bk, int band_size);
 bool set_size_ok(int set_size);   // within 1 .. RP_WAKEWORD_SET_MAX
 // rp_bank_calls.cpp
+bool model_set_size_ok(int set_size);   // within 1 .. RP_MODEL_SET_MAX
 // after the null-handle test of a call over a bank: the bank's owner must be the call's context, whose device becomes current; null with the error set
 inline Ctx *bank_call_ctx(rp_ctx *ctx, const Ctx *owner) {
     Ctx *c = ctx->impl.get();

@@ -873,4 +873,43 @@ hipError_t launch_mlp_bank_stream(hipStream_t st, const ModelBankDev &b, int max
 hipError_t launch_nn_score_bank_stream(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *logits, size_t S, size_t n_new,
                                        float score_ref10, int calc_avg, float threshold, float avg_threshold, float *agg, float *avg, int32_t *label);
 
+// ---- model sets (rp_mlp_model_set.hip, rp_scan_model_set.hip): stream s holds up to kScanMaxWakewords models of a model bank, sets
+// [S][set_size] (outside [0, W): an empty slot) -- a `Rustpotter` with several add_wakeword calls of models.  Its window is Lmax(s) frames, the
+// longest train_size of its live slots; slot j scores the oldest L_j frames of it.
+// Whole recordings: stream s has n_win_s = n_frames - Lmax(s) + 1 windows.  The launch shape of the models a call uses: one
+// model_set_shape_add per (Lmax of a stream, a model of its set).
+void model_set_shape_add(ModelBankShape *sh, size_t n_frames, int lmax, int L, int tail_floats);
+// mean [S][set_size][win_pitch][16]: row (s, j, w) is the mean of the L_j frames from frame w of stream s
+hipError_t launch_window_means_model_set(hipStream_t st, const ModelBankDev &b, const int32_t *sets, int set_size, const float *mfcc, size_t S,
+                                         size_t n_frames, size_t win_pitch, float *mean);
+// logits [S][set_size][win_pitch][label_pitch], zeroed here: row (s, j, w) gets the labels of model sets[s][j] for w < n_win_s
+hipError_t launch_mlp_windows_model_set(hipStream_t st, const ModelBankDev &b, const ModelBankShape &sh, const int32_t *sets, int set_size,
+                                        const float *mfcc, size_t S, size_t n_frames, const float *mean, size_t win_pitch, float *logits);
+// the proposal of every window, [S][win_pitch] each: the best passing score over the live slots (-2: nobody proposes; the first slot of
+// equals wins), its average score, the winner's bank index (-1) and label (-1).  hot [S] (optional) as in launch_nn_score_bank.
+hipError_t launch_nn_score_model_set(hipStream_t st, const ModelBankDev &b, const int32_t *sets, int set_size, const float *logits, size_t S,
+                                     size_t n_frames, size_t win_pitch, float score_ref10, int calc_avg, float threshold, float avg_threshold,
+                                     float *best, float *best_avg, int32_t *best_ww, int32_t *best_label, uint32_t *hot);
+// the state machine over those rows; b: ModelBank::scan.  det_ww / det_label (optional): each detection's bank index and label
+hipError_t launch_scan_model_set(hipStream_t st, const BankDev &b, const int32_t *stream_models, int set_size, const float *best,
+                                 const float *best_avg, const int32_t *best_ww, const int32_t *best_label, size_t win_pitch, const float *vad_value,
+                                 float vad_mode_value, size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det, int32_t *det_ww,
+                                 int32_t *det_label, int32_t *n_det, int max_det, uint32_t *hot);
+// Live: frames, cap, fill, n_new and max_L as for launch_mlp_bank_stream; the window of stream s that ends at new frame i starts Lmax(s) - 1
+// frames before it for every slot.  mean [S][set_size][n_new][16], logits [S][set_size][n_new][label_pitch] (every row written).
+hipError_t launch_window_means_set_stream(hipStream_t st, const ModelBankDev &b, int max_L, const int32_t *sets, int set_size, const float *frames,
+                                          size_t S, size_t cap, size_t fill, size_t n_new, float *mean);
+hipError_t launch_mlp_set_stream(hipStream_t st, const ModelBankDev &b, int max_L, const int32_t *sets, int set_size, const float *frames, size_t S,
+                                 size_t cap, size_t fill, size_t n_new, const float *mean, float *logits);
+// agg / avg / label [S][set_size][n_new] slot by slot; an empty slot: -2, 0, -1
+hipError_t launch_nn_score_set_stream(hipStream_t st, const ModelBankDev &b, const int32_t *sets, int set_size, const float *logits, size_t S,
+                                      size_t n_new, float score_ref10, int calc_avg, float threshold, float avg_threshold, float *agg, float *avg,
+                                      int32_t *label);
+// per frame the best proposal of the stream's slots over those rows (b: ModelBank::scan); det_ww: the winner's bank index, det_label: the
+// label of the detection's best window
+hipError_t launch_scan_model_set_stream(hipStream_t st, const BankDev &b, const int32_t *stream_models, int set_size, const float *agg,
+                                        const float *avg, const int32_t *label, const float *vad_value, float vad_mode_value, size_t S, long long f0,
+                                        int n_new, const ScanConfig &cfg, void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label,
+                                        int32_t *n_det, int max_det);
+
 }  // namespace rp

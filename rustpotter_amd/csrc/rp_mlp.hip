@@ -59,47 +59,7 @@ hipError_t launch_normalize_windows(hipStream_t st, const float *mfcc, size_t fi
     return launch_normalize_windows_batch(st, mfcc, 0, first_win + n_win, first_win, n_win, L, K, x);
 }
 
-// calc_inverse_similarity, wakeword_nn.rs:161-163
-__device__ __forceinline__ float nn_inverse_similarity(float n1, float n2, float reference) {
-    return 1.f - (1.f / (1.f + expf(((n1 - n2) - reference) / reference)));
-}
-
-// the integer f32::total_cmp orders by: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN
-__device__ __forceinline__ int nn_total_cmp_key(float x) {
-    const int b = __float_as_int(x);
-    return b ^ (int)((unsigned)(b >> 31) >> 1);
-}
-
-// get_label (:47-60: max_by(total_cmp) keeps the LAST maximum), run_detection_by_label (:61-99: second_prob is the
-// smallest other logit), validate_scores (:113-123)
-// one window's logits lg [nl] -> its label, score (-2: no valid detection) and avg score
-// A NaN logit is ordered as total_cmp orders it: a positive NaN is the maximum and stays the label, its scores are NaN and fail both
-// gates (>= is false), so the window never passes -- unless that label is the none label, which is no detection either; a negative NaN is
-// the smallest value.  second_prob leaves out only what == the label's value (nothing, when that is NaN) and is the total_cmp minimum
-// of the rest.  The rp_detector.cpp loop and the oracle's follow the same rule.
-__device__ __forceinline__ void nn_score_row(const float *__restrict__ lg, int nl, int none_index, float ref, int calc_avg, float threshold,
-                                             float avg_threshold, float *score_out, float *avg_out, int *label_out) {
-    int bi = 0;
-    for (int i = 1; i < nl; ++i) if (!(nn_total_cmp_key(lg[i]) < nn_total_cmp_key(lg[bi]))) bi = i;
-    float score = -2.f, av = 0.f;
-    if (bi != none_index) {
-        const float label_prob = lg[bi], none_prob = none_index >= 0 ? lg[none_index] : 0.f;
-        float second = 0.f;
-        if (calc_avg) {
-            bool any = false;
-            for (int i = 0; i < nl; ++i) {
-                if (lg[i] == label_prob) continue;
-                if (!any || !(nn_total_cmp_key(lg[i]) > nn_total_cmp_key(second))) { second = lg[i]; any = true; }
-            }
-            if (!any) second = 0.f;
-            av = nn_inverse_similarity(label_prob, second, ref);
-        }
-        const float sc = nn_inverse_similarity(label_prob, none_prob, ref);
-        if (sc >= threshold && av >= avg_threshold) score = sc;
-    }
-    *score_out = score; *avg_out = av; *label_out = bi;
-}
-
+// (nn_score_row, a window's label, score and average score, is in rp_mlp_dev.h: rp_mlp_model_set.hip shares it)
 __global__ __launch_bounds__(256) void nn_score_kernel(const float *__restrict__ logits, size_t n_rows, int nl, int none_index,
                                                        float ref, int calc_avg, float threshold, float avg_threshold,
                                                        float *__restrict__ agg, float *__restrict__ avg, int32_t *__restrict__ label,

@@ -95,6 +95,16 @@ __device__ __forceinline__ BankLane bank_lane(const BankDev &b, int wi, const Sc
     return r;
 }
 
+// on_wakeword_change, src/detector.rs:328-334: the window of a detector is as long as its longest wakeword; 0: no live slot
+__device__ __forceinline__ int set_max_len(const BankDev &b, const int32_t *__restrict__ set, int set_size) {
+    int lmax = 0;
+    for (int j = 0; j < set_size; ++j) {
+        const int wi = set[j];
+        if (wi >= 0 && wi < b.W) lmax = max(lmax, b.ww[wi].max_len);
+    }
+    return lmax;
+}
+
 // ------------------------------------------------------------------------- the state machine
 // The partial-detection / countdown state machine of src/detector.rs:377-454 with reset() of :290-302 for one lane, over the frames
 // f0 .. f0+n-1 (i = 0 .. n-1; vv[i] is frame f0+i's VAD value, vwin[.][lane] the lane's VadDetector::window).  propose(f, i) is what the

@@ -6,15 +6,7 @@
 
 namespace rp {
 
-// on_wakeword_change, src/detector.rs:328-334: the window of a detector is as long as its longest wakeword; 0: no live slot
-__device__ __forceinline__ int set_max_len(const BankDev &b, const int32_t *__restrict__ set, int set_size) {
-    int lmax = 0;
-    for (int j = 0; j < set_size; ++j) {
-        const int wi = set[j];
-        if (wi >= 0 && wi < b.W) lmax = max(lmax, b.ww[wi].max_len);
-    }
-    return lmax;
-}
+// (set_max_len, the window of a stream that holds a set, is in rp_scan.h: rp_scan_model_set.hip shares it)
 
 // scan_bank_kernel for sets: the window length (and the countdown, Lmax(s) / 2) comes from the stream's set, the proposal of a window from
 // the three rows dtw_set_kernel folded -- best_ww < 0: nobody proposes.  A stream without a live slot, or with fewer frames than its window,

@@ -1,5 +1,5 @@
 // rp_stream_batch.cpp -- live-stream batches (rp_stream_batch_*): S streams fed a few chunks per call, every stream's state on the device.
-// A batch holds shared wakewords (references and / or models), or every stream its own: of a wakeword bank, or of a model bank.
+// A batch holds shared wakewords (references and / or models), or every stream its own: of a wakeword bank, or of a model bank -- one, or a set.
 #include <cmath>
 #include <cstring>
 
@@ -41,6 +41,8 @@ struct rp_stream_batch {
     int label_pitch = 0;
     DevBuf bank_label;
     size_t logit_frames = 0;
+    // made by rp_stream_batch_new_model_bank_sets (mbank with set_size 1..8): stream s holds the set of models bank_idx[s][0 .. set_size), -1 an
+    // empty slot; bank_agg / bank_avg / bank_label and `logits` are then per slot, [S][set_size][frames per call]([label_pitch])
     size_t slots() const { return set_size ? (size_t)set_size : 1; }
     int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
     DevBuf det_ww, det_label, logits, mean, xrows, xs2;
@@ -100,9 +102,10 @@ static bool stream_batch_alloc(rp_stream_batch *b) {
             (w->m && !w->label.reserve(rows * sizeof(int32_t) + 16)))
             return false;
     if (b->bank && (!b->bank_agg.reserve(rows * b->slots() * sizeof(float) + 16) || !b->bank_avg.reserve(rows * b->slots() * sizeof(float) + 16))) return false;
-    if (b->mbank && (!b->bank_agg.reserve(rows * sizeof(float) + 16) || !b->bank_avg.reserve(rows * sizeof(float) + 16) ||
-                     !b->bank_label.reserve(rows * sizeof(int32_t) + 16) || !b->mean.reserve(rows * 16 * sizeof(float) + 16) ||
-                     !b->logits.reserve(rows * (size_t)b->label_pitch * sizeof(float) + 16))) return false;
+    const size_t mrows = rows * b->slots();   // a batch over model sets: a row per slot
+    if (b->mbank && (!b->bank_agg.reserve(mrows * sizeof(float) + 16) || !b->bank_avg.reserve(mrows * sizeof(float) + 16) ||
+                     !b->bank_label.reserve(mrows * sizeof(int32_t) + 16) || !b->mean.reserve(mrows * 16 * sizeof(float) + 16) ||
+                     !b->logits.reserve(mrows * (size_t)b->label_pitch * sizeof(float) + 16))) return false;
     if (!b->pcm[0].reserve(pcm_bytes) || !b->pcm[1].reserve(pcm_bytes) || !b->mfcc[0].reserve(S * pitch * K * sizeof(float) + slack) ||
         !b->mfcc[1].reserve(S * pitch * K * sizeof(float) + slack) || !b->state.reserve(S * stream_state_bytes()) ||
         !b->scores.reserve(rows * (size_t)b->Tmax * sizeof(float) + 16) || !b->vad.reserve(rows * sizeof(float) + 16) ||
@@ -333,6 +336,12 @@ static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, con
     if (b->mbank) {
         // window length (countdown L / 2) per stream from the bank's scan entries; their thresholds are -1: nn_score_bank_stream_kernel applied the gates
         const ScanConfig sc = scan_config(b->cfg, 0, true, (int)b->fpf());
+        if (b->set_size)   // Lmax(s) from the scan entries of the stream's set; per frame the best proposal of its slots
+            return timed(c, kKernelScan, "scan_model_set_stream_kernel", [&] {
+                return launch_scan_model_set_stream(c->stream, b->mbank->scan, b->bank_idx.as<int32_t>(), b->set_size, b->bank_agg.as<float>(),
+                                                    b->bank_avg.as<float>(), b->bank_label.as<int32_t>(), dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl,
+                                                    dn, max_det);
+            });
         return timed(c, kKernelScan, "scan_bank_stream_kernel", [&] {
             return launch_scan_bank_stream(c->stream, b->mbank->scan, b->bank_idx.as<int32_t>(), b->bank_agg.as<float>(), b->bank_avg.as<float>(), dv, vm,
                                            b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn, max_det, b->bank_label.as<int32_t>());
@@ -388,10 +397,19 @@ static bool score_model_bank_stream(rp_stream_batch *b, const NewFrames &f, size
     b->logit_frames = n_new;
     // no model yet (a reserved empty bank): rp_stream_batch_logits answers zero rows
     if (bk.dev.W == 0)
-        return !b->label_pitch || hip_ok(hipMemsetAsync(b->logits.p, 0, b->S * n_new * (size_t)b->label_pitch * sizeof(float), c->stream), "hipMemsetAsync");
+        return !b->label_pitch || hip_ok(hipMemsetAsync(b->logits.p, 0, b->S * b->slots() * n_new * (size_t)b->label_pitch * sizeof(float), c->stream), "hipMemsetAsync");
     if (bk.dev.label_pitch != b->label_pitch || bk.max_L > b->max_len) { set_last_error("stream batch: the model bank outgrew what the batch was sized for"); return false; }
     const int32_t *idx = b->bank_idx.as<int32_t>();
     float *mean = b->mean.as<float>(), *dlog = b->logits.as<float>();
+    if (b->set_size) {   // every slot of every stream's set is a row; Lmax(s) is read from the bank in this call
+        if (!hip_ok(launch_window_means_set_stream(c->stream, bk.dev, bk.max_L, idx, b->set_size, f.rows, b->S, b->cap, f.fill, n_new, mean),
+                    "window_means_set_stream_kernel")) return false;
+        if (!timed(c, kKernelMlp, "mlp_set_stream_kernel", [&] {
+                return launch_mlp_set_stream(c->stream, bk.dev, bk.max_L, idx, b->set_size, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); })) return false;
+        return hip_ok(launch_nn_score_set_stream(c->stream, bk.dev, idx, b->set_size, dlog, b->S, n_new, b->cfg.score_ref * 10.f,
+                                                 b->cfg.avg_threshold != 0.f ? 1 : 0, b->cfg.threshold, b->cfg.avg_threshold, b->bank_agg.as<float>(),
+                                                 b->bank_avg.as<float>(), b->bank_label.as<int32_t>()), "nn_score_set_stream_kernel");
+    }
     if (!hip_ok(launch_window_means_bank_stream(c->stream, bk.dev, bk.max_L, idx, f.rows, b->S, b->cap, f.fill, n_new, mean), "window_means_bank_stream_kernel"))
         return false;
     if (!timed(c, kKernelMlp, "mlp_bank_stream_kernel", [&] {
@@ -524,19 +542,23 @@ int rp_stream_batch_new_bank_sets(rp_ctx *ctx, const rp_wakeword_bank *bank, con
 }
 // live-stream batches in which stream s runs its own model bank[stream_model[s]] (personal wakeword models; rp_batch_detect_model_bank with
 // the state carried between calls).  Thresholds are the config's, mfcc_size is 16, the arithmetic RP_MLP_F32.
-int rp_stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, size_t S,
-                                   size_t max_chunks_per_call, rp_stream_batch **out) {
+// Both constructors over a model bank; sets: rp_stream_batch_new_model_bank_sets, rows of set_size indices per stream (else one index)
+static int stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, bool sets, int set_size,
+                                       const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
     return guarded([&]() -> int {
+        const std::string name = sets ? "rp_stream_batch_new_model_bank_sets" : "rp_stream_batch_new_model_bank";
         if (!ctx || !bank) { set_last_error("null handle"); return -1; }
         if (!config || !out || !stream_model) { set_last_error("null argument"); return -1; }
         *out = nullptr;
+        if (sets && !model_set_size_ok(set_size)) return -1;
         const ModelBank &bk = *bank->impl;
         Ctx *c = bank_call_ctx(ctx, bk.ctx);
         if (!c) return -1;
-        if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new_model_bank: S and max_chunks_per_call must be >= 1"); return -1; }
+        if (S == 0 || max_chunks_per_call == 0) { set_last_error(name + ": S and max_chunks_per_call must be >= 1"); return -1; }
         // before anything is allocated
-        if ((c->flags & RP_CTX_HOST_POINTERS) && !bank_indices_ok(bk.dev.W, 0, S, 0, stream_model, "model index")) return -1;
+        if ((c->flags & RP_CTX_HOST_POINTERS) && !bank_indices_ok(bk.dev.W, 0, S, sets ? set_size : 0, stream_model, "model index")) return -1;
         std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
+        b->set_size = sets ? set_size : 0;
         b->c = c; b->mbank = &bk; ++bk.live_batches; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
         b->K = 16; b->max_len = bk.max_window(); b->label_pitch = bk.dev.label_pitch; b->Tmax = 1;
         if (!bank_indices_put(b.get(), 0, S, stream_model)) return -1;
@@ -546,6 +568,15 @@ int rp_stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const
         *out = b.release();
         return 0;
     });
+}
+int rp_stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, size_t S,
+                                   size_t max_chunks_per_call, rp_stream_batch **out) {
+    return stream_batch_new_model_bank(ctx, bank, stream_model, false, 0, config, S, max_chunks_per_call, out);
+}
+// ... in which stream s holds the SET of models bank[stream_models[s][0 .. set_size)] (rp_batch_detect_model_bank_sets with the state carried)
+int rp_stream_batch_new_model_bank_sets(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_models, int set_size,
+                                        const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
+    return stream_batch_new_model_bank(ctx, bank, stream_models, true, set_size, config, S, max_chunks_per_call, out);
 }
 void rp_stream_batch_free(rp_stream_batch *b) { delete b; }
 size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b) { return b ? b->chunks_seen : 0; }
@@ -675,7 +706,8 @@ static int stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, s
         if (!c) return -1;
         if (b->mbank) {
             set_last_error(std::string(sets ? "rp_stream_batch_set_wakeword_sets" : "rp_stream_batch_set_wakewords") +
-                           ": the batch runs over a model bank (rp_stream_batch_new_model_bank), whose streams are re-targeted with rp_stream_batch_set_models");
+                           (b->set_size ? ": the batch runs over model sets (rp_stream_batch_new_model_bank_sets), whose streams are re-targeted with rp_stream_batch_set_model_sets"
+                                        : ": the batch runs over a model bank (rp_stream_batch_new_model_bank), whose streams are re-targeted with rp_stream_batch_set_models"));
             return -1;
         }
         if (sets && !b->set_size) { set_last_error("rp_stream_batch_set_wakeword_sets: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
@@ -707,21 +739,25 @@ int rp_stream_batch_set_wakeword_sets(rp_stream_batch *b, size_t first_stream, s
 }
 
 // connect / disconnect / retarget slots of a batch over a model bank: as rp_stream_batch_set_wakewords, each touched stream reset
-int rp_stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *models) {
+// Both re-targeting calls; sets: rp_stream_batch_set_model_sets, rows of set_size indices -- remove-all plus add-in-order
+static int stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *models, bool sets) {
     bool touched = false;
     const int r = guarded([&]() -> int {
+        const std::string name = sets ? "rp_stream_batch_set_model_sets" : "rp_stream_batch_set_models";
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
-        if (!b->mbank) { set_last_error("rp_stream_batch_set_models: the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
+        if (sets && !(b->mbank && b->set_size)) { set_last_error(name + ": the batch was not made by rp_stream_batch_new_model_bank_sets"); return -1; }
+        if (!b->mbank) { set_last_error(name + ": the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
+        if (!sets && b->set_size) { set_last_error(name + ": the batch holds model sets (rp_stream_batch_new_model_bank_sets); use rp_stream_batch_set_model_sets"); return -1; }
         if (first_stream > b->S || n > b->S - first_stream) {
-            set_last_error("rp_stream_batch_set_models: streams " + std::to_string(first_stream) + " .. " + std::to_string(first_stream) + " + " +
+            set_last_error(name + ": streams " + std::to_string(first_stream) + " .. " + std::to_string(first_stream) + " + " +
                            std::to_string(n) + " reach past the batch's " + std::to_string(b->S) + " streams");
             return -1;
         }
         if (n == 0) return 0;
         if (!models) { set_last_error("null argument"); return -1; }
         // a refused index leaves the batch as it was
-        if ((c->flags & RP_CTX_HOST_POINTERS) && !bank_indices_ok(b->mbank->dev.W, first_stream, n, 0, models, "model index")) return -1;
+        if ((c->flags & RP_CTX_HOST_POINTERS) && !bank_indices_ok(b->mbank->dev.W, first_stream, n, b->set_size, models, "model index")) return -1;
         touched = true;
         if (!bank_indices_put(b, first_stream, n, models)) return -1;
         return hip_ok(launch_stream_state_reset_range(c->stream, b->state.p, b->S, first_stream, n, (long long)b->fpf() * (long long)b->chunks_seen),
@@ -730,15 +766,22 @@ int rp_stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size_t n
     if (r != 0 && touched) b->poisoned = true;
     return r;
 }
+int rp_stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *models) {
+    return stream_batch_set_models(b, first_stream, n, models, false);
+}
+int rp_stream_batch_set_model_sets(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *stream_models) {
+    return stream_batch_set_models(b, first_stream, n, stream_models, true);
+}
 
-// the logits of the last process call of a batch over a model bank, [S][frames of that call][rp_model_bank_labels(bank, -1)]
+// the logits of the last process call of a batch over a model bank, [S][frames of that call][rp_model_bank_labels(bank, -1)]; a batch over
+// model sets: [S][set_size][frames of that call][..]
 int rp_stream_batch_logits(rp_stream_batch *b, float *logits) {
     return guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
         if (!b->mbank) { set_last_error("rp_stream_batch_logits: the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
         if (!b->logit_frames) { set_last_error("rp_stream_batch_logits: the streams have not received audio yet"); return -1; }
-        const size_t bytes = b->S * b->logit_frames * (size_t)b->label_pitch * sizeof(float);
+        const size_t bytes = b->S * b->slots() * b->logit_frames * (size_t)b->label_pitch * sizeof(float);
         if (bytes == 0) return 0;   // an empty bank has no labels
         if (!logits) { set_last_error("null argument"); return -1; }
         const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
@@ -751,6 +794,7 @@ int rp_stream_batch_slot_scores(rp_stream_batch *b, float *agg, float *avg) {
     return guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (b->mbank && b->set_size) { set_last_error("rp_stream_batch_slot_scores: a batch over model sets keeps no aggregate per slot; rp_stream_batch_logits returns its per-slot, per-window output"); return -1; }
         if (b->mbank) { set_last_error("rp_stream_batch_slot_scores: a batch over a model bank has one model per stream and no slots; rp_stream_batch_logits returns its per-window output"); return -1; }
         if (!b->set_size) { set_last_error("rp_stream_batch_slot_scores: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
         if (!b->slot_frames) { set_last_error("rp_stream_batch_slot_scores: the streams have not received audio yet"); return -1; }
