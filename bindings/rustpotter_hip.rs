@@ -311,6 +311,15 @@ extern "C" {
                                test_accuracy: *mut f32) -> c_int;
     pub fn rp_model_bank_read_image(bank: *const rp_model_bank, model: i64, out: *mut c_void, cap: usize, need: *mut usize) -> c_int;
     pub fn rp_model_bank_last_put_ms(bank: *const rp_model_bank) -> f64;
+    pub fn rp_model_bank_set_rms_levels(bank: *mut rp_model_bank, rms_levels: *const f32) -> c_int;
+    pub fn rp_model_bank_rms_level(bank: *const rp_model_bank, model: i64) -> f32;
+    pub fn rp_frontend_batch_bank_sets(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                       filters: *const rp_filters_config, bank: *const rp_wakeword_bank, stream_wakewords: *const i32,
+                                       set_size: c_int, pcm_out: *mut f32, out_stride: usize, rms: *mut f32, gains: *mut f32) -> c_int;
+    pub fn rp_frontend_batch_model_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                        filters: *const rp_filters_config, bank: *const rp_model_bank, stream_models: *const i32,
+                                        set_size: c_int, pcm_out: *mut f32, out_stride: usize, rms: *mut f32, gains: *mut f32) -> c_int;
+    pub fn rp_stream_batch_set_filters_per_stream(b: *mut rp_stream_batch, filters: *const rp_filters_config) -> c_int;
     pub fn rp_mlp_forward_windows_bank(ctx: *mut rp_ctx, bank: *const rp_model_bank, stream_model: *const i32, mfcc: *const f32, S: usize,
                                        n_frames: usize, precision: c_int, logits: *mut f32, win_pitch: usize) -> c_int;
     pub fn rp_batch_detect_model_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
@@ -503,6 +512,13 @@ impl ModelBank {
     pub fn pool_growths(&self) -> usize { unsafe { rp_model_bank_pool_growths(self.h) }.max(0) as usize }
     /// the put kernel's own time in the last put, in milliseconds (0 unless the context times its kernels)
     pub fn last_put_ms(&self) -> f64 { unsafe { rp_model_bank_last_put_ms(self.h) } }
+    /// `WakewordModel::rms_level` of one model (NaN: none): what the gain normaliser of a stream that holds it works towards
+    pub fn rms_level(&self, model: usize) -> f32 { unsafe { rp_model_bank_rms_level(self.h, model as i64) } }
+    /// One level per model (NaN: none), in force from the next call that uses the bank
+    pub fn set_rms_levels(&self, rms_levels: &[f32]) -> Result<(), String> {
+        assert!(rms_levels.len() == self.size());
+        status(unsafe { rp_model_bank_set_rms_levels(self.h, rms_levels.as_ptr()) })
+    }
     // The calls below change the bank through `&self`: a `StreamBatch` borrows its bank for life, and changing the bank under a live batch
     // is what they are for.  The library orders every update on the context's stream and returns when it is complete.
     /// Declares the largest window and label count the bank will ever hold (what a live batch over it keeps room for; 0: leave) and
@@ -1042,6 +1058,39 @@ impl HipContext {
         })?;
         Ok((out, rms, gains))
     }
+    /// `frontend_batch_bank` in front of `batch_detect_bank_sets`: stream `s` holds `stream_wakewords[s * set_size ..][..set_size]` (-1: an
+    /// empty slot) and works towards the largest non-NaN `rms_level` of its live slots over `max(Lmax(s) / 3, 1)` chunk levels
+    pub fn frontend_batch_bank_sets(&self, pcm: &[f32], n_samples: usize, filters: &FiltersConfig, bank: &WakewordBank, stream_wakewords: &[i32],
+                                    set_size: usize) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>), String> {
+        assert!(set_size >= 1 && stream_wakewords.len() % set_size == 0);
+        let n_streams = stream_wakewords.len() / set_size;
+        assert!(pcm.len() >= n_streams * n_samples);
+        let f: rp_filters_config = filters.into();
+        let nch = n_samples / 480;
+        let (mut out, mut rms, mut gains) = (vec![0f32; n_streams * n_samples], vec![0f32; n_streams * nch], vec![0f32; n_streams * nch]);
+        status(unsafe {
+            rp_frontend_batch_bank_sets(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, &f, bank.h,
+                                        stream_wakewords.as_ptr(), set_size as c_int, out.as_mut_ptr(), n_samples, rms.as_mut_ptr(),
+                                        gains.as_mut_ptr())
+        })?;
+        Ok((out, rms, gains))
+    }
+    /// ... over a model bank, in front of `batch_detect_model_bank` (`set_size` 1) and `batch_detect_model_bank_sets`
+    pub fn frontend_batch_model_bank(&self, pcm: &[f32], n_samples: usize, filters: &FiltersConfig, bank: &ModelBank, stream_models: &[i32],
+                                     set_size: usize) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>), String> {
+        assert!(set_size >= 1 && stream_models.len() % set_size == 0);
+        let n_streams = stream_models.len() / set_size;
+        assert!(pcm.len() >= n_streams * n_samples);
+        let f: rp_filters_config = filters.into();
+        let nch = n_samples / 480;
+        let (mut out, mut rms, mut gains) = (vec![0f32; n_streams * n_samples], vec![0f32; n_streams * nch], vec![0f32; n_streams * nch]);
+        status(unsafe {
+            rp_frontend_batch_model_bank(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, &f, bank.h,
+                                         stream_models.as_ptr(), set_size as c_int, out.as_mut_ptr(), n_samples, rms.as_mut_ptr(),
+                                         gains.as_mut_ptr())
+        })?;
+        Ok((out, rms, gains))
+    }
     /// `AudioEncoder::reencode_to_mono_with_sample_rate` (src/audio/encoder.rs:41-60) for whole streams: f32 input at `sample_rate`
     /// with `channels` interleaved channels -> 16 kHz mono.
     pub fn resample_batch(&self, pcm: &[f32], channels: u16, sample_rate: usize, n_streams: usize, n_samples: usize) -> Result<Vec<f32>, String> {
@@ -1128,6 +1177,13 @@ impl<'a> StreamBatch<'a> {
     pub fn set_filters_bank(&mut self, filters: &FiltersConfig) -> Result<(), String> {
         let f: rp_filters_config = filters.into();
         status(unsafe { rp_stream_batch_set_filters_bank(self.h, &f) })
+    }
+    /// `set_filters` for every batch over a bank (wakeword sets, a model bank, model sets; on a batch of `new_bank` the bits of
+    /// `set_filters_bank`): stream `s` works towards the largest non-NaN `rms_level` of the entries it holds over a window of
+    /// `max(Lmax(s) / 3, 1)` chunk levels (on_wakeword_change, src/detector.rs:328-338); before the first audio
+    pub fn set_filters_per_stream(&mut self, filters: &FiltersConfig) -> Result<(), String> {
+        let f: rp_filters_config = filters.into();
+        status(unsafe { rp_stream_batch_set_filters_per_stream(self.h, &f) })
     }
     /// Wakeword sets on live streams: stream `s` holds `stream_wakewords[s * set_size ..][..set_size]` (-1: an empty slot) --
     /// `batch_detect_bank_sets` with the state carried between calls.  `process_multi` reports the winner's bank index.

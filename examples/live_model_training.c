@@ -2,8 +2,11 @@
  * model, two users train theirs while the batch runs, their slots are connected, and the next audio runs through the new models -- no stream
  * loses its state and no parameter leaves the device (add_wakeword on a running Rustpotter, src/detector.rs:304-346, for a batch of users).
  *   rp_model_bank_new(0 models) -> rp_model_bank_reserve(the largest window and label count ever) -> rp_stream_batch_new_model_bank(every
- *   slot -1) -> rp_stream_batch_process ... -> rp_model_bank_train(the users' recordings) -> rp_stream_batch_set_models(their slots)
- *   -> rp_stream_batch_process ...
+ *   slot -1) -> rp_stream_batch_set_filters_per_stream(gain normaliser on) -> rp_stream_batch_process ... -> rp_model_bank_train(the users'
+ *   recordings) -> rp_stream_batch_set_models(their slots) -> rp_stream_batch_process ...
+ * The gain normaliser of a slot works towards the level its user's model was trained at (WakewordModel::rms_level, which the training leaves
+ * in the bank) over a window of train_size / 3 chunk levels: both are read from the bank at the start of every call, so a slot connected
+ * to a model trained a moment ago is normalised to that model's level from its next chunk on; a slot without a model has gain 1.
  *
  *   gcc -std=c99 -Iinclude examples/live_model_training.c -Lrustpotter_amd -lrustpotter_hip -Wl,-rpath,$PWD/rustpotter_amd -o live_model_training
  *   ./live_model_training tests/golden
@@ -46,17 +49,19 @@ static int feed(rp_stream_batch *batch, const int16_t *speech, size_t chunks, in
     static int16_t part[SLOTS * CALL_CHUNKS * CHUNK];
     rp_batch_detection det[SLOTS * MAX_DET];
     int32_t n_det[SLOTS], model[SLOTS * MAX_DET], label[SLOTS * MAX_DET];
+    float gains[SLOTS * CALL_CHUNKS];
     for (size_t c = 0; c < chunks; c += CALL_CHUNKS) {
         const size_t n = chunks - c < CALL_CHUNKS ? chunks - c : CALL_CHUNKS;
         memset(part, 0, sizeof(part));
         for (int u = 0; speech && u < USERS; ++u)
             memcpy(part + (size_t)(FIRST_USER_SLOT + u) * n * CHUNK, speech + c * CHUNK, n * CHUNK * sizeof(int16_t));
-        if (rp_stream_batch_process_multi(batch, part, RP_SAMPLE_I16, n, n * CHUNK, det, model, label, n_det, MAX_DET) < 0) return -1;
+        if (rp_stream_batch_process_multi(batch, part, RP_SAMPLE_I16, n, n * CHUNK, det, model, label, n_det, MAX_DET) < 0 ||
+            rp_stream_batch_levels(batch, NULL, gains) < 0) return -1;
         for (int s = 0; s < SLOTS; ++s)
             for (int i = 0; i < n_det[s] && i < MAX_DET; ++i) {
                 const rp_batch_detection *d = &det[s * MAX_DET + i];
-                printf("slot %d: detection at chunk %d by model %d, label %d, score %.7f\n", s, (int)d->frame / 3 + 1, (int)model[s * MAX_DET + i],
-                       (int)label[s * MAX_DET + i], d->score);
+                printf("slot %d: detection at chunk %d by model %d, label %d, score %.7f, gain of the call's last chunk %.1f\n", s,
+                       (int)d->frame / 3 + 1, (int)model[s * MAX_DET + i], (int)label[s * MAX_DET + i], d->score, gains[(size_t)s * n + n - 1]);
                 ++*detections;
             }
     }
@@ -87,6 +92,11 @@ int main(int argc, char **argv) {
     /* 2. the live batch: nobody has a model yet */
     const int32_t nobody[SLOTS] = {-1, -1, -1, -1};
     if (rp_stream_batch_new_model_bank(ctx, bank, nobody, &cfg.detector, SLOTS, CALL_CHUNKS, &batch) < 0) goto out;
+    /* ... with RustpotterConfig.filters.gain_normalizer, every slot towards the level of ITS model (before the first audio) */
+    cfg.filters.gain_normalizer.enabled = true;
+    cfg.filters.gain_normalizer.min_gain = 0.5f;
+    cfg.filters.gain_normalizer.max_gain = 2.0f;
+    if (rp_stream_batch_set_filters_per_stream(batch, &cfg.filters) < 0) goto out;
     if (feed(batch, NULL, 20, &detections) < 0) goto out;
     printf("%d model(s) in the bank, %d detection(s) so far\n", rp_model_bank_size(bank), detections);
     /* 3. two users train while the batch runs: user 0 on every recording, user 1 on one wakeword recording less; both are tested on the
@@ -106,8 +116,8 @@ int main(int argc, char **argv) {
     if (rp_model_bank_train(bank, 0, USERS, &opt, NULL, train_counts, train_names, train_wavs, train_lens, test_counts, test_names, test_wavs,
                             test_lens, NULL, NULL, NULL, NULL, loss, accuracy) < 0) goto out;
     for (int u = 0; u < USERS; ++u)
-        printf("trained model %d: windows of %d frames, %d labels, loss %.5f, test accuracy %.2f\n", u, rp_model_bank_train_size(bank, u),
-               rp_model_bank_labels(bank, u), loss[u], accuracy[u]);
+        printf("trained model %d: windows of %d frames, %d labels, loss %.5f, test accuracy %.2f, rms level %.4f\n", u,
+               rp_model_bank_train_size(bank, u), rp_model_bank_labels(bank, u), loss[u], accuracy[u], rp_model_bank_rms_level(bank, u));
     /* 4. their slots are connected (and reset, as add_wakeword does) */
     const int32_t theirs[USERS] = {0, 1};
     if (rp_stream_batch_set_models(batch, FIRST_USER_SLOT, USERS, theirs) < 0) goto out;

@@ -780,7 +780,8 @@ int rp_stream_batch_set_filters_bank(rp_stream_batch *b, const rp_filters_config
  * On such a batch rp_stream_batch_process works without agg (with agg it is refused: a batch of several wakewords has no single aggregate
  * per window; see rp_stream_batch_slot_scores), rp_stream_batch_process_multi reports det_wakeword = the winner's bank index and det_label
  * -1; rp_stream_batch_set_input, _reset and rp_stream_batch_set_filters with the band-pass alone work as on a bank batch;
- * rp_stream_batch_set_wakewords and rp_stream_batch_set_filters_bank fail (the gain normaliser on sets is not built). */
+ * rp_stream_batch_set_wakewords and rp_stream_batch_set_filters_bank fail; the gain normaliser of a sets batch comes with
+ * rp_stream_batch_set_filters_per_stream (below the model sets). */
 int rp_stream_batch_new_bank_sets(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size,
                                   const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out);
 /* rp_stream_batch_set_wakewords for a sets batch (an error on any other), at any time between process calls: streams first_stream ..
@@ -973,8 +974,8 @@ int rp_batch_detect_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fm
  * On such a batch rp_stream_batch_process works without agg (with agg it is refused: the per-window output is the logits, see
  * rp_stream_batch_logits); rp_stream_batch_process_multi reports det_wakeword = the stream's model index and det_label = the label index
  * of the detection's best window; rp_stream_batch_set_input, _reset and _chunks_seen work as everywhere; rp_stream_batch_set_filters takes
- * the band-pass filter alone (with the gain normaliser enabled it is refused: a per-model rms_level is not built); VAD works as on every
- * live batch.  rp_stream_batch_set_wakewords, _set_wakeword_sets, _set_filters_bank and _slot_scores are refused with an error that says
+ * the band-pass filter alone (with the gain normaliser enabled it is refused; rp_stream_batch_set_filters_per_stream gives every stream the
+ * gain normaliser of its own model); VAD works as on every live batch.  rp_stream_batch_set_wakewords, _set_wakeword_sets, _set_filters_bank and _slot_scores are refused with an error that says
  * why. */
 int rp_stream_batch_new_model_bank(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_model, const rp_detector_config *config, size_t S,
                                    size_t max_chunks_per_call, rp_stream_batch **out);
@@ -1021,14 +1022,59 @@ int rp_batch_detect_model_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_form
  * into calls and equal, slot by slot, those of rp_stream_batch_new_multi with the live slots' models (calls of at most 10 chunks).
  * rp_stream_batch_process works without agg and is refused with agg; rp_stream_batch_process_multi reports det_wakeword = the winner's bank
  * index and det_label; rp_stream_batch_logits returns [S][set_size][frames of the call][label pitch]; rp_stream_batch_set_input, _reset,
- * _chunks_seen and the band-pass-only rp_stream_batch_set_filters work as on a model-bank batch.  The gain normaliser, _set_models,
- * _set_wakewords, _set_wakeword_sets, _set_filters_bank and _slot_scores are refused, each with an error that says why. */
+ * _chunks_seen and the band-pass-only rp_stream_batch_set_filters work as on a model-bank batch.  The gain normaliser through
+ * rp_stream_batch_set_filters, _set_models, _set_wakewords, _set_wakeword_sets, _set_filters_bank and _slot_scores are refused, each with an
+ * error that says why; rp_stream_batch_set_filters_per_stream gives such a batch the gain normaliser. */
 int rp_stream_batch_new_model_bank_sets(rp_ctx *ctx, const rp_model_bank *bank, const int32_t *stream_models, int set_size,
                                         const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out);
 /* Re-target streams first_stream .. first_stream + n - 1 of such a batch: stream_models [n][set_size].  All slots are removed, the new ones
  * added in order and the stream reset, as rp_stream_batch_set_wakeword_sets does.  A refused row (host arrays) names its stream and slot and
  * changes nothing.  An error on any other kind of batch. */
 int rp_stream_batch_set_model_sets(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *stream_models);
+
+/* The gain normaliser where a stream holds SEVERAL entries of a bank, or a model.  A Rustpotter with several wakewords works towards the
+ * largest rms_level of its wakewords, NaN ignored (f32::max folded from NaN; NaN when none has a level: gain 1), over a window of
+ * max_mfcc_frames / 3 chunk levels, at least 1 (on_wakeword_change, src/detector.rs:328-338; set_rms_level_ref,
+ * gain_normalizer_filter.rs:42-48).  For stream s that is target(s) = the largest non-NaN level and Lmax(s) = the longest window over the
+ * live slots of its row; one short kernel (gain_targets_kernel) prepares both per stream in front of the per-stream gain kernels of
+ * rp_frontend_batch_bank and rp_stream_batch_set_filters_bank, which are unchanged.  A model's level is part of the model bank:
+ * WakewordModel::rms_level, kept from the .rpw files by rp_model_bank_new_from_rpw / _put_from_rpw, the level of the trained file after
+ * rp_model_bank_train (rustpotter's trainer: the running mean of the non-"none" samples' levels), NaN for models given as handles
+ * (rp_model_bank_new / _put).  It moves with the model when the bank's pools grow.
+ * rms_levels: a HOST array [rp_model_bank_size], NaN allowed, whatever the pointer flag of the context; the write is ordered on the
+ * context's stream and holds from the next call that uses the bank (rp_frontend_batch_model_bank, a live-stream batch with
+ * rp_stream_batch_set_filters_per_stream). */
+int rp_model_bank_set_rms_levels(rp_model_bank *bank, const float *rms_levels);
+/* ... of one model as last set; NaN for a NULL bank or an index outside the bank. */
+float rp_model_bank_rms_level(const rp_model_bank *bank, long long model);
+/* rp_frontend_batch_bank for wakeword sets, what goes in front of rp_batch_detect_bank_sets: stream s works towards target(s) over
+ * max(Lmax(s) / 3, 1) chunk levels (filters->gain_normalizer.gain_ref for every stream when has_gain_ref).  A row without a live slot is a
+ * detector without wakewords: gain 1 for every chunk, the band-pass as on any stream.  stream_wakewords [S][set_size] as in
+ * rp_dtw_score_bank_sets: with RP_CTX_HOST_POINTERS an index outside [-1, n_wakewords) is an error that names stream and slot, found before
+ * anything is launched or written; with device arrays such an index counts as -1.  With set_size 1 the bits of rp_frontend_batch_bank. */
+int rp_frontend_batch_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size,
+                                float *pcm_out, size_t out_stride, float *rms, float *gains);
+/* ... for a model bank, in front of rp_batch_detect_model_bank (set_size 1) and rp_batch_detect_model_bank_sets: stream_models
+ * [S][set_size] as in rp_mlp_forward_windows_bank_sets, the level of a slot is rp_model_bank_rms_level, its window the model's train_size. */
+int rp_frontend_batch_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                 const rp_filters_config *filters, const rp_model_bank *bank, const int32_t *stream_models, int set_size,
+                                 float *pcm_out, size_t out_stride, float *rms, float *gains);
+/* rp_stream_batch_set_filters for every batch over a bank: rp_stream_batch_new_bank_sets, rp_stream_batch_new_model_bank,
+ * rp_stream_batch_new_model_bank_sets, and rp_stream_batch_new_bank, where it gives the bits of rp_stream_batch_set_filters_bank (a set of
+ * one).  An error on a batch of shared wakewords (rp_stream_batch_new / _new_multi: rp_stream_batch_set_filters is theirs).  The gain
+ * normaliser of stream s works towards target(s) over max(Lmax(s) / 3, 1) chunk levels (gain_ref for every stream when has_gain_ref); both
+ * are prepared from the batch's indices and the bank at the start of EVERY process call, so a bank that changed under the batch
+ * (rp_wakeword_bank_put / _enrol / _set_rms_levels, rp_model_bank_put / _put_from_rpw / _train / _set_rms_levels) is seen from the next call.
+ * The ring of a stream has room for the bank's largest window (or its reservation), as on a one-wakeword bank batch.
+ * The rules of rp_stream_batch_set_filters[_bank] hold: before the first audio, 30 ms chunks only, either order with
+ * rp_stream_batch_set_input; rp_stream_batch_levels reports each chunk's level and gain; with the band-pass alone it behaves as
+ * rp_stream_batch_set_filters; a refused call leaves the batch as it was.
+ * Retargeting (rp_stream_batch_set_wakewords, _set_wakeword_sets, _set_models, _set_model_sets) does what remove-all plus add-in-order do in
+ * the reference: the stream gets its new level and window size, the window of chunk levels is neither cleared nor shortened
+ * (gain_normalizer_filter.rs:42-48), a stream left without a live slot has gain 1 and keeps its window for later.  rp_stream_batch_reset
+ * leaves the filters alone, as everywhere. */
+int rp_stream_batch_set_filters_per_stream(rp_stream_batch *b, const rp_filters_config *filters);
 
 /* Synthetic benchmark input of BASELINE.md §2, generated on the device:
  * pcm[s][i] = (splitmix64(seed ^ ((first_stream+s)<<32 + i)) >> 40) / 2^24 - 0.5 */

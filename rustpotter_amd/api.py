@@ -126,6 +126,8 @@ SYMBOLS = [
     "rp_model_bank_train", "rp_model_bank_read_image", "rp_model_bank_last_put_ms",
     "rp_stream_batch_new_model_bank", "rp_stream_batch_set_models", "rp_stream_batch_logits",
     "rp_mlp_forward_windows_bank_sets", "rp_batch_detect_model_bank_sets", "rp_stream_batch_new_model_bank_sets", "rp_stream_batch_set_model_sets",
+    "rp_model_bank_set_rms_levels", "rp_model_bank_rms_level", "rp_frontend_batch_bank_sets", "rp_frontend_batch_model_bank",
+    "rp_stream_batch_set_filters_per_stream",
 ]
 
 
@@ -317,6 +319,13 @@ def load_library():
                                                   vp, vp, vp, vp, C.c_int]
     L.rp_stream_batch_new_model_bank_sets.argtypes = [vp, vp, vp, C.c_int, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.rp_stream_batch_set_model_sets.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
+    L.rp_model_bank_set_rms_levels.argtypes = [vp, fp]
+    L.rp_model_bank_rms_level.argtypes = [vp, C.c_longlong]
+    L.rp_model_bank_rms_level.restype = C.c_float
+    L.rp_frontend_batch_bank_sets.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(_FiltersCfg), vp, vp, C.c_int, vp,
+                                              C.c_size_t, vp, vp]
+    L.rp_frontend_batch_model_bank.argtypes = L.rp_frontend_batch_bank_sets.argtypes
+    L.rp_stream_batch_set_filters_per_stream.argtypes = [vp, C.POINTER(_FiltersCfg)]
     _LIB = L
     return L
 
@@ -636,6 +645,21 @@ class ModelBank:
         """model_bank_put_kernel's time in the last put (0 unless the context times its kernels)"""
         return float(self._L.rp_model_bank_last_put_ms(self._h))
 
+    @property
+    def rms_levels(self):
+        """rp_model_bank_rms_level of every model: [W] float32, NaN = no level (kept from the .rpw files and by train(); NaN for Model handles)"""
+        import numpy as np
+        return np.array([self._L.rp_model_bank_rms_level(self._h, w) for w in range(self.W)], np.float32)
+
+    def set_rms_levels(self, rms_levels):
+        """rp_model_bank_set_rms_levels: [W] levels (NaN: none), in force from the next call that uses the bank"""
+        import numpy as np
+        a = np.ascontiguousarray(rms_levels, np.float32)
+        if a.shape != (self.W,):
+            raise ValueError("rms_levels must be [W]")
+        if self._L.rp_model_bank_set_rms_levels(self._h, a.ctypes.data_as(C.POINTER(C.c_float))) < 0:
+            raise _err()
+
     def reserve(self, max_train_size=0, max_labels=0, n_models=0, n_frames=0):
         """rp_model_bank_reserve: the largest window and label count the bank will ever hold (what a live batch over it keeps room for)
         and pool size hints"""
@@ -870,7 +894,7 @@ class StreamBatch:
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
                  mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None, bank_filters=None,
-                 stream_wakewords=None, set_size=None, model_bank=None, stream_model=None, stream_models=None):
+                 stream_wakewords=None, set_size=None, model_bank=None, stream_model=None, stream_models=None, per_stream_filters=None):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
         with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
@@ -880,6 +904,8 @@ class StreamBatch:
         bank[stream_wakeword[s]], -1 = none; stream_wakeword is [S] int32 (with device pointers: the address of a device array).
         bank_filters (rp_stream_batch_set_filters_bank, with bank): a FiltersConfig whose gain normaliser works per stream, towards
         the rms_level of the stream's own wakeword over its own window.
+        per_stream_filters (rp_stream_batch_set_filters_per_stream, with bank or model_bank, one entry or a set per stream): a FiltersConfig
+        whose gain normaliser works per stream, towards the largest rms_level of the entries the stream holds over max(Lmax(s) / 3, 1) levels.
         bank + stream_wakewords (rp_stream_batch_new_bank_sets): stream s holds the SET of wakewords stream_wakewords[s], [S][set_size]
         int32 with -1 = an empty slot (with device pointers: the address of a device array and set_size).
         model_bank + stream_model (rp_stream_batch_new_model_bank; templates is then None): stream s runs its own model
@@ -939,6 +965,8 @@ class StreamBatch:
             self.set_filters(filters, rms_level_ref)
         if bank_filters is not None:
             self.set_filters_bank(bank_filters)
+        if per_stream_filters is not None:
+            self.set_filters_per_stream(per_stream_filters)
         self.samples_per_chunk = self._L.rp_stream_batch_samples_per_chunk(h)
         self._last_chunks = 0
         # MFCC frames a stream gains per input frame: 3 (30 ms frames) or 4 (the 40 ms frames of 11.025 / 22.05 kHz input)
@@ -1044,6 +1072,15 @@ class StreamBatch:
         rc.filters = filters
         f = rc._filters_c()
         if self._L.rp_stream_batch_set_filters_bank(self._h, C.byref(f)) < 0:
+            raise _err()
+
+    def set_filters_per_stream(self, filters):
+        """rp_stream_batch_set_filters_per_stream (a batch over a WakewordBank or a ModelBank, one entry or a set per stream; before the
+        first process call)"""
+        rc = RustpotterConfig()
+        rc.filters = filters
+        f = rc._filters_c()
+        if self._L.rp_stream_batch_set_filters_per_stream(self._h, C.byref(f)) < 0:
             raise _err()
 
     def levels(self):
@@ -1521,6 +1558,60 @@ class BatchContext:
         f = rc._filters_c()
         if self._L.rp_frontend_batch_bank(self._h, pcm_ptr, fmt, S, n_samples, pcm_stride, C.byref(f), bank._h, idx_ptr, out_ptr, out_stride,
                                           rms_ptr, gains_ptr) < 0:
+            raise _err()
+
+    def _frontend_sets(self, fn, pcm, filters_config, bank, indices):
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        idx = np.ascontiguousarray(indices, np.int32)
+        if idx.ndim == 1:
+            idx = idx[:, None]
+        assert idx.ndim == 2 and idx.shape[0] == S
+        rc = RustpotterConfig()
+        rc.filters = filters_config
+        f = rc._filters_c()
+        out = np.empty((S, N), np.float32)
+        rms = np.empty((S, N // 480), np.float32)
+        gains = np.empty((S, N // 480), np.float32)
+        if fn(self._h, pcm.ctypes.data, fmt, S, N, N, C.byref(f), bank._h, idx.ctypes.data, idx.shape[1], out.ctypes.data, N, rms.ctypes.data,
+              gains.ctypes.data) < 0:
+            raise _err()
+        return out, rms, gains
+
+    def frontend_bank_sets(self, pcm, filters_config, bank, stream_wakewords):
+        """rp_frontend_batch_bank_sets: frontend_bank() for wakeword sets, stream_wakewords [S][set_size] (-1: an empty slot).  Stream s works
+        towards the largest non-NaN rms_level of its live slots over max(Lmax(s) / 3, 1) chunk levels -> (pcm f32, rms, gains)."""
+        return self._frontend_sets(self._L.rp_frontend_batch_bank_sets, pcm, filters_config, bank, stream_wakewords)
+
+    def frontend_model_bank(self, pcm, filters_config, model_bank, stream_models):
+        """rp_frontend_batch_model_bank: the same over a ModelBank, stream_models [S] or [S][set_size] (-1: none)."""
+        return self._frontend_sets(self._L.rp_frontend_batch_model_bank, pcm, filters_config, model_bank, stream_models)
+
+    def frontend_bank_sets_dev(self, pcm_ptr, fmt, S, n_samples, pcm_stride, filters_config, bank, idx_ptr, set_size, out_ptr, out_stride, rms_ptr,
+                               gains_ptr):
+        """rp_frontend_batch_bank_sets with device pointers"""
+        rc = RustpotterConfig()
+        rc.filters = filters_config
+        f = rc._filters_c()
+        if self._L.rp_frontend_batch_bank_sets(self._h, pcm_ptr, fmt, S, n_samples, pcm_stride, C.byref(f), bank._h, idx_ptr, set_size, out_ptr,
+                                               out_stride, rms_ptr, gains_ptr) < 0:
+            raise _err()
+
+    def frontend_model_bank_dev(self, pcm_ptr, fmt, S, n_samples, pcm_stride, filters_config, model_bank, idx_ptr, set_size, out_ptr, out_stride,
+                                rms_ptr, gains_ptr):
+        """rp_frontend_batch_model_bank with device pointers"""
+        rc = RustpotterConfig()
+        rc.filters = filters_config
+        f = rc._filters_c()
+        if self._L.rp_frontend_batch_model_bank(self._h, pcm_ptr, fmt, S, n_samples, pcm_stride, C.byref(f), model_bank._h, idx_ptr, set_size,
+                                                out_ptr, out_stride, rms_ptr, gains_ptr) < 0:
             raise _err()
 
     def dtw_scores(self, mfcc, templates, score_ref=0.22, band_size=5, score_mode=ScoreMode.Max, with_avg=False):

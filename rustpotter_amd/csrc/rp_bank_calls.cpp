@@ -269,6 +269,49 @@ int rp_frontend_batch_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, s
     });
 }
 
+// ... with every stream's SET of wakewords: the level and window of on_wakeword_change (src/detector.rs:328-338) per stream, prepared by
+// gain_targets_kernel in front of the same kernels.  Indices as rp_dtw_score_bank_sets takes them.
+int rp_frontend_batch_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size,
+                                float *pcm_out, size_t out_stride, float *rms, float *gains) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (S && !stream_wakewords) { set_last_error("null argument"); return -1; }
+        if (!set_size_ok(set_size)) return -1;
+        const Bank &bk = *bank->impl;
+        Ctx *c = bank_call_ctx(ctx, bk.ctx);
+        if (!c) return -1;
+        Staged sg(c);
+        BankIndices bi;   // a refused index: before anything is launched or written
+        if (!stage_bank_indices(c, sg, bk, stream_wakewords, S, set_size, 0, &bi)) return -1;
+        GainSource src;
+        src.ww = bk.dev.ww; src.level = bk.rms_level; src.W = bk.dev.W;
+        return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(bk.dev.max_len / 3, 1), nullptr, bi.dev, pcm_out,
+                              out_stride, rms, gains, &src, set_size);
+    });
+}
+
+// ... with every stream's model, or set of models, of a model bank (set_size 1: rp_batch_detect_model_bank's streams)
+int rp_frontend_batch_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                 const rp_filters_config *filters, const rp_model_bank *bank, const int32_t *stream_models, int set_size,
+                                 float *pcm_out, size_t out_stride, float *rms, float *gains) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank) { set_last_error("null handle"); return -1; }
+        if (S && !stream_models) { set_last_error("null argument"); return -1; }
+        if (!model_set_size_ok(set_size)) return -1;
+        const ModelBank &bk = *bank->impl;
+        Ctx *c = bank_call_ctx(ctx, bk.ctx);
+        if (!c) return -1;
+        Staged sg(c);
+        BankIndices bi;
+        if (!stage_indices(c, sg, bk.dev.W, bk.min_L, [&](size_t w) { return bk.e[w].L; }, "model index", stream_models, S, set_size, 0, &bi)) return -1;
+        GainSource src;
+        src.ww = bk.scan.ww; src.level = bk.rms_level(); src.W = bk.dev.W;
+        return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(bk.max_L / 3, 1), nullptr, bi.dev, pcm_out,
+                              out_stride, rms, gains, &src, set_size);
+    });
+}
+
 int rp_batch_detect_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                          const rp_wakeword_bank *bank, const int32_t *stream_wakeword, const rp_detector_config *config,
                          rp_batch_detection *det, int32_t *n_det, int max_det, float *agg, float *avg, size_t win_pitch) {

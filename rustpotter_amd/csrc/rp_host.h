@@ -191,6 +191,7 @@ struct Ctx {
     // intermediates of rp_batch_detect
     DevBuf ws_mfcc, ws_scores, ws_agg, ws_avg, ws_vad, ws_ring, ws_rms, ws_gain, ws_list, ws_hot;
     DevBuf ws_bank_idx;  // the per-stream wakeword indices of a bank call with RP_CTX_HOST_POINTERS
+    DevBuf ws_gain_tab;  // rp_frontend_batch_bank_sets / _model_bank: the per-stream table of gain_targets_kernel
     DevBuf ws_set_ww, ws_set_agg, ws_set_avg;  // wakeword-set calls: the proposals' bank indices [S][n_win]; the per-slot rows of a call with host pointers
     DevBuf ws_dtw;  // [2 * kDtwSchedChunks | 2 + 2 * kDtwFixCap] uint32: tile counters and fix list of the DTW launchers, zero between calls
     // rp_batch_detect_ingest: copy stream, two device blocks of PCM, per block "copy landed" / "kernels done with it" events
@@ -333,8 +334,14 @@ struct ModelBank {
     DevBuf d_e, d_wimg, d_b1, d_wsum, d_tail, d_ww;
     BankDev scan;                    // W and a BankWakeword per model for scan_bank_kernel: max_len = L, avg set, both thresholds -1
     int max_L = 0, min_L = 0;
-    // models: W handles of this context; none_index [W] (null: every -1); false with the error set
-    static ModelBank *create(Ctx *ctx, size_t W, Model *const *models, int mfcc_size, const int32_t *none_index);
+    // WakewordModel::rms_level of every model (NaN: none), beside scan.ww on the device: what the gain normaliser of a stream reads through
+    // its indices (GainSource), as Bank::rms_levels / rms_level
+    std::vector<float> rms_levels;
+    DevBuf d_level;                  // [cap_models], device
+    const float *rms_level() const { return d_level.as<float>(); }
+    bool set_rms_levels(const float *levels);   // HOST array [W]; ordered on the context's stream
+    // models: W handles of this context; none_index [W] (null: every -1); levels [W] (null: every NaN); false with the error set
+    static ModelBank *create(Ctx *ctx, size_t W, Model *const *models, int mfcc_size, const int32_t *none_index, const float *levels = nullptr);
 
     // ---- a bank that grows (rp_model_bank_reserve / _put / _put_from_rpw / _train), after Bank's.  The six device arrays are pools: a put
     // appends its entries behind used[] (model_bank_put_kernel builds them there), a replaced model's old ones stay behind as garbage
@@ -352,6 +359,7 @@ struct ModelBank {
     struct PutItem {
         const float *w[3] = {nullptr, nullptr, nullptr}, *b[3] = {nullptr, nullptr, nullptr};
         ModelBankEntry entry{};
+        float rms_level = NAN;
     };
     // What the bank refuses in a model of these layer widths, as ModelBank::create words it (`why` without the "model <index>: "), and its
     // entry's shape.  image_ok: the handle's verdict on its three-part image; -1: worked out from the shape, as Model::create does.

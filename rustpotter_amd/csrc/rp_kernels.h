@@ -560,6 +560,30 @@ struct PerStreamGain {
     int W = 0, has_fixed_ref = 0;
     float fixed_ref = 0.f;
 };
+// The same parameters for a stream that holds a SET of a bank's entries (wakeword sets, model sets; a model bank's one model is a set of
+// one): gain_targets_kernel (rp_gain_targets.hip) folds every stream's row of set_size indices into one row of a per-stream table --
+// max_len = Lmax(s), the longest window of the live slots; level = the largest non-NaN level of the live slots, NaN when none
+// (on_wakeword_change, src/detector.rs:328-338); idx = s, or -1 for a stream without a live slot -- and the per-stream gain kernels read
+// that table as they read a bank: PerStreamGain{idx, table, level, W = S}.
+struct GainSource {                             // where the windows and levels come from
+    const BankWakeword *ww = nullptr;           // [W], device: BankDev::ww of a wakeword bank, ModelBank::scan.ww (max_len = L) of a model bank
+    const float *level = nullptr;               // [W], device: Bank::rms_level / ModelBank::rms_level, NaN: none
+    int W = 0;
+};
+struct GainTargets {
+    const int32_t *idx = nullptr;               // [S][set_size], device; outside [0, W): an empty slot
+    int set_size = 1;
+    const BankWakeword *ww = nullptr;
+    const float *level = nullptr;
+    int W = 0;
+    BankWakeword *table = nullptr;              // [S]
+    float *tlevel = nullptr;                    // [S]
+    int32_t *tidx = nullptr;                    // [S]
+};
+size_t gain_targets_bytes(size_t S);            // the workspace of S streams
+// One short launch; fills per->stream_wakeword / ww / rms_level / W (has_fixed_ref and fixed_ref stay the caller's)
+hipError_t launch_gain_targets(hipStream_t st, const GainSource &src, const int32_t *idx, int set_size, size_t S, void *workspace,
+                               PerStreamGain *per);
 // Decode + GainNormalizerFilter + BandPassFilter over whole streams.  ring [S][window_size], rms / gains
 // [S][n_samples/480] are device workspaces; biquad coefficients as BandPassFilter::new computes them.
 hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,

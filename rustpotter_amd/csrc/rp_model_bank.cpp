@@ -93,7 +93,7 @@ static void entry_space(const ModelBankEntry &e, size_t n[4]) {
 }
 static const size_t kPoolUnit[4] = {16, 4, 4, 4};   // bytes
 
-ModelBank *ModelBank::create(Ctx *ctx, size_t W, Model *const *models, int mfcc_size, const int32_t *none_index) {
+ModelBank *ModelBank::create(Ctx *ctx, size_t W, Model *const *models, int mfcc_size, const int32_t *none_index, const float *levels) {
     if (W > 0x7fffffffULL) { set_last_error("model bank: too many models"); return nullptr; }
     if (W && mfcc_size != 16) {
         set_last_error("model bank: mfcc_size " + std::to_string(mfcc_size) + " is not built (mlp_windows_bank_kernel takes mfcc_size 16)");
@@ -103,6 +103,8 @@ ModelBank *ModelBank::create(Ctx *ctx, size_t W, Model *const *models, int mfcc_
     std::unique_ptr<ModelBank> b(new ModelBank());
     b->ctx = ctx;
     b->e.resize(W);
+    b->rms_levels.assign(W, NAN);   // no level until the .rpw files or rp_model_bank_set_rms_levels give one
+    if (levels) std::copy(levels, levels + W, b->rms_levels.begin());
     std::vector<BankWakeword> ww(W);
     size_t at[4] = {0, 0, 0, 0};
     for (size_t i = 0; i < W; ++i) {
@@ -128,7 +130,8 @@ ModelBank *ModelBank::create(Ctx *ctx, size_t W, Model *const *models, int mfcc_
     b->scan.W = (int)W; b->scan.K = 16; b->scan.max_len = b->max_L; b->scan.min_len = b->min_L;
     if (W == 0) return b.release();
     if (!b->d_e.reserve(W * sizeof(ModelBankEntry)) || !b->d_ww.reserve(W * sizeof(BankWakeword)) || !b->d_wimg.reserve(at[kImg] * 16) ||
-        !b->d_b1.reserve(at[kB1] * 4) || !b->d_wsum.reserve(at[kWsum] * 4) || !b->d_tail.reserve(at[kTail] * 4)) return nullptr;
+        !b->d_b1.reserve(at[kB1] * 4) || !b->d_wsum.reserve(at[kWsum] * 4) || !b->d_tail.reserve(at[kTail] * 4) ||
+        !b->d_level.reserve(W * sizeof(float))) return nullptr;
     auto d2d = [&](void *dst, const void *src, size_t bytes) {
         return hip_ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync(D2D)");
     };
@@ -143,6 +146,7 @@ ModelBank *ModelBank::create(Ctx *ctx, size_t W, Model *const *models, int mfcc_
     }
     if (!hip_ok(hipMemcpyAsync(b->d_e.p, b->e.data(), W * sizeof(ModelBankEntry), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(H2D)") ||
         !hip_ok(hipMemcpyAsync(b->d_ww.p, ww.data(), W * sizeof(BankWakeword), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(H2D)") ||
+        !hip_ok(hipMemcpyAsync(b->d_level.p, b->rms_levels.data(), W * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(H2D)") ||
         !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) return nullptr;   // the handles may be freed when this returns
     b->dev.e = b->d_e.as<ModelBankEntry>();
     b->dev.wimg = b->d_wimg.p;
@@ -152,6 +156,15 @@ ModelBank *ModelBank::create(Ctx *ctx, size_t W, Model *const *models, int mfcc_
     for (int k = 0; k < 4; ++k) b->used[k] = b->cap[k] = at[k];
     b->cap_models = W;
     return b.release();
+}
+
+bool ModelBank::set_rms_levels(const float *levels) {
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return false;
+    if (rms_levels.empty()) return true;
+    std::copy(levels, levels + rms_levels.size(), rms_levels.begin());
+    // behind whatever the context's stream still runs with the old levels; the host copy is the bank's own, so it may change again at once
+    return hip_ok(hipMemcpyAsync(d_level.p, rms_levels.data(), rms_levels.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream),
+                  "hipMemcpyAsync(rms levels)") && hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
 }
 
 // ---------------------------------------------------------------------------------------------------------------- a bank that grows
@@ -185,14 +198,15 @@ static void take_over(DevBuf &pool, DevBuf &fresh) { std::swap(pool.p, fresh.p);
 
 bool ModelBank::grow_models(size_t n) {
     if (n <= cap_models) return true;
-    DevBuf ne, nw;
+    DevBuf ne, nw, nl;   // the levels move with the descriptors
     const size_t W = (size_t)dev.W;
     // behind whatever still reads the old arrays; they are freed after the stream has drained
-    if (!ne.reserve(n * sizeof(ModelBankEntry)) || !nw.reserve(n * sizeof(BankWakeword)) ||
-        (W && (!hip_ok(hipMemcpyAsync(ne.p, d_e.p, W * sizeof(ModelBankEntry), hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync(model bank)") ||
+    if (!ne.reserve(n * sizeof(ModelBankEntry)) || !nw.reserve(n * sizeof(BankWakeword)) || !nl.reserve(n * sizeof(float)) ||
+        (W && (!hip_ok(hipMemcpyAsync(nl.p, d_level.p, W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync(model bank)") ||
+               !hip_ok(hipMemcpyAsync(ne.p, d_e.p, W * sizeof(ModelBankEntry), hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync(model bank)") ||
                !hip_ok(hipMemcpyAsync(nw.p, d_ww.p, W * sizeof(BankWakeword), hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync(model bank)"))) ||
         !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) return false;
-    take_over(d_e, ne); take_over(d_ww, nw);
+    take_over(d_e, ne); take_over(d_ww, nw); take_over(d_level, nl);
     dev.e = d_e.as<ModelBankEntry>(); scan.ww = d_ww.as<BankWakeword>();
     cap_models = n;
     return true;
@@ -301,6 +315,7 @@ bool ModelBank::put(size_t first, const std::vector<PutItem> &items, const char 
     std::vector<ModelPutItem> tab(n);
     std::vector<ModelBankEntry> ne(n);
     std::vector<BankWakeword> nww(n);
+    std::vector<float> nlevel(n);
     size_t at[4] = {used[0], used[1], used[2], used[3]};
     for (size_t i = 0; i < n; ++i) {
         ModelBankEntry &x = ne[i];
@@ -312,6 +327,7 @@ bool ModelBank::put(size_t first, const std::vector<PutItem> &items, const char 
         for (int l = 0; l < 3; ++l) { tab[i].w[l] = items[i].w[l]; tab[i].b[l] = items[i].b[l]; }
         tab[i].e = x;
         nww[i] = BankWakeword{0, 0, x.L, 0, 0, -1.f, -1.f, 0};
+        nlevel[i] = items[i].rms_level;
     }
     const size_t tab_bytes = n * sizeof(ModelPutItem);
     if (!put_ws.reserve(tab_bytes + n * sizeof(uint32_t))) return false;
@@ -340,6 +356,7 @@ bool ModelBank::put(size_t first, const std::vector<PutItem> &items, const char 
     // commit: the descriptors -- behind every launch that took the bank as it was
     if (!hip_ok(hipMemcpyAsync(d_e.as<ModelBankEntry>() + first, ne.data(), n * sizeof(ModelBankEntry), hipMemcpyHostToDevice, st), "hipMemcpyAsync(model bank)") ||
         !hip_ok(hipMemcpyAsync(d_ww.as<BankWakeword>() + first, nww.data(), n * sizeof(BankWakeword), hipMemcpyHostToDevice, st), "hipMemcpyAsync(model bank)") ||
+        !hip_ok(hipMemcpyAsync(d_level.as<float>() + first, nlevel.data(), n * sizeof(float), hipMemcpyHostToDevice, st), "hipMemcpyAsync(model bank)") ||
         !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize")) return false;
     for (size_t w = first; w < std::min(first + n, e.size()); ++w) {   // what a replaced model leaves behind
         size_t sp[4];
@@ -347,8 +364,9 @@ bool ModelBank::put(size_t first, const std::vector<PutItem> &items, const char 
         for (int k = 0; k < 4; ++k) dead[k] += sp[k];
     }
     for (int k = 0; k < 4; ++k) used[k] = at[k];
-    if (e.size() < first + n) e.resize(first + n);
+    if (e.size() < first + n) { e.resize(first + n); rms_levels.resize(first + n, NAN); }
     std::copy(ne.begin(), ne.end(), e.begin() + (long)first);
+    std::copy(nlevel.begin(), nlevel.end(), rms_levels.begin() + (long)first);
     dev.W = (int)e.size();
     int largest = 0;
     max_L = min_L = 0;
@@ -421,6 +439,7 @@ int rp_model_bank_new_from_rpw(rp_ctx *ctx, size_t n_models, const uint8_t *cons
         std::vector<std::unique_ptr<Model>> owned;
         std::vector<Model *> ms;
         std::vector<int32_t> none;
+        std::vector<float> levels;
         int K = 0;
         for (size_t w = 0; w < n_models; ++w) {
             auto fail = [&](const std::string &why) { set_last_error("wakeword " + std::to_string(w) + ": " + why); return -1; };
@@ -440,8 +459,9 @@ int rp_model_bank_new_from_rpw(rp_ctx *ctx, size_t n_models, const uint8_t *cons
             ms.push_back(m.get());
             owned.push_back(std::move(m));
             none.push_back(ni);
+            levels.push_back(model.rms_level);
         }
-        return bank_handle(std::unique_ptr<ModelBank>(ModelBank::create(c, n_models, ms.data(), n_models ? K : 16, none.data())), out);
+        return bank_handle(std::unique_ptr<ModelBank>(ModelBank::create(c, n_models, ms.data(), n_models ? K : 16, none.data(), levels.data())), out);
     });
 }
 
@@ -476,6 +496,19 @@ int rp_model_bank_reserved(const rp_model_bank *bank, int *max_train_size, int *
 int rp_model_bank_pool_growths(const rp_model_bank *bank) {
     if (!bank) { set_last_error("null handle"); return -1; }
     return (int)std::min<size_t>(bank->impl->grown, 0x7fffffff);
+}
+
+int rp_model_bank_set_rms_levels(rp_model_bank *bank, const float *rms_levels) {
+    return guarded([&]() -> int {
+        if (!bank) { set_last_error("null handle"); return -1; }
+        if (!rms_levels && bank->impl->dev.W) { set_last_error("null argument"); return -1; }
+        return bank->impl->set_rms_levels(rms_levels) ? 0 : -1;
+    });
+}
+
+float rp_model_bank_rms_level(const rp_model_bank *bank, long long model) {
+    if (!bank || model < 0 || model >= (long long)bank->impl->dev.W) return NAN;
+    return bank->impl->rms_levels[(size_t)model];
 }
 
 double rp_model_bank_last_put_ms(const rp_model_bank *bank) { return bank ? bank->impl->last_put_ms : 0.0; }
@@ -531,6 +564,7 @@ int rp_model_bank_put_from_rpw(rp_model_bank *bank, size_t first, size_t n, cons
             if (dims.back() != (int)model.labels.size()) return fail("Incorrect model layers");
             if (K != 16) { set_last_error("model bank: mfcc_size " + std::to_string(K) + kNotBuilt); return -1; }
             if (!put_item_of(dims, ni, -1, "wakeword", first + w, &items[w])) return -1;
+            items[w].rms_level = model.rms_level;
             for (int l = 0; l < n_layers; ++l) {
                 raw.w_at.push_back(raw.add(wp[l], (size_t)dims[l] * (size_t)dims[l + 1]));
                 raw.b_at.push_back(raw.add(bp[l], (size_t)dims[l + 1]));
@@ -593,6 +627,7 @@ int rp_model_bank_train(rp_model_bank *bank, size_t first, size_t n, const rp_tr
             std::vector<const float *> wp, bp;
             if (!model_layers(models[w], &n_layers, &dims, &wp, &bp, &ni)) { set_last_error("model " + std::to_string(first + w) + ": " + last_error()); return -1; }
             if (!put_item_of(dims, ni, -1, "model", first + w, &items[w])) return -1;
+            items[w].rms_level = models[w].rms_level;   // the level the trained file carries (rp_train.cpp)
             for (int l = 0; l < n_layers; ++l) { items[w].w[l] = ws + left.jobs[w].w[l]; items[w].b[l] = ws + left.jobs[w].b[l]; }
         }
         if (!bk.put_check(first, items, "model")) return -1;

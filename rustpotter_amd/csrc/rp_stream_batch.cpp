@@ -76,6 +76,11 @@ struct rp_stream_batch {
     // rp_stream_batch_set_filters_bank: the gain normaliser of stream s takes its reference level and window size from its own wakeword of the
     // bank, read through bank_idx at the start of every call; gain_window is then the capacity of a stream's ring, the bank's largest window
     bool per_stream_gain = false;
+    // rp_stream_batch_set_filters_per_stream: the level and window of stream s come from ALL the bank entries it holds (a set of wakewords or of
+    // models, one model, one wakeword), folded by gain_targets_kernel at the start of every call into gain_tab, the per-stream table the same
+    // gain kernels then read; a bank that changed under the batch is seen from the next call
+    bool prep_gain = false;
+    DevBuf gain_tab;
     DevBuf filt_state, lv_rms, lv_gain;
     size_t levels_chunks = 0;
     bool filters_on() const { return has_filters && (filt.gain_normalizer.enabled || filt.band_pass.enabled); }
@@ -230,7 +235,13 @@ static bool stream_frames(rp_stream_batch *b, const MfccTablesDev &tb, const Str
         // with filters, ONE launch in the place of launch_stream_stage: history chunk | the new chunks decoded and filtered, levels kept
         const rp_gain_normalization_config &g = b->filt.gain_normalizer;
         PerStreamGain per;
-        if (b->per_stream_gain) {
+        if (b->prep_gain) {
+            GainSource src;
+            if (b->mbank) { src.ww = b->mbank->scan.ww; src.level = b->mbank->rms_level(); src.W = b->mbank->dev.W; }
+            else { src.ww = b->bank->dev.ww; src.level = b->bank->rms_level; src.W = b->bank->dev.W; }
+            if (!hip_ok(launch_gain_targets(c->stream, src, b->bank_idx.as<int32_t>(), (int)b->slots(), S, b->gain_tab.p, &per), "gain_targets_kernel")) return false;
+            per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
+        } else if (b->per_stream_gain) {
             per.stream_wakeword = b->bank_idx.as<int32_t>(); per.ww = b->bank->dev.ww; per.rms_level = b->bank->rms_level; per.W = b->bank->dev.W;
             per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;   // fixed_rms_level, gain_normalizer_filter.rs:56-66
         }
@@ -609,13 +620,18 @@ int rp_stream_batch_set_input(rp_stream_batch *b, size_t sample_rate, int channe
 }
 size_t rp_stream_batch_samples_per_chunk(const rp_stream_batch *b) { return b ? b->in_len * (size_t)b->channels : 0; }
 
-// Both filter calls; per_stream: rp_stream_batch_set_filters_bank (rms_level_ref is then not read)
-static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref, bool per_stream) {
+// The three filter calls; per_stream: rp_stream_batch_set_filters_bank, prepared: rp_stream_batch_set_filters_per_stream (rms_level_ref is then
+// not read)
+static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *filters, float rms_level_ref, bool per_stream, bool prepared = false) {
     return guarded([&]() -> int {
-        const std::string name = per_stream ? "rp_stream_batch_set_filters_bank" : "rp_stream_batch_set_filters";
+        const std::string name = prepared ? "rp_stream_batch_set_filters_per_stream" : per_stream ? "rp_stream_batch_set_filters_bank" : "rp_stream_batch_set_filters";
         if (b && !filters) { set_last_error("null argument"); return -1; }
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (prepared && !b->bank && !b->mbank) {
+            set_last_error(name + ": the batch holds shared wakewords, one level and one window for every stream; rp_stream_batch_set_filters takes them");
+            return -1;
+        }
         if (per_stream && b->mbank) {
             set_last_error(name + ": the gain normaliser per model is not built for a batch over a model bank (a model's rms_level is not part of the "
                                   "bank); rp_stream_batch_set_filters takes the band-pass filter alone");
@@ -630,12 +646,12 @@ static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config 
         if (b->chunks_seen) { set_last_error(name + ": the streams have already received audio"); return -1; }
         if (b->out_len != 480) { set_last_error(kFiltersNeed30ms); return -1; }
         const rp_gain_normalization_config &g = filters->gain_normalizer;
-        if (b->mbank && g.enabled) {
+        if (b->mbank && g.enabled && !prepared) {
             set_last_error("rp_stream_batch_set_filters: the gain normaliser is not available on a batch over a model bank (its window and "
                            "rms_level_ref would be per stream, and a model's rms_level is not part of the bank); the band-pass filter alone is");
             return -1;
         }
-        if (b->bank && g.enabled && !per_stream) {
+        if (b->bank && g.enabled && !per_stream && !prepared) {
             set_last_error("rp_stream_batch_set_filters: the gain normaliser is not available on a batch over a wakeword bank (its window and "
                            "rms_level_ref would be per stream, stream_filters_kernel takes one value of each); the band-pass filter alone is, "
                            "and rp_stream_batch_set_filters_bank gives every stream the gain normaliser of its own wakeword");
@@ -645,11 +661,13 @@ static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config 
         const int window = std::max(b->max_len / 3, 1);   // on_wakeword_change, src/detector.rs:337; set_rms_level_ref :47
         const size_t lv = b->S * b->max_chunks * sizeof(float) + 16, st = stream_filter_state_bytes(b->S, window);
         if (!b->filt_state.reserve(st) || !b->lv_rms.reserve(lv) || !b->lv_gain.reserve(lv)) return -1;
+        if (prepared && g.enabled && !b->gain_tab.reserve(gain_targets_bytes(b->S))) return -1;
         if (!hip_ok(hipMemsetAsync(b->filt_state.p, 0, st, c->stream), "hipMemsetAsync")) return -1;
         b->filt = *filters;
         b->rms_level_ref = g.enabled && g.has_gain_ref ? g.gain_ref : rms_level_ref;  // fixed_rms_level, gain_normalizer_filter.rs:56-66
         b->gain_window = window;
-        b->per_stream_gain = per_stream && g.enabled;
+        b->per_stream_gain = (per_stream || prepared) && g.enabled;
+        b->prep_gain = prepared && g.enabled;
         band_pass_coefficients(filters->band_pass, b->bq);
         b->has_filters = true;
         return 0;
@@ -661,6 +679,10 @@ int rp_stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config *fil
 }
 int rp_stream_batch_set_filters_bank(rp_stream_batch *b, const rp_filters_config *filters) {
     return stream_batch_set_filters(b, filters, NAN, true);
+}
+
+int rp_stream_batch_set_filters_per_stream(rp_stream_batch *b, const rp_filters_config *filters) {
+    return stream_batch_set_filters(b, filters, NAN, false, true);
 }
 
 int rp_stream_batch_levels(rp_stream_batch *b, float *rms, float *gains) {
