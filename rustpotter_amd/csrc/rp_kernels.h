@@ -761,7 +761,10 @@ struct MlpStreamPlan {
 };
 bool mlp_stream_supported(const MlpDev &m, const float *x, int precision);
 hipError_t launch_mlp_stream(hipStream_t st, const MlpDev &m, const MlpStreamPlan &p, const float *x, size_t B, int precision, float *out,
-                             int n_cu, uint32_t *redo);   // the streaming pass alone (kMlpF16x2: mlp_forward runs the second pass)
+                             int n_cu, uint32_t *redo, const char **build = nullptr);   // the streaming pass alone (kMlpF16x2: mlp_forward
+                                                                                       // runs the second pass).  *build: "" for the build the
+                                                                                       // launcher picks by itself, else the ring depth and waves
+                                                                                       // RP_MLP_STREAM_DEPTH / RP_MLP_STREAM_WAVES moved it to
 // The rows may also be windows of L = dims[0]/K frames read IN PLACE from mfcc [S][frame_pitch][K] (window w of stream s starts at frame
 // s * frame_pitch + w): the window mean (MfccNormalizer::normalize) is taken out after layer 1, W.(f - mu) = W.f - sum_k mu[k] * wsum[o][k],
 // wsum[o][k] = sum_i W[o][i*K + k] (Model::wsum_for); mean [S*n_win][K] from launch_window_means.

@@ -705,12 +705,13 @@ bool mlp_forward(Ctx &c, const MlpForward &q) {
     const MlpRoute r = mlp_route(md, q);
     uint32_t *redo = r.kind == kMlpLayers ? nullptr : c.mlp_redo(rows);
     hipError_t e = (r.kind != kMlpLayers && !redo) ? hipErrorOutOfMemory : hipSuccess;
+    const char *build = "";   // mlp_stream_kernel: the build a launch knob chose, where it is not the default one
     if (e == hipSuccess && rows) {
         switch (r.kind) {
         case kMlpLayers:
             e = launch_mlp(c.stream, q.x, rows, (int)md.dims.size() - 1, md.dims.data(), md.W.data(), md.B.data(), q.scratch[0], q.scratch[1], q.out);
             break;
-        case kMlpStream: e = launch_mlp_stream(c.stream, m, r.plan, q.x, rows, r.prec, q.out, c.n_cu, redo); break;
+        case kMlpStream: e = launch_mlp_stream(c.stream, m, r.plan, q.x, rows, r.prec, q.out, c.n_cu, redo, &build); break;
         case kMlpWindows:
         case kMlpWindowsWide:
             if (rows > 0xffffffffULL || r.win.bps * q.S > 0x7fffffffULL || r.win.lds > 160 * 1024) e = hipErrorInvalidValue;
@@ -724,7 +725,7 @@ bool mlp_forward(Ctx &c, const MlpForward &q) {
         // the two counter words go back to zero behind whatever was queued, as dtw_abort does for the DTW words
         if (e != hipSuccess && redo) (void)hipMemsetAsync(redo, 0, 2 * sizeof(uint32_t), c.stream);
     }
-    if (e == hipSuccess && q.report && !r.report.empty()) c.last_mlp_kernel = r.report;
+    if (e == hipSuccess && q.report && !r.report.empty()) c.last_mlp_kernel = r.report + build;
     if (q.timed) c.time_end();
     return hip_ok(e, r.kind == kMlpLayers ? "mlp_layer_kernel" : "mlp_mfma_kernel");
 }

@@ -383,12 +383,14 @@ bool mlp_stream_supported(const MlpDev &m, const float *x, int precision) {
 }
 
 hipError_t launch_mlp_stream(hipStream_t st, const MlpDev &m, const MlpStreamPlan &p, const float *x, size_t B, int precision, float *out, int n_cu,
-                             uint32_t *redo) {
+                             uint32_t *redo, const char **build) {
+    if (build) *build = "";
     if (B == 0) return hipSuccess;
     if (precision == kMlpF16x2 && (!redo || B > 0xffffffffULL)) return hipErrorInvalidValue;
     int h2p = 4;
     const int tail_lds = stream_tail_lds(m, &h2p);
-    int depth = stream_lds_bytes(m.nt, precision, 2, tail_lds, h2p) <= 160 * 1024 ? 2 : 1;
+    const int depth0 = stream_lds_bytes(m.nt, precision, 2, tail_lds, h2p) <= 160 * 1024 ? 2 : 1;   // the default build: eight waves, this ring
+    int depth = depth0;
     if (const char *e = getenv("RP_MLP_STREAM_DEPTH")) if (e[0] == '1') depth = 1;   // benchmarks: the shallower ring
     int waves = 8;
     if (const char *e = getenv("RP_MLP_STREAM_WAVES")) if (e[0] == '4' && 2 * stream_lds_bytes(m.nt, precision, 1, tail_lds, h2p, 4) <= 160 * 1024) { waves = 4; depth = 1; }
@@ -396,6 +398,10 @@ hipError_t launch_mlp_stream(hipStream_t st, const MlpDev &m, const MlpStreamPla
     // waves' row rings.  Measured at BASELINE C5: eight waves with the shallow ring 0.1545 ms, six waves with the deep one 0.208 -- and the
     // two-part form runs 0.132 ms with either ring: depth is not what the three-part form waits for.  RP_MLP_STREAM_WAVES=6: that A/B)
     if (const char *e = getenv("RP_MLP_STREAM_WAVES")) if (e[0] == '6' && precision == kMlpBf16x3 && stream_lds_bytes(m.nt, precision, 2, tail_lds, h2p, 6) <= 160 * 1024) { waves = 6; depth = 2; }
+    // rp_ctx_last_mlp_kernel names the build only where a knob moved it off the default (a knob the LDS conditions above refuse, or one that
+    // asks for what the default is anyway, leaves the report as it is)
+    if (build && (waves != 8 || depth != depth0))
+        *build = waves == 6 ? " [stream build: depth 2, 6 waves]" : waves == 4 ? " [stream build: depth 1, 4 waves]" : " [stream build: depth 1, 8 waves]";
 #define RP_STREAM_CASE(NT_, PREC_)                                                                        \
     if (m.nt == NT_ && precision == PREC_) {                                                              \
         if (waves == 6) return launch_stream_t<NT_, PREC_, 2, 6>(st, m, p, x, B, out, tail_lds, h2p, n_cu, redo); \
