@@ -139,6 +139,7 @@ extern "C" {
     pub fn rp_ctx_synchronize(ctx: *mut rp_ctx) -> c_int;
     pub fn rp_ctx_dtw_ref_pairs(ctx: *mut rp_ctx, pairs: *mut u64) -> c_int;
     pub fn rp_ctx_dtw_kernels(ctx: *mut rp_ctx) -> c_int;
+    pub fn rp_ctx_last_window_scores(ctx: *mut rp_ctx, out: *mut f32, n: usize) -> c_int;
     pub fn rp_ctx_set_arithmetic(ctx: *mut rp_ctx, arith: c_int, ragged_matrix: c_int) -> c_int;
     pub fn rp_ctx_arithmetic(ctx: *mut rp_ctx, ragged_matrix: *mut c_int) -> c_int;
     pub fn rp_ctx_last_mlp_kernel(ctx: *mut rp_ctx) -> *const c_char;
@@ -707,6 +708,13 @@ impl HipContext {
         let mut v: u64 = 0;
         status(unsafe { rp_ctx_dtw_ref_pairs(self.h, &mut v) })?;
         Ok(v)
+    }
+    /// diagnostics of detect-only calls: the `[n_streams * n_win][n_templates]` sample-template scores the last ungated `rp_batch_detect*`
+    /// of this context left in its workspace (an abandoned DTW holds 0)
+    pub fn last_window_scores(&self, n_streams: usize, n_win: usize, n_templates: usize) -> Result<Vec<f32>, String> {
+        let mut out = vec![0f32; n_streams * n_win * n_templates];
+        status(unsafe { rp_ctx_last_window_scores(self.h, out.as_mut_ptr(), out.len()) })?;
+        Ok(out)
     }
 
     /// `MfccExtractor::compute` (src/mfcc/extractor.rs:60-163) over `n_streams` whole streams of `n_samples` f32 samples:

@@ -239,6 +239,13 @@ enum {
     RP_DTW_KERNEL_BANK_SETS_STREAM = 32768 /* dtw_set_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank_sets) */
 };
 int rp_ctx_dtw_kernels(rp_ctx *ctx);
+/* Diagnostics of detect-only calls (replaces nothing): the first n floats of the [S * n_win][T] sample-template score workspace as the last
+ * rp_batch_detect* of this context left it (waits for the context's stream; `out` is a HOST array whatever the context's flags say).
+ * Fails when the context has made no such call or n exceeds what that call wrote.  An abandoned DTW holds 0 there.  Only defined after
+ * UNGATED calls: the averaged-template gate (a detect-only call of a set with an averaged template and avg_threshold != 0) leaves the rows
+ * it does not list as an earlier call wrote them.  Calls that hand their scores to a device array of the caller's, the several-wakeword
+ * and model entry points and live-stream batches leave nothing to read here. */
+int rp_ctx_last_window_scores(rp_ctx *ctx, float *out, size_t n);
 /* Which build this library is (replaces nothing): the target architecture and the compiler flags it differs by from the
  * product's Makefile defaults -- "gfx950" for the product, "gfx950 +-DRP_..." for an experiment build (tools/ab.sh builds
  * those into rustpotter_amd/variants/, never over the product).  bench.py prints it on its JSON line. */

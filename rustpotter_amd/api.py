@@ -103,7 +103,7 @@ SYMBOLS = [
     "rp_get_partial_detection", "rp_get_rms_level", "rp_get_gain", "rp_get_rms_level_ref", "rp_process_bytes",
     "rp_process_samples_i8", "rp_process_samples_i16", "rp_process_samples_i32", "rp_process_samples_f32",
     "rp_update_config", "rp_update_detector_config", "rp_update_filters_config", "rp_reset", "rp_last_error",
-    "rp_ctx_new", "rp_ctx_free", "rp_ctx_set_stream", "rp_ctx_synchronize", "rp_ctx_dtw_ref_pairs", "rp_ctx_dtw_kernels", "rp_ctx_set_arithmetic", "rp_ctx_arithmetic", "rp_ctx_last_mlp_kernel", "rp_build_info", "rp_sharded_gather_info", "rp_mfcc_num_frames", "rp_mfcc_batch", "rp_mfcc_batch_fmt", "rp_batch_detect_fmt", "rp_batch_detect_ingest", "rp_frontend_batch", "rp_wakeword_ref_build", "rp_buffer_free",
+    "rp_ctx_new", "rp_ctx_free", "rp_ctx_set_stream", "rp_ctx_synchronize", "rp_ctx_dtw_ref_pairs", "rp_ctx_dtw_kernels", "rp_ctx_last_window_scores", "rp_ctx_set_arithmetic", "rp_ctx_arithmetic", "rp_ctx_last_mlp_kernel", "rp_build_info", "rp_sharded_gather_info", "rp_mfcc_num_frames", "rp_mfcc_batch", "rp_mfcc_batch_fmt", "rp_batch_detect_fmt", "rp_batch_detect_ingest", "rp_frontend_batch", "rp_wakeword_ref_build", "rp_buffer_free",
     "rp_mfcc_average_batch", "rp_wakeword_ref_build_batch",
     "rp_templates_new", "rp_templates_free", "rp_templates_max_len", "rp_dtw_score_batch", "rp_detect_scan", "rp_batch_detect",
     "rp_model_new", "rp_model_free", "rp_mlp_forward_batch", "rp_mlp_forward_windows", "rp_synth_pcm_batch", "rp_ctx_timing_enable", "rp_ctx_timing_read", "rp_ctx_timing_reset",
@@ -187,6 +187,7 @@ def load_library():
     L.rp_ctx_dtw_ref_pairs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rp_ctx_dtw_kernels.argtypes = [vp]
     L.rp_ctx_dtw_kernels.restype = C.c_int
+    L.rp_ctx_last_window_scores.argtypes = [vp, vp, C.c_size_t]
     L.rp_ctx_set_arithmetic.argtypes = [vp, C.c_int, C.c_int]
     L.rp_ctx_set_arithmetic.restype = C.c_int
     L.rp_ctx_arithmetic.argtypes = [vp, C.POINTER(C.c_int)]
@@ -1296,6 +1297,15 @@ class BatchContext:
         if self._L.rp_ctx_dtw_ref_pairs(self._h, C.byref(v)) < 0:
             raise _err()
         return int(v.value)
+
+    def last_window_scores(self, S, n_win, T):
+        """[S][n_win][T] sample-template scores as the last rp_batch_detect* of this context left them in its workspace
+        (rp_ctx_last_window_scores): what a detect-only call computed, an abandoned DTW as 0.  Defined after ungated calls only."""
+        import numpy as np
+        out = np.empty((S, n_win, T), np.float32)
+        if self._L.rp_ctx_last_window_scores(self._h, out.ctypes.data, out.size) < 0:
+            raise _err()
+        return out
 
     DTW_KERNELS = {1: "dtw_mfma_kernel", 2: "dtw_mfma_wide_kernel", 4: "dtw_ragged_kernel", 8: "register kernels", 16: "dtw_generic_kernel",
                    32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel", 4096: "dtw_bank_kernel",

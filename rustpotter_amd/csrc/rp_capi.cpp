@@ -246,6 +246,16 @@ int rp_ctx_dtw_ref_pairs(rp_ctx *ctx, uint64_t *pairs) {
     return 0;
 }
 
+int rp_ctx_last_window_scores(rp_ctx *ctx, float *out, size_t n) {
+    if (!ctx || (n && !out)) { set_last_error("null argument"); return -1; }
+    Ctx *c = ctx->impl.get();
+    if (c->last_window_scores == 0) { set_last_error("rp_ctx_last_window_scores: this context has made no rp_batch_detect call that left its scores in the workspace"); return -1; }
+    if (n > c->last_window_scores) { set_last_error("rp_ctx_last_window_scores: n exceeds what the last call wrote"); return -1; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice") || !hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize")) return -1;
+    if (n && !hip_ok(hipMemcpy(out, c->ws_scores.as<float>(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(window scores)")) return -1;
+    return 0;
+}
+
 #ifndef RP_BUILD_ARCH
 #define RP_BUILD_ARCH "gfx950"
 #endif
@@ -633,7 +643,9 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
         }
         // caller-provided score arrays are used directly when they are device pointers
         float *ds = (scores && !sg.host) ? scores : nullptr, *dg = (agg && !sg.host) ? agg : nullptr;
+        c->last_window_scores = 0;
         if (!ds) { if (!c->ws_scores.reserve(rows * td.T * sizeof(float) + 16)) return -1; ds = c->ws_scores.as<float>(); }
+        const bool ds_is_ws = ds == c->ws_scores.as<float>();
         if (!dg) { if (!c->ws_agg.reserve(rows * sizeof(float) + 16)) return -1; dg = c->ws_agg.as<float>(); }
         float *da = nullptr;
         if (do_avg) { if (!c->ws_avg.reserve(rows * sizeof(float) + 16)) return -1; da = c->ws_avg.as<float>(); }
@@ -651,6 +663,7 @@ static int batch_detect_impl(rp_ctx *ctx, const void *pcm, rp_sample_format fmt,
             if (!q.hot) return -1;
         }
         if (!dtw_score(*c, q)) return -1;
+        if (ds_is_ws) c->last_window_scores = rows * (size_t)td.T;   // rp_ctx_last_window_scores
         ScanConfig sc = scan_config(*config, td.max_len, do_avg);
         sc.stream_base = gather.stream_base;
         if (!detect_scan(c, *config, f.dm, S, nf, td.K, sc, dg, da, q.hot, nullptr, f.dd, nullptr, f.dn, max_det)) return -1;
@@ -840,6 +853,7 @@ int rp_batch_detect_multi(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
         if (!c->ws_scores.reserve(rows * maxT * sizeof(float) + 16) || !c->ws_agg.reserve(n_wakewords * rows * sizeof(float) + 16) ||
             !c->ws_avg.reserve(n_wakewords * rows * sizeof(float) + 16)) return -1;
         float *ds = c->ws_scores.as<float>();
+        c->last_window_scores = 0;   // the wakewords share the buffer: no [S * n_win][T] block of one call is left in it
         for (size_t j = 0; j < n_wakewords; ++j) {
             const TemplatesDev &td = t[j]->impl->dev;
             const float thr = thresholds && !std::isnan(thresholds[j]) ? thresholds[j] : config->threshold;
@@ -956,6 +970,7 @@ int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc
         const float *dm = static_cast<const float *>(sg.in(mfcc, S * n_frames * (size_t)K * 4, c->stage_in));
         float *dl = static_cast<float *>(sg.out(logits, rows * (size_t)m.dims[nl] * 4, c->stage_out));
         if (!dm || !dl) return -1;
+        c->last_window_scores = 0;   // ws_scores serves the forward here
         if (!window_logits(c, m, dm, S, n_frames, n_win, L, K, precision, dl, c->ws_gain, c->ws_scores, c->ws_gain, false)) return -1;
         if (!sg.back(logits, dl, rows * (size_t)m.dims[nl] * 4) || !sg.finish()) return -1;
         return 0;
@@ -985,6 +1000,7 @@ int rp_batch_detect_model(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, si
         if (!c->ws_ring.reserve(rows * (size_t)n_labels * sizeof(float) + 16) || !c->ws_agg.reserve(rows * sizeof(float) + 16) ||
             !c->ws_avg.reserve(rows * sizeof(float) + 16) || !c->ws_rms.reserve(rows * sizeof(int32_t) + 16)) return -1;
         float *dlog = c->ws_ring.as<float>();
+        c->last_window_scores = 0;   // ws_scores serves the forward here
         if (!window_logits(c, m, f.dm, S, nf, n_win, L, K, precision, dlog, c->ws_gain, c->ws_scores, c->ws_gain, false)) return -1;
         float *dg = c->ws_agg.as<float>(), *da = c->ws_avg.as<float>();
         int32_t *dlab = c->ws_rms.as<int32_t>();

@@ -190,6 +190,9 @@ struct Ctx {
     DevBuf stage_in, stage_out, stage_out2, stage_out3;
     // intermediates of rp_batch_detect
     DevBuf ws_mfcc, ws_scores, ws_agg, ws_avg, ws_vad, ws_ring, ws_rms, ws_gain, ws_list, ws_hot;
+    // floats of ws_scores the last rp_batch_detect* wrote as its [S * n_win][T] score block (rp_ctx_last_window_scores); 0: none, the
+    // scores went to the caller's device array, or another call has used the workspace since
+    size_t last_window_scores = 0;
     DevBuf ws_bank_idx;  // the per-stream wakeword indices of a bank call with RP_CTX_HOST_POINTERS
     DevBuf ws_gain_tab;  // rp_frontend_batch_bank_sets / _model_bank: the per-stream table of gain_targets_kernel
     DevBuf ws_set_ww, ws_set_agg, ws_set_avg;  // wakeword-set calls: the proposals' bank indices [S][n_win]; the per-slot rows of a call with host pointers

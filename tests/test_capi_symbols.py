@@ -23,6 +23,8 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(L, name), name
     assert b"gfx950" in L.rp_version()
+    # the diagnostics read-back of a detect-only call's score workspace: declared, exported, and refused without a context
+    assert "rp_ctx_last_window_scores" in declared and L.rp_ctx_last_window_scores(None, None, 0) == -1
 
 
 def test_default_config_matches_reference_constants():

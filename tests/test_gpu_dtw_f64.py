@@ -11,6 +11,7 @@ operands) run through the same measurement; their ratios are printed and bounded
 import numpy as np
 import pytest
 
+from abandon_ref import f64_scores   # the f64 restatement (tests/abandon_ref.py; pinned on the CPU in tests/test_abandon_ref.py)
 from oracle import rp_oracle as orc
 
 SEED = 0x5EED000000000001
@@ -21,38 +22,6 @@ K, T, L, BAND, SCORE_REF = 5, 8, 100, 5, 0.22
 def ra():
     import rustpotter_amd
     return rustpotter_amd
-
-
-def f64_scores(mfcc, templates, band=BAND, score_ref=SCORE_REF):
-    """Score[w][t] in double precision from the f32 frames and f32 templates (the reference's inputs), every window at once.
-    Rows = template frames (first sequence), columns = window frames; row r meets columns max(1, r - w) .. min(n, r + w - 1);
-    the result is D[m-1][n] of the (m+1) x (n+1) matrix (dtw.rs:56-105)."""
-    x = np.asarray(mfcc, np.float64)
-    nf = x.shape[0]
-    out = []
-    for tpl in templates:
-        a = np.asarray(tpl, np.float64)
-        m = n = a.shape[0]
-        n_win = nf - m + 1
-        idx = np.arange(n_win)[:, None] + np.arange(n)[None, :]
-        win = x[idx]                                        # [n_win][n][K]
-        win = win - win.sum(axis=1, keepdims=True) / n      # MfccNormalizer::normalize of the cut window
-        na = (a * a).sum(axis=1)                            # [m]
-        nb = (win * win).sum(axis=2)                        # [n_win][n]
-        w = max(band, 0)
-        D = np.full((n_win, m + 1, n + 1), np.inf)
-        D[:, 0, 0] = 0.0
-        for r in range(1, m + 1):
-            lo = max(1, r - w) if r > w else 1
-            hi = min(n + 1, r + w)
-            for c in range(lo, hi):
-                mag = np.sqrt(na[r - 1] * nb[:, c - 1])
-                dot = win[:, c - 1, :] @ a[r - 1]
-                cos = np.where(mag == 0.0, 0.0, dot / np.where(mag == 0.0, 1.0, mag))
-                D[:, r, c] = (1.0 - cos) + np.minimum(np.minimum(D[:, r - 1, c], D[:, r, c - 1]), D[:, r - 1, c - 1])
-        nc = D[:, m - 1, n] / (m + n)
-        out.append(1.0 / (1.0 + np.exp((nc - score_ref) / score_ref)))
-    return np.stack(out, axis=1)
 
 
 @pytest.fixture(scope="module")

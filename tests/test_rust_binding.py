@@ -225,6 +225,7 @@ def test_wrapper_keeps_the_reference_signatures():
         # the operator seam
         "pub fn mfcc_batch(&self, pcm: &[f32], n_streams: usize, n_samples: usize, mfcc_size: u16) -> Result<Vec<f32>, String>",
         "pub fn dtw_score_batch(&self, mfcc: &[f32], n_streams: usize, n_frames: usize, t: &Templates, score_ref: f32, band_size: u16, score_mode: ScoreMode, with_avg: bool) -> Result<WindowScores, String>",
+        "pub fn last_window_scores(&self, n_streams: usize, n_win: usize, n_templates: usize) -> Result<Vec<f32>, String>",
         "pub fn mlp_forward_batch(&self, m: &Model, x: &[f32], rows: usize, bf16: bool) -> Result<Vec<f32>, String>",
     ):
         assert sig in src, sig
