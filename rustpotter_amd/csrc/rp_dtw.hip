@@ -1,7 +1,11 @@
 // rp_dtw.hip -- window scoring: dtw_band_kernel / dtw_band_wide_kernel / dtw_generic_kernel
 // (src/mfcc/dtw.rs:56-105 + comparator.rs + normalizer.rs + wakeword_comp.rs:22-27; one lane per window, band and ring
 // in registers) and aggregate_kernel (src/wakewords/comp/wakeword_comp.rs:38-49,108-139).  DESIGN.md §4.2.
+// The three register kernels share their per-lane walk -- lane -> window maps, column means, ring column load, the wide row sweep, the
+// averaged-template guard and the score epilogue -- with each other and with bank_dtw through rp_dtw_lane.h; here each keeps its own tile
+// shape, band layout, row body and abandon check.
 #include "rp_device.h"
+#include "rp_dtw_lane.h"
 #include "rp_host.h"
 
 #include <cmath>
@@ -19,7 +23,6 @@ namespace rp {
 // to unit length here, so a cell costs K fused multiply-adds instead of three dot
 // products, a sqrt and a divide (comparator.rs:28-48); zero vectors stay zero, which
 // reproduces the reference's "magnitude == 0 -> similarity 0".
-constexpr int kDtwWin = 64;   // windows per wave
 
 // One wave = 64 consecutive windows of one stream x one chunk of TC same-length templates.
 // Per lane: the window's column means, a ring of the 2W unit-length window frames inside the
@@ -49,110 +52,21 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_kernel(
     const int lane = threadIdx.x;
     const DtwChunk *ch = chunks + chunk_base + ci;
     const int L = ch->len;  // m == n == L
-    // Lane -> (stream, window).  flat != 0: the 64 lanes are consecutive entries of the flattened
-    // (stream, window) space, so a wave may straddle two streams (needs n_win >= 64) and no lane is
-    // wasted on a ragged last tile; flat == 0: tiles never cross a stream.
     size_t s;
     int w;
     bool valid;
     const float *xl;
     if (GX) {
         static_assert(!GX || KP == K, "global-memory frames have pitch K");
-        size_t f = (size_t)tile * kDtwWin + lane;
-        if (gl.list) {
-            // the windows that passed the averaged-template gate (gate_compact_kernel): row ids s * n_win + w.  The grid is
-            // sized for every window; tiles past the list's end have nothing to do.
-            const uint32_t n_listed = *gl.count;
-            if ((size_t)tile * kDtwWin >= n_listed || (gl.dense_min && n_listed >= gl.dense_min)) return;
-            valid = f < n_listed;
-            f = gl.list[valid ? f : n_listed - 1];
-        } else {
-            if (gl.count && *gl.count < gl.dense_min) return;
-            valid = f < n_streams * n_win;
-        }
-        s = valid ? f / n_win : 0;
-        w = valid ? (int)(f - s * n_win) : 0;
-        xl = mfcc + (s * frame_pitch + first_win + (size_t)w) * K;
+        RP_DTW_GLOBAL_ENTRY(kDtwWin, (size_t)tile * kDtwWin + lane, s, w, valid, xl);
     } else {
         if (gl.count && *gl.count < gl.dense_min) return;  // DENSE mode of the gate: only when (nearly) every window passed
-        size_t sA, sB = 0;
-        int wA, nA, nB = 0;
-        if (flat) {
-            const size_t f0 = (size_t)tile * kDtwWin;  // here `tiles` counts flattened tiles and there is no stream index
-            sA = f0 / n_win;
-            wA = (int)(f0 - sA * n_win);
-            nA = (int)n_win - wA < kDtwWin ? (int)n_win - wA : kDtwWin;
-            if (nA < kDtwWin && sA + 1 < n_streams) { sB = sA + 1; nB = kDtwWin - nA; }
-        } else {
-            sA = blockIdx.x / ((size_t)tiles * n_chunks);
-            wA = (int)tile * kDtwWin;
-            nA = (int)n_win - wA < kDtwWin ? (int)n_win - wA : kDtwWin;
-        }
-        const int segA = nA + L + W;  // frames staged for the first stream segment
-        {
-            const float *src = mfcc + sA * frame_pitch * K;
-            const size_t g0 = first_win + wA;
-            for (int i = lane; i < segA * K; i += kDtwWin) {
-                int f = i / K, k = i - f * K;
-                size_t g = g0 + f;
-                xs[f * KP + k] = g < n_frames_total ? src[g * K + k] : 0.f;
-            }
-        }
-        if (nB > 0) {
-            const float *src = mfcc + sB * frame_pitch * K;
-            const int segB = nB + L + W;
-            for (int i = lane; i < segB * K; i += kDtwWin) {
-                int f = i / K, k = i - f * K;
-                size_t g = first_win + f;
-                xs[(segA + f) * KP + k] = g < n_frames_total ? src[g * K + k] : 0.f;
-            }
-        }
-        __syncthreads();
-        const bool inA = lane < nA;
-        valid = inA || (lane - nA < nB);
-        s = inA ? sA : sB;
-        w = inA ? wA + lane : lane - nA;
-        xl = xs + (inA ? lane : (valid ? segA + lane - nA : 0)) * KP;
+        RP_DTW_STAGE_SEGMENTS(kDtwWin);
+        RP_DTW_STAGED_ENTRY(lane, s, w, valid, xl);
     }
-    // MfccNormalizer::normalize, src/mfcc/normalizer.rs:17-29: sequential column sums
-    float mu[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = 0.f;
-#ifndef RP_DTW_MEAN_UNROLL  // frames in flight per wait: left rolled, every frame of a window paid a whole LDS / memory round trip
-#define RP_DTW_MEAN_UNROLL 10
-#endif
-#pragma unroll RP_DTW_MEAN_UNROLL
-    for (int i = 0; i < L; ++i) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) mu[k] += xl[i * KP + k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = mu[k] / (float)L;
+    RP_DTW_COL_MEANS();
 
-    v2f ring[B / 2][K];  // ring[j][k] = { y_slot(2j)[k], y_slot(2j+1)[k] }
-#pragma unroll
-    for (int j = 0; j < B / 2; ++j)
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring[j][k] = (v2f){0.f, 0.f};
-
-    float chk = 0.f;  // max over the frames seen of (squared norm, its reciprocal square root): > kDtwFixLimit -> listed for dtw_ref_kernel
-#define RP_LOAD_COL(c, slot)                                                              \
-    do {                                                                                  \
-        float y_[K], bb_ = 0.f;                                                           \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
-            y_[k] = xl[((c)-1) * KP + k] - mu[k];                                         \
-            bb_ = fmaf(y_[k], y_[k], bb_);                                                \
-        }                                                                                 \
-        const float inv_ = bb_ > 0.f ? rsqrtf(bb_) : 0.f;                                 \
-        chk = fmaxf(fmaxf(chk, inv_), bb_); /* one v_max3_f32: the norm-range test */     \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
-            if (((slot)&1) == 0) ring[(slot) / 2][k].x = y_[k] * inv_;                    \
-            else ring[(slot) / 2][k].y = y_[k] * inv_;                                    \
-        }                                                                                 \
-    } while (0)
-
-#pragma unroll
-    for (int c = 1; c < W; ++c) RP_LOAD_COL(c, c % B);
+    RP_DTW_RING_START();  // ring, chk
 
     // P[tp][q] = D[r-1][(r-1-W)+q] of templates (2tp, 2tp+1); row 0 has D[0][0] = 0 at q = W
     v2f P[TC / 2][B + 1];
@@ -164,39 +78,25 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_kernel(
     }
 
     const float *rows = dup + ch->rows_off;
-#define RP_ROWS(GUARD)                                                                                 \
-    _Pragma("unroll") for (int u = 0; u < B; ++u) {                                                    \
-        const int r = r0 + u;                                                                          \
-        if (r < L) { /* rows 1..m-1 only: row m is never read (dtw.rs:101) */                          \
-            RP_LOAD_COL(r + W - 1, (u + W) % B);                                                       \
-            _Pragma("unroll") for (int t = 0; t < TC / 2; ++t) {                                       \
-                /* coefficients of the template pair, interleaved (t0,t1) per k: one scalar pair */    \
-                const v2f *arow = reinterpret_cast<const v2f *>(rows + ((size_t)(r - 1) * (TC / 2) + t) * K * 2); \
-                v2f a2[K];                                                                             \
-                _Pragma("unroll") for (int k = 0; k < K; ++k) a2[k] = arow[k];                         \
-                /* costs of the 2W band cells first (independent FMA chains), then the serial min chain */ \
-                v2f d[B];                                                                              \
-                _Pragma("unroll") for (int q = 0; q < B; ++q) d[q] = (v2f){1.f, 1.f};                  \
-                _Pragma("unroll") for (int k = 0; k < K; ++k) {                                        \
-                    _Pragma("unroll") for (int q = 0; q < B; ++q) {                                    \
-                        const int slot = (1 + u + q + B - W) % B;                                      \
-                        const v2f yy = (slot & 1) ? ring[slot / 2][k].yy : ring[slot / 2][k].xx;       \
-                        d[q] = __builtin_elementwise_fma(-a2[k], yy, d[q]);                            \
-                    }                                                                                  \
-                }                                                                                      \
-                v2f left = (v2f){RP_INF, RP_INF};                                                      \
-                _Pragma("unroll") for (int q = 0; q < B; ++q) {                                        \
-                    v2f m;                                                                             \
-                    m.x = fminf(fminf(P[t][q + 1].x, left.x), P[t][q].x);                              \
-                    m.y = fminf(fminf(P[t][q + 1].y, left.y), P[t][q].y);                              \
-                    v2f v = d[q] + m;                                                                  \
-                    if (GUARD) v = (r - W + q >= 1) ? v : (v2f){RP_INF, RP_INF};                       \
-                    P[t][q] = v;                                                                       \
-                    left = v;                                                                          \
-                }                                                                                      \
+    // row r of every template pair: the pair's coefficients interleaved (t0, t1) per k, one scalar pair; the costs of the 2W band cells first
+    // (independent FMA chains, the window component broadcast to both templates), then the serial min chain
+#define RP_PAIR_ROWS(GUARD)                                                                            \
+    _Pragma("unroll") for (int t = 0; t < TC / 2; ++t) {                                               \
+        const v2f *arow = reinterpret_cast<const v2f *>(rows + ((size_t)(r - 1) * (TC / 2) + t) * K * 2); \
+        v2f a2[K];                                                                                     \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) a2[k] = arow[k];                                 \
+        v2f d[B];                                                                                      \
+        _Pragma("unroll") for (int q = 0; q < B; ++q) d[q] = (v2f){1.f, 1.f};                          \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                                \
+            _Pragma("unroll") for (int q = 0; q < B; ++q) {                                            \
+                const int slot = (1 + u + q + B - W) % B;                                              \
+                const v2f yy = (slot & 1) ? ring[slot / 2][k].yy : ring[slot / 2][k].xx;               \
+                d[q] = __builtin_elementwise_fma(-a2[k], yy, d[q]);                                    \
             }                                                                                          \
         }                                                                                              \
+        RP_DTW_MIN_CHAIN2(GUARD, d, P[t]);                                                             \
     }
+#define RP_ROWS(GUARD) RP_DTW_ROW_BLOCK(RP_DTW_LOAD_COL, RP_PAIR_ROWS(GUARD))
 
     {
         const int r0 = 1;
@@ -211,17 +111,17 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_kernel(
                 v2f m = P[t][0];
 #pragma unroll
                 for (int q = 1; q < B; ++q) m = (v2f){fminf(m.x, P[t][q].x), fminf(m.y, P[t][q].y)};
-                // the averaged template (tid == T) is never abandoned: its score is reported and gates (as in the band2 / wide
-                // kernels); Templates::create keeps it out of this kernel's chunks today, this guard keeps that an optimisation
-                alive = alive || (2 * t < ch->count && (m.x <= abandon_cost || ch->tid[2 * t] >= T)) ||
-                        (2 * t + 1 < ch->count && (m.y <= abandon_cost || ch->tid[2 * t + 1] >= T));
+                // asked of each template: Templates::create keeps the averaged one out of this kernel's chunks today, the guard keeps
+                // that an optimisation
+                alive = alive || (2 * t < ch->count && (m.x <= abandon_cost || dtw_is_averaged(ch, 2 * t, T))) ||
+                        (2 * t + 1 < ch->count && (m.y <= abandon_cost || dtw_is_averaged(ch, 2 * t + 1, T)));
             }
             if (!__any(alive && valid)) {
                 if (valid) {
                     const size_t row = s * out_win_pitch + (size_t)w;
                     for (int t = 0; t < ch->count; ++t)
-                        if (ch->tid[t] < T) scores[row * T + ch->tid[t]] = 0.f;
-                    if (chk > kDtwFixLimit) dtw_fix_append(gl.fix, row, (uint32_t)(chunk_base + (int)ci));
+                        if (!dtw_is_averaged(ch, t, T)) scores[row * T + ch->tid[t]] = 0.f;
+                    RP_DTW_LIST_IF_OUT_OF_RANGE(chk, row);
                 }
                 return;
             }
@@ -229,23 +129,16 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_kernel(
         RP_ROWS(false)
     }
 #undef RP_ROWS
-#undef RP_LOAD_COL
+#undef RP_PAIR_ROWS
 
     if (valid) {
         const size_t row = s * out_win_pitch + (size_t)w;
         const float denom = (float)(L + L);
 #pragma unroll
         for (int t = 0; t < TC; ++t) {
-            if (t < ch->count) {
-                const float cost = (t & 1) ? P[t / 2][W + 1].y : P[t / 2][W + 1].x;  // D[m-1][n] for m == n
-                const float nc = cost / denom;
-                const float sc = dtw_logistic(nc, score_ref);
-                const int tid = ch->tid[t];
-                if (tid < T) scores[row * T + tid] = sc;
-                else avg[row] = sc;
-            }
+            if (t < ch->count) RP_DTW_STORE_SCORE((t & 1) ? P[t / 2][W + 1].y : P[t / 2][W + 1].x, ch->tid[t], row);  // D[m-1][n] for m == n
         }
-        if (chk > kDtwFixLimit) dtw_fix_append(gl.fix, row, (uint32_t)(chunk_base + (int)ci));
+        RP_DTW_LIST_IF_OUT_OF_RANGE(chk, row);
     }
 }
 
@@ -277,6 +170,8 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
     const float *xl[2];
     if (GX) {
         static_assert(!GX || KP == K, "global-memory frames have pitch K");
+        // RP_DTW_GLOBAL_ENTRY for two entries, with the leave tests taken once in front: spelled out, because the macro expanded twice
+        // compiles to another prologue (and another register allocation) in the four builds of this branch
         unsigned n_listed = 0;
         if (gl.list) {
             n_listed = *gl.count;
@@ -297,62 +192,15 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
         }
     } else {
         if (gl.count && *gl.count < gl.dense_min) return;
-        size_t sA, sB = 0;
-        int wA, nA, nB = 0;
-        if (flat) {
-            const size_t f0 = (size_t)tile * NW;
-            sA = f0 / n_win;
-            wA = (int)(f0 - sA * n_win);
-            nA = (int)n_win - wA < NW ? (int)n_win - wA : NW;
-            if (nA < NW && sA + 1 < n_streams) { sB = sA + 1; nB = NW - nA; }
-        } else {
-            sA = blockIdx.x / ((size_t)tiles * n_chunks);
-            wA = (int)tile * NW;
-            nA = (int)n_win - wA < NW ? (int)n_win - wA : NW;
-        }
-        const int segA = nA + L + W;
-        {
-            const float *src = mfcc + sA * frame_pitch * K;
-            const size_t g0 = first_win + wA;
-            for (int i = lane; i < segA * K; i += kDtwWin) {
-                int f = i / K, k = i - f * K;
-                size_t g = g0 + f;
-                xs[f * KP + k] = g < n_frames_total ? src[g * K + k] : 0.f;
-            }
-        }
-        if (nB > 0) {
-            const float *src = mfcc + sB * frame_pitch * K;
-            const int segB = nB + L + W;
-            for (int i = lane; i < segB * K; i += kDtwWin) {
-                int f = i / K, k = i - f * K;
-                size_t g = first_win + f;
-                xs[(segA + f) * KP + k] = g < n_frames_total ? src[g * K + k] : 0.f;
-            }
-        }
-        __syncthreads();
+        RP_DTW_STAGE_SEGMENTS(NW);
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const int ent = e * kDtwWin + lane;
-            const bool inA = ent < nA;
-            valid[e] = inA || (ent - nA < nB);
-            s[e] = inA ? sA : sB;
-            w[e] = inA ? wA + ent : ent - nA;
-            xl[e] = xs + (inA ? ent : (valid[e] ? segA + ent - nA : 0)) * KP;
+            RP_DTW_STAGED_ENTRY(ent, s[e], w[e], valid[e], xl[e]);
         }
     }
     const float *x0 = xl[0], *x1 = xl[1];
-    // MfccNormalizer::normalize: sequential column sums, both windows at once
-    v2f mu[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = (v2f){0.f, 0.f};
-#pragma unroll RP_DTW_MEAN_UNROLL
-    for (int i = 0; i < L; ++i) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) mu[k] += (v2f){x0[i * KP + k], x1[i * KP + k]};
-    }
-    const float fl = (float)L;
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = (v2f){mu[k].x / fl, mu[k].y / fl};
+    RP_DTW_COL_MEANS2();
 
     v2f ring[B][K];  // ring[slot][k] = unit-length frame of the slot, (window 0, window 1)
 #pragma unroll
@@ -360,21 +208,9 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
 #pragma unroll
         for (int k = 0; k < K; ++k) ring[j][k] = (v2f){0.f, 0.f};
 
-    v2f chk = (v2f){0.f, 0.f};  // the norm-range test of the two windows (see dtw_band_kernel)
-#define RP_LOAD_COL2(c, slot)                                                                       \
-    do {                                                                                            \
-        v2f y_[K], bb_ = (v2f){0.f, 0.f};                                                           \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                             \
-            y_[k] = (v2f){x0[((c)-1) * KP + k], x1[((c)-1) * KP + k]} - mu[k];                      \
-            bb_ = __builtin_elementwise_fma(y_[k], y_[k], bb_);                                     \
-        }                                                                                           \
-        const v2f inv_ = (v2f){bb_.x > 0.f ? rsqrtf(bb_.x) : 0.f, bb_.y > 0.f ? rsqrtf(bb_.y) : 0.f}; \
-        chk.x = fmaxf(fmaxf(chk.x, inv_.x), bb_.x); chk.y = fmaxf(fmaxf(chk.y, inv_.y), bb_.y);     \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) ring[slot][k] = y_[k] * inv_;                 \
-    } while (0)
-
+    v2f chk = (v2f){0.f, 0.f};  // the norm-range test of the two windows (RP_DTW_LOAD_COL2)
 #pragma unroll
-    for (int c = 1; c < W; ++c) RP_LOAD_COL2(c, c % B);
+    for (int c = 1; c < W; ++c) RP_DTW_LOAD_COL2(c, c % B);
 
     v2f P[B + 1];
 #pragma unroll
@@ -382,32 +218,19 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
     P[W] = (v2f){0.f, 0.f};
 
     const float *rows = dup + ch->rows_off;  // [len][1][K][2]: the template's coefficients (stored twice)
-#define RP_ROWS2(GUARD)                                                                                \
-    _Pragma("unroll") for (int u = 0; u < B; ++u) {                                                    \
-        const int r = r0 + u;                                                                          \
-        if (r < L) {                                                                                   \
-            RP_LOAD_COL2(r + W - 1, (u + W) % B);                                                      \
-            const float *arow = rows + (size_t)(r - 1) * K * 2;                                        \
-            v2f d[B];                                                                                  \
-            _Pragma("unroll") for (int q = 0; q < B; ++q) d[q] = (v2f){1.f, 1.f};                      \
-            _Pragma("unroll") for (int k = 0; k < K; ++k) {                                            \
-                const float a = arow[2 * k];                                                           \
-                const v2f na = (v2f){-a, -a};                                                          \
-                _Pragma("unroll") for (int q = 0; q < B; ++q)                                          \
-                    d[q] = __builtin_elementwise_fma(na, ring[(1 + u + q + B - W) % B][k], d[q]);      \
-            }                                                                                          \
-            v2f left = (v2f){RP_INF, RP_INF};                                                          \
-            _Pragma("unroll") for (int q = 0; q < B; ++q) {                                            \
-                v2f m;                                                                                 \
-                m.x = fminf(fminf(P[q + 1].x, left.x), P[q].x);                                        \
-                m.y = fminf(fminf(P[q + 1].y, left.y), P[q].y);                                        \
-                v2f v = d[q] + m;                                                                      \
-                if (GUARD) v = (r - W + q >= 1) ? v : (v2f){RP_INF, RP_INF};                           \
-                P[q] = v;                                                                              \
-                left = v;                                                                              \
-            }                                                                                          \
-        }                                                                                              \
-    }
+    // row r: the template's coefficient broadcast to both windows
+#define RP_WINDOW_PAIR_ROW(GUARD)                                                                      \
+    const float *arow = rows + (size_t)(r - 1) * K * 2;                                                \
+    v2f d[B];                                                                                          \
+    _Pragma("unroll") for (int q = 0; q < B; ++q) d[q] = (v2f){1.f, 1.f};                              \
+    _Pragma("unroll") for (int k = 0; k < K; ++k) {                                                    \
+        const float a = arow[2 * k];                                                                   \
+        const v2f na = (v2f){-a, -a};                                                                  \
+        _Pragma("unroll") for (int q = 0; q < B; ++q)                                                  \
+            d[q] = __builtin_elementwise_fma(na, ring[(1 + u + q + B - W) % B][k], d[q]);              \
+    }                                                                                                  \
+    RP_DTW_MIN_CHAIN2(GUARD, d, P);
+#define RP_ROWS2(GUARD) RP_DTW_ROW_BLOCK(RP_DTW_LOAD_COL2, RP_WINDOW_PAIR_ROW(GUARD))
     {
         const int r0 = 1;
         RP_ROWS2(true)
@@ -415,7 +238,7 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
     const int tid = ch->tid[0];
     const float abandon_cost = gl.abandon_nc * (float)(L + L);
     for (int r0 = 1 + B; r0 < L; r0 += B) {
-        if (gl.abandon_nc < RP_INF && tid < T) {  // never for the averaged template: its score is reported and gates
+        if (gl.abandon_nc < RP_INF && !dtw_is_averaged(ch, 0, T)) {  // asked of the chunk: it is one template
             v2f m = P[0];
 #pragma unroll
             for (int q = 1; q < B; ++q) m = (v2f){fminf(m.x, P[q].x), fminf(m.y, P[q].y)};
@@ -425,7 +248,7 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
                 for (int e = 0; e < 2; ++e)
                     if (valid[e]) {
                         scores[(s[e] * out_win_pitch + (size_t)w[e]) * T + tid] = 0.f;
-                        if ((e ? chk.y : chk.x) > kDtwFixLimit) dtw_fix_append(gl.fix, s[e] * out_win_pitch + (size_t)w[e], (uint32_t)(chunk_base + (int)ci));
+                        RP_DTW_LIST_IF_OUT_OF_RANGE(e ? chk.y : chk.x, s[e] * out_win_pitch + (size_t)w[e]);
                     }
                 return;
             }
@@ -433,19 +256,15 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band2_kernel(
         RP_ROWS2(false)
     }
 #undef RP_ROWS2
-#undef RP_LOAD_COL2
+#undef RP_WINDOW_PAIR_ROW
 
     const float denom = (float)(L + L);
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         if (valid[e]) {
             const size_t row = s[e] * out_win_pitch + (size_t)w[e];
-            const float cost = e ? P[W + 1].y : P[W + 1].x;  // D[m-1][n] for m == n
-            const float nc = cost / denom;
-            const float sc = dtw_logistic(nc, score_ref);
-            if (tid < T) scores[row * T + tid] = sc;
-            else avg[row] = sc;
-            if ((e ? chk.y : chk.x) > kDtwFixLimit) dtw_fix_append(gl.fix, row, (uint32_t)(chunk_base + (int)ci));
+            RP_DTW_STORE_SCORE(e ? P[W + 1].y : P[W + 1].x, tid, row);  // D[m-1][n] for m == n
+            RP_DTW_LIST_IF_OUT_OF_RANGE(e ? chk.y : chk.x, row);
         }
     }
 }
@@ -476,21 +295,10 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_wide_kernel(
     bool valid;
     const float *xl;
     if (GX) {
-        // lanes are consecutive entries of the flattened (stream, window) space, or of the gate's list (see dtw_band_kernel)
-        size_t f = (size_t)tile * kDtwWin + lane;
-        if (gl.list) {
-            const uint32_t n_listed = *gl.count;
-            if ((size_t)tile * kDtwWin >= n_listed || (gl.dense_min && n_listed >= gl.dense_min)) return;
-            valid = f < n_listed;
-            f = gl.list[valid ? f : n_listed - 1];
-        } else {
-            if (gl.count && *gl.count < gl.dense_min) return;
-            valid = f < n_streams * n_win;
-        }
-        s = valid ? f / n_win : 0;
-        wl = valid ? f - s * n_win : 0;
-        xl = mfcc + (s * frame_pitch + first_win + wl) * K;
+        RP_DTW_GLOBAL_ENTRY(kDtwWin, (size_t)tile * kDtwWin + lane, s, wl, valid, xl);
     } else {
+        // one stream segment of a whole tile's 64 + L + W frames, never flat: not RP_DTW_STAGE_SEGMENTS (it stages n + L + W frames of up
+        // to two segments, which is another instruction stream)
         if (gl.count && *gl.count < gl.dense_min) return;
         s = blockIdx.x / ((size_t)tiles * n_chunks);
         const size_t w0 = first_win + (size_t)tile * kDtwWin;
@@ -506,45 +314,9 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_wide_kernel(
         valid = wl < n_win;
         xl = xs + lane * KP;
     }
-    // MfccNormalizer::normalize, src/mfcc/normalizer.rs:17-29: sequential column sums
-    float mu[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = 0.f;
-#ifndef RP_DTW_MEAN_UNROLL_WIDE  // 13 / 16 components per frame: four frames in flight keep the register count where it was
-#define RP_DTW_MEAN_UNROLL_WIDE 4
-#endif
-#pragma unroll RP_DTW_MEAN_UNROLL_WIDE
-    for (int i = 0; i < L; ++i) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) mu[k] += xl[i * KP + k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = mu[k] / (float)L;
+    RP_DTW_COL_MEANS();
 
-    v2f ring[B / 2][K];  // ring[j][k] = { y_slot(2j)[k], y_slot(2j+1)[k] }
-#pragma unroll
-    for (int j = 0; j < B / 2; ++j)
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring[j][k] = (v2f){0.f, 0.f};
-
-    float chk = 0.f;  // max over the frames seen of (squared norm, its reciprocal square root): > kDtwFixLimit -> listed for dtw_ref_kernel
-#define RP_LOAD_COL(c, slot)                                                              \
-    do {                                                                                  \
-        float y_[K], bb_ = 0.f;                                                           \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
-            y_[k] = xl[((c)-1) * KP + k] - mu[k];                                         \
-            bb_ = fmaf(y_[k], y_[k], bb_);                                                \
-        }                                                                                 \
-        const float inv_ = bb_ > 0.f ? rsqrtf(bb_) : 0.f;                                 \
-        chk = fmaxf(fmaxf(chk, inv_), bb_); /* one v_max3_f32: the norm-range test */     \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
-            if (((slot)&1) == 0) ring[(slot) / 2][k].x = y_[k] * inv_;                    \
-            else ring[(slot) / 2][k].y = y_[k] * inv_;                                    \
-        }                                                                                 \
-    } while (0)
-
-#pragma unroll
-    for (int c = 1; c < W; ++c) RP_LOAD_COL(c, c % B);
+    RP_DTW_RING_START();  // ring, chk
 
     // P[t][q] = D[r-1][(r-1-W)+q] of template t; row 0 has D[0][0] = 0 at q = W
     float P[TC][B + 1];
@@ -555,41 +327,18 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_wide_kernel(
         P[t][W] = 0.f;
     }
 
+    // template t's row: coefficient k of the pair (t / 2) at [2 k + (t & 1)] of the interleaved pair row
     const float *rows = dup + ch->rows_off;
-#define RP_ROWS(GUARD)                                                                                 \
-    _Pragma("unroll") for (int u = 0; u < B; ++u) {                                                    \
-        const int r = r0 + u;                                                                          \
-        if (r < L) { /* rows 1..m-1 only: row m is never read (dtw.rs:101) */                          \
-            RP_LOAD_COL(r + W - 1, (u + W) % B);                                                       \
-            _Pragma("unroll") for (int t = 0; t < TC; ++t) {                                           \
-                const float *arow = rows + ((size_t)(r - 1) * TP + t / 2) * K * 2 + (t & 1);           \
-                v2f dd[B / 2];                                                                         \
-                _Pragma("unroll") for (int j = 0; j < B / 2; ++j) dd[j] = (v2f){1.f, 1.f};             \
-                _Pragma("unroll") for (int k = 0; k < K; ++k) {                                        \
-                    const v2f a2 = (v2f){arow[2 * k], arow[2 * k]};                                   \
-                    _Pragma("unroll") for (int j = 0; j < B / 2; ++j)                                  \
-                        dd[j] = __builtin_elementwise_fma(-a2, ring[j][k], dd[j]);                     \
-                }                                                                                      \
-                float left = RP_INF;                                                                   \
-                _Pragma("unroll") for (int q = 0; q < B; ++q) {                                        \
-                    const int slot = (1 + u + q + B - W) % B;                                          \
-                    const float d = (slot & 1) ? dd[slot / 2].y : dd[slot / 2].x;                      \
-                    float v = d + fminf(fminf(P[t][q + 1], left), P[t][q]);                            \
-                    if (GUARD) v = (r - W + q >= 1) ? v : RP_INF;                                      \
-                    P[t][q] = v;                                                                       \
-                    left = v;                                                                          \
-                }                                                                                      \
-            }                                                                                          \
-        }                                                                                              \
-    }
-
+#define RP_ROWS(GUARD)                                            \
+    RP_DTW_ROW_BLOCK(RP_DTW_LOAD_COL, _Pragma("unroll") for (int t = 0; t < TC; ++t) \
+                     RP_DTW_WIDE_SWEEP(GUARD, rows + ((size_t)(r - 1) * TP + t / 2) * K * 2 + (t & 1), 2, P[t]))
     {
         const int r0 = 1;
         RP_ROWS(true)
     }
     const float abandon_cost = gl.abandon_nc * (float)(L + L);
     for (int r0 = 1 + B; r0 < L; r0 += B) {
-        if (gl.abandon_nc < RP_INF && ch->tid[0] < T) {
+        if (gl.abandon_nc < RP_INF && !dtw_is_averaged(ch, 0, T)) {  // asked of the chunk: the averaged template has one of its own
             bool alive = false;
 #pragma unroll
             for (int t = 0; t < TC; ++t) {
@@ -601,7 +350,7 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_wide_kernel(
             if (!__any(alive && valid)) {
                 if (valid) {
                     for (int t = 0; t < ch->count; ++t) scores[(s * out_win_pitch + wl) * T + ch->tid[t]] = 0.f;
-                    if (chk > kDtwFixLimit) dtw_fix_append(gl.fix, s * out_win_pitch + wl, (uint32_t)(chunk_base + (int)ci));
+                    RP_DTW_LIST_IF_OUT_OF_RANGE(chk, s * out_win_pitch + wl);
                 }
                 return;
             }
@@ -609,23 +358,15 @@ __global__ __launch_bounds__(kDtwWin) void dtw_band_wide_kernel(
         RP_ROWS(false)
     }
 #undef RP_ROWS
-#undef RP_LOAD_COL
 
     if (valid) {
         const size_t row = s * out_win_pitch + wl;
         const float denom = (float)(L + L);
 #pragma unroll
         for (int t = 0; t < TC; ++t) {
-            if (t < ch->count) {
-                const float cost = P[t][W + 1];  // D[m-1][n] for m == n
-                const float nc = cost / denom;
-                const float sc = dtw_logistic(nc, score_ref);
-                const int tid = ch->tid[t];
-                if (tid < T) scores[row * T + tid] = sc;
-                else avg[row] = sc;
-            }
+            if (t < ch->count) RP_DTW_STORE_SCORE(P[t][W + 1], ch->tid[t], row);  // D[m-1][n] for m == n
         }
-        if (chk > kDtwFixLimit) dtw_fix_append(gl.fix, row, (uint32_t)(chunk_base + (int)ci));
+        RP_DTW_LIST_IF_OUT_OF_RANGE(chk, row);
     }
 }
 
@@ -965,8 +706,6 @@ static hipError_t launch_dtw_wide_all(const DtwCall &c, int n1, bool few, const 
     return launch_dtw_wide<K, W, 2>(c, t.class_first[0], t.class_count[0], few, gl);
 }
 
-// Largest template tile the register kernels are built for at this (mfcc_size, band) (0 = only the generic
-// kernel applies).  Built: mfcc_size 5 with band 3..6 (tile 8), mfcc_size 13 and 16 with band 3..6 (tile 2).
 // ---- one DTW per wave, for a handful of windows (the single-stream API: three new windows per 30 ms chunk) -----
 // The register kernels above give every lane a whole DTW: with 3 windows x 5 templates that is 15 busy lanes walking
 // ~100 dependent rows each (35 us).  Here a workgroup of one wave owns ONE (window, template) pair: all 64 lanes
@@ -1087,6 +826,8 @@ __global__ __launch_bounds__(64) void dtw_single_kernel(
     }
 }
 
+// Largest template tile the register kernels are built for at this (mfcc_size, band) (0 = only the generic
+// kernel applies).  Built: mfcc_size 5 with band 3..6 (tile 8), mfcc_size 13 and 16 with band 3..6 (tile 2).
 int dtw_register_tile(int K, int band) {
     if (K == 5 && band >= 3 && band <= 6) return 8;
     if ((K == 13 || K == 16) && band >= 3 && band <= 6) return 2;

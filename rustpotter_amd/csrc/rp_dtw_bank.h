@@ -2,56 +2,21 @@
 // (a set of wakewords per stream): bank_dtw, bank_chk_window, bank_dtw_ref.  Device code only; include behind rp_device.h.
 #pragma once
 #include "rp_device.h"
+#include "rp_dtw_lane.h"
 
 namespace rp {
 
 // One DTW of the lane's window against one template of L rows (m == n == L: the window is cut to the template's length keeping the oldest
-// frames), with the arithmetic of the register kernels of rp_dtw.hip OPERATION FOR OPERATION -- sequential column sums / L, unit-length frame by
-// rsqrtf of the fma-chained squared norm, d = fmaf(-a[k], y[k], d) chained from 1, v = d + min3, cost / (m + n), dtw_logistic -- so that a
-// window gets the bits it gets from dtw_band_kernel / dtw_band2_kernel / dtw_band_wide_kernel.  The form is dtw_band_wide_kernel's with one
-// template: the ring of the 2W unit-length frames inside the band as register pairs, two band cells per packed FMA, the template row a
-// wave-uniform read (scalar loads), rows unrolled 2W at a time so that every ring slot and band index is a compile-time register.
-// chk: max over the frames loaded of (squared norm, its reciprocal square root) -- the norm-range test of those kernels, same columns.
+// frames), built from the pieces the register kernels of rp_dtw.hip are built from (rp_dtw_lane.h): their column means, their ring column
+// load, and dtw_band_wide_kernel's row sweep with one template -- two band cells per packed FMA, the template row a wave-uniform read
+// (scalar loads), here as plain rows [L][K].  So a window gets the bits it gets from dtw_band_kernel / dtw_band2_kernel /
+// dtw_band_wide_kernel (which differ in how many templates or windows share a packed instruction, not in a cell's operations) because it
+// runs their code.  chk: the norm-range test of those kernels, same columns.
 template <int K, int W, int KP>
 __device__ __forceinline__ float bank_dtw(const float *xl, int L, const float *__restrict__ rows, float score_ref, float &chk_out) {
     constexpr int B = 2 * W;
-    constexpr int MEAN_UNROLL = K <= 5 ? 10 : 4;   // frames in flight per wait, as the register kernels
-    // MfccNormalizer::normalize, src/mfcc/normalizer.rs:17-29: sequential column sums
-    float mu[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = 0.f;
-#pragma unroll MEAN_UNROLL
-    for (int i = 0; i < L; ++i) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) mu[k] += xl[i * KP + k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) mu[k] = mu[k] / (float)L;
-
-    v2f ring[B / 2][K];  // ring[j][k] = { y_slot(2j)[k], y_slot(2j+1)[k] }
-#pragma unroll
-    for (int j = 0; j < B / 2; ++j)
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring[j][k] = (v2f){0.f, 0.f};
-
-    float chk = 0.f;
-#define RP_LOAD_COL(c, slot)                                                              \
-    do {                                                                                  \
-        float y_[K], bb_ = 0.f;                                                           \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
-            y_[k] = xl[((c)-1) * KP + k] - mu[k];                                         \
-            bb_ = fmaf(y_[k], y_[k], bb_);                                                \
-        }                                                                                 \
-        const float inv_ = bb_ > 0.f ? rsqrtf(bb_) : 0.f;                                 \
-        chk = fmaxf(fmaxf(chk, inv_), bb_);                                               \
-        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                   \
-            if (((slot)&1) == 0) ring[(slot) / 2][k].x = y_[k] * inv_;                    \
-            else ring[(slot) / 2][k].y = y_[k] * inv_;                                    \
-        }                                                                                 \
-    } while (0)
-
-#pragma unroll
-    for (int c = 1; c < W; ++c) RP_LOAD_COL(c, c % B);
+    RP_DTW_COL_MEANS();   // mu
+    RP_DTW_RING_START();  // ring, chk
 
     // P[q] = D[r-1][(r-1-W)+q]; row 0 has D[0][0] = 0 at q = W
     float P[B + 1];
@@ -59,39 +24,13 @@ __device__ __forceinline__ float bank_dtw(const float *xl, int L, const float *_
     for (int q = 0; q <= B; ++q) P[q] = RP_INF;
     P[W] = 0.f;
 
-    // columns c > n are never read back by an in-range cell and stay unguarded, as in the register kernels (the stage holds W frames of slack)
-#define RP_ROWS(GUARD)                                                                                 \
-    _Pragma("unroll") for (int u = 0; u < B; ++u) {                                                    \
-        const int r = r0 + u;                                                                          \
-        if (r < L) { /* rows 1..m-1 only: row m is never read (dtw.rs:101) */                          \
-            RP_LOAD_COL(r + W - 1, (u + W) % B);                                                       \
-            const float *arow = rows + (size_t)(r - 1) * K;                                            \
-            v2f dd[B / 2];                                                                             \
-            _Pragma("unroll") for (int j = 0; j < B / 2; ++j) dd[j] = (v2f){1.f, 1.f};                 \
-            _Pragma("unroll") for (int k = 0; k < K; ++k) {                                            \
-                const v2f a2 = (v2f){arow[k], arow[k]};                                                \
-                _Pragma("unroll") for (int j = 0; j < B / 2; ++j)                                      \
-                    dd[j] = __builtin_elementwise_fma(-a2, ring[j][k], dd[j]);                         \
-            }                                                                                          \
-            float left = RP_INF;                                                                       \
-            _Pragma("unroll") for (int q = 0; q < B; ++q) {                                            \
-                const int slot = (1 + u + q + B - W) % B;                                              \
-                const float d = (slot & 1) ? dd[slot / 2].y : dd[slot / 2].x;                          \
-                float v = d + fminf(fminf(P[q + 1], left), P[q]);                                      \
-                if (GUARD) v = (r - W + q >= 1) ? v : RP_INF;                                          \
-                P[q] = v;                                                                              \
-                left = v;                                                                              \
-            }                                                                                          \
-        }                                                                                              \
-    }
-
+#define RP_ROWS(GUARD) RP_DTW_ROW_BLOCK(RP_DTW_LOAD_COL, RP_DTW_WIDE_SWEEP(GUARD, rows + (size_t)(r - 1) * K, 1, P))
     {
         const int r0 = 1;
         RP_ROWS(true)
     }
     for (int r0 = 1 + B; r0 < L; r0 += B) { RP_ROWS(false) }
 #undef RP_ROWS
-#undef RP_LOAD_COL
     chk_out = chk;
     return dtw_logistic(P[W + 1] / (float)(L + L), score_ref);   // D[m-1][n] for m == n
 }
