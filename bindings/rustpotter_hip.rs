@@ -79,6 +79,7 @@ pub const RP_DTW_KERNEL_BANK: c_int = 4096;
 pub const RP_DTW_KERNEL_BANK_STREAM: c_int = 8192;
 pub const RP_DTW_KERNEL_BANK_SETS: c_int = 16384;
 pub const RP_DTW_KERNEL_BANK_SETS_STREAM: c_int = 32768;
+pub const RP_DTW_KERNEL_MIXED_SETS_STREAM: c_int = 65536;
 /// wakewords a stream's set may hold (`stream_wakewords [S][set_size]`)
 pub const RP_WAKEWORD_SET_MAX: c_int = 8;
 pub const RP_MODEL_SET_MAX: c_int = 8;
@@ -321,6 +322,20 @@ extern "C" {
                                         filters: *const rp_filters_config, bank: *const rp_model_bank, stream_models: *const i32,
                                         set_size: c_int, pcm_out: *mut f32, out_stride: usize, rms: *mut f32, gains: *mut f32) -> c_int;
     pub fn rp_stream_batch_set_filters_per_stream(b: *mut rp_stream_batch, filters: *const rp_filters_config) -> c_int;
+    pub fn rp_batch_detect_mixed_sets(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                      bank: *const rp_wakeword_bank, stream_wakewords: *const i32, ref_set_size: c_int,
+                                      model_bank: *const rp_model_bank, stream_models: *const i32, model_set_size: c_int,
+                                      config: *const rp_detector_config, precision: c_int, det: *mut rp_batch_detection, det_wakeword: *mut i32,
+                                      det_label: *mut i32, n_det: *mut i32, max_det: c_int) -> c_int;
+    pub fn rp_stream_batch_new_mixed_sets(ctx: *mut rp_ctx, bank: *const rp_wakeword_bank, stream_wakewords: *const i32, ref_set_size: c_int,
+                                          model_bank: *const rp_model_bank, stream_models: *const i32, model_set_size: c_int,
+                                          config: *const rp_detector_config, S: usize, max_chunks_per_call: usize, out: *mut *mut rp_stream_batch) -> c_int;
+    pub fn rp_stream_batch_set_mixed_sets(b: *mut rp_stream_batch, first_stream: usize, n: usize, stream_wakewords: *const i32,
+                                          stream_models: *const i32) -> c_int;
+    pub fn rp_frontend_batch_mixed_sets(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
+                                        filters: *const rp_filters_config, bank: *const rp_wakeword_bank, stream_wakewords: *const i32,
+                                        ref_set_size: c_int, model_bank: *const rp_model_bank, stream_models: *const i32, model_set_size: c_int,
+                                        pcm_out: *mut f32, out_stride: usize, rms: *mut f32, gains: *mut f32) -> c_int;
     pub fn rp_mlp_forward_windows_bank(ctx: *mut rp_ctx, bank: *const rp_model_bank, stream_model: *const i32, mfcc: *const f32, S: usize,
                                        n_frames: usize, precision: c_int, logits: *mut f32, win_pitch: usize) -> c_int;
     pub fn rp_batch_detect_model_bank(ctx: *mut rp_ctx, pcm: *const c_void, fmt: c_int, S: usize, n_samples: usize, pcm_stride: usize,
@@ -1037,6 +1052,49 @@ impl HipContext {
         let (w, l) = (cut(&which), cut(&label));
         Ok((split_detections(det, n_det, max_det), w, l))
     }
+    /// One detector per stream that holds wakeword references AND wakeword models: `stream_wakewords[s * ref_set_size ..][..ref_set_size]`
+    /// indexes `bank`, `stream_models[s * model_set_size ..][..model_set_size]` indexes `model_bank` (-1: an empty slot; a size of 0: the
+    /// side is absent), as a `Rustpotter` with `add_wakeword_ref` for the live reference slots, then `add_wakeword_model` for the live
+    /// model slots.  Returns detections, each winner's index in its own bank, and its label (-1: a reference won).
+    pub fn batch_detect_mixed_sets(&self, pcm: &[f32], n_streams: usize, n_samples: usize, bank: &WakewordBank, stream_wakewords: &[i32],
+                                   ref_set_size: usize, model_bank: &ModelBank, stream_models: &[i32], model_set_size: usize,
+                                   config: &DetectorConfig, max_det: usize) -> Result<(Detections, Vec<Vec<i32>>, Vec<Vec<i32>>), String> {
+        assert!(ref_set_size <= RP_WAKEWORD_SET_MAX as usize && model_set_size <= RP_MODEL_SET_MAX as usize && pcm.len() >= n_streams * n_samples);
+        assert!(stream_wakewords.len() == n_streams * ref_set_size && stream_models.len() == n_streams * model_set_size);
+        let c: rp_detector_config = config.into();
+        let mut det = vec![rp_batch_detection::default(); n_streams * max_det];
+        let (mut which, mut label) = (vec![0i32; n_streams * max_det], vec![0i32; n_streams * max_det]);
+        let mut n_det = vec![0i32; n_streams];
+        let rows = |v: &[i32]| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+        status(unsafe {
+            rp_batch_detect_mixed_sets(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, bank.h,
+                                       rows(stream_wakewords), ref_set_size as c_int, model_bank.h, rows(stream_models), model_set_size as c_int, &c,
+                                       RP_MLP_F32, det.as_mut_ptr(), which.as_mut_ptr(), label.as_mut_ptr(), n_det.as_mut_ptr(), max_det as c_int)
+        })?;
+        let cut = |v: &Vec<i32>| -> Vec<Vec<i32>> {
+            (0..n_streams).map(|s| v[s * max_det..s * max_det + (n_det[s].max(0) as usize).min(max_det)].to_vec()).collect()
+        };
+        let (w, l) = (cut(&which), cut(&label));
+        Ok((split_detections(det, n_det, max_det), w, l))
+    }
+    /// `frontend_batch_bank_sets` in front of `batch_detect_mixed_sets`: stream `s` works towards the largest non-NaN `rms_level` over the
+    /// live slots of both rows over `max(Lmax(s) / 3, 1)` chunk levels
+    pub fn frontend_batch_mixed_sets(&self, pcm: &[f32], n_streams: usize, n_samples: usize, filters: &FiltersConfig, bank: &WakewordBank,
+                                     stream_wakewords: &[i32], ref_set_size: usize, model_bank: &ModelBank, stream_models: &[i32],
+                                     model_set_size: usize) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>), String> {
+        assert!(stream_wakewords.len() == n_streams * ref_set_size && stream_models.len() == n_streams * model_set_size);
+        assert!(pcm.len() >= n_streams * n_samples);
+        let f: rp_filters_config = filters.into();
+        let nch = n_samples / 480;
+        let (mut out, mut rms, mut gains) = (vec![0f32; n_streams * n_samples], vec![0f32; n_streams * nch], vec![0f32; n_streams * nch]);
+        let rows = |v: &[i32]| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+        status(unsafe {
+            rp_frontend_batch_mixed_sets(self.h, pcm.as_ptr() as *const c_void, RP_SAMPLE_F32, n_streams, n_samples, n_samples, &f, bank.h,
+                                         rows(stream_wakewords), ref_set_size as c_int, model_bank.h, rows(stream_models), model_set_size as c_int,
+                                         out.as_mut_ptr(), n_samples, rms.as_mut_ptr(), gains.as_mut_ptr())
+        })?;
+        Ok((out, rms, gains))
+    }
     /// The audio front-end of `Rustpotter::process_audio` (gain normaliser + band-pass, src/detector.rs:358-371) for whole streams:
     /// returns (filtered audio, per-chunk rms levels, per-chunk gains).
     pub fn frontend_batch(&self, pcm: &[f32], n_streams: usize, n_samples: usize, filters: &FiltersConfig, rms_level_ref: f32,
@@ -1134,7 +1192,9 @@ pub struct StreamBatch<'a> { h: *mut rp_stream_batch, n_streams: usize, last_chu
                             /// wakewords per stream of a `new_bank_sets` batch, 0 for every other batch; MFCC frames a stream gains per chunk (3, or 4 with 40 ms input frames)
                             set_size: usize, frames_per_chunk: usize,
                             /// label pitch of the bank of a `new_model_bank` batch, 0 for every other batch
-                            label_pitch: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
+                            label_pitch: usize,
+                            /// model slots per stream of a `new_mixed_sets` batch (its `set_size` counts the reference slots), 0 for every other batch
+                            model_set_size: usize, _ctx: &'a HipContext, _t: std::marker::PhantomData<&'a Templates> }
 /// One wakeword of a detector that holds several (`Rustpotter::add_wakeword_ref` / `add_wakeword_model`, src/detector.rs:144-150)
 pub enum BatchWakeword<'a> {
     /// a reference with its own `threshold` / `avg_threshold` options (`WakewordRef::threshold`, `::avg_threshold`)
@@ -1148,7 +1208,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new(ctx.h, t.h, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, model_set_size: 0, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// S detectors that each hold `wakewords` (references and / or models sharing `mfcc_size`): the best score of the wakewords
     /// whose own thresholds pass wins a frame (`run_wakeword_detectors`, src/detector.rs:433-447)
@@ -1165,7 +1225,7 @@ impl<'a> StreamBatch<'a> {
         }).collect();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_multi(ctx.h, specs.len(), specs.as_ptr(), mfcc_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, model_set_size: 0, n_streams, last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Personal wakewords on live streams: stream `s` holds the one wakeword `bank[stream_wakeword[s]]` (-1: none) with its own window
     /// length and thresholds -- `batch_detect_bank` with the state carried between calls.  `process_multi` reports the bank index.
@@ -1174,7 +1234,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_bank(ctx.h, bank.h, stream_wakeword.as_ptr(), &c, stream_wakeword.len(), max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams: stream_wakeword.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, model_set_size: 0, n_streams: stream_wakeword.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Connect / disconnect of device slots (a batch of `new_bank`): streams `first_stream ..` get new bank indices and are reset
     pub fn set_wakewords(&mut self, first_stream: usize, wakewords: &[i32]) -> Result<(), String> {
@@ -1202,7 +1262,7 @@ impl<'a> StreamBatch<'a> {
         let n_streams = stream_wakewords.len() / set_size;
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_bank_sets(ctx.h, bank.h, stream_wakewords.as_ptr(), set_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, model_set_size: 0, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, label_pitch: 0, _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Re-target the streams `first_stream ..` of a `new_bank_sets` batch, one row of the batch's `set_size` indices per stream: remove-all
     /// plus add-in-order, each stream reset.  An error on any other batch.
@@ -1227,7 +1287,7 @@ impl<'a> StreamBatch<'a> {
         let c: rp_detector_config = config.into();
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_model_bank(ctx.h, bank.h, stream_model.as_ptr(), &c, stream_model.len(), max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams: stream_model.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: bank.labels(), _ctx: ctx,
+        Ok(StreamBatch { h, model_set_size: 0, n_streams: stream_model.len(), last_chunks: 0, set_size: 0, frames_per_chunk: 3, label_pitch: bank.labels(), _ctx: ctx,
                          _t: std::marker::PhantomData })
     }
     /// Connect / disconnect / retarget slots of a `new_model_bank` batch: streams `first_stream ..` get new model indices and are reset.
@@ -1244,7 +1304,7 @@ impl<'a> StreamBatch<'a> {
         let n_streams = stream_models.len() / set_size;
         let mut h = std::ptr::null_mut();
         status(unsafe { rp_stream_batch_new_model_bank_sets(ctx.h, bank.h, stream_models.as_ptr(), set_size as c_int, &c, n_streams, max_chunks_per_call, &mut h) })?;
-        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, label_pitch: bank.labels(), _ctx: ctx, _t: std::marker::PhantomData })
+        Ok(StreamBatch { h, model_set_size: 0, n_streams, last_chunks: 0, set_size, frames_per_chunk: 3, label_pitch: bank.labels(), _ctx: ctx, _t: std::marker::PhantomData })
     }
     /// Re-target the streams `first_stream ..` of a `new_model_bank_sets` batch, one row of the batch's `set_size` indices per stream:
     /// remove-all plus add-in-order, each stream reset.  An error on any other batch.
@@ -1253,11 +1313,39 @@ impl<'a> StreamBatch<'a> {
         assert!(stream_models.len() % self.set_size == 0, "rows of set_size indices");
         status(unsafe { rp_stream_batch_set_model_sets(self.h, first_stream, stream_models.len() / self.set_size, stream_models.as_ptr()) })
     }
+    /// Mixed sets on live streams: stream `s` holds the references `stream_wakewords[s * ref_set_size ..][..ref_set_size]` of `bank` and the
+    /// models `stream_models[s * model_set_size ..][..model_set_size]` of `model_bank` on one detector (-1: an empty slot; a size of 0: the
+    /// side is absent) -- `batch_detect_mixed_sets` with the state carried between calls.  `process_multi` reports the winner's index in its
+    /// own bank and its label (-1: a reference won); `slot_scores` answers the reference slots, `logits` the model slots.
+    pub fn new_mixed_sets(ctx: &'a HipContext, bank: &'a WakewordBank, stream_wakewords: &[i32], ref_set_size: usize, model_bank: &'a ModelBank,
+                          stream_models: &[i32], model_set_size: usize, n_streams: usize, config: &DetectorConfig, max_chunks_per_call: usize)
+                          -> Result<StreamBatch<'a>, String> {
+        assert!(ref_set_size <= RP_WAKEWORD_SET_MAX as usize && model_set_size <= RP_MODEL_SET_MAX as usize);
+        assert!(stream_wakewords.len() == n_streams * ref_set_size && stream_models.len() == n_streams * model_set_size);
+        let c: rp_detector_config = config.into();
+        let rows = |v: &[i32]| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+        let mut h = std::ptr::null_mut();
+        status(unsafe {
+            rp_stream_batch_new_mixed_sets(ctx.h, bank.h, rows(stream_wakewords), ref_set_size as c_int, model_bank.h, rows(stream_models),
+                                           model_set_size as c_int, &c, n_streams, max_chunks_per_call, &mut h)
+        })?;
+        Ok(StreamBatch { h, n_streams, last_chunks: 0, set_size: ref_set_size, frames_per_chunk: 3, label_pitch: model_bank.labels(), model_set_size,
+                         _ctx: ctx, _t: std::marker::PhantomData })
+    }
+    /// Re-target the streams `first_stream ..` of a `new_mixed_sets` batch, one row of each side per stream: remove-all plus add-in-order
+    /// (references, then models), each stream reset.  An error on any other batch.
+    pub fn set_mixed_sets(&mut self, first_stream: usize, n: usize, stream_wakewords: &[i32], stream_models: &[i32]) -> Result<(), String> {
+        assert!(stream_wakewords.len() == n * self.set_size && stream_models.len() == n * self.model_set_size, "rows of the batch's set sizes");
+        let rows = |v: &[i32]| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+        status(unsafe { rp_stream_batch_set_mixed_sets(self.h, first_stream, n, rows(stream_wakewords), rows(stream_models)) })
+    }
     /// The logits of the last `process` / `process_multi` call of a `new_model_bank` batch, `[streams][frames of that call][label pitch of
     /// the bank]` (a `new_model_bank_sets` batch: `[streams][set_size][frames][label pitch]`), zeros behind a model's labels.  An error on
     /// any other batch and before the first call.
     pub fn logits(&mut self) -> Result<Vec<f32>, String> {
-        let mut out = vec![0f32; self.n_streams * self.set_size.max(1) * self.last_chunks.max(1) * self.frames_per_chunk * self.label_pitch];
+        // (a `new_mixed_sets` batch: its model slots)
+        let slots = if self.model_set_size > 0 { self.model_set_size } else { self.set_size.max(1) };
+        let mut out = vec![0f32; self.n_streams * slots * self.last_chunks.max(1) * self.frames_per_chunk * self.label_pitch];
         status(unsafe { rp_stream_batch_logits(self.h, out.as_mut_ptr()) })?;
         Ok(out)
     }

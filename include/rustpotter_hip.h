@@ -236,7 +236,8 @@ enum {
     RP_DTW_KERNEL_BANK = 4096,     /* dtw_bank_kernel: every stream against its own wakeword of a bank (rp_dtw_score_bank, rp_batch_detect_bank) */
     RP_DTW_KERNEL_BANK_STREAM = 8192, /* dtw_bank_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank) */
     RP_DTW_KERNEL_BANK_SETS = 16384,  /* dtw_set_kernel: every stream against its own SET of wakewords of a bank (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets) */
-    RP_DTW_KERNEL_BANK_SETS_STREAM = 32768 /* dtw_set_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank_sets) */
+    RP_DTW_KERNEL_BANK_SETS_STREAM = 32768, /* dtw_set_stream_kernel: the same for the new windows of a live-stream batch (rp_stream_batch_new_bank_sets) */
+    RP_DTW_KERNEL_MIXED_SETS_STREAM = 65536 /* dtw_mixed_stream_kernel: the reference slots of a live-stream batch over mixed sets (rp_stream_batch_new_mixed_sets) */
 };
 int rp_ctx_dtw_kernels(rp_ctx *ctx);
 /* Diagnostics of detect-only calls (replaces nothing): the first n floats of the [S * n_win][T] sample-template score workspace as the last
@@ -1082,6 +1083,67 @@ int rp_frontend_batch_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format 
  * (gain_normalizer_filter.rs:42-48), a stream left without a live slot has gain 1 and keeps its window for later.  rp_stream_batch_reset
  * leaves the filters alone, as everywhere. */
 int rp_stream_batch_set_filters_per_stream(rp_stream_batch *b, const rp_filters_config *filters);
+
+/* MIXED sets: wakeword references and wakeword models together on one stream, over whole recordings.  Stream s carries two rows:
+ * stream_wakewords[s][0 .. ref_set_size) indexes a wakeword bank, stream_models[s][0 .. model_set_size) a model bank.  Each size is
+ * 0 .. 8; a size of 0 (the array may then be NULL) means that side is absent; -1 is an empty slot anywhere in a row; duplicates change
+ * nothing.  Stream s behaves as Rustpotter::new(config), add_wakeword for its live reference slots in slot order, then add_wakeword for its
+ * live model slots in slot order, then process_samples (src/detector.rs:304-346, 433-447):
+ *  - its window is Lmax(s) frames, the longest over the live slots of BOTH rows (max_len of a reference, train_size of a model), its
+ *    countdown Lmax(s) / 2, and it has n_win_s = n_frames - Lmax(s) + 1 windows; a stream shorter than Lmax(s) reports nothing, even where a
+ *    shorter wakeword of its set would fit;
+ *  - every slot scores the OLDEST frames of that window, as many as its own length (wakeword_comp.rs:22-27, wakeword_nn.rs:137);
+ *  - a reference proposes under its own thresholds over the config's (>), its averaged-template test as in rp_batch_detect_bank_sets; a
+ *    model proposes under the config's thresholds (>=): the rules of the two families;
+ *  - the best passing score wins; of equal scores the first in that order: references before models, slot order within a kind;
+ *  - a detection reports window = frame - Lmax(s) + 1; det_wakeword is the winner's index in ITS OWN bank; det_label is the label index
+ *    of the winner's best window for a model and -1 for a reference, so det_label >= 0 says that a model won.  Behind a stream's
+ *    detections det_wakeword is 0 and det_label -1.
+ * A stream with no live slot in either row is a detector without wakewords.  With every model slot -1 (or model_set_size 0) a stream
+ * reports exactly what rp_batch_detect_bank_sets reports, with every reference slot -1 exactly what rp_batch_detect_model_bank_sets reports.
+ * Both banks belong to the call's context.  The wakeword bank must have mfcc_size 16, which is what a model bank is; any other size fails
+ * with "Usage of wakewords with different mfcc size is not supported, ignoring wakeword".  band_size 3..6, or 0.  Arithmetic is that of the
+ * two families: references in f32 vector FMAs whatever rp_ctx_set_arithmetic says, models RP_MLP_F32 (RP_MLP_BF16 computes the same; the
+ * others are refused).  Index rules are those of the two families: with RP_CTX_HOST_POINTERS an index outside its bank is an error that
+ * names stream, slot and side ("wakeword index" / "model index"), found before anything is allocated or launched; with device arrays it
+ * counts as -1.  Two empty banks, or rows of all -1: the call succeeds and reports nothing.  VAD and the reset after a detection as
+ * everywhere.  rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK_SETS: the call runs dtw_set_kernel and the model-set forward as they are, one
+ * short kernel (mixed_targets_kernel) folds Lmax(s) per stream, and one scan (scan_mixed_set_kernel) reads both kinds' proposals. */
+int rp_batch_detect_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                               const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size, const rp_model_bank *model_bank,
+                               const int32_t *stream_models, int model_set_size, const rp_detector_config *config, int precision,
+                               rp_batch_detection *det, int32_t *det_wakeword, int32_t *det_label, int32_t *n_det, int max_det);
+/* rp_frontend_batch_bank_sets with both rows and both banks, what goes in front of rp_batch_detect_mixed_sets: stream s works towards the
+ * largest non-NaN rms_level over the live slots of BOTH rows (on_wakeword_change, src/detector.rs:328-338) over max(Lmax(s) / 3, 1) chunk
+ * levels; gain_ref for every stream when has_gain_ref; a stream without a live slot, or with every level NaN, has gain 1.  Rows, sizes,
+ * index rules and the mfcc_size rule as in rp_batch_detect_mixed_sets. */
+int rp_frontend_batch_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                 const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size,
+                                 const rp_model_bank *model_bank, const int32_t *stream_models, int model_set_size, float *pcm_out,
+                                 size_t out_stride, float *rms, float *gains);
+/* Mixed sets on LIVE streams: rp_batch_detect_mixed_sets with the state carried between calls.  History per stream is the larger of what a
+ * bank-sets batch and a model-sets batch would keep, reservations included; both banks count the batch, and both may change under it by
+ * rp_wakeword_bank_put / _put_from_rpw / _enrol and rp_model_bank_put / _put_from_rpw / _train within what the batch was sized for: Lmax(s),
+ * every threshold and the gain normaliser's level are read from the banks at the start of EVERY process call (mixed_targets_kernel), so a
+ * changed bank is seen from the next call.  A process call scores the reference slots with dtw_mixed_stream_kernel (rp_ctx_dtw_kernels reports
+ * RP_DTW_KERNEL_MIXED_SETS_STREAM and only that bit) and the model slots with ONE forward launch (mlp_mixed_stream_kernel); the window that
+ * ends at a new frame starts Lmax(s) - 1 frames before it for every slot of either kind.  A stream fed in pieces reports the detections of
+ * rp_batch_detect_mixed_sets over the concatenation: frame, window, counter, det_wakeword and det_label exact, reference scores within 1e-5,
+ * model scores within 2e-6; the kind of a partial detection is carried between calls with it.
+ * rp_stream_batch_process works without agg and is refused with agg; rp_stream_batch_process_multi reports det_wakeword (the winner's index
+ * in its own bank) and det_label (>= 0: a model won); rp_stream_batch_slot_scores answers the reference slots, [S][ref_set_size][frames of the
+ * call]; rp_stream_batch_logits the model slots, [S][model_set_size][frames of the call][label pitch]; rp_stream_batch_set_filters_per_stream
+ * gives the gain normaliser over both rows; rp_stream_batch_set_input, _reset, _chunks_seen and the band-pass-only
+ * rp_stream_batch_set_filters work.  rp_stream_batch_set_wakewords, _set_wakeword_sets, _set_models, _set_model_sets, _set_filters_bank and
+ * the gain normaliser through rp_stream_batch_set_filters are refused, each with an error that says why. */
+int rp_stream_batch_new_mixed_sets(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size,
+                                   const rp_model_bank *model_bank, const int32_t *stream_models, int model_set_size,
+                                   const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out);
+/* Re-target streams first_stream .. first_stream + n - 1 of such a batch: stream_wakewords [n][ref_set_size] and stream_models
+ * [n][model_set_size] (the sizes of the batch; NULL for a size of 0).  All slots of both rows are removed, the new ones added in order --
+ * references, then models -- and the stream reset, as rp_stream_batch_set_wakeword_sets does.  A refused row (host arrays) names its stream,
+ * slot and side and changes nothing.  An error on any other kind of batch. */
+int rp_stream_batch_set_mixed_sets(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *stream_wakewords, const int32_t *stream_models);
 
 /* Synthetic benchmark input of BASELINE.md §2, generated on the device:
  * pcm[s][i] = (splitmix64(seed ^ ((first_stream+s)<<32 + i)) >> 40) / 2^24 - 0.5 */

@@ -128,6 +128,7 @@ SYMBOLS = [
     "rp_mlp_forward_windows_bank_sets", "rp_batch_detect_model_bank_sets", "rp_stream_batch_new_model_bank_sets", "rp_stream_batch_set_model_sets",
     "rp_model_bank_set_rms_levels", "rp_model_bank_rms_level", "rp_frontend_batch_bank_sets", "rp_frontend_batch_model_bank",
     "rp_stream_batch_set_filters_per_stream",
+    "rp_batch_detect_mixed_sets", "rp_frontend_batch_mixed_sets", "rp_stream_batch_new_mixed_sets", "rp_stream_batch_set_mixed_sets",
 ]
 
 
@@ -327,6 +328,12 @@ def load_library():
                                               C.c_size_t, vp, vp]
     L.rp_frontend_batch_model_bank.argtypes = L.rp_frontend_batch_bank_sets.argtypes
     L.rp_stream_batch_set_filters_per_stream.argtypes = [vp, C.POINTER(_FiltersCfg)]
+    L.rp_batch_detect_mixed_sets.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_int, vp, vp, C.c_int,
+                                             C.POINTER(_DetectorConfig), C.c_int, vp, vp, vp, vp, C.c_int]
+    L.rp_stream_batch_new_mixed_sets.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(_DetectorConfig), C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.rp_stream_batch_set_mixed_sets.argtypes = [vp, C.c_size_t, C.c_size_t, vp, vp]
+    L.rp_frontend_batch_mixed_sets.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(_FiltersCfg), vp, vp, C.c_int, vp, vp,
+                                               C.c_int, vp, C.c_size_t, vp, vp]
     _LIB = L
     return L
 
@@ -895,7 +902,8 @@ class StreamBatch:
 
     def __init__(self, ctx, templates, detector_config, S, max_chunks_per_call=1, sample_rate=16000, channels=1, wakewords=None,
                  mfcc_size=None, filters=None, rms_level_ref=float("nan"), bank=None, stream_wakeword=None, bank_filters=None,
-                 stream_wakewords=None, set_size=None, model_bank=None, stream_model=None, stream_models=None, per_stream_filters=None):
+                 stream_wakewords=None, set_size=None, model_bank=None, stream_model=None, stream_models=None, per_stream_filters=None,
+                 model_set_size=None):
         """templates: one wakeword reference (rp_stream_batch_new).  wakewords (rp_stream_batch_new_multi): a list of
         dicts, each {"templates": Templates} or {"model": Model, "none_index": int, "precision": "f32" | "bf16"}, optionally
         with "threshold" / "avg_threshold" (the wakeword's own overrides); mfcc_size is then required.
@@ -913,14 +921,31 @@ class StreamBatch:
         model_bank[stream_model[s]], -1 = none; set_models() re-targets streams, logits() returns the last call's logits.
         model_bank + stream_models (rp_stream_batch_new_model_bank_sets): stream s holds the SET of models stream_models[s], [S][set_size]
         int32 with -1 = an empty slot (with device pointers: the address of a device array and set_size); set_model_sets() re-targets
-        streams, logits() is then [S][set_size][frames][label pitch]."""
+        streams, logits() is then [S][set_size][frames][label pitch].
+        bank + model_bank (rp_stream_batch_new_mixed_sets): stream s holds the references stream_wakewords[s] of bank AND the models
+        stream_models[s] of model_bank on one detector; either may be None (that side is absent).  With device pointers: addresses with
+        set_size / model_set_size.  set_mixed_sets() re-targets streams; slot_scores() answers the reference slots, logits() the model slots."""
         self._L = load_library()
         self.set_size = 0
+        self.model_set_size = 0
+        self.mixed = False
         self.label_pitch = 0
         self.ctx, self.templates, self.S, self.max_chunks = ctx, templates, S, max_chunks_per_call
         h = C.c_void_p()
         c = detector_config._c()
-        if model_bank is not None and stream_models is not None:
+        if model_bank is not None and bank is not None:
+            self._keep = (bank, model_bank)   # the batch borrows both banks
+            self.label_pitch = model_bank.label_pitch
+            self.mixed = True
+            ridx, rptr = self._indices(stream_wakewords)
+            midx, mptr = self._indices(stream_models)
+            self.set_size = int((ridx.shape[1] if ridx is not None else 0) if set_size is None else set_size)
+            self.model_set_size = int((midx.shape[1] if midx is not None else 0) if model_set_size is None else model_set_size)
+            if self._L.rp_stream_batch_new_mixed_sets(ctx._h, bank._h, rptr if self.set_size else None, self.set_size, model_bank._h,
+                                                      mptr if self.model_set_size else None, self.model_set_size, C.byref(c), S, max_chunks_per_call,
+                                                      C.byref(h)) < 0:
+                raise _err()
+        elif model_bank is not None and stream_models is not None:
             self._keep = model_bank   # the batch borrows the bank
             self.label_pitch = model_bank.label_pitch
             idx, ptr = self._indices(stream_models)
@@ -1018,13 +1043,25 @@ class StreamBatch:
         if self._L.rp_stream_batch_set_model_sets(self._h, first_stream, len(idx) if n is None else n, ptr) < 0:
             raise _err()
 
+    def set_mixed_sets(self, first_stream, stream_wakewords, stream_models, n=None):
+        """rp_stream_batch_set_mixed_sets: streams first_stream .. get the rows stream_wakewords [n][set_size] and stream_models
+        [n][model_set_size] (-1: an empty slot; None for a side the batch does not have) and are reset -- remove-all plus add-in-order;
+        between process calls.  With device pointers: the addresses of device int32 arrays of n rows."""
+        ridx, rptr = self._indices(stream_wakewords)
+        midx, mptr = self._indices(stream_models)
+        if n is None:
+            n = len(ridx) if ridx is not None else len(midx)
+        if self._L.rp_stream_batch_set_mixed_sets(self._h, first_stream, n, rptr if self.set_size else None, mptr if self.model_set_size else None) < 0:
+            raise _err()
+
     def logits(self):
         """rp_stream_batch_logits -> [S][frames of the last process call][label pitch of the bank]; a batch over model sets:
-        [S][set_size][frames][label pitch]"""
+        [S][set_size][frames][label pitch]; a batch over mixed sets: its model slots, [S][model_set_size][frames][label pitch]"""
         import numpy as np
         assert self.ctx.host
         n = max(self._last_chunks, 1) * self.frames_per_chunk
-        out = np.empty((self.S, self.set_size, n, self.label_pitch) if self.set_size else (self.S, n, self.label_pitch), np.float32)
+        slots = self.model_set_size if self.mixed else self.set_size
+        out = np.empty((self.S, slots, n, self.label_pitch) if (slots or self.mixed) else (self.S, n, self.label_pitch), np.float32)
         if self._L.rp_stream_batch_logits(self._h, out.ctypes.data) < 0:
             raise _err()
         return out
@@ -1038,7 +1075,7 @@ class StreamBatch:
         import numpy as np
         assert self.ctx.host
         n = max(self._last_chunks, 1) * self.frames_per_chunk
-        agg = np.empty((self.S, max(self.set_size, 1), n), np.float32)
+        agg = np.empty((self.S, self.set_size if self.mixed else max(self.set_size, 1), n), np.float32)
         avg = np.empty_like(agg)
         if self._L.rp_stream_batch_slot_scores(self._h, agg.ctypes.data, avg.ctypes.data) < 0:
             raise _err()
@@ -1309,7 +1346,8 @@ class BatchContext:
 
     DTW_KERNELS = {1: "dtw_mfma_kernel", 2: "dtw_mfma_wide_kernel", 4: "dtw_ragged_kernel", 8: "register kernels", 16: "dtw_generic_kernel",
                    32: "dtw_single_kernel", 64: "dtw_ref_kernel (every window)", 128: "dtw_mfma_group_kernel", 4096: "dtw_bank_kernel",
-                   8192: "dtw_bank_stream_kernel", 16384: "dtw_set_kernel", 32768: "dtw_set_stream_kernel"}
+                   8192: "dtw_bank_stream_kernel", 16384: "dtw_set_kernel", 32768: "dtw_set_stream_kernel",
+                   65536: "dtw_mixed_stream_kernel"}
     DTW_PRODUCTS = {256: "bf16x3", 512: "f16x2"}
     DTW_MFMA_WAVES = {1024: 8, 2048: 12}
 
@@ -1603,6 +1641,43 @@ class BatchContext:
     def frontend_model_bank(self, pcm, filters_config, model_bank, stream_models):
         """rp_frontend_batch_model_bank: the same over a ModelBank, stream_models [S] or [S][set_size] (-1: none)."""
         return self._frontend_sets(self._L.rp_frontend_batch_model_bank, pcm, filters_config, model_bank, stream_models)
+
+    @staticmethod
+    def _mixed_rows(rows, S):
+        """a side's rows of a mixed-set call -> (int32 array or None, pointer or None, set_size); None: the side is absent (set_size 0, NULL)"""
+        import numpy as np
+        if rows is None:
+            return None, None, 0
+        idx = np.ascontiguousarray(rows, np.int32)
+        assert idx.ndim == 2 and idx.shape[0] == S
+        return idx, (idx.ctypes.data if idx.shape[1] else None), idx.shape[1]
+
+    def frontend_batch_mixed_sets(self, pcm, filters_config, bank, stream_wakewords, model_bank, stream_models):
+        """rp_frontend_batch_mixed_sets: frontend_bank_sets() for streams that hold references AND models -- stream_wakewords [S][ref_set_size]
+        over the WakewordBank, stream_models [S][model_set_size] over the ModelBank (-1: an empty slot; None: the side is absent).  Stream s
+        works towards the largest non-NaN rms_level over the live slots of both rows over max(Lmax(s) / 3, 1) chunk levels
+        -> (pcm f32, rms, gains)."""
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        _ri, rp, rn = self._mixed_rows(stream_wakewords, S)
+        _mi, mp, mn = self._mixed_rows(stream_models, S)
+        rc = RustpotterConfig()
+        rc.filters = filters_config
+        f = rc._filters_c()
+        out = np.empty((S, N), np.float32)
+        rms = np.empty((S, N // 480), np.float32)
+        gains = np.empty((S, N // 480), np.float32)
+        if self._L.rp_frontend_batch_mixed_sets(self._h, pcm.ctypes.data, fmt, S, N, N, C.byref(f), bank._h, rp, rn, model_bank._h, mp, mn,
+                                                out.ctypes.data, N, rms.ctypes.data, gains.ctypes.data) < 0:
+            raise _err()
+        return out, rms, gains
 
     def frontend_bank_sets_dev(self, pcm_ptr, fmt, S, n_samples, pcm_stride, filters_config, bank, idx_ptr, set_size, out_ptr, out_stride, rms_ptr,
                                gains_ptr):
@@ -2075,6 +2150,42 @@ class BatchContext:
         c = detector_config._c()
         if self._L.rp_batch_detect_model_bank_sets(self._h, pcm_ptr, int(fmt), S, N, stride, bank._h, idx_ptr, set_size, C.byref(c),
                                                    MLP_PRECISION[precision], det_ptr, model_ptr, label_ptr, n_det_ptr, max_det) < 0:
+            raise _err()
+
+    def batch_detect_mixed_sets(self, pcm, bank, stream_wakewords, model_bank, stream_models, detector_config, precision="f32", max_det=8):
+        """rp_batch_detect_mixed_sets: the whole path with stream s holding references AND models on one detector -- stream_wakewords
+        [S][ref_set_size] over the WakewordBank, stream_models [S][model_set_size] over the ModelBank (-1: an empty slot; None: the side is
+        absent) -> (det, det_wakeword, det_label, n_det).  det_wakeword: the winner's index in its own bank; det_label: its label for a
+        model, -1 for a reference."""
+        import numpy as np
+        assert self.host
+        pcm = np.ascontiguousarray(pcm)
+        fmt = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2}.get(pcm.dtype)
+        if fmt is None:
+            pcm, fmt = np.ascontiguousarray(pcm, np.float32), 3
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        S, N = pcm.shape
+        _ri, rp, rn = self._mixed_rows(stream_wakewords, S)
+        _mi, mp, mn = self._mixed_rows(stream_models, S)
+        det = np.zeros((S, max_det), dtype=DET_DTYPE)
+        dww = np.zeros((S, max_det), np.int32)
+        dlab = np.zeros((S, max_det), np.int32)
+        n_det = np.zeros(S, np.int32)
+        c = detector_config._c()
+        if self._L.rp_batch_detect_mixed_sets(self._h, pcm.ctypes.data, fmt, S, N, N, bank._h, rp, rn, model_bank._h, mp, mn, C.byref(c),
+                                              MLP_PRECISION[precision], det.ctypes.data, dww.ctypes.data, dlab.ctypes.data, n_det.ctypes.data,
+                                              max_det) < 0:
+            raise _err()
+        return det, dww, dlab, n_det
+
+    def batch_detect_mixed_sets_dev(self, pcm_ptr, fmt, S, N, stride, bank, ref_ptr, ref_set_size, model_bank, model_ptr, model_set_size,
+                                    detector_config, precision, det_ptr, ww_ptr, label_ptr, n_det_ptr, max_det):
+        """rp_batch_detect_mixed_sets on device pointers (tools/bench_mixed_sets.py)"""
+        c = detector_config._c()
+        if self._L.rp_batch_detect_mixed_sets(self._h, pcm_ptr, int(fmt), S, N, stride, bank._h, ref_ptr, ref_set_size, model_bank._h, model_ptr,
+                                              model_set_size, C.byref(c), MLP_PRECISION[precision], det_ptr, ww_ptr, label_ptr, n_det_ptr,
+                                              max_det) < 0:
             raise _err()
 
     def batch_detect_model_dev(self, pcm_ptr, fmt, S, N, stride, model, mfcc_size, none_index, detector_config, precision, det_ptr, label_ptr,

@@ -443,6 +443,7 @@ int bank_from(rp_ctx *ctx, std::unique_ptr<Bank> b, rp_wakeword_bank **out) {
 extern "C" {
 
 static_assert(RP_DTW_KERNEL_BANK_SETS == (int)kDtwRanBankSets && RP_DTW_KERNEL_BANK_SETS_STREAM == (int)kDtwRanBankSetsStream && RP_WAKEWORD_SET_MAX == kScanMaxWakewords, "rustpotter_hip.h mirrors rp_kernels.h");
+static_assert(RP_DTW_KERNEL_MIXED_SETS_STREAM == (int)kDtwRanMixedSetsStream, "rustpotter_hip.h mirrors rp_kernels.h");
 static_assert(RP_DTW_KERNEL_BANK == (int)kDtwRanBank && RP_DTW_KERNEL_BANK_STREAM == (int)kDtwRanBankStream && RP_WAKEWORD_BANK_MAX_TEMPLATES == kBankMaxTemplates, "rustpotter_hip.h mirrors rp_kernels.h");
 
 int rp_wakeword_bank_new(rp_ctx *ctx, size_t n_wakewords, int mfcc_size, const int32_t *counts, const int32_t *lens, const float *feats,

@@ -2,8 +2,10 @@
 // rp_batch_detect_bank, rp_frontend_batch_bank; kernels: rp_dtw_bank.hip, scan_bank_kernel in rp_scan.hip), against its own SET of wakewords
 // (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets; rp_dtw_set.hip, rp_scan_set.hip), or is run by ITS model of a model bank
 // (rp_mlp_forward_windows_bank, rp_batch_detect_model_bank; mlp_windows_bank_kernel, window_means_bank_kernel, nn_score_bank_kernel in
-// rp_mlp_windows.hip / rp_mlp.hip).  Every call reads: arguments, staged indices, the empty-bank answer, front, score, scan, copy back.  The banks themselves are
-// rp_bank.cpp and rp_model_bank.cpp; DESIGN.md sections 4.2 - 4.4.
+// rp_mlp_windows.hip / rp_mlp.hip), or holds references of a wakeword bank AND models of a model bank on one detector (mixed sets:
+// rp_batch_detect_mixed_sets, rp_frontend_batch_mixed_sets; rp_mixed_targets.hip, scan_mixed_set_kernel in rp_scan_mixed.hip).  Every call
+// reads: arguments, staged indices, the empty-bank answer, front, score, scan, copy back.  The banks themselves are rp_bank.cpp and
+// rp_model_bank.cpp; DESIGN.md sections 4.2 - 4.4.
 #include <algorithm>
 #include <cstring>
 #include <initializer_list>
@@ -29,7 +31,7 @@ bool bank_indices_ok(int W, size_t first, size_t n, int set_size, const int32_t 
 // the window of entry w; used (optional, [W]): set for every entry a stream of a HOST array uses.
 template <class LenOf>
 static bool stage_indices(Ctx *c, Staged &sg, int W, int min_len, LenOf len_of, const char *what, const int32_t *idx, size_t S, int set_size,
-                          size_t n_frames, BankIndices *bi, std::vector<char> *used = nullptr) {
+                          size_t n_frames, BankIndices *bi, std::vector<char> *used = nullptr, DevBuf *buf = nullptr) {
     auto n_win_of = [&](int len) { return n_frames >= (size_t)len ? n_frames - (size_t)len + 1 : (size_t)0; };
     *bi = BankIndices();
     if (!sg.host) {
@@ -50,7 +52,7 @@ static bool stage_indices(Ctx *c, Staged &sg, int W, int min_len, LenOf len_of, 
         if (lmax > 0) bi->max_n_win = std::max(bi->max_n_win, n_win_of(lmax));
     }
     if (S == 0) return true;
-    bi->dev = static_cast<const int32_t *>(sg.in(idx, S * row * sizeof(int32_t), c->ws_bank_idx));
+    bi->dev = static_cast<const int32_t *>(sg.in(idx, S * row * sizeof(int32_t), buf ? *buf : c->ws_bank_idx));   // (buf: a call that stages two arrays)
     return bi->dev != nullptr;
 }
 
@@ -86,8 +88,9 @@ bool stage_model_indices(Ctx *c, Staged &sg, const ModelBank &bk, const int32_t 
 
 // The same for rows of set_size indices (model sets): Lmax(s), the longest window of a row's live slots, decides the stream's window count
 // and cut, every live slot's own window the staging -- host arrays: of the rows as they are; device arrays: of every pair the bank allows
-bool stage_model_set_indices(Ctx *c, Staged &sg, const ModelBank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, ModelBankCall *q) {
-    if (!stage_indices(c, sg, bk.dev.W, bk.min_L, [&](size_t w) { return bk.e[w].L; }, "model index", idx, S, set_size, n_frames, &q->idx)) return false;
+bool stage_model_set_indices(Ctx *c, Staged &sg, const ModelBank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, ModelBankCall *q,
+                             DevBuf *buf = nullptr) {
+    if (!stage_indices(c, sg, bk.dev.W, bk.min_L, [&](size_t w) { return bk.e[w].L; }, "model index", idx, S, set_size, n_frames, &q->idx, nullptr, buf)) return false;
     if (sg.host) {
         for (size_t s = 0; s < S; ++s) {
             const int32_t *row = idx + s * (size_t)set_size;
@@ -547,6 +550,172 @@ int rp_batch_detect_model_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_form
             })) return -1;
         if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
         return sg.back(det_model, dw, col) && sg.back(det_label, dl, col) && sg.finish() ? 0 : -1;
+    });
+}
+
+}  // extern "C"
+
+// ---- mixed sets: stream s holds a row of references of a wakeword bank and a row of models of a model bank on ONE detector
+namespace {
+
+// What both mixed calls check first: handles, the two set sizes (0: the side is absent), the arrays, the banks' context (whose device
+// becomes current) and add_wakeword's mfcc_size rule (src/detector.rs:316-319) -- a model bank is at 16.  With host arrays every index of
+// both rows is checked here, before anything is allocated or launched; the error names stream, slot and side.
+struct MixedCall {
+    Ctx *c = nullptr;
+    const Bank *bk = nullptr;
+    const ModelBank *mb = nullptr;
+    bool refs_on = false, models_on = false;   // the side has rows AND its bank has entries: only then is anything of it staged, scored or read
+};
+bool mixed_enter(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size, const rp_model_bank *model_bank,
+                 const int32_t *stream_models, int model_set_size, size_t S, MixedCall *m) {
+    if (!ctx || !bank || !model_bank) { set_last_error("null handle"); return false; }
+    if (ref_set_size < 0 || ref_set_size > RP_WAKEWORD_SET_MAX) {
+        set_last_error("ref_set_size " + std::to_string(ref_set_size) + " is outside 0 .. " + std::to_string((int)RP_WAKEWORD_SET_MAX) + " (RP_WAKEWORD_SET_MAX)");
+        return false;
+    }
+    if (model_set_size < 0 || model_set_size > RP_MODEL_SET_MAX) {
+        set_last_error("model_set_size " + std::to_string(model_set_size) + " is outside 0 .. " + std::to_string((int)RP_MODEL_SET_MAX) + " (RP_MODEL_SET_MAX)");
+        return false;
+    }
+    if (S && ((ref_set_size && !stream_wakewords) || (model_set_size && !stream_models))) { set_last_error("null argument"); return false; }
+    m->bk = bank->impl.get(); m->mb = model_bank->impl.get();
+    Ctx *c = ctx->impl.get();
+    if (m->bk->ctx != c) { set_last_error("the wakeword bank belongs to another context"); return false; }
+    if (m->mb->ctx != c) { set_last_error("the model bank belongs to another context"); return false; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return false;
+    m->c = c;
+    // (an empty bank that was never reserved has a placeholder mfcc_size: a detector without references)
+    if ((m->bk->dev.W || m->bk->ceiling) && m->bk->dev.K != 16) {
+        set_last_error("Usage of wakewords with different mfcc size is not supported, ignoring wakeword");
+        return false;
+    }
+    if (c->flags & RP_CTX_HOST_POINTERS) {
+        if (ref_set_size && !bank_indices_ok(m->bk->dev.W, 0, S, ref_set_size, stream_wakewords, "wakeword index")) return false;
+        if (model_set_size && !bank_indices_ok(m->mb->dev.W, 0, S, model_set_size, stream_models, "model index")) return false;
+    }
+    m->refs_on = ref_set_size > 0 && m->bk->dev.W > 0;
+    m->models_on = model_set_size > 0 && m->mb->dev.W > 0;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// rp_frontend_batch_bank_sets over both rows: the level and window of on_wakeword_change over every live slot of either kind, prepared by
+// mixed_targets_kernel in front of the same per-stream gain kernels
+int rp_frontend_batch_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                                 const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size,
+                                 const rp_model_bank *model_bank, const int32_t *stream_models, int model_set_size, float *pcm_out, size_t out_stride,
+                                 float *rms, float *gains) {
+    return guarded([&]() -> int {
+        MixedCall m;
+        if (!mixed_enter(ctx, bank, stream_wakewords, ref_set_size, model_bank, stream_models, model_set_size, S, &m)) return -1;
+        Ctx *c = m.c;
+        const Bank &bk = *m.bk;
+        const ModelBank &mb = *m.mb;
+        Staged sg(c);
+        BankIndices ri, mi;
+        if (m.refs_on && !stage_bank_indices(c, sg, bk, stream_wakewords, S, ref_set_size, 0, &ri)) return -1;
+        if (m.models_on && !stage_indices(c, sg, mb.dev.W, mb.min_L, [&](size_t w) { return mb.e[w].L; }, "model index", stream_models, S, model_set_size, 0,
+                                          &mi, nullptr, &c->ws_mix_idx)) return -1;
+        MixedSide sides[2];
+        if (m.refs_on) { sides[0].rows = ri.dev; sides[0].set_size = ref_set_size; sides[0].ww = bk.dev.ww; sides[0].level = bk.rms_level; sides[0].W = bk.dev.W; }
+        if (m.models_on) { sides[1].rows = mi.dev; sides[1].set_size = model_set_size; sides[1].ww = mb.scan.ww; sides[1].level = mb.rms_level(); sides[1].W = mb.dev.W; }
+        const int longest = std::max(m.refs_on ? bk.dev.max_len : 0, m.models_on ? mb.max_L : 0);   // the capacity of a stream's ring
+        return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(longest / 3, 1), nullptr, nullptr, pcm_out, out_stride,
+                              rms, gains, nullptr, 0, sides);
+    });
+}
+
+int rp_batch_detect_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
+                               const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size, const rp_model_bank *model_bank,
+                               const int32_t *stream_models, int model_set_size, const rp_detector_config *config, int precision,
+                               rp_batch_detection *det, int32_t *det_wakeword, int32_t *det_label, int32_t *n_det, int max_det) {
+    return guarded([&]() -> int {
+        MixedCall m;
+        if (!mixed_enter(ctx, bank, stream_wakewords, ref_set_size, model_bank, stream_models, model_set_size, S, &m)) return -1;
+        if (!config || (S && (!pcm || !det || !n_det))) { set_last_error("null argument"); return -1; }
+        Ctx *c = m.c;
+        const Bank &bk = *m.bk;
+        const ModelBank &mb = *m.mb;
+        if (!bank_band_ok(bk, (int)config->band_size) || !bank_precision_ok(precision)) return -1;
+        if (max_det < 0) { set_last_error("max_det must be >= 0"); return -1; }
+        Staged sg(c);
+        const size_t nf = rp_mfcc_num_frames(n_samples);
+        const size_t col = S * (size_t)max_det * sizeof(int32_t);
+        // no reference and no model anywhere: every stream is a detector without wakewords
+        if (!m.refs_on && !m.models_on)
+            return empty_bank_answer(c, sg, fmt, S, n_samples, pcm_stride, det, n_det, max_det, {{det_wakeword, col}, {det_label, col}});
+        BankIndices ri;
+        ModelBankCall q;
+        if (m.refs_on && !stage_bank_indices(c, sg, bk, stream_wakewords, S, ref_set_size, nf, &ri)) return -1;
+        if (m.models_on && !stage_model_set_indices(c, sg, mb, stream_models, S, model_set_size, nf, &q, &c->ws_mix_idx)) return -1;
+        DetectFront f;
+        if (!detect_front(c, sg, pcm, fmt, S, n_samples, pcm_stride, 16, 1, det, n_det, max_det, &f)) return -1;
+        // the two int32 columns: the caller's arrays on the device, else the halves of one staging buffer
+        int32_t *dw = det_wakeword, *dl = det_label;
+        if (sg.host && col && (det_wakeword || det_label)) {
+            if (!c->stage_out3.reserve(2 * col)) return -1;
+            if (det_wakeword) dw = c->stage_out3.as<int32_t>();
+            if (det_label) dl = c->stage_out3.as<int32_t>() + S * (size_t)max_det;
+        }
+        // Both sides write their proposals for their OWN window counts (each at least the stream's: Lmax(s) is the longer window), into
+        // separate workspaces with one pitch
+        const size_t pitch = std::max<size_t>(std::max(m.refs_on ? ri.max_n_win : 0, m.models_on ? q.idx.max_n_win : 0), 1), rows = S * pitch;
+        if (!c->ws_gain_tab.reserve(gain_targets_bytes(S))) return -1;
+        if (m.refs_on && (!c->ws_agg.reserve(rows * sizeof(float) + 16) || !c->ws_avg.reserve(rows * sizeof(float) + 16) ||
+                          !c->ws_set_ww.reserve(rows * sizeof(int32_t) + 16))) return -1;
+        if (m.models_on && (!c->ws_ring.reserve(rows * (size_t)model_set_size * (size_t)mb.dev.label_pitch * sizeof(float) + 16) ||
+                            !c->ws_mix_best.reserve(rows * sizeof(float) + 16) || !c->ws_mix_avg.reserve(rows * sizeof(float) + 16) ||
+                            !c->ws_mix_ww.reserve(rows * sizeof(int32_t) + 16) || !c->ws_mix_label.reserve(rows * sizeof(int32_t) + 16))) return -1;
+        MixedSide sides[2];
+        MixedProposals pr, pm;
+        if (m.refs_on) {
+            sides[0].rows = ri.dev; sides[0].set_size = ref_set_size; sides[0].ww = bk.dev.ww; sides[0].level = bk.rms_level; sides[0].W = bk.dev.W;
+            pr.bank = bk.dev; pr.rows = ri.dev; pr.set_size = ref_set_size;
+            pr.best = c->ws_agg.as<float>(); pr.best_avg = c->ws_avg.as<float>(); pr.best_ww = c->ws_set_ww.as<int32_t>();
+        }
+        if (m.models_on) {
+            sides[1].rows = q.idx.dev; sides[1].set_size = model_set_size; sides[1].ww = mb.scan.ww; sides[1].level = mb.rms_level(); sides[1].W = mb.dev.W;
+            pm.bank = mb.scan; pm.rows = q.idx.dev; pm.set_size = model_set_size;
+            pm.best = c->ws_mix_best.as<float>(); pm.best_avg = c->ws_mix_avg.as<float>(); pm.best_ww = c->ws_mix_ww.as<int32_t>();
+            pm.best_label = c->ws_mix_label.as<int32_t>();
+        }
+        uint32_t *hot = nullptr;
+        PerStreamGain per;   // (its table is what the scan reads Lmax(s) from)
+        if (S) {
+            if (!hip_ok(launch_mixed_targets(c->stream, sides[0], sides[1], S, c->ws_gain_tab.p, &per), "mixed_targets_kernel")) return -1;
+            // both scoring kernels raise the same flag per stream with a proposal: the scan skips the others and puts the flags back
+            hot = c->hot_flags(S);
+            if (!hot) return -1;
+            if (m.refs_on) {
+                BankSetScore qs;
+                qs.mfcc = f.dm; qs.S = S; qs.n_frames = nf; qs.win_pitch = pitch; qs.stream_wakewords = ri.dev; qs.set_size = ref_set_size;
+                qs.band = (int)config->band_size; qs.score_mode = (int)config->score_mode; qs.score_ref = config->score_ref; qs.avg_mode = 2;
+                qs.gate = (c->flags & RP_CTX_FULL_SCORES) ? 0 : 1;   // detect-only
+                qs.threshold = config->threshold; qs.avg_threshold = config->avg_threshold;
+                qs.best = c->ws_agg.as<float>(); qs.best_avg = c->ws_avg.as<float>(); qs.best_ww = c->ws_set_ww.as<int32_t>();
+                qs.hot = hot;
+                if (!score_bank_sets(c, bk, qs)) return -1;
+            }
+            if (m.models_on) {
+                float *dlog = c->ws_ring.as<float>();
+                if (!bank_set_logits(c, mb, q, model_set_size, f.dm, S, nf, pitch, dlog)) return -1;
+                if (!hip_ok(launch_nn_score_model_set(c->stream, mb.dev, q.idx.dev, model_set_size, dlog, S, nf, pitch, config->score_ref * 10.f,
+                                                      config->avg_threshold != 0.f ? 1 : 0, config->threshold, config->avg_threshold, c->ws_mix_best.as<float>(),
+                                                      c->ws_mix_avg.as<float>(), c->ws_mix_ww.as<int32_t>(), c->ws_mix_label.as<int32_t>(), hot),
+                            "nn_score_model_set_kernel")) return -1;
+            }
+        }
+        // Lmax(s) (countdown Lmax(s) / 2) from the table; the gates were applied by the scoring kernels
+        const ScanConfig sc = scan_config(*config, 0, true);
+        if (!detect_scan(c, *config, f.dm, S, nf, 16, "scan_mixed_set_kernel", [&](const float *dv, float vm) {
+                return launch_scan_mixed_set(c->stream, pr, pm, per.ww, pitch, dv, vm, S, nf, sc, f.dd, dw, dl, f.dn, max_det, hot);
+            })) return -1;
+        if (!sg.back_detections(S, max_det, det, f.dd, n_det, f.dn)) return -1;
+        return sg.back(det_wakeword, dw, col) && sg.back(det_label, dl, col) && sg.finish() ? 0 : -1;
     });
 }
 

@@ -196,6 +196,9 @@ struct Ctx {
     DevBuf ws_bank_idx;  // the per-stream wakeword indices of a bank call with RP_CTX_HOST_POINTERS
     DevBuf ws_gain_tab;  // rp_frontend_batch_bank_sets / _model_bank: the per-stream table of gain_targets_kernel
     DevBuf ws_set_ww, ws_set_agg, ws_set_avg;  // wakeword-set calls: the proposals' bank indices [S][n_win]; the per-slot rows of a call with host pointers
+    // mixed-set calls (rp_batch_detect_mixed_sets): the model rows' staged indices and the model side's four proposal rows [S][n_win] -- the
+    // reference side's live in ws_bank_idx / ws_agg / ws_avg / ws_set_ww, and both are read by one scan
+    DevBuf ws_mix_idx, ws_mix_best, ws_mix_avg, ws_mix_ww, ws_mix_label;
     DevBuf ws_dtw;  // [2 * kDtwSchedChunks | 2 + 2 * kDtwFixCap] uint32: tile counters and fix list of the DTW launchers, zero between calls
     // rp_batch_detect_ingest: copy stream, two device blocks of PCM, per block "copy landed" / "kernels done with it" events
     hipStream_t copy_stream = nullptr;

@@ -249,7 +249,9 @@ enum : uint32_t { kDtwRanMfma = 1u, kDtwRanMfmaWide = 2u, kDtwRanRagged = 4u, kD
                   // dtw_bank_stream_kernel (rp_dtw_bank.hip): the same for the new windows of a live-stream batch
                   kDtwRanBankStream = 8192u,
                   // dtw_set_kernel / dtw_set_stream_kernel (rp_dtw_set.hip): a set of wakewords of a bank per stream
-                  kDtwRanBankSets = 16384u, kDtwRanBankSetsStream = 32768u };
+                  kDtwRanBankSets = 16384u, kDtwRanBankSetsStream = 32768u,
+                  // dtw_mixed_stream_kernel (rp_dtw_mixed.hip): the reference slots of a live-stream batch over mixed sets
+                  kDtwRanMixedSetsStream = 65536u };
 inline void dtw_mark(const DtwWork &wk, uint32_t bit) { if (wk.ran) *wk.ran |= bit; }
 __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { return reinterpret_cast<unsigned long long *>(fix + 2 + 2 * (size_t)kDtwFixCap); }
 // (dtw_fix_append, the kernels' side of the list: rp_device.h)
@@ -938,5 +940,57 @@ hipError_t launch_scan_model_set_stream(hipStream_t st, const BankDev &b, const 
                                         const float *avg, const int32_t *label, const float *vad_value, float vad_mode_value, size_t S, long long f0,
                                         int n_new, const ScanConfig &cfg, void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label,
                                         int32_t *n_det, int max_det);
+
+// ---- mixed sets (rp_mixed_targets.hip, rp_scan_mixed.hip): stream s holds a row of wakeword references of a wakeword bank AND a row of models
+// of a model bank -- one `Rustpotter` with add_wakeword of both kinds (src/detector.rs:304-346,433-447).  Its window is Lmax(s) frames, the
+// longest over the live slots of BOTH rows.
+// One row of a mixed call: rows [S][set_size] of indices into a bank of W entries (ww: BankDev::ww / ModelBank::scan.ww, level: the bank's
+// rms levels).  set_size 0 (rows may be null): the side is absent.
+struct MixedSide {
+    const int32_t *rows = nullptr;
+    int set_size = 0;
+    const BankWakeword *ww = nullptr;
+    const float *level = nullptr;
+    int W = 0;
+};
+// gain_targets_kernel over both rows: the same per-stream table (gain_targets_bytes(S) of workspace) -- table[s].max_len = Lmax(s) over both
+// rows, level[s] = the largest non-NaN level over both, idx[s] = s or -1 -- read by the per-stream gain kernels through `per` and by the
+// mixed scan kernels through per->ww
+hipError_t launch_mixed_targets(hipStream_t st, const MixedSide &refs, const MixedSide &models, size_t S, void *workspace, PerStreamGain *per);
+// The proposals of one side of a whole-recording mixed call, rows win_pitch apart: those of launch_dtw_set (label null) or of
+// launch_nn_score_model_set.  bank: the side's BankDev (ModelBank::scan for models); set_size 0: the side is absent and nothing is read.
+struct MixedProposals {
+    BankDev bank;
+    const int32_t *rows = nullptr;
+    int set_size = 0;
+    const float *best = nullptr, *best_avg = nullptr;
+    const int32_t *best_ww = nullptr, *best_label = nullptr;
+};
+// the state machine of a stream that holds a mixed set: Lmax(s) from table (launch_mixed_targets), per window the better of the two sides'
+// proposals, the reference of equals; a side without a live slot for the stream is not read.  det_ww: the winner's index in ITS OWN bank,
+// det_label: the winner's label for a model, -1 for a reference (both optional).  `hot` as in launch_scan_bank.
+hipError_t launch_scan_mixed_set(hipStream_t st, const MixedProposals &refs, const MixedProposals &models, const BankWakeword *table, size_t win_pitch,
+                                 const float *vad_value, float vad_mode_value, size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det,
+                                 int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det, uint32_t *hot);
+// Live (rp_dtw_mixed.hip, rp_mlp_mixed.hip, rp_scan_mixed.hip): the window of stream s that ends at a new frame starts Lmax(s) - 1 frames
+// before it, with the COMBINED Lmax(s) of `table`; max_window: the longest window any stream of the batch may have (its history + 1).
+// launch_dtw_set_stream with the combined window: q.stream_wakeword [S][set_size], q.agg / q.avg [S][set_size][n_new]; mfcc_size 16 only
+hipError_t launch_dtw_mixed_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size, const BankWakeword *table,
+                                   int max_window);
+// launch_window_means_set_stream / launch_mlp_set_stream with the combined window (max_L: the model bank's longest window);
+// launch_nn_score_set_stream scores their logits as it is
+hipError_t launch_window_means_mixed_stream(hipStream_t st, const ModelBankDev &b, int max_L, int max_window, const int32_t *sets, int set_size,
+                                            const BankWakeword *table, const float *frames, size_t S, size_t cap, size_t fill, size_t n_new,
+                                            float *mean);
+hipError_t launch_mlp_mixed_stream(hipStream_t st, const ModelBankDev &b, int max_L, int max_window, const int32_t *sets, int set_size,
+                                   const BankWakeword *table, const float *frames, size_t S, size_t cap, size_t fill, size_t n_new,
+                                   const float *mean, float *logits);
+// the carried state machine over both sides' slot rows: ragg / ravg [S][ref_size][n_new] under the references' own thresholds (rb: the
+// wakeword bank), magg / mavg / mlabel [S][model_size][n_new] where not -2 (mb: ModelBank::scan); a size of 0: the side is absent
+hipError_t launch_scan_mixed_set_stream(hipStream_t st, const BankDev &rb, const int32_t *ref_rows, int ref_size, const BankDev &mb,
+                                        const int32_t *model_rows, int model_size, const BankWakeword *table, const float *ragg, const float *ravg,
+                                        const float *magg, const float *mavg, const int32_t *mlabel, const float *vad_value, float vad_mode_value,
+                                        size_t S, long long f0, int n_new, const ScanConfig &cfg, void *state, BatchDetection *det, int32_t *det_ww,
+                                        int32_t *det_label, int32_t *n_det, int max_det);
 
 }  // namespace rp

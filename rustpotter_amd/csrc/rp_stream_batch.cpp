@@ -1,5 +1,6 @@
 // rp_stream_batch.cpp -- live-stream batches (rp_stream_batch_*): S streams fed a few chunks per call, every stream's state on the device.
-// A batch holds shared wakewords (references and / or models), or every stream its own: of a wakeword bank, or of a model bank -- one, or a set.
+// A batch holds shared wakewords (references and / or models), or every stream its own: of a wakeword bank, or of a model bank -- one, or a set --
+// or of both banks at once (mixed sets: references and models on one detector per stream).
 #include <cmath>
 #include <cstring>
 
@@ -44,6 +45,15 @@ struct rp_stream_batch {
     // made by rp_stream_batch_new_model_bank_sets (mbank with set_size 1..8): stream s holds the set of models bank_idx[s][0 .. set_size), -1 an
     // empty slot; bank_agg / bank_avg / bank_label and `logits` are then per slot, [S][set_size][frames per call]([label_pitch])
     size_t slots() const { return set_size ? (size_t)set_size : 1; }
+    // made by rp_stream_batch_new_mixed_sets (`mixed`; bank AND mbank set): stream s holds the references bank_idx[s][0 .. set_size) of `bank` and
+    // the models model_idx[s][0 .. mset_size) of `mbank` on one detector; either size may be 0 (the side is absent).  max_len is the longer of the
+    // two banks' windows (reservations included).  bank_agg / bank_avg are the reference slots' scores [S][set_size][frames per call], m_agg /
+    // m_avg / bank_label the model slots' [S][mset_size][..], `logits` [S][mset_size][frames][label_pitch].  gain_tab holds the per-stream table
+    // of mixed_targets_kernel, written at the start of EVERY call: Lmax(s) for the scoring and scan kernels, the level for the gain normaliser.
+    bool mixed = false;
+    int mset_size = 0;
+    DevBuf model_idx, m_agg, m_avg;
+    PerStreamGain mixed_per;   // what the last launch_mixed_targets filled (mixed_per.ww: the table)
     int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
     DevBuf det_ww, det_label, logits, mean, xrows, xs2;
     rp_detector_config cfg{};
@@ -106,9 +116,15 @@ static bool stream_batch_alloc(rp_stream_batch *b) {
         if (!w->agg.reserve(rows * sizeof(float) + 16) || !w->avg.reserve(rows * sizeof(float) + 16) ||
             (w->m && !w->label.reserve(rows * sizeof(int32_t) + 16)))
             return false;
-    if (b->bank && (!b->bank_agg.reserve(rows * b->slots() * sizeof(float) + 16) || !b->bank_avg.reserve(rows * b->slots() * sizeof(float) + 16))) return false;
+    if (b->mixed) {   // a row per reference slot and per model slot; the table of every call
+        const size_t rr = rows * (size_t)b->set_size, mr = rows * (size_t)b->mset_size;
+        if (!b->bank_agg.reserve(rr * sizeof(float) + 16) || !b->bank_avg.reserve(rr * sizeof(float) + 16) || !b->m_agg.reserve(mr * sizeof(float) + 16) ||
+            !b->m_avg.reserve(mr * sizeof(float) + 16) || !b->bank_label.reserve(mr * sizeof(int32_t) + 16) || !b->mean.reserve(mr * 16 * sizeof(float) + 16) ||
+            !b->logits.reserve(mr * (size_t)b->label_pitch * sizeof(float) + 16) || !b->gain_tab.reserve(gain_targets_bytes(S))) return false;
+    }
+    if (!b->mixed && b->bank && (!b->bank_agg.reserve(rows * b->slots() * sizeof(float) + 16) || !b->bank_avg.reserve(rows * b->slots() * sizeof(float) + 16))) return false;
     const size_t mrows = rows * b->slots();   // a batch over model sets: a row per slot
-    if (b->mbank && (!b->bank_agg.reserve(mrows * sizeof(float) + 16) || !b->bank_avg.reserve(mrows * sizeof(float) + 16) ||
+    if (!b->mixed && b->mbank && (!b->bank_agg.reserve(mrows * sizeof(float) + 16) || !b->bank_avg.reserve(mrows * sizeof(float) + 16) ||
                      !b->bank_label.reserve(mrows * sizeof(int32_t) + 16) || !b->mean.reserve(mrows * 16 * sizeof(float) + 16) ||
                      !b->logits.reserve(mrows * (size_t)b->label_pitch * sizeof(float) + 16))) return false;
     if (!b->pcm[0].reserve(pcm_bytes) || !b->pcm[1].reserve(pcm_bytes) || !b->mfcc[0].reserve(S * pitch * K * sizeof(float) + slack) ||
@@ -184,15 +200,33 @@ static bool batch_indices_ok(const Ctx *c, const Bank &bk, size_t first, size_t 
     return !(c->flags & RP_CTX_HOST_POINTERS) || bank_indices_ok(bk.dev.W, first, n, set_size, idx);
 }
 // ... -> the batch's own device copy (a sets batch: rows of set_size indices)
-static bool bank_indices_put(rp_stream_batch *b, size_t first, size_t n, const int32_t *idx) {
+// (dst, row: the batch's array and its row length -- bank_idx with slots() but for the model rows of a mixed batch)
+static bool indices_put(rp_stream_batch *b, DevBuf &dst, size_t row, size_t first, size_t n, const int32_t *idx) {
     Ctx *c = b->c;
     const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
-    const size_t row = b->slots();
-    if (!b->bank_idx.reserve(b->S * row * sizeof(int32_t))) return false;
-    if (!hip_ok(hipMemcpyAsync(b->bank_idx.as<int32_t>() + first * row, idx, n * row * sizeof(int32_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream),
+    if (!dst.reserve(b->S * row * sizeof(int32_t) + 16)) return false;
+    if (row == 0 || n == 0) return true;
+    if (!hip_ok(hipMemcpyAsync(dst.as<int32_t>() + first * row, idx, n * row * sizeof(int32_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream),
                 "hipMemcpyAsync(wakeword indices)")) return false;
     // the caller's host array is the caller's again when the call returns
     return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+}
+static bool bank_indices_put(rp_stream_batch *b, size_t first, size_t n, const int32_t *idx) { return indices_put(b, b->bank_idx, b->slots(), first, n, idx); }
+
+// A batch over mixed sets: both rows of every stream folded over both banks into the per-stream table (Lmax(s), level, idx) -- one short
+// launch at the start of every call, so a bank that changed under the batch is seen from this call on.  A side without rows, or whose bank
+// is empty, is absent.  Refuses banks that outgrew what the batch was sized for.
+static bool mixed_targets(rp_stream_batch *b) {
+    const Bank &bk = *b->bank;
+    const ModelBank &mb = *b->mbank;
+    if ((bk.dev.W && (bk.dev.K != 16 || bk.dev.max_len > b->max_len)) || (mb.dev.W && (mb.max_L > b->max_len || mb.dev.label_pitch != b->label_pitch))) {
+        set_last_error("stream batch: a bank outgrew what the batch was sized for");
+        return false;
+    }
+    MixedSide rs, ms;
+    if (b->set_size && bk.dev.W) { rs.rows = b->bank_idx.as<int32_t>(); rs.set_size = b->set_size; rs.ww = bk.dev.ww; rs.level = bk.rms_level; rs.W = bk.dev.W; }
+    if (b->mset_size && mb.dev.W) { ms.rows = b->model_idx.as<int32_t>(); ms.set_size = b->mset_size; ms.ww = mb.scan.ww; ms.level = mb.rms_level(); ms.W = mb.dev.W; }
+    return hip_ok(launch_mixed_targets(b->c->stream, rs, ms, b->S, b->gain_tab.p, &b->mixed_per), "mixed_targets_kernel");
 }
 
 // what the MFCC front of a call reads: the caller's chunks where they lie on the device, or the resampler's 16 kHz output
@@ -231,11 +265,15 @@ static bool stream_frames(rp_stream_batch *b, const MfccTablesDev &tb, const Str
     // 16 kHz mono input is read where it lies: the MFCC kernel takes [history chunk | new chunks] from two buffers and
     // leaves the last chunk as the next call's history.  Other inputs are staged into one row per stream first.
     bool staged = b->filters_on() || b->rs || in.channels != 1;
+    if (b->mixed && !mixed_targets(b)) return false;   // every call: the scoring and scan kernels read Lmax(s) from the table
     if (b->filters_on()) {
         // with filters, ONE launch in the place of launch_stream_stage: history chunk | the new chunks decoded and filtered, levels kept
         const rp_gain_normalization_config &g = b->filt.gain_normalizer;
         PerStreamGain per;
-        if (b->prep_gain) {
+        if (b->mixed) {
+            per = b->mixed_per;
+            per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
+        } else if (b->prep_gain) {
             GainSource src;
             if (b->mbank) { src.ww = b->mbank->scan.ww; src.level = b->mbank->rms_level(); src.W = b->mbank->dev.W; }
             else { src.ww = b->bank->dev.ww; src.level = b->bank->rms_level; src.W = b->bank->dev.W; }
@@ -344,6 +382,15 @@ static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, con
     }
     const float vm = vad_mode_value(b->cfg.vad_mode);
     const long long f0 = (long long)b->fpf() * (long long)b->chunks_seen - 3;
+    if (b->mixed) {   // Lmax(s) from this call's table; the references' own thresholds from the bank, the models' gates applied by nn_score_set_stream_kernel
+        const ScanConfig sc = scan_config(b->cfg, 0, true, (int)b->fpf());
+        return timed(c, kKernelScan, "scan_mixed_set_stream_kernel", [&] {
+            return launch_scan_mixed_set_stream(c->stream, b->bank->dev, b->bank_idx.as<int32_t>(), b->set_size, b->mbank->scan, b->model_idx.as<int32_t>(),
+                                                b->mset_size, b->mixed_per.ww, b->bank_agg.as<float>(), b->bank_avg.as<float>(), b->m_agg.as<float>(),
+                                                b->m_avg.as<float>(), b->bank_label.as<int32_t>(), dv, vm, b->S, f0, (int)n_new, sc, b->state.p, dd, dw, dl, dn,
+                                                max_det);
+        });
+    }
     if (b->mbank) {
         // window length (countdown L / 2) per stream from the bank's scan entries; their thresholds are -1: nn_score_bank_stream_kernel applied the gates
         const ScanConfig sc = scan_config(b->cfg, 0, true, (int)b->fpf());
@@ -430,14 +477,56 @@ static bool score_model_bank_stream(rp_stream_batch *b, const NewFrames &f, size
                                               b->bank_label.as<int32_t>()), "nn_score_bank_stream_kernel");
 }
 
+// A batch over mixed sets: the reference slots' scores -> bank_agg / bank_avg (dtw_mixed_stream_kernel) and the model slots' logits, scores and
+// labels -> logits, m_agg / m_avg / bank_label (one forward launch), every window Lmax(s) frames long with the combined Lmax(s) of this call's
+// table.  band_size 0 and an empty wakeword bank: zero reference rows; an empty model bank: zero logits, and the scan reads no model row.
+static bool score_mixed_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new, bool detect_only) {
+    Ctx *c = b->c;
+    const Bank &bk = *b->bank;
+    const ModelBank &mb = *b->mbank;
+    const BankWakeword *table = b->mixed_per.ww;
+    b->slot_frames = b->logit_frames = n_new;
+    if (b->set_size) {
+        const size_t bytes = b->S * (size_t)b->set_size * n_new * sizeof(float);
+        if (b->cfg.band_size == 0 || bk.dev.W == 0) {
+            if (!hip_ok(hipMemsetAsync(b->bank_agg.p, 0, bytes, c->stream), "hipMemsetAsync") || !hip_ok(hipMemsetAsync(b->bank_avg.p, 0, bytes, c->stream), "hipMemsetAsync"))
+                return false;
+        } else {
+            BankStreamScore q;
+            q.mfcc = f.rows; q.S = b->S; q.frame_pitch = b->cap; q.first_new = f.fill; q.n_new = n_new; q.stream_wakeword = b->bank_idx.as<int32_t>();
+            q.band = (int)b->cfg.band_size; q.score_mode = (int)b->cfg.score_mode; q.score_ref = b->cfg.score_ref; q.gate = detect_only ? 1 : 0;
+            q.avg_threshold = b->cfg.avg_threshold; q.agg = b->bank_agg.as<float>(); q.avg = b->bank_avg.as<float>();
+            const DtwWork wk = c->dtw_work();
+            q.fix = wk.fix;
+            dtw_mark(wk, kDtwRanMixedSetsStream);
+            if (!timed(c, kKernelDtw, "dtw_mixed_stream_kernel", [&] { return launch_dtw_mixed_stream(c->stream, bk.dev, q, b->set_size, table, b->max_len); }))
+                return false;
+        }
+    }
+    if (!b->mset_size) return true;
+    const int32_t *idx = b->model_idx.as<int32_t>();
+    float *mean = b->mean.as<float>(), *dlog = b->logits.as<float>();
+    if (mb.dev.W == 0)   // no model yet: rp_stream_batch_logits answers zero rows
+        return !b->label_pitch || hip_ok(hipMemsetAsync(b->logits.p, 0, b->S * (size_t)b->mset_size * n_new * (size_t)b->label_pitch * sizeof(float), c->stream), "hipMemsetAsync");
+    if (!hip_ok(launch_window_means_mixed_stream(c->stream, mb.dev, mb.max_L, b->max_len, idx, b->mset_size, table, f.rows, b->S, b->cap, f.fill, n_new, mean),
+                "window_means_mixed_stream_kernel")) return false;
+    if (!timed(c, kKernelMlp, "mlp_mixed_stream_kernel", [&] {
+            return launch_mlp_mixed_stream(c->stream, mb.dev, mb.max_L, b->max_len, idx, b->mset_size, table, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); }))
+        return false;
+    return hip_ok(launch_nn_score_set_stream(c->stream, mb.dev, idx, b->mset_size, dlog, b->S, n_new, b->cfg.score_ref * 10.f, b->cfg.avg_threshold != 0.f ? 1 : 0,
+                                             b->cfg.threshold, b->cfg.avg_threshold, b->m_agg.as<float>(), b->m_avg.as<float>(), b->bank_label.as<int32_t>()),
+                  "nn_score_set_stream_kernel");
+}
+
 // Score + scan stage: scores of this call's n_new windows per stream for every wakeword, then the state machine over all of them.
 // detect_only: nobody reads the per-window arrays.
 static bool stream_score_and_scan(rp_stream_batch *b, Staged &sg, const NewFrames &f, size_t n_new, bool detect_only, BatchDetection *dd,
                                   int32_t *dn, int max_det, int32_t *det_wakeword, int32_t *det_label) {
     ScanWakewords sw{};
     sw.n = (int)b->ww.size();
-    if (b->bank && !score_bank_stream(b, f, n_new, detect_only)) return false;
-    if (b->mbank && !score_model_bank_stream(b, f, n_new)) return false;
+    if (b->mixed) { if (!score_mixed_stream(b, f, n_new, detect_only)) return false; }
+    else if (b->bank && !score_bank_stream(b, f, n_new, detect_only)) return false;
+    else if (b->mbank && !score_model_bank_stream(b, f, n_new)) return false;
     for (size_t j = 0; j < b->ww.size(); ++j)
         if (!(b->ww[j]->t ? score_reference(b, *b->ww[j], f, n_new, detect_only, sw, j) : score_model(b, *b->ww[j], f, n_new, sw, j))) return false;
     const size_t col = b->S * (size_t)max_det * sizeof(int32_t);
@@ -461,6 +550,11 @@ static int stream_batch_process(rp_stream_batch *b, const void *pcm, rp_sample_f
         const size_t in_chunk = b->in_len * (size_t)b->channels;
         if (pcm_stride < n_chunks * in_chunk) { set_last_error("pcm_stride smaller than n_chunks * samples per chunk"); return -1; }
         if (!sample_format_ok(fmt)) return -1;
+        if (b->mixed && agg) {
+            set_last_error("rp_stream_batch_process: a batch over mixed sets has no single aggregate per window; rp_stream_batch_slot_scores returns the reference "
+                           "slots' scores, rp_stream_batch_logits the model slots' logits");
+            return -1;
+        }
         if (b->mbank && agg) {
             set_last_error("rp_stream_batch_process: a batch over a model bank has no aggregate per window; its per-window output is the logits (rp_stream_batch_logits)");
             return -1;
@@ -589,6 +683,92 @@ int rp_stream_batch_new_model_bank_sets(rp_ctx *ctx, const rp_model_bank *bank, 
                                         const rp_detector_config *config, size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
     return stream_batch_new_model_bank(ctx, bank, stream_models, true, set_size, config, S, max_chunks_per_call, out);
 }
+// live-stream batches over MIXED sets: stream s holds the references bank[stream_wakewords[s][..]] and the models model_bank[stream_models[s][..]]
+// on one detector (rp_batch_detect_mixed_sets with the state carried)
+// the two set sizes of a mixed batch: 0 .. 8 each, the text of rp_batch_detect_mixed_sets
+static bool mixed_sizes_ok(int ref_set_size, int model_set_size) {
+    if (ref_set_size < 0 || ref_set_size > RP_WAKEWORD_SET_MAX) {
+        set_last_error("ref_set_size " + std::to_string(ref_set_size) + " is outside 0 .. " + std::to_string((int)RP_WAKEWORD_SET_MAX) + " (RP_WAKEWORD_SET_MAX)");
+        return false;
+    }
+    if (model_set_size < 0 || model_set_size > RP_MODEL_SET_MAX) {
+        set_last_error("model_set_size " + std::to_string(model_set_size) + " is outside 0 .. " + std::to_string((int)RP_MODEL_SET_MAX) + " (RP_MODEL_SET_MAX)");
+        return false;
+    }
+    return true;
+}
+// both rows of streams first .. first + n - 1 in HOST arrays: every index within its bank, else an error that names stream, slot and side
+static bool mixed_rows_ok(const Ctx *c, const Bank &bk, int ref_set_size, const int32_t *refs, const ModelBank &mb, int model_set_size, const int32_t *models,
+                          size_t first, size_t n) {
+    if (!(c->flags & RP_CTX_HOST_POINTERS)) return true;
+    return (!ref_set_size || bank_indices_ok(bk.dev.W, first, n, ref_set_size, refs, "wakeword index")) &&
+           (!model_set_size || bank_indices_ok(mb.dev.W, first, n, model_set_size, models, "model index"));
+}
+int rp_stream_batch_new_mixed_sets(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size,
+                                   const rp_model_bank *model_bank, const int32_t *stream_models, int model_set_size, const rp_detector_config *config,
+                                   size_t S, size_t max_chunks_per_call, rp_stream_batch **out) {
+    return guarded([&]() -> int {
+        if (!ctx || !bank || !model_bank) { set_last_error("null handle"); return -1; }
+        if (!config || !out) { set_last_error("null argument"); return -1; }
+        *out = nullptr;
+        if (!mixed_sizes_ok(ref_set_size, model_set_size)) return -1;
+        if ((ref_set_size && !stream_wakewords) || (model_set_size && !stream_models)) { set_last_error("null argument"); return -1; }
+        const Bank &bk = *bank->impl;
+        const ModelBank &mb = *model_bank->impl;
+        Ctx *c = ctx->impl.get();
+        if (bk.ctx != c) { set_last_error("the wakeword bank belongs to another context"); return -1; }
+        if (mb.ctx != c) { set_last_error("the model bank belongs to another context"); return -1; }
+        if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
+        if (S == 0 || max_chunks_per_call == 0) { set_last_error("rp_stream_batch_new_mixed_sets: S and max_chunks_per_call must be >= 1"); return -1; }
+        // add_wakeword, src/detector.rs:316-319: a model bank is at mfcc_size 16 (an empty bank that was never reserved has a placeholder size)
+        if ((bk.dev.W || bk.ceiling) && bk.dev.K != 16) { set_last_error("Usage of wakewords with different mfcc size is not supported, ignoring wakeword"); return -1; }
+        if (!bank_band_ok(bk, (int)config->band_size)) return -1;
+        if (config->band_size != 0 && dtw_register_tile(16, (int)config->band_size) <= 0) {
+            set_last_error("rp_stream_batch_new_mixed_sets: band_size " + std::to_string((int)config->band_size) + " is not built (3..6, or 0)");
+            return -1;
+        }
+        // before anything is allocated
+        if (!mixed_rows_ok(c, bk, ref_set_size, stream_wakewords, mb, model_set_size, stream_models, 0, S)) return -1;
+        std::unique_ptr<rp_stream_batch> b(new rp_stream_batch());
+        b->mixed = true; b->set_size = ref_set_size; b->mset_size = model_set_size;
+        b->c = c; b->bank = &bk; ++bk.live_batches; b->mbank = &mb; ++mb.live_batches; b->cfg = *config; b->S = S; b->max_chunks = max_chunks_per_call;
+        // the history of the longer of the two banks' windows, reservations included: what a bank-sets batch and a model-sets batch would keep
+        b->K = 16; b->max_len = std::max(bk.max_window(), mb.max_window()); b->label_pitch = mb.dev.label_pitch; b->Tmax = 1;
+        if (!indices_put(b.get(), b->bank_idx, (size_t)ref_set_size, 0, S, stream_wakewords) ||
+            !indices_put(b.get(), b->model_idx, (size_t)model_set_size, 0, S, stream_models)) return -1;
+        if (!c->tables_for(b->K)) return -1;
+        b->hist_frames = (size_t)b->max_len - 1;
+        if (!stream_batch_alloc(b.get())) return -1;
+        *out = b.release();
+        return 0;
+    });
+}
+// Re-target streams first_stream .. first_stream + n - 1 of such a batch: both rows removed, the new ones added in order (references, then
+// models), the stream reset.  A refused row changes nothing.
+int rp_stream_batch_set_mixed_sets(rp_stream_batch *b, size_t first_stream, size_t n, const int32_t *stream_wakewords, const int32_t *stream_models) {
+    bool touched = false;
+    const int r = guarded([&]() -> int {
+        Ctx *c = stream_batch_enter(b, true);
+        if (!c) return -1;
+        if (!b->mixed) { set_last_error("rp_stream_batch_set_mixed_sets: the batch was not made by rp_stream_batch_new_mixed_sets"); return -1; }
+        if (first_stream > b->S || n > b->S - first_stream) {
+            set_last_error("rp_stream_batch_set_mixed_sets: streams " + std::to_string(first_stream) + " .. " + std::to_string(first_stream) + " + " +
+                           std::to_string(n) + " reach past the batch's " + std::to_string(b->S) + " streams");
+            return -1;
+        }
+        if (n == 0) return 0;
+        if ((b->set_size && !stream_wakewords) || (b->mset_size && !stream_models)) { set_last_error("null argument"); return -1; }
+        // a refused index on either side leaves the batch as it was
+        if (!mixed_rows_ok(c, *b->bank, b->set_size, stream_wakewords, *b->mbank, b->mset_size, stream_models, first_stream, n)) return -1;
+        touched = true;
+        if (!indices_put(b, b->bank_idx, (size_t)b->set_size, first_stream, n, stream_wakewords) ||
+            !indices_put(b, b->model_idx, (size_t)b->mset_size, first_stream, n, stream_models)) return -1;
+        return hip_ok(launch_stream_state_reset_range(c->stream, b->state.p, b->S, first_stream, n, (long long)b->fpf() * (long long)b->chunks_seen),
+                      "stream_state_reset_kernel") ? 0 : -1;
+    });
+    if (r != 0 && touched) b->poisoned = true;
+    return r;
+}
 void rp_stream_batch_free(rp_stream_batch *b) { delete b; }
 size_t rp_stream_batch_chunks_seen(const rp_stream_batch *b) { return b ? b->chunks_seen : 0; }
 
@@ -628,6 +808,17 @@ static int stream_batch_set_filters(rp_stream_batch *b, const rp_filters_config 
         if (b && !filters) { set_last_error("null argument"); return -1; }
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (b->mixed && per_stream) {
+            set_last_error(name + ": a batch over mixed sets takes its level and window from several wakewords of two banks per stream; "
+                                  "rp_stream_batch_set_filters_per_stream gives it the gain normaliser");
+            return -1;
+        }
+        if (b->mixed && filters->gain_normalizer.enabled && !prepared) {
+            set_last_error("rp_stream_batch_set_filters: the gain normaliser is not available on a batch over mixed sets (its window and rms_level_ref would be "
+                           "per stream); the band-pass filter alone is, and rp_stream_batch_set_filters_per_stream gives every stream the gain normaliser "
+                           "of its own wakewords");
+            return -1;
+        }
         if (prepared && !b->bank && !b->mbank) {
             set_last_error(name + ": the batch holds shared wakewords, one level and one window for every stream; rp_stream_batch_set_filters takes them");
             return -1;
@@ -726,6 +917,11 @@ static int stream_batch_set_wakewords(rp_stream_batch *b, size_t first_stream, s
     const int r = guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (b->mixed) {
+            set_last_error(std::string(sets ? "rp_stream_batch_set_wakeword_sets" : "rp_stream_batch_set_wakewords") +
+                           ": the batch runs over mixed sets (rp_stream_batch_new_mixed_sets), whose streams are re-targeted with rp_stream_batch_set_mixed_sets, both rows at once");
+            return -1;
+        }
         if (b->mbank) {
             set_last_error(std::string(sets ? "rp_stream_batch_set_wakeword_sets" : "rp_stream_batch_set_wakewords") +
                            (b->set_size ? ": the batch runs over model sets (rp_stream_batch_new_model_bank_sets), whose streams are re-targeted with rp_stream_batch_set_model_sets"
@@ -768,6 +964,10 @@ static int stream_batch_set_models(rp_stream_batch *b, size_t first_stream, size
         const std::string name = sets ? "rp_stream_batch_set_model_sets" : "rp_stream_batch_set_models";
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (b->mixed) {
+            set_last_error(name + ": the batch runs over mixed sets (rp_stream_batch_new_mixed_sets), whose streams are re-targeted with rp_stream_batch_set_mixed_sets, both rows at once");
+            return -1;
+        }
         if (sets && !(b->mbank && b->set_size)) { set_last_error(name + ": the batch was not made by rp_stream_batch_new_model_bank_sets"); return -1; }
         if (!b->mbank) { set_last_error(name + ": the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
         if (!sets && b->set_size) { set_last_error(name + ": the batch holds model sets (rp_stream_batch_new_model_bank_sets); use rp_stream_batch_set_model_sets"); return -1; }
@@ -803,7 +1003,7 @@ int rp_stream_batch_logits(rp_stream_batch *b, float *logits) {
         if (!c) return -1;
         if (!b->mbank) { set_last_error("rp_stream_batch_logits: the batch was not made by rp_stream_batch_new_model_bank"); return -1; }
         if (!b->logit_frames) { set_last_error("rp_stream_batch_logits: the streams have not received audio yet"); return -1; }
-        const size_t bytes = b->S * b->slots() * b->logit_frames * (size_t)b->label_pitch * sizeof(float);
+        const size_t bytes = b->S * (b->mixed ? (size_t)b->mset_size : b->slots()) * b->logit_frames * (size_t)b->label_pitch * sizeof(float);
         if (bytes == 0) return 0;   // an empty bank has no labels
         if (!logits) { set_last_error("null argument"); return -1; }
         const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
@@ -816,6 +1016,15 @@ int rp_stream_batch_slot_scores(rp_stream_batch *b, float *agg, float *avg) {
     return guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
+        if (b->mixed) {   // the reference slots' rows; the model slots' per-window output is rp_stream_batch_logits
+            if (!b->slot_frames) { set_last_error("rp_stream_batch_slot_scores: the streams have not received audio yet"); return -1; }
+            const size_t bytes = b->S * (size_t)b->set_size * b->slot_frames * sizeof(float);
+            const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
+            const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+            if (bytes && agg && !hip_ok(hipMemcpyAsync(agg, b->bank_agg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
+            if (bytes && avg && !hip_ok(hipMemcpyAsync(avg, b->bank_avg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
+            return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
+        }
         if (b->mbank && b->set_size) { set_last_error("rp_stream_batch_slot_scores: a batch over model sets keeps no aggregate per slot; rp_stream_batch_logits returns its per-slot, per-window output"); return -1; }
         if (b->mbank) { set_last_error("rp_stream_batch_slot_scores: a batch over a model bank has one model per stream and no slots; rp_stream_batch_logits returns its per-window output"); return -1; }
         if (!b->set_size) { set_last_error("rp_stream_batch_slot_scores: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
