@@ -1044,7 +1044,7 @@ int rp_stream_batch_set_model_sets(rp_stream_batch *b, size_t first_stream, size
  * largest rms_level of its wakewords, NaN ignored (f32::max folded from NaN; NaN when none has a level: gain 1), over a window of
  * max_mfcc_frames / 3 chunk levels, at least 1 (on_wakeword_change, src/detector.rs:328-338; set_rms_level_ref,
  * gain_normalizer_filter.rs:42-48).  For stream s that is target(s) = the largest non-NaN level and Lmax(s) = the longest window over the
- * live slots of its row; one short kernel (gain_targets_kernel) prepares both per stream in front of the per-stream gain kernels of
+ * live slots of its row; one short kernel (stream_targets_kernel) prepares both per stream in front of the per-stream gain kernels of
  * rp_frontend_batch_bank and rp_stream_batch_set_filters_bank, which are unchanged.  A model's level is part of the model bank:
  * WakewordModel::rms_level, kept from the .rpw files by rp_model_bank_new_from_rpw / _put_from_rpw, the level of the trained file after
  * rp_model_bank_train (rustpotter's trainer: the running mean of the non-"none" samples' levels), NaN for models given as handles
@@ -1108,7 +1108,7 @@ int rp_stream_batch_set_filters_per_stream(rp_stream_batch *b, const rp_filters_
  * names stream, slot and side ("wakeword index" / "model index"), found before anything is allocated or launched; with device arrays it
  * counts as -1.  Two empty banks, or rows of all -1: the call succeeds and reports nothing.  VAD and the reset after a detection as
  * everywhere.  rp_ctx_dtw_kernels reports RP_DTW_KERNEL_BANK_SETS: the call runs dtw_set_kernel and the model-set forward as they are, one
- * short kernel (mixed_targets_kernel) folds Lmax(s) per stream, and one scan (scan_mixed_set_kernel) reads both kinds' proposals. */
+ * short kernel (stream_targets_kernel) folds Lmax(s) per stream, and one scan (scan_mixed_set_kernel) reads both kinds' proposals. */
 int rp_batch_detect_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                                const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size, const rp_model_bank *model_bank,
                                const int32_t *stream_models, int model_set_size, const rp_detector_config *config, int precision,
@@ -1124,7 +1124,7 @@ int rp_frontend_batch_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format 
 /* Mixed sets on LIVE streams: rp_batch_detect_mixed_sets with the state carried between calls.  History per stream is the larger of what a
  * bank-sets batch and a model-sets batch would keep, reservations included; both banks count the batch, and both may change under it by
  * rp_wakeword_bank_put / _put_from_rpw / _enrol and rp_model_bank_put / _put_from_rpw / _train within what the batch was sized for: Lmax(s),
- * every threshold and the gain normaliser's level are read from the banks at the start of EVERY process call (mixed_targets_kernel), so a
+ * every threshold and the gain normaliser's level are read from the banks at the start of EVERY process call (stream_targets_kernel), so a
  * changed bank is seen from the next call.  A process call scores the reference slots with dtw_mixed_stream_kernel (rp_ctx_dtw_kernels reports
  * RP_DTW_KERNEL_MIXED_SETS_STREAM and only that bit) and the model slots with ONE forward launch (mlp_mixed_stream_kernel); the window that
  * ends at a new frame starts Lmax(s) - 1 frames before it for every slot of either kind.  A stream fed in pieces reports the detections of

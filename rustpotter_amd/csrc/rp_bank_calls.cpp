@@ -1,9 +1,9 @@
 // rp_bank_calls.cpp -- the whole-recording calls over a bank.  Stream s is scored against ITS wakeword of a wakeword bank (rp_dtw_score_bank,
 // rp_batch_detect_bank, rp_frontend_batch_bank; kernels: rp_dtw_bank.hip, scan_bank_kernel in rp_scan.hip), against its own SET of wakewords
-// (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets; rp_dtw_set.hip, rp_scan_set.hip), or is run by ITS model of a model bank
+// (rp_dtw_score_bank_sets, rp_batch_detect_bank_sets; rp_dtw_set.hip, rp_scan_sets.hip), or is run by ITS model of a model bank
 // (rp_mlp_forward_windows_bank, rp_batch_detect_model_bank; mlp_windows_bank_kernel, window_means_bank_kernel, nn_score_bank_kernel in
 // rp_mlp_windows.hip / rp_mlp.hip), or holds references of a wakeword bank AND models of a model bank on one detector (mixed sets:
-// rp_batch_detect_mixed_sets, rp_frontend_batch_mixed_sets; rp_mixed_targets.hip, scan_mixed_set_kernel in rp_scan_mixed.hip).  Every call
+// rp_batch_detect_mixed_sets, rp_frontend_batch_mixed_sets; rp_gain_targets.hip, scan_mixed_set_kernel in rp_scan_sets.hip).  Every call
 // reads: arguments, staged indices, the empty-bank answer, front, score, scan, copy back.  The banks themselves are rp_bank.cpp and
 // rp_model_bank.cpp; DESIGN.md sections 4.2 - 4.4.
 #include <algorithm>
@@ -273,7 +273,7 @@ int rp_frontend_batch_bank(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, s
 }
 
 // ... with every stream's SET of wakewords: the level and window of on_wakeword_change (src/detector.rs:328-338) per stream, prepared by
-// gain_targets_kernel in front of the same kernels.  Indices as rp_dtw_score_bank_sets takes them.
+// stream_targets_kernel in front of the same kernels.  Indices as rp_dtw_score_bank_sets takes them.
 int rp_frontend_batch_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                                 const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int set_size,
                                 float *pcm_out, size_t out_stride, float *rms, float *gains) {
@@ -287,10 +287,9 @@ int rp_frontend_batch_bank_sets(rp_ctx *ctx, const void *pcm, rp_sample_format f
         Staged sg(c);
         BankIndices bi;   // a refused index: before anything is launched or written
         if (!stage_bank_indices(c, sg, bk, stream_wakewords, S, set_size, 0, &bi)) return -1;
-        GainSource src;
-        src.ww = bk.dev.ww; src.level = bk.rms_level; src.W = bk.dev.W;
-        return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(bk.dev.max_len / 3, 1), nullptr, bi.dev, pcm_out,
-                              out_stride, rms, gains, &src, set_size);
+        const TargetSide sides[2] = {{bi.dev, set_size, bk.dev.ww, bk.rms_level, bk.dev.W}, {}};
+        return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(bk.dev.max_len / 3, 1), nullptr, nullptr, pcm_out,
+                              out_stride, rms, gains, sides);
     });
 }
 
@@ -308,10 +307,9 @@ int rp_frontend_batch_model_bank(rp_ctx *ctx, const void *pcm, rp_sample_format 
         Staged sg(c);
         BankIndices bi;
         if (!stage_indices(c, sg, bk.dev.W, bk.min_L, [&](size_t w) { return bk.e[w].L; }, "model index", stream_models, S, set_size, 0, &bi)) return -1;
-        GainSource src;
-        src.ww = bk.scan.ww; src.level = bk.rms_level(); src.W = bk.dev.W;
-        return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(bk.max_L / 3, 1), nullptr, bi.dev, pcm_out,
-                              out_stride, rms, gains, &src, set_size);
+        const TargetSide sides[2] = {{bi.dev, set_size, bk.scan.ww, bk.rms_level(), bk.dev.W}, {}};
+        return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(bk.max_L / 3, 1), nullptr, nullptr, pcm_out,
+                              out_stride, rms, gains, sides);
     });
 }
 
@@ -604,7 +602,7 @@ bool mixed_enter(rp_ctx *ctx, const rp_wakeword_bank *bank, const int32_t *strea
 extern "C" {
 
 // rp_frontend_batch_bank_sets over both rows: the level and window of on_wakeword_change over every live slot of either kind, prepared by
-// mixed_targets_kernel in front of the same per-stream gain kernels
+// stream_targets_kernel in front of the same per-stream gain kernels
 int rp_frontend_batch_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride,
                                  const rp_filters_config *filters, const rp_wakeword_bank *bank, const int32_t *stream_wakewords, int ref_set_size,
                                  const rp_model_bank *model_bank, const int32_t *stream_models, int model_set_size, float *pcm_out, size_t out_stride,
@@ -620,12 +618,12 @@ int rp_frontend_batch_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format 
         if (m.refs_on && !stage_bank_indices(c, sg, bk, stream_wakewords, S, ref_set_size, 0, &ri)) return -1;
         if (m.models_on && !stage_indices(c, sg, mb.dev.W, mb.min_L, [&](size_t w) { return mb.e[w].L; }, "model index", stream_models, S, model_set_size, 0,
                                           &mi, nullptr, &c->ws_mix_idx)) return -1;
-        MixedSide sides[2];
-        if (m.refs_on) { sides[0].rows = ri.dev; sides[0].set_size = ref_set_size; sides[0].ww = bk.dev.ww; sides[0].level = bk.rms_level; sides[0].W = bk.dev.W; }
-        if (m.models_on) { sides[1].rows = mi.dev; sides[1].set_size = model_set_size; sides[1].ww = mb.scan.ww; sides[1].level = mb.rms_level(); sides[1].W = mb.dev.W; }
+        TargetSide sides[2];
+        if (m.refs_on) sides[0] = {ri.dev, ref_set_size, bk.dev.ww, bk.rms_level, bk.dev.W};
+        if (m.models_on) sides[1] = {mi.dev, model_set_size, mb.scan.ww, mb.rms_level(), mb.dev.W};
         const int longest = std::max(m.refs_on ? bk.dev.max_len : 0, m.models_on ? mb.max_L : 0);   // the capacity of a stream's ring
         return frontend_batch(c, pcm, fmt, S, n_samples, pcm_stride, filters, 0.f, (size_t)std::max(longest / 3, 1), nullptr, nullptr, pcm_out, out_stride,
-                              rms, gains, nullptr, 0, sides);
+                              rms, gains, sides);
     });
 }
 
@@ -670,15 +668,15 @@ int rp_batch_detect_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fm
         if (m.models_on && (!c->ws_ring.reserve(rows * (size_t)model_set_size * (size_t)mb.dev.label_pitch * sizeof(float) + 16) ||
                             !c->ws_mix_best.reserve(rows * sizeof(float) + 16) || !c->ws_mix_avg.reserve(rows * sizeof(float) + 16) ||
                             !c->ws_mix_ww.reserve(rows * sizeof(int32_t) + 16) || !c->ws_mix_label.reserve(rows * sizeof(int32_t) + 16))) return -1;
-        MixedSide sides[2];
+        TargetSide sides[2];
         MixedProposals pr, pm;
         if (m.refs_on) {
-            sides[0].rows = ri.dev; sides[0].set_size = ref_set_size; sides[0].ww = bk.dev.ww; sides[0].level = bk.rms_level; sides[0].W = bk.dev.W;
+            sides[0] = {ri.dev, ref_set_size, bk.dev.ww, bk.rms_level, bk.dev.W};
             pr.bank = bk.dev; pr.rows = ri.dev; pr.set_size = ref_set_size;
             pr.best = c->ws_agg.as<float>(); pr.best_avg = c->ws_avg.as<float>(); pr.best_ww = c->ws_set_ww.as<int32_t>();
         }
         if (m.models_on) {
-            sides[1].rows = q.idx.dev; sides[1].set_size = model_set_size; sides[1].ww = mb.scan.ww; sides[1].level = mb.rms_level(); sides[1].W = mb.dev.W;
+            sides[1] = {q.idx.dev, model_set_size, mb.scan.ww, mb.rms_level(), mb.dev.W};
             pm.bank = mb.scan; pm.rows = q.idx.dev; pm.set_size = model_set_size;
             pm.best = c->ws_mix_best.as<float>(); pm.best_avg = c->ws_mix_avg.as<float>(); pm.best_ww = c->ws_mix_ww.as<int32_t>();
             pm.best_label = c->ws_mix_label.as<int32_t>();
@@ -686,7 +684,7 @@ int rp_batch_detect_mixed_sets(rp_ctx *ctx, const void *pcm, rp_sample_format fm
         uint32_t *hot = nullptr;
         PerStreamGain per;   // (its table is what the scan reads Lmax(s) from)
         if (S) {
-            if (!hip_ok(launch_mixed_targets(c->stream, sides[0], sides[1], S, c->ws_gain_tab.p, &per), "mixed_targets_kernel")) return -1;
+            if (!hip_ok(launch_stream_targets(c->stream, sides[0], sides[1], S, c->ws_gain_tab.p, &per), "stream_targets_kernel")) return -1;
             // both scoring kernels raise the same flag per stream with a proposal: the scan skips the others and puts the flags back
             hot = c->hot_flags(S);
             if (!hot) return -1;

@@ -37,7 +37,7 @@ namespace rp {
 
 int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, const rp_filters_config *filters,
                    float rms_level_ref, size_t window_size, const Bank *bank, const int32_t *stream_wakeword, float *pcm_out, size_t out_stride,
-                   float *rms, float *gains, const GainSource *sets, int set_size, const MixedSide *mixed) {
+                   float *rms, float *gains, const TargetSide *sides) {
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return -1;
     if (pcm_stride < n_samples || out_stride < n_samples) { set_last_error("stride smaller than n_samples"); return -1; }
     if (!sample_format_ok(fmt)) return -1;
@@ -45,8 +45,8 @@ int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size
     const rp_gain_normalization_config &g = filters->gain_normalizer;
     const rp_band_pass_config &b = filters->band_pass;
     if (bank) window_size = (size_t)std::max(bank->dev.max_len / 3, 1);   // the ring's capacity: the bank's largest window (src/detector.rs:337)
-    else if (!sets && !mixed && g.enabled && g.has_gain_ref) rms_level_ref = g.gain_ref;   // fixed_rms_level, gain_normalizer_filter.rs:56-66
-    // (sets: window_size is the caller's, the largest window of the bank the rows index)
+    else if (!sides && g.enabled && g.has_gain_ref) rms_level_ref = g.gain_ref;   // fixed_rms_level, gain_normalizer_filter.rs:56-66
+    // (sides: window_size is the caller's, the largest window of the banks the rows index)
     if (window_size == 0) window_size = 1;                                // set_rms_level_ref :47
     if (window_size > 1u << 20) { set_last_error("window_size too large"); return -1; }
     float q[5];
@@ -62,14 +62,9 @@ int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size
         per.ww = bank->dev.ww; per.rms_level = bank->rms_level; per.W = bank->dev.W;
         per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
     }
-    if (sets) {  // stream_wakeword: the staged DEVICE rows of set_size indices; every stream's level and window, prepared in front of the gain kernel
+    if (sides) {  // the staged DEVICE rows of one bank, or of references and of models: every stream's level and window, prepared in front of the gain kernel
         if (!c->ws_gain_tab.reserve(gain_targets_bytes(S))) return -1;
-        if (!hip_ok(launch_gain_targets(c->stream, *sets, stream_wakeword, set_size, S, c->ws_gain_tab.p, &per), "gain_targets_kernel")) return -1;
-        per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
-    }
-    if (mixed) {  // the same table folded over a row of references and a row of models (mixed sets): the staged DEVICE rows are in mixed[0] / mixed[1]
-        if (!c->ws_gain_tab.reserve(gain_targets_bytes(S))) return -1;
-        if (!hip_ok(launch_mixed_targets(c->stream, mixed[0], mixed[1], S, c->ws_gain_tab.p, &per), "mixed_targets_kernel")) return -1;
+        if (!hip_ok(launch_stream_targets(c->stream, sides[0], sides[1], S, c->ws_gain_tab.p, &per), "stream_targets_kernel")) return -1;
         per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
     }
     const void *dp = sg.in(pcm, S * pcm_stride * sample_bytes(fmt), c->stage_in);
@@ -77,7 +72,7 @@ int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size
     if (S && (!dp || !dout)) { if (!pcm || !pcm_out) set_last_error("null argument"); return -1; }
     if (!c->ws_rms.reserve(S * n_chunks * 4 + 16) || !c->ws_gain.reserve(S * n_chunks * 4 + 16) ||
         !c->ws_ring.reserve(S * window_size * 4 + 16)) return -1;
-    const hipError_t e = bank || sets || mixed ? launch_frontend_per_stream(c->stream, dp, (int)fmt, S, n_samples, pcm_stride, g.enabled ? 1 : 0, per, (int)window_size,
+    const hipError_t e = bank || sides ? launch_frontend_per_stream(c->stream, dp, (int)fmt, S, n_samples, pcm_stride, g.enabled ? 1 : 0, per, (int)window_size,
                                                            g.min_gain, g.max_gain, b.enabled ? 1 : 0, a0, a1, a2, b1, b2, c->ws_ring.as<float>(),
                                                            c->ws_rms.as<float>(), c->ws_gain.as<float>(), dout, out_stride)
                               : launch_frontend(c->stream, dp, (int)fmt, S, n_samples, pcm_stride, g.enabled ? 1 : 0, rms_level_ref, g.min_gain,

@@ -126,13 +126,12 @@ struct BankIndices {
 };
 bool stage_bank_indices(Ctx *c, Staged &sg, const Bank &bk, const int32_t *idx, size_t S, int set_size, size_t n_frames, BankIndices *bi);
 // rp_frontend_batch and rp_frontend_batch_bank (rp_capi.cpp): with `bank`, every stream takes its gain window and reference level from its own
-// wakeword bank[stream_wakeword[s]] and rms_level_ref / window_size are not read.  With `sets` (rp_frontend_batch_bank_sets / _model_bank; `bank`
-// null): stream_wakeword is the DEVICE array [S][set_size] the caller staged and checked, window_size the capacity of a stream's ring (the
-// largest window of the bank the rows index), and every stream's level and window come from gain_targets_kernel.  With `mixed`
-// (rp_frontend_batch_mixed_sets; `bank` and `sets` null): mixed[0] / mixed[1] are the staged DEVICE rows of references and of models with
-// their banks, window_size as with `sets` over both banks, and mixed_targets_kernel prepares the same table.
+// wakeword bank[stream_wakeword[s]] and rms_level_ref / window_size are not read.  With `sides` (rp_frontend_batch_bank_sets / _model_bank /
+// _mixed_sets; `bank` and stream_wakeword null): sides[0] / sides[1] are the DEVICE rows [S][set_size] the caller staged and checked with
+// their banks -- one bank: the second side absent; mixed sets: references, then models -- window_size is the capacity of a stream's ring
+// (the largest window of the banks the rows index), and every stream's level and window come from stream_targets_kernel.
 int frontend_batch(Ctx *c, const void *pcm, rp_sample_format fmt, size_t S, size_t n_samples, size_t pcm_stride, const rp_filters_config *filters,
                    float rms_level_ref, size_t window_size, const Bank *bank, const int32_t *stream_wakeword, float *pcm_out, size_t out_stride,
-                   float *rms, float *gains, const GainSource *sets = nullptr, int set_size = 0, const MixedSide *mixed = nullptr);
+                   float *rms, float *gains, const TargetSide *sides = nullptr);
 
 }  // namespace rp

@@ -1,5 +1,6 @@
 // rp_dtw_bank.h -- the per-lane DTW walks of the wakeword-bank kernels, shared by rp_dtw_bank.hip (one wakeword per stream) and rp_dtw_set.hip
-// (a set of wakewords per stream): bank_dtw, bank_chk_window, bank_dtw_ref.  Device code only; include behind rp_device.h.
+// (a set of wakewords per stream, alone or beside models): bank_dtw, bank_chk_window, bank_dtw_ref, and RP_BANK_LIVE_LANE, the lane of the
+// three live kernels.  Device code only; include behind rp_device.h.
 #pragma once
 #include "rp_device.h"
 #include "rp_dtw_lane.h"
@@ -65,7 +66,9 @@ __device__ __noinline__ float bank_chk_window(const float *xl, int L) {
 // The same DTW with the reference-shaped cell of dtw_ref_kernel (comparator.rs:28-48: three sequential dot products of the template row AS
 // GIVEN and the mean-normalised frame, one sqrt, one divide), for windows with a frame outside kDtwNormLo..kDtwFixLimit and wakewords with a
 // row outside kDtwNormLo..kDtwNormHiRow.  Band in LDS, lane-minor; the whole wave walks it, the lanes that need it keep the result.
-template <int K, int W, int KP>
+// COPY: an out-of-line function with ONE calling kernel gets that kernel's LDS address of Pb as a constant; called from two kernels of one
+// source it takes the address in a register and both kernels change.  Kernels that share a source and (K, W, KP) name a copy each.
+template <int K, int W, int KP, int COPY = 0>
 __device__ __noinline__ float bank_dtw_ref(const float *xl, int L, const float *__restrict__ raw, float score_ref, float *Pb, int lane) {
     constexpr int B = 2 * W;
     float mu[K];
@@ -104,5 +107,73 @@ __device__ __noinline__ float bank_dtw_ref(const float *xl, int L, const float *
     }
     return dtw_logistic(Pb[(W + 1) * 64 + lane] / (float)(L + L), score_ref);   // column n of row m-1 sits at band offset W + 1
 }
+
+// The lane of the live kernels (dtw_bank_stream_kernel, dtw_set_stream_kernel, dtw_mixed_stream_kernel): row `row` of the call's flattened
+// space is new window i of stream s for bank wakeword wi (live: wi lies inside the bank), and the window that ends at new frame i is lmax
+// frames long -- the three kernels differ in how a row decodes to these and in where lmax comes from, nothing else.  The lane walks ITS
+// wakeword, the averaged template first when it is to be scored, then the sample templates, so template count, template length and
+// template rows are per-lane values: the template loop runs to the wave's largest count, bank_dtw's row loop to the wave's longest
+// template, both under the lane mask, and template rows come by vector loads.  The gate is per lane: a window that did not pass leaves the
+// walk, and the wave stops once no lane has a template left.  Norm-range test (dtw_bank_kernel recomputes for the whole wave once one lane
+// is flagged: over fewer frames an unflagged lane stays unflagged), reference-shaped rescoring (the lanes that need it only) and the
+// percentile block as dtw_bank_kernel; the cell arithmetic is bank_dtw's, so a stream gets the bits dtw_bank_kernel gives it.
+// sl [kBankMaxTemplates][64]: a lane's scores (percentile modes), lane-minor; Pb [13][64]: band of the reference-shaped cell.  COPY: the
+// kernel's copy of bank_dtw_ref (see there).  A macro, not a function: as a __forceinline__ function the same text compiled to other
+// instruction streams in all 28 kernels (profiles/live_lane_fold.txt).
+#define RP_BANK_LIVE_LANE(LMAX, COPY) \
+    const BankWakeword *bw = bank_ww + (live ? wi : 0); \
+    const float *xl = mfcc + (live ? ((size_t)s * q.frame_pitch + (q.first_new + i + 1 - (size_t)(LMAX))) * K : (size_t)0); \
+    const float own_athr = bw->avg_threshold; \
+    const float athr = own_athr == own_athr ? own_athr : q.avg_threshold; \
+    const int avg_e = bw->avg, T = live ? bw->count : 0, first = bw->first, ref_only = bw->ref_only, window_chk = bw->window_chk; \
+    const bool do_avg = live && avg_e >= 0 && athr != 0.f; \
+    const int mode = q.score_mode; \
+    float acc = 0.f, avg_sc = 0.f; \
+    bool scored = live; \
+    for (int ti = -1; __any(scored && ti < T); ++ti) { \
+        const bool act = scored && ti < T && (ti >= 0 || do_avg); \
+        float sc = 0.f, chk = 0.f; \
+        int L = 1; \
+        size_t off = 0; \
+        if (act) { \
+            const int e = ti < 0 ? avg_e : first + ti; \
+            L = bank_tlen[e]; \
+            off = (size_t)bank_trow[e] * K; \
+            sc = bank_dtw<K, W, K>(xl, L, bank_unit + off, q.score_ref, chk); \
+            if (window_chk && chk > kDtwFixLimit) chk = bank_chk_window<K, K>(xl, L); \
+        } \
+        const bool slow = act && (ref_only || chk > kDtwFixLimit); \
+        const unsigned long long slow_mask = __ballot(slow); \
+        if (slow_mask) { \
+            if (slow) sc = bank_dtw_ref<K, W, K, COPY>(xl, L, bank_raw + off, q.score_ref, Pb, lane); \
+            if (lane == 0 && fix) atomicAdd(dtw_fix_stats(fix), (unsigned long long)__popcll(slow_mask)); \
+        } \
+        if (act) { \
+            if (ti < 0) { \
+                avg_sc = sc; \
+                if (q.gate && sc < athr) scored = false; \
+            } else if (mode == 1) acc = ti == 0 ? sc : fmaxf(acc, sc); \
+            else if (mode == 0) acc += sc; \
+            else sl[ti * 64 + lane] = sc; \
+        } \
+    } \
+    float a = 0.f; \
+    if (scored) { \
+        if (mode == 1) a = acc; \
+        else if (mode == 0) a = acc / (float)T; \
+        else { \
+            for (int j = 1; j < T; ++j) { \
+                const float x = sl[j * 64 + lane]; \
+                int p = j - 1; \
+                while (p >= 0 && sl[p * 64 + lane] > x) { sl[(p + 1) * 64 + lane] = sl[p * 64 + lane]; --p; } \
+                sl[(p + 1) * 64 + lane] = x; \
+            } \
+            a = percentile_sorted(sl + lane, T, percentile_of_mode(mode), 64); \
+        } \
+    } \
+    if (valid) { \
+        agg[row] = a; \
+        avg[row] = do_avg ? avg_sc : 0.f; \
+    }
 
 }  // namespace rp

@@ -161,66 +161,7 @@ __global__ __launch_bounds__(64) void dtw_bank_stream_kernel(const BankWakeword 
     const uint32_t s = valid ? row / n_new : 0u, i = row - s * n_new;
     const int wi = valid ? stream_wakeword[s] : -1;
     const bool live = wi >= 0 && wi < bank_W;   // an index outside the bank is "no wakeword" (the host checks it where it can see it)
-    const BankWakeword *bw = bank_ww + (live ? wi : 0);
-    // the window ending at new frame i: max_len frames, the oldest first
-    const float *xl = mfcc + (live ? ((size_t)s * q.frame_pitch + (q.first_new + i + 1 - (size_t)bw->max_len)) * K : (size_t)0);
-    const float own_athr = bw->avg_threshold;
-    const float athr = own_athr == own_athr ? own_athr : q.avg_threshold;
-    const int avg_e = bw->avg, T = live ? bw->count : 0, first = bw->first, ref_only = bw->ref_only, window_chk = bw->window_chk;
-    const bool do_avg = live && avg_e >= 0 && athr != 0.f;   // wakeword_comp.rs:85
-    const int mode = q.score_mode;
-
-    float acc = 0.f, avg_sc = 0.f;
-    bool scored = live;
-    for (int ti = -1; __any(scored && ti < T); ++ti) {
-        const bool act = scored && ti < T && (ti >= 0 || do_avg);
-        float sc = 0.f, chk = 0.f;
-        int L = 1;
-        size_t off = 0;
-        if (act) {
-            const int e = ti < 0 ? avg_e : first + ti;
-            L = bank_tlen[e];
-            off = (size_t)bank_trow[e] * K;
-            sc = bank_dtw<K, W, K>(xl, L, bank_unit + off, q.score_ref, chk);
-            // (dtw_bank_kernel recomputes for the whole wave once one lane is flagged: over fewer frames an unflagged lane stays unflagged)
-            if (window_chk && chk > kDtwFixLimit) chk = bank_chk_window<K, K>(xl, L);
-        }
-        const bool slow = act && (ref_only || chk > kDtwFixLimit);
-        const unsigned long long slow_mask = __ballot(slow);
-        if (slow_mask) {   // wave-uniform
-            if (slow) sc = bank_dtw_ref<K, W, K>(xl, L, bank_raw + off, q.score_ref, Pb, lane);
-            if (lane == 0 && fix) atomicAdd(dtw_fix_stats(fix), (unsigned long long)__popcll(slow_mask));   // rp_ctx_dtw_ref_pairs
-        }
-        if (act) {
-            if (ti < 0) {
-                avg_sc = sc;
-                // the averaged-template gate (wakeword_comp.rs:85-93), per lane: a window that did not pass leaves the walk, and the wave
-                // stops once no lane has a template left
-                if (q.gate && sc < athr) scored = false;
-            } else if (mode == 1) acc = ti == 0 ? sc : fmaxf(acc, sc);   // Max
-            else if (mode == 0) acc += sc;                               // Average: sequential sum in template order
-            else sl[ti * 64 + lane] = sc;
-        }
-    }
-    float a = 0.f;
-    if (scored) {
-        if (mode == 1) a = acc;
-        else if (mode == 0) a = acc / (float)T;
-        else {   // Median / percentiles: the lane sorts its column ascending, then the reference's f32 interpolation
-            for (int j = 1; j < T; ++j) {
-                const float x = sl[j * 64 + lane];
-                int p = j - 1;
-                while (p >= 0 && sl[p * 64 + lane] > x) { sl[(p + 1) * 64 + lane] = sl[p * 64 + lane]; --p; }
-                sl[(p + 1) * 64 + lane] = x;
-            }
-            a = percentile_sorted(sl + lane, T, percentile_of_mode(mode), 64);
-        }
-    }
-    // a window the gate rejected was never compared -> aggregate 0 (agg_store's rule, rp_dtw.hip); a stream without a wakeword: zero rows
-    if (valid) {
-        agg[row] = a;
-        avg[row] = do_avg ? avg_sc : 0.f;
-    }
+    RP_BANK_LIVE_LANE(bw->max_len, 0)
 }
 
 template <int K, int W>

@@ -2,7 +2,8 @@
 // slot) -- the batched form of one `Rustpotter` per user with several add_wakeword calls (src/detector.rs:304-346,433-447).  The window is as
 // long as the longest wakeword of the stream's set, Lmax(s), and every wakeword scores its oldest frames (wakeword_comp.rs:22-27).
 // dtw_set_kernel: whole recordings, one wave per (stream, tile of 64 window starts), the slots walked by the wave and the window's proposal
-// folded in registers; dtw_set_stream_kernel: the new windows of a live-stream batch, lanes = rows of [S][set_size][n_new].  The DTW walks
+// folded in registers; dtw_set_stream_kernel: the new windows of a live-stream batch, lanes = rows of [S][set_size][n_new], and
+// dtw_mixed_stream_kernel, the same for a stream that also holds models (Lmax(s) over both).  The DTW walks
 // are those of rp_dtw_bank.hip (rp_dtw_bank.h), operation for operation.  DESIGN.md §4.2c.
 #include "rp_device.h"
 #include "rp_dtw_bank.h"
@@ -193,82 +194,60 @@ __global__ __launch_bounds__(64) void dtw_set_stream_kernel(const BankWakeword *
             const int wj = stream_wakewords[(size_t)s * set_size + j];
             if (wj >= 0 && wj < bank_W) lmax = max(lmax, bank_ww[wj].max_len);
         }
-    const BankWakeword *bw = bank_ww + (live ? wi : 0);
-    // the window ending at new frame i: Lmax(s) frames, the oldest first; this wakeword scores the oldest of them
-    const float *xl = mfcc + (live ? ((size_t)s * q.frame_pitch + (q.first_new + i + 1 - (size_t)lmax)) * K : (size_t)0);
-    const float own_athr = bw->avg_threshold;
-    const float athr = own_athr == own_athr ? own_athr : q.avg_threshold;
-    const int avg_e = bw->avg, T = live ? bw->count : 0, first = bw->first, ref_only = bw->ref_only, window_chk = bw->window_chk;
-    const bool do_avg = live && avg_e >= 0 && athr != 0.f;   // wakeword_comp.rs:85
-    const int mode = q.score_mode;
-
-    float acc = 0.f, avg_sc = 0.f;
-    bool scored = live;
-    for (int ti = -1; __any(scored && ti < T); ++ti) {
-        const bool act = scored && ti < T && (ti >= 0 || do_avg);
-        float sc = 0.f, chk = 0.f;
-        int L = 1;
-        size_t off = 0;
-        if (act) {
-            const int e = ti < 0 ? avg_e : first + ti;
-            L = bank_tlen[e];
-            off = (size_t)bank_trow[e] * K;
-            sc = bank_dtw<K, W, K>(xl, L, bank_unit + off, q.score_ref, chk);
-            if (window_chk && chk > kDtwFixLimit) chk = bank_chk_window<K, K>(xl, L);
-        }
-        const bool slow = act && (ref_only || chk > kDtwFixLimit);
-        const unsigned long long slow_mask = __ballot(slow);
-        if (slow_mask) {   // wave-uniform
-            if (slow) sc = bank_dtw_ref<K, W, K>(xl, L, bank_raw + off, q.score_ref, Pb, lane);
-            if (lane == 0 && fix) atomicAdd(dtw_fix_stats(fix), (unsigned long long)__popcll(slow_mask));   // rp_ctx_dtw_ref_pairs
-        }
-        if (act) {
-            if (ti < 0) {
-                avg_sc = sc;
-                // the averaged-template gate (wakeword_comp.rs:85-93), per lane
-                if (q.gate && sc < athr) scored = false;
-            } else if (mode == 1) acc = ti == 0 ? sc : fmaxf(acc, sc);   // Max
-            else if (mode == 0) acc += sc;                               // Average: sequential sum in template order
-            else sl[ti * 64 + lane] = sc;
-        }
-    }
-    float a = 0.f;
-    if (scored) {
-        if (mode == 1) a = acc;
-        else if (mode == 0) a = acc / (float)T;
-        else {   // Median / percentiles: the lane sorts its column ascending, then the reference's f32 interpolation
-            for (int j = 1; j < T; ++j) {
-                const float x = sl[j * 64 + lane];
-                int p = j - 1;
-                while (p >= 0 && sl[p * 64 + lane] > x) { sl[(p + 1) * 64 + lane] = sl[p * 64 + lane]; --p; }
-                sl[(p + 1) * 64 + lane] = x;
-            }
-            a = percentile_sorted(sl + lane, T, percentile_of_mode(mode), 64);
-        }
-    }
-    // a window the gate rejected was never compared -> aggregate 0 (agg_store's rule, rp_dtw.hip); an empty slot: zero rows
-    if (valid) {
-        agg[row] = a;
-        avg[row] = do_avg ? avg_sc : 0.f;
-    }
+    RP_BANK_LIVE_LANE(lmax, 0)
 }
 
+// dtw_set_stream_kernel for a live-stream batch over MIXED sets (rp_stream_batch_new_mixed_sets; mfcc_size 16, what a model bank is): the
+// stream also holds models, and its window is Lmax(s) frames with the COMBINED Lmax(s) over both rows, read from the per-stream table of
+// stream_targets_kernel -- the wakeword bank alone cannot tell where a live window starts.  Everything else is dtw_set_stream_kernel's.
 template <int K, int W>
-static hipError_t launch_set_stream_kw(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size, unsigned blocks) {
+__global__ __launch_bounds__(64) void dtw_mixed_stream_kernel(const BankWakeword *__restrict__ bank_ww, const int *__restrict__ bank_tlen,
+                                                              const long long *__restrict__ bank_trow, const float *__restrict__ bank_unit,
+                                                              const float *__restrict__ bank_raw, const float *__restrict__ mfcc,
+                                                              const int32_t *__restrict__ stream_wakewords,
+                                                              const BankWakeword *__restrict__ table, float *__restrict__ agg,
+                                                              float *__restrict__ avg, uint32_t *__restrict__ fix, int bank_W, int set_size,
+                                                              BankStreamScore q) {
+    __shared__ float sl[kBankMaxTemplates * 64];   // a lane's scores (percentile modes), lane-minor
+    __shared__ float Pb[13 * 64];                  // band of the reference-shaped cell
+    const int lane = threadIdx.x;
+    const uint32_t row = blockIdx.x * 64u + lane, n_new = (uint32_t)q.n_new;
+    const bool valid = row < (uint32_t)(q.S * (size_t)set_size * q.n_new);
+    const uint32_t sj = valid ? row / n_new : 0u, i = row - sj * n_new;   // sj = s * set_size + j
+    const uint32_t s = sj / (uint32_t)set_size;
+    const int wi = valid ? stream_wakewords[sj] : -1;
+    const bool live = wi >= 0 && wi < bank_W;   // an index outside the bank is an empty slot (the host checks it where it can see it)
+    const int lmax = live ? table[s].max_len : 0;   // over both rows: at least this wakeword's window
+    RP_BANK_LIVE_LANE(lmax, 1)
+}
+
+// table (with max_window, the longest window any stream of the batch may have: the combined history + 1): a batch over mixed sets, Lmax(s)
+// from the table; nullptr: the set's own
+template <int K, int W>
+static hipError_t launch_set_stream_kw(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size, const BankWakeword *table, unsigned blocks) {
+    if constexpr (K == 16) {
+        if (table) {
+            hipLaunchKernelGGL((dtw_mixed_stream_kernel<K, W>), dim3(blocks), dim3(64), 0, st, b.ww, b.tlen, b.trow, b.unit, b.raw, q.mfcc, q.stream_wakeword,
+                               table, q.agg, q.avg, q.fix, b.W, set_size, q);
+            return hipGetLastError();
+        }
+    }
     hipLaunchKernelGGL((dtw_set_stream_kernel<K, W>), dim3(blocks), dim3(64), 0, st, b.ww, b.tlen, b.trow, b.unit, b.raw, q.mfcc, q.stream_wakeword,
                        q.agg, q.avg, q.fix, b.W, set_size, q);
     return hipGetLastError();
 }
 
-hipError_t launch_dtw_set_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size) {
+hipError_t launch_dtw_set_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size, const BankWakeword *table, int max_window) {
     if (q.S == 0 || q.n_new == 0) return hipSuccess;
     if (set_size < 1 || set_size > kScanMaxWakewords) return hipErrorInvalidValue;
-    if (b.W < 1 || dtw_register_tile(b.K, q.band) <= 0) return hipErrorNotSupported;
-    // rows are 32-bit in the kernel; no window may start before its stream's row
-    if (q.S > 0x7fffffffULL / (q.n_new * (size_t)set_size) || q.first_new + 1 < (size_t)b.max_len || q.first_new + q.n_new > q.frame_pitch)
+    if (b.W < 1 || (table && b.K != 16) || dtw_register_tile(b.K, q.band) <= 0) return hipErrorNotSupported;
+    if (!table) max_window = b.max_len;   // the set's own Lmax(s): at most the bank's longest window
+    else if (max_window < b.max_len) return hipErrorInvalidValue;
+    // rows are 32-bit in the kernel; no window may start before its stream's row: Lmax(s) <= max_window
+    if (q.S > 0x7fffffffULL / (q.n_new * (size_t)set_size) || q.first_new + 1 < (size_t)max_window || q.first_new + q.n_new > q.frame_pitch)
         return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((q.S * (size_t)set_size * q.n_new + 63) / 64);
-#define RP_SET(KK, WW) launch_set_stream_kw<KK, WW>(st, b, q, set_size, blocks)
+#define RP_SET(KK, WW) launch_set_stream_kw<KK, WW>(st, b, q, set_size, table, blocks)
 #define RP_SET_BAND(KK) \
     switch (q.band) { case 3: return RP_SET(KK, 3); case 4: return RP_SET(KK, 4); case 5: return RP_SET(KK, 5); default: return RP_SET(KK, 6); }
     if (b.K == 5) { RP_SET_BAND(5) }

@@ -194,7 +194,7 @@ struct Ctx {
     // scores went to the caller's device array, or another call has used the workspace since
     size_t last_window_scores = 0;
     DevBuf ws_bank_idx;  // the per-stream wakeword indices of a bank call with RP_CTX_HOST_POINTERS
-    DevBuf ws_gain_tab;  // rp_frontend_batch_bank_sets / _model_bank: the per-stream table of gain_targets_kernel
+    DevBuf ws_gain_tab;  // rp_frontend_batch_bank_sets / _model_bank: the per-stream table of stream_targets_kernel
     DevBuf ws_set_ww, ws_set_agg, ws_set_avg;  // wakeword-set calls: the proposals' bank indices [S][n_win]; the per-slot rows of a call with host pointers
     // mixed-set calls (rp_batch_detect_mixed_sets): the model rows' staged indices and the model side's four proposal rows [S][n_win] -- the
     // reference side's live in ws_bank_idx / ws_agg / ws_avg / ws_set_ww, and both are read by one scan

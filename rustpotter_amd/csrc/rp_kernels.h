@@ -250,7 +250,7 @@ enum : uint32_t { kDtwRanMfma = 1u, kDtwRanMfmaWide = 2u, kDtwRanRagged = 4u, kD
                   kDtwRanBankStream = 8192u,
                   // dtw_set_kernel / dtw_set_stream_kernel (rp_dtw_set.hip): a set of wakewords of a bank per stream
                   kDtwRanBankSets = 16384u, kDtwRanBankSetsStream = 32768u,
-                  // dtw_mixed_stream_kernel (rp_dtw_mixed.hip): the reference slots of a live-stream batch over mixed sets
+                  // dtw_mixed_stream_kernel (rp_dtw_set.hip): the reference slots of a live-stream batch over mixed sets
                   kDtwRanMixedSetsStream = 65536u };
 inline void dtw_mark(const DtwWork &wk, uint32_t bit) { if (wk.ran) *wk.ran |= bit; }
 __host__ __device__ inline unsigned long long *dtw_fix_stats(uint32_t *fix) { return reinterpret_cast<unsigned long long *>(fix + 2 + 2 * (size_t)kDtwFixCap); }
@@ -563,29 +563,24 @@ struct PerStreamGain {
     float fixed_ref = 0.f;
 };
 // The same parameters for a stream that holds a SET of a bank's entries (wakeword sets, model sets; a model bank's one model is a set of
-// one): gain_targets_kernel (rp_gain_targets.hip) folds every stream's row of set_size indices into one row of a per-stream table --
-// max_len = Lmax(s), the longest window of the live slots; level = the largest non-NaN level of the live slots, NaN when none
-// (on_wakeword_change, src/detector.rs:328-338); idx = s, or -1 for a stream without a live slot -- and the per-stream gain kernels read
-// that table as they read a bank: PerStreamGain{idx, table, level, W = S}.
-struct GainSource {                             // where the windows and levels come from
+// one) or rows of TWO banks (mixed sets: references of a wakeword bank and models of a model bank on one detector): stream_targets_kernel
+// (rp_gain_targets.hip) folds every stream's rows into one row of a per-stream table -- max_len = Lmax(s), the longest window of the live
+// slots; level = the largest non-NaN level of the live slots, NaN when none (on_wakeword_change, src/detector.rs:328-338); idx = s, or -1
+// for a stream without a live slot -- and the per-stream gain kernels read that table as they read a bank: PerStreamGain{idx, table,
+// level, W = S}.  The mixed scoring and scan kernels read Lmax(s) from it (per->ww).
+// One side of it: rows [S][set_size] of indices into a bank of W entries, outside [0, W): an empty slot.  set_size 0 (rows may be null):
+// the side is absent.
+struct TargetSide {
+    const int32_t *rows = nullptr;              // device
+    int set_size = 0;
     const BankWakeword *ww = nullptr;           // [W], device: BankDev::ww of a wakeword bank, ModelBank::scan.ww (max_len = L) of a model bank
     const float *level = nullptr;               // [W], device: Bank::rms_level / ModelBank::rms_level, NaN: none
     int W = 0;
 };
-struct GainTargets {
-    const int32_t *idx = nullptr;               // [S][set_size], device; outside [0, W): an empty slot
-    int set_size = 1;
-    const BankWakeword *ww = nullptr;
-    const float *level = nullptr;
-    int W = 0;
-    BankWakeword *table = nullptr;              // [S]
-    float *tlevel = nullptr;                    // [S]
-    int32_t *tidx = nullptr;                    // [S]
-};
 size_t gain_targets_bytes(size_t S);            // the workspace of S streams
-// One short launch; fills per->stream_wakeword / ww / rms_level / W (has_fixed_ref and fixed_ref stay the caller's)
-hipError_t launch_gain_targets(hipStream_t st, const GainSource &src, const int32_t *idx, int set_size, size_t S, void *workspace,
-                               PerStreamGain *per);
+// One short launch over up to two sides (a call over one bank passes TargetSide{} as the second); fills per->stream_wakeword / ww /
+// rms_level / W (has_fixed_ref and fixed_ref stay the caller's)
+hipError_t launch_stream_targets(hipStream_t st, const TargetSide &first, const TargetSide &second, size_t S, void *workspace, PerStreamGain *per);
 // Decode + GainNormalizerFilter + BandPassFilter over whole streams.  ring [S][window_size], rms / gains
 // [S][n_samples/480] are device workspaces; biquad coefficients as BandPassFilter::new computes them.
 hipError_t launch_frontend(hipStream_t st, const void *pcm, int fmt, size_t S, size_t n_samples, size_t pcm_stride, int gain_on,
@@ -648,7 +643,7 @@ hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32
                                    void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det,
                                    const int32_t *label = nullptr);   // label [S][n_new] (a model bank's batch): det_label is the label of the detection's best window
 
-// ---- wakeword sets (rp_dtw_set.hip, rp_scan_set.hip): stream s holds up to kScanMaxWakewords wakewords of a bank, stream_wakewords
+// ---- wakeword sets (rp_dtw_set.hip, rp_scan_sets.hip): stream s holds up to kScanMaxWakewords wakewords of a bank, stream_wakewords
 // [S][set_size] (outside [0, W): an empty slot) -- a `Rustpotter` with several add_wakeword calls.  Its window is Lmax(s) frames, the longest
 // of its set; every wakeword scores the oldest frames of it.
 // One scoring call over whole recordings; the BankScore fields mean what they mean there.  Stream s has n_win_s = n_frames - Lmax(s) + 1 windows.
@@ -673,8 +668,11 @@ struct BankSetScore {
 // built for dtw_register_tile(K, band) > 0, as launch_dtw_bank
 hipError_t launch_dtw_set(hipStream_t st, const BankDev &b, const BankSetScore &q);
 // One call of a live-stream batch over sets: q as for launch_dtw_bank_stream with q.stream_wakeword [S][set_size] and q.agg / q.avg
-// [S][set_size][n_new]; the window of stream s that ends at a new frame starts Lmax(s) - 1 frames before it
-hipError_t launch_dtw_set_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size);
+// [S][set_size][n_new]; the window of stream s that ends at a new frame starts Lmax(s) - 1 frames before it.  table (optional): a batch
+// over mixed sets (mfcc_size 16 only) -- the COMBINED Lmax(s) of the per-stream table in the place of the set's own, with max_window the
+// longest window any stream of the batch may have (its history + 1); without it max_window is not read
+hipError_t launch_dtw_set_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size, const BankWakeword *table = nullptr,
+                                 int max_window = 0);
 // the state machine of a stream that holds a set over the proposal rows of launch_dtw_set (window f - Lmax(s) + 1 of rows win_pitch apart);
 // det_ww (optional): the bank index of each detection's wakeword.  `hot` as in launch_scan_bank.
 hipError_t launch_scan_set(hipStream_t st, const BankDev &b, const int32_t *stream_wakewords, int set_size, const float *best, const float *best_avg,
@@ -902,7 +900,7 @@ hipError_t launch_mlp_bank_stream(hipStream_t st, const ModelBankDev &b, int max
 hipError_t launch_nn_score_bank_stream(hipStream_t st, const ModelBankDev &b, const int32_t *stream_model, const float *logits, size_t S, size_t n_new,
                                        float score_ref10, int calc_avg, float threshold, float avg_threshold, float *agg, float *avg, int32_t *label);
 
-// ---- model sets (rp_mlp_model_set.hip, rp_scan_model_set.hip): stream s holds up to kScanMaxWakewords models of a model bank, sets
+// ---- model sets (rp_mlp_model_set.hip, rp_scan_sets.hip): stream s holds up to kScanMaxWakewords models of a model bank, sets
 // [S][set_size] (outside [0, W): an empty slot) -- a `Rustpotter` with several add_wakeword calls of models.  Its window is Lmax(s) frames, the
 // longest train_size of its live slots; slot j scores the oldest L_j frames of it.
 // Whole recordings: stream s has n_win_s = n_frames - Lmax(s) + 1 windows.  The launch shape of the models a call uses: one
@@ -941,22 +939,9 @@ hipError_t launch_scan_model_set_stream(hipStream_t st, const BankDev &b, const 
                                         int n_new, const ScanConfig &cfg, void *state, BatchDetection *det, int32_t *det_ww, int32_t *det_label,
                                         int32_t *n_det, int max_det);
 
-// ---- mixed sets (rp_mixed_targets.hip, rp_scan_mixed.hip): stream s holds a row of wakeword references of a wakeword bank AND a row of models
+// ---- mixed sets (rp_gain_targets.hip, rp_scan_sets.hip): stream s holds a row of wakeword references of a wakeword bank AND a row of models
 // of a model bank -- one `Rustpotter` with add_wakeword of both kinds (src/detector.rs:304-346,433-447).  Its window is Lmax(s) frames, the
 // longest over the live slots of BOTH rows.
-// One row of a mixed call: rows [S][set_size] of indices into a bank of W entries (ww: BankDev::ww / ModelBank::scan.ww, level: the bank's
-// rms levels).  set_size 0 (rows may be null): the side is absent.
-struct MixedSide {
-    const int32_t *rows = nullptr;
-    int set_size = 0;
-    const BankWakeword *ww = nullptr;
-    const float *level = nullptr;
-    int W = 0;
-};
-// gain_targets_kernel over both rows: the same per-stream table (gain_targets_bytes(S) of workspace) -- table[s].max_len = Lmax(s) over both
-// rows, level[s] = the largest non-NaN level over both, idx[s] = s or -1 -- read by the per-stream gain kernels through `per` and by the
-// mixed scan kernels through per->ww
-hipError_t launch_mixed_targets(hipStream_t st, const MixedSide &refs, const MixedSide &models, size_t S, void *workspace, PerStreamGain *per);
 // The proposals of one side of a whole-recording mixed call, rows win_pitch apart: those of launch_dtw_set (label null) or of
 // launch_nn_score_model_set.  bank: the side's BankDev (ModelBank::scan for models); set_size 0: the side is absent and nothing is read.
 struct MixedProposals {
@@ -966,19 +951,15 @@ struct MixedProposals {
     const float *best = nullptr, *best_avg = nullptr;
     const int32_t *best_ww = nullptr, *best_label = nullptr;
 };
-// the state machine of a stream that holds a mixed set: Lmax(s) from table (launch_mixed_targets), per window the better of the two sides'
+// the state machine of a stream that holds a mixed set: Lmax(s) from table (launch_stream_targets), per window the better of the two sides'
 // proposals, the reference of equals; a side without a live slot for the stream is not read.  det_ww: the winner's index in ITS OWN bank,
 // det_label: the winner's label for a model, -1 for a reference (both optional).  `hot` as in launch_scan_bank.
 hipError_t launch_scan_mixed_set(hipStream_t st, const MixedProposals &refs, const MixedProposals &models, const BankWakeword *table, size_t win_pitch,
                                  const float *vad_value, float vad_mode_value, size_t S, size_t n_frames, const ScanConfig &cfg, BatchDetection *det,
                                  int32_t *det_ww, int32_t *det_label, int32_t *n_det, int max_det, uint32_t *hot);
-// Live (rp_dtw_mixed.hip, rp_mlp_mixed.hip, rp_scan_mixed.hip): the window of stream s that ends at a new frame starts Lmax(s) - 1 frames
-// before it, with the COMBINED Lmax(s) of `table`; max_window: the longest window any stream of the batch may have (its history + 1).
-// launch_dtw_set_stream with the combined window: q.stream_wakeword [S][set_size], q.agg / q.avg [S][set_size][n_new]; mfcc_size 16 only
-hipError_t launch_dtw_mixed_stream(hipStream_t st, const BankDev &b, const BankStreamScore &q, int set_size, const BankWakeword *table,
-                                   int max_window);
-// launch_window_means_set_stream / launch_mlp_set_stream with the combined window (max_L: the model bank's longest window);
-// launch_nn_score_set_stream scores their logits as it is
+// Live, the model side of a batch over mixed sets (rp_mlp_mixed.hip): launch_window_means_set_stream / launch_mlp_set_stream with the COMBINED
+// Lmax(s) of `table` (max_L: the model bank's longest window; max_window: the longest window any stream of the batch may have, its
+// history + 1); launch_nn_score_set_stream scores their logits as it is
 hipError_t launch_window_means_mixed_stream(hipStream_t st, const ModelBankDev &b, int max_L, int max_window, const int32_t *sets, int set_size,
                                             const BankWakeword *table, const float *frames, size_t S, size_t cap, size_t fill, size_t n_new,
                                             float *mean);

@@ -1,6 +1,6 @@
 // rp_mlp_mixed.hip -- the model side of a live-stream batch over MIXED sets (rp_stream_batch_new_mixed_sets): the fronts of
 // rp_mlp_model_set.hip's live kernels with the COMBINED Lmax(s) -- the longest window over the live slots of the stream's reference row and
-// model row, read from the per-stream table of mixed_targets_kernel -- in the place of the model row's own.  The first window of a call
+// model row, read from the per-stream table of stream_targets_kernel -- in the place of the model row's own.  The first window of a call
 // starts Lmax(s) - 1 frames before the first new frame for every slot; slot j reads L_j frames from there.  The bodies are shared
 // (window_means_body, rp_mlp_windows.h; mlp_bank_stream_body, rp_mlp_bank_stream.h); nn_score_set_stream_kernel does not read Lmax and is
 // reused as it is.

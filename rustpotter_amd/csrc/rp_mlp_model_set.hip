@@ -1,7 +1,7 @@
 // rp_mlp_model_set.hip -- MODEL SETS: stream s holds up to kScanMaxWakewords models of a model bank, sets [S][set_size] (outside [0, W): an
 // empty slot) -- a `Rustpotter` with several add_wakeword calls of wakeword models (src/detector.rs:304-346,433-447, wakeword_nn.rs:137).
 // The detector's window is Lmax(s) frames, the longest train_size of the stream's live slots; slot j scores the OLDEST L_j frames of it.
-// Here: the window means, the two forwards (whole recordings, live) and the decision kernels; the scan fronts are in rp_scan_model_set.hip, the
+// Here: the window means, the two forwards (whole recordings, live) and the decision kernels; the scan fronts are in rp_scan_sets.hip, the
 // calls in rp_bank_calls.cpp and rp_stream_batch.cpp.  DESIGN.md §4.4.
 //
 // WHOLE RECORDINGS (mlp_windows_model_set_kernel<NT>, 1 .. 7 tiles; 256 threads, two workgroups per CU as mlp_windows_bank_kernel): a front

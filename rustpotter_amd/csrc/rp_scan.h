@@ -1,5 +1,6 @@
-// rp_scan.h -- what the scan kernels share (rp_scan.hip, rp_scan_set.hip): the carried lane state, the detections' output block, a window's
-// proposal, bank_lane and scan_frames, the one copy of the detection state machine.  Device code only; include behind rp_device.h.
+// rp_scan.h -- what the scan kernels share (rp_scan.hip, rp_scan_sets.hip): the carried lane state, the detections' output block, a window's
+// proposal, bank_lane, the slots of a set, scan_frames -- the one copy of the detection state machine -- and the two frames around it,
+// scan_recording and scan_live.  Device code only; include behind rp_device.h.
 #pragma once
 #include "rp_device.h"
 
@@ -105,6 +106,59 @@ __device__ __forceinline__ int set_max_len(const BankDev &b, const int32_t *__re
     return lmax;
 }
 
+// ------------------------------------------------------------------------- the slots of a live set
+// A live kernel keeps the slots of its stream's set in registers: every loop over them is unrolled to the limit of a set.
+// Reference slots: wi[j] as given, r[j] = bank_lane (none: an empty slot); model slots: mi[j], -1 for an empty slot (b: ModelBank::scan).
+// Both return the longest window over the live slots, 0: none is live.
+__device__ __forceinline__ int load_ref_slots(const BankDev &b, const int32_t *__restrict__ set, int set_size, const ScanConfig &cfg,
+                                              int (&wi)[kScanMaxWakewords], BankLane (&r)[kScanMaxWakewords]) {
+    int max_len = 0;
+#pragma unroll
+    for (int j = 0; j < kScanMaxWakewords; ++j) {
+        wi[j] = j < set_size ? set[j] : -1;
+        r[j] = bank_lane(b, wi[j], cfg);
+        max_len = max(max_len, r[j].max_len);
+    }
+    return max_len;
+}
+__device__ __forceinline__ int load_model_slots(const BankDev &b, const int32_t *__restrict__ set, int set_size, int (&mi)[kScanMaxWakewords]) {
+    int max_len = 0;
+#pragma unroll
+    for (int j = 0; j < kScanMaxWakewords; ++j) {
+        mi[j] = j < set_size ? set[j] : -1;
+        if (mi[j] < 0 || mi[j] >= b.W) mi[j] = -1;
+        else max_len = max(max_len, b.ww[mi[j]].max_len);
+    }
+    return max_len;
+}
+// What the slots say about new frame i, folded into p (ww < 0: nobody has proposed yet): the best score wins, the first slot of equals --
+// propose_best's rule (run_wakeword_detectors, src/detector.rs:433-447) with the bank index as the wakeword.  rows: the stream's
+// [set_size][n_new].  A reference slot proposes with its own thresholds (>), a model slot where its score is not -2:
+// nn_score_set_stream_kernel applied its gates (>=); its window's label travels with the proposal.
+__device__ __forceinline__ void propose_ref_slots(Proposal &p, const int (&wi)[kScanMaxWakewords], const BankLane (&r)[kScanMaxWakewords],
+                                                  const float *__restrict__ agg, const float *__restrict__ avg, size_t row0, int n_new, int i) {
+#pragma unroll
+    for (int j = 0; j < kScanMaxWakewords; ++j) {
+        if (r[j].none) continue;
+        const size_t row = row0 + (size_t)j * (size_t)n_new + i;
+        const float sj = agg[row];
+        float aj = 0.f;
+        bool pass = true;
+        if (r[j].avg_on) { aj = avg[row]; pass = !(aj < r[j].athr); }
+        if (pass && sj > r[j].thr && (p.ww < 0 || sj > p.score)) { p.ww = wi[j]; p.score = sj; p.avg = aj; }
+    }
+}
+__device__ __forceinline__ void propose_model_slots(Proposal &p, const int (&mi)[kScanMaxWakewords], const float *__restrict__ agg,
+                                                    const float *__restrict__ avg, const int32_t *__restrict__ label, size_t row0, int n_new, int i) {
+#pragma unroll
+    for (int j = 0; j < kScanMaxWakewords; ++j) {
+        if (mi[j] < 0) continue;
+        const size_t row = row0 + (size_t)j * (size_t)n_new + i;
+        const float sj = agg[row];
+        if (sj != -2.f && (p.ww < 0 || sj > p.score)) { p.ww = mi[j]; p.score = sj; p.avg = avg[row]; p.label = label[row]; }
+    }
+}
+
 // ------------------------------------------------------------------------- the state machine
 // The partial-detection / countdown state machine of src/detector.rs:377-454 with reset() of :290-302 for one lane, over the frames
 // f0 .. f0+n-1 (i = 0 .. n-1; vv[i] is frame f0+i's VAD value, vwin[.][lane] the lane's VadDetector::window).  propose(f, i) is what the
@@ -178,6 +232,43 @@ __device__ __forceinline__ void stream_state_store(StreamState *sp, const ScanLa
     if (vad)
         for (int i = 0; i < 50; ++i) sp->vad_window[i] = vwin[i][lane];
     __builtin_memcpy(&sp->lane, &z, sizeof(ScanLane));
+}
+
+// ------------------------------------------------------------------------- the two frames
+// Whole recordings: stream s (this lane) from a fresh state over frames 0 .. n_frames - 1, its window max_len frames long.  hot (optional):
+// the flag the scoring pass raised for a stream with a window that can fire, put back to 0 here (Ctx::hot_flags); a stream without it, one
+// that is not live (no wakeword, no live slot) and one with fewer frames than its window report nothing.
+template <class Propose, class Emit>
+__device__ __forceinline__ void scan_recording(float (*vwin)[64], int lane, size_t s, uint32_t *__restrict__ hot, int max_len, bool live,
+                                               const float *__restrict__ vad_value, float vad_mode_value, size_t n_frames, const ScanConfig &cfg,
+                                               const ScanOut &out, Propose propose, Emit emit) {
+    bool candidate = true;
+    if (hot) {
+        candidate = hot[s] != 0u;
+        if (candidate) hot[s] = 0u;   // consumed
+    }
+    if (!live || !candidate || n_frames < (size_t)max_len) { out.finish(s, 0); return; }
+    const float *vv = vad_value ? vad_value + s * n_frames : nullptr;
+    if (vv)
+        for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
+    ScanLane z = fresh_lane();
+    out.finish(s, scan_frames(z, vwin, lane, vv, vad_mode_value, 0, (int)n_frames, max_len, cfg, propose, emit));
+}
+// Live: the n_new frames of this call with the carried state of stream s (this lane); vad_value [S][n_new].  A stream that is not live
+// reports nothing and keeps its state as it is (re-targeting a stream resets it).
+template <class Propose, class Emit>
+__device__ __forceinline__ void scan_live(float (*vwin)[64], int lane, size_t s, int max_len, bool live, const float *__restrict__ vad_value,
+                                          float vad_mode_value, long long f0, int n_new, const ScanConfig &cfg, StreamState *__restrict__ state,
+                                          const ScanOut &out, Propose propose, Emit emit) {
+    int nd = 0;
+    if (live) {
+        const float *vv = vad_value ? vad_value + s * (size_t)n_new : nullptr;
+        ScanLane z;
+        stream_state_load(state + s, z, vwin, lane, vv != nullptr);
+        nd = scan_frames(z, vwin, lane, vv, vad_mode_value, f0, n_new, max_len, cfg, propose, emit);
+        stream_state_store(state + s, z, vwin, lane, vv != nullptr);
+    }
+    out.finish(s, nd);
 }
 
 }  // namespace rp

@@ -1,6 +1,6 @@
 // rp_scan.hip -- the detection state machine over precomputed window scores (src/detector.rs:290-302,377-454, src/mfcc/vad.rs).
 // scan_frames (rp_scan.h) is the state machine -- VAD gate, countdown, partial detection, reset after an emit -- and the only copy of it.  The
-// four scan kernels here (and the two of rp_scan_set.hip) run it, one lane per stream, and add what is their own: scan_kernel the whole
+// four scan kernels here (and the two of rp_scan_sets.hip) run it, one lane per stream, and add what is their own: scan_kernel the whole
 // recording of a detector with up to eight wakewords, scan_bank_kernel the same for a stream that holds one wakeword of a bank,
 // scan_stream_kernel / scan_bank_stream_kernel the two over the new frames of a live call with the state carried between calls.  Also
 // here: the VAD value kernels and the staging of live-stream batches.
@@ -175,27 +175,16 @@ __global__ __launch_bounds__(64) void scan_bank_kernel(BankDev b, const int32_t 
     const int lane = threadIdx.x;
     const size_t s = (size_t)blockIdx.x * 64 + lane;
     if (s >= S) return;
-    bool candidate = true;
-    if (hot) {
-        candidate = hot[s] != 0u;
-        if (candidate) hot[s] = 0u;   // consumed (Ctx::hot_flags)
-    }
     const int wi = stream_wakeword[s];
     const BankLane r = bank_lane(b, wi, cfg);
     const int max_len = r.max_len;
     const ScanOut out{det, nullptr, nullptr, n_det, max_det};
-    if (r.none || !candidate || n_frames < (size_t)max_len) { out.finish(s, 0); return; }
     const bool avg_on = avg && r.avg_on;
     const size_t row0 = s * win_pitch;
-    const float *vv = vad_value ? vad_value + s * n_frames : nullptr;
-    if (vv)
-        for (int i = 0; i < 50; ++i) vwin[i][lane] = __builtin_nanf("");
-    ScanLane z = fresh_lane();
-    const int nd = scan_frames(
-        z, vwin, lane, vv, vad_mode_value, 0, (int)n_frames, max_len, cfg,
+    scan_recording(
+        vwin, lane, s, hot, max_len, !r.none, vad_value, vad_mode_value, n_frames, cfg, out,
         [&](long long f, int) { return propose_one(agg, avg, row0 + (size_t)(f - max_len + 1), r.thr, r.athr, avg_on, wi); },
         [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s + cfg.stream_base, f, z, 0, -1); });
-    out.finish(s, nd);
 }
 
 hipError_t launch_scan_bank(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg, size_t win_pitch,
@@ -305,15 +294,10 @@ __global__ __launch_bounds__(64) void scan_stream_kernel(ScanWakewords ww, const
     if (s >= S) return;
     const ScanOut out{det, det_ww, det_label, n_det, max_det};
     const size_t row0 = s * (size_t)n_new;
-    const float *vv = vad_value ? vad_value + row0 : nullptr;
-    ScanLane z;
-    stream_state_load(state + s, z, vwin, lane, vv != nullptr);
-    const int nd = scan_frames(
-        z, vwin, lane, vv, vad_mode_value, f0, n_new, cfg.max_len, cfg,
+    scan_live(
+        vwin, lane, s, cfg.max_len, true, vad_value, vad_mode_value, f0, n_new, cfg, state, out,
         [&](long long, int i) { return propose_best(ww, row0 + i); },
         [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s, f, z, z.p_ww, z.p_label); });
-    stream_state_store(state + s, z, vwin, lane, vv != nullptr);
-    out.finish(s, nd);
 }
 
 hipError_t launch_scan_stream_multi(hipStream_t st, const ScanWakewords &ww, const float *vad_value, float vad_mode_value, size_t S,
@@ -345,23 +329,15 @@ __global__ __launch_bounds__(64) void scan_bank_stream_kernel(BankDev b, const i
     const ScanOut out{det, det_ww, det_label, n_det, max_det};
     const int wi = stream_wakeword[s];
     const BankLane r = bank_lane(b, wi, cfg);
-    int nd = 0;
-    if (!r.none) {
-        const size_t row0 = s * (size_t)n_new;
-        const float *vv = vad_value ? vad_value + row0 : nullptr;
-        ScanLane z;
-        stream_state_load(state + s, z, vwin, lane, vv != nullptr);
-        nd = scan_frames(
-            z, vwin, lane, vv, vad_mode_value, f0, n_new, r.max_len, cfg,
-            [&](long long, int i) {
-                Proposal p = propose_one(agg, avg, row0 + i, r.thr, r.athr, r.avg_on, wi);
-                if (label) p.label = label[row0 + i];
-                return p;
-            },
-            [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s, f, z, z.p_ww, label ? z.p_label : -1); });
-        stream_state_store(state + s, z, vwin, lane, vv != nullptr);
-    }
-    out.finish(s, nd);
+    const size_t row0 = s * (size_t)n_new;
+    scan_live(
+        vwin, lane, s, r.max_len, !r.none, vad_value, vad_mode_value, f0, n_new, cfg, state, out,
+        [&](long long, int i) {
+            Proposal p = propose_one(agg, avg, row0 + i, r.thr, r.athr, r.avg_on, wi);
+            if (label) p.label = label[row0 + i];
+            return p;
+        },
+        [&](int nd, long long f, const ScanLane &z) { out.put(s, nd, (int32_t)s, f, z, z.p_ww, label ? z.p_label : -1); });
 }
 
 hipError_t launch_scan_bank_stream(hipStream_t st, const BankDev &b, const int32_t *stream_wakeword, const float *agg, const float *avg,

@@ -49,11 +49,11 @@ struct rp_stream_batch {
     // the models model_idx[s][0 .. mset_size) of `mbank` on one detector; either size may be 0 (the side is absent).  max_len is the longer of the
     // two banks' windows (reservations included).  bank_agg / bank_avg are the reference slots' scores [S][set_size][frames per call], m_agg /
     // m_avg / bank_label the model slots' [S][mset_size][..], `logits` [S][mset_size][frames][label_pitch].  gain_tab holds the per-stream table
-    // of mixed_targets_kernel, written at the start of EVERY call: Lmax(s) for the scoring and scan kernels, the level for the gain normaliser.
+    // of stream_targets_kernel, written at the start of EVERY call: Lmax(s) for the scoring and scan kernels, the level for the gain normaliser.
     bool mixed = false;
     int mset_size = 0;
     DevBuf model_idx, m_agg, m_avg;
-    PerStreamGain mixed_per;   // what the last launch_mixed_targets filled (mixed_per.ww: the table)
+    PerStreamGain mixed_per;   // what the last launch_stream_targets filled (mixed_per.ww: the table)
     int K = 0, max_len = 0, Tmax = 1;             // mfcc_size, max_mfcc_frames (longest wakeword), most templates of a reference
     DevBuf det_ww, det_label, logits, mean, xrows, xs2;
     rp_detector_config cfg{};
@@ -87,7 +87,7 @@ struct rp_stream_batch {
     // bank, read through bank_idx at the start of every call; gain_window is then the capacity of a stream's ring, the bank's largest window
     bool per_stream_gain = false;
     // rp_stream_batch_set_filters_per_stream: the level and window of stream s come from ALL the bank entries it holds (a set of wakewords or of
-    // models, one model, one wakeword), folded by gain_targets_kernel at the start of every call into gain_tab, the per-stream table the same
+    // models, one model, one wakeword), folded by stream_targets_kernel at the start of every call into gain_tab, the per-stream table the same
     // gain kernels then read; a bank that changed under the batch is seen from the next call
     bool prep_gain = false;
     DevBuf gain_tab;
@@ -213,20 +213,24 @@ static bool indices_put(rp_stream_batch *b, DevBuf &dst, size_t row, size_t firs
 }
 static bool bank_indices_put(rp_stream_batch *b, size_t first, size_t n, const int32_t *idx) { return indices_put(b, b->bank_idx, b->slots(), first, n, idx); }
 
-// A batch over mixed sets: both rows of every stream folded over both banks into the per-stream table (Lmax(s), level, idx) -- one short
-// launch at the start of every call, so a bank that changed under the batch is seen from this call on.  A side without rows, or whose bank
-// is empty, is absent.  Refuses banks that outgrew what the batch was sized for.
-static bool mixed_targets(rp_stream_batch *b) {
-    const Bank &bk = *b->bank;
-    const ModelBank &mb = *b->mbank;
-    if ((bk.dev.W && (bk.dev.K != 16 || bk.dev.max_len > b->max_len)) || (mb.dev.W && (mb.max_L > b->max_len || mb.dev.label_pitch != b->label_pitch))) {
-        set_last_error("stream batch: a bank outgrew what the batch was sized for");
-        return false;
-    }
-    MixedSide rs, ms;
-    if (b->set_size && bk.dev.W) { rs.rows = b->bank_idx.as<int32_t>(); rs.set_size = b->set_size; rs.ww = bk.dev.ww; rs.level = bk.rms_level; rs.W = bk.dev.W; }
-    if (b->mset_size && mb.dev.W) { ms.rows = b->model_idx.as<int32_t>(); ms.set_size = b->mset_size; ms.ww = mb.scan.ww; ms.level = mb.rms_level(); ms.W = mb.dev.W; }
-    return hip_ok(launch_mixed_targets(b->c->stream, rs, ms, b->S, b->gain_tab.p, &b->mixed_per), "mixed_targets_kernel");
+// The per-stream table (Lmax(s), level, idx) of this call, folded over the rows of whichever banks the batch has -- one short launch, so a
+// bank that changed under the batch is seen from this call on.  A batch over mixed sets: both rows (a side without rows, or whose bank is
+// empty, is absent), at the start of every call -- the scoring and scan kernels read Lmax(s) from it; refuses banks that outgrew what the
+// batch was sized for.  The other kinds: their one bank, and only for the gain normaliser.
+static bool stream_targets(rp_stream_batch *b, PerStreamGain *per) {
+    TargetSide first, second;
+    if (b->mixed) {
+        const Bank &bk = *b->bank;
+        const ModelBank &mb = *b->mbank;
+        if ((bk.dev.W && (bk.dev.K != 16 || bk.dev.max_len > b->max_len)) || (mb.dev.W && (mb.max_L > b->max_len || mb.dev.label_pitch != b->label_pitch))) {
+            set_last_error("stream batch: a bank outgrew what the batch was sized for");
+            return false;
+        }
+        if (b->set_size && bk.dev.W) first = {b->bank_idx.as<int32_t>(), b->set_size, bk.dev.ww, bk.rms_level, bk.dev.W};
+        if (b->mset_size && mb.dev.W) second = {b->model_idx.as<int32_t>(), b->mset_size, mb.scan.ww, mb.rms_level(), mb.dev.W};
+    } else if (b->mbank) first = {b->bank_idx.as<int32_t>(), (int)b->slots(), b->mbank->scan.ww, b->mbank->rms_level(), b->mbank->dev.W};
+    else first = {b->bank_idx.as<int32_t>(), (int)b->slots(), b->bank->dev.ww, b->bank->rms_level, b->bank->dev.W};
+    return hip_ok(launch_stream_targets(b->c->stream, first, second, b->S, b->gain_tab.p, per), "stream_targets_kernel");
 }
 
 // what the MFCC front of a call reads: the caller's chunks where they lie on the device, or the resampler's 16 kHz output
@@ -265,24 +269,15 @@ static bool stream_frames(rp_stream_batch *b, const MfccTablesDev &tb, const Str
     // 16 kHz mono input is read where it lies: the MFCC kernel takes [history chunk | new chunks] from two buffers and
     // leaves the last chunk as the next call's history.  Other inputs are staged into one row per stream first.
     bool staged = b->filters_on() || b->rs || in.channels != 1;
-    if (b->mixed && !mixed_targets(b)) return false;   // every call: the scoring and scan kernels read Lmax(s) from the table
+    if (b->mixed && !stream_targets(b, &b->mixed_per)) return false;   // every call, filters or not
     if (b->filters_on()) {
         // with filters, ONE launch in the place of launch_stream_stage: history chunk | the new chunks decoded and filtered, levels kept
         const rp_gain_normalization_config &g = b->filt.gain_normalizer;
         PerStreamGain per;
-        if (b->mixed) {
-            per = b->mixed_per;
-            per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
-        } else if (b->prep_gain) {
-            GainSource src;
-            if (b->mbank) { src.ww = b->mbank->scan.ww; src.level = b->mbank->rms_level(); src.W = b->mbank->dev.W; }
-            else { src.ww = b->bank->dev.ww; src.level = b->bank->rms_level; src.W = b->bank->dev.W; }
-            if (!hip_ok(launch_gain_targets(c->stream, src, b->bank_idx.as<int32_t>(), (int)b->slots(), S, b->gain_tab.p, &per), "gain_targets_kernel")) return false;
-            per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;
-        } else if (b->per_stream_gain) {
-            per.stream_wakeword = b->bank_idx.as<int32_t>(); per.ww = b->bank->dev.ww; per.rms_level = b->bank->rms_level; per.W = b->bank->dev.W;
-            per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;   // fixed_rms_level, gain_normalizer_filter.rs:56-66
-        }
+        if (b->mixed) per = b->mixed_per;
+        else if (b->prep_gain) { if (!stream_targets(b, &per)) return false; }
+        else if (b->per_stream_gain) { per.stream_wakeword = b->bank_idx.as<int32_t>(); per.ww = b->bank->dev.ww; per.rms_level = b->bank->rms_level; per.W = b->bank->dev.W; }
+        per.has_fixed_ref = g.has_gain_ref ? 1 : 0; per.fixed_ref = g.gain_ref;   // fixed_rms_level, gain_normalizer_filter.rs:56-66
         if (!hip_ok(launch_stream_filters(c->stream, in.p, in.fmt, in.channels, S, n_chunks, in.stride, hp_old, b->last_off, hp, pcm_pitch,
                                           g.enabled ? 1 : 0, b->rms_level_ref, g.min_gain, g.max_gain, b->gain_window,
                                           b->filt.band_pass.enabled ? 1 : 0, b->bq[0], b->bq[1], b->bq[2], b->bq[3], b->bq[4],
@@ -423,9 +418,11 @@ static bool live_scan(rp_stream_batch *b, const float *frames, size_t n_new, con
     });
 }
 
-// A batch over a bank: every stream's n_new new windows against its own wakeword -> bank_agg / bank_avg.  band_size 0: no cell lies in the
-// band and every score is 0 (dtw.rs:64-75); an empty bank: no stream has a wakeword -- zero rows either way, as rp_batch_detect_bank.
-static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new, bool detect_only) {
+// A batch over a wakeword bank, or the reference side of a batch over mixed sets: every stream's n_new new windows against its own wakeword,
+// or every slot of its set, -> bank_agg / bank_avg.  table: the per-stream table of a mixed batch, whose windows are Lmax(s) frames with the
+// COMBINED Lmax(s); null: the bank's own.  band_size 0: no cell lies in the band and every score is 0 (dtw.rs:64-75); an empty bank: no
+// stream has a wakeword -- zero rows either way, as rp_batch_detect_bank.
+static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new, bool detect_only, const BankWakeword *table) {
     Ctx *c = b->c;
     const BankDev &bd = b->bank->dev;
     const size_t bytes = b->S * b->slots() * n_new * sizeof(float);
@@ -438,6 +435,10 @@ static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_n
     q.avg_threshold = b->cfg.avg_threshold; q.agg = b->bank_agg.as<float>(); q.avg = b->bank_avg.as<float>();
     const DtwWork wk = c->dtw_work();
     q.fix = wk.fix;
+    if (table) {
+        dtw_mark(wk, kDtwRanMixedSetsStream);
+        return timed(c, kKernelDtw, "dtw_mixed_stream_kernel", [&] { return launch_dtw_set_stream(c->stream, bd, q, b->set_size, table, b->max_len); });
+    }
     if (b->set_size) {   // every slot of every stream's set is a row
         dtw_mark(wk, kDtwRanBankSetsStream);
         return timed(c, kKernelDtw, "dtw_set_stream_kernel", [&] { return launch_dtw_set_stream(c->stream, bd, q, b->set_size); });
@@ -446,76 +447,44 @@ static bool score_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_n
     return timed(c, kKernelDtw, "dtw_bank_stream_kernel", [&] { return launch_dtw_bank_stream(c->stream, bd, q); });
 }
 
-// A batch over a model bank: the logits of every stream's n_new new windows with its own model (one forward launch, inside the context's
-// kKernelMlp bracket), then their scores and labels -> bank_agg / bank_avg / bank_label.  An empty bank: no stream has a model, nothing runs
-// and the scan reports nothing.
-static bool score_model_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new) {
+// A batch over a model bank, or the model side of a batch over mixed sets: the logits of every stream's n_new new windows with its own model,
+// or every slot of its set (one forward launch, inside the context's kKernelMlp bracket), then their scores and labels -> agg / avg /
+// bank_label.  idx, set_size (0: one model per stream): the side's rows; table as for score_bank_stream.  An empty bank: no stream has a
+// model, nothing runs and the scan reports nothing.
+static bool score_model_bank_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new, const int32_t *idx, int set_size, float *agg, float *avg,
+                                    const BankWakeword *table) {
     Ctx *c = b->c;
     const ModelBank &bk = *b->mbank;
     b->logit_frames = n_new;
     // no model yet (a reserved empty bank): rp_stream_batch_logits answers zero rows
     if (bk.dev.W == 0)
-        return !b->label_pitch || hip_ok(hipMemsetAsync(b->logits.p, 0, b->S * b->slots() * n_new * (size_t)b->label_pitch * sizeof(float), c->stream), "hipMemsetAsync");
+        return !b->label_pitch || hip_ok(hipMemsetAsync(b->logits.p, 0, b->S * (size_t)std::max(set_size, 1) * n_new * (size_t)b->label_pitch * sizeof(float), c->stream), "hipMemsetAsync");
     if (bk.dev.label_pitch != b->label_pitch || bk.max_L > b->max_len) { set_last_error("stream batch: the model bank outgrew what the batch was sized for"); return false; }
-    const int32_t *idx = b->bank_idx.as<int32_t>();
     float *mean = b->mean.as<float>(), *dlog = b->logits.as<float>();
-    if (b->set_size) {   // every slot of every stream's set is a row; Lmax(s) is read from the bank in this call
-        if (!hip_ok(launch_window_means_set_stream(c->stream, bk.dev, bk.max_L, idx, b->set_size, f.rows, b->S, b->cap, f.fill, n_new, mean),
-                    "window_means_set_stream_kernel")) return false;
-        if (!timed(c, kKernelMlp, "mlp_set_stream_kernel", [&] {
-                return launch_mlp_set_stream(c->stream, bk.dev, bk.max_L, idx, b->set_size, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); })) return false;
-        return hip_ok(launch_nn_score_set_stream(c->stream, bk.dev, idx, b->set_size, dlog, b->S, n_new, b->cfg.score_ref * 10.f,
-                                                 b->cfg.avg_threshold != 0.f ? 1 : 0, b->cfg.threshold, b->cfg.avg_threshold, b->bank_agg.as<float>(),
-                                                 b->bank_avg.as<float>(), b->bank_label.as<int32_t>()), "nn_score_set_stream_kernel");
+    const float ref10 = b->cfg.score_ref * 10.f;
+    const int calc_avg = b->cfg.avg_threshold != 0.f ? 1 : 0;
+    if (set_size) {   // every slot of every stream's set is a row; Lmax(s) is read from the bank, or from the table, in this call
+        if (table) {
+            if (!hip_ok(launch_window_means_mixed_stream(c->stream, bk.dev, bk.max_L, b->max_len, idx, set_size, table, f.rows, b->S, b->cap, f.fill, n_new, mean),
+                        "window_means_mixed_stream_kernel")) return false;
+            if (!timed(c, kKernelMlp, "mlp_mixed_stream_kernel", [&] {
+                    return launch_mlp_mixed_stream(c->stream, bk.dev, bk.max_L, b->max_len, idx, set_size, table, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); }))
+                return false;
+        } else {
+            if (!hip_ok(launch_window_means_set_stream(c->stream, bk.dev, bk.max_L, idx, set_size, f.rows, b->S, b->cap, f.fill, n_new, mean),
+                        "window_means_set_stream_kernel")) return false;
+            if (!timed(c, kKernelMlp, "mlp_set_stream_kernel", [&] {
+                    return launch_mlp_set_stream(c->stream, bk.dev, bk.max_L, idx, set_size, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); })) return false;
+        }
+        return hip_ok(launch_nn_score_set_stream(c->stream, bk.dev, idx, set_size, dlog, b->S, n_new, ref10, calc_avg, b->cfg.threshold, b->cfg.avg_threshold,
+                                                 agg, avg, b->bank_label.as<int32_t>()), "nn_score_set_stream_kernel");
     }
     if (!hip_ok(launch_window_means_bank_stream(c->stream, bk.dev, bk.max_L, idx, f.rows, b->S, b->cap, f.fill, n_new, mean), "window_means_bank_stream_kernel"))
         return false;
     if (!timed(c, kKernelMlp, "mlp_bank_stream_kernel", [&] {
             return launch_mlp_bank_stream(c->stream, bk.dev, bk.max_L, idx, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); })) return false;
-    return hip_ok(launch_nn_score_bank_stream(c->stream, bk.dev, idx, dlog, b->S, n_new, b->cfg.score_ref * 10.f, b->cfg.avg_threshold != 0.f ? 1 : 0,
-                                              b->cfg.threshold, b->cfg.avg_threshold, b->bank_agg.as<float>(), b->bank_avg.as<float>(),
+    return hip_ok(launch_nn_score_bank_stream(c->stream, bk.dev, idx, dlog, b->S, n_new, ref10, calc_avg, b->cfg.threshold, b->cfg.avg_threshold, agg, avg,
                                               b->bank_label.as<int32_t>()), "nn_score_bank_stream_kernel");
-}
-
-// A batch over mixed sets: the reference slots' scores -> bank_agg / bank_avg (dtw_mixed_stream_kernel) and the model slots' logits, scores and
-// labels -> logits, m_agg / m_avg / bank_label (one forward launch), every window Lmax(s) frames long with the combined Lmax(s) of this call's
-// table.  band_size 0 and an empty wakeword bank: zero reference rows; an empty model bank: zero logits, and the scan reads no model row.
-static bool score_mixed_stream(rp_stream_batch *b, const NewFrames &f, size_t n_new, bool detect_only) {
-    Ctx *c = b->c;
-    const Bank &bk = *b->bank;
-    const ModelBank &mb = *b->mbank;
-    const BankWakeword *table = b->mixed_per.ww;
-    b->slot_frames = b->logit_frames = n_new;
-    if (b->set_size) {
-        const size_t bytes = b->S * (size_t)b->set_size * n_new * sizeof(float);
-        if (b->cfg.band_size == 0 || bk.dev.W == 0) {
-            if (!hip_ok(hipMemsetAsync(b->bank_agg.p, 0, bytes, c->stream), "hipMemsetAsync") || !hip_ok(hipMemsetAsync(b->bank_avg.p, 0, bytes, c->stream), "hipMemsetAsync"))
-                return false;
-        } else {
-            BankStreamScore q;
-            q.mfcc = f.rows; q.S = b->S; q.frame_pitch = b->cap; q.first_new = f.fill; q.n_new = n_new; q.stream_wakeword = b->bank_idx.as<int32_t>();
-            q.band = (int)b->cfg.band_size; q.score_mode = (int)b->cfg.score_mode; q.score_ref = b->cfg.score_ref; q.gate = detect_only ? 1 : 0;
-            q.avg_threshold = b->cfg.avg_threshold; q.agg = b->bank_agg.as<float>(); q.avg = b->bank_avg.as<float>();
-            const DtwWork wk = c->dtw_work();
-            q.fix = wk.fix;
-            dtw_mark(wk, kDtwRanMixedSetsStream);
-            if (!timed(c, kKernelDtw, "dtw_mixed_stream_kernel", [&] { return launch_dtw_mixed_stream(c->stream, bk.dev, q, b->set_size, table, b->max_len); }))
-                return false;
-        }
-    }
-    if (!b->mset_size) return true;
-    const int32_t *idx = b->model_idx.as<int32_t>();
-    float *mean = b->mean.as<float>(), *dlog = b->logits.as<float>();
-    if (mb.dev.W == 0)   // no model yet: rp_stream_batch_logits answers zero rows
-        return !b->label_pitch || hip_ok(hipMemsetAsync(b->logits.p, 0, b->S * (size_t)b->mset_size * n_new * (size_t)b->label_pitch * sizeof(float), c->stream), "hipMemsetAsync");
-    if (!hip_ok(launch_window_means_mixed_stream(c->stream, mb.dev, mb.max_L, b->max_len, idx, b->mset_size, table, f.rows, b->S, b->cap, f.fill, n_new, mean),
-                "window_means_mixed_stream_kernel")) return false;
-    if (!timed(c, kKernelMlp, "mlp_mixed_stream_kernel", [&] {
-            return launch_mlp_mixed_stream(c->stream, mb.dev, mb.max_L, b->max_len, idx, b->mset_size, table, f.rows, b->S, b->cap, f.fill, n_new, mean, dlog); }))
-        return false;
-    return hip_ok(launch_nn_score_set_stream(c->stream, mb.dev, idx, b->mset_size, dlog, b->S, n_new, b->cfg.score_ref * 10.f, b->cfg.avg_threshold != 0.f ? 1 : 0,
-                                             b->cfg.threshold, b->cfg.avg_threshold, b->m_agg.as<float>(), b->m_avg.as<float>(), b->bank_label.as<int32_t>()),
-                  "nn_score_set_stream_kernel");
 }
 
 // Score + scan stage: scores of this call's n_new windows per stream for every wakeword, then the state machine over all of them.
@@ -524,9 +493,15 @@ static bool stream_score_and_scan(rp_stream_batch *b, Staged &sg, const NewFrame
                                   int32_t *dn, int max_det, int32_t *det_wakeword, int32_t *det_label) {
     ScanWakewords sw{};
     sw.n = (int)b->ww.size();
-    if (b->mixed) { if (!score_mixed_stream(b, f, n_new, detect_only)) return false; }
-    else if (b->bank && !score_bank_stream(b, f, n_new, detect_only)) return false;
-    else if (b->mbank && !score_model_bank_stream(b, f, n_new)) return false;
+    if (b->mixed) {   // each side that has rows; every window Lmax(s) frames long with the combined Lmax(s) of this call's table
+        const BankWakeword *table = b->mixed_per.ww;
+        b->slot_frames = b->logit_frames = n_new;
+        if (b->set_size && !score_bank_stream(b, f, n_new, detect_only, table)) return false;
+        if (b->mset_size && !score_model_bank_stream(b, f, n_new, b->model_idx.as<int32_t>(), b->mset_size, b->m_agg.as<float>(), b->m_avg.as<float>(), table))
+            return false;
+    } else if (b->bank && !score_bank_stream(b, f, n_new, detect_only, nullptr)) return false;
+    else if (b->mbank && !score_model_bank_stream(b, f, n_new, b->bank_idx.as<int32_t>(), b->set_size, b->bank_agg.as<float>(), b->bank_avg.as<float>(), nullptr))
+        return false;
     for (size_t j = 0; j < b->ww.size(); ++j)
         if (!(b->ww[j]->t ? score_reference(b, *b->ww[j], f, n_new, detect_only, sw, j) : score_model(b, *b->ww[j], f, n_new, sw, j))) return false;
     const size_t col = b->S * (size_t)max_det * sizeof(int32_t);
@@ -1016,24 +991,17 @@ int rp_stream_batch_slot_scores(rp_stream_batch *b, float *agg, float *avg) {
     return guarded([&]() -> int {
         Ctx *c = stream_batch_enter(b, true);
         if (!c) return -1;
-        if (b->mixed) {   // the reference slots' rows; the model slots' per-window output is rp_stream_batch_logits
-            if (!b->slot_frames) { set_last_error("rp_stream_batch_slot_scores: the streams have not received audio yet"); return -1; }
-            const size_t bytes = b->S * (size_t)b->set_size * b->slot_frames * sizeof(float);
-            const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
-            const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-            if (bytes && agg && !hip_ok(hipMemcpyAsync(agg, b->bank_agg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
-            if (bytes && avg && !hip_ok(hipMemcpyAsync(avg, b->bank_avg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
-            return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
+        if (!b->mixed) {   // (a batch over mixed sets: the reference slots' rows; the model slots' per-window output is rp_stream_batch_logits)
+            if (b->mbank && b->set_size) { set_last_error("rp_stream_batch_slot_scores: a batch over model sets keeps no aggregate per slot; rp_stream_batch_logits returns its per-slot, per-window output"); return -1; }
+            if (b->mbank) { set_last_error("rp_stream_batch_slot_scores: a batch over a model bank has one model per stream and no slots; rp_stream_batch_logits returns its per-window output"); return -1; }
+            if (!b->set_size) { set_last_error("rp_stream_batch_slot_scores: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
         }
-        if (b->mbank && b->set_size) { set_last_error("rp_stream_batch_slot_scores: a batch over model sets keeps no aggregate per slot; rp_stream_batch_logits returns its per-slot, per-window output"); return -1; }
-        if (b->mbank) { set_last_error("rp_stream_batch_slot_scores: a batch over a model bank has one model per stream and no slots; rp_stream_batch_logits returns its per-window output"); return -1; }
-        if (!b->set_size) { set_last_error("rp_stream_batch_slot_scores: the batch was not made by rp_stream_batch_new_bank_sets"); return -1; }
         if (!b->slot_frames) { set_last_error("rp_stream_batch_slot_scores: the streams have not received audio yet"); return -1; }
-        const size_t bytes = b->S * (size_t)b->set_size * b->slot_frames * sizeof(float);
+        const size_t bytes = b->S * (size_t)b->set_size * b->slot_frames * sizeof(float);   // 0: a mixed batch without a reference side
         const bool host = (c->flags & RP_CTX_HOST_POINTERS) != 0;
         const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (agg && !hip_ok(hipMemcpyAsync(agg, b->bank_agg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
-        if (avg && !hip_ok(hipMemcpyAsync(avg, b->bank_avg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
+        if (bytes && agg && !hip_ok(hipMemcpyAsync(agg, b->bank_agg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
+        if (bytes && avg && !hip_ok(hipMemcpyAsync(avg, b->bank_avg.p, bytes, kind, c->stream), "hipMemcpyAsync")) return -1;
         return !host || hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize") ? 0 : -1;
     });
 }

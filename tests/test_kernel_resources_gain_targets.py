@@ -1,5 +1,5 @@
-"""gain_targets_kernel (rustpotter_amd/csrc/rp_gain_targets.hip), the preparation kernel in front of the per-stream gain kernels: nothing
-spilled and no scratch memory -- a lane folds at most eight indices into a length and a level.  Reads the compiler's own resource remarks
+"""stream_targets_kernel (rustpotter_amd/csrc/rp_gain_targets.hip), the preparation kernel in front of the per-stream gain kernels: nothing
+spilled and no scratch memory -- a lane folds at most two rows of eight indices into a length and a level.  Reads the compiler's own resource remarks
 (tools/kernel_regs.py compiles with the Makefile's flags; CPU only, hipcc cross-compiles), as tests/test_kernel_resources_bank_put.py does."""
 import os
 import re
@@ -10,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = "rp_gain_targets.hip"
-KERNELS = ["gain_targets_kernel"]
+KERNELS = ["stream_targets_kernel"]
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-"""The kernels of model sets (rustpotter_amd/csrc/rp_mlp_model_set.hip and rp_scan_model_set.hip): every instantiation is listed, spills
+"""The kernels of model sets (rustpotter_amd/csrc/rp_mlp_model_set.hip, and their scan kernels in rp_scan_sets.hip): every instantiation is listed, spills
 nothing, uses no scratch memory and keeps the waves per SIMD the file header states -- mlp_set_stream_kernel<1> three (at most 168
 registers), <2> two, mlp_windows_model_set_kernel<1 .. 7> two (two workgroups of 256 threads per CU, as mlp_windows_bank_kernel, whose
 body it shares).  The register counts of the build the kernels were written with are caps.  Reads the compiler's own resource remarks
@@ -21,7 +21,7 @@ KERNELS = {
     "mlp_windows_model_set_kernel<7>": ("rp_mlp_model_set.hip", 202, 2),
     "window_means_model_set_kernel": ("rp_mlp_model_set.hip", 40, 2), "window_means_set_stream_kernel": ("rp_mlp_model_set.hip", 40, 2),
     "nn_score_model_set_kernel": ("rp_mlp_model_set.hip", 28, 2), "nn_score_set_stream_kernel": ("rp_mlp_model_set.hip", 15, 2),
-    "scan_model_set_kernel": ("rp_scan_model_set.hip", 91, 1), "scan_model_set_stream_kernel": ("rp_scan_model_set.hip", 142, 1),
+    "scan_model_set_kernel": ("rp_scan_sets.hip", 91, 1), "scan_model_set_stream_kernel": ("rp_scan_sets.hip", 142, 1),
 }
 
 
@@ -40,8 +40,14 @@ def remarks():
 
 def test_every_instantiation_is_listed(remarks):
     """both row-tile builds of the live forward, one build per tile count of the whole-recording forward, and every other kernel of the
-    two sources; no name contains mlp_bank_stream_kernel or mlp_windows_bank_kernel, whose own tests list their instantiations"""
-    assert sorted(remarks) == sorted(KERNELS)
+    two sources -- rp_scan_sets.hip also holds the scan kernels of wakeword sets and mixed sets, listed in the tests of their families; no
+    name contains mlp_bank_stream_kernel or mlp_windows_bank_kernel, whose own tests list their instantiations"""
+    import test_kernel_resources_mixed as mixed
+    import test_kernel_resources_sets as sets
+    sources = {k[0] for k in KERNELS.values()}
+    elsewhere = {k for t in (mixed, sets) for k, v in t.KERNELS.items() if v[0] in sources}
+    assert not elsewhere & set(KERNELS)
+    assert sorted(remarks) == sorted(set(KERNELS) | elsewhere)
     assert not [k for k in remarks if "mlp_bank_stream_kernel" in k or "mlp_windows_bank_kernel" in k]
 
 

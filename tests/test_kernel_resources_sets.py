@@ -1,4 +1,4 @@
-"""The wakeword-set kernels (rustpotter_amd/csrc/rp_dtw_set.hip, rp_scan_set.hip): nothing spilled and no scratch memory.  dtw_set_kernel and
+"""The wakeword-set kernels (rustpotter_amd/csrc/rp_dtw_set.hip, rp_scan_sets.hip): nothing spilled and no scratch memory.  dtw_set_kernel and
 dtw_set_stream_kernel run the DTW walks of the bank kernels (rp_dtw_bank.h) inside a loop over the slots of a set / over rows of slots; a
 ring or band the compiler leaves rolled becomes a run-time index and the array goes to scratch memory, and scan_set_stream_kernel keeps the
 slots of a set in registers behind fully unrolled loops -- exactly these counters show when either fails.  The register counts the build
@@ -26,7 +26,7 @@ KERNELS = {
     "dtw_set_stream_kernel<13, 5>": ("rp_dtw_set.hip", 216), "dtw_set_stream_kernel<13, 6>": ("rp_dtw_set.hip", 244),
     "dtw_set_stream_kernel<16, 3>": ("rp_dtw_set.hip", 174), "dtw_set_stream_kernel<16, 4>": ("rp_dtw_set.hip", 216),
     "dtw_set_stream_kernel<16, 5>": ("rp_dtw_set.hip", 250), "dtw_set_stream_kernel<16, 6>": ("rp_dtw_set.hip", 270),
-    "scan_set_kernel": ("rp_scan_set.hip", 85), "scan_set_stream_kernel": ("rp_scan_set.hip", 143),
+    "scan_set_kernel": ("rp_scan_sets.hip", 85), "scan_set_stream_kernel": ("rp_scan_sets.hip", 143),
 }
 
 
@@ -44,8 +44,14 @@ def remarks():
 
 
 def test_every_instantiation_is_listed(remarks):
-    """a new (mfcc_size, band) pair of a kernel, or a new kernel in these sources, comes with its line above"""
-    assert sorted(remarks) == sorted(KERNELS)
+    """a new (mfcc_size, band) pair of a kernel, or a new kernel in these sources, comes with its line above, or -- the two sources also hold
+    the kernels of model sets and mixed sets -- with its line in the test of its own family"""
+    import test_kernel_resources_mixed as mixed
+    import test_kernel_resources_model_set as model_sets
+    sources = {s for s, _ in KERNELS.values()}
+    elsewhere = {k for t in (mixed, model_sets) for k, v in t.KERNELS.items() if v[0] in sources}
+    assert not elsewhere & set(KERNELS)
+    assert sorted(remarks) == sorted(set(KERNELS) | elsewhere)
 
 
 @pytest.mark.parametrize("kernel", sorted(KERNELS))

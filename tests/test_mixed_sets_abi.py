@@ -57,12 +57,16 @@ def test_the_constant_of_the_live_dtw_kernel():
 
 
 def test_the_kernels_are_new_sources_and_the_old_ones_are_where_they_were():
-    """the existing resource tests list every kernel of the sets' sources exactly: the mixed kernels live in files of their own"""
+    """the resource tests list every kernel of these sources exactly.  Since the live-lane fold the mixed kernels sit beside their set twins
+    (one targets kernel, one source for the set scans, the live DTW front next to dtw_set_stream_kernel); the two live forward fronts keep
+    their own source, and the whole-recording and model-set sources hold nothing of mixed sets"""
     mk = read("rustpotter_amd", "csrc", "Makefile")
-    for src, kernel in (("rp_mixed_targets.hip", "mixed_targets_kernel"), ("rp_scan_mixed.hip", "scan_mixed_set_kernel"),
-                        ("rp_scan_mixed.hip", "scan_mixed_set_stream_kernel"), ("rp_dtw_mixed.hip", "dtw_mixed_stream_kernel"),
+    for src, kernel in (("rp_gain_targets.hip", "stream_targets_kernel"), ("rp_scan_sets.hip", "scan_mixed_set_kernel"),
+                        ("rp_scan_sets.hip", "scan_mixed_set_stream_kernel"), ("rp_dtw_set.hip", "dtw_mixed_stream_kernel"),
                         ("rp_mlp_mixed.hip", "window_means_mixed_stream_kernel"), ("rp_mlp_mixed.hip", "mlp_mixed_stream_kernel")):
         assert src in mk, src
         assert kernel in read("rustpotter_amd", "csrc", src)
-    for src in ("rp_scan_set.hip", "rp_scan_model_set.hip", "rp_gain_targets.hip", "rp_dtw_set.hip", "rp_mlp_model_set.hip"):
+    for gone in ("rp_mixed_targets.hip", "rp_scan_mixed.hip", "rp_dtw_mixed.hip", "rp_scan_set.hip", "rp_scan_model_set.hip"):
+        assert gone not in mk and not os.path.exists(os.path.join(ROOT, "rustpotter_amd", "csrc", gone)), gone
+    for src in ("rp_dtw_bank.hip", "rp_mlp_model_set.hip"):
         assert "mixed" not in read("rustpotter_amd", "csrc", src), src

@@ -48,7 +48,7 @@ def test_the_preparation_kernel_is_built_and_the_gain_kernels_are_where_they_wer
     mk = read("rustpotter_amd", "csrc", "Makefile")
     assert "rp_gain_targets.hip" in mk
     src = read("rustpotter_amd", "csrc", "rp_gain_targets.hip")
-    assert "gain_targets_kernel" in src and "__launch_bounds__(64)" in src
+    assert "stream_targets_kernel" in src and "__launch_bounds__(64)" in src
     fe = read("rustpotter_amd", "csrc", "rp_frontend.hip")
     for name in ("gain_per_stream_kernel", "lane_gain", "stream_filters_kernel"):
         assert name in fe and name not in src, name   # the existing per-stream kernels stay in rp_frontend.hip; the new file has none of them

@@ -1,5 +1,5 @@
 """What the gain normaliser costs the live-stream batches whose streams hold a SET of bank entries or a model
-(rp_stream_batch_set_filters_per_stream: gain_targets_kernel folds every stream's row into a level and a window at the start of each call,
+(rp_stream_batch_set_filters_per_stream: stream_targets_kernel folds every stream's row into a level and a window at the start of each call,
 then the per-stream form of stream_filters_kernel): a wakeword-sets batch, a model-bank batch and a model-sets batch with gain normaliser +
 band-pass, each against the SAME batch with the band-pass alone (rp_stream_batch_set_filters), the path that existed before.
 S streams fed `chunks` 30 ms chunks of i16 noise per call from the device (every stream at its own loudness, so the gains are not all
