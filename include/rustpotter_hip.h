@@ -835,6 +835,10 @@ int rp_mlp_forward_batch(rp_ctx *ctx, const rp_model *model, const float *x, siz
  * n_win = n_frames - train_size + 1 (0 rows when a stream is shorter than a window).  The windows are never materialised: a
  * stream's frames are staged once and the window mean is taken out after layer 1 (W.(f - mu) = W.f - sum_k mu[k] wsum[k]);
  * RP_MLP_BF16 is accepted and computes as RP_MLP_F32 here (bf16 is an INPUT format of rp_mlp_forward_batch's dense rows).
+ * From 32 windows on (mfcc_size 16) a workgroup stages its share of a stream -- at most 224 consecutive windows -- minus the mean of its
+ * middle window: a frame far outside the others' range inside that window leaves the workgroup's OTHER windows right to 1e-5 of
+ * |their mean - that mean| (about the frame's value / train_size), not of their own features.  The windows that hold the frame, the
+ * stream's other workgroups and the other streams are not affected.
  * rp_batch_detect_model is this call between rp_mfcc_batch and the score / detection passes. */
 int rp_mlp_forward_windows(rp_ctx *ctx, const rp_model *model, const float *mfcc, size_t S, size_t n_frames, int mfcc_size,
                            int precision, float *logits);

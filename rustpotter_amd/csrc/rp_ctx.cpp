@@ -801,7 +801,7 @@ Model *Model::create(Ctx *ctx, int n_layers, const int *dims, const float *const
         if (tail.empty()) tail.push_back(0.f);
         d.tail_floats = (int)tail.size();
         if (!mlp_mfma_fits(d)) { m->mfma_ok = false; d.nt = 0; return m.release(); }   // e.g. a 255-wide hidden layer: per-layer kernel
-        if (dims[0] % 16 == 0 && n1 <= 160) {   // mlp_windows_kernel / mlp_windows_wide_kernel (mfcc_size 16): [frame][32-output tile q][part][k-half][output][8 k]
+        if (dims[0] % 16 == 0 && n1 <= 144) {   // (144: what d.nt above allows) mlp_windows_kernel / mlp_windows_wide_kernel (mfcc_size 16): [frame][32-output tile q][part][k-half][output][8 k]
             const int Lw = dims[0] / 16, NQ = (n1 + 31) / 32;
             std::vector<uint16_t> img((size_t)Lw * NQ * 2 * 2 * 32 * 8, 0);
             for (int f = 0; f < Lw; ++f)

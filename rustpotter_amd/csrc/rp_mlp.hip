@@ -649,10 +649,14 @@ static MlpRoute mlp_route(Model &md, const MlpForward &q) {
     r.redo = r.prec == kMlpF16x2;
     if (q.windows) {
         // whole streams (or long runs of windows): the staged-frame kernels, the frames staged once per workgroup -- mfcc_size 16, layer 1
-        // <= 32 (mlp_windows_kernel) or <= 160 (mlp_windows_wide_kernel) wide, the tail layers <= 32
+        // <= 32 (mlp_windows_kernel) or <= 144 (mlp_windows_wide_kernel, five output tiles; Model::create has no matrix-core form beyond
+        // 144, md.mfma_ok above) wide, the tail layers <= 32, windows of 2 .. 256 frames.  A window of ONE frame is its own mean: every
+        // normalised feature is exactly 0, and only mlp_mfma_kernel, which subtracts the row's own mean as it loads, keeps that; staged about
+        // another window's mean, W.(f - c) and the correction (mu - c).wsum are two roundings of one quantity, and what they leave is
+        // measured against logits that carry no feature at all (2.2 x the 1e-5 gate, tests/test_gpu_mlp_windows_builds.py)
         int form = 0;
-        if (r.prec != kMlpF32 && (r.prec == kMlpBf16x3 ? m.wwin3 : m.wwin) && q.K == 16 && m.dims[0] % 16 == 0 && m.dims[1] <= 160 &&
-            q.n_win >= 32 && m.dims[0] / 16 <= 256 && m.tail_floats <= 6144) {
+        if (r.prec != kMlpF32 && (r.prec == kMlpBf16x3 ? m.wwin3 : m.wwin) && q.K == 16 && m.dims[0] % 16 == 0 && m.dims[1] <= 144 &&
+            q.n_win >= 32 && m.dims[0] / 16 >= 2 && m.dims[0] / 16 <= 256 && m.tail_floats <= 6144) {
             form = m.dims[1] <= 32 ? 1 : 2;
             for (int l2 = 2; l2 <= m.n_layers; ++l2) if (m.dims[l2] > 32) form = 0;
             if (const char *env = std::getenv("RP_MLP_WINDOWS")) if (env[0] == '0') form = 0;

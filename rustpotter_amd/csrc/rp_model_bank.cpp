@@ -55,7 +55,8 @@ Model *model_from_data(Ctx *ctx, const WakewordModelData &model, int *n_layers, 
 }
 
 // The bank's limits are the shapes mlp_route sends to mlp_windows_kernel: mfcc_size 16, windows of at most 256 frames, layer 1 and the tail
-// layers at most 32 wide, a packed tail of at most 6144 floats.  Every refusal names its limit.
+// layers at most 32 wide, a packed tail of at most 6144 floats.  Every refusal names its limit.  (mlp_route itself keeps windows of ONE
+// frame, which the bank accepts, with mlp_mfma_kernel: rp_mlp.hip.)
 bool ModelBank::entry_of(const std::vector<int> &dims, int ni, int image_ok, ModelBankEntry *out, std::string *why) {
     const int nl = (int)dims.size() - 1;
     auto fail = [&](const std::string &w) { *why = w; return false; };

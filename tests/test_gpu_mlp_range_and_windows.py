@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import mlp_windows_cases
 from oracle import rp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -134,7 +135,8 @@ def _window_model(rng, L, K, hidden, labels):
     (195, (130, 32), 3, 430, 2),    # Large: five tiles; 236 windows = two workgroups of four row tiles per stream
     (60, (40, 20), 2, 100, 3),      # two output tiles, 41 windows = the two-row-tile form
     (100, (97,), 4, 200, 1),        # four output tiles, no hidden tail layer
-    (30, (160,), 160, 70, 1),       # 160 outputs of a single layer written straight from the tiles
+    (30, (160,), 160, 70, 1),       # 160 outputs of a single layer: beyond 144 Model::create has no matrix-core form, the per-layer kernel runs
+    (30, (), 144, 70, 1),           # 144 outputs of a single layer written straight from five output tiles (mlp_windows_wide_kernel, NQ 5)
 ])
 def test_window_logits_match_the_oracle(ra, ctx, L, hidden, labels, nf, S):
     """rp_mlp_forward_windows against the oracle's window-by-window forward (normalise, flatten, ModelImpl::forward): features on
@@ -150,7 +152,11 @@ def test_window_logits_match_the_oracle(ra, ctx, L, hidden, labels, nf, S):
     off = rng.uniform(-30.0, 30.0, K).astype(np.float32)
     drift = np.linspace(0.0, 1.0, nf)[None, :, None] * rng.uniform(-6.0, 6.0, (S, 1, K))
     mfcc = (rng.standard_normal((S, nf, K)) * rng.uniform(0.5, 2.0, (S, 1, 1)) + off + drift).astype(np.float32)
+    before = ctx.last_mlp_kernel()
     got = ctx.mlp_forward_windows(mfcc, model)
+    # the kernel the case is about did run (the route restated in tests/mlp_windows_cases.py; the per-layer kernel leaves the name as it was)
+    want = mlp_windows_cases.route([L * K] + list(hidden) + [labels], K, nf - L + 1, "f32")[0]
+    assert ctx.last_mlp_kernel() == (before if want is None else want)
     ref = _window_logits_oracle(mfcc, L, ws, bs).astype(np.float64)
     assert got.shape == ref.shape and np.isfinite(got).all()
     # the gate scales with the CENTRED features (what the model sees), not with the offsets they sit on
